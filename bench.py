@@ -2,18 +2,25 @@
 """Benchmark of the LQER quantized-Linear hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c4row|c5|c4a16|c2int|c2introw|c3int|c2w8a8|c2w8a8m8k|d1|d16|d1a16|d1layer]
-                    [--sweep auto|weak|strong] [--shard none|n] [--no-configs] [--no-cpu-baseline] [--no-check] [--no-module]
-                    [--graph G] [--prewarm-ms T] [--dry-run-cpu]
+                    [--sweep auto|weak|strong] [--shard none|n] [--graph G] [--prewarm-ms T] [--dump-outputs DIR] [--dry-run-cpu]
+                    [--full [--no-configs] [--no-cpu-baseline] [--no-check] [--no-module] [--no-two-streams]]
+
+A plain run does only what the headline needs: setup, the device clock ramp, the W warm-up steps, the K timed steps, the
+outputs of the last timed step if --dump-outputs is given, and the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's configuration).  Every other figure and check described below - the `configs` of the default line,
+the roofline and sustained clock, the CPU baseline, the module / uninstrumented / two-stream / shared-input / group / resident
+regions, `replicas_c2`, and the oracle parity of the timed outputs - runs only with --full.
 
 A step = one pass of the hot path (x fp16 in -> activation quantize -> rank-r side GEMM -> fused W4A8 GEMM -> y fp16
 out) over one batch of synthetic tokens for every Linear unit this rank owns, inputs resident in HBM.  Default
 workload = BASELINE.json configs[1]: one LqerLinear 4096 -> 4096, rank 32, W4A8 MXINT (block 16), M = 2048 tokens.
-On the default line (one GPU, workload c2) the JSON also carries `configs`: every other BASELINE configuration at its full token
+On the default line (one GPU, workload c2) the --full JSON also carries `configs`: every other BASELINE configuration at its full token
 count - c3 (Llama-7B, all 32 layers x 7 projections), c3int (the same shapes with the reference's INT template: int8 MFMA), c4
 (Llama-13B W4A8-INT rank 64, M = 16384: 8 of its 40 layers), c5 (OPT-6.7B rank 128, all 32 layers x 6 projections) - each with its
 own packed images per Linear, timed region, per-shape dominant-kernel time / fraction of peak, the sustained shader clock and
 oracle parity, so that every BASELINE configuration is under the driver's clock.  With --gpus N > 1 and no --workload the
-headline is BASELINE's multi-GPU configuration (c4, layers split over the ranks) and `replicas_c2` the N independent C2 Linears.
+headline is BASELINE's multi-GPU configuration (c4, layers split over the ranks) and, with --full, `replicas_c2` the N
+independent C2 Linears.
 
 Multi-GPU (one rank per GPU).  Either the driver launches the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE in the environment), or a plain `python bench.py
@@ -32,12 +39,17 @@ are GATHERED after the timed region.  No collective on the data path.
     Linear column-parallel (optional row): rank g packs and runs W[n0:n1], B[:, n0:n1] - cuts at multiples
     of 16, exact with no reduction - and y[:, n0:n1] is all-gathered outside the timed region: "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (driver contract) with these extra objects: "roofline" (dominant kernel: algorithmic
+Prints ONE JSON line on rank 0 (driver contract); with --full it carries these extra objects: "roofline" (dominant kernel: algorithmic
 FLOPs / its HIP-event time inside the timed region, against the dense MFMA peak of the main loop's operand type),
 "cpu_baseline" (the CPU oracle timed on this box's host cores on a bounded sample), "module" (the same K steps timed
 through the drop-in nn.Module, `mod(x)` - the boundary the reference's callers use; `value` is the C-ABI figure),
 "uninstrumented" (the K steps once more without the roofline's event pairs) and "parity_rel_l2" (row slices of the
 outputs the timed kernels just wrote, against the CPU oracle).
+
+--dump-outputs DIR: right after the timed region, rank 0 writes what the last timed step computed - the y of every
+Linear unit it ran (DIR/y.npy for a single Linear, DIR/y_<K>x<N>.npy per projection shape of a model sweep, DIR/layer<i>_<proj>.npy
+for d1layer) - as float32, at most 64 MB in all: an output larger than its share keeps a fixed, seeded sample of its rows.
+The inputs come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 Timing: setup (packing, plans, broadcast), an untimed device clock ramp of --prewarm-ms (300 ms: after idling the GPU
 needs tens of milliseconds of load to reach the clocks it then holds, and the default C2 run is only ~5 ms long), the W
@@ -89,11 +101,18 @@ def parse_args(argv=None):
                     help="n: single-Linear workloads column-parallel - rank g owns the output columns [n0, n1) (cuts at multiples "
                          "of 16: exact, no reduction), y all-gathered outside the timed region")
     ap.add_argument("--layers", type=int, default=0, help="override the model's decoder layer count (profiling runs: --layers 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="every figure and check beside the headline: `configs`, roofline, sustained clock, CPU baseline, the module / "
+                         "uninstrumented / two-stream / shared-input / group / resident regions, `replicas_c2`, oracle parity (the --no-* "
+                         "options below trim it); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all: a fixed, seeded "
+                         "row sample of a larger output)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="default line only: skip the `configs` object (one decoder layer of c3 / c4 / c5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle comparison of the timed outputs")
-    ap.add_argument("--no-module", action="store_true", help="skip the second timed region through the nn.Module")
+                    help="--full, default line only: skip the `configs` object (one decoder layer of c3 / c4 / c5)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the oracle comparison of the timed outputs")
+    ap.add_argument("--no-module", action="store_true", help="--full: skip the second timed region through the nn.Module")
     ap.add_argument("--tuning", type=lambda v: int(v, 0), default=0,
                     help="lqer_linear_desc_t.tuning for every Linear (LQER_TUNE_* bits of include/lqer_hip.h: kernel-variant A/B, same bits), "
                          "e.g. 0x800000 = the block-16 activation side as two launches, 0x200000 = the int8 route's as three")
@@ -106,7 +125,7 @@ def parse_args(argv=None):
                          "weight stream comes from HBM and not from the 256 MB Infinity Cache (default 48 = 451 MB of 4096 x 4096 "
                          "images; 0 = one resident weight); the resident figure is reported beside it")
     ap.add_argument("--no-two-streams", action="store_true",
-                    help="skip the secondary figure with the step's independent forwards issued alternately on two HIP streams")
+                    help="--full: skip the secondary figure with the step's independent forwards issued alternately on two HIP streams")
     ap.add_argument("--shared-weights", action="store_true",
                     help="model sweeps: re-run ONE packed image per projection shape for every layer (the round-1/2 behaviour: "
                          "~60 MB of weights that never leave the Infinity Cache) instead of one distinct copy per Linear of the "
@@ -114,7 +133,24 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="no GPU, no kernel: the multi-rank host logic alone (launcher, partition, gloo broadcast / gather, "
                          "timed-region protocol, the JSON line) - value is null")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    for name in ("steps", "warmup"):
+        v = getattr(args, name)
+        if v is not None and v < (1 if name == "steps" else 0):
+            ap.error(f"--{name} {v}: at least {1 if name == 'steps' else 0}")
+    return args
+
+
+def run_opts(args):
+    """The Opts of the headline workload.  A plain run (no --full) times the headline alone: no secondary region, no oracle, no
+    CPU baseline, no roofline; --full runs them all but what the --no-* options leave out."""
+    from benchlib.runner import Opts
+
+    full = args.full
+    return Opts(workload=args.workload, steps=args.steps, warmup=args.warmup, layers=args.layers, sweep=args.sweep, shard=args.shard,
+                check=full and not args.no_check, module=full and not args.no_module, two_streams=full and not args.no_two_streams,
+                cpu_base=full and not args.no_cpu_baseline, prewarm_ms=args.prewarm_ms, graph=args.graph, rotate=args.rotate,
+                shared_weights=args.shared_weights, tuning=args.tuning, uninstrumented=full, full=full, dump=args.dump_outputs)
 
 
 def config_layers(ctx, args):
@@ -190,15 +226,12 @@ def main():
     from benchlib.runner import Ctx, Opts, run_workload
 
     ctx = Ctx(rank=rank, world=world, dev=dev, dist=dist)
-    opts = Opts(workload=args.workload, steps=args.steps, warmup=args.warmup, layers=args.layers, sweep=args.sweep, shard=args.shard,
-                check=not args.no_check, module=not args.no_module, two_streams=not args.no_two_streams,
-                cpu_base=not args.no_cpu_baseline, prewarm_ms=args.prewarm_ms, graph=args.graph, rotate=args.rotate,
-                shared_weights=args.shared_weights, tuning=args.tuning)
-    out = run_workload(ctx, opts)
-    default_line = (world == 1 and args.workload == "c2" and args.layers == 0 and args.shard == "none" and not args.graph
+    full = args.full
+    out = run_workload(ctx, run_opts(args))
+    default_line = (full and world == 1 and args.workload == "c2" and args.layers == 0 and args.shard == "none" and not args.graph
                     and not args.no_configs)
     replicas = None
-    if world > 1 and default_workload and args.shard == "none" and not args.graph:
+    if full and world > 1 and default_workload and args.shard == "none" and not args.graph:
         # every rank its own C2 Linear on the broadcast batch (N independent units): the weak-scaling figure next to the headline
         rep = run_workload(ctx, Opts(workload="c2", steps=None, warmup=None, check=not args.no_check, module=False, two_streams=False,
                                      cpu_base=False, prewarm_ms=100.0, uninstrumented=False))

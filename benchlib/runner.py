@@ -48,6 +48,31 @@ class Opts:
     shared_weights: bool = False
     uninstrumented: bool = True  # a second timed region without event pairs
     tuning: int = 0              # lqer_linear_desc_t.tuning of every module (LQER_TUNE_*: kernel-variant A/B on one box, same bits)
+    full: bool = True            # the figures beside the headline (roofline, sustained clock, group / resident regions); bench.py's
+                                 # plain run sets False together with check / module / two_streams / cpu_base / uninstrumented
+    dump: Optional[str] = None   # directory for the outputs of the last timed step (dump_outputs)
+
+
+# at most this many bytes of float32 outputs per --dump-outputs directory
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory, named):
+    """Write every (name, tensor) of `named` as directory/<name>.npy in float32, at most DUMP_BYTES in all: a 2-D output larger
+    than its equal share keeps a fixed, seeded sample of its rows (sorted; the same rows for the same shape in every run)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // max(len(named), 1)
+    for i, (name, t) in enumerate(named):
+        a = t.detach().float().cpu()
+        a = a.reshape(-1, a.shape[-1]) if a.dim() > 1 else a.reshape(1, -1)
+        if a.numel() * 4 > share:
+            keep = max(1, share // (a.shape[1] * 4))
+            rows = np.sort(np.random.default_rng(1000 + i).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+            a = a[torch.from_numpy(rows)]
+        np.save(os.path.join(directory, name + ".npy"), a.numpy().astype(np.float32))
+    print(f"# outputs of the last timed step: {len(named)} arrays -> {directory}", file=sys.stderr)
 
 
 def timed_region(ctx: Ctx, fn, steps):
@@ -348,7 +373,18 @@ def run_workload(ctx: Ctx, o: Opts) -> Optional[dict]:
                 step(True)
 
     elapsed_rank = timed_region(ctx, run_abi, steps)
-    if graph is not None:
+    if o.dump is not None:
+        # what the last timed step wrote, before any other region touches the output buffers (column shards: the all-gathered y)
+        named = []
+        for mod, xd, K, Nl, reps, y, wts, N in mods:
+            if shard_n:
+                y = sweep.all_gather_columns(y, col_ranges[N], N)
+            elif mod is None:
+                continue
+            named.append(("y" if len(shapes) == 1 else f"y_{K}x{N}", y))
+        if rank == 0:
+            dump_outputs(o.dump, named)
+    if graph is not None and o.full:
         for _ in range(min(steps, 4 * EV_EVERY)):
             step(True)
         torch.cuda.synchronize()
@@ -404,7 +440,7 @@ def run_workload(ctx: Ctx, o: Opts) -> Optional[dict]:
                         _lib.check(rc, "linear_gemm")
 
     sustained_mhz = None
-    if M > 64 and layers_here > 0 and graph is None and not one_launch:
+    if o.full and M > 64 and layers_here > 0 and graph is None and not one_launch:
         gemm_s = max(sum(e0.elapsed_time(e1) for e0, e1, _, _ in gemm_events[:64]) / max(len(gemm_events[:64]), 1) * 1e-3, 1e-6) \
             if gemm_events else elapsed / steps
         per_step_launches = sum(reps for reps, _, _, _ in calls_for(stream))
@@ -416,7 +452,7 @@ def run_workload(ctx: Ctx, o: Opts) -> Optional[dict]:
 
     # decode workloads: the same steps once more on ONE resident weight (what rounds 1-2 reported: an upper bound)
     resident_fig = None
-    if rotate > 1 and graph is None:
+    if o.full and rotate > 1 and graph is None:
         rot_events, gemm_events = gemm_events, []
         resident[0] = True
         for _ in range(warmup):
@@ -445,7 +481,7 @@ def run_workload(ctx: Ctx, o: Opts) -> Optional[dict]:
 
     # decode workloads (M <= 8): the Linears a model hands the SAME token to - q/k/v - as ONE launch (lqer_linear_forward_group)
     group_fig = None
-    if one_launch and layers == 1 and len(live) == 1 and world == 1 and graph is None and not shard_n:
+    if o.full and one_launch and layers == 1 and len(live) == 1 and world == 1 and graph is None and not shard_n:
         group_fig = _decode_group_region(ctx, live[0], M, r, has_bias, rotate, warmup, steps, ev_flags,
                                          n_members=int(os.environ.get("LQER_BENCH_GROUP_MEMBERS", "3")))  # (2..4: probe of the group size)
 
@@ -490,11 +526,13 @@ def run_workload(ctx: Ctx, o: Opts) -> Optional[dict]:
         return None
 
     # ---- roofline of the dominant kernel (benchlib/roofline.py) from the event samples taken inside the timed region
-    cal_x = (live[0][1], live[0][2]) if live else None
-    ev_overhead_ms = RL.event_pair_overhead_ms(L, _lib, ops, dev, stream, cal_x, new_pair, M) if live else 0.0
     routes = sorted({pl["route"] for pl in plans})
     int8 = routes == [_lib.ROUTE_I8]  # every GEMM of the step ran the int8 MFMA main loop
-    rl = RL.mfma_roofline(gemm_events, ev_overhead_ms, M, r, routes, int8, one_launch, _lib, o.workload, ev_flags)
+    rl = None
+    if o.full:
+        cal_x = (live[0][1], live[0][2]) if live else None
+        ev_overhead_ms = RL.event_pair_overhead_ms(L, _lib, ops, dev, stream, cal_x, new_pair, M) if live else 0.0
+        rl = RL.mfma_roofline(gemm_events, ev_overhead_ms, M, r, routes, int8, one_launch, _lib, o.workload, ev_flags)
     if sustained_mhz is not None and rank == 0:
         # peaks are priced at the 2.4 GHz the data sheet quotes; at the clock the chip actually holds under this load the same
         # kernel can reach peak x sustained / 2400 at most: frac_at_sustained_clock = loop efficiency x everything but the clock
@@ -508,7 +546,7 @@ def run_workload(ctx: Ctx, o: Opts) -> Optional[dict]:
         else:  # (the probe window missed the load: whatever it read is not this kernel's clock)
             rl["sustained_mhz"] = None
             rl["frac_at_sustained_clock"] = None
-    if M <= 64:
+    if o.full and M <= 64:
         rl = RL.hbm_roofline(gemm_events, ev_overhead_ms, M, r, has_bias, routes, one_launch, _lib, o.workload, ev_flags, rotate,
                              ms_per_step, resident_fig)
     f16x = bool(live) and live[0][0]._x_f16
@@ -857,7 +895,8 @@ def _decode_layer(ctx, o):
     dtc = _lib.F16
     lay = []
     keep = []
-    for _ in range(layers):
+    outs = []  # (name, y) of every launch's output, layer by layer (--dump-outputs)
+    for li in range(layers):
         q, k, v, op = (copy.deepcopy(protos[(H, H)][0]) for _ in range(4))
         gt, up = (copy.deepcopy(protos[(H, I)][0]) for _ in range(2))
         dn = copy.deepcopy(protos[(I, H)][0])
@@ -882,6 +921,7 @@ def _decode_layer(ctx, o):
             y = torch.empty(M, m.out_features, dtype=torch.float16, device=dev)
             singles.append((C.byref(desc), x.data_ptr(), dt, M, m.in_features, consts, y, ws_bytes))
             keep.append((desc, y))
+        outs += [(f"layer{li}_{p}", y) for p, y in zip(("q", "k", "v", "gate", "up", "o", "down"), ys + [sg[6] for sg in singles])]
         lay.append((p_qkv, p_gu, singles))
         keep.append((q, k, v, op, gt, up, dn, g_qkv, g_gu, ys))
     ws = ops.workspace(dev, max([pl["ws"] for la in lay for pl in la[:2]] + [sg[7] for la in lay for sg in la[2]] + [256]))
@@ -918,21 +958,28 @@ def _decode_layer(ctx, o):
         step(False)
     el = timed_region(ctx, lambda n: [step(True) for _ in range(n)], steps)
     torch.cuda.synchronize()
-    ovh = RL.event_pair_overhead_ms(L, _lib, ops, dev, stream, (xh, H), new_pair, M)
+    if o.dump is not None:
+        dump_outputs(o.dump, outs)
     # algorithmic bytes (SURVEY 8d's decode model): packed W 0.5625 B per weight, B^T and A^T one bf16 limb, x and y fp16
     rp = -(-r // 16) * 16
     lin = lambda K, N: N * K * 0.5625 + N * rp * 2 + rp * K * 2 + M * K * 2 + M * N * 2
     by = {"qkv": 3 * lin(H, H) - 2 * M * H * 2, "o": lin(H, H), "gate_up": 2 * lin(H, I) - M * H * 2, "down": lin(I, H)}
     by_layer = sum(by.values())
-    per = {}
-    for kind, evs in events.items():
-        ms = sorted(max(e0.elapsed_time(e1) - ovh, 1e-6) for e0, e1 in evs)
-        if ms:
-            med = ms[len(ms) // 2]
-            per[kind] = {"launch_us": round(med * 1e3, 2), "samples": len(ms), "algorithmic_mb": round(by[kind] / 1e6, 2),
-                         "gb_s": round(by[kind] / (med * 1e-3) / 1e9, 1), "frac_of_hbm_peak": round(by[kind] / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
     us_layer = el / steps / layers * 1e6
     gbs = by_layer / (us_layer * 1e-6) / 1e9
+    roofline = None
+    if o.full:
+        ovh = RL.event_pair_overhead_ms(L, _lib, ops, dev, stream, (xh, H), new_pair, M)
+        per = {}
+        for kind, evs in events.items():
+            ms = sorted(max(e0.elapsed_time(e1) - ovh, 1e-6) for e0, e1 in evs)
+            if ms:
+                med = ms[len(ms) // 2]
+                per[kind] = {"launch_us": round(med * 1e3, 2), "samples": len(ms), "algorithmic_mb": round(by[kind] / 1e6, 2),
+                             "gb_s": round(by[kind] / (med * 1e-3) / 1e9, 1), "frac_of_hbm_peak": round(by[kind] / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+        roofline = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                    "traffic": None, "kernel": "k_decode1 (four launches per layer, launch gaps included: the whole layer step)",
+                    "algorithmic_bytes_per_layer": int(by_layer), "per_launch": per, "event_pair_overhead_us": round(ovh * 1e3, 2)}
     # parity: q of the first layer against the oracle
     parity = None
     if o.check:
@@ -956,7 +1003,5 @@ def _decode_layer(ctx, o):
                        "boundary": "C ABI: lqer_linear_forward_group (q/k/v, gate/up) + lqer_linear_forward (o, down), pre-built plans"},
             "tokens_per_s": round(M * steps / el, 1), "us_per_layer": round(us_layer, 2), "us_per_linear": round(us_layer / 7, 2),
             "launches_per_layer": 4,
-            "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                         "traffic": None, "kernel": "k_decode1 (four launches per layer, launch gaps included: the whole layer step)",
-                         "algorithmic_bytes_per_layer": int(by_layer), "per_launch": per, "event_pair_overhead_us": round(ovh * 1e3, 2)},
+            "roofline": roofline,
             "parity_rel_l2": parity}

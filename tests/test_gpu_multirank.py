@@ -25,7 +25,7 @@ def test_two_ranks_on_one_gpu(workload, extra, scaling, layers):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-module"] + extra
+           "--full", "--no-cpu-baseline", "--no-module"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -85,7 +85,7 @@ def test_default_multi_gpu_line_is_c4_with_c2_replicas_rehearsed():
     and `replicas_c2` carries the N independent C2 Linears (weak scaling), both oracle-checked."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _bench(["--gpus", "2", "--layers", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-module"], {"LQER_BENCH_REHEARSE": "1"})
+    d = _bench(["--gpus", "2", "--layers", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-module"], {"LQER_BENCH_REHEARSE": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["layers_per_rank"] == [1, 1] and "Llama-13B" in d["config"]["workload"]
     assert d["dtype"] == "int8" and d["parity_rel_l2"] <= 1e-3 and d["value"] > 0
     r = d["replicas_c2"]
@@ -98,7 +98,7 @@ def test_two_gpus_over_rccl():
     one-GPU boxes of this pool."""
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (RCCL)")
-    d = _bench(["--gpus", "2", "--workload", "c4", "--layers", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-module"],
+    d = _bench(["--gpus", "2", "--workload", "c4", "--layers", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-module"],
                {"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["layers_per_rank"] == [2, 2]
     assert d["parity_rel_l2"] <= 1e-3 and d["value"] > 0 and d["broadcast_ms"] > 0

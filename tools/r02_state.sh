@@ -4,9 +4,9 @@ set -e
 O=gpurun_out/$1; mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -3 $O/pytest.log
-python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 for w in c3 c4 c4row c5 d1 d16; do
-  python bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err
+  python bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err
   echo "$w done"
 done
 cat $O/bench_*.json

@@ -7,8 +7,8 @@ python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1 || { tail -30 $O/pytest
 tail -3 $O/pytest.log
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_driver.json 2> $O/bench_c2_driver.err
 echo "driver line done"
-python bench.py --no-configs > $O/bench_c2.json 2> $O/bench_c2.err
+python bench.py --full --no-configs > $O/bench_c2.json 2> $O/bench_c2.err
 for w in c3 c4 c4row c5 d1 d16; do
-  python bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err
+  python bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err
   echo "$w done"
 done

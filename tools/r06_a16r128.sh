@@ -8,7 +8,7 @@ pick='import json,sys
 r=json.load(sys.stdin); print(sys.argv[1], r["value"], r["ms_per_step"], [ (p["K"],p["N"],p["avg_launch_us"]) for p in r["roofline"]["per_shape"]])'
 for rep in 1 2 3; do
   for t in 0 0x800000; do
-    timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --no-two-streams --no-module --tuning $t 2>/dev/null | python -c "$pick" "c5 tuning=$t" >> $O/a16r128.txt
+    timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --no-two-streams --no-module --tuning $t 2>/dev/null | python -c "$pick" "c5 tuning=$t" >> $O/a16r128.txt
   done
 done
 cat $O/a16r128.txt

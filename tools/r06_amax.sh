@@ -10,10 +10,10 @@ pick='import json,sys
 r=json.load(sys.stdin); print(sys.argv[1], r["value"], r["ms_per_step"], "module", (r.get("module") or {}).get("ms_per_step"), [ (p["K"],p["N"],p["avg_launch_us"]) for p in r["roofline"]["per_shape"]])'
 for rep in 1 2; do
 for t in 0 0x80000 0x40000; do
-  timeout -k 10 300 python bench.py --workload c3int --no-cpu-baseline --no-two-streams --tuning $t 2>/dev/null | python -c "$pick" "c3int tuning=$t" >> $O/amax.txt
+  timeout -k 10 300 python bench.py --full --workload c3int --no-cpu-baseline --no-two-streams --tuning $t 2>/dev/null | python -c "$pick" "c3int tuning=$t" >> $O/amax.txt
 done
 done
 for t in 0 0x40000; do
-  timeout -k 10 300 python bench.py --workload c4 --no-cpu-baseline --no-two-streams --tuning $t 2>/dev/null | python -c "$pick" "c4 tuning=$t" >> $O/amax.txt
+  timeout -k 10 300 python bench.py --full --workload c4 --no-cpu-baseline --no-two-streams --tuning $t 2>/dev/null | python -c "$pick" "c4 tuning=$t" >> $O/amax.txt
 done
 cat $O/amax.txt
