@@ -107,10 +107,7 @@ typedef struct lqer_linear_desc {
 #define LQER_TUNE_TILE_ROWS_128 0x1   /* 128-row kernel family (LQER_ROUTE_TILE128): always 128-row tiles                     */
 #define LQER_TUNE_TILE_ROWS_64 0x2    /* ... always 64-row tiles (two workgroups per CU); default: 64 rows when the 128-row grid
                                          covers at most half of the CUs                                                        */
-#define LQER_TUNE_XCD_BLOCK(t) (((t) & 0x3f) << 4) /* XCD-local tile BLOCKS of `t` token tiles x (tiles / 8 / t) weight tiles in the
-                                         128-row kernel instead of rows of weight tiles; applied only where the tile grid divides
-                                         (16 x 16 tiles: 8, 4 or 16); measured +-0 (the weight stream through every XCD's L2 is
-                                         served by the Infinity Cache)                                                        */
+/* 0x3f0: retired (once XCD-local tile blocks in the 128-row and int8 kernels); ignored - do not reuse */
 #define LQER_TUNE_I8_ROWS_128 0x4      /* int8 kernel (LQER_ROUTE_I8): always 128-row tiles                                      */
 #define LQER_TUNE_I8_ROWS_256 0x8      /* ... always 256-row tiles; default: whichever takes fewer weighted rounds of one tile per
                                          CU (lqer_gemm_tile_rows says which)                                                    */
@@ -124,10 +121,7 @@ typedef struct lqer_linear_desc {
                                          AMAX pin above restores the pre-pass).  This bit makes every workgroup treat the others'
                                          granules as missing, i.e. take the fall-back that computes the whole band's maxima itself (a
                                          workgroup that times out on a neighbour does the same): same bits                          */
-#define LQER_TUNE_XA_REDUCE_IN_GEMM 0x20000 /* lqer_linear_forward on 128-row tiles: no reduce launch between the quantizer and the
-                                         GEMM - its workgroups sum the partial tiles of x A for their own rows (lqer_tile_partials).
-                                         Off by default: measured slower (C2: the GEMM grows by 5.3 us, the launch it saves took
-                                         4.9 us - 16 partial tiles at K = 4096, summed in front of the main loop, whose accumulators it opens)           */
+/* 0x20000: retired (once the partial tiles of x A summed inside the 128-row GEMM); ignored - do not reuse */
 #define LQER_TUNE_ACT8_SPLIT 0x200000 /* int8 route (LQER_Q_MXINT_I8), lqer_quantize_act_xa / lqer_linear_forward: quantizer, split-K side GEMM
                                          and reduce as three launches even where the one-launch kernel applies (16-bit tensors, a_limbs =
                                          -1, padded rank 16 / 32 / 64, M <= 4096): bit-identical int8 image and row scales, x A summed in
@@ -332,13 +326,8 @@ int lqer_gemm_tile_rows(const lqer_linear_desc_t* desc, int64_t M, int dtype);
  * lqer_linear_gemm with xaq_bf16 == NULL and the SAME scratch buffer (scratch_bytes = lqer_lowrank_xa_scratch_bytes):
  * the GEMM sums the tiles in the same fixed order and applies A_out itself.  lqer_linear_forward does this on its own. */
 int lqer_decode_partials(const lqer_linear_desc_t* desc, int64_t M);
-/* The same hand-over at the token counts of the 128-row tile kernel, for callers that ask for it (descriptor tuning bit
- * LQER_TUNE_XA_REDUCE_IN_GEMM; 1 when lqer_linear_forward then takes it for M tokens of `dtype`: LQER_ROUTE_TILE128 with
- * 128-row tiles, fp16 / bf16 tensors, x / A_out in blocks of 16, padded rank <= 64, one limb of A, B_out pass-through or in
- * blocks of 16): every GEMM workgroup sums the partial tiles for its own 128 rows in ascending chunk order and applies A_out
- * on the way into the side product's LDS stage - k_xa_reduce4's arithmetic item by item, same bits (csrc/gemm_w4a8.hip,
- * XAPART).  A measured dead end kept selectable: the sum delays the main loop by more than the launch it replaces.  Same
- * calling convention: lqer_quantize_act_xa and lqer_linear_gemm with xaq_bf16 == NULL and the same scratch. */
+/* The partial-tile hand-over at the 128-row tile kernel's token counts is retired: 0 for every descriptor, token count and
+ * dtype.  Kept for ABI compatibility; lqer_decode_partials names the only route that takes xaq_bf16 == NULL. */
 int lqer_tile_partials(const lqer_linear_desc_t* desc, int64_t M, int dtype);
 
 /* lqer_linear_gemm with an explicit row stride of xaq (elements; a multiple of 8, >= the padded rank): Linears that

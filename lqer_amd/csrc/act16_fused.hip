@@ -254,9 +254,6 @@ int a_b16_prepare_dispatch(const void* a_t_limbs, int64_t K, int64_t r, void* ou
 // LQER_E_UNSUPPORTED: not this kernel's case (the caller takes k_quant_xa16 + k_xa_reduce4 on the image's first part)
 int act16_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t ldx, const QP& qx, bf16_t* xq, const void* a_b16, int64_t r,
                          const QP& qa, bf16_t* xaq, int tuning, hipStream_t st) {
-#ifdef LQER_NO_ACT16_FUSED
-  return LQER_E_UNSUPPORTED;
-#endif
   if (tuning & LQER_TUNE_ACT16_SPLIT) return LQER_E_UNSUPPORTED;
   const int64_t rp = lqer_padded_r(r), Kp = lqer_padded_k(K);
   if (dtype == LQER_F32 || !a_b16 || !xaq || !xq || r <= 0 || M <= 0) return LQER_E_UNSUPPORTED;

@@ -304,9 +304,6 @@ int a_frag_dispatch(void* a_f16, int64_t K, int64_t r, hipStream_t st) {
 int act8_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t ldx, const QP& qx, void* xq_i8, const void* a_f16, int64_t r,
                         const QP& qa, bf16_t* xaq, int tuning, hipStream_t st, float* zero_p, size_t zero_bytes, bool* zeroed) {
   if (zeroed) *zeroed = false;
-#ifdef LQER_NO_ACT8_FUSED
-  return LQER_E_UNSUPPORTED;
-#endif
   if (tuning & LQER_TUNE_ACT8_SPLIT) return LQER_E_UNSUPPORTED;
   const int64_t rp = lqer_padded_r(r);
   if (dtype == LQER_F32 || !a_f16 || !xaq || r <= 0 || M <= 0) return LQER_E_UNSUPPORTED;
@@ -333,18 +330,19 @@ int act8_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t 
   const bool zfit = zero_p && zero_bytes > 0 && zero_bytes / 4 <= (size_t)((M + a8f::ROWS - 1) / a8f::ROWS) * 512;
   float* const zp = zfit ? zero_p : nullptr;
   const int zn = zfit ? (int)(zero_bytes / 4) : 0;
-  if (zeroed) *zeroed = zfit;  // (every return below this line that is not LQER_E_UNSUPPORTED has launched the kernel)
-#define A8F_DT(DTv)                                                                                                                       \
-  do {                                                                                                                                    \
-    if (nch_p <= 64 * 8) return a8f::launch<DTv, 8>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st);       \
-    if (nch_p <= 64 * 12) return a8f::launch<DTv, 12>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st);     \
-    if constexpr (DTv == LQER_F16) /* (bf16 rows beyond 6144 elements: 112 raw registers + the wider conversion spill - three launches) */ \
-      if (nch_p <= 64 * 28) return a8f::launch<DTv, 28>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st);   \
-  } while (0)
-  if (dtype == LQER_F16) A8F_DT(LQER_F16);
-  else if (dtype == LQER_BF16) A8F_DT(LQER_BF16);
-#undef A8F_DT
-  return LQER_E_UNSUPPORTED;
+  // row chunks the kernel holds in registers (bf16 rows beyond 6144 elements: 112 raw registers + the wider conversion spill - three launches)
+  const int maxch = nch_p <= 64 * 8 ? 8 : nch_p <= 64 * 12 ? 12 : (dtype == LQER_F16 && nch_p <= 64 * 28) ? 28 : 0;
+  if (maxch == 0 || (dtype != LQER_F16 && dtype != LQER_BF16)) return LQER_E_UNSUPPORTED;
+  if (zeroed) *zeroed = zfit;  // (every return below this line has launched the kernel)
+#define A8F(DTv, MAXCHv) return a8f::launch<DTv, MAXCHv>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st)
+  if (dtype == LQER_F16) {
+    if (maxch == 8) A8F(LQER_F16, 8);
+    if (maxch == 12) A8F(LQER_F16, 12);
+    A8F(LQER_F16, 28);
+  }
+  if (maxch == 8) A8F(LQER_BF16, 8);
+  A8F(LQER_BF16, 12);
+#undef A8F
 }
 
 }  // namespace lqer

@@ -190,21 +190,6 @@ FwdT fwd_t;
 #endif
 
 extern "C" {
-static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, GemmArgs& g);
-// Token counts of the 128-row tile kernel, on request (LQER_TUNE_XA_REDUCE_IN_GEMM - measured slower, include/lqer_hip.h): its workgroups sum the partial tiles for their own rows on the way into the
-// side product's LDS stage (k_lqer_gemm XAPART) - the reduce launch between the quantizer and the GEMM is skipped
-static bool tile_partials_ok(const lqer_linear_desc_t* d, int64_t M, int dtype) {
-  if (!d || d->rank <= 0 || M <= 64 || (dtype != LQER_F16 && dtype != LQER_BF16) || !(d->tuning & LQER_TUNE_XA_REDUCE_IN_GEMM)) return false;
-  if (d->w_fmt.kind != LQER_Q_MXINT || d->x_fmt.kind != LQER_Q_MXINT || d->a_out_fmt.kind != LQER_Q_MXINT || w_limbs(d) != 1) return false;
-  if (!xa_fused_partials_ok(make_qp(d->x_fmt), make_qp(d->a_out_fmt), d->rank)) return false;
-  const lqer_qfmt_t& bo = d->b_out_fmt;  // (other B_out blocks: the pre-pass reads xAq)
-  if (!(bo.kind == LQER_Q_PASSTHROUGH || (bo.kind == LQER_Q_MXINT && bo.block == 16))) return false;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  if (gemm_shape_args(d, M, dtype, g)) return false;
-  return gemm_route(g, true) == LQER_ROUTE_TILE128 && gemm_tile_rows(g) == 128;
-}
-
 int lqer_version(void) { return LQER_ABI_VERSION; }
 size_t lqer_sizeof_qfmt(void) { return sizeof(lqer_qfmt_t); }
 size_t lqer_sizeof_linear_desc(void) { return sizeof(lqer_linear_desc_t); }
@@ -535,9 +520,9 @@ static int quantize_act_xa_single(const lqer_linear_desc_t* d, const void* x, in
     a_limbs = 1;
   }
   if (d->rank > 0 && a_t && !xaq) {  // partial tiles only: the GEMM reduces them (decode sizes)
-    if (!decode_partials_ok(d, M) && !tile_partials_ok(d, M, dtype)) {
-      set_error("quantize_act_xa: xaq == NULL needs M <= 64 or the 128-row tile kernel's token counts with fp16 / bf16 tensors, "
-                "x / A_out block_fp in blocks of 16 (width <= 9), padded rank <= 64 and B_out pass-through or in blocks of 16");
+    if (!decode_partials_ok(d, M)) {
+      set_error("quantize_act_xa: xaq == NULL needs M <= 64, x / A_out block_fp in blocks of 16 (width <= 9), padded rank <= 64 "
+                "and B_out pass-through or in blocks of 16");
       return LQER_E_INVALID;
     }
     const int rc = quant_xa_fused_dispatch(x, dtype, M, d->in_features, ldx, make_qp(d->x_fmt), (bf16_t*)xq, (const bf16_t*)a_t,
@@ -699,7 +684,7 @@ static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t
     return LQER_E_INVALID;
   }
   const bool lowrank = d->rank > 0;
-  const bool from_partials = lowrank && !xaq && b_t && scratch && (decode_partials_ok(d, M) || tile_partials_ok(d, M, dtype));
+  const bool from_partials = lowrank && !xaq && b_t && scratch && decode_partials_ok(d, M);
   if (lowrank && ((!xaq && !from_partials) || !b_t)) {
     set_error("linear_gemm: rank %d but no side-path operands (xaq == NULL: only the decode route, see lqer_decode_partials)", d->rank);
     return LQER_E_INVALID;
@@ -785,7 +770,6 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
     HT_MARK(3);
     const size_t nscr = lqer_lowrank_xa_scratch_bytes(d, M);
     HT_MARK(4);
-#ifndef LQER_NO_DECODE1
     // up to 8 tokens: ONE launch (decode1.hip) - producer workgroups publish the partial tiles of x A, the weight-streaming
     // workgroups quantize x themselves and pick the tiles up at their very end
     const int esz = dtype == LQER_F32 ? 4 : 2;
@@ -813,20 +797,11 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
       HT_DONE();
       if (rc != LQER_E_UNSUPPORTED) return rc;
     }
-#endif
     // two launches: the GEMM sums the partial tiles of x A itself
     rc = lqer_quantize_act_xa(d, x, dtype, M, ldx, a_t, a_limbs, xq, nullptr, xa_scratch, nscr, stream);
     if (rc) return rc;
     return lqer_linear_gemm(d, xq, M, w_packed, nullptr, b_t, b_limbs, bias_q, y, dtype, ldy, xa_scratch, nscr, stream);
   }
-#ifndef LQER_NO_TILE_PARTIALS
-  if (a_t && b_t && a_limbs == 1 && tile_partials_ok(d, M, dtype)) {  // two launches: no reduce kernel in between
-    const size_t nscr = lqer_lowrank_xa_scratch_bytes(d, M);
-    rc = lqer_quantize_act_xa(d, x, dtype, M, ldx, a_t, a_limbs, xq, nullptr, xa_scratch, nscr, stream);
-    if (rc) return rc;
-    return lqer_linear_gemm(d, xq, M, w_packed, nullptr, b_t, b_limbs, bias_q, y, dtype, ldy, xa_scratch, nscr, stream);
-  }
-#endif
   // (a pre-pass on atomicMax cells behind the one-launch int8 activation kernel: that kernel zeroes the cells - the two calls share the
   // scratch, whose size is the larger of their needs - instead of a memset launch between them)
   AmaxZeroReq zr = amax_zero_request(d, M, dtype, a_limbs, b_t ? xa_scratch : nullptr);
@@ -917,7 +892,7 @@ int lqer_desc_limbs(const lqer_linear_desc_t* d, int* act, int* xa) {
 
 int lqer_decode_partials(const lqer_linear_desc_t* d, int64_t M) { return decode_partials_ok(d, M) ? 1 : 0; }
 
-int lqer_tile_partials(const lqer_linear_desc_t* d, int64_t M, int dtype) { return tile_partials_ok(d, M, dtype) ? 1 : 0; }
+int lqer_tile_partials(const lqer_linear_desc_t*, int64_t, int) { return 0; }  // (the route it reported is retired)
 
 int lqer_f16_prepare(const void* w_packed, int64_t N, int64_t K, const void* a_t_limbs, int a_limbs, int64_t r, void* a_t_f16,
                      int32_t* flags, void* stream) {

@@ -42,16 +42,7 @@ constexpr int R_SLOT = (BN / 16) * LQER_PANEL_BYTES;  // 9216 B  packed weight p
 constexpr int OFF_A = 0;
 // per tile height (MT 32-row tiles): activation slot 16 KiB (128 rows) or 8 KiB (64 rows), bf16; the panels behind the ring
 constexpr int a_slot_bytes(int mt) { return 32 * mt * BK * 2; }
-#ifdef LQER_ABL_E4M3SIM
-// Timing-only experiment (profiles/r05_e4m3_sim.txt): what the main loop would cost with a second, prefill-only
-// weight image of one e4m3 byte per weight - one more 1-KiB LDS-DMA per wave and step into a shadow region behind the ring (bytes of
-// a neighbouring k-step), one more 16-byte fragment read, and an expand of four v_cvt_scalef32_pk_bf16_fp8 per 8 weights.  The
-// results of this build are garbage; 128-row tiles only.
-constexpr int SH_SLOT = 8192, SH_PAD = 4096;
-constexpr int gemm_lds_bytes(int mt) { return NSLOT * a_slot_bytes(mt) + NSLOT * R_SLOT + NSLOT * SH_SLOT + SH_PAD; }
-#else
-constexpr int gemm_lds_bytes(int mt) { return NSLOT * a_slot_bytes(mt) + NSLOT * R_SLOT; }
-#endif  // 102400 B / 69632 B (two workgroups per CU)
+constexpr int gemm_lds_bytes(int mt) { return NSLOT * a_slot_bytes(mt) + NSLOT * R_SLOT; }  // 102400 B / 69632 B (two workgroups per CU)
 
 // byte offset of 16-byte chunk `c` (8 bf16 along k) of tile row `r`; rows are 128 B.
 // chunk ^ ((row >> 1) & 7): the 16 lanes of a ds_read_b128 group then hit 16 distinct 16-B slots.
@@ -112,9 +103,6 @@ __device__ __forceinline__ void lds_wait(u32x2& a, int& b) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b));
 }
 
-#ifndef LQER_DEFER_WHERE
-#define LQER_DEFER_WHERE 0  // DEFER pieces: 0 inside COMPUTE (between its MFMAs), 1 at the head of LOAD
-#endif
 #ifdef LQER_STAMPS
 #define LQER_LOAD_BARRIER ""  // the diagnostic build stamps between the waits and the barrier
 #else
@@ -146,12 +134,6 @@ __device__ unsigned long long* g_stamp_buf = nullptr;  // diagnostic builds only
 // WTWOS: the packed weight holds two's-complement nibbles (w_quantizer = integer, codes -8 .. 7): the second expand of common.h
 // (128-row tiles, staged side path and 16-bit / fp32 tensors only: a format no template configuration uses gets a working
 // kernel, not a tuned one).
-// XAPART: there is no xAq yet - the fused quantize kernel left the split-K partial tiles of x A (g.xa_part: part[c][m][rp] fp32) and
-// the workgroup sums them in ascending chunk order and applies A_out (blocks of 16) to its 128 / 64 rows on the way into the
-// LDS stage: k_xa_reduce4's arithmetic, item by item, and one dependent launch less per Linear.  Selectable only
-// (LQER_TUNE_XA_REDUCE_IN_GEMM): at C2 the launch it saves took 4.9 us and this kernel grows by 5.3 us (1.0 of it the staged
-// route's barriers) - the quantizer leaves one partial tile per 256 k (16 at K = 4096: 256 KB per workgroup, four round trips
-// of four chunks), and the sum sits in front of the main loop, whose accumulators it opens, with nothing to hide behind.
 // DEFER (round 6): the B_out re-quantization of the side product leaves the prologue.  There it was ~800 vector instructions per wave
 // between the side product's MFMAs and the first k-step with nothing to hide behind: 3.5 of the 5.4 us in front of the main loop at
 // 2048 x 4096 x 4096 (tools/clock_probe.py, "prologue split").  Here the side product stays in registers of its own (sp), the main
@@ -159,11 +141,10 @@ __device__ unsigned long long* g_stamp_buf = nullptr;  // diagnostic builds only
 // MFMAs (even piece: a block's maximum, exponent and scale factors; odd piece: its eight values), and sp is added behind the last
 // k-step - as gemm_smallm.hip and decode1.hip always did.  Same formula (the scale exponent clamped to normal floats, exact while
 // |x| <= 1e-8 passes through: gemm_w4a8_i8.hip's epilogue); blocks of 16, clamps up to 2^22 and K >= 1024 (launch_gemm).
-template <int DT, bool LOWRANK, int BOUT, bool STAGED = false, int MT = 4, bool WTWOS = false, bool XAPART = false, bool DEFER = false>
+template <int DT, bool LOWRANK, int BOUT, bool STAGED = false, int MT = 4, bool WTWOS = false, bool DEFER = false>
 __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   static_assert(MT == 4 || MT == 2, "128- or 64-row tiles");
-  static_assert(!DEFER || (LOWRANK && BOUT == 1 && MT == 4 && !XAPART), "deferred B_out: blocks of 16 on 128-row tiles");
-  static_assert(!XAPART || (LOWRANK && STAGED), "the partial tiles of x A enter through the LDS stage");
+  static_assert(!DEFER || (LOWRANK && BOUT == 1 && MT == 4), "deferred B_out: blocks of 16 on 128-row tiles");
   static_assert(!WTWOS || DT != LQER_F16X, "integer weights: no fp16 main loop");
   constexpr int BMk = 32 * MT;   // tile rows
   constexpr int AP = MT / 2;     // 8-row LDS-DMA pieces of the activation tile per wave and k-step
@@ -186,14 +167,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     const int b = blockIdx.x, xcd = b & 7, q8 = nt >> 3, r8 = nt & 7;
     tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
   }
-  int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
-  if (g.xcd_bm > 0) {
-    // XCD-local tile BLOCKS (the host checked divisibility): xcd_bm token tiles x nt / 8 / xcd_bm weight tiles per XCD, the XCDs
-    // as a (tiles_m / xcd_bm) x (rest) grid - the bytes an XCD pulls through its L2 become W / gn + x / gm instead of W + x / 8
-    const int b = blockIdx.x, xcd = b & 7, l = b >> 3;
-    const int bn = (nt >> 3) / g.xcd_bm, gm = g.tiles_m / g.xcd_bm;
-    tm = (xcd % gm) * g.xcd_bm + l % g.xcd_bm, tn = (xcd / gm) * bn + l / g.xcd_bm;
-  }
+  const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BMk, n0 = tn * BN;
   const int nk = g.Kp / BK;
 
@@ -223,23 +197,14 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   unsigned char* const a_dst0 = smem + OFF_A + wave * (8 * AP) * 128;  // + slot * A_SLOT + piece * 1024
   unsigned char* const w_dst0 = smem + OFF_R + wave * 1024;      // + slot * R_SLOT
   auto issue_loads = [&](int kt, int slot) {  // 3 LDS-DMA instructions per wave (wave 0: 4)
-#ifndef LQER_ABL_NO_A_LOAD
 #pragma unroll
     for (int i = 0; i < AP; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (lds_void*)(a_dst0 + slot * A_SLOT + i * 1024), 16, a_voff[i],
                                                kt * (BK * 2), 0, 0);
-#endif
-#ifndef LQER_ABL_NO_W_LOAD
     __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void*)(w_dst0 + slot * R_SLOT), 16, w_voff, kt * LQER_PANEL_BYTES, 0, 0);
     if (wave == 0)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void*)(smem + OFF_R + 8192 + slot * R_SLOT), 16, w_voff8,
                                                kt * LQER_PANEL_BYTES, 0, 0);
-#endif
-#ifdef LQER_ABL_E4M3SIM
-    if constexpr (MT == 4)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void*)(smem + OFF_R + NSLOT * R_SLOT + slot * SH_SLOT + wave * 1024), 16, w_voff,
-                                               (kt ^ 1) * LQER_PANEL_BYTES, 0, 0);
-#endif
   };
   // fragment read addresses (slot 0).  Activation: row = wave tile row + lane & 31, chunk 2 ks + (lane >> 5),
   // swizzled; the second m tile is +32 rows = +4096 B (row + 32 keeps (row >> 1) & 7).
@@ -266,8 +231,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   bf16x8 sb[STAGED ? 2 : 1][STAGED ? 4 : 1];  // B^T fragments of one limb of the pass, double-buffered
   const uint32_t stage = lds0 + OFF_A + (NSLOT - 1) * A_SLOT;
   const bf16_t* const bt_row = STAGED ? g.bt + (int64_t)(n0 + wn * 32 + l31) * g.rp + 8 * lh : nullptr;
-  float4 pv[XAPART ? 8 : 1];                                    // XAPART: the thread's first four chunk reads (8 floats each)
-  const int xa_rows = XAPART ? (int)(g.xa_cstride / g.rp) : 0;  // rows the partial tiles hold (a multiple of 32)
   auto side_fetch_b = [&](int p0, int l, auto buf_c) {  // limb l of this wave's B^T fragments -> sb[buf]
     constexpr int BUF = decltype(buf_c)::value;
     if constexpr (STAGED) {
@@ -281,24 +244,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     if constexpr (!STAGED) return;
     const int cols = g.rp - p0 < 64 ? g.rp - p0 : 64;  // a multiple of 16
     const int cpr = cols >> 3;                          // 16-byte chunks per row
-    if constexpr (XAPART) {
-      // one item = 8 consecutive rank entries of one token; a thread has one item (rank <= 32) or two.  The first four chunk
-      // reads of the thread (4 chunks of its item, or 2 of each) are requested here, ahead of the ring prefetch; side_reduce
-      // (behind it) sums, requests the rest and quantizes
-      const int nit = BMk * cpr > 512 ? 2 : 1;  // (workgroup-uniform)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j = nit == 2 ? q >> 1 : 0, u = nit == 2 ? q & 1 : q;
-        const int c = tid + 512 * j;
-        const int row = c / cpr, ch = c - row * cpr;
-        // (branch-free: rows and chunks that do not exist read the last one that does and are dropped in side_reduce - a
-        // predicated load would be waited for on the spot, one round trip per chunk)
-        const int rowc = m0 + row < xa_rows ? m0 + row : xa_rows - 1, uc = u < g.xa_nchunk ? u : g.xa_nchunk - 1;
-        const float* src = g.xa_part + (int64_t)rowc * g.rp + p0 + 8 * ch + uc * g.xa_cstride;
-        pv[2 * q] = *(const float4*)src;
-        pv[2 * q + 1] = *(const float4*)(src + 4);
-      }
-    } else {
 #pragma unroll
     for (int j = 0; j < STG; ++j) {
       const int c = tid + 512 * j;
@@ -307,63 +252,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
         stg[j] = *(const u32x4*)(g.xaq + (int64_t)(m0 + row) * g.xaq_ld + p0 + 8 * ch);
       }
     }
-    }
     side_fetch_b(p0, 0, std::integral_constant<int, 0>{});
-  };
-  // XAPART: chunks summed in ascending order (k_xa_reduce4's order and arithmetic), A_out over the block of 16 = the items of
-  // lanes l and l ^ 1 (cpr is even), bf16 bits into the stage registers
-  auto side_reduce = [&](int p0) {
-    if constexpr (XAPART) {
-      const int cols = g.rp - p0 < 64 ? g.rp - p0 : 64;
-      const int cpr = cols >> 3;
-      auto items = [&](auto nit_c) {
-        constexpr int NIT = decltype(nit_c)::value, FB = 4 / NIT;  // items per thread, chunks per item already requested
-#pragma unroll
-        for (int j = 0; j < NIT; ++j) {
-          const int c = tid + 512 * j;
-          const int row = c / cpr, ch = c - row * cpr;
-          const bool live = c < BMk * cpr && m0 + row < xa_rows;
-          float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          auto add = [&](const float4& a, const float4& b, bool on) {  // (x + 0 = x: a dropped chunk leaves the sum's bits alone)
-            s[0] += on ? a.x : 0.f, s[1] += on ? a.y : 0.f, s[2] += on ? a.z : 0.f, s[3] += on ? a.w : 0.f;
-            s[4] += on ? b.x : 0.f, s[5] += on ? b.y : 0.f, s[6] += on ? b.z : 0.f, s[7] += on ? b.w : 0.f;
-          };
-#pragma unroll
-          for (int u = 0; u < FB; ++u) add(pv[2 * (FB * j + u)], pv[2 * (FB * j + u) + 1], live && u < g.xa_nchunk);
-          const int rowc = m0 + row < xa_rows ? m0 + row : xa_rows - 1;
-          const float* src = g.xa_part + (int64_t)rowc * g.rp + p0 + 8 * ch;
-          for (int cc = FB; cc < g.xa_nchunk; cc += 4) {  // one chunk per 256 k: four more chunks per round trip
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int uc = cc + u < g.xa_nchunk ? cc + u : g.xa_nchunk - 1;
-              v[2 * u] = *(const float4*)(src + uc * g.xa_cstride), v[2 * u + 1] = *(const float4*)(src + uc * g.xa_cstride + 4);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) add(v[2 * u], v[2 * u + 1], live && cc + u < g.xa_nchunk);
-          }
-          float amax = 0.f;
-#pragma unroll
-          for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(s[k]));
-          amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-          const bool any = amax > 0.f;
-          const int e = any ? block_exponent(amax, g.aout) : 0;
-          uint32_t w[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float v0 = any ? ldexpf(mxint_mantissa(s[2 * k], e, g.aout), e - g.aout.mbits) : 0.f;
-            const float v1 = any ? ldexpf(mxint_mantissa(s[2 * k + 1], e, g.aout), e - g.aout.mbits) : 0.f;
-            w[k] = exact_bf16_bits(v0) | (exact_bf16_bits(v1) << 16);
-          }
-          stg[j] = (u32x4){w[0], w[1], w[2], w[3]};
-        }
-      };
-      if (BMk * cpr > 512) {
-        if constexpr (STG == 2) items(std::integral_constant<int, 2>{});
-      } else {
-        items(std::integral_constant<int, 1>{});
-      }
-    }
   };
   // (a side product of at most two 16-deep slices - rank <= 32 with one limb - is cheaper fetched directly: the two
   // barriers of the staged route cost more than they save there; launch_gemm picks the instantiation)
@@ -427,7 +316,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
         asm volatile("s_barrier" ::: "memory");  // the previous pass's fragment reads are done (lgkmcnt(0) below)
         side_fetch(p0);
       }
-      side_reduce(p0);
 #pragma unroll
       for (int j = 0; j < STG; ++j) {
         const int c = tid + 512 * j;
@@ -518,11 +406,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   // which ends (lgkmcnt(0)) before barrier 2kt-1; the overwriting loads are issued after it.
   const bool late = wave >= 4;
   // loads(0) landed; two batches of AP + 1 (3, or 2 with 64-row tiles) may stay in flight
-#ifdef LQER_ABL_E4M3SIM
-  if constexpr (MT == 4) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-#else
   if constexpr (MT == 4) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-#endif
   else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
   if (late) asm volatile("s_barrier" ::: "memory");
 #ifdef LQER_CLOCKPROBE
@@ -606,11 +490,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     constexpr int SLOT = decltype(slot_c)::value;
     constexpr int slot_new = SLOT == 0 ? NSLOT - 1 : SLOT - 1;  // (slot + DEPTH) % NSLOT
     STAMP(7);
-#if LQER_DEFER_WHERE == 1  // (experiment: the piece at the head of LOAD, under the partner wave's MFMAs)
-    defer_piece(piece_c);
-    defer_pin(piece_c);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     __builtin_amdgcn_s_setprio(1);
     const int ktn = __builtin_amdgcn_readfirstlane(kt + DEPTH);
     const int a_soff = ktn * (BK * 2), w_soff = ktn * LQER_PANEL_BYTES;
@@ -619,20 +498,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     bf16x8 xa[4][MT];  // [ks][m tile]
     u32x4 wr;
     uint32_t we;
-#ifdef LQER_ABL_E4M3SIM
-    u32x4 wr2 = {0u, 0u, 0u, 0u};
-    if constexpr (MT == 4) {  // the second half of the e4m3 fragment + its LDS-DMA (waited for by the statement below)
-      const uint32_t m0sh = lds0 + OFF_R + NSLOT * R_SLOT + slot_new * SH_SLOT + wave * 1024;
-      const int sh_soff = (ktn ^ 1) * LQER_PANEL_BYTES;
-      asm volatile("ds_read_b128 %0, %1 offset:%c2\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, %6 offen lds"
-                   : "=&v"(wr2)
-                   : "v"(fw_addr), "i"(NSLOT * R_SLOT + SLOT * SH_SLOT), "v"(w_voff), "s"(w_rs), "s"(m0sh), "s"(sh_soff)
-                   : "memory");
-    }
-#define LQER_I_VM "8"
-#else
-#define LQER_I_VM "6"
-#endif
     if constexpr (MT == 4) {
       asm volatile(
           "ds_read_b128 %0, %18 offset:%c25\n\tds_read_b32 %1, %19 offset:%c25+512\n\t"
@@ -651,7 +516,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
           "s_mov_b32 m0, %35\n\ts_nop 0\n\tbuffer_load_dwordx4 %29, %31, %37 offen lds\n\t"
           // own loads of step kt+1 landed: the batches of kt+2 and kt+3 (3 loads each, wave 0: 4 - it waits a little
           // more than it must) may stay in flight
-          "1:\n\ts_waitcnt vmcnt(" LQER_I_VM ") lgkmcnt(0)"
+          "1:\n\ts_waitcnt vmcnt(6) lgkmcnt(0)"
           : "=&v"(wr), "=&v"(we), "=&v"(xa[0][0]), "=&v"(xa[0][1]), "=&v"(xa[0][2]), "=&v"(xa[0][3]), "=&v"(xa[1][0]),
             "=&v"(xa[1][1]), "=&v"(xa[1][2]), "=&v"(xa[1][3]), "=&v"(xa[2][0]), "=&v"(xa[2][1]), "=&v"(xa[2][2]),
             "=&v"(xa[2][3]), "=&v"(xa[3][0]), "=&v"(xa[3][1]), "=&v"(xa[3][2]), "=&v"(xa[3][3])
@@ -681,33 +546,17 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
           : "memory", "scc");
     }
     STAMP(1);  // LDS reads + DMA issue + waits
-#ifdef LQER_ABL_E4M3SIM
-    int sim_ks = 0;
-    auto expand = [&](uint32_t word, uint32_t scale_bits) {  // 8 weights = 2 words of e4m3 bytes: four conversions, nothing else
-      const float scale = __uint_as_float(scale_bits);
-      const uint32_t w2 = wr2[sim_ks++ & 3];
-      u32x4 r;
-      r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(word, scale, false));
-      r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(word, scale, true));
-      r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w2, scale, false));
-      r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w2, scale, true));
-      return __builtin_bit_cast(bf16x8, r);
-    };
-#else
     auto expand = [](uint32_t word, uint32_t scale_bits) {
       if constexpr (WTWOS) return expand_frag_twos(word, scale_bits);
       else return expand_frag_t<XF16>(word, scale_bits);
     };
-#endif
     bf16x8 wb_first = expand(wr[0], (we & 0xffu) << 23);
     asm volatile("s_barrier" : "+v"(wb_first)::"memory");
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     STAMP(4);  // expand of the first fragment + barrier
     // ---- COMPUTE(kt)
-#if LQER_DEFER_WHERE == 0
     defer_piece(piece_c);
-#endif
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       // biased exponent byte ks -> fp32 bits of the block scale 2^(e - mbits)
@@ -716,9 +565,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < MT; ++i) acc[i] = mfma_32x32x16<XF16>(wb, xa[ks][i], acc[i]);
     }
-#if LQER_DEFER_WHERE == 0
     defer_pin(piece_c);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     STAMP(5);  // COMPUTE section issue
     asm volatile("s_barrier" ::: "memory");
@@ -775,12 +622,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   }
   // ---- store ----------------------------------------------------------------------------------
   // per 32x32 tile and quad q: regs 4q..4q+3 = columns n = nb + 8q + 4 lh + (0..3) of token row m
-#ifdef LQER_ABL_NO_STORE
-  if (g.M > 0) {
-    for (int i = 0; i < MT; ++i) asm volatile("" ::"v"(acc[i]));
-    return;
-  }
-#endif
   const bool aligned16 = (((uintptr_t)g.y) & 15) == 0;
   const int nb = n0 + wn * 32;
 #pragma unroll
@@ -1127,26 +968,6 @@ static int launch_gemm(const GemmArgs& g, bool lowrank, int bout, hipStream_t st
       return check_launch("lqer_gemm");
     }
   }
-  if (lowrank && g.xa_part) {  // the partial tiles of x A instead of xAq (api: lqer_tile_partials): staged side path, 16-bit tensors
-    if constexpr (DT != LQER_F16 && DT != LQER_BF16) {
-      set_error("linear_gemm: the partial-tile route takes fp16 / bf16 tensors");
-      return LQER_E_UNSUPPORTED;
-    } else {
-#define LQER_GEMM_LAUNCH_XAP(BO, MTv)                                                                           \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, true, BO, true, MTv, false, true>, gemm_lds_bytes(MTv));          \
-    k_lqer_gemm<DT, true, BO, true, MTv, false, true><<<grid, 512, gemm_lds_bytes(MTv), st>>>(g);               \
-  } while (0)
-      if (bout == 2 || g.tiles_m_rows != BM) {  // (64-row tiles: two workgroups per CU leave the reduction no registers)
-        set_error("linear_gemm: the partial-tile route serves 128-row tiles with B_out in blocks of 16 or pass-through");
-        return LQER_E_UNSUPPORTED;
-      }
-      if (bout == 1) LQER_GEMM_LAUNCH_XAP(1, 4); else LQER_GEMM_LAUNCH_XAP(0, 4);
-#undef LQER_GEMM_LAUNCH_XAP
-      return check_launch("lqer_gemm");
-    }
-  }
 #define LQER_GEMM_LAUNCH_H64(LR, BO, ST)                                                                        \
   do {                                                                                                          \
     static LdsLimitOnce lds_once;                                                                               \
@@ -1168,8 +989,8 @@ static int launch_gemm(const GemmArgs& g, bool lowrank, int bout, hipStream_t st
 #define LQER_GEMM_LAUNCH_DEFER(ST)                                                                              \
   do {                                                                                                          \
     static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, true, 1, ST, 4, false, false, true>, gemm_lds_bytes(4));          \
-    k_lqer_gemm<DT, true, 1, ST, 4, false, false, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);               \
+    lds_once.set((const void*)k_lqer_gemm<DT, true, 1, ST, 4, false, true>, gemm_lds_bytes(4));                 \
+    k_lqer_gemm<DT, true, 1, ST, 4, false, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                      \
   } while (0)
   if (!lowrank)
     LQER_GEMM_LAUNCH(false, 0);
@@ -1249,13 +1070,11 @@ int gemm_route(const GemmArgs& g, bool lowrank) {
 // (twice the workgroups, half the MFMA work per expanded weight fragment - the k-step is then paced by the weight expand,
 // NOTEBOOK.md §4.1) as long as they still fit one round.
 int gemm_tile_rows(const GemmArgs& g) {
-#ifndef LQER_NO_H64
   constexpr int CUS = 256;
   const int64_t tn = g.Np / BN;
   const int64_t t128 = (int64_t)((g.M + BM - 1) / BM) * tn, t64 = (int64_t)((g.M + 63) / 64) * tn;
   const int pin = (g.tuning & LQER_TUNE_TILE_ROWS_128) ? 128 : ((g.tuning & LQER_TUNE_TILE_ROWS_64) ? 64 : 0);  // (tests)
   if (!g.w_twos && ((pin != 128 && 2 * t128 <= CUS && t64 > t128 && g.M > 64) || (pin == 64 && g.M > 64))) return 64;
-#endif
   return BM;
 }
 
@@ -1365,7 +1184,6 @@ int gemm_dispatch(GemmArgs g, int dtype, bool lowrank, void* scratch, size_t scr
       const unsigned grid = (unsigned)((waves + 3) / 4);
       if (parts) g.bout_nseg = nseg_used;
 #define LQER_AMAX(RGv, NKSv) k_bout_amax<RGv, NKSv><<<grid, 256, 0, st>>>(g, tiles_n32, seg_tiles)
-#ifndef LQER_AMAX_NO_LDS
       const int64_t wgroups4 = ((((g.M + 31) / 32 + 3) / 4) + 3) / 4;  // workgroups of the LDS variant along the rows (4 waves x 4 row groups)
       if (nks == 4 && g.rp == 64 && (!parts || wgroups4 * LQER_AMAX_NSEG >= 256)) {  // rank 64: the B^T run through LDS, four row groups per workgroup
         int ns = (int)((LQER_AMAX_WAVES / 4) / wgroups4);
@@ -1388,7 +1206,6 @@ int gemm_dispatch(GemmArgs g, int dtype, bool lowrank, void* scratch, size_t scr
           default: LQER_AMAX(2, 4); break;
         }
       } else
-#endif
       switch (nks) {
         case 1: LQER_AMAX(4, 1); break;
         case 2: LQER_AMAX(4, 2); break;
@@ -1421,18 +1238,11 @@ int gemm_dispatch(GemmArgs g, int dtype, bool lowrank, void* scratch, size_t scr
   }
   if (!g.w_twos) {
     if (smallm_eligible(g, bout)) return smallm_dispatch(g, dtype, lowrank, bout, st);  // decode sizes: HBM-bound variant
-    if (m256_eligible(g) && !g.xa_part) return m256_dispatch(g, dtype, lowrank, bout, st);  // large M: 256 x 256 tiles
+    if (m256_eligible(g)) return m256_dispatch(g, dtype, lowrank, bout, st);  // large M: 256 x 256 tiles
   }
   g.tiles_n = g.Np / BN;
   g.tiles_m_rows = gemm_tile_rows(g);
   g.tiles_m = (g.M + g.tiles_m_rows - 1) / g.tiles_m_rows;
-  {
-    const int bm = (g.tuning >> 4) & 0x3f, nt = g.tiles_m * g.tiles_n;  // LQER_TUNE_XCD_BLOCK (measurements)
-    g.xcd_bm = 0;
-    if (bm > 0 && nt % 8 == 0 && (nt / 8) % bm == 0 && g.tiles_m % bm == 0 && 8 % (g.tiles_m / bm) == 0 &&
-        g.tiles_n % (8 / (g.tiles_m / bm)) == 0 && (nt / 8) / bm == g.tiles_n / (8 / (g.tiles_m / bm)))
-      g.xcd_bm = bm;
-  }
   switch (dtype) {
     case LQER_F32: return launch_gemm<LQER_F32>(g, lowrank, bout, st);
     case LQER_F16: return g.x_f16 ? launch_gemm<LQER_F16X>(g, lowrank, bout, st) : launch_gemm<LQER_F16>(g, lowrank, bout, st);

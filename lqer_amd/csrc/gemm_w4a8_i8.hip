@@ -396,16 +396,8 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   }
   const int nt = g.tiles_m * g.tiles_n;
   // XCD-aware tile order of a virtual block id (blocks b, b + 8, ... share an XCD; the grid is a multiple of 8 or covers nt)
-  // g.xcd_bm > 0 (round 6, LQER_TUNE_XCD_BLOCK; host-checked: nt % 8 == 0 and the grid divides): an XCD's nt / 8 tiles form a BLOCK of
-  // xcd_bm token tiles x (nt / 8 / xcd_bm) weight tiles instead of whole rows of weight tiles - 16 x 16 tiles as 4 x 8 blocks read
-  // 2 + 4.2 MB per XCD instead of 1 + 8.5 (K = 4096)
   auto tile_of = [&](int b) {
     const int xcd = b & 7, q8 = nt >> 3, r8 = nt & 7;
-    if (g.xcd_bm > 0) {
-      const int bn = q8 / g.xcd_bm, gx = g.tiles_n / bn;  // block width in weight tiles; XCD blocks per row of blocks
-      const int xr = xcd / gx, xc = xcd - xr * gx, i = b >> 3, r = i / bn, c = i - r * bn;
-      return (xr * g.xcd_bm + r) * g.tiles_n + xc * bn + c;
-    }
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
   };
   const int Kp8 = g.Kp;  // (the int8 image's row stride)
@@ -907,24 +899,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   // the side product's fragments, column scale and bias) - loads return in issue order, so the counted waits below, which leave only the
   // TAIL's requests in flight, cover it.  TAIL: the steps behind the first (past the end of K: dropped by the buffer range check) and the
   // tables' LDS writes.
-  // The gather of the epilogue, requested EARLY (round 6): the main loop's last three LOADs request steps past the end of K - dead
-  // requests that only keep the counted waits uniform.  In the FIRST of them (step nk) waves 0 and 1 send their two activation pieces'
-  // requests to the granules instead: same instruction, same count, other descriptor / offset / LDS address - the agent-scope round trip
-  // (~3.9 k cycles, which waves 0-1 used to wait out behind the conversion pass with the other six at the barrier) passes under the last
-  // three steps.  By then (K >= 2048: > 15 steps = 10 us after the prologue's publish) every resident workgroup has published; shorter K
-  // keep the request at the epilogue.
-#ifndef LQER_XCH_EARLY_GATHER
-#define LQER_XCH_EARLY_GATHER 0  // 1: the form above (measured, round 6: the epilogue gains nothing - what waves 0-1 spend behind the
-                                   // conversion pass is the tag test's instructions, not the round trip - and the operand selects cost the
-                                   // main loop 5-6 %: 24.7 vs 23.4 us at K = 4096, profiles/r06_i8_timeline.txt); 0: requested at the epilogue
-#endif
-  const bool xg_early = LQER_XCH_EARLY_GATHER && XCH && !W8 && nk >= 16;  // (uniform)
-  const u32x4 xg_rs = make_rs((const uint8_t*)g.bout_amax, XCH ? (uint32_t)(xch_Mp / 4 * LQER_AMAX_NSEG * 8) : 0u);
-  int xg_voff[2] = {0, 0};
-  if constexpr (XCH) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) xg_voff[j] = (int)(((m0 >> 2) + 16 * wave + 8 * j + (lane >> 3)) * (LQER_AMAX_NSEG * 8)) + (lane & 7) * 16;
-  }
   auto ring_fill_head = [&]() {
     using std::integral_constant;
     if constexpr (W8D) {
@@ -1367,19 +1341,10 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       __builtin_amdgcn_sched_barrier(0);
     }
     const int ktn = __builtin_amdgcn_readfirstlane(kt + DEPTH);
-    int a_soff = ktn * I8_BK;
+    const int a_soff = ktn * I8_BK;
     const int w_soff = ktn * I8_WBLOCK;
-    uint32_t m0a0 = m0_a + slot_new * A_SLOT, m0a1 = m0a0 + 1024;
+    const uint32_t m0a0 = m0_a + slot_new * A_SLOT, m0a1 = m0a0 + 1024;
     const uint32_t m0w0 = m0_w + slot_new * W_SLOT, m0w1 = m0w0 + 1024, m0s = m0_s + slot_new * W_SLOT;
-    u32x4 ars_e = a_rs;
-    int av0_e = a_voff[0], av1_e = a_voff[1];
-    if constexpr (XCH && !W8) {
-      if (xg_early && ktn == nk && wave < 2) {  // (uniform) the step past the end of K: the granules instead of nothing
-        ars_e = xg_rs, a_soff = 0;
-        m0a0 = lds0 + G::EP_GATHER + wave * 2048, m0a1 = m0a0 + 1024;
-        av0_e = xg_voff[0], av1_e = xg_voff[1];
-      }
-    }
     i32x4 xa[4][4];  // [token tile][slice]
     u32x4 wr0, wr1;
     asm volatile(
@@ -1393,8 +1358,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
         "ds_read_b128 %[x32], %[fa2] offset:%c[aimm]+12288\n\tds_read_b128 %[x33], %[fa3] offset:%c[aimm]+12288\n\t"
         "ds_read_b128 %[wr0], %[fwa] offset:%c[wimm]\n\tds_read_b128 %[wr1], %[fwb] offset:%c[wimm]\n\t"
         "ds_read_u8 %[sv], %[fs] offset:%c[wimm]\n\t"
-        // (no cache-policy bits on these two even when they carry the gather: the CU's L1 is invalidated at the launch's start and nobody
-        // on this CU has read the granule lines since; sc0 on every activation piece cost the main loop 17 %)
+        // (no cache-policy bits on the activation pieces: sc0 on every one cost the main loop 17 %)
         "s_mov_b32 m0, %[m0a0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av0], %[ars], %[asoff] offen lds\n\t"
         "s_mov_b32 m0, %[m0a1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av1], %[ars], %[asoff] offen lds\n\t"
         "s_mov_b32 m0, %[m0w0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv0], %[wrs], %[wsoff] offen lds\n\t"
@@ -1407,8 +1371,8 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
           [x22] "=&v"(xa[2][2]), [x23] "=&v"(xa[2][3]), [x30] "=&v"(xa[3][0]), [x31] "=&v"(xa[3][1]), [x32] "=&v"(xa[3][2]),
           [x33] "=&v"(xa[3][3]), [wr0] "=&v"(wr0), [wr1] "=&v"(wr1), [sv] "=&v"(sv)
         : [fa0] "v"(fa_lo[0]), [fa1] "v"(fa_lo[1]), [fa2] "v"(fa_lo[2]), [fa3] "v"(fa_lo[3]), [aimm] "i"(A_IMM), [fwa] "v"(fw_a),
-          [fwb] "v"(fw_b), [fs] "v"(fs_addr), [wimm] "i"(SLOT * W_SLOT), [av0] "v"(av0_e), [av1] "v"(av1_e),
-          [wv0] "v"(w_voff0), [wv1] "v"(w_voff1), [sv4] "v"(s_voff), [ars] "s"(ars_e), [wrs] "s"(w_rs), [m0a0] "s"(m0a0),
+          [fwb] "v"(fw_b), [fs] "v"(fs_addr), [wimm] "i"(SLOT * W_SLOT), [av0] "v"(a_voff[0]), [av1] "v"(a_voff[1]),
+          [wv0] "v"(w_voff0), [wv1] "v"(w_voff1), [sv4] "v"(s_voff), [ars] "s"(a_rs), [wrs] "s"(w_rs), [m0a0] "s"(m0a0),
           [m0a1] "s"(m0a1), [m0w0] "s"(m0w0), [m0w1] "s"(m0w1), [m0s] "s"(m0s), [asoff] "s"(a_soff), [wsoff] "s"(w_soff),
           [wave] "s"(wave)
         : "memory", "scc");
@@ -1587,9 +1551,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     __builtin_amdgcn_sched_barrier(0);
   };
   using std::integral_constant;
-#ifndef LQER_I8_KSPLIT
-#define LQER_I8_KSPLIT 1  // 0: the token-tile split for every mode (A/B builds)
-#endif
   auto main_loop = [&](auto mode_c) {
     if constexpr (W8D) {
       // unrolled by the ring size (activation slot and register set are compile-time constants) with NO exit inside the four steps:
@@ -1626,7 +1587,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       }
     } else {
       auto hs = [&](int kt, auto slot_c, auto half_c) {
-        if constexpr (LQER_I8_KSPLIT && decltype(mode_c)::value != I8_MODE_FOLD) half_step_k(kt, slot_c, half_c, mode_c);
+        if constexpr (decltype(mode_c)::value != I8_MODE_FOLD) half_step_k(kt, slot_c, half_c, mode_c);
         else half_step(kt, slot_c, half_c, mode_c);
       };
       for (int kt = 0; kt < nk; kt += NSLOT) {  // unrolled by the ring size: slots are compile-time constants
@@ -1740,25 +1701,18 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   // 16-deep slice) pairs - rank 64 with fp16 A / B, rank 128 with 8-bit A / B -, else re-fetched from L2 for every token
   // tile.  Their latency passes under the conversion of the integer tile (below).
   // exchange: the granules of this tile's 32 row quads x every column tile (4 KiB), requested now by LDS-DMA (no registers held across
-  // the conversion pass; first read at sc0 - XCH_GATHER_AUX - or, with XCD tile blocks, sc1) into the gather region behind the xAq panel
+  // the conversion pass; first read at sc0 - XCH_GATHER_AUX) into the gather region behind the xAq panel
   // (round 6; it was activation slot 3): wave w (0, 1) brings quads 16 w .. 16 w + 15 with two requests - request j, lane l:
   // quad 8 j + l / 8, piece l % 8 (16 B = the granules of column tiles 2 p, 2 p + 1) - and reads back what it requested itself
   // (vmcnt, no barrier).  The round trip passes under the staging and the conversion.
   const int tid_e = wave * 64 + lane;
   if constexpr (XCH_OK) {
-    if (xch && wave < 2 && !xg_early) {
-      if (g.xcd_bm > 0) {  // (XCD blocks: a row band's column tiles sit on several XCDs - agent scope from the first read on)
+    if (xch && wave < 2) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(xch_rsrc, (lds_void*)(smem + G::EP_GATHER + wave * 2048 + j * 1024), 16,
-                                                   (int)(((m0 >> 2) + 16 * wave + 8 * j + (lane >> 3)) * (LQER_AMAX_NSEG * 8)) + (lane & 7) * 16, 0, 0, 16);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(xch_rsrc, (lds_void*)(smem + G::EP_GATHER + wave * 2048 + j * 1024), 16,
-                                                   (int)(((m0 >> 2) + 16 * wave + 8 * j + (lane >> 3)) * (LQER_AMAX_NSEG * 8)) + (lane & 7) * 16, 0, 0,
-                                                   XCH_GATHER_AUX);
-      }
+      for (int j = 0; j < 2; ++j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xch_rsrc, (lds_void*)(smem + G::EP_GATHER + wave * 2048 + j * 1024), 16,
+                                                 (int)(((m0 >> 2) + 16 * wave + 8 * j + (lane >> 3)) * (LQER_AMAX_NSEG * 8)) + (lane & 7) * 16, 0, 0,
+                                                 XCH_GATHER_AUX);
     }
   }
   bf16x8 sb[LOWRANK ? 8 : 1];
@@ -2144,17 +2098,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
 template <int DT, int NT>
 static int launch(GemmArgs g, bool lowrank, int bout, hipStream_t st);
 
-// LQER_TUNE_XCD_BLOCK(t) for the int8 kernel: t token tiles per XCD block, applied only where the tile grid divides - every XCD gets
-// nt / 8 tiles (nt % 8 == 0), a block is t x (nt / 8 / t) tiles, blocks tile the grid (tiles_m % t == 0, tiles_n % bn == 0) and there
-// are exactly 8 of them.  0 = rows of weight tiles (the default map).
-static int i8_xcd_block(const GemmArgs& g, int nt) {
-  const int t = (g.tuning >> 4) & 0x3f;
-  if (t <= 0 || nt % 8 != 0 || (nt / 8) % t != 0 || g.tiles_m % t != 0) return 0;
-  const int bn = (nt / 8) / t;
-  if (bn <= 0 || g.tiles_n % bn != 0 || (g.tiles_m / t) * (g.tiles_n / bn) != 8) return 0;
-  return t;
-}
-
 // 8-bit weight codes: 128-row tiles with the codes straight into registers, or 256-row tiles with a half-step weight ring in LDS
 template <int DT, int NT>
 static int launch_w8(GemmArgs g, bool lowrank, int bout, hipStream_t st) {
@@ -2164,7 +2107,6 @@ static int launch_w8(GemmArgs g, bool lowrank, int bout, hipStream_t st) {
   constexpr int CUS = 256;
   const int nt_all = g.tiles_m * g.tiles_n;
   const unsigned grid = (unsigned)(nt_all < CUS ? nt_all : CUS);
-  g.xcd_bm = i8_xcd_block(g, nt_all);
 #define LQER_I8_LAUNCH8(LR, BO)                                                                   \
   do {                                                                                            \
     static LdsLimitOnce lds_once;                                                                 \
@@ -2199,7 +2141,6 @@ static int launch(GemmArgs g, bool lowrank, int bout, hipStream_t st) {
   constexpr int CUS = 256;
   const int nt_all = g.tiles_m * g.tiles_n;
   const unsigned grid = (unsigned)(nt_all < CUS ? nt_all : CUS);
-  g.xcd_bm = i8_xcd_block(g, nt_all);
 #define LQER_I8_LAUNCH(LR, BO)                                                                    \
   do {                                                                                            \
     if (g.i8_shift) {                                                                             \

@@ -910,16 +910,8 @@ __global__ __launch_bounds__(QX_K) void k_quant_xa16(const void* __restrict__ x,
         }
       }
       uint4* dst = (uint4*)(xq + m * Kp + k0);   // rows up to the padded M are allocated
-#ifdef LQER_XQ_STORE_MODS  // cache-policy experiment (tools/ab_step.py): e.g. -DLQER_XQ_STORE_MODS='"nt"'
-      {
-        const u32x4 lo = {w[0], w[1], w[2], w[3]}, hi = {w[4], w[5], w[6], w[7]};
-        asm volatile("global_store_dwordx4 %0, %1, off " LQER_XQ_STORE_MODS "\n\tglobal_store_dwordx4 %0, %2, off offset:16 " LQER_XQ_STORE_MODS
-                     ::"v"(dst), "v"(lo), "v"(hi) : "memory");
-      }
-#else
       dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
       dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-#endif
     }
     *(uint4*)(slab + qx_swz(row, 2 * seg)) = make_uint4(w[0], w[1], w[2], w[3]);
     *(uint4*)(slab + qx_swz(row, 2 * seg + 1)) = make_uint4(w[4], w[5], w[6], w[7]);
@@ -998,12 +990,7 @@ int quant_xa_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int6
   const int G = La / 4;
   if (rp % La != 0 || La % 4 != 0 || (G & (G - 1)) != 0 || G > 64) return LQER_E_UNSUPPORTED;
   if (M == 0) return LQER_OK;
-#ifndef LQER_NO_QXA128
-#ifdef LQER_QXA128_ALL  // experiment: every rank through the tile kernel (rank 32: one rank tile, three of four waves per row group idle in the MFMA part)
-  if (rp % 32 == 0 && M >= 512 && a_limbs == 1 && dtype != LQER_F32 && K % 8 == 0 && (uintptr_t)x % 16 == 0 && (ldx * 2) % 16 == 0) {
-#else
   if (rp > 64) {
-#endif
     // rank 65..128: 128-row tiles, both MFMA operands through LDS (xal::k_quant_xa128), the plan of the LDS-staged side GEMM
     const int64_t ldx_b = ldx * 2;
     if (rp % 32 != 0 || a_limbs != 1 || M < 512 || dtype == LQER_F32 || K % 8 != 0 || (uintptr_t)x % 16 != 0 || ldx_b % 16 != 0 ||
@@ -1021,15 +1008,8 @@ int quant_xa_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int6
     const size_t need = (size_t)nch * plan.row_groups * XA_ROWS * rp * sizeof(float);
     if (!scratch || scratch_bytes < need) return LQER_E_UNSUPPORTED;
     const int nt = rp / 32;
-#ifdef LQER_QXA128_ALL
-#define QX128(DT) (nt == 1 ? xal::launch_q<DT, 1>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st) \
-                 : nt == 2 ? xal::launch_q<DT, 2>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st) \
-                 : nt == 3 ? xal::launch_q<DT, 3>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st) \
-                           : xal::launch_q<DT, 4>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st))
-#else
 #define QX128(DT) (nt == 3 ? xal::launch_q<DT, 3>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st) \
                            : xal::launch_q<DT, 4>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st))
-#endif
     if (dtype == LQER_F16) QX128(LQER_F16); else QX128(LQER_BF16);
 #undef QX128
     if (!xaq) return check_launch("quantize_act_xa");
@@ -1046,9 +1026,6 @@ int quant_xa_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int6
     }
     return check_launch("quantize_act_xa");
   }
-#else
-  if (rp > 64) return LQER_E_UNSUPPORTED;
-#endif
   XaPlan plan;
   plan.row_groups = (int)((M + XA_ROWS - 1) / XA_ROWS);
   plan.nchunk = (int)((Kp + QX_K - 1) / QX_K);
@@ -1121,7 +1098,6 @@ int lowrank_xa_dispatch(const bf16_t* xq, int64_t M, int64_t K, int x_limbs, con
     return LQER_E_WORKSPACE;
   }
   const int nt = (rp + 31) / 32;
-#ifndef LQER_XA_NO_LDS
   bool staged = false;
   XaPlan plan_l = plan;
   // the LDS-staged kernel (xal): the int8 route's images at any rank tile count up to 2; the bf16 image x one bf16 limb of A^T
@@ -1147,10 +1123,6 @@ int lowrank_xa_dispatch(const bf16_t* xq, int64_t M, int64_t K, int x_limbs, con
     }
     staged = true;
   }
-#else
-  const bool staged = false;
-  const XaPlan plan_l = plan;
-#endif
   // row groups per wave: two while RG x NT accumulator tiles + two activation windows fit the register file
   const int rgw = nt <= 4 ? 2 : 1;
   const int wave_rows = (plan.row_groups + rgw - 1) / rgw;

@@ -309,7 +309,6 @@ static int launch_quant(const void* x, int64_t rows, int64_t cols, int64_t ld, c
     // the int8 image alone, from an aligned 16-bit tensor: one wave per row, the row in registers (k_quant_row8)
     bool done = false;
     if constexpr (DT != LQER_F32) {
-#ifndef LQER_NO_QUANT_ROW8
       if (o.xq8 && !o.xq && !o.deq && !o.codes && !o.exps && vec0 && cols % 8 == 0 && q.mbits <= 7) {
         const unsigned grid = (unsigned)((rows + 3) / 4);
         const int64_t nch_p = o.cols_p8 / 8;
@@ -321,7 +320,6 @@ static int launch_quant(const void* x, int64_t rows, int64_t cols, int64_t ld, c
           done = true;
         }
       }
-#endif
     }
     if (!done) k_quant_row<DT><<<dim3((unsigned)rows), 256, 0, st>>>(x, rows, cols, ld, q, o, vec0);
   } else if (q.block == 16) {

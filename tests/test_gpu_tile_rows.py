@@ -70,10 +70,9 @@ def test_64_row_tiles_equal_128_row_tiles_and_the_oracle(lq, M, K, N, r, bias, b
     assert err <= (4e-3 if dtype == torch.bfloat16 else 1e-3), err
 
 
-def test_forced_64_row_tiles_and_xcd_blocks_give_the_same_bits(lq):
-    """Round-3 experiment hooks of the 128-row kernel at the C2 shape (16 x 16 tiles, one per CU): 64-row tiles forced at
-    M = 2048 (two workgroups per CU, 69.6 KB of LDS each) and XCD-local tile blocks (8 / 4 / 16 token tiles per XCD) are pure
-    re-mappings of the same arithmetic - bit-identical outputs."""
+def test_forced_64_row_tiles_give_the_same_bits(lq):
+    """Round-3 experiment hook of the 128-row kernel at the C2 shape (16 x 16 tiles, one per CU): 64-row tiles forced at
+    M = 2048 (two workgroups per CU, 69.6 KB of LDS each) are a pure re-mapping of the same arithmetic - bit-identical outputs."""
     from bench import MXINT_Q, make_case
     from lqer_amd import _lib
 
@@ -86,9 +85,6 @@ def test_forced_64_row_tiles_and_xcd_blocks_give_the_same_bits(lq):
     y0 = mod(xd).clone()
     mod.tuning = _lib.TUNE_TILE_ROWS_64
     assert torch.equal(mod(xd), y0)
-    for bm in (8, 4, 16, 3):  # (3 does not divide the grid: ignored)
-        mod.tuning = _lib.tune_xcd_block(bm)
-        assert torch.equal(mod(xd), y0), bm
     mod.tuning = 0
 
 
@@ -102,11 +98,10 @@ PARTIAL_CASES = [  # M, K, N, rank, bias, B_out, dtype
 
 
 @pytest.mark.parametrize("M,K,N,r,bias,bout,dtype", PARTIAL_CASES)
-def test_gemm_summing_the_partial_tiles_equals_the_reduce_launch(lq, M, K, N, r, bias, bout, dtype):
-    """LQER_TUNE_XA_REDUCE_IN_GEMM: lqer_linear_forward on 128-row tiles skips k_xa_reduce4 - the GEMM's workgroups sum the
-    split-K partial tiles of x A in ascending chunk order and apply A_out on the way into the side product's LDS stage
-    (k_lqer_gemm XAPART) - the same arithmetic item by item, so y must carry the bits of the default three-launch route.
-    (Selectable, not the default: measured slower, include/lqer_hip.h.)"""
+def test_128_row_tiles_behind_the_reduce_launch_match_the_oracle(lq, M, K, N, r, bias, bout, dtype):
+    """lqer_linear_forward on 128-row tiles: quantizer, split-K partial tiles of x A summed by k_xa_reduce4 in ascending chunk
+    order, then the GEMM - many chunks, rank 64 (two items per thread), B_out pass-through.  The partial-tile hand-over at these
+    token counts is retired: lqer_tile_partials says 0."""
     from bench import MXINT_Q, make_case
     from lqer_amd import _lib
 
@@ -122,14 +117,11 @@ def test_gemm_summing_the_partial_tiles_equals_the_reduce_launch(lq, M, K, N, r,
     mod = mod.to(DEV).to(dtype)
     xd = x.to(dtype).to(DEV)
     mod.tuning = _lib.TUNE_TILE_ROWS_128
+    assert _lib.lib().lqer_tile_partials(mod._desc(), M, _lib.F16 if dtype == torch.float16 else _lib.BF16) == 0
     y3 = mod(xd).clone()
-    mod.tuning = _lib.TUNE_TILE_ROWS_128 | _lib.TUNE_XA_REDUCE_IN_GEMM
-    assert _lib.lib().lqer_tile_partials(mod._desc(), M, _lib.F16 if dtype == torch.float16 else _lib.BF16) == 1
-    y2 = mod(xd).clone()
-    assert torch.equal(y2, y3)
     h = lambda t: None if t is None else t.to(dtype).float()
     ref = O.lqer_linear_forward(h(x), h(W), h(case[4]) if bias else None, h(A), h(B), qc)
-    err = float((y2.float().cpu() - ref).norm() / ref.norm())
+    err = float((y3.float().cpu() - ref).norm() / ref.norm())
     assert err <= (4e-3 if dtype == torch.bfloat16 else 1e-3), err
 
 
