@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LQER_ABI_VERSION 13
+#define LQER_ABI_VERSION 14
 
 /* error codes */
 #define LQER_OK 0
@@ -66,6 +66,22 @@ extern "C" {
                         w_quantizer: signed, width 2..4 - the codes -8..7 travel as two's-complement nibbles in the same panels
                         (lqer_pack_weight_mxint; the 128-row tile kernel at every token count); unsigned or wider integer
                         weights: LQER_E_UNSUPPORTED */
+
+#define LQER_Q_MINIFLOAT 5 /* "minifloat" (reference quantizers/minifloat.py:120-182, minifloat_ieee): per element, in fp32,
+                        e = clamp(floor(log2(|x| + 1e-9)), -exp_bias, 2^exp_width-1-exp_bias) with torch's correctly rounded log2;
+                        m = width-exp_width-1 mantissa bits; normal (e != -exp_bias): S = clamp(rne(|x| 2^(m-e) - 2^m), 0, 2^m-1),
+                        v = 2^e (1 + S 2^-m); subnormal (e == -exp_bias): S = clamp(rne(|x| 2^(m-1-e)), 0, 2^m-1),
+                        v = 2^(e+1) S 2^-m; result sign(x) v (no rounding into the next binade, no inf / NaN: the largest value is
+                        (2 - 2^-m) 2^(2^exp_width-1-exp_bias)); |x| <= 1e-8 is kept as is (packed and bf16 images: 0).  Fields:
+                        width 2..8; exp_width 1..width-1; exp_bias = the resolved bias (reference default 2^(exp_width-1)-1),
+                        such that every non-zero value is a normal bf16 number; block is ignored.  Implemented for the x, b,
+                        A_out and B_out quantizers (elementwise: no maxima, no pre-pass - B_out in the 128-row tile kernel's
+                        prologue at every token count), in lqer_quantize_mxint (deq, and as codes the minifloat bit pattern
+                        sign | exponent | mantissa; exps must be NULL) and as w_quantizer of width 2..4: the nibble holds
+                        sign << 3 | exponent << m | mantissa, expanded through a per-format 8-entry e4m3 table times one
+                        constant power-of-two scale (lqer_pack_weight_mxint; the 128-row tile kernel at every token count).
+                        Minifloat weights of 5..8 bits, minifloat on the int8 route (LQER_Q_MXINT_I8) and 2-D weight tiles:
+                        LQER_E_UNSUPPORTED */
 
 /* Geometry of the packed operands (fixed by the kernels; exported so callers can size buffers). */
 #define LQER_K_ALIGN 64     /* K is zero-padded to a multiple of this                        */

@@ -28,6 +28,38 @@ int check_launch(const char* what) {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// a minifloat format the HIP path serves: width 2..max_width, exp_width 1..width-1, every non-zero value a normal bf16 number (the bf16
+// images are exact, the MFMAs see no subnormal operand); weights also need the e4m3 table of their 4-bit codes (mf_e4m3_table)
+static bool minifloat_fmt_ok(const lqer_qfmt_t& f, const char* name, int max_width) {
+  if (f.width < 2 || f.width > max_width) {
+    set_error("%s: minifloat width %d outside [2,%d]%s", name, f.width, max_width,
+              max_width == 4 ? " (minifloat weights of 5..8 bits need an 8-bit code image: not implemented)" : "");
+    return false;
+  }
+  if (f.exp_width < 1 || f.exp_width > f.width - 1) {
+    set_error("%s: minifloat exponent_width %d outside [1,%d] (width %d: mantissa bits = width - exponent_width - 1 >= 0)", name,
+              f.exp_width, f.width - 1, f.width);
+    return false;
+  }
+  const int mbits = f.width - f.exp_width - 1;
+  const int emax = (1 << f.exp_width) - 1 - f.exp_bias, lowest = 1 - f.exp_bias - mbits;  // exponents of the largest / smallest value
+  if (f.exp_bias < -1000 || f.exp_bias > 1000 || emax > 127 || lowest < -126) {
+    set_error("%s: minifloat exponent_bias %d: the values span 2^%d .. 2^%d, outside the normal bf16 range 2^-126 .. 2^127", name,
+              f.exp_bias, lowest, emax);
+    return false;
+  }
+  if (max_width == 4) {
+    uint32_t lut[2];
+    int s;
+    if (!mf_e4m3_table(f, lut, &s)) {
+      set_error("%s: minifloat(%d, %d, %d): its values are not e4m3 numbers times one power of two", name, f.width, f.exp_width,
+                f.exp_bias);
+      return false;
+    }
+  }
+  return true;
+}
+
 static bool fmt_ok(const lqer_qfmt_t* f, const char* name, int max_width) {
   if (!f) {
     set_error("%s: null format", name);
@@ -56,6 +88,16 @@ static bool fmt_ok(const lqer_qfmt_t* f, const char* name, int max_width) {
       return false;
     }
     return true;
+  }
+  if (f->kind == LQER_Q_MINIFLOAT) {  // width, exp_width, exp_bias = the resolved bias (include/lqer_hip.h)
+    const bool role_ok = !strcmp(name, "x_quantizer") || !strcmp(name, "b_quantizer") || !strcmp(name, "A_out_quantizer") ||
+                         !strcmp(name, "B_out_quantizer") || !strcmp(name, "quantize_mxint") || !strcmp(name, "w_quantizer") ||
+                         !strncmp(name, "matmul ", 7);
+    if (!role_ok) {
+      set_error("%s: the minifloat quantizer is not implemented in this role", name);
+      return false;
+    }
+    return minifloat_fmt_ok(*f, name, !strcmp(name, "w_quantizer") ? 4 : 8);
   }
   if (f->kind != LQER_Q_MXINT && f->kind != LQER_Q_MXINT_I8) {
     set_error("%s: quantizer kind %d is not implemented on the HIP path", name, f->kind);
@@ -213,8 +255,12 @@ int lqer_quantize_mxint(const void* x, int dtype, int64_t rows, int64_t cols, in
     return LQER_E_INVALID;
   }
   if (!fmt_ok(fmt, "quantize_mxint", 24)) return LQER_E_UNSUPPORTED;
-  if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT) {
-    set_error("quantize_mxint: format is neither block_fp nor integer");
+  if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT && fmt->kind != LQER_Q_MINIFLOAT) {
+    set_error("quantize_mxint: format is neither block_fp, integer nor minifloat");
+    return LQER_E_INVALID;
+  }
+  if (fmt->kind == LQER_Q_MINIFLOAT && exps) {
+    set_error("quantize_mxint: a minifloat format has no block exponents (exps must be NULL)");
     return LQER_E_INVALID;
   }
   if (codes && fmt->width > 8) {
@@ -259,8 +305,8 @@ int lqer_quantize_act_mxint(const void* x, int dtype, int64_t M, int64_t K, int6
     return LQER_E_INVALID;
   }
   if (!fmt_ok(fmt, "x_quantizer", 9)) return LQER_E_UNSUPPORTED;
-  if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT) {
-    set_error("x_quantizer: only block_fp and integer activations have a bf16 image on the HIP path");
+  if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT && fmt->kind != LQER_Q_MINIFLOAT) {
+    set_error("x_quantizer: only block_fp, integer and minifloat activations have a bf16 image on the HIP path");
     return LQER_E_UNSUPPORTED;
   }
   QP q = make_qp(*fmt);
@@ -376,9 +422,18 @@ int lqer_pack_weight_mxint(const void* W, int dtype, int64_t N, int64_t K, int64
     return LQER_E_INVALID;
   }
   if (!fmt_ok(fmt, "w_quantizer", 8)) return LQER_E_UNSUPPORTED;
-  if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT) {
-    set_error("w_quantizer: only block_fp and integer weights can be packed");
+  if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT && fmt->kind != LQER_Q_MINIFLOAT) {
+    set_error("w_quantizer: only block_fp, integer and minifloat weights can be packed");
     return LQER_E_UNSUPPORTED;
+  }
+  if (fmt->kind == LQER_Q_MINIFLOAT) {  // one scale byte for the whole image: the s of the table the GEMM will expand with
+    uint32_t lut[2];
+    int s;
+    if (!mf_e4m3_table(*fmt, lut, &s)) {
+      set_error("w_quantizer: minifloat(%d, %d, %d) has no e4m3 table", fmt->width, fmt->exp_width, fmt->exp_bias);
+      return LQER_E_UNSUPPORTED;
+    }
+    return pack_weight_mf_dispatch(W, dtype, N, K, ldw, make_qp(*fmt), 127 + s, w_packed, (hipStream_t)stream);
   }
   return pack_weight_dispatch(W, dtype, N, K, ldw, make_qp(*fmt), 1, w_packed, scratch, (hipStream_t)stream);
 }
@@ -402,6 +457,12 @@ int lqer_unpack_weight_mxint(const void* w_packed, int64_t N, int64_t K, const l
   if (!w_packed || !w_f32 || !fmt || N <= 0 || K <= 0) {
     set_error("unpack_weight: bad argument");
     return LQER_E_INVALID;
+  }
+  if (fmt->kind == LQER_Q_MINIFLOAT) {  // (the image's own e4m3 table and scale bytes, as the GEMM reads them)
+    uint32_t lut[2];
+    int s;
+    if (!fmt_ok(fmt, "w_quantizer", 8) || !mf_e4m3_table(*fmt, lut, &s)) return LQER_E_UNSUPPORTED;
+    return unpack_weight_mf_dispatch(w_packed, N, K, lut, w_f32, (hipStream_t)stream);
   }
   return unpack_weight_dispatch(w_packed, N, K, fmt->width - 1, fmt->kind == LQER_Q_INT, w_f32, (hipStream_t)stream);
 }
@@ -611,6 +672,21 @@ static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, Ge
   g.w_mbits = w_limbs(d) > 1 ? 3 : d->w_fmt.width - 1;
   g.tuning = d->tuning;
   g.w_twos = d->w_fmt.kind == LQER_Q_INT ? 1 : 0;
+  if (d->w_fmt.kind == LQER_Q_MINIFLOAT) {  // minifloat weights: the nibble's magnitude code through the format's e4m3 table
+    int s;
+    if (x_is_f16(d) || x_is_i8(d)) {
+      set_error("linear_gemm: minifloat weights run the bf16 128-row tile kernel only (x_quantizer %s)",
+                x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");
+      return LQER_E_UNSUPPORTED;
+    }
+    if (!mf_e4m3_table(d->w_fmt, g.w_lut, &s)) return LQER_E_UNSUPPORTED;
+    g.w_mf = 1;
+  }
+  if (lowrank && d->b_out_fmt.kind == LQER_Q_MINIFLOAT && (x_is_i8(d) || x_is_f16(d))) {
+    set_error("linear_gemm: a minifloat B_out runs on the bf16 128-row tile kernel only (x_quantizer %s)",
+              x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH with width 11" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");
+    return LQER_E_UNSUPPORTED;
+  }
   if (lowrank) g.bout = make_qp(d->b_out_fmt);
   if (x_is_i8(d)) {
     if (!i8_formats_ok(d)) return LQER_E_UNSUPPORTED;
@@ -942,8 +1018,10 @@ int lqer_matmul_q(const void* x, const void* y, void* out, int dtype, int64_t ba
   }
   if (!fmt_ok(x_fmt, "matmul x_quantizer", 8) || !fmt_ok(y_fmt, "matmul w_quantizer", 8)) return LQER_E_UNSUPPORTED;
   auto blk_ok = [](const lqer_qfmt_t* f, int64_t cols) { return f->block <= 0 || f->block >= cols || f->block % 16 == 0; };
-  if (x_fmt->kind != LQER_Q_MXINT || y_fmt->kind != LQER_Q_MXINT || !blk_ok(x_fmt, K) || !blk_ok(y_fmt, S2)) {
-    set_error("matmul_q: both quantizers must be block_fp with blocks of 16 n elements, or whole rows, along the last dim (got kinds %d / %d, "
+  // (minifloat operands: elementwise - block -1, the standalone quantizer's bf16 image)
+  auto kind_ok = [](const lqer_qfmt_t* f) { return f->kind == LQER_Q_MXINT || f->kind == LQER_Q_MINIFLOAT; };
+  if (!kind_ok(x_fmt) || !kind_ok(y_fmt) || !blk_ok(x_fmt, K) || !blk_ok(y_fmt, S2)) {
+    set_error("matmul_q: both quantizers must be block_fp with blocks of 16 n elements, or whole rows, along the last dim, or minifloat (got kinds %d / %d, "
               "blocks %d / %d)", x_fmt->kind, y_fmt->kind, x_fmt->block, y_fmt->block);
     return LQER_E_UNSUPPORTED;
   }

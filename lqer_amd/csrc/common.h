@@ -47,6 +47,11 @@ __host__ inline QP make_qp(const lqer_qfmt_t& f) {
     q.mneg = is_signed ? (float)(1 << (f.width - 1)) : 0.0f;
     q.eps = 0.0f, q.tiny = -1.0f;
   }
+  if (f.kind == LQER_Q_MINIFLOAT) {  // per-element exponent in [emin, emax] = [-bias, 2^exp_width-1-bias], mbits mantissa bits
+    q.mbits = f.width - f.exp_width - 1;
+    q.block = -1;
+    q.mmax = q.mneg = (float)((1 << q.mbits) - 1);  // the largest mantissa field S
+  }
   return q;
 }
 
@@ -133,6 +138,80 @@ __device__ __forceinline__ int ceil_log2_rule(float amax) {
   const uint32_t tw = p < 4 ? 0x02010000u : 0x16160B05u;
   const int slack = (int)((tw >> ((p & 3) * 8)) & 0xffu);
   return mant > slack ? k + 1 : k;
+}
+
+// e = torch.floor(torch.log2(v)) in fp32 (the minifloat quantizer, minifloat.py:159): for v = 2^K (1 - d 2^-24) just below a power of
+// two the correctly rounded log2 is K itself while d <= floor(2^q ln 2), q = floor(log2 |K|) (one less for K = +2^j) - the floor then
+// reads K, not K - 1 (pinned by tests/golden/minifloat.npz; a power of two or anything else: its exponent field).  v normal, > 0.
+__device__ __forceinline__ int floor_log2_rule(float v) {
+  const uint32_t bits = __float_as_uint(v);
+  const int kl = (int)((bits >> 23) & 0xff) - 127;
+  const int d = (1 << 23) - (int)(bits & 0x7fffffu);
+  const int K = kl + 1, aK = K < 0 ? -K : K;
+  const int q = 31 - __clz(aK | 1) - ((K > 0 && (K & (K - 1)) == 0) ? 1 : 0);
+  const int slack = q < 0 ? 0 : (int)ldexpf(0.6931472f, q);
+  return d <= slack ? K : kl;
+}
+
+// The minifloat quantizer of one element (reference minifloat.py:120-182, minifloat_ieee; QP of LQER_Q_MINIFLOAT: mbits mantissa bits,
+// exponents [emin, emax] with emin = -bias, mmax = 2^mbits - 1):
+//   e = clamp(floor(log2(|x| + 1e-9)), emin, emax);
+//   normal (e != emin):  S = clamp(rne(|x| 2^(mbits-e) - 2^mbits), 0, mmax), v = 2^e (1 + S 2^-mbits)
+//   subnormal (e = emin): S = clamp(rne(|x| 2^(mbits-1-e)), 0, mmax),       v = 2^(e+1) S 2^-mbits
+// -> sign(x) v; |x| <= 1e-8 is kept as is (the caller's packed images flush it).  Power-of-two scalings are exact, so this is the
+// reference's fp32 arithmetic (value / 2^e * shift - shift) step for step.  The magnitude's code is (E << mbits) | S with E = e - emin for
+// normal values, 0 for subnormal ones: monotonic in the value (the packed weight's nibble, minifloat_decode).
+__device__ __forceinline__ float minifloat_mag(float a, const QP& q, int* code = nullptr) {
+  int e = floor_log2_rule(a + 1e-9f);
+  e = e < q.emin ? q.emin : (e > q.emax ? q.emax : e);
+  const bool sub = e == q.emin;
+  const float shift = (float)(1 << q.mbits);
+  const float t = ldexpf(a, q.mbits - e - (sub ? 1 : 0));
+  const float S = __builtin_amdgcn_fmed3f(rintf(sub ? t : t - shift), 0.0f, q.mmax);
+  if (code) *code = ((sub ? 0 : e - q.emin) << q.mbits) | (int)S;
+  return ldexpf(sub ? 2.0f * S : shift + S, e - q.mbits);
+}
+__device__ __forceinline__ float minifloat_value(float x, const QP& q) {
+  const float a = fabsf(x);
+  return a <= 1e-8f ? x + 0.0f : copysignf(minifloat_mag(a, q), x);  // (x + 0: the reference's 0 v + 1 x turns -0 into +0)
+}
+// value of a magnitude code (E << mbits) | S: the inverse of minifloat_mag's code
+__host__ __device__ inline float minifloat_decode(int code, const QP& q) {
+  const int E = code >> q.mbits, S = code & ((1 << q.mbits) - 1);
+  return E == 0 ? ldexpf((float)(2 * S), q.emin - q.mbits) : ldexpf((float)((1 << q.mbits) + S), q.emin + E - q.mbits);
+}
+
+// Minifloat weights of 2..4 bits: the 3-bit magnitude code c = (E << mbits) | S of a nibble -> the e4m3 byte of decode(c) / 2^s, the
+// eight bytes as the two dwords of a v_perm_b32 table (expand_frag_lut), s = the one scale every exponent byte of the panels carries
+// (byte 127 + s).  s puts the largest value in e4m3's binade 7 (never beyond -126); false when some value is no e4m3 number then.
+__host__ inline bool mf_e4m3_table(const lqer_qfmt_t& f, uint32_t (&lut)[2], int* s_out) {
+  const QP q = make_qp(f);
+  int s = q.emax - 7;
+  s = s < -126 ? -126 : s;
+  lut[0] = lut[1] = 0;
+  for (int c = 0; c < 8; ++c) {
+    if (c >= (1 << (f.width - 1))) continue;  // (narrower formats: codes beyond theirs never occur)
+    const float u = ldexpf(minifloat_decode(c, q), -s);
+    uint32_t b = 0;
+    if (u != 0.0f) {
+      const int E = ilogbf(u);
+      int mant;
+      if (E >= -6) {
+        const float m8 = ldexpf(u, 3 - E) - 8.0f;
+        mant = (int)m8;
+        if ((float)mant != m8 || E + 7 > 15 || (E + 7 == 15 && mant == 7)) return false;
+        b = (uint32_t)((E + 7) << 3 | mant);
+      } else {
+        const float m9 = ldexpf(u, 9);
+        mant = (int)m9;
+        if ((float)mant != m9 || mant < 1 || mant > 7) return false;
+        b = (uint32_t)mant;
+      }
+    }
+    lut[c >> 2] |= b << (8 * (c & 3));
+  }
+  *s_out = s;
+  return true;
 }
 
 __device__ __forceinline__ int block_exponent(float amax, const QP& q) {
@@ -327,6 +406,24 @@ __device__ __forceinline__ bf16x8 expand_frag(uint32_t word, uint32_t scale_bits
   return __builtin_bit_cast(bf16x8, r);
 }
 
+
+// Minifloat nibbles (w_quantizer = minifloat, 2..4 bits: sign << 3 | magnitude code, include/lqer_hip.h): expand_frag with the format's
+// own 8-entry e4m3 table (mf_e4m3_table: two dwords, kernel arguments) in place of the integers 0..7; the exponent bytes carry the
+// format's one scale 2^s.  14 vector instructions per 8 weights, as expand_frag; every step exact.
+__device__ __forceinline__ bf16x8 expand_frag_lut(uint32_t word, uint32_t scale_bits, uint32_t lut_lo, uint32_t lut_hi) {
+  const float scale = __uint_as_float(scale_bits);
+  const uint32_t t = word >> 4;
+  uint32_t fe = __builtin_amdgcn_perm(lut_hi, lut_lo, word & 0x07070707u);  // k 0..3
+  uint32_t fo = __builtin_amdgcn_perm(lut_hi, lut_lo, t & 0x07070707u);     // k 4..7
+  fe |= (word << 4) & 0x80808080u;
+  fo |= word & 0x80808080u;
+  u32x4 r;
+  r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fe, scale, false));
+  r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fe, scale, true));
+  r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fo, scale, false));
+  r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fo, scale, true));
+  return __builtin_bit_cast(bf16x8, r);
+}
 
 // Two's-complement nibbles (the `integer` weight quantizer: codes -8 .. 7, reference quantizers/integer.py:37-40): the e4m3 byte
 // comes from one of two 8-entry tables indexed by the low three bits - values 0..7, or -8..-1 with the sign baked in - chosen per
@@ -572,6 +669,10 @@ struct GemmArgs {
   // (gemm_w4a8_i8.hip "exchange"); xch_nonce = the host part of the tag
   int bout_xch;
   uint32_t xch_nonce;
+  // minifloat weights (w_quantizer = minifloat, 2..4 bits): the 128-row tile kernel's table expand (expand_frag_lut), w_lut = the
+  // format's e4m3 table of the eight magnitude codes (mf_e4m3_table)
+  int w_mf;
+  uint32_t w_lut[2];
 };
 
 int quantize_dispatch(const void* x, int dtype, int64_t rows, int64_t cols, int64_t ld, const QP& q,
@@ -581,6 +682,9 @@ int quantize_tiles_dispatch(const void* x, int dtype, int64_t batches, int64_t r
 int pack_weight_dispatch(const void* W, int dtype, int64_t N, int64_t K, int64_t ld, const QP& q, int64_t block_rows, void* out,
                          void* scratch, hipStream_t st);
 int unpack_weight_dispatch(const void* in, int64_t N, int64_t K, int mbits, bool twos, float* out, hipStream_t st);
+int pack_weight_mf_dispatch(const void* W, int dtype, int64_t N, int64_t K, int64_t ld, const QP& q, int scale_byte, void* out,
+                            hipStream_t st);
+int unpack_weight_mf_dispatch(const void* in, int64_t N, int64_t K, const uint32_t (&lut)[2], float* out, hipStream_t st);
 int pack_lowrank_dispatch(const void* A, const void* B, int dtype, int64_t K, int64_t N, int64_t r, void* a_t,
                           void* b_t, int32_t* flags, hipStream_t st);
 int bias_passthrough_dispatch(const void* b, int dtype, int64_t N, float* out, hipStream_t st);

@@ -141,7 +141,9 @@ __device__ unsigned long long* g_stamp_buf = nullptr;  // diagnostic builds only
 // MFMAs (even piece: a block's maximum, exponent and scale factors; odd piece: its eight values), and sp is added behind the last
 // k-step - as gemm_smallm.hip and decode1.hip always did.  Same formula (the scale exponent clamped to normal floats, exact while
 // |x| <= 1e-8 passes through: gemm_w4a8_i8.hip's epilogue); blocks of 16, clamps up to 2^22 and K >= 1024 (launch_gemm).
-template <int DT, bool LOWRANK, int BOUT, bool STAGED = false, int MT = 4, bool WTWOS = false, bool DEFER = false>
+// WMF: the packed weight holds minifloat codes (w_quantizer = minifloat, 2..4 bits): the magnitude code indexes the format's e4m3 table
+// (g.w_lut, expand_frag_lut) instead of the integer one.  BOUT 3: a minifloat B_out, elementwise (minifloat_value) in the prologue.
+template <int DT, bool LOWRANK, int BOUT, bool STAGED = false, int MT = 4, bool WTWOS = false, bool DEFER = false, bool WMF = false>
 __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   static_assert(MT == 4 || MT == 2, "128- or 64-row tiles");
   static_assert(!DEFER || (LOWRANK && BOUT == 1 && MT == 4), "deferred B_out: blocks of 16 on 128-row tiles");
@@ -355,7 +357,12 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 #ifdef LQER_CLOCKPROBE
     asm volatile("s_waitcnt vmcnt(6)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cp_rq)::"memory");  // side operands landed, MFMAs issued
 #endif
-    if constexpr (BOUT != 0 && !DEFER) {
+    if constexpr (BOUT == 3) {  // minifloat: per element, no maxima
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[i][k] = minifloat_value(acc[i][k], g.bout);
+    } else if constexpr (BOUT != 0 && !DEFER) {
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -546,8 +553,9 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
           : "memory", "scc");
     }
     STAMP(1);  // LDS reads + DMA issue + waits
-    auto expand = [](uint32_t word, uint32_t scale_bits) {
-      if constexpr (WTWOS) return expand_frag_twos(word, scale_bits);
+    auto expand = [&](uint32_t word, uint32_t scale_bits) {
+      if constexpr (WMF) return expand_frag_lut(word, scale_bits, g.w_lut[0], g.w_lut[1]);
+      else if constexpr (WTWOS) return expand_frag_twos(word, scale_bits);
       else return expand_frag_t<XF16>(word, scale_bits);
     };
     bf16x8 wb_first = expand(wr[0], (we & 0xffu) << 23);
@@ -949,6 +957,33 @@ static int launch_gemm(const GemmArgs& g, bool lowrank, int bout, hipStream_t st
 #define LQER_STAGE_MIN 32
 #endif
   const bool staged = lowrank && g.rp * g.b_limbs > LQER_STAGE_MIN;  // more than two 16-deep slices of side product
+  if (g.w_mf || bout == 3) {  // minifloat weights and / or B_out: 128-row tiles, one instantiation per (element type, side path, B_out)
+    if constexpr (DT == LQER_F16X) {
+      set_error("linear_gemm: minifloat weights and B_out have no fp16 main loop (pass-through fp16 activations take the limb route)");
+      return LQER_E_UNSUPPORTED;
+    } else {
+#define LQER_GEMM_LAUNCH_MF(LR, BO, ST, WM)                                                                     \
+  do {                                                                                                          \
+    static LdsLimitOnce lds_once;                                                                               \
+    lds_once.set((const void*)k_lqer_gemm<DT, LR, BO, ST, 4, false, false, WM>, gemm_lds_bytes(4));             \
+    k_lqer_gemm<DT, LR, BO, ST, 4, false, false, WM><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                  \
+  } while (0)
+      if (!g.w_mf) {  // (block_fp / integer weights here: only with a minifloat B_out)
+        if (g.w_twos) {  // (integer weights: the staged side path, as below)
+          static LdsLimitOnce lds_once;
+          lds_once.set((const void*)k_lqer_gemm<DT, true, 3, true, 4, true>, gemm_lds_bytes(4));
+          k_lqer_gemm<DT, true, 3, true, 4, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);
+        } else if (staged) LQER_GEMM_LAUNCH_MF(true, 3, true, false);
+        else LQER_GEMM_LAUNCH_MF(true, 3, false, false);
+      } else if (!lowrank) LQER_GEMM_LAUNCH_MF(false, 0, false, true);
+      else if (bout == 1) LQER_GEMM_LAUNCH_MF(true, 1, true, true);
+      else if (bout == 2) LQER_GEMM_LAUNCH_MF(true, 2, true, true);
+      else if (bout == 3) LQER_GEMM_LAUNCH_MF(true, 3, true, true);
+      else LQER_GEMM_LAUNCH_MF(true, 0, true, true);
+#undef LQER_GEMM_LAUNCH_MF
+      return check_launch("lqer_gemm");
+    }
+  }
   if (g.w_twos) {  // integer weights: one instantiation per (element type, side path, B_out) - 128-row tiles, staged side path
     if constexpr (DT == LQER_F16X) {
       set_error("linear_gemm: integer weights have no fp16 main loop (pass-through fp16 activations take the limb route)");
@@ -1040,6 +1075,10 @@ static int bout_mode(const GemmArgs& g, bool lowrank, int* L_out) {
     if (L_out) *L_out = 0;
     return 2;
   }
+  if (lowrank && g.bout.kind == LQER_Q_MINIFLOAT) {  // elementwise with an exponent per element: the 128-row tile kernel's BOUT 3
+    if (L_out) *L_out = 0;
+    return 3;
+  }
   if (lowrank && g.bout.kind != LQER_Q_PASSTHROUGH) {
     set_error("B_out_quantizer kind %d not implemented", g.bout.kind);
     return LQER_E_UNSUPPORTED;
@@ -1061,6 +1100,7 @@ int gemm_route(const GemmArgs& g, bool lowrank) {
     return gemm_route(t, lowrank);
   }
   if (g.w_twos) return LQER_ROUTE_TILE128;  // integer weights (two's-complement nibbles): the 128-row tile kernel at every M
+  if (g.w_mf || bout == 3) return LQER_ROUTE_TILE128;  // minifloat weights or B_out: the same
   if (smallm_eligible(g, bout)) return LQER_ROUTE_SMALLM;
   if (m256_eligible(g)) return LQER_ROUTE_TILE256;
   return LQER_ROUTE_TILE128;
@@ -1074,7 +1114,8 @@ int gemm_tile_rows(const GemmArgs& g) {
   const int64_t tn = g.Np / BN;
   const int64_t t128 = (int64_t)((g.M + BM - 1) / BM) * tn, t64 = (int64_t)((g.M + 63) / 64) * tn;
   const int pin = (g.tuning & LQER_TUNE_TILE_ROWS_128) ? 128 : ((g.tuning & LQER_TUNE_TILE_ROWS_64) ? 64 : 0);  // (tests)
-  if (!g.w_twos && ((pin != 128 && 2 * t128 <= CUS && t64 > t128 && g.M > 64) || (pin == 64 && g.M > 64))) return 64;
+  const bool mf = g.w_mf || g.bout.kind == LQER_Q_MINIFLOAT;  // (minifloat: 128-row instantiations only)
+  if (!g.w_twos && !mf && ((pin != 128 && 2 * t128 <= CUS && t64 > t128 && g.M > 64) || (pin == 64 && g.M > 64))) return 64;
   return BM;
 }
 
@@ -1236,7 +1277,7 @@ int gemm_dispatch(GemmArgs g, int dtype, bool lowrank, void* scratch, size_t scr
     }
     return i8_dispatch(g, dtype, lowrank, bout, st);
   }
-  if (!g.w_twos) {
+  if (!g.w_twos && !g.w_mf && bout != 3) {
     if (smallm_eligible(g, bout)) return smallm_dispatch(g, dtype, lowrank, bout, st);  // decode sizes: HBM-bound variant
     if (m256_eligible(g)) return m256_dispatch(g, dtype, lowrank, bout, st);  // large M: 256 x 256 tiles
   }

@@ -688,7 +688,8 @@ static void launch(const void* xq, int64_t x_ld, const bf16_t* a_img, int64_t Kp
 
 // Fixed-order sum over the chunks + A_out + bf16 store.  One lane per 4 consecutive rank entries; the G = L/4
 // lanes of a block (G a power of two <= 64, lanes of one wave) share their max through xor-shuffles.
-template <int G>
+// MF (G = 1): a minifloat A_out - elementwise minifloat_value, |v| <= 1e-8 -> 0 as in every bf16 image.
+template <int G, bool MF = false>
 __global__ __launch_bounds__(256) void k_xa_reduce4(const float* __restrict__ part, XaPlan plan, int rp, QP q,
                                                     bf16_t* __restrict__ xaq, const float* __restrict__ rowscale = nullptr) {
   const int64_t total = (int64_t)plan.row_groups * XA_ROWS * rp / 4;  // float4 items (rp/4 per row, a multiple of G)
@@ -722,6 +723,15 @@ __global__ __launch_bounds__(256) void k_xa_reduce4(const float* __restrict__ pa
   if (rowscale && live) {  // int8 activation image: the sums are of mantissas, the row's power-of-two scale comes last (exact)
     const float sc = rowscale[idx / (rp / 4)];
     s.x *= sc, s.y *= sc, s.z *= sc, s.w *= sc;
+  }
+  if constexpr (MF) {
+    if (!live) return;
+    const float v[4] = {s.x, s.y, s.z, s.w};
+    uint32_t b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b[i] = fabsf(v[i]) <= 1e-8f ? 0u : exact_bf16_bits(minifloat_value(v[i], q));
+    *(uint2*)(xaq + idx * 4) = make_uint2(b[0] | (b[1] << 16), b[2] | (b[3] << 16));
+    return;
   }
   float amax = fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fmaxf(fabsf(s.z), fabsf(s.w)));
 #pragma unroll
@@ -1076,9 +1086,11 @@ int lowrank_xa_dispatch(const bf16_t* xq, int64_t M, int64_t K, int x_limbs, con
   const int rp = (int)lqer_padded_r(r);
   const bool pass = q.kind == LQER_Q_PASSTHROUGH;
   const bool fixed = q.kind == LQER_Q_INT;  // (integer: the reduce pass quantizes with the pinned exponent, common.h)
-  if (pass ? (xa_limbs != 2 && xa_limbs != 3) : !((q.kind == LQER_Q_MXINT && q.mbits <= 8) || (fixed && q.mmax <= 256.f && q.mneg <= 256.f))) {
-    set_error("A_out_quantizer must be block_fp or integer with codes up to 256 (a bf16 image), or passthrough with 2 or 3 limbs, on "
-              "the HIP path (got kind %d width %d)", q.kind, q.width);
+  const bool mf = q.kind == LQER_Q_MINIFLOAT;  // (minifloat: elementwise, k_xa_reduce4<1, true>)
+  if (pass ? (xa_limbs != 2 && xa_limbs != 3)
+           : !((q.kind == LQER_Q_MXINT && q.mbits <= 8) || (fixed && q.mmax <= 256.f && q.mneg <= 256.f) || (mf && q.width <= 8))) {
+    set_error("A_out_quantizer must be block_fp or integer with codes up to 256 (a bf16 image), minifloat, or passthrough with 2 or 3 "
+              "limbs, on the HIP path (got kind %d width %d)", q.kind, q.width);
     return LQER_E_UNSUPPORTED;
   }
   const int L = pass ? 4 : ((q.block <= 0 || q.block >= rp) ? rp : q.block);
@@ -1152,7 +1164,11 @@ int lowrank_xa_dispatch(const bf16_t* xq, int64_t M, int64_t K, int x_limbs, con
   }
 #undef XA_CASE
   const int G = L / 4;
-  if (pass) {
+  if (mf) {
+    const int64_t items = (int64_t)plan.row_groups * XA_ROWS * rp / 4;
+    const unsigned bs = items <= 128 * 256 ? 64 : 256;  // (as below)
+    k_xa_reduce4<1, true><<<(unsigned)((items + bs - 1) / bs), bs, 0, st>>>(scratch, plan_l, rp, q, xaq, rowscale);
+  } else if (pass) {
     const int64_t items = (int64_t)plan.row_groups * XA_ROWS * rp / 4;
     const unsigned grid2 = (unsigned)((items + 255) / 256);
     if (xa_limbs == 2)

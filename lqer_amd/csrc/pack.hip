@@ -140,6 +140,67 @@ __global__ __launch_bounds__(256) void k_w_pack(const void* __restrict__ W, int6
   }
 }
 
+// pass 2 of a minifloat weight (2..4 bits, no pass 1: no block exponents): the nibble is sign << 3 | the magnitude code (E << mbits) | S of
+// minifloat_mag (|w| <= 1e-8 -> 0, as every packed image), every exponent byte the format's one scale 127 + s (mf_e4m3_table)
+template <int DT>
+__global__ __launch_bounds__(256) void k_w_pack_mf(const void* __restrict__ W, int64_t N, int64_t K, int64_t ld, QP q, int scale_byte,
+                                                   int64_t Np, int64_t Kp, uint8_t* __restrict__ out) {
+  const int64_t segs = Kp / 16;
+  const int64_t total = Np * segs;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int64_t row = idx / segs, seg = idx - row * segs, k0 = seg * 16;
+    uint32_t lo = 0, hi = 0;
+    if (row < N && k0 < K) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float w = (k0 + i < K) ? load_elem<DT>(W, row * ld + k0 + i) : 0.0f;
+        int code = 0;
+        (void)minifloat_mag(fabsf(w), q, &code);
+        const uint32_t c = fabsf(w) <= 1e-8f ? 0u : ((uint32_t)code | (w < 0.0f ? 8u : 0u));
+        const int j = i & 7, pos = j < 4 ? 2 * j : 2 * (j - 4) + 1;
+        if (i < 8)
+          lo |= c << (4 * pos);
+        else
+          hi |= c << (4 * pos);
+      }
+    }
+    uint8_t* panel = out + ((row / 16) * (Kp / 64) + seg / 4) * LQER_PANEL_BYTES;
+    *(uint32_t*)(panel + (row % 16) * 32 + (seg % 4) * 4) = lo;
+    *(uint32_t*)(panel + (row % 16) * 32 + 16 + (seg % 4) * 4) = hi;
+    panel[512 + (row % 16) * 4 + (seg % 4)] = (uint8_t)scale_byte;
+  }
+}
+
+// the value of an e4m3 (OCP fn) byte
+__device__ __forceinline__ float e4m3_value(uint32_t b) {
+  const int e = (int)((b >> 3) & 15), m = (int)(b & 7);
+  const float v = e == 0 ? ldexpf((float)m, -9) : ldexpf((float)(8 + m), e - 10);
+  return (b & 0x80u) ? -v : v;
+}
+
+// a minifloat weight image -> fp32, as the GEMM expands it: the nibble's magnitude through the e4m3 table, its sign, the exponent byte's scale
+__global__ __launch_bounds__(256) void k_w_unpack_mf(const uint8_t* __restrict__ in, int64_t N, int64_t K, int64_t Kp, uint32_t lut_lo,
+                                                     uint32_t lut_hi, float* __restrict__ out) {
+  const int64_t segs = Kp / 16;
+  const int64_t total = N * segs;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int64_t row = idx / segs, seg = idx - row * segs, k0 = seg * 16;
+    const uint8_t* panel = in + ((row / 16) * (Kp / 64) + seg / 4) * LQER_PANEL_BYTES;
+    const uint32_t cx = *(const uint32_t*)(panel + (row % 16) * 32 + (seg % 4) * 4);
+    const uint32_t cy = *(const uint32_t*)(panel + (row % 16) * 32 + 16 + (seg % 4) * 4);
+    const int sc = (int)panel[512 + (row % 16) * 4 + (seg % 4)] - 127;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const uint32_t word = i < 8 ? cx : cy;
+      const int j = i & 7, pos = j < 4 ? 2 * j : 2 * (j - 4) + 1;
+      const uint32_t nib = (word >> (4 * pos)) & 0xfu, mag = nib & 7u;
+      const uint32_t b = ((mag < 4 ? lut_lo : lut_hi) >> (8 * (mag & 3))) & 0xffu;
+      const float v = ldexpf(e4m3_value(b), sc);
+      if (k0 + i < K) out[row * K + k0 + i] = (nib & 8u) ? -v : v;
+    }
+  }
+}
+
 // (limbs = 3: the image of a 5..8-bit weight - the value is the sum of its three limbs, each digit x 2^(exponent byte - 127))
 __global__ __launch_bounds__(256) void k_w_unpack(const uint8_t* __restrict__ in, int64_t N, int64_t K, int64_t Kp,
                                                   int mbits, bool twos, int limbs, float* __restrict__ out) {
@@ -227,6 +288,10 @@ static int pack_w(const void* W, int64_t N, int64_t K, int64_t ld, const QP& q, 
 
 int pack_weight_dispatch(const void* W, int dtype, int64_t N, int64_t K, int64_t ld, const QP& q, int64_t block_rows, void* out,
                          void* scratch, hipStream_t st) {
+  if (q.kind == LQER_Q_MINIFLOAT) {
+    set_error("minifloat weights: pack_weight_mf_dispatch (the scale byte of the format's e4m3 table)");
+    return LQER_E_INVALID;
+  }
   if (q.width < 2 || q.width > 8 || (q.kind == LQER_Q_INT && q.width > 4)) {
     set_error("packed weights hold 4-bit codes (block_fp widths 5..8: three 4-bit limbs): w_quantizer width must be 2..8 (integer: 2..4), got %d", q.width);
     return LQER_E_UNSUPPORTED;
@@ -242,6 +307,34 @@ int pack_weight_dispatch(const void* W, int dtype, int64_t N, int64_t K, int64_t
   }
   set_error("unknown dtype %d", dtype);
   return LQER_E_INVALID;
+}
+
+// scale_byte = 127 + s of the format's e4m3 table (mf_e4m3_table, which the caller built and checked: the GEMM reads that very table)
+int pack_weight_mf_dispatch(const void* W, int dtype, int64_t N, int64_t K, int64_t ld, const QP& q, int scale_byte, void* out,
+                            hipStream_t st) {
+  if (q.kind != LQER_Q_MINIFLOAT || q.width < 2 || q.width > 4) {
+    set_error("minifloat weights: width 2..4 (5..8 bits need an 8-bit code image), got %d", q.width);
+    return LQER_E_UNSUPPORTED;
+  }
+  const int64_t Np = lqer_padded_n(N), Kp = lqer_padded_k(K);
+  const int64_t total = Np * (Kp / 16);
+  const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+  switch (dtype) {
+    case LQER_F32: k_w_pack_mf<LQER_F32><<<grid, 256, 0, st>>>(W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out); break;
+    case LQER_F16: k_w_pack_mf<LQER_F16><<<grid, 256, 0, st>>>(W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out); break;
+    case LQER_BF16: k_w_pack_mf<LQER_BF16><<<grid, 256, 0, st>>>(W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out); break;
+    default: set_error("unknown dtype %d", dtype); return LQER_E_INVALID;
+  }
+  return check_launch("pack_weight (minifloat)");
+}
+
+int unpack_weight_mf_dispatch(const void* in, int64_t N, int64_t K, const uint32_t (&lut)[2], float* out, hipStream_t st) {
+  const int64_t Kp = lqer_padded_k(K);
+  const int64_t total = N * (Kp / 16);
+  if (total == 0) return LQER_OK;
+  const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+  k_w_unpack_mf<<<grid, 256, 0, st>>>((const uint8_t*)in, N, K, Kp, lut[0], lut[1], out);
+  return check_launch("unpack_weight (minifloat)");
 }
 
 int unpack_weight_dispatch(const void* in, int64_t N, int64_t K, int mbits, bool twos, float* out, hipStream_t st) {

@@ -291,11 +291,63 @@ __global__ __launch_bounds__(256) void k_quant_int(const void* __restrict__ x, i
   }
 }
 
+// "minifloat" (reference quantizers/minifloat.py:120-182): elementwise through minifloat_mag (common.h), one lane per 16 elements.
+// Images: fp32 values (|x| <= 1e-8 kept), int8 codes = the minifloat bit pattern sign << (width-1) | E << mbits | S (a byte of
+// width 8 read as int8), the bf16 image (exact: at most 7 significand bits, normal bf16 exponents - make_qfmt / fmt_ok).
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void k_quant_mf(const void* __restrict__ x, int64_t rows, int64_t cols, int64_t ld, QP q,
+                                                  QuantOut o) {
+  const int64_t segs = o.xq ? o.cols_p / 16 : (cols + 15) / 16;
+  const int64_t total = rows * segs;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int64_t row = idx / segs;
+    const int64_t k0 = (idx - row * segs) * 16;
+    float v[16], m[16];
+    int c[16];
+    if (VEC && k0 + 16 <= cols) load16<DT, true>(x, row * ld, k0, cols, v);
+    else load16<DT, false>(x, row * ld, k0, cols, v);  // (elements past `cols` read as 0 -> 0)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float a = fabsf(v[i]);
+      m[i] = minifloat_mag(a, q, &c[i]);
+      const bool tiny = a <= 1e-8f;
+      m[i] = tiny ? 0.0f : copysignf(m[i], v[i]);
+      c[i] = tiny ? 0 : (c[i] | (v[i] < 0.0f ? 1 << (q.width - 1) : 0));
+    }
+    if (o.xq) {
+      uint32_t w[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) w[i] = exact_bf16_bits(m[2 * i]) | (exact_bf16_bits(m[2 * i + 1]) << 16);
+      uint4* dst = (uint4*)(o.xq + row * o.cols_p + k0);
+      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (k0 + i < cols) {
+        if (o.deq) o.deq[row * cols + k0 + i] = fabsf(v[i]) <= 1e-8f ? v[i] + 0.0f : m[i];  // (minifloat_value)
+        if (o.codes) o.codes[row * cols + k0 + i] = (int8_t)(uint8_t)c[i];
+      }
+  }
+}
+
 template <int DT>
 static int launch_quant(const void* x, int64_t rows, int64_t cols, int64_t ld, const QP& q, const QuantOut& o,
                         hipStream_t st) {
   if (rows == 0 || cols == 0) return LQER_OK;
   const int64_t width = o.xq ? o.cols_p : cols;
+  if (q.kind == LQER_Q_MINIFLOAT) {
+    if (o.exps || o.xq8) {
+      set_error("quantize (minifloat): no block exponents, no int8 image");
+      return LQER_E_UNSUPPORTED;
+    }
+    const int64_t total = rows * ((width + 15) / 16);
+    const unsigned grid = (unsigned)((total + 255) / 256 < 1 << 20 ? (total + 255) / 256 : 1 << 20);
+    const int esz = DT == LQER_F32 ? 4 : 2;
+    if (((uintptr_t)x % 16 == 0) && ((ld * esz) % 16 == 0)) k_quant_mf<DT, true><<<grid, 256, 0, st>>>(x, rows, cols, ld, q, o);
+    else k_quant_mf<DT, false><<<grid, 256, 0, st>>>(x, rows, cols, ld, q, o);
+    return check_launch("quantize (minifloat)");
+  }
   if (q.kind == LQER_Q_INT) {
     const int64_t total = rows * ((width + 15) / 16);
     const unsigned grid = (unsigned)((total + 255) / 256 < 1 << 20 ? (total + 255) / 256 : 1 << 20);

@@ -6,8 +6,8 @@ Blocks run along the last dim of each operand, which for y is NOT the contractio
 templates' settings (block_fp, width <= 8, blocks of 16) the whole product is ONE fused HIP GEMM (lqer_matmul_q,
 csrc/matmul_q.hip): x is quantized in the GEMM's load path - read from HBM once, no quantized copy -, y through a small bf16
 image, bf16 MFMA with fp32 accumulation of exact products; 4-D [bsz, heads, ..] operands are folded into one batch dim.  Other
-block lengths (16 n elements, or whole rows; no template uses them) take the same product kernel behind the library's
-standalone quantizer: that operand's bf16 image is written first and read as it is - the same bits.  Only operands whose
+block lengths (16 n elements, or whole rows; no template uses them) and minifloat operands take the same product kernel behind the
+library's standalone quantizer: that operand's bf16 image is written first and read as it is - the same bits.  Only operands whose
 leading dims broadcast (no call site has them) run the quantizer kernels on both operands and hand the two quantized tensors to
 torch.matmul / torch.bmm.  Quantizer settings outside what the kernels implement raise - there is no software fallback.
 """
@@ -29,6 +29,9 @@ def _quantize(t: torch.Tensor, cfg: dict) -> torch.Tensor:
     name = cfg.get("name")
     if name == "passthrough":
         return t
+    if name == "minifloat":  # elementwise: the standalone HIP quantizer
+        ops._need_gpu(t)
+        return ops.quantize_mxint(t, ops.make_qfmt(cfg), want=("deq",))["deq"].to(t.dtype)
     if name != "block_fp":
         raise NotImplementedError(f"lqer_amd.functional: quantizer {name!r} is not implemented on the HIP path")
     ops._need_gpu(t)
@@ -48,7 +51,9 @@ def _quantize(t: torch.Tensor, cfg: dict) -> torch.Tensor:
 def _fused_fmt(cfg: dict):
     """The lqer_qfmt_t of a quantizer the library's product kernels cover (block_fp, width <= 8, blocks of 16 n elements or
     whole rows along the last dim: 16 runs fused in the load path, other lengths through the standalone quantizer's bf16
-    image first - csrc/matmul_q.hip), else None."""
+    image first - csrc/matmul_q.hip; minifloat operands likewise, through that quantizer's bf16 image), else None."""
+    if cfg.get("name") == "minifloat":
+        return ops.make_qfmt(cfg, "x")  # (raises on a format the HIP path refuses, as _quantize would)
     if cfg.get("name") != "block_fp" or int(cfg.get("width", 12)) > 8:
         return None
     try:

@@ -121,8 +121,10 @@ class _LinearBase(nn.Linear):
         self._x_i8 = False
         self._fw_cache = {}
         fx, fw, K = self._fmt["x"], self._fmt["w"], self.in_features
+        mf_side = any(self._fmt.get(r) is not None and self._fmt[r].kind == _lib.Q_MINIFLOAT for r in ("A_out", "B_out"))
         if (self.a8_native and fx.kind == _lib.Q_MXINT and fw.kind == _lib.Q_MXINT and fx.width <= 8 and (fx.block <= 0 or fx.block >= K)
-                and K >= 128 and (fw.block <= 0 or fw.block >= K or fw.block % 128 == 0)):
+                and K >= 128 and (fw.block <= 0 or fw.block >= K or fw.block % 128 == 0) and not mf_side):
+            # (a minifloat A_out / B_out keeps the bf16 route: the int8 kernel has no elementwise-exponent epilogue)
             # one activation exponent per token, weight blocks of 128 k or more (the W4A8 INT configurations): integer
             # accumulation is exact - the int8 MFMA route, if every weight row's sums provably stay inside i32
             ok, w2 = ops.i8_prepare(p["w"], self.out_features, K, fw)
@@ -147,9 +149,9 @@ class _LinearBase(nn.Linear):
             p = dict(p)
             p["a_t_b16"] = ops.a_b16_image(p["a_t"], K, self.rank)
         if (self._fmt["x"].kind == _lib.Q_PASSTHROUGH and self.weight.dtype == torch.float16 and self.a16_native
-                and fw.kind == _lib.Q_MXINT and fw.width <= 4):
+                and fw.kind == _lib.Q_MXINT and fw.width <= 4 and not self._bout_minifloat()):
             # (integer weights - two's-complement nibbles - have no fp16 main loop, weights of 5..8 bits travel as three 4-bit limbs
-            # over a repeated activation image: the limb route)
+            # over a repeated activation image, a minifloat B_out has no fp16-main-loop instantiation: the limb route)
             ok, a16 = ops.f16_prepare(p["w"], self.out_features, self.in_features, p.get("a_t"), int(p.get("a_limbs", 0)), self.rank)
             if ok:
                 self._x_f16 = True
@@ -168,6 +170,10 @@ class _LinearBase(nn.Linear):
             q["a_t"] = ops.replicate_rows(p["a_t"], 3 * rp, Kp * 2, xl)
             q["b_t"] = ops.replicate_rows(p["b_t"], 3 * Np, rp * 2, al)
         return q
+
+    def _bout_minifloat(self) -> bool:
+        f = self._fmt.get("B_out")
+        return f is not None and f.kind == _lib.Q_MINIFLOAT
 
     def _single_copy(self, name: str) -> torch.Tensor:
         """Copy 0 of a repeated image, as flat bytes (inverse of _replicate)."""
@@ -435,7 +441,7 @@ class _LinearBase(nn.Linear):
                 return t
             if fm.kind == _lib.Q_MXINT:
                 return ops.quantize_act_tiles(t, fm)
-            return ops.quantize_mxint(t, fm, want=("deq",))["deq"].to(t.dtype)  # integer: elementwise
+            return ops.quantize_mxint(t, fm, want=("deq",))["deq"].to(t.dtype)  # integer, minifloat: elementwise
 
         w, b = self._parameters["weight"], self._parameters["bias"]
         inner = self.__dict__.get("_inner")
@@ -576,6 +582,8 @@ class SharedActivation:
         ok = ok and m0._fmt["x"].kind == _lib.Q_MXINT  # (pass-through activations: every member splits x itself)
         # (weights of 5..8 bits read a three-times repeated activation image: every member makes its own)
         ok = ok and all(ops.w_limbs(m._fmt["w"]) == 1 for m in self.members)
+        # (minifloat in any role: every member runs its own forward - the group launches are built around block_fp images)
+        ok = ok and not any(f is not None and f.kind == _lib.Q_MINIFLOAT for m in self.members for f in m._fmt.values())
         self.enabled = bool(ok)
         self._cat = None      # concatenated A^T limb image + member offsets
         self._x = None        # the tensor the images below were made from (strong reference: its address stays taken)

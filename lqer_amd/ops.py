@@ -73,8 +73,10 @@ def make_qfmt(cfg: Optional[dict], role: str = "x") -> QFmt:
             # (codes -2^(w-1) .. 2^(w-1)-1 travel as two's-complement nibbles of the packed image: signed, 2..4 bits)
             raise NotImplementedError("an integer weight quantizer must be signed with width 2..4 on the HIP path (4-bit packed image)")
         return QFmt(_lib.Q_INT, int(cfg["width"]), -1, 1 if signed else 0, int(cfg["frac_width"]))
+    if name == "minifloat":
+        return _minifloat_qfmt(cfg, role)
     if name != "block_fp":
-        raise NotImplementedError(f"quantizer '{name}' is not implemented on the HIP path (block_fp, integer, passthrough)")
+        raise NotImplementedError(f"quantizer '{name}' is not implemented on the HIP path (block_fp, integer, minifloat, passthrough)")
     bs = cfg.get("block_size", [16])
     bs = [bs] if isinstance(bs, int) else list(bs)
     skip = bool(cfg.get("skip_first_dim", True))
@@ -116,6 +118,29 @@ def make_qfmt(cfg: Optional[dict], role: str = "x") -> QFmt:
     if role != "b" and act_tiles is not None:
         fmt.act_tiles = act_tiles    # (R, L, skip_first_dim) as configured - a Python attribute, see above
     return fmt
+
+
+def _minifloat_qfmt(cfg: dict, role: str) -> QFmt:
+    """The reference's `minifloat` (quantizers/minifloat.py:120-182, minifloat_ieee) -> LQER_Q_MINIFLOAT: width, exp_width, the resolved
+    exp_bias.  Elementwise in every role (block_size / skip_first_dim do not apply).  Refused: a config without `exponent_width` (it names
+    no format), width - exponent_width - 1 < 0, widths outside 2..8, a bias that puts some value outside the normal bf16 range, and
+    weights wider than 4 bits (they need an 8-bit code image)."""
+    if "exponent_width" not in cfg:
+        raise NotImplementedError("a minifloat quantizer config needs `exponent_width` (width alone names no format)")
+    w, ew = int(cfg["width"]), int(cfg["exponent_width"])
+    eb = cfg.get("exponent_bias", None)
+    eb = 2 ** (ew - 1) - 1 if eb in (None, "none", "None", "NA") else int(eb)
+    mbits = w - ew - 1
+    if mbits < 0 or ew < 1 or not 2 <= w <= 8:
+        raise ValueError(f"minifloat(width={w}, exponent_width={ew}): needs 2 <= width <= 8 and 1 <= exponent_width <= width - 1")
+    emax, lowest = 2 ** ew - 1 - eb, 1 - eb - mbits  # exponents of the largest and of the smallest non-zero value
+    if emax > 127 or lowest < -126:
+        raise NotImplementedError(f"minifloat(width={w}, exponent_width={ew}, exponent_bias={eb}): its values span 2^{lowest} .. 2^{emax}, "
+                                  "outside the normal bf16 range the HIP images hold")
+    if role == "w" and w > 4:
+        raise NotImplementedError("a minifloat weight quantizer must have width 2..4 on the HIP path (4-bit packed image; 5..8 bits need an "
+                                  "8-bit code image)")
+    return QFmt(_lib.Q_MINIFLOAT, w, -1, ew, eb)
 
 
 def act_rows_per_block(fmt: Optional[QFmt], shape) -> int:
@@ -171,6 +196,8 @@ def quantize_mxint(x: torch.Tensor, fmt: QFmt, want=("deq", "codes", "exps")) ->
     tiles (`fmt.block_rows` != 1, make_qfmt role "w") is honoured too: the values then come from the packed image of
     lqer_pack_weight_mxint_2d (one exponent per tile), |x| <= 1e-8 kept as is (block_fp.py:79-80) - `deq` of a 2-D tensor only."""
     _need_gpu(x)
+    if fmt.kind == _lib.Q_MINIFLOAT:
+        want = tuple(k for k in want if k != "exps")  # (elementwise: no block exponents; `codes` = the minifloat bit pattern)
     if int(getattr(fmt, "block_rows", 1)) != 1:
         if tuple(want) != ("deq",) or x.dim() != 2:
             raise NotImplementedError("quantize_mxint with 2-D weight tiles (block_rows != 1) returns `deq` of a 2-D tensor only")
