@@ -489,6 +489,21 @@ int lqer_matmul_q(const void* x, const void* y, void* out, int dtype, int64_t ba
                   int64_t x_bs, int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const lqer_qfmt_t* x_fmt,
                   const lqer_qfmt_t* y_fmt, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
+ * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's
+ * x.float() does) for the per-input-channel sum|x| and max|x|; any of the three outputs may be NULL, not all of them:
+ *   run_absmean_max [K] fp32, in/out: max(run, sum|x[:, k]| / M) - the scale hook's body, scale.py:32-38
+ *                       (x.float().abs().view(-1, K).mean(0), torch.maximum into the running scale); a NaN on either side stays;
+ *   col_absmax      [K] fp32, out: max|x[:, k]| of this call, exact (NaN for a column that holds one, as torch's amax);
+ *   n_cols_ge       [1] int32, out: #{k : some |x[m, k]| >= threshold} of this call - the threshold hook's count,
+ *                       threshold.py:39-40 (x.abs().ge(t).view(-1, K).any(dim=0).sum(); a NaN compares false).
+ * The sums are added in an order fixed by (M, K, dtype) - no floating-point atomics - so two calls on the same input give the
+ * same bits; any K, any ldx >= K, any alignment of x (16-byte aligned rows take 16-byte loads, others element loads: same bits).
+ * workspace: lqer_col_abs_stats_workspace_bytes(M, K) bytes, 4-byte aligned, contents irrelevant.  Two launches on `stream`. */
+size_t lqer_col_abs_stats_workspace_bytes(int64_t M, int64_t K);
+int lqer_col_abs_stats(const void* x, int dtype, int64_t M, int64_t K, int64_t ldx, float* run_absmean_max, float* col_absmax,
+                       float threshold, int32_t* n_cols_ge, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement aid ---------------------------------------------------------------------------------------------------
  * The shader clock the chip holds while other work runs: `nblocks` (1..64) one-wave workgroups on `stream` (a stream of its
  * own, beside the kernels under study) each write {shader cycles, 100 MHz ticks} elapsed over the last three quarters of about `duration_us` of real time to

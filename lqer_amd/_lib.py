@@ -107,6 +107,9 @@ SIGNATURES = {
     "lqer_unpack_weight_i8_fmt": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),
     "lqer_quantize_act_i8": (_i, [_vp, _i, _i64, _i64, _i64, _qp, _vp, _vp]),
     "lqer_clock_probe": (_i, [_vp, _i, _i64, _vp]),
+    # calibration statistics (csrc/col_stats.hip): per-column mean|x| folded into a running maximum, max|x|, outlier-column count
+    "lqer_col_abs_stats_workspace_bytes": (_sz, [_i64, _i64]),
+    "lqer_col_abs_stats": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, C.c_float, _vp, _vp, _sz, _vp]),
     "lqer_matmul_q_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "lqer_matmul_q_workspace_bytes_fmt": (_sz, [_i64, _i64, _i64, _i64, _qp, _qp]),
     "lqer_matmul_q": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _qp, _qp, _vp, _sz, _vp]),

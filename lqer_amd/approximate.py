@@ -76,7 +76,8 @@ def approximate_model(model: nn.Module, a_cfg: Optional[dict] = None, b_cfg: Opt
                       scale_dict: Optional[Dict[str, torch.Tensor]] = None, factors_fn=None) -> Dict[str, torch.Tensor]:
     """Fill A and B of every LinearFlexibleLqer of a model prepared by models.quantize_model (weights still dense, on
     the GPU).  Returns the dictionary the reference stores as low_rank_dict.pt ({"<module>.A", "<module>.B"}).
-    scale_dict maps module names to activation scales [in_features] (L2QER); missing names use plain SVD.
+    scale_dict maps "<module name>.scale" (what calibrate.profile_model / the reference's profiler write) or the plain module name to
+    activation scales [in_features] (L2QER); missing names use plain SVD.
 
     With an initialised torch.distributed group (one process per GPU, every rank holding the same model) the SVDs are
     split over the ranks by decoder layer (module_owners) and each module's A, B are broadcast from their owner, so all
@@ -94,7 +95,8 @@ def approximate_model(model: nn.Module, a_cfg: Optional[dict] = None, b_cfg: Opt
             raise RuntimeError(f"{name}: weight already replaced by its quantized values (run before the first forward)")
         if owners[name] == rank:
             w_cfg = m.q_config.get("w_quantizer", m.q_config["default"])
-            sc = scale_dict.get(name) if scale_dict else None
+            # (the reference's key first - "<module>.scale", statistic_profiler/scale.py:65, lqer_act.py:156 -, then the plain name)
+            sc = (scale_dict[name + ".scale"] if name + ".scale" in scale_dict else scale_dict.get(name)) if scale_dict else None
             A, B = factors_fn(m.weight.data, w_cfg, m.rank, a_cfg, b_cfg, sc)
             m.A.data.copy_(A.to(m.A.dtype))
             m.B.data.copy_(B.to(m.B.dtype))

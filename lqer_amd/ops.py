@@ -4,7 +4,7 @@ kernels; a CPU tensor is an error, not a fallback."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -424,6 +424,44 @@ def pack_bias(bias: torch.Tensor, fmt: QFmt) -> torch.Tensor:
     bias = bias.contiguous()
     check(_lib.lib().lqer_pack_bias(bias.data_ptr(), dtype_code(bias), N, C.byref(fmt), out.data_ptr(), _stream(bias.device)), "lqer_pack_bias")
     return out
+
+
+class ColStats(NamedTuple):
+    """What col_abs_stats returns: the running scale (fp32 [K], updated in place), max|x| per column of this call (fp32 [K]) and the
+    number of columns holding an |x| >= threshold (int32 [1], on the device); None for what was not asked for."""
+    run: Optional[torch.Tensor]
+    absmax: Optional[torch.Tensor]
+    count: Optional[torch.Tensor]
+
+
+@_on_tensor_device
+def col_abs_stats(x: torch.Tensor, run: Optional[torch.Tensor] = None, want_absmax: bool = False,
+                  threshold: Optional[float] = None) -> ColStats:
+    """Calibration statistics of an activation in one pass (lqer_col_abs_stats): x [..., K] is read as [M, K] like the reference hook's
+    `.view(-1, K)` (statistic_profiler/scale.py:36); `run` (fp32 [K] on x's device) becomes max(run, mean|x| per column) in place - with
+    run = None and nothing else asked for, a fresh zero vector is used, i.e. the column means themselves come back."""
+    _need_gpu(x, run)
+    K = x.shape[-1]
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    if x2.stride(-1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < K):
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    if M == 0 or K == 0:
+        raise ValueError(f"col_abs_stats: empty input {tuple(x.shape)}")
+    dev = x.device
+    if run is None and not want_absmax and threshold is None:
+        run = torch.zeros(K, dtype=torch.float32, device=dev)
+    if run is not None and (run.dtype != torch.float32 or run.shape != (K,) or not run.is_contiguous() or run.device != dev):
+        raise ValueError(f"col_abs_stats: run must be a contiguous float32 [{K}] tensor on {dev}")
+    absmax = torch.empty(K, dtype=torch.float32, device=dev) if want_absmax else None
+    count = torch.empty(1, dtype=torch.int32, device=dev) if threshold is not None else None
+    L = _lib.lib()
+    nbytes = L.lqer_col_abs_stats_workspace_bytes(M, K)
+    ws = workspace(dev, nbytes)
+    check(L.lqer_col_abs_stats(x2.data_ptr(), dtype_code(x2), M, K, x2.stride(0) if M > 1 else K, _ptr(run), _ptr(absmax),
+                               0.0 if threshold is None else float(threshold), _ptr(count), ws.data_ptr(), nbytes, _stream(dev)),
+          "lqer_col_abs_stats")
+    return ColStats(run, absmax, count)
 
 
 # grow-only per-(device, stream) scratch shared by every Linear (stream-ordered reuse is safe)
