@@ -20,6 +20,17 @@
  *    stream) and performs no host synchronisation, so calls may be captured in a hipGraph;
  *  - return value 0 = success, <0 = error (LQER_E_*); lqer_last_error() gives the text of the
  *    last error raised on the calling thread.
+ *  - extents (held by tests/test_gpu_footprint.py between guard zones, at exactly these sizes): a strided tensor x / y / W of
+ *    [rows, cols] with row stride ld is (rows - 1) * ld + cols elements - no call writes a column >= cols of any row (the gaps
+ *    between the rows of y keep their bytes) or anything behind the last element of the last row, whatever ld and the
+ *    pointer's alignment are (rows that are not 16-byte aligned take element stores: same bits); every other output is written
+ *    inside the size its declaration names and, for the one-time images (lqer_pack_*, lqer_*_prepare), written WHOLE - padding
+ *    included - so an image never carries bytes of whatever the buffer held before.  The per-call buffers are the exception by
+ *    design: xq has lqer_padded_m(M) rows of which only rows < M are written (the tile kernels read the others; no output bit
+ *    of a row < M depends on them), xaq likewise ([lqer_padded_m(M)][padded rank x limbs] bf16, 16-byte aligned), and
+ *    workspace / scratch contents are never assumed: every call gives the same bits over any previous contents, NaN patterns
+ *    included.  Inputs are never written.  workspace, xq, xaq, scratch: 256-byte aligned in the tests; the group workspace and
+ *    the small flag / count outputs: 16-byte aligned there.
  *  - "MXINT(w, L)" = the reference's block_fp format (quantizers/block_fp.py:7-82): blocks of L
  *    consecutive elements along the last dim share an exponent e = ceil(log2(max|block|)); each
  *    element is a sign and a (w-1)-bit magnitude m; value = +-m * 2^(e-(w-1)).
@@ -266,7 +277,8 @@ int lqer_linear_forward(const lqer_linear_desc_t* desc, const void* x, int dtype
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* Up to 8 tokens (block_fp activations in blocks of 16, A_out in blocks of 16, padded rank <= 64, one limb of A, B_out
- * pass-through or in blocks of 16 - lqer_decode_partials - and 16-byte aligned rows of x) lqer_linear_forward issues ONE
+ * pass-through or in blocks of 16 - lqer_decode_partials -, in_features a multiple of 16 and 16-byte aligned rows of x; anything
+ * else at decode sizes: the two-launch route, same bits) lqer_linear_forward issues ONE
  * launch (csrc/decode1.hip): producer workgroups publish the split-K partial tiles of x A as {value, tag} granules in the
  * workspace, the weight-streaming workgroups quantize x themselves and read the tiles at their very end.  The tag is a
  * per-LAUNCH value: a process-wide atomic call counter (the library's only mutable state besides the thread-local error
@@ -364,8 +376,8 @@ int lqer_linear_gemm_ld(const lqer_linear_desc_t* desc, const void* xq_bf16, int
  *   a_t_cat:    A^T of the members concatenated along the rank: bf16 [sum of padded ranks][padded K] - lqer_pack_lowrank of
  *               [A_0 | A_1 | ...] (each A_i zero-padded to its padded rank); a_limbs must be 1 (8-bit MXINT values);
  *   workspace:  >= lqer_group_workspace_bytes(K, sum of padded ranks), 16-byte aligned.
- * Served: 2..4 members with equal in_features and equal x / A_out / B_out formats, each with lqer_decode_partials(desc, M) == 1,
- * M <= 8, 16-byte aligned rows of x, sum of padded ranks <= 128.  Anything else returns LQER_E_UNSUPPORTED WITHOUT launching:
+ * Served: 2..4 members with equal in_features (a multiple of 16) and equal x / A_out / B_out formats, each with
+ * lqer_decode_partials(desc, M) == 1, M <= 8, 16-byte aligned rows of x, sum of padded ranks <= 128.  Anything else returns LQER_E_UNSUPPORTED WITHOUT launching:
  * the caller then runs the members one by one. */
 typedef struct lqer_group_member {
   const lqer_linear_desc_t* desc;
@@ -459,6 +471,8 @@ int lqer_a_b16_prepare(const void* a_t_limbs, int64_t K, int64_t r, void* out, v
  *    route (exact, three times the work).  128- or 256-row tiles (lqer_gemm_tile_rows says which): on 128-row tiles a wave's codes go
  *    straight from this image into registers (four coalesced 16-byte loads per lane and step, no LDS), on 256-row tiles through a
  *    half-step LDS ring. */
+/* lqer_i8_prepare reads the first image and writes the second one whole, the 256-byte padding of its per-tile mode table included;
+ * the first image and the alignment gap between the two are not touched. */
 int lqer_i8_prepare(void* w_packed, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, int32_t* flags, void* stream);
 /* Test hooks: the int8 weight image (inside w_packed) -> dequantized fp32 [N,K]; x [M,K] -> the int8 activation image. */
 int lqer_unpack_weight_i8(const void* w_packed, int64_t N, int64_t K, float* w_f32, void* stream);

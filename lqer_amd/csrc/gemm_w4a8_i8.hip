@@ -165,6 +165,8 @@ __global__ __launch_bounds__(256) void k_i8_rows(const uint8_t* __restrict__ wp,
   const int tile_any = __syncthreads_or(row_any);
   const int mode = !tile_any ? I8_MODE_NONE : (tile_wide ? I8_MODE_FOLD : (tile_two ? I8_MODE_PRESHIFT : I8_MODE_PRESHIFT1));
   if (threadIdx.x == 0) mode_tab[tn] = (uint8_t)mode;
+  // (the padding of the mode table to 256 bytes is part of the image: written, so that the image never carries stale bytes)
+  if (blockIdx.x == 0 && Np / 256 + threadIdx.x < (Np / 256 + 255) / 256 * 256) mode_tab[Np / 256 + threadIdx.x] = 0;
   // pass 2: shift bytes and the i32 bound  sum_g sum_k |lane| * 127 < 2^31  (lane = 16 c 2^s, or c 2^(4-q))
   unsigned long long bound = 0;
   for (int s = 0; s < nk8; ++s) {
