@@ -503,6 +503,36 @@ int lqer_matmul_q(const void* x, const void* y, void* out, int dtype, int64_t ba
                   int64_t x_bs, int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const lqer_qfmt_t* x_fmt,
                   const lqer_qfmt_t* y_fmt, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused quantized attention (reference models/llama_decoder.py:259-297, opt_decoder.py:125,190: both products through
+ * matmul_flexible / bmm_flexible, the softmax in fp32 between them) ------------------------------------------------------------
+ * Per batch element b and head h, with g = h / (heads / kv_heads) (grouped-query K / V are read through the head mapping, never
+ * repeated in memory) and DT the element type `dtype` of q, k, v, mask and out; ->DT is a rounding to DT:
+ *     S  = q_fmt(Q[b,h]) k_fmt(K[b,g]^T) ->DT        [S, T]  blocks of 16 along d resp. along t; fp32 accumulation of exact products
+ *     S1 = S scaling ->DT;   S2 = S1 + mask[b,h] ->DT  (with a mask tensor);   P = softmax_fp32(S2 over t) ->DT
+ *     out[b,h] = p_fmt(P) v_fmt(V[b,g]) ->DT          [S, D]  blocks of 16 along t resp. along d
+ * - bit for bit the two lqer_matmul_q products with torch's scale, add and fp32 softmax between them, each materialised in DT
+ * (lqer_amd/attention.py), but for the order of the fp32 sums and the last bits of exp: the [S, T] scores never reach memory.
+ * The four formats must be LQER_Q_MXINT, width <= 8, block 16; D a multiple of 16, D <= 128; S, T >= 1 arbitrary (ragged last
+ * blocks are zero-padded on the right, as in lqer_matmul_q).  Anything else: LQER_E_UNSUPPORTED, nothing launched.
+ * Strides are in ELEMENTS over (batch, head, row) - q_strides[3], k_strides[3] (head = kv head), v_strides[3], out_strides[3] - with
+ * the last dim (d) contiguous; out_strides let the call write [b, s, h, d] directly.  Mask, one of:
+ *   mask != NULL   additive tensor of DT, mask_strides[3] over (batch, head, query row) with 0 = broadcast, t contiguous; added and
+ *                  rounded literally, so fully masked rows behave as in the unfused route;
+ *   causal = 1     key j is visible to query i iff j <= i + (T - S); invisible keys contribute exactly 0 and key tiles without a
+ *                  visible key are skipped (for S <= T the same bits as the tensor form of that mask).  Not both.
+ * row_stats (may be NULL): float [batch][heads][S][2] = {row maximum of S2, row sum of exp(S2 - maximum)} over the visible keys.
+ * workspace: lqer_attention_q_workspace_bytes(...) bytes, 256-byte aligned, contents irrelevant, layout
+ *   [bf16 image of k_fmt(K^T): batch kv_heads x (T rounded up to 128) x (D rounded up to 64)]
+ *   [bf16 image of v_fmt(V):   batch kv_heads x 128 x (T rounded up to 64)]          each part rounded up to 256 bytes
+ * - independent of heads and S.  A workspace shorter than that is LQER_E_INVALID.  Three launches on `stream` (two image kernels,
+ * the attention kernel), no allocation, no host synchronisation: capturable in a hipGraph. */
+size_t lqer_attention_q_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D);
+int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype,
+                     int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                     const int64_t* k_strides, const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides,
+                     float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                     const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's
  * x.float() does) for the per-input-channel sum|x| and max|x|; any of the three outputs may be NULL, not all of them:

@@ -57,6 +57,7 @@ class LinearSizes(C.Structure):
 
 _vp, _i, _i64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 _qp, _dp = C.POINTER(QFmt), C.POINTER(LinearDesc)
+_sp = C.POINTER(C.c_int64)  # a stride triple
 
 # name -> (restype, argtypes); must list every symbol declared in include/lqer_hip.h
 SIGNATURES = {
@@ -113,6 +114,11 @@ SIGNATURES = {
     "lqer_matmul_q_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "lqer_matmul_q_workspace_bytes_fmt": (_sz, [_i64, _i64, _i64, _i64, _qp, _qp]),
     "lqer_matmul_q": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _qp, _qp, _vp, _sz, _vp]),
+    # fused quantized attention (csrc/attn_q.hip): q, k, v, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, five stride
+    # triples (elements over batch / head / row), scaling, causal, four formats, workspace, bytes, stream
+    "lqer_attention_q_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "lqer_attention_q": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _sp, _sp, _sp, _sp, _sp, C.c_float, _i,
+                              _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -16,33 +16,30 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .functional import matmul_flexible
+from .functional import _repeat_kv, attention_flexible, unfused_attention  # noqa: F401  (_repeat_kv: the one spelling, in functional)
 
 IMPLEMENTATION = "lqer_eager"
-
-
-def _repeat_kv(t: torch.Tensor, n_rep: int) -> torch.Tensor:
-    if n_rep == 1:
-        return t
-    b, h, s, d = t.shape
-    return t[:, :, None, :, :].expand(b, h, n_rep, s, d).reshape(b, h * n_rep, s, d)
+IMPLEMENTATION_FUSED = "lqer_fused"  # the same computation as ONE kernel (csrc/attn_q.hip): enable_quantized_attention(..., fused=True)
 
 
 def lqer_eager_attention_forward(module: nn.Module, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                                  attention_mask: Optional[torch.Tensor], scaling: float, dropout: float = 0.0, **kwargs):
     cfg0, cfg1 = module._lqer_matmul_cfg
-    key_states = _repeat_kv(key, getattr(module, "num_key_value_groups", 1))
-    value_states = _repeat_kv(value, getattr(module, "num_key_value_groups", 1))
-    b, h, s, d = query.shape
-    t = key_states.shape[2]
-    scores = matmul_flexible(query.reshape(b * h, s, d), key_states.reshape(b * h, t, d).transpose(1, 2), cfg0)
-    attn_weights = scores.reshape(b, h, s, t) * scaling
-    if attention_mask is not None:
-        attn_weights = attn_weights + attention_mask
-    attn_weights = nn.functional.softmax(attn_weights, dim=-1, dtype=torch.float32).to(query.dtype)
-    attn_weights = nn.functional.dropout(attn_weights, p=dropout, training=module.training)
-    out = matmul_flexible(attn_weights.reshape(b * h, s, t), value_states.reshape(b * h, t, d), cfg1)
-    return out.reshape(b, h, s, d).transpose(1, 2).contiguous(), attn_weights
+    out, attn_weights = unfused_attention(query, key, value, cfg0, cfg1, scaling, attention_mask, dropout=dropout, training=module.training)
+    return out.transpose(1, 2).contiguous(), attn_weights
+
+
+def lqer_fused_attention_forward(module: nn.Module, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
+                                 attention_mask: Optional[torch.Tensor], scaling: float, dropout: float = 0.0, **kwargs):
+    """lqer_eager_attention_forward through attention_flexible: the mask tensor goes to the kernel as it is, grouped-query K / V
+    are read through the head mapping, the output is written as [b, s, h, d] and no weights exist to return.  A caller that wants
+    the weights (output_attentions), trains with dropout or hands over a mask of another dtype gets the unfused function."""
+    if (kwargs.get("output_attentions") or (dropout > 0.0 and module.training)
+            or (attention_mask is not None and attention_mask.dtype != query.dtype)):  # (a wider mask: torch adds it with type promotion)
+        return lqer_eager_attention_forward(module, query, key, value, attention_mask, scaling, dropout=dropout, **kwargs)
+    cfg0, cfg1 = module._lqer_matmul_cfg
+    out = attention_flexible(query, key, value, cfg0, cfg1, scaling, attention_mask=attention_mask, out_layout="bshd")
+    return out, None
 
 
 def _register() -> None:
@@ -51,13 +48,17 @@ def _register() -> None:
 
     AttentionInterface.register(IMPLEMENTATION, lqer_eager_attention_forward)
     AttentionMaskInterface.register(IMPLEMENTATION, eager_mask)
+    AttentionInterface.register(IMPLEMENTATION_FUSED, lqer_fused_attention_forward)
+    AttentionMaskInterface.register(IMPLEMENTATION_FUSED, eager_mask)
 
 
-def enable_quantized_attention(model: nn.Module, q_config: dict) -> nn.Module:
+def enable_quantized_attention(model: nn.Module, q_config: dict, fused: bool = False) -> nn.Module:
     """Route every decoder layer's attention through matmul_flexible.  q_config["matmul"] applies to both products of
     every layer unless `model_layer_<i>` / `model_layer` carry `self_attn: {matmul_0, matmul_1}` overrides
     (llama_decoder.py:423-482); OPT models read q_config["bmm"] and `bmm_0` / `bmm_1` instead, as the reference's OPT
-    decoder does (opt_decoder.py:125,190,329-339).  Model families without the attention-interface hook raise."""
+    decoder does (opt_decoder.py:125,190,329-339).  Model families without the attention-interface hook raise.
+    `fused=True` selects the implementation "lqer_fused": the whole attention as one HIP kernel where the quantizers and the head
+    dim allow it (functional.attention_flexible), the unfused sequence - with its results - where they do not."""
     from .models import _OPT, _decoder_layers
 
     _register()
@@ -78,5 +79,5 @@ def enable_quantized_attention(model: nn.Module, q_config: dict) -> nn.Module:
         attn._lqer_matmul_cfg = tuple(cfgs)
     if not hasattr(model, "set_attn_implementation"):
         raise NotImplementedError(f"{type(model).__name__}: no attention-implementation switch in this transformers version")
-    model.set_attn_implementation(IMPLEMENTATION)
+    model.set_attn_implementation(IMPLEMENTATION_FUSED if fused else IMPLEMENTATION)
     return model

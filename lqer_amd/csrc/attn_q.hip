@@ -1,0 +1,405 @@
+// Fused quantized attention (reference models/llama_decoder.py:259-297, opt_decoder.py:125,190, as lqer_amd/attention.py runs it):
+//     S  = Q_x0(Q) Q_w0(K^T) ->DT;  S1 = S scaling ->DT;  S2 = S1 + mask ->DT;  P = softmax_fp32(S2) ->DT;  O = Q_x1(P) Q_w1(V) ->DT
+// with the four block_fp quantizers of the two products (width <= 8, blocks of 16 along the last dim of each operand) and every
+// ->DT a rounding to the element type where the unfused route materialises a tensor.  The [s, t] scores never leave the chip.
+//
+// P is divided by the whole row's sum BEFORE it is rounded and quantized and the quantizer is not linear, so the output accumulator
+// cannot be rescaled afterwards (no online softmax): every query tile sweeps the key tiles twice,
+//   sweep 1: Q K^T -> S2 -> running row maximum and row sum (rescaled as the maximum grows - that is exact enough for a SUM);
+//   sweep 2: Q K^T again -> S2 -> P = exp(S2 - max) / sum ->DT -> Q_x1 in registers -> P V.
+// 6 s t d flops instead of 4 s t d, all on v_mfma_f32_32x32x16_bf16 (every 8-bit MXINT value is an exact bf16 number).
+//
+//   k_attn_kimage / k_attn_vimage   K, V -> bf16 images [b kv_heads][t][d] of Q_w0(K^T) (blocks of 16 along t) and [b kv_heads][d][t]
+//                                   of Q_w1(V) (blocks along d): the tile bodies of matmul_q.hip's image kernels (qmm_image.h) with
+//                                   a stride each for batch and kv head; grouped-query heads share an image.
+//   k_attn_q                        one workgroup = 128 queries of one head = 4 waves x 32 queries.  The product is issued
+//                                   TRANSPOSED, S^T = Kq Qq^T (key image rows as the A operand, the quantized query rows - in
+//                                   registers for the tile's life - as B): a lane owns ONE query and 16 of a 32-key subtile's scores,
+//                                   keys (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  Registers 0-7 of lanes l and l ^ 32 are one block of
+//                                   16 along t, registers 8-15 the next: the block maximum of Q_x1 needs one v_permlane32_swap, and the
+//                                   8 quantized values of a register octet ARE the B fragment of one k-step of O^T = Vq^T P^T (the
+//                                   image rows of V as A, read from LDS in the accumulator's key order) - P never moves between lanes
+//                                   and never touches LDS.  O^T leaves a lane with its query's d values, 4 consecutive per store.
+//                                   Key tiles of 64 go through LDS (rows padded against bank conflicts), the next tile's loads are
+//                                   requested before the current tile's MFMAs (register staging; one buffer, two barriers per tile).
+#include "qmm_image.h"
+
+namespace lqer {
+
+namespace attn {
+
+constexpr int NW = 4, BQ = 32 * NW, BT = 64;  // waves, queries per workgroup, keys per LDS tile
+constexpr int VD = 128;                      // rows of the V image per (batch, kv head): D padded to the image kernel's 128
+
+struct Args {
+  const void* q;
+  const bf16_t* kimg;  // [batch kv_heads][Tp][Dp]
+  const bf16_t* vimg;  // [batch kv_heads][VD][Tv]
+  const void* mask;
+  void* out;
+  float* stats;
+  int64_t S, T, D, Tp, Dp, Tv;
+  int64_t q_bs, q_hs, q_rs, m_bs, m_hs, m_rs, o_bs, o_hs, o_rs;
+  int heads, kv_heads, mode;  // mode: 0 no mask, 1 additive mask tensor, 2 causal rule
+  float scaling;
+  QP q0, q1;  // Q_x0 (queries), Q_x1 (probabilities)
+  bool qvec, mvec;
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_attn_kimage(const void* __restrict__ k, int64_t D, int64_t T, int64_t k_bs, int64_t k_hs, int64_t k_rs,
+                                                      int kv_heads, QP q, bf16_t* __restrict__ img, int64_t Tp, int64_t Dp, bool vec) {
+  const int64_t z = blockIdx.z;  // y = K^T [d][t], d contiguous: blocks of 16 along t
+  qmm::bimage_k_tile<DT>(k, (z / kv_heads) * k_bs + (z % kv_heads) * k_hs, D, T, k_rs, q, img + z * Tp * Dp, Tp, Dp, vec, (int64_t)blockIdx.x * 64,
+                         (int64_t)blockIdx.y * 64);
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v, int64_t D, int64_t T, int64_t v_bs, int64_t v_hs, int64_t v_rs,
+                                                      int kv_heads, QP q, bf16_t* __restrict__ img, int64_t Tv, bool vec) {
+  const int64_t z = blockIdx.z;  // y = V [t][d], d contiguous: blocks of 16 along d, transposed through LDS
+  qmm::bimage_j_tile<DT, false>(v, (z / kv_heads) * v_bs + (z % kv_heads) * v_hs, T, D, v_rs, q, img + z * VD * Tv, VD, Tv, vec, (int64_t)blockIdx.y * 64,
+                                (int64_t)blockIdx.x * 64);
+}
+
+template <int DT>
+__device__ __forceinline__ float rnd(float x) {  // ->DT
+  if constexpr (DT == LQER_F16) return (float)(_Float16)x;
+  else if constexpr (DT == LQER_BF16) return __uint_as_float((uint32_t)f32_to_bf16_rne(x) << 16);
+  else return x;
+}
+
+// exp(x) for x <= 0 on v_exp_f32 with the rounding of x log2(e) compensated (the bare product is off by |x| 2^-24 in the exponent:
+// 30 ulps at x = -20): about 2 ulps.  Below -200 (-inf included) the result is 0; a NaN stays a NaN (the comparison is false for it).
+__device__ __forceinline__ float exp_neg(float x) {
+  x = x < -200.0f ? -200.0f : x;
+  const float t = x * 1.44269502162933349609375f;
+  const float r = __builtin_fmaf(x, 1.44269502162933349609375f, -t) + x * 1.925963033500011e-8f;
+  const float e = __builtin_amdgcn_exp2f(t);
+  return __builtin_fmaf(e, r * 0.693147182464599609375f, e);
+}
+
+// the 8 values a lane holds of a block of 16 (the other 8 sit in lane ^ 32) -> 8 exact bf16 values: quant16_bf16's arithmetic
+template <bool FLUSH_TINY>
+__device__ __forceinline__ void quant8of16_bf16(const float (&v)[8], const QP& q, uint32_t (&w)[4]) {
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(v[i]));
+  const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(am), __float_as_uint(am), false, false);
+  const float amax = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) w[i] = 0;
+  if (amax > 0.f) {
+    const int e = block_exponent(amax, q);
+    if (mxint16_fast_ok(e, q)) {
+      mxint16_bf16_fast<FLUSH_TINY, 8>(v, e, q, w);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
+        const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
+        w[i] = lo | (hi << 16);
+      }
+    }
+  }
+}
+
+template <int DT, int DK>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
+__global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
+  constexpr int KS = 64 * DK + 16;  // bytes of a key row in LDS (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
+  constexpr int VS = 128 + 8;       // bytes of a V^T row (64 keys) in LDS (+8: the 8-byte reads of 32 rows hit 32 bank pairs)
+  __shared__ __attribute__((aligned(16))) unsigned char sK[BT * KS];
+  __shared__ __attribute__((aligned(16))) unsigned char sV[32 * DK * VS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+  const int64_t nq = (a.S + BQ - 1) / BQ;
+  const int64_t qt = a.mode == 2 ? nq - 1 - (int64_t)blockIdx.x : (int64_t)blockIdx.x;  // causal: the long tiles first
+  const int64_t h = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + h / (a.heads / a.kv_heads);
+  const int64_t q0 = qt * BQ, qi = q0 + wave * 32 + l31;
+  const int64_t off = a.T - a.S;  // causal: key j is visible to query i iff j <= i + off
+  const float NEG_INF = -__builtin_inff();
+
+  // ---- this lane's query row, quantized: fragment ks holds d = 16 ks + 8 lh .. + 7
+  bf16x8 qf[2 * DK];
+#pragma unroll
+  for (int ks = 0; ks < 2 * DK; ++ks) {
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (qi < a.S && ks * 16 < a.D) {
+      float v[16];
+      qmm::load16<DT>(a.q, b * a.q_bs + h * a.q_hs + qi * a.q_rs + ks * 16, 16, a.qvec, v);
+      qmm::quant16_bf16<DT != LQER_F16>(v, a.q0, w);
+    }
+    const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
+    qf[ks] = __builtin_bit_cast(bf16x8, f);
+  }
+
+  // ---- key tiles this workgroup / wave / lane looks at
+  const int64_t q_last = (q0 + BQ < a.S ? q0 + BQ : a.S) - 1;
+  int64_t t_end = a.T;  // keys [0, t_end) are visible to some query of the workgroup
+  if (a.mode == 2) {
+    const int64_t e = q_last + off + 1;
+    t_end = e < 0 ? 0 : (e < a.T ? e : a.T);
+  }
+  const int nt = (int)((t_end + BT - 1) / BT);
+  int64_t w_end = a.T;  // ... of this wave
+  if (a.mode == 2) {
+    const int64_t e = q0 + wave * 32 + 31 + off + 1;
+    w_end = e < 0 ? 0 : (e < a.T ? e : a.T);
+  }
+  int64_t tmax = a.T - 1;  // the last key visible to this lane's query
+  if (a.mode == 2) tmax = qi + off < tmax ? qi + off : tmax;
+  const int64_t qic = qi < a.S ? qi : a.S - 1;
+  const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + qic * a.m_rs : 0;
+
+  // (the staged pieces travel BY VALUE: arrays captured by reference in these lambdas ended up in scratch memory)
+  struct Stage {
+    uint4 r[DK];
+  };
+  auto fetch_k = [&](int it) {
+    Stage st;
+    const bf16_t* base = a.kimg + (z * a.Tp + (int64_t)it * BT) * a.Dp;
+#pragma unroll
+    for (int u = 0; u < DK; ++u) {
+      const int p = tid + 256 * u, row = p / (4 * DK), ch = p % (4 * DK);
+      st.r[u] = *(const uint4*)(base + (int64_t)row * a.Dp + ch * 8);
+    }
+    return st;
+  };
+  auto put_k = [&](const Stage st) {
+#pragma unroll
+    for (int u = 0; u < DK; ++u) {
+      const int p = tid + 256 * u, row = p / (4 * DK), ch = p % (4 * DK);
+      *(uint4*)(sK + row * KS + ch * 16) = st.r[u];
+    }
+  };
+  auto fetch_v = [&](int it) {
+    Stage st;
+    const bf16_t* base = a.vimg + z * VD * a.Tv + (int64_t)it * BT;
+#pragma unroll
+    for (int u = 0; u < DK; ++u) {
+      const int p = tid + 256 * u, row = p >> 3, ch = p & 7;
+      st.r[u] = *(const uint4*)(base + (int64_t)row * a.Tv + ch * 8);
+    }
+    return st;
+  };
+  auto put_v = [&](const Stage st) {
+#pragma unroll
+    for (int u = 0; u < DK; ++u) {
+      const int p = tid + 256 * u, row = p >> 3, ch = p & 7;
+      *(uint2*)(sV + row * VS + ch * 16) = make_uint2(st.r[u].x, st.r[u].y);
+      *(uint2*)(sV + row * VS + ch * 16 + 8) = make_uint2(st.r[u].z, st.r[u].w);
+    }
+  };
+
+  // S2 of the 32-key subtile at tb for this lane's query: s2[r] is key tb + (r & 3) + 8 (r >> 2) + 4 lh
+  auto scores = [&](int64_t tb, int u, float (&s2)[16]) {
+    float mk[16];
+    if (a.mode == 1) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int64_t t = tb + 8 * g + 4 * lh;
+        if (a.mvec) {  // (T a multiple of 4: a group of four lies inside the row or behind it - read from a clamped address, unused then)
+          const int64_t tc = t < a.T ? t : a.T - 4;
+          if constexpr (DT == LQER_F32) {
+            const float4 m4 = *(const float4*)((const float*)a.mask + moff + tc);
+            mk[4 * g] = m4.x, mk[4 * g + 1] = m4.y, mk[4 * g + 2] = m4.z, mk[4 * g + 3] = m4.w;
+          } else {
+            const uint2 m2 = *(const uint2*)((const bf16_t*)a.mask + moff + tc);
+            const uint32_t wd[2] = {m2.x, m2.y};
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              if constexpr (DT == LQER_F16) {
+                typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+                const h2 hv = __builtin_bit_cast(h2, wd[j]);
+                mk[4 * g + 2 * j] = (float)hv[0], mk[4 * g + 2 * j + 1] = (float)hv[1];
+              } else {
+                mk[4 * g + 2 * j] = __uint_as_float(wd[j] << 16), mk[4 * g + 2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
+              }
+            }
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) mk[4 * g + j] = t + j < a.T ? load_elem<DT>(a.mask, moff + t + j) : 0.f;
+        }
+      }
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 2 * DK; ++ks) {
+      const bf16x8 kf = *(const bf16x8*)(sK + (32 * u + l31) * KS + (2 * ks + lh) * 16);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float s = rnd<DT>(rnd<DT>(acc[r]) * a.scaling);
+      if (a.mode == 1) s = rnd<DT>(s + mk[r]);
+      s2[r] = s;
+    }
+  };
+
+  // ---- sweep 1: row maximum and row sum of exp(S2 - maximum), per lane over its own keys, then across the lane pair
+  float m = NEG_INF, l = 0.f;
+  Stage kr = fetch_k(0), vr;  // (nt = 0: rows 0-63 of the image exist)
+  for (int it = 0; it < nt; ++it) {
+    __syncthreads();  // the previous tile's fragment reads are done
+    put_k(kr);
+    __syncthreads();
+    kr = fetch_k(it + 1 < nt ? it + 1 : it);  // the next tile's loads travel under this tile's work (past the end: a re-read, unused)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int64_t tb = (int64_t)it * BT + 32 * u;
+      if (tb >= w_end) continue;  // wave-uniform: no key of the subtile is visible to the wave
+      float s2[16];
+      scores(tb, u, s2);
+      const int64_t lim = tmax - tb - 4 * lh;  // register r is visible iff (r & 3) + 8 (r >> 2) <= lim
+      float tm = NEG_INF;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tm = (r & 3) + 8 * (r >> 2) <= lim ? fmaxf(tm, s2[r]) : tm;
+      const float mn = fmaxf(m, tm), mref = mn == NEG_INF ? 0.f : mn;
+      float ls = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ls += (r & 3) + 8 * (r >> 2) <= lim ? exp_neg(s2[r] - mref) : 0.f;
+      l = l * exp_neg(m - mref) + ls;
+      m = mn;
+    }
+  }
+  float M, L;
+  {
+    const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+    const auto sl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l), __float_as_uint(l), false, false);
+    const float m0 = __uint_as_float(sm[0]), m1 = __uint_as_float(sm[1]), l0 = __uint_as_float(sl[0]), l1 = __uint_as_float(sl[1]);
+    M = fmaxf(m0, m1);
+    const float mref = M == NEG_INF ? 0.f : M;
+    L = l0 * exp_neg(m0 - mref) + l1 * exp_neg(m1 - mref);
+  }
+  if (a.stats && lh == 0 && qi < a.S) {
+    float* st = a.stats + ((b * a.heads + h) * a.S + qi) * 2;
+    st[0] = M, st[1] = L;
+  }
+
+  // ---- sweep 2: S2 again -> P ->DT -> Q_x1 -> O^T += Vq^T P^T
+  f32x16 o[DK];
+#pragma unroll
+  for (int dt = 0; dt < DK; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+  kr = fetch_k(0), vr = fetch_v(0);
+  for (int it = 0; it < nt; ++it) {
+    __syncthreads();
+    put_k(kr);
+    put_v(vr);
+    __syncthreads();
+    kr = fetch_k(it + 1 < nt ? it + 1 : it);
+    vr = fetch_v(it + 1 < nt ? it + 1 : it);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int64_t tb = (int64_t)it * BT + 32 * u;
+      if (tb >= w_end) continue;
+      float s2[16];
+      scores(tb, u, s2);
+      const int64_t lim = tmax - tb - 4 * lh;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s2[r] = (r & 3) + 8 * (r >> 2) <= lim ? rnd<DT>(exp_neg(s2[r] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {  // registers 8 s .. 8 s + 7: keys tb + 16 s + {0-3, 8-11} + 4 lh - half a block of 16, one k-step of P V
+        const float v8[8] = {s2[8 * s], s2[8 * s + 1], s2[8 * s + 2], s2[8 * s + 3], s2[8 * s + 4], s2[8 * s + 5], s2[8 * s + 6], s2[8 * s + 7]};
+        uint32_t w[4];
+        quant8of16_bf16<DT != LQER_F16>(v8, a.q1, w);
+        const u32x4 pw = {w[0], w[1], w[2], w[3]};
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
+#pragma unroll
+        for (int dt = 0; dt < DK; ++dt) {
+          const unsigned char* vp = sV + (32 * dt + l31) * VS + (32 * u + 16 * s + 4 * lh) * 2;
+          const uint2 v0 = *(const uint2*)vp, v1 = *(const uint2*)(vp + 16);
+          const u32x4 vw = {v0.x, v0.y, v1.x, v1.y};
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vw), pf, o[dt], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // ---- O^T: this lane's query, d = 32 dt + 8 (r >> 2) + 4 lh + (r & 3)
+  if (qi < a.S) {
+    const int64_t at0 = b * a.o_bs + h * a.o_hs + qi * a.o_rs;
+#pragma unroll
+    for (int dt = 0; dt < DK; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = 32 * dt + 8 * g + 4 * lh;
+        if (d < a.D) {
+          const float o4[4] = {o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]};
+          store_row4<DT>(a.out, at0 + d, d, (int)a.D, o4);
+        }
+      }
+  }
+}
+
+template <int DT>
+static int launch(const void* q, const void* k, const void* v, Args a, const QP& qk, const QP& qv, const int64_t (&ks)[3], const int64_t (&vs)[3],
+                  int64_t batch, hipStream_t st) {
+  const int esz = DT == LQER_F32 ? 4 : 2;
+  auto al16 = [&](const void* p, const int64_t (&s)[3]) {
+    return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
+  };
+  const unsigned nz = (unsigned)(batch * a.kv_heads);
+  k_attn_kimage<DT><<<dim3((unsigned)(a.Dp / 64), (unsigned)(a.Tp / 64), nz), 256, 0, st>>>(k, a.D, a.T, ks[0], ks[1], ks[2], a.kv_heads, qk,
+                                                                                        (bf16_t*)a.kimg, a.Tp, a.Dp, al16(k, ks));
+  k_attn_vimage<DT><<<dim3((unsigned)(VD / 64), (unsigned)(a.Tv / 64), nz), 256, 0, st>>>(v, a.D, a.T, vs[0], vs[1], vs[2], a.kv_heads, qv,
+                                                                                      (bf16_t*)a.vimg, a.Tv, al16(v, vs));
+  const int64_t qs[3] = {a.q_bs, a.q_hs, a.q_rs};
+  a.qvec = al16(q, qs);
+  // the mask is read in groups of four elements: rows and pointer aligned to that, and T a multiple of four
+  a.mvec = a.mode == 1 && a.T % 4 == 0 && (uintptr_t)a.mask % (4 * esz) == 0 && a.m_bs % 4 == 0 && a.m_hs % 4 == 0 && a.m_rs % 4 == 0;
+  const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)batch);
+  const int dk = (int)((a.D + 31) / 32);
+  switch (dk) {
+    case 1: k_attn_q<DT, 1><<<grid, 64 * NW, 0, st>>>(a); break;
+    case 2: k_attn_q<DT, 2><<<grid, 64 * NW, 0, st>>>(a); break;
+    case 3: k_attn_q<DT, 3><<<grid, 64 * NW, 0, st>>>(a); break;
+    default: k_attn_q<DT, 4><<<grid, 64 * NW, 0, st>>>(a); break;
+  }
+  return check_launch("lqer_attention_q");
+}
+
+}  // namespace attn
+
+static size_t attn_align(size_t v) { return (v + 255) / 256 * 256; }
+static void attn_dims(int64_t T, int64_t D, int64_t* Tp, int64_t* Dp, int64_t* Tv) {
+  *Tp = (T + 127) / 128 * 128, *Dp = (D + 63) / 64 * 64, *Tv = (T + 63) / 64 * 64;
+}
+// [K image: batch kv_heads x Tp x Dp bf16][V image: batch kv_heads x 128 x Tv bf16], each rounded up to 256 bytes
+size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, int64_t D) {
+  int64_t Tp, Dp, Tv;
+  attn_dims(T, D, &Tp, &Dp, &Tv);
+  return attn_align((size_t)(batch * kv_heads * Tp * Dp) * sizeof(bf16_t)) + attn_align((size_t)(batch * kv_heads * attn::VD * Tv) * sizeof(bf16_t));
+}
+
+int attention_q_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                         int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks, const int64_t* vs,
+                         const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
+                         const QP& q_w1, void* workspace, hipStream_t st) {
+  attn::Args a;
+  a.q = q, a.mask = mask, a.out = out, a.stats = row_stats;
+  a.S = S, a.T = T, a.D = D;
+  attn_dims(T, D, &a.Tp, &a.Dp, &a.Tv);
+  a.kimg = (const bf16_t*)workspace;
+  a.vimg = (const bf16_t*)((const unsigned char*)workspace + attn_align((size_t)(batch * kv_heads * a.Tp * a.Dp) * sizeof(bf16_t)));
+  a.q_bs = qs[0], a.q_hs = qs[1], a.q_rs = qs[2];
+  a.m_bs = mask ? ms[0] : 0, a.m_hs = mask ? ms[1] : 0, a.m_rs = mask ? ms[2] : 0;
+  a.o_bs = os[0], a.o_hs = os[1], a.o_rs = os[2];
+  a.heads = (int)heads, a.kv_heads = (int)kv_heads, a.mode = causal ? 2 : (mask ? 1 : 0);
+  a.scaling = scaling;
+  a.q0 = q_x0, a.q1 = q_x1;
+  a.qvec = a.mvec = false;
+  const int64_t k3[3] = {ks[0], ks[1], ks[2]}, v3[3] = {vs[0], vs[1], vs[2]};
+  switch (dtype) {
+    case LQER_F32: return attn::launch<LQER_F32>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st);
+    case LQER_F16: return attn::launch<LQER_F16>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st);
+    case LQER_BF16: return attn::launch<LQER_BF16>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st);
+  }
+  set_error("unknown dtype %d", dtype);
+  return LQER_E_INVALID;
+}
+
+}  // namespace lqer

@@ -127,6 +127,146 @@ def bmm_flexible(x, y, q_config):
     return generic_matmul_flexible(x, y, q_config, style="bmm")
 
 
+# ---- fused attention (csrc/attn_q.hip) --------------------------------------------------------------------------------------
+ROUTE_FUSED, ROUTE_UNFUSED = "fused", "unfused"
+_ATTN_MAX_D = 128
+_ATTN_MAX_T = 65535 * 64  # the image kernels put t / 64 on grid.y
+
+
+def _attn_fmts(cfg0: dict, cfg1: dict):
+    """The four lqer_qfmt_t (Q, K^T, P, V) when the fused kernel covers them - block_fp, width <= 8, blocks of 16 along the
+    last dim, no tiles that span rows - else None."""
+    fmts = []
+    for cfg in (cfg0, cfg1):
+        for key in ("x_quantizer", "w_quantizer"):
+            c = cfg.get(key, cfg.get("default"))
+            if c is None or c.get("name") != "block_fp":
+                return None
+            f = _fused_fmt(deepcopy(c))
+            if f is None or f.kind != _lib.Q_MXINT or f.block != 16:
+                return None
+            fmts.append(f)
+    return fmts
+
+
+def _attention_route(q, k, v, cfg0, cfg1, attention_mask=None, causal=False):
+    """(route tag, formats): which route attention_flexible takes for these operands."""
+    if not (q.dim() == k.dim() == v.dim() == 4) or not (q.is_cuda and k.is_cuda and v.is_cuda):
+        return ROUTE_UNFUSED, None
+    b, h, s, d = q.shape
+    hk, t = k.shape[1], k.shape[2]
+    ok = (q.dtype == k.dtype == v.dtype and q.dtype in ops._DT and d % 16 == 0 and 0 < d <= _ATTN_MAX_D and s > 0 and 0 < t <= _ATTN_MAX_T and b > 0
+          and not (causal and s > t)  # (rows without a visible key: the kernel gives them 0, the mask tensor a uniform row)
+          and k.shape == v.shape and k.shape[0] == b and k.shape[3] == d and hk > 0 and h % hk == 0
+          and b <= _MAX_GRID_Z and h <= _MAX_GRID_Z and b * hk <= _MAX_GRID_Z
+          and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1)
+    if ok and attention_mask is not None:
+        m = attention_mask
+        ok = (not causal and m.dim() == 4 and m.dtype == q.dtype and m.device == q.device and m.shape[3] == t and (m.stride(3) == 1 or t == 1)
+              and m.shape[0] in (1, b) and m.shape[1] in (1, h) and m.shape[2] in (1, s))
+    if not ok:
+        return ROUTE_UNFUSED, None
+    fmts = _attn_fmts(cfg0, cfg1)
+    return (ROUTE_FUSED, fmts) if fmts is not None else (ROUTE_UNFUSED, None)
+
+
+def _repeat_kv(t: torch.Tensor, n_rep: int) -> torch.Tensor:
+    if n_rep == 1:
+        return t
+    b, h, s, d = t.shape
+    return t[:, :, None, :, :].expand(b, h, n_rep, s, d).reshape(b, h * n_rep, s, d)
+
+
+def unfused_attention(q, k, v, cfg0, cfg1, scaling, attention_mask=None, dropout=0.0, training=False):
+    """The unfused sequence - the ONE body behind lqer_amd.attention.lqer_eager_attention_forward and every fall-back of
+    attention_flexible: grouped-query K / V repeated, matmul_flexible, scale, mask add, fp32 softmax, cast, (dropout,) matmul_flexible.
+    q [b, h, s, d], k / v [b, h_kv, t, d] -> out [b, h, s, d], weights [b, h, s, t]."""
+    b, h, s, d = q.shape
+    k, v = _repeat_kv(k, h // k.shape[1]), _repeat_kv(v, h // v.shape[1])
+    t = k.shape[2]
+    scores = matmul_flexible(q.reshape(b * h, s, d), k.reshape(b * h, t, d).transpose(1, 2), cfg0)
+    w = scores.reshape(b, h, s, t) * scaling
+    if attention_mask is not None:
+        w = w + attention_mask
+    w = torch.nn.functional.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
+    w = torch.nn.functional.dropout(w, p=dropout, training=training)
+    out = matmul_flexible(w.reshape(b * h, s, t), v.reshape(b * h, t, d), cfg1)
+    return out.reshape(b, h, s, d), w
+
+
+def _causal_mask(s, t, dtype, device):
+    """The additive tensor form of the causal rule, as eager_mask builds it: the dtype's most negative finite value where j > i + (t - s)."""
+    i, j = torch.arange(s, device=device)[:, None], torch.arange(t, device=device)[None, :]
+    return torch.zeros(s, t, dtype=dtype, device=device).masked_fill_(j > i + (t - s), torch.finfo(dtype).min)[None, None]
+
+
+def _bcast_stride(m: torch.Tensor, dim: int) -> int:
+    return 0 if m.shape[dim] == 1 else m.stride(dim)
+
+
+@torch.no_grad()
+def attention_flexible(q, k, v, cfg0, cfg1, scaling, attention_mask=None, causal=False, out_layout="bhsd", return_stats=False,
+                       return_route=False):
+    """softmax(Q_x0(q) Q_w0(k^T) * scaling + mask) -> Q_x1 -> @ Q_w1(v) on q [b, h, s, d], k / v [b, h_kv, t, d] (grouped-query heads
+    through the head mapping): lqer_eager_attention_forward's computation, every intermediate rounded to the operands' dtype where
+    that route materialises it.  With the templates' quantizers (block_fp, width <= 8, blocks of 16), d a multiple of 16 up to 128
+    and rows dense along d it is ONE fused HIP kernel behind two small image kernels (lqer_attention_q, csrc/attn_q.hip) and the
+    scores stay on the chip; anything else runs the unfused sequence with that route's results - never an approximation.
+    `attention_mask`: additive, broadcastable [b|1, h|1, s|1, t] of q's dtype; `causal`: key j visible to query i iff j <= i + (t - s)
+    (the tensor form of that rule: with s > t, where early rows see no key at all, the unfused sequence runs on that tensor).
+    `out_layout`: "bhsd" or "bshd" (what the HuggingFace attention interface returns, written directly).  Returns out, then
+    `stats` [b, h, s, 2] fp32 = {row max of the masked scores, row sum of exp(score - max)} with return_stats (fused route only,
+    else None), then the route tag with return_route."""
+    if out_layout not in ("bhsd", "bshd"):
+        raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
+    if attention_mask is not None and causal:
+        raise ValueError("attention_flexible: attention_mask and causal=True are two forms of one mask - pass one")
+    ops._need_gpu(q, k, v, attention_mask)
+    route, fmts = _attention_route(q, k, v, cfg0, cfg1, attention_mask, causal)
+    stats = None
+    if route == ROUTE_FUSED:
+        b, h, s, d = q.shape
+        hk, t = k.shape[1], k.shape[2]
+        out = torch.empty((b, h, s, d) if out_layout == "bhsd" else (b, s, h, d), dtype=q.dtype, device=q.device)
+        ob = out if out_layout == "bhsd" else out.transpose(1, 2)
+        if return_stats:
+            stats = torch.empty(b, h, s, 2, dtype=torch.float32, device=q.device)
+        tri = lambda *xs: (C.c_int64 * 3)(*xs)
+        m = attention_mask
+        L = _lib.lib()
+        with torch.cuda.device(q.device):
+            nws = L.lqer_attention_q_workspace_bytes(b, h, hk, s, t, d)
+            ws = ops.workspace(q.device, max(nws, 16))
+            _lib.check(L.lqer_attention_q(q.data_ptr(), k.data_ptr(), v.data_ptr(), m.data_ptr() if m is not None else None, out.data_ptr(),
+                                          stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, hk, s, t, d,
+                                          tri(q.stride(0), q.stride(1), q.stride(2)), tri(k.stride(0), k.stride(1), k.stride(2)),
+                                          tri(v.stride(0), v.stride(1), v.stride(2)),
+                                          tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
+                                          tri(ob.stride(0), ob.stride(1), ob.stride(2)), float(scaling), int(bool(causal)),
+                                          C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
+                                          ops._stream(q.device)),
+                       "lqer_attention_q")
+    else:
+        if causal:
+            attention_mask = _causal_mask(q.shape[2], k.shape[2], q.dtype, q.device)
+        out, _ = unfused_attention(q, k, v, cfg0, cfg1, scaling, attention_mask)
+        if out_layout == "bshd":
+            out = out.transpose(1, 2).contiguous()
+    res = (out,)
+    if return_stats:
+        res += (stats,)
+    if return_route:
+        res += (route,)
+    return res[0] if len(res) == 1 else res
+
+
+def _route_tag(q, k, v, cfg0, cfg1, attention_mask=None, causal=False) -> str:
+    return _attention_route(q, k, v, cfg0, cfg1, attention_mask, causal)[0]
+
+
+attention_flexible.route = _route_tag
+
+
 QUANTIZED_FUNCTION_MAP = {"matmul": {"flexible": matmul_flexible}, "bmm": {"flexible": bmm_flexible}}
 
 
