@@ -271,26 +271,16 @@ int act16_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t
   const bf16_t* const a_frag = (const bf16_t*)a_b16 + rp * Kp;
   const unsigned grid = (unsigned)((M + a16f::ROWS - 1) / a16f::ROWS);
   const int lds = (int)a16f::lds_bytes((int)rp);
-#define A16F_LAUNCH(DTv, RTv)                                                                                              \
-  do {                                                                                                                     \
-    static LdsLimitOnce once;                                                                                              \
-    once.set((const void*)a16f::k_act16_fused<DTv, RTv>, 160 * 1024);                                                       \
-    a16f::k_act16_fused<DTv, RTv><<<grid, 512, lds, st>>>(x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);                     \
-  } while (0)
-#define A16F_DT(DTv)                     \
-  switch (rp / 16) {                     \
-    case 1: A16F_LAUNCH(DTv, 1); break;  \
-    case 2: A16F_LAUNCH(DTv, 2); break;  \
-    default: A16F_LAUNCH(DTv, 4); break; \
-  }
-  if (dtype == LQER_F16) {
-    A16F_DT(LQER_F16)
-  } else {
-    A16F_DT(LQER_BF16)
-  }
-#undef A16F_DT
-#undef A16F_LAUNCH
-  return check_launch("quantize_act_xa (fused block-16 route)");
+  auto run = [&](auto dt) {
+    constexpr int DT = decltype(dt)::value, LIMIT = 160 * 1024;
+    const char* const what = "quantize_act_xa (fused block-16 route)";
+    switch (rp / 16) {  // 16-column tiles of the padded rank
+      case 1: return launch_k<a16f::k_act16_fused<DT, 1>, LIMIT>(what, grid, 512, lds, st, x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);
+      case 2: return launch_k<a16f::k_act16_fused<DT, 2>, LIMIT>(what, grid, 512, lds, st, x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);
+      default: return launch_k<a16f::k_act16_fused<DT, 4>, LIMIT>(what, grid, 512, lds, st, x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);
+    }
+  };
+  return dtype == LQER_F16 ? run(std::integral_constant<int, LQER_F16>{}) : run(std::integral_constant<int, LQER_BF16>{});
 }
 
 }  // namespace lqer

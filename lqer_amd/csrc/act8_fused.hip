@@ -78,7 +78,7 @@ __global__ __launch_bounds__(512) void k_act8_fused(const void* __restrict__ x, 
   // ---- requests: the row, then the first batch of this wave's A^T fragments (independent of the row: their latency passes under the
   // quantizer's arithmetic)
   const u32x4* p = (const u32x4*)((const bf16_t*)x + row * ld);
-  // (the GEMM's pre-pass behind this launch wants its atomicMax cells zero - gemm_amax_zero_bytes: one store per thread here instead of a
+  // (the GEMM's pre-pass behind this launch wants its atomicMax cells zero - GemmPlan::prep_zero_bytes: one store per thread here instead of a
   // memset launch there)
   if ((int)(blockIdx.x * 512 + threadIdx.x) < zero_n) zero_p[blockIdx.x * 512 + threadIdx.x] = 0.f;
   // register u of lane l holds chunk 2 l + (u & 1) + 128 (u >> 1): a lane's registers 2 v, 2 v + 1 are NEIGHBOURING chunks, so their 16
@@ -264,19 +264,13 @@ static int launch(const void* x, int64_t M, int64_t K, int64_t ld, const QP& qx,
                   const QP& qa, int L, int rp, bf16_t* xaq, float* zero_p, int zero_n, hipStream_t st) {
   const unsigned grid = (unsigned)((M + ROWS - 1) / ROWS);
   const int lds = (int)lds_bytes(cols_p8, rp);
-#define A8F_LAUNCH(RTv)                                                                                                            \
-  do {                                                                                                                             \
-    static LdsLimitOnce once;                                                                                                      \
-    once.set((const void*)k_act8_fused<DT, MAXCH, RTv>, 160 * 1024);                                                                \
-    k_act8_fused<DT, MAXCH, RTv><<<grid, 512, lds, st>>>(x, M, K, ld, qx, xq8, cols_p8, xscale, a_frag, qa, L, xaq, zero_p, zero_n); \
-  } while (0)
-  switch (rp / 16) {
-    case 1: A8F_LAUNCH(1); break;
-    case 2: A8F_LAUNCH(2); break;
-    default: A8F_LAUNCH(4); break;
+  constexpr int LIMIT = 160 * 1024;
+  const char* const what = "quantize_act_xa (fused int8 route)";
+  switch (rp / 16) {  // 16-column tiles of the padded rank
+    case 1: return launch_k<k_act8_fused<DT, MAXCH, 1>, LIMIT>(what, grid, 512, lds, st, x, M, K, ld, qx, xq8, cols_p8, xscale, a_frag, qa, L, xaq, zero_p, zero_n);
+    case 2: return launch_k<k_act8_fused<DT, MAXCH, 2>, LIMIT>(what, grid, 512, lds, st, x, M, K, ld, qx, xq8, cols_p8, xscale, a_frag, qa, L, xaq, zero_p, zero_n);
+    default: return launch_k<k_act8_fused<DT, MAXCH, 4>, LIMIT>(what, grid, 512, lds, st, x, M, K, ld, qx, xq8, cols_p8, xscale, a_frag, qa, L, xaq, zero_p, zero_n);
   }
-#undef A8F_LAUNCH
-  return check_launch("quantize_act_xa (fused int8 route)");
 }
 
 }  // namespace a8f
@@ -334,15 +328,17 @@ int act8_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t 
   const int maxch = nch_p <= 64 * 8 ? 8 : nch_p <= 64 * 12 ? 12 : (dtype == LQER_F16 && nch_p <= 64 * 28) ? 28 : 0;
   if (maxch == 0 || (dtype != LQER_F16 && dtype != LQER_BF16)) return LQER_E_UNSUPPORTED;
   if (zeroed) *zeroed = zfit;  // (every return below this line has launched the kernel)
-#define A8F(DTv, MAXCHv) return a8f::launch<DTv, MAXCHv>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st)
+  auto run = [&](auto dt, auto mc) {
+    return a8f::launch<decltype(dt)::value, decltype(mc)::value>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st);
+  };
+  using std::integral_constant;
   if (dtype == LQER_F16) {
-    if (maxch == 8) A8F(LQER_F16, 8);
-    if (maxch == 12) A8F(LQER_F16, 12);
-    A8F(LQER_F16, 28);
+    if (maxch == 8) return run(integral_constant<int, LQER_F16>{}, integral_constant<int, 8>{});
+    if (maxch == 12) return run(integral_constant<int, LQER_F16>{}, integral_constant<int, 12>{});
+    return run(integral_constant<int, LQER_F16>{}, integral_constant<int, 28>{});
   }
-  if (maxch == 8) A8F(LQER_BF16, 8);
-  A8F(LQER_BF16, 12);
-#undef A8F
+  if (maxch == 8) return run(integral_constant<int, LQER_BF16>{}, integral_constant<int, 8>{});
+  return run(integral_constant<int, LQER_BF16>{}, integral_constant<int, 12>{});
 }
 
 }  // namespace lqer

@@ -96,20 +96,12 @@ int split_act_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t l
   const bool vec = ((uintptr_t)x % 16 == 0) && ((ldx * esz) % 16 == 0);
   const int64_t total = M * (Kp / 8);
   const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-#define SPLIT_LAUNCH(DT, L) k_split_act<DT, L><<<grid, 256, 0, st>>>(x, M, K, ldx, vec, xq, Kp)
-  if (dtype == LQER_BF16 && limbs == 1)
-    SPLIT_LAUNCH(LQER_BF16, 1);
-  else if (dtype == LQER_F16 && limbs == 2)
-    SPLIT_LAUNCH(LQER_F16, 2);
-  else if (dtype == LQER_F32 && limbs == 3)
-    SPLIT_LAUNCH(LQER_F32, 3);
-  else {
-    set_error("x_quantizer passthrough: %d limb(s) do not hold element type %d exactly (bf16: width 8 = 1 limb, fp16: "
-              "width 11 = 2, fp32: width 24 = 3)", limbs, dtype);
-    return LQER_E_INVALID;
-  }
-#undef SPLIT_LAUNCH
-  return check_launch("split_act");
+  if (dtype == LQER_BF16 && limbs == 1) return launch_k<k_split_act<LQER_BF16, 1>>("split_act", grid, 256, 0, st, x, M, K, ldx, vec, xq, Kp);
+  if (dtype == LQER_F16 && limbs == 2) return launch_k<k_split_act<LQER_F16, 2>>("split_act", grid, 256, 0, st, x, M, K, ldx, vec, xq, Kp);
+  if (dtype == LQER_F32 && limbs == 3) return launch_k<k_split_act<LQER_F32, 3>>("split_act", grid, 256, 0, st, x, M, K, ldx, vec, xq, Kp);
+  set_error("x_quantizer passthrough: %d limb(s) do not hold element type %d exactly (bf16: width 8 = 1 limb, fp16: "
+            "width 11 = 2, fp32: width 24 = 3)", limbs, dtype);
+  return LQER_E_INVALID;
 }
 
 }  // namespace lqer

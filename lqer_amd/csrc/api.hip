@@ -4,7 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace lqer {
 
@@ -169,10 +169,10 @@ static bool i8_formats_ok(const lqer_linear_desc_t* d) {
 // LQER_Q_PASSTHROUGH_F16: a dense fp16 tensor whose extents are already the padded ones IS the activation image
 // (M a multiple of the row padding: the tile kernels read whole row tiles; M <= 64: the small-M kernel and the side
 // GEMM never read past row M - 1 - unless B_out blocks other than 16 send a decode-size call to the tile kernel)
-static bool f16_image_is_input(const lqer_linear_desc_t* d, const void* x, int64_t M, int64_t ldx) {
-  // (asked of the dispatcher itself, so the two can not drift: an integer B_out, or B_out blocks other than 16, send a
-  // decode-size call to the tile kernel, whose buffer range covers whole row tiles)
-  const bool smallm = M <= 64 && x_is_f16(d) && lqer_gemm_route(d, M, LQER_F16) == LQER_ROUTE_SMALLM;
+// (route: the plan's for (d, M, LQER_F16) - an integer B_out, or B_out blocks other than 16, send a decode-size call to the tile kernel,
+// whose buffer range covers whole row tiles)
+static bool f16_image_is_input(const lqer_linear_desc_t* d, const void* x, int64_t M, int64_t ldx, int route) {
+  const bool smallm = M <= 64 && route == LQER_ROUTE_SMALLM;
   return x_is_f16(d) && ldx == d->in_features && d->in_features % LQER_K_ALIGN == 0 && (M % LQER_M_ALIGN == 0 || smallm) &&
          ((uintptr_t)x & 15) == 0 && w_limbs(d) == 1;
 }
@@ -406,7 +406,6 @@ int lqer_linear_sizes(const lqer_linear_desc_t* d, int64_t m_max, lqer_linear_si
   }
   // (the int8 activation image + row scales of LQER_Q_MXINT_I8 fit the bf16 image's slot: K >= 128)
   const size_t act = act_image_bytes(d, m_max);
-  (void)wl;
   if (x_is_i8(d) && i8_act_image_bytes(m_max, d->in_features) + Mp * sizeof(float) > act) {
     set_error("linear_sizes: int8 activation image larger than the bf16 one (K %d)", d->in_features);
     return LQER_E_UNSUPPORTED;
@@ -511,23 +510,26 @@ int lqer_lowrank_xa(const lqer_linear_desc_t* d, const void* xq, int64_t M, cons
                              (bf16_t*)xaq, (float*)scratch, scratch_bytes, (hipStream_t)stream);
 }
 
-// lqer_linear_forward only: the GEMM call behind this one wants `bytes` at the head of the shared scratch zeroed (gemm_amax_zero_bytes);
+// lqer_linear_forward only: the GEMM call behind this one wants `bytes` at the head of the shared scratch zeroed (GemmPlan::prep_zero_bytes);
 // `done` says whether a kernel of this call wrote the zeros (the one-launch int8 activation kernel does, the other routes do not)
 struct AmaxZeroReq {
   void* p;       // head of the scratch the GEMM call will be handed
   size_t bytes;
   bool done;
 };
-static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, GemmArgs& g);
-// the request for M tokens of this descriptor: bytes > 0 when the GEMM launches a pre-pass on atomicMax cells
-static AmaxZeroReq amax_zero_request(const lqer_linear_desc_t* d, int64_t M, int dtype, int a_limbs, void* gemm_scratch) {
-  AmaxZeroReq zr{gemm_scratch, 0, false};
-  if (d && gemm_scratch && d->rank > 0 && x_is_i8(d) && a_limbs == -1 && M > 0) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    if (gemm_shape_args(d, M, dtype, g) == LQER_OK) zr.bytes = gemm_amax_zero_bytes(g, true);
-  }
-  return zr;
+// What a GEMM call of (d, M, dtype) launches: the kernel arguments that depend on the descriptor and the token count alone, and their
+// plan.  Evaluated once per descriptor a call launches with and handed down (lqer_linear_forward -> linear_gemm_impl).
+struct Planned {
+  int rc;  // of gemm_shape_args (its text kept in p.msg: calls in between may leave their own)
+  GemmArgs g;
+  GemmPlan p;
+};
+static Planned plan_for(const lqer_linear_desc_t* d, int64_t M, int dtype, int b_limbs, bool for_launch = true);
+static int plan_route(const Planned& pl);
+// a call in front of the GEMM call can zero the pre-pass cells on its behalf (GemmPlan::prep_zero_bytes at the head of gemm_scratch): the
+// int8 route's one-launch activation kernel
+static bool can_prep_amax(const lqer_linear_desc_t* d, int64_t M, int a_limbs, const void* gemm_scratch) {
+  return d && gemm_scratch && d->rank > 0 && x_is_i8(d) && a_limbs == -1 && M > 0;
 }
 static int quantize_act_xa_single(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx, const void* a_t,
                                   int a_limbs, void* xq, void* xaq, void* scratch, size_t scratch_bytes, void* stream, AmaxZeroReq* zr);
@@ -543,7 +545,11 @@ int lqer_quantize_act_xa_prep(const lqer_linear_desc_t* d, const void* x, int dt
                               int a_limbs, void* xq, void* xaq, void* scratch, size_t scratch_bytes, void* gemm_scratch,
                               size_t* ready_bytes, void* stream) {
   if (ready_bytes) *ready_bytes = 0;
-  AmaxZeroReq zr = amax_zero_request(d, M, dtype, a_limbs, ready_bytes ? gemm_scratch : nullptr);
+  AmaxZeroReq zr{ready_bytes ? gemm_scratch : nullptr, 0, false};
+  if (can_prep_amax(d, M, a_limbs, zr.p)) {  // (a split-API call: the plan of the GEMM call that will follow)
+    const Planned pl = plan_for(d, M, dtype, 0);
+    if (pl.rc == LQER_OK) zr.bytes = pl.p.prep_zero_bytes;
+  }
   const int rc = quantize_act_xa_impl(d, x, dtype, M, ldx, a_t, a_limbs, xq, xaq, scratch, scratch_bytes, stream, &zr);
   if (rc == LQER_OK && ready_bytes && zr.done) *ready_bytes = zr.bytes;
   return rc;
@@ -603,7 +609,7 @@ static int quantize_act_xa_single(const lqer_linear_desc_t* d, const void* x, in
   if (x_is_f16(d)) {
     if (!need_f16(d, dtype, "quantize_act_xa")) return LQER_E_INVALID;
     if (xq == x) {  // the tensor itself is the image: nothing to write
-      if (!f16_image_is_input(d, x, M, ldx)) {
+      if (!f16_image_is_input(d, x, M, ldx, M <= 64 ? lqer_gemm_route(d, M, LQER_F16) : LQER_ROUTE_TILE128)) {
         set_error("quantize_act_xa: xq == x needs a dense fp16 tensor with K %% %d == 0, M %% %d == 0 or M <= 64, 16-byte aligned",
                   LQER_K_ALIGN, LQER_M_ALIGN);
         return LQER_E_INVALID;
@@ -694,9 +700,32 @@ static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, Ge
     g.i8_shift = !(d->w_fmt.block <= 0 || d->w_fmt.block >= d->in_features);  // one weight block per row: no shifts at all
     g.w_i8codes = w_panel_limbs(d) > 1 ? 1 : 0;  // weights of 5..8 bits: the image holds the codes, one exponent per row (lqer_i8_prepare checked)
     if (g.w_i8codes) g.i8_shift = 0;
-    g.w8 = (const uint8_t*)(uintptr_t)1;  // (route query: "the image exists"; lqer_linear_gemm sets the real pointer)
   }
   return LQER_OK;
+}
+
+// for_launch = false (the route queries): no HIP call - the CU count, which only the travel of the row maxima depends on, is not asked
+static Planned plan_for(const lqer_linear_desc_t* d, int64_t M, int dtype, int b_limbs, bool for_launch) {
+  Planned pl;
+  memset(&pl.g, 0, sizeof(pl.g));
+  pl.rc = gemm_shape_args(d, M, dtype, pl.g);
+  pl.g.b_limbs = b_limbs;
+  if (pl.rc == LQER_OK) {
+    // (the device's CUs decide one thing: whether the int8 kernel exchanges the row maxima of a wide-block B_out itself)
+    const bool asks_cus = for_launch && x_is_i8(d) && d->rank > 0 && d->b_out_fmt.kind == LQER_Q_MXINT && d->b_out_fmt.block != 16;
+    pl.p = plan_gemm(pl.g, d->rank > 0, x_is_i8(d), dtype, asks_cus ? device_cus() : 0);
+  } else {
+    pl.p = GemmPlan{};
+    snprintf(pl.p.msg, sizeof(pl.p.msg), "%s", g_err);
+  }
+  return pl;
+}
+
+// LQER_ROUTE_* of the plan, or the refusal the route queries report (with its text)
+static int plan_route(const Planned& pl) {
+  const int rc = pl.rc ? pl.rc : pl.p.err;
+  if (rc) set_error("%s", pl.p.msg);
+  return rc ? rc : pl.p.route;
 }
 
 int lqer_gemm_route(const lqer_linear_desc_t* d, int64_t M, int dtype) {
@@ -704,11 +733,7 @@ int lqer_gemm_route(const lqer_linear_desc_t* d, int64_t M, int dtype) {
     set_error("gemm_route: bad argument");
     return LQER_E_INVALID;
   }
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  const int rc = gemm_shape_args(d, M, dtype, g);
-  if (rc) return rc;
-  return gemm_route(g, d->rank > 0);
+  return plan_route(plan_for(d, M, dtype, 0, false));
 }
 
 int lqer_gemm_tile_rows(const lqer_linear_desc_t* d, int64_t M, int dtype) {
@@ -716,45 +741,38 @@ int lqer_gemm_tile_rows(const lqer_linear_desc_t* d, int64_t M, int dtype) {
     set_error("gemm_tile_rows: bad argument");
     return LQER_E_INVALID;
   }
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  const int rc = gemm_shape_args(d, M, dtype, g);
-  if (rc) return rc;
-  const int route = gemm_route(g, d->rank > 0);
-  if (route < 0) return route;
-  switch (route) {
-    case LQER_ROUTE_SMALLM: return 0;
-    case LQER_ROUTE_TILE256: return 256;
-    case LQER_ROUTE_I8: return i8_tile_rows(g);
-    default: return gemm_tile_rows(g);
-  }
+  const Planned pl = plan_for(d, M, dtype, 0, false);
+  const int route = plan_route(pl);
+  return route < 0 ? route : pl.p.tile_rows;
 }
 
 static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                             int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
-                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed);
+                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl);
 
 int lqer_linear_gemm_ld(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                         int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
                         void* scratch, size_t scratch_bytes, void* stream) {
-  return linear_gemm_impl(d, xq, M, w_packed, xaq, xaq_ld, b_t, b_limbs, bias_q, y, dtype, ldy, scratch, scratch_bytes, stream, false);
+  return linear_gemm_impl(d, xq, M, w_packed, xaq, xaq_ld, b_t, b_limbs, bias_q, y, dtype, ldy, scratch, scratch_bytes, stream, false, nullptr);
 }
 
 int lqer_linear_gemm_prepared(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                               const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy, void* scratch,
                               size_t scratch_bytes, size_t ready_bytes, void* stream) {
   bool zeroed = false;
-  if (d && ready_bytes > 0) {  // (covers this launch's cells?  a_limbs = -1: the request's own condition, met by whoever prepared them)
-    const AmaxZeroReq zr = amax_zero_request(d, M, dtype, -1, scratch);
-    zeroed = zr.bytes > 0 && ready_bytes >= zr.bytes;
+  Planned pl;
+  const bool planned = ready_bytes > 0 && can_prep_amax(d, M, -1, scratch);  // (a_limbs = -1: met by whoever prepared the cells)
+  if (planned) {  // covers this launch's cells?
+    pl = plan_for(d, M, dtype, b_limbs);
+    zeroed = pl.rc == LQER_OK && pl.p.prep_zero_bytes > 0 && ready_bytes >= pl.p.prep_zero_bytes;
   }
   return linear_gemm_impl(d, xq, M, w_packed, xaq, d ? lqer_padded_r(d->rank) * xa_limbs(d) : 0, b_t, b_limbs, bias_q, y, dtype, ldy,
-                          scratch, scratch_bytes, stream, zeroed);
+                          scratch, scratch_bytes, stream, zeroed, planned ? &pl : nullptr);
 }
 
 static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                             int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
-                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed) {
+                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl) {
   if (!d || !xq || !w_packed || !y || M < 0 || ldy < d->out_features) {
     set_error("linear_gemm: bad argument");
     return LQER_E_INVALID;
@@ -769,10 +787,13 @@ static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t
     set_error("linear_gemm: b_limbs %d outside [0,3]", b_limbs);
     return LQER_E_INVALID;
   }
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  const int rc = gemm_shape_args(d, M, dtype, g);
-  if (rc) return rc;
+  Planned own;
+  if (!pl) own = plan_for(d, M, dtype, b_limbs), pl = &own;
+  if (pl->rc) {
+    set_error("%s", pl->p.msg);
+    return pl->rc;
+  }
+  GemmArgs g = pl->g;
   g.xq = (const bf16_t*)xq;
   g.wp = (const uint8_t*)w_packed;
   g.xaq = (const bf16_t*)xaq;
@@ -801,8 +822,7 @@ static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t
     g.xa_part = (const float*)scratch;
     g.aout = make_qp(d->a_out_fmt);
   }
-  g.amax_zeroed = amax_zeroed ? 1 : 0;
-  return gemm_dispatch(g, dtype, lowrank, scratch, scratch_bytes, (hipStream_t)stream);
+  return gemm_launch(pl->p, g, dtype, scratch, scratch_bytes, amax_zeroed, (hipStream_t)stream);
 }
 
 int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
@@ -818,30 +838,33 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
   int rc = lqer_linear_sizes(d, M, &sz);
   if (rc) return rc;
   HT_MARK(0);
+  // the one plan of this forward (its refusals are reported where the GEMM call reports them)
+  Planned pl = plan_for(d, M, dtype, b_limbs);
   lqer_linear_desc_t plain;
-  if (x_is_i8(d) && lqer_gemm_route(d, M, dtype) != LQER_ROUTE_I8) {
-    // token counts the int8 tile kernel does not serve run the bf16 kernels on the sign-magnitude image (same buffers)
+  if (x_is_i8(d) && plan_route(pl) != LQER_ROUTE_I8) {
+    // token counts the int8 tile kernel does not serve run the bf16 kernels on the sign-magnitude image (same buffers): a second
+    // descriptor, a second plan
     plain = *d;
     plain.x_fmt.kind = LQER_Q_MXINT;
     d = &plain;
+    pl = plan_for(d, M, dtype, b_limbs);
   }
   if (workspace_bytes < sz.workspace || (!workspace && sz.workspace)) {
     set_error("linear_forward: workspace %zu B < %zu B needed for M=%lld", workspace_bytes, sz.workspace, (long long)M);
     return LQER_E_WORKSPACE;
   }
   if (M == 0) return LQER_OK;
-  const size_t Kp = lqer_padded_k(d->in_features), Mp = lqer_padded_m(M);
+  const size_t Mp = lqer_padded_m(M);
   unsigned char* ws = (unsigned char*)workspace;
   void* xq = ws;
   const size_t rp = lqer_padded_r(d->rank);
-  const size_t xl = act_limbs(d), al = xa_limbs(d);
+  const size_t al = xa_limbs(d);
   HT_MARK(1);
-  if (dtype == LQER_F16 && f16_image_is_input(d, x, M, ldx)) xq = const_cast<void*>(x);  // no copy (never written)
+  if (dtype == LQER_F16 && f16_image_is_input(d, x, M, ldx, plan_route(pl))) xq = const_cast<void*>(x);  // no copy (never written)
   HT_MARK(2);
   const size_t act = act_image_bytes(d, M);
   void* xaq = ws + act;
   void* xa_scratch = ws + act + align_up(Mp * rp * 2 * al, 256);
-  (void)Kp, (void)xl;
   if (decode_partials_ok(d, M) && a_t && b_t) {
     HT_MARK(3);
     const size_t nscr = lqer_lowrank_xa_scratch_bytes(d, M);
@@ -853,17 +876,17 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
     // previous replay's tiles although its arguments - the host's per-call counter among them - are frozen)
     if (M <= 8 && a_limbs == 1 && !x_is_f16(d) && ((uintptr_t)x & 15) == 0 &&
         (ldx * esz) % 16 == 0 && b_limbs >= 1 && b_limbs <= 3) {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      rc = gemm_shape_args(d, M, dtype, g);
-      if (rc) return rc;
+      if (pl.rc) {
+        set_error("%s", pl.p.msg);
+        return pl.rc;
+      }
+      GemmArgs g = pl.g;
       HT_MARK(5);
       g.wp = (const uint8_t*)w_packed;
       g.bt = (const bf16_t*)b_t;
       g.bias = d->has_bias ? bias_q : nullptr;
       g.y = y;
       g.ldy = ldy;
-      g.b_limbs = b_limbs;
       g.aout = make_qp(d->a_out_fmt);
       const int bout = d->b_out_fmt.kind == LQER_Q_PASSTHROUGH ? 0 : 1;  // (decode_partials_ok: pass-through or blocks of 16)
       const DecodeMember one{g.wp, g.bt, g.bias, g.y, g.ldy, g.N, g.Np, g.rp, g.b_limbs};
@@ -876,16 +899,18 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
     // two launches: the GEMM sums the partial tiles of x A itself
     rc = lqer_quantize_act_xa(d, x, dtype, M, ldx, a_t, a_limbs, xq, nullptr, xa_scratch, nscr, stream);
     if (rc) return rc;
-    return lqer_linear_gemm(d, xq, M, w_packed, nullptr, b_t, b_limbs, bias_q, y, dtype, ldy, xa_scratch, nscr, stream);
+    return linear_gemm_impl(d, xq, M, w_packed, nullptr, lqer_padded_r(d->rank) * xa_limbs(d), b_t, b_limbs, bias_q, y, dtype, ldy, xa_scratch,
+                            nscr, stream, false, &pl);
   }
   // (a pre-pass on atomicMax cells behind the one-launch int8 activation kernel: that kernel zeroes the cells - the two calls share the
   // scratch, whose size is the larger of their needs - instead of a memset launch between them)
-  AmaxZeroReq zr = amax_zero_request(d, M, dtype, a_limbs, b_t ? xa_scratch : nullptr);
+  AmaxZeroReq zr{b_t ? xa_scratch : nullptr, 0, false};
+  if (can_prep_amax(d, M, a_limbs, zr.p) && pl.rc == LQER_OK) zr.bytes = pl.p.prep_zero_bytes;
   const size_t side_bytes = lqer_lowrank_xa_scratch_bytes(d, M), gemm_bytes = lqer_linear_gemm_scratch_bytes(d, M);
   rc = quantize_act_xa_impl(d, x, dtype, M, ldx, a_t, a_limbs, xq, xaq, xa_scratch, side_bytes, stream, &zr);
   if (rc) return rc;
   return linear_gemm_impl(d, xq, M, w_packed, d->rank > 0 ? xaq : nullptr, lqer_padded_r(d->rank) * xa_limbs(d), b_t, b_limbs, bias_q, y, dtype,
-                          ldy, xa_scratch, gemm_bytes, stream, zr.done);
+                          ldy, xa_scratch, gemm_bytes, stream, zr.done, &pl);
 }
 
 size_t lqer_group_workspace_bytes(int64_t K, int64_t rank_padded_sum) {

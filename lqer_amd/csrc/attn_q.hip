@@ -393,13 +393,7 @@ int attention_q_dispatch(const void* q, const void* k, const void* v, const void
   a.q0 = q_x0, a.q1 = q_x1;
   a.qvec = a.mvec = false;
   const int64_t k3[3] = {ks[0], ks[1], ks[2]}, v3[3] = {vs[0], vs[1], vs[2]};
-  switch (dtype) {
-    case LQER_F32: return attn::launch<LQER_F32>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st);
-    case LQER_F16: return attn::launch<LQER_F16>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st);
-    case LQER_BF16: return attn::launch<LQER_BF16>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  return with_dtype(dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st); });
 }
 
 }  // namespace lqer

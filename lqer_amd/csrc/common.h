@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/lqer_hip.h"
 
@@ -521,6 +522,20 @@ __host__ inline size_t i8_weight8_image_bytes(int64_t N, int64_t K) {
   return (size_t)(Np / 256) * (padded_k8(K) / 64) * (256 * 64) + (size_t)Np * sizeof(float);
 }
 
+// ---- tile constants of the fused GEMM that its launch plan (gemm_plan.hip) shares with the kernels --------------------------------
+constexpr int BM = 128, BN = 256, BK = 64;  // the 128-row tile kernel (gemm_w4a8.hip); every GEMM kernel's tiles are 256 columns wide
+constexpr int SM_MAX_M = 64;                // tokens handled by the small-M kernel (MT = ceil(M / 16) <= 4 token tiles)
+constexpr int LQER_I8_ROWS128_COST = 56;    // a 128-row tile of the int8 kernel, in hundredths of a 256-row one
+constexpr int LQER_M256_COST = 19;          // a 256 x 256 tile, in tenths of a 128 x 256 one
+#ifndef LQER_M256_MIN_M
+#define LQER_M256_MIN_M 512
+#endif
+#ifndef LQER_STAGE_MIN
+#define LQER_STAGE_MIN 32  // padded rank x limbs of B beyond which the tile kernel's side product goes through LDS
+#endif
+#ifndef LQER_AMAX_WAVES
+#define LQER_AMAX_WAVES 2048  // waves of one round of the B_out pre-pass (k_bout_amax)
+#endif
 #ifndef LQER_AMAX_NSEG
 #define LQER_AMAX_NSEG 16  // column-segment partials per row of a one-block-per-row B_out (int8 route: k_bout_amax -> k_lqer_gemm_i8)
 #define LQER_AMAX_NSEG_WIDE 32  // ... beyond N = 4096 (more than 8 column tiles per segment otherwise): twice the cells, the same scratch as the exchange's granules
@@ -652,11 +667,11 @@ struct GemmArgs {
   int w_mbits;
   QP bout;
   int tiles_m, tiles_n;
-  int tiles_m_rows;     // rows of a tile of the 128-row kernel family: 128, or 64 for token counts that leave its grid thin
+  int tiles_m_rows;     // (host-only, no kernel reads it; unused since GemmPlan::tile_rows carries the tile height - kept for the layout)
   float* bout_amax;     // [Mp][bout_nblk] row-block maxima of xAq @ B (B_out blocks other than 16), else null
   int bout_L, bout_nblk;
   int bout_nseg;        // > 0 (int8 route, one block per row): bout_amax holds [bout_nseg][Mp] column-segment partials (no atomics)
-  int amax_zeroed;      // host side: the atomicMax cells of the pre-pass are zero already (gemm_amax_zero_bytes) - no memset launch
+  int amax_zeroed;      // (host-only, unused: gemm_launch is told whether the pre-pass cells are zero already - kept for the layout)
   // int8 route: xq holds the int8 activation image (+ row scales), w8 the two's-complement weight image
   const uint8_t* w8;
   const float* xscale;  // [Mp] row scales 2^(e - mbits) of the int8 activation image
@@ -667,7 +682,7 @@ struct GemmArgs {
   // int8 route, one round of 128-row tiles, one B_out block per row: NO pre-pass launch - every workgroup publishes the row maxima of
   // its own tile's side product as {value, tag} granules [tiles_n][Mp] in bout_amax and gathers its row band's at the epilogue
   // (gemm_w4a8_i8.hip "exchange"); xch_nonce = the host part of the tag
-  int bout_xch;
+  int bout_xch;         // (host-only, unused: GemmPlan::amax says AMAX_XCH / AMAX_MRX - kept for the layout)
   uint32_t xch_nonce;
   // minifloat weights (w_quantizer = minifloat, 2..4 bits): the 128-row tile kernel's table expand (expand_frag_lut), w_lut = the
   // format's e4m3 table of the eight magnitude codes (mf_e4m3_table)
@@ -705,7 +720,7 @@ size_t a_b16_image_bytes(int64_t K, int64_t r);
 int a_b16_prepare_dispatch(const void* a_t_limbs, int64_t K, int64_t r, void* out, hipStream_t st);
 int act8_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t ldx, const QP& qx, void* xq_i8, const void* a_f16, int64_t r,
                         const QP& qa, bf16_t* xaq, int tuning, hipStream_t st, float* zero_p = nullptr, size_t zero_bytes = 0,
-                        bool* zeroed = nullptr);  // (zero_p: gemm_amax_zero_bytes at the head of the scratch the GEMM call will be handed)
+                        bool* zeroed = nullptr);  // (zero_p: GemmPlan::prep_zero_bytes at the head of the scratch the GEMM call will be handed)
 size_t a_f16_image_bytes(int64_t K, int64_t r);
 int a_frag_dispatch(void* a_f16, int64_t K, int64_t r, hipStream_t st);
 int f16_prepare_dispatch(const void* w_packed, int64_t N, int64_t K, const void* a_limbs_img, int a_limbs, int64_t r, void* a_f16,
@@ -717,22 +732,9 @@ int quant_xa_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int6
                             size_t scratch_bytes, hipStream_t st);  // xaq == nullptr: leave the partial tiles in scratch
 bool xa_fused_partials_ok(const QP& qx, const QP& qa, int64_t r);  // formats the GEMM can reduce itself (decode sizes)
 void xa_fused_plan(int64_t M, int64_t K, int64_t r, int* nchunk, int64_t* cstride);
-int gemm_dispatch(GemmArgs g, int dtype, bool lowrank, void* scratch, size_t scratch_bytes, hipStream_t st);
 size_t gemm_scratch_bytes(int64_t m_max, int64_t N, const QP& bout);
-size_t gemm_amax_zero_bytes(GemmArgs g, bool lowrank);
-int gemm_route(const GemmArgs& g, bool lowrank);  // LQER_ROUTE_* the dispatch would take (or an error code)
-int gemm_tile_rows(const GemmArgs& g);  // 128, or 64 for token counts that leave the 128-row grid thin (LQER_ROUTE_TILE128 family)
-bool m256_eligible(const GemmArgs& g);  // gemm_w4a8_m256.hip: fewer (weighted) rounds with 256 x 256 tiles
-int m256_dispatch(const GemmArgs& g, int dtype, bool lowrank, int bout, hipStream_t st);
-bool i8_eligible(const GemmArgs& g, int bout);     // gemm_w4a8_i8.hip: the int8 MFMA main loop (g.w8 set, large M)
-int i8_dispatch(const GemmArgs& g, int dtype, bool lowrank, int bout, hipStream_t st);
-int i8_tile_rows(const GemmArgs& g);  // 256, or 128 where that takes fewer (weighted) rounds of one tile per CU
-bool i8_amax_exchange_ok(const GemmArgs& g, bool lowrank, int bout);  // the int8 kernel can exchange the B_out row maxima itself (one round)
-bool i8_amax_mrx_ok(const GemmArgs& g, bool lowrank, int bout);       // ... or compute and exchange them over several rounds (MRX)
 int i8_prepare_dispatch(const void* w_packed, int64_t N, int64_t K, int mbits, void* w_i8, int32_t* flags, hipStream_t st);
 int i8_unpack_dispatch(const void* w_i8, int64_t N, int64_t K, float* out, hipStream_t st, bool codes8 = false);
-bool smallm_eligible(const GemmArgs& g, int bout);  // gemm_smallm.hip: M <= 64, B_out pass-through or blocks of 16
-int smallm_dispatch(const GemmArgs& g, int dtype, bool lowrank, int bout, hipStream_t st);
 
 // decode1.hip: the whole forward of M <= 8 tokens in one launch (LQER_E_UNSUPPORTED without launching when outside its shapes)
 size_t decode1_scratch_bytes(int64_t Kp, int rp);
@@ -757,7 +759,11 @@ int attention_q_dispatch(const void* q, const void* k, const void* v, const void
 int qmatmul_dispatch(const void* x, const void* y, void* out, int dtype, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs,
                      int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, void* workspace, hipStream_t st);
 
-// ---- kernel attributes (host) -----------------------------------------------------------------------
+// ---- error plumbing (host) -------------------------------------------------------------------
+void set_error(const char* fmt, ...);
+int check_launch(const char* what);
+
+// ---- launches (host) ----------------------------------------------------------------------------------
 // Raising a kernel's dynamic-LDS limit is idempotent but not free: done once per kernel instantiation and device,
 // thread-safely (the only process-wide state of the library besides the thread-local error text).
 struct LdsLimitOnce {
@@ -771,8 +777,28 @@ struct LdsLimitOnce {
   }
 };
 
-// ---- error plumbing (host) -------------------------------------------------------------------
-void set_error(const char* fmt, ...);
-int check_launch(const char* what);
+// The one way a kernel with dynamic LDS is launched: the kernel is a template argument, so the LDS limit's once-flag exists once per
+// instantiation.  lds > 0: dynamic LDS, its limit raised first - to LdsLimit where the bytes vary from call to call, else to lds.
+template <auto Kernel, int LdsLimit = 0, class... A>
+int launch_k(const char* what, dim3 grid, unsigned block, int lds, hipStream_t st, A... args) {
+  if (lds > 0) {
+    static LdsLimitOnce once;
+    once.set((const void*)Kernel, LdsLimit ? LdsLimit : lds);
+  }
+  Kernel<<<grid, block, lds, st>>>(args...);
+  return check_launch(what);
+}
+
+// f(std::integral_constant<int, DT>) for the caller's element type
+template <class F>
+int with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case LQER_F32: return f(std::integral_constant<int, LQER_F32>{});
+    case LQER_F16: return f(std::integral_constant<int, LQER_F16>{});
+    case LQER_BF16: return f(std::integral_constant<int, LQER_BF16>{});
+  }
+  set_error("unknown dtype %d", dtype);
+  return LQER_E_INVALID;
+}
 
 }  // namespace lqer

@@ -770,25 +770,15 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
   static HostT host_t;
   timespec ht1; clock_gettime(CLOCK_MONOTONIC, &ht1);
 #endif
-#define D1_LAUNCH(DT, BO)                                                                     \
-  do {                                                                                        \
-    if (nmem > 1) {                                                                           \
-      static LdsLimitOnce lds_once;                                                           \
-      lds_once.set((const void*)d1::k_decode1<DT, BO, true>, 150 * 1024);                     \
-      d1::k_decode1<DT, BO, true><<<grid, 64 * d1::NW, lds, st>>>(a);                         \
-    } else {                                                                                  \
-      static LdsLimitOnce lds_once;                                                           \
-      lds_once.set((const void*)d1::k_decode1<DT, BO, false>, 150 * 1024);                    \
-      d1::k_decode1<DT, BO, false><<<grid, 64 * d1::NW, lds, st>>>(a1);                       \
-    }                                                                                         \
-  } while (0)
-  switch (dtype) {
-    case LQER_F32: if (bout == 1) D1_LAUNCH(LQER_F32, 1); else D1_LAUNCH(LQER_F32, 0); break;
-    case LQER_F16: if (bout == 1) D1_LAUNCH(LQER_F16, 1); else D1_LAUNCH(LQER_F16, 0); break;
-    case LQER_BF16: if (bout == 1) D1_LAUNCH(LQER_BF16, 1); else D1_LAUNCH(LQER_BF16, 0); break;
-    default: set_error("unknown dtype %d", dtype); return LQER_E_INVALID;
-  }
-#undef D1_LAUNCH
+  const int rc = with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value, LIMIT = 150 * 1024;
+    const unsigned block = 64 * d1::NW;
+    if (nmem > 1)
+      return bout == 1 ? launch_k<d1::k_decode1<DT, 1, true>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a)
+                       : launch_k<d1::k_decode1<DT, 0, true>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a);
+    return bout == 1 ? launch_k<d1::k_decode1<DT, 1, false>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a1)
+                     : launch_k<d1::k_decode1<DT, 0, false>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a1);
+  });
 #ifdef LQER_HOST_TIMING
   {
     timespec ht2; clock_gettime(CLOCK_MONOTONIC, &ht2);
@@ -797,7 +787,7 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
     host_t.n++;
   }
 #endif
-  return check_launch("lqer_decode1");
+  return rc;
 }
 
 }  // namespace lqer

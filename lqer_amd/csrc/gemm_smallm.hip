@@ -15,11 +15,10 @@
 // A B_out block (16 consecutive n of a token) is the 4 registers of the 4 lanes l, l^16, l^32, l^48.
 // The 8 waves' partial sums are added in a fixed order through LDS (bit-reproducible); wave 0 adds the side
 // path (MFMA straight from global memory, re-quantized in registers), the bias, and stores.
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace lqer {
 
-constexpr int SM_MAX_M = 64;   // tokens handled by this kernel (MT = ceil(M / 16) <= 4 token tiles)
 constexpr int SM_NW = 8;       // waves per workgroup: wave w takes panels w, w + 8, ...
 template <int MT> struct SmUnr { static constexpr int v = MT <= 2 ? 4 : 2; };  // panels per register buffer (two buffers)
 
@@ -222,38 +221,29 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
   }
 }
 
-bool smallm_eligible(const GemmArgs& g, int bout) { return g.M <= SM_MAX_M && bout <= 1; }
-
-template <int DT>
-static int launch_smallm(const GemmArgs& g, bool lowrank, int bout, hipStream_t st) {
-  const unsigned grid = (unsigned)(g.Np / 16);
-  const int mt = (g.M + 15) / 16;
-#define SM_LAUNCH(LR, BO)                                                           \
-  switch (mt) {                                                                     \
-    case 1: k_lqer_gemm_smallm<DT, LR, BO, 1><<<grid, 64 * SM_NW, 0, st>>>(g); break;      \
-    case 2: k_lqer_gemm_smallm<DT, LR, BO, 2><<<grid, 64 * SM_NW, 0, st>>>(g); break;      \
-    case 3: k_lqer_gemm_smallm<DT, LR, BO, 3><<<grid, 64 * SM_NW, 0, st>>>(g); break;      \
-    default: k_lqer_gemm_smallm<DT, LR, BO, 4><<<grid, 64 * SM_NW, 0, st>>>(g); break;     \
+template <int DT, bool LR, int BO>
+static int run_smallm(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  switch (p.mt) {  // 16-row token tiles
+    case 1: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 1>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
+    case 2: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 2>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
+    case 3: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 3>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
+    default: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 4>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
   }
-  if (!lowrank) {
-    SM_LAUNCH(false, 0)
-  } else if (bout == 1) {
-    SM_LAUNCH(true, 1)
-  } else {
-    SM_LAUNCH(true, 0)
-  }
-#undef SM_LAUNCH
-  return check_launch("lqer_gemm_smallm");
 }
 
-int smallm_dispatch(const GemmArgs& g, int dtype, bool lowrank, int bout, hipStream_t st) {
-  switch (dtype) {
-    case LQER_F32: return launch_smallm<LQER_F32>(g, lowrank, bout, st);
-    case LQER_F16: return g.x_f16 ? launch_smallm<LQER_F16X>(g, lowrank, bout, st) : launch_smallm<LQER_F16>(g, lowrank, bout, st);
-    case LQER_BF16: return launch_smallm<LQER_BF16>(g, lowrank, bout, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+template <int DT>
+static int launch_smallm(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if (!p.lowrank) return run_smallm<DT, false, 0>(p, g, st);
+  return p.bout == 1 ? run_smallm<DT, true, 1>(p, g, st) : run_smallm<DT, true, 0>(p, g, st);
+}
+
+int smallm_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {
+  return with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if constexpr (DT == LQER_F16)
+      if (p.f16x) return launch_smallm<LQER_F16X>(p, g, st);
+    return launch_smallm<DT>(p, g, st);
+  });
 }
 
 }  // namespace lqer

@@ -28,11 +28,10 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace lqer {
 
-constexpr int BM = 128, BN = 256, BK = 64;
 #ifndef LQER_DEPTH
 #define LQER_DEPTH 3
 #endif
@@ -718,9 +717,6 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 // requested one batch ahead of the MFMAs that consume it (two named register sets), the first MFMA of a tile takes a literal
 // zero accumulator, and a lane keeps one running maximum per row group (every register of its accumulator is the same token
 // row), folded with v_max3_f32; the lane pair is combined once, at the commit.
-#ifndef LQER_AMAX_WAVES
-#define LQER_AMAX_WAVES 2048
-#endif
 template <int RG, int NKS>
 __global__ __launch_bounds__(256) void k_bout_amax(GemmArgs g, int tiles_n32, int seg_tiles) {
   // One wave = 32 RG token rows x a run of `seg_tiles` 32-column tiles: the rows' xAq fragments stay in registers, the
@@ -938,109 +934,61 @@ __global__ __launch_bounds__(256) void k_bout_amax_lds(GemmArgs g, int tiles_n32
   commit();
 }
 
+// One instantiation of the tile kernel per (element type, side path, B_out, ...): MT = 4 the 128-row tile, 2 the 64-row one.
+template <int DT, bool LR, int BO, bool ST = false, int MT = 4, bool WTWOS = false, bool DEFER = false, bool WMF = false>
+static int run_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  return launch_k<k_lqer_gemm<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>>("lqer_gemm", p.grid, 512, gemm_lds_bytes(MT), st, g);
+}
+
+// the plan's variant -> the instantiation (only those listed here exist)
 template <int DT>
-static int launch_gemm(const GemmArgs& g, bool lowrank, int bout, hipStream_t st) {
-  const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n);
-#define LQER_GEMM_LAUNCH(LR, BO)                                                                                \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, LR, BO>, gemm_lds_bytes(4));                                      \
-    k_lqer_gemm<DT, LR, BO><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                                           \
-  } while (0)
-#define LQER_GEMM_LAUNCH_STAGED(BO)                                                                             \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, true, BO, true>, gemm_lds_bytes(4));                              \
-    k_lqer_gemm<DT, true, BO, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                                   \
-  } while (0)
-#ifndef LQER_STAGE_MIN
-#define LQER_STAGE_MIN 32
-#endif
-  const bool staged = lowrank && g.rp * g.b_limbs > LQER_STAGE_MIN;  // more than two 16-deep slices of side product
-  if (g.w_mf || bout == 3) {  // minifloat weights and / or B_out: 128-row tiles, one instantiation per (element type, side path, B_out)
-    if constexpr (DT == LQER_F16X) {
-      set_error("linear_gemm: minifloat weights and B_out have no fp16 main loop (pass-through fp16 activations take the limb route)");
-      return LQER_E_UNSUPPORTED;
-    } else {
-#define LQER_GEMM_LAUNCH_MF(LR, BO, ST, WM)                                                                     \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, LR, BO, ST, 4, false, false, WM>, gemm_lds_bytes(4));             \
-    k_lqer_gemm<DT, LR, BO, ST, 4, false, false, WM><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                  \
-  } while (0)
-      if (!g.w_mf) {  // (block_fp / integer weights here: only with a minifloat B_out)
-        if (g.w_twos) {  // (integer weights: the staged side path, as below)
-          static LdsLimitOnce lds_once;
-          lds_once.set((const void*)k_lqer_gemm<DT, true, 3, true, 4, true>, gemm_lds_bytes(4));
-          k_lqer_gemm<DT, true, 3, true, 4, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);
-        } else if (staged) LQER_GEMM_LAUNCH_MF(true, 3, true, false);
-        else LQER_GEMM_LAUNCH_MF(true, 3, false, false);
-      } else if (!lowrank) LQER_GEMM_LAUNCH_MF(false, 0, false, true);
-      else if (bout == 1) LQER_GEMM_LAUNCH_MF(true, 1, true, true);
-      else if (bout == 2) LQER_GEMM_LAUNCH_MF(true, 2, true, true);
-      else if (bout == 3) LQER_GEMM_LAUNCH_MF(true, 3, true, true);
-      else LQER_GEMM_LAUNCH_MF(true, 0, true, true);
-#undef LQER_GEMM_LAUNCH_MF
-      return check_launch("lqer_gemm");
+static int launch_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  const bool S = p.staged;
+  if constexpr (DT != LQER_F16X) {  // (no fp16 main loop beside integer / minifloat nibbles or a minifloat B_out: the plan refuses)
+    if (p.w_mf) {  // minifloat weights: 128-row tiles, the staged side path
+      if (!p.lowrank) return run_tile<DT, false, 0, false, 4, false, false, true>(p, g, st);
+      switch (p.bout) {
+        case 1: return run_tile<DT, true, 1, true, 4, false, false, true>(p, g, st);
+        case 2: return run_tile<DT, true, 2, true, 4, false, false, true>(p, g, st);
+        case 3: return run_tile<DT, true, 3, true, 4, false, false, true>(p, g, st);
+        default: return run_tile<DT, true, 0, true, 4, false, false, true>(p, g, st);
+      }
+    }
+    if (p.w_twos) {  // integer weights: the same
+      if (!p.lowrank) return run_tile<DT, false, 0, false, 4, true>(p, g, st);
+      switch (p.bout) {
+        case 1: return run_tile<DT, true, 1, true, 4, true>(p, g, st);
+        case 2: return run_tile<DT, true, 2, true, 4, true>(p, g, st);
+        case 3: return run_tile<DT, true, 3, true, 4, true>(p, g, st);
+        default: return run_tile<DT, true, 0, true, 4, true>(p, g, st);
+      }
+    }
+    if (p.bout == 3) return S ? run_tile<DT, true, 3, true>(p, g, st) : run_tile<DT, true, 3, false>(p, g, st);  // minifloat B_out
+  }
+  if (p.tile_rows == 64) {  // (the 128-row grid would fill at most half of the CUs)
+    if (!p.lowrank) return run_tile<DT, false, 0, false, 2>(p, g, st);
+    switch (p.bout) {
+      case 1: return S ? run_tile<DT, true, 1, true, 2>(p, g, st) : run_tile<DT, true, 1, false, 2>(p, g, st);
+      case 2: return S ? run_tile<DT, true, 2, true, 2>(p, g, st) : run_tile<DT, true, 2, false, 2>(p, g, st);
+      default: return S ? run_tile<DT, true, 0, true, 2>(p, g, st) : run_tile<DT, true, 0, false, 2>(p, g, st);
     }
   }
-  if (g.w_twos) {  // integer weights: one instantiation per (element type, side path, B_out) - 128-row tiles, staged side path
-    if constexpr (DT == LQER_F16X) {
-      set_error("linear_gemm: integer weights have no fp16 main loop (pass-through fp16 activations take the limb route)");
-      return LQER_E_UNSUPPORTED;
-    } else {
-#define LQER_GEMM_LAUNCH_TWOS(LR, BO, ST)                                                                       \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, LR, BO, ST, 4, true>, gemm_lds_bytes(4));                         \
-    k_lqer_gemm<DT, LR, BO, ST, 4, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                              \
-  } while (0)
-      if (!lowrank) LQER_GEMM_LAUNCH_TWOS(false, 0, false);
-      else if (bout == 1) LQER_GEMM_LAUNCH_TWOS(true, 1, true);
-      else if (bout == 2) LQER_GEMM_LAUNCH_TWOS(true, 2, true);
-      else LQER_GEMM_LAUNCH_TWOS(true, 0, true);
-#undef LQER_GEMM_LAUNCH_TWOS
-      return check_launch("lqer_gemm");
-    }
+  if (!p.lowrank) return run_tile<DT, false, 0>(p, g, st);
+  if (p.defer) return S ? run_tile<DT, true, 1, true, 4, false, true>(p, g, st) : run_tile<DT, true, 1, false, 4, false, true>(p, g, st);
+  switch (p.bout) {
+    case 1: return S ? run_tile<DT, true, 1, true>(p, g, st) : run_tile<DT, true, 1>(p, g, st);
+    case 2: return S ? run_tile<DT, true, 2, true>(p, g, st) : run_tile<DT, true, 2>(p, g, st);
+    default: return S ? run_tile<DT, true, 0, true>(p, g, st) : run_tile<DT, true, 0>(p, g, st);
   }
-#define LQER_GEMM_LAUNCH_H64(LR, BO, ST)                                                                        \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, LR, BO, ST, 2>, gemm_lds_bytes(2));                               \
-    k_lqer_gemm<DT, LR, BO, ST, 2><<<grid, 512, gemm_lds_bytes(2), st>>>(g);                                    \
-  } while (0)
-  if (g.tiles_m_rows == 64) {  // (gemm_dispatch: the 128-row grid would fill at most half of the CUs)
-    if (!lowrank) LQER_GEMM_LAUNCH_H64(false, 0, false);
-    else if (bout == 1) { if (staged) LQER_GEMM_LAUNCH_H64(true, 1, true); else LQER_GEMM_LAUNCH_H64(true, 1, false); }
-    else if (bout == 2) { if (staged) LQER_GEMM_LAUNCH_H64(true, 2, true); else LQER_GEMM_LAUNCH_H64(true, 2, false); }
-    else { if (staged) LQER_GEMM_LAUNCH_H64(true, 0, true); else LQER_GEMM_LAUNCH_H64(true, 0, false); }
-    return check_launch("lqer_gemm");
-  }
-#undef LQER_GEMM_LAUNCH_H64
-  // B_out in blocks of 16 re-quantized under the first 16 k-steps instead of in front of the main loop (DEFER above): K >= 1024,
-  // clamps within the magic-number rounding, and the 1e-8 pass-through that makes the clamped scale exponent exact
-  const bool defer = lowrank && bout == 1 && !(g.tuning & LQER_TUNE_BOUT_IN_PROLOGUE) && g.Kp / BK >= 16 && g.bout.kind == LQER_Q_MXINT &&
-                     g.bout.mmax <= 4194304.0f && g.bout.mneg <= 4194304.0f && g.bout.tiny >= 1e-8f;
-#define LQER_GEMM_LAUNCH_DEFER(ST)                                                                              \
-  do {                                                                                                          \
-    static LdsLimitOnce lds_once;                                                                               \
-    lds_once.set((const void*)k_lqer_gemm<DT, true, 1, ST, 4, false, true>, gemm_lds_bytes(4));                 \
-    k_lqer_gemm<DT, true, 1, ST, 4, false, true><<<grid, 512, gemm_lds_bytes(4), st>>>(g);                      \
-  } while (0)
-  if (!lowrank)
-    LQER_GEMM_LAUNCH(false, 0);
-  else if (bout == 1 && defer) {
-    if (staged) LQER_GEMM_LAUNCH_DEFER(true); else LQER_GEMM_LAUNCH_DEFER(false);
-  } else if (bout == 1) {
-    if (staged) LQER_GEMM_LAUNCH_STAGED(1); else LQER_GEMM_LAUNCH(true, 1);
-  } else if (bout == 2) {
-    if (staged) LQER_GEMM_LAUNCH_STAGED(2); else LQER_GEMM_LAUNCH(true, 2);
-  } else {
-    if (staged) LQER_GEMM_LAUNCH_STAGED(0); else LQER_GEMM_LAUNCH(true, 0);
-  }
-#undef LQER_GEMM_LAUNCH_STAGED
-#undef LQER_GEMM_LAUNCH
-  return check_launch("lqer_gemm");
+}
+
+int tile128_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {
+  return with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if constexpr (DT == LQER_F16)
+      if (p.f16x) return launch_tile<LQER_F16X>(p, g, st);
+    return launch_tile<DT>(p, g, st);
+  });
 }
 
 #if defined(LQER_STAMPS) || defined(LQER_CLOCKPROBE)
@@ -1059,238 +1007,89 @@ size_t gemm_scratch_bytes(int64_t m_max, int64_t N, const QP& bout) {
   return (size_t)lqer_padded_m(m_max) * (nblk == 1 ? 2 * LQER_AMAX_NSEG : nblk) * sizeof(float);
 }
 
-// B_out handling of a launch: 0 pass-through, 1 blocks of 16 (maxima in registers), 2 other blocks (pre-pass); < 0 error
-static int bout_mode(const GemmArgs& g, bool lowrank, int* L_out) {
-  if (lowrank && g.bout.kind == LQER_Q_MXINT) {
-    if (g.bout.block == 16) return 1;
-    const int L = (g.bout.block <= 0 || g.bout.block >= g.N) ? g.Np : g.bout.block;
-    if (L % 16 != 0) {
-      set_error("B_out_quantizer block %d: must be a multiple of 16 or cover the row", g.bout.block);
-      return LQER_E_UNSUPPORTED;
-    }
-    if (L_out) *L_out = L;
-    return 2;
-  }
-  if (lowrank && g.bout.kind == LQER_Q_INT) {  // fixed point: elementwise, no block maxima - the "any block" code without its pre-pass
-    if (L_out) *L_out = 0;
-    return 2;
-  }
-  if (lowrank && g.bout.kind == LQER_Q_MINIFLOAT) {  // elementwise with an exponent per element: the 128-row tile kernel's BOUT 3
-    if (L_out) *L_out = 0;
-    return 3;
-  }
-  if (lowrank && g.bout.kind != LQER_Q_PASSTHROUGH) {
-    set_error("B_out_quantizer kind %d not implemented", g.bout.kind);
-    return LQER_E_UNSUPPORTED;
-  }
-  return 0;
-}
-
-int gemm_route(const GemmArgs& g, bool lowrank) {
-  const int bout = bout_mode(g, lowrank, nullptr);
-  if (bout < 0) return bout;
-  if (g.w8) {  // LQER_Q_MXINT_I8: the int8 kernel or nothing (the caller falls back to LQER_Q_MXINT on the same buffers)
-    GemmArgs t = g;
-    if (bout == 2 && g.bout.kind == LQER_Q_MXINT) {
-      const int L = (g.bout.block <= 0 || g.bout.block >= g.N) ? g.Np : g.bout.block;
-      t.bout_nblk = (g.Np + L - 1) / L;
-    }
-    if (i8_eligible(t, bout)) return LQER_ROUTE_I8;
-    t.w8 = nullptr;
-    return gemm_route(t, lowrank);
-  }
-  if (g.w_twos) return LQER_ROUTE_TILE128;  // integer weights (two's-complement nibbles): the 128-row tile kernel at every M
-  if (g.w_mf || bout == 3) return LQER_ROUTE_TILE128;  // minifloat weights or B_out: the same
-  if (smallm_eligible(g, bout)) return LQER_ROUTE_SMALLM;
-  if (m256_eligible(g)) return LQER_ROUTE_TILE256;
-  return LQER_ROUTE_TILE128;
-}
-
-// Rows of a tile of the 128-row kernel family.  Token counts whose 128-row grid covers at most half of the CUs: 64-row tiles
-// (twice the workgroups, half the MFMA work per expanded weight fragment - the k-step is then paced by the weight expand,
-// NOTEBOOK.md §4.1) as long as they still fit one round.
-int gemm_tile_rows(const GemmArgs& g) {
-  constexpr int CUS = 256;
-  const int64_t tn = g.Np / BN;
-  const int64_t t128 = (int64_t)((g.M + BM - 1) / BM) * tn, t64 = (int64_t)((g.M + 63) / 64) * tn;
-  const int pin = (g.tuning & LQER_TUNE_TILE_ROWS_128) ? 128 : ((g.tuning & LQER_TUNE_TILE_ROWS_64) ? 64 : 0);  // (tests)
-  const bool mf = g.w_mf || g.bout.kind == LQER_Q_MINIFLOAT;  // (minifloat: 128-row instantiations only)
-  if (!g.w_twos && !mf && ((pin != 128 && 2 * t128 <= CUS && t64 > t128 && g.M > 64) || (pin == 64 && g.M > 64))) return 64;
-  return BM;
-}
-
 __global__ void k_zero_cells(uint32_t* p, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = 0u;
 }
 
-// How a launch with one or more B_out blocks per row (bout == 2, block_fp; g.bout_nblk set) gets its row-block maxima:
-//   xch   - one round of the int8 kernel's 128-row tiles: exchanged inside the GEMM launch, no pre-pass;
-//   parts - one block per row, consumed by the int8 kernel: every wave of the pre-pass leaves the maximum of ITS column segment in its
-//           own cell [segment][row] (plain stores; at most LQER_AMAX_NSEG segments, the GEMM folds them when it reads a row's
-//           constants) - no atomics, so no zero-fill launch in front (4.7 us of a 62-us step at M = 2048).  Taken while the segments stay
-//           narrow (up to 8 column tiles: beyond N = 4096 wider segments mean half the waves, each twice as long - 2048 x 11008, rank 32:
-//           111.9 us with partials against 104.4 with cells; tools/ab_i8.py --rows --amax), or where the pre-pass would not use more
-//           than LQER_AMAX_NSEG segments anyway (token counts from ~16k: C4 - the same pre-pass grid, minus the zero fill);
-//   else  - one atomicMax cell per (row, block), zeroed first: `need` bytes at the head of the scratch.
-struct AmaxPlan {
-  bool parts, xch, mrx;
-  size_t need;
-};
-static AmaxPlan amax_plan(const GemmArgs& g, bool lowrank, int bout) {
-  const int tiles_n32 = g.Np / 32;
-  const bool one = g.w8 && g.bout_nblk == 1;
-  // segments the pre-pass would use with no cap (its LDS variant at rank 64, else the register variant at its default row groups)
-  int64_t uncapped;
-  if (g.rp == 64) {
-    const int64_t wgroups4 = ((((g.M + 31) / 32 + 3) / 4) + 3) / 4;
-    uncapped = (LQER_AMAX_WAVES / 4) / wgroups4;
-  } else {
-    const int RG = g.rp <= 64 ? 4 : (g.rp <= 128 ? 2 : 1);
-    uncapped = LQER_AMAX_WAVES / (((g.M + 31) / 32 + RG - 1) / RG);
-  }
-  AmaxPlan p;
-  p.parts = one && !(g.tuning & LQER_TUNE_AMAX_ATOMIC) &&
-            (tiles_n32 <= 8 * LQER_AMAX_NSEG || uncapped <= LQER_AMAX_NSEG || (g.tuning & LQER_TUNE_AMAX_PARTS));
-  // ... or no pre-pass at all: one round of the int8 kernel's 128-row tiles exchanges the maxima inside the GEMM launch
-  p.xch = one && !(g.tuning & (LQER_TUNE_AMAX_ATOMIC | LQER_TUNE_AMAX_PARTS)) && i8_eligible(g, bout) && i8_amax_exchange_ok(g, lowrank, bout);
-  //   mrx - several rounds of 128-row tiles on a resident grid: the GEMM's workgroups each compute one item of the pre-pass at their start
-  //         and exchange {maximum, tag} granules (gemm_w4a8_i8.hip, MRX): no pre-pass launch, nothing zeroed
-  p.mrx = one && !p.xch && !(g.tuning & (LQER_TUNE_AMAX_NO_MRX | LQER_TUNE_AMAX_ATOMIC | LQER_TUNE_AMAX_PARTS)) && i8_eligible(g, bout) &&
-          i8_amax_mrx_ok(g, lowrank, bout);
-  if (p.mrx) p.parts = false;
-  p.need = (size_t)lqer_padded_m(g.M) * ((p.xch || p.mrx) ? 2 * LQER_AMAX_NSEG : (p.parts ? LQER_AMAX_NSEG_WIDE : g.bout_nblk)) * sizeof(float);
-  return p;
+template <int RG, int NKS>
+static int run_amax(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  return launch_k<k_bout_amax<RG, NKS>>("lqer_gemm (B_out pre-pass)", p.pre.grid, 256, 0, st, g, p.pre.tiles_n32, p.pre.seg_tiles);
 }
 
-// Bytes at the head of the GEMM's scratch that the pre-pass of this launch needs zeroed before it runs (0: no pre-pass, segment
-// partials or the in-launch exchange).  lqer_linear_forward lets the one-launch activation kernel of the same forward write the
-// zeros (the two calls are handed the same scratch) and sets g.amax_zeroed - the memset launch in front of the pre-pass cost 4.8 us
-// of the 116-us forward at 2048 x 4096 -> 11008.
-size_t gemm_amax_zero_bytes(GemmArgs g, bool lowrank) {
-  int L = 0;
-  if (g.M == 0 || g.N == 0 || bout_mode(g, lowrank, &L) != 2 || g.bout.kind != LQER_Q_MXINT) return 0;
-  g.bout_L = L, g.bout_nblk = (g.Np + L - 1) / L;
-  // (asked before the GEMM call's limb count is known: the permissive answer - a launch that then cannot exchange the maxima itself
-  // finds nothing prepared and zero-fills its cells as ever)
-  if (g.b_limbs == 0) g.b_limbs = 1;
-  const AmaxPlan p = amax_plan(g, lowrank, 2);
-  return (p.parts || p.xch || p.mrx) ? 0 : p.need;
+// the pre-pass of the plan: row groups per wave x 16-deep slices of the padded rank (only the pairs listed here exist)
+static int launch_amax(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if (p.pre.lds)
+    return launch_k<k_bout_amax_lds>("lqer_gemm (B_out pre-pass)", p.pre.grid, 256, 0, st, g, p.pre.tiles_n32, p.pre.seg_tiles);
+  switch (p.pre.rg * 32 + p.pre.nks) {
+    case 32 + 1: return run_amax<1, 1>(p, g, st);
+    case 64 + 1: return run_amax<2, 1>(p, g, st);
+    case 32 + 2: return run_amax<1, 2>(p, g, st);
+    case 64 + 2: return run_amax<2, 2>(p, g, st);
+    case 32 + 3: return run_amax<1, 3>(p, g, st);
+    case 64 + 3: return run_amax<2, 3>(p, g, st);
+    case 32 + 4: return run_amax<1, 4>(p, g, st);
+    case 64 + 4: return run_amax<2, 4>(p, g, st);
+    case 128 + 1: return run_amax<4, 1>(p, g, st);
+    case 128 + 2: return run_amax<4, 2>(p, g, st);
+    case 128 + 3: return run_amax<4, 3>(p, g, st);
+    case 128 + 4: return run_amax<4, 4>(p, g, st);
+    case 64 + 5: return run_amax<2, 5>(p, g, st);
+    case 64 + 6: return run_amax<2, 6>(p, g, st);
+    case 64 + 7: return run_amax<2, 7>(p, g, st);
+    case 64 + 8: return run_amax<2, 8>(p, g, st);
+    case 32 + 9: return run_amax<1, 9>(p, g, st);
+    case 32 + 10: return run_amax<1, 10>(p, g, st);
+    case 32 + 11: return run_amax<1, 11>(p, g, st);
+    case 32 + 12: return run_amax<1, 12>(p, g, st);
+    case 32 + 13: return run_amax<1, 13>(p, g, st);
+    case 32 + 14: return run_amax<1, 14>(p, g, st);
+    case 32 + 15: return run_amax<1, 15>(p, g, st);
+    case 32 + 16: return run_amax<1, 16>(p, g, st);
+  }
+  set_error("%s", p.msg);  // (plan_prepass refused: more slices than any instantiation has)
+  return p.launch_err;
 }
 
-int gemm_dispatch(GemmArgs g, int dtype, bool lowrank, void* scratch, size_t scratch_bytes, hipStream_t st) {
-  if (g.M == 0 || g.N == 0) return LQER_OK;
-  int L = 0;
-  const int bout = bout_mode(g, lowrank, &L);
-  if (bout < 0) return bout;
-  if (bout == 2 && g.bout.kind == LQER_Q_INT) {
-    g.bout_L = 16, g.bout_nblk = 0, g.bout_amax = nullptr;
-  } else if (bout == 2) {
-      g.bout_L = L;
-      g.bout_nblk = (g.Np + L - 1) / L;
-      const int tiles_n32 = g.Np / 32;
-      const AmaxPlan ap = amax_plan(g, lowrank, bout);
-      const bool parts = ap.parts, xch = ap.xch || ap.mrx;
-      const size_t need = ap.need;
-      if (!scratch || scratch_bytes < need) {
-        set_error("linear_gemm: scratch %zu B < %zu B for the B_out row-block maxima", scratch_bytes, need);
-        return LQER_E_WORKSPACE;
-      }
-      g.bout_amax = (float*)scratch;
-      g.bout_nseg = 0;
-      g.bout_xch = 0;
-      if (xch) {
-        // the call's tag: a counter spread over all 32 bits (odd multiplier: a bijection); the kernel mixes in its dispatch id and queue
-        static std::atomic<uint32_t> xch_calls{1};
-        g.bout_xch = ap.mrx ? 2 : 1;
-        g.xch_nonce = xch_calls.fetch_add(1, std::memory_order_relaxed) * 0x9E3779B1u;
-      } else {
-      // (amax_zeroed: the activation kernel of the same forward did it.  A kernel, not hipMemsetAsync: as a memset NODE of a captured graph
-      // the fill left two of every four cells untouched on replay - ROCm 7.2, tools/graph_replay_gemm.py - while the eager call was fine)
-      if (!parts && !g.amax_zeroed) k_zero_cells<<<(unsigned)((need / 4 + 255) / 256), 256, 0, st>>>((uint32_t*)scratch, (int64_t)(need / 4));
-      // padded rank (x limbs of x A) -> 16-deep slices (a template parameter: exact, no per-slice branch) and row groups per wave
-      const int nks = g.rp / 16;
-      int RG = g.rp <= 64 ? 4 : (g.rp <= 128 ? 2 : 1);
-      const int nseg_cap = parts ? (tiles_n32 <= 8 * LQER_AMAX_NSEG ? LQER_AMAX_NSEG : LQER_AMAX_NSEG_WIDE) : tiles_n32;
-      // (segment partials cap the column split: fewer row groups per wave keep the grid at about a thousand waves)
-      if (parts && nks <= 4)
-        while (RG > 1 && (((g.M + 31) / 32 + RG - 1) / RG) * nseg_cap < 1024) RG >>= 1;
-      const int64_t groups = ((g.M + 31) / 32 + RG - 1) / RG;
-      int nseg = (int)(LQER_AMAX_WAVES / groups);  // one round of two waves per SIMD (the kernel holds 184-256 registers)
-      nseg = nseg < 1 ? 1 : (nseg > tiles_n32 ? tiles_n32 : nseg);
-      nseg = nseg > nseg_cap ? nseg_cap : nseg;
-      const int seg_tiles = (tiles_n32 + nseg - 1) / nseg;
-      const int nseg_used = (tiles_n32 + seg_tiles - 1) / seg_tiles;
-      const int64_t waves = groups * nseg_used;
-      const unsigned grid = (unsigned)((waves + 3) / 4);
-      if (parts) g.bout_nseg = nseg_used;
-#define LQER_AMAX(RGv, NKSv) k_bout_amax<RGv, NKSv><<<grid, 256, 0, st>>>(g, tiles_n32, seg_tiles)
-      const int64_t wgroups4 = ((((g.M + 31) / 32 + 3) / 4) + 3) / 4;  // workgroups of the LDS variant along the rows (4 waves x 4 row groups)
-      if (nks == 4 && g.rp == 64 && (!parts || wgroups4 * LQER_AMAX_NSEG >= 256)) {  // rank 64: the B^T run through LDS, four row groups per workgroup
-        int ns = (int)((LQER_AMAX_WAVES / 4) / wgroups4);
-        ns = ns < 1 ? 1 : (ns > tiles_n32 ? tiles_n32 : ns);
-        ns = ns > nseg_cap ? nseg_cap : ns;
-        const int st_l = (tiles_n32 + ns - 1) / ns;
-        const int ns_used = (tiles_n32 + st_l - 1) / st_l;
-        const int64_t wgs = wgroups4 * ns_used;
-        if (parts) g.bout_nseg = ns_used;
-        k_bout_amax_lds<<<(unsigned)wgs, 256, 0, st>>>(g, tiles_n32, st_l);
-      } else if (nks <= 4 && RG < 4) {
-        switch (nks * 4 + RG) {
-          case 4 + 1: LQER_AMAX(1, 1); break;
-          case 4 + 2: LQER_AMAX(2, 1); break;
-          case 8 + 1: LQER_AMAX(1, 2); break;
-          case 8 + 2: LQER_AMAX(2, 2); break;
-          case 12 + 1: LQER_AMAX(1, 3); break;
-          case 12 + 2: LQER_AMAX(2, 3); break;
-          case 16 + 1: LQER_AMAX(1, 4); break;
-          default: LQER_AMAX(2, 4); break;
-        }
-      } else
-      switch (nks) {
-        case 1: LQER_AMAX(4, 1); break;
-        case 2: LQER_AMAX(4, 2); break;
-        case 3: LQER_AMAX(4, 3); break;
-        case 4: LQER_AMAX(4, 4); break;
-        case 5: LQER_AMAX(2, 5); break;
-        case 6: LQER_AMAX(2, 6); break;
-        case 7: LQER_AMAX(2, 7); break;
-        case 8: LQER_AMAX(2, 8); break;
-        case 9: LQER_AMAX(1, 9); break;
-        case 10: LQER_AMAX(1, 10); break;
-        case 11: LQER_AMAX(1, 11); break;
-        case 12: LQER_AMAX(1, 12); break;
-        case 13: LQER_AMAX(1, 13); break;
-        case 14: LQER_AMAX(1, 14); break;
-        case 15: LQER_AMAX(1, 15); break;
-        case 16: LQER_AMAX(1, 16); break;
-        default: set_error("B_out pre-pass: padded rank %d x limbs > 256", g.rp); return LQER_E_UNSUPPORTED;
-      }
-#undef LQER_AMAX
-      }  // (pre-pass)
+int gemm_launch(const GemmPlan& p, GemmArgs g, int dtype, void* scratch, size_t scratch_bytes, bool amax_zeroed, hipStream_t st) {
+  if (p.empty) return LQER_OK;
+  if (p.err) {
+    set_error("%s", p.msg);
+    return p.err;
   }
-  if (g.w8) {  // LQER_Q_MXINT_I8: xq is the int8 image - only the int8 kernel can read it
-    if (!i8_eligible(g, bout)) {
-      set_error("linear_gemm: LQER_Q_MXINT_I8 is not served for M=%d here (lqer_gemm_route != LQER_ROUTE_I8): call with "
-                "LQER_Q_MXINT", g.M);
-      return LQER_E_UNSUPPORTED;
+  g.tiles_m = p.tiles_m, g.tiles_n = p.tiles_n;
+  if (p.bout == 2) g.bout_L = p.bout_L, g.bout_nblk = p.bout_nblk, g.bout_amax = nullptr, g.bout_nseg = p.pre.nseg;
+  if (p.amax != AMAX_NONE) {
+    if (!scratch || scratch_bytes < p.need) {
+      set_error("linear_gemm: scratch %zu B < %zu B for the B_out row-block maxima", scratch_bytes, p.need);
+      return LQER_E_WORKSPACE;
     }
-    return i8_dispatch(g, dtype, lowrank, bout, st);
+    g.bout_amax = (float*)scratch;
   }
-  if (!g.w_twos && !g.w_mf && bout != 3) {
-    if (smallm_eligible(g, bout)) return smallm_dispatch(g, dtype, lowrank, bout, st);  // decode sizes: HBM-bound variant
-    if (m256_eligible(g)) return m256_dispatch(g, dtype, lowrank, bout, st);  // large M: 256 x 256 tiles
+  if (p.amax == AMAX_XCH || p.amax == AMAX_MRX) {
+    // the call's tag: a counter spread over all 32 bits (odd multiplier: a bijection); the kernel mixes in its dispatch id and queue
+    static std::atomic<uint32_t> xch_calls{1};
+    g.xch_nonce = xch_calls.fetch_add(1, std::memory_order_relaxed) * 0x9E3779B1u;
+  } else if (p.amax != AMAX_NONE) {
+    // (amax_zeroed: the activation kernel of the same forward did it.  A kernel, not hipMemsetAsync: as a memset NODE of a captured graph
+    // the fill left two of every four cells untouched on replay - ROCm 7.2, tools/graph_replay_gemm.py - while the eager call was fine)
+    int rc = LQER_OK;
+    if (p.zero_bytes && !amax_zeroed)
+      rc = launch_k<k_zero_cells>("lqer_gemm (zero fill)", (unsigned)((p.zero_bytes / 4 + 255) / 256), 256, 0, st, (uint32_t*)scratch,
+                                  (int64_t)(p.zero_bytes / 4));
+    if (rc == LQER_OK) rc = launch_amax(p, g, st);
+    if (rc) return rc;
   }
-  g.tiles_n = g.Np / BN;
-  g.tiles_m_rows = gemm_tile_rows(g);
-  g.tiles_m = (g.M + g.tiles_m_rows - 1) / g.tiles_m_rows;
-  switch (dtype) {
-    case LQER_F32: return launch_gemm<LQER_F32>(g, lowrank, bout, st);
-    case LQER_F16: return g.x_f16 ? launch_gemm<LQER_F16X>(g, lowrank, bout, st) : launch_gemm<LQER_F16>(g, lowrank, bout, st);
-    case LQER_BF16: return launch_gemm<LQER_BF16>(g, lowrank, bout, st);
+  if (p.launch_err) {  // (behind the pre-pass, where these refusals have always been reported)
+    set_error("%s", p.msg);
+    return p.launch_err;
   }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  switch (p.route) {
+    case LQER_ROUTE_I8: return i8_launch(p, g, dtype, st);
+    case LQER_ROUTE_SMALLM: return smallm_launch(p, g, dtype, st);  // decode sizes: HBM-bound variant
+    case LQER_ROUTE_TILE256: return m256_launch(p, g, dtype, st);   // large M: 256 x 256 tiles
+    default: return tile128_launch(p, g, dtype, st);
+  }
 }
 
 }  // namespace lqer

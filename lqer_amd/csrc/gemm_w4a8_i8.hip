@@ -31,7 +31,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace lqer {
 
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void k_i8_unpack8(const uint8_t* __restrict__ 
 //           four register sets, three steps ahead beside the activation ring (step4_w8).  35.8 us per round of 4096-k tiles on
 //           all 256 CUs where 256-row tiles fill half of them in 63 us (M = 2048, 4096 x 4096); 1,500 cycles per step.
 // XCH (round 6): the instantiation for ONE round of 128-row tiles that exchanges the B_out row maxima inside the launch (what used to be
-// the runtime flag g.bout_xch) - no tile loop, every operand of the epilogue requested in the prologue (the xAq panel in an LDS region
+// a runtime flag) - no tile loop, every operand of the epilogue requested in the prologue (the xAq panel in an LDS region
 // of its own behind the row tables, the wave's B^T fragments, column scale and bias in registers across the main loop), the first ring
 // step requested before anything else.
 // MRX (round 6): the same exchange for grids of SEVERAL rounds of 128-row tiles (2048 x 4096 -> 11008: 688 tiles on 256 resident
@@ -679,7 +679,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       }
     }
   };
-  const int xch_key = XCH_OK ? g.b_limbs * 16 + xch_nsl : 0;  // (wave-uniform; i8_amax_exchange_ok admits exactly six cases)
+  const int xch_key = XCH_OK ? g.b_limbs * 16 + xch_nsl : 0;  // (wave-uniform; gemm_plan.hip i8_in_launch_amax admits exactly six cases)
   // ... the waves' maxima through LDS (asm: an LDS access hipcc can see would wait for every LDS-DMA in flight): [wave][row] fp32 in
   // activation slot 3 - free in the prologue until the first LOAD requests step 3, and at the epilogue until the output transposes
   const uint32_t xch_red = lds0 + OFF_A + 3 * A_SLOT;
@@ -2097,100 +2097,38 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
 #endif
 }
 
-template <int DT, int NT>
-static int launch(GemmArgs g, bool lowrank, int bout, hipStream_t st);
+template <int DT, bool LR, int BO, bool SHIFT, int NT, bool W8 = false, bool XCH = false, bool MRX = false>
+static int run(const char* what, const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  constexpr int LDS = (XCH || MRX) ? Geo<NT>::KERNEL_LDS_XCH : Geo<NT>::KERNEL_LDS;
+  return launch_k<k_lqer_gemm_i8<DT, LR, BO, SHIFT, NT, W8, XCH, MRX>>(what, p.grid, 512, LDS, st, g);
+}
 
 // 8-bit weight codes: 128-row tiles with the codes straight into registers, or 256-row tiles with a half-step weight ring in LDS
 template <int DT, int NT>
-static int launch_w8(GemmArgs g, bool lowrank, int bout, hipStream_t st) {
-  constexpr int BM = Geo<NT>::BM, KERNEL_LDS = Geo<NT>::KERNEL_LDS;
-  g.tiles_m = (g.M + BM - 1) / BM;
-  g.tiles_n = g.Np / BN;
-  constexpr int CUS = 256;
-  const int nt_all = g.tiles_m * g.tiles_n;
-  const unsigned grid = (unsigned)(nt_all < CUS ? nt_all : CUS);
-#define LQER_I8_LAUNCH8(LR, BO)                                                                   \
-  do {                                                                                            \
-    static LdsLimitOnce lds_once;                                                                 \
-    lds_once.set((const void*)k_lqer_gemm_i8<DT, LR, BO, false, NT, true>, KERNEL_LDS);             \
-    k_lqer_gemm_i8<DT, LR, BO, false, NT, true><<<grid, 512, KERNEL_LDS, st>>>(g);                  \
-  } while (0)
+static int launch_w8(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if constexpr (NT == 4)  // one round, the B_out row maxima exchanged inside the launch: its own instantiation
+    if (p.amax == AMAX_XCH) return run<DT, true, 2, false, NT, true, true>("lqer_gemm_i8 (8-bit weights, exchange)", p, g, st);
+  if (!p.lowrank) return run<DT, false, 0, false, NT, true>("lqer_gemm_i8 (8-bit weights)", p, g, st);
+  return p.bout == 2 ? run<DT, true, 2, false, NT, true>("lqer_gemm_i8 (8-bit weights)", p, g, st)
+                     : run<DT, true, 0, false, NT, true>("lqer_gemm_i8 (8-bit weights)", p, g, st);
+}
+
+template <int DT, int NT, bool SHIFT>
+static int launch_w4(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
   if constexpr (NT == 4) {
-    if (g.bout_xch) {  // one round, the B_out row maxima exchanged inside the launch: its own instantiation
-      constexpr int LDS_X = Geo<NT>::KERNEL_LDS_XCH;
-      static LdsLimitOnce lds_once;
-      lds_once.set((const void*)k_lqer_gemm_i8<DT, true, 2, false, NT, true, true>, LDS_X);
-      k_lqer_gemm_i8<DT, true, 2, false, NT, true, true><<<grid, 512, LDS_X, st>>>(g);
-      return check_launch("lqer_gemm_i8 (8-bit weights, exchange)");
-    }
+    // several rounds, the row maxima computed and exchanged by the GEMM's own workgroups (MRX)
+    if (p.amax == AMAX_MRX) return run<DT, true, 2, SHIFT, NT, false, false, true>("lqer_gemm_i8 (multi-round exchange)", p, g, st);
+    // one round, the B_out row maxima exchanged inside the launch
+    if (p.amax == AMAX_XCH) return run<DT, true, 2, SHIFT, NT, false, true>("lqer_gemm_i8 (exchange)", p, g, st);
   }
-  if (!lowrank)
-    LQER_I8_LAUNCH8(false, 0);
-  else if (bout == 2)
-    LQER_I8_LAUNCH8(true, 2);
-  else
-    LQER_I8_LAUNCH8(true, 0);
-#undef LQER_I8_LAUNCH8
-  return check_launch("lqer_gemm_i8 (8-bit weights)");
+  if (!p.lowrank) return run<DT, false, 0, SHIFT, NT>("lqer_gemm_i8", p, g, st);
+  return p.bout == 2 ? run<DT, true, 2, SHIFT, NT>("lqer_gemm_i8", p, g, st) : run<DT, true, 0, SHIFT, NT>("lqer_gemm_i8", p, g, st);
 }
 
 template <int DT, int NT>
-static int launch(GemmArgs g, bool lowrank, int bout, hipStream_t st) {
-  constexpr int BM = Geo<NT>::BM, KERNEL_LDS = Geo<NT>::KERNEL_LDS;
-  g.tiles_m = (g.M + BM - 1) / BM;
-  g.tiles_n = g.Np / BN;
-  // persistent: at most one workgroup per CU (the LDS ring leaves room for one), each walks tiles b, b + grid, ...
-  constexpr int CUS = 256;
-  const int nt_all = g.tiles_m * g.tiles_n;
-  const unsigned grid = (unsigned)(nt_all < CUS ? nt_all : CUS);
-#define LQER_I8_LAUNCH(LR, BO)                                                                    \
-  do {                                                                                            \
-    if (g.i8_shift) {                                                                             \
-      static LdsLimitOnce lds_once;                                                               \
-      lds_once.set((const void*)k_lqer_gemm_i8<DT, LR, BO, true, NT>, KERNEL_LDS);                  \
-      k_lqer_gemm_i8<DT, LR, BO, true, NT><<<grid, 512, KERNEL_LDS, st>>>(g);                       \
-    } else {                                                                                      \
-      static LdsLimitOnce lds_once;                                                               \
-      lds_once.set((const void*)k_lqer_gemm_i8<DT, LR, BO, false, NT>, KERNEL_LDS);                 \
-      k_lqer_gemm_i8<DT, LR, BO, false, NT><<<grid, 512, KERNEL_LDS, st>>>(g);                      \
-    }                                                                                             \
-  } while (0)
-  if constexpr (NT == 4) {
-    if (g.bout_xch == 2) {  // several rounds, the row maxima computed and exchanged by the GEMM's own workgroups (MRX)
-      constexpr int LDS_X = Geo<NT>::KERNEL_LDS_XCH;
-      if (g.i8_shift) {
-        static LdsLimitOnce lds_once;
-        lds_once.set((const void*)k_lqer_gemm_i8<DT, true, 2, true, NT, false, false, true>, LDS_X);
-        k_lqer_gemm_i8<DT, true, 2, true, NT, false, false, true><<<grid, 512, LDS_X, st>>>(g);
-      } else {
-        static LdsLimitOnce lds_once;
-        lds_once.set((const void*)k_lqer_gemm_i8<DT, true, 2, false, NT, false, false, true>, LDS_X);
-        k_lqer_gemm_i8<DT, true, 2, false, NT, false, false, true><<<grid, 512, LDS_X, st>>>(g);
-      }
-      return check_launch("lqer_gemm_i8 (multi-round exchange)");
-    }
-    if (g.bout_xch) {  // one round, the B_out row maxima exchanged inside the launch: its own instantiation
-      constexpr int LDS_X = Geo<NT>::KERNEL_LDS_XCH;
-      if (g.i8_shift) {
-        static LdsLimitOnce lds_once;
-        lds_once.set((const void*)k_lqer_gemm_i8<DT, true, 2, true, NT, false, true>, LDS_X);
-        k_lqer_gemm_i8<DT, true, 2, true, NT, false, true><<<grid, 512, LDS_X, st>>>(g);
-      } else {
-        static LdsLimitOnce lds_once;
-        lds_once.set((const void*)k_lqer_gemm_i8<DT, true, 2, false, NT, false, true>, LDS_X);
-        k_lqer_gemm_i8<DT, true, 2, false, NT, false, true><<<grid, 512, LDS_X, st>>>(g);
-      }
-      return check_launch("lqer_gemm_i8 (exchange)");
-    }
-  }
-  if (!lowrank)
-    LQER_I8_LAUNCH(false, 0);
-  else if (bout == 2)
-    LQER_I8_LAUNCH(true, 2);
-  else
-    LQER_I8_LAUNCH(true, 0);
-#undef LQER_I8_LAUNCH
-  return check_launch("lqer_gemm_i8");
+static int launch(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if (p.i8_codes) return launch_w8<DT, NT>(p, g, st);
+  return p.i8_shift ? launch_w4<DT, NT, true>(p, g, st) : launch_w4<DT, NT, false>(p, g, st);
 }
 
 }  // namespace i8
@@ -2201,28 +2139,9 @@ extern "C" int lqer_debug_set_i8_stamp_buffer(void* p) {
 }
 #endif
 
-// Rows of a tile of the int8 kernel: rounds of one tile per CU (the grid is persistent: a CU walks ceil(tiles / 256) tiles), a
-// 128-row tile priced at 0.56 of a 256-row one (half the main loop and epilogue, the same ring fill and launch ramp; the weight
-// expand per MFMA doubles).  Llama-7B projections at M = 2048: 4096 x 4096 fills 128 CUs with 256-row tiles and all 256 with
-// 128-row ones; N = 11008: 2 rounds of 256 rows against 3 x 0.56.  LQER_TUNE_I8_ROWS_* pins the choice (tests: same bits).
-int i8_tile_rows(const GemmArgs& g) {
-  if (g.tuning & LQER_TUNE_I8_ROWS_128) return 128;
-  if (g.tuning & LQER_TUNE_I8_ROWS_256) return 256;
-  // (8-bit weight codes: the same rule - the 128-row kernel, codes straight into registers, takes 35.8 us per round of 4096-k tiles
-  // against 63.5 us of the 256-row kernel's half-step LDS ring: 0.56 again.  M = 2048 x 4096 x 4096: 128 rows, all 256 CUs,
-  // 35.8 us against 63 us on half of them; M = 8192: 256 rows, 127 us against 137 us)
-  constexpr int64_t CUS = 256;
-  const int64_t tn = g.Np / i8::BN;
-  const int64_t r256 = (((g.M + 255) / 256) * tn + CUS - 1) / CUS, r128 = (((g.M + 127) / 128) * tn + CUS - 1) / CUS;
-  return r128 * 56 < r256 * 100 ? 128 : 256;
-}
-
-// The int8 kernel exchanges the B_out row maxima itself (no pre-pass launch) when every tile is resident at once - one round of
-// 128-row tiles, at most one per CU -, the row band has at most LQER_AMAX_NSEG column tiles (one granule each per row) and the side
-// product is at most 2 limbs x 4 slices (its operands wait in registers under the ring fill).
-// (the CUs this device really has - a partitioned part shows 32 of them: a grid that runs in rounds there would send every workgroup
-// through its polls and its fall-back; queried once per device)
-static int device_cus() {
+// The CUs this device really has (a partitioned part shows 32 of them), queried once per device: the one HIP query among the inputs
+// of plan_gemm, which asks whether a grid is resident at once before it lets the kernel exchange the B_out row maxima itself.
+int device_cus() {
   static std::atomic<int> cus[64];
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -2234,60 +2153,11 @@ static int device_cus() {
   return c;
 }
 
-bool i8_amax_exchange_ok(const GemmArgs& g, bool lowrank, int bout) {
-  if (!lowrank || bout != 2 || g.bout_nblk != 1) return false;
-  if (i8_tile_rows(g) != 128) return false;
-  const int64_t tn = g.Np / i8::BN, tm = (g.M + 127) / 128;
-  const int cus = device_cus();
-  if (tn > LQER_AMAX_NSEG || tm * tn > (cus < 256 ? cus : 256)) return false;
-  const int nsl = g.rp / 16;
-  return (g.b_limbs == 1 || g.b_limbs == 2) && (nsl == 1 || nsl == 2 || nsl == 4);
-}
-
-// ... and over SEVERAL rounds of 128-row tiles (MRX: 4-bit weights): the persistent grid of min(tiles, 256) workgroups is resident at
-// once, and every (row band, sixteenth of the columns) item of the pre-pass has a workgroup of its own.
-bool i8_amax_mrx_ok(const GemmArgs& g, bool lowrank, int bout) {
-  if (!lowrank || bout != 2 || g.bout_nblk != 1 || g.w_i8codes || g.rp > 64) return false;
-  if (i8_tile_rows(g) != 128) return false;
-  const int64_t tn = g.Np / i8::BN, tm = (g.M + 127) / 128;
-  const int cus = device_cus();
-  const int64_t grid = tm * tn < 256 ? tm * tn : 256;
-  if (tm * tn <= (cus < 256 ? cus : 256) && tn <= LQER_AMAX_NSEG) return false;  // (one round: the exchange instantiation)
-  if (grid > cus || tm * LQER_AMAX_NSEG > grid) return false;
-  const int nsl = g.rp / 16;
-  return (g.b_limbs == 1 || g.b_limbs == 2) && (nsl == 1 || nsl == 2 || nsl == 4);
-}
-
-// The int8 main loop needs: the int8 images (g.w8 set by the caller for an LQER_Q_MXINT_I8 descriptor), a token count of the
-// tile kernels (M >= 128; below, the sign-magnitude image serves the weight-streaming and 64-row kernels), B_out pass-through
-// or one block per row, at most two 64-column panels of xAq.  An int8 tile costs 0.58 (256 rows) / 0.65 (128 rows) of the bf16
-// kernel's tiles over the same rows, so there is no token count from which the bf16 tile kernel would be the better choice.
-bool i8_eligible(const GemmArgs& g, int bout) {
-  if (!g.w8 || g.M < 128) return false;
-  if (!(bout == 0 || (bout == 2 && g.bout_nblk == 1))) return false;
-  if (g.rp > 128) return false;
-  return true;
-}
-
-int i8_dispatch(const GemmArgs& g, int dtype, bool lowrank, int bout, hipStream_t st) {
-  if (g.w_i8codes) {
-    const bool w128 = i8_tile_rows(g) == 128;
-    switch (dtype) {
-      case LQER_F32: return w128 ? i8::launch_w8<LQER_F32, 4>(g, lowrank, bout, st) : i8::launch_w8<LQER_F32, 8>(g, lowrank, bout, st);
-      case LQER_F16: return w128 ? i8::launch_w8<LQER_F16, 4>(g, lowrank, bout, st) : i8::launch_w8<LQER_F16, 8>(g, lowrank, bout, st);
-      case LQER_BF16: return w128 ? i8::launch_w8<LQER_BF16, 4>(g, lowrank, bout, st) : i8::launch_w8<LQER_BF16, 8>(g, lowrank, bout, st);
-    }
-    set_error("unknown dtype %d", dtype);
-    return LQER_E_INVALID;
-  }
-  const bool t128 = i8_tile_rows(g) == 128;
-  switch (dtype) {
-    case LQER_F32: return t128 ? i8::launch<LQER_F32, 4>(g, lowrank, bout, st) : i8::launch<LQER_F32, 8>(g, lowrank, bout, st);
-    case LQER_F16: return t128 ? i8::launch<LQER_F16, 4>(g, lowrank, bout, st) : i8::launch<LQER_F16, 8>(g, lowrank, bout, st);
-    case LQER_BF16: return t128 ? i8::launch<LQER_BF16, 4>(g, lowrank, bout, st) : i8::launch<LQER_BF16, 8>(g, lowrank, bout, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+int i8_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {
+  return with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    return p.tile_rows == 128 ? i8::launch<DT, 4>(p, g, st) : i8::launch<DT, 8>(p, g, st);
+  });
 }
 
 int i8_prepare_dispatch(const void* w_packed, int64_t N, int64_t K, int mbits, void* w_i8, int32_t* flags, hipStream_t st) {

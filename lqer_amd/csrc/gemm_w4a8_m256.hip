@@ -13,10 +13,10 @@
 // would not fit beside the accumulators: LOAD(h) reads the 16 activation fragments and the two code words of
 // half-step h, issues half of the step's prefetch (k-step + 2 into a 3-slot ring), waits, barrier; COMPUTE(h)
 // expands 2 weight fragments and issues 16 MFMAs, barrier.  The two waves of a SIMD run one barrier apart.
-// Used for shapes with at least two rounds of 256 x 256 tiles (gemm_dispatch).
+// Used for shapes with at least two rounds of 256 x 256 tiles (plan_gemm).
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace lqer {
 
@@ -401,54 +401,30 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
   }
 }
 
+template <int DT, bool LR, int BO>
+static int run(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  return launch_k<k_lqer_gemm_m256<DT, LR, BO>>("lqer_gemm_m256", p.grid, 512, GEMM_LDS, st, g);
+}
+
 template <int DT>
-static int launch(GemmArgs g, bool lowrank, int bout, hipStream_t st) {
-  g.tiles_m = (g.M + BM - 1) / BM;
-  g.tiles_n = g.Np / BN;
-  const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n);
-#define LQER_M256_LAUNCH(LR, BO)                                                                                    \
-  do {                                                                                                              \
-    static LdsLimitOnce lds_once;                                                                                   \
-    lds_once.set((const void*)k_lqer_gemm_m256<DT, LR, BO>, GEMM_LDS);                                              \
-    k_lqer_gemm_m256<DT, LR, BO><<<grid, 512, GEMM_LDS, st>>>(g);                                                   \
-  } while (0)
-  if (!lowrank)
-    LQER_M256_LAUNCH(false, 0);
-  else if (bout == 1)
-    LQER_M256_LAUNCH(true, 1);
-  else if (bout == 2)
-    LQER_M256_LAUNCH(true, 2);
-  else
-    LQER_M256_LAUNCH(true, 0);
-#undef LQER_M256_LAUNCH
-  return check_launch("lqer_gemm_m256");
+static int launch(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if (!p.lowrank) return run<DT, false, 0>(p, g, st);
+  switch (p.bout) {
+    case 1: return run<DT, true, 1>(p, g, st);
+    case 2: return run<DT, true, 2>(p, g, st);
+    default: return run<DT, true, 0>(p, g, st);
+  }
 }
 
 }  // namespace m256
 
-// A 256 x 256 tile costs about 1.9 tiles of 128 x 256 (one weight expand per 8 MFMAs instead of 4, half the per-tile
-// fixed work), but both kernels run in whole rounds of one tile per CU: take the large tiles only when they still need
-// less time after rounding up - e.g. 16384 x 5120: 5 rounds against 10, 4096 x 4096: 1 against 2, but 2048 x 11008:
-// 2 (344 tiles) against 3 (688) keeps the small tiles (measured: 157 vs 178 us).
-#ifndef LQER_M256_MIN_M
-#define LQER_M256_MIN_M 512
-#endif
-bool m256_eligible(const GemmArgs& g) {
-  constexpr int64_t CUS = 256;
-  const int64_t t256 = (int64_t)((g.M + m256::BM - 1) / m256::BM) * (g.Np / m256::BN);
-  const int64_t t128 = (int64_t)((g.M + 127) / 128) * (g.Np / m256::BN);
-  const int64_t r256 = (t256 + CUS - 1) / CUS, r128 = (t128 + CUS - 1) / CUS;
-  return g.M >= LQER_M256_MIN_M && r256 * 19 < r128 * 10;
-}
-
-int m256_dispatch(const GemmArgs& g, int dtype, bool lowrank, int bout, hipStream_t st) {
-  switch (dtype) {
-    case LQER_F32: return m256::launch<LQER_F32>(g, lowrank, bout, st);
-    case LQER_F16: return g.x_f16 ? m256::launch<LQER_F16X>(g, lowrank, bout, st) : m256::launch<LQER_F16>(g, lowrank, bout, st);
-    case LQER_BF16: return m256::launch<LQER_BF16>(g, lowrank, bout, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+int m256_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {
+  return with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if constexpr (DT == LQER_F16)
+      if (p.f16x) return m256::launch<LQER_F16X>(p, g, st);
+    return m256::launch<DT>(p, g, st);
+  });
 }
 
 }  // namespace lqer

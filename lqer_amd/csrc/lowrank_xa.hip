@@ -666,23 +666,19 @@ __global__ __launch_bounds__(64 * WAVES) void k_quant_xa128(const uint8_t* __res
 #endif                      // rank-96 / 128 forward at K = 4096 against 128-row tiles; +-0 at K = 16384)
 constexpr int qx_rows = LQER_QXA128_ROWS;  // token rows per workgroup of the fused quantizer (its K chunks double at 64)
 template <int DT, int NT>
-static void launch_q(const void* x, int64_t M, int64_t K, int64_t ldx_b, const QP& q, bf16_t* xq, int64_t Kp, const bf16_t* a_img,
+static int launch_q(const void* x, int64_t M, int64_t K, int64_t ldx_b, const QP& q, bf16_t* xq, int64_t Kp, const bf16_t* a_img,
                      int row_groups, int tiles, int nch, int spc, int steps_total, float* part, hipStream_t st) {
   constexpr int W = LQER_QXA128_WAVES, R = LQER_QXA128_ROWS;
   constexpr int lds = 3 * (R * BKB + 32 * NT * 128);
-  static LdsLimitOnce once;
-  once.set((const void*)k_quant_xa128<DT, NT, W, R>, lds);
-  k_quant_xa128<DT, NT, W, R><<<(unsigned)(tiles * nch), 64 * W, lds, st>>>((const uint8_t*)x, M, K, ldx_b, q, (uint8_t*)xq, Kp, a_img,
-                                                                           row_groups, nch, spc, steps_total, part);
+  return launch_k<k_quant_xa128<DT, NT, W, R>>("quantize_act_xa", (unsigned)(tiles * nch), 64 * W, lds, st, (const uint8_t*)x, M, K, ldx_b, q,
+                                               (uint8_t*)xq, Kp, a_img, row_groups, nch, spc, steps_total, part);
 }
 
 template <int NT, bool I8>
-static void launch(const void* xq, int64_t x_ld, const bf16_t* a_img, int64_t Kp, int row_groups, int tiles, int nch, int spc,
+static int launch(const void* xq, int64_t x_ld, const bf16_t* a_img, int64_t Kp, int row_groups, int tiles, int nch, int spc,
                    int steps_total, float* part, hipStream_t st) {
-  static LdsLimitOnce once;
-  once.set((const void*)k_xa_partial_lds<NT, I8>, lds_bytes(NT, I8));
-  k_xa_partial_lds<NT, I8><<<(unsigned)(tiles * nch), 256, lds_bytes(NT, I8), st>>>((const uint8_t*)xq, x_ld, a_img, Kp, row_groups, nch,
-                                                                                    spc, steps_total, part);
+  return launch_k<k_xa_partial_lds<NT, I8>>("lowrank_xa", (unsigned)(tiles * nch), 256, lds_bytes(NT, I8), st, (const uint8_t*)xq, x_ld, a_img, Kp,
+                                            row_groups, nch, spc, steps_total, part);
 }
 }  // namespace xal
 
@@ -1018,11 +1014,13 @@ int quant_xa_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int6
     const size_t need = (size_t)nch * plan.row_groups * XA_ROWS * rp * sizeof(float);
     if (!scratch || scratch_bytes < need) return LQER_E_UNSUPPORTED;
     const int nt = rp / 32;
-#define QX128(DT) (nt == 3 ? xal::launch_q<DT, 3>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st) \
-                           : xal::launch_q<DT, 4>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st))
-    if (dtype == LQER_F16) QX128(LQER_F16); else QX128(LQER_BF16);
-#undef QX128
-    if (!xaq) return check_launch("quantize_act_xa");
+    auto run = [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      return nt == 3 ? xal::launch_q<DT, 3>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st)
+                     : xal::launch_q<DT, 4>(x, M, K, ldx_b, qx, xq, Kp, a_t, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
+    };
+    const int rc = dtype == LQER_F16 ? run(std::integral_constant<int, LQER_F16>{}) : run(std::integral_constant<int, LQER_BF16>{});
+    if (rc || !xaq) return rc;
     const int64_t items = (int64_t)plan.row_groups * XA_ROWS * rp / 4;
     const unsigned bs = items <= 128 * 256 ? 64 : 256;
     const unsigned grid2 = (unsigned)((items + bs - 1) / bs);
@@ -1045,16 +1043,13 @@ int quant_xa_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int6
   const int esz = dtype == LQER_F32 ? 4 : 2;
   const bool vec = ((uintptr_t)x % 16 == 0) && ((ldx * esz) % 16 == 0);
   const unsigned grid = (unsigned)(plan.row_groups * plan.nchunk);
-#define QX_LAUNCH(DT, NT) k_quant_xa16<DT, NT><<<grid, QX_K, 0, st>>>(x, M, K, ldx, vec, qx, xq, Kp, a_t, a_limbs, rp, plan.row_groups, scratch)
   const int nt = (rp + 31) / 32;
-  switch (dtype) {
-    case LQER_F32: if (nt == 1) QX_LAUNCH(LQER_F32, 1); else QX_LAUNCH(LQER_F32, 2); break;
-    case LQER_F16: if (nt == 1) QX_LAUNCH(LQER_F16, 1); else QX_LAUNCH(LQER_F16, 2); break;
-    case LQER_BF16: if (nt == 1) QX_LAUNCH(LQER_BF16, 1); else QX_LAUNCH(LQER_BF16, 2); break;
-    default: set_error("unknown dtype %d", dtype); return LQER_E_INVALID;
-  }
-#undef QX_LAUNCH
-  if (!xaq) return check_launch("quantize_act_xa");  // the consumer reduces the partial tiles itself
+  const int rc = with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    return nt == 1 ? launch_k<k_quant_xa16<DT, 1>>("quantize_act_xa", grid, QX_K, 0, st, x, M, K, ldx, vec, qx, xq, Kp, a_t, a_limbs, rp, plan.row_groups, scratch)
+                   : launch_k<k_quant_xa16<DT, 2>>("quantize_act_xa", grid, QX_K, 0, st, x, M, K, ldx, vec, qx, xq, Kp, a_t, a_limbs, rp, plan.row_groups, scratch);
+  });
+  if (rc || !xaq) return rc;  // (xaq == nullptr: the consumer reduces the partial tiles itself)
   const int64_t items = (int64_t)plan.row_groups * XA_ROWS * rp / 4;
   const unsigned bs = items <= 128 * 256 ? 64 : 256;  // up to 32 Ki items (C2: 16 Ki): one wave per workgroup spreads them over all CUs
   const unsigned grid2 = (unsigned)((items + bs - 1) / bs);
@@ -1126,13 +1121,15 @@ int lowrank_xa_dispatch(const bf16_t* xq, int64_t M, int64_t K, int x_limbs, con
     const int spc = (steps_total + nch - 1) / nch;
     nch = (steps_total + spc - 1) / spc;
     plan_l.nchunk = nch;
+    int rc;
     if (lds_i8) {
-      if (nt == 1) xal::launch<1, true>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
-      else xal::launch<2, true>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
+      if (nt == 1) rc = xal::launch<1, true>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
+      else rc = xal::launch<2, true>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
     } else {
-      if (nt == 3) xal::launch<3, false>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
-      else xal::launch<4, false>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
+      if (nt == 3) rc = xal::launch<3, false>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
+      else rc = xal::launch<4, false>(xq, x_ld, a_t, Kp, plan.row_groups, tiles, nch, spc, steps_total, scratch, st);
     }
+    if (rc) return rc;
     staged = true;
   }
   // row groups per wave: two while RG x NT accumulator tiles + two activation windows fit the register file

@@ -537,13 +537,9 @@ static int launch_qmm(const void* x, const void* y, void* out, int64_t batch, in
 int qmatmul_dispatch(const void* x, const void* y, void* out, int dtype, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs,
                      int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, void* workspace, hipStream_t st) {
   if (batch == 0 || S1 == 0 || S2 == 0) return LQER_OK;
-  switch (dtype) {
-    case LQER_F32: return launch_qmm<LQER_F32>(x, y, out, batch, S1, K, S2, x_bs, x_rs, y_bs, y_ks, y_js, qx, qy, (bf16_t*)workspace, st);
-    case LQER_F16: return launch_qmm<LQER_F16>(x, y, out, batch, S1, K, S2, x_bs, x_rs, y_bs, y_ks, y_js, qx, qy, (bf16_t*)workspace, st);
-    case LQER_BF16: return launch_qmm<LQER_BF16>(x, y, out, batch, S1, K, S2, x_bs, x_rs, y_bs, y_ks, y_js, qx, qy, (bf16_t*)workspace, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  return with_dtype(dtype, [&](auto dt) {
+    return launch_qmm<decltype(dt)::value>(x, y, out, batch, S1, K, S2, x_bs, x_rs, y_bs, y_ks, y_js, qx, qy, (bf16_t*)workspace, st);
+  });
 }
 
 }  // namespace lqer

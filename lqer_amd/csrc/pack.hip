@@ -300,13 +300,7 @@ int pack_weight_dispatch(const void* W, int dtype, int64_t N, int64_t K, int64_t
     set_error("w_quantizer block %d: must be a multiple of 16 or cover the row", q.block);
     return LQER_E_UNSUPPORTED;
   }
-  switch (dtype) {
-    case LQER_F32: return pack_w<LQER_F32>(W, N, K, ld, q, block_rows, (uint8_t*)out, (int8_t*)scratch, st);
-    case LQER_F16: return pack_w<LQER_F16>(W, N, K, ld, q, block_rows, (uint8_t*)out, (int8_t*)scratch, st);
-    case LQER_BF16: return pack_w<LQER_BF16>(W, N, K, ld, q, block_rows, (uint8_t*)out, (int8_t*)scratch, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  return with_dtype(dtype, [&](auto dt) { return pack_w<decltype(dt)::value>(W, N, K, ld, q, block_rows, (uint8_t*)out, (int8_t*)scratch, st); });
 }
 
 // scale_byte = 127 + s of the format's e4m3 table (mf_e4m3_table, which the caller built and checked: the GEMM reads that very table)
@@ -319,13 +313,9 @@ int pack_weight_mf_dispatch(const void* W, int dtype, int64_t N, int64_t K, int6
   const int64_t Np = lqer_padded_n(N), Kp = lqer_padded_k(K);
   const int64_t total = Np * (Kp / 16);
   const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-  switch (dtype) {
-    case LQER_F32: k_w_pack_mf<LQER_F32><<<grid, 256, 0, st>>>(W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out); break;
-    case LQER_F16: k_w_pack_mf<LQER_F16><<<grid, 256, 0, st>>>(W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out); break;
-    case LQER_BF16: k_w_pack_mf<LQER_BF16><<<grid, 256, 0, st>>>(W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out); break;
-    default: set_error("unknown dtype %d", dtype); return LQER_E_INVALID;
-  }
-  return check_launch("pack_weight (minifloat)");
+  return with_dtype(dtype, [&](auto dt) {
+    return launch_k<k_w_pack_mf<decltype(dt)::value>>("pack_weight (minifloat)", grid, 256, 0, st, W, N, K, ld, q, scale_byte, Np, Kp, (uint8_t*)out);
+  });
 }
 
 int unpack_weight_mf_dispatch(const void* in, int64_t N, int64_t K, const uint32_t (&lut)[2], float* out, hipStream_t st) {
@@ -366,13 +356,7 @@ static int pack_lr(const void* A, const void* B, int64_t K, int64_t N, int64_t r
 
 int pack_lowrank_dispatch(const void* A, const void* B, int dtype, int64_t K, int64_t N, int64_t r, void* a_t,
                           void* b_t, int32_t* flags, hipStream_t st) {
-  switch (dtype) {
-    case LQER_F32: return pack_lr<LQER_F32>(A, B, K, N, r, (bf16_t*)a_t, (bf16_t*)b_t, flags, st);
-    case LQER_F16: return pack_lr<LQER_F16>(A, B, K, N, r, (bf16_t*)a_t, (bf16_t*)b_t, flags, st);
-    case LQER_BF16: return pack_lr<LQER_BF16>(A, B, K, N, r, (bf16_t*)a_t, (bf16_t*)b_t, flags, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  return with_dtype(dtype, [&](auto dt) { return pack_lr<decltype(dt)::value>(A, B, K, N, r, (bf16_t*)a_t, (bf16_t*)b_t, flags, st); });
 }
 
 // ---- fp16 fast path of pass-through fp16 activations (LQER_Q_PASSTHROUGH_F16) -----------------------------------
@@ -423,13 +407,7 @@ int f16_prepare_dispatch(const void* w_packed, int64_t N, int64_t K, const void*
 int bias_passthrough_dispatch(const void* b, int dtype, int64_t N, float* out, hipStream_t st) {
   const int64_t Np = lqer_padded_n(N);
   const unsigned grid = (unsigned)((Np + 255) / 256);
-  switch (dtype) {
-    case LQER_F32: k_bias_passthrough<LQER_F32><<<grid, 256, 0, st>>>(b, N, Np, out); break;
-    case LQER_F16: k_bias_passthrough<LQER_F16><<<grid, 256, 0, st>>>(b, N, Np, out); break;
-    case LQER_BF16: k_bias_passthrough<LQER_BF16><<<grid, 256, 0, st>>>(b, N, Np, out); break;
-    default: set_error("unknown dtype %d", dtype); return LQER_E_INVALID;
-  }
-  return check_launch("pack_bias");
+  return with_dtype(dtype, [&](auto dt) { return launch_k<k_bias_passthrough<decltype(dt)::value>>("pack_bias", grid, 256, 0, st, b, N, Np, out); });
 }
 
 }  // namespace lqer

@@ -396,13 +396,7 @@ static int launch_quant(const void* x, int64_t rows, int64_t cols, int64_t ld, c
 
 int quantize_dispatch(const void* x, int dtype, int64_t rows, int64_t cols, int64_t ld, const QP& q,
                       const QuantOut& o, hipStream_t st) {
-  switch (dtype) {
-    case LQER_F32: return launch_quant<LQER_F32>(x, rows, cols, ld, q, o, st);
-    case LQER_F16: return launch_quant<LQER_F16>(x, rows, cols, ld, q, o, st);
-    case LQER_BF16: return launch_quant<LQER_BF16>(x, rows, cols, ld, q, o, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  return with_dtype(dtype, [&](auto dt) { return launch_quant<decltype(dt)::value>(x, rows, cols, ld, q, o, st); });
 }
 
 // ---- 2-D tiles of an activation (blocks that span token rows) --------------------------------------------------------------------
@@ -471,13 +465,7 @@ static int launch_tiles(const void* x, int64_t batches, int64_t rows, int64_t co
 
 int quantize_tiles_dispatch(const void* x, int dtype, int64_t batches, int64_t rows, int64_t cols, int64_t R, int64_t L, const QP& q,
                             float* out, float* amax, hipStream_t st) {
-  switch (dtype) {
-    case LQER_F32: return launch_tiles<LQER_F32>(x, batches, rows, cols, R, L, q, out, amax, st);
-    case LQER_F16: return launch_tiles<LQER_F16>(x, batches, rows, cols, R, L, q, out, amax, st);
-    case LQER_BF16: return launch_tiles<LQER_BF16>(x, batches, rows, cols, R, L, q, out, amax, st);
-  }
-  set_error("unknown dtype %d", dtype);
-  return LQER_E_INVALID;
+  return with_dtype(dtype, [&](auto dt) { return launch_tiles<decltype(dt)::value>(x, batches, rows, cols, R, L, q, out, amax, st); });
 }
 
 }  // namespace lqer

@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Device code of two builds, kernel by kernel: codeobj_diff.py OBJDIR_A OBJDIR_B  (make OBJDIR=...; no GPU needed).
+For every X.o of either directory: the gfx950 code object's FUNC / OBJECT symbols (name, size), each function's disassembly with
+addresses stripped, and the amdhsa.kernels notes (registers, LDS, scratch, kernarg size) must be equal.  Exit status 1 if not."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+run = lambda *a: subprocess.run(a, check=True, capture_output=True, text=True).stdout
+
+
+def device_code(obj, tmp):
+    fat, co = os.path.join(tmp, "f.fat"), os.path.join(tmp, "f.co")
+    if ".hip_fatbin" not in run(f"{LLVM}/llvm-readelf", "-S", "-W", obj):
+        return {}, {}, {}  # (host code only)
+    run(f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj)
+    run(f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}")
+    syms = {}
+    for ln in run(f"{LLVM}/llvm-readelf", "-s", "-W", co).splitlines():
+        f = ln.split()
+        if len(f) == 8 and f[3] in ("FUNC", "OBJECT") and not f[7].startswith("__hip_cuid_"):
+            syms[f[7]] = (f[3], f[2])
+    code, name = {}, None
+    for ln in run(f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co).splitlines():
+        m = re.match(r"^(?:[0-9a-f]+ )?<(.+)>:$", ln)
+        if m:
+            name = m.group(1)
+        elif name and ln.strip() not in ("", "..."):  # ("...": the padding behind the last function)
+            code.setdefault(name, []).append(re.sub(r"\s*// [0-9A-Fa-f]+:.*$|<[^>]*\+0x[0-9a-f]+>", "", ln).strip())
+    notes = run(f"{LLVM}/llvm-readelf", "--notes", co)
+    keys = r"\.(\w*gpr_count|\w*_spill_count|\w+_segment_\w*size|max_flat_workgroup_size|uses_dynamic_stack):\s+(\S+)"
+    meta = {m.group(1): sorted(re.findall(keys, blk)) for blk in notes.split("  - .") if (m := re.search(r"\.name:\s+(\S+)", blk))
+            and ".kernarg_segment_size" in blk}
+    return syms, code, meta
+
+
+def main(a, b):
+    bad = 0
+    for o in sorted({f for d in (a, b) for f in os.listdir(d) if f.endswith(".o")}):
+        pa, pb = os.path.join(a, o), os.path.join(b, o)
+        if not (os.path.exists(pa) and os.path.exists(pb)):
+            with tempfile.TemporaryDirectory() as t:
+                only = device_code(pa if os.path.exists(pa) else pb, t)
+            kernels = len(only[2])
+            print(f"{o}: in one build only, {kernels} kernels")
+            bad += kernels > 0
+            continue
+        with tempfile.TemporaryDirectory() as t:
+            A, B = device_code(pa, t), device_code(pb, t)
+        diff = [f"{what} {k}" for what, x, y in zip(("symbol", "code", "notes"), A, B) for k in sorted(set(x) | set(y)) if x.get(k) != y.get(k)]
+        assert len(A[1]) >= len(A[2]), f"{o}: {len(A[1])} functions disassembled for {len(A[2])} kernels"
+        print(f"{o}: {len(A[0])} symbols, {len(A[1])} functions, {len(A[2])} kernels: " + ("identical" if not diff else "DIFFERENT: " + "; ".join(diff[:8])))
+        bad += bool(diff)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1], sys.argv[2]))
