@@ -533,6 +533,36 @@ int lqer_attention_q(const void* q, const void* k, const void* v, const void* ma
                      float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
                      const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same attention for decode steps, split over the keys (reference models/llama_decoder.py:259-297, opt_decoder.py:125,190
+ * with 1 <= S <= 8 query rows - a step of generate() with a KV cache, or up to 8 speculated tokens) ------------------------------
+ * The arithmetic, the strides, the two mask forms (causal: key j visible to query i iff j <= i + (T - S)), row_stats and the
+ * argument list are lqer_attention_q's; the results agree with it within the order of the fp32 sums.  lqer_attention_q gives every
+ * query a lane and every 128 queries a workgroup - one live lane in 32 at S = 1 - and writes two bf16 images of K and V first; this
+ * call gives every CHUNK of keys a workgroup that serves all (heads / kv_heads) S query rows of a kv head and reads K and V once, in
+ * DT, from the caller's tensors (rows of q, k, v that are not 16-byte aligned take element loads: same bits).  P is normalised by
+ * the whole row's sum before it is quantized, so there is no online softmax: the scores of all chunks come first.
+ * Chunks: C = 16 min(max(ceil(T / 256), 1), 8) keys, nch = ceil(T / C) of them - a function of T alone; every sum over chunks runs in
+ * chunk order and nothing is accumulated with atomics: the same bits run to run, for a batch slice, and for a slice of the heads of
+ * one kv group.
+ * workspace: lqer_attention_q_decode_workspace_bytes(...) bytes, 256-byte aligned, contents irrelevant on entry (nothing survives
+ * between calls, no counters), layout with rows = batch heads S
+ *   [S2, fp32: rows x (nch C)][chunk statistics {max, sum exp(S2 - max)}, fp32: rows x nch x 2][partial outputs, fp32: rows x nch x D]
+ * each part rounded up to 256 bytes; 0 for batch = 0, S = 0 or T = 0.  Three launches on `stream` (scores and chunk statistics;
+ * P and the chunk's P V; the sum over chunks, which stores through out_strides), no allocation, no host synchronisation, no wait:
+ * capturable in a hipGraph.
+ * Refused with a message, nothing launched or touched:
+ *   LQER_E_UNSUPPORTED  S > 8; a format that is not LQER_Q_MXINT, width <= 8, block 16; D not a multiple of 16 or > 128; T > 2^30;
+ *                       batch or kv_heads > 65535;
+ *   LQER_E_INVALID      a null pointer (q, k, v, out, workspace, a stride array, a format); heads not a multiple of kv_heads; negative
+ *                       sizes; T = 0 with work to do; an unknown dtype; a workspace shorter than the query function's or not
+ *                       16-byte aligned (the kernels access it in 16-byte pieces); mask together with causal = 1. */
+size_t lqer_attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D);
+int lqer_attention_q_decode(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype,
+                            int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                            const int64_t* k_strides, const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides,
+                            float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                            const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's
  * x.float() does) for the per-input-channel sum|x| and max|x|; any of the three outputs may be NULL, not all of them:

@@ -119,6 +119,10 @@ SIGNATURES = {
     "lqer_attention_q_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _sp, _sp, _sp, _sp, _sp, C.c_float, _i,
                               _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    # ... for 1 <= S <= 8 query rows, split over the keys (csrc/attn_decode.hip): the same argument list
+    "lqer_attention_q_decode_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "lqer_attention_q_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _sp, _sp, _sp, _sp, _sp, C.c_float,
+                                     _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1149,6 +1149,92 @@ int lqer_attention_q(const void* q, const void* k, const void* v, const void* ma
                               (hipStream_t)stream);
 }
 
+size_t lqer_attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D) {
+  if (batch <= 0 || heads <= 0 || kv_heads <= 0 || S <= 0 || T <= 0 || D <= 0) return 0;
+  return attention_q_decode_workspace_bytes(batch, heads, S, T, D);
+}
+
+int lqer_attention_q_decode(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                            int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
+                            const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                            const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (batch < 0 || heads <= 0 || kv_heads <= 0 || S < 0 || T < 0 || D <= 0) {
+    set_error("attention_q_decode: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", (long long)batch, (long long)heads,
+              (long long)kv_heads, (long long)S, (long long)T, (long long)D);
+    return LQER_E_INVALID;
+  }
+  if (heads % kv_heads != 0) {
+    set_error("attention_q_decode: heads %lld is not a multiple of kv_heads %lld", (long long)heads, (long long)kv_heads);
+    return LQER_E_INVALID;
+  }
+  if (dtype != LQER_F32 && dtype != LQER_F16 && dtype != LQER_BF16) {
+    set_error("attention_q_decode: unknown dtype %d", dtype);
+    return LQER_E_INVALID;
+  }
+  if (!q_strides || !k_strides || !v_strides || !out_strides || (mask && !mask_strides)) {
+    set_error("attention_q_decode: null stride array");
+    return LQER_E_INVALID;
+  }
+  if (mask && causal) {
+    set_error("attention_q_decode: a mask tensor and causal = 1 are two forms of one mask - pass one");
+    return LQER_E_INVALID;
+  }
+  if (!q_fmt || !k_fmt || !p_fmt || !v_fmt) {
+    set_error("attention_q_decode: null quantizer format");
+    return LQER_E_INVALID;
+  }
+  if (S > attention_q_decode_max_s()) {
+    set_error("attention_q_decode: S = %lld query rows - the split over the keys takes up to %d (lqer_attention_q takes any)", (long long)S,
+              attention_q_decode_max_s());
+    return LQER_E_UNSUPPORTED;
+  }
+  if (D % 16 != 0 || D > 128) {
+    set_error("attention_q_decode: head dim %lld - the fused kernels take multiples of 16 up to 128 (the two products of lqer_matmul_q take any)",
+              (long long)D);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (!fmt_ok(q_fmt, "attention Q quantizer", 8) || !fmt_ok(k_fmt, "attention K quantizer", 8) || !fmt_ok(p_fmt, "attention P quantizer", 8) ||
+      !fmt_ok(v_fmt, "attention V quantizer", 8))
+    return LQER_E_UNSUPPORTED;
+  for (const lqer_qfmt_t* f : {q_fmt, k_fmt, p_fmt, v_fmt})
+    if (f->kind != LQER_Q_MXINT || f->block != 16) {
+      set_error("attention_q_decode: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
+                "formats run as the two products of lqer_matmul_q", f->kind, f->block);
+      return LQER_E_UNSUPPORTED;
+    }
+  if (T > (int64_t)1 << 30) {  // (chunk indices and the fold over them are 32-bit)
+    set_error("attention_q_decode: T = %lld beyond 2^30 keys", (long long)T);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (batch > 65535 || kv_heads > 65535) {
+    set_error("attention_q_decode: batch %lld / kv_heads %lld beyond the launch grid (65535 each): call in chunks", (long long)batch,
+              (long long)kv_heads);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (batch == 0 || S == 0) return LQER_OK;
+  if (T == 0) {
+    set_error("attention_q_decode: T = 0 (a softmax over no keys)");
+    return LQER_E_INVALID;
+  }
+  if (!q || !k || !v || !out || !workspace) {
+    set_error("attention_q_decode: null pointer");
+    return LQER_E_INVALID;
+  }
+  if ((uintptr_t)workspace % 16 != 0) {  // (the kernels store and load the workspace in 16-byte pieces)
+    set_error("attention_q_decode: workspace %p is not 16-byte aligned", workspace);
+    return LQER_E_INVALID;
+  }
+  const size_t need = attention_q_decode_workspace_bytes(batch, heads, S, T, D);
+  if (workspace_bytes < need) {
+    set_error("attention_q_decode: workspace %zu B < %zu B (lqer_attention_q_decode_workspace_bytes)", workspace_bytes, need);
+    return LQER_E_INVALID;
+  }
+  return attention_q_decode_dispatch(q, k, v, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides,
+                                     mask_strides, out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt),
+                                     make_qp(*v_fmt), workspace, (hipStream_t)stream);
+}
+
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {
   if (!src || !dst || rows < 0 || row_bytes < 0 || copies < 1) {
     set_error("replicate_rows: bad argument");

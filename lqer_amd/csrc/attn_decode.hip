@@ -1,0 +1,350 @@
+// Fused quantized attention for decode steps: 1 <= S <= 8 query rows against T keys, split over the KEYS (reference
+// models/llama_decoder.py:259-297, opt_decoder.py:125,190 - the arithmetic of attn_q.hip's header, unchanged):
+//     S  = Q_x0(Q) Q_w0(K^T) ->DT;  S1 = S scaling ->DT;  S2 = S1 + mask ->DT;  P = softmax_fp32(S2) ->DT;  O = Q_x1(P) Q_w1(V) ->DT
+// attn_q.hip gives a lane one query and a workgroup 128 of them: at S = 1 that is one live lane in 32, heads x batch workgroups, and
+// two bf16 images of the whole K and V written and read back.  Here a workgroup owns one CHUNK of keys for all R = (heads / kv_heads) S
+// query rows of its kv head; K and V are read once, in DT, straight from the caller's tensors (grouped-query K / V once per kv head).
+//
+// P is divided by the whole row's sum BEFORE it is rounded and quantized, so partial outputs over chunks cannot be rescaled afterwards
+// (no online softmax, no flash-decoding merge): the row's maximum and sum must be complete before any P exists.  Three launches:
+//   k_attn_dec_scores  grid (chunks, kv heads, batch).  The chunk's K rows -> registers with the lanes along d (a lane: 4 consecutive d
+//                      x 16 keys = four blocks of Q_w0, no cross-lane step for the block maximum) -> quant16_bf16 -> LDS [key][d] ->
+//                      S^T = Kq Qq^T on v_mfma_f32_32x32x16_bf16 (a wave: 32 keys x 32 query rows, the fragment layout of k_attn_q) ->
+//                      S2 to the workspace, {max, sum exp(S2 - max)} of the chunk per row next to it.
+//   k_attn_dec_pv      same grid.  Folds the row's chunk statistics IN CHUNK ORDER, P = exp(S2 - max) / sum ->DT, Q_x1 over 16 keys in a
+//                      lane pair (quant8of16_bf16), the chunk's V rows -> quant16_bf16 along d -> LDS [key][d], O^T += Vq^T Pq^T, the
+//                      R x D fp32 partial of the chunk to the workspace.  Chunk 0 writes row_stats.
+//   k_attn_dec_sum     adds the partials IN CHUNK ORDER, rounds ->DT, stores through the output strides.
+// The chunk length depends on T alone (dec_chunk), a row's arithmetic on that row alone: no floating-point atomics, no counters, the
+// same bits run to run, for a batch slice and for a slice of a kv group's heads.
+#include "attn_math.h"
+
+namespace lqer {
+
+namespace attn {
+
+constexpr int DEC_MAX_S = 8;     // query rows per head
+constexpr int DEC_CMAX = 128;    // keys per chunk at most
+constexpr int DEC_LS = 256 + 16; // bytes of an LDS row of 128 bf16 (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
+
+// keys per chunk: 16 ceil(T / 256) clamped to [16, 128] - T / 16 chunks up to T = 256, then 16, from T = 2048 on chunks of 128.
+// Llama-7B's step (32 heads, T = 2048): 16 x 32 = 512 workgroups of 4 waves, two per CU on 256 CUs.
+__host__ __device__ inline int dec_chunk(int64_t T, int64_t D) {
+  (void)D;
+  const int64_t n = (T + 255) / 256;
+  return 16 * (int)(n < 1 ? 1 : (n > 8 ? 8 : n));
+}
+
+struct DArgs {
+  const void *q, *k, *v, *mask;
+  void* out;
+  float* stats;
+  float *s2, *cst, *part;  // workspace: S2 [rows][Tp], chunk statistics [rows][nch][2], partial outputs [rows][nch][D]
+  int64_t S, T, D, R, Tp, rows;
+  int64_t q_bs, q_hs, q_rs, k_bs, k_hs, k_rs, v_bs, v_hs, v_rs, m_bs, m_hs, m_rs, o_bs, o_hs, o_rs;
+  int C, nch, heads, kv_heads, rep, mode;  // mode: 0 no mask, 1 additive mask tensor, 2 causal rule
+  float scaling;
+  QP q0, qk, q1, qv;
+  bool qvec, kvec, vvec;
+};
+
+// four consecutive elements; one 8- / 16-byte load when the row is aligned
+template <int DT>
+__device__ __forceinline__ void load4(const void* base, int64_t off, bool vec, float (&v)[4]) {
+  if (vec) {
+    if constexpr (DT == LQER_F32) {
+      const float4 t = *(const float4*)((const float*)base + off);
+      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+      const uint2 t = *(const uint2*)((const bf16_t*)base + off);
+      const uint32_t wd[2] = {t.x, t.y};
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if constexpr (DT == LQER_F16) {
+          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+          const h2 hv = __builtin_bit_cast(h2, wd[j]);
+          v[2 * j] = (float)hv[0], v[2 * j + 1] = (float)hv[1];
+        } else {
+          v[2 * j] = __uint_as_float(wd[j] << 16), v[2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = load_elem<DT>(base, off + j);
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
+  __shared__ float sSt[4][32][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+  const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
+  const int64_t t0 = c * a.C;
+  const int D = (int)a.D, C = a.C;
+  const float NEG_INF = -__builtin_inff();
+
+  // ---- the chunk's keys: a thread owns 4 consecutive d of 16 consecutive keys = four blocks of Q_w0 (blocks of 16 along t)
+  {
+    const int dq = D / 4, ncol = (C / 16) * dq;
+    for (int col = tid; col < ncol; col += 256) {
+      const int kb = col / dq, d0 = 4 * (col % dq);
+      float x[4][16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int64_t t = t0 + 16 * kb + i;
+        float v4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t < a.T) load4<DT>(a.k, b * a.k_bs + g * a.k_hs + t * a.k_rs + d0, a.kvec, v4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j][i] = v4[j];
+      }
+      uint32_t w[4][8];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) qmm::quant16_bf16<DT != LQER_F16>(x[j], a.qk, w[j]);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {  // key 16 kb + i: the four d as one 8-byte store
+        const int sh = 16 * (i & 1);
+        const uint32_t lo = ((w[0][i >> 1] >> sh) & 0xffffu) | ((w[1][i >> 1] >> sh) << 16);
+        const uint32_t hi = ((w[2][i >> 1] >> sh) & 0xffffu) | ((w[3][i >> 1] >> sh) << 16);
+        *(uint2*)(sK + (16 * kb + i) * DEC_LS + d0 * 2) = make_uint2(lo, hi);
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- S^T = Kq Qq^T: wave w takes keys 32 w .. 32 w + 31 of the chunk, a lane ONE query row and 16 of those keys,
+  // (r & 3) + 8 (r >> 2) + 4 lh (rows of sK at and beyond C hold whatever LDS held: their scores are never used)
+  const int nsub = (C + 31) / 32;
+  const int64_t off = a.T - a.S;
+  for (int64_t rg = 0; rg < a.R; rg += 32) {
+    const int64_t row = rg + l31;
+    const bool live = row < a.R;
+    const int64_t rowc = live ? row : a.R - 1;
+    const int64_t h = g * a.rep + rowc / a.S, si = rowc % a.S;
+    float m = NEG_INF, l = 0.f;
+    if (wave < nsub) {
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        if (ks * 16 < D) {
+          uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+          if (live) {
+            float v[16];
+            qmm::load16<DT>(a.q, b * a.q_bs + h * a.q_hs + si * a.q_rs + ks * 16, 16, a.qvec, v);
+            qmm::quant16_bf16<DT != LQER_F16>(v, a.q0, w);
+          }
+          const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
+          const bf16x8 kf = *(const bf16x8*)(sK + (32 * wave + l31) * DEC_LS + (2 * ks + lh) * 16);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8, f), acc, 0, 0, 0);
+        }
+      }
+      int64_t tvis = a.T - 1;  // the last key visible to this lane's query
+      if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
+      const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + si * a.m_rs : 0;
+      float s2[16];
+      bool vis[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kk = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int64_t t = t0 + kk;
+        float s = rnd<DT>(rnd<DT>(acc[r]) * a.scaling);
+        if (a.mode == 1) s = rnd<DT>(s + (t < a.T ? load_elem<DT>(a.mask, moff + t) : 0.f));
+        s2[r] = s;
+        vis[r] = kk < C && t <= tvis;
+      }
+      float tm = NEG_INF;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tm = vis[r] ? fmaxf(tm, s2[r]) : tm;
+      const float mref = tm == NEG_INF ? 0.f : tm;
+      float ls = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ls += vis[r] ? exp_neg(s2[r] - mref) : 0.f;
+      if (live) {
+        float* dst = a.s2 + (z * a.R + row) * a.Tp + t0 + 32 * wave + 4 * lh;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4)
+          if (32 * wave + 8 * q4 + 4 * lh < C) *(float4*)(dst + 8 * q4) = make_float4(s2[4 * q4], s2[4 * q4 + 1], s2[4 * q4 + 2], s2[4 * q4 + 3]);
+      }
+      // the lane pair (l, l ^ 32): lower lane's keys first in both lanes
+      const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(tm), __float_as_uint(tm), false, false);
+      const auto sl = __builtin_amdgcn_permlane32_swap(__float_as_uint(ls), __float_as_uint(ls), false, false);
+      const float m0 = __uint_as_float(sm[0]), m1 = __uint_as_float(sm[1]), l0 = __uint_as_float(sl[0]), l1 = __uint_as_float(sl[1]);
+      m = fmaxf(m0, m1);
+      const float mr = m == NEG_INF ? 0.f : m;
+      l = l0 * exp_neg(m0 - mr) + l1 * exp_neg(m1 - mr);
+      if (lh == 0) sSt[wave][l31][0] = m, sSt[wave][l31][1] = l;
+    }
+    __syncthreads();
+    if (wave == 0 && lh == 0 && live) {  // the chunk's subtiles in key order
+      float M = NEG_INF;
+      for (int u = 0; u < nsub; ++u) M = fmaxf(M, sSt[u][l31][0]);
+      const float mr = M == NEG_INF ? 0.f : M;
+      float L = 0.f;
+      for (int u = 0; u < nsub; ++u) L += sSt[u][l31][1] * exp_neg(sSt[u][l31][0] - mr);
+      float* cs = a.cst + ((z * a.R + row) * a.nch + c) * 2;
+      cs[0] = M, cs[1] = L;
+    }
+    __syncthreads();
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+  const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
+  const int64_t t0 = c * a.C;
+  const int D = (int)a.D, C = a.C;
+  const float NEG_INF = -__builtin_inff();
+
+  // ---- the chunk's V rows: a thread quantizes 16 consecutive d of one key (blocks of 16 along d); keys beyond T are zero rows
+  {
+    const int db_n = D / 16, items = C * db_n;
+    for (int it = tid; it < items; it += 256) {
+      const int key = it / db_n, db = it % db_n;
+      const int64_t t = t0 + key;
+      uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (t < a.T) {
+        float x[16];
+        qmm::load16<DT>(a.v, b * a.v_bs + g * a.v_hs + t * a.v_rs + 16 * db, 16, a.vvec, x);
+        qmm::quant16_bf16<DT != LQER_F16>(x, a.qv, w);
+      }
+      uint4* dst = (uint4*)(sV + key * DEC_LS + db * 32);
+      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+  }
+  __syncthreads();
+  if (wave * 32 >= D) return;  // wave w owns d = 32 w .. 32 w + 31 (no barrier follows)
+
+  const int64_t off = a.T - a.S;
+  for (int64_t rg = 0; rg < a.R; rg += 32) {
+    const int64_t row = rg + l31;
+    const bool live = row < a.R;
+    const int64_t rowc = live ? row : a.R - 1;
+    const int64_t si = rowc % a.S;
+    // ---- the row's maximum and sum from the chunk statistics, in chunk order
+    const float* cs = a.cst + (z * a.R + rowc) * a.nch * 2;
+    float M = NEG_INF;
+    for (int cc = 0; cc < a.nch; ++cc) M = fmaxf(M, cs[2 * cc]);
+    const float mr = M == NEG_INF ? 0.f : M;
+    float L = 0.f;
+    for (int cc = 0; cc < a.nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
+    if (a.stats && c == 0 && wave == 0 && lh == 0 && live) {
+      float* st = a.stats + (z * a.R + row) * 2;
+      st[0] = M, st[1] = L;
+    }
+    int64_t tvis = a.T - 1;
+    if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
+    if (!live) tvis = -1;
+
+    // ---- O^T += Vq^T Pq^T: a k-step is one block of 16 keys of Q_x1, this lane's half of it keys 8 lh .. 8 lh + 7
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float* srow = a.s2 + (z * a.R + rowc) * a.Tp;
+    for (int kst = 0; kst < C / 16; ++kst) {
+      const int64_t tb = t0 + 16 * kst + 8 * lh;
+      const float4 sa = *(const float4*)(srow + tb), sb = *(const float4*)(srow + tb + 4);
+      const float s8[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+      float p[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) p[i] = tb + i <= tvis ? rnd<DT>(exp_neg(s8[i] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
+      uint32_t w[4];
+      quant8of16_bf16<DT != LQER_F16>(p, a.q1, w);
+      const u32x4 pw = {w[0], w[1], w[2], w[3]};
+      const unsigned short* vp = (const unsigned short*)(sV + (16 * kst + 8 * lh) * DEC_LS) + 32 * wave + l31;
+      uint32_t e[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) e[i] = vp[i * (DEC_LS / 2)];
+      const u32x4 vw = {e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vw), __builtin_bit_cast(bf16x8, pw), acc, 0, 0, 0);
+    }
+    if (live) {  // d = 32 wave + 8 q4 + 4 lh + (0..3)
+      float* dst = a.part + ((z * a.R + row) * a.nch + c) * a.D + 32 * wave + 4 * lh;
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4)
+        if (32 * wave + 8 * q4 + 4 * lh < D) *(float4*)(dst + 8 * q4) = make_float4(acc[4 * q4], acc[4 * q4 + 1], acc[4 * q4 + 2], acc[4 * q4 + 3]);
+    }
+  }
+}
+
+// one thread = four consecutive d of one output row
+template <int DT>
+__global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int dq = (int)a.D / 4;
+  if (i >= a.rows * dq) return;
+  const int64_t grow = i / dq;
+  const int d = 4 * (int)(i % dq);
+  const float* p = a.part + grow * a.nch * a.D + d;
+  float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int cc = 0; cc < a.nch; ++cc) {
+    const float4 t = *(const float4*)(p + (int64_t)cc * a.D);
+    o[0] += t.x, o[1] += t.y, o[2] += t.z, o[3] += t.w;
+  }
+  const int64_t b = grow / (a.heads * a.S), h = (grow / a.S) % a.heads, si = grow % a.S;
+  store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
+}
+
+template <int DT>
+static int launch_decode(DArgs a, int64_t batch, hipStream_t st) {
+  const int esz = DT == LQER_F32 ? 4 : 2;
+  auto al16 = [&](const void* p, int64_t s0, int64_t s1, int64_t s2) {
+    return ((uintptr_t)p % 16 == 0) && (s0 * esz) % 16 == 0 && (s1 * esz) % 16 == 0 && (s2 * esz) % 16 == 0;
+  };
+  a.qvec = al16(a.q, a.q_bs, a.q_hs, a.q_rs);
+  a.kvec = al16(a.k, a.k_bs, a.k_hs, a.k_rs);
+  a.vvec = al16(a.v, a.v_bs, a.v_hs, a.v_rs);
+  const dim3 grid((unsigned)a.nch, (unsigned)a.kv_heads, (unsigned)batch);
+  k_attn_dec_scores<DT><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_sum<DT><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
+  return check_launch("lqer_attention_q_decode");
+}
+
+}  // namespace attn
+
+static size_t dec_align(size_t v) { return (v + 255) / 256 * 256; }
+
+int attention_q_decode_max_s() { return attn::DEC_MAX_S; }
+
+// rows = batch heads S, C = dec_chunk(T, D), nch = ceil(T / C):
+// [S2: rows x nch C fp32][chunk statistics: rows x nch x 2 fp32][partial outputs: rows x nch x D fp32], each rounded up to 256 bytes
+size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D) {
+  const int64_t C = attn::dec_chunk(T, D), nch = (T + C - 1) / C, rows = batch * heads * S;
+  return dec_align((size_t)(rows * nch * C) * 4) + dec_align((size_t)(rows * nch * 2) * 4) + dec_align((size_t)(rows * nch * D) * 4);
+}
+
+int attention_q_decode_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                                int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks,
+                                const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0,
+                                const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st) {
+  attn::DArgs a;
+  a.q = q, a.k = k, a.v = v, a.mask = mask, a.out = out, a.stats = row_stats;
+  a.S = S, a.T = T, a.D = D;
+  a.C = attn::dec_chunk(T, D), a.nch = (int)((T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
+  a.rep = (int)(heads / kv_heads), a.R = a.rep * S, a.rows = batch * heads * S;
+  unsigned char* ws = (unsigned char*)workspace;
+  a.s2 = (float*)ws;
+  ws += dec_align((size_t)(a.rows * a.Tp) * 4);
+  a.cst = (float*)ws;
+  ws += dec_align((size_t)(a.rows * a.nch * 2) * 4);
+  a.part = (float*)ws;
+  a.q_bs = qs[0], a.q_hs = qs[1], a.q_rs = qs[2];
+  a.k_bs = ks[0], a.k_hs = ks[1], a.k_rs = ks[2];
+  a.v_bs = vs[0], a.v_hs = vs[1], a.v_rs = vs[2];
+  a.m_bs = mask ? ms[0] : 0, a.m_hs = mask ? ms[1] : 0, a.m_rs = mask ? ms[2] : 0;
+  a.o_bs = os[0], a.o_hs = os[1], a.o_rs = os[2];
+  a.heads = (int)heads, a.kv_heads = (int)kv_heads, a.mode = causal ? 2 : (mask ? 1 : 0);
+  a.scaling = scaling;
+  a.q0 = q_x0, a.qk = q_w0, a.q1 = q_x1, a.qv = q_w1;
+  a.qvec = a.kvec = a.vvec = false;
+  return with_dtype(dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value>(a, batch, st); });
+}
+
+}  // namespace lqer

@@ -22,7 +22,7 @@
 //                                   and never touches LDS.  O^T leaves a lane with its query's d values, 4 consecutive per store.
 //                                   Key tiles of 64 go through LDS (rows padded against bank conflicts), the next tile's loads are
 //                                   requested before the current tile's MFMAs (register staging; one buffer, two barriers per tile).
-#include "qmm_image.h"
+#include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16: shared with attn_decode.hip
 
 namespace lqer {
 
@@ -60,48 +60,6 @@ __global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v,
   const int64_t z = blockIdx.z;  // y = V [t][d], d contiguous: blocks of 16 along d, transposed through LDS
   qmm::bimage_j_tile<DT, false>(v, (z / kv_heads) * v_bs + (z % kv_heads) * v_hs, T, D, v_rs, q, img + z * VD * Tv, VD, Tv, vec, (int64_t)blockIdx.y * 64,
                                 (int64_t)blockIdx.x * 64);
-}
-
-template <int DT>
-__device__ __forceinline__ float rnd(float x) {  // ->DT
-  if constexpr (DT == LQER_F16) return (float)(_Float16)x;
-  else if constexpr (DT == LQER_BF16) return __uint_as_float((uint32_t)f32_to_bf16_rne(x) << 16);
-  else return x;
-}
-
-// exp(x) for x <= 0 on v_exp_f32 with the rounding of x log2(e) compensated (the bare product is off by |x| 2^-24 in the exponent:
-// 30 ulps at x = -20): about 2 ulps.  Below -200 (-inf included) the result is 0; a NaN stays a NaN (the comparison is false for it).
-__device__ __forceinline__ float exp_neg(float x) {
-  x = x < -200.0f ? -200.0f : x;
-  const float t = x * 1.44269502162933349609375f;
-  const float r = __builtin_fmaf(x, 1.44269502162933349609375f, -t) + x * 1.925963033500011e-8f;
-  const float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * 0.693147182464599609375f, e);
-}
-
-// the 8 values a lane holds of a block of 16 (the other 8 sit in lane ^ 32) -> 8 exact bf16 values: quant16_bf16's arithmetic
-template <bool FLUSH_TINY>
-__device__ __forceinline__ void quant8of16_bf16(const float (&v)[8], const QP& q, uint32_t (&w)[4]) {
-  float am = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(v[i]));
-  const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(am), __float_as_uint(am), false, false);
-  const float amax = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = 0;
-  if (amax > 0.f) {
-    const int e = block_exponent(amax, q);
-    if (mxint16_fast_ok(e, q)) {
-      mxint16_bf16_fast<FLUSH_TINY, 8>(v, e, q, w);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
-        const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
-        w[i] = lo | (hi << 16);
-      }
-    }
-  }
 }
 
 template <int DT, int DK>  // DK: 32-wide tiles of the head dim (D <= 32 DK)

@@ -756,6 +756,13 @@ int attention_q_dispatch(const void* q, const void* k, const void* v, const void
                          int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks, const int64_t* vs,
                          const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
                          const QP& q_w1, void* workspace, hipStream_t st);
+// attn_decode.hip: the same attention for 1 <= S <= attention_q_decode_max_s() query rows, split over the keys
+int attention_q_decode_max_s();
+size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D);
+int attention_q_decode_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                                int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks,
+                                const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0,
+                                const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st);
 int qmatmul_dispatch(const void* x, const void* y, void* out, int dtype, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs,
                      int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, void* workspace, hipStream_t st);
 

@@ -127,10 +127,12 @@ def bmm_flexible(x, y, q_config):
     return generic_matmul_flexible(x, y, q_config, style="bmm")
 
 
-# ---- fused attention (csrc/attn_q.hip) --------------------------------------------------------------------------------------
+# ---- fused attention (csrc/attn_q.hip: prefill; csrc/attn_decode.hip: up to 8 query rows, split over the keys) ----------------
 ROUTE_FUSED, ROUTE_UNFUSED = "fused", "unfused"
+KERNEL_PREFILL, KERNEL_DECODE = "prefill", "decode"
 _ATTN_MAX_D = 128
 _ATTN_MAX_T = 65535 * 64  # the image kernels put t / 64 on grid.y
+_ATTN_DECODE_MAX_S = 8    # query rows per head the decode kernel takes (lqer_attention_q_decode refuses more)
 
 
 def _attn_fmts(cfg0: dict, cfg1: dict):
@@ -170,6 +172,54 @@ def _attention_route(q, k, v, cfg0, cfg1, attention_mask=None, causal=False):
     return (ROUTE_FUSED, fmts) if fmts is not None else (ROUTE_UNFUSED, None)
 
 
+def _decode_covers(q) -> bool:
+    """Operands of the fused route that the decode kernel takes as well (everything else it needs, the fused route needs too)."""
+    return q.shape[2] <= _ATTN_DECODE_MAX_S
+
+
+# The automatic rule follows the measurement of tools/attn_decode_bench.py (profiles/attn_decode.json: fp16, d = 128, whole calls of
+# attention_flexible timed, 15 shapes), in terms of the K / V streams = batch x kv_heads and of t:
+#   streams <= 64: the decode kernel won at every t measured from 512 to 32768 (32 streams; 64 streams at t = 2048, with and without
+#                  grouped-query heads), by 1.07x to 10x; below 32 streams nothing else was ever in reach of it;
+#   t <= 128 with 32 streams or more: the prefill kernel (43.5 against 43.9 us at 32 streams, 44.3 against 58.0 us at 256: one
+#                  workgroup per head covers so few keys, and nothing is split);
+#   streams > 64 and t > 128: the unfused route (128 streams, t = 2048: 113.2 against 115.1 us; 256 streams, t = 512 / 2048 / 8192:
+#                  91.7 / 165.7 / 656.8 against 124.5 / 214.8 / 970.9 us) - the decode kernel streams K and V at about 1.3 TB/s, the two
+#                  unfused products do better once there is enough of them.  Between 64 and 128 streams nothing is measured.
+_ATTN_DECODE_MAX_STREAMS = 64
+_ATTN_DECODE_SHORT_T, _ATTN_DECODE_SHORT_T_STREAMS = 128, 32
+
+
+def _decode_rule(b: int, hk: int, t: int):
+    """"decode", "prefill" or None (the unfused route) for s <= 8 query rows."""
+    streams = b * hk
+    if t <= _ATTN_DECODE_SHORT_T and streams >= _ATTN_DECODE_SHORT_T_STREAMS:
+        return KERNEL_PREFILL
+    if streams > _ATTN_DECODE_MAX_STREAMS:
+        return None
+    return KERNEL_DECODE
+
+
+def _attention_kernel(q, k, v, cfg0, cfg1, attention_mask=None, causal=False, kernel=None):
+    """(kernel name or None for the unfused route, formats).  kernel=None: up to 8 query rows take the decode kernel - or, where
+    tools/attn_decode_bench.py measured another leg faster, that leg (_decode_rule) -, more take the prefill kernel;
+    "prefill" / "decode" force one and raise where it does not apply."""
+    if kernel not in (None, KERNEL_PREFILL, KERNEL_DECODE):
+        raise ValueError(f"kernel {kernel!r}: None, 'prefill' or 'decode'")
+    route, fmts = _attention_route(q, k, v, cfg0, cfg1, attention_mask, causal)
+    if route != ROUTE_FUSED:
+        if kernel is not None:
+            raise ValueError(f"attention_flexible: kernel={kernel!r} forced, but these operands take the unfused route (attention_flexible.route)")
+        return None, None
+    if kernel == KERNEL_DECODE and not _decode_covers(q):
+        raise ValueError(f"attention_flexible: kernel='decode' takes up to {_ATTN_DECODE_MAX_S} query rows per head, got {q.shape[2]}")
+    if kernel is None:
+        kernel = _decode_rule(q.shape[0], k.shape[1], k.shape[2]) if _decode_covers(q) else KERNEL_PREFILL
+        if kernel is None:
+            return None, None
+    return kernel, fmts
+
+
 def _repeat_kv(t: torch.Tensor, n_rep: int) -> torch.Tensor:
     if n_rep == 1:
         return t
@@ -206,12 +256,15 @@ def _bcast_stride(m: torch.Tensor, dim: int) -> int:
 
 @torch.no_grad()
 def attention_flexible(q, k, v, cfg0, cfg1, scaling, attention_mask=None, causal=False, out_layout="bhsd", return_stats=False,
-                       return_route=False):
+                       return_route=False, kernel=None):
     """softmax(Q_x0(q) Q_w0(k^T) * scaling + mask) -> Q_x1 -> @ Q_w1(v) on q [b, h, s, d], k / v [b, h_kv, t, d] (grouped-query heads
     through the head mapping): lqer_eager_attention_forward's computation, every intermediate rounded to the operands' dtype where
     that route materialises it.  With the templates' quantizers (block_fp, width <= 8, blocks of 16), d a multiple of 16 up to 128
     and rows dense along d it is ONE fused HIP kernel behind two small image kernels (lqer_attention_q, csrc/attn_q.hip) and the
     scores stay on the chip; anything else runs the unfused sequence with that route's results - never an approximation.
+    With up to 8 query rows (a decode step against a KV cache) the fused route runs the kernel that is split over the keys instead
+    (lqer_attention_q_decode, csrc/attn_decode.hip: K and V read once, no images); `kernel` = "prefill" / "decode" forces one of the
+    two (ValueError where it does not cover the operands), None chooses; attention_flexible.kernel(...) tells which.
     `attention_mask`: additive, broadcastable [b|1, h|1, s|1, t] of q's dtype; `causal`: key j visible to query i iff j <= i + (t - s)
     (the tensor form of that rule: with s > t, where early rows see no key at all, the unfused sequence runs on that tensor).
     `out_layout`: "bhsd" or "bshd" (what the HuggingFace attention interface returns, written directly).  Returns out, then
@@ -221,8 +274,9 @@ def attention_flexible(q, k, v, cfg0, cfg1, scaling, attention_mask=None, causal
         raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
     if attention_mask is not None and causal:
         raise ValueError("attention_flexible: attention_mask and causal=True are two forms of one mask - pass one")
+    kern, fmts = _attention_kernel(q, k, v, cfg0, cfg1, attention_mask, causal, kernel)  # (validates `kernel`; CPU tensors: no kernel)
     ops._need_gpu(q, k, v, attention_mask)
-    route, fmts = _attention_route(q, k, v, cfg0, cfg1, attention_mask, causal)
+    route = ROUTE_FUSED if kern is not None else ROUTE_UNFUSED
     stats = None
     if route == ROUTE_FUSED:
         b, h, s, d = q.shape
@@ -234,18 +288,19 @@ def attention_flexible(q, k, v, cfg0, cfg1, scaling, attention_mask=None, causal
         tri = lambda *xs: (C.c_int64 * 3)(*xs)
         m = attention_mask
         L = _lib.lib()
+        name = "lqer_attention_q_decode" if kern == KERNEL_DECODE else "lqer_attention_q"
         with torch.cuda.device(q.device):
-            nws = L.lqer_attention_q_workspace_bytes(b, h, hk, s, t, d)
+            nws = getattr(L, name + "_workspace_bytes")(b, h, hk, s, t, d)
             ws = ops.workspace(q.device, max(nws, 16))
-            _lib.check(L.lqer_attention_q(q.data_ptr(), k.data_ptr(), v.data_ptr(), m.data_ptr() if m is not None else None, out.data_ptr(),
-                                          stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, hk, s, t, d,
-                                          tri(q.stride(0), q.stride(1), q.stride(2)), tri(k.stride(0), k.stride(1), k.stride(2)),
-                                          tri(v.stride(0), v.stride(1), v.stride(2)),
-                                          tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
-                                          tri(ob.stride(0), ob.stride(1), ob.stride(2)), float(scaling), int(bool(causal)),
-                                          C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
-                                          ops._stream(q.device)),
-                       "lqer_attention_q")
+            _lib.check(getattr(L, name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), m.data_ptr() if m is not None else None, out.data_ptr(),
+                                        stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, hk, s, t, d,
+                                        tri(q.stride(0), q.stride(1), q.stride(2)), tri(k.stride(0), k.stride(1), k.stride(2)),
+                                        tri(v.stride(0), v.stride(1), v.stride(2)),
+                                        tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
+                                        tri(ob.stride(0), ob.stride(1), ob.stride(2)), float(scaling), int(bool(causal)),
+                                        C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
+                                        ops._stream(q.device)),
+                       name)
     else:
         if causal:
             attention_mask = _causal_mask(q.shape[2], k.shape[2], q.dtype, q.device)
@@ -261,10 +316,17 @@ def attention_flexible(q, k, v, cfg0, cfg1, scaling, attention_mask=None, causal
 
 
 def _route_tag(q, k, v, cfg0, cfg1, attention_mask=None, causal=False) -> str:
-    return _attention_route(q, k, v, cfg0, cfg1, attention_mask, causal)[0]
+    """The tag attention_flexible returns with return_route for these operands (kernel=None)."""
+    return ROUTE_FUSED if _attention_kernel(q, k, v, cfg0, cfg1, attention_mask, causal)[0] is not None else ROUTE_UNFUSED
+
+
+def _kernel_tag(q, k, v, cfg0, cfg1, attention_mask=None, causal=False):
+    """"decode", "prefill", or None for the unfused route: what attention_flexible runs for these operands with kernel=None."""
+    return _attention_kernel(q, k, v, cfg0, cfg1, attention_mask, causal)[0]
 
 
 attention_flexible.route = _route_tag
+attention_flexible.kernel = _kernel_tag
 
 
 QUANTIZED_FUNCTION_MAP = {"matmul": {"flexible": matmul_flexible}, "bmm": {"flexible": bmm_flexible}}
