@@ -563,6 +563,54 @@ int lqer_attention_q_decode(const void* q, const void* k, const void* v, const v
                             float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
                             const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- packed KV cache: what lqer_attention_q_decode multiplies, kept between the steps ---------------------------------------------
+ * A decode step quantizes the whole K (k_fmt, blocks of 16 along t) and V (v_fmt, blocks of 16 along d) again, with the results of
+ * the step before: a block of 16 keys never changes once it is full, a V row never changes at all.  The cache holds the quantizer's
+ * OUTPUT - a one-byte code per element and a one-byte exponent per block - and lqer_attention_q_decode_kv reads that: the same codes,
+ * exponents, chunks and order of sums as lqer_attention_q_decode on the raw tensors, so the SAME BITS (K or V holding a NaN excepted:
+ * a code cannot carry one), from 2 D (1 + 1/16) bytes per cached token and kv head instead of 2 D sizeof(DT).
+ * One caller-allocated buffer per cache, 16-byte aligned, lqer_kv_cache_bytes(...) bytes (0 for a dtype, head dim or size the cache
+ * does not take); the library keeps no pointer.  With cap = capacity rounded up to 16, Z = batch kv_heads, sections in this order,
+ * each rounded up to 256 bytes:
+ *   K codes      [Z][cap][D]            uint8  sign-magnitude: bit 7 the sign, bits 6..0 |mantissa| (value = +-m 2^(e - (width - 1)));
+ *                                              sign-magnitude keeps the quantizer's -0, which a two's-complement code cannot
+ *   K exponents  [Z][cap / 16][D]       uint8  e + exp_bias of the block of keys 16 i .. 16 i + 15 at this d
+ *   V codes      [Z][cap][D]            uint8  as K codes
+ *   V exponents  [Z][cap / 16][D / 16][16] uint8  e + exp_bias of (key 16 i + r, block j of 16 d) at [i][j][r] - the bytes of
+ *                                              [cap][D / 16] regrouped so that the exponents of four consecutive keys are one dword
+ *   K staging    [Z][16][D]             DT     the raw keys of the open (last, partial) block of keys, rows 0 .. len % 16 - 1
+ * A block whose values are all zero stores codes 0 and the exponent nearest to 0.
+ * lqer_kv_cache_append: k_new / v_new [batch][kv_heads][n][D] of DT through k_strides[3] / v_strides[3] (elements, over batch, kv
+ * head, row; d contiguous; rows that are not 16-byte aligned take element loads: same bits) become keys len .. len + n - 1 of a cache
+ * that holds len.  V rows are quantized and stored at once.  Every block of 16 keys the new keys touch is quantized from the staging
+ * rows plus the new keys - the open block at the end included, zero-padded on the right as the quantizer pads a ragged block - and
+ * its codes (all 16 rows) and exponents are rewritten; the raw keys of the block left open go to the staging rows.  So the reader
+ * sees one format and has no tail path.  n >= 1 is arbitrary (a prefill goes in with one call); nothing depends on cache contents
+ * beyond row len or on staging rows beyond len % 16, so a fresh cache needs no initialisation (len = 0).  One launch on `stream`, two
+ * when the new keys leave a non-empty open block; k_new and v_new are only read.  Appends are issued once, in order: one that leaves a
+ * non-empty open block overwrites the staging rows it read, so repeating it at the same len does not give the same cache (a captured
+ * graph that is replayed restarts from a length whose open block it rebuilds itself, e.g. 0, or appends inside one open block).
+ * lqer_attention_q_decode_kv: lqer_attention_q_decode with (k, v, k_strides, v_strides) replaced by (cache, cache_bytes, capacity); T
+ * is the cache's length; k_fmt and v_fmt are those of the appends.  Arithmetic, masks, row_stats, workspace (size and layout), chunks,
+ * launches and refusals are lqer_attention_q_decode's; the cache is only read.  Rows at and beyond T are never read.
+ * lqer_kv_cache_unpack (test hook): the dequantized K and V [batch][kv_heads][T][D] as dense fp32 (either may be NULL).
+ * Refused with a message, nothing launched or touched:
+ *   LQER_E_UNSUPPORTED  k_fmt / v_fmt not LQER_Q_MXINT, width <= 8, block 16; D not a multiple of 16 or > 128;
+ *   LQER_E_INVALID      null pointers; negative sizes; n < 1; len + n (append) or T (attention, unpack) > capacity; an unknown dtype;
+ *                       a cache shorter than lqer_kv_cache_bytes or not 16-byte aligned. */
+size_t lqer_kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D);
+int lqer_kv_cache_append(void* cache, size_t cache_bytes, const void* k_new, const void* v_new, const int64_t* k_strides,
+                         const int64_t* v_strides, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t len,
+                         int64_t n, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
+int lqer_kv_cache_unpack(const void* cache, size_t cache_bytes, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D,
+                         int64_t T, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, float* k_f32, float* v_f32, void* stream);
+size_t lqer_attention_q_decode_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D);
+int lqer_attention_q_decode_kv(const void* q, const void* cache, size_t cache_bytes, int64_t capacity, const void* mask, void* out,
+                               float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D,
+                               const int64_t* q_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                               const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's
  * x.float() does) for the per-input-channel sum|x| and max|x|; any of the three outputs may be NULL, not all of them:

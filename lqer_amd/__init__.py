@@ -6,7 +6,8 @@ Public surface mirrors the reference's `lqer.quantize` package for this path:
 All compute is in liblqer_hip.so (hand-written HIP); see include/lqer_hip.h and DESIGN.md.
 """
 from .functional import attention_flexible, bmm_flexible, get_quantized_func, matmul_flexible  # noqa: F401
+from .kvcache import QuantizedKVCache, attention_flexible_cached  # noqa: F401
 from .linear import LinearFlexible, LinearFlexibleLqer, get_quantized_layer_cls  # noqa: F401
 
 __all__ = ["LinearFlexible", "LinearFlexibleLqer", "get_quantized_layer_cls", "matmul_flexible", "bmm_flexible",
-           "attention_flexible", "get_quantized_func"]
+           "attention_flexible", "get_quantized_func", "QuantizedKVCache", "attention_flexible_cached"]

@@ -123,6 +123,12 @@ SIGNATURES = {
     "lqer_attention_q_decode_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _sp, _sp, _sp, _sp, _sp, C.c_float,
                                      _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    "lqer_kv_cache_bytes": (_sz, [_i, _i64, _i64, _i64, _i64]),
+    "lqer_kv_cache_append": (_i, [_vp, _sz, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _qp, _qp, _vp]),
+    "lqer_kv_cache_unpack": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _i64, _qp, _qp, _vp, _vp, _vp]),
+    "lqer_attention_q_decode_kv_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "lqer_attention_q_decode_kv": (_i, [_vp, _vp, _sz, _i64, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _sp, _sp, _sp, C.c_float,
+                                        _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

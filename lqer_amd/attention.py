@@ -16,7 +16,8 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .functional import _repeat_kv, attention_flexible, unfused_attention  # noqa: F401  (_repeat_kv: the one spelling, in functional)
+from .functional import _ATTN_DECODE_MAX_S, _repeat_kv, attention_flexible, unfused_attention  # noqa: F401  (_repeat_kv: the one spelling, in functional)
+from .kvcache import QuantizedKVCache, attention_flexible_cached
 
 IMPLEMENTATION = "lqer_eager"
 IMPLEMENTATION_FUSED = "lqer_fused"  # the same computation as ONE kernel (csrc/attn_q.hip): enable_quantized_attention(..., fused=True)
@@ -33,13 +34,135 @@ def lqer_fused_attention_forward(module: nn.Module, query: torch.Tensor, key: to
                                  attention_mask: Optional[torch.Tensor], scaling: float, dropout: float = 0.0, **kwargs):
     """lqer_eager_attention_forward through attention_flexible: the mask tensor goes to the kernel as it is, grouped-query K / V
     are read through the head mapping, the output is written as [b, s, h, d] and no weights exist to return.  A caller that wants
-    the weights (output_attentions), trains with dropout or hands over a mask of another dtype gets the unfused function."""
-    if (kwargs.get("output_attentions") or (dropout > 0.0 and module.training)
-            or (attention_mask is not None and attention_mask.dtype != query.dtype)):  # (a wider mask: torch adds it with type promotion)
+    the weights (output_attentions), trains with dropout or hands over a mask of another dtype gets the unfused function.
+    key / value that carry a packed cache layer (quantized_kv_cache below: a decode step, key and value are the NEW tokens only) run
+    attention_flexible_cached over that layer's cache; there the unfused function has nothing to run on, and those callers get an error."""
+    unfused = (kwargs.get("output_attentions") or (dropout > 0.0 and module.training)
+               or (attention_mask is not None and attention_mask.dtype != query.dtype))  # (a wider mask: torch adds it with type promotion)
+    layer = getattr(key, _KV_LAYER_ATTR, None)
+    if layer is not None:
+        if unfused or query.shape[2] > _ATTN_DECODE_MAX_S:
+            raise NotImplementedError("lqer_fused attention over a packed KV cache: output_attentions, dropout in training, a mask of another "
+                                      f"dtype and more than {_ATTN_DECODE_MAX_S} new tokens need the raw K and V, which the cache does not keep")
+        return attention_flexible_cached(query, layer.cache, scaling, attention_mask=attention_mask, out_layout="bshd"), None
+    if unfused:
         return lqer_eager_attention_forward(module, query, key, value, attention_mask, scaling, dropout=dropout, **kwargs)
     cfg0, cfg1 = module._lqer_matmul_cfg
     out = attention_flexible(query, key, value, cfg0, cfg1, scaling, attention_mask=attention_mask, out_layout="bshd")
     return out, None
+
+
+_KV_LAYER_ATTR = "_lqer_kv_layer"  # on the key / value tensors a packed cache layer's update() returns for a decode step
+
+
+def _kv_layer_cls():
+    """The cache layer class, made on first use (transformers is imported only where a model is at hand)."""
+    global _KV_LAYER_CLS
+    if _KV_LAYER_CLS is not None:
+        return _KV_LAYER_CLS
+    from transformers.cache_utils import CacheLayerMixin
+
+    class QuantizedKVLayer(CacheLayerMixin):
+        """One attention layer's K and V as a QuantizedKVCache.  An update() on the empty layer (the prefill) packs k and v and returns
+        them as they are: the attention runs over the raw tensors, as without a cache.  An update() with up to 8 new tokens on a
+        non-empty layer appends them and returns the NEW k and v tagged with this layer; lqer_fused_attention_forward then attends over
+        the cache.  More new tokens on a non-empty layer raise: the raw K and V of the past are gone."""
+
+        is_sliding = False
+
+        def __init__(self, cfg0: dict, cfg1: dict, capacity: int = 256):
+            super().__init__()
+            self.cfg0, self.cfg1, self.capacity0 = cfg0, cfg1, capacity
+            self.cache: Optional[QuantizedKVCache] = None
+
+        def lazy_initialization(self, key_states: torch.Tensor, value_states: torch.Tensor) -> None:
+            b, hk, _, d = key_states.shape
+            self.dtype, self.device = key_states.dtype, key_states.device
+            self.cache = QuantizedKVCache(b, hk, d, self.cfg0, self.cfg1, self.dtype, self.device, capacity=self.capacity0)
+            self.is_initialized = True
+
+        def update(self, key_states: torch.Tensor, value_states: torch.Tensor, *args, **kwargs):
+            if not self.is_initialized:
+                self.lazy_initialization(key_states, value_states)
+            past, n = self.cache.length, key_states.shape[-2]
+            if past > 0 and n > _ATTN_DECODE_MAX_S:
+                raise NotImplementedError(f"packed KV cache: {n} new tokens on a cache of {past} - the kernel over the cache takes up to "
+                                          f"{_ATTN_DECODE_MAX_S} query rows, and the raw K and V of the past are not kept (no chunked prefill)")
+            self.cache.append(key_states, value_states)
+            if past > 0:
+                setattr(key_states, _KV_LAYER_ATTR, self)
+                setattr(value_states, _KV_LAYER_ATTR, self)
+            return key_states, value_states
+
+        def get_mask_sizes(self, query_length: int) -> tuple:
+            return self.get_seq_length() + query_length, 0
+
+        def get_seq_length(self) -> int:
+            return self.cache.length if self.cache is not None else 0
+
+        def get_max_length(self) -> int:
+            return -1
+
+        @property
+        def nbytes(self) -> int:
+            return self.cache.nbytes if self.cache is not None else 0
+
+        def reset(self) -> None:
+            if self.cache is not None:
+                self.cache.reset()
+
+        def _no(self, what):
+            raise NotImplementedError(f"packed KV cache: {what} is not implemented")
+
+        def offload(self):
+            self._no("offloading")
+
+        def prefetch(self):
+            pass
+
+        def reorder_cache(self, beam_idx) -> None:
+            self._no("beam search (reorder_cache)")
+
+        def crop(self, *args, **kwargs) -> None:
+            self._no("crop")
+
+        def batch_repeat_interleave(self, repeats: int) -> None:
+            self._no("batch_repeat_interleave")
+
+        def batch_select_indices(self, indices) -> None:
+            self._no("batch_select_indices")
+
+    _KV_LAYER_CLS = QuantizedKVLayer
+    return QuantizedKVLayer
+
+
+_KV_LAYER_CLS = None
+
+
+def quantized_kv_cache(model: nn.Module, capacity: int = 256):
+    """A transformers.Cache for `model` (after enable_quantized_attention(model, q_config, fused=True)) whose layers hold K and V as
+    the codes of that layer's two matmul configs (QuantizedKVCache): pass it as past_key_values to forward() or generate().  The
+    decode steps give the bits of a DynamicCache run that takes the decode kernel.  Llama-family and OPT attention hand update()'s
+    tensors to the attention interface untouched, which is what carries the layer to lqer_fused_attention_forward."""
+    from transformers.cache_utils import Cache
+
+    from .models import _decoder_layers
+
+    impl = getattr(getattr(model, "config", None), "_attn_implementation", None)
+    if impl != IMPLEMENTATION_FUSED:
+        raise ValueError(f"quantized_kv_cache: the model's attention implementation is {impl!r}, not {IMPLEMENTATION_FUSED!r} - only the fused "
+                         "kernel reads the packed cache (enable_quantized_attention(model, q_config, fused=True))")
+    layers, _ = _decoder_layers(model)
+    cls, out = _kv_layer_cls(), []
+    for i, layer in enumerate(layers):
+        attn = layer.self_attn
+        cfg0, cfg1 = attn._lqer_matmul_cfg
+        head_dim = int(getattr(attn, "head_dim"))
+        if not QuantizedKVCache.covers(cfg0, cfg1, head_dim, model.dtype):
+            raise NotImplementedError(f"quantized_kv_cache: layer {i} (head_dim {head_dim}, {model.dtype}) has matmul quantizers outside the packed "
+                                      "cache: block_fp, width <= 8, blocks of 16; head dims that are multiples of 16 up to 128")
+        out.append(cls(cfg0, cfg1, capacity))
+    return Cache(layers=out)
 
 
 def _register() -> None:

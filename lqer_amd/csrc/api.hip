@@ -1154,43 +1154,45 @@ size_t lqer_attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int
   return attention_q_decode_workspace_bytes(batch, heads, S, T, D);
 }
 
-int lqer_attention_q_decode(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                            int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
-                            const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
-                            const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+// the checks lqer_attention_q_decode and lqer_attention_q_decode_kv share (kv: K and V come from the packed cache - no k, v, strides):
+// LQER_OK = go on, 1 = nothing to do, else the refusal
+static int attn_decode_check(const char* who, bool kv, const void* q, const void* k, const void* v, const void* mask, void* out, int dtype,
+                             int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                             const int64_t* k_strides, const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, int causal,
+                             const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                             size_t workspace_bytes) {
   if (batch < 0 || heads <= 0 || kv_heads <= 0 || S < 0 || T < 0 || D <= 0) {
-    set_error("attention_q_decode: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", (long long)batch, (long long)heads,
+    set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)batch, (long long)heads,
               (long long)kv_heads, (long long)S, (long long)T, (long long)D);
     return LQER_E_INVALID;
   }
   if (heads % kv_heads != 0) {
-    set_error("attention_q_decode: heads %lld is not a multiple of kv_heads %lld", (long long)heads, (long long)kv_heads);
+    set_error("%s: heads %lld is not a multiple of kv_heads %lld", who, (long long)heads, (long long)kv_heads);
     return LQER_E_INVALID;
   }
   if (dtype != LQER_F32 && dtype != LQER_F16 && dtype != LQER_BF16) {
-    set_error("attention_q_decode: unknown dtype %d", dtype);
+    set_error("%s: unknown dtype %d", who, dtype);
     return LQER_E_INVALID;
   }
-  if (!q_strides || !k_strides || !v_strides || !out_strides || (mask && !mask_strides)) {
-    set_error("attention_q_decode: null stride array");
+  if (!q_strides || (!kv && (!k_strides || !v_strides)) || !out_strides || (mask && !mask_strides)) {
+    set_error("%s: null stride array", who);
     return LQER_E_INVALID;
   }
   if (mask && causal) {
-    set_error("attention_q_decode: a mask tensor and causal = 1 are two forms of one mask - pass one");
+    set_error("%s: a mask tensor and causal = 1 are two forms of one mask - pass one", who);
     return LQER_E_INVALID;
   }
   if (!q_fmt || !k_fmt || !p_fmt || !v_fmt) {
-    set_error("attention_q_decode: null quantizer format");
+    set_error("%s: null quantizer format", who);
     return LQER_E_INVALID;
   }
   if (S > attention_q_decode_max_s()) {
-    set_error("attention_q_decode: S = %lld query rows - the split over the keys takes up to %d (lqer_attention_q takes any)", (long long)S,
+    set_error("%s: S = %lld query rows - the split over the keys takes up to %d (lqer_attention_q takes any)", who, (long long)S,
               attention_q_decode_max_s());
     return LQER_E_UNSUPPORTED;
   }
   if (D % 16 != 0 || D > 128) {
-    set_error("attention_q_decode: head dim %lld - the fused kernels take multiples of 16 up to 128 (the two products of lqer_matmul_q take any)",
+    set_error("%s: head dim %lld - the fused kernels take multiples of 16 up to 128 (the two products of lqer_matmul_q take any)", who,
               (long long)D);
     return LQER_E_UNSUPPORTED;
   }
@@ -1199,40 +1201,168 @@ int lqer_attention_q_decode(const void* q, const void* k, const void* v, const v
     return LQER_E_UNSUPPORTED;
   for (const lqer_qfmt_t* f : {q_fmt, k_fmt, p_fmt, v_fmt})
     if (f->kind != LQER_Q_MXINT || f->block != 16) {
-      set_error("attention_q_decode: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
-                "formats run as the two products of lqer_matmul_q", f->kind, f->block);
+      set_error("%s: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
+                "formats run as the two products of lqer_matmul_q", who, f->kind, f->block);
       return LQER_E_UNSUPPORTED;
     }
   if (T > (int64_t)1 << 30) {  // (chunk indices and the fold over them are 32-bit)
-    set_error("attention_q_decode: T = %lld beyond 2^30 keys", (long long)T);
+    set_error("%s: T = %lld beyond 2^30 keys", who, (long long)T);
     return LQER_E_UNSUPPORTED;
   }
   if (batch > 65535 || kv_heads > 65535) {
-    set_error("attention_q_decode: batch %lld / kv_heads %lld beyond the launch grid (65535 each): call in chunks", (long long)batch,
-              (long long)kv_heads);
+    set_error("%s: batch %lld / kv_heads %lld beyond the launch grid (65535 each): call in chunks", who, (long long)batch, (long long)kv_heads);
     return LQER_E_UNSUPPORTED;
   }
-  if (batch == 0 || S == 0) return LQER_OK;
+  if (batch == 0 || S == 0) return 1;
   if (T == 0) {
-    set_error("attention_q_decode: T = 0 (a softmax over no keys)");
+    set_error("%s: T = 0 (a softmax over no keys)", who);
     return LQER_E_INVALID;
   }
-  if (!q || !k || !v || !out || !workspace) {
-    set_error("attention_q_decode: null pointer");
+  if (!q || (!kv && (!k || !v)) || !out || !workspace) {
+    set_error("%s: null pointer", who);
     return LQER_E_INVALID;
   }
   if ((uintptr_t)workspace % 16 != 0) {  // (the kernels store and load the workspace in 16-byte pieces)
-    set_error("attention_q_decode: workspace %p is not 16-byte aligned", workspace);
+    set_error("%s: workspace %p is not 16-byte aligned", who, workspace);
     return LQER_E_INVALID;
   }
   const size_t need = attention_q_decode_workspace_bytes(batch, heads, S, T, D);
   if (workspace_bytes < need) {
-    set_error("attention_q_decode: workspace %zu B < %zu B (lqer_attention_q_decode_workspace_bytes)", workspace_bytes, need);
+    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, workspace_bytes, need, who);
     return LQER_E_INVALID;
   }
+  return LQER_OK;
+}
+
+int lqer_attention_q_decode(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                            int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
+                            const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                            const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  const int rc = attn_decode_check("attention_q_decode", false, q, k, v, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides,
+                                   v_strides, mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
+  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
   return attention_q_decode_dispatch(q, k, v, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides,
                                      mask_strides, out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt),
                                      make_qp(*v_fmt), workspace, (hipStream_t)stream);
+}
+
+// ---- the packed KV cache (kv_pack.h, kv_cache.hip) ----
+static bool kv_dtype_ok(int dtype) { return dtype == LQER_F32 || dtype == LQER_F16 || dtype == LQER_BF16; }
+
+size_t lqer_kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D) {
+  if (!kv_dtype_ok(dtype) || batch <= 0 || kv_heads <= 0 || capacity <= 0 || D <= 0 || D % 16 != 0 || D > 128) return 0;
+  return kv_cache_bytes(dtype, batch, kv_heads, capacity, D);
+}
+
+// what append, attention and unpack ask of a cache: LQER_OK or the refusal
+static int kv_cache_check(const char* who, const void* cache, size_t cache_bytes, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity,
+                          int64_t D, int64_t T, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt) {
+  if (batch < 0 || kv_heads <= 0 || capacity <= 0 || D <= 0 || T < 0) {
+    set_error("%s: bad KV cache shape batch=%lld kv_heads=%lld capacity=%lld D=%lld length=%lld", who, (long long)batch, (long long)kv_heads,
+              (long long)capacity, (long long)D, (long long)T);
+    return LQER_E_INVALID;
+  }
+  if (!kv_dtype_ok(dtype)) {
+    set_error("%s: unknown dtype %d of the KV cache", who, dtype);
+    return LQER_E_INVALID;
+  }
+  if (!k_fmt || !v_fmt) {
+    set_error("%s: null quantizer format of the KV cache", who);
+    return LQER_E_INVALID;
+  }
+  if (D % 16 != 0 || D > 128) {
+    set_error("%s: head dim %lld - the packed KV cache takes multiples of 16 up to 128", who, (long long)D);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (!fmt_ok(k_fmt, "attention K quantizer", 8) || !fmt_ok(v_fmt, "attention V quantizer", 8)) return LQER_E_UNSUPPORTED;
+  for (const lqer_qfmt_t* f : {k_fmt, v_fmt})
+    if (f->kind != LQER_Q_MXINT || f->block != 16) {
+      set_error("%s: the packed KV cache holds block_fp codes of width <= 8 with blocks of 16 (got kind %d, block %d)", who, f->kind, f->block);
+      return LQER_E_UNSUPPORTED;
+    }
+  if (T > capacity) {
+    set_error("%s: %lld keys beyond the KV cache's capacity %lld", who, (long long)T, (long long)capacity);
+    return LQER_E_INVALID;
+  }
+  if (batch == 0) return LQER_OK;
+  if (!cache) {
+    set_error("%s: null KV cache", who);
+    return LQER_E_INVALID;
+  }
+  if ((uintptr_t)cache % 16 != 0) {  // (codes and exponents travel in 16-byte pieces)
+    set_error("%s: KV cache %p is not 16-byte aligned", who, cache);
+    return LQER_E_INVALID;
+  }
+  const size_t need = kv_cache_bytes(dtype, batch, kv_heads, capacity, D);
+  if (cache_bytes < need) {
+    set_error("%s: KV cache of %zu B < %zu B (lqer_kv_cache_bytes)", who, cache_bytes, need);
+    return LQER_E_INVALID;
+  }
+  return LQER_OK;
+}
+
+int lqer_kv_cache_append(void* cache, size_t cache_bytes, const void* k_new, const void* v_new, const int64_t* k_strides, const int64_t* v_strides,
+                         int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const lqer_qfmt_t* k_fmt,
+                         const lqer_qfmt_t* v_fmt, void* stream) {
+  if (len < 0 || n < 1) {
+    set_error("kv_cache_append: length %lld / %lld new keys of the KV cache (length >= 0, at least one new key)", (long long)len, (long long)n);
+    return LQER_E_INVALID;
+  }
+  if (capacity > 0 && n > capacity) {  // (before len + n can overflow)
+    set_error("kv_cache_append: %lld new keys beyond the KV cache's capacity %lld", (long long)n, (long long)capacity);
+    return LQER_E_INVALID;
+  }
+  const int rc = kv_cache_check("kv_cache_append", cache, cache_bytes, dtype, batch, kv_heads, capacity, D, len + n, k_fmt, v_fmt);
+  if (rc != LQER_OK) return rc;
+  if (batch == 0) return LQER_OK;
+  if (!k_new || !v_new || !k_strides || !v_strides) {
+    set_error("kv_cache_append: null pointer (new keys / values of the KV cache or their strides)");
+    return LQER_E_INVALID;
+  }
+  if (batch * kv_heads * ((n + 15) / 16 + 1 + n) > ((int64_t)1 << 31)) {  // (work items over grid.x, 256 a workgroup: D / 4 <= 32 per row)
+    set_error("kv_cache_append: %lld new keys for %lld KV cache streams beyond one launch grid: append in pieces", (long long)n,
+              (long long)(batch * kv_heads));
+    return LQER_E_UNSUPPORTED;
+  }
+  return kv_cache_append_dispatch(cache, k_new, v_new, k_strides, v_strides, dtype, batch, kv_heads, capacity, D, len, n, make_qp(*k_fmt),
+                                  make_qp(*v_fmt), (hipStream_t)stream);
+}
+
+int lqer_kv_cache_unpack(const void* cache, size_t cache_bytes, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T,
+                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, float* k_f32, float* v_f32, void* stream) {
+  const int rc = kv_cache_check("kv_cache_unpack", cache, cache_bytes, dtype, batch, kv_heads, capacity, D, T, k_fmt, v_fmt);
+  if (rc != LQER_OK) return rc;
+  if (batch == 0 || T == 0) return LQER_OK;
+  if (!k_f32 && !v_f32) {
+    set_error("kv_cache_unpack: null outputs for the KV cache's K and V");
+    return LQER_E_INVALID;
+  }
+  if (batch * kv_heads * T * D > ((int64_t)1 << 39)) {
+    set_error("kv_cache_unpack: %lld elements of the KV cache beyond one launch grid", (long long)(batch * kv_heads * T * D));
+    return LQER_E_UNSUPPORTED;
+  }
+  return kv_cache_unpack_dispatch(cache, dtype, batch, kv_heads, capacity, D, T, make_qp(*k_fmt), make_qp(*v_fmt), k_f32, v_f32,
+                                  (hipStream_t)stream);
+}
+
+size_t lqer_attention_q_decode_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D) {
+  return lqer_attention_q_decode_workspace_bytes(batch, heads, kv_heads, S, T, D);
+}
+
+int lqer_attention_q_decode_kv(const void* q, const void* cache, size_t cache_bytes, int64_t capacity, const void* mask, void* out, float* row_stats,
+                               int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                               const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                               const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  int rc = attn_decode_check("attention_q_decode_kv", true, q, nullptr, nullptr, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides,
+                             nullptr, nullptr, mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
+  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
+  rc = kv_cache_check("attention_q_decode_kv", cache, cache_bytes, dtype, batch, kv_heads, capacity, D, T, k_fmt, v_fmt);
+  if (rc != LQER_OK) return rc;
+  return attention_q_decode_kv_dispatch(q, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides,
+                                        out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
+                                        (hipStream_t)stream);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

@@ -17,7 +17,12 @@
 //   k_attn_dec_sum     adds the partials IN CHUNK ORDER, rounds ->DT, stores through the output strides.
 // The chunk length depends on T alone (dec_chunk), a row's arithmetic on that row alone: no floating-point atomics, no counters, the
 // same bits run to run, for a batch slice and for a slice of a kv group's heads.
+//
+// Both kernels take their K / V from one of two sources (template parameter PK): the caller's tensors in DT, quantized here, or the
+// packed KV cache (kv_pack.h: the codes and block exponents of Q_w0(K^T) and Q_w1(V), written by kv_cache.hip) - 16-byte loads of
+// codes, a convert and a scale.  Either source writes the SAME bf16 image to LDS; everything after the first barrier is one body.
 #include "attn_math.h"
+#include "kv_pack.h"
 
 namespace lqer {
 
@@ -46,36 +51,11 @@ struct DArgs {
   float scaling;
   QP q0, qk, q1, qv;
   bool qvec, kvec, vvec;
+  const unsigned char *kc, *ke, *vc, *ve;  // the packed source: codes and exponents of K and of V (kv_pack.h), cap keys per (batch, kv head)
+  int64_t cap;
 };
 
-// four consecutive elements; one 8- / 16-byte load when the row is aligned
-template <int DT>
-__device__ __forceinline__ void load4(const void* base, int64_t off, bool vec, float (&v)[4]) {
-  if (vec) {
-    if constexpr (DT == LQER_F32) {
-      const float4 t = *(const float4*)((const float*)base + off);
-      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-      const uint2 t = *(const uint2*)((const bf16_t*)base + off);
-      const uint32_t wd[2] = {t.x, t.y};
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        if constexpr (DT == LQER_F16) {
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-          const h2 hv = __builtin_bit_cast(h2, wd[j]);
-          v[2 * j] = (float)hv[0], v[2 * j + 1] = (float)hv[1];
-        } else {
-          v[2 * j] = __uint_as_float(wd[j] << 16), v[2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = load_elem<DT>(base, off + j);
-  }
-}
-
-template <int DT>
+template <int DT, bool PK>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
@@ -85,8 +65,34 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   const int D = (int)a.D, C = a.C;
   const float NEG_INF = -__builtin_inff();
 
-  // ---- the chunk's keys: a thread owns 4 consecutive d of 16 consecutive keys = four blocks of Q_w0 (blocks of 16 along t)
-  {
+  if constexpr (PK) {
+    // ---- the chunk's keys from the packed cache: a thread owns 16 consecutive d of 4 consecutive keys - four 16-byte loads of codes and
+    // the 16 exponents of their block (one per d); keys at and beyond T are zero rows and are not read
+    const int dg_n = D / 16, items = (C / 4) * dg_n;
+    for (int it = tid; it < items; it += 256) {
+      const int kq = it / dg_n, dg = it % dg_n;
+      const int64_t tq = t0 + 4 * kq;
+      uint4 e4 = make_uint4(0, 0, 0, 0), c[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
+      if (tq < a.T) {
+        e4 = *(const uint4*)(a.ke + (z * (a.cap / 16) + tq / 16) * D + 16 * dg);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (tq + j < a.T) c[j] = *(const uint4*)(a.kc + (z * a.cap + tq + j) * D + 16 * dg);
+      }
+      const uint32_t eb[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (tq + j < a.T) kvc::codes16_to_bf16(c[j], eb, a.qk, w);
+        uint4* dst = (uint4*)(sK + (4 * kq + j) * DEC_LS + dg * 32);
+        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+      }
+    }
+  } else {
+    // ---- the chunk's keys: a thread owns 4 consecutive d of 16 consecutive keys = four blocks of Q_w0 (blocks of 16 along t)
     const int dq = D / 4, ncol = (C / 16) * dq;
     for (int col = tid; col < ncol; col += 256) {
       const int kb = col / dq, d0 = 4 * (col % dq);
@@ -191,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   }
 }
 
-template <int DT>
+template <int DT, bool PK>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
@@ -200,8 +206,36 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   const int D = (int)a.D, C = a.C;
   const float NEG_INF = -__builtin_inff();
 
-  // ---- the chunk's V rows: a thread quantizes 16 consecutive d of one key (blocks of 16 along d); keys beyond T are zero rows
-  {
+  if constexpr (PK) {
+    // ---- the chunk's V rows from the packed cache: a thread owns 16 consecutive d (one block of Q_w1) of 4 consecutive keys - four
+    // 16-byte loads of codes, one dword of their four exponents; keys at and beyond T are zero rows and are not read
+    const int db_n = D / 16, items = (C / 4) * db_n;
+    for (int it = tid; it < items; it += 256) {
+      const int kq = it / db_n, db = it % db_n;
+      const int64_t tq = t0 + 4 * kq;
+      uint32_t e4 = 0;
+      uint4 c[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
+      if (tq < a.T) {
+        e4 = *(const uint32_t*)(a.ve + ((z * (a.cap / 16) + tq / 16) * db_n + db) * 16 + tq % 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (tq + j < a.T) c[j] = *(const uint4*)(a.vc + (z * a.cap + tq + j) * D + 16 * db);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const uint32_t e1 = ((e4 >> (8 * j)) & 0xffu) * 0x01010101u;
+        const uint32_t eb[4] = {e1, e1, e1, e1};
+        if (tq + j < a.T) kvc::codes16_to_bf16(c[j], eb, a.qv, w);
+        uint4* dst = (uint4*)(sV + (4 * kq + j) * DEC_LS + db * 32);
+        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+      }
+    }
+  } else {
+    // ---- the chunk's V rows: a thread quantizes 16 consecutive d of one key (blocks of 16 along d); keys beyond T are zero rows
     const int db_n = D / 16, items = C * db_n;
     for (int it = tid; it < items; it += 256) {
       const int key = it / db_n, db = it % db_n;
@@ -291,20 +325,22 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
-template <int DT>
+template <int DT, bool PK>
 static int launch_decode(DArgs a, int64_t batch, hipStream_t st) {
   const int esz = DT == LQER_F32 ? 4 : 2;
   auto al16 = [&](const void* p, int64_t s0, int64_t s1, int64_t s2) {
     return ((uintptr_t)p % 16 == 0) && (s0 * esz) % 16 == 0 && (s1 * esz) % 16 == 0 && (s2 * esz) % 16 == 0;
   };
   a.qvec = al16(a.q, a.q_bs, a.q_hs, a.q_rs);
-  a.kvec = al16(a.k, a.k_bs, a.k_hs, a.k_rs);
-  a.vvec = al16(a.v, a.v_bs, a.v_hs, a.v_rs);
+  if constexpr (!PK) {
+    a.kvec = al16(a.k, a.k_bs, a.k_hs, a.k_rs);
+    a.vvec = al16(a.v, a.v_bs, a.v_hs, a.v_rs);
+  }
   const dim3 grid((unsigned)a.nch, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_scores<DT, PK><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT, PK><<<grid, 256, 0, st>>>(a);
   k_attn_dec_sum<DT><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
-  return check_launch("lqer_attention_q_decode");
+  return check_launch(PK ? "lqer_attention_q_decode_kv" : "lqer_attention_q_decode");
 }
 
 }  // namespace attn
@@ -320,10 +356,11 @@ size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t 
   return dec_align((size_t)(rows * nch * C) * 4) + dec_align((size_t)(rows * nch * 2) * 4) + dec_align((size_t)(rows * nch * D) * 4);
 }
 
-int attention_q_decode_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                                int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks,
-                                const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0,
-                                const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st) {
+// `cache` == nullptr: K and V are the caller's tensors; else the packed cache of `capacity` keys (kv_pack.h) and k, v, ks, vs unused
+static int decode_dispatch(const void* q, const void* k, const void* v, const void* cache, int64_t capacity, const void* mask, void* out,
+                           float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D,
+                           const int64_t* qs, const int64_t* ks, const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal,
+                           const QP& q_x0, const QP& q_w0, const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st) {
   attn::DArgs a;
   a.q = q, a.k = k, a.v = v, a.mask = mask, a.out = out, a.stats = row_stats;
   a.S = S, a.T = T, a.D = D;
@@ -336,15 +373,38 @@ int attention_q_decode_dispatch(const void* q, const void* k, const void* v, con
   ws += dec_align((size_t)(a.rows * a.nch * 2) * 4);
   a.part = (float*)ws;
   a.q_bs = qs[0], a.q_hs = qs[1], a.q_rs = qs[2];
-  a.k_bs = ks[0], a.k_hs = ks[1], a.k_rs = ks[2];
-  a.v_bs = vs[0], a.v_hs = vs[1], a.v_rs = vs[2];
+  a.k_bs = ks ? ks[0] : 0, a.k_hs = ks ? ks[1] : 0, a.k_rs = ks ? ks[2] : 0;
+  a.v_bs = vs ? vs[0] : 0, a.v_hs = vs ? vs[1] : 0, a.v_rs = vs ? vs[2] : 0;
   a.m_bs = mask ? ms[0] : 0, a.m_hs = mask ? ms[1] : 0, a.m_rs = mask ? ms[2] : 0;
   a.o_bs = os[0], a.o_hs = os[1], a.o_rs = os[2];
   a.heads = (int)heads, a.kv_heads = (int)kv_heads, a.mode = causal ? 2 : (mask ? 1 : 0);
   a.scaling = scaling;
   a.q0 = q_x0, a.qk = q_w0, a.q1 = q_x1, a.qv = q_w1;
   a.qvec = a.kvec = a.vvec = false;
-  return with_dtype(dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value>(a, batch, st); });
+  a.kc = a.ke = a.vc = a.ve = nullptr, a.cap = 0;
+  if (cache) {
+    const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
+    const unsigned char* base = (const unsigned char*)cache;
+    a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.cap = l.cap;
+    return with_dtype(dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, true>(a, batch, st); });
+  }
+  return with_dtype(dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, false>(a, batch, st); });
+}
+
+int attention_q_decode_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                                int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks,
+                                const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0,
+                                const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st) {
+  return decode_dispatch(q, k, v, nullptr, 0, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, qs, ks, vs, ms, os, scaling, causal, q_x0,
+                         q_w0, q_x1, q_w1, workspace, st);
+}
+
+int attention_q_decode_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
+                                   int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs,
+                                   const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
+                                   const QP& q_w1, void* workspace, hipStream_t st) {
+  return decode_dispatch(q, nullptr, nullptr, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, qs, nullptr, nullptr, ms,
+                         os, scaling, causal, q_x0, q_w0, q_x1, q_w1, workspace, st);
 }
 
 }  // namespace lqer

@@ -1,0 +1,160 @@
+// The packed KV cache's writer and its test hook (layout and codes: kv_pack.h, include/lqer_hip.h "packed KV cache").
+//   k_kv_append  new V rows: quantized along d and stored at once (a thread: 16 d of one key - 16 bytes of codes, one exponent byte).
+//                new K rows: every block of 16 keys they touch is quantized along t from the staging rows (the raw keys of the open
+//                block that were there before) plus the new keys, zero-padded on the right, and stored whole - codes of all 16 rows,
+//                the exponents of the block (a thread: 4 d of the 16 keys, as k_attn_dec_scores reads raw keys).  The raw keys of the
+//                block left open go to the staging rows.
+// One launch when the staging rows read and the staging rows written cannot meet (the new keys stay inside the open block, or the
+// cache ended on a block boundary); otherwise the staging rows are written by a second launch of the same kernel.
+//   k_kv_unpack  code x 2^(e - mbits) as fp32, one element per thread.
+#include "kv_pack.h"
+
+namespace lqer {
+
+namespace kvc {
+
+struct AArgs {
+  unsigned char *kc, *ke, *vc, *ve;
+  void* stage;
+  const void *kn, *vn;
+  int64_t Z, kvh, cap, D, len, n;
+  int64_t k_bs, k_hs, k_rs, v_bs, v_hs, v_rs;
+  int64_t kb0, nkb;  // the blocks of 16 keys the new keys touch
+  int64_t s0, ns;    // keys s0 .. s0 + ns - 1 (of the block left open) go to staging rows t % 16
+  int phase;         // 1: quantize K blocks and V rows, 2: write the staging rows, 3: both
+  QP qk, qv;
+  bool kvec, vvec;
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int D = (int)a.D, dq = D / 4, db_n = D / 16;
+  if (a.phase & 1) {
+    const int64_t nK = a.Z * a.nkb * dq, nV = a.Z * a.n * db_n;
+    if (i < nK) {  // ---- 4 d of one block of 16 keys
+      const int64_t z = i / (a.nkb * dq), rem = i % (a.nkb * dq);
+      const int64_t kb = a.kb0 + rem / dq, b = z / a.kvh, g = z % a.kvh;
+      const int d0 = 4 * (int)(rem % dq);
+      float x[4][16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t t = 16 * kb + r;
+        float v4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t < a.len) attn::load4<DT>(a.stage, (z * 16 + r) * a.D + d0, true, v4);
+        else if (t < a.len + a.n) attn::load4<DT>(a.kn, b * a.k_bs + g * a.k_hs + (t - a.len) * a.k_rs + d0, a.kvec, v4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j][r] = v4[j];
+      }
+      uint32_t cw[4][4], eb = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) eb |= quant16_codes<DT != LQER_F16>(x[j], a.qk, cw[j]) << (8 * j);
+      unsigned char* kc = a.kc + (z * a.cap + 16 * kb) * a.D + d0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {  // key 16 kb + r: the four d as one dword
+        const int sh = 8 * (r & 3);
+        *(uint32_t*)(kc + r * a.D) = ((cw[0][r >> 2] >> sh) & 0xffu) | (((cw[1][r >> 2] >> sh) & 0xffu) << 8) |
+                                     (((cw[2][r >> 2] >> sh) & 0xffu) << 16) | (((cw[3][r >> 2] >> sh) & 0xffu) << 24);
+      }
+      *(uint32_t*)(a.ke + (z * (a.cap / 16) + kb) * a.D + d0) = eb;
+      return;
+    }
+    i -= nK;
+    if (i < nV) {  // ---- 16 d of one new key
+      const int64_t z = i / (a.n * db_n), rem = i % (a.n * db_n);
+      const int64_t j = rem / db_n, b = z / a.kvh, g = z % a.kvh, t = a.len + j;
+      const int db = (int)(rem % db_n);
+      float x[16];
+      qmm::load16<DT>(a.vn, b * a.v_bs + g * a.v_hs + j * a.v_rs + 16 * db, 16, a.vvec, x);
+      uint32_t cw[4];
+      const uint32_t eb = quant16_codes<DT != LQER_F16>(x, a.qv, cw);
+      *(uint4*)(a.vc + (z * a.cap + t) * a.D + 16 * db) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+      a.ve[((z * (a.cap / 16) + t / 16) * db_n + db) * 16 + t % 16] = (unsigned char)eb;
+      return;
+    }
+    i -= nV;
+  }
+  if ((a.phase & 2) && i < a.Z * a.ns * dq) {  // ---- 4 d of one raw key of the open block, bits as they are
+    const int64_t z = i / (a.ns * dq), rem = i % (a.ns * dq);
+    const int64_t t = a.s0 + rem / dq, b = z / a.kvh, g = z % a.kvh;
+    const int d0 = 4 * (int)(rem % dq);
+    const int64_t src = b * a.k_bs + g * a.k_hs + (t - a.len) * a.k_rs + d0, dst = (z * 16 + t % 16) * a.D + d0;
+    if constexpr (DT == LQER_F32) {
+      const uint32_t* s = (const uint32_t*)a.kn + src;
+      *(uint4*)((uint32_t*)a.stage + dst) = a.kvec ? *(const uint4*)s : make_uint4(s[0], s[1], s[2], s[3]);
+    } else {
+      const unsigned short* s = (const unsigned short*)a.kn + src;
+      *(uint2*)((unsigned short*)a.stage + dst) =
+          a.kvec ? *(const uint2*)s : make_uint2((uint32_t)s[0] | ((uint32_t)s[1] << 16), (uint32_t)s[2] | ((uint32_t)s[3] << 16));
+    }
+  }
+}
+
+struct UArgs {
+  const unsigned char *kc, *ke, *vc, *ve;
+  float *kf, *vf;
+  int64_t Z, cap, T, D;
+  QP qk, qv;
+};
+
+__global__ __launch_bounds__(256) void k_kv_unpack(const UArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.Z * a.T * a.D) return;
+  const int64_t z = i / (a.T * a.D), t = (i / a.D) % a.T, d = i % a.D;
+  const int64_t at = (z * a.cap + t) * a.D + d, blk = z * (a.cap / 16) + t / 16;
+  if (a.kf) a.kf[i] = code_value(a.kc[at], a.ke[blk * a.D + d], a.qk);
+  if (a.vf) a.vf[i] = code_value(a.vc[at], a.ve[(blk * (a.D / 16) + d / 16) * 16 + t % 16], a.qv);
+}
+
+}  // namespace kvc
+
+size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D) {
+  return kvc::layout(dtype, batch, kv_heads, capacity, D).total;
+}
+
+int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int dtype, int64_t batch,
+                             int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const QP& qk, const QP& qv, hipStream_t st) {
+  const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
+  unsigned char* base = (unsigned char*)cache;
+  kvc::AArgs a;
+  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.stage = base + l.k_stage;
+  a.kn = k_new, a.vn = v_new;
+  a.Z = batch * kv_heads, a.kvh = kv_heads, a.cap = l.cap, a.D = D, a.len = len, a.n = n;
+  a.k_bs = ks[0], a.k_hs = ks[1], a.k_rs = ks[2], a.v_bs = vs[0], a.v_hs = vs[1], a.v_rs = vs[2];
+  a.kb0 = len / 16, a.nkb = (len + n - 1) / 16 - a.kb0 + 1;
+  const int64_t open0 = (len + n) / 16 * 16;  // first key of the block left open
+  a.s0 = open0 > len ? open0 : len, a.ns = len + n - a.s0;
+  a.qk = qk, a.qv = qv;
+  const int esz = dtype == LQER_F32 ? 4 : 2;
+  auto al16 = [&](const void* p, const int64_t* s) {
+    return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
+  };
+  a.kvec = al16(k_new, ks), a.vvec = al16(v_new, vs);
+  // staging rows read: 0 .. len % 16 - 1; written: (t % 16) of keys s0 .. len + n - 1 - apart when the new keys stay in the open block
+  const bool one = len % 16 == 0 || a.s0 == len || a.ns == 0;
+  const int64_t n1 = a.Z * (a.nkb * (D / 4) + n * (D / 16)), n2 = a.Z * a.ns * (D / 4);
+  return with_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    a.phase = one ? 3 : 1;
+    const int64_t items = n1 + (one ? n2 : 0);
+    kvc::k_kv_append<DT><<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
+    if (!one) {
+      a.phase = 2;
+      kvc::k_kv_append<DT><<<dim3((unsigned)((n2 + 255) / 256)), 256, 0, st>>>(a);
+    }
+    return check_launch("lqer_kv_cache_append");
+  });
+}
+
+int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
+                             const QP& qv, float* k_f32, float* v_f32, hipStream_t st) {
+  const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
+  const unsigned char* base = (const unsigned char*)cache;
+  kvc::UArgs a;
+  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps;
+  a.kf = k_f32, a.vf = v_f32, a.Z = batch * kv_heads, a.cap = l.cap, a.T = T, a.D = D, a.qk = qk, a.qv = qv;
+  kvc::k_kv_unpack<<<dim3((unsigned)((a.Z * T * D + 255) / 256)), 256, 0, st>>>(a);
+  return check_launch("lqer_kv_cache_unpack");
+}
+
+}  // namespace lqer

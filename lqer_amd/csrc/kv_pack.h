@@ -1,0 +1,159 @@
+// The packed KV cache (include/lqer_hip.h "packed KV cache"): what Q_w0(K^T) and Q_w1(V) of the fused attention ARE - a code per
+// element and an exponent per block of 16 - so that a decode step converts and scales instead of quantizing the whole K and V again.
+// Shared by kv_cache.hip (append, unpack) and attn_decode.hip (the packed operand source): the layout, the quantizer that keeps the
+// codes, and the way back to the bf16 bits quant16_bf16 would have written - one spelling of each, so the two sides cannot drift.
+//
+// A code is SIGN-MAGNITUDE: bit 7 the sign, bits 6..0 the mantissa's magnitude (width <= 8: at most 127).  The quantizer's image
+// knows a -0 (a negative value that rounds to zero keeps its sign in the slow path; an fp16 -0 in the fast one): sign-magnitude
+// carries it, and the way back is a v_cvt_f32_ubyte, a multiply and an OR of the sign - no sign extension, no special code.
+// An exponent byte is e - emin = e + exp_bias (0 .. 2^exp_width - 1); a zero block stores the exponent closest to 0.
+#pragma once
+#include "qmm_image.h"
+
+namespace lqer {
+
+namespace kvc {
+
+struct Layout {  // byte offsets of the five sections, each rounded up to 256 bytes
+  int64_t cap;   // capacity rounded up to 16 keys
+  size_t k_codes, k_exps, v_codes, v_exps, k_stage, total;
+};
+
+__host__ inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// D a multiple of 16, dtype one of the three: the caller checked
+__host__ inline Layout layout(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D) {
+  Layout l;
+  l.cap = (capacity + 15) / 16 * 16;
+  const size_t Z = (size_t)(batch * kv_heads), esz = dtype == LQER_F32 ? 4 : 2;
+  const size_t codes = up256(Z * l.cap * D), exps = up256(Z * (l.cap / 16) * D);
+  l.k_codes = 0;
+  l.k_exps = l.k_codes + codes;
+  l.v_codes = l.k_exps + exps;
+  l.v_exps = l.v_codes + codes;
+  l.k_stage = l.v_exps + exps;
+  l.total = l.k_stage + up256(Z * 16 * D * esz);
+  return l;
+}
+
+// one block of 16 -> 16 codes (four dwords, element i in byte i) and the exponent byte: quant16_bf16's decisions and arithmetic,
+// stopped before the final scaling (the fast path: mxint16_bf16_fast's r; the other: mxint_mantissa)
+template <bool FLUSH_TINY>
+__device__ __forceinline__ uint32_t quant16_codes(const float (&v)[16], const QP& q, uint32_t (&cw)[4]) {
+  typedef __attribute__((ext_vector_type(2))) float f2;
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cw[i] = 0;
+  int e = 0 < q.emin ? q.emin : (0 > q.emax ? q.emax : 0);
+  if (amax > 0.f) {
+    e = block_exponent(amax, q);
+    float r[16];
+    if (mxint16_fast_ok(e, q)) {
+      const float s = __uint_as_float((uint32_t)(127 + q.mbits - e) << 23);
+      const float es = 1e-9f * s, lo = -q.mneg, hi = q.mmax;
+      const f2 magic = {12582912.0f, 12582912.0f};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const f2 x = {v[2 * i], v[2 * i + 1]};
+        const f2 c = {copysignf(es, x[0]), copysignf(es, x[1])};
+        f2 t = (__builtin_elementwise_fma(x, (f2){s, s}, c) + magic) - magic;
+        t[0] = __builtin_amdgcn_fmed3f(t[0], lo, hi);
+        t[1] = __builtin_amdgcn_fmed3f(t[1], lo, hi);
+        if constexpr (FLUSH_TINY) {
+          t[0] = fabsf(x[0]) <= 1e-8f ? 0.f : t[0];
+          t[1] = fabsf(x[1]) <= 1e-8f ? 0.f : t[1];
+        }
+        r[2 * i] = t[0], r[2 * i + 1] = t[1];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) r[i] = mxint_mantissa(v[i], e, q);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const uint32_t code = ((__float_as_uint(r[i]) >> 24) & 0x80u) | (uint32_t)fabsf(r[i]);
+      cw[i >> 2] |= code << (8 * (i & 3));
+    }
+  }
+  return (uint32_t)(e - q.emin);
+}
+
+// value of one code under the exponent byte eb (the unpack hook: the quantizer's output, exact)
+__device__ __forceinline__ float code_value(uint32_t code, uint32_t eb, const QP& q) {
+  const float m = ldexpf((float)(code & 0x7fu), (int)eb + q.emin - q.mbits);
+  return (code & 0x80u) ? -m : m;
+}
+
+// 16 codes -> the 16 bf16 values quant16_bf16 writes for them (w[i]: elements 2 i, 2 i + 1), element i under the exponent byte
+// (eb[i >> 2] >> 8 (i & 3)) & 0xff.  k = e - mbits within [-126, 126] for all 16 (mxint16_fast_ok): magnitude x 2^k, the power of two
+// built from exponent bits; otherwise ldexpf, as the quantizer's slow path (the same values wherever both apply: every product is exact).
+__device__ __forceinline__ void codes16_to_bf16(const uint4& c, const uint32_t (&eb)[4], const QP& q, uint32_t (&w)[8]) {
+  typedef __attribute__((ext_vector_type(2))) float f2;
+  const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
+  const int kb = q.emin - q.mbits;
+  int k[16];
+  bool fast = true;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    k[i] = (int)((eb[i >> 2] >> (8 * (i & 3))) & 0xffu) + kb;
+    fast = fast && k[i] >= -126 && k[i] <= 126;
+  }
+  if (fast) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t m = cw[j] & 0x7f7f7f7fu, s = cw[j] & 0x80808080u;
+      const f2 a = (f2){(float)(m & 0xffu), (float)((m >> 8) & 0xffu)} *
+                   (f2){__uint_as_float((uint32_t)(127 + k[4 * j]) << 23), __uint_as_float((uint32_t)(127 + k[4 * j + 1]) << 23)};
+      const f2 b = (f2){(float)((m >> 16) & 0xffu), (float)(m >> 24)} *
+                   (f2){__uint_as_float((uint32_t)(127 + k[4 * j + 2]) << 23), __uint_as_float((uint32_t)(127 + k[4 * j + 3]) << 23)};
+      // the two high halves, then the sign bytes into bits 15 and 31
+      w[2 * j] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u) | __builtin_amdgcn_perm(s, s, 0x010c000cu);
+      w[2 * j + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u) | __builtin_amdgcn_perm(s, s, 0x030c020cu);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t c0 = (cw[i >> 1] >> (16 * (i & 1))) & 0xffu, c1 = (cw[i >> 1] >> (16 * (i & 1) + 8)) & 0xffu;
+      const uint32_t lo = exact_bf16_bits(ldexpf((float)(c0 & 0x7fu), k[2 * i])) | ((c0 & 0x80u) << 8);
+      const uint32_t hi = exact_bf16_bits(ldexpf((float)(c1 & 0x7fu), k[2 * i + 1])) | ((c1 & 0x80u) << 8);
+      w[i] = lo | (hi << 16);
+    }
+  }
+}
+
+}  // namespace kvc
+
+namespace attn {
+
+// four consecutive elements; one 8- / 16-byte load when the row is aligned
+template <int DT>
+__device__ __forceinline__ void load4(const void* base, int64_t off, bool vec, float (&v)[4]) {
+  if (vec) {
+    if constexpr (DT == LQER_F32) {
+      const float4 t = *(const float4*)((const float*)base + off);
+      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+      const uint2 t = *(const uint2*)((const bf16_t*)base + off);
+      const uint32_t wd[2] = {t.x, t.y};
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if constexpr (DT == LQER_F16) {
+          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+          const h2 hv = __builtin_bit_cast(h2, wd[j]);
+          v[2 * j] = (float)hv[0], v[2 * j + 1] = (float)hv[1];
+        } else {
+          v[2 * j] = __uint_as_float(wd[j] << 16), v[2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = load_elem<DT>(base, off + j);
+  }
+}
+
+}  // namespace attn
+
+}  // namespace lqer

@@ -1,0 +1,200 @@
+"""A packed MXINT KV cache for the fused quantized attention (include/lqer_hip.h "packed KV cache"; csrc/kv_cache.hip writes it,
+csrc/attn_decode.hip reads it).
+
+The decode kernel quantizes the whole K (blocks of 16 along t) and V (blocks of 16 along d) in every step, with the results of
+the step before.  The cache keeps the quantizer's output instead of the raw tensors - a one-byte code per element, a one-byte
+exponent per block - and `attention_flexible_cached` multiplies that: the same bits as `attention_flexible(kernel="decode")` on the
+raw K and V, from 2 d (1 + 1/16) bytes per token and kv head instead of 2 d itemsize.  The raw values are gone once appended, so
+nothing here falls back: what the kernel does not cover raises."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib, ops
+from .functional import _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _MAX_GRID_Z, _attn_fmts, _bcast_stride
+
+
+def _tri(*xs):
+    return (C.c_int64 * 3)(*xs)
+
+
+def cache_bytes(dtype: torch.dtype, batch: int, kv_heads: int, capacity: int, head_dim: int) -> int:
+    return _lib.lib().lqer_kv_cache_bytes(ops._DT[dtype], batch, kv_heads, capacity, head_dim)
+
+
+def _sections(dtype: torch.dtype, batch: int, kv_heads: int, capacity: int, head_dim: int):
+    """[(name, byte offset, bytes per (batch, kv head) and block of 16 keys - None for the staging rows, copied whole)] of the header's
+    layout, and the total."""
+    up = lambda v: (v + 255) // 256 * 256
+    cap, z = (capacity + 15) // 16 * 16, batch * kv_heads
+    codes, exps = up(z * cap * head_dim), up(z * (cap // 16) * head_dim)
+    stage = up(z * 16 * head_dim * torch.empty((), dtype=dtype).element_size())
+    out, at = [], 0
+    for name, size, per_block in (("k_codes", codes, 16 * head_dim), ("k_exps", exps, head_dim), ("v_codes", codes, 16 * head_dim),
+                                  ("v_exps", exps, head_dim), ("k_stage", stage, None)):
+        out.append((name, at, per_block))
+        at += size
+    return out, at
+
+
+@torch.no_grad()
+def append_packed(buf: torch.Tensor, k: torch.Tensor, v: torch.Tensor, length: int, capacity: int, k_fmt, v_fmt) -> None:
+    """lqer_kv_cache_append on a caller's buffer: k / v [batch, kv_heads, n, d] become keys length .. length + n - 1."""
+    ops._need_gpu(buf, k, v)
+    if k.dim() != 4 or k.shape != v.shape or k.dtype != v.dtype:
+        raise ValueError(f"append: k {tuple(k.shape)} {k.dtype} and v {tuple(v.shape)} {v.dtype} must be equal-shaped [batch, kv_heads, n, d]")
+    if k.stride(3) != 1:
+        k = k.contiguous()
+    if v.stride(3) != 1:
+        v = v.contiguous()
+    b, hk, n, d = k.shape
+    with torch.cuda.device(k.device):
+        _lib.check(_lib.lib().lqer_kv_cache_append(buf.data_ptr(), buf.numel(), k.data_ptr(), v.data_ptr(), _tri(k.stride(0), k.stride(1), k.stride(2)),
+                                                   _tri(v.stride(0), v.stride(1), v.stride(2)), ops.dtype_code(k), b, hk, capacity, d, length, n,
+                                                   C.byref(k_fmt), C.byref(v_fmt), ops._stream(k.device)),
+                   "lqer_kv_cache_append")
+
+
+@torch.no_grad()
+def unpack_packed(buf: torch.Tensor, dtype: torch.dtype, batch: int, kv_heads: int, capacity: int, head_dim: int, length: int, k_fmt, v_fmt):
+    """The dequantized K and V [batch, kv_heads, length, d] as fp32 (lqer_kv_cache_unpack, a test hook)."""
+    ops._need_gpu(buf)
+    kf = torch.empty(batch, kv_heads, length, head_dim, dtype=torch.float32, device=buf.device)
+    vf = torch.empty_like(kf)
+    with torch.cuda.device(buf.device):
+        _lib.check(_lib.lib().lqer_kv_cache_unpack(buf.data_ptr(), buf.numel(), ops._DT[dtype], batch, kv_heads, capacity, head_dim, length,
+                                                   C.byref(k_fmt), C.byref(v_fmt), kf.data_ptr(), vf.data_ptr(), ops._stream(buf.device)),
+                   "lqer_kv_cache_unpack")
+    return kf, vf
+
+
+@torch.no_grad()
+def attend_packed(q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask=None, causal=False, out=None, stats=None, ws=None):
+    """lqer_attention_q_decode_kv on a caller's buffer.  q [b, h, s, d]; out: a [b, h, s, d] tensor or view (any strides over b, h, s);
+    stats: [b, h, s, 2] fp32 or None; ws: a uint8 workspace or None (the stream's)."""
+    b, h, s, d = q.shape
+    m = attention_mask
+    L = _lib.lib()
+    with torch.cuda.device(q.device):
+        nws = L.lqer_attention_q_decode_kv_workspace_bytes(b, h, kv_heads, s, length, d)
+        if ws is None:
+            ws = ops.workspace(q.device, max(nws, 16))
+        _lib.check(L.lqer_attention_q_decode_kv(q.data_ptr(), buf.data_ptr(), buf.numel(), capacity, m.data_ptr() if m is not None else None,
+                                                out.data_ptr(), stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, kv_heads,
+                                                s, length, d, _tri(q.stride(0), q.stride(1), q.stride(2)),
+                                                _tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
+                                                _tri(out.stride(0), out.stride(1), out.stride(2)), float(scaling), int(bool(causal)),
+                                                C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
+                                                ops._stream(q.device)),
+                   "lqer_attention_q_decode_kv")
+
+
+class QuantizedKVCache:
+    """K and V of one attention layer as the codes and block exponents of the layer's two matmul configs (cfg0: Q K^T, cfg1: P V).
+
+    .append(k, v)   k / v [batch, kv_heads, n, head_dim] of `dtype`, any n >= 1; grows by doubling when the capacity is passed
+    .length         cached tokens;  .capacity  tokens the buffer holds;  .nbytes  bytes of the buffer
+    .reset()        length 0 (the buffer needs no clearing: nothing depends on rows beyond the length)
+    .dequantized()  (K, V) [batch, kv_heads, length, head_dim] fp32 - the quantizers' outputs, for tests"""
+
+    @staticmethod
+    def covers(cfg0: dict, cfg1: dict, head_dim: int, dtype: torch.dtype) -> bool:
+        """Whether the packed cache and its kernel take these formats (block_fp, width <= 8, blocks of 16 - all four quantizers, since the
+        attention over the cache is the fused decode kernel), this head dim (a multiple of 16 up to 128) and this dtype."""
+        return (_attn_fmts(cfg0, cfg1) is not None and isinstance(head_dim, int) and 0 < head_dim <= _ATTN_MAX_D and head_dim % 16 == 0
+                and dtype in ops._DT)
+
+    def __init__(self, batch: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device, capacity: int = 256):
+        if not self.covers(cfg0, cfg1, head_dim, dtype):
+            raise NotImplementedError(f"QuantizedKVCache: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
+                                      "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
+                                      "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
+        if batch < 1 or kv_heads < 1 or capacity < 1 or batch > _MAX_GRID_Z or kv_heads > _MAX_GRID_Z:
+            raise ValueError(f"QuantizedKVCache: batch {batch}, kv_heads {kv_heads}, capacity {capacity}")
+        self.batch, self.kv_heads, self.head_dim, self.dtype, self.device = batch, kv_heads, head_dim, dtype, torch.device(device)
+        self.cfg0, self.cfg1 = cfg0, cfg1
+        self.fmts = _attn_fmts(cfg0, cfg1)  # Q, K^T, P, V
+        self.length = 0
+        self.capacity = (capacity + 15) // 16 * 16
+        self.buf = self._alloc(self.capacity)
+
+    def _alloc(self, capacity: int) -> torch.Tensor:
+        return torch.empty(cache_bytes(self.dtype, self.batch, self.kv_heads, capacity, self.head_dim), dtype=torch.uint8, device=self.device)
+
+    @property
+    def nbytes(self) -> int:
+        return self.buf.numel()
+
+    def reset(self) -> None:
+        self.length = 0
+
+    def _grow(self, need: int) -> None:
+        cap = self.capacity
+        while cap < need:
+            cap *= 2
+        new = self._alloc(cap)
+        old_s, _ = _sections(self.dtype, self.batch, self.kv_heads, self.capacity, self.head_dim)
+        new_s, _ = _sections(self.dtype, self.batch, self.kv_heads, cap, self.head_dim)
+        z, blocks = self.batch * self.kv_heads, (self.length + 15) // 16
+        for (_, o_at, per_block), (_, n_at, _) in zip(old_s, new_s):
+            if per_block is None:  # the staging rows: one size at every capacity
+                n = z * 16 * self.head_dim * torch.empty((), dtype=self.dtype).element_size()
+                new[n_at:n_at + n].copy_(self.buf[o_at:o_at + n])
+            elif blocks:
+                o_row, n_row = (self.capacity // 16) * per_block, (cap // 16) * per_block
+                src = self.buf[o_at:o_at + z * o_row].view(z, o_row)[:, :blocks * per_block]
+                new[n_at:n_at + z * n_row].view(z, n_row)[:, :blocks * per_block].copy_(src)
+        self.buf, self.capacity = new, cap
+
+    @torch.no_grad()
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> None:
+        want = (self.batch, self.kv_heads, self.head_dim)
+        if k.dim() != 4 or (k.shape[0], k.shape[1], k.shape[3]) != want or k.shape != v.shape or k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError(f"QuantizedKVCache.append: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} for a cache of "
+                             f"[{self.batch}, {self.kv_heads}, n, {self.head_dim}] {self.dtype}")
+        n = k.shape[2]
+        if n == 0:
+            return
+        if self.length + n > self.capacity:
+            self._grow(self.length + n)
+        append_packed(self.buf, k, v, self.length, self.capacity, self.fmts[1], self.fmts[3])
+        self.length += n
+
+    def dequantized(self):
+        return unpack_packed(self.buf, self.dtype, self.batch, self.kv_heads, self.capacity, self.head_dim, self.length, self.fmts[1], self.fmts[3])
+
+
+@torch.no_grad()
+def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mask=None, causal=False, out_layout="bhsd", return_stats=False):
+    """attention_flexible(q, K, V, cache.cfg0, cache.cfg1, scaling, ..., kernel="decode") for the K and V appended to `cache`, bit for
+    bit, without K and V: lqer_attention_q_decode_kv reads the cache's codes.  q [b, h, s, d] with s <= 8 (ValueError beyond: a prefill
+    attends over its own raw K and V with attention_flexible and then appends); masks, `out_layout` and `return_stats` as there.
+    Operands the kernel does not take raise ValueError - there is no other route to the cached values."""
+    if out_layout not in ("bhsd", "bshd"):
+        raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
+    if attention_mask is not None and causal:
+        raise ValueError("attention_flexible_cached: attention_mask and causal=True are two forms of one mask - pass one")
+    ops._need_gpu(q, attention_mask)
+    if q.dim() != 4:
+        raise ValueError(f"attention_flexible_cached: q {tuple(q.shape)} is not [b, h, s, d]")
+    b, h, s, d = q.shape
+    t = cache.length
+    if s > _ATTN_DECODE_MAX_S:
+        raise ValueError(f"attention_flexible_cached: {s} query rows per head - the kernel over the packed cache takes up to {_ATTN_DECODE_MAX_S}")
+    if (q.dtype != cache.dtype or q.device != cache.buf.device or b != cache.batch or d != cache.head_dim or h % cache.kv_heads or s < 1 or t < 1
+            or h > _MAX_GRID_Z or (causal and s > t)):
+        raise ValueError(f"attention_flexible_cached: q {tuple(q.shape)} {q.dtype} against a cache of {t} keys [{cache.batch}, {cache.kv_heads}, "
+                         f"{cache.head_dim}] {cache.dtype}" + (" (causal with more query rows than keys)" if causal and s > t else ""))
+    m = attention_mask
+    if m is not None and not (m.dim() == 4 and m.dtype == q.dtype and m.device == q.device and m.shape[3] == t and (m.stride(3) == 1 or t == 1)
+                              and m.shape[0] in (1, b) and m.shape[1] in (1, h) and m.shape[2] in (1, s)):
+        raise ValueError(f"attention_flexible_cached: mask {tuple(m.shape)} {m.dtype} - additive, [b|1, h|1, s|1, {t}] of q's dtype, dense along t")
+    if q.stride(3) != 1:
+        q = q.contiguous()
+    out = torch.empty((b, h, s, d) if out_layout == "bhsd" else (b, s, h, d), dtype=q.dtype, device=q.device)
+    stats = torch.empty(b, h, s, 2, dtype=torch.float32, device=q.device) if return_stats else None
+    attend_packed(q, cache.buf, cache.kv_heads, cache.capacity, t, cache.fmts, scaling, m, causal,
+                  out if out_layout == "bhsd" else out.transpose(1, 2), stats)
+    return (out, stats) if return_stats else out
