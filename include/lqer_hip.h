@@ -593,6 +593,16 @@ int lqer_attention_q_decode(const void* q, const void* k, const void* v, const v
  * lqer_attention_q_decode_kv: lqer_attention_q_decode with (k, v, k_strides, v_strides) replaced by (cache, cache_bytes, capacity); T
  * is the cache's length; k_fmt and v_fmt are those of the appends.  Arithmetic, masks, row_stats, workspace (size and layout), chunks,
  * launches and refusals are lqer_attention_q_decode's; the cache is only read.  Rows at and beyond T are never read.
+ * lqer_attention_q_kv: lqer_attention_q with (k, v, k_strides, v_strides) replaced by (cache, cache_bytes, capacity) - the argument list
+ * of lqer_attention_q_decode_kv - for ANY S >= 1: a second prompt, a long prompt fed in chunks, a speculated block of more than 8
+ * tokens on a cache that no longer has the raw K and V.  T is the cache's length; k_fmt and v_fmt are those of the appends.  The two
+ * bf16 images of lqer_attention_q's workspace (same size, same layout: lqer_attention_q_kv_workspace_bytes) are written from the
+ * codes and exponents - a conversion and a scaling, the padding as zeros - instead of quantizing K and V, and the same attention
+ * kernel runs on them: the SAME BITS as lqer_attention_q on the raw K and V that were appended - out and row_stats, both mask forms,
+ * grouped-query heads (K or V holding a NaN excepted, as above).  The cache is only read; rows at and beyond T are never read.  Three
+ * launches on `stream` (K image, V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a
+ * hipGraph.  Refusals: lqer_attention_q's (formats, D, null pointers, heads not a multiple of kv_heads, mask together with causal, a
+ * short workspace, S or T beyond the launch grid) and the cache's below; also LQER_E_INVALID for a workspace that is not 16-byte aligned.
  * lqer_kv_cache_unpack (test hook): the dequantized K and V [batch][kv_heads][T][D] as dense fp32 (either may be NULL).
  * Refused with a message, nothing launched or touched:
  *   LQER_E_UNSUPPORTED  k_fmt / v_fmt not LQER_Q_MXINT, width <= 8, block 16; D not a multiple of 16 or > 128;
@@ -610,6 +620,12 @@ int lqer_attention_q_decode_kv(const void* q, const void* cache, size_t cache_by
                                const int64_t* q_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
                                const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
                                void* workspace, size_t workspace_bytes, void* stream);
+size_t lqer_attention_q_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D);
+int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, int64_t capacity, const void* mask, void* out, float* row_stats,
+                        int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                        const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                        const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's

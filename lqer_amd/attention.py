@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .functional import _ATTN_DECODE_MAX_S, _repeat_kv, attention_flexible, unfused_attention  # noqa: F401  (_repeat_kv: the one spelling, in functional)
+from .functional import KERNEL_PREFILL, _ATTN_DECODE_MAX_S, _repeat_kv, attention_flexible, unfused_attention  # noqa: F401  (_repeat_kv: the one spelling, in functional)
 from .kvcache import QuantizedKVCache, attention_flexible_cached
 
 IMPLEMENTATION = "lqer_eager"
@@ -36,15 +36,18 @@ def lqer_fused_attention_forward(module: nn.Module, query: torch.Tensor, key: to
     are read through the head mapping, the output is written as [b, s, h, d] and no weights exist to return.  A caller that wants
     the weights (output_attentions), trains with dropout or hands over a mask of another dtype gets the unfused function.
     key / value that carry a packed cache layer (quantized_kv_cache below: a decode step, key and value are the NEW tokens only) run
-    attention_flexible_cached over that layer's cache; there the unfused function has nothing to run on, and those callers get an error."""
+    attention_flexible_cached over that layer's cache - more than 8 new tokens, which only a chunked_prefill layer tags, with the prefill
+    kernel; there the unfused function has nothing to run on, and those callers get an error."""
     unfused = (kwargs.get("output_attentions") or (dropout > 0.0 and module.training)
                or (attention_mask is not None and attention_mask.dtype != query.dtype))  # (a wider mask: torch adds it with type promotion)
     layer = getattr(key, _KV_LAYER_ATTR, None)
     if layer is not None:
-        if unfused or query.shape[2] > _ATTN_DECODE_MAX_S:
+        chunk = query.shape[2] > _ATTN_DECODE_MAX_S
+        if unfused or (chunk and not layer.chunked_prefill):
             raise NotImplementedError("lqer_fused attention over a packed KV cache: output_attentions, dropout in training, a mask of another "
                                       f"dtype and more than {_ATTN_DECODE_MAX_S} new tokens need the raw K and V, which the cache does not keep")
-        return attention_flexible_cached(query, layer.cache, scaling, attention_mask=attention_mask, out_layout="bshd"), None
+        return attention_flexible_cached(query, layer.cache, scaling, attention_mask=attention_mask, out_layout="bshd",
+                                         kernel=KERNEL_PREFILL if chunk else None), None
     if unfused:
         return lqer_eager_attention_forward(module, query, key, value, attention_mask, scaling, dropout=dropout, **kwargs)
     cfg0, cfg1 = module._lqer_matmul_cfg
@@ -66,13 +69,15 @@ def _kv_layer_cls():
         """One attention layer's K and V as a QuantizedKVCache.  An update() on the empty layer (the prefill) packs k and v and returns
         them as they are: the attention runs over the raw tensors, as without a cache.  An update() with up to 8 new tokens on a
         non-empty layer appends them and returns the NEW k and v tagged with this layer; lqer_fused_attention_forward then attends over
-        the cache.  More new tokens on a non-empty layer raise: the raw K and V of the past are gone."""
+        the cache.  More new tokens on a non-empty layer raise: the raw K and V of the past are gone - unless the layer was made with
+        chunked_prefill=True: then they are appended and tagged like a decode step's, and the attention over the cache is the prefill
+        kernel on images written from the codes (attention_flexible_cached(kernel="prefill"))."""
 
         is_sliding = False
 
-        def __init__(self, cfg0: dict, cfg1: dict, capacity: int = 256):
+        def __init__(self, cfg0: dict, cfg1: dict, capacity: int = 256, chunked_prefill: bool = False):
             super().__init__()
-            self.cfg0, self.cfg1, self.capacity0 = cfg0, cfg1, capacity
+            self.cfg0, self.cfg1, self.capacity0, self.chunked_prefill = cfg0, cfg1, capacity, bool(chunked_prefill)
             self.cache: Optional[QuantizedKVCache] = None
 
         def lazy_initialization(self, key_states: torch.Tensor, value_states: torch.Tensor) -> None:
@@ -85,7 +90,7 @@ def _kv_layer_cls():
             if not self.is_initialized:
                 self.lazy_initialization(key_states, value_states)
             past, n = self.cache.length, key_states.shape[-2]
-            if past > 0 and n > _ATTN_DECODE_MAX_S:
+            if past > 0 and n > _ATTN_DECODE_MAX_S and not self.chunked_prefill:
                 raise NotImplementedError(f"packed KV cache: {n} new tokens on a cache of {past} - the kernel over the cache takes up to "
                                           f"{_ATTN_DECODE_MAX_S} query rows, and the raw K and V of the past are not kept (no chunked prefill)")
             self.cache.append(key_states, value_states)
@@ -139,11 +144,14 @@ def _kv_layer_cls():
 _KV_LAYER_CLS = None
 
 
-def quantized_kv_cache(model: nn.Module, capacity: int = 256):
+def quantized_kv_cache(model: nn.Module, capacity: int = 256, chunked_prefill: bool = False):
     """A transformers.Cache for `model` (after enable_quantized_attention(model, q_config, fused=True)) whose layers hold K and V as
     the codes of that layer's two matmul configs (QuantizedKVCache): pass it as past_key_values to forward() or generate().  The
     decode steps give the bits of a DynamicCache run that takes the decode kernel.  Llama-family and OPT attention hand update()'s
-    tensors to the attention interface untouched, which is what carries the layer to lqer_fused_attention_forward."""
+    tensors to the attention interface untouched, which is what carries the layer to lqer_fused_attention_forward.
+    chunked_prefill=True: the layers also take more than 8 new tokens on a non-empty cache (a second turn, a long prompt in chunks, a
+    speculated block) - the prefill kernel over the cache, with the bits of a DynamicCache run that takes the prefill kernel on the raw K
+    and V.  The default keeps the NotImplementedError for such a call."""
     from transformers.cache_utils import Cache
 
     from .models import _decoder_layers
@@ -161,7 +169,7 @@ def quantized_kv_cache(model: nn.Module, capacity: int = 256):
         if not QuantizedKVCache.covers(cfg0, cfg1, head_dim, model.dtype):
             raise NotImplementedError(f"quantized_kv_cache: layer {i} (head_dim {head_dim}, {model.dtype}) has matmul quantizers outside the packed "
                                       "cache: block_fp, width <= 8, blocks of 16; head dims that are multiples of 16 up to 128")
-        out.append(cls(cfg0, cfg1, capacity))
+        out.append(cls(cfg0, cfg1, capacity, chunked_prefill))
     return Cache(layers=out)
 
 

@@ -1077,38 +1077,41 @@ size_t lqer_attention_q_workspace_bytes(int64_t batch, int64_t heads, int64_t kv
   return attention_q_workspace_bytes(batch, kv_heads, T, D);
 }
 
-int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                     int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
-                     const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
-                     const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+// the checks lqer_attention_q and lqer_attention_q_kv share (kv: K and V come from the packed cache - no k, v, strides - and the
+// workspace, which the cache's image kernels store in 16-byte pieces, must be aligned to that): LQER_OK = go on, 1 = nothing to do,
+// else the refusal
+static int attn_q_check(const char* who, bool kv, const void* q, const void* k, const void* v, const void* mask, void* out, int dtype,
+                        int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                        const int64_t* k_strides, const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, int causal,
+                        const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                        size_t workspace_bytes) {
   if (batch < 0 || heads <= 0 || kv_heads <= 0 || S < 0 || T < 0 || D <= 0) {
-    set_error("attention_q: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", (long long)batch, (long long)heads,
+    set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)batch, (long long)heads,
               (long long)kv_heads, (long long)S, (long long)T, (long long)D);
     return LQER_E_INVALID;
   }
   if (heads % kv_heads != 0) {
-    set_error("attention_q: heads %lld is not a multiple of kv_heads %lld", (long long)heads, (long long)kv_heads);
+    set_error("%s: heads %lld is not a multiple of kv_heads %lld", who, (long long)heads, (long long)kv_heads);
     return LQER_E_INVALID;
   }
   if (dtype != LQER_F32 && dtype != LQER_F16 && dtype != LQER_BF16) {
-    set_error("attention_q: unknown dtype %d", dtype);
+    set_error("%s: unknown dtype %d", who, dtype);
     return LQER_E_INVALID;
   }
-  if (!q_strides || !k_strides || !v_strides || !out_strides || (mask && !mask_strides)) {
-    set_error("attention_q: null stride array");
+  if (!q_strides || (!kv && (!k_strides || !v_strides)) || !out_strides || (mask && !mask_strides)) {
+    set_error("%s: null stride array", who);
     return LQER_E_INVALID;
   }
   if (mask && causal) {
-    set_error("attention_q: a mask tensor and causal = 1 are two forms of one mask - pass one");
+    set_error("%s: a mask tensor and causal = 1 are two forms of one mask - pass one", who);
     return LQER_E_INVALID;
   }
   if (!q_fmt || !k_fmt || !p_fmt || !v_fmt) {
-    set_error("attention_q: null quantizer format");
+    set_error("%s: null quantizer format", who);
     return LQER_E_INVALID;
   }
   if (D % 16 != 0 || D > 128) {
-    set_error("attention_q: head dim %lld - the fused kernel takes multiples of 16 up to 128 (the two products of lqer_matmul_q take any)",
+    set_error("%s: head dim %lld - the fused kernel takes multiples of 16 up to 128 (the two products of lqer_matmul_q take any)", who,
               (long long)D);
     return LQER_E_UNSUPPORTED;
   }
@@ -1117,33 +1120,48 @@ int lqer_attention_q(const void* q, const void* k, const void* v, const void* ma
     return LQER_E_UNSUPPORTED;
   for (const lqer_qfmt_t* f : {q_fmt, k_fmt, p_fmt, v_fmt})
     if (f->kind != LQER_Q_MXINT || f->block != 16) {
-      set_error("attention_q: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
-                "formats run as the two products of lqer_matmul_q", f->kind, f->block);
+      set_error("%s: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
+                "formats run as the two products of lqer_matmul_q", who, f->kind, f->block);
       return LQER_E_UNSUPPORTED;
     }
-  if (T > (int64_t)65535 * 64 || S > (int64_t)1 << 30) {  // (the image kernels put T / 64 on grid.y; tile indices are 32-bit)
-    set_error("attention_q: S = %lld / T = %lld beyond the launch grid (T <= 4194240, S <= 2^30)", (long long)S, (long long)T);
+  if (T > (int64_t)65535 * 64 || S > (int64_t)1 << 30) {  // (the image kernels put T / 64 on a grid dim of 65535; tile indices are 32-bit)
+    set_error("%s: S = %lld / T = %lld beyond the launch grid (T <= 4194240, S <= 2^30)", who, (long long)S, (long long)T);
     return LQER_E_UNSUPPORTED;
   }
   if (batch > 65535 || heads > 65535 || batch * kv_heads > 65535) {
-    set_error("attention_q: batch %lld x heads %lld beyond the launch grid (65535 heads, batch x kv_heads): call in chunks", (long long)batch,
+    set_error("%s: batch %lld x heads %lld beyond the launch grid (65535 heads, batch x kv_heads): call in chunks", who, (long long)batch,
               (long long)heads);
     return LQER_E_UNSUPPORTED;
   }
-  if (batch == 0 || S == 0) return LQER_OK;
+  if (batch == 0 || S == 0) return 1;
   if (T == 0) {
-    set_error("attention_q: T = 0 (a softmax over no keys)");
+    set_error("%s: T = 0 (a softmax over no keys)", who);
     return LQER_E_INVALID;
   }
-  if (!q || !k || !v || !out || !workspace) {
-    set_error("attention_q: null pointer");
+  if (!q || (!kv && (!k || !v)) || !out || !workspace) {
+    set_error("%s: null pointer", who);
+    return LQER_E_INVALID;
+  }
+  if (kv && (uintptr_t)workspace % 16 != 0) {
+    set_error("%s: workspace %p is not 16-byte aligned", who, workspace);
     return LQER_E_INVALID;
   }
   const size_t need = attention_q_workspace_bytes(batch, kv_heads, T, D);
   if (workspace_bytes < need) {
-    set_error("attention_q: workspace %zu B < %zu B (lqer_attention_q_workspace_bytes)", workspace_bytes, need);
+    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, workspace_bytes, need, who);
     return LQER_E_INVALID;
   }
+  return LQER_OK;
+}
+
+int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                     int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
+                     const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                     const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  const int rc = attn_q_check("attention_q", false, q, k, v, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides,
+                              mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
+  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
   return attention_q_dispatch(q, k, v, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides, mask_strides,
                               out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
                               (hipStream_t)stream);
@@ -1363,6 +1381,25 @@ int lqer_attention_q_decode_kv(const void* q, const void* cache, size_t cache_by
   return attention_q_decode_kv_dispatch(q, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides,
                                         out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
                                         (hipStream_t)stream);
+}
+
+size_t lqer_attention_q_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D) {
+  return lqer_attention_q_workspace_bytes(batch, heads, kv_heads, S, T, D);
+}
+
+int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, int64_t capacity, const void* mask, void* out, float* row_stats,
+                        int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
+                        const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                        const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  int rc = attn_q_check("attention_q_kv", true, q, nullptr, nullptr, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides, nullptr, nullptr,
+                        mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
+  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
+  rc = kv_cache_check("attention_q_kv", cache, cache_bytes, dtype, batch, kv_heads, capacity, D, T, k_fmt, v_fmt);
+  if (rc != LQER_OK) return rc;
+  return attention_q_kv_dispatch(q, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides,
+                                 out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
+                                 (hipStream_t)stream);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

@@ -29,7 +29,7 @@ namespace lqer {
 namespace attn {
 
 constexpr int NW = 4, BQ = 32 * NW, BT = 64;  // waves, queries per workgroup, keys per LDS tile
-constexpr int VD = 128;                      // rows of the V image per (batch, kv head): D padded to the image kernel's 128
+constexpr int VD = ATTN_V_ROWS;              // rows of the V image per (batch, kv head): D padded to the image kernel's 128
 
 struct Args {
   const void* q;
@@ -293,18 +293,21 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
 }
 
+// k == nullptr: the two images are already on their way on `st` (attention_q_kv_dispatch: written from the packed KV cache)
 template <int DT>
 static int launch(const void* q, const void* k, const void* v, Args a, const QP& qk, const QP& qv, const int64_t (&ks)[3], const int64_t (&vs)[3],
-                  int64_t batch, hipStream_t st) {
+                  int64_t batch, hipStream_t st, const char* who) {
   const int esz = DT == LQER_F32 ? 4 : 2;
   auto al16 = [&](const void* p, const int64_t (&s)[3]) {
     return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
   };
-  const unsigned nz = (unsigned)(batch * a.kv_heads);
-  k_attn_kimage<DT><<<dim3((unsigned)(a.Dp / 64), (unsigned)(a.Tp / 64), nz), 256, 0, st>>>(k, a.D, a.T, ks[0], ks[1], ks[2], a.kv_heads, qk,
-                                                                                        (bf16_t*)a.kimg, a.Tp, a.Dp, al16(k, ks));
-  k_attn_vimage<DT><<<dim3((unsigned)(VD / 64), (unsigned)(a.Tv / 64), nz), 256, 0, st>>>(v, a.D, a.T, vs[0], vs[1], vs[2], a.kv_heads, qv,
-                                                                                      (bf16_t*)a.vimg, a.Tv, al16(v, vs));
+  if (k) {
+    const unsigned nz = (unsigned)(batch * a.kv_heads);
+    k_attn_kimage<DT><<<dim3((unsigned)(a.Dp / 64), (unsigned)(a.Tp / 64), nz), 256, 0, st>>>(k, a.D, a.T, ks[0], ks[1], ks[2], a.kv_heads, qk,
+                                                                                          (bf16_t*)a.kimg, a.Tp, a.Dp, al16(k, ks));
+    k_attn_vimage<DT><<<dim3((unsigned)(VD / 64), (unsigned)(a.Tv / 64), nz), 256, 0, st>>>(v, a.D, a.T, vs[0], vs[1], vs[2], a.kv_heads, qv,
+                                                                                        (bf16_t*)a.vimg, a.Tv, al16(v, vs));
+  }
   const int64_t qs[3] = {a.q_bs, a.q_hs, a.q_rs};
   a.qvec = al16(q, qs);
   // the mask is read in groups of four elements: rows and pointer aligned to that, and T a multiple of four
@@ -317,7 +320,7 @@ static int launch(const void* q, const void* k, const void* v, Args a, const QP&
     case 3: k_attn_q<DT, 3><<<grid, 64 * NW, 0, st>>>(a); break;
     default: k_attn_q<DT, 4><<<grid, 64 * NW, 0, st>>>(a); break;
   }
-  return check_launch("lqer_attention_q");
+  return check_launch(who);
 }
 
 }  // namespace attn
@@ -333,10 +336,10 @@ size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, i
   return attn_align((size_t)(batch * kv_heads * Tp * Dp) * sizeof(bf16_t)) + attn_align((size_t)(batch * kv_heads * attn::VD * Tv) * sizeof(bf16_t));
 }
 
-int attention_q_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                         int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks, const int64_t* vs,
-                         const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
-                         const QP& q_w1, void* workspace, hipStream_t st) {
+// what k_attn_q needs but for qvec / mvec (attn::launch sets them): the two images at their places in the workspace
+static attn::Args attn_args(const void* q, const void* mask, void* out, float* row_stats, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S,
+                            int64_t T, int64_t D, const int64_t* qs, const int64_t* ms, const int64_t* os, float scaling, int causal,
+                            const QP& q_x0, const QP& q_x1, void* workspace) {
   attn::Args a;
   a.q = q, a.mask = mask, a.out = out, a.stats = row_stats;
   a.S = S, a.T = T, a.D = D;
@@ -350,8 +353,29 @@ int attention_q_dispatch(const void* q, const void* k, const void* v, const void
   a.scaling = scaling;
   a.q0 = q_x0, a.q1 = q_x1;
   a.qvec = a.mvec = false;
+  return a;
+}
+
+int attention_q_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                         int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks, const int64_t* vs,
+                         const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
+                         const QP& q_w1, void* workspace, hipStream_t st) {
+  const attn::Args a = attn_args(q, mask, out, row_stats, batch, heads, kv_heads, S, T, D, qs, ms, os, scaling, causal, q_x0, q_x1, workspace);
   const int64_t k3[3] = {ks[0], ks[1], ks[2]}, v3[3] = {vs[0], vs[1], vs[2]};
-  return with_dtype(dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st); });
+  return with_dtype(dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st, "lqer_attention_q"); });
+}
+
+// the same attention with the two images written from the packed KV cache's codes (kv_cache.hip) instead of the raw K and V
+int attention_q_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
+                            int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ms,
+                            const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1, const QP& q_w1,
+                            void* workspace, hipStream_t st) {
+  const attn::Args a = attn_args(q, mask, out, row_stats, batch, heads, kv_heads, S, T, D, qs, ms, os, scaling, causal, q_x0, q_x1, workspace);
+  kv_cache_images_dispatch(cache, dtype, batch, kv_heads, capacity, D, T, q_w0, q_w1, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv, st);
+  const int64_t none[3] = {0, 0, 0};
+  return with_dtype(dtype, [&](auto dt) {
+    return attn::launch<decltype(dt)::value>(q, nullptr, nullptr, a, q_w0, q_w1, none, none, batch, st, "lqer_attention_q_kv");
+  });
 }
 
 }  // namespace lqer

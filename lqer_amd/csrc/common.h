@@ -773,6 +773,14 @@ int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, 
                              int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const QP& qk, const QP& qv, hipStream_t st);
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
                              const QP& qv, float* k_f32, float* v_f32, hipStream_t st);
+// ... and the prefill kernel over the packed KV cache: kv_cache.hip writes the two images from the codes, attn_q.hip runs k_attn_q on them
+constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128
+void kv_cache_images_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
+                              const QP& qv, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv, hipStream_t st);
+int attention_q_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
+                            int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ms,
+                            const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1, const QP& q_w1,
+                            void* workspace, hipStream_t st);
 int qmatmul_dispatch(const void* x, const void* y, void* out, int dtype, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs,
                      int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, void* workspace, hipStream_t st);
 

@@ -7,6 +7,9 @@
 // One launch when the staging rows read and the staging rows written cannot meet (the new keys stay inside the open block, or the
 // cache ended on a block boundary); otherwise the staging rows are written by a second launch of the same kernel.
 //   k_kv_unpack  code x 2^(e - mbits) as fp32, one element per thread.
+//   k_kv_kimage / k_kv_vimage   the cache -> the two bf16 images k_attn_q reads (attn_q.hip; what k_attn_kimage / k_attn_vimage write from
+//                the raw K and V): codes16_to_bf16 on 16 codes per 16-byte load, zeros wherever the raw image kernels write their
+//                padding - every key at or beyond T, every d at or beyond D.  Nothing of the cache at or beyond key T reaches an image.
 #include "kv_pack.h"
 
 namespace lqer {
@@ -106,6 +109,86 @@ __global__ __launch_bounds__(256) void k_kv_unpack(const UArgs a) {
   if (a.vf) a.vf[i] = code_value(a.vc[at], a.ve[(blk * (a.D / 16) + d / 16) * 16 + t % 16], a.qv);
 }
 
+struct IArgs {
+  const unsigned char *kc, *ke, *vc, *ve;
+  bf16_t *kimg, *vimg;  // [Z][Tp][Dp], [Z][ATTN_V_ROWS][Tv]
+  int64_t cap, D, T, Tp, Dp, Tv;
+  QP qk, qv;
+};
+
+// K image: the codes' own layout, no transpose.  A thread: 16 d of one key - 16 code bytes, the 16 exponent bytes of (block of keys, d),
+// 32 bytes of the image row; consecutive threads, consecutive pieces of the row.  grid.x covers Tp (Dp / 16) exactly (a multiple of 512).
+__global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
+  const int64_t z = blockIdx.y, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int dq = (int)(a.Dp / 16);
+  const int64_t t = i / dq;
+  const int d0 = 16 * (int)(i % dq);
+  uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (t < a.T && d0 < a.D) {
+    const uint4 c = *(const uint4*)(a.kc + (z * a.cap + t) * a.D + d0);
+    const uint4 e = *(const uint4*)(a.ke + (z * (a.cap / 16) + t / 16) * a.D + d0);
+    const uint32_t eb[4] = {e.x, e.y, e.z, e.w};
+    codes16_to_bf16(c, eb, a.qk, w);
+  }
+  uint4* dst = (uint4*)(a.kimg + (z * a.Tp + t) * a.Dp + d0);
+  dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// V image: V^T, rows d, t contiguous - a transpose through LDS.  One workgroup = 64 keys x all ATTN_V_ROWS image rows.
+// In: thread (db = tid & 7, tg = tid >> 3) takes 16 d of the four keys t0 + 4 tg ..: four 16-byte code loads and ONE dword of
+// exponents (the cache keeps the bytes of four consecutive keys of a d block together), and stores, per d, the four keys' bf16 as
+// 8 bytes of the tile row d.  Out: thread (c = tid & 7) moves 16 bytes (8 keys) of the rows tid >> 3 + 16 u: eight consecutive
+// lanes write the 128 contiguous bytes of an image row.
+// Tile: [128 d][64 t] bf16 in 128-byte rows; the 8-byte group g of row d lives at group (g + 2 (d >> 4)) & 15.  The 8-byte stores are
+// served in groups of 16 consecutive lanes on 32 banks - lanes (db 0-7, tg 2 j, 2 j + 1) at one i: without the rotation eight rows 16
+// apart put all eight db on the same two groups (8-way); with it the 16 lanes hit the 16 groups of a 128-byte bank row once each.
+// The rotation is even, so a 16-byte pair of groups stays a pair: the reads - per group of 16 lanes two even and two odd rows (256-byte
+// bank row: the odd rows are the upper half), chunks 0-3 of one row and 4-7 of the other, all rotated by the same d >> 4 - stay
+// conflict-free.
+__global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char tile[ATTN_V_ROWS * 128];
+  static_assert(ATTN_V_ROWS == 128, "the thread maps below cover 8 blocks of 16 d");
+  const int tid = threadIdx.x;
+  const int64_t z = blockIdx.y, t0 = (int64_t)blockIdx.x * 64;
+  {
+    const int db = tid & 7, tg = tid >> 3;
+    const int64_t t = t0 + 4 * tg;
+    uint32_t w[4][8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w[r][j] = 0;
+    if (16 * db < a.D && t < a.T) {  // (t < T <= cap, t a multiple of 4: the dword of exponents lies inside the section)
+      const uint32_t e4 = *(const uint32_t*)(a.ve + ((z * (a.cap / 16) + t / 16) * (a.D / 16) + db) * 16 + t % 16);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (t + r < a.T) {
+          const uint4 c = *(const uint4*)(a.vc + (z * a.cap + t + r) * a.D + 16 * db);
+          const uint32_t e = ((e4 >> (8 * r)) & 0xffu) * 0x01010101u;  // one exponent for the 16 d
+          const uint32_t eb[4] = {e, e, e, e};
+          codes16_to_bf16(c, eb, a.qv, w[r]);
+        }
+    }
+    unsigned char* row = tile + (16 * db) * 128 + 8 * ((tg + 2 * db) & 15);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int sh = 16 * (i & 1);
+      *(uint2*)(row + i * 128) = make_uint2(((w[0][i >> 1] >> sh) & 0xffffu) | (((w[1][i >> 1] >> sh) & 0xffffu) << 16),
+                                            ((w[2][i >> 1] >> sh) & 0xffffu) | (((w[3][i >> 1] >> sh) & 0xffffu) << 16));
+    }
+  }
+  __syncthreads();
+  {
+    const int c = tid & 7;
+#pragma unroll
+    for (int u = 0; u < ATTN_V_ROWS / 16; ++u) {
+      const int d = (tid >> 3) + 16 * u;  // d >> 4 == u
+      *(uint4*)(a.vimg + (z * ATTN_V_ROWS + d) * a.Tv + t0 + 8 * c) = *(const uint4*)(tile + d * 128 + 16 * ((c + u) & 7));
+    }
+  }
+}
+
 }  // namespace kvc
 
 size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D) {
@@ -155,6 +238,19 @@ int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_
   a.kf = k_f32, a.vf = v_f32, a.Z = batch * kv_heads, a.cap = l.cap, a.T = T, a.D = D, a.qk = qk, a.qv = qv;
   kvc::k_kv_unpack<<<dim3((unsigned)((a.Z * T * D + 255) / 256)), 256, 0, st>>>(a);
   return check_launch("lqer_kv_cache_unpack");
+}
+
+// the two images of lqer_attention_q's workspace from the cache's first T keys; the caller (attn_q.hip) checks the launches
+void kv_cache_images_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
+                              const QP& qv, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv, hipStream_t st) {
+  const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
+  const unsigned char* base = (const unsigned char*)cache;
+  kvc::IArgs a;
+  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps;
+  a.kimg = kimg, a.vimg = vimg, a.cap = l.cap, a.D = D, a.T = T, a.Tp = Tp, a.Dp = Dp, a.Tv = Tv, a.qk = qk, a.qv = qv;
+  const unsigned nz = (unsigned)(batch * kv_heads);
+  kvc::k_kv_kimage<<<dim3((unsigned)(Tp * (Dp / 16) / 256), nz), 256, 0, st>>>(a);
+  kvc::k_kv_vimage<<<dim3((unsigned)(Tv / 64), nz), 128, 0, st>>>(a);
 }
 
 }  // namespace lqer

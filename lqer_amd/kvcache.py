@@ -1,11 +1,12 @@
 """A packed MXINT KV cache for the fused quantized attention (include/lqer_hip.h "packed KV cache"; csrc/kv_cache.hip writes it,
-csrc/attn_decode.hip reads it).
+csrc/attn_decode.hip reads it; for more than 8 query rows csrc/kv_cache.hip turns it into the prefill kernel's two images).
 
 The decode kernel quantizes the whole K (blocks of 16 along t) and V (blocks of 16 along d) in every step, with the results of
 the step before.  The cache keeps the quantizer's output instead of the raw tensors - a one-byte code per element, a one-byte
 exponent per block - and `attention_flexible_cached` multiplies that: the same bits as `attention_flexible(kernel="decode")` on the
-raw K and V, from 2 d (1 + 1/16) bytes per token and kv head instead of 2 d itemsize.  The raw values are gone once appended, so
-nothing here falls back: what the kernel does not cover raises."""
+raw K and V, from 2 d (1 + 1/16) bytes per token and kv head instead of 2 d itemsize.  With kernel="prefill" it takes any number of
+query rows - a second prompt, a prompt fed in chunks - and gives the bits of `attention_flexible(kernel="prefill")`.  The raw values are
+gone once appended, so nothing here falls back: what the kernels do not cover raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,7 +14,8 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from .functional import _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _MAX_GRID_Z, _attn_fmts, _bcast_stride
+from .functional import (KERNEL_DECODE, KERNEL_PREFILL, _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _ATTN_MAX_T, _MAX_GRID_Z, _attn_fmts,
+                         _bcast_stride)
 
 
 def _tri(*xs):
@@ -70,25 +72,35 @@ def unpack_packed(buf: torch.Tensor, dtype: torch.dtype, batch: int, kv_heads: i
     return kf, vf
 
 
+def _attend(name, q, buf, kv_heads, capacity, length, fmts, scaling, m, causal, out, stats, ws):
+    """The C call `name` (lqer_attention_q_decode_kv / lqer_attention_q_kv: one argument list) with its own workspace function."""
+    b, h, s, d = q.shape
+    L = _lib.lib()
+    with torch.cuda.device(q.device):
+        nws = getattr(L, name + "_workspace_bytes")(b, h, kv_heads, s, length, d)
+        if ws is None:
+            ws = ops.workspace(q.device, max(nws, 16))
+        _lib.check(getattr(L, name)(q.data_ptr(), buf.data_ptr(), buf.numel(), capacity, m.data_ptr() if m is not None else None,
+                                    out.data_ptr(), stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, kv_heads,
+                                    s, length, d, _tri(q.stride(0), q.stride(1), q.stride(2)),
+                                    _tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
+                                    _tri(out.stride(0), out.stride(1), out.stride(2)), float(scaling), int(bool(causal)),
+                                    C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
+                                    ops._stream(q.device)),
+                   name)
+
+
 @torch.no_grad()
 def attend_packed(q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask=None, causal=False, out=None, stats=None, ws=None):
     """lqer_attention_q_decode_kv on a caller's buffer.  q [b, h, s, d]; out: a [b, h, s, d] tensor or view (any strides over b, h, s);
     stats: [b, h, s, 2] fp32 or None; ws: a uint8 workspace or None (the stream's)."""
-    b, h, s, d = q.shape
-    m = attention_mask
-    L = _lib.lib()
-    with torch.cuda.device(q.device):
-        nws = L.lqer_attention_q_decode_kv_workspace_bytes(b, h, kv_heads, s, length, d)
-        if ws is None:
-            ws = ops.workspace(q.device, max(nws, 16))
-        _lib.check(L.lqer_attention_q_decode_kv(q.data_ptr(), buf.data_ptr(), buf.numel(), capacity, m.data_ptr() if m is not None else None,
-                                                out.data_ptr(), stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, kv_heads,
-                                                s, length, d, _tri(q.stride(0), q.stride(1), q.stride(2)),
-                                                _tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
-                                                _tri(out.stride(0), out.stride(1), out.stride(2)), float(scaling), int(bool(causal)),
-                                                C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
-                                                ops._stream(q.device)),
-                   "lqer_attention_q_decode_kv")
+    _attend("lqer_attention_q_decode_kv", q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask, causal, out, stats, ws)
+
+
+@torch.no_grad()
+def prefill_packed(q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask=None, causal=False, out=None, stats=None, ws=None):
+    """lqer_attention_q_kv on a caller's buffer: attend_packed's arguments, any number of query rows."""
+    _attend("lqer_attention_q_kv", q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask, causal, out, stats, ws)
 
 
 class QuantizedKVCache:
@@ -167,11 +179,17 @@ class QuantizedKVCache:
 
 
 @torch.no_grad()
-def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mask=None, causal=False, out_layout="bhsd", return_stats=False):
+def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mask=None, causal=False, out_layout="bhsd", return_stats=False,
+                              kernel=None):
     """attention_flexible(q, K, V, cache.cfg0, cache.cfg1, scaling, ..., kernel="decode") for the K and V appended to `cache`, bit for
     bit, without K and V: lqer_attention_q_decode_kv reads the cache's codes.  q [b, h, s, d] with s <= 8 (ValueError beyond: a prefill
     attends over its own raw K and V with attention_flexible and then appends); masks, `out_layout` and `return_stats` as there.
-    Operands the kernel does not take raise ValueError - there is no other route to the cached values."""
+    kernel="prefill" takes any s >= 1 - a second prompt or a chunk of a long one on a non-empty cache - and gives the bits of
+    attention_flexible(..., kernel="prefill"): lqer_attention_q_kv writes the prefill kernel's two images from the codes.  None and
+    "decode" are the decode kernel.  Operands the kernels do not take raise ValueError - there is no other route to the cached values."""
+    if kernel not in (None, KERNEL_PREFILL, KERNEL_DECODE):
+        raise ValueError(f"kernel {kernel!r}: None, 'prefill' or 'decode'")
+    prefill = kernel == KERNEL_PREFILL
     if out_layout not in ("bhsd", "bshd"):
         raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
     if attention_mask is not None and causal:
@@ -181,10 +199,10 @@ def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mas
         raise ValueError(f"attention_flexible_cached: q {tuple(q.shape)} is not [b, h, s, d]")
     b, h, s, d = q.shape
     t = cache.length
-    if s > _ATTN_DECODE_MAX_S:
+    if not prefill and s > _ATTN_DECODE_MAX_S:
         raise ValueError(f"attention_flexible_cached: {s} query rows per head - the kernel over the packed cache takes up to {_ATTN_DECODE_MAX_S}")
     if (q.dtype != cache.dtype or q.device != cache.buf.device or b != cache.batch or d != cache.head_dim or h % cache.kv_heads or s < 1 or t < 1
-            or h > _MAX_GRID_Z or (causal and s > t)):
+            or h > _MAX_GRID_Z or (causal and s > t) or (prefill and (t > _ATTN_MAX_T or b * cache.kv_heads > _MAX_GRID_Z))):
         raise ValueError(f"attention_flexible_cached: q {tuple(q.shape)} {q.dtype} against a cache of {t} keys [{cache.batch}, {cache.kv_heads}, "
                          f"{cache.head_dim}] {cache.dtype}" + (" (causal with more query rows than keys)" if causal and s > t else ""))
     m = attention_mask
@@ -195,6 +213,6 @@ def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mas
         q = q.contiguous()
     out = torch.empty((b, h, s, d) if out_layout == "bhsd" else (b, s, h, d), dtype=q.dtype, device=q.device)
     stats = torch.empty(b, h, s, 2, dtype=torch.float32, device=q.device) if return_stats else None
-    attend_packed(q, cache.buf, cache.kv_heads, cache.capacity, t, cache.fmts, scaling, m, causal,
-                  out if out_layout == "bhsd" else out.transpose(1, 2), stats)
+    (prefill_packed if prefill else attend_packed)(q, cache.buf, cache.kv_heads, cache.capacity, t, cache.fmts, scaling, m, causal,
+                                                   out if out_layout == "bhsd" else out.transpose(1, 2), stats)
     return (out, stats) if return_stats else out
