@@ -1077,192 +1077,123 @@ size_t lqer_attention_q_workspace_bytes(int64_t batch, int64_t heads, int64_t kv
   return attention_q_workspace_bytes(batch, kv_heads, T, D);
 }
 
-// the checks lqer_attention_q and lqer_attention_q_kv share (kv: K and V come from the packed cache - no k, v, strides - and the
-// workspace, which the cache's image kernels store in 16-byte pieces, must be aligned to that): LQER_OK = go on, 1 = nothing to do,
-// else the refusal
-static int attn_q_check(const char* who, bool kv, const void* q, const void* k, const void* v, const void* mask, void* out, int dtype,
-                        int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
-                        const int64_t* k_strides, const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, int causal,
-                        const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                        size_t workspace_bytes) {
-  if (batch < 0 || heads <= 0 || kv_heads <= 0 || S < 0 || T < 0 || D <= 0) {
-    set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)batch, (long long)heads,
-              (long long)kv_heads, (long long)S, (long long)T, (long long)D);
-    return LQER_E_INVALID;
-  }
-  if (heads % kv_heads != 0) {
-    set_error("%s: heads %lld is not a multiple of kv_heads %lld", who, (long long)heads, (long long)kv_heads);
-    return LQER_E_INVALID;
-  }
-  if (dtype != LQER_F32 && dtype != LQER_F16 && dtype != LQER_BF16) {
-    set_error("%s: unknown dtype %d", who, dtype);
-    return LQER_E_INVALID;
-  }
-  if (!q_strides || (!kv && (!k_strides || !v_strides)) || !out_strides || (mask && !mask_strides)) {
-    set_error("%s: null stride array", who);
-    return LQER_E_INVALID;
-  }
-  if (mask && causal) {
-    set_error("%s: a mask tensor and causal = 1 are two forms of one mask - pass one", who);
-    return LQER_E_INVALID;
-  }
-  if (!q_fmt || !k_fmt || !p_fmt || !v_fmt) {
-    set_error("%s: null quantizer format", who);
-    return LQER_E_INVALID;
-  }
-  if (D % 16 != 0 || D > 128) {
-    set_error("%s: head dim %lld - the fused kernel takes multiples of 16 up to 128 (the two products of lqer_matmul_q take any)", who,
-              (long long)D);
-    return LQER_E_UNSUPPORTED;
-  }
-  if (!fmt_ok(q_fmt, "attention Q quantizer", 8) || !fmt_ok(k_fmt, "attention K quantizer", 8) || !fmt_ok(p_fmt, "attention P quantizer", 8) ||
-      !fmt_ok(v_fmt, "attention V quantizer", 8))
-    return LQER_E_UNSUPPORTED;
-  for (const lqer_qfmt_t* f : {q_fmt, k_fmt, p_fmt, v_fmt})
-    if (f->kind != LQER_Q_MXINT || f->block != 16) {
-      set_error("%s: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
-                "formats run as the two products of lqer_matmul_q", who, f->kind, f->block);
-      return LQER_E_UNSUPPORTED;
-    }
-  if (T > (int64_t)65535 * 64 || S > (int64_t)1 << 30) {  // (the image kernels put T / 64 on a grid dim of 65535; tile indices are 32-bit)
-    set_error("%s: S = %lld / T = %lld beyond the launch grid (T <= 4194240, S <= 2^30)", who, (long long)S, (long long)T);
-    return LQER_E_UNSUPPORTED;
-  }
-  if (batch > 65535 || heads > 65535 || batch * kv_heads > 65535) {
-    set_error("%s: batch %lld x heads %lld beyond the launch grid (65535 heads, batch x kv_heads): call in chunks", who, (long long)batch,
-              (long long)heads);
-    return LQER_E_UNSUPPORTED;
-  }
-  if (batch == 0 || S == 0) return 1;
-  if (T == 0) {
-    set_error("%s: T = 0 (a softmax over no keys)", who);
-    return LQER_E_INVALID;
-  }
-  if (!q || (!kv && (!k || !v)) || !out || !workspace) {
-    set_error("%s: null pointer", who);
-    return LQER_E_INVALID;
-  }
-  if (kv && (uintptr_t)workspace % 16 != 0) {
-    set_error("%s: workspace %p is not 16-byte aligned", who, workspace);
-    return LQER_E_INVALID;
-  }
-  const size_t need = attention_q_workspace_bytes(batch, kv_heads, T, D);
-  if (workspace_bytes < need) {
-    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, workspace_bytes, need, who);
-    return LQER_E_INVALID;
-  }
-  return LQER_OK;
-}
-
-int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                     int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
-                     const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
-                     const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                     size_t workspace_bytes, void* stream) {
-  const int rc = attn_q_check("attention_q", false, q, k, v, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides,
-                              mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
-  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
-  return attention_q_dispatch(q, k, v, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides, mask_strides,
-                              out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
-                              (hipStream_t)stream);
-}
-
 size_t lqer_attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D) {
   if (batch <= 0 || heads <= 0 || kv_heads <= 0 || S <= 0 || T <= 0 || D <= 0) return 0;
   return attention_q_decode_workspace_bytes(batch, heads, S, T, D);
 }
 
-// the checks lqer_attention_q_decode and lqer_attention_q_decode_kv share (kv: K and V come from the packed cache - no k, v, strides):
-// LQER_OK = go on, 1 = nothing to do, else the refusal
-static int attn_decode_check(const char* who, bool kv, const void* q, const void* k, const void* v, const void* mask, void* out, int dtype,
-                             int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
-                             const int64_t* k_strides, const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, int causal,
-                             const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                             size_t workspace_bytes) {
-  if (batch < 0 || heads <= 0 || kv_heads <= 0 || S < 0 || T < 0 || D <= 0) {
-    set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)batch, (long long)heads,
-              (long long)kv_heads, (long long)S, (long long)T, (long long)D);
+// What the one check asks on behalf of the kernel that will run: everything in which the prefill kernel (attn_q.hip) and the split over
+// the keys (attn_decode.hip) differ.
+struct AttnKernel {
+  int max_s;          // query rows taken; 0 = any
+  const char* takes;  // the head-dim message's words for what runs
+  int (*grid_limits)(const char* who, const AttnCall& c);  // S, T, batch and heads against the launch grids: LQER_OK or the refusal
+  bool ws_al16_raw;   // the workspace must be 16-byte aligned with raw K and V too (with a cache it always must)
+  size_t (*workspace_bytes)(const AttnCall& c);
+  int (*dispatch)(const AttnCall& c);  // its launches
+};
+
+static int prefill_grid_limits(const char* who, const AttnCall& c) {
+  if (c.T > (int64_t)65535 * 64 || c.S > (int64_t)1 << 30) {  // (the image kernels put T / 64 on a grid dim of 65535; tile indices are 32-bit)
+    set_error("%s: S = %lld / T = %lld beyond the launch grid (T <= 4194240, S <= 2^30)", who, (long long)c.S, (long long)c.T);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (c.batch > 65535 || c.heads > 65535 || c.batch * c.kv_heads > 65535) {
+    set_error("%s: batch %lld x heads %lld beyond the launch grid (65535 heads, batch x kv_heads): call in chunks", who, (long long)c.batch,
+              (long long)c.heads);
+    return LQER_E_UNSUPPORTED;
+  }
+  return LQER_OK;
+}
+
+static int decode_grid_limits(const char* who, const AttnCall& c) {
+  if (c.T > (int64_t)1 << 30) {  // (chunk indices and the fold over them are 32-bit)
+    set_error("%s: T = %lld beyond 2^30 keys", who, (long long)c.T);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (c.batch > 65535 || c.kv_heads > 65535) {
+    set_error("%s: batch %lld / kv_heads %lld beyond the launch grid (65535 each): call in chunks", who, (long long)c.batch,
+              (long long)c.kv_heads);
+    return LQER_E_UNSUPPORTED;
+  }
+  return LQER_OK;
+}
+
+static size_t prefill_workspace_bytes(const AttnCall& c) { return attention_q_workspace_bytes(c.batch, c.kv_heads, c.T, c.D); }
+static size_t decode_workspace_bytes(const AttnCall& c) { return attention_q_decode_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D); }
+
+// (only the cache's image kernels store the prefill workspace in 16-byte pieces; the decode kernels store and load theirs so from any source)
+static const AttnKernel ATTN_PREFILL = {0, "kernel takes", prefill_grid_limits, false, prefill_workspace_bytes,
+                                        attention_q_dispatch};
+static const AttnKernel ATTN_DECODE = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, decode_workspace_bytes,
+                                       attention_q_decode_dispatch};
+
+// the check of the four attention calls, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
+static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) {
+  if (c.batch < 0 || c.heads <= 0 || c.kv_heads <= 0 || c.S < 0 || c.T < 0 || c.D <= 0) {
+    set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)c.batch, (long long)c.heads,
+              (long long)c.kv_heads, (long long)c.S, (long long)c.T, (long long)c.D);
     return LQER_E_INVALID;
   }
-  if (heads % kv_heads != 0) {
-    set_error("%s: heads %lld is not a multiple of kv_heads %lld", who, (long long)heads, (long long)kv_heads);
+  if (c.heads % c.kv_heads != 0) {
+    set_error("%s: heads %lld is not a multiple of kv_heads %lld", who, (long long)c.heads, (long long)c.kv_heads);
     return LQER_E_INVALID;
   }
-  if (dtype != LQER_F32 && dtype != LQER_F16 && dtype != LQER_BF16) {
-    set_error("%s: unknown dtype %d", who, dtype);
+  if (c.dtype != LQER_F32 && c.dtype != LQER_F16 && c.dtype != LQER_BF16) {
+    set_error("%s: unknown dtype %d", who, c.dtype);
     return LQER_E_INVALID;
   }
-  if (!q_strides || (!kv && (!k_strides || !v_strides)) || !out_strides || (mask && !mask_strides)) {
+  if (!c.qs || (!c.packed && (!c.ks || !c.vs)) || !c.os || (c.mask && !c.ms)) {
     set_error("%s: null stride array", who);
     return LQER_E_INVALID;
   }
-  if (mask && causal) {
+  if (c.mask && c.causal) {
     set_error("%s: a mask tensor and causal = 1 are two forms of one mask - pass one", who);
     return LQER_E_INVALID;
   }
-  if (!q_fmt || !k_fmt || !p_fmt || !v_fmt) {
+  if (!c.q_fmt || !c.k_fmt || !c.p_fmt || !c.v_fmt) {
     set_error("%s: null quantizer format", who);
     return LQER_E_INVALID;
   }
-  if (S > attention_q_decode_max_s()) {
-    set_error("%s: S = %lld query rows - the split over the keys takes up to %d (lqer_attention_q takes any)", who, (long long)S,
-              attention_q_decode_max_s());
+  if (kn.max_s && c.S > kn.max_s) {
+    set_error("%s: S = %lld query rows - the split over the keys takes up to %d (lqer_attention_q takes any)", who, (long long)c.S,
+              kn.max_s);
     return LQER_E_UNSUPPORTED;
   }
-  if (D % 16 != 0 || D > 128) {
-    set_error("%s: head dim %lld - the fused kernels take multiples of 16 up to 128 (the two products of lqer_matmul_q take any)", who,
-              (long long)D);
+  if (c.D % 16 != 0 || c.D > 128) {
+    set_error("%s: head dim %lld - the fused %s multiples of 16 up to 128 (the two products of lqer_matmul_q take any)", who, (long long)c.D,
+              kn.takes);
     return LQER_E_UNSUPPORTED;
   }
-  if (!fmt_ok(q_fmt, "attention Q quantizer", 8) || !fmt_ok(k_fmt, "attention K quantizer", 8) || !fmt_ok(p_fmt, "attention P quantizer", 8) ||
-      !fmt_ok(v_fmt, "attention V quantizer", 8))
+  if (!fmt_ok(c.q_fmt, "attention Q quantizer", 8) || !fmt_ok(c.k_fmt, "attention K quantizer", 8) ||
+      !fmt_ok(c.p_fmt, "attention P quantizer", 8) || !fmt_ok(c.v_fmt, "attention V quantizer", 8))
     return LQER_E_UNSUPPORTED;
-  for (const lqer_qfmt_t* f : {q_fmt, k_fmt, p_fmt, v_fmt})
+  for (const lqer_qfmt_t* f : {c.q_fmt, c.k_fmt, c.p_fmt, c.v_fmt})
     if (f->kind != LQER_Q_MXINT || f->block != 16) {
       set_error("%s: the four quantizers must be block_fp with blocks of 16 along the last dim (got kind %d, block %d); other "
                 "formats run as the two products of lqer_matmul_q", who, f->kind, f->block);
       return LQER_E_UNSUPPORTED;
     }
-  if (T > (int64_t)1 << 30) {  // (chunk indices and the fold over them are 32-bit)
-    set_error("%s: T = %lld beyond 2^30 keys", who, (long long)T);
-    return LQER_E_UNSUPPORTED;
-  }
-  if (batch > 65535 || kv_heads > 65535) {
-    set_error("%s: batch %lld / kv_heads %lld beyond the launch grid (65535 each): call in chunks", who, (long long)batch, (long long)kv_heads);
-    return LQER_E_UNSUPPORTED;
-  }
-  if (batch == 0 || S == 0) return 1;
-  if (T == 0) {
+  if (const int rc = kn.grid_limits(who, c)) return rc;
+  if (c.batch == 0 || c.S == 0) return 1;
+  if (c.T == 0) {
     set_error("%s: T = 0 (a softmax over no keys)", who);
     return LQER_E_INVALID;
   }
-  if (!q || (!kv && (!k || !v)) || !out || !workspace) {
+  if (!c.q || (!c.packed && (!c.k || !c.v)) || !c.out || !c.workspace) {
     set_error("%s: null pointer", who);
     return LQER_E_INVALID;
   }
-  if ((uintptr_t)workspace % 16 != 0) {  // (the kernels store and load the workspace in 16-byte pieces)
-    set_error("%s: workspace %p is not 16-byte aligned", who, workspace);
+  if ((c.packed || kn.ws_al16_raw) && (uintptr_t)c.workspace % 16 != 0) {
+    set_error("%s: workspace %p is not 16-byte aligned", who, c.workspace);
     return LQER_E_INVALID;
   }
-  const size_t need = attention_q_decode_workspace_bytes(batch, heads, S, T, D);
-  if (workspace_bytes < need) {
-    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, workspace_bytes, need, who);
+  const size_t need = kn.workspace_bytes(c);
+  if (c.workspace_bytes < need) {
+    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need, who);
     return LQER_E_INVALID;
   }
   return LQER_OK;
-}
-
-int lqer_attention_q_decode(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                            int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
-                            const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
-                            const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-  const int rc = attn_decode_check("attention_q_decode", false, q, k, v, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides,
-                                   v_strides, mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
-  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
-  return attention_q_decode_dispatch(q, k, v, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, k_strides, v_strides,
-                                     mask_strides, out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt),
-                                     make_qp(*v_fmt), workspace, (hipStream_t)stream);
 }
 
 // ---- the packed KV cache (kv_pack.h, kv_cache.hip) ----
@@ -1368,23 +1299,64 @@ size_t lqer_attention_q_decode_kv_workspace_bytes(int64_t batch, int64_t heads, 
   return lqer_attention_q_decode_workspace_bytes(batch, heads, kv_heads, S, T, D);
 }
 
+size_t lqer_attention_q_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D) {
+  return lqer_attention_q_workspace_bytes(batch, heads, kv_heads, S, T, D);
+}
+
+// the check for the kernel that will run, the cache's check where K and V come from one, the launches
+static int attn_run(const char* who, const AttnKernel& kn, const AttnCall& c) {
+  int rc = attn_check(who, kn, c);
+  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
+  if (c.packed) {
+    rc = kv_cache_check(who, c.cache, c.cache_bytes, c.dtype, c.batch, c.kv_heads, c.capacity, c.D, c.T, c.k_fmt, c.v_fmt);
+    if (rc != LQER_OK) return rc;
+  }
+  return kn.dispatch(c);
+}
+
+int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                     int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
+                     const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                     const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  AttnCall c = {};
+  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
+  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
+  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
+  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  c.k = k, c.v = v, c.ks = k_strides, c.vs = v_strides;
+  return attn_run("attention_q", ATTN_PREFILL, c);
+}
+
+int lqer_attention_q_decode(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                            int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
+                            const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                            const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  AttnCall c = {};
+  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
+  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
+  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
+  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  c.k = k, c.v = v, c.ks = k_strides, c.vs = v_strides;
+  return attn_run("attention_q_decode", ATTN_DECODE, c);
+}
+
 int lqer_attention_q_decode_kv(const void* q, const void* cache, size_t cache_bytes, int64_t capacity, const void* mask, void* out, float* row_stats,
                                int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides,
                                const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                                const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  int rc = attn_decode_check("attention_q_decode_kv", true, q, nullptr, nullptr, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides,
-                             nullptr, nullptr, mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
-  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
-  rc = kv_cache_check("attention_q_decode_kv", cache, cache_bytes, dtype, batch, kv_heads, capacity, D, T, k_fmt, v_fmt);
-  if (rc != LQER_OK) return rc;
-  return attention_q_decode_kv_dispatch(q, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides,
-                                        out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
-                                        (hipStream_t)stream);
-}
-
-size_t lqer_attention_q_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D) {
-  return lqer_attention_q_workspace_bytes(batch, heads, kv_heads, S, T, D);
+  AttnCall c = {};
+  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
+  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
+  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
+  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  c.packed = true, c.cache = cache, c.cache_bytes = cache_bytes, c.capacity = capacity;
+  return attn_run("attention_q_decode_kv", ATTN_DECODE, c);
 }
 
 int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, int64_t capacity, const void* mask, void* out, float* row_stats,
@@ -1392,14 +1364,14 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
                         const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  int rc = attn_q_check("attention_q_kv", true, q, nullptr, nullptr, mask, out, dtype, batch, heads, kv_heads, S, T, D, q_strides, nullptr, nullptr,
-                        mask_strides, out_strides, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes);
-  if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
-  rc = kv_cache_check("attention_q_kv", cache, cache_bytes, dtype, batch, kv_heads, capacity, D, T, k_fmt, v_fmt);
-  if (rc != LQER_OK) return rc;
-  return attention_q_kv_dispatch(q, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides,
-                                 out_strides, scaling, causal, make_qp(*q_fmt), make_qp(*k_fmt), make_qp(*p_fmt), make_qp(*v_fmt), workspace,
-                                 (hipStream_t)stream);
+  AttnCall c = {};
+  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
+  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
+  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
+  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  c.packed = true, c.cache = cache, c.cache_bytes = cache_bytes, c.capacity = capacity;
+  return attn_run("attention_q_kv", ATTN_PREFILL, c);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

@@ -326,16 +326,7 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
 }
 
 template <int DT, bool PK>
-static int launch_decode(DArgs a, int64_t batch, hipStream_t st) {
-  const int esz = DT == LQER_F32 ? 4 : 2;
-  auto al16 = [&](const void* p, int64_t s0, int64_t s1, int64_t s2) {
-    return ((uintptr_t)p % 16 == 0) && (s0 * esz) % 16 == 0 && (s1 * esz) % 16 == 0 && (s2 * esz) % 16 == 0;
-  };
-  a.qvec = al16(a.q, a.q_bs, a.q_hs, a.q_rs);
-  if constexpr (!PK) {
-    a.kvec = al16(a.k, a.k_bs, a.k_hs, a.k_rs);
-    a.vvec = al16(a.v, a.v_bs, a.v_hs, a.v_rs);
-  }
+static int launch_decode(const DArgs& a, int64_t batch, hipStream_t st) {
   const dim3 grid((unsigned)a.nch, (unsigned)a.kv_heads, (unsigned)batch);
   k_attn_dec_scores<DT, PK><<<grid, 256, 0, st>>>(a);
   k_attn_dec_pv<DT, PK><<<grid, 256, 0, st>>>(a);
@@ -356,55 +347,36 @@ size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t 
   return dec_align((size_t)(rows * nch * C) * 4) + dec_align((size_t)(rows * nch * 2) * 4) + dec_align((size_t)(rows * nch * D) * 4);
 }
 
-// `cache` == nullptr: K and V are the caller's tensors; else the packed cache of `capacity` keys (kv_pack.h) and k, v, ks, vs unused
-static int decode_dispatch(const void* q, const void* k, const void* v, const void* cache, int64_t capacity, const void* mask, void* out,
-                           float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D,
-                           const int64_t* qs, const int64_t* ks, const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal,
-                           const QP& q_x0, const QP& q_w0, const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st) {
+int attention_q_decode_dispatch(const AttnCall& c) {
   attn::DArgs a;
-  a.q = q, a.k = k, a.v = v, a.mask = mask, a.out = out, a.stats = row_stats;
-  a.S = S, a.T = T, a.D = D;
-  a.C = attn::dec_chunk(T, D), a.nch = (int)((T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
-  a.rep = (int)(heads / kv_heads), a.R = a.rep * S, a.rows = batch * heads * S;
-  unsigned char* ws = (unsigned char*)workspace;
+  a.q = c.q, a.k = c.k, a.v = c.v, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
+  a.S = c.S, a.T = c.T, a.D = c.D;
+  a.C = attn::dec_chunk(c.T, c.D), a.nch = (int)((c.T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
+  a.rep = (int)(c.heads / c.kv_heads), a.R = a.rep * c.S, a.rows = c.batch * c.heads * c.S;
+  unsigned char* ws = (unsigned char*)c.workspace;
   a.s2 = (float*)ws;
   ws += dec_align((size_t)(a.rows * a.Tp) * 4);
   a.cst = (float*)ws;
   ws += dec_align((size_t)(a.rows * a.nch * 2) * 4);
   a.part = (float*)ws;
-  a.q_bs = qs[0], a.q_hs = qs[1], a.q_rs = qs[2];
-  a.k_bs = ks ? ks[0] : 0, a.k_hs = ks ? ks[1] : 0, a.k_rs = ks ? ks[2] : 0;
-  a.v_bs = vs ? vs[0] : 0, a.v_hs = vs ? vs[1] : 0, a.v_rs = vs ? vs[2] : 0;
-  a.m_bs = mask ? ms[0] : 0, a.m_hs = mask ? ms[1] : 0, a.m_rs = mask ? ms[2] : 0;
-  a.o_bs = os[0], a.o_hs = os[1], a.o_rs = os[2];
-  a.heads = (int)heads, a.kv_heads = (int)kv_heads, a.mode = causal ? 2 : (mask ? 1 : 0);
-  a.scaling = scaling;
-  a.q0 = q_x0, a.qk = q_w0, a.q1 = q_x1, a.qv = q_w1;
-  a.qvec = a.kvec = a.vvec = false;
-  a.kc = a.ke = a.vc = a.ve = nullptr, a.cap = 0;
-  if (cache) {
-    const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
-    const unsigned char* base = (const unsigned char*)cache;
-    a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.cap = l.cap;
-    return with_dtype(dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, true>(a, batch, st); });
+  const int esz = c.dtype == LQER_F32 ? 4 : 2;
+  a.q_bs = c.qs[0], a.q_hs = c.qs[1], a.q_rs = c.qs[2];
+  a.m_bs = c.mask ? c.ms[0] : 0, a.m_hs = c.mask ? c.ms[1] : 0, a.m_rs = c.mask ? c.ms[2] : 0;
+  a.o_bs = c.os[0], a.o_hs = c.os[1], a.o_rs = c.os[2];
+  a.heads = (int)c.heads, a.kv_heads = (int)c.kv_heads, a.mode = c.causal ? 2 : (c.mask ? 1 : 0);
+  a.scaling = c.scaling;
+  a.q0 = make_qp(*c.q_fmt), a.qk = make_qp(*c.k_fmt), a.q1 = make_qp(*c.p_fmt), a.qv = make_qp(*c.v_fmt);
+  a.qvec = al16(c.q, c.qs, esz);
+  if (c.packed) {  // the packed source: no k, v or their strides
+    const auto s = kvc::sections((const unsigned char*)c.cache, kvc::layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
+    a.k = a.v = nullptr, a.k_bs = a.k_hs = a.k_rs = a.v_bs = a.v_hs = a.v_rs = 0, a.kvec = a.vvec = false;
+    a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve, a.cap = s.cap;
+    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, true>(a, c.batch, c.st); });
   }
-  return with_dtype(dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, false>(a, batch, st); });
-}
-
-int attention_q_decode_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                                int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks,
-                                const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0,
-                                const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st) {
-  return decode_dispatch(q, k, v, nullptr, 0, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, qs, ks, vs, ms, os, scaling, causal, q_x0,
-                         q_w0, q_x1, q_w1, workspace, st);
-}
-
-int attention_q_decode_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
-                                   int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs,
-                                   const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
-                                   const QP& q_w1, void* workspace, hipStream_t st) {
-  return decode_dispatch(q, nullptr, nullptr, cache, capacity, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, qs, nullptr, nullptr, ms,
-                         os, scaling, causal, q_x0, q_w0, q_x1, q_w1, workspace, st);
+  a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
+  a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
+  a.kc = a.ke = a.vc = a.ve = nullptr, a.cap = 0;
+  return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, false>(a, c.batch, c.st); });
 }
 
 }  // namespace lqer

@@ -293,34 +293,29 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
 }
 
-// k == nullptr: the two images are already on their way on `st` (attention_q_kv_dispatch: written from the packed KV cache)
+// with a cache the two images are already on their way on c.st (kv_cache_images_dispatch: written from the packed KV cache)
 template <int DT>
-static int launch(const void* q, const void* k, const void* v, Args a, const QP& qk, const QP& qv, const int64_t (&ks)[3], const int64_t (&vs)[3],
-                  int64_t batch, hipStream_t st, const char* who) {
+static int launch(const AttnCall& c, Args a) {
   const int esz = DT == LQER_F32 ? 4 : 2;
-  auto al16 = [&](const void* p, const int64_t (&s)[3]) {
-    return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
-  };
-  if (k) {
-    const unsigned nz = (unsigned)(batch * a.kv_heads);
-    k_attn_kimage<DT><<<dim3((unsigned)(a.Dp / 64), (unsigned)(a.Tp / 64), nz), 256, 0, st>>>(k, a.D, a.T, ks[0], ks[1], ks[2], a.kv_heads, qk,
-                                                                                          (bf16_t*)a.kimg, a.Tp, a.Dp, al16(k, ks));
-    k_attn_vimage<DT><<<dim3((unsigned)(VD / 64), (unsigned)(a.Tv / 64), nz), 256, 0, st>>>(v, a.D, a.T, vs[0], vs[1], vs[2], a.kv_heads, qv,
-                                                                                        (bf16_t*)a.vimg, a.Tv, al16(v, vs));
+  if (!c.packed) {
+    const unsigned nz = (unsigned)(c.batch * a.kv_heads);
+    k_attn_kimage<DT><<<dim3((unsigned)(a.Dp / 64), (unsigned)(a.Tp / 64), nz), 256, 0, c.st>>>(
+        c.k, a.D, a.T, c.ks[0], c.ks[1], c.ks[2], a.kv_heads, make_qp(*c.k_fmt), (bf16_t*)a.kimg, a.Tp, a.Dp, al16(c.k, c.ks, esz));
+    k_attn_vimage<DT><<<dim3((unsigned)(VD / 64), (unsigned)(a.Tv / 64), nz), 256, 0, c.st>>>(
+        c.v, a.D, a.T, c.vs[0], c.vs[1], c.vs[2], a.kv_heads, make_qp(*c.v_fmt), (bf16_t*)a.vimg, a.Tv, al16(c.v, c.vs, esz));
   }
-  const int64_t qs[3] = {a.q_bs, a.q_hs, a.q_rs};
-  a.qvec = al16(q, qs);
+  a.qvec = al16(c.q, c.qs, esz);
   // the mask is read in groups of four elements: rows and pointer aligned to that, and T a multiple of four
   a.mvec = a.mode == 1 && a.T % 4 == 0 && (uintptr_t)a.mask % (4 * esz) == 0 && a.m_bs % 4 == 0 && a.m_hs % 4 == 0 && a.m_rs % 4 == 0;
-  const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)batch);
+  const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)c.batch);
   const int dk = (int)((a.D + 31) / 32);
   switch (dk) {
-    case 1: k_attn_q<DT, 1><<<grid, 64 * NW, 0, st>>>(a); break;
-    case 2: k_attn_q<DT, 2><<<grid, 64 * NW, 0, st>>>(a); break;
-    case 3: k_attn_q<DT, 3><<<grid, 64 * NW, 0, st>>>(a); break;
-    default: k_attn_q<DT, 4><<<grid, 64 * NW, 0, st>>>(a); break;
+    case 1: k_attn_q<DT, 1><<<grid, 64 * NW, 0, c.st>>>(a); break;
+    case 2: k_attn_q<DT, 2><<<grid, 64 * NW, 0, c.st>>>(a); break;
+    case 3: k_attn_q<DT, 3><<<grid, 64 * NW, 0, c.st>>>(a); break;
+    default: k_attn_q<DT, 4><<<grid, 64 * NW, 0, c.st>>>(a); break;
   }
-  return check_launch(who);
+  return check_launch(c.packed ? "lqer_attention_q_kv" : "lqer_attention_q");
 }
 
 }  // namespace attn
@@ -336,46 +331,24 @@ size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, i
   return attn_align((size_t)(batch * kv_heads * Tp * Dp) * sizeof(bf16_t)) + attn_align((size_t)(batch * kv_heads * attn::VD * Tv) * sizeof(bf16_t));
 }
 
-// what k_attn_q needs but for qvec / mvec (attn::launch sets them): the two images at their places in the workspace
-static attn::Args attn_args(const void* q, const void* mask, void* out, float* row_stats, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S,
-                            int64_t T, int64_t D, const int64_t* qs, const int64_t* ms, const int64_t* os, float scaling, int causal,
-                            const QP& q_x0, const QP& q_x1, void* workspace) {
+// the two images at their places in the workspace - from the raw K and V (attn::launch) or from the packed KV cache's codes
+// (kv_cache.hip) - then k_attn_q on them
+int attention_q_dispatch(const AttnCall& c) {
   attn::Args a;
-  a.q = q, a.mask = mask, a.out = out, a.stats = row_stats;
-  a.S = S, a.T = T, a.D = D;
-  attn_dims(T, D, &a.Tp, &a.Dp, &a.Tv);
-  a.kimg = (const bf16_t*)workspace;
-  a.vimg = (const bf16_t*)((const unsigned char*)workspace + attn_align((size_t)(batch * kv_heads * a.Tp * a.Dp) * sizeof(bf16_t)));
-  a.q_bs = qs[0], a.q_hs = qs[1], a.q_rs = qs[2];
-  a.m_bs = mask ? ms[0] : 0, a.m_hs = mask ? ms[1] : 0, a.m_rs = mask ? ms[2] : 0;
-  a.o_bs = os[0], a.o_hs = os[1], a.o_rs = os[2];
-  a.heads = (int)heads, a.kv_heads = (int)kv_heads, a.mode = causal ? 2 : (mask ? 1 : 0);
-  a.scaling = scaling;
-  a.q0 = q_x0, a.q1 = q_x1;
-  a.qvec = a.mvec = false;
-  return a;
-}
-
-int attention_q_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                         int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks, const int64_t* vs,
-                         const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
-                         const QP& q_w1, void* workspace, hipStream_t st) {
-  const attn::Args a = attn_args(q, mask, out, row_stats, batch, heads, kv_heads, S, T, D, qs, ms, os, scaling, causal, q_x0, q_x1, workspace);
-  const int64_t k3[3] = {ks[0], ks[1], ks[2]}, v3[3] = {vs[0], vs[1], vs[2]};
-  return with_dtype(dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(q, k, v, a, q_w0, q_w1, k3, v3, batch, st, "lqer_attention_q"); });
-}
-
-// the same attention with the two images written from the packed KV cache's codes (kv_cache.hip) instead of the raw K and V
-int attention_q_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
-                            int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ms,
-                            const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1, const QP& q_w1,
-                            void* workspace, hipStream_t st) {
-  const attn::Args a = attn_args(q, mask, out, row_stats, batch, heads, kv_heads, S, T, D, qs, ms, os, scaling, causal, q_x0, q_x1, workspace);
-  kv_cache_images_dispatch(cache, dtype, batch, kv_heads, capacity, D, T, q_w0, q_w1, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv, st);
-  const int64_t none[3] = {0, 0, 0};
-  return with_dtype(dtype, [&](auto dt) {
-    return attn::launch<decltype(dt)::value>(q, nullptr, nullptr, a, q_w0, q_w1, none, none, batch, st, "lqer_attention_q_kv");
-  });
+  a.q = c.q, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
+  a.S = c.S, a.T = c.T, a.D = c.D;
+  attn_dims(c.T, c.D, &a.Tp, &a.Dp, &a.Tv);
+  a.kimg = (const bf16_t*)c.workspace;
+  a.vimg = (const bf16_t*)((const unsigned char*)c.workspace + attn_align((size_t)(c.batch * c.kv_heads * a.Tp * a.Dp) * sizeof(bf16_t)));
+  a.q_bs = c.qs[0], a.q_hs = c.qs[1], a.q_rs = c.qs[2];
+  a.m_bs = c.mask ? c.ms[0] : 0, a.m_hs = c.mask ? c.ms[1] : 0, a.m_rs = c.mask ? c.ms[2] : 0;
+  a.o_bs = c.os[0], a.o_hs = c.os[1], a.o_rs = c.os[2];
+  a.heads = (int)c.heads, a.kv_heads = (int)c.kv_heads, a.mode = c.causal ? 2 : (c.mask ? 1 : 0);
+  a.scaling = c.scaling;
+  a.q0 = make_qp(*c.q_fmt), a.q1 = make_qp(*c.p_fmt);
+  a.qvec = a.mvec = false;  // (attn::launch sets them)
+  if (c.packed) kv_cache_images_dispatch(c, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv);
+  return with_dtype(c.dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(c, a); });
 }
 
 }  // namespace lqer

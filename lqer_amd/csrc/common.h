@@ -751,36 +751,46 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
 
 size_t qmatmul_workspace_bytes(int64_t batch, int64_t K, int64_t S2);  // matmul_q.hip
 size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t S2, bool x_pre, bool y_pre);
+// One attention call as the C ABI receives it: what lqer_attention_q, _decode, _decode_kv and _kv fill, their one check reads and the
+// two dispatch functions launch from.  Host only - never a kernel argument.  `packed`: K and V come from the packed KV cache of
+// `capacity` keys (kv_pack.h) and k, v, ks, vs are unused; a flag of its own because a null `cache` is the cache's check to refuse, in
+// its words.  The dispatch functions read `packed` alone; past the checks it implies cache != nullptr.  The stride triples are the
+// caller's pointers: the check must see a null one.
+struct AttnCall {
+  bool packed;
+  const void *q, *k, *v, *cache, *mask;
+  void* out;
+  float* row_stats;
+  size_t cache_bytes;
+  int64_t capacity;
+  int dtype;
+  int64_t batch, heads, kv_heads, S, T, D;
+  const int64_t *qs, *ks, *vs, *ms, *os;  // elements over batch / head / row (ms: only with a mask)
+  float scaling;
+  int causal;
+  const lqer_qfmt_t *q_fmt, *k_fmt, *p_fmt, *v_fmt;  // Q_x0, Q_w0, Q_x1, Q_w1
+  void* workspace;
+  size_t workspace_bytes;
+  hipStream_t st;
+};
+// a tensor whose pointer and three strides (elements of esz bytes) are multiples of 16 bytes: its rows load in 16-byte pieces
+__host__ inline bool al16(const void* p, const int64_t* s, int esz) {
+  return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
+}
 size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, int64_t D);  // attn_q.hip
-int attention_q_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                         int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks, const int64_t* vs,
-                         const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
-                         const QP& q_w1, void* workspace, hipStream_t st);
+int attention_q_dispatch(const AttnCall& c);  // (with a cache: kv_cache.hip writes the two images from the codes, k_attn_q runs on them)
 // attn_decode.hip: the same attention for 1 <= S <= attention_q_decode_max_s() query rows, split over the keys
 int attention_q_decode_max_s();
 size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D);
-int attention_q_decode_dispatch(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                                int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ks,
-                                const int64_t* vs, const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0,
-                                const QP& q_x1, const QP& q_w1, void* workspace, hipStream_t st);
-// ... with K and V read from the packed KV cache (kv_pack.h; kv_cache.hip writes it)
-int attention_q_decode_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
-                                   int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs,
-                                   const int64_t* ms, const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1,
-                                   const QP& q_w1, void* workspace, hipStream_t st);
+int attention_q_decode_dispatch(const AttnCall& c);  // (with a cache: the kernels read its codes, kv_pack.h)
 size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D);  // kv_cache.hip
 int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int dtype, int64_t batch,
                              int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const QP& qk, const QP& qv, hipStream_t st);
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
                              const QP& qv, float* k_f32, float* v_f32, hipStream_t st);
-// ... and the prefill kernel over the packed KV cache: kv_cache.hip writes the two images from the codes, attn_q.hip runs k_attn_q on them
 constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128
-void kv_cache_images_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
-                              const QP& qv, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv, hipStream_t st);
-int attention_q_kv_dispatch(const void* q, const void* cache, int64_t capacity, const void* mask, void* out, float* row_stats, int dtype,
-                            int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* qs, const int64_t* ms,
-                            const int64_t* os, float scaling, int causal, const QP& q_x0, const QP& q_w0, const QP& q_x1, const QP& q_w1,
-                            void* workspace, hipStream_t st);
+// the two images of lqer_attention_q's workspace from the first T keys of c's cache; the caller (attn_q.hip) checks the launches
+void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv);
 int qmatmul_dispatch(const void* x, const void* y, void* out, int dtype, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs,
                      int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, void* workspace, hipStream_t st);
 

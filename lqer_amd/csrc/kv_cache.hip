@@ -198,21 +198,18 @@ size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capaci
 int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int dtype, int64_t batch,
                              int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const QP& qk, const QP& qv, hipStream_t st) {
   const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
-  unsigned char* base = (unsigned char*)cache;
+  const auto s = kvc::sections((unsigned char*)cache, l);
   kvc::AArgs a;
-  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.stage = base + l.k_stage;
+  a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve, a.stage = (unsigned char*)cache + l.k_stage;
   a.kn = k_new, a.vn = v_new;
-  a.Z = batch * kv_heads, a.kvh = kv_heads, a.cap = l.cap, a.D = D, a.len = len, a.n = n;
+  a.Z = batch * kv_heads, a.kvh = kv_heads, a.cap = s.cap, a.D = D, a.len = len, a.n = n;
   a.k_bs = ks[0], a.k_hs = ks[1], a.k_rs = ks[2], a.v_bs = vs[0], a.v_hs = vs[1], a.v_rs = vs[2];
   a.kb0 = len / 16, a.nkb = (len + n - 1) / 16 - a.kb0 + 1;
   const int64_t open0 = (len + n) / 16 * 16;  // first key of the block left open
   a.s0 = open0 > len ? open0 : len, a.ns = len + n - a.s0;
   a.qk = qk, a.qv = qv;
   const int esz = dtype == LQER_F32 ? 4 : 2;
-  auto al16 = [&](const void* p, const int64_t* s) {
-    return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
-  };
-  a.kvec = al16(k_new, ks), a.vvec = al16(v_new, vs);
+  a.kvec = al16(k_new, ks, esz), a.vvec = al16(v_new, vs, esz);
   // staging rows read: 0 .. len % 16 - 1; written: (t % 16) of keys s0 .. len + n - 1 - apart when the new keys stay in the open block
   const bool one = len % 16 == 0 || a.s0 == len || a.ns == 0;
   const int64_t n1 = a.Z * (a.nkb * (D / 4) + n * (D / 16)), n2 = a.Z * a.ns * (D / 4);
@@ -231,26 +228,24 @@ int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, 
 
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
                              const QP& qv, float* k_f32, float* v_f32, hipStream_t st) {
-  const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
-  const unsigned char* base = (const unsigned char*)cache;
+  const auto s = kvc::sections((const unsigned char*)cache, kvc::layout(dtype, batch, kv_heads, capacity, D));
   kvc::UArgs a;
-  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps;
-  a.kf = k_f32, a.vf = v_f32, a.Z = batch * kv_heads, a.cap = l.cap, a.T = T, a.D = D, a.qk = qk, a.qv = qv;
+  a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve;
+  a.kf = k_f32, a.vf = v_f32, a.Z = batch * kv_heads, a.cap = s.cap, a.T = T, a.D = D, a.qk = qk, a.qv = qv;
   kvc::k_kv_unpack<<<dim3((unsigned)((a.Z * T * D + 255) / 256)), 256, 0, st>>>(a);
   return check_launch("lqer_kv_cache_unpack");
 }
 
 // the two images of lqer_attention_q's workspace from the cache's first T keys; the caller (attn_q.hip) checks the launches
-void kv_cache_images_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
-                              const QP& qv, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv, hipStream_t st) {
-  const kvc::Layout l = kvc::layout(dtype, batch, kv_heads, capacity, D);
-  const unsigned char* base = (const unsigned char*)cache;
+void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv) {
+  const auto s = kvc::sections((const unsigned char*)c.cache, kvc::layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
   kvc::IArgs a;
-  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps;
-  a.kimg = kimg, a.vimg = vimg, a.cap = l.cap, a.D = D, a.T = T, a.Tp = Tp, a.Dp = Dp, a.Tv = Tv, a.qk = qk, a.qv = qv;
-  const unsigned nz = (unsigned)(batch * kv_heads);
-  kvc::k_kv_kimage<<<dim3((unsigned)(Tp * (Dp / 16) / 256), nz), 256, 0, st>>>(a);
-  kvc::k_kv_vimage<<<dim3((unsigned)(Tv / 64), nz), 128, 0, st>>>(a);
+  a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve;
+  a.kimg = kimg, a.vimg = vimg, a.cap = s.cap, a.D = c.D, a.T = c.T, a.Tp = Tp, a.Dp = Dp, a.Tv = Tv;
+  a.qk = make_qp(*c.k_fmt), a.qv = make_qp(*c.v_fmt);
+  const unsigned nz = (unsigned)(c.batch * c.kv_heads);
+  kvc::k_kv_kimage<<<dim3((unsigned)(Tp * (Dp / 16) / 256), nz), 256, 0, c.st>>>(a);
+  kvc::k_kv_vimage<<<dim3((unsigned)(Tv / 64), nz), 128, 0, c.st>>>(a);
 }
 
 }  // namespace lqer

@@ -36,6 +36,16 @@ __host__ inline Layout layout(int dtype, int64_t batch, int64_t kv_heads, int64_
   return l;
 }
 
+template <class B>  // unsigned char for the writer (append), const unsigned char for the readers
+struct Sections {    // the four sections a kernel reads or writes, and the keys each (batch, kv head) has room for
+  B *kc, *ke, *vc, *ve;
+  int64_t cap;
+};
+template <class B>
+__host__ inline Sections<B> sections(B* base, const Layout& l) {
+  return {base + l.k_codes, base + l.k_exps, base + l.v_codes, base + l.v_exps, l.cap};
+}
+
 // one block of 16 -> 16 codes (four dwords, element i in byte i) and the exponent byte: quant16_bf16's decisions and arithmetic,
 // stopped before the final scaling (the fast path: mxint16_bf16_fast's r; the other: mxint_mantissa)
 template <bool FLUSH_TINY>

@@ -151,6 +151,13 @@ def _attn_fmts(cfg0: dict, cfg1: dict):
     return fmts
 
 
+def _mask_ok(m, q, t: int) -> bool:
+    """A mask the fused kernels read: additive, [b|1, h|1, s|1, t] of q's dtype on q's device, dense along t."""
+    b, h, s, _ = q.shape
+    return (m.dim() == 4 and m.dtype == q.dtype and m.device == q.device and m.shape[3] == t and (m.stride(3) == 1 or t == 1)
+            and m.shape[0] in (1, b) and m.shape[1] in (1, h) and m.shape[2] in (1, s))
+
+
 def _attention_route(q, k, v, cfg0, cfg1, attention_mask=None, causal=False):
     """(route tag, formats): which route attention_flexible takes for these operands."""
     if not (q.dim() == k.dim() == v.dim() == 4) or not (q.is_cuda and k.is_cuda and v.is_cuda):
@@ -163,9 +170,7 @@ def _attention_route(q, k, v, cfg0, cfg1, attention_mask=None, causal=False):
           and b <= _MAX_GRID_Z and h <= _MAX_GRID_Z and b * hk <= _MAX_GRID_Z
           and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1)
     if ok and attention_mask is not None:
-        m = attention_mask
-        ok = (not causal and m.dim() == 4 and m.dtype == q.dtype and m.device == q.device and m.shape[3] == t and (m.stride(3) == 1 or t == 1)
-              and m.shape[0] in (1, b) and m.shape[1] in (1, h) and m.shape[2] in (1, s))
+        ok = not causal and _mask_ok(attention_mask, q, t)
     if not ok:
         return ROUTE_UNFUSED, None
     fmts = _attn_fmts(cfg0, cfg1)
@@ -200,12 +205,23 @@ def _decode_rule(b: int, hk: int, t: int):
     return KERNEL_DECODE
 
 
+def _check_kernel_arg(kernel) -> None:
+    if kernel not in (None, KERNEL_PREFILL, KERNEL_DECODE):
+        raise ValueError(f"kernel {kernel!r}: None, 'prefill' or 'decode'")
+
+
+def _check_layout_and_mask(who: str, out_layout, attention_mask, causal) -> None:
+    if out_layout not in ("bhsd", "bshd"):
+        raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
+    if attention_mask is not None and causal:
+        raise ValueError(f"{who}: attention_mask and causal=True are two forms of one mask - pass one")
+
+
 def _attention_kernel(q, k, v, cfg0, cfg1, attention_mask=None, causal=False, kernel=None):
     """(kernel name or None for the unfused route, formats).  kernel=None: up to 8 query rows take the decode kernel - or, where
     tools/attn_decode_bench.py measured another leg faster, that leg (_decode_rule) -, more take the prefill kernel;
     "prefill" / "decode" force one and raise where it does not apply."""
-    if kernel not in (None, KERNEL_PREFILL, KERNEL_DECODE):
-        raise ValueError(f"kernel {kernel!r}: None, 'prefill' or 'decode'")
+    _check_kernel_arg(kernel)
     route, fmts = _attention_route(q, k, v, cfg0, cfg1, attention_mask, causal)
     if route != ROUTE_FUSED:
         if kernel is not None:
@@ -250,8 +266,50 @@ def _causal_mask(s, t, dtype, device):
     return torch.zeros(s, t, dtype=dtype, device=device).masked_fill_(j > i + (t - s), torch.finfo(dtype).min)[None, None]
 
 
-def _bcast_stride(m: torch.Tensor, dim: int) -> int:
-    return 0 if m.shape[dim] == 1 else m.stride(dim)
+_I64X3 = C.c_int64 * 3
+
+
+def _tri(t: torch.Tensor, bcast: bool = False):
+    """The stride triple (elements over batch / head / row) of a 4-d tensor for the C ABI; bcast: 0 over a dim of size 1 (a mask's)."""
+    st = t.stride()
+    if bcast:
+        sh = t.shape
+        return _I64X3(0 if sh[0] == 1 else st[0], 0 if sh[1] == 1 else st[1], 0 if sh[2] == 1 else st[2])
+    return _I64X3(st[0], st[1], st[2])
+
+
+def _attention_outputs(q, out_layout: str, return_stats: bool):
+    """(out, its [b, h, s, d] view, stats or None) for q [b, h, s, d]: out is [b, s, h, d] with "bshd", written through the view."""
+    b, h, s, d = q.shape
+    out = torch.empty((b, h, s, d) if out_layout == "bhsd" else (b, s, h, d), dtype=q.dtype, device=q.device)
+    stats = torch.empty(b, h, s, 2, dtype=torch.float32, device=q.device) if return_stats else None
+    return out, (out if out_layout == "bhsd" else out.transpose(1, 2)), stats
+
+
+def _attention_call(name: str, q, *, kv=None, cache=None, mask, causal, out, stats, fmts, scaling, ws=None) -> None:
+    """The C attention call `name` (one of the four: one argument list but for the K / V source) on q [b, h, s, d].  The source is
+    kv = (k, v), tensors [b, h_kv, t, d], or cache = (buf, capacity, kv_heads, length) of a packed cache.  mask: the tensor or None;
+    out: a [b, h, s, d] tensor or view; stats: [b, h, s, 2] fp32 or None; ws: a uint8 workspace, or None for the stream's at the size
+    `name`_workspace_bytes asks."""
+    b, h, s, d = q.shape
+    m = mask
+    if cache is None:
+        k, v = kv
+        hk, t = k.shape[1], k.shape[2]
+        src, src_tri = (k.data_ptr(), v.data_ptr()), (_tri(k), _tri(v))
+    else:
+        buf, capacity, hk, t = cache
+        src, src_tri = (buf.data_ptr(), buf.numel(), capacity), ()
+    L = _lib.lib()
+    with torch.cuda.device(q.device):
+        if ws is None:
+            ws = ops.workspace(q.device, max(getattr(L, name + "_workspace_bytes")(b, h, hk, s, t, d), 16))
+        _lib.check(getattr(L, name)(q.data_ptr(), *src, m.data_ptr() if m is not None else None, out.data_ptr(),
+                                    stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, hk, s, t, d, _tri(q), *src_tri,
+                                    _tri(m, bcast=True) if m is not None else None, _tri(out), float(scaling), int(bool(causal)),
+                                    C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
+                                    ops._stream(q.device)),
+                   name)
 
 
 @torch.no_grad()
@@ -270,37 +328,15 @@ def attention_flexible(q, k, v, cfg0, cfg1, scaling, attention_mask=None, causal
     `out_layout`: "bhsd" or "bshd" (what the HuggingFace attention interface returns, written directly).  Returns out, then
     `stats` [b, h, s, 2] fp32 = {row max of the masked scores, row sum of exp(score - max)} with return_stats (fused route only,
     else None), then the route tag with return_route."""
-    if out_layout not in ("bhsd", "bshd"):
-        raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
-    if attention_mask is not None and causal:
-        raise ValueError("attention_flexible: attention_mask and causal=True are two forms of one mask - pass one")
+    _check_layout_and_mask("attention_flexible", out_layout, attention_mask, causal)
     kern, fmts = _attention_kernel(q, k, v, cfg0, cfg1, attention_mask, causal, kernel)  # (validates `kernel`; CPU tensors: no kernel)
     ops._need_gpu(q, k, v, attention_mask)
     route = ROUTE_FUSED if kern is not None else ROUTE_UNFUSED
     stats = None
     if route == ROUTE_FUSED:
-        b, h, s, d = q.shape
-        hk, t = k.shape[1], k.shape[2]
-        out = torch.empty((b, h, s, d) if out_layout == "bhsd" else (b, s, h, d), dtype=q.dtype, device=q.device)
-        ob = out if out_layout == "bhsd" else out.transpose(1, 2)
-        if return_stats:
-            stats = torch.empty(b, h, s, 2, dtype=torch.float32, device=q.device)
-        tri = lambda *xs: (C.c_int64 * 3)(*xs)
-        m = attention_mask
-        L = _lib.lib()
-        name = "lqer_attention_q_decode" if kern == KERNEL_DECODE else "lqer_attention_q"
-        with torch.cuda.device(q.device):
-            nws = getattr(L, name + "_workspace_bytes")(b, h, hk, s, t, d)
-            ws = ops.workspace(q.device, max(nws, 16))
-            _lib.check(getattr(L, name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), m.data_ptr() if m is not None else None, out.data_ptr(),
-                                        stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, hk, s, t, d,
-                                        tri(q.stride(0), q.stride(1), q.stride(2)), tri(k.stride(0), k.stride(1), k.stride(2)),
-                                        tri(v.stride(0), v.stride(1), v.stride(2)),
-                                        tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
-                                        tri(ob.stride(0), ob.stride(1), ob.stride(2)), float(scaling), int(bool(causal)),
-                                        C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
-                                        ops._stream(q.device)),
-                       name)
+        out, ob, stats = _attention_outputs(q, out_layout, return_stats)
+        _attention_call("lqer_attention_q_decode" if kern == KERNEL_DECODE else "lqer_attention_q", q, kv=(k, v), mask=attention_mask, causal=causal,
+                        out=ob, stats=stats, fmts=fmts, scaling=scaling)
     else:
         if causal:
             attention_mask = _causal_mask(q.shape[2], k.shape[2], q.dtype, q.device)

@@ -14,12 +14,8 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from .functional import (KERNEL_DECODE, KERNEL_PREFILL, _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _ATTN_MAX_T, _MAX_GRID_Z, _attn_fmts,
-                         _bcast_stride)
-
-
-def _tri(*xs):
-    return (C.c_int64 * 3)(*xs)
+from .functional import (KERNEL_PREFILL, _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _ATTN_MAX_T, _MAX_GRID_Z, _attention_call, _attention_outputs,
+                         _attn_fmts, _check_kernel_arg, _check_layout_and_mask, _mask_ok, _tri)
 
 
 def cache_bytes(dtype: torch.dtype, batch: int, kv_heads: int, capacity: int, head_dim: int) -> int:
@@ -53,9 +49,8 @@ def append_packed(buf: torch.Tensor, k: torch.Tensor, v: torch.Tensor, length: i
         v = v.contiguous()
     b, hk, n, d = k.shape
     with torch.cuda.device(k.device):
-        _lib.check(_lib.lib().lqer_kv_cache_append(buf.data_ptr(), buf.numel(), k.data_ptr(), v.data_ptr(), _tri(k.stride(0), k.stride(1), k.stride(2)),
-                                                   _tri(v.stride(0), v.stride(1), v.stride(2)), ops.dtype_code(k), b, hk, capacity, d, length, n,
-                                                   C.byref(k_fmt), C.byref(v_fmt), ops._stream(k.device)),
+        _lib.check(_lib.lib().lqer_kv_cache_append(buf.data_ptr(), buf.numel(), k.data_ptr(), v.data_ptr(), _tri(k), _tri(v), ops.dtype_code(k), b, hk,
+                                                   capacity, d, length, n, C.byref(k_fmt), C.byref(v_fmt), ops._stream(k.device)),
                    "lqer_kv_cache_append")
 
 
@@ -72,35 +67,19 @@ def unpack_packed(buf: torch.Tensor, dtype: torch.dtype, batch: int, kv_heads: i
     return kf, vf
 
 
-def _attend(name, q, buf, kv_heads, capacity, length, fmts, scaling, m, causal, out, stats, ws):
-    """The C call `name` (lqer_attention_q_decode_kv / lqer_attention_q_kv: one argument list) with its own workspace function."""
-    b, h, s, d = q.shape
-    L = _lib.lib()
-    with torch.cuda.device(q.device):
-        nws = getattr(L, name + "_workspace_bytes")(b, h, kv_heads, s, length, d)
-        if ws is None:
-            ws = ops.workspace(q.device, max(nws, 16))
-        _lib.check(getattr(L, name)(q.data_ptr(), buf.data_ptr(), buf.numel(), capacity, m.data_ptr() if m is not None else None,
-                                    out.data_ptr(), stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, kv_heads,
-                                    s, length, d, _tri(q.stride(0), q.stride(1), q.stride(2)),
-                                    _tri(_bcast_stride(m, 0), _bcast_stride(m, 1), _bcast_stride(m, 2)) if m is not None else None,
-                                    _tri(out.stride(0), out.stride(1), out.stride(2)), float(scaling), int(bool(causal)),
-                                    C.byref(fmts[0]), C.byref(fmts[1]), C.byref(fmts[2]), C.byref(fmts[3]), ws.data_ptr(), ws.numel(),
-                                    ops._stream(q.device)),
-                   name)
-
-
 @torch.no_grad()
 def attend_packed(q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask=None, causal=False, out=None, stats=None, ws=None):
     """lqer_attention_q_decode_kv on a caller's buffer.  q [b, h, s, d]; out: a [b, h, s, d] tensor or view (any strides over b, h, s);
     stats: [b, h, s, 2] fp32 or None; ws: a uint8 workspace or None (the stream's)."""
-    _attend("lqer_attention_q_decode_kv", q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask, causal, out, stats, ws)
+    _attention_call("lqer_attention_q_decode_kv", q, cache=(buf, capacity, kv_heads, length), mask=attention_mask, causal=causal, out=out, stats=stats,
+                    fmts=fmts, scaling=scaling, ws=ws)
 
 
 @torch.no_grad()
 def prefill_packed(q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask=None, causal=False, out=None, stats=None, ws=None):
     """lqer_attention_q_kv on a caller's buffer: attend_packed's arguments, any number of query rows."""
-    _attend("lqer_attention_q_kv", q, buf, kv_heads, capacity, length, fmts, scaling, attention_mask, causal, out, stats, ws)
+    _attention_call("lqer_attention_q_kv", q, cache=(buf, capacity, kv_heads, length), mask=attention_mask, causal=causal, out=out, stats=stats,
+                    fmts=fmts, scaling=scaling, ws=ws)
 
 
 class QuantizedKVCache:
@@ -187,13 +166,9 @@ def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mas
     kernel="prefill" takes any s >= 1 - a second prompt or a chunk of a long one on a non-empty cache - and gives the bits of
     attention_flexible(..., kernel="prefill"): lqer_attention_q_kv writes the prefill kernel's two images from the codes.  None and
     "decode" are the decode kernel.  Operands the kernels do not take raise ValueError - there is no other route to the cached values."""
-    if kernel not in (None, KERNEL_PREFILL, KERNEL_DECODE):
-        raise ValueError(f"kernel {kernel!r}: None, 'prefill' or 'decode'")
+    _check_kernel_arg(kernel)
     prefill = kernel == KERNEL_PREFILL
-    if out_layout not in ("bhsd", "bshd"):
-        raise ValueError(f"out_layout {out_layout!r}: 'bhsd' or 'bshd'")
-    if attention_mask is not None and causal:
-        raise ValueError("attention_flexible_cached: attention_mask and causal=True are two forms of one mask - pass one")
+    _check_layout_and_mask("attention_flexible_cached", out_layout, attention_mask, causal)
     ops._need_gpu(q, attention_mask)
     if q.dim() != 4:
         raise ValueError(f"attention_flexible_cached: q {tuple(q.shape)} is not [b, h, s, d]")
@@ -206,13 +181,10 @@ def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mas
         raise ValueError(f"attention_flexible_cached: q {tuple(q.shape)} {q.dtype} against a cache of {t} keys [{cache.batch}, {cache.kv_heads}, "
                          f"{cache.head_dim}] {cache.dtype}" + (" (causal with more query rows than keys)" if causal and s > t else ""))
     m = attention_mask
-    if m is not None and not (m.dim() == 4 and m.dtype == q.dtype and m.device == q.device and m.shape[3] == t and (m.stride(3) == 1 or t == 1)
-                              and m.shape[0] in (1, b) and m.shape[1] in (1, h) and m.shape[2] in (1, s)):
+    if m is not None and not _mask_ok(m, q, t):
         raise ValueError(f"attention_flexible_cached: mask {tuple(m.shape)} {m.dtype} - additive, [b|1, h|1, s|1, {t}] of q's dtype, dense along t")
     if q.stride(3) != 1:
         q = q.contiguous()
-    out = torch.empty((b, h, s, d) if out_layout == "bhsd" else (b, s, h, d), dtype=q.dtype, device=q.device)
-    stats = torch.empty(b, h, s, 2, dtype=torch.float32, device=q.device) if return_stats else None
-    (prefill_packed if prefill else attend_packed)(q, cache.buf, cache.kv_heads, cache.capacity, t, cache.fmts, scaling, m, causal,
-                                                   out if out_layout == "bhsd" else out.transpose(1, 2), stats)
+    out, ob, stats = _attention_outputs(q, out_layout, return_stats)
+    (prefill_packed if prefill else attend_packed)(q, cache.buf, cache.kv_heads, cache.capacity, t, cache.fmts, scaling, m, causal, ob, stats)
     return (out, stats) if return_stats else out
