@@ -28,6 +28,25 @@
 // Tile, ring and wave structure are those of gemm_w4a8_m256.hip: 256(m) x 256(n) per workgroup, 8 waves side by side
 // along n, LDS-DMA into a 3-slot ring two steps ahead (one step = 128 k = 128 B per activation row, the same row
 // pitch and swizzle), LOAD / COMPUTE ping-pong between the two waves of a SIMD, half a step (4 token tiles) per phase.
+//
+// Map of this file: the weight-image kernels (k_i8_rows .. k_i8_unpack8), then ONE kernel function, k_lqer_gemm_i8 (75 instantiations),
+// then the launch tables.  The kernel's body in order, with the helpers of each section (lambdas of the kernel unless noted; what
+// several sections or step bodies share is written once, in front of its first user):
+//   head            arguments in one batch, tile_of, the launch's tag (xtag, xch_Mp), load_mode
+//   per tile        (the persistent loop starts here) laundered ids, staging and fragment addresses
+//   ring requests   issue_step, issue_a8, issue_w8, issue_wq
+//   row tables      load_tables, write_bout_scales (a row's three B_out words: also the epilogue's), write_tables
+//   exchange        xaq_panel_dma, xch_load_s, xch_compute_s, xch_key / xch_case (limbs and slices as constants), xch_reduce,
+//                   row_absmax (file scope); MRX: mrx_span, mrx_load_batch, mrx_publish, mrx_issue, mrx_finish, mrx_item, wg_any
+//   prologue        ring_fill_head, ring_fill_tail, ring_fill; XCH: requests, row maxima, granules published; MRX: the workgroup's item
+//   main loop       fold_group, expand_w, the shared asm text and issue schedules (I8_READS_4X4 / _8X2, I8_OUTS_4X4 / _8X2, I8_DMA,
+//                   I8_DMA3, I8_DMA_SHIFT, I8_SLOT, I8_SCHED_PRESHIFT, I8_SCHED_FOLD), then the five step bodies half_step,
+//                   half_step_k, step4, step4_w8, half_step_w8 and main_loop, which picks among them
+//   behind the loop the last fold; MRX: the tile's granules (polls, fall-back mrx_item); the next tile's first step and row constants
+//   epilogue        (own laundered ids) XCH gather request, xAq stage, load_sb, conversion pass, XCH tables from the gather or the
+//                   fall-back, side_static, side, B_out quantizer, stores
+// I8_CP(...) is a statement of the -DLQER_CLOCKPROBE build (tools/clock_probe_i8.py) and nothing otherwise.
+// A change to this text is checked with tools/codeobj_diff.py against a build of the commit before.
 #include <atomic>
 #include <type_traits>
 
@@ -92,27 +111,33 @@ extern "C" __device__ unsigned long long lqer_dispatch_id() __asm("llvm.amdgcn.d
 // The gather's FIRST read of the granules: sc0 alone (past the CU's L1, served by the XCD's L2).  The tile map puts a row band's column
 // tiles on one XCD whenever a band has at most 32 of them, and the publisher's sc1 store goes through that same L2: a hit costs a
 // fraction of the agent-scope round trip behind the L2.  A stale or foreign line just fails the tag test and is polled at agent scope.
-#ifndef LQER_XCH_GATHER_AUX
-#define LQER_XCH_GATHER_AUX 1
-#endif
-constexpr int XCH_GATHER_AUX = LQER_XCH_GATHER_AUX;
+constexpr int XCH_GATHER_AUX = 1;
 // polls of a missing granule (s_sleep 8 + an agent-scope re-read: ~1.5 us each) before the workgroup computes the band's maxima itself.
 // Round 6: 6 instead of 64 - every workgroup publishes in its prologue and gathers ~25 us later, so a granule that is still missing
 // belongs to a workgroup that is not resident (another stream holds its CU): waiting longer than the fall-back costs (the band's side
 // products: tiles_n x 16 MFMAs, a few us) buys nothing, and every late tile paid the full bound
-#ifndef LQER_XCH_SWEEPS
-#define LQER_XCH_SWEEPS 6
-#endif
-constexpr int XCH_SWEEPS = LQER_XCH_SWEEPS;
+constexpr int XCH_SWEEPS = 6;
 typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+
+// the largest |acc[k]| of a 32 x 32 accumulator's row: this lane's 16 registers, then lanes l and l ^ 32 (which hold the row's other half)
+__device__ __forceinline__ float row_absmax(const f32x16& acc) {
+  float m = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; k += 2) m = fmaxf(fmaxf(m, fabsf(acc[k])), fabsf(acc[k + 1]));
+  auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+  return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+}
 
 #ifdef LQER_CLOCKPROBE
 // diagnostic build (tools/clock_probe_i8.py): shader cycles (s_memtime) and 100 MHz ticks (s_memrealtime) at the start of the
 // kernel, around the main loop and at the end, written to a buffer nothing else reads
 __device__ unsigned long long* g_i8_stamp_buf = nullptr;
 #define I8_STAMP(c, r) asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c), "=s"(r)::"memory")
+#define I8_CP(...) __VA_ARGS__  // a statement of the diagnostic build inside the kernel body
+#else
+#define I8_CP(...)
 #endif
 
 // ---- weight image ---------------------------------------------------------------------------------------------------
@@ -568,8 +593,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
           t_amax = 1.0f;
         } else if constexpr (MRX) {
           // the row's 16 {maximum, tag} granules: 128 contiguous bytes, agent scope (published inside this launch by other workgroups)
-          const int64_t Mp = (int64_t)(g.M + LQER_M_ALIGN - 1) / LQER_M_ALIGN * LQER_M_ALIGN;
-          const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.bout_amax, 0, (int)(Mp * LQER_AMAX_NSEG * 8), 0x00020000);
+          const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.bout_amax, 0, (int)(xch_Mp * LQER_AMAX_NSEG * 8), 0x00020000);
           i32x4 q[LQER_AMAX_NSEG / 2];
 #pragma unroll
           for (int j = 0; j < LQER_AMAX_NSEG / 2; ++j)
@@ -607,21 +631,36 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       }
     }
   };
+  // B_out with one block per row: the row's block exponent -> its three table words behind `ta` (the row's word of the first table):
+  // 2^(mbits - e), 2^(e - mbits), 1e-9 * 2^(mbits - e)
+  auto write_bout_scales = [&](uint32_t ta, int e_row) {
+    // both B_out scales as normal floats: mbits - e lies in [-121, 134] for an 8-bit exponent field; rows with
+    // e < mbits - 126 have |s| < 2^-119 <= 1e-8 everywhere (a zero row: e = -127), i.e. every element takes the
+    // pass-through whatever the scale - clamp, the result does not change
+    int up = g.bout.mbits - e_row;
+    up = up > 126 ? 126 : (up < -126 ? -126 : up);
+    const uint32_t upb = (uint32_t)(127 + up) << 23;
+    asm volatile("ds_write_b32 %0, %1 offset:1024\n\tds_write_b32 %0, %2 offset:2048\n\tds_write_b32 %0, %3 offset:3072" ::"v"(ta),
+                 "v"(upb), "v"((uint32_t)(127 - up) << 23), "v"(1e-9f * __uint_as_float(upb))
+                 : "memory");
+  };
   auto write_tables = [&]() {
     if (tid < BM) {
       const uint32_t ta = lds0 + EP_TAB + 4 * tid;
       asm volatile("ds_write_b32 %0, %1" ::"v"(ta), "v"(t_xs) : "memory");
-      if constexpr (LOWRANK && BOUT == 2) {
-        // both B_out scales as normal floats: mbits - e lies in [-121, 134] for an 8-bit exponent field; rows with
-        // e < mbits - 126 have |s| < 2^-119 <= 1e-8 everywhere (a zero row: e = -127), i.e. every element takes the
-        // pass-through whatever the scale - clamp, the result does not change
-        int up = g.bout.mbits - block_exponent(t_amax, g.bout);
-        up = up > 126 ? 126 : (up < -126 ? -126 : up);
-        const uint32_t upb = (uint32_t)(127 + up) << 23;
-        asm volatile("ds_write_b32 %0, %1 offset:1024\n\tds_write_b32 %0, %2 offset:2048\n\tds_write_b32 %0, %3 offset:3072" ::"v"(ta),
-                     "v"(upb), "v"((uint32_t)(127 - up) << 23), "v"(1e-9f * __uint_as_float(upb))
-                     : "memory");
-      }
+      if constexpr (LOWRANK && BOUT == 2) write_bout_scales(ta, block_exponent(t_amax, g.bout));
+    }
+  };
+  // exchange: rows [row0, row0 + BM) of xAq -> the panel region behind the row tables by LDS-DMA, NPA requests per wave (the activation
+  // tile's row pitch and swizzle; 64 columns: the exchange instantiations have one panel)
+  auto xaq_panel_dma = [&](int row0) {
+    const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(g.xaq + (int64_t)row0 * g.xaq_ld), 0, BM * g.xaq_ld * 2, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < NPA; ++i) {
+      const int row = wave * (8 * NPA) + i * 8 + (lane >> 3);
+      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void*)(smem + G::EP_XAQ + wave * (8 * NPA) * 128 + i * 1024), 16,
+                                               row * g.xaq_ld * 2 + chunk * 16, 0, 0, 0);
     }
   };
   // exchange: the side product of column tile `tnx` against this workgroup's 128 rows, this wave's 32 columns - operands straight from
@@ -669,17 +708,21 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) acc4[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sbx[l * NSL + ks], pxf[u][ks], acc4[u], 0, 0, 0);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const f32x16 acc = acc4[u];
-        float m = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; k += 2) m = fmaxf(fmaxf(m, fabsf(acc[k])), fabsf(acc[k + 1]));
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);  // lanes l and l ^ 32
-        mx[u] = fmaxf(mx[u], fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])));
-      }
+      for (int u = 0; u < 4; ++u) mx[u] = fmaxf(mx[u], row_absmax(acc4[u]));
     }
   };
   const int xch_key = XCH_OK ? g.b_limbs * 16 + xch_nsl : 0;  // (wave-uniform; gemm_plan.hip i8_in_launch_amax admits exactly six cases)
+  auto xch_case = [&](auto f) {  // f(limbs, slices per limb) with both as compile-time constants
+    using std::integral_constant;
+    switch (xch_key) {
+      case 16 + 1: f(integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
+      case 16 + 2: f(integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
+      case 16 + 4: f(integral_constant<int, 1>{}, integral_constant<int, 4>{}); break;
+      case 32 + 1: f(integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
+      case 32 + 2: f(integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
+      default: f(integral_constant<int, 2>{}, integral_constant<int, 4>{}); break;
+    }
+  };
   // ... the waves' maxima through LDS (asm: an LDS access hipcc can see would wait for every LDS-DMA in flight): [wave][row] fp32 in
   // activation slot 3 - free in the prologue until the first LOAD requests step 3, and at the epilogue until the output transposes
   const uint32_t xch_red = lds0 + OFF_A + 3 * A_SLOT;
@@ -732,38 +775,28 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       }
     }
   };
+  auto mrx_publish = [&](int item, float r) {  // r: the item's maximum of row `tid` of its band (xch_reduce)
+    if constexpr (MRX) {
+      if (tid < BM) {
+        const int seg = item & (LQER_AMAX_NSEG - 1), mb = (item >> 4) * BM;
+        const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.bout_amax, 0, (int)(xch_Mp * LQER_AMAX_NSEG * 8), 0x00020000);
+        const u32x2_g gv = {__float_as_uint(r), xtag};
+        __builtin_amdgcn_raw_buffer_store_b64(gv, m_rsrc, (int)((((mb + tid) * LQER_AMAX_NSEG) + seg) * 8), 0, 16);  // sc1
+      }
+    }
+  };
   auto mrx_issue = [&](int item) {  // the band's panel (LDS-DMA: NPA requests per wave) and the first batch of fragments
     if constexpr (MRX) {
-      using std::integral_constant;
       int t_lo, t_hi;
       mrx_span(item, t_lo, t_hi);
-      const int mb = (item >> 4) * BM;
-      const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(g.xaq + (int64_t)mb * g.xaq_ld), 0, BM * g.xaq_ld * 2, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < NPA; ++i) {
-        const int row = wave * (8 * NPA) + i * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void*)(smem + G::EP_XAQ + wave * (8 * NPA) * 128 + i * 1024), 16,
-                                                 row * g.xaq_ld * 2 + chunk * 16, 0, 0, 0);
-      }
-      if (t_hi > t_lo) {
-        switch (xch_key) {
-          case 16 + 1: mrx_load_batch(t_lo, t_hi, integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
-          case 16 + 2: mrx_load_batch(t_lo, t_hi, integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
-          case 16 + 4: mrx_load_batch(t_lo, t_hi, integral_constant<int, 1>{}, integral_constant<int, 4>{}); break;
-          case 32 + 1: mrx_load_batch(t_lo, t_hi, integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
-          case 32 + 2: mrx_load_batch(t_lo, t_hi, integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
-          default: mrx_load_batch(t_lo, t_hi, integral_constant<int, 2>{}, integral_constant<int, 4>{}); break;
-        }
-      }
+      xaq_panel_dma((item >> 4) * BM);
+      if (t_hi > t_lo) xch_case([&](auto nl_c, auto nsl_c) { mrx_load_batch(t_lo, t_hi, nl_c, nsl_c); });
     }
   };
   auto mrx_finish = [&](int item) {  // (the panel has landed for every wave: the caller's wait + barrier)
     if constexpr (MRX) {
-      using std::integral_constant;
       int t_lo, t_hi;
       mrx_span(item, t_lo, t_hi);
-      const int seg = item & (LQER_AMAX_NSEG - 1), mb = (item >> 4) * BM;
       float mx[4] = {0.f, 0.f, 0.f, 0.f};
       auto batches = [&](auto nl_c, auto nsl_c) {
         constexpr int NL = decltype(nl_c)::value, NSL = decltype(nsl_c)::value, TP = NL * NSL <= 4 ? 3 : 1;
@@ -799,34 +832,13 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
                   for (int u = 0; u < 2; ++u)
                     acc2[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mfr[j * NL * NSL + l * NSL + ks], pxf[u][ks], acc2[u], 0, 0, 0);
 #pragma unroll
-              for (int u = 0; u < 2; ++u) {
-                float m = 0.f;
-#pragma unroll
-                for (int k = 0; k < 16; k += 2) m = fmaxf(fmaxf(m, fabsf(acc2[u][k])), fabsf(acc2[u][k + 1]));
-                auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);  // lanes l and l ^ 32
-                mx[2 * up + u] = fmaxf(mx[2 * up + u], fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])));
-              }
+              for (int u = 0; u < 2; ++u) mx[2 * up + u] = fmaxf(mx[2 * up + u], row_absmax(acc2[u]));
             }
           }
         }
       };
-      if (t_hi > t_lo) {
-        switch (xch_key) {
-          case 16 + 1: batches(integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
-          case 16 + 2: batches(integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
-          case 16 + 4: batches(integral_constant<int, 1>{}, integral_constant<int, 4>{}); break;
-          case 32 + 1: batches(integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
-          case 32 + 2: batches(integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
-          default: batches(integral_constant<int, 2>{}, integral_constant<int, 4>{}); break;
-        }
-      }
-      const float r = xch_reduce(mx);  // (its barrier: every wave is done with the panel)
-      if (tid < BM) {
-        const int64_t Mp = (int64_t)(g.M + LQER_M_ALIGN - 1) / LQER_M_ALIGN * LQER_M_ALIGN;
-        const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.bout_amax, 0, (int)(Mp * LQER_AMAX_NSEG * 8), 0x00020000);
-        const u32x2_g gv = {__float_as_uint(r), xtag};
-        __builtin_amdgcn_raw_buffer_store_b64(gv, m_rsrc, (int)((((mb + tid) * LQER_AMAX_NSEG) + seg) * 8), 0, 16);  // sc1
-      }
+      if (t_hi > t_lo) xch_case(batches);
+      mrx_publish(item, xch_reduce(mx));  // (its barrier: every wave is done with the panel)
     }
   };
   // the fall-back (a band whose producers did not publish in time): the same item, slowly - one row group, one fragment at a time, runtime
@@ -835,17 +847,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     if constexpr (MRX) {
       int t_lo, t_hi;
       mrx_span(item, t_lo, t_hi);
-      const int seg = item & (LQER_AMAX_NSEG - 1), mb = (item >> 4) * BM;
-      {
-        const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(g.xaq + (int64_t)mb * g.xaq_ld), 0, BM * g.xaq_ld * 2, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < NPA; ++i) {
-          const int row = wave * (8 * NPA) + i * 8 + (lane >> 3);
-          const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void*)(smem + G::EP_XAQ + wave * (8 * NPA) * 128 + i * 1024), 16,
-                                                   row * g.xaq_ld * 2 + chunk * 16, 0, 0, 0);
-        }
-      }
+      xaq_panel_dma((item >> 4) * BM);
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
       float mx[4] = {0.f, 0.f, 0.f, 0.f};
       const int64_t limb = (int64_t)g.Np * g.rp;
@@ -861,20 +863,10 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
               asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(px) : "v"(lds0 + G::EP_XAQ + u * 4096 + swz(l31, 2 * ks + lh)) : "memory");
               acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr, px, acc, 0, 0, 0);
             }
-          float m = 0.f;
-#pragma unroll
-          for (int k = 0; k < 16; k += 2) m = fmaxf(fmaxf(m, fabsf(acc[k])), fabsf(acc[k + 1]));
-          auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-          mx[u] = fmaxf(mx[u], fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])));
+          mx[u] = fmaxf(mx[u], row_absmax(acc));
         }
       }
-      const float r = xch_reduce(mx);
-      if (tid < BM) {
-        const int64_t Mp = (int64_t)(g.M + LQER_M_ALIGN - 1) / LQER_M_ALIGN * LQER_M_ALIGN;
-        const auto m_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.bout_amax, 0, (int)(Mp * LQER_AMAX_NSEG * 8), 0x00020000);
-        const u32x2_g gv = {__float_as_uint(r), xtag};
-        __builtin_amdgcn_raw_buffer_store_b64(gv, m_rsrc, (int)((((mb + tid) * LQER_AMAX_NSEG) + seg) * 8), 0, 16);  // sc1
-      }
+      mrx_publish(item, xch_reduce(mx));
     }
   };
   // MRX: a vote of the workgroup - true when `c` holds for some lane of waves 0-1 (the row threads); two barriers.  The word carries the
@@ -952,58 +944,30 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   // one switch around both halves, so that only the registers of the (limbs, slices) case at hand are live across the fill
   float xmx[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (XCH) {
-    using std::integral_constant;
     // request order: [the xAq panel, the B^T fragments, row / column constants] [ring steps 0, 1, 2 - 15 requests per wave, no branch].
     // The first group is small (48 KiB per workgroup) and lands a ring step's transfer time ahead of step 0: the row maxima are computed,
     // reduced and published while the ring fills.
-    {
-      const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(g.xaq + (int64_t)m0 * g.xaq_ld), 0, BM * g.xaq_ld * 2, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < NPA; ++i) {
-        const int row = wave * (8 * NPA) + i * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void*)(smem + G::EP_XAQ + wave * (8 * NPA) * 128 + i * 1024), 16,
-                                                 row * g.xaq_ld * 2 + chunk * 16, 0, 0, 0);
-      }
-    }
+    xaq_panel_dma(m0);
     // (fragments the (limbs, slices) case at hand does not have stay undefined - nothing reads them; a zero fill would have to wait for
     // the requests in flight before it may write their registers)
-    switch (xch_key) {
-      case 16 + 1: xch_load_s(tn, integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
-      case 16 + 2: xch_load_s(tn, integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
-      case 16 + 4: xch_load_s(tn, integral_constant<int, 1>{}, integral_constant<int, 4>{}); break;
-      case 32 + 1: xch_load_s(tn, integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
-      case 32 + 2: xch_load_s(tn, integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
-      default: xch_load_s(tn, integral_constant<int, 2>{}, integral_constant<int, 4>{}); break;
-    }
+    xch_case([&](auto nl_c, auto nsl_c) { xch_load_s(tn, nl_c, nsl_c); });
     load_tables(m0);
     {
       const int n_ = n0 + wave * 32 + l31;
       ws_x = ((const float*)(g.w8 + (size_t)g.tiles_n * nk * (W8 ? 2 * W8_SLOT : I8_WBLOCK)))[n_];
       bv_x = g.bias ? g.bias[n_] : 0.f;
     }
-#ifdef LQER_CLOCKPROBE
-    I8_STAMP(cp_p[0], cp_x);
-#endif
+    I8_CP(I8_STAMP(cp_p[0], cp_x);)
     ring_fill_head();
     ring_fill_tail();  // (its table writes wait for this lane's row constant: the youngest request of the first group)
     // the first group has landed for this wave (the ring's requests - W4: 15, W8 codes into registers: 18 - may stay in flight), then for all
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(W8D ? 18 : 15) : "memory");
-#ifdef LQER_CLOCKPROBE
-    I8_STAMP(cp_p[1], cp_x);
-#endif
-    switch (xch_key) {
-      case 16 + 1: xch_compute_s(xmx, integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
-      case 16 + 2: xch_compute_s(xmx, integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
-      case 16 + 4: xch_compute_s(xmx, integral_constant<int, 1>{}, integral_constant<int, 4>{}); break;
-      case 32 + 1: xch_compute_s(xmx, integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
-      case 32 + 2: xch_compute_s(xmx, integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
-      default: xch_compute_s(xmx, integral_constant<int, 2>{}, integral_constant<int, 4>{}); break;
-    }
-#ifdef LQER_CLOCKPROBE
-    asm volatile("" ::"v"(xmx[0]), "v"(xmx[3]));
-    I8_STAMP(cp_p[2], cp_x);
-#endif
+    I8_CP(I8_STAMP(cp_p[1], cp_x);)
+    xch_case([&](auto nl_c, auto nsl_c) { xch_compute_s(xmx, nl_c, nsl_c); });
+    I8_CP(
+      asm volatile("" ::"v"(xmx[0]), "v"(xmx[3]));
+      I8_STAMP(cp_p[2], cp_x);
+    )
   } else {
     // MRX, first tile: this workgroup's item of the pre-pass - its requests (the band's panel, the first fragments) in FRONT of the tile's
     // ring fill, its arithmetic behind it (loads return in issue order: the counted wait leaves the ring's 15 requests in flight)
@@ -1014,16 +978,12 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     }
     ring_fill();
     if constexpr (MRX) {
-#ifdef LQER_CLOCKPROBE
-      if (first) I8_STAMP(cp_p[0], cp_x);  // the item's and the first tile's requests are out
-#endif
+      I8_CP(if (first) I8_STAMP(cp_p[0], cp_x);)  // the item's and the first tile's requests are out
       if (mrx_mine) {
         asm volatile("s_waitcnt vmcnt(15)\n\ts_barrier" ::: "memory");
         mrx_finish((int)blockIdx.x);
       }
-#ifdef LQER_CLOCKPROBE
-      if (first) I8_STAMP(cp_p[1], cp_x);  // the item is published
-#endif
+      I8_CP(if (first) I8_STAMP(cp_p[1], cp_x);)  // the item is published
     }
   }
   if constexpr (XCH_OK) {
@@ -1041,9 +1001,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
         }
       }
       if (tid == 0) asm volatile("ds_write_b32 %0, %1 offset:1020" ::"v"(lds0 + EP_TAB), "v"(0u) : "memory");
-#ifdef LQER_CLOCKPROBE
-      I8_STAMP(cp_p[3], cp_x);
-#endif
+      I8_CP(I8_STAMP(cp_p[3], cp_x);)
     }
   }
 
@@ -1067,37 +1025,51 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   else if constexpr (W8D) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   if (late) asm volatile("s_barrier" ::: "memory");
-#ifdef LQER_CLOCKPROBE
-  I8_STAMP(cp_c[1], cp_r[1]);
-  if constexpr (MRX) { if (first) cp_p[3] = cp_c[1]; }
-#endif
+  I8_CP(
+    I8_STAMP(cp_c[1], cp_r[1]);
+    if constexpr (MRX) { if (first) cp_p[3] = cp_c[1]; }
+  )
   i32x4 wf[4];     // the step's expanded weight fragments (slices 0..3): live across both half-steps
   uint32_t sv = 0;  // this lane's (column's) shift of the step's 128-k group
   // SHIFT: the group sums of a half-step's LAST token tile are folded at the head of the next half-step's LOAD section - the
   // partner wave of the SIMD is computing then and the vector ALU is idle -, those of the other three tiles under the MFMAs
   // of the tile after them (4 folds per MFMA slot, from two slots behind the tile's last MFMA: its results have landed)
   i32x16 Gd = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  auto half_step = [&](int kt, auto slot_c, auto half_c, auto mode_c) {
-    constexpr int SLOT = decltype(slot_c)::value;
-    constexpr int P = decltype(half_c)::value;
-    constexpr int MODE = decltype(mode_c)::value;  // I8_MODE_* of this tile
-    constexpr int slot_new = (SLOT + DEPTH) % NSLOT;
-    constexpr int A_IMM = (SLOT == 2 ? 0 : SLOT * A_SLOT) + 4 * P * 4096;  // tile t of this half: + 4096 t
-    __builtin_amdgcn_s_setprio(1);
-    if constexpr (MODE == I8_MODE_FOLD) {  // the previous half-step's last tile (sv still holds that step's shift: the asm below updates it)
-      constexpr int prev = 4 * (1 - P) + 3;
+  auto fold_group = [&](i32x16& r, const i32x16& gsum) {  // FOLD: a group sum into the running tile, one v_lshl_add_u32 per element
 #pragma unroll
-      for (int j = 0; j < 16; ++j) R[prev][j] = (int)(((uint32_t)Gd[j] << sv) + (uint32_t)R[prev][j]);
-      __builtin_amdgcn_sched_barrier(0);
+    for (int j = 0; j < 16; ++j) r[j] = (int)(((uint32_t)gsum[j] << sv) + (uint32_t)r[j]);
+  };
+  // nibble words -> the int8 lanes of one 32-k slice, in the tile's MODE.
+  // PRESHIFT: the lane is the nibble's value arithmetically shifted: (cw << 4) >> q per byte.  The logical shift moves only
+  // zeros across byte borders (the low nibble of every byte of x is 0, q <= 4); the sign fill comes from v_perm_b32's
+  // sign selectors (a byte of 0x00 / 0xFF per odd byte of its sources: w and w << 8 give the four high-nibble signs, w << 4
+  // and w << 12 the low-nibble ones) masked to the q vacated bits (hq4: per byte the q high bits, ((0xFF00 >> sv) & 0xFF) * 0x01010101,
+  // from the step's shift byte).  11 vector instructions per word of 8 weights.
+  auto expand_w = [&](auto mode_c, uint32_t hq4, uint32_t w0, uint32_t w1) {
+    constexpr int MODE = decltype(mode_c)::value;
+    if constexpr (MODE == I8_MODE_PRESHIFT1) {  // q <= 1: (x >> q) | (x & 0x80808080) - the one vacated bit is the sign bit
+      const uint32_t a0 = (w0 << 4) & 0xF0F0F0F0u, b0 = w0 & 0xF0F0F0F0u, a1 = (w1 << 4) & 0xF0F0F0F0u, b1 = w1 & 0xF0F0F0F0u;
+      return (i32x4){(int)((a0 & 0x80808080u) | (a0 >> sv)), (int)((b0 & 0x80808080u) | (b0 >> sv)),
+                     (int)((a1 & 0x80808080u) | (a1 >> sv)), (int)((b1 & 0x80808080u) | (b1 >> sv))};
+    } else if constexpr (MODE == I8_MODE_PRESHIFT) {
+      auto one = [&](uint32_t w, uint32_t& lo, uint32_t& hi) {
+        const uint32_t t = w << 4;
+        const uint32_t m_hi = __builtin_amdgcn_perm(w, w << 8, 0x0B090A08u), m_lo = __builtin_amdgcn_perm(t, w << 12, 0x0B090A08u);
+        lo = (m_lo & hq4) | ((t & 0xF0F0F0F0u) >> sv);
+        hi = (m_hi & hq4) | ((w & 0xF0F0F0F0u) >> sv);
+      };
+      uint32_t l0, h0, l1, h1;
+      one(w0, l0, h0);
+      one(w1, l1, h1);
+      return (i32x4){(int)l0, (int)h0, (int)l1, (int)h1};
+    } else {
+      return (i32x4){(int)((w0 << 4) & 0xF0F0F0F0u), (int)(w0 & 0xF0F0F0F0u), (int)((w1 << 4) & 0xF0F0F0F0u), (int)(w1 & 0xF0F0F0F0u)};
     }
-    const int ktn = __builtin_amdgcn_readfirstlane(kt + DEPTH);
-    const int a_soff = ktn * I8_BK, w_soff = ktn * I8_WBLOCK;
-    const uint32_t m0a0 = m0_a + slot_new * A_SLOT + (2 * P) * 1024, m0a1 = m0a0 + 1024;
-    const uint32_t m0w = m0_w + slot_new * W_SLOT + P * 1024, m0s = m0_s + slot_new * W_SLOT;
-    i32x4 xa[4][4];  // [tile of this half][slice]
-    u32x4 wr0, wr1;
-    // (symbolic operand names: x<tile><slice> activation fragments, fa<slice> their address registers)
-#define I8_READS_X                                                                                                     \
+  };
+  // The assembly text the step bodies share (symbolic operand names: x<tile><slice> activation fragments, fa<slice> their address
+  // registers, aimm the slot's offset; tile t: + 4096 t).  Each body pastes them into ONE asm statement with its own waits.
+  // 4 token tiles x 4 slices (half_step, step4, step4_w8) ...
+#define I8_READS_4X4                                                                                                   \
       "ds_read_b128 %[x00], %[fa0] offset:%c[aimm]\n\tds_read_b128 %[x01], %[fa1] offset:%c[aimm]\n\t"                   \
       "ds_read_b128 %[x02], %[fa2] offset:%c[aimm]\n\tds_read_b128 %[x03], %[fa3] offset:%c[aimm]\n\t"                   \
       "ds_read_b128 %[x10], %[fa0] offset:%c[aimm]+4096\n\tds_read_b128 %[x11], %[fa1] offset:%c[aimm]+4096\n\t"         \
@@ -1106,67 +1078,94 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       "ds_read_b128 %[x22], %[fa2] offset:%c[aimm]+8192\n\tds_read_b128 %[x23], %[fa3] offset:%c[aimm]+8192\n\t"         \
       "ds_read_b128 %[x30], %[fa0] offset:%c[aimm]+12288\n\tds_read_b128 %[x31], %[fa1] offset:%c[aimm]+12288\n\t"       \
       "ds_read_b128 %[x32], %[fa2] offset:%c[aimm]+12288\n\tds_read_b128 %[x33], %[fa3] offset:%c[aimm]+12288\n\t"
-#define I8_DMA                                                                                                         \
-      "s_mov_b32 m0, %[m0a0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av0], %[ars], %[asoff] offen lds\n\t"                   \
-      "s_mov_b32 m0, %[m0a1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av1], %[ars], %[asoff] offen lds\n\t"                   \
-      "s_mov_b32 m0, %[m0w]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv], %[wrs], %[wsoff] offen lds\n\t"
-#define I8_OUTS_X                                                                                                      \
+#define I8_OUTS_4X4(xa)                                                                                                \
       [x00] "=&v"(xa[0][0]), [x01] "=&v"(xa[0][1]), [x02] "=&v"(xa[0][2]), [x03] "=&v"(xa[0][3]), [x10] "=&v"(xa[1][0]),      \
       [x11] "=&v"(xa[1][1]), [x12] "=&v"(xa[1][2]), [x13] "=&v"(xa[1][3]), [x20] "=&v"(xa[2][0]), [x21] "=&v"(xa[2][1]),      \
       [x22] "=&v"(xa[2][2]), [x23] "=&v"(xa[2][3]), [x30] "=&v"(xa[3][0]), [x31] "=&v"(xa[3][1]), [x32] "=&v"(xa[3][2]),      \
       [x33] "=&v"(xa[3][3])
+  // ... 8 token tiles x the 2 slices of a half (half_step_k, half_step_w8)
+#define I8_READS_8X2                                                                                                   \
+      "ds_read_b128 %[x00], %[fa0] offset:%c[aimm]\n\tds_read_b128 %[x01], %[fa1] offset:%c[aimm]\n\t"                   \
+      "ds_read_b128 %[x10], %[fa0] offset:%c[aimm]+4096\n\tds_read_b128 %[x11], %[fa1] offset:%c[aimm]+4096\n\t"         \
+      "ds_read_b128 %[x20], %[fa0] offset:%c[aimm]+8192\n\tds_read_b128 %[x21], %[fa1] offset:%c[aimm]+8192\n\t"         \
+      "ds_read_b128 %[x30], %[fa0] offset:%c[aimm]+12288\n\tds_read_b128 %[x31], %[fa1] offset:%c[aimm]+12288\n\t"       \
+      "ds_read_b128 %[x40], %[fa0] offset:%c[aimm]+16384\n\tds_read_b128 %[x41], %[fa1] offset:%c[aimm]+16384\n\t"       \
+      "ds_read_b128 %[x50], %[fa0] offset:%c[aimm]+20480\n\tds_read_b128 %[x51], %[fa1] offset:%c[aimm]+20480\n\t"       \
+      "ds_read_b128 %[x60], %[fa0] offset:%c[aimm]+24576\n\tds_read_b128 %[x61], %[fa1] offset:%c[aimm]+24576\n\t"       \
+      "ds_read_b128 %[x70], %[fa0] offset:%c[aimm]+28672\n\tds_read_b128 %[x71], %[fa1] offset:%c[aimm]+28672\n\t"
+#define I8_OUTS_8X2(xk)                                                                                                \
+      [x00] "=&v"(xk[0][0]), [x01] "=&v"(xk[0][1]), [x10] "=&v"(xk[1][0]), [x11] "=&v"(xk[1][1]), [x20] "=&v"(xk[2][0]),      \
+      [x21] "=&v"(xk[2][1]), [x30] "=&v"(xk[3][0]), [x31] "=&v"(xk[3][1]), [x40] "=&v"(xk[4][0]), [x41] "=&v"(xk[4][1]),      \
+      [x50] "=&v"(xk[5][0]), [x51] "=&v"(xk[5][1]), [x60] "=&v"(xk[6][0]), [x61] "=&v"(xk[6][1]), [x70] "=&v"(xk[7][0]),      \
+      [x71] "=&v"(xk[7][1])
+  // one 1-KiB LDS-DMA request (LDS address through m0, lane offset, descriptor, scalar offset: operand NAMES) ...
+  // (no cache-policy bits on the activation pieces: sc0 on every one cost the main loop 17 %)
+#define I8_DMA(m0r, voff, rsrc, soff) \
+      "s_mov_b32 m0, %[" #m0r "]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[" #voff "], %[" #rsrc "], %[" #soff "] offen lds\n\t"
+  // ... and a half-step's three: two activation pieces, one piece of nibbles
+#define I8_DMA3 I8_DMA(m0a0, av0, ars, asoff) I8_DMA(m0a1, av1, ars, asoff) I8_DMA(m0w, wv, wrs, wsoff)
+  // wave 0's request for the step's 256 shift bytes, and the end of the label it jumps over
+#define I8_DMA_SHIFT                                                                                                   \
+      "s_cmp_lg_u32 %[wave], 0\n\ts_cbranch_scc1 1f\n\t"                                                                 \
+      "s_mov_b32 m0, %[m0s]\n\ts_nop 0\n\tbuffer_load_dword %[sv4], %[wrs], %[wsoff] offen lds\n\t"                      \
+      "1:\n\t"
+  // issue order of a COMPUTE section: one MFMA, then the NV vector instructions that go into its shadow
+#define I8_SLOT(NV)                                     \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
+    if constexpr ((NV) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (NV), 0);
+  // PRESHIFT, 16 MFMAs slice-major: the expand of slice ks + 1 (<= 22 vector instructions) in the shadow of the four MFMAs of slice ks
+#define I8_SCHED_PRESHIFT                       \
+    I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5) \
+    I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5) \
+    I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5) \
+    I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0)
+  // FOLD, 16 MFMAs tile-major: the expands of the step's remaining weight fragments first (P = 0: needed by the MFMAs of slots 1..3;
+  // P = 1 has none), the folds of tile t from slot 4 t + 5 on
+#define I8_SCHED_FOLD(P)                                                               \
+    I8_SLOT((P) == 0 ? 6 : 0) I8_SLOT((P) == 0 ? 6 : 0) I8_SLOT((P) == 0 ? 6 : 0) I8_SLOT(0) \
+    I8_SLOT(0) I8_SLOT(4) I8_SLOT(4) I8_SLOT(4)                                        \
+    I8_SLOT(4) I8_SLOT(4) I8_SLOT(4) I8_SLOT(4)                                        \
+    I8_SLOT(4) I8_SLOT(5) I8_SLOT(5) I8_SLOT(6)
+  auto half_step = [&](int kt, auto slot_c, auto half_c, auto mode_c) {
+    constexpr int SLOT = decltype(slot_c)::value;
+    constexpr int P = decltype(half_c)::value;
+    constexpr int MODE = decltype(mode_c)::value;  // I8_MODE_* of this tile
+    constexpr int slot_new = (SLOT + DEPTH) % NSLOT;
+    constexpr int A_IMM = (SLOT == 2 ? 0 : SLOT * A_SLOT) + 4 * P * 4096;  // tile t of this half: + 4096 t
+    __builtin_amdgcn_s_setprio(1);
+    if constexpr (MODE == I8_MODE_FOLD) {  // the previous half-step's last tile (sv still holds that step's shift: the asm below updates it)
+      fold_group(R[4 * (1 - P) + 3], Gd);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const int ktn = __builtin_amdgcn_readfirstlane(kt + DEPTH);
+    const int a_soff = ktn * I8_BK, w_soff = ktn * I8_WBLOCK;
+    const uint32_t m0a0 = m0_a + slot_new * A_SLOT + (2 * P) * 1024, m0a1 = m0a0 + 1024;
+    const uint32_t m0w = m0_w + slot_new * W_SLOT + P * 1024, m0s = m0_s + slot_new * W_SLOT;
+    i32x4 xa[4][4];  // [tile of this half][slice]
+    u32x4 wr0, wr1;
 #define I8_INS                                                                                                         \
       [fa0] "v"(SLOT == 2 ? fa_hi[0] : fa_lo[0]), [fa1] "v"(SLOT == 2 ? fa_hi[1] : fa_lo[1]),                                 \
       [fa2] "v"(SLOT == 2 ? fa_hi[2] : fa_lo[2]), [fa3] "v"(SLOT == 2 ? fa_hi[3] : fa_lo[3]), [aimm] "i"(A_IMM),              \
       [av0] "v"(a_voff[2 * P]), [av1] "v"(a_voff[2 * P + 1]), [wv] "v"(P == 0 ? w_voff0 : w_voff1), [ars] "s"(a_rs),          \
       [wrs] "s"(w_rs), [m0a0] "s"(m0a0), [m0a1] "s"(m0a1), [asoff] "s"(a_soff), [m0w] "s"(m0w), [wsoff] "s"(w_soff)
     if constexpr (P == 0) {
-      asm volatile(I8_READS_X
+      asm volatile(I8_READS_4X4
                    "ds_read_b128 %[wr0], %[fwa] offset:%c[wimm]\n\tds_read_b128 %[wr1], %[fwb] offset:%c[wimm]\n\t"
                    "ds_read_u8 %[sv], %[fs] offset:%c[wimm]\n\t"
-                   I8_DMA "s_waitcnt lgkmcnt(0)"
-                   : I8_OUTS_X, [wr0] "=&v"(wr0), [wr1] "=&v"(wr1), [sv] "=&v"(sv)
+                   I8_DMA3 "s_waitcnt lgkmcnt(0)"
+                   : I8_OUTS_4X4(xa), [wr0] "=&v"(wr0), [wr1] "=&v"(wr1), [sv] "=&v"(sv)
                    : I8_INS, [fwa] "v"(fw_a), [fwb] "v"(fw_b), [fs] "v"(fs_addr), [wimm] "i"(SLOT * W_SLOT)
                    : "memory");
     } else {
-      asm volatile(I8_READS_X I8_DMA
-                   "s_cmp_lg_u32 %[wave], 0\n\ts_cbranch_scc1 1f\n\t"
-                   "s_mov_b32 m0, %[m0s]\n\ts_nop 0\n\tbuffer_load_dword %[sv4], %[wrs], %[wsoff] offen lds\n\t"
-                   "1:\n\ts_waitcnt vmcnt(6) lgkmcnt(0)"
-                   : I8_OUTS_X
+      asm volatile(I8_READS_4X4 I8_DMA3 I8_DMA_SHIFT "s_waitcnt vmcnt(6) lgkmcnt(0)"
+                   : I8_OUTS_4X4(xa)
                    : I8_INS, [wave] "s"(wave), [sv4] "v"(s_voff), [m0s] "s"(m0s)
                    : "memory", "scc");
     }
-#undef I8_READS_X
-#undef I8_DMA
-#undef I8_OUTS_X
 #undef I8_INS
-    // PRESHIFT: the lane is the nibble's value arithmetically shifted: (cw << 4) >> q per byte.  The logical shift moves only
-    // zeros across byte borders (the low nibble of every byte of x is 0, q <= 4); the sign fill comes from v_perm_b32's
-    // sign selectors (a byte of 0x00 / 0xFF per odd byte of its sources: w and w << 8 give the four high-nibble signs, w << 4
-    // and w << 12 the low-nibble ones) masked to the q vacated bits.  11 vector instructions per word of 8 weights.
-    uint32_t hq4 = 0;  // per byte: the q high bits
+    uint32_t hq4 = 0;  // PRESHIFT: per byte the q high bits (expand_w)
     if constexpr (MODE == I8_MODE_PRESHIFT && P == 0) hq4 = ((0xFF00u >> sv) & 0xFFu) * 0x01010101u;
-    auto expand = [&](uint32_t w0, uint32_t w1) {
-      if constexpr (MODE == I8_MODE_PRESHIFT1) {  // q <= 1: (x >> q) | (x & 0x80808080) - the one vacated bit is the sign bit
-        const uint32_t a0 = (w0 << 4) & 0xF0F0F0F0u, b0 = w0 & 0xF0F0F0F0u, a1 = (w1 << 4) & 0xF0F0F0F0u, b1 = w1 & 0xF0F0F0F0u;
-        return (i32x4){(int)((a0 & 0x80808080u) | (a0 >> sv)), (int)((b0 & 0x80808080u) | (b0 >> sv)),
-                       (int)((a1 & 0x80808080u) | (a1 >> sv)), (int)((b1 & 0x80808080u) | (b1 >> sv))};
-      } else if constexpr (MODE == I8_MODE_PRESHIFT) {
-        auto one = [&](uint32_t w, uint32_t& lo, uint32_t& hi) {
-          const uint32_t t = w << 4;
-          const uint32_t m_hi = __builtin_amdgcn_perm(w, w << 8, 0x0B090A08u), m_lo = __builtin_amdgcn_perm(t, w << 12, 0x0B090A08u);
-          lo = (m_lo & hq4) | ((t & 0xF0F0F0F0u) >> sv);
-          hi = (m_hi & hq4) | ((w & 0xF0F0F0F0u) >> sv);
-        };
-        uint32_t l0, h0, l1, h1;
-        one(w0, l0, h0);
-        one(w1, l1, h1);
-        return (i32x4){(int)l0, (int)h0, (int)l1, (int)h1};
-      } else {
-        return (i32x4){(int)((w0 << 4) & 0xF0F0F0F0u), (int)(w0 & 0xF0F0F0F0u), (int)((w1 << 4) & 0xF0F0F0F0u), (int)(w1 & 0xF0F0F0F0u)};
-      }
-    };
+    auto expand = [&](uint32_t w0, uint32_t w1) { return expand_w(mode_c, hq4, w0, w1); };
     if constexpr (P == 0) {
       wf[0] = expand(wr0[0], wr0[1]);
       asm volatile("s_barrier" : "+v"(wf[0])::"memory");
@@ -1187,15 +1186,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) R[4 * P + t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][ks], wf[ks], R[4 * P + t], 0, 0, 0);
       if constexpr ((MODE == I8_MODE_PRESHIFT || MODE == I8_MODE_PRESHIFT1) && P == 0) {
-        // issue order: the expand of slice ks + 1 (22 vector instructions) in the shadow of the four MFMAs of slice ks
-#define I8_SLOT(NV)                                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
-        if constexpr ((NV) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (NV), 0);
-        I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5)
-        I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5)
-        I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5)
-        I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0)
-#undef I8_SLOT
+        I8_SCHED_PRESHIFT
       }
     } else {
       const i32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1205,22 +1196,10 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
         G[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][0], wf[0], z, 0, 0, 0);
 #pragma unroll
         for (int ks = 1; ks < 4; ++ks) G[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][ks], wf[ks], G[t], 0, 0, 0);
-        if (t > 0) {
-#pragma unroll
-          for (int j = 0; j < 16; ++j) R[4 * P + t - 1][j] = (int)(((uint32_t)G[t - 1][j] << sv) + (uint32_t)R[4 * P + t - 1][j]);
-        }
+        if (t > 0) fold_group(R[4 * P + t - 1], G[t - 1]);
       }
       Gd = G[3];
-      // issue order: one MFMA, then the vector instructions that fit its shadow - the expands of the step's remaining weight
-      // fragments first (P = 0: needed by the MFMAs of slots 1..3), the folds of tile t from slot 4 t + 5 on
-#define I8_SLOT(NV)                                       \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
-      if constexpr ((NV) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (NV), 0);
-      I8_SLOT(P == 0 ? 6 : 0) I8_SLOT(P == 0 ? 6 : 0) I8_SLOT(P == 0 ? 6 : 0) I8_SLOT(0)
-      I8_SLOT(0) I8_SLOT(4) I8_SLOT(4) I8_SLOT(4)
-      I8_SLOT(4) I8_SLOT(4) I8_SLOT(4) I8_SLOT(4)
-      I8_SLOT(4) I8_SLOT(5) I8_SLOT(5) I8_SLOT(6)
-#undef I8_SLOT
+      I8_SCHED_FOLD(P)
     }
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_barrier" ::: "memory");
@@ -1246,65 +1225,27 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     const uint32_t m0w = m0_w + slot_new * W_SLOT + P * 1024, m0s = m0_s + slot_new * W_SLOT;
     i32x4 xk[8][2];  // [token tile][slice of this half]
     u32x4 wr;        // the half's weight words: slices 2P, 2P + 1
-#define I8K_READS                                                                                                      \
-      "ds_read_b128 %[x00], %[fa0] offset:%c[aimm]\n\tds_read_b128 %[x01], %[fa1] offset:%c[aimm]\n\t"  \
-      "ds_read_b128 %[x10], %[fa0] offset:%c[aimm]+4096\n\tds_read_b128 %[x11], %[fa1] offset:%c[aimm]+4096\n\t"  \
-      "ds_read_b128 %[x20], %[fa0] offset:%c[aimm]+8192\n\tds_read_b128 %[x21], %[fa1] offset:%c[aimm]+8192\n\t"  \
-      "ds_read_b128 %[x30], %[fa0] offset:%c[aimm]+12288\n\tds_read_b128 %[x31], %[fa1] offset:%c[aimm]+12288\n\t"  \
-      "ds_read_b128 %[x40], %[fa0] offset:%c[aimm]+16384\n\tds_read_b128 %[x41], %[fa1] offset:%c[aimm]+16384\n\t"  \
-      "ds_read_b128 %[x50], %[fa0] offset:%c[aimm]+20480\n\tds_read_b128 %[x51], %[fa1] offset:%c[aimm]+20480\n\t"  \
-      "ds_read_b128 %[x60], %[fa0] offset:%c[aimm]+24576\n\tds_read_b128 %[x61], %[fa1] offset:%c[aimm]+24576\n\t"  \
-      "ds_read_b128 %[x70], %[fa0] offset:%c[aimm]+28672\n\tds_read_b128 %[x71], %[fa1] offset:%c[aimm]+28672\n\t"  \
-      "ds_read_b128 %[wr], %[fw] offset:%c[wimm]\n\t"
-#define I8K_DMA                                                                                                        \
-      "s_mov_b32 m0, %[m0a0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av0], %[ars], %[asoff] offen lds\n\t"                   \
-      "s_mov_b32 m0, %[m0a1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av1], %[ars], %[asoff] offen lds\n\t"                   \
-      "s_mov_b32 m0, %[m0w]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv], %[wrs], %[wsoff] offen lds\n\t"
-#define I8K_OUTS [x00] "=&v"(xk[0][0]), [x01] "=&v"(xk[0][1]), [x10] "=&v"(xk[1][0]), [x11] "=&v"(xk[1][1]), [x20] "=&v"(xk[2][0]), [x21] "=&v"(xk[2][1]), [x30] "=&v"(xk[3][0]), [x31] "=&v"(xk[3][1]), [x40] "=&v"(xk[4][0]), [x41] "=&v"(xk[4][1]), [x50] "=&v"(xk[5][0]), [x51] "=&v"(xk[5][1]), [x60] "=&v"(xk[6][0]), [x61] "=&v"(xk[6][1]), [x70] "=&v"(xk[7][0]), [x71] "=&v"(xk[7][1]), [wr] "=&v"(wr)
+#define I8K_READS I8_READS_8X2 "ds_read_b128 %[wr], %[fw] offset:%c[wimm]\n\t"
 #define I8K_INS                                                                                                        \
       [fa0] "v"(SLOT == 2 ? fa_hi[2 * P] : fa_lo[2 * P]), [fa1] "v"(SLOT == 2 ? fa_hi[2 * P + 1] : fa_lo[2 * P + 1]),         \
       [aimm] "i"(A_IMM), [fw] "v"(P == 0 ? fw_a : fw_b), [wimm] "i"(SLOT * W_SLOT), [av0] "v"(a_voff[2 * P]),                 \
       [av1] "v"(a_voff[2 * P + 1]), [wv] "v"(P == 0 ? w_voff0 : w_voff1), [ars] "s"(a_rs), [wrs] "s"(w_rs), [m0a0] "s"(m0a0), \
       [m0a1] "s"(m0a1), [asoff] "s"(a_soff), [m0w] "s"(m0w), [wsoff] "s"(w_soff)
     if constexpr (P == 0) {
-      asm volatile(I8K_READS "ds_read_u8 %[sv], %[fs] offset:%c[wimm]\n\t" I8K_DMA "s_waitcnt lgkmcnt(0)"
-                   : I8K_OUTS, [sv] "=&v"(sv)
+      asm volatile(I8K_READS "ds_read_u8 %[sv], %[fs] offset:%c[wimm]\n\t" I8_DMA3 "s_waitcnt lgkmcnt(0)"
+                   : I8_OUTS_8X2(xk), [wr] "=&v"(wr), [sv] "=&v"(sv)
                    : I8K_INS, [fs] "v"(fs_addr)
                    : "memory");
     } else {
-      asm volatile(I8K_READS I8K_DMA
-                   "s_cmp_lg_u32 %[wave], 0\n\ts_cbranch_scc1 1f\n\t"
-                   "s_mov_b32 m0, %[m0s]\n\ts_nop 0\n\tbuffer_load_dword %[sv4], %[wrs], %[wsoff] offen lds\n\t"
-                   "1:\n\ts_waitcnt vmcnt(6) lgkmcnt(0)"
-                   : I8K_OUTS
+      asm volatile(I8K_READS I8_DMA3 I8_DMA_SHIFT "s_waitcnt vmcnt(6) lgkmcnt(0)"
+                   : I8_OUTS_8X2(xk), [wr] "=&v"(wr)
                    : I8K_INS, [wave] "s"(wave), [sv4] "v"(s_voff), [m0s] "s"(m0s)
                    : "memory", "scc");
     }
 #undef I8K_READS
-#undef I8K_DMA
-#undef I8K_OUTS
 #undef I8K_INS
     if constexpr (MODE == I8_MODE_PRESHIFT && P == 0) hq4_k = ((0xFF00u >> sv) & 0xFFu) * 0x01010101u;
-    auto expand = [&](uint32_t w0, uint32_t w1) {
-      if constexpr (MODE == I8_MODE_PRESHIFT1) {  // q <= 1: (x >> q) | (x & 0x80808080) - the one vacated bit is the sign bit
-        const uint32_t a0 = (w0 << 4) & 0xF0F0F0F0u, b0 = w0 & 0xF0F0F0F0u, a1 = (w1 << 4) & 0xF0F0F0F0u, b1 = w1 & 0xF0F0F0F0u;
-        return (i32x4){(int)((a0 & 0x80808080u) | (a0 >> sv)), (int)((b0 & 0x80808080u) | (b0 >> sv)),
-                       (int)((a1 & 0x80808080u) | (a1 >> sv)), (int)((b1 & 0x80808080u) | (b1 >> sv))};
-      } else if constexpr (MODE == I8_MODE_PRESHIFT) {  // (the lane cw << (4 - q): see half_step)
-        auto one = [&](uint32_t w, uint32_t& lo, uint32_t& hi) {
-          const uint32_t t = w << 4;
-          const uint32_t m_hi = __builtin_amdgcn_perm(w, w << 8, 0x0B090A08u), m_lo = __builtin_amdgcn_perm(t, w << 12, 0x0B090A08u);
-          lo = (m_lo & hq4_k) | ((t & 0xF0F0F0F0u) >> sv);
-          hi = (m_hi & hq4_k) | ((w & 0xF0F0F0F0u) >> sv);
-        };
-        uint32_t l0, h0, l1, h1;
-        one(w0, l0, h0);
-        one(w1, l1, h1);
-        return (i32x4){(int)l0, (int)h0, (int)l1, (int)h1};
-      } else {
-        return (i32x4){(int)((w0 << 4) & 0xF0F0F0F0u), (int)(w0 & 0xF0F0F0F0u), (int)((w1 << 4) & 0xF0F0F0F0u), (int)(w1 & 0xF0F0F0F0u)};
-      }
-    };
+    auto expand = [&](uint32_t w0, uint32_t w1) { return expand_w(mode_c, hq4_k, w0, w1); };
     i32x4 wa = expand(wr[0], wr[1]);
     asm volatile("s_barrier" : "+v"(wa)::"memory");
     __builtin_amdgcn_s_setprio(0);
@@ -1316,12 +1257,8 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) R[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xk[t][1], wb, R[t], 0, 0, 0);
     if constexpr (MODE == I8_MODE_PRESHIFT || MODE == I8_MODE_PRESHIFT1) {  // the second slice's expand: <= 3 vector instructions per MFMA slot
-#define I8_SLOT(NV)                                     \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
-      if constexpr ((NV) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (NV), 0);
       I8_SLOT(3) I8_SLOT(3) I8_SLOT(3) I8_SLOT(3) I8_SLOT(3) I8_SLOT(3) I8_SLOT(3) I8_SLOT(3)
       I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0)
-#undef I8_SLOT
     }
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_barrier" ::: "memory");
@@ -1338,8 +1275,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     constexpr int A_IMM = SLOT * A_SLOT;  // tile t: + 4096 t (every slot within the DS offset field)
     __builtin_amdgcn_s_setprio(1);
     if constexpr (MODE == I8_MODE_FOLD) {  // the previous step's last tile (sv still holds that step's shift: the asm below updates it)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) R[3][j] = (int)(((uint32_t)Gd[j] << sv) + (uint32_t)R[3][j]);
+      fold_group(R[3], Gd);
       __builtin_amdgcn_sched_barrier(0);
     }
     const int ktn = __builtin_amdgcn_readfirstlane(kt + DEPTH);
@@ -1349,57 +1285,21 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     const uint32_t m0w0 = m0_w + slot_new * W_SLOT, m0w1 = m0w0 + 1024, m0s = m0_s + slot_new * W_SLOT;
     i32x4 xa[4][4];  // [token tile][slice]
     u32x4 wr0, wr1;
-    asm volatile(
-        "ds_read_b128 %[x00], %[fa0] offset:%c[aimm]\n\tds_read_b128 %[x01], %[fa1] offset:%c[aimm]\n\t"
-        "ds_read_b128 %[x02], %[fa2] offset:%c[aimm]\n\tds_read_b128 %[x03], %[fa3] offset:%c[aimm]\n\t"
-        "ds_read_b128 %[x10], %[fa0] offset:%c[aimm]+4096\n\tds_read_b128 %[x11], %[fa1] offset:%c[aimm]+4096\n\t"
-        "ds_read_b128 %[x12], %[fa2] offset:%c[aimm]+4096\n\tds_read_b128 %[x13], %[fa3] offset:%c[aimm]+4096\n\t"
-        "ds_read_b128 %[x20], %[fa0] offset:%c[aimm]+8192\n\tds_read_b128 %[x21], %[fa1] offset:%c[aimm]+8192\n\t"
-        "ds_read_b128 %[x22], %[fa2] offset:%c[aimm]+8192\n\tds_read_b128 %[x23], %[fa3] offset:%c[aimm]+8192\n\t"
-        "ds_read_b128 %[x30], %[fa0] offset:%c[aimm]+12288\n\tds_read_b128 %[x31], %[fa1] offset:%c[aimm]+12288\n\t"
-        "ds_read_b128 %[x32], %[fa2] offset:%c[aimm]+12288\n\tds_read_b128 %[x33], %[fa3] offset:%c[aimm]+12288\n\t"
-        "ds_read_b128 %[wr0], %[fwa] offset:%c[wimm]\n\tds_read_b128 %[wr1], %[fwb] offset:%c[wimm]\n\t"
-        "ds_read_u8 %[sv], %[fs] offset:%c[wimm]\n\t"
-        // (no cache-policy bits on the activation pieces: sc0 on every one cost the main loop 17 %)
-        "s_mov_b32 m0, %[m0a0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av0], %[ars], %[asoff] offen lds\n\t"
-        "s_mov_b32 m0, %[m0a1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av1], %[ars], %[asoff] offen lds\n\t"
-        "s_mov_b32 m0, %[m0w0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv0], %[wrs], %[wsoff] offen lds\n\t"
-        "s_mov_b32 m0, %[m0w1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv1], %[wrs], %[wsoff] offen lds\n\t"
-        "s_cmp_lg_u32 %[wave], 0\n\ts_cbranch_scc1 1f\n\t"
-        "s_mov_b32 m0, %[m0s]\n\ts_nop 0\n\tbuffer_load_dword %[sv4], %[wrs], %[wsoff] offen lds\n\t"
-        "1:\n\ts_waitcnt vmcnt(8) lgkmcnt(0)"
-        : [x00] "=&v"(xa[0][0]), [x01] "=&v"(xa[0][1]), [x02] "=&v"(xa[0][2]), [x03] "=&v"(xa[0][3]), [x10] "=&v"(xa[1][0]),
-          [x11] "=&v"(xa[1][1]), [x12] "=&v"(xa[1][2]), [x13] "=&v"(xa[1][3]), [x20] "=&v"(xa[2][0]), [x21] "=&v"(xa[2][1]),
-          [x22] "=&v"(xa[2][2]), [x23] "=&v"(xa[2][3]), [x30] "=&v"(xa[3][0]), [x31] "=&v"(xa[3][1]), [x32] "=&v"(xa[3][2]),
-          [x33] "=&v"(xa[3][3]), [wr0] "=&v"(wr0), [wr1] "=&v"(wr1), [sv] "=&v"(sv)
-        : [fa0] "v"(fa_lo[0]), [fa1] "v"(fa_lo[1]), [fa2] "v"(fa_lo[2]), [fa3] "v"(fa_lo[3]), [aimm] "i"(A_IMM), [fwa] "v"(fw_a),
-          [fwb] "v"(fw_b), [fs] "v"(fs_addr), [wimm] "i"(SLOT * W_SLOT), [av0] "v"(a_voff[0]), [av1] "v"(a_voff[1]),
-          [wv0] "v"(w_voff0), [wv1] "v"(w_voff1), [sv4] "v"(s_voff), [ars] "s"(a_rs), [wrs] "s"(w_rs), [m0a0] "s"(m0a0),
-          [m0a1] "s"(m0a1), [m0w0] "s"(m0w0), [m0w1] "s"(m0w1), [m0s] "s"(m0s), [asoff] "s"(a_soff), [wsoff] "s"(w_soff),
-          [wave] "s"(wave)
-        : "memory", "scc");
-    uint32_t hq4 = 0;  // PRESHIFT: per byte the q high bits (see half_step)
+    asm volatile(I8_READS_4X4
+                 "ds_read_b128 %[wr0], %[fwa] offset:%c[wimm]\n\tds_read_b128 %[wr1], %[fwb] offset:%c[wimm]\n\t"
+                 "ds_read_u8 %[sv], %[fs] offset:%c[wimm]\n\t"
+                 I8_DMA(m0a0, av0, ars, asoff) I8_DMA(m0a1, av1, ars, asoff) I8_DMA(m0w0, wv0, wrs, wsoff) I8_DMA(m0w1, wv1, wrs, wsoff)
+                 I8_DMA_SHIFT "s_waitcnt vmcnt(8) lgkmcnt(0)"
+                 : I8_OUTS_4X4(xa), [wr0] "=&v"(wr0), [wr1] "=&v"(wr1), [sv] "=&v"(sv)
+                 : [fa0] "v"(fa_lo[0]), [fa1] "v"(fa_lo[1]), [fa2] "v"(fa_lo[2]), [fa3] "v"(fa_lo[3]), [aimm] "i"(A_IMM), [fwa] "v"(fw_a),
+                   [fwb] "v"(fw_b), [fs] "v"(fs_addr), [wimm] "i"(SLOT * W_SLOT), [av0] "v"(a_voff[0]), [av1] "v"(a_voff[1]),
+                   [wv0] "v"(w_voff0), [wv1] "v"(w_voff1), [sv4] "v"(s_voff), [ars] "s"(a_rs), [wrs] "s"(w_rs), [m0a0] "s"(m0a0),
+                   [m0a1] "s"(m0a1), [m0w0] "s"(m0w0), [m0w1] "s"(m0w1), [m0s] "s"(m0s), [asoff] "s"(a_soff), [wsoff] "s"(w_soff),
+                   [wave] "s"(wave)
+                 : "memory", "scc");
+    uint32_t hq4 = 0;  // PRESHIFT: per byte the q high bits (expand_w)
     if constexpr (MODE == I8_MODE_PRESHIFT) hq4 = ((0xFF00u >> sv) & 0xFFu) * 0x01010101u;
-    auto expand = [&](uint32_t w0, uint32_t w1) {
-      if constexpr (MODE == I8_MODE_PRESHIFT1) {
-        const uint32_t a0 = (w0 << 4) & 0xF0F0F0F0u, b0 = w0 & 0xF0F0F0F0u, a1 = (w1 << 4) & 0xF0F0F0F0u, b1 = w1 & 0xF0F0F0F0u;
-        return (i32x4){(int)((a0 & 0x80808080u) | (a0 >> sv)), (int)((b0 & 0x80808080u) | (b0 >> sv)),
-                       (int)((a1 & 0x80808080u) | (a1 >> sv)), (int)((b1 & 0x80808080u) | (b1 >> sv))};
-      } else if constexpr (MODE == I8_MODE_PRESHIFT) {
-        auto one = [&](uint32_t w, uint32_t& lo, uint32_t& hi) {
-          const uint32_t t = w << 4;
-          const uint32_t m_hi = __builtin_amdgcn_perm(w, w << 8, 0x0B090A08u), m_lo = __builtin_amdgcn_perm(t, w << 12, 0x0B090A08u);
-          lo = (m_lo & hq4) | ((t & 0xF0F0F0F0u) >> sv);
-          hi = (m_hi & hq4) | ((w & 0xF0F0F0F0u) >> sv);
-        };
-        uint32_t l0, h0, l1, h1;
-        one(w0, l0, h0);
-        one(w1, l1, h1);
-        return (i32x4){(int)l0, (int)h0, (int)l1, (int)h1};
-      } else {
-        return (i32x4){(int)((w0 << 4) & 0xF0F0F0F0u), (int)(w0 & 0xF0F0F0F0u), (int)((w1 << 4) & 0xF0F0F0F0u), (int)(w1 & 0xF0F0F0F0u)};
-      }
-    };
+    auto expand = [&](uint32_t w0, uint32_t w1) { return expand_w(mode_c, hq4, w0, w1); };
     wf[0] = expand(wr0[0], wr0[1]);
     asm volatile("s_barrier" : "+v"(wf[0])::"memory");
     __builtin_amdgcn_s_setprio(0);
@@ -1408,20 +1308,13 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     wf[1] = expand(wr0[2], wr0[3]);
     wf[2] = expand(wr1[0], wr1[1]);
     wf[3] = expand(wr1[2], wr1[3]);
-#define I8_SLOT(NV)                                     \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
-    if constexpr ((NV) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (NV), 0);
     if constexpr (MODE != I8_MODE_FOLD) {
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
         for (int t = 0; t < 4; ++t) R[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][ks], wf[ks], R[t], 0, 0, 0);
       if constexpr (MODE == I8_MODE_PRESHIFT || MODE == I8_MODE_PRESHIFT1) {
-        // issue order: the expand of slice ks + 1 (<= 22 vector instructions) in the shadow of the four MFMAs of slice ks
-        I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5)
-        I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5)
-        I8_SLOT(6) I8_SLOT(6) I8_SLOT(5) I8_SLOT(5)
-        I8_SLOT(0) I8_SLOT(0) I8_SLOT(0) I8_SLOT(0)
+        I8_SCHED_PRESHIFT
       }
     } else {
       const i32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1431,18 +1324,11 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
         G4[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][0], wf[0], z, 0, 0, 0);
 #pragma unroll
         for (int ks = 1; ks < 4; ++ks) G4[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xa[t][ks], wf[ks], G4[t], 0, 0, 0);
-        if (t > 0) {
-#pragma unroll
-          for (int j = 0; j < 16; ++j) R[t - 1][j] = (int)(((uint32_t)G4[t - 1][j] << sv) + (uint32_t)R[t - 1][j]);
-        }
+        if (t > 0) fold_group(R[t - 1], G4[t - 1]);
       }
       Gd = G4[3];
-      I8_SLOT(6) I8_SLOT(6) I8_SLOT(6) I8_SLOT(0)
-      I8_SLOT(0) I8_SLOT(4) I8_SLOT(4) I8_SLOT(4)
-      I8_SLOT(4) I8_SLOT(4) I8_SLOT(4) I8_SLOT(4)
-      I8_SLOT(4) I8_SLOT(5) I8_SLOT(5) I8_SLOT(6)
+      I8_SCHED_FOLD(0)
     }
-#undef I8_SLOT
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -1462,22 +1348,10 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     asm volatile("" ::: "memory");
     issue_wq(w_base, ktn, std::integral_constant<int, slot_new>{});
     i32x4 xa[4][4];  // [token tile][slice]
-    asm volatile(
-        "ds_read_b128 %[x00], %[fa0] offset:%c[aimm]\n\tds_read_b128 %[x01], %[fa1] offset:%c[aimm]\n\t"
-        "ds_read_b128 %[x02], %[fa2] offset:%c[aimm]\n\tds_read_b128 %[x03], %[fa3] offset:%c[aimm]\n\t"
-        "ds_read_b128 %[x10], %[fa0] offset:%c[aimm]+4096\n\tds_read_b128 %[x11], %[fa1] offset:%c[aimm]+4096\n\t"
-        "ds_read_b128 %[x12], %[fa2] offset:%c[aimm]+4096\n\tds_read_b128 %[x13], %[fa3] offset:%c[aimm]+4096\n\t"
-        "ds_read_b128 %[x20], %[fa0] offset:%c[aimm]+8192\n\tds_read_b128 %[x21], %[fa1] offset:%c[aimm]+8192\n\t"
-        "ds_read_b128 %[x22], %[fa2] offset:%c[aimm]+8192\n\tds_read_b128 %[x23], %[fa3] offset:%c[aimm]+8192\n\t"
-        "ds_read_b128 %[x30], %[fa0] offset:%c[aimm]+12288\n\tds_read_b128 %[x31], %[fa1] offset:%c[aimm]+12288\n\t"
-        "ds_read_b128 %[x32], %[fa2] offset:%c[aimm]+12288\n\tds_read_b128 %[x33], %[fa3] offset:%c[aimm]+12288\n\t"
-        "s_waitcnt vmcnt(16) lgkmcnt(0)"
-        : [x00] "=&v"(xa[0][0]), [x01] "=&v"(xa[0][1]), [x02] "=&v"(xa[0][2]), [x03] "=&v"(xa[0][3]), [x10] "=&v"(xa[1][0]),
-          [x11] "=&v"(xa[1][1]), [x12] "=&v"(xa[1][2]), [x13] "=&v"(xa[1][3]), [x20] "=&v"(xa[2][0]), [x21] "=&v"(xa[2][1]),
-          [x22] "=&v"(xa[2][2]), [x23] "=&v"(xa[2][3]), [x30] "=&v"(xa[3][0]), [x31] "=&v"(xa[3][1]), [x32] "=&v"(xa[3][2]),
-          [x33] "=&v"(xa[3][3])
-        : [fa0] "v"(fa_lo[0]), [fa1] "v"(fa_lo[1]), [fa2] "v"(fa_lo[2]), [fa3] "v"(fa_lo[3]), [aimm] "i"(A_IMM)
-        : "memory");
+    asm volatile(I8_READS_4X4 "s_waitcnt vmcnt(16) lgkmcnt(0)"
+                 : I8_OUTS_4X4(xa)
+                 : [fa0] "v"(fa_lo[0]), [fa1] "v"(fa_lo[1]), [fa2] "v"(fa_lo[2]), [fa3] "v"(fa_lo[3]), [aimm] "i"(A_IMM)
+                 : "memory");
     asm volatile("s_barrier" ::: "memory");
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -1515,31 +1389,17 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     const uint32_t m0w0 = m0_w + WS_NEW * W8_SLOT, m0w1 = m0w0 + 1024;
     i32x4 xk[8][2];  // [token tile][slice of this half]
     i32x4 w0, w1;    // the half's weight fragments: slices 2P, 2P + 1
-    asm volatile(
-        "ds_read_b128 %[x00], %[fa0] offset:%c[aimm]\n\tds_read_b128 %[x01], %[fa1] offset:%c[aimm]\n\t"
-        "ds_read_b128 %[x10], %[fa0] offset:%c[aimm]+4096\n\tds_read_b128 %[x11], %[fa1] offset:%c[aimm]+4096\n\t"
-        "ds_read_b128 %[x20], %[fa0] offset:%c[aimm]+8192\n\tds_read_b128 %[x21], %[fa1] offset:%c[aimm]+8192\n\t"
-        "ds_read_b128 %[x30], %[fa0] offset:%c[aimm]+12288\n\tds_read_b128 %[x31], %[fa1] offset:%c[aimm]+12288\n\t"
-        "ds_read_b128 %[x40], %[fa0] offset:%c[aimm]+16384\n\tds_read_b128 %[x41], %[fa1] offset:%c[aimm]+16384\n\t"
-        "ds_read_b128 %[x50], %[fa0] offset:%c[aimm]+20480\n\tds_read_b128 %[x51], %[fa1] offset:%c[aimm]+20480\n\t"
-        "ds_read_b128 %[x60], %[fa0] offset:%c[aimm]+24576\n\tds_read_b128 %[x61], %[fa1] offset:%c[aimm]+24576\n\t"
-        "ds_read_b128 %[x70], %[fa0] offset:%c[aimm]+28672\n\tds_read_b128 %[x71], %[fa1] offset:%c[aimm]+28672\n\t"
-        "s_mov_b32 m0, %[m0w0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv0], %[wrs], %[wsoff] offen lds\n\t"
-        "s_mov_b32 m0, %[m0w1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[wv1], %[wrs], %[wsoff] offen lds\n\t"
-        "s_mov_b32 m0, %[m0a0]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av0], %[ars], %[asoff] offen lds\n\t"
-        "s_mov_b32 m0, %[m0a1]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[av1], %[ars], %[asoff] offen lds\n\t"
-        "s_waitcnt vmcnt(10)\n\t"
-        "ds_read_b128 %[w0], %[fw0] offset:%c[wimm]\n\tds_read_b128 %[w1], %[fw1] offset:%c[wimm]\n\t"
-        "s_waitcnt vmcnt(%c[vmend]) lgkmcnt(0)"
-        : [x00] "=&v"(xk[0][0]), [x01] "=&v"(xk[0][1]), [x10] "=&v"(xk[1][0]), [x11] "=&v"(xk[1][1]), [x20] "=&v"(xk[2][0]),
-          [x21] "=&v"(xk[2][1]), [x30] "=&v"(xk[3][0]), [x31] "=&v"(xk[3][1]), [x40] "=&v"(xk[4][0]), [x41] "=&v"(xk[4][1]),
-          [x50] "=&v"(xk[5][0]), [x51] "=&v"(xk[5][1]), [x60] "=&v"(xk[6][0]), [x61] "=&v"(xk[6][1]), [x70] "=&v"(xk[7][0]),
-          [x71] "=&v"(xk[7][1]), [w0] "=&v"(w0), [w1] "=&v"(w1)
-        : [fa0] "v"(SLOT == 2 ? fa_hi[2 * P] : fa_lo[2 * P]), [fa1] "v"(SLOT == 2 ? fa_hi[2 * P + 1] : fa_lo[2 * P + 1]), [aimm] "i"(A_IMM),
-          [fw0] "v"(fw8_0), [fw1] "v"(fw8_1), [wimm] "i"(WS * W8_SLOT), [av0] "v"(a_voff[2 * P]), [av1] "v"(a_voff[2 * P + 1]),
-          [wv0] "v"(w_voff0), [wv1] "v"(w_voff1), [ars] "s"(a_rs), [wrs] "s"(w_rs), [m0a0] "s"(m0a0), [m0a1] "s"(m0a1), [m0w0] "s"(m0w0),
-          [m0w1] "s"(m0w1), [asoff] "s"(a_soff), [wsoff] "s"(w_soff), [vmend] "i"(P == 1 ? 8 : 10)
-        : "memory");
+    asm volatile(I8_READS_8X2
+                 I8_DMA(m0w0, wv0, wrs, wsoff) I8_DMA(m0w1, wv1, wrs, wsoff) I8_DMA(m0a0, av0, ars, asoff) I8_DMA(m0a1, av1, ars, asoff)
+                 "s_waitcnt vmcnt(10)\n\t"
+                 "ds_read_b128 %[w0], %[fw0] offset:%c[wimm]\n\tds_read_b128 %[w1], %[fw1] offset:%c[wimm]\n\t"
+                 "s_waitcnt vmcnt(%c[vmend]) lgkmcnt(0)"
+                 : I8_OUTS_8X2(xk), [w0] "=&v"(w0), [w1] "=&v"(w1)
+                 : [fa0] "v"(SLOT == 2 ? fa_hi[2 * P] : fa_lo[2 * P]), [fa1] "v"(SLOT == 2 ? fa_hi[2 * P + 1] : fa_lo[2 * P + 1]), [aimm] "i"(A_IMM),
+                   [fw0] "v"(fw8_0), [fw1] "v"(fw8_1), [wimm] "i"(WS * W8_SLOT), [av0] "v"(a_voff[2 * P]), [av1] "v"(a_voff[2 * P + 1]),
+                   [wv0] "v"(w_voff0), [wv1] "v"(w_voff1), [ars] "s"(a_rs), [wrs] "s"(w_rs), [m0a0] "s"(m0a0), [m0a1] "s"(m0a1), [m0w0] "s"(m0w0),
+                   [m0w1] "s"(m0w1), [asoff] "s"(a_soff), [wsoff] "s"(w_soff), [vmend] "i"(P == 1 ? 8 : 10)
+                 : "memory");
     asm volatile("s_barrier" : "+v"(w0)::"memory");
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -1552,6 +1412,16 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
     asm volatile("s_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
   };
+#undef I8_READS_4X4
+#undef I8_OUTS_4X4
+#undef I8_READS_8X2
+#undef I8_OUTS_8X2
+#undef I8_DMA
+#undef I8_DMA3
+#undef I8_DMA_SHIFT
+#undef I8_SLOT
+#undef I8_SCHED_PRESHIFT
+#undef I8_SCHED_FOLD
   using std::integral_constant;
   auto main_loop = [&](auto mode_c) {
     if constexpr (W8D) {
@@ -1618,14 +1488,9 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the prefetches issued past the end of K have drained
   if (!late) asm volatile("s_barrier" ::: "memory");
-#ifdef LQER_CLOCKPROBE
-  I8_STAMP(cp_c[2], cp_r[2]);
-#endif
+  I8_CP(I8_STAMP(cp_c[2], cp_r[2]);)
   if constexpr (SHIFT) {  // FOLD: the last half-step's last tile
-    if (tile_mode == I8_MODE_FOLD) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) R[NT - 1][j] = (int)(((uint32_t)Gd[j] << sv) + (uint32_t)R[NT - 1][j]);
-    }
+    if (tile_mode == I8_MODE_FOLD) fold_group(R[NT - 1], Gd);
   }
   // every wave is past its last LDS read of the ring: the epilogue may overwrite it after one more barrier
   asm volatile("s_barrier" ::: "memory");
@@ -1642,7 +1507,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
         load_tables(m0);
         const bool miss = (g.tuning & LQER_TUNE_AMAX_XCH_MISS) != 0;  // (test knob: take the fall-back)
         if (!wg_any(t_bad != 0) && !miss) break;
-        if (miss || ++sweeps > LQER_XCH_SWEEPS) {
+        if (miss || ++sweeps > XCH_SWEEPS) {
           for (int sg = 0; sg < LQER_AMAX_NSEG; ++sg) mrx_item((m0 / BM) * LQER_AMAX_NSEG + sg);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           load_tables(m0);
@@ -1652,12 +1517,12 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       }
       write_tables();
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef LQER_CLOCKPROBE
-      if (first) {
-        I8_STAMP(cp_p[2], cp_x);  // the band's granules seen, tables written
-        cp_tries = (unsigned long long)sweeps;
-      }
-#endif
+      I8_CP(
+        if (first) {
+          I8_STAMP(cp_p[2], cp_x);  // the band's granules seen, tables written
+          cp_tries = (unsigned long long)sweeps;
+        }
+      )
     }
   }
   const int vb_next = vb + (int)gridDim.x;
@@ -1725,6 +1590,8 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   const int64_t bt_limb = (int64_t)g.Np * g.rp;
   if constexpr (LOWRANK && !XCH) {
     // (exact range: the 128-byte pieces of a narrow xAq run into the next row, past the last row of the buffer they read 0)
+    // (xaq_panel_dma's loop, kept apart: the epilogue's own laundered ids, its stage base and up to two panels - three more arguments,
+    // and every instantiation without an exchange runs this one)
     const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(g.xaq + (int64_t)m0 * g.xaq_ld), 0, BM * g.xaq_ld * 2, 0x00020000);
     const int npanel = (g.rp + 63) >> 6;
     for (int pn = 0; pn < npanel; ++pn)
@@ -1760,9 +1627,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
   }
   const float ws = XCH ? ws_x : wscale[n];
   const float bv = XCH ? bv_x : (g.bias ? g.bias[n] : 0.f);
-#ifdef LQER_CLOCKPROBE
-  I8_STAMP(cp_a, cp_x);
-#endif
+  I8_CP(I8_STAMP(cp_a, cp_x);)
   // the integer tile -> v = float(R) * xs[m] * ws[n] + bias[n], in place, two elements per packed fp32 instruction
   typedef __attribute__((ext_vector_type(2))) float f2;
   {
@@ -1791,22 +1656,11 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       asm volatile("" : "+v"(R[i]));
     }
   }
-#ifdef LQER_CLOCKPROBE
-  asm volatile("" ::"v"(R[0][0]), "v"(R[NT - 1][15]));
-  I8_STAMP(cp_b, cp_x);
-#endif
-  // exchange: the row's B_out scales from the gathered maximum (write_tables' arithmetic), in front of the barrier below
-  auto xch_tables = [&](int e_row) {  // (e_row = block_exponent of the row's maximum)
-    if constexpr (XCH_OK) {
-      int up = g.bout.mbits - e_row;
-      up = up > 126 ? 126 : (up < -126 ? -126 : up);
-      const uint32_t upb = (uint32_t)(127 + up) << 23;
-      asm volatile("ds_write_b32 %0, %1 offset:1024\n\tds_write_b32 %0, %2 offset:2048\n\tds_write_b32 %0, %3 offset:3072" ::"v"(
-                       lds0 + EP_TAB + 4 * tid_e),
-                   "v"(upb), "v"((uint32_t)(127 - up) << 23), "v"(1e-9f * __uint_as_float(upb))
-                   : "memory");
-    }
-  };
+  I8_CP(
+    asm volatile("" ::"v"(R[0][0]), "v"(R[NT - 1][15]));
+    I8_STAMP(cp_b, cp_x);
+  )
+  // exchange: the row's B_out scales from the gathered maximum (write_tables' routine), in front of the barrier below
   if constexpr (XCH_OK) {
     if (xch && wave < 2) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wave's requests: the granules - and the xAq pieces, awaited below anyway)
@@ -1837,9 +1691,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
       uint32_t bad = stale();
       if (ok && __builtin_amdgcn_ballot_w64(bad != 0) != 0) {  // (rare: some granule of this wave's 64 rows is not there yet)
         for (int tries = 0; tries < XCH_SWEEPS && __builtin_amdgcn_ballot_w64(bad != 0) != 0; ++tries) {
-#ifdef LQER_CLOCKPROBE
-          cp_tries = (unsigned long long)(tries + 1);
-#endif
+          I8_CP(cp_tries = (unsigned long long)(tries + 1);)
           __builtin_amdgcn_s_sleep(8);
           if (bad != 0) {
 #pragma unroll
@@ -1859,16 +1711,14 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
           const uint32_t v0 = 2 * j < ntile ? 0xffu : 0u, v1 = 2 * j + 1 < ntile ? 0xffu : 0u;
           eb = max(eb, max((gq[j][0] >> sh) & v0, (gq[j][2] >> sh) & v1));
         }
-        xch_tables((int)eb + g.bout.emin);
+        write_bout_scales(lds0 + EP_TAB + 4 * tid_e, (int)eb + g.bout.emin);
       } else {
         asm volatile("ds_write_b32 %0, %1 offset:1020" ::"v"(lds0 + EP_TAB), "v"(1u) : "memory");  // the workgroup's vote
       }
     }
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#ifdef LQER_CLOCKPROBE
-  I8_STAMP(cp_cc, cp_x);
-#endif
+  I8_CP(I8_STAMP(cp_cc, cp_x);)
   __syncthreads();  // the xAq tile has landed for every wave
   if constexpr (XCH_OK) {
     if (xch) {
@@ -1890,11 +1740,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
                 const bf16x8 xfr = *(const bf16x8*)(g.xaq + (int64_t)(m0 + 32 * u + l31) * g.xaq_ld + ks * 16 + 8 * lh);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr, xfr, acc, 0, 0, 0);
               }
-            float m = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; k += 2) m = fmaxf(fmaxf(m, fabsf(acc[k])), fabsf(acc[k + 1]));
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-            m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+            const float m = row_absmax(acc);
             if (u == 0) mx[0] = fmaxf(mx[0], m);
             else if (u == 1) mx[1] = fmaxf(mx[1], m);
             else if (u == 2) mx[2] = fmaxf(mx[2], m);
@@ -1902,14 +1748,12 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
           }
         }
         const float r = xch_reduce(mx);
-        if (tid_e < BM) xch_tables(block_exponent(r, g.bout));
+        if (tid_e < BM) write_bout_scales(lds0 + EP_TAB + 4 * tid_e, block_exponent(r, g.bout));
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       }
     }
   }
-#ifdef LQER_CLOCKPROBE
-  I8_STAMP(cp_e1, cp_e1r);
-#endif
+  I8_CP(I8_STAMP(cp_e1, cp_e1r);)
   // xAq fragment addresses: row l31 (+ 32 i: + 4096 B), chunk 2 (ks & 3) + lh, panel ks >> 2
   uint32_t xaddr[4];
 #pragma unroll
@@ -2031,12 +1875,12 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
         yv[j] = v[0], yv[j + 1] = v[1];
       }
     }
-#ifdef LQER_CLOCKPROBE
-    if (i == 1) {  // tiles 0 and 1 computed (not yet stored)
-      asm volatile("" ::"v"(yv[0]), "v"(yv[15]));
-      I8_STAMP(cp_e2, cp_e2r);
-    }
-#endif
+    I8_CP(
+      if (i == 1) {  // tiles 0 and 1 computed (not yet stored)
+        asm volatile("" ::"v"(yv[0]), "v"(yv[15]));
+        I8_STAMP(cp_e2, cp_e2r);
+      }
+    )
     if constexpr (DT == LQER_F32) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) {

@@ -2,9 +2,12 @@
 """The int8 main loop against the bf16 256-row kernel on the SAME Linear (W4, per-token A8, rank r, fp16 A / B, per-row
 B_out: the C4 configuration), interleaved rounds in one process: lqer_linear_gemm alone (activation images prepared
 once per route), and the whole forward (quantizer + side GEMM + pre-pass + GEMM).
-usage: python tools/ab_i8.py [--M 16384 --K 5120 --N 5120 --r 64 --wblock 128] [--rounds 8 --iters 10]"""
+usage: python tools/ab_i8.py [--M 16384 --K 5120 --N 5120 --r 64 --wblock 128 --wbits 4] [--rounds 8 --iters 10]
+--lib PATH times another build of the library (A/B of two trees: one process per tree, alternating; every line carries the slowest
+round too, and --json FILE keeps the rounds)."""
 import argparse
 import ctypes as C
+import json
 import os
 import sys
 
@@ -27,6 +30,8 @@ def main():
     ap.add_argument("--N", type=int, default=5120)
     ap.add_argument("--r", type=int, default=64)
     ap.add_argument("--wblock", type=int, default=128)
+    ap.add_argument("--wbits", type=int, default=4, help="8: 8-bit weights, one block per row (the W8A8 format; use with --only int8)")
+    ap.add_argument("--json", default=None, help="write every round of every variant, in us, to this file")
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--lib", default=None, help="path of another build of liblqer_hip.so")
@@ -37,7 +42,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     M, K, N, r = a.M, a.K, a.N, a.r
-    qc = dict(INT_Q, w_quantizer=_bfp(4, [1, a.wblock], False))
+    qc = dict(INT_Q, w_quantizer=_bfp(a.wbits, [1, -1 if a.wbits > 4 else a.wblock], False))
     x, W, A, B = make_case(M, K, N, r, seed=0, quantize_ab=False)
     mod = lqer_amd.LinearFlexibleLqer(K, N, bias=False, q_config=qc, l_config={"rank": r})
     mod.load_state_dict({"weight": W, "A": A, "B": B})
@@ -112,6 +117,7 @@ def main():
         print("128-row vs 256-row int8 tiles bit-identical:", bool(torch.equal(outs["i8r128"], outs["i8r256"])),
               " default tile rows:", L.lqer_gemm_tile_rows(C.byref(mod._desc()), M, _lib.F16))
     fl = 2.0 * M * K * N + 2.0 * M * r * N
+    record = {}
     for what, fn in (("GEMM alone (incl. B_out pre-pass)", lambda rt: gemm(rt)), ("whole forward", lambda rt: (quant(rt), gemm(rt)))):
         times = {k: [] for k in routes}
         for _ in range(a.rounds):
@@ -126,7 +132,11 @@ def main():
         for name in routes:
             t = sorted(times[name])
             med = t[len(t) // 2]
-            print(f"{what:36s} {name:5s} median {med:9.1f} us  min {t[0]:9.1f} us   {fl / med / 1e6:8.1f} T(FL)OP/s")
+            print(f"{what:36s} {name:5s} median {med:9.1f} us  min {t[0]:9.1f} us  max {t[-1]:9.1f} us   {fl / med / 1e6:8.1f} T(FL)OP/s")
+            record.setdefault(what, {})[name] = times[name]
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"shape_m_k_n_r": [M, K, N, r], "wbits": a.wbits, "iters": a.iters, "lib": _lib.LIB_PATH, "rounds_us": record}, f)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Device code of two builds, kernel by kernel: codeobj_diff.py OBJDIR_A OBJDIR_B  (make OBJDIR=...; no GPU needed).
+"""Device code of two builds, kernel by kernel: codeobj_diff.py [--kernels] OBJDIR_A OBJDIR_B  (make OBJDIR=...; no GPU needed).
 For every X.o of either directory: the gfx950 code object's FUNC / OBJECT symbols (name, size), each function's disassembly with
-addresses stripped, and the amdhsa.kernels notes (registers, LDS, scratch, kernarg size) must be equal.  Exit status 1 if not."""
+addresses (pc-relative distances to global variables included) stripped, and the amdhsa.kernels notes (registers, LDS, scratch, kernarg size) must be equal.  Exit status 1 if not.
+--kernels: one line per differing kernel (its symbol: template arguments as I..E) - instruction count A/B and the notes that differ - instead of the first eight
+differences of a file."""
 import os
 import re
 import subprocess
@@ -29,7 +31,12 @@ def device_code(obj, tmp):
         if m:
             name = m.group(1)
         elif name and ln.strip() not in ("", "..."):  # ("...": the padding behind the last function)
-            code.setdefault(name, []).append(re.sub(r"\s*// [0-9A-Fa-f]+:.*$|<[^>]*\+0x[0-9a-f]+>", "", ln).strip())
+            ins = re.sub(r"\s*// [0-9A-Fa-f]+:.*$|<[^>]*\+0x[0-9a-f]+>", "", ln).strip()
+            # the low half of a pc-relative address (s_getpc_b64, then s_add_u32 with the distance to a global variable as a literal): an
+            # address like the others - it moves whenever a function between the two changes its size
+            if code.get(name) and code[name][-1].startswith("s_getpc_b64"):
+                ins = re.sub(r"^(s_add_u32 s\d+, s\d+), 0x[0-9a-f]+$", r"\1, <pc-relative>", ins)
+            code.setdefault(name, []).append(ins)
     notes = run(f"{LLVM}/llvm-readelf", "--notes", co)
     keys = r"\.(\w*gpr_count|\w*_spill_count|\w+_segment_\w*size|max_flat_workgroup_size|uses_dynamic_stack):\s+(\S+)"
     meta = {m.group(1): sorted(re.findall(keys, blk)) for blk in notes.split("  - .") if (m := re.search(r"\.name:\s+(\S+)", blk))
@@ -37,7 +44,16 @@ def device_code(obj, tmp):
     return syms, code, meta
 
 
-def main(a, b):
+def per_kernel(A, B):
+    """One line per function whose code or notes differ: instruction count A/B, then every note as key A/B that is not equal."""
+    names = sorted(k for k in set(A[1]) | set(B[1]) | set(A[2]) | set(B[2]) if A[1].get(k) != B[1].get(k) or A[2].get(k) != B[2].get(k))
+    for k in names:
+        na, nb = dict(A[2].get(k, ())), dict(B[2].get(k, ()))
+        notes = [f"{key} {na.get(key, '-')}/{nb.get(key, '-')}" for key in sorted(set(na) | set(nb)) if na.get(key) != nb.get(key)]
+        print(f"  {k}: instructions {len(A[1].get(k, ()))}/{len(B[1].get(k, ()))}; " + (", ".join(notes) if notes else "notes equal"))
+
+
+def main(a, b, kernels=False):
     bad = 0
     for o in sorted({f for d in (a, b) for f in os.listdir(d) if f.endswith(".o")}):
         pa, pb = os.path.join(a, o), os.path.join(b, o)
@@ -53,9 +69,12 @@ def main(a, b):
         diff = [f"{what} {k}" for what, x, y in zip(("symbol", "code", "notes"), A, B) for k in sorted(set(x) | set(y)) if x.get(k) != y.get(k)]
         assert len(A[1]) >= len(A[2]), f"{o}: {len(A[1])} functions disassembled for {len(A[2])} kernels"
         print(f"{o}: {len(A[0])} symbols, {len(A[1])} functions, {len(A[2])} kernels: " + ("identical" if not diff else "DIFFERENT: " + "; ".join(diff[:8])))
+        if kernels and diff:
+            per_kernel(A, B)
         bad += bool(diff)
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = [x for x in sys.argv[1:] if x != "--kernels"]
+    sys.exit(main(args[0], args[1], kernels="--kernels" in sys.argv[1:]))
