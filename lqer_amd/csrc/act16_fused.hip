@@ -4,18 +4,23 @@
 // 4.9-us launch-floor kernel beside a 56-us GEMM at BASELINE configs[1] and resisted three fusions into its neighbours (NOTEBOOK 7-9).
 //
 // A workgroup owns ROWS = 8 token rows over ALL of K (no partial tiles in HBM, no reduce launch, no cross-workgroup protocol), and inside
-// it every WAVE is a pipeline of its own over slabs of 512 k (slab s belongs to wave s % 8) - a block's exponent needs nothing outside
-// its 16 elements, so nothing waits for a whole row:
-//   load     the slab of each of the 8 rows: one 16-byte request per lane and row, a contiguous KiB per wave instruction;
+// it every WAVE is a pipeline of its own over slabs of 512 k (slab s belongs to wave s % 8), each slab in four QUARTERS of 128 k - a
+// block's exponent needs nothing outside its 16 elements, so nothing waits for a whole row, and a 32-k MFMA step needs all 8 rows of its
+// k only:
+//   load     one 16-byte request per lane covers 4 rows x 256 B of a quarter (two whole 128-byte lines per row), two requests a quarter
+//            of all 8 rows; the slab's eight requests go out in front of everything else the kernel does, quarter 0 first, from
+//            arguments that arrive preloaded in SGPRs (Makefile: A16_FLAGS);
 //   quantize a block of 16 = two neighbouring lanes (the maximum crosses with one DPP); k_quant_xa16's arithmetic (mxint16_bf16_fast or,
 //            at extreme exponents, the element routine) on the lane's 8 values -> 8 bf16 = 16 bytes, stored to the activation image
-//            (a KiB per wave instruction) and to the wave's PRIVATE LDS slab [8 rows][1040 B] - no workgroup barrier;
-//   multiply 16 steps of v_mfma_f32_16x16x32_bf16: the 8 rows as rows 0-7 of the 16-row operand (one ds_read_b128 per step: row
-//            lane & 7, chunk 4 t + lane / 16; the pitch of 1040 B keeps a 16-lane group on 16 distinct bank quads), A^T fragments as
-//            ONE coalesced 16-byte load per lane from the fragment-major copy behind the bf16 image (lqer_a_b16_prepare), both halves of
-//            the slab's fragments requested in front of the quantizer's arithmetic;
+//            and to the wave's PRIVATE LDS slab [8 rows][1040 B] - no workgroup barrier;
+//   multiply as soon as a quarter of all 8 rows is quantized, its 4 steps of v_mfma_f32_16x16x32_bf16 while the later quarters are still
+//            arriving: the 8 rows as rows 0-7 of the 16-row operand (one ds_read_b128 per step: row lane & 7, chunk 4 t + lane / 16; the
+//            pitch of 1040 B keeps a 16-lane group on 16 distinct bank quads), A^T fragments as ONE coalesced 16-byte load per lane from
+//            the fragment-major copy behind the bf16 image (lqer_a_b16_prepare), in two register sets; steps ascending in one
+//            accumulator chain per rank tile, whatever the order of the loads;
 //   finally  the 8 waves' partial tiles through LDS, summed in wave order (fixed: run-to-run bit-stable), A_out exactly as k_xa_reduce4.
 // The image is bit for bit k_quant_xa16's; x A is summed in another order (xAq inside the summation-order envelope, tests/_envelope.py).
+// Both are bit for bit what the row-major body of round 6 wrote (tests/test_gpu_act16_golden.py).
 #include "common.h"
 
 namespace lqer {
@@ -35,135 +40,188 @@ __device__ unsigned long long* g_a16_stamp_buf = nullptr;  // diagnostic build: 
 #endif
 
 template <int DT, int RT>
-__global__ __launch_bounds__(512) void k_act16_fused(const void* __restrict__ x, int64_t M, int64_t K, int64_t ld, QP qx, bf16_t* __restrict__ xq,
-                                                      int64_t Kp, const bf16_t* __restrict__ a_frag, QP qa, int L_aout, bf16_t* __restrict__ xaq) {
+__global__ __launch_bounds__(512) void k_act16_fused(const void* __restrict__ x, int64_t M, int64_t ld, int64_t K, int64_t Kp,
+                                                      const bf16_t* __restrict__ a_frag, bf16_t* __restrict__ xq, bf16_t* __restrict__ xaq, QP qx, QP qa,
+                                                      int L_aout) {
   constexpr int RP = 16 * RT;
-  constexpr int HB = RT == 8 ? 2 : (RT == 4 ? 4 : 8);  // steps per part of a slab (16 / HB parts, two register sets of HB x RT fragments: <= 128 registers)
-  constexpr int NPART = 16 / HB;
+  constexpr int QK = SLAB / 4, QS = QK / 32;  // a quarter of a slab: 128 k = 4 MFMA steps
+  constexpr int HB = RT == 4 ? 2 : 4;         // steps per fragment part: two register sets of HB x RT fragments (<= 32 registers each)
+  constexpr int NP = QS / HB;                 // parts per quarter; part p of a slab (steps HB p .. HB p + HB - 1) lives in set p & 1
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char* const wb = smem + (size_t)wave * ROWS * PITCH;                 // this wave's slab: [ROWS][PITCH]
-  float* const red = (float*)(smem + (size_t)WAVES * ROWS * PITCH);             // [WAVES][ROWS][RP] partial tiles
   const int64_t m0 = (int64_t)blockIdx.x * ROWS;
-  const int nslab = (int)((Kp + SLAB - 1) / SLAB);
-  const int g = lane >> 4;
-  const unsigned char* const tok = wb + (lane & 7) * PITCH + 16 * g;  // + 64 t: row lane & 7, chunk 4 t + g
-  const u32x4* const fr = (const u32x4*)a_frag + lane;                // block (step, rank tile): fr[(step * RT + tile) * 64]
-  f32x4 acc[RT];
-#pragma unroll
-  for (int t = 0; t < RT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #ifdef LQER_CLOCKPROBE
   unsigned long long cp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   A16_STAMP(0);
 #endif
-
-  for (int s = wave; s < nslab; s += WAVES) {
-    const int64_t k0 = (int64_t)s * SLAB + 8 * lane;  // this lane's 8 elements of every row
-    const bool in_img = k0 < Kp, in_x = k0 < K;       // (K % 8 == 0: a chunk is inside x or outside it as a whole)
-    u32x4 raw[ROWS];
+  // ---- the first slab's requests, in front of every other piece of setup.  Request j = 2 q + h of a slab: quarter q, rows 4 h .. 4 h + 3;
+  // the lane's row is 4 h + lane / 16, its 8 elements the chunk lane % 16 of the quarter.  Every load is unconditional (a row past M reads
+  // row M - 1, a chunk past K the row's last chunk, a step past the padded K fragment block 0; what is out of range is zeroed or multiplies
+  // zeros where it is used): straight-line code, so each wait counts exactly the requests behind the one it needs.
+  const int rl = lane >> 4, cl = lane & 15;
+  const int nslab = (int)((Kp + SLAB - 1) / SLAB), nst = (int)(Kp / 32);
+  const bool row_ok[2] = {m0 + rl < M, m0 + 4 + rl < M};
+  const bf16_t* const xr[2] = {(const bf16_t*)x + (row_ok[0] ? m0 + rl : M - 1) * ld, (const bf16_t*)x + (row_ok[1] ? m0 + 4 + rl : M - 1) * ld};
+  const u32x4* const fr = (const u32x4*)a_frag + lane;  // block (step, rank tile): fr[(step * RT + tile) * 64]
+  u32x4 raw[ROWS], fa[HB][RT], fb[HB][RT];
+  auto load_rows = [&](int s, auto j0, auto j1) {
+    asm volatile("" ::: "memory");
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-      raw[r] = (in_x && m0 + r < M) ? *(const u32x4*)((const bf16_t*)x + (m0 + r) * ld + k0) : (u32x4){0, 0, 0, 0};
-    // the slab's A^T fragments: 16 steps x RT tiles, requested behind the rows (they land under the quantizer's arithmetic).  Steps past
-    // the padded K read block 0 again and multiply zeros (the slab's tail is zero-filled below).
-    const int st0 = s * (SLAB / 32), nst = (int)(Kp / 32);
-    u32x4 fa[HB][RT], fb[HB][RT];
-    auto load_part = [&](u32x4 (&f)[HB][RT], int part) {
-#pragma unroll
-      for (int i = 0; i < HB; ++i)
-#pragma unroll
-        for (int t = 0; t < RT; ++t) {
-          const int st = st0 + part * HB + i;
-          f[i][t] = fr[((int64_t)(st < nst ? st : 0) * RT + t) * 64];
-        }
-    };
-    // (requested in the MIDDLE of the quantizer's loop, not beside the rows: the texture path's queue is shallow - a wave that issues 32
-    // fragment requests in a row stands still until the path has taken them, and with it its rows' arithmetic: act8_fused.hip found the
-    // same, tools/clock_probe_a8.py)
-    // ---- quantize: the lane's 8 values of each row; the block's other half sits in lane ^ 1
-    if (s == wave) A16_STAMP(1);  // the rows' requests are out
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      if (r == 1 && s == wave) A16_STAMP(2);  // row 0 landed and quantized
-      if (r == 2) {
-        asm volatile("" ::: "memory");
-        load_part(fa, 0);
-        asm volatile("" ::: "memory");
-      }
-      if (r == 5) {
-        asm volatile("" ::: "memory");
-        load_part(fb, 1);
-        asm volatile("" ::: "memory");
-      }
-      float v[8];
-      const uint32_t wd[4] = {raw[r][0], raw[r][1], raw[r][2], raw[r][3]};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (DT == LQER_F16) {
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-          const h2 h = __builtin_bit_cast(h2, wd[j]);
-          v[2 * j] = (float)h[0], v[2 * j + 1] = (float)h[1];
-        } else {
-          v[2 * j] = __uint_as_float(wd[j] << 16), v[2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
-        }
-      }
-      float amax = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
-      amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-      uint32_t w[4] = {0, 0, 0, 0};
-      if (amax > 0.f) {
-        const int e = block_exponent_u(amax, qx);
-        if (mxint16_fast_ok(e, qx)) {
-          mxint16_bf16_fast<DT != LQER_F16, 8>(v, e, qx, w);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, qx), e - qx.mbits));
-            const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, qx), e - qx.mbits));
-            w[i] = lo | (hi << 16);
-          }
-        }
-      }
-      const u32x4 wv = {w[0], w[1], w[2], w[3]};
-      if (in_img) *(u32x4*)(xq + (m0 + r) * Kp + k0) = wv;  // (rows up to the padded M are allocated; rows past M and k past K: zeros)
-      *(u32x4*)(wb + r * PITCH + 16 * lane) = wv;
+    for (int j = decltype(j0)::value; j < decltype(j1)::value; ++j) {
+      const int64_t k = (int64_t)s * SLAB + (j >> 1) * QK + 8 * cl;
+      raw[j] = *(const u32x4*)(xr[j & 1] + (k < K ? k : K - 8));
     }
-    if (s == wave) A16_STAMP(3);  // all rows quantized, image stores issued
-    // (the wave reads back what it wrote itself: LDS executes a wave's accesses in order - no workgroup barrier; the fence keeps the
-    // compiler from moving the reads up)
+    asm volatile("" ::: "memory");
+  };
+  // (part p of slab s: HB steps x RT tiles of A^T fragments, ONE coalesced 16-byte load per lane and block)
+  auto load_part = [&](u32x4 (&f)[HB][RT], int s, int p) {
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < HB; ++i)
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        const int st = s * (SLAB / 32) + p * HB + i;
+        f[i][t] = fr[((int64_t)(st < nst ? st : 0) * RT + t) * 64];
+      }
+    asm volatile("" ::: "memory");
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I2 = std::integral_constant<int, 2>;
+  using I4 = std::integral_constant<int, 4>;
+  using I8 = std::integral_constant<int, 8>;
+  // Loads complete in the order they were issued, so a fragment part lands behind every row requested in front of it: parts 0 and 1 go out
+  // between the rows of the quarters they belong to (the rows of quarter 0 keep the memory busy meanwhile), the later parts from inside the
+  // slab, each into the register set that a multiplied part has freed.
+  auto front = [&](int s) {
+    load_rows(s, I0{}, I2{});
+    load_part(fa, s, 0);
+    if constexpr (NP == 1) load_rows(s, I2{}, I4{});
+    load_part(fb, s, 1);
+    if constexpr (NP == 1) load_rows(s, I4{}, I8{});
+    else load_rows(s, I2{}, I8{});
+  };
+  if (wave < nslab) front(wave);
+  A16_STAMP(1);  // the first slab's requests are out
+  unsigned char* const wb = smem + (size_t)wave * ROWS * PITCH;                 // this wave's slab: [ROWS][PITCH]
+  float* const red = (float*)(smem + (size_t)WAVES * ROWS * PITCH);             // [WAVES][ROWS][RP] partial tiles
+  const int g = lane >> 4;
+  const unsigned char* const tok = wb + (lane & 7) * PITCH + 16 * g;  // + 64 t: row lane & 7, chunk 4 t + g
+  unsigned char* const wr[2] = {wb + rl * PITCH + 16 * cl, wb + (4 + rl) * PITCH + 16 * cl};  // + 256 q: the lane's chunk of quarter q
+  bf16_t* const xqr[2] = {xq + (m0 + rl) * Kp + 8 * cl, xq + (m0 + 4 + rl) * Kp + 8 * cl};    // + the quarter's first k
+  f32x4 acc[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // ---- quantize request j of slab s: the lane's 8 values of its row; the block's other half sits in lane ^ 1.  FULL: the slab lies inside K
+  auto piece = [&](int s, int j, auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    const int64_t kq = (int64_t)s * SLAB + (j >> 1) * QK, k = kq + 8 * cl;
+    const bool live = row_ok[j & 1] && (FULL || k < K);  // (K % 8 == 0: a chunk is inside x or outside it as a whole)
+    float v[8];
+    const uint32_t wd[4] = {live ? raw[j][0] : 0u, live ? raw[j][1] : 0u, live ? raw[j][2] : 0u, live ? raw[j][3] : 0u};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (DT == LQER_F16) {
+        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+        const h2 h = __builtin_bit_cast(h2, wd[i]);
+        v[2 * i] = (float)h[0], v[2 * i + 1] = (float)h[1];
+      } else {
+        v[2 * i] = __uint_as_float(wd[i] << 16), v[2 * i + 1] = __uint_as_float(wd[i] & 0xffff0000u);
+      }
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (amax > 0.f) {
+      const int e = block_exponent_u(amax, qx);
+      if (mxint16_fast_ok(e, qx)) {
+        mxint16_bf16_fast<DT != LQER_F16, 8>(v, e, qx, w);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, qx), e - qx.mbits));
+          const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, qx), e - qx.mbits));
+          w[i] = lo | (hi << 16);
+        }
+      }
+    }
+    const u32x4 wv = {w[0], w[1], w[2], w[3]};
+    if (FULL || k < Kp) *(u32x4*)(xqr[j & 1] + kq) = wv;  // (rows up to the padded M are allocated; rows past M and k past K: zeros)
+    *(u32x4*)(wr[j & 1] + 256 * (j >> 1)) = wv;
+    __builtin_amdgcn_sched_barrier(0);  // (pieces are not interleaved: each would keep its temporaries alive beside the fragment sets)
+  };
+  // ---- multiply part p: HB steps of 32 k
+  auto mult = [&](const u32x4 (&f)[HB][RT], int p) {
+    // (the wave reads back what it wrote itself: LDS executes a wave's accesses in order - no workgroup barrier; the fences keep the
+    // compiler from moving the reads up, or the next quarter's writes in front of them)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // ---- multiply: 16 steps of 32 k
-    auto half = [&](const u32x4 (&f)[HB][RT], int t0) {
-      u32x4 tk[HB];
+    __builtin_amdgcn_sched_barrier(0);
+    u32x4 tk[HB];
 #pragma unroll
-      for (int i = 0; i < HB; ++i) tk[i] = *(const u32x4*)(tok + 64 * (t0 + i));
+    for (int i = 0; i < HB; ++i) tk[i] = *(const u32x4*)(tok + 64 * (HB * p + i));
 #pragma unroll
-      for (int i = 0; i < HB; ++i)
+    for (int i = 0; i < HB; ++i)
 #pragma unroll
-        for (int t = 0; t < RT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16v8, tk[i]), __builtin_bit_cast(bf16v8, f[i][t]), acc[t], 0, 0, 0);
-    };
-    // parts alternate between the two register sets; a set is refilled (part + 2) as soon as its steps have been multiplied
-#pragma unroll
-    for (int pp = 0; pp < NPART; pp += 2) {
-      half(fa, pp * HB);
-      if (pp + 2 < NPART) load_part(fa, pp + 2);
-      half(fb, (pp + 1) * HB);
-      if (pp + 3 < NPART) load_part(fb, pp + 3);
-    }
-    // (the next slab overwrites the wave's LDS slab: its reads above must have been issued - they have, in program order)
+      for (int t = 0; t < RT; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16v8, tk[i]), __builtin_bit_cast(bf16v8, f[i][t]), acc[t], 0, 0, 0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // ---- a slab, quarter by quarter: quantize the quarter of all 8 rows as soon as it has landed, multiply its 4 steps while the later
+  // quarters are still arriving; behind the last quarter 4 steps remain.  FULL: the slab lies inside K.
+  // (Four rank tiles: a set holds half a quarter, so only quarter 0's parts can be requested in front of the later rows; the other
+  // parts would land behind the last row wherever they were multiplied, and are multiplied behind it - 12 steps.)
+  auto slab = [&](int s, auto full) {
+    [[maybe_unused]] const bool first = s == wave;
+    piece(s, 0, full), piece(s, 1, full);
+    if (first) A16_STAMP(2);  // quarter 0 landed and quantized
+    if constexpr (NP == 1) {
+      mult(fa, 0);
+      load_part(fa, s, 2);
+      piece(s, 2, full), piece(s, 3, full);
+      mult(fb, 1);
+      load_part(fb, s, 3);
+      piece(s, 4, full), piece(s, 5, full);
+      mult(fa, 2);
+      piece(s, 6, full), piece(s, 7, full);
+      if (first) A16_STAMP(3);  // the last quarter quantized, image stores issued
+      mult(fb, 3);
+    } else {
+      mult(fa, 0);
+      load_part(fa, s, 2);
+      mult(fb, 1);
+      load_part(fb, s, 3);
+#pragma unroll
+      for (int j = 2; j < 8; ++j) piece(s, j, full);
+      if (first) A16_STAMP(3);
+#pragma unroll
+      for (int p = 2; p < 4 * NP; p += 2) {
+        mult(fa, p);
+        if (p + 2 < 4 * NP) load_part(fa, s, p + 2);
+        mult(fb, p + 1);
+        if (p + 3 < 4 * NP) load_part(fb, s, p + 3);
+      }
+    }
+  };
+  for (int s = wave; s < nslab; s += WAVES) {
+    if ((int64_t)(s + 1) * SLAB <= K) slab(s, std::true_type{});
+    else slab(s, std::false_type{});
 #ifdef LQER_CLOCKPROBE
     if (s == wave) {
       asm volatile("" ::"v"(acc[0]));
-      A16_STAMP(4);  // the slab's fragments landed, 16 steps multiplied
+      A16_STAMP(4);  // the slab's last step multiplied
     }
 #endif
+    // (the wave's next slab: its requests go out as soon as the last part's registers are free.  Inside the branches above they would
+    // cost more than they gain: a wait behind the join of a taken and a not-taken path counts for the path with fewer requests, so the
+    // last quarter's multiply would wait for the next slab's rows)
+    if (s + WAVES < nslab) front(s + WAVES);
   }
   // D layout: column n = lane & 15, rows 4 g + j: token rows 0-7 live in g = 0, 1
   if (g < 2) {
@@ -275,9 +333,9 @@ int act16_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t
     constexpr int DT = decltype(dt)::value, LIMIT = 160 * 1024;
     const char* const what = "quantize_act_xa (fused block-16 route)";
     switch (rp / 16) {  // 16-column tiles of the padded rank
-      case 1: return launch_k<a16f::k_act16_fused<DT, 1>, LIMIT>(what, grid, 512, lds, st, x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);
-      case 2: return launch_k<a16f::k_act16_fused<DT, 2>, LIMIT>(what, grid, 512, lds, st, x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);
-      default: return launch_k<a16f::k_act16_fused<DT, 4>, LIMIT>(what, grid, 512, lds, st, x, M, K, ldx, qx, xq, Kp, a_frag, qa, L, xaq);
+      case 1: return launch_k<a16f::k_act16_fused<DT, 1>, LIMIT>(what, grid, 512, lds, st, x, M, ldx, K, Kp, a_frag, xq, xaq, qx, qa, L);
+      case 2: return launch_k<a16f::k_act16_fused<DT, 2>, LIMIT>(what, grid, 512, lds, st, x, M, ldx, K, Kp, a_frag, xq, xaq, qx, qa, L);
+      default: return launch_k<a16f::k_act16_fused<DT, 4>, LIMIT>(what, grid, 512, lds, st, x, M, ldx, K, Kp, a_frag, xq, xaq, qx, qa, L);
     }
   };
   return dtype == LQER_F16 ? run(std::integral_constant<int, LQER_F16>{}) : run(std::integral_constant<int, LQER_BF16>{});

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """In-kernel timeline of the block-16 one-launch activation kernel (act16_fused.hip, -DLQER_CLOCKPROBE build): shader cycles from a wave's
-start to the phase boundaries of its first slab, medians over all waves.
+start to the phase boundaries of its first slab (a slab is loaded, quantized and multiplied in quarters of 128 k), medians over all waves.
 usage: python tools/clock_probe_a16.py build/abl/liblqer_cp.so [--M 2048 --K 4096 --r 32]"""
 import argparse, ctypes as C, os, sys, time
 import torch
@@ -50,7 +50,7 @@ for _ in range(20): launch()
 e1.record(); torch.cuda.synchronize()
 b = buf.cpu().view(wgs, 8, 8).double()
 med = lambda t: t.median().item()
-names = ["row requests out", "row 0 landed + quantized", "8 rows quantized, stores issued", "fragments landed, 16 steps multiplied", "partial tiles barrier passed"]
+names = ["first slab's requests out", "quarter 0 landed + quantized", "last quarter quantized, stores issued", "last step multiplied", "partial tiles barrier passed"]
 print(f"M={M} K={K} r={r}: call {e0.elapsed_time(e1) / 20 * 1e3:.1f} us, {wgs} workgroups of 8 rows")
 for i, n in enumerate(names, 1):
     print(f"  {n:40s} {med(b[:, :, i]):8.0f} cycles (min {b[:, :, i].min().item():.0f}, max {b[:, :, i].max().item():.0f})")
