@@ -627,6 +627,77 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- paged KV pool: the packed KV cache in pages of 16 keys, per-sequence lengths in a decode batch ------------------------------
+ * The packed cache above has one length for the whole batch and one dense slab: a ragged batch is padded to its longest sequence, a
+ * finished sequence cannot hand its memory to a new one, and growing copies everything.  The pool stores the SAME codes and exponents
+ * in PAGES: a page holds LQER_KV_PAGE_KEYS = 16 keys of ALL kv heads of one sequence - one block of the K quantizer, one group of V
+ * exponents, so a page is a whole number of everything the cache stores, and a decode chunk (a multiple of 16 keys) a whole number
+ * of pages.  One caller-allocated buffer, 16-byte aligned, lqer_kv_pool_bytes(...) bytes (0 for a dtype, head dim or size the pool does
+ * not take); the library keeps no pointer.  Page p and kv head g address ITEM p kv_heads + g of each section; sections in this order,
+ * each rounded up to 256 bytes:
+ *   K codes      [pages][kv_heads][16][D]        uint8   the dense cache's codes (sign-magnitude)
+ *   K exponents  [pages][kv_heads][D]            uint8
+ *   V codes      [pages][kv_heads][16][D]        uint8
+ *   V exponents  [pages][kv_heads][D / 16][16]   uint8   the dense cache's regrouping: four consecutive keys' exponents in one dword
+ *   K staging    [slots][kv_heads][16][D]        DT      raw keys of a sequence's open block - one set per sequence SLOT, not per page
+ * Within an item the bytes are exactly the dense cache's bytes for that block of 16 keys.
+ * Metadata, all on the DEVICE and written by the caller:
+ *   block_table  int32 [slots][table_stride]: entry [s][i] is the page of keys 16 i .. 16 i + 15 of the sequence in slot s;
+ *   seq_slots    int32 [batch]: the slot of the b-th sequence of THIS call - any subset of the slots, in any order;
+ *   lens         int32 [batch]: for append the sequence's length BEFORE the call, for attention its number of keys T_b;
+ *   max_len      host: an upper bound on every lens[b] (for append: on lens[b] + n), 1 <= max_len <= min(16 table_stride, 2^30).  It
+ *                sizes grids and the workspace only - no result depends on it, and no host decision depends on a length.
+ * The library cannot see device contents from the host, so VALID TABLES AND LENGTHS ARE THE CALLER'S CONTRACT, as valid pointers are:
+ * every page index a call reaches (entries 0 .. ceil(len / 16) - 1 of an addressed slot's row) lies in [0, pages); no page belongs to
+ * two live sequences; no slot is named twice in one call; every seq_slots[b] lies in [0, slots); 0 <= lens[b] and lens[b] (+ n)
+ * <= max_len.  A call that breaks this reads or writes outside the pool.  Nothing depends on the contents of a page beyond its
+ * sequence's length or on staging rows beyond len % 16: pages and slots are reused dirty, a fresh pool needs no initialisation.
+ * lqer_kv_pool_append: k_new / v_new [batch][kv_heads][n][D] of DT through k_strides[3] / v_strides[3], n >= 1 uniform over the call
+ * (a decode step: n = 1 for every live sequence; a prompt: a call with batch = 1).  Per sequence lqer_kv_cache_append's semantics, word
+ * for word: V rows quantized and stored at once, every block of 16 keys the new keys touch re-quantized from the staging rows plus the
+ * new keys, zero-padded on the right, and rewritten whole, the raw keys of the block left open to the slot's staging rows.  ONE launch
+ * on `stream` whatever the lengths are (the thread that reads a staging column also writes it); like the dense append it is issued
+ * once per step, in order.
+ * lqer_attention_q_decode_paged: lqer_attention_q_decode_kv with (cache, cache_bytes, capacity, T) replaced by (pool, pool_bytes, pages,
+ * slots, block_table, table_stride, seq_slots, lens, max_len) and without a mask tensor: the mask forms are none and causal = 1, with
+ * sequence b's own offset T_b - S (S <= T_b is the caller's to keep); per-sequence lengths replace the padding mask.  S <= 8, uniform
+ * over the call.  A workgroup takes T = lens[b] and from it the chunk length C, the chunk count nch and the causal offset of ITS
+ * sequence; the grid's x is the largest nch that any T <= max_len has (nch is not monotonic in T), and workgroups beyond their
+ * sequence's nch leave at once.  For every b, out[b] and row_stats[b] are the SAME BITS as lqer_attention_q_decode with batch = 1 on
+ * the raw K and V of that sequence - whatever else is in the batch, whatever pages it lives on, whatever max_len is.  A sequence
+ * with lens[b] = 0 gets out[b] = 0 and its row_stats untouched.  The pool is only read.
+ * workspace: lqer_attention_q_decode_paged_workspace_bytes(batch, heads, kv_heads, S, max_len, D) bytes, 16-byte aligned, contents
+ * irrelevant, strides fixed by max_len: with rows = batch heads S, Tp = max_len rounded up to 128 and nchs = the largest nch of any
+ * T <= max_len (ceil(max_len / 16) up to 256 keys, 16 up to 2048, ceil(max_len / 128) beyond)
+ *   [S2, fp32: rows x Tp][chunk statistics, fp32: rows x nchs x 2][partial outputs, fp32: rows x nchs x D]    each rounded up to 256 bytes.
+ * Three launches on `stream`, no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
+ * lqer_kv_pool_gather: one sequence - row `slot` of block_table, T keys (host) - out of the pool into a dense lqer_kv_cache buffer of
+ * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
+ * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack), more than 8 query rows on a paged sequence
+ * (lqer_attention_q_kv), an export path.
+ * Refused with a message, nothing launched or touched (decided from host arguments only):
+ *   LQER_E_UNSUPPORTED  what lqer_attention_q_decode_kv / lqer_kv_cache_append refuse so (S > 8, formats, D, batch or kv_heads > 65535);
+ *                       max_len > 2^30 (every call);
+ *   LQER_E_INVALID      null block_table / seq_slots / lens or any other null pointer; pages, slots or table_stride < 1; max_len < 1
+ *                       or > 16 table_stride; n < 1 or n > max_len; a pool shorter than lqer_kv_pool_bytes or not 16-byte aligned;
+ *                       a short or misaligned workspace; gather: slot outside [0, slots), T > capacity, a short or misaligned cache. */
+#define LQER_KV_PAGE_KEYS 16
+size_t lqer_kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D);
+int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                        const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const void* k_new, const void* v_new,
+                        const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t n,
+                        const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
+int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                        const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
+                        int64_t capacity, void* stream);
+size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
+int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
+                                  float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D,
+                                  const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                                  const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's
  * x.float() does) for the per-input-channel sum|x| and max|x|; any of the three outputs may be NULL, not all of them:

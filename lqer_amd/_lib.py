@@ -133,6 +133,13 @@ SIGNATURES = {
     "lqer_attention_q_kv_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_kv": (_i, [_vp, _vp, _sz, _i64, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _sp, _sp, _sp, C.c_float,
                                  _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    # the paged KV pool (csrc/kv_cache.hip, csrc/attn_decode.hip): pages of 16 keys, a block table, per-sequence lengths on the device
+    "lqer_kv_pool_bytes": (_sz, [_i, _i64, _i64, _i64, _i64]),
+    "lqer_kv_pool_append": (_i, [_vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64, _qp, _qp, _vp]),
+    "lqer_kv_pool_gather": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _i64, _vp]),
+    "lqer_attention_q_decode_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "lqer_attention_q_decode_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
+                                           _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1127,6 +1127,10 @@ static const AttnKernel ATTN_PREFILL = {0, "kernel takes", prefill_grid_limits, 
                                         attention_q_dispatch};
 static const AttnKernel ATTN_DECODE = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, decode_workspace_bytes,
                                        attention_q_decode_dispatch};
+// the decode kernels on the paged pool: c.T is the bound max_len, which sizes the workspace (and the grid)
+static size_t paged_workspace_bytes(const AttnCall& c) { return attention_q_decode_paged_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D); }
+static const AttnKernel ATTN_DECODE_PAGED = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, paged_workspace_bytes,
+                                             attention_q_decode_dispatch};
 
 // the check of the four attention calls, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
 static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) {
@@ -1204,18 +1208,8 @@ size_t lqer_kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t c
   return kv_cache_bytes(dtype, batch, kv_heads, capacity, D);
 }
 
-// what append, attention and unpack ask of a cache: LQER_OK or the refusal
-static int kv_cache_check(const char* who, const void* cache, size_t cache_bytes, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity,
-                          int64_t D, int64_t T, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt) {
-  if (batch < 0 || kv_heads <= 0 || capacity <= 0 || D <= 0 || T < 0) {
-    set_error("%s: bad KV cache shape batch=%lld kv_heads=%lld capacity=%lld D=%lld length=%lld", who, (long long)batch, (long long)kv_heads,
-              (long long)capacity, (long long)D, (long long)T);
-    return LQER_E_INVALID;
-  }
-  if (!kv_dtype_ok(dtype)) {
-    set_error("%s: unknown dtype %d of the KV cache", who, dtype);
-    return LQER_E_INVALID;
-  }
+// what the codes of a cache or a pool ask of the head dim and the two quantizers: LQER_OK or the refusal
+static int kv_codes_check(const char* who, int64_t D, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt) {
   if (!k_fmt || !v_fmt) {
     set_error("%s: null quantizer format of the KV cache", who);
     return LQER_E_INVALID;
@@ -1230,6 +1224,22 @@ static int kv_cache_check(const char* who, const void* cache, size_t cache_bytes
       set_error("%s: the packed KV cache holds block_fp codes of width <= 8 with blocks of 16 (got kind %d, block %d)", who, f->kind, f->block);
       return LQER_E_UNSUPPORTED;
     }
+  return LQER_OK;
+}
+
+// what append, attention and unpack ask of a cache: LQER_OK or the refusal
+static int kv_cache_check(const char* who, const void* cache, size_t cache_bytes, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity,
+                          int64_t D, int64_t T, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt) {
+  if (batch < 0 || kv_heads <= 0 || capacity <= 0 || D <= 0 || T < 0) {
+    set_error("%s: bad KV cache shape batch=%lld kv_heads=%lld capacity=%lld D=%lld length=%lld", who, (long long)batch, (long long)kv_heads,
+              (long long)capacity, (long long)D, (long long)T);
+    return LQER_E_INVALID;
+  }
+  if (!kv_dtype_ok(dtype)) {
+    set_error("%s: unknown dtype %d of the KV cache", who, dtype);
+    return LQER_E_INVALID;
+  }
+  if (const int rc = kv_codes_check(who, D, k_fmt, v_fmt)) return rc;
   if (T > capacity) {
     set_error("%s: %lld keys beyond the KV cache's capacity %lld", who, (long long)T, (long long)capacity);
     return LQER_E_INVALID;
@@ -1303,11 +1313,124 @@ size_t lqer_attention_q_kv_workspace_bytes(int64_t batch, int64_t heads, int64_t
   return lqer_attention_q_workspace_bytes(batch, heads, kv_heads, S, T, D);
 }
 
-// the check for the kernel that will run, the cache's check where K and V come from one, the launches
+// ---- the paged KV pool (kv_pack.h: PoolLayout; kv_cache.hip, attn_decode.hip) ----
+size_t lqer_kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D) {
+  if (!kv_dtype_ok(dtype) || pages <= 0 || slots <= 0 || kv_heads <= 0 || D <= 0 || D % 16 != 0 || D > 128) return 0;
+  return kv_pool_bytes(dtype, pages, slots, kv_heads, D);
+}
+
+// what append, attention and gather ask of a pool and its page table (host arguments only: the table's and the lengths' CONTENTS are
+// the caller's contract).  A call that addresses sequences through seq_slots / lens (append, attention) needs the two arrays; gather
+// names its slot on the host.  The quantizers are the caller's to check (kv_codes_check, attn_check).  LQER_OK or the refusal
+enum PoolUse { POOL_BATCH, POOL_ONE_SLOT };
+static int kv_pool_check(const char* who, const KvPool& p, PoolUse use) {
+  if (p.pages < 1 || p.slots < 1 || p.kv_heads < 1 || p.table_stride < 1 || p.D <= 0) {
+    set_error("%s: bad KV pool shape pages=%lld slots=%lld kv_heads=%lld table_stride=%lld D=%lld", who, (long long)p.pages, (long long)p.slots,
+              (long long)p.kv_heads, (long long)p.table_stride, (long long)p.D);
+    return LQER_E_INVALID;
+  }
+  if (!kv_dtype_ok(p.dtype)) {
+    set_error("%s: unknown dtype %d of the KV pool", who, p.dtype);
+    return LQER_E_INVALID;
+  }
+  if (p.D % 16 != 0 || p.D > 128) {
+    set_error("%s: head dim %lld - the KV pool takes multiples of 16 up to 128", who, (long long)p.D);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (p.pages > ((int64_t)1 << 31) - 1 || p.slots > ((int64_t)1 << 31) - 1) {
+    set_error("%s: %lld pages / %lld slots of the KV pool beyond the 32-bit page table", who, (long long)p.pages, (long long)p.slots);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (p.max_len > ((int64_t)1 << 30)) {  // (as the decode kernels' T: chunk indices are 32-bit)
+    set_error("%s: max_len %lld of the KV pool beyond 2^30 keys", who, (long long)p.max_len);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (p.max_len < 1 || (p.max_len + 15) / 16 > p.table_stride) {
+    set_error("%s: max_len %lld of the KV pool outside 1 .. 16 table_stride = 16 x %lld keys", who, (long long)p.max_len,
+              (long long)p.table_stride);
+    return LQER_E_INVALID;
+  }
+  if (!p.block_table || (use == POOL_BATCH && (!p.seq_slots || !p.lens))) {
+    set_error("%s: null block_table / seq_slots / lens of the KV pool", who);
+    return LQER_E_INVALID;
+  }
+  if (!p.pool) {
+    set_error("%s: null KV pool", who);
+    return LQER_E_INVALID;
+  }
+  if ((uintptr_t)p.pool % 16 != 0) {
+    set_error("%s: KV pool %p is not 16-byte aligned", who, p.pool);
+    return LQER_E_INVALID;
+  }
+  const size_t need = kv_pool_bytes(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  if (p.pool_bytes < need) {
+    set_error("%s: KV pool of %zu B < %zu B (lqer_kv_pool_bytes)", who, p.pool_bytes, need);
+    return LQER_E_INVALID;
+  }
+  return LQER_OK;
+}
+
+int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                        const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const void* k_new, const void* v_new,
+                        const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t n,
+                        const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
+  if (batch < 0 || n < 1) {
+    set_error("kv_pool_append: batch %lld / %lld new keys for the KV pool (batch >= 0, at least one new key)", (long long)batch, (long long)n);
+    return LQER_E_INVALID;
+  }
+  const KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  int rc = kv_codes_check("kv_pool_append", D, k_fmt, v_fmt);
+  if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append", p, POOL_BATCH);
+  if (rc != LQER_OK) return rc;
+  if (n > max_len) {
+    set_error("kv_pool_append: %lld new keys beyond max_len %lld of the KV pool (a bound on lens[b] + n)", (long long)n, (long long)max_len);
+    return LQER_E_INVALID;
+  }
+  if (batch == 0) return LQER_OK;
+  if (!k_new || !v_new || !k_strides || !v_strides) {
+    set_error("kv_pool_append: null pointer (new keys / values for the KV pool or their strides)");
+    return LQER_E_INVALID;
+  }
+  if (batch * kv_heads * ((n + 14) / 16 + 1 + n) > ((int64_t)1 << 31)) {  // (work items over grid.x, 256 a workgroup: D / 4 <= 32 per row)
+    set_error("kv_pool_append: %lld new keys for %lld KV pool streams beyond one launch grid: append in pieces", (long long)n,
+              (long long)(batch * kv_heads));
+    return LQER_E_UNSUPPORTED;
+  }
+  return kv_pool_append_dispatch(p, k_new, v_new, k_strides, v_strides, batch, n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
+}
+
+int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                        const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
+                        int64_t capacity, void* stream) {
+  if (slot < 0 || slot >= slots || T < 0 || capacity < 1 || T > capacity) {
+    set_error("kv_pool_gather: slot %lld of %lld / %lld keys of the KV pool into a cache of capacity %lld", (long long)slot, (long long)slots,
+              (long long)T, (long long)capacity);
+    return LQER_E_INVALID;
+  }
+  const KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, nullptr, nullptr, table_stride, T > 0 ? T : 1};
+  const int rc = kv_pool_check("kv_pool_gather", p, POOL_ONE_SLOT);
+  if (rc != LQER_OK) return rc;
+  if (!cache || (uintptr_t)cache % 16 != 0 || cache_bytes < kv_cache_bytes(dtype, 1, kv_heads, capacity, D)) {
+    set_error("kv_pool_gather: KV cache %p of %zu B - null, not 16-byte aligned or shorter than lqer_kv_cache_bytes(batch 1) = %zu B", cache,
+              cache_bytes, kv_cache_bytes(dtype, 1, kv_heads, capacity, D));
+    return LQER_E_INVALID;
+  }
+  return kv_pool_gather_dispatch(p, slot, T, cache, capacity, (hipStream_t)stream);
+}
+
+size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
+  if (batch <= 0 || heads <= 0 || kv_heads <= 0 || S <= 0 || max_len <= 0 || D <= 0) return 0;
+  return attention_q_decode_paged_workspace_bytes(batch, heads, S, max_len, D);
+}
+
+// the check for the kernel that will run, the cache's or the pool's check where K and V come from one, the launches
 static int attn_run(const char* who, const AttnKernel& kn, const AttnCall& c) {
   int rc = attn_check(who, kn, c);
   if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
-  if (c.packed) {
+  if (c.paged) {
+    rc = kv_pool_check(who, c.pool, POOL_BATCH);  // (attn_check has seen D and the four quantizers)
+    if (rc != LQER_OK) return rc;
+  } else if (c.packed) {
     rc = kv_cache_check(who, c.cache, c.cache_bytes, c.dtype, c.batch, c.kv_heads, c.capacity, c.D, c.T, c.k_fmt, c.v_fmt);
     if (rc != LQER_OK) return rc;
   }
@@ -1372,6 +1495,22 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
   c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
   c.packed = true, c.cache = cache, c.cache_bytes = cache_bytes, c.capacity = capacity;
   return attn_run("attention_q_kv", ATTN_PREFILL, c);
+}
+
+int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                                  int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
+                                  const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                                  const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
+  AttnCall c = {};
+  c.q = q, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
+  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = max_len, c.D = D;  // (T: the bound - the check's, the workspace's)
+  c.qs = q_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
+  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  c.packed = c.paged = true;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  return attn_run("attention_q_decode_paged", ATTN_DECODE_PAGED, c);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

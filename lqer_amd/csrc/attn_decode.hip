@@ -18,9 +18,14 @@
 // The chunk length depends on T alone (dec_chunk), a row's arithmetic on that row alone: no floating-point atomics, no counters, the
 // same bits run to run, for a batch slice and for a slice of a kv group's heads.
 //
-// Both kernels take their K / V from one of two sources (template parameter PK): the caller's tensors in DT, quantized here, or the
+// Both kernels take their K / V from one of three sources (template parameter SRC): the caller's tensors in DT, quantized here; the
 // packed KV cache (kv_pack.h: the codes and block exponents of Q_w0(K^T) and Q_w1(V), written by kv_cache.hip) - 16-byte loads of
-// codes, a convert and a scale.  Either source writes the SAME bf16 image to LDS; everything after the first barrier is one body.
+// codes, a convert and a scale; or the paged pool - the same codes, a block of 16 keys found through the sequence's row of a page
+// table.  Every source writes the SAME bf16 image to LDS; everything after the first barrier is one body.
+// With the paged pool the sequences of a batch have lengths of their own, read from the device: a workgroup takes T = lens[b], and with
+// it the chunk length, the chunk count and the causal offset of ITS sequence; the grid and the workspace strides come from the bound
+// max_len (dec_max_chunks), and a workgroup whose chunk its sequence does not have leaves before the first barrier.  A sequence's
+// results are those of a call of batch 1 at T = lens[b]: nothing it computes depends on max_len or on the rest of the batch.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -30,6 +35,7 @@ namespace attn {
 
 constexpr int DEC_MAX_S = 8;     // query rows per head
 constexpr int DEC_CMAX = 128;    // keys per chunk at most
+constexpr int SRC_RAW = 0, SRC_PACKED = 1, SRC_PAGED = 2;  // where K and V come from
 constexpr int DEC_LS = 256 + 16; // bytes of an LDS row of 128 bf16 (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
 
 // keys per chunk: 16 ceil(T / 256) clamped to [16, 128] - T / 16 chunks up to T = 256, then 16, from T = 2048 on chunks of 128.
@@ -38,6 +44,13 @@ __host__ __device__ inline int dec_chunk(int64_t T, int64_t D) {
   (void)D;
   const int64_t n = (T + 255) / 256;
   return 16 * (int)(n < 1 ? 1 : (n > 8 ? 8 : n));
+}
+
+// the most chunks any T <= max_len has - the grid's x and the workspace's chunk stride with per-sequence lengths.  nch is not monotonic
+// in T (256 keys: 16 chunks of 16; 257: 9 of 32; 2049: 17 of 128): up to 256 keys it is ceil(T / 16), from 257 to 2048 at most 16
+// (reached at every multiple of 256), beyond 2048 ceil(T / 128) >= 17.
+__host__ inline int dec_max_chunks(int64_t max_len) {
+  return (int)(max_len <= 256 ? (max_len + 15) / 16 : (max_len <= 2048 ? 16 : (max_len + 127) / 128));
 }
 
 struct DArgs {
@@ -53,19 +66,45 @@ struct DArgs {
   bool qvec, kvec, vvec;
   const unsigned char *kc, *ke, *vc, *ve;  // the packed source: codes and exponents of K and of V (kv_pack.h), cap keys per (batch, kv head)
   int64_t cap;
+  int nchs;  // chunks the workspace has room for per row (its stride over rows): nch, or dec_max_chunks(max_len) with the paged source
+  const int32_t *tbl, *slots, *lens;  // the paged source (device): [slots][tstride] pages, [batch] slot and length of the b-th sequence
+  int64_t tstride;
 };
 
-template <int DT, bool PK>
+// the paged source's sizes of workgroup b's own sequence; false: chunk c is none of its chunks
+__device__ __forceinline__ bool paged_sizes(const DArgs& a, int64_t b, int64_t c, int64_t& T, int& C, int& nch) {
+  T = a.lens[b];
+  C = dec_chunk(T, a.D);
+  nch = (int)((T + C - 1) / C);
+  return c < nch;
+}
+
+// the index of the block of keys 16 kb .. 16 kb + 15 of (batch b, kv head g) in the code and exponent sections (kv_pack.h)
+template <int SRC>
+__device__ __forceinline__ int64_t kv_block(const DArgs& a, const int32_t* row, int64_t z, int64_t g, int64_t kb) {
+  if constexpr (SRC == SRC_PAGED) return (int64_t)row[kb] * a.kv_heads + g;
+  else return z * (a.cap / 16) + kb;
+}
+
+template <int DT, int SRC>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
-  const int64_t t0 = c * a.C;
-  const int D = (int)a.D, C = a.C;
+  int64_t T = a.T;
+  int C = a.C, nch = a.nch;
+  const int32_t* prow = nullptr;  // the slot's row of the page table
+  if constexpr (SRC == SRC_PAGED) {
+    if (!paged_sizes(a, b, c, T, C, nch)) return;  // (uniform over the workgroup, before any barrier)
+    prow = a.tbl + (int64_t)a.slots[b] * a.tstride;
+  }
+  (void)nch, (void)prow;
+  const int64_t t0 = c * C;
+  const int D = (int)a.D;
   const float NEG_INF = -__builtin_inff();
 
-  if constexpr (PK) {
+  if constexpr (SRC != SRC_RAW) {
     // ---- the chunk's keys from the packed cache: a thread owns 16 consecutive d of 4 consecutive keys - four 16-byte loads of codes and
     // the 16 exponents of their block (one per d); keys at and beyond T are zero rows and are not read
     const int dg_n = D / 16, items = (C / 4) * dg_n;
@@ -75,17 +114,18 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       uint4 e4 = make_uint4(0, 0, 0, 0), c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
-      if (tq < a.T) {
-        e4 = *(const uint4*)(a.ke + (z * (a.cap / 16) + tq / 16) * D + 16 * dg);
+      if (tq < T) {  // (paged: the one table entry first, the five loads one round trip behind it)
+        const int64_t blk = kv_block<SRC>(a, prow, z, g, tq / 16);
+        e4 = *(const uint4*)(a.ke + blk * D + 16 * dg);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (tq + j < a.T) c[j] = *(const uint4*)(a.kc + (z * a.cap + tq + j) * D + 16 * dg);
+          if (tq + j < T) c[j] = *(const uint4*)(a.kc + (blk * 16 + tq % 16 + j) * D + 16 * dg);
       }
       const uint32_t eb[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (tq + j < a.T) kvc::codes16_to_bf16(c[j], eb, a.qk, w);
+        if (tq + j < T) kvc::codes16_to_bf16(c[j], eb, a.qk, w);
         uint4* dst = (uint4*)(sK + (4 * kq + j) * DEC_LS + dg * 32);
         dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
         dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
@@ -101,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       for (int i = 0; i < 16; ++i) {
         const int64_t t = t0 + 16 * kb + i;
         float v4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (t < a.T) load4<DT>(a.k, b * a.k_bs + g * a.k_hs + t * a.k_rs + d0, a.kvec, v4);
+        if (t < T) load4<DT>(a.k, b * a.k_bs + g * a.k_hs + t * a.k_rs + d0, a.kvec, v4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[j][i] = v4[j];
       }
@@ -122,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   // ---- S^T = Kq Qq^T: wave w takes keys 32 w .. 32 w + 31 of the chunk, a lane ONE query row and 16 of those keys,
   // (r & 3) + 8 (r >> 2) + 4 lh (rows of sK at and beyond C hold whatever LDS held: their scores are never used)
   const int nsub = (C + 31) / 32;
-  const int64_t off = a.T - a.S;
+  const int64_t off = T - a.S;
   for (int64_t rg = 0; rg < a.R; rg += 32) {
     const int64_t row = rg + l31;
     const bool live = row < a.R;
@@ -147,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8, f), acc, 0, 0, 0);
         }
       }
-      int64_t tvis = a.T - 1;  // the last key visible to this lane's query
+      int64_t tvis = T - 1;  // the last key visible to this lane's query
       if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
       const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + si * a.m_rs : 0;
       float s2[16];
@@ -157,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
         const int kk = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int64_t t = t0 + kk;
         float s = rnd<DT>(rnd<DT>(acc[r]) * a.scaling);
-        if (a.mode == 1) s = rnd<DT>(s + (t < a.T ? load_elem<DT>(a.mask, moff + t) : 0.f));
+        if (a.mode == 1) s = rnd<DT>(s + (t < T ? load_elem<DT>(a.mask, moff + t) : 0.f));
         s2[r] = s;
         vis[r] = kk < C && t <= tvis;
       }
@@ -190,23 +230,31 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       const float mr = M == NEG_INF ? 0.f : M;
       float L = 0.f;
       for (int u = 0; u < nsub; ++u) L += sSt[u][l31][1] * exp_neg(sSt[u][l31][0] - mr);
-      float* cs = a.cst + ((z * a.R + row) * a.nch + c) * 2;
+      float* cs = a.cst + ((z * a.R + row) * a.nchs + c) * 2;
       cs[0] = M, cs[1] = L;
     }
     __syncthreads();
   }
 }
 
-template <int DT, bool PK>
+template <int DT, int SRC>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
-  const int64_t t0 = c * a.C;
-  const int D = (int)a.D, C = a.C;
+  int64_t T = a.T;
+  int C = a.C, nch = a.nch;
+  const int32_t* prow = nullptr;
+  if constexpr (SRC == SRC_PAGED) {
+    if (!paged_sizes(a, b, c, T, C, nch)) return;
+    prow = a.tbl + (int64_t)a.slots[b] * a.tstride;
+  }
+  (void)prow;
+  const int64_t t0 = c * C;
+  const int D = (int)a.D;
   const float NEG_INF = -__builtin_inff();
 
-  if constexpr (PK) {
+  if constexpr (SRC != SRC_RAW) {
     // ---- the chunk's V rows from the packed cache: a thread owns 16 consecutive d (one block of Q_w1) of 4 consecutive keys - four
     // 16-byte loads of codes, one dword of their four exponents; keys at and beyond T are zero rows and are not read
     const int db_n = D / 16, items = (C / 4) * db_n;
@@ -217,18 +265,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       uint4 c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
-      if (tq < a.T) {
-        e4 = *(const uint32_t*)(a.ve + ((z * (a.cap / 16) + tq / 16) * db_n + db) * 16 + tq % 16);
+      if (tq < T) {
+        const int64_t blk = kv_block<SRC>(a, prow, z, g, tq / 16);
+        e4 = *(const uint32_t*)(a.ve + (blk * db_n + db) * 16 + tq % 16);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (tq + j < a.T) c[j] = *(const uint4*)(a.vc + (z * a.cap + tq + j) * D + 16 * db);
+          if (tq + j < T) c[j] = *(const uint4*)(a.vc + (blk * 16 + tq % 16 + j) * D + 16 * db);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const uint32_t e1 = ((e4 >> (8 * j)) & 0xffu) * 0x01010101u;
         const uint32_t eb[4] = {e1, e1, e1, e1};
-        if (tq + j < a.T) kvc::codes16_to_bf16(c[j], eb, a.qv, w);
+        if (tq + j < T) kvc::codes16_to_bf16(c[j], eb, a.qv, w);
         uint4* dst = (uint4*)(sV + (4 * kq + j) * DEC_LS + db * 32);
         dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
         dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
@@ -241,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       const int key = it / db_n, db = it % db_n;
       const int64_t t = t0 + key;
       uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (t < a.T) {
+      if (t < T) {
         float x[16];
         qmm::load16<DT>(a.v, b * a.v_bs + g * a.v_hs + t * a.v_rs + 16 * db, 16, a.vvec, x);
         qmm::quant16_bf16<DT != LQER_F16>(x, a.qv, w);
@@ -254,24 +303,24 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   __syncthreads();
   if (wave * 32 >= D) return;  // wave w owns d = 32 w .. 32 w + 31 (no barrier follows)
 
-  const int64_t off = a.T - a.S;
+  const int64_t off = T - a.S;
   for (int64_t rg = 0; rg < a.R; rg += 32) {
     const int64_t row = rg + l31;
     const bool live = row < a.R;
     const int64_t rowc = live ? row : a.R - 1;
     const int64_t si = rowc % a.S;
     // ---- the row's maximum and sum from the chunk statistics, in chunk order
-    const float* cs = a.cst + (z * a.R + rowc) * a.nch * 2;
+    const float* cs = a.cst + (z * a.R + rowc) * a.nchs * 2;
     float M = NEG_INF;
-    for (int cc = 0; cc < a.nch; ++cc) M = fmaxf(M, cs[2 * cc]);
+    for (int cc = 0; cc < nch; ++cc) M = fmaxf(M, cs[2 * cc]);
     const float mr = M == NEG_INF ? 0.f : M;
     float L = 0.f;
-    for (int cc = 0; cc < a.nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
+    for (int cc = 0; cc < nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
     if (a.stats && c == 0 && wave == 0 && lh == 0 && live) {
       float* st = a.stats + (z * a.R + row) * 2;
       st[0] = M, st[1] = L;
     }
-    int64_t tvis = a.T - 1;
+    int64_t tvis = T - 1;
     if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
     if (!live) tvis = -1;
 
@@ -298,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vw), __builtin_bit_cast(bf16x8, pw), acc, 0, 0, 0);
     }
     if (live) {  // d = 32 wave + 8 q4 + 4 lh + (0..3)
-      float* dst = a.part + ((z * a.R + row) * a.nch + c) * a.D + 32 * wave + 4 * lh;
+      float* dst = a.part + ((z * a.R + row) * a.nchs + c) * a.D + 32 * wave + 4 * lh;
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4)
         if (32 * wave + 8 * q4 + 4 * lh < D) *(float4*)(dst + 8 * q4) = make_float4(acc[4 * q4], acc[4 * q4 + 1], acc[4 * q4 + 2], acc[4 * q4 + 3]);
@@ -306,18 +355,24 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   }
 }
 
-// one thread = four consecutive d of one output row
-template <int DT>
+// one thread = four consecutive d of one output row (PAGED: the chunks of the row's own sequence)
+template <int DT, bool PAGED>
 __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int dq = (int)a.D / 4;
   if (i >= a.rows * dq) return;
   const int64_t grow = i / dq;
   const int d = 4 * (int)(i % dq);
-  const float* p = a.part + grow * a.nch * a.D + d;
+  int nch = a.nch;
+  if constexpr (PAGED) {
+    int64_t T;
+    int C;
+    paged_sizes(a, grow / (a.heads * a.S), 0, T, C, nch);
+  }
+  const float* p = a.part + grow * a.nchs * a.D + d;
   float o[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
-  for (int cc = 0; cc < a.nch; ++cc) {
+  for (int cc = 0; cc < nch; ++cc) {
     const float4 t = *(const float4*)(p + (int64_t)cc * a.D);
     o[0] += t.x, o[1] += t.y, o[2] += t.z, o[3] += t.w;
   }
@@ -325,13 +380,13 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
-template <int DT, bool PK>
+template <int DT, int SRC>
 static int launch_decode(const DArgs& a, int64_t batch, hipStream_t st) {
-  const dim3 grid((unsigned)a.nch, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT, PK><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT, PK><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_sum<DT><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
-  return check_launch(PK ? "lqer_attention_q_decode_kv" : "lqer_attention_q_decode");
+  const dim3 grid((unsigned)a.nchs, (unsigned)a.kv_heads, (unsigned)batch);
+  k_attn_dec_scores<DT, SRC><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT, SRC><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_sum<DT, SRC == SRC_PAGED><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
+  return check_launch(SRC == SRC_PAGED ? "lqer_attention_q_decode_paged" : (SRC == SRC_PACKED ? "lqer_attention_q_decode_kv" : "lqer_attention_q_decode"));
 }
 
 }  // namespace attn
@@ -347,17 +402,26 @@ size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t 
   return dec_align((size_t)(rows * nch * C) * 4) + dec_align((size_t)(rows * nch * 2) * 4) + dec_align((size_t)(rows * nch * D) * 4);
 }
 
+// the paged source: the same three parts with strides fixed by the bound max_len - S2 rows of max_len rounded up to 128 (every T <= max_len
+// rounded up to its chunk fits), dec_max_chunks(max_len) chunks per row
+size_t attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t max_len, int64_t D) {
+  const int64_t Tp = (max_len + 127) / 128 * 128, nchs = attn::dec_max_chunks(max_len), rows = batch * heads * S;
+  return dec_align((size_t)(rows * Tp) * 4) + dec_align((size_t)(rows * nchs * 2) * 4) + dec_align((size_t)(rows * nchs * D) * 4);
+}
+
 int attention_q_decode_dispatch(const AttnCall& c) {
   attn::DArgs a;
   a.q = c.q, a.k = c.k, a.v = c.v, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
   a.S = c.S, a.T = c.T, a.D = c.D;
-  a.C = attn::dec_chunk(c.T, c.D), a.nch = (int)((c.T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
+  a.C = attn::dec_chunk(c.T, c.D), a.nch = a.nchs = (int)((c.T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
+  a.tbl = a.slots = a.lens = nullptr, a.tstride = 0;
+  if (c.paged) a.nchs = attn::dec_max_chunks(c.T), a.Tp = (c.T + 127) / 128 * 128;  // (T = max_len; the kernels take T, C, nch from lens[b])
   a.rep = (int)(c.heads / c.kv_heads), a.R = a.rep * c.S, a.rows = c.batch * c.heads * c.S;
   unsigned char* ws = (unsigned char*)c.workspace;
   a.s2 = (float*)ws;
   ws += dec_align((size_t)(a.rows * a.Tp) * 4);
   a.cst = (float*)ws;
-  ws += dec_align((size_t)(a.rows * a.nch * 2) * 4);
+  ws += dec_align((size_t)(a.rows * a.nchs * 2) * 4);
   a.part = (float*)ws;
   const int esz = c.dtype == LQER_F32 ? 4 : 2;
   a.q_bs = c.qs[0], a.q_hs = c.qs[1], a.q_rs = c.qs[2];
@@ -367,16 +431,24 @@ int attention_q_decode_dispatch(const AttnCall& c) {
   a.scaling = c.scaling;
   a.q0 = make_qp(*c.q_fmt), a.qk = make_qp(*c.k_fmt), a.q1 = make_qp(*c.p_fmt), a.qv = make_qp(*c.v_fmt);
   a.qvec = al16(c.q, c.qs, esz);
+  if (c.paged) {  // the paged source: the pool's sections, the table, the slots and the lengths
+    const kvc::PoolLayout l = kvc::pool_layout(c.dtype, c.pool.pages, c.pool.slots, c.kv_heads, c.D);
+    const unsigned char* base = (const unsigned char*)c.pool.pool;
+    a.k = a.v = nullptr, a.k_bs = a.k_hs = a.k_rs = a.v_bs = a.v_hs = a.v_rs = 0, a.kvec = a.vvec = false;
+    a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.cap = 0;
+    a.tbl = c.pool.block_table, a.slots = c.pool.seq_slots, a.lens = c.pool.lens, a.tstride = c.pool.table_stride;
+    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
+  }
   if (c.packed) {  // the packed source: no k, v or their strides
     const auto s = kvc::sections((const unsigned char*)c.cache, kvc::layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
     a.k = a.v = nullptr, a.k_bs = a.k_hs = a.k_rs = a.v_bs = a.v_hs = a.v_rs = 0, a.kvec = a.vvec = false;
     a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve, a.cap = s.cap;
-    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, true>(a, c.batch, c.st); });
+    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });
   }
   a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
   a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
   a.kc = a.ke = a.vc = a.ve = nullptr, a.cap = 0;
-  return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, false>(a, c.batch, c.st); });
+  return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_RAW>(a, c.batch, c.st); });
 }
 
 }  // namespace lqer

@@ -755,9 +755,20 @@ size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t 
 // two dispatch functions launch from.  Host only - never a kernel argument.  `packed`: K and V come from the packed KV cache of
 // `capacity` keys (kv_pack.h) and k, v, ks, vs are unused; a flag of its own because a null `cache` is the cache's check to refuse, in
 // its words.  The dispatch functions read `packed` alone; past the checks it implies cache != nullptr.  The stride triples are the
-// caller's pointers: the check must see a null one.
+// caller's pointers: the check must see a null one.  `paged` (with `packed`, which it implies: no k, v, ks, vs): the codes live in
+// the paged pool `pool` instead of `cache`, T is the pool's max_len - the bound that sizes the grid and the workspace - and the kernels
+// read every sequence's own length from the device.
+struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayout); the three metadata arrays are DEVICE pointers
+  const void* pool;
+  size_t pool_bytes;
+  int dtype;
+  int64_t pages, slots, kv_heads, D;
+  const int32_t *block_table, *seq_slots, *lens;
+  int64_t table_stride, max_len;
+};
 struct AttnCall {
-  bool packed;
+  bool packed, paged;
+  KvPool pool;
   const void *q, *k, *v, *cache, *mask;
   void* out;
   float* row_stats;
@@ -782,12 +793,17 @@ int attention_q_dispatch(const AttnCall& c);  // (with a cache: kv_cache.hip wri
 // attn_decode.hip: the same attention for 1 <= S <= attention_q_decode_max_s() query rows, split over the keys
 int attention_q_decode_max_s();
 size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D);
-int attention_q_decode_dispatch(const AttnCall& c);  // (with a cache: the kernels read its codes, kv_pack.h)
+size_t attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t max_len, int64_t D);
+int attention_q_decode_dispatch(const AttnCall& c);  // (with a cache or a pool: the kernels read its codes, kv_pack.h)
 size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D);  // kv_cache.hip
 int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int dtype, int64_t batch,
                              int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const QP& qk, const QP& qv, hipStream_t st);
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
                              const QP& qv, float* k_f32, float* v_f32, hipStream_t st);
+size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D);
+int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
+                            const QP& qk, const QP& qv, hipStream_t st);
+int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st);
 constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128
 // the two images of lqer_attention_q's workspace from the first T keys of c's cache; the caller (attn_q.hip) checks the launches
 void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv);

@@ -7,6 +7,8 @@
 // One launch when the staging rows read and the staging rows written cannot meet (the new keys stay inside the open block, or the
 // cache ended on a block boundary); otherwise the staging rows are written by a second launch of the same kernel.
 //   k_kv_unpack  code x 2^(e - mbits) as fp32, one element per thread.
+//   k_kv_pool_append / k_kv_pool_gather   the same append into the paged pool (a page = 16 keys of all kv heads; per-sequence lengths
+//                and a block table on the device), in one launch (see the kernel), and one sequence's bytes out of the pool into a dense cache.
 //   k_kv_kimage / k_kv_vimage   the cache -> the two bf16 images k_attn_q reads (attn_q.hip; what k_attn_kimage / k_attn_vimage write from
 //                the raw K and V): codes16_to_bf16 on 16 codes per 16-byte load, zeros wherever the raw image kernels write their
 //                padding - every key at or beyond T, every d at or beyond D.  Nothing of the cache at or beyond key T reaches an image.
@@ -29,6 +31,46 @@ struct AArgs {
   bool kvec, vvec;
 };
 
+// 4 d of one block of 16 keys (x[j][r]: d0 + j of key r) -> the codes of the 16 rows (row pitch D bytes, the four d as one dword) and
+// the four exponent bytes of the block: the K side of an append, dense or paged
+template <int DT>
+__device__ __forceinline__ void store_kblock4(const float (&x)[4][16], const QP& qk, unsigned char* kc, int64_t D, unsigned char* ke) {
+  uint32_t cw[4][4], eb = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) eb |= quant16_codes<DT != LQER_F16>(x[j], qk, cw[j]) << (8 * j);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {  // key r of the block: the four d as one dword
+    const int sh = 8 * (r & 3);
+    *(uint32_t*)(kc + r * D) = ((cw[0][r >> 2] >> sh) & 0xffu) | (((cw[1][r >> 2] >> sh) & 0xffu) << 8) |
+                               (((cw[2][r >> 2] >> sh) & 0xffu) << 16) | (((cw[3][r >> 2] >> sh) & 0xffu) << 24);
+  }
+  *(uint32_t*)ke = eb;
+}
+
+// 16 d of one new V row -> its 16 codes and its exponent byte: the V side of an append, dense or paged
+template <int DT>
+__device__ __forceinline__ void store_vrow16(const void* vn, int64_t off, bool vec, const QP& qv, unsigned char* vc, unsigned char* ve) {
+  float x[16];
+  qmm::load16<DT>(vn, off, 16, vec, x);
+  uint32_t cw[4];
+  const uint32_t eb = quant16_codes<DT != LQER_F16>(x, qv, cw);
+  *(uint4*)vc = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  *ve = (unsigned char)eb;
+}
+
+// 4 d of one raw key -> a staging row, bits as they are (dst 16- / 8-byte aligned: d0 a multiple of 4 of a row of D elements)
+template <int DT>
+__device__ __forceinline__ void copy_raw4(const void* kn, int64_t src, bool vec, void* stage, int64_t dst) {
+  if constexpr (DT == LQER_F32) {
+    const uint32_t* s = (const uint32_t*)kn + src;
+    *(uint4*)((uint32_t*)stage + dst) = vec ? *(const uint4*)s : make_uint4(s[0], s[1], s[2], s[3]);
+  } else {
+    const unsigned short* s = (const unsigned short*)kn + src;
+    *(uint2*)((unsigned short*)stage + dst) =
+        vec ? *(const uint2*)s : make_uint2((uint32_t)s[0] | ((uint32_t)s[1] << 16), (uint32_t)s[2] | ((uint32_t)s[3] << 16));
+  }
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -49,17 +91,7 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[j][r] = v4[j];
       }
-      uint32_t cw[4][4], eb = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) eb |= quant16_codes<DT != LQER_F16>(x[j], a.qk, cw[j]) << (8 * j);
-      unsigned char* kc = a.kc + (z * a.cap + 16 * kb) * a.D + d0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {  // key 16 kb + r: the four d as one dword
-        const int sh = 8 * (r & 3);
-        *(uint32_t*)(kc + r * a.D) = ((cw[0][r >> 2] >> sh) & 0xffu) | (((cw[1][r >> 2] >> sh) & 0xffu) << 8) |
-                                     (((cw[2][r >> 2] >> sh) & 0xffu) << 16) | (((cw[3][r >> 2] >> sh) & 0xffu) << 24);
-      }
-      *(uint32_t*)(a.ke + (z * (a.cap / 16) + kb) * a.D + d0) = eb;
+      store_kblock4<DT>(x, a.qk, a.kc + (z * a.cap + 16 * kb) * a.D + d0, a.D, a.ke + (z * (a.cap / 16) + kb) * a.D + d0);
       return;
     }
     i -= nK;
@@ -67,12 +99,8 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
       const int64_t z = i / (a.n * db_n), rem = i % (a.n * db_n);
       const int64_t j = rem / db_n, b = z / a.kvh, g = z % a.kvh, t = a.len + j;
       const int db = (int)(rem % db_n);
-      float x[16];
-      qmm::load16<DT>(a.vn, b * a.v_bs + g * a.v_hs + j * a.v_rs + 16 * db, 16, a.vvec, x);
-      uint32_t cw[4];
-      const uint32_t eb = quant16_codes<DT != LQER_F16>(x, a.qv, cw);
-      *(uint4*)(a.vc + (z * a.cap + t) * a.D + 16 * db) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-      a.ve[((z * (a.cap / 16) + t / 16) * db_n + db) * 16 + t % 16] = (unsigned char)eb;
+      store_vrow16<DT>(a.vn, b * a.v_bs + g * a.v_hs + j * a.v_rs + 16 * db, a.vvec, a.qv, a.vc + (z * a.cap + t) * a.D + 16 * db,
+                       a.ve + ((z * (a.cap / 16) + t / 16) * db_n + db) * 16 + t % 16);
       return;
     }
     i -= nV;
@@ -82,15 +110,97 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
     const int64_t t = a.s0 + rem / dq, b = z / a.kvh, g = z % a.kvh;
     const int d0 = 4 * (int)(rem % dq);
     const int64_t src = b * a.k_bs + g * a.k_hs + (t - a.len) * a.k_rs + d0, dst = (z * 16 + t % 16) * a.D + d0;
-    if constexpr (DT == LQER_F32) {
-      const uint32_t* s = (const uint32_t*)a.kn + src;
-      *(uint4*)((uint32_t*)a.stage + dst) = a.kvec ? *(const uint4*)s : make_uint4(s[0], s[1], s[2], s[3]);
-    } else {
-      const unsigned short* s = (const unsigned short*)a.kn + src;
-      *(uint2*)((unsigned short*)a.stage + dst) =
-          a.kvec ? *(const uint2*)s : make_uint2((uint32_t)s[0] | ((uint32_t)s[1] << 16), (uint32_t)s[2] | ((uint32_t)s[3] << 16));
-    }
+    copy_raw4<DT>(a.kn, src, a.kvec, a.stage, dst);
   }
+}
+
+// ---- the paged pool (kv_pack.h: PoolLayout; include/lqer_hip.h "paged KV pool") --------------------------------------------------------
+struct PArgs {
+  unsigned char *kc, *ke, *vc, *ve;
+  void* stage;
+  const void *kn, *vn;
+  const int32_t *tbl, *slots, *lens;  // device: [slots][tstride] pages, [batch] slot of the call's b-th sequence, [batch] its length before the call
+  int64_t batch, kvh, D, n, tstride;
+  int64_t nkbm;  // blocks of 16 keys that n new keys can touch at most (from len % 16 = 15): (n + 14) / 16 + 1
+  int64_t k_bs, k_hs, k_rs, v_bs, v_hs, v_rs;
+  QP qk, qv;
+  bool kvec, vvec;
+};
+
+// lqer_kv_cache_append's semantics per sequence, the length read from the device and the blocks found through the slot's table row.
+// ONE launch, whatever len % 16 is: the dense append needs a second launch where the staging rows read (0 .. len % 16 - 1) and the
+// staging rows written (the open block left behind) can meet, because there different threads read and write them.  Here the thread
+// that quantizes 4 d of the FIRST block a sequence's new keys touch - the only thread of the launch that reads the staging column
+// (slot, kv head, d0 .. d0 + 3) - also writes that column's new rows, after its reads in program order; no other thread of the launch
+// touches the column (a slot is named once per call: the caller's contract), so there is no race and nothing to order between launches.
+template <int DT>
+__global__ __launch_bounds__(256) void k_kv_pool_append(const PArgs a) {
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int D = (int)a.D, dq = D / 4, db_n = D / 16;
+  const int64_t Z = a.batch * a.kvh, nK = Z * a.nkbm * dq, nV = Z * a.n * db_n;
+  if (i < nK) {  // ---- 4 d of one block of 16 keys
+    const int64_t z = i / (a.nkbm * dq), rem = i % (a.nkbm * dq);
+    const int64_t j = rem / dq, b = z / a.kvh, g = z % a.kvh;
+    const int d0 = 4 * (int)(rem % dq);
+    const int64_t len = a.lens[b], end = len + a.n, kb = len / 16 + j;
+    if (kb > (end - 1) / 16) return;  // this sequence's new keys touch fewer blocks
+    const int64_t slot = a.slots[b], zs = slot * a.kvh + g;
+    const int64_t blk = (int64_t)a.tbl[slot * a.tstride + kb] * a.kvh + g;
+    const int64_t kn0 = b * a.k_bs + g * a.k_hs + d0;
+    float x[4][16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t t = 16 * kb + r;
+      float v4[4] = {0.f, 0.f, 0.f, 0.f};
+      if (t < len) attn::load4<DT>(a.stage, (zs * 16 + r) * a.D + d0, true, v4);  // (only j == 0 meets keys below len)
+      else if (t < end) attn::load4<DT>(a.kn, kn0 + (t - len) * a.k_rs, a.kvec, v4);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) x[jj][r] = v4[jj];
+    }
+    store_kblock4<DT>(x, a.qk, a.kc + blk * 16 * a.D + d0, a.D, a.ke + blk * a.D + d0);
+    if (j == 0) {  // the raw keys of the block left open -> staging rows t % 16 of this thread's column
+      const int64_t open0 = end / 16 * 16, s0 = open0 > len ? open0 : len;
+      for (int64_t t = s0; t < end; ++t) copy_raw4<DT>(a.kn, kn0 + (t - len) * a.k_rs, a.kvec, a.stage, (zs * 16 + t % 16) * a.D + d0);
+    }
+    return;
+  }
+  i -= nK;
+  if (i < nV) {  // ---- 16 d of one new key
+    const int64_t z = i / (a.n * db_n), rem = i % (a.n * db_n);
+    const int64_t j = rem / db_n, b = z / a.kvh, g = z % a.kvh, t = a.lens[b] + j;
+    const int db = (int)(rem % db_n);
+    const int64_t blk = (int64_t)a.tbl[(int64_t)a.slots[b] * a.tstride + t / 16] * a.kvh + g;
+    store_vrow16<DT>(a.vn, b * a.v_bs + g * a.v_hs + j * a.v_rs + 16 * db, a.vvec, a.qv, a.vc + (blk * 16 + t % 16) * a.D + 16 * db,
+                     a.ve + (blk * db_n + db) * 16 + t % 16);
+  }
+}
+
+struct GArgs {
+  const unsigned char* src[5];  // the pool's sections
+  unsigned char* dst[5];        // the dense cache's (batch 1)
+  const int32_t* row;           // the slot's table row (device)
+  int64_t slot, kvh, D, nblk, capb, stage16;  // blocks of 16 keys copied, cap / 16 of the dense cache, 16-byte pieces of a kv head's staging rows
+};
+
+// One sequence out of the pool into a dense cache of batch 1: bytes as they are, in 16-byte pieces.  A thread: one piece of one
+// (kv head, block) - D pieces of K codes, D / 16 of K exponents, D of V codes, D / 16 of V exponents - or one piece of the staging rows.
+__global__ __launch_bounds__(256) void k_kv_pool_gather(const GArgs a) {
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t e16 = a.D / 16, per = 2 * (a.D + e16), nB = a.kvh * a.nblk * per;
+  if (i < nB) {
+    const int64_t g = i / (a.nblk * per), kb = (i / per) % a.nblk;
+    int64_t u = i % per;
+    const int64_t sblk = (int64_t)a.row[kb] * a.kvh + g, dblk = g * a.capb + kb;
+    int sec = 0;
+    if (u >= a.D) u -= a.D, sec = 1;
+    if (sec == 1 && u >= e16) u -= e16, sec = 2;
+    if (sec == 2 && u >= a.D) u -= a.D, sec = 3;
+    const int64_t item = (sec & 1) ? e16 : a.D;  // 16-byte pieces of a block in this section
+    ((uint4*)a.dst[sec])[dblk * item + u] = ((const uint4*)a.src[sec])[sblk * item + u];
+    return;
+  }
+  i -= nB;
+  if (i < a.kvh * a.stage16) ((uint4*)a.dst[4])[i] = ((const uint4*)a.src[4])[a.slot * a.kvh * a.stage16 + i];
 }
 
 struct UArgs {
@@ -224,6 +334,44 @@ int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, 
     }
     return check_launch("lqer_kv_cache_append");
   });
+}
+
+size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D) {
+  return kvc::pool_layout(dtype, pages, slots, kv_heads, D).total;
+}
+
+int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
+                            const QP& qk, const QP& qv, hipStream_t st) {
+  const kvc::PoolLayout l = kvc::pool_layout(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  unsigned char* base = (unsigned char*)p.pool;
+  kvc::PArgs a;
+  a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.stage = base + l.k_stage;
+  a.kn = k_new, a.vn = v_new, a.tbl = p.block_table, a.slots = p.seq_slots, a.lens = p.lens;
+  a.batch = batch, a.kvh = p.kv_heads, a.D = p.D, a.n = n, a.tstride = p.table_stride, a.nkbm = (n + 14) / 16 + 1;
+  a.k_bs = ks[0], a.k_hs = ks[1], a.k_rs = ks[2], a.v_bs = vs[0], a.v_hs = vs[1], a.v_rs = vs[2];
+  a.qk = qk, a.qv = qv;
+  const int esz = p.dtype == LQER_F32 ? 4 : 2;
+  a.kvec = al16(k_new, ks, esz), a.vvec = al16(v_new, vs, esz);
+  const int64_t items = batch * p.kv_heads * (a.nkbm * (p.D / 4) + n * (p.D / 16));
+  return with_dtype(p.dtype, [&](auto dt) {
+    kvc::k_kv_pool_append<decltype(dt)::value><<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
+    return check_launch("lqer_kv_pool_append");
+  });
+}
+
+int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st) {
+  const kvc::PoolLayout pl = kvc::pool_layout(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  const kvc::Layout dl = kvc::layout(p.dtype, 1, p.kv_heads, capacity, p.D);
+  const unsigned char* sb = (const unsigned char*)p.pool;
+  unsigned char* db = (unsigned char*)cache;
+  kvc::GArgs a;
+  const size_t so[5] = {pl.k_codes, pl.k_exps, pl.v_codes, pl.v_exps, pl.k_stage}, dof[5] = {dl.k_codes, dl.k_exps, dl.v_codes, dl.v_exps, dl.k_stage};
+  for (int i = 0; i < 5; ++i) a.src[i] = sb + so[i], a.dst[i] = db + dof[i];
+  a.row = p.block_table + slot * p.table_stride, a.slot = slot, a.kvh = p.kv_heads, a.D = p.D;
+  a.nblk = (T + 15) / 16, a.capb = dl.cap / 16, a.stage16 = p.D * (p.dtype == LQER_F32 ? 4 : 2);  // 16 rows x D x esz / 16
+  const int64_t items = p.kv_heads * (a.nblk * 2 * (p.D + p.D / 16) + a.stage16);
+  kvc::k_kv_pool_gather<<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
+  return check_launch("lqer_kv_pool_gather");
 }
 
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,

@@ -46,6 +46,28 @@ __host__ inline Sections<B> sections(B* base, const Layout& l) {
   return {base + l.k_codes, base + l.k_exps, base + l.v_codes, base + l.v_exps, l.cap};
 }
 
+// The paged pool (include/lqer_hip.h "paged KV pool"): the same five sections, but an ITEM - one (page, kv head), i.e. one block of 16
+// keys of one kv head - at index page * kv_heads + g instead of the dense cache's z * (cap / 16) + t / 16; within an item the bytes are
+// the dense cache's.  So one spelling of the addresses serves both: block index `blk` -> codes of key t at (blk * 16 + t % 16) * D,
+// K exponents at blk * D, V exponents at (blk * (D / 16) + d / 16) * 16 + t % 16.  The staging rows are per sequence SLOT.
+struct PoolLayout {
+  size_t k_codes, k_exps, v_codes, v_exps, k_stage, total;
+};
+
+// D a multiple of 16, dtype one of the three: the caller checked
+__host__ inline PoolLayout pool_layout(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D) {
+  PoolLayout l;
+  const size_t items = (size_t)(pages * kv_heads), esz = dtype == LQER_F32 ? 4 : 2;
+  const size_t codes = up256(items * 16 * D), exps = up256(items * D);
+  l.k_codes = 0;
+  l.k_exps = l.k_codes + codes;
+  l.v_codes = l.k_exps + exps;
+  l.v_exps = l.v_codes + codes;
+  l.k_stage = l.v_exps + exps;
+  l.total = l.k_stage + up256((size_t)(slots * kv_heads) * 16 * D * esz);
+  return l;
+}
+
 // one block of 16 -> 16 codes (four dwords, element i in byte i) and the exponent byte: quant16_bf16's decisions and arithmetic,
 // stopped before the final scaling (the fast path: mxint16_bf16_fast's r; the other: mxint_mantissa)
 template <bool FLUSH_TINY>

@@ -188,3 +188,262 @@ def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mas
     out, ob, stats = _attention_outputs(q, out_layout, return_stats)
     (prefill_packed if prefill else attend_packed)(q, cache.buf, cache.kv_heads, cache.capacity, t, cache.fmts, scaling, m, causal, ob, stats)
     return (out, stats) if return_stats else out
+
+
+# ---- the paged pool (include/lqer_hip.h "paged KV pool"): pages of 16 keys, per-sequence lengths in a decode batch ------------------
+PAGE_KEYS = 16
+
+
+def pool_bytes(dtype: torch.dtype, pages: int, slots: int, kv_heads: int, head_dim: int) -> int:
+    return _lib.lib().lqer_kv_pool_bytes(ops._DT[dtype], pages, slots, kv_heads, head_dim)
+
+
+class PageTable:
+    """The page allocator and the host mirror of the block table and the lengths: plain host state, no torch device in it.
+
+    A sequence id is handed out once and never again, so a freed id stays refused; it maps to a SLOT (a row of the table, a set of
+    staging rows), and slots and pages are reused.  `reserve` is all or nothing: it validates every addressed sequence and counts
+    the pages of the whole call before it takes one."""
+
+    def __init__(self, num_pages: int, max_seqs: int, max_pages_per_seq=None):
+        if max_pages_per_seq is None:
+            max_pages_per_seq = num_pages
+        if num_pages < 1 or max_seqs < 1 or max_pages_per_seq < 1:
+            raise ValueError(f"PageTable: num_pages {num_pages}, max_seqs {max_seqs}, max_pages_per_seq {max_pages_per_seq}")
+        self.num_pages, self.max_seqs, self.max_pages_per_seq = num_pages, max_seqs, max_pages_per_seq
+        self._free_pages = list(range(num_pages - 1, -1, -1))  # a stack: the page freed last is taken first
+        self._free_slots = list(range(max_seqs - 1, -1, -1))
+        self._slot = {}                                        # live seq -> slot
+        self._next_seq = 0
+        self.table = [[0] * max_pages_per_seq for _ in range(max_seqs)]  # [slot][i]: the page of keys 16 i .. 16 i + 15
+        self.pages_of = [0] * max_seqs                                   # entries of a slot's row that are its pages
+        self.lengths = [0] * max_seqs                                    # [slot]
+
+    @property
+    def pages_free(self) -> int:
+        return len(self._free_pages)
+
+    @property
+    def max_len(self) -> int:
+        """The bound handed to the library with every call: what the table's rows have room for, whatever the lengths are."""
+        return PAGE_KEYS * self.max_pages_per_seq
+
+    def alloc(self) -> int:
+        if not self._free_slots:
+            raise RuntimeError(f"PagedKVCache: all {self.max_seqs} sequence slots are live")
+        seq, self._next_seq = self._next_seq, self._next_seq + 1
+        slot = self._free_slots.pop()
+        self._slot[seq] = slot
+        self.pages_of[slot] = self.lengths[slot] = 0
+        return seq
+
+    def slot(self, seq: int) -> int:
+        try:
+            return self._slot[seq]
+        except (KeyError, TypeError):
+            raise KeyError(f"PagedKVCache: sequence {seq!r} is unknown or already freed") from None
+
+    def free(self, seq: int) -> None:
+        slot = self.slot(seq)
+        del self._slot[seq]
+        row = self.table[slot]
+        for i in range(self.pages_of[slot] - 1, -1, -1):
+            self._free_pages.append(row[i])
+        self.pages_of[slot] = self.lengths[slot] = 0
+        self._free_slots.append(slot)
+
+    def length(self, seq: int) -> int:
+        return self.lengths[self.slot(seq)]
+
+    def slots(self, seqs) -> list:
+        """The slots of `seqs`; raises for an unknown, freed or repeated one."""
+        out = [self.slot(s) for s in seqs]
+        if len(set(out)) != len(out):
+            raise ValueError(f"PagedKVCache: a sequence is named twice in {list(seqs)}")
+        return out
+
+    def reserve(self, seqs, n: int):
+        """Pages for n more keys of every sequence of `seqs`, taken before anything is launched: (slots, lengths before, pages taken
+        per slot).  Raises with no page taken and nothing changed; the lengths advance with commit(), and rollback() hands the
+        pages back when the launch is refused after all."""
+        slots = self.slots(seqs)
+        if n < 1:
+            raise ValueError(f"PagedKVCache.append: {n} new keys")
+        need = []
+        for seq, s in zip(seqs, slots):
+            pages = (self.lengths[s] + n + PAGE_KEYS - 1) // PAGE_KEYS
+            if pages > self.max_pages_per_seq:
+                raise RuntimeError(f"PagedKVCache.append: sequence {seq} would hold {self.lengths[s] + n} keys = {pages} pages, beyond "
+                                   f"max_pages_per_seq = {self.max_pages_per_seq}")
+            need.append(pages - self.pages_of[s])
+        if sum(need) > len(self._free_pages):
+            raise RuntimeError(f"PagedKVCache.append: out of pages - {sum(need)} needed, {len(self._free_pages)} of {self.num_pages} free")
+        for s, k in zip(slots, need):
+            for _ in range(k):
+                self.table[s][self.pages_of[s]] = self._free_pages.pop()
+                self.pages_of[s] += 1
+        return slots, [self.lengths[s] for s in slots], need
+
+    def rollback(self, slots, taken) -> None:
+        """Undo a reserve() whose launch did not happen: the pages go back in the order that makes the next reserve() take the same."""
+        for s, k in zip(reversed(slots), reversed(taken)):
+            for _ in range(k):
+                self.pages_of[s] -= 1
+                self._free_pages.append(self.table[s][self.pages_of[s]])
+
+    def commit(self, slots, n: int) -> None:
+        for s in slots:
+            self.lengths[s] += n
+
+
+class PagedKVCache:
+    """K and V of one attention layer for MANY sequences of their own lengths, as QuantizedKVCache's codes and exponents in pages of 16
+    keys (include/lqer_hip.h "paged KV pool"): memory is paid per page in use, a freed sequence's pages serve the next, nothing is copied
+    to grow.  A batch of a decode step addresses any subset of the live sequences in any order - continuous batching.
+
+    .alloc() -> seq    a new, empty sequence;  .free(seq)  its pages and slot back to the pool (no clearing: pages are reused dirty)
+    .append(seqs, k, v)   k / v [len(seqs), kv_heads, n, head_dim]: n more keys for every sequence of `seqs`.  The pages of the WHOLE
+                       call are taken before anything is launched; out of pages, beyond max_pages_per_seq, an unknown, freed or
+                       repeated seq raise with the pool untouched and no page taken - and so does a refusal of the library itself:
+                       the reservation is rolled back
+    .length(seq);  .pages_free;  .nbytes
+    .to_dense(seq) -> QuantizedKVCache (batch 1) with the sequence's bytes - for more than 8 query rows (attention_flexible_cached
+                       with kernel="prefill") or an export;  .dequantized(seq) -> (K, V) [1, kv_heads, length, head_dim] fp32, for tests"""
+
+    covers = staticmethod(QuantizedKVCache.covers)
+
+    def __init__(self, num_pages: int, max_seqs: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device,
+                 max_pages_per_seq=None):
+        if not self.covers(cfg0, cfg1, head_dim, dtype):
+            raise NotImplementedError(f"PagedKVCache: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
+                                      "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
+                                      "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
+        self.pt = PageTable(num_pages, max_seqs, max_pages_per_seq)
+        if kv_heads < 1 or kv_heads > _MAX_GRID_Z or max_seqs > _MAX_GRID_Z or self.pt.max_len > 1 << 30:
+            raise ValueError(f"PagedKVCache: kv_heads {kv_heads}, max_seqs {max_seqs}, max_pages_per_seq {self.pt.max_pages_per_seq}")
+        self.kv_heads, self.head_dim, self.dtype, self.device = kv_heads, head_dim, dtype, torch.device(device)
+        self.cfg0, self.cfg1 = cfg0, cfg1
+        self.fmts = _attn_fmts(cfg0, cfg1)  # Q, K^T, P, V
+        self.buf = torch.empty(pool_bytes(dtype, num_pages, max_seqs, kv_heads, head_dim), dtype=torch.uint8, device=self.device)
+        # the device copies of the metadata: the table (rows updated when they change), the slots and the lengths of the current call
+        self.table = torch.zeros(max_seqs, self.pt.max_pages_per_seq, dtype=torch.int32, device=self.device)
+        self._slots = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
+        self._lens = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
+
+    num_pages = property(lambda self: self.pt.num_pages)
+    max_seqs = property(lambda self: self.pt.max_seqs)
+    pages_free = property(lambda self: self.pt.pages_free)
+    nbytes = property(lambda self: self.buf.numel())
+
+    def alloc(self) -> int:
+        return self.pt.alloc()
+
+    def free(self, seq: int) -> None:
+        self.pt.free(seq)
+
+    def length(self, seq: int) -> int:
+        return self.pt.length(seq)
+
+    def _pool_args(self):
+        return (self.buf.data_ptr(), self.buf.numel(), self.pt.num_pages, self.pt.max_seqs, self.table.data_ptr(), self.pt.max_pages_per_seq)
+
+    def _call_meta(self, slots, lens):
+        """seq_slots and lens of one call on the device: ordinary copies on the current stream, ordered before the launches."""
+        n = len(slots)
+        self._slots[:n].copy_(torch.tensor(slots, dtype=torch.int32))
+        self._lens[:n].copy_(torch.tensor(lens, dtype=torch.int32))
+        return self._slots.data_ptr(), self._lens.data_ptr(), self.pt.max_len
+
+    @torch.no_grad()
+    def append(self, seqs, k: torch.Tensor, v: torch.Tensor) -> None:
+        seqs = list(seqs)
+        want = (len(seqs), self.kv_heads, self.head_dim)
+        if k.dim() != 4 or (k.shape[0], k.shape[1], k.shape[3]) != want or k.shape != v.shape or k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError(f"PagedKVCache.append: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} for {len(seqs)} sequences of "
+                             f"[{self.kv_heads}, n, {self.head_dim}] {self.dtype}")
+        if k.device != self.buf.device or v.device != self.buf.device:
+            raise ValueError(f"PagedKVCache.append: k on {k.device} / v on {v.device} for a pool on {self.buf.device}")
+        n = k.shape[2]
+        if n == 0 or not seqs:
+            self.pt.slots(seqs)
+            return
+        slots, lens, taken = self.pt.reserve(seqs, n)  # (raises with nothing taken)
+        try:
+            self._launch_append(slots, lens, taken, k, v, n)
+        except BaseException:
+            self.pt.rollback(slots, taken)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
+            raise
+        self.pt.commit(slots, n)
+
+    def _launch_append(self, slots, lens, taken, k, v, n) -> None:
+        for s, t in zip(slots, taken):
+            if t:
+                self.table[s].copy_(torch.tensor(self.pt.table[s], dtype=torch.int32))
+        if k.stride(3) != 1:
+            k = k.contiguous()
+        if v.stride(3) != 1:
+            v = v.contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lqer_kv_pool_append(*self._pool_args(), *self._call_meta(slots, lens), k.data_ptr(), v.data_ptr(), _tri(k), _tri(v),
+                                                      ops._DT[self.dtype], len(slots), self.kv_heads, self.head_dim, n, C.byref(self.fmts[1]),
+                                                      C.byref(self.fmts[3]), ops._stream(self.device)),
+                       "lqer_kv_pool_append")
+
+    @torch.no_grad()
+    def to_dense(self, seq: int) -> QuantizedKVCache:
+        slot, t = self.pt.slot(seq), self.pt.length(seq)
+        dense = QuantizedKVCache(1, self.kv_heads, self.head_dim, self.cfg0, self.cfg1, self.dtype, self.device, capacity=max(t, PAGE_KEYS))
+        if t:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().lqer_kv_pool_gather(self.buf.data_ptr(), self.buf.numel(), ops._DT[self.dtype], self.pt.num_pages,
+                                                          self.pt.max_seqs, self.kv_heads, self.head_dim, self.table.data_ptr(),
+                                                          self.pt.max_pages_per_seq, slot, t, dense.buf.data_ptr(), dense.buf.numel(),
+                                                          dense.capacity, ops._stream(self.device)),
+                           "lqer_kv_pool_gather")
+        dense.length = t
+        return dense
+
+    def dequantized(self, seq: int):
+        return self.to_dense(seq).dequantized()
+
+
+@torch.no_grad()
+def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False, out_layout="bhsd", return_stats=False, ws=None):
+    """attention_flexible(q[b:b+1], K_b, V_b, cache.cfg0, cache.cfg1, scaling, causal=causal, kernel="decode") for every sequence
+    seqs[b] of a PagedKVCache, bit for bit, in ONE call over sequences of different lengths (lqer_attention_q_decode_paged).
+    q [len(seqs), h, s, d] with s <= 8; `causal`: key j of sequence b visible to query i iff j <= i + (length_b - s).  There is no mask
+    tensor - the per-sequence lengths are what a padding mask stood for - and no other route: an empty sequence, causal with
+    s > a length, s > 8, a wrong dtype, device or head count raise ValueError.  `out_layout` and `return_stats` as attention_flexible;
+    ws: a uint8 workspace or None (the stream's)."""
+    _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
+    seqs = list(seqs)
+    if q.dim() != 4:
+        raise ValueError(f"attention_flexible_paged: q {tuple(q.shape)} is not [len(seqs), h, s, d]")
+    b, h, s, d = q.shape
+    if s > _ATTN_DECODE_MAX_S:
+        raise ValueError(f"attention_flexible_paged: {s} query rows per head - the kernel over the paged cache takes up to {_ATTN_DECODE_MAX_S} "
+                         "(more: attention_flexible_cached(q, cache.to_dense(seq), ..., kernel='prefill'))")
+    if q.dtype != cache.dtype or q.device != cache.buf.device or b != len(seqs) or b < 1 or d != cache.head_dim or h % cache.kv_heads or s < 1 or h > _MAX_GRID_Z:
+        raise ValueError(f"attention_flexible_paged: q {tuple(q.shape)} {q.dtype} on {q.device} for {len(seqs)} sequences of a cache "
+                         f"[{cache.kv_heads}, {cache.head_dim}] {cache.dtype} on {cache.buf.device}")
+    try:
+        slots = cache.pt.slots(seqs)
+    except KeyError as e:
+        raise ValueError(e.args[0]) from None
+    lens = [cache.pt.lengths[x] for x in slots]
+    if min(lens) < 1 or (causal and s > min(lens)):
+        raise ValueError(f"attention_flexible_paged: lengths {lens} of sequences {seqs} - an empty sequence has nothing to attend to"
+                         + (f", and causal needs {s} query rows <= every length" if causal else ""))
+    if q.stride(3) != 1:
+        q = q.contiguous()
+    out, ob, stats = _attention_outputs(q, out_layout, return_stats)
+    L, f = _lib.lib(), cache.fmts
+    with torch.cuda.device(q.device):
+        if ws is None:
+            ws = ops.workspace(q.device, max(L.lqer_attention_q_decode_paged_workspace_bytes(b, h, cache.kv_heads, s, cache.pt.max_len, d), 16))
+        _lib.check(L.lqer_attention_q_decode_paged(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens), ob.data_ptr(),
+                                                   stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, cache.kv_heads, s, d,
+                                                   _tri(q), _tri(ob), float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]),
+                                                   C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device)),
+                   "lqer_attention_q_decode_paged")
+    return (out, stats) if return_stats else out
