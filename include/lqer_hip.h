@@ -167,6 +167,12 @@ typedef struct lqer_linear_desc {
 #define LQER_TUNE_BOUT_IN_PROLOGUE 0x2000000 /* 128-row tile kernel, B_out in blocks of 16: re-quantize the side product in front of the main
                                               loop (rounds 1-5) instead of under its first 16 k-steps with the product added behind the
                                               last one (default from K = 1024; csrc/gemm_w4a8.hip, DEFER)                               */
+#define LQER_TUNE_W_EXP_TABLE 0x8000000 /* 128-row kernel family, sign-magnitude 4-bit weights on the bf16 main loop: expand the nibbles
+                                           through the e4m3 table (the minifloat weights' instantiations with the integers' table:
+                                           128-row tiles, staged side path) instead of reading them as e4m3 subnormals with the
+                                           block scale carrying 2^9.  Same bits - and REQUIRED for a weight image that holds an
+                                           exponent byte above 245 (a block maximum of 2^121 or more; lqer_f16_prepare reports
+                                           it as flags[0] & 2), where byte + 9 leaves the fp32 exponent field                  */
 #define LQER_TUNE_DECODE_NO_POLL 0x10000 /* one-launch decode route: no wait for the producers' tiles - every weight-streaming
                                          workgroup computes the partial tiles of x A itself (the bounded wait's fall-back)     */
 
@@ -415,6 +421,8 @@ int lqer_desc_limbs(const lqer_linear_desc_t* desc, int* act_limbs, int* xa_limb
  * Allowed only when
  * this call leaves flags[0] (a weight block scale outside the fp16 range 2^-24 .. 2^13) and flags[1] (an element of
  * A that is not an fp16 number) at zero (device int32[2]); otherwise use LQER_Q_PASSTHROUGH with width 11.
+ * flags[0] & 2 (r = 0 and null A images ask for the weight flags alone): an exponent byte above 245 - such an image needs
+ * LQER_TUNE_W_EXP_TABLE in the descriptor of every lqer_linear_gemm* / lqer_linear_forward* call on the bf16 route.
  * A_out / xaq / b_t are as for LQER_Q_PASSTHROUGH.  Calls take dtype = LQER_F16.  A dense tensor (ldx == K) with
  * K % LQER_K_ALIGN == 0, M % LQER_M_ALIGN == 0 (or M <= 64) and 16-byte alignment already is its image: lqer_linear_forward
  * then skips the copy, and the split API accepts xq == x in lqer_quantize_act_xa / lqer_linear_gemm. */

@@ -688,6 +688,12 @@ static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, Ge
     if (!mf_e4m3_table(d->w_fmt, g.w_lut, &s)) return LQER_E_UNSUPPORTED;
     g.w_mf = 1;
   }
+  // sign-magnitude nibbles whose image holds an exponent byte the table-free expand cannot carry (expand_frag_lin): the table
+  // instantiations, with the integers 0..7 as the table (expand_frag's own).  The fp16 and int8 main loops expand otherwise.
+  if ((d->tuning & LQER_TUNE_W_EXP_TABLE) && d->w_fmt.kind == LQER_Q_MXINT && !x_is_f16(d) && !x_is_i8(d)) {
+    g.w_lut[0] = 0x44403800u, g.w_lut[1] = 0x4E4C4A48u;
+    g.w_mf = 1;
+  }
   if (lowrank && d->b_out_fmt.kind == LQER_Q_MINIFLOAT && (x_is_i8(d) || x_is_f16(d))) {
     set_error("linear_gemm: a minifloat B_out runs on the bf16 128-row tile kernel only (x_quantizer %s)",
               x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH with width 11" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");

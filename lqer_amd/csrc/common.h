@@ -383,6 +383,21 @@ __device__ __forceinline__ float row16_max(float v) {
 }
 
 
+// ((v >> 8 B) & 0xff) << 23: byte B of a dword of biased block exponents -> the fp32 bits of its scale, as ONE vector instruction (an
+// SDWA shift that selects the byte; hipcc finds that form for byte 0 only and takes a shift + and pair for the others).  The shift
+// count travels in a scalar register: SDWA takes no inline constant on gfx9.
+template <int B>
+__device__ __forceinline__ uint32_t exp_byte_bits(uint32_t v) {
+  static_assert(B >= 0 && B < 4, "byte of a dword");
+  uint32_t r;
+  const uint32_t sh = 23;
+  if constexpr (B == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "s"(sh), "v"(v));
+  else if constexpr (B == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "s"(sh), "v"(v));
+  else if constexpr (B == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "s"(sh), "v"(v));
+  else asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "s"(sh), "v"(v));
+  return r;
+}
+
 // Expand 8 sign-magnitude 4-bit codes (one 32-bit word = 8 consecutive k of one weight row; nibble p
 // holds k = p/2 for even p, 4 + p/2 for odd p) times the block scale into one MFMA operand fragment:
 // magnitude -> fp8 (e4m3) byte through a v_perm_b32 table, sign bit OR-ed in, then
@@ -399,6 +414,25 @@ __device__ __forceinline__ bf16x8 expand_frag(uint32_t word, uint32_t scale_bits
   uint32_t fo = __builtin_amdgcn_perm(LUT_HI, LUT_LO, t & 0x07070707u);     // k 4..7
   fe |= (word << 4) & 0x80808080u;
   fo |= word & 0x80808080u;
+  u32x4 r;
+  r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fe, scale, false));
+  r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fe, scale, true));
+  r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fo, scale, false));
+  r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fo, scale, true));
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+// The same fragment without the table: an e4m3 byte sign << 7 | magnitude has a zero exponent field, i.e. it is the subnormal
+// magnitude * 2^-9 - linear in the 3-bit magnitude - so the nibble's own bits are the byte and the block scale carries the 2^9:
+// scale9_bits = (exponent byte + 9) << 23 (the caller adds the 9 once per exponent dword).  6 logic + 4 conversions instead of 10 + 4;
+// every step exact (tests/expand_probe.hip: all nibble words x all exponent bytes).  Only for images whose exponent bytes stay
+// <= LIN_EXP_BYTE_MAX - beyond it byte + 9 leaves the fp32 exponent field; pack.hip::k_w_f16_range reports such an image
+// (flags[0] & 2) and its caller keeps the table form (LQER_TUNE_W_EXP_TABLE).
+constexpr int LIN_EXP_BYTE_MAX = 254 - 9;
+__device__ __forceinline__ bf16x8 expand_frag_lin(uint32_t word, uint32_t scale9_bits) {
+  const float scale = __uint_as_float(scale9_bits);
+  const uint32_t fe = (word & 0x07070707u) | ((word << 4) & 0x80808080u);  // k 0..3
+  const uint32_t fo = ((word >> 4) & 0x07070707u) | (word & 0x80808080u);  // k 4..7
   u32x4 r;
   r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fe, scale, false));
   r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(fe, scale, true));

@@ -21,7 +21,9 @@
 //    4-slot ring, three k-steps ahead, retired with a COUNTED s_waitcnt vmcnt so that loads stay in
 //    flight across barriers.  The activation tile is staged as bf16 (XOR swizzle on the source
 //    address); the weights stay PACKED in LDS (4-bit codes + block exponents, 0.56 B per weight) and
-//    each wave expands the fragments it needs in registers, in the shadow of its MFMAs.
+//    each wave expands the fragments it needs in registers, in the shadow of its MFMAs - sign-magnitude nibbles
+//    on the bf16 main loop without a table (common.h expand_frag_lin: 11 vector instructions per fragment with
+//    its scale, 45 per wave and k-step in all; with the table 55).
 //  * the two waves of a SIMD run half a k-step apart (LOAD / COMPUTE ping-pong, see the main loop).
 //  * tiles are numbered so that each of the 8 XCDs works on a contiguous run of tiles (same token
 //    rows -> the activation slab stays in that XCD's L2).
@@ -552,23 +554,28 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
           : "memory", "scc");
     }
     STAMP(1);  // LDS reads + DMA issue + waits
+    // sign-magnitude nibbles on the bf16 main loop: the table-free expand (expand_frag_lin), its 2^9 added to the step's four
+    // exponent bytes at once (no carry: the plan sends an image with a byte beyond LIN_EXP_BYTE_MAX to the WMF instantiation)
+    constexpr bool WLIN = !WMF && !WTWOS && !XF16;
+    if constexpr (WLIN) we += 0x09090909u;
     auto expand = [&](uint32_t word, uint32_t scale_bits) {
       if constexpr (WMF) return expand_frag_lut(word, scale_bits, g.w_lut[0], g.w_lut[1]);
       else if constexpr (WTWOS) return expand_frag_twos(word, scale_bits);
+      else if constexpr (WLIN) return expand_frag_lin(word, scale_bits);
       else return expand_frag_t<XF16>(word, scale_bits);
     };
-    bf16x8 wb_first = expand(wr[0], (we & 0xffu) << 23);
+    bf16x8 wb_first = expand(wr[0], exp_byte_bits<0>(we));
     asm volatile("s_barrier" : "+v"(wb_first)::"memory");
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     STAMP(4);  // expand of the first fragment + barrier
     // ---- COMPUTE(kt)
     defer_piece(piece_c);
+    // biased exponent byte ks -> fp32 bits of the block scale 2^(e - mbits)
+    const uint32_t sc[4] = {0u, exp_byte_bits<1>(we), exp_byte_bits<2>(we), exp_byte_bits<3>(we)};  // ([0]: wb_first has it)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      // biased exponent byte ks -> fp32 bits of the block scale 2^(e - mbits)
-      const uint32_t sc = ((we >> (8 * ks)) & 0xffu) << 23;
-      const bf16x8 wb = ks == 0 ? wb_first : expand(wr[ks], sc);
+      const bf16x8 wb = ks == 0 ? wb_first : expand(wr[ks], sc[ks]);
 #pragma unroll
       for (int i = 0; i < MT; ++i) acc[i] = mfma_32x32x16<XF16>(wb, xa[ks][i], acc[i]);
     }

@@ -363,18 +363,20 @@ int pack_lowrank_dispatch(const void* A, const void* B, int dtype, int64_t K, in
 // The main loops then expand the weights to fp16 (code * 2^(eb - 127), eb the stored exponent byte) and the side GEMM
 // reads A as ONE fp16 image.  Both must be exact: flags[0] is raised when a weight block's scale leaves the fp16
 // range (subnormals included: 2^-24 .. 2^13 keeps 7 * scale finite), flags[1] when an element of A is not an fp16
-// number.  The caller falls back to bf16 limbs (act_limbs.hip) if either is set.
+// number.  The caller falls back to bf16 limbs (act_limbs.hip) if either is set.  flags[0] & 2: an exponent byte beyond
+// LIN_EXP_BYTE_MAX - the caller of the bf16 route then asks for the table expand (LQER_TUNE_W_EXP_TABLE).
 __global__ __launch_bounds__(256) void k_w_f16_range(const uint8_t* __restrict__ wp, int64_t panels, int32_t* __restrict__ flags) {
-  bool bad = false;
+  bool bad = false, big = false;  // big: beyond the table-free expand of the bf16 main loop (expand_frag_lin: byte + 9 <= 254)
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < panels * 16; idx += (int64_t)gridDim.x * 256) {
     const uint32_t e4 = *(const uint32_t*)(wp + (idx >> 4) * LQER_PANEL_BYTES + 512 + (idx & 15) * 4);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const int eb = (int)((e4 >> (8 * b)) & 0xffu);
       bad |= eb < 127 - 24 || eb > 127 + 13;
+      big |= eb > LIN_EXP_BYTE_MAX;
     }
   }
-  if (bad) atomicOr(flags, 1);
+  if (bad) atomicOr(flags, big ? 3 : 1);
 }
 
 __global__ __launch_bounds__(256) void k_a_f16(const bf16_t* __restrict__ limbs, int a_limbs, int64_t total, _Float16* __restrict__ out,

@@ -64,6 +64,7 @@ class _LinearBase(nn.Linear):
         self._x_i8 = False         # per-token 8-bit activations on the int8 MFMA route (decided when the images are built)
         self.i8_a_f16 = True       # int8 route: fp16 A as one fp16 image for the side GEMM (False: the bf16 limb pair)
         self.a8_native = True      # False: keep them on the bf16 route
+        self._w_exp_table = False  # the weight image holds an exponent byte above 245: the bf16 GEMM's table expand (decided when the images are built)
         self.a16_fused = True      # block-16 MXINT activations: build the image the one-launch activation kernel reads (a_limbs = -2)
         self.tuning = 0            # lqer_linear_desc_t.tuning (_lib.TUNE_*): per-call kernel-variant knobs of tests, same bits
         self._setup_quantizers(q_config)
@@ -106,7 +107,7 @@ class _LinearBase(nn.Linear):
 
         return LinearDesc(self.in_features, self.out_features, self.rank, int(self.bias is not None),
                           eff("x", _SIG_BITS[dt]), f["w"], f.get("b", none), eff("A_out", 24 if dt == torch.float32 else 16),
-                          f.get("B_out", none), int(getattr(self, "tuning", 0)))
+                          f.get("B_out", none), int(getattr(self, "tuning", 0)) | (_lib.TUNE_W_EXP_TABLE if self._w_exp_table else 0))
 
     def _limbs(self):
         """(activation limbs, x A limbs) of the packed images - 1, 1 unless x / A_out are pass-through."""
@@ -121,6 +122,9 @@ class _LinearBase(nn.Linear):
         self._x_i8 = False
         self._fw_cache = {}
         fx, fw, K = self._fmt["x"], self._fmt["w"], self.in_features
+        # sign-magnitude nibbles: the bf16 main loop reads them as e4m3 subnormals and adds 9 to the block's exponent byte - an image
+        # with a byte above 245 (block maxima from 2^121) keeps the table expand, in every descriptor of this module
+        self._w_exp_table = fw.kind == _lib.Q_MXINT and ops.w_exp_needs_table(p["w"], self.out_features, K, fw)
         mf_side = any(self._fmt.get(r) is not None and self._fmt[r].kind == _lib.Q_MINIFLOAT for r in ("A_out", "B_out"))
         if (self.a8_native and fx.kind == _lib.Q_MXINT and fw.kind == _lib.Q_MXINT and fx.width <= 8 and (fx.block <= 0 or fx.block >= K)
                 and K >= 128 and (fw.block <= 0 or fw.block >= K or fw.block % 128 == 0) and not mf_side):
@@ -215,6 +219,7 @@ class _LinearBase(nn.Linear):
         self._fw_cache = {}
         self._x_f16 = False
         self._x_i8 = False
+        self._w_exp_table = False
         self._w_ver = None
         if weight_changed:
             self._w_single = None

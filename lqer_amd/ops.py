@@ -308,6 +308,20 @@ def f16_prepare(w_packed: torch.Tensor, N: int, K: int, a_t_limbs: Optional[torc
 
 
 @_on_tensor_device
+def w_exp_needs_table(w_packed: torch.Tensor, N: int, K: int, fmt: QFmt) -> bool:
+    """True when a sign-magnitude weight image (single copy) holds an exponent byte above 245: the bf16 main loop's table-free
+    expand adds 9 to the byte, so such an image needs _lib.TUNE_W_EXP_TABLE in its descriptors (include/lqer_hip.h).  Once per
+    image, as f16_prepare.  Synchronises."""
+    _need_gpu(w_packed)
+    L = _lib.lib()
+    dev = w_packed.device
+    flags = torch.zeros(2, dtype=torch.int32, device=dev)
+    k_all = L.lqer_padded_k(K) * w_limbs(fmt)  # (the limb images of a 5..8-bit weight lie side by side along k)
+    check(L.lqer_f16_prepare(w_packed.data_ptr(), N, k_all, None, 0, 0, None, flags.data_ptr(), _stream(dev)), "lqer_f16_prepare")
+    return bool(flags.tolist()[0] & 2)
+
+
+@_on_tensor_device
 def a_f16_image(w_packed: torch.Tensor, N: int, K: int, a_t_limbs: torch.Tensor, a_limbs: int, r: int):
     """A^T as ONE fp16 image [rp][Kp] for the int8 route's side GEMM (int8 mantissas x fp16 A on the fp16 MFMA, a_limbs = -1
     in lqer_lowrank_xa / lqer_quantize_act_xa / lqer_linear_forward): (ok, image) - ok is False when an element of A is not
