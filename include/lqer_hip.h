@@ -679,13 +679,28 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * T <= max_len (ceil(max_len / 16) up to 256 keys, 16 up to 2048, ceil(max_len / 128) beyond)
  *   [S2, fp32: rows x Tp][chunk statistics, fp32: rows x nchs x 2][partial outputs, fp32: rows x nchs x D]    each rounded up to 256 bytes.
  * Three launches on `stream`, no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
+ * lqer_attention_q_paged: lqer_attention_q_decode_paged's argument list, word for word, and its metadata contract, for ANY S >= 1
+ * (uniform over the call) - a prompt, a second turn, a chunk of a long prompt or a speculated block of more than 8 tokens on paged
+ * sequences, the whole ragged batch in one call.  It is to lqer_attention_q_kv what the call above is to lqer_attention_q_decode_kv:
+ * the two bf16 images of the prefill kernel are written from the pool's codes and exponents, found through the block table - no
+ * gather, no dense copy -, and the attention kernel takes T = lens[b], and with it the causal offset T_b - S, per sequence.  For every
+ * b, out[b] and row_stats[b] are the SAME BITS as lqer_attention_q with batch = 1 on the raw K and V of that sequence - whatever else
+ * is in the batch, whatever pages it lives on, whatever max_len is and whatever the workspace held (K or V holding a NaN excepted, as
+ * with the packed cache).  A sequence with lens[b] = 0 gets out[b] = 0 and its row_stats untouched.  The pool is only read.
+ * workspace: lqer_attention_q_paged_workspace_bytes(batch, heads, kv_heads, S, max_len, D) = lqer_attention_q_kv_workspace_bytes at
+ * T = max_len bytes, 16-byte aligned, contents irrelevant: K image [batch kv_heads][Tp][Dp], V image [batch kv_heads][128][Tv], the
+ * strides fixed by max_len.  Of sequence b's images the call writes the keys up to the end of the last 64-key tile that holds a key
+ * below lens[b] - converted codes below lens[b], zeros from there on - which is all the attention kernel reads of them; image
+ * workgroups beyond that leave at once, so a ragged batch pays for its keys and not for max_len.  Three launches on `stream` (K image,
+ * V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
  * lqer_kv_pool_gather: one sequence - row `slot` of block_table, T keys (host) - out of the pool into a dense lqer_kv_cache buffer of
  * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
- * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack), more than 8 query rows on a paged sequence
- * (lqer_attention_q_kv), an export path.
+ * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack) and an export path (more than 8 query rows
+ * on paged sequences need no copy: lqer_attention_q_paged).
  * Refused with a message, nothing launched or touched (decided from host arguments only):
  *   LQER_E_UNSUPPORTED  what lqer_attention_q_decode_kv / lqer_kv_cache_append refuse so (S > 8, formats, D, batch or kv_heads > 65535);
- *                       max_len > 2^30 (every call);
+ *                       max_len > 2^30 (every call); lqer_attention_q_paged: what lqer_attention_q_kv refuses so instead (formats, D, S
+ *                       or max_len beyond the launch grid, batch, heads or batch x kv_heads > 65535) - S > 8 is not among them;
  *   LQER_E_INVALID      null block_table / seq_slots / lens or any other null pointer; pages, slots or table_stride < 1; max_len < 1
  *                       or > 16 table_stride; n < 1 or n > max_len; a pool shorter than lqer_kv_pool_bytes or not 16-byte aligned;
  *                       a short or misaligned workspace; gather: slot outside [0, slots), T > capacity, a short or misaligned cache. */
@@ -705,6 +720,12 @@ int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_b
                                   const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                                   const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
                                   size_t workspace_bytes, void* stream);
+size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
+int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                           int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                           int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
+                           const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                           const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's

@@ -1519,6 +1519,26 @@ int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_b
   return attn_run("attention_q_decode_paged", ATTN_DECODE_PAGED, c);
 }
 
+size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
+  return lqer_attention_q_kv_workspace_bytes(batch, heads, kv_heads, S, max_len, D);
+}
+
+int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                           int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                           int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
+                           const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                           const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
+  AttnCall c = {};
+  c.q = q, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
+  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = max_len, c.D = D;  // (T: the bound - the check's, the workspace's)
+  c.qs = q_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
+  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  c.packed = c.paged = true;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  return attn_run("attention_q_paged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
+}
+
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {
   if (!src || !dst || rows < 0 || row_bytes < 0 || copies < 1) {
     set_error("replicate_rows: bad argument");

@@ -35,7 +35,6 @@ namespace attn {
 
 constexpr int DEC_MAX_S = 8;     // query rows per head
 constexpr int DEC_CMAX = 128;    // keys per chunk at most
-constexpr int SRC_RAW = 0, SRC_PACKED = 1, SRC_PAGED = 2;  // where K and V come from
 constexpr int DEC_LS = 256 + 16; // bytes of an LDS row of 128 bf16 (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
 
 // keys per chunk: 16 ceil(T / 256) clamped to [16, 128] - T / 16 chunks up to T = 256, then 16, from T = 2048 on chunks of 128.

@@ -22,6 +22,8 @@
 //                                   and never touches LDS.  O^T leaves a lane with its query's d values, 4 consecutive per store.
 //                                   Key tiles of 64 go through LDS (rows padded against bank conflicts), the next tile's loads are
 //                                   requested before the current tile's MFMAs (register staging; one buffer, two barriers per tile).
+//                                   A second instantiation (PSL) reads each sequence's number of keys from the device: one call over
+//                                   the sequences of a paged pool (lqer_attention_q_paged).
 #include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16: shared with attn_decode.hip
 
 namespace lqer {
@@ -44,6 +46,7 @@ struct Args {
   float scaling;
   QP q0, q1;  // Q_x0 (queries), Q_x1 (probabilities)
   bool qvec, mvec;
+  const int32_t* lens;  // PSL: [batch] keys of the b-th sequence (device); T above is then the bound max_len the images' strides come from
 };
 
 template <int DT>
@@ -62,7 +65,9 @@ __global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v,
                                 (int64_t)blockIdx.x * 64);
 }
 
-template <int DT, int DK>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
+// PSL (per-sequence lengths, the paged pool): a workgroup takes T = lens[b] - and with it the causal offset and every key bound below -
+// from the device; Tp and Tv stay those of the bound.  A sequence of no keys gets zeros and no statistics.
+template <int DT, int DK, bool PSL = false>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
 __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   constexpr int KS = 64 * DK + 16;  // bytes of a key row in LDS (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
   constexpr int VS = 128 + 8;       // bytes of a V^T row (64 keys) in LDS (+8: the 8-byte reads of 32 rows hit 32 bank pairs)
@@ -73,7 +78,18 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   const int64_t qt = a.mode == 2 ? nq - 1 - (int64_t)blockIdx.x : (int64_t)blockIdx.x;  // causal: the long tiles first
   const int64_t h = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + h / (a.heads / a.kv_heads);
   const int64_t q0 = qt * BQ, qi = q0 + wave * 32 + l31;
-  const int64_t off = a.T - a.S;  // causal: key j is visible to query i iff j <= i + off
+  int64_t T = a.T;
+  if constexpr (PSL) {
+    T = a.lens[b];
+    if (T == 0) {  // (uniform over the workgroup, before any barrier)
+      if (qi < a.S) {
+        const float o4[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int d = 4 * lh; d < (int)a.D; d += 8) store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + qi * a.o_rs + d, d, (int)a.D, o4);
+      }
+      return;
+    }
+  }
+  const int64_t off = T - a.S;  // causal: key j is visible to query i iff j <= i + off
   const float NEG_INF = -__builtin_inff();
 
   // ---- this lane's query row, quantized: fragment ks holds d = 16 ks + 8 lh .. + 7
@@ -92,18 +108,18 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
 
   // ---- key tiles this workgroup / wave / lane looks at
   const int64_t q_last = (q0 + BQ < a.S ? q0 + BQ : a.S) - 1;
-  int64_t t_end = a.T;  // keys [0, t_end) are visible to some query of the workgroup
+  int64_t t_end = T;  // keys [0, t_end) are visible to some query of the workgroup
   if (a.mode == 2) {
     const int64_t e = q_last + off + 1;
-    t_end = e < 0 ? 0 : (e < a.T ? e : a.T);
+    t_end = e < 0 ? 0 : (e < T ? e : T);
   }
   const int nt = (int)((t_end + BT - 1) / BT);
-  int64_t w_end = a.T;  // ... of this wave
+  int64_t w_end = T;  // ... of this wave
   if (a.mode == 2) {
     const int64_t e = q0 + wave * 32 + 31 + off + 1;
-    w_end = e < 0 ? 0 : (e < a.T ? e : a.T);
+    w_end = e < 0 ? 0 : (e < T ? e : T);
   }
-  int64_t tmax = a.T - 1;  // the last key visible to this lane's query
+  int64_t tmax = T - 1;  // the last key visible to this lane's query
   if (a.mode == 2) tmax = qi + off < tmax ? qi + off : tmax;
   const int64_t qic = qi < a.S ? qi : a.S - 1;
   const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + qic * a.m_rs : 0;
@@ -156,7 +172,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
       for (int g = 0; g < 4; ++g) {
         const int64_t t = tb + 8 * g + 4 * lh;
         if (a.mvec) {  // (T a multiple of 4: a group of four lies inside the row or behind it - read from a clamped address, unused then)
-          const int64_t tc = t < a.T ? t : a.T - 4;
+          const int64_t tc = t < T ? t : T - 4;
           if constexpr (DT == LQER_F32) {
             const float4 m4 = *(const float4*)((const float*)a.mask + moff + tc);
             mk[4 * g] = m4.x, mk[4 * g + 1] = m4.y, mk[4 * g + 2] = m4.z, mk[4 * g + 3] = m4.w;
@@ -176,7 +192,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
           }
         } else {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) mk[4 * g + j] = t + j < a.T ? load_elem<DT>(a.mask, moff + t + j) : 0.f;
+          for (int j = 0; j < 4; ++j) mk[4 * g + j] = t + j < T ? load_elem<DT>(a.mask, moff + t + j) : 0.f;
         }
       }
     }
@@ -309,13 +325,18 @@ static int launch(const AttnCall& c, Args a) {
   a.mvec = a.mode == 1 && a.T % 4 == 0 && (uintptr_t)a.mask % (4 * esz) == 0 && a.m_bs % 4 == 0 && a.m_hs % 4 == 0 && a.m_rs % 4 == 0;
   const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)c.batch);
   const int dk = (int)((a.D + 31) / 32);
-  switch (dk) {
-    case 1: k_attn_q<DT, 1><<<grid, 64 * NW, 0, c.st>>>(a); break;
-    case 2: k_attn_q<DT, 2><<<grid, 64 * NW, 0, c.st>>>(a); break;
-    case 3: k_attn_q<DT, 3><<<grid, 64 * NW, 0, c.st>>>(a); break;
-    default: k_attn_q<DT, 4><<<grid, 64 * NW, 0, c.st>>>(a); break;
-  }
-  return check_launch(c.packed ? "lqer_attention_q_kv" : "lqer_attention_q");
+  const auto go = [&](auto psl) {
+    constexpr bool PSL = decltype(psl)::value;
+    switch (dk) {
+      case 1: k_attn_q<DT, 1, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 2: k_attn_q<DT, 2, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 3: k_attn_q<DT, 3, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      default: k_attn_q<DT, 4, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
+    }
+  };
+  if (c.paged) go(std::true_type{});
+  else go(std::false_type{});
+  return check_launch(c.paged ? "lqer_attention_q_paged" : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));
 }
 
 }  // namespace attn
@@ -331,8 +352,8 @@ size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, i
   return attn_align((size_t)(batch * kv_heads * Tp * Dp) * sizeof(bf16_t)) + attn_align((size_t)(batch * kv_heads * attn::VD * Tv) * sizeof(bf16_t));
 }
 
-// the two images at their places in the workspace - from the raw K and V (attn::launch) or from the packed KV cache's codes
-// (kv_cache.hip) - then k_attn_q on them
+// the two images at their places in the workspace - from the raw K and V (attn::launch) or from the codes of the packed KV cache or
+// of the paged pool (kv_cache.hip) - then k_attn_q on them
 int attention_q_dispatch(const AttnCall& c) {
   attn::Args a;
   a.q = c.q, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
@@ -347,6 +368,7 @@ int attention_q_dispatch(const AttnCall& c) {
   a.scaling = c.scaling;
   a.q0 = make_qp(*c.q_fmt), a.q1 = make_qp(*c.p_fmt);
   a.qvec = a.mvec = false;  // (attn::launch sets them)
+  a.lens = c.paged ? c.pool.lens : nullptr;  // (paged: c.T is the bound max_len - the images' strides; the kernels take T from lens[b])
   if (c.packed) kv_cache_images_dispatch(c, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv);
   return with_dtype(c.dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(c, a); });
 }

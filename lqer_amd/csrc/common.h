@@ -791,7 +791,8 @@ size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t 
 // its words.  The dispatch functions read `packed` alone; past the checks it implies cache != nullptr.  The stride triples are the
 // caller's pointers: the check must see a null one.  `paged` (with `packed`, which it implies: no k, v, ks, vs): the codes live in
 // the paged pool `pool` instead of `cache`, T is the pool's max_len - the bound that sizes the grid and the workspace - and the kernels
-// read every sequence's own length from the device.
+// (the decode kernels, or the image kernels and k_attn_q's per-sequence-length instantiation) read every sequence's own length from
+// the device.
 struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayout); the three metadata arrays are DEVICE pointers
   const void* pool;
   size_t pool_bytes;
@@ -823,7 +824,7 @@ __host__ inline bool al16(const void* p, const int64_t* s, int esz) {
   return ((uintptr_t)p % 16 == 0) && (s[0] * esz) % 16 == 0 && (s[1] * esz) % 16 == 0 && (s[2] * esz) % 16 == 0;
 }
 size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, int64_t D);  // attn_q.hip
-int attention_q_dispatch(const AttnCall& c);  // (with a cache: kv_cache.hip writes the two images from the codes, k_attn_q runs on them)
+int attention_q_dispatch(const AttnCall& c);  // (with a cache or a pool: kv_cache.hip writes the two images from the codes, k_attn_q runs on them)
 // attn_decode.hip: the same attention for 1 <= S <= attention_q_decode_max_s() query rows, split over the keys
 int attention_q_decode_max_s();
 size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D);
@@ -839,7 +840,8 @@ int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_ne
                             const QP& qk, const QP& qv, hipStream_t st);
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st);
 constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128
-// the two images of lqer_attention_q's workspace from the first T keys of c's cache; the caller (attn_q.hip) checks the launches
+// the two images of lqer_attention_q's workspace from the first T keys of c's cache, or from the first lens[b] keys of every sequence
+// of c's pool (strides of T = max_len); the caller (attn_q.hip) checks the launches
 void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv);
 int qmatmul_dispatch(const void* x, const void* y, void* out, int dtype, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs,
                      int64_t x_rs, int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, void* workspace, hipStream_t st);

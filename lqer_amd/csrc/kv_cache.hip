@@ -12,6 +12,8 @@
 //   k_kv_kimage / k_kv_vimage   the cache -> the two bf16 images k_attn_q reads (attn_q.hip; what k_attn_kimage / k_attn_vimage write from
 //                the raw K and V): codes16_to_bf16 on 16 codes per 16-byte load, zeros wherever the raw image kernels write their
 //                padding - every key at or beyond T, every d at or beyond D.  Nothing of the cache at or beyond key T reaches an image.
+//                Templated on the source as attn_decode.hip's kernels: the dense cache, or the paged pool - a block of 16 keys found
+//                through the page table, T = lens[b] per sequence of the call (lqer_attention_q_paged).
 #include "kv_pack.h"
 
 namespace lqer {
@@ -225,18 +227,53 @@ struct IArgs {
   int64_t cap, D, T, Tp, Dp, Tv;
   QP qk, qv;
 };
+// the paged source (SRC_PAGED): the sections are the pool's, z runs over (sequence of the call, kv head), T, Tp and Tv come from the
+// bound max_len and a workgroup takes its sequence's own T from lens (device) - cap and T above are unused
+struct PIArgs : IArgs {
+  const int32_t *tbl, *slots, *lens;  // [slots][tstride] pages, [batch] slot and length of the b-th sequence
+  int64_t kvh, tstride;
+};
+template <int SRC>
+using ImgArgs = std::conditional_t<SRC == attn::SRC_PAGED, PIArgs, IArgs>;
+
+// the paged source's sizes for image z = b kv_heads + g: the sequence's length, its row of the page table and its kv head
+__device__ __forceinline__ int64_t paged_seq(const PIArgs& a, int64_t z, const int32_t*& row, int64_t& g) {
+  const int64_t b = z / a.kvh;
+  g = z % a.kvh;
+  row = a.tbl + (int64_t)a.slots[b] * a.tstride;
+  return a.lens[b];
+}
 
 // K image: the codes' own layout, no transpose.  A thread: 16 d of one key - 16 code bytes, the 16 exponent bytes of (block of keys, d),
 // 32 bytes of the image row; consecutive threads, consecutive pieces of the row.  grid.x covers Tp (Dp / 16) exactly (a multiple of 512).
-__global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
+// SRC_PAGED: the block of 16 keys is found through the sequence's row of the page table - one entry per thread, the two loads one round
+// trip behind it - and keys at and beyond lens[b] are zeros up to the end of the 64-key tile k_attn_q reads last; a workgroup (32 or 64
+// keys) that starts beyond that tile writes nothing and leaves at once: a short sequence of a ragged batch costs its own keys.
+template <int SRC>
+__global__ __launch_bounds__(256) void k_kv_kimage(const ImgArgs<SRC> a) {
   const int64_t z = blockIdx.y, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int dq = (int)(a.Dp / 16);
   const int64_t t = i / dq;
   const int d0 = 16 * (int)(i % dq);
+  int64_t T = a.T;
+  const int32_t* prow = nullptr;
+  int64_t g = 0;
+  if constexpr (SRC == attn::SRC_PAGED) {
+    T = paged_seq(a, z, prow, g);
+    if ((int64_t)blockIdx.x * (256 / dq) >= (T + 63) / 64 * 64) return;  // (uniform over the workgroup; the kernel has no barrier)
+  }
+  (void)prow, (void)g;
   uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (t < a.T && d0 < a.D) {
-    const uint4 c = *(const uint4*)(a.kc + (z * a.cap + t) * a.D + d0);
-    const uint4 e = *(const uint4*)(a.ke + (z * (a.cap / 16) + t / 16) * a.D + d0);
+  if (t < T && d0 < a.D) {
+    uint4 c, e;
+    if constexpr (SRC == attn::SRC_PAGED) {
+      const int64_t blk = (int64_t)prow[t / 16] * a.kvh + g;
+      c = *(const uint4*)(a.kc + (blk * 16 + t % 16) * a.D + d0);
+      e = *(const uint4*)(a.ke + blk * a.D + d0);
+    } else {
+      c = *(const uint4*)(a.kc + (z * a.cap + t) * a.D + d0);
+      e = *(const uint4*)(a.ke + (z * (a.cap / 16) + t / 16) * a.D + d0);
+    }
     const uint32_t eb[4] = {e.x, e.y, e.z, e.w};
     codes16_to_bf16(c, eb, a.qk, w);
   }
@@ -256,11 +293,22 @@ __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
 // The rotation is even, so a 16-byte pair of groups stays a pair: the reads - per group of 16 lanes two even and two odd rows (256-byte
 // bank row: the odd rows are the upper half), chunks 0-3 of one row and 4-7 of the other, all rotated by the same d >> 4 - stay
 // conflict-free.
-__global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
+// SRC_PAGED: T = lens[b]; the four keys of a thread lie in one page - one table entry, the five loads one round trip behind it; a
+// workgroup whose 64 keys start at or beyond T (a tile k_attn_q does not read for this sequence) leaves before the barrier.
+template <int SRC>
+__global__ __launch_bounds__(128) void k_kv_vimage(const ImgArgs<SRC> a) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[ATTN_V_ROWS * 128];
   static_assert(ATTN_V_ROWS == 128, "the thread maps below cover 8 blocks of 16 d");
   const int tid = threadIdx.x;
   const int64_t z = blockIdx.y, t0 = (int64_t)blockIdx.x * 64;
+  int64_t T = a.T;
+  const int32_t* prow = nullptr;
+  int64_t g = 0;
+  if constexpr (SRC == attn::SRC_PAGED) {
+    T = paged_seq(a, z, prow, g);
+    if (t0 >= T) return;  // (uniform over the workgroup)
+  }
+  (void)prow, (void)g;
   {
     const int db = tid & 7, tg = tid >> 3;
     const int64_t t = t0 + 4 * tg;
@@ -269,12 +317,18 @@ __global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int j = 0; j < 8; ++j) w[r][j] = 0;
-    if (16 * db < a.D && t < a.T) {  // (t < T <= cap, t a multiple of 4: the dword of exponents lies inside the section)
-      const uint32_t e4 = *(const uint32_t*)(a.ve + ((z * (a.cap / 16) + t / 16) * (a.D / 16) + db) * 16 + t % 16);
+    if (16 * db < a.D && t < T) {  // (t < T <= cap, t a multiple of 4: the dword of exponents lies inside the section)
+      int64_t blk = 0;  // the block of 16 keys
+      if constexpr (SRC == attn::SRC_PAGED) blk = (int64_t)prow[t / 16] * a.kvh + g;
+      else blk = z * (a.cap / 16) + t / 16;
+      const uint32_t e4 = *(const uint32_t*)(a.ve + (blk * (a.D / 16) + db) * 16 + t % 16);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (t + r < a.T) {
-          const uint4 c = *(const uint4*)(a.vc + (z * a.cap + t + r) * a.D + 16 * db);
+        if (t + r < T) {
+          const unsigned char* cp;
+          if constexpr (SRC == attn::SRC_PAGED) cp = a.vc + (blk * 16 + t % 16 + r) * a.D + 16 * db;
+          else cp = a.vc + (z * a.cap + t + r) * a.D + 16 * db;
+          const uint4 c = *(const uint4*)cp;
           const uint32_t e = ((e4 >> (8 * r)) & 0xffu) * 0x01010101u;  // one exponent for the 16 d
           const uint32_t eb[4] = {e, e, e, e};
           codes16_to_bf16(c, eb, a.qv, w[r]);
@@ -384,16 +438,26 @@ int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_
   return check_launch("lqer_kv_cache_unpack");
 }
 
-// the two images of lqer_attention_q's workspace from the cache's first T keys; the caller (attn_q.hip) checks the launches
+// the two images of lqer_attention_q's workspace from the cache's first T keys - or, from the paged pool, from every sequence's first
+// lens[b] keys, the images' strides those of T = max_len; the caller (attn_q.hip) checks the launches
 void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64_t Dp, bf16_t* vimg, int64_t Tv) {
-  const auto s = kvc::sections((const unsigned char*)c.cache, kvc::layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
-  kvc::IArgs a;
-  a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve;
-  a.kimg = kimg, a.vimg = vimg, a.cap = s.cap, a.D = c.D, a.T = c.T, a.Tp = Tp, a.Dp = Dp, a.Tv = Tv;
+  kvc::PIArgs a;
+  a.kimg = kimg, a.vimg = vimg, a.D = c.D, a.T = c.T, a.Tp = Tp, a.Dp = Dp, a.Tv = Tv;
   a.qk = make_qp(*c.k_fmt), a.qv = make_qp(*c.v_fmt);
-  const unsigned nz = (unsigned)(c.batch * c.kv_heads);
-  kvc::k_kv_kimage<<<dim3((unsigned)(Tp * (Dp / 16) / 256), nz), 256, 0, c.st>>>(a);
-  kvc::k_kv_vimage<<<dim3((unsigned)(Tv / 64), nz), 128, 0, c.st>>>(a);
+  const dim3 kgrid((unsigned)(Tp * (Dp / 16) / 256), (unsigned)(c.batch * c.kv_heads)), vgrid((unsigned)(Tv / 64), (unsigned)(c.batch * c.kv_heads));
+  if (c.paged) {
+    const kvc::PoolLayout l = kvc::pool_layout(c.dtype, c.pool.pages, c.pool.slots, c.kv_heads, c.D);
+    const unsigned char* base = (const unsigned char*)c.pool.pool;
+    a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.cap = 0;
+    a.tbl = c.pool.block_table, a.slots = c.pool.seq_slots, a.lens = c.pool.lens, a.kvh = c.kv_heads, a.tstride = c.pool.table_stride;
+    kvc::k_kv_kimage<attn::SRC_PAGED><<<kgrid, 256, 0, c.st>>>(a);
+    kvc::k_kv_vimage<attn::SRC_PAGED><<<vgrid, 128, 0, c.st>>>(a);
+    return;
+  }
+  const auto s = kvc::sections((const unsigned char*)c.cache, kvc::layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
+  a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve, a.cap = s.cap;
+  kvc::k_kv_kimage<attn::SRC_PACKED><<<kgrid, 256, 0, c.st>>>((const kvc::IArgs&)a);
+  kvc::k_kv_vimage<attn::SRC_PACKED><<<vgrid, 128, 0, c.st>>>((const kvc::IArgs&)a);
 }
 
 }  // namespace lqer

@@ -159,6 +159,8 @@ __device__ __forceinline__ void codes16_to_bf16(const uint4& c, const uint32_t (
 
 namespace attn {
 
+constexpr int SRC_RAW = 0, SRC_PACKED = 1, SRC_PAGED = 2;  // where K and V come from (attn_decode.hip; kv_cache.hip's image kernels: the last two)
+
 // four consecutive elements; one 8- / 16-byte load when the row is aligned
 template <int DT>
 __device__ __forceinline__ void load4(const void* base, int64_t off, bool vec, float (&v)[4]) {

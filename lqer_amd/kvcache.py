@@ -1,5 +1,6 @@
 """A packed MXINT KV cache for the fused quantized attention (include/lqer_hip.h "packed KV cache"; csrc/kv_cache.hip writes it,
-csrc/attn_decode.hip reads it; for more than 8 query rows csrc/kv_cache.hip turns it into the prefill kernel's two images).
+csrc/attn_decode.hip reads it; for more than 8 query rows csrc/kv_cache.hip turns it - the dense cache or the paged pool - into the
+prefill kernel's two images).
 
 The decode kernel quantizes the whole K (blocks of 16 along t) and V (blocks of 16 along d) in every step, with the results of
 the step before.  The cache keeps the quantizer's output instead of the raw tensors - a one-byte code per element, a one-byte
@@ -14,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from .functional import (KERNEL_PREFILL, _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _ATTN_MAX_T, _MAX_GRID_Z, _attention_call, _attention_outputs,
+from .functional import (KERNEL_DECODE, KERNEL_PREFILL, _ATTN_DECODE_MAX_S, _ATTN_MAX_D, _ATTN_MAX_T, _MAX_GRID_Z, _attention_call, _attention_outputs,
                          _attn_fmts, _check_kernel_arg, _check_layout_and_mask, _mask_ok, _tri)
 
 
@@ -307,8 +308,9 @@ class PagedKVCache:
                        repeated seq raise with the pool untouched and no page taken - and so does a refusal of the library itself:
                        the reservation is rolled back
     .length(seq);  .pages_free;  .nbytes
-    .to_dense(seq) -> QuantizedKVCache (batch 1) with the sequence's bytes - for more than 8 query rows (attention_flexible_cached
-                       with kernel="prefill") or an export;  .dequantized(seq) -> (K, V) [1, kv_heads, length, head_dim] fp32, for tests"""
+    .to_dense(seq) -> QuantizedKVCache (batch 1) with the sequence's bytes - an export, and the test hook (more than 8 query rows
+                       need no copy: attention_flexible_paged(kernel="prefill"));  .dequantized(seq) -> (K, V) [1, kv_heads, length,
+                       head_dim] fp32, for tests"""
 
     covers = staticmethod(QuantizedKVCache.covers)
 
@@ -347,12 +349,13 @@ class PagedKVCache:
     def _pool_args(self):
         return (self.buf.data_ptr(), self.buf.numel(), self.pt.num_pages, self.pt.max_seqs, self.table.data_ptr(), self.pt.max_pages_per_seq)
 
-    def _call_meta(self, slots, lens):
-        """seq_slots and lens of one call on the device: ordinary copies on the current stream, ordered before the launches."""
+    def _call_meta(self, slots, lens, max_len=None):
+        """seq_slots and lens of one call on the device: ordinary copies on the current stream, ordered before the launches.
+        max_len: the bound handed to the library - the table's room, or a tighter one that still covers `lens`."""
         n = len(slots)
         self._slots[:n].copy_(torch.tensor(slots, dtype=torch.int32))
         self._lens[:n].copy_(torch.tensor(lens, dtype=torch.int32))
-        return self._slots.data_ptr(), self._lens.data_ptr(), self.pt.max_len
+        return self._slots.data_ptr(), self._lens.data_ptr(), self.pt.max_len if max_len is None else max_len
 
     @torch.no_grad()
     def append(self, seqs, k: torch.Tensor, v: torch.Tensor) -> None:
@@ -407,23 +410,38 @@ class PagedKVCache:
         return self.to_dense(seq).dequantized()
 
 
+KERNEL_AUTO = "auto"
+
+
 @torch.no_grad()
-def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False, out_layout="bhsd", return_stats=False, ws=None):
-    """attention_flexible(q[b:b+1], K_b, V_b, cache.cfg0, cache.cfg1, scaling, causal=causal, kernel="decode") for every sequence
-    seqs[b] of a PagedKVCache, bit for bit, in ONE call over sequences of different lengths (lqer_attention_q_decode_paged).
-    q [len(seqs), h, s, d] with s <= 8; `causal`: key j of sequence b visible to query i iff j <= i + (length_b - s).  There is no mask
-    tensor - the per-sequence lengths are what a padding mask stood for - and no other route: an empty sequence, causal with
-    s > a length, s > 8, a wrong dtype, device or head count raise ValueError.  `out_layout` and `return_stats` as attention_flexible;
-    ws: a uint8 workspace or None (the stream's)."""
+def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False, out_layout="bhsd", return_stats=False, ws=None,
+                             kernel=KERNEL_DECODE):
+    """attention_flexible(q[b:b+1], K_b, V_b, cache.cfg0, cache.cfg1, scaling, causal=causal, kernel=kernel) for every sequence
+    seqs[b] of a PagedKVCache, bit for bit, in ONE call over sequences of different lengths.
+    q [len(seqs), h, s, d]; `causal`: key j of sequence b visible to query i iff j <= i + (length_b - s).
+    kernel="decode" (the default): s <= 8, lqer_attention_q_decode_paged reads the pool's codes.  kernel="prefill": any s >= 1 - a prompt,
+    a second turn, a chunk of a long prompt on sequences that already hold keys - through lqer_attention_q_paged: the prefill kernel's
+    two images are written from the pool through the block table (no dense copy) and the kernel takes every sequence's own length;
+    the library's bound max_len is then the longest addressed length rounded up to 128 (capped at the table's room), so the image
+    workspace follows the batch at hand.  kernel="auto": decode for s <= 8, prefill beyond.
+    There is no mask tensor - the per-sequence lengths are what a padding mask stood for - and no other route: an empty sequence,
+    causal with s > a length, s > 8 with kernel="decode", an unknown `kernel`, a wrong dtype, device or head count raise ValueError.
+    `out_layout` and `return_stats` as attention_flexible; ws: a uint8 workspace or None (the stream's)."""
+    if kernel not in (KERNEL_DECODE, KERNEL_PREFILL, KERNEL_AUTO):
+        raise ValueError(f"attention_flexible_paged: kernel={kernel!r} - 'decode', 'prefill' or 'auto'")
     _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
     seqs = list(seqs)
     if q.dim() != 4:
         raise ValueError(f"attention_flexible_paged: q {tuple(q.shape)} is not [len(seqs), h, s, d]")
     b, h, s, d = q.shape
-    if s > _ATTN_DECODE_MAX_S:
-        raise ValueError(f"attention_flexible_paged: {s} query rows per head - the kernel over the paged cache takes up to {_ATTN_DECODE_MAX_S} "
-                         "(more: attention_flexible_cached(q, cache.to_dense(seq), ..., kernel='prefill'))")
-    if q.dtype != cache.dtype or q.device != cache.buf.device or b != len(seqs) or b < 1 or d != cache.head_dim or h % cache.kv_heads or s < 1 or h > _MAX_GRID_Z:
+    if kernel == KERNEL_AUTO:
+        kernel = KERNEL_DECODE if s <= _ATTN_DECODE_MAX_S else KERNEL_PREFILL
+    prefill = kernel == KERNEL_PREFILL
+    if not prefill and s > _ATTN_DECODE_MAX_S:
+        raise ValueError(f"attention_flexible_paged: {s} query rows per head - the decode kernel over the paged cache takes up to "
+                         f"{_ATTN_DECODE_MAX_S} (more: kernel='prefill')")
+    if (q.dtype != cache.dtype or q.device != cache.buf.device or b != len(seqs) or b < 1 or d != cache.head_dim or h % cache.kv_heads or s < 1
+            or h > _MAX_GRID_Z or (prefill and b * cache.kv_heads > _MAX_GRID_Z)):
         raise ValueError(f"attention_flexible_paged: q {tuple(q.shape)} {q.dtype} on {q.device} for {len(seqs)} sequences of a cache "
                          f"[{cache.kv_heads}, {cache.head_dim}] {cache.dtype} on {cache.buf.device}")
     try:
@@ -431,19 +449,22 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     except KeyError as e:
         raise ValueError(e.args[0]) from None
     lens = [cache.pt.lengths[x] for x in slots]
-    if min(lens) < 1 or (causal and s > min(lens)):
+    if min(lens) < 1 or (causal and s > min(lens)) or (prefill and max(lens) > _ATTN_MAX_T):
         raise ValueError(f"attention_flexible_paged: lengths {lens} of sequences {seqs} - an empty sequence has nothing to attend to"
                          + (f", and causal needs {s} query rows <= every length" if causal else ""))
     if q.stride(3) != 1:
         q = q.contiguous()
     out, ob, stats = _attention_outputs(q, out_layout, return_stats)
     L, f = _lib.lib(), cache.fmts
+    # the bound that sizes grids and workspace: the table's room for the decode kernels (as ever), the batch at hand for the images
+    max_len = min((max(lens) + 127) // 128 * 128, cache.pt.max_len) if prefill else cache.pt.max_len
+    name = "lqer_attention_q_paged" if prefill else "lqer_attention_q_decode_paged"
     with torch.cuda.device(q.device):
         if ws is None:
-            ws = ops.workspace(q.device, max(L.lqer_attention_q_decode_paged_workspace_bytes(b, h, cache.kv_heads, s, cache.pt.max_len, d), 16))
-        _lib.check(L.lqer_attention_q_decode_paged(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens), ob.data_ptr(),
-                                                   stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, cache.kv_heads, s, d,
-                                                   _tri(q), _tri(ob), float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]),
-                                                   C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device)),
-                   "lqer_attention_q_decode_paged")
+            ws = ops.workspace(q.device, max(getattr(L, name + "_workspace_bytes")(b, h, cache.kv_heads, s, max_len, d), 16))
+        _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), ob.data_ptr(),
+                                    stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, cache.kv_heads, s, d,
+                                    _tri(q), _tri(ob), float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]),
+                                    C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device)),
+                   name)
     return (out, stats) if return_stats else out
