@@ -1126,19 +1126,19 @@ static int decode_grid_limits(const char* who, const AttnCall& c) {
 }
 
 static size_t prefill_workspace_bytes(const AttnCall& c) { return attention_q_workspace_bytes(c.batch, c.kv_heads, c.T, c.D); }
-static size_t decode_workspace_bytes(const AttnCall& c) { return attention_q_decode_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D); }
+// (on the paged pool c.T is the bound max_len, which sizes the workspace and the grid)
+static size_t decode_workspace_bytes(const AttnCall& c) {
+  return c.paged ? attention_q_decode_paged_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D)
+                 : attention_q_decode_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D);
+}
 
 // (only the cache's image kernels store the prefill workspace in 16-byte pieces; the decode kernels store and load theirs so from any source)
 static const AttnKernel ATTN_PREFILL = {0, "kernel takes", prefill_grid_limits, false, prefill_workspace_bytes,
                                         attention_q_dispatch};
 static const AttnKernel ATTN_DECODE = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, decode_workspace_bytes,
                                        attention_q_decode_dispatch};
-// the decode kernels on the paged pool: c.T is the bound max_len, which sizes the workspace (and the grid)
-static size_t paged_workspace_bytes(const AttnCall& c) { return attention_q_decode_paged_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D); }
-static const AttnKernel ATTN_DECODE_PAGED = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, paged_workspace_bytes,
-                                             attention_q_decode_dispatch};
 
-// the check of the four attention calls, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
+// the check of the six attention calls, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
 static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) {
   if (c.batch < 0 || c.heads <= 0 || c.kv_heads <= 0 || c.S < 0 || c.T < 0 || c.D <= 0) {
     set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)c.batch, (long long)c.heads,
@@ -1443,17 +1443,27 @@ static int attn_run(const char* who, const AttnKernel& kn, const AttnCall& c) {
   return kn.dispatch(c);
 }
 
-int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
-                     int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
-                     const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
-                     const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+// what every attention entry point fills alike; each then says where K and V come from
+static AttnCall attn_call(const void* q, const void* mask, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads,
+                          int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* mask_strides, const int64_t* out_strides,
+                          float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                          const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
   AttnCall c = {};
   c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
   c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
   c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
   c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
   c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  return c;
+}
+
+int lqer_attention_q(const void* q, const void* k, const void* v, const void* mask, void* out, float* row_stats, int dtype, int64_t batch,
+                     int64_t heads, int64_t kv_heads, int64_t S, int64_t T, int64_t D, const int64_t* q_strides, const int64_t* k_strides,
+                     const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
+                     const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  AttnCall c = attn_call(q, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   c.k = k, c.v = v, c.ks = k_strides, c.vs = v_strides;
   return attn_run("attention_q", ATTN_PREFILL, c);
 }
@@ -1463,12 +1473,8 @@ int lqer_attention_q_decode(const void* q, const void* k, const void* v, const v
                             const int64_t* v_strides, const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal,
                             const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  AttnCall c = {};
-  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
-  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
-  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
-  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
-  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  AttnCall c = attn_call(q, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   c.k = k, c.v = v, c.ks = k_strides, c.vs = v_strides;
   return attn_run("attention_q_decode", ATTN_DECODE, c);
 }
@@ -1478,12 +1484,8 @@ int lqer_attention_q_decode_kv(const void* q, const void* cache, size_t cache_by
                                const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                                const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  AttnCall c = {};
-  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
-  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
-  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
-  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
-  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  AttnCall c = attn_call(q, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   c.packed = true, c.cache = cache, c.cache_bytes = cache_bytes, c.capacity = capacity;
   return attn_run("attention_q_decode_kv", ATTN_DECODE, c);
 }
@@ -1493,12 +1495,8 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
                         const int64_t* mask_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  AttnCall c = {};
-  c.q = q, c.mask = mask, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
-  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = T, c.D = D;
-  c.qs = q_strides, c.ms = mask_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
-  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
-  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  AttnCall c = attn_call(q, mask, out, row_stats, dtype, batch, heads, kv_heads, S, T, D, q_strides, mask_strides, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   c.packed = true, c.cache = cache, c.cache_bytes = cache_bytes, c.capacity = capacity;
   return attn_run("attention_q_kv", ATTN_PREFILL, c);
 }
@@ -1508,15 +1506,12 @@ int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_b
                                   int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
                                   const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                                   const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
-  AttnCall c = {};
-  c.q = q, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
-  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = max_len, c.D = D;  // (T: the bound - the check's, the workspace's)
-  c.qs = q_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
-  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
-  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  // (no mask; T: the bound max_len - the check's, the workspace's)
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   c.packed = c.paged = true;
   c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  return attn_run("attention_q_decode_paged", ATTN_DECODE_PAGED, c);
+  return attn_run("attention_q_decode_paged", ATTN_DECODE, c);
 }
 
 size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
@@ -1528,12 +1523,9 @@ int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, i
                            int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
                            const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                            const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
-  AttnCall c = {};
-  c.q = q, c.out = out, c.row_stats = row_stats, c.dtype = dtype;
-  c.batch = batch, c.heads = heads, c.kv_heads = kv_heads, c.S = S, c.T = max_len, c.D = D;  // (T: the bound - the check's, the workspace's)
-  c.qs = q_strides, c.os = out_strides, c.scaling = scaling, c.causal = causal;
-  c.q_fmt = q_fmt, c.k_fmt = k_fmt, c.p_fmt = p_fmt, c.v_fmt = v_fmt;
-  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+  // (no mask; T: the bound max_len - the check's, the workspace's)
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   c.packed = c.paged = true;
   c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
   return attn_run("attention_q_paged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)

@@ -63,26 +63,14 @@ struct DArgs {
   float scaling;
   QP q0, qk, q1, qv;
   bool qvec, kvec, vvec;
-  const unsigned char *kc, *ke, *vc, *ve;  // the packed source: codes and exponents of K and of V (kv_pack.h), cap keys per (batch, kv head)
-  int64_t cap;
   int nchs;  // chunks the workspace has room for per row (its stride over rows): nch, or dec_max_chunks(max_len) with the paged source
-  const int32_t *tbl, *slots, *lens;  // the paged source (device): [slots][tstride] pages, [batch] slot and length of the b-th sequence
-  int64_t tstride;
+  kvc::KvSrc<const unsigned char> src;  // the packed and the paged source (kv_pack.h)
 };
 
-// the paged source's sizes of workgroup b's own sequence; false: chunk c is none of its chunks
-__device__ __forceinline__ bool paged_sizes(const DArgs& a, int64_t b, int64_t c, int64_t& T, int& C, int& nch) {
-  T = a.lens[b];
+// the paged source: chunk length and chunk count of a sequence of T = lens[b] keys
+__device__ __forceinline__ void paged_chunks(const DArgs& a, int64_t T, int& C, int& nch) {
   C = dec_chunk(T, a.D);
   nch = (int)((T + C - 1) / C);
-  return c < nch;
-}
-
-// the index of the block of keys 16 kb .. 16 kb + 15 of (batch b, kv head g) in the code and exponent sections (kv_pack.h)
-template <int SRC>
-__device__ __forceinline__ int64_t kv_block(const DArgs& a, const int32_t* row, int64_t z, int64_t g, int64_t kb) {
-  if constexpr (SRC == SRC_PAGED) return (int64_t)row[kb] * a.kv_heads + g;
-  else return z * (a.cap / 16) + kb;
 }
 
 template <int DT, int SRC>
@@ -91,14 +79,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   __shared__ float sSt[4][32][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
-  int64_t T = a.T;
+  const int32_t* prow;  // the slot's row of the page table
+  const int64_t T = kvc::seq<SRC>(a.src, b, a.T, prow);
   int C = a.C, nch = a.nch;
-  const int32_t* prow = nullptr;  // the slot's row of the page table
   if constexpr (SRC == SRC_PAGED) {
-    if (!paged_sizes(a, b, c, T, C, nch)) return;  // (uniform over the workgroup, before any barrier)
-    prow = a.tbl + (int64_t)a.slots[b] * a.tstride;
+    paged_chunks(a, T, C, nch);
+    if (c >= nch) return;  // (none of this sequence's chunks; uniform over the workgroup, before any barrier)
   }
-  (void)nch, (void)prow;
   const int64_t t0 = c * C;
   const int D = (int)a.D;
   const float NEG_INF = -__builtin_inff();
@@ -114,11 +101,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
       if (tq < T) {  // (paged: the one table entry first, the five loads one round trip behind it)
-        const int64_t blk = kv_block<SRC>(a, prow, z, g, tq / 16);
-        e4 = *(const uint4*)(a.ke + blk * D + 16 * dg);
+        const int64_t blk = kvc::block<SRC>(a.src, prow, z, g, tq / 16);
+        e4 = *(const uint4*)(a.src.ke + blk * D + 16 * dg);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (tq + j < T) c[j] = *(const uint4*)(a.kc + (blk * 16 + tq % 16 + j) * D + 16 * dg);
+          if (tq + j < T) c[j] = *(const uint4*)(a.src.kc + (blk * 16 + tq % 16 + j) * D + 16 * dg);
       }
       const uint32_t eb[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
@@ -241,14 +228,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
-  int64_t T = a.T;
+  const int32_t* prow;
+  const int64_t T = kvc::seq<SRC>(a.src, b, a.T, prow);
   int C = a.C, nch = a.nch;
-  const int32_t* prow = nullptr;
   if constexpr (SRC == SRC_PAGED) {
-    if (!paged_sizes(a, b, c, T, C, nch)) return;
-    prow = a.tbl + (int64_t)a.slots[b] * a.tstride;
+    paged_chunks(a, T, C, nch);
+    if (c >= nch) return;
   }
-  (void)prow;
   const int64_t t0 = c * C;
   const int D = (int)a.D;
   const float NEG_INF = -__builtin_inff();
@@ -264,13 +250,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       uint4 c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
-      if (tq < T) {
-        const int64_t blk = kv_block<SRC>(a, prow, z, g, tq / 16);
-        e4 = *(const uint32_t*)(a.ve + (blk * db_n + db) * 16 + tq % 16);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (tq + j < T) c[j] = *(const uint4*)(a.vc + (blk * 16 + tq % 16 + j) * D + 16 * db);
-      }
+      if (tq < T) e4 = kvc::load_v4(a.src, kvc::block<SRC>(a.src, prow, z, g, tq / 16), tq, T, D, db, c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -364,9 +344,8 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
   const int d = 4 * (int)(i % dq);
   int nch = a.nch;
   if constexpr (PAGED) {
-    int64_t T;
     int C;
-    paged_sizes(a, grow / (a.heads * a.S), 0, T, C, nch);
+    paged_chunks(a, a.src.lens[grow / (a.heads * a.S)], C, nch);
   }
   const float* p = a.part + grow * a.nchs * a.D + d;
   float o[4] = {0.f, 0.f, 0.f, 0.f};
@@ -413,7 +392,6 @@ int attention_q_decode_dispatch(const AttnCall& c) {
   a.q = c.q, a.k = c.k, a.v = c.v, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
   a.S = c.S, a.T = c.T, a.D = c.D;
   a.C = attn::dec_chunk(c.T, c.D), a.nch = a.nchs = (int)((c.T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
-  a.tbl = a.slots = a.lens = nullptr, a.tstride = 0;
   if (c.paged) a.nchs = attn::dec_max_chunks(c.T), a.Tp = (c.T + 127) / 128 * 128;  // (T = max_len; the kernels take T, C, nch from lens[b])
   a.rep = (int)(c.heads / c.kv_heads), a.R = a.rep * c.S, a.rows = c.batch * c.heads * c.S;
   unsigned char* ws = (unsigned char*)c.workspace;
@@ -430,23 +408,15 @@ int attention_q_decode_dispatch(const AttnCall& c) {
   a.scaling = c.scaling;
   a.q0 = make_qp(*c.q_fmt), a.qk = make_qp(*c.k_fmt), a.q1 = make_qp(*c.p_fmt), a.qv = make_qp(*c.v_fmt);
   a.qvec = al16(c.q, c.qs, esz);
-  if (c.paged) {  // the paged source: the pool's sections, the table, the slots and the lengths
-    const kvc::PoolLayout l = kvc::pool_layout(c.dtype, c.pool.pages, c.pool.slots, c.kv_heads, c.D);
-    const unsigned char* base = (const unsigned char*)c.pool.pool;
-    a.k = a.v = nullptr, a.k_bs = a.k_hs = a.k_rs = a.v_bs = a.v_hs = a.v_rs = 0, a.kvec = a.vvec = false;
-    a.kc = base + l.k_codes, a.ke = base + l.k_exps, a.vc = base + l.v_codes, a.ve = base + l.v_exps, a.cap = 0;
-    a.tbl = c.pool.block_table, a.slots = c.pool.seq_slots, a.lens = c.pool.lens, a.tstride = c.pool.table_stride;
-    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
+  a.k_bs = a.k_hs = a.k_rs = a.v_bs = a.v_hs = a.v_rs = 0, a.kvec = a.vvec = false, a.src = {};
+  if (c.packed) {  // the codes of a cache or a pool: no k, v (null in c) or their strides
+    a.src = kvc::src_of(c);
+  } else {
+    a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
+    a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
   }
-  if (c.packed) {  // the packed source: no k, v or their strides
-    const auto s = kvc::sections((const unsigned char*)c.cache, kvc::layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
-    a.k = a.v = nullptr, a.k_bs = a.k_hs = a.k_rs = a.v_bs = a.v_hs = a.v_rs = 0, a.kvec = a.vvec = false;
-    a.kc = s.kc, a.ke = s.ke, a.vc = s.vc, a.ve = s.ve, a.cap = s.cap;
-    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });
-  }
-  a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
-  a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
-  a.kc = a.ke = a.vc = a.ve = nullptr, a.cap = 0;
+  if (c.paged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
+  if (c.packed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });
   return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_RAW>(a, c.batch, c.st); });
 }
 

@@ -785,8 +785,8 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
 
 size_t qmatmul_workspace_bytes(int64_t batch, int64_t K, int64_t S2);  // matmul_q.hip
 size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t S2, bool x_pre, bool y_pre);
-// One attention call as the C ABI receives it: what lqer_attention_q, _decode, _decode_kv and _kv fill, their one check reads and the
-// two dispatch functions launch from.  Host only - never a kernel argument.  `packed`: K and V come from the packed KV cache of
+// One attention call as the C ABI receives it: what the six entry points fill - lqer_attention_q and lqer_attention_q_decode, each from
+// raw K and V, from the packed cache (_kv) and from the paged pool (_paged) - their one check reads and the two dispatch functions launch from.  Host only - never a kernel argument.  `packed`: K and V come from the packed KV cache of
 // `capacity` keys (kv_pack.h) and k, v, ks, vs are unused; a flag of its own because a null `cache` is the cache's check to refuse, in
 // its words.  The dispatch functions read `packed` alone; past the checks it implies cache != nullptr.  The stride triples are the
 // caller's pointers: the check must see a null one.  `paged` (with `packed`, which it implies: no k, v, ks, vs): the codes live in

@@ -12,10 +12,15 @@
 
 namespace lqer {
 
+namespace attn {
+constexpr int SRC_RAW = 0, SRC_PACKED = 1, SRC_PAGED = 2;  // where K and V come from (attn_decode.hip; kv_cache.hip's kernels: the last two)
+}
+
 namespace kvc {
 
 struct Layout {  // byte offsets of the five sections, each rounded up to 256 bytes
   int64_t cap;   // capacity rounded up to 16 keys
+  int64_t kv_heads;
   size_t k_codes, k_exps, v_codes, v_exps, k_stage, total;
 };
 
@@ -24,7 +29,7 @@ __host__ inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 // D a multiple of 16, dtype one of the three: the caller checked
 __host__ inline Layout layout(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D) {
   Layout l;
-  l.cap = (capacity + 15) / 16 * 16;
+  l.cap = (capacity + 15) / 16 * 16, l.kv_heads = kv_heads;
   const size_t Z = (size_t)(batch * kv_heads), esz = dtype == LQER_F32 ? 4 : 2;
   const size_t codes = up256(Z * l.cap * D), exps = up256(Z * (l.cap / 16) * D);
   l.k_codes = 0;
@@ -34,16 +39,6 @@ __host__ inline Layout layout(int dtype, int64_t batch, int64_t kv_heads, int64_
   l.k_stage = l.v_exps + exps;
   l.total = l.k_stage + up256(Z * 16 * D * esz);
   return l;
-}
-
-template <class B>  // unsigned char for the writer (append), const unsigned char for the readers
-struct Sections {    // the four sections a kernel reads or writes, and the keys each (batch, kv head) has room for
-  B *kc, *ke, *vc, *ve;
-  int64_t cap;
-};
-template <class B>
-__host__ inline Sections<B> sections(B* base, const Layout& l) {
-  return {base + l.k_codes, base + l.k_exps, base + l.v_codes, base + l.v_exps, l.cap};
 }
 
 // The paged pool (include/lqer_hip.h "paged KV pool"): the same five sections, but an ITEM - one (page, kv head), i.e. one block of 16
@@ -66,6 +61,64 @@ __host__ inline PoolLayout pool_layout(int dtype, int64_t pages, int64_t slots, 
   l.k_stage = l.v_exps + exps;
   l.total = l.k_stage + up256((size_t)(slots * kv_heads) * 16 * D * esz);
   return l;
+}
+
+// Where a kernel finds the codes: the sections of a dense cache or of the pool, and what turns (sequence, kv head, block of 16 keys)
+// into a block index.  A host struct and a member of every kernel's argument record; the kernel's template parameter SRC says which
+// of the two it describes.
+template <class B>  // unsigned char for the writer (append), const unsigned char for the readers
+struct KvSrc {
+  B *kc, *ke, *vc, *ve;
+  int64_t cap16;                      // SRC_PACKED: blocks of 16 keys per (batch, kv head)
+  int kvh;                            // kv heads
+  const int32_t *tbl, *slots, *lens;  // SRC_PAGED (device): [slots][tstride] pages, [batch] slot and length of the call's b-th sequence
+  int64_t tstride;
+  B* stage;                           // the staging rows (append and gather only)
+};
+
+template <class B>
+__host__ inline KvSrc<B> src_of(B* cache, const Layout& l) {
+  return {cache + l.k_codes, cache + l.k_exps, cache + l.v_codes, cache + l.v_exps, l.cap / 16, (int)l.kv_heads, nullptr, nullptr, nullptr, 0, cache + l.k_stage};
+}
+template <class B = const unsigned char>  // (the one place that turns a pool into section pointers)
+__host__ inline KvSrc<B> src_of(const KvPool& p) {
+  const PoolLayout l = pool_layout(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  B* base = (B*)p.pool;
+  return {base + l.k_codes, base + l.k_exps, base + l.v_codes, base + l.v_exps, 0, (int)p.kv_heads, p.block_table, p.seq_slots, p.lens, p.table_stride, base + l.k_stage};
+}
+__host__ inline KvSrc<const unsigned char> src_of(const AttnCall& c) {  // (c.packed)
+  return c.paged ? src_of(c.pool) : src_of((const unsigned char*)c.cache, layout(c.dtype, c.batch, c.kv_heads, c.capacity, c.D));
+}
+
+// the length of the call's b-th sequence and its row of the page table: lens[b] and the slot's row, or the host's T and no row
+template <int SRC, class B>
+__device__ __forceinline__ int64_t seq(const KvSrc<B>& s, int64_t b, int64_t T, const int32_t*& row) {
+  row = nullptr;
+  if constexpr (SRC == attn::SRC_PAGED) {
+    row = s.tbl + (int64_t)s.slots[b] * s.tstride;
+    return s.lens[b];
+  }
+  return T;
+}
+
+// the index of the block of keys 16 kb .. 16 kb + 15 of (sequence b, kv head g), z = b kvh + g, in the code and exponent sections:
+// the pool's item of (page row[kb], kv head g), or the dense cache's
+__device__ __forceinline__ int64_t page_block(const int32_t* row, int64_t kvh, int64_t g, int64_t kb) { return (int64_t)row[kb] * kvh + g; }
+template <int SRC, class B>
+__device__ __forceinline__ int64_t block(const KvSrc<B>& s, const int32_t* row, int64_t z, int64_t g, int64_t kb) {
+  if constexpr (SRC == attn::SRC_PAGED) return page_block(row, s.kvh, g, kb);
+  else return z * s.cap16 + kb;
+}
+
+// 16 d (block db of D / 16) of the V rows of keys t .. t + 3 of block blk, t a multiple of 4: the dword of their four exponents
+// (returned) and the four 16-byte code rows; a key at or beyond T is not read and leaves c[r] as it was
+template <class B>
+__device__ __forceinline__ uint32_t load_v4(const KvSrc<B>& s, int64_t blk, int64_t t, int64_t T, int D, int db, uint4 (&c)[4]) {
+  const uint32_t e4 = *(const uint32_t*)(s.ve + (blk * (D / 16) + db) * 16 + t % 16);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (t + r < T) c[r] = *(const uint4*)(s.vc + (blk * 16 + t % 16 + r) * D + 16 * db);
+  return e4;
 }
 
 // one block of 16 -> 16 codes (four dwords, element i in byte i) and the exponent byte: quant16_bf16's decisions and arithmetic,
@@ -158,8 +211,6 @@ __device__ __forceinline__ void codes16_to_bf16(const uint4& c, const uint32_t (
 }  // namespace kvc
 
 namespace attn {
-
-constexpr int SRC_RAW = 0, SRC_PACKED = 1, SRC_PAGED = 2;  // where K and V come from (attn_decode.hip; kv_cache.hip's image kernels: the last two)
 
 // four consecutive elements; one 8- / 16-byte load when the row is aligned
 template <int DT>

@@ -126,6 +126,53 @@ def test_append_patterns_and_capacities_give_one_cache(dtype, t):
     assert torch.equal(cache.dequantized()[0], _cache(k[:, :, :9], v[:, :, :9]).dequantized()[0])  # (a reset cache starts over)
 
 
+# ---- 2b. the bytes an append leaves behind ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32], ids=["f16", "f32"])
+def test_append_steps_leave_the_bytes_of_one_append(dtype):
+    """One cache of capacity 80 through appends of 5, 11, 1, 40, 7 and 3 keys - inside the open block, up to its end, from a boundary,
+    across three further blocks from a non-empty open block, across one, from a boundary again.  After every step (a) the bytes of every
+    section's blocks below ceil(length / 16) are those of a cache that got the same keys in ONE append (both buffers start from the same
+    bytes, so what neither writes - V rows at and beyond the length - compares too), and (b) staging row t % 16 holds the raw bits of K
+    row t for every t of the open block.  The buffers lie between guard zones."""
+    from _guard import guarded
+
+    from lqer_amd import QuantizedKVCache, kvcache
+
+    b, hk, d, capacity = 2, 2, 48, 80
+    z, bits = b * hk, torch.int16 if dtype == torch.float16 else torch.int32
+    k, v = (x.to(DEV) for x in _kv((b, hk, 67, d), dtype, 500))
+    sections, total = kvcache._sections(dtype, b, hk, capacity, d)
+
+    def cache_on_guard():
+        g = guarded(total, name="cache")
+        c = QuantizedKVCache(b, hk, d, CFG, CFG, dtype, DEV, capacity=capacity)
+        assert c.capacity == capacity and c.buf.numel() == total
+        c.buf = g.payload
+        return c, g
+
+    cache, guard = cache_on_guard()
+    for before, n in ((0, 5), (5, 11), (16, 1), (17, 40), (57, 7), (64, 3)):
+        assert cache.length == before
+        cache.append(k[:, :, before:before + n], v[:, :, before:before + n])
+        length = before + n
+        fresh, fresh_guard = cache_on_guard()
+        fresh.append(k[:, :, :length], v[:, :, :length])
+        torch.cuda.synchronize()
+        for gz in (guard, fresh_guard):
+            gz.check()
+        assert cache.buf.data_ptr() == guard.ptr
+        blocks = (length + 15) // 16
+        for name, at, per_block in sections[:4]:
+            row = (capacity // 16) * per_block
+            got, want = (c.buf[at:at + z * row].view(z, row)[:, :blocks * per_block] for c in (cache, fresh))
+            assert torch.equal(got, want), f"{before} + {n}: {name}: {(got != want).sum().item()} bytes differ from the one-append cache"
+        name, at, _ = sections[4]
+        assert name == "k_stage"
+        stage = cache.buf[at:at + z * 16 * d * k.element_size()].view(bits).view(z, 16, d)
+        for t in range(length // 16 * 16, length):
+            assert torch.equal(stage[:, t % 16], k[:, :, t].reshape(z, d).view(bits)), f"{before} + {n}: staging row {t % 16} is not K row {t}"
+
+
 # ---- 3. the same bits as the decode kernel on the raw tensors ------------------------------------------------------------------
 SHAPES = Dm.PARITY + [(2, 4, 2, 1, 16, 48), (2, 8, 2, 3, 32, 64), (1, 4, 2, 1, 2048, 128)]
 
@@ -203,7 +250,7 @@ def _shifted(x):
 def test_guard_zones(dtype, mode):
     """The cache (exactly lqer_kv_cache_bytes), out (rows padded: stride d + 8), row_stats and the workspace between guards, over a
     pseudo-random fill and over 0xFF (NaN in every float type, 255 in every code: nothing may read rows beyond the length).  Appends
-    of 21, 1, 1, 5 and 7 keys - inside the open block, up to its end, and across it from a non-empty open block (two launches)."""
+    of 21, 1, 1, 5 and 7 keys - inside the open block, up to its end, and across it from a non-empty open block (the append reads and rewrites staging rows in one launch)."""
     from _guard import guarded, rows_bytes
 
     from lqer_amd import _lib, ops
@@ -289,7 +336,7 @@ def test_guard_zones(dtype, mode):
 def test_graph_capture_and_replay(len0, n):
     """Appends at fixed lengths plus the attention call, captured and replayed on new q / k_new / v_new, against the eager calls on a
     second cache.  The captured step starts from length 0 - the len0 past keys, then the n new ones - because an append that leaves a
-    non-empty open block overwrites the staging rows it read (30 + 3: two launches) and cannot be repeated at the same length."""
+    non-empty open block overwrites the staging rows it read (30 + 3) and cannot be repeated at the same length."""
     from lqer_amd import attention_flexible_cached
     from lqer_amd.graph import GraphedCallable
 
