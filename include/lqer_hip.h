@@ -104,7 +104,13 @@ extern "C" {
 
 /* One MXINT quantizer: `width` bits per element incl. sign; `block` elements share an exponent
  * (block <= 0: one block per row); exponent clamped to [-exp_bias, 2^exp_width-1-exp_bias]
- * (block_fp.py:46-51; exp_width=8, exp_bias=127 in every template config). */
+ * (block_fp.py:46-51; exp_width=8, exp_bias=127 in every template config): e = clamp(ceil(log2(max |x|)), emin, emax) with
+ * emin = -exp_bias, emax = 2^exp_width - 1 - exp_bias, for exp_width 1..8.  The bias is bounded like the minifloat one: a format with
+ * emax - (width - 1) < -126 or emin > 127 is LQER_E_UNSUPPORTED (the message states the range).  Every kernel builds the block scale
+ * 2^(e - (width-1)) from exponent bits where that is a normal float and argues that it is not one only for blocks wholly below the
+ * 1e-8 flush; that holds for the lower end of any accepted format (e - mbits < -126 then needs max |x| < 2^-119) but not when the
+ * UPPER clamp itself lies below mbits - 126, where blocks of any size would take it.  With emin > 127 every block's 2^e is beyond fp32.
+ * Accepted biases: [-127, 2^exp_width - 1 - (width-1) + 126]. */
 typedef struct lqer_qfmt {
   int32_t kind;      /* LQER_Q_* */
   int32_t width;     /* passthrough (x / A_out): significand bits to carry - 8 bf16, 11 fp16, 24 fp32 - see

@@ -111,6 +111,16 @@ static bool fmt_ok(const lqer_qfmt_t* f, const char* name, int max_width) {
     set_error("%s: exponent_width %d outside [1,8]", name, f->exp_width);
     return false;
   }
+  // every block scale 2^(e - mbits), e in [emin, emax], must be reachable as a normal float from some block: the kernels build it from
+  // exponent bits (and flush what is below 1e-8) on the argument that e - mbits < -126 happens only under an upper clamp nobody
+  // configures - and an emin beyond 127 would put every block's 2^e past fp32 (include/lqer_hip.h, lqer_qfmt_t)
+  const int mbits = f->width - 1, emin = -f->exp_bias, emax = (1 << f->exp_width) - 1 - f->exp_bias;
+  if (f->exp_bias > 1000 || f->exp_bias < -1000 || emax - mbits < -126 || emin > 127) {
+    set_error("%s: block_fp exponent_bias %d (exponent_width %d, width %d): exponents [%d,%d] - needs emax - (width-1) >= -126 and "
+              "emin <= 127, i.e. a bias in [-127,%d]", name, f->exp_bias, f->exp_width, f->width, emin, emax,
+              (1 << f->exp_width) - 1 - mbits + 126);
+    return false;
+  }
   return true;
 }
 

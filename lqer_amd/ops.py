@@ -112,7 +112,13 @@ def make_qfmt(cfg: Optional[dict], role: str = "x") -> QFmt:
     ew = int(cfg.get("exponent_width", 8))
     eb = cfg.get("exponent_bias", None)
     eb = 2 ** (ew - 1) - 1 if eb in (None, "none", "None", "NA") else int(eb)
-    fmt = QFmt(_lib.Q_MXINT, int(cfg.get("width", 12)), int(bs[-1]), ew, eb)
+    width = int(cfg.get("width", 12))
+    emin, emax = -eb, 2 ** ew - 1 - eb
+    if emax - (width - 1) < -126 or emin > 127:
+        # (the library's rule, include/lqer_hip.h lqer_qfmt_t: every kernel builds the block scale 2^(e - mbits) from exponent bits)
+        raise NotImplementedError(f"block_fp(width={width}, exponent_width={ew}, exponent_bias={eb}): exponents [{emin}, {emax}] - the HIP path "
+                                  f"needs emax - (width - 1) >= -126 and emin <= 127, i.e. a bias in [-127, {2 ** ew - 1 - (width - 1) + 126}]")
+    fmt = QFmt(_lib.Q_MXINT, width, int(bs[-1]), ew, eb)
     if role != "b" and block_rows != 1:
         fmt.block_rows = block_rows  # (a Python attribute beside the C fields: only the packing call needs it)
     if role != "b" and act_tiles is not None:

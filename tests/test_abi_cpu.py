@@ -264,3 +264,73 @@ def test_activation_tiles_take_the_tile_route():
     mod = lqer_amd.LinearFlexibleLqer(64, 64, bias=False, q_config=dict(base, x_quantizer=bfp(8, [16], True)), l_config={"rank": 16})
     assert mod._tiles and not mod._tiles_only
     assert mod._needs_tiles(torch.zeros(2, 3, 64)) and not mod._needs_tiles(torch.zeros(6, 64)) and not mod._needs_tiles(torch.zeros(4, 1, 64))
+
+
+def test_block_fp_bias_range_is_refused_at_both_ends(lib):
+    """A block_fp format whose exponent range the kernels' scale arguments do not cover is refused by the library (fmt_ok) and by
+    ops.make_qfmt alike, with the range in the message: emax - (width-1) < -126 (every block scale would be below the normal floats)
+    and emin > 127 (every 2^e beyond fp32).  The boundary values and every format of tests/_formats.py are accepted.  No kernel runs:
+    a zero-row quantizer call and the size query stop after the format check."""
+    import _formats as F
+    from lqer_amd import _lib, ops
+
+    def c_accepts(width, ew, bias, block=16):
+        f = _lib.QFmt(_lib.Q_MXINT, width, block, ew, bias)
+        rc = lib.lqer_quantize_mxint(None, _lib.F32, 0, 0, 0, C.byref(f), None, None, None, None)
+        msg = lib.lqer_last_error().decode() if rc else ""
+        # ... and as the weight format of a descriptor
+        f8 = _lib.QFmt(_lib.Q_MXINT, 8, 16, 8, 127)
+        d = _lib.LinearDesc(256, 256, 0, 0, f8, f, f8, f8, f8)
+        rc2 = lib.lqer_linear_sizes(C.byref(d), 8, C.byref(_lib.LinearSizes())) if width <= 8 else rc
+        assert (rc == 0) == (rc2 == 0), (width, ew, bias, rc, rc2)
+        return rc == 0, msg
+
+    def py_accepts(width, ew, bias):
+        try:
+            f = ops.make_qfmt(dict(name="block_fp", width=width, exponent_width=ew, exponent_bias=bias, block_size=[1, 16]))
+        except NotImplementedError as e:
+            return False, str(e)
+        assert (f.width, f.exp_width, f.exp_bias) == (width, ew, bias)
+        return True, ""
+
+    for width, ew in ((8, 8), (4, 8), (2, 8), (8, 4), (4, 1), (6, 3)):
+        mbits = width - 1
+        top = 2 ** ew - 1 - mbits + 126  # the largest accepted bias: emax - mbits = -126
+        for bias, want in ((top, True), (top + 1, False), (400, False), (-127, True), (-128, False), (-400, False)):
+            for fn in (c_accepts, py_accepts):
+                ok, msg = fn(width, ew, bias)
+                assert ok == want, (fn.__name__, width, ew, bias, msg)
+                if not want:  # the message states the format's range and the accepted one
+                    emin, emax = -bias, 2 ** ew - 1 - bias
+                    assert str(emin) in msg and str(emax) in msg and "-127" in msg and str(top) in msg, msg
+    for fid, width in sorted(set(F.ACT_PAIRS + F.W4_PAIRS + F.W8_PAIRS)):
+        assert c_accepts(width, F.FORMATS[fid][0], F.bias_of(fid))[0], (fid, width)
+        f = ops.make_qfmt(F.cfg(fid, width), "x")
+        assert (f.exp_width, f.exp_bias) == (F.FORMATS[fid][0], F.bias_of(fid))
+
+
+def test_refused_block_fp_bias_takes_the_unfused_route():
+    """functional._fused_fmt swallows the NotImplementedError of a format the product kernels do not cover: the bias refusal is one."""
+    import _formats as F
+    from lqer_amd import functional
+
+    assert functional._fused_fmt(dict(F.cfg("e8", 8), exponent_bias=400)) is None
+    assert functional._fused_fmt(F.cfg("e3bm2", 4)) is not None
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_format_ladder_reaches_both_clamps(dtype):
+    """The input ladder of tests/_formats.py, as the GPU tests draw it: for every format narrower than the dtype, each of {clamped at
+    emin, unclamped, clamped at emax} holds at least 15 % of the non-zero blocks by the oracle's own exponents."""
+    import _formats as F
+
+    ids = F.FP16_IDS if dtype == torch.float16 else tuple(F.FORMATS)
+    reached = 0
+    for fid in ids:
+        for block, (rows, cols) in ((16, (8, 200)), (32, (8, 200)), (-1, (24, 200)), (128, (8, 320))):
+            for width in (8, 4, 2):
+                x = F.ladder(fid, dtype, rows, cols, block, seed=3)
+                lo, un, hi = F.assert_covered(x, fid, F.cfg(fid, width, [1, block]), dtype)
+                reached += (lo > 0) + (hi > 0)
+                assert bool(torch.isfinite(x.float()).all())
+    assert reached > 0

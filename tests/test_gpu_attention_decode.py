@@ -17,23 +17,13 @@ import pytest
 import torch
 
 import test_gpu_attention_fused as F
+from _attention import _mask, _pad  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CFG, DEV, BAR, DTYPES = F.CFG, F.DEV, F.BAR, F.DTYPES
 DT_IDS = ["f16", "bf16", "f32"]
 _ids = lambda c: "x".join(map(str, c))
-
-
-def _pad(s, t):
-    return max(0, t - s - 3)  # the last batch element is left-padded by this many keys: every row keeps a visible key
-
-
-def _mask(mode, b, s, t, dtype):
-    """none / causal / 'mask': the causal tensor whose last batch element is left-padded."""
-    if mode == "none":
-        return None
-    return F._causal_mask(s, t, dtype, pad=_pad(s, t) if mode == "mask" else None, batch=b)
 
 
 def decode(q, k, v, scaling, mask=None, causal=False, **kw):

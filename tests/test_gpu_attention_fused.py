@@ -9,50 +9,16 @@ sums and the last bits of exp, which flip a few codes of P at quantizer ties: th
 and an fp64 softmax differs by at most 5.4e-5, so the bar leaves a factor of about 18 over the reference's own spread.
 """
 import json
-import os
 import types
 
 import pytest
 import torch
 
+from _attention import BAR, CFG, DEV, _causal_mask, _randn, _rel, comparator  # noqa: F401 (shared with the other attention modules)
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CFG = json.load(open(os.path.join(HERE, "golden", "matmul_config.json")))
 DTYPES = [torch.float16, torch.bfloat16, torch.float32]
-DEV = "cuda:0"
-BAR = 1e-3
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
-
-
-def _causal_mask(s, t, dtype, pad=None, batch=1):
-    """eager_mask's tensor: 0 where key j is visible to query i (j <= i + t - s), the dtype's most negative finite value elsewhere;
-    `pad` masks the first keys of the LAST batch element as well (a left-padded sequence: its early rows are fully masked)."""
-    i, j = torch.arange(s)[:, None], torch.arange(t)[None, :]
-    dead = (j > i + (t - s))[None, None].expand(batch, 1, s, t).clone()
-    if pad:
-        dead[-1, :, :, :pad] = True
-    return torch.zeros(batch, 1, s, t, dtype=dtype).masked_fill_(dead, torch.finfo(dtype).min)
-
-
-def comparator(q, k, v, scaling, mask=None):
-    """CPU tensors of dtype DT -> (O, S2, P) in DT."""
-    from oracle import lqer_oracle as O
-
-    dt = q.dtype
-    b, h, s, d = q.shape
-    hk, t = k.shape[1], k.shape[2]
-    rep = lambda x: x[:, :, None].expand(b, hk, h // hk, t, d).reshape(b * h, t, d).float()
-    S = O.matmul_flexible(q.reshape(b * h, s, d).float(), rep(k).transpose(1, 2), CFG).reshape(b, h, s, t).to(dt)
-    S2 = (S.float() * torch.tensor(scaling, dtype=torch.float32)).to(dt)
-    if mask is not None:
-        S2 = (S2.float() + mask.float()).to(dt)
-    P = torch.softmax(S2.float(), dim=-1).to(dt)
-    out = O.matmul_flexible(P.reshape(b * h, s, t).float(), rep(v), CFG).reshape(b, h, s, d).to(dt)
-    return out, S2, P
 
 
 def fused(q, k, v, scaling, mask=None, causal=False, cfg0=CFG, cfg1=CFG, **kw):
@@ -72,11 +38,6 @@ def unfused_gpu(q, k, v, scaling, mask=None):
     from lqer_amd import attention as A
 
     return A.lqer_eager_attention_forward(_module(q.shape[1] // k.shape[1]), q, k, v, mask, scaling)
-
-
-def _randn(shape, dtype, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (scale * torch.randn(*shape, generator=g)).to(dtype)
 
 
 # ---- 1. the exact leg ---------------------------------------------------------------------------------------------------------

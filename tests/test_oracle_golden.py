@@ -186,3 +186,69 @@ def test_fp16_evaluation_of_the_reference_differs_only_at_small_magnitude_ties()
         w = meta[0]
         step = (ours - y).abs()
         assert (step[diff] <= y.abs().max() * 2.0 ** (2 - w) + 1e-12).all(), name
+
+
+# ---- narrow exponent fields: both clamps of block_fp.py:46-51 active (tests/golden/make_golden_expfield.py) -------------------------
+def _expfield():
+    import os
+
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "quantizers_expfield.npz"))
+
+
+def _expfield_names(g):
+    return sorted({k.rsplit("/", 1)[0] for k in g.files})
+
+
+def _expfield_kw(meta):
+    width, ew, has_b, eb, skip = meta[:5]
+    return dict(width=width, exponent_width=ew, exponent_bias=eb if has_b else None, block_size=meta[5:], skip_first_dim=bool(skip))
+
+
+def test_expfield_golden_present_and_clamped():
+    """The fixture holds every (format, width) pair of tests/_formats.py, and in every format narrower than fp32 the reference met
+    both clamps: each of {clamped at emin, unclamped, clamped at emax} holds at least 15 % of the non-zero blocks."""
+    import _formats as F
+
+    g = _expfield()
+    names = _expfield_names(g)
+    for p in set(F.ACT_PAIRS + F.W4_PAIRS + F.W8_PAIRS):
+        assert f"b16/{F.pair_id(p)}" in names
+    for kind in ("b128", "row", "tile4x16", "act3d", "act3d_tile"):
+        assert any(n.startswith(kind + "/") for n in names), kind
+    for name in names:
+        fid = name.split("/")[1].split("-")[0]
+        kw = _expfield_kw(g[f"{name}/meta"].tolist())
+        F.assert_covered(torch.from_numpy(g[f"{name}/x"]), fid, dict(kw, name="block_fp"), torch.float32)
+
+
+@pytest.mark.parametrize("via_unfold", [False, True])
+def test_expfield_quantizer_bit_exact(via_unfold):
+    """Every value of the fixture, bit for bit - except the sign of a zero, which this test, like test_mxint_quantizer_bit_exact,
+    does not pin: the oracle writes +0 where the reference's sign(x + 1e-9) * 0 leaves -0."""
+    g = _expfield()
+    for name in _expfield_names(g):
+        x, y = torch.from_numpy(g[f"{name}/x"]), torch.from_numpy(g[f"{name}/y"])
+        kw = _expfield_kw(g[f"{name}/meta"].tolist())
+        got = O.mxint_quantize(x, **kw, via_unfold=via_unfold)
+        assert got.dtype == torch.float32 and got.shape == y.shape
+        assert torch.equal(got.view(torch.int32), y.view(torch.int32)) or torch.equal(got, y), name
+        assert torch.equal(O.mxint_quantize(x, **kw, libm_log2=True), got), name
+
+
+def test_expfield_decompose_reconstructs():
+    """decompose=True: codes 2^(exponent - mbits) is the quantizer's output (the |x| <= 1e-8 pass-through as 0), the exponents lie
+    inside the field's range and the codes inside the width's."""
+    g = _expfield()
+    for name in _expfield_names(g):
+        x = torch.from_numpy(g[f"{name}/x"])
+        kw = _expfield_kw(g[f"{name}/meta"].tolist())
+        y, codes, exps = O.mxint_quantize(x, **kw, decompose=True)
+        cblk, restore = O._blocks(codes.float(), list(kw["block_size"]), kw["skip_first_dim"])
+        rebuilt = restore(cblk * torch.pow(2.0, (exps.float() - (kw["width"] - 1)))[..., None])
+        ref = torch.where(x.abs() <= 1e-8, torch.zeros_like(y), y)
+        assert torch.equal(rebuilt, ref), name
+        assert int(codes.abs().max()) <= 2 ** (kw["width"] - 1) - 1
+        eb = 2 ** (kw["exponent_width"] - 1) - 1 if kw["exponent_bias"] is None else kw["exponent_bias"]
+        xb, _ = O._blocks(x, list(kw["block_size"]), kw["skip_first_dim"])
+        nz = xb.abs().amax(dim=-1) != 0
+        assert int(exps[nz].min()) >= -eb and int(exps[nz].max()) <= 2 ** kw["exponent_width"] - 1 - eb, name
