@@ -662,8 +662,10 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  *   max_len      host: an upper bound on every lens[b] (for append: on lens[b] + n), 1 <= max_len <= min(16 table_stride, 2^30).  It
  *                sizes grids and the workspace only - no result depends on it, and no host decision depends on a length.
  * The library cannot see device contents from the host, so VALID TABLES AND LENGTHS ARE THE CALLER'S CONTRACT, as valid pointers are:
- * every page index a call reaches (entries 0 .. ceil(len / 16) - 1 of an addressed slot's row) lies in [0, pages); no page belongs to
- * two live sequences; no slot is named twice in one call; every seq_slots[b] lies in [0, slots); 0 <= lens[b] and lens[b] (+ n)
+ * every page index a call reaches (entries 0 .. ceil(len / 16) - 1 of an addressed slot's row) lies in [0, pages); a page may belong to
+ * several live sequences only if all of its 16 keys lie below the length of every owner (a full page is never written again, so it
+ * can be shared: lqer_kv_pool_fork) - the page at len / 16 of a sequence with len % 16 != 0 belongs to it alone; no slot is named
+ * twice in one call; every seq_slots[b] lies in [0, slots); 0 <= lens[b] and lens[b] (+ n)
  * <= max_len.  A call that breaks this reads or writes outside the pool.  Nothing depends on the contents of a page beyond its
  * sequence's length or on staging rows beyond len % 16: pages and slots are reused dirty, a fresh pool needs no initialisation.
  * lqer_kv_pool_append: k_new / v_new [batch][kv_heads][n][D] of DT through k_strides[3] / v_strides[3], n >= 1 uniform over the call
@@ -703,6 +705,18 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
  * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack) and an export path (more than 8 query rows
  * on paged sequences need no copy: lqer_attention_q_paged).
+ * lqer_kv_pool_fork: n pairs (src_slots[i], dst_slots[i], lens[i]), three DEVICE arrays: the sequence in slot dst becomes a copy of the
+ * first L = lens[i] keys of the one in slot src - a second sample of one prompt, a beam, a snapshot to come back to when speculated
+ * tokens are rejected.  The caller writes src's entries 0 .. L / 16 - 1 into dst's table row: full pages are shared by reference and
+ * nothing of them is copied.  With L % 16 != 0 the item (block_table[src][L / 16], g) is copied to (block_table[dst][L / 16], g) - a
+ * page of dst's own - for every kv head g in all four code and exponent sections, bytes as they are; always, the 16 staging rows of
+ * slot src are copied to slot dst for every kv head (with L % 16 == 0 only they move, and nothing depends on them).  From there on
+ * dst appends and attends like any sequence, with the bits of a sequence that was appended the same keys itself.  ONE launch on
+ * `stream` for all pairs, in 16-byte pieces; the grid comes from n and kv_heads alone - a workgroup whose pair has no open block leaves
+ * at once -, no allocation, no host synchronisation, no atomics.  Caller's contract: a slot may be src of several pairs; every dst is
+ * named once and is not a src of the same call; the table rows of dst are valid up to ceil(L / 16) entries before the launch; L is
+ * at most src's length.  Refused: LQER_E_INVALID - any null pointer, n < 1, pages, slots, kv_heads, table_stride or D < 1, a short or
+ * misaligned pool; LQER_E_UNSUPPORTED - a dtype or D lqer_kv_pool_bytes rejects, n x kv_heads beyond the launch grid (2^31 - 1).
  * Refused with a message, nothing launched or touched (decided from host arguments only):
  *   LQER_E_UNSUPPORTED  what lqer_attention_q_decode_kv / lqer_kv_cache_append refuse so (S > 8, formats, D, batch or kv_heads > 65535);
  *                       max_len > 2^30 (every call); lqer_attention_q_paged: what lqer_attention_q_kv refuses so instead (formats, D, S
@@ -719,6 +733,9 @@ int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t sl
 int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
                         const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
                         int64_t capacity, void* stream);
+int lqer_kv_pool_fork(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                      const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
+                      int64_t n, void* stream);
 size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
 int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                                   int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,

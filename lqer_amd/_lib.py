@@ -138,6 +138,8 @@ SIGNATURES = {
     "lqer_kv_pool_bytes": (_sz, [_i, _i64, _i64, _i64, _i64]),
     "lqer_kv_pool_append": (_i, [_vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64, _qp, _qp, _vp]),
     "lqer_kv_pool_gather": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _i64, _vp]),
+    # pool, bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, src_slots, dst_slots, lens, pairs, stream
+    "lqer_kv_pool_fork": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "lqer_attention_q_decode_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_decode_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
                                            _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),

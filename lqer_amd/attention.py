@@ -125,17 +125,22 @@ def _kv_layer_cls():
         def prefetch(self):
             pass
 
+        def _select(self, indices) -> None:  # (a layer not yet initialised has no batch: the first update() brings it)
+            if self.cache is not None:
+                self.cache.select(indices)
+
         def reorder_cache(self, beam_idx) -> None:
-            self._no("beam search (reorder_cache)")
+            self._select(beam_idx)
 
         def crop(self, *args, **kwargs) -> None:
             self._no("crop")
 
         def batch_repeat_interleave(self, repeats: int) -> None:
-            self._no("batch_repeat_interleave")
+            if self.cache is not None:
+                self._select(torch.arange(self.cache.batch).repeat_interleave(repeats))
 
         def batch_select_indices(self, indices) -> None:
-            self._no("batch_select_indices")
+            self._select(indices)
 
     _KV_LAYER_CLS = QuantizedKVLayer
     return QuantizedKVLayer

@@ -1434,6 +1434,33 @@ int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t 
   return kv_pool_gather_dispatch(p, slot, T, cache, capacity, (hipStream_t)stream);
 }
 
+int lqer_kv_pool_fork(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                      const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
+                      int64_t n, void* stream) {
+  if (n < 1) {
+    set_error("kv_pool_fork: %lld pairs for the KV pool (at least one)", (long long)n);
+    return LQER_E_INVALID;
+  }
+  if (!src_slots) {
+    set_error("kv_pool_fork: null src_slots for the KV pool");
+    return LQER_E_INVALID;
+  }
+  if (!kv_dtype_ok(dtype)) {  // (what lqer_kv_pool_bytes rejects, one code for dtype and head dim)
+    set_error("kv_pool_fork: dtype %d - the KV pool takes fp32, fp16 and bf16", dtype);
+    return LQER_E_UNSUPPORTED;
+  }
+  // the bound on the lengths is the room of a table row, or the library's 2^30 where the row has more
+  const int64_t room = table_stride < ((int64_t)1 << 26) ? 16 * table_stride : (int64_t)1 << 30;
+  const KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, dst_slots, lens, table_stride, room};
+  const int rc = kv_pool_check("kv_pool_fork", p, POOL_BATCH);
+  if (rc != LQER_OK) return rc;
+  if (n > (((int64_t)1 << 31) - 1) / kv_heads) {  // (a workgroup pair per (pair, kv head) over grid.x)
+    set_error("kv_pool_fork: %lld pairs x %lld kv heads of the KV pool beyond one launch grid: fork in pieces", (long long)n, (long long)kv_heads);
+    return LQER_E_UNSUPPORTED;
+  }
+  return kv_pool_fork_dispatch(p, src_slots, n, (hipStream_t)stream);
+}
+
 size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
   if (batch <= 0 || heads <= 0 || kv_heads <= 0 || S <= 0 || max_len <= 0 || D <= 0) return 0;
   return attention_q_decode_paged_workspace_bytes(batch, heads, S, max_len, D);

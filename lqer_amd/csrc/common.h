@@ -839,6 +839,7 @@ size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, 
 int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
                             const QP& qk, const QP& qv, hipStream_t st);
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st);
+int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, hipStream_t st);  // (p.seq_slots: the children's slots)
 constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128
 // the two images of lqer_attention_q's workspace from the first T keys of c's cache, or from the first lens[b] keys of every sequence
 // of c's pool (strides of T = max_len); the caller (attn_q.hip) checks the launches

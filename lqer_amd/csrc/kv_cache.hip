@@ -9,6 +9,7 @@
 //                block left open go to the staging rows.  One launch, whatever the length was (see the kernel).
 //   k_kv_unpack  code x 2^(e - mbits) as fp32, one element per thread.
 //   k_kv_pool_gather   one sequence's bytes out of the pool into a dense cache.
+//   k_kv_pool_fork     children that share their parents' full pages: the open block's item and the staging rows, copied per child.
 //   k_kv_kimage / k_kv_vimage   the cache -> the two bf16 images k_attn_q reads (attn_q.hip; what k_attn_kimage / k_attn_vimage write from
 //                the raw K and V): codes16_to_bf16 on 16 codes per 16-byte load, zeros wherever the raw image kernels write their
 //                padding - every key at or beyond T, every d at or beyond D.  Nothing of the cache at or beyond key T reaches an image.
@@ -147,6 +148,42 @@ __global__ __launch_bounds__(256) void k_kv_pool_gather(const GArgs a) {
   }
   i -= nB;
   if (i < a.kvh * a.stage16) ((uint4*)a.dst[4])[i] = ((const uint4*)a.src[4])[a.slot * a.kvh * a.stage16 + i];
+}
+
+struct FArgs {
+  KvSrc<unsigned char> src;  // the pool; src.slots / src.lens: the CHILD's slot and the length forked at, per pair (device)
+  const int32_t* from;       // the parent's slot, per pair (device)
+  int64_t D, stage16;        // 16-byte pieces of a kv head's staging rows
+};
+
+// Fork: pair i makes the sequence in slot src.slots[i] a copy of the first L = src.lens[i] keys of the one in slot from[i], whose full
+// pages the child's table row already names - they are shared, not copied.  What is copied, bytes as they are, in 16-byte pieces: the
+// parent's staging rows, and with L % 16 != 0 the item of the open block L / 16 - K codes, K exponents, V codes, V exponents - from the
+// parent's page to the child's own.  grid (pairs x kv heads, 2): y = 0 the staging rows, y = 1 the item; a workgroup of y = 1 whose pair
+// has no open block leaves at once.  Nothing here is read by another workgroup of the launch (a child is named once and is no parent).
+__global__ __launch_bounds__(256) void k_kv_pool_fork(const FArgs a) {
+  const int64_t kvh = a.src.kvh, i = blockIdx.x / kvh, g = blockIdx.x % kvh;
+  const int32_t* drow;
+  const int64_t L = seq<attn::SRC_PAGED>(a.src, i, 0, drow), from = a.from[i];
+  if (blockIdx.y == 0) {
+    const uint4* s = (const uint4*)a.src.stage + (from * kvh + g) * a.stage16;
+    uint4* d = (uint4*)a.src.stage + ((int64_t)a.src.slots[i] * kvh + g) * a.stage16;
+    for (int64_t u = threadIdx.x; u < a.stage16; u += 256) d[u] = s[u];
+    return;
+  }
+  if (L % 16 == 0) return;  // (uniform over the workgroup)
+  const int64_t e16 = a.D / 16, per = 2 * (a.D + e16);
+  const int64_t sblk = page_block(slot_row(a.src, from), kvh, g, L / 16), dblk = page_block(drow, kvh, g, L / 16);
+  for (int64_t p = threadIdx.x; p < per; p += 256) {
+    int64_t u = p;
+    int sec = 0;
+    if (u >= a.D) u -= a.D, sec = 1;
+    if (sec == 1 && u >= e16) u -= e16, sec = 2;
+    if (sec == 2 && u >= a.D) u -= a.D, sec = 3;
+    const int64_t item = (sec & 1) ? e16 : a.D;  // 16-byte pieces of a block in this section
+    uint4* base = (uint4*)(sec == 0 ? a.src.kc : sec == 1 ? a.src.ke : sec == 2 ? a.src.vc : a.src.ve);
+    base[dblk * item + u] = base[sblk * item + u];
+  }
 }
 
 struct UArgs {
@@ -314,6 +351,13 @@ int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cach
   const int64_t items = p.kv_heads * (a.nblk * 2 * (p.D + p.D / 16) + a.stage16);
   kvc::k_kv_pool_gather<<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
   return check_launch("lqer_kv_pool_gather");
+}
+
+// p.seq_slots: the children's slots; the grid comes from n and kv_heads alone
+int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, hipStream_t st) {
+  kvc::FArgs a = {kvc::src_of<unsigned char>(p), src_slots, p.D, p.D * (p.dtype == LQER_F32 ? 4 : 2)};  // 16 rows x D x esz / 16
+  kvc::k_kv_pool_fork<<<dim3((unsigned)(n * p.kv_heads), 2), 256, 0, st>>>(a);
+  return check_launch("lqer_kv_pool_fork");
 }
 
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,

@@ -91,11 +91,13 @@ __host__ inline KvSrc<const unsigned char> src_of(const AttnCall& c) {  // (c.pa
 }
 
 // the length of the call's b-th sequence and its row of the page table: lens[b] and the slot's row, or the host's T and no row
+template <class B>
+__device__ __forceinline__ const int32_t* slot_row(const KvSrc<B>& s, int64_t slot) { return s.tbl + slot * s.tstride; }
 template <int SRC, class B>
 __device__ __forceinline__ int64_t seq(const KvSrc<B>& s, int64_t b, int64_t T, const int32_t*& row) {
   row = nullptr;
   if constexpr (SRC == attn::SRC_PAGED) {
-    row = s.tbl + (int64_t)s.slots[b] * s.tstride;
+    row = slot_row(s, (int64_t)s.slots[b]);
     return s.lens[b];
   }
   return T;

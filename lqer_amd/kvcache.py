@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -157,6 +158,34 @@ class QuantizedKVCache:
     def dequantized(self):
         return unpack_packed(self.buf, self.dtype, self.batch, self.kv_heads, self.capacity, self.head_dim, self.length, self.fmts[1], self.fmts[3])
 
+    @torch.no_grad()
+    def select(self, indices) -> None:
+        """Gather along the batch: row i becomes the old row indices[i] - a beam search's reorder, a repeat for several samples of one
+        prompt, a subset; the batch may grow or shrink.  Out of place, as _grow: a new buffer of the same capacity takes the live
+        blocks of the four code and exponent sections and the staging rows of every kv head of the selected rows, bytes as they are
+        (torch's index_select - no kernel of the library), so row i then appends and attends with the bits old row indices[i] had."""
+        idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1).cpu()
+        if idx.numel() < 1 or idx.numel() > _MAX_GRID_Z or int(idx.min()) < 0 or int(idx.max()) >= self.batch:
+            raise ValueError(f"QuantizedKVCache.select: indices {idx.tolist()} for a batch of {self.batch}")
+        idx = idx.to(self.device)
+        old_batch, old_buf, hk = self.batch, self.buf, self.kv_heads
+        self.batch = idx.numel()
+        try:
+            new = self._alloc(self.capacity)
+        except BaseException:
+            self.batch = old_batch
+            raise
+        old_s, _ = _sections(self.dtype, old_batch, hk, self.capacity, self.head_dim)
+        new_s, _ = _sections(self.dtype, self.batch, hk, self.capacity, self.head_dim)
+        blocks = (self.length + 15) // 16
+        for (_, o_at, per_block), (_, n_at, _) in zip(old_s, new_s):
+            row = 16 * self.head_dim * torch.empty((), dtype=self.dtype).element_size() if per_block is None else (self.capacity // 16) * per_block
+            live = row if per_block is None else blocks * per_block
+            if live:
+                src = old_buf[o_at:o_at + old_batch * hk * row].view(old_batch, hk, row)[:, :, :live]
+                new[n_at:n_at + self.batch * hk * row].view(self.batch, hk, row)[:, :, :live].copy_(src.index_select(0, idx))
+        self.buf = new
+
 
 @torch.no_grad()
 def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mask=None, causal=False, out_layout="bhsd", return_stats=False,
@@ -204,7 +233,11 @@ class PageTable:
 
     A sequence id is handed out once and never again, so a freed id stays refused; it maps to a SLOT (a row of the table, a set of
     staging rows), and slots and pages are reused.  `reserve` is all or nothing: it validates every addressed sequence and counts
-    the pages of the whole call before it takes one."""
+    the pages of the whole call before it takes one.
+
+    A page has a count of owners.  `fork` gives a new sequence the FULL pages of its parent by reference - a full page is never
+    written again, so it needs no copy - and a page of its own for the open block; `free` hands a page back when its last owner
+    goes.  A sequence that was never forked owns every one of its pages alone, and its books are what they were without the counts."""
 
     def __init__(self, num_pages: int, max_seqs: int, max_pages_per_seq=None):
         if max_pages_per_seq is None:
@@ -219,10 +252,16 @@ class PageTable:
         self.table = [[0] * max_pages_per_seq for _ in range(max_seqs)]  # [slot][i]: the page of keys 16 i .. 16 i + 15
         self.pages_of = [0] * max_seqs                                   # entries of a slot's row that are its pages
         self.lengths = [0] * max_seqs                                    # [slot]
+        self._owners = np.zeros(num_pages, dtype=np.int32)               # [page]: the live sequences whose rows name it
 
     @property
     def pages_free(self) -> int:
         return len(self._free_pages)
+
+    @property
+    def pages_shared(self) -> int:
+        """Pages with more than one owner."""
+        return int((self._owners > 1).sum())
 
     @property
     def max_len(self) -> int:
@@ -248,8 +287,10 @@ class PageTable:
         slot = self.slot(seq)
         del self._slot[seq]
         row = self.table[slot]
-        for i in range(self.pages_of[slot] - 1, -1, -1):
-            self._free_pages.append(row[i])
+        if self.pages_of[slot]:
+            pages = np.array(row[self.pages_of[slot] - 1::-1])  # the last page first: the order pages have always gone back in
+            self._owners[pages] -= 1
+            self._free_pages.extend(pages[self._owners[pages] == 0].tolist())  # (those whose last owner this was)
         self.pages_of[slot] = self.lengths[slot] = 0
         self._free_slots.append(slot)
 
@@ -281,7 +322,8 @@ class PageTable:
             raise RuntimeError(f"PagedKVCache.append: out of pages - {sum(need)} needed, {len(self._free_pages)} of {self.num_pages} free")
         for s, k in zip(slots, need):
             for _ in range(k):
-                self.table[s][self.pages_of[s]] = self._free_pages.pop()
+                self.table[s][self.pages_of[s]] = page = self._free_pages.pop()
+                self._owners[page] = 1
                 self.pages_of[s] += 1
         return slots, [self.lengths[s] for s in slots], need
 
@@ -290,11 +332,59 @@ class PageTable:
         for s, k in zip(reversed(slots), reversed(taken)):
             for _ in range(k):
                 self.pages_of[s] -= 1
+                self._owners[self.table[s][self.pages_of[s]]] = 0
                 self._free_pages.append(self.table[s][self.pages_of[s]])
 
     def commit(self, slots, n: int) -> None:
         for s in slots:
             self.lengths[s] += n
+
+    def fork(self, parents):
+        """One new sequence per entry of `parents` (repeats allowed), each of its parent's length: (children, parents' slots,
+        children's slots, lengths).  A child's row takes the parent's full pages, their counts raised, and - where the length is no
+        multiple of 16 - one fresh page for the open block, which the launch fills.  All or nothing: the slots and pages of the
+        whole call are counted first; out of either raises RuntimeError with nothing taken.  rollback_fork() undoes it."""
+        parents = list(parents)
+        src = [self.slot(p) for p in parents]
+        lens = [self.lengths[s] for s in src]
+        pages = sum(1 for n in lens if n % PAGE_KEYS)
+        if len(parents) > len(self._free_slots):
+            raise RuntimeError(f"PagedKVCache.fork: {len(parents)} new sequences, {len(self._free_slots)} of {self.max_seqs} sequence slots free")
+        if pages > len(self._free_pages):
+            raise RuntimeError(f"PagedKVCache.fork: out of pages - {pages} needed, {len(self._free_pages)} of {self.num_pages} free")
+        children, dst, shared = [], [], {}
+        for s, n in zip(src, lens):
+            child = self.alloc()
+            d, full = self._slot[child], n // PAGE_KEYS
+            row = self.table[d]
+            if full:
+                row[:full] = self.table[s][:full]
+                if s not in shared:
+                    shared[s] = np.array(row[:full])
+                self._owners[shared[s]] += 1
+            if n % PAGE_KEYS:
+                row[full] = page = self._free_pages.pop()
+                self._owners[page] = 1
+            self.pages_of[d], self.lengths[d] = (n + PAGE_KEYS - 1) // PAGE_KEYS, n
+            children.append(child), dst.append(d)
+        return children, src, dst, lens
+
+    def rollback_fork(self, children) -> None:
+        """Undo a fork() whose launch did not happen: the ids, slots and pages go back so that the next call takes the same."""
+        for child in reversed(children):
+            self.free(child)
+        self._next_seq -= len(children)
+
+    def snapshot(self, seqs=()):
+        """The books, and the table rows of `seqs` - what restore() needs to put back sequences that were freed since."""
+        return (self._free_pages[:], self._free_slots[:], dict(self._slot), self._next_seq, self.pages_of[:], self.lengths[:], self._owners.copy(),
+                {self.slot(s): self.table[self.slot(s)][:] for s in seqs})
+
+    def restore(self, snap) -> None:
+        self._free_pages, self._free_slots, self._slot, self._next_seq, self.pages_of, self.lengths, self._owners = (
+            snap[0][:], snap[1][:], dict(snap[2]), snap[3], snap[4][:], snap[5][:], snap[6].copy())
+        for s, row in snap[7].items():
+            self.table[s][:] = row
 
 
 class PagedKVCache:
@@ -310,7 +400,18 @@ class PagedKVCache:
     .length(seq);  .pages_free;  .nbytes
     .to_dense(seq) -> QuantizedKVCache (batch 1) with the sequence's bytes - an export, and the test hook (more than 8 query rows
                        need no copy: attention_flexible_paged(kernel="prefill"));  .dequantized(seq) -> (K, V) [1, kv_heads, length,
-                       head_dim] fp32, for tests"""
+                       head_dim] fp32, for tests
+    .fork(seq, n=1) / .fork_many(parents) -> new sequences that hold their parent's keys: a page is one K quantizer block, an append
+                       rewrites only the block at length / 16 and those after it, so a FULL page is never written again and is
+                       shared by reference - no copy-on-write; a child costs one page (the open block, if there is one) and one
+                       launch for the whole set
+    .reorder(seqs, parent_idx) -> the beam step: the ids of the beams that continue seqs[parent_idx[i]]
+    .pages_shared      pages with more than one owner
+
+    Taking speculated tokens back: `snap, = cache.fork(seq)`, append the speculated block to `seq` and attend; if only the first m of
+    its keys are accepted, `cache.free(seq)` and append those m keys' k / v - the step still has them - to `snap`, which goes on as
+    the sequence: the bits of one that only ever saw the m.  There is no in-place crop: the raw keys of a closed block are gone,
+    so a shortened block cannot be given the codes and exponents it would have had."""
 
     covers = staticmethod(QuantizedKVCache.covers)
 
@@ -391,6 +492,89 @@ class PagedKVCache:
                                                       ops._DT[self.dtype], len(slots), self.kv_heads, self.head_dim, n, C.byref(self.fmts[1]),
                                                       C.byref(self.fmts[3]), ops._stream(self.device)),
                        "lqer_kv_pool_append")
+
+    # ---- sequences over shared pages (lqer_kv_pool_fork) ----
+    def fork(self, seq: int, n: int = 1) -> list:
+        """n new sequences that hold seq's keys: fork_many([seq] * n)."""
+        if n < 1:
+            raise ValueError(f"PagedKVCache.fork: {n} children")
+        return self.fork_many([seq] * n)
+
+    @torch.no_grad()
+    def fork_many(self, parents) -> list:
+        """One new sequence per entry of `parents` (repeats allowed) with its parent's keys - samples of one prompt, sequences behind
+        one system prompt, beams - from then on a sequence like any other: it appends and attends with the bits of a sequence that was
+        appended the same keys itself, and is freed on its own.  The parent's full pages are shared by reference; what one launch for
+        the whole set copies is the open block (a page of the child's own) and the staging rows per child.  Slots and pages of the
+        whole call are taken first; out of either, an unknown or freed parent, or a refusal of the library raise with the pool and
+        the books as they were.  A parent of length 0 gives empty children, and nothing is launched."""
+        parents = list(parents)
+        if not parents:
+            return []
+        children, src, dst, lens = self.pt.fork(parents)  # (raises with nothing taken)
+        try:
+            self._launch_fork(src, dst, lens)
+        except BaseException:
+            self.pt.rollback_fork(children)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
+            raise
+        return children
+
+    def _launch_fork(self, src, dst, lens) -> None:
+        """The children's table rows, then the one launch.  Everything the device needs goes up in ONE small copy - the three arrays of
+        the call, and (child's slot, entry, page) of every open block - and the rows are made on the device: the parent's row, which
+        names the shared pages, with the child's own page put in at the open block (entries beyond a length are read by nothing)."""
+        pairs = [(s, d, n) for s, d, n in zip(src, dst, lens) if n]
+        if not pairs:
+            return
+        src, dst, lens = (list(x) for x in zip(*pairs))
+        n = len(pairs)
+        own = [(d, t // PAGE_KEYS, self.pt.table[d][t // PAGE_KEYS]) for d, t in zip(dst, lens) if t % PAGE_KEYS]
+        pad = [0] * (n - len(own))
+        meta = torch.tensor([src, dst, lens] + [[x[i] for x in own] + pad for i in range(3)], dtype=torch.int32).to(self.device)
+        idx = meta.long()
+        self.table.index_copy_(0, idx[1], self.table.index_select(0, idx[0]))
+        if own:
+            k = len(own)
+            self.table.index_put_((idx[3, :k], idx[4, :k]), meta[5, :k])
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lqer_kv_pool_fork(self.buf.data_ptr(), self.buf.numel(), ops._DT[self.dtype], self.pt.num_pages, self.pt.max_seqs,
+                                                    self.kv_heads, self.head_dim, self.table.data_ptr(), self.pt.max_pages_per_seq,
+                                                    meta[0].data_ptr(), meta[1].data_ptr(), meta[2].data_ptr(), n, ops._stream(self.device)),
+                       "lqer_kv_pool_fork")
+
+    @torch.no_grad()
+    def reorder(self, seqs, parent_idx) -> list:
+        """The beam step: the ids of the new beams, beam i continuing seqs[parent_idx[i]].  The first beam that continues a parent
+        keeps the parent's id and nothing is copied; further ones are forks (one launch for all of them); parents nobody continues
+        are freed - before pages are taken, so their pages can serve the forks.  A pure permutation launches nothing and takes no
+        page.  A call the pool cannot serve raises RuntimeError with the pool and the books as they were, and so does one the library
+        refuses."""
+        seqs, parent_idx = list(seqs), [int(j) for j in parent_idx]
+        self.pt.slots(seqs)
+        if any(not 0 <= j < len(seqs) for j in parent_idx):
+            raise ValueError(f"PagedKVCache.reorder: parent_idx {parent_idx} for {len(seqs)} sequences")
+        out, forks, kept = [], [], set()
+        for j in parent_idx:
+            out.append(None if j in kept else seqs[j])
+            if j in kept:
+                forks.append(seqs[j])
+            kept.add(j)
+        dropped = [s for j, s in enumerate(seqs) if j not in kept]
+        if not forks and not dropped:
+            return out
+        snap = self.pt.snapshot(dropped)
+        try:
+            for s in dropped:
+                self.pt.free(s)
+            children = iter(self.fork_many(forks))  # (out of slots or pages: raises with nothing taken)
+        except BaseException:
+            self.pt.restore(snap)
+            for s, row in snap[-1].items():  # the freed sequences' device rows, which a child may have taken
+                self.table[s].copy_(torch.tensor(row, dtype=torch.int32))
+            raise
+        return [next(children) if s is None else s for s in out]
+
+    pages_shared = property(lambda self: self.pt.pages_shared)
 
     @torch.no_grad()
     def to_dense(self, seq: int) -> QuantizedKVCache:
