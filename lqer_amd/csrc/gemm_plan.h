@@ -1,5 +1,5 @@
 // The launch plan of the fused GEMM: what runs for a (descriptor, token count, element type) - computed once, by one pure function
-// (gemm_plan.hip), read by the launches (gemm_w4a8*.hip, gemm_smallm.hip) and by the public queries (api.hip).
+// (gemm_plan.hip), read by the launches (gemm_launch.hip, bout_amax.hip, gemm_w4a8*.hip, gemm_smallm.hip) and by the public queries (api.hip).
 #pragma once
 #include "common.h"
 
@@ -62,7 +62,8 @@ int device_cus();  // CUs of the current device (gemm_w4a8_i8.hip: the one HIP q
 
 // fills the plan's share of the kernel arguments (tiles, B_out blocks, segments), checks the scratch, runs the pre-pass or draws the
 // exchange tag, and launches the route's kernel
-int gemm_launch(const GemmPlan& p, GemmArgs g, int dtype, void* scratch, size_t scratch_bytes, bool amax_zeroed, hipStream_t st);
+int gemm_launch(const GemmPlan& p, GemmArgs g, int dtype, void* scratch, size_t scratch_bytes, bool amax_zeroed, hipStream_t st);  // gemm_launch.hip
+int launch_amax(const GemmPlan& p, const GemmArgs& g, bool amax_zeroed, hipStream_t st);  // bout_amax.hip: zero fill (unless done) + pre-pass
 int tile128_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st);  // gemm_w4a8.hip
 int m256_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st);     // gemm_w4a8_m256.hip
 int i8_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st);       // gemm_w4a8_i8.hip

@@ -27,10 +27,14 @@
 //  * the two waves of a SIMD run half a k-step apart (LOAD / COMPUTE ping-pong, see the main loop).
 //  * tiles are numbered so that each of the 8 XCDs works on a contiguous run of tiles (same token
 //    rows -> the activation slab stays in that XCD's L2).
-#include <atomic>
+//
+// This file holds the 128- and 64-row kernel and its launch.  What it shares with the other tile kernels is in gemm_tile.h; the
+// pre-pass for B_out blocks other than 16 in bout_amax.hip; the dispatcher of all four routes in gemm_launch.hip.
 #include <type_traits>
+#include <utility>
 
 #include "gemm_plan.h"
+#include "gemm_tile.h"
 
 namespace lqer {
 
@@ -44,20 +48,6 @@ constexpr int OFF_A = 0;
 // per tile height (MT 32-row tiles): activation slot 16 KiB (128 rows) or 8 KiB (64 rows), bf16; the panels behind the ring
 constexpr int a_slot_bytes(int mt) { return 32 * mt * BK * 2; }
 constexpr int gemm_lds_bytes(int mt) { return NSLOT * a_slot_bytes(mt) + NSLOT * R_SLOT; }  // 102400 B / 69632 B (two workgroups per CU)
-
-// byte offset of 16-byte chunk `c` (8 bf16 along k) of tile row `r`; rows are 128 B.
-// chunk ^ ((row >> 1) & 7): the 16 lanes of a ds_read_b128 group then hit 16 distinct 16-B slots.
-__device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-// max over lanes l and l^32
-__device__ __forceinline__ float pair32_max(float v) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
 
 // ---- LDS access in inline asm -------------------------------------------------------------------
 // hipcc's waitcnt pass treats every global_load_lds in flight as a pending LDS write and puts
@@ -163,13 +153,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cp_rin)::"memory");
 #endif
 
-  // XCD-aware tile order: blocks b, b+8, ... share an XCD; give each XCD a contiguous tile range.
-  const int nt = g.tiles_m * g.tiles_n;
-  int tile;
-  {
-    const int b = blockIdx.x, xcd = b & 7, q8 = nt >> 3, r8 = nt & 7;
-    tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BMk, n0 = tn * BN;
   const int nk = g.Kp / BK;
@@ -186,17 +170,11 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     const int chunk = (lane & 7) ^ ((row >> 1) & 7);
     a_voff[i] = (row * g.Kp + chunk * 8) * 2;
   }
-  // weights: the 16 panels of a k-step (16 x 576 B) are contiguous in the ring slot and are filled by nine 1-KiB
-  // LDS-DMAs with per-lane source offsets (576 = 36 x 16: a lane's 16 bytes lie inside one panel): wave w issues
-  // piece w, wave 0 also piece 8 - 25 LDS-DMA instructions per k-step and workgroup, all with full EXEC.
+  // weights: nine 1-KiB pieces per k-step (gemm_tile.h w_piece_voff): wave w issues piece w, wave 0 also piece 8 -
+  // 25 LDS-DMA instructions per k-step and workgroup, all with full EXEC.
   const uint8_t* w_base = g.wp + ((int64_t)(n0 / 16) * nk) * LQER_PANEL_BYTES;
   const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, 16 * nk * LQER_PANEL_BYTES, 0x00020000);
-  auto w_piece_voff = [&](int piece) {
-    const int byte = piece * 1024 + lane * 16;
-    const int pnl = byte / LQER_PANEL_BYTES;
-    return pnl * nk * LQER_PANEL_BYTES + (byte - pnl * LQER_PANEL_BYTES);
-  };
-  const int w_voff = w_piece_voff(wave), w_voff8 = w_piece_voff(8);
+  const int w_voff = w_piece_voff(wave, lane, nk), w_voff8 = w_piece_voff(8, lane, nk);
   unsigned char* const a_dst0 = smem + OFF_A + wave * (8 * AP) * 128;  // + slot * A_SLOT + piece * 1024
   unsigned char* const w_dst0 = smem + OFF_R + wave * 1024;      // + slot * R_SLOT
   auto issue_loads = [&](int kt, int slot) {  // 3 LDS-DMA instructions per wave (wave 0: 4)
@@ -392,7 +370,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   if (g.bias) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      const float bv = g.bias[n0 + wn * 32 + (k & 3) + 8 * (k >> 2) + 4 * lh];
+      const float bv = g.bias[acc_col(n0 + wn * 32, k, lh)];
 #pragma unroll
       for (int i = 0; i < MT; ++i) acc[i][k] += bv;
     }
@@ -426,16 +404,11 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
 #endif
-  // hand-built buffer descriptors for the in-asm LDS-DMA (wave-uniform words).  Exact ranges: every step issues its
-  // prefetch, also past the end of K - those lanes read inside the tile's rows or are dropped by the range check
-  const unsigned long long a_base64 = (unsigned long long)(g.xq + (int64_t)m0 * g.Kp);
-  const unsigned long long w_base64 = (unsigned long long)w_base;
-  const u32x4 a_rs = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a_base64),
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a_base64 >> 32)) & 0xffffu,
-                      (uint32_t)(BMk * g.Kp * 2), 0x00020000u};
-  const u32x4 w_rs = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w_base64),
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w_base64 >> 32)) & 0xffffu,
-                      (uint32_t)(16 * nk * LQER_PANEL_BYTES), 0x00020000u};
+  // hand-built buffer descriptors for the in-asm LDS-DMA (gemm_tile.h ring_rsrc_base): the tile's rows of xq, the column tile's panels
+  const u32x2 a_rs01 = ring_rsrc_base(g.xq + (int64_t)m0 * g.Kp);
+  const u32x4 a_rs = {a_rs01[0], a_rs01[1], (uint32_t)(BMk * g.Kp * 2), 0x00020000u};
+  const u32x2 w_rs01 = ring_rsrc_base(w_base);
+  const u32x4 w_rs = {w_rs01[0], w_rs01[1], (uint32_t)(16 * nk * LQER_PANEL_BYTES), 0x00020000u};
   const uint32_t m0_a = lds0 + OFF_A + wave * (8 * AP) * 128;  // + slot * A_SLOT (+ 1024: second piece)
   const uint32_t m0_w = lds0 + OFF_R + wave * 1024;      // + slot * R_SLOT
   const uint32_t m0_w8 = lds0 + OFF_R + 8192;            // + slot * R_SLOT (piece 8, wave 0)
@@ -509,19 +482,13 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     if constexpr (MT == 4) {
       asm volatile(
           "ds_read_b128 %0, %18 offset:%c25\n\tds_read_b32 %1, %19 offset:%c25+512\n\t"
-          "ds_read_b128 %2, %20 offset:%c24\n\tds_read_b128 %3, %20 offset:%c24+4096\n\t"
-          "ds_read_b128 %4, %20 offset:%c24+8192\n\tds_read_b128 %5, %20 offset:%c24+12288\n\t"
-          "ds_read_b128 %6, %21 offset:%c24\n\tds_read_b128 %7, %21 offset:%c24+4096\n\t"
-          "ds_read_b128 %8, %21 offset:%c24+8192\n\tds_read_b128 %9, %21 offset:%c24+12288\n\t"
-          "ds_read_b128 %10, %22 offset:%c24\n\tds_read_b128 %11, %22 offset:%c24+4096\n\t"
-          "ds_read_b128 %12, %22 offset:%c24+8192\n\tds_read_b128 %13, %22 offset:%c24+12288\n\t"
-          "ds_read_b128 %14, %23 offset:%c24\n\tds_read_b128 %15, %23 offset:%c24+4096\n\t"
-          "ds_read_b128 %16, %23 offset:%c24+8192\n\tds_read_b128 %17, %23 offset:%c24+12288\n\t"
-          "s_mov_b32 m0, %32\n\ts_nop 0\n\tbuffer_load_dwordx4 %26, %30, %36 offen lds\n\t"
-          "s_mov_b32 m0, %33\n\ts_nop 0\n\tbuffer_load_dwordx4 %27, %30, %36 offen lds\n\t"
-          "s_mov_b32 m0, %34\n\ts_nop 0\n\tbuffer_load_dwordx4 %28, %31, %37 offen lds\n\t"
+          LQER_READ_X2("%2", "%3", "%20", "%c24") LQER_READ_X2("%4", "%5", "%20", "%c24+8192")
+          LQER_READ_X2("%6", "%7", "%21", "%c24") LQER_READ_X2("%8", "%9", "%21", "%c24+8192")
+          LQER_READ_X2("%10", "%11", "%22", "%c24") LQER_READ_X2("%12", "%13", "%22", "%c24+8192")
+          LQER_READ_X2("%14", "%15", "%23", "%c24") LQER_READ_X2("%16", "%17", "%23", "%c24+8192")
+          LQER_LDS_DMA("%32", "%26", "%30", "%36") LQER_LDS_DMA("%33", "%27", "%30", "%36") LQER_LDS_DMA("%34", "%28", "%31", "%37")
           "s_cmp_lg_u32 %38, 0\n\ts_cbranch_scc1 1f\n\t"
-          "s_mov_b32 m0, %35\n\ts_nop 0\n\tbuffer_load_dwordx4 %29, %31, %37 offen lds\n\t"
+          LQER_LDS_DMA("%35", "%29", "%31", "%37")
           // own loads of step kt+1 landed: the batches of kt+2 and kt+3 (3 loads each, wave 0: 4 - it waits a little
           // more than it must) may stay in flight
           "1:\n\ts_waitcnt vmcnt(6) lgkmcnt(0)"
@@ -536,14 +503,11 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     } else {  // 64-row tile: two m tiles per k slice, one activation piece per wave
       asm volatile(
           "ds_read_b128 %0, %10 offset:%c17\n\tds_read_b32 %1, %11 offset:%c17+512\n\t"
-          "ds_read_b128 %2, %12 offset:%c16\n\tds_read_b128 %3, %12 offset:%c16+4096\n\t"
-          "ds_read_b128 %4, %13 offset:%c16\n\tds_read_b128 %5, %13 offset:%c16+4096\n\t"
-          "ds_read_b128 %6, %14 offset:%c16\n\tds_read_b128 %7, %14 offset:%c16+4096\n\t"
-          "ds_read_b128 %8, %15 offset:%c16\n\tds_read_b128 %9, %15 offset:%c16+4096\n\t"
-          "s_mov_b32 m0, %23\n\ts_nop 0\n\tbuffer_load_dwordx4 %18, %21, %26 offen lds\n\t"
-          "s_mov_b32 m0, %24\n\ts_nop 0\n\tbuffer_load_dwordx4 %19, %22, %27 offen lds\n\t"
+          LQER_READ_X2("%2", "%3", "%12", "%c16") LQER_READ_X2("%4", "%5", "%13", "%c16")
+          LQER_READ_X2("%6", "%7", "%14", "%c16") LQER_READ_X2("%8", "%9", "%15", "%c16")
+          LQER_LDS_DMA("%23", "%18", "%21", "%26") LQER_LDS_DMA("%24", "%19", "%22", "%27")
           "s_cmp_lg_u32 %28, 0\n\ts_cbranch_scc1 1f\n\t"
-          "s_mov_b32 m0, %25\n\ts_nop 0\n\tbuffer_load_dwordx4 %20, %22, %27 offen lds\n\t"
+          LQER_LDS_DMA("%25", "%20", "%22", "%27")
           "1:\n\ts_waitcnt vmcnt(4) lgkmcnt(0)"
           : "=&v"(wr), "=&v"(we), "=&v"(xa[0][0]), "=&v"(xa[0][1]), "=&v"(xa[1][0]), "=&v"(xa[1][1]), "=&v"(xa[2][0]),
             "=&v"(xa[2][1]), "=&v"(xa[3][0]), "=&v"(xa[3][1])
@@ -713,288 +677,50 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 #endif
 }
 
-// Pre-pass for B_out blocks other than 16 columns: max |xAq @ B| over every (token row, block of L columns),
-// L a multiple of 16.  One wave = one 32 x 32 tile of the product (same MFMA orientation as the GEMM
-// prologue); the per-16-column maxima are folded into amax[m][n / L] with atomicMax on the fp32 bit pattern
-// (non-negative floats order like unsigned integers; max is order-independent, so the result is
-// reproducible).  The buffer is zeroed on the stream before this kernel.
-// RG 32-row groups per wave (every B^T fragment feeds RG MFMAs), NKS 16-deep slices of the padded rank (exact: no per-slice branch).
-// Round 3: the kernel was a chain of load -> vmcnt(0) -> 4 MFMAs per slice (a branch per slice kept hipcc from batching the
-// loads; 228 registers: two waves per SIMD) - a third of its MFMA time.  Now a (column tile, limb) BATCH of NKS fragments is
-// requested one batch ahead of the MFMAs that consume it (two named register sets), the first MFMA of a tile takes a literal
-// zero accumulator, and a lane keeps one running maximum per row group (every register of its accumulator is the same token
-// row), folded with v_max3_f32; the lane pair is combined once, at the commit.
-template <int RG, int NKS>
-__global__ __launch_bounds__(256) void k_bout_amax(GemmArgs g, int tiles_n32, int seg_tiles) {
-  // One wave = 32 RG token rows x a run of `seg_tiles` 32-column tiles: the rows' xAq fragments stay in registers, the
-  // running maximum of the current B_out block stays in a register and is committed (one atomicMax per row) when
-  // the run leaves the block - a handful of atomics per row instead of one per 16 columns.
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t groups = ((g.M + 31) / 32 + RG - 1) / RG;
-  const int nseg = (tiles_n32 + seg_tiles - 1) / seg_tiles;
-  if (wid >= groups * nseg) return;
-  const int tg = (int)(wid / nseg), sg = (int)(wid - (int64_t)tg * nseg);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int Mp = (g.M + LQER_M_ALIGN - 1) / LQER_M_ALIGN * LQER_M_ALIGN;  // rows of xaq / bout_amax that exist
-  bf16x8 xa[RG][NKS];
-  int rowv[RG];
-#pragma unroll
-  for (int u = 0; u < RG; ++u) {
-    const int row = (tg * RG + u) * 32 + l31;
-    rowv[u] = row < Mp ? row : -1;
-    const int rc = row < Mp ? row : Mp - 1;  // (a clamped duplicate: computed, never committed)
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) xa[u][ks] = *(const bf16x8*)(g.xaq + (int64_t)rc * g.xaq_ld + ks * 16 + 8 * lh);
-  }
-  const int t_begin = sg * seg_tiles;
-  const int t_end = t_begin + seg_tiles < tiles_n32 ? t_begin + seg_tiles : tiles_n32;
-  int cur_blk = (t_begin * 32) / g.bout_L;
-  float cur[RG];
-#pragma unroll
-  for (int u = 0; u < RG; ++u) cur[u] = 0.f;
-  auto commit = [&]() {
-#pragma unroll
-    for (int u = 0; u < RG; ++u) {
-      const float m = pair32_max(cur[u]);  // lanes l and l ^ 32 hold the two column halves of the same token row
-      if (lh == 0 && rowv[u] >= 0) {
-        if (g.bout_nseg > 0) g.bout_amax[(int64_t)sg * Mp + rowv[u]] = m;  // one block per row: this segment's partial (plain store)
-        else atomicMax((unsigned int*)g.bout_amax + (int64_t)rowv[u] * g.bout_nblk + cur_blk, __float_as_uint(m));
-      }
-    }
-  };
-  const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const int nb = (t_end - t_begin) * g.b_limbs;  // batches: (tile, limb), limb fastest - the GEMM kernels' summation order
-  const int64_t limb_stride = (int64_t)g.Np * g.rp;
-  const bf16_t* const b_lane = g.bt + (int64_t)l31 * g.rp + 8 * lh;
-  bf16x8 ba[NKS], bb[NKS];
-  auto load = [&](int i, bf16x8 (&dst)[NKS]) {  // batch i (past the end: the last one again - never used)
-    const int ii = i < nb ? i : nb - 1;
-    const int tn = t_begin + ii / g.b_limbs, l = ii - (ii / g.b_limbs) * g.b_limbs;
-    const bf16_t* p = b_lane + l * limb_stride + (int64_t)tn * 32 * g.rp;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) dst[ks] = *(const bf16x8*)(p + ks * 16);
-  };
-  f32x16 acc[RG];
-  int tn = t_begin, l = 0;
-  auto consume = [&](const bf16x8 (&src)[NKS]) {
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      if (l == 0 && ks == 0) {
-#pragma unroll
-        for (int u = 0; u < RG; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(src[0], xa[u][0], zero, 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int u = 0; u < RG; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(src[ks], xa[u][ks], acc[u], 0, 0, 0);
-      }
-    }
-    if (++l == g.b_limbs) {  // the tile's product is complete: fold it into the running maxima
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int blk = (tn * 32 + 16 * b) / g.bout_L;  // wave-uniform
-        if (blk != cur_blk) {
-          commit();
-          cur_blk = blk;
-#pragma unroll
-          for (int u = 0; u < RG; ++u) cur[u] = 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < RG; ++u) {
-          float m = cur[u];
-#pragma unroll
-          for (int k = 0; k < 8; k += 2) m = fmaxf(fmaxf(m, fabsf(acc[u][8 * b + k])), fabsf(acc[u][8 * b + k + 1]));  // v_max3_f32 |.|
-          cur[u] = m;
-        }
-      }
-      l = 0, ++tn;
-    }
-  };
-  if (nb > 0) load(0, ba);
-  for (int i = 0; i < nb; i += 2) {
-    load(i + 1, bb);
-    consume(ba);
-    if (i + 1 >= nb) break;
-    load(i + 2, ba);
-    consume(bb);
-  }
-  commit();
+// The instantiations of the tile kernel that exist - the variants the plan can ask for (gemm_plan.hip), per element type:
+template <int DT, bool LR, int BO, bool ST, int MT, bool WTWOS, bool DEFER, bool WMF>
+constexpr bool tile_variant_exists() {
+  constexpr bool nibbles = WTWOS || WMF;
+  if (WTWOS && WMF) return false;
+  // integer / minifloat nibbles, minifloat B_out: 128-row tiles, and no fp16 main loop beside them (the plan refuses)
+  if ((nibbles || BO == 3) && (MT != 4 || DT == LQER_F16X)) return false;
+  if (!LR) return BO == 0 && !ST && !DEFER;  // no side path: nothing of it to choose
+  if (nibbles) return ST && !DEFER;          // beside integer / minifloat nibbles the side path is always staged
+  if (DEFER) return BO == 1 && MT == 4;      // blocks of 16 under the main loop of the 128-row tile
+  return true;                               // B_out 0 .. 3, direct or staged, 128- or 64-row tiles
 }
 
-// The same pre-pass with the B^T fragments through LDS, for rank 64 (the W4A8 INT configurations).  Counters of k_bout_amax<4, 4>
-// at C4 (tools/r03_sidepmc.sh): the texture addresser is busy 62 % of the kernel, the MFMA pipe 30 % - every wave fetches its own
-// copy of the B^T run, 32 lanes x 128-byte rows per request.  Here the four waves of a workgroup take four different groups of
-// 128 token rows over the SAME run of column tiles: a stage of AMX_SB (tile, limb) batches - 4 KB each, contiguous in the B^T
-// image - is read once per workgroup with one 16-byte request per thread and batch (16 lanes per 256-byte line), swizzled into
-// LDS (two stage buffers, one barrier per stage), and every wave reads its fragments from there.  Same maxima (max is
-// order-independent), same commit.
-constexpr int AMX_SB = 4;
-__global__ __launch_bounds__(256) void k_bout_amax_lds(GemmArgs g, int tiles_n32, int seg_tiles) {
-  constexpr int RG = 4, NKS = 4;
-  __shared__ __attribute__((aligned(16))) unsigned char sbuf[2][AMX_SB][4096];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int64_t groups = ((g.M + 31) / 32 + RG - 1) / RG;
-  const int nseg = (tiles_n32 + seg_tiles - 1) / seg_tiles;
-  const int wgr = (int)(blockIdx.x / nseg), sg = (int)(blockIdx.x - (int64_t)wgr * nseg);
-  const int64_t tg_raw = (int64_t)wgr * 4 + wave;
-  const bool live = tg_raw < groups;               // (a wave past the last row group still stages and meets the barriers)
-  const int tg = (int)(live ? tg_raw : groups - 1);
-  const int Mp = (g.M + LQER_M_ALIGN - 1) / LQER_M_ALIGN * LQER_M_ALIGN;
-  bf16x8 xa[RG][NKS];
-  int rowv[RG];
-#pragma unroll
-  for (int u = 0; u < RG; ++u) {
-    const int row = (tg * RG + u) * 32 + l31;
-    rowv[u] = live && row < Mp ? row : -1;
-    const int rc = row < Mp ? row : Mp - 1;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) xa[u][ks] = *(const bf16x8*)(g.xaq + (int64_t)rc * g.xaq_ld + ks * 16 + 8 * lh);
+// variant I, its bits as in launch_tile's key: launched if it exists and is the plan's
+template <int DT, int I>
+static bool run_tile(int key, const GemmPlan& p, const GemmArgs& g, hipStream_t st, int& rc) {
+  constexpr bool LR = I & 1, ST = I & 2, WTWOS = I & 8, DEFER = I & 16, WMF = I & 32;
+  constexpr int MT = I & 4 ? 2 : 4, BO = I >> 6;
+  if constexpr (tile_variant_exists<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>()) {
+    if (key == I) {
+      rc = launch_k<k_lqer_gemm<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>>("lqer_gemm", p.grid, 512, gemm_lds_bytes(MT), st, g);
+      return true;
+    }
   }
-  const int t_begin = sg * seg_tiles;
-  const int t_end = t_begin + seg_tiles < tiles_n32 ? t_begin + seg_tiles : tiles_n32;
-  int cur_blk = (t_begin * 32) / g.bout_L;
-  float cur[RG];
-#pragma unroll
-  for (int u = 0; u < RG; ++u) cur[u] = 0.f;
-  auto commit = [&]() {
-#pragma unroll
-    for (int u = 0; u < RG; ++u) {
-      const float m = pair32_max(cur[u]);
-      if (lh == 0 && rowv[u] >= 0) {
-        if (g.bout_nseg > 0) g.bout_amax[(int64_t)sg * Mp + rowv[u]] = m;
-        else atomicMax((unsigned int*)g.bout_amax + (int64_t)rowv[u] * g.bout_nblk + cur_blk, __float_as_uint(m));
-      }
-    }
-  };
-  const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const int nb = (t_end - t_begin) * g.b_limbs;  // batches (tile, limb), limb fastest
-  const int nst = (nb + AMX_SB - 1) / AMX_SB;
-  const int64_t limb_stride = (int64_t)g.Np * g.rp;
-  // staging: thread t moves 16-byte chunk t of a batch's 4 KB (row t / 8 of the tile, chunk t % 8 of its 128 B) to the swizzled slot
-  const int srow = tid >> 3, sch = tid & 7;
-  const int sdst = srow * 128 + ((sch ^ (srow & 7)) << 4);
-  u32x4 st[AMX_SB];
-  auto gload = [&](int s) {
-#pragma unroll
-    for (int u = 0; u < AMX_SB; ++u) {
-      const int i = s * AMX_SB + u, ii = i < nb ? i : nb - 1;  // (past the end: the last batch again, never consumed)
-      const int tn = t_begin + ii / g.b_limbs, l = ii - (ii / g.b_limbs) * g.b_limbs;
-      st[u] = *(const u32x4*)(g.bt + l * limb_stride + (int64_t)tn * 32 * g.rp + tid * 8);
-    }
-  };
-  auto lwrite = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < AMX_SB; ++u) *(u32x4*)(&sbuf[buf][u][sdst]) = st[u];
-  };
-  int fo[NKS];  // fragment offsets inside a batch: row l31, chunk 2 ks + lh
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) fo[ks] = l31 * 128 + (((2 * ks + lh) ^ (l31 & 7)) << 4);
-  f32x16 acc[RG];
-  int tn = t_begin, l = 0;
-  gload(0);
-  lwrite(0);
-  __syncthreads();
-  for (int s = 0; s < nst; ++s) {
-    if (s + 1 < nst) gload(s + 1);
-    const int buf = s & 1;
-#pragma unroll
-    for (int u2 = 0; u2 < AMX_SB; ++u2) {
-      if (s * AMX_SB + u2 < nb) {
-        bf16x8 fr[NKS];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) fr[ks] = *(const bf16x8*)(&sbuf[buf][u2][fo[ks]]);
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-          if (l == 0 && ks == 0) {
-#pragma unroll
-            for (int u = 0; u < RG; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[0], xa[u][0], zero, 0, 0, 0);
-          } else {
-#pragma unroll
-            for (int u = 0; u < RG; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[ks], xa[u][ks], acc[u], 0, 0, 0);
-          }
-        }
-        if (++l == g.b_limbs) {
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            const int blk = (tn * 32 + 16 * b) / g.bout_L;  // wave-uniform
-            if (blk != cur_blk) {
-              commit();
-              cur_blk = blk;
-#pragma unroll
-              for (int u = 0; u < RG; ++u) cur[u] = 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < RG; ++u) {
-              float m = cur[u];
-#pragma unroll
-              for (int k = 0; k < 8; k += 2) m = fmaxf(fmaxf(m, fabsf(acc[u][8 * b + k])), fabsf(acc[u][8 * b + k + 1]));
-              cur[u] = m;
-            }
-          }
-          l = 0, ++tn;
-        }
-      }
-    }
-    if (s + 1 < nst) lwrite(buf ^ 1);  // (everybody left that buffer before the previous barrier)
-    __syncthreads();
-  }
-  commit();
+  return false;
 }
 
-// One instantiation of the tile kernel per (element type, side path, B_out, ...): MT = 4 the 128-row tile, 2 the 64-row one.
-template <int DT, bool LR, int BO, bool ST = false, int MT = 4, bool WTWOS = false, bool DEFER = false, bool WMF = false>
-static int run_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
-  return launch_k<k_lqer_gemm<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>>("lqer_gemm", p.grid, 512, gemm_lds_bytes(MT), st, g);
-}
-
-// the plan's variant -> the instantiation (only those listed here exist)
-template <int DT>
-static int launch_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
-  const bool S = p.staged;
-  if constexpr (DT != LQER_F16X) {  // (no fp16 main loop beside integer / minifloat nibbles or a minifloat B_out: the plan refuses)
-    if (p.w_mf) {  // minifloat weights: 128-row tiles, the staged side path
-      if (!p.lowrank) return run_tile<DT, false, 0, false, 4, false, false, true>(p, g, st);
-      switch (p.bout) {
-        case 1: return run_tile<DT, true, 1, true, 4, false, false, true>(p, g, st);
-        case 2: return run_tile<DT, true, 2, true, 4, false, false, true>(p, g, st);
-        case 3: return run_tile<DT, true, 3, true, 4, false, false, true>(p, g, st);
-        default: return run_tile<DT, true, 0, true, 4, false, false, true>(p, g, st);
-      }
-    }
-    if (p.w_twos) {  // integer weights: the same
-      if (!p.lowrank) return run_tile<DT, false, 0, false, 4, true>(p, g, st);
-      switch (p.bout) {
-        case 1: return run_tile<DT, true, 1, true, 4, true>(p, g, st);
-        case 2: return run_tile<DT, true, 2, true, 4, true>(p, g, st);
-        case 3: return run_tile<DT, true, 3, true, 4, true>(p, g, st);
-        default: return run_tile<DT, true, 0, true, 4, true>(p, g, st);
-      }
-    }
-    if (p.bout == 3) return S ? run_tile<DT, true, 3, true>(p, g, st) : run_tile<DT, true, 3, false>(p, g, st);  // minifloat B_out
-  }
-  if (p.tile_rows == 64) {  // (the 128-row grid would fill at most half of the CUs)
-    if (!p.lowrank) return run_tile<DT, false, 0, false, 2>(p, g, st);
-    switch (p.bout) {
-      case 1: return S ? run_tile<DT, true, 1, true, 2>(p, g, st) : run_tile<DT, true, 1, false, 2>(p, g, st);
-      case 2: return S ? run_tile<DT, true, 2, true, 2>(p, g, st) : run_tile<DT, true, 2, false, 2>(p, g, st);
-      default: return S ? run_tile<DT, true, 0, true, 2>(p, g, st) : run_tile<DT, true, 0, false, 2>(p, g, st);
-    }
-  }
-  if (!p.lowrank) return run_tile<DT, false, 0>(p, g, st);
-  if (p.defer) return S ? run_tile<DT, true, 1, true, 4, false, true>(p, g, st) : run_tile<DT, true, 1, false, 4, false, true>(p, g, st);
-  switch (p.bout) {
-    case 1: return S ? run_tile<DT, true, 1, true>(p, g, st) : run_tile<DT, true, 1>(p, g, st);
-    case 2: return S ? run_tile<DT, true, 2, true>(p, g, st) : run_tile<DT, true, 2>(p, g, st);
-    default: return S ? run_tile<DT, true, 0, true>(p, g, st) : run_tile<DT, true, 0>(p, g, st);
-  }
+// the plan's variant -> the instantiation
+template <int DT, int... I>
+static int launch_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st, std::integer_sequence<int, I...>) {
+  const int key = p.lowrank | p.staged << 1 | (p.tile_rows == 64) << 2 | p.w_twos << 3 | p.defer << 4 | p.w_mf << 5 | p.bout << 6;
+  int rc;
+  if ((run_tile<DT, I>(key, p, g, st, rc) || ...)) return rc;
+  set_error("linear_gemm: the plan asks for a tile kernel variant that does not exist (%#x)", key);
+  return LQER_E_UNSUPPORTED;
 }
 
 int tile128_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {
+  constexpr std::make_integer_sequence<int, 4 << 6> variants{};
   return with_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     if constexpr (DT == LQER_F16)
-      if (p.f16x) return launch_tile<LQER_F16X>(p, g, st);
-    return launch_tile<DT>(p, g, st);
+      if (p.f16x) return launch_tile<LQER_F16X>(p, g, st, variants);
+    return launch_tile<DT>(p, g, st, variants);
   });
 }
 
@@ -1003,100 +729,5 @@ extern "C" int lqer_debug_set_stamp_buffer(void* p) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &p, sizeof(p));
 }
 #endif
-
-size_t gemm_scratch_bytes(int64_t m_max, int64_t N, const QP& bout) {
-  if (bout.kind != LQER_Q_MXINT || bout.block == 16) return 0;
-  const int64_t Np = lqer_padded_n(N);
-  const int64_t L = (bout.block <= 0 || bout.block >= N) ? Np : bout.block;
-  const int64_t nblk = (Np + L - 1) / L;
-  // (one block per row on the int8 route: up to LQER_AMAX_NSEG column-segment partials per row instead of one atomic cell - or as
-  // many {value, tag} granules of 8 bytes when the GEMM exchanges the maxima itself)
-  return (size_t)lqer_padded_m(m_max) * (nblk == 1 ? 2 * LQER_AMAX_NSEG : nblk) * sizeof(float);
-}
-
-__global__ void k_zero_cells(uint32_t* p, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0u;
-}
-
-template <int RG, int NKS>
-static int run_amax(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
-  return launch_k<k_bout_amax<RG, NKS>>("lqer_gemm (B_out pre-pass)", p.pre.grid, 256, 0, st, g, p.pre.tiles_n32, p.pre.seg_tiles);
-}
-
-// the pre-pass of the plan: row groups per wave x 16-deep slices of the padded rank (only the pairs listed here exist)
-static int launch_amax(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
-  if (p.pre.lds)
-    return launch_k<k_bout_amax_lds>("lqer_gemm (B_out pre-pass)", p.pre.grid, 256, 0, st, g, p.pre.tiles_n32, p.pre.seg_tiles);
-  switch (p.pre.rg * 32 + p.pre.nks) {
-    case 32 + 1: return run_amax<1, 1>(p, g, st);
-    case 64 + 1: return run_amax<2, 1>(p, g, st);
-    case 32 + 2: return run_amax<1, 2>(p, g, st);
-    case 64 + 2: return run_amax<2, 2>(p, g, st);
-    case 32 + 3: return run_amax<1, 3>(p, g, st);
-    case 64 + 3: return run_amax<2, 3>(p, g, st);
-    case 32 + 4: return run_amax<1, 4>(p, g, st);
-    case 64 + 4: return run_amax<2, 4>(p, g, st);
-    case 128 + 1: return run_amax<4, 1>(p, g, st);
-    case 128 + 2: return run_amax<4, 2>(p, g, st);
-    case 128 + 3: return run_amax<4, 3>(p, g, st);
-    case 128 + 4: return run_amax<4, 4>(p, g, st);
-    case 64 + 5: return run_amax<2, 5>(p, g, st);
-    case 64 + 6: return run_amax<2, 6>(p, g, st);
-    case 64 + 7: return run_amax<2, 7>(p, g, st);
-    case 64 + 8: return run_amax<2, 8>(p, g, st);
-    case 32 + 9: return run_amax<1, 9>(p, g, st);
-    case 32 + 10: return run_amax<1, 10>(p, g, st);
-    case 32 + 11: return run_amax<1, 11>(p, g, st);
-    case 32 + 12: return run_amax<1, 12>(p, g, st);
-    case 32 + 13: return run_amax<1, 13>(p, g, st);
-    case 32 + 14: return run_amax<1, 14>(p, g, st);
-    case 32 + 15: return run_amax<1, 15>(p, g, st);
-    case 32 + 16: return run_amax<1, 16>(p, g, st);
-  }
-  set_error("%s", p.msg);  // (plan_prepass refused: more slices than any instantiation has)
-  return p.launch_err;
-}
-
-int gemm_launch(const GemmPlan& p, GemmArgs g, int dtype, void* scratch, size_t scratch_bytes, bool amax_zeroed, hipStream_t st) {
-  if (p.empty) return LQER_OK;
-  if (p.err) {
-    set_error("%s", p.msg);
-    return p.err;
-  }
-  g.tiles_m = p.tiles_m, g.tiles_n = p.tiles_n;
-  if (p.bout == 2) g.bout_L = p.bout_L, g.bout_nblk = p.bout_nblk, g.bout_amax = nullptr, g.bout_nseg = p.pre.nseg;
-  if (p.amax != AMAX_NONE) {
-    if (!scratch || scratch_bytes < p.need) {
-      set_error("linear_gemm: scratch %zu B < %zu B for the B_out row-block maxima", scratch_bytes, p.need);
-      return LQER_E_WORKSPACE;
-    }
-    g.bout_amax = (float*)scratch;
-  }
-  if (p.amax == AMAX_XCH || p.amax == AMAX_MRX) {
-    // the call's tag: a counter spread over all 32 bits (odd multiplier: a bijection); the kernel mixes in its dispatch id and queue
-    static std::atomic<uint32_t> xch_calls{1};
-    g.xch_nonce = xch_calls.fetch_add(1, std::memory_order_relaxed) * 0x9E3779B1u;
-  } else if (p.amax != AMAX_NONE) {
-    // (amax_zeroed: the activation kernel of the same forward did it.  A kernel, not hipMemsetAsync: as a memset NODE of a captured graph
-    // the fill left two of every four cells untouched on replay - ROCm 7.2, tools/graph_replay_gemm.py - while the eager call was fine)
-    int rc = LQER_OK;
-    if (p.zero_bytes && !amax_zeroed)
-      rc = launch_k<k_zero_cells>("lqer_gemm (zero fill)", (unsigned)((p.zero_bytes / 4 + 255) / 256), 256, 0, st, (uint32_t*)scratch,
-                                  (int64_t)(p.zero_bytes / 4));
-    if (rc == LQER_OK) rc = launch_amax(p, g, st);
-    if (rc) return rc;
-  }
-  if (p.launch_err) {  // (behind the pre-pass, where these refusals have always been reported)
-    set_error("%s", p.msg);
-    return p.launch_err;
-  }
-  switch (p.route) {
-    case LQER_ROUTE_I8: return i8_launch(p, g, dtype, st);
-    case LQER_ROUTE_SMALLM: return smallm_launch(p, g, dtype, st);  // decode sizes: HBM-bound variant
-    case LQER_ROUTE_TILE256: return m256_launch(p, g, dtype, st);   // large M: 256 x 256 tiles
-    default: return tile128_launch(p, g, dtype, st);
-  }
-}
 
 }  // namespace lqer

@@ -51,6 +51,7 @@
 #include <type_traits>
 
 #include "gemm_plan.h"
+#include "gemm_tile.h"  // swz, lds_void, xcd_tile
 
 namespace lqer {
 
@@ -117,9 +118,6 @@ constexpr int XCH_GATHER_AUX = 1;
 // belongs to a workgroup that is not resident (another stream holds its CU): waiting longer than the fall-back costs (the band's side
 // products: tiles_n x 16 MFMAs, a few us) buys nothing, and every late tile paid the full bound
 constexpr int XCH_SWEEPS = 6;
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
 
 // the largest |acc[k]| of a 32 x 32 accumulator's row: this lane's 16 registers, then lanes l and l ^ 32 (which hold the row's other half)
 __device__ __forceinline__ float row_absmax(const f32x16& acc) {
@@ -422,11 +420,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_i8(GemmArgs g) {
                  "s"(g.tuning), "s"(g.bout.mbits), "s"(g.bout.emin), "s"(g.bout.emax));
   }
   const int nt = g.tiles_m * g.tiles_n;
-  // XCD-aware tile order of a virtual block id (blocks b, b + 8, ... share an XCD; the grid is a multiple of 8 or covers nt)
-  auto tile_of = [&](int b) {
-    const int xcd = b & 7, q8 = nt >> 3, r8 = nt & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-  };
+  auto tile_of = [&](int b) { return xcd_tile(b, nt); };  // of a virtual block id
   const int Kp8 = g.Kp;  // (the int8 image's row stride)
   const int nk = Kp8 / I8_BK;
   const uint8_t* const xq8 = (const uint8_t*)g.xq;

@@ -13,10 +13,12 @@
 // would not fit beside the accumulators: LOAD(h) reads the 16 activation fragments and the two code words of
 // half-step h, issues half of the step's prefetch (k-step + 2 into a 3-slot ring), waits, barrier; COMPUTE(h)
 // expands 2 weight fragments and issues 16 MFMAs, barrier.  The two waves of a SIMD run one barrier apart.
-// Used for shapes with at least two rounds of 256 x 256 tiles (plan_gemm).
+// Used for shapes with at least two rounds of 256 x 256 tiles (plan_gemm).  What the two kernels say in the same words - swizzle,
+// tile order, weight-piece offsets, descriptor base words, the text of the LOAD statements - is in gemm_tile.h.
 #include <type_traits>
 
 #include "gemm_plan.h"
+#include "gemm_tile.h"
 
 namespace lqer {
 
@@ -31,15 +33,6 @@ constexpr int OFF_A = 0;
 constexpr int OFF_R = NSLOT * A_SLOT;
 constexpr int GEMM_LDS = OFF_R + NSLOT * R_SLOT;      // 125952 B
 
-__device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ float pair32_max(float v) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
 template <int DT, bool LOWRANK, int BOUT>
 __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
   constexpr bool XF16 = DT == LQER_F16X;  // (gemm_w4a8.hip)
@@ -49,13 +42,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
   const int wn = wave;
   const int l31 = lane & 31, lh = lane >> 5;
 
-  // XCD-aware tile order: blocks b, b+8, ... share an XCD; give each XCD a contiguous tile range.
-  const int nt = g.tiles_m * g.tiles_n;
-  int tile;
-  {
-    const int b = blockIdx.x, xcd = b & 7, q8 = nt >> 3, r8 = nt & 7;
-    tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int nk = g.Kp / BK;
@@ -71,12 +58,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
   }
   const uint8_t* w_base = g.wp + ((int64_t)(n0 / 16) * nk) * LQER_PANEL_BYTES;
   const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, 0x7fffffff, 0x00020000);
-  auto w_piece_voff = [&](int piece) {
-    const int byte = piece * 1024 + lane * 16;
-    const int pnl = byte / LQER_PANEL_BYTES;
-    return pnl * nk * LQER_PANEL_BYTES + (byte - pnl * LQER_PANEL_BYTES);
-  };
-  const int w_voff = w_piece_voff(wave), w_voff8 = w_piece_voff(8);
+  const int w_voff = w_piece_voff(wave, lane, nk), w_voff8 = w_piece_voff(8, lane, nk);
   unsigned char* const a_dst0 = smem + OFF_A + wave * 32 * 128;  // + slot * A_SLOT + piece * 1024
   unsigned char* const w_dst0 = smem + OFF_R + wave * 1024;      // + slot * R_SLOT
   // half 0: activation pieces 0,1 + the wave's weight piece (3 loads); half 1: pieces 2,3 (+ wave 0: piece 8)
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
     }
     if (g.bias) {
 #pragma unroll
-      for (int k = 0; k < 16; ++k) t[k] += g.bias[n0 + wn * 32 + (k & 3) + 8 * (k >> 2) + 4 * lh];
+      for (int k = 0; k < 16; ++k) t[k] += g.bias[acc_col(n0 + wn * 32, k, lh)];
     }
     acc[i] = t;
   }
@@ -231,16 +213,11 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
   }
   if (late) asm volatile("s_barrier" ::: "memory");
-  // hand-built buffer descriptors for the in-asm LDS-DMA (wave-uniform words).  Exact ranges: every half-step issues
-  // its prefetch, also past the end of K - those lanes read inside the tile's rows or are dropped by the range check
-  const unsigned long long a_base = (unsigned long long)(g.xq + (int64_t)m0 * g.Kp);
-  const unsigned long long w_base64 = (unsigned long long)w_base;
-  const u32x4 a_rs = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a_base),
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a_base >> 32)) & 0xffffu,
-                      (uint32_t)(BM * g.Kp * 2), 0x00020000u};
-  const u32x4 w_rs = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w_base64),
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w_base64 >> 32)) & 0xffffu,
-                      (uint32_t)(16 * nk * LQER_PANEL_BYTES), 0x00020000u};
+  // hand-built buffer descriptors for the in-asm LDS-DMA (gemm_tile.h ring_rsrc_base): the tile's rows of xq, the column tile's panels
+  const u32x2 a_rs01 = ring_rsrc_base(g.xq + (int64_t)m0 * g.Kp);
+  const u32x4 a_rs = {a_rs01[0], a_rs01[1], (uint32_t)(BM * g.Kp * 2), 0x00020000u};
+  const u32x2 w_rs01 = ring_rsrc_base(w_base);
+  const u32x4 w_rs = {w_rs01[0], w_rs01[1], (uint32_t)(16 * nk * LQER_PANEL_BYTES), 0x00020000u};
   const uint32_t m0_a = lds0 + OFF_A + wave * 32 * 128;  // + slot * A_SLOT + piece * 1024
   const uint32_t m0_w = lds0 + OFF_R + wave * 1024;      // + slot * R_SLOT
   const uint32_t m0_w8 = lds0 + OFF_R + 8192;            // + slot * R_SLOT (piece 8, wave 0)
@@ -262,17 +239,12 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
     uint32_t we;
 #define LQER_READS                                                                                                  \
       "ds_read_b64 %0, %18 offset:%c23\n\tds_read_b32 %1, %19 offset:%c22+512\n\t"                                  \
-      "ds_read_b128 %2, %20\n\tds_read_b128 %3, %20 offset:4096\n\t"                                                \
-      "ds_read_b128 %4, %20 offset:8192\n\tds_read_b128 %5, %20 offset:12288\n\t"                                   \
-      "ds_read_b128 %6, %20 offset:16384\n\tds_read_b128 %7, %20 offset:20480\n\t"                                  \
-      "ds_read_b128 %8, %20 offset:24576\n\tds_read_b128 %9, %20 offset:28672\n\t"                                  \
-      "ds_read_b128 %10, %21\n\tds_read_b128 %11, %21 offset:4096\n\t"                                              \
-      "ds_read_b128 %12, %21 offset:8192\n\tds_read_b128 %13, %21 offset:12288\n\t"                                 \
-      "ds_read_b128 %14, %21 offset:16384\n\tds_read_b128 %15, %21 offset:20480\n\t"                                \
-      "ds_read_b128 %16, %21 offset:24576\n\tds_read_b128 %17, %21 offset:28672\n\t"
-#define LQER_DMA_A                                                                                                  \
-      "s_mov_b32 m0, %29\n\ts_nop 0\n\tbuffer_load_dwordx4 %24, %27, %31 offen lds\n\t"                             \
-      "s_mov_b32 m0, %30\n\ts_nop 0\n\tbuffer_load_dwordx4 %25, %27, %31 offen lds\n\t"
+      LQER_READ_X2("%2", "%3", "%20", "0") LQER_READ_X2("%4", "%5", "%20", "8192")                                  \
+      LQER_READ_X2("%6", "%7", "%20", "16384") LQER_READ_X2("%8", "%9", "%20", "24576")                             \
+      LQER_READ_X2("%10", "%11", "%21", "0") LQER_READ_X2("%12", "%13", "%21", "8192")                              \
+      LQER_READ_X2("%14", "%15", "%21", "16384") LQER_READ_X2("%16", "%17", "%21", "24576")
+#define LQER_DMA_A LQER_LDS_DMA("%29", "%24", "%27", "%31") LQER_LDS_DMA("%30", "%25", "%27", "%31")
+#define LQER_DMA_W LQER_LDS_DMA("%32", "%26", "%28", "%33")  // the wave's weight piece (half 0) / wave 0's piece 8 (half 1)
 #define LQER_OUTS                                                                                                   \
       "=&v"(wr), "=&v"(we), "=&v"(xa[0][0]), "=&v"(xa[0][1]), "=&v"(xa[0][2]), "=&v"(xa[0][3]), "=&v"(xa[0][4]),    \
       "=&v"(xa[0][5]), "=&v"(xa[0][6]), "=&v"(xa[0][7]), "=&v"(xa[1][0]), "=&v"(xa[1][1]), "=&v"(xa[1][2]),         \
@@ -284,8 +256,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
       "s"(a_rs), "s"(w_rs), "s"(m0a0), "s"(m0a1), "s"(a_soff), "s"(m0w), "s"(w_soff), "s"(wave) /* 27..34 */
     if constexpr (P == 0) {
       // within a step only this wave's LDS reads are waited for (vmcnt(15) never blocks: <= 11 loads are in flight)
-      asm volatile(LQER_READS LQER_DMA_A
-                   "s_mov_b32 m0, %32\n\ts_nop 0\n\tbuffer_load_dwordx4 %26, %28, %33 offen lds\n\t"
+      asm volatile(LQER_READS LQER_DMA_A LQER_DMA_W
                    "s_waitcnt vmcnt(15) lgkmcnt(0)"
                    : LQER_OUTS
                    : LQER_INS
@@ -294,7 +265,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
       // the next reads are of step kt+1: its loads have landed once only the 5 (wave 0: 6) of step kt+2 are in flight
       asm volatile(LQER_READS LQER_DMA_A
                    "s_cmp_lg_u32 %34, 0\n\ts_cbranch_scc1 1f\n\t"
-                   "s_mov_b32 m0, %32\n\ts_nop 0\n\tbuffer_load_dwordx4 %26, %28, %33 offen lds\n\t"
+                   LQER_DMA_W
                    "1:\n\ts_waitcnt vmcnt(5) lgkmcnt(0)"
                    : LQER_OUTS
                    : LQER_INS
@@ -302,6 +273,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm_m256(GemmArgs g) {
     }
 #undef LQER_READS
 #undef LQER_DMA_A
+#undef LQER_DMA_W
 #undef LQER_OUTS
 #undef LQER_INS
     auto scale_bits = [&](int j) { return ((we >> (8 * (2 * P + j))) & 0xffu) << 23; };  // exponent byte -> 2^(e - mbits)

@@ -9,7 +9,7 @@
 // product is exact in fp32; only the fp32 accumulation order differs from the reference's torch.matmul.
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_tile.h"  // lds_void
 
 namespace lqer {
 
@@ -279,7 +279,6 @@ __global__ __launch_bounds__(256) void k_xa_partial(const bf16_t* __restrict__ x
 namespace xal {
 constexpr int ROWS = 128, BKB = 128;  // token rows per workgroup, activation bytes per row and step
 constexpr int X_SLOT = ROWS * BKB;    // 16 KiB
-typedef __attribute__((address_space(3))) void lds_void;
 constexpr int a_row_bytes(bool i8) { return i8 ? 256 : 128; }
 #ifndef LQER_XAL_SLOTS
 #define LQER_XAL_SLOTS 3

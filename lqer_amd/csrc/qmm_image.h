@@ -4,15 +4,13 @@
 #pragma once
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_tile.h"  // swz: the operand tiles have the fused GEMM's swizzled LDS layout
 
 namespace lqer {
 
 namespace qmm {
 
 constexpr int BM = 128, BN = 128, BK = 64;
-
-__device__ __forceinline__ int swz(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
 
 // 16 consecutive elements (or fewer at the end of a row), 128-bit loads when the piece is aligned and complete
 template <int DT>

@@ -125,6 +125,34 @@ def test_128_row_tiles_behind_the_reduce_launch_match_the_oracle(lq, M, K, N, r,
     assert err <= (4e-3 if dtype == torch.bfloat16 else 1e-3), err
 
 
+@pytest.mark.parametrize("r,dtype", [(32, torch.float32), (48, torch.bfloat16)])
+def test_minifloat_b_out_on_128_row_tiles_matches_the_statement(lq, r, dtype):
+    """k_lqer_gemm<..., BOUT = 3>: a minifloat B_out (elementwise, in the prologue) beside block_fp x / w / A_out, side path direct
+    (rank 32) and staged (padded rank 48); two row tiles, the last ragged, two column tiles, the last ragged.  Against the
+    reference's formula with the minifloat quantizer of tests/_minifloat.py, at this file's bars."""
+    import ctypes as C
+
+    import _minifloat as MF
+    from bench import MXINT_Q, make_case
+    from lqer_amd import _lib
+
+    M, K, N = 130, 320, 272
+    qc = dict(MXINT_Q, B_out_quantizer=dict(name="minifloat", width=8, exponent_width=4, exponent_bias=10))
+    x, W, A, B, bvec = make_case(M, K, N, max(r, 16), seed=43, bias=True)[:5]
+    A, B = A[:, :r].contiguous(), B[:r].contiguous()
+    mod = lq.LinearFlexibleLqer(K, N, bias=True, q_config=qc, l_config={"rank": r})
+    mod.load_state_dict({"weight": W, "A": A, "B": B, "bias": bvec})
+    mod = mod.to(DEV).to(dtype)
+    y = mod(x.to(dtype).to(DEV)).float().cpu()
+    d = mod._desc()
+    dtc = _lib.F32 if dtype == torch.float32 else _lib.BF16
+    assert _lib.lib().lqer_gemm_route(C.byref(d), M, dtc) == _lib.ROUTE_TILE128 and _lib.lib().lqer_gemm_tile_rows(C.byref(d), M, dtc) == 128
+    h = lambda t: t.to(dtype).float()
+    ref = MF.linear_forward(h(x), h(W), h(bvec), h(A), h(B), qc)
+    err = float((y - ref).norm() / ref.norm())
+    assert err <= (4e-3 if dtype == torch.bfloat16 else 1e-3), err
+
+
 DEFER_CASES = [  # M, K, N, rank, bias, dtype
     (2048, 4096, 4096, 32, False, torch.float16),   # BASELINE configs[1]: the direct side path (two 16-deep slices)
     (300, 1024, 520, 20, True, torch.bfloat16),     # the shortest K that defers (16 k-steps), ragged M / N, padded rank, bias

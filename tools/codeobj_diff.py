@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Device code of two builds, kernel by kernel: codeobj_diff.py [--kernels] OBJDIR_A OBJDIR_B  (make OBJDIR=...; no GPU needed).
+"""Device code of two builds, kernel by kernel: codeobj_diff.py [--kernels] [--by-symbol] OBJDIR_A OBJDIR_B  (make OBJDIR=...; no GPU needed).
 For every X.o of either directory: the gfx950 code object's FUNC / OBJECT symbols (name, size), each function's disassembly with
 addresses (pc-relative distances to global variables included) stripped, and the amdhsa.kernels notes (registers, LDS, scratch, kernarg size) must be equal.  Exit status 1 if not.
 --kernels: one line per differing kernel (its symbol: template arguments as I..E) - instruction count A/B and the notes that differ - instead of the first eight
-differences of a file."""
+differences of a file.
+--by-symbol: functions are paired by symbol across all objects of a directory instead of file by file - for a change that moves kernels to another .hip file."""
 import os
 import re
 import subprocess
@@ -53,7 +54,27 @@ def per_kernel(A, B):
         print(f"  {k}: instructions {len(A[1].get(k, ()))}/{len(B[1].get(k, ()))}; " + (", ".join(notes) if notes else "notes equal"))
 
 
-def main(a, b, kernels=False):
+def whole_build(d):
+    """The device code of every X.o of a directory as one: a kernel that moved to another file keeps its symbol."""
+    S, C, M = {}, {}, {}
+    for o in sorted(f for f in os.listdir(d) if f.endswith(".o")):
+        with tempfile.TemporaryDirectory() as t:
+            s, c, m = device_code(os.path.join(d, o), t)
+        assert not (set(c) & set(C)), f"{d}/{o}: functions of an earlier object again: {sorted(set(c) & set(C))[:4]}"
+        S.update(s), C.update(c), M.update(m)
+    return S, C, M
+
+
+def main(a, b, kernels=False, by_symbol=False):
+    if by_symbol:
+        A, B = whole_build(a), whole_build(b)
+        diff = [f"{what} {k}" for what, x, y in zip(("symbol", "code", "notes"), A, B) for k in sorted(set(x) | set(y)) if x.get(k) != y.get(k)]
+        only = sorted(set(A[2]) ^ set(B[2]))
+        print(f"all objects: {len(A[2])}/{len(B[2])} kernels, {len(only)} in one build only" + "".join(f"\n  only in {'A' if k in A[2] else 'B'}: {k}" for k in only)
+              + ": " + ("identical" if not diff else "DIFFERENT: " + "; ".join(diff[:8])))
+        if kernels and diff:
+            per_kernel(A, B)
+        return 1 if diff else 0
     bad = 0
     for o in sorted({f for d in (a, b) for f in os.listdir(d) if f.endswith(".o")}):
         pa, pb = os.path.join(a, o), os.path.join(b, o)
@@ -76,5 +97,5 @@ def main(a, b, kernels=False):
 
 
 if __name__ == "__main__":
-    args = [x for x in sys.argv[1:] if x != "--kernels"]
-    sys.exit(main(args[0], args[1], kernels="--kernels" in sys.argv[1:]))
+    args = [x for x in sys.argv[1:] if x not in ("--kernels", "--by-symbol")]
+    sys.exit(main(args[0], args[1], kernels="--kernels" in sys.argv[1:], by_symbol="--by-symbol" in sys.argv[1:]))
