@@ -687,6 +687,16 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * T <= max_len (ceil(max_len / 16) up to 256 keys, 16 up to 2048, ceil(max_len / 128) beyond)
  *   [S2, fp32: rows x Tp][chunk statistics, fp32: rows x nchs x 2][partial outputs, fp32: rows x nchs x D]    each rounded up to 256 bytes.
  * Three launches on `stream`, no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
+ * lqer_attention_q_decode_paged_window: lqer_attention_q_decode_paged's argument list plus `window` = W >= 1, a SLIDING WINDOW on top of
+ * the causal rule (causal = 1 is required): query row i of sequence b sits at position p = i + (lens[b] - S) and sees the keys j with
+ * p - W < j <= p - W keys including its own, as Mistral's sliding_window; W >= lens[b] is plain causal.  For every b, out[b] and
+ * row_stats[b] are the SAME BITS as lqer_attention_q_decode with batch = 1 on the FULL raw K and V of that sequence and the additive
+ * window mask - 0 inside the window, the dtype's most negative finite value outside - WHATEVER THE PAGES BELOW THE WINDOW NOW HOLD:
+ * no table entry and no page wholly below key lens[b] - S - window + 1 is read (K or V, codes or exponents), so the caller may hand
+ * those pages to other sequences and leave the stale entries in the row - they must only still be the row's first entries by
+ * position: the table stays indexed by absolute key / 16.  Chunks wholly below that key cost nothing but an early exit.  Workspace,
+ * grid and strides are lqer_attention_q_decode_paged's (lqer_attention_q_decode_paged_workspace_bytes, sized by max_len), three
+ * launches, capturable alike.  Refused as the call above, and LQER_E_INVALID for window < 1 or causal = 0.
  * lqer_attention_q_paged: lqer_attention_q_decode_paged's argument list, word for word, and its metadata contract, for ANY S >= 1
  * (uniform over the call) - a prompt, a second turn, a chunk of a long prompt or a speculated block of more than 8 tokens on paged
  * sequences, the whole ragged batch in one call.  It is to lqer_attention_q_kv what the call above is to lqer_attention_q_decode_kv:
@@ -743,6 +753,13 @@ int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_b
                                   const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                                   const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
                                   size_t workspace_bytes, void* stream);
+int lqer_attention_q_decode_paged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                         const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                         int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+                                         int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides, const int64_t* out_strides,
+                                         float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                                         const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
+                                         void* stream, int64_t window);
 size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
 int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                            int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,

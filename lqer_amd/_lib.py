@@ -143,6 +143,9 @@ SIGNATURES = {
     "lqer_attention_q_decode_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_decode_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
                                            _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    # ... with a sliding window over the causal rule: the same argument list plus `window`
+    "lqer_attention_q_decode_paged_window": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64,
+                                                  _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
     # ... for any number of query rows: the prefill kernel on images written from the pool through the block table, T = lens[b]
     "lqer_attention_q_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,

@@ -1171,6 +1171,11 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
     set_error("%s: a mask tensor and causal = 1 are two forms of one mask - pass one", who);
     return LQER_E_INVALID;
   }
+  if (c.windowed && (c.window < 1 || !c.causal)) {
+    set_error("%s: window = %lld, causal = %d - a sliding window is W >= 1 keys on top of the causal rule (causal = 1)", who, (long long)c.window,
+              c.causal);
+    return LQER_E_INVALID;
+  }
   if (!c.q_fmt || !c.k_fmt || !c.p_fmt || !c.v_fmt) {
     set_error("%s: null quantizer format", who);
     return LQER_E_INVALID;
@@ -1210,7 +1215,8 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
   }
   const size_t need = kn.workspace_bytes(c);
   if (c.workspace_bytes < need) {
-    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need, who);
+    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need,
+              c.windowed ? "attention_q_decode_paged" : who);  // (the windowed call has the unwindowed one's workspace)
     return LQER_E_INVALID;
   }
   return LQER_OK;
@@ -1549,6 +1555,20 @@ int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_b
   c.packed = c.paged = true;
   c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
   return attn_run("attention_q_decode_paged", ATTN_DECODE, c);
+}
+
+int lqer_attention_q_decode_paged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                         int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
+                                         float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D,
+                                         const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                                         size_t workspace_bytes, void* stream, int64_t window) {
+  // (the call above with the window rule; grid and workspace still follow max_len)
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  c.packed = c.paged = c.windowed = true, c.window = window;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  return attn_run("attention_q_decode_paged_window", ATTN_DECODE, c);
 }
 
 size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {

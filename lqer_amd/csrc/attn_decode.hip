@@ -13,7 +13,7 @@
 //                      S2 to the workspace, {max, sum exp(S2 - max)} of the chunk per row next to it.
 //   k_attn_dec_pv      same grid.  Folds the row's chunk statistics IN CHUNK ORDER, P = exp(S2 - max) / sum ->DT, Q_x1 over 16 keys in a
 //                      lane pair (quant8of16_bf16), the chunk's V rows -> quant16_bf16 along d -> LDS [key][d], O^T += Vq^T Pq^T, the
-//                      R x D fp32 partial of the chunk to the workspace.  Chunk 0 writes row_stats.
+//                      R x D fp32 partial of the chunk to the workspace.  Chunk 0 (with a window: the first live chunk) writes row_stats.
 //   k_attn_dec_sum     adds the partials IN CHUNK ORDER, rounds ->DT, stores through the output strides.
 // The chunk length depends on T alone (dec_chunk), a row's arithmetic on that row alone: no floating-point atomics, no counters, the
 // same bits run to run, for a batch slice and for a slice of a kv group's heads.
@@ -26,6 +26,14 @@
 // it the chunk length, the chunk count and the causal offset of ITS sequence; the grid and the workspace strides come from the bound
 // max_len (dec_max_chunks), and a workgroup whose chunk its sequence does not have leaves before the first barrier.  A sequence's
 // results are those of a call of batch 1 at T = lens[b]: nothing it computes depends on max_len or on the rest of the batch.
+//
+// A sliding window (template parameter WIN, DArgs::win = W keys, with the causal rule): the query at position p sees keys p - W < j <= p.
+// A key outside the window gives P = +0 on the mask-tensor route (exp_neg underflows, Q_x1 of zeros is zero, a chunk whose keys are
+// all masked folds into the row's sum with factor 0), so applying the window as a RULE gives that route's bits and lets the kernels
+// skip what no row of the call can see: with lo = max(0, T - S - W + 1), chunks below lo / C leave before the first barrier and are
+// left out of both folds (their workspace cells are never written and never read; chunk lo / C writes row_stats), and keys below the
+// page boundary 16 (lo / 16) are zero rows in LDS whose table entries and pages are never dereferenced - a released page may hold
+// anything.  A page is one block of Q_w0 along t and one group of Q_w1's exponents, so the live pages' codes do not depend on the rest.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -65,6 +73,7 @@ struct DArgs {
   bool qvec, kvec, vvec;
   int nchs;  // chunks the workspace has room for per row (its stride over rows): nch, or dec_max_chunks(max_len) with the paged source
   kvc::KvSrc<const unsigned char> src;  // the packed and the paged source (kv_pack.h)
+  int64_t win;  // the window W of the kernels with WIN (mode 2 only); 0: none.  (Last: the members above keep their kernarg offsets)
 };
 
 // the paged source: chunk length and chunk count of a sequence of T = lens[b] keys
@@ -73,7 +82,13 @@ __device__ __forceinline__ void paged_chunks(const DArgs& a, int64_t T, int& C, 
   nch = (int)((T + C - 1) / C);
 }
 
-template <int DT, int SRC>
+// WIN: the first key that any of the S rows of a sequence of T keys sees
+__device__ __forceinline__ int64_t win_first(const DArgs& a, int64_t T) {
+  const int64_t lo = T - a.S - a.win + 1;
+  return lo > 0 ? lo : 0;
+}
+
+template <int DT, int SRC, bool WIN>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
@@ -86,6 +101,16 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
     paged_chunks(a, T, C, nch);
     if (c >= nch) return;  // (none of this sequence's chunks; uniform over the workgroup, before any barrier)
   }
+  int64_t plo = 0;  // WIN: keys below plo lie on pages wholly outside every row's window - zero rows, their table entries and pages unread
+  if constexpr (WIN) {
+    const int64_t lo = win_first(a, T);
+    if (c < lo / C) return;  // (a dead chunk: nothing written, and nothing reads its workspace cells)
+    plo = lo / 16 * 16;
+  }
+  const auto dead = [&](int64_t t) {
+    if constexpr (WIN) return t < plo;
+    else return false;
+  };
   const int64_t t0 = c * C;
   const int D = (int)a.D;
   const float NEG_INF = -__builtin_inff();
@@ -100,7 +125,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       uint4 e4 = make_uint4(0, 0, 0, 0), c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
-      if (tq < T) {  // (paged: the one table entry first, the five loads one round trip behind it)
+      const bool gone = dead(tq);  // (four keys of one page: all of them or none)
+      if (tq < T && !gone) {  // (paged: the one table entry first, the five loads one round trip behind it)
         const int64_t blk = kvc::block<SRC>(a.src, prow, z, g, tq / 16);
         e4 = *(const uint4*)(a.src.ke + blk * D + 16 * dg);
 #pragma unroll
@@ -111,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (tq + j < T) kvc::codes16_to_bf16(c[j], eb, a.qk, w);
+        if (tq + j < T && !gone) kvc::codes16_to_bf16(c[j], eb, a.qk, w);
         uint4* dst = (uint4*)(sK + (4 * kq + j) * DEC_LS + dg * 32);
         dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
         dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
@@ -127,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       for (int i = 0; i < 16; ++i) {
         const int64_t t = t0 + 16 * kb + i;
         float v4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (t < T) load4<DT>(a.k, b * a.k_bs + g * a.k_hs + t * a.k_rs + d0, a.kvec, v4);
+        if (t < T && !dead(t)) load4<DT>(a.k, b * a.k_bs + g * a.k_hs + t * a.k_rs + d0, a.kvec, v4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[j][i] = v4[j];
       }
@@ -175,6 +201,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       }
       int64_t tvis = T - 1;  // the last key visible to this lane's query
       if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
+      int64_t tlo = 0;  // WIN: the first key this lane's query sees (negative: all of them)
+      if constexpr (WIN) tlo = si + off - a.win + 1;
       const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + si * a.m_rs : 0;
       float s2[16];
       bool vis[16];
@@ -185,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
         float s = rnd<DT>(rnd<DT>(acc[r]) * a.scaling);
         if (a.mode == 1) s = rnd<DT>(s + (t < T ? load_elem<DT>(a.mask, moff + t) : 0.f));
         s2[r] = s;
-        vis[r] = kk < C && t <= tvis;
+        vis[r] = kk < C && t <= tvis && (!WIN || t >= tlo);
       }
       float tm = NEG_INF;
 #pragma unroll
@@ -223,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   }
 }
 
-template <int DT, int SRC>
+template <int DT, int SRC, bool WIN>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
@@ -235,6 +263,18 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
     paged_chunks(a, T, C, nch);
     if (c >= nch) return;
   }
+  int64_t plo = 0;
+  int c_lo = 0;  // WIN: the first chunk that holds a visible key
+  if constexpr (WIN) {
+    const int64_t lo = win_first(a, T);
+    c_lo = (int)(lo / C);
+    if (c < c_lo) return;
+    plo = lo / 16 * 16;
+  }
+  const auto dead = [&](int64_t t) {
+    if constexpr (WIN) return t < plo;
+    else return false;
+  };
   const int64_t t0 = c * C;
   const int D = (int)a.D;
   const float NEG_INF = -__builtin_inff();
@@ -250,13 +290,14 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       uint4 c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
-      if (tq < T) e4 = kvc::load_v4(a.src, kvc::block<SRC>(a.src, prow, z, g, tq / 16), tq, T, D, db, c);
+      const bool gone = dead(tq);
+      if (tq < T && !gone) e4 = kvc::load_v4(a.src, kvc::block<SRC>(a.src, prow, z, g, tq / 16), tq, T, D, db, c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         const uint32_t e1 = ((e4 >> (8 * j)) & 0xffu) * 0x01010101u;
         const uint32_t eb[4] = {e1, e1, e1, e1};
-        if (tq + j < T) kvc::codes16_to_bf16(c[j], eb, a.qv, w);
+        if (tq + j < T && !gone) kvc::codes16_to_bf16(c[j], eb, a.qv, w);
         uint4* dst = (uint4*)(sV + (4 * kq + j) * DEC_LS + db * 32);
         dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
         dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
@@ -269,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       const int key = it / db_n, db = it % db_n;
       const int64_t t = t0 + key;
       uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (t < T) {
+      if (t < T && !dead(t)) {
         float x[16];
         qmm::load16<DT>(a.v, b * a.v_bs + g * a.v_hs + t * a.v_rs + 16 * db, 16, a.vvec, x);
         qmm::quant16_bf16<DT != LQER_F16>(x, a.qv, w);
@@ -291,17 +332,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
     // ---- the row's maximum and sum from the chunk statistics, in chunk order
     const float* cs = a.cst + (z * a.R + rowc) * a.nchs * 2;
     float M = NEG_INF;
-    for (int cc = 0; cc < nch; ++cc) M = fmaxf(M, cs[2 * cc]);
+    for (int cc = c_lo; cc < nch; ++cc) M = fmaxf(M, cs[2 * cc]);
     const float mr = M == NEG_INF ? 0.f : M;
     float L = 0.f;
-    for (int cc = 0; cc < nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
-    if (a.stats && c == 0 && wave == 0 && lh == 0 && live) {
+    for (int cc = c_lo; cc < nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
+    if (a.stats && c == (WIN ? c_lo : 0) && wave == 0 && lh == 0 && live) {
       float* st = a.stats + (z * a.R + row) * 2;
       st[0] = M, st[1] = L;
     }
     int64_t tvis = T - 1;
     if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
     if (!live) tvis = -1;
+    int64_t tlo = 0;
+    if constexpr (WIN) tlo = si + off - a.win + 1;
 
     // ---- O^T += Vq^T Pq^T: a k-step is one block of 16 keys of Q_x1, this lane's half of it keys 8 lh .. 8 lh + 7
     f32x16 acc;
@@ -314,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       const float s8[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
       float p[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) p[i] = tb + i <= tvis ? rnd<DT>(exp_neg(s8[i] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
+      for (int i = 0; i < 8; ++i) p[i] = tb + i <= tvis && (!WIN || tb + i >= tlo) ? rnd<DT>(exp_neg(s8[i] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
       uint32_t w[4];
       quant8of16_bf16<DT != LQER_F16>(p, a.q1, w);
       const u32x4 pw = {w[0], w[1], w[2], w[3]};
@@ -335,22 +378,24 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
 }
 
 // one thread = four consecutive d of one output row (PAGED: the chunks of the row's own sequence)
-template <int DT, bool PAGED>
+template <int DT, bool PAGED, bool WIN>
 __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int dq = (int)a.D / 4;
   if (i >= a.rows * dq) return;
   const int64_t grow = i / dq;
   const int d = 4 * (int)(i % dq);
-  int nch = a.nch;
+  int64_t T = a.T;
+  int C = a.C, nch = a.nch, c_lo = 0;
   if constexpr (PAGED) {
-    int C;
-    paged_chunks(a, a.src.lens[grow / (a.heads * a.S)], C, nch);
+    T = a.src.lens[grow / (a.heads * a.S)];
+    paged_chunks(a, T, C, nch);
   }
+  if constexpr (WIN) c_lo = (int)(win_first(a, T) / C);  // (the partials of the chunks below were never written)
   const float* p = a.part + grow * a.nchs * a.D + d;
   float o[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
-  for (int cc = 0; cc < nch; ++cc) {
+  for (int cc = c_lo; cc < nch; ++cc) {
     const float4 t = *(const float4*)(p + (int64_t)cc * a.D);
     o[0] += t.x, o[1] += t.y, o[2] += t.z, o[3] += t.w;
   }
@@ -358,12 +403,13 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
-template <int DT, int SRC>
+template <int DT, int SRC, bool WIN = false>
 static int launch_decode(const DArgs& a, int64_t batch, hipStream_t st) {
   const dim3 grid((unsigned)a.nchs, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT, SRC><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT, SRC><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_sum<DT, SRC == SRC_PAGED><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
+  k_attn_dec_scores<DT, SRC, WIN><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT, SRC, WIN><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
+  if (WIN) return check_launch("lqer_attention_q_decode_paged_window");
   return check_launch(SRC == SRC_PAGED ? "lqer_attention_q_decode_paged" : (SRC == SRC_PACKED ? "lqer_attention_q_decode_kv" : "lqer_attention_q_decode"));
 }
 
@@ -405,6 +451,7 @@ int attention_q_decode_dispatch(const AttnCall& c) {
   a.m_bs = c.mask ? c.ms[0] : 0, a.m_hs = c.mask ? c.ms[1] : 0, a.m_rs = c.mask ? c.ms[2] : 0;
   a.o_bs = c.os[0], a.o_hs = c.os[1], a.o_rs = c.os[2];
   a.heads = (int)c.heads, a.kv_heads = (int)c.kv_heads, a.mode = c.causal ? 2 : (c.mask ? 1 : 0);
+  a.win = c.windowed ? (c.window < ((int64_t)1 << 31) ? c.window : (int64_t)1 << 31) : 0;  // (beyond every T <= 2^30 the rule is plain causal)
   a.scaling = c.scaling;
   a.q0 = make_qp(*c.q_fmt), a.qk = make_qp(*c.k_fmt), a.q1 = make_qp(*c.p_fmt), a.qv = make_qp(*c.v_fmt);
   a.qvec = al16(c.q, c.qs, esz);
@@ -415,6 +462,8 @@ int attention_q_decode_dispatch(const AttnCall& c) {
     a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
     a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
   }
+  // (the window has a public entry on the paged source only, so only that instantiation of the rule exists)
+  if (c.paged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true>(a, c.batch, c.st); });
   if (c.paged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
   if (c.packed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });
   return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_RAW>(a, c.batch, c.st); });

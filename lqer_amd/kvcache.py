@@ -237,7 +237,13 @@ class PageTable:
 
     A page has a count of owners.  `fork` gives a new sequence the FULL pages of its parent by reference - a full page is never
     written again, so it needs no copy - and a page of its own for the open block; `free` hands a page back when its last owner
-    goes.  A sequence that was never forked owns every one of its pages alone, and its books are what they were without the counts."""
+    goes.  A sequence that was never forked owns every one of its pages alone, and its books are what they were without the counts.
+
+    `release(seq, before_key)` lets a sequence FORGET its oldest keys (a sliding window): it stops owning the leading pages that lie
+    wholly below the key, and `released[slot]` counts them.  The row stays indexed by absolute key / 16: the released entries keep
+    their old page ids - stale, but valid indices that nothing reads - and `pages_of` still counts entries from the row's start, so
+    the pages a sequence holds are entries released .. pages_of - 1, and a row still needs room for the sequence's whole length.
+    Indexing the row as a ring, so that it could be as short as the window, is not done here."""
 
     def __init__(self, num_pages: int, max_seqs: int, max_pages_per_seq=None):
         if max_pages_per_seq is None:
@@ -250,7 +256,8 @@ class PageTable:
         self._slot = {}                                        # live seq -> slot
         self._next_seq = 0
         self.table = [[0] * max_pages_per_seq for _ in range(max_seqs)]  # [slot][i]: the page of keys 16 i .. 16 i + 15
-        self.pages_of = [0] * max_seqs                                   # entries of a slot's row that are its pages
+        self.pages_of = [0] * max_seqs                                   # entries of a slot's row in use, from the row's start
+        self.released = [0] * max_seqs                                   # ... of which the leading ones are no longer its pages
         self.lengths = [0] * max_seqs                                    # [slot]
         self._owners = np.zeros(num_pages, dtype=np.int32)               # [page]: the live sequences whose rows name it
 
@@ -274,7 +281,7 @@ class PageTable:
         seq, self._next_seq = self._next_seq, self._next_seq + 1
         slot = self._free_slots.pop()
         self._slot[seq] = slot
-        self.pages_of[slot] = self.lengths[slot] = 0
+        self.pages_of[slot] = self.lengths[slot] = self.released[slot] = 0
         return seq
 
     def slot(self, seq: int) -> int:
@@ -287,15 +294,47 @@ class PageTable:
         slot = self.slot(seq)
         del self._slot[seq]
         row = self.table[slot]
-        if self.pages_of[slot]:
-            pages = np.array(row[self.pages_of[slot] - 1::-1])  # the last page first: the order pages have always gone back in
+        if self.pages_of[slot] > self.released[slot]:
+            pages = np.array(row[self.released[slot]:self.pages_of[slot]][::-1])  # the last page first: the order pages have always gone back in
             self._owners[pages] -= 1
             self._free_pages.extend(pages[self._owners[pages] == 0].tolist())  # (those whose last owner this was)
-        self.pages_of[slot] = self.lengths[slot] = 0
+        self.pages_of[slot] = self.lengths[slot] = self.released[slot] = 0
         self._free_slots.append(slot)
 
     def length(self, seq: int) -> int:
         return self.lengths[self.slot(seq)]
+
+    def pages_held(self, seq: int) -> int:
+        """The pages the sequence owns, alone or shared: its row's entries minus the released ones."""
+        slot = self.slot(seq)
+        return self.pages_of[slot] - self.released[slot]
+
+    def release(self, seq: int, before_key: int) -> list:
+        """The sequence gives up its pages that lie wholly below key `before_key` (page i: keys 16 i .. 16 i + 15, so i <
+        before_key // 16) - full pages only, never the open block.  A page goes back to the free stack when its last owner goes
+        (forks share pages); returns the pages that did, in the order they went.  The row keeps the entries; a smaller or
+        repeated `before_key` changes nothing.  unrelease() undoes the call."""
+        slot = self.slot(seq)
+        first, upto = self.released[slot], min(before_key // PAGE_KEYS, self.lengths[slot] // PAGE_KEYS)
+        if upto <= first:
+            return []
+        pages = np.array(self.table[slot][first:upto])
+        self._owners[pages] -= 1
+        freed = pages[self._owners[pages] == 0].tolist()
+        self._free_pages.extend(freed)
+        self.released[slot] = upto
+        return freed
+
+    def unrelease(self, seq: int, first: int, freed: list) -> None:
+        """Undo the release() that took released[slot] from `first` to its present value and returned `freed`, with no page taken
+        or handed back since (or every such step undone): the books as they were, the free stack in its order."""
+        slot = self.slot(seq)
+        if freed:
+            assert self._free_pages[-len(freed):] == freed
+            del self._free_pages[-len(freed):]
+        if self.released[slot] > first:
+            self._owners[np.array(self.table[slot][first:self.released[slot]])] += 1
+        self.released[slot] = first
 
     def slots(self, seqs) -> list:
         """The slots of `seqs`; raises for an unknown, freed or repeated one."""
@@ -356,16 +395,16 @@ class PageTable:
         for s, n in zip(src, lens):
             child = self.alloc()
             d, full = self._slot[child], n // PAGE_KEYS
-            row = self.table[d]
+            row, gone = self.table[d], self.released[s]
             if full:
-                row[:full] = self.table[s][:full]
+                row[:full] = self.table[s][:full]  # (the stale entries too: valid indices, read by nothing)
                 if s not in shared:
-                    shared[s] = np.array(row[:full])
-                self._owners[shared[s]] += 1
+                    shared[s] = np.array(row[gone:full], dtype=np.int64)
+                self._owners[shared[s]] += 1       # the live entries only: a released page is not the parent's to share
             if n % PAGE_KEYS:
                 row[full] = page = self._free_pages.pop()
                 self._owners[page] = 1
-            self.pages_of[d], self.lengths[d] = (n + PAGE_KEYS - 1) // PAGE_KEYS, n
+            self.pages_of[d], self.lengths[d], self.released[d] = (n + PAGE_KEYS - 1) // PAGE_KEYS, n, gone
             children.append(child), dst.append(d)
         return children, src, dst, lens
 
@@ -378,12 +417,13 @@ class PageTable:
     def snapshot(self, seqs=()):
         """The books, and the table rows of `seqs` - what restore() needs to put back sequences that were freed since."""
         return (self._free_pages[:], self._free_slots[:], dict(self._slot), self._next_seq, self.pages_of[:], self.lengths[:], self._owners.copy(),
-                {self.slot(s): self.table[self.slot(s)][:] for s in seqs})
+                self.released[:], {self.slot(s): self.table[self.slot(s)][:] for s in seqs})
 
     def restore(self, snap) -> None:
         self._free_pages, self._free_slots, self._slot, self._next_seq, self.pages_of, self.lengths, self._owners = (
             snap[0][:], snap[1][:], dict(snap[2]), snap[3], snap[4][:], snap[5][:], snap[6].copy())
-        for s, row in snap[7].items():
+        self.released = snap[7][:]
+        for s, row in snap[-1].items():
             self.table[s][:] = row
 
 
@@ -411,16 +451,30 @@ class PagedKVCache:
     Taking speculated tokens back: `snap, = cache.fork(seq)`, append the speculated block to `seq` and attend; if only the first m of
     its keys are accepted, `cache.free(seq)` and append those m keys' k / v - the step still has them - to `snap`, which goes on as
     the sequence: the bits of one that only ever saw the m.  There is no in-place crop: the raw keys of a closed block are gone,
-    so a shortened block cannot be given the codes and exponents it would have had."""
+    so a shortened block cannot be given the codes and exponents it would have had.
+
+    window=W (None: keep everything): a SLIDING-WINDOW cache - attention_flexible_paged then defaults to the window rule (a query at
+    position p sees keys p - W < j <= p), and `append` hands back the pages nothing can see any more: for each addressed sequence
+    those wholly below min(T_after - W - 7, 16 (T_before // 16)) - a later call of up to 8 query rows starts at key T - 8 - W + 1
+    >= T_after - W - 7, and the append itself touches the block at T_before // 16 and those after it.  The release comes BEFORE the
+    reservation, so the append can take the pages it has just freed and a pool sized for the window keeps running however long the
+    sequences grow; it is undone, with the books as they were, when the reservation or the launch is refused.  After an append of
+    n <= W + 7 keys a sequence holds at most (W + 37) // 16 pages (.pages_held(seq)).  Forks share pages as ever: a released page
+    goes back to the pool with its last owner.  The table's rows stay indexed by absolute key / 16 (no ring), so max_pages_per_seq
+    still bounds a sequence's total length.  The early keys of a sequence that has released pages are gone: to_dense() and
+    dequantized() raise ValueError for it."""
 
     covers = staticmethod(QuantizedKVCache.covers)
 
     def __init__(self, num_pages: int, max_seqs: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device,
-                 max_pages_per_seq=None):
+                 max_pages_per_seq=None, window=None):
         if not self.covers(cfg0, cfg1, head_dim, dtype):
             raise NotImplementedError(f"PagedKVCache: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
                                       "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
                                       "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
+        if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
+            raise ValueError(f"PagedKVCache: window {window!r} - None or a number of keys >= 1")
+        self.window = window
         self.pt = PageTable(num_pages, max_seqs, max_pages_per_seq)
         if kv_heads < 1 or kv_heads > _MAX_GRID_Z or max_seqs > _MAX_GRID_Z or self.pt.max_len > 1 << 30:
             raise ValueError(f"PagedKVCache: kv_heads {kv_heads}, max_seqs {max_seqs}, max_pages_per_seq {self.pt.max_pages_per_seq}")
@@ -447,6 +501,9 @@ class PagedKVCache:
     def length(self, seq: int) -> int:
         return self.pt.length(seq)
 
+    def pages_held(self, seq: int) -> int:
+        return self.pt.pages_held(seq)
+
     def _pool_args(self):
         return (self.buf.data_ptr(), self.buf.numel(), self.pt.num_pages, self.pt.max_seqs, self.table.data_ptr(), self.pt.max_pages_per_seq)
 
@@ -471,13 +528,31 @@ class PagedKVCache:
         if n == 0 or not seqs:
             self.pt.slots(seqs)
             return
-        slots, lens, taken = self.pt.reserve(seqs, n)  # (raises with nothing taken)
+        undo = self._release_outside_window(seqs, n) if self.window is not None else []
         try:
-            self._launch_append(slots, lens, taken, k, v, n)
+            slots, lens, taken = self.pt.reserve(seqs, n)  # (raises with nothing taken)
+            try:
+                self._launch_append(slots, lens, taken, k, v, n)
+            except BaseException:
+                self.pt.rollback(slots, taken)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
+                raise
         except BaseException:
-            self.pt.rollback(slots, taken)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
+            for u in reversed(undo):
+                self.pt.unrelease(*u)
             raise
         self.pt.commit(slots, n)
+
+    def _release_outside_window(self, seqs, n) -> list:
+        """Before an append of n keys to `seqs` (validated here, so a bad call releases nothing): every sequence gives up the pages no
+        later call can see and this append does not touch.  Returns what PageTable.unrelease needs, in the order of the calls."""
+        undo = []
+        for seq, s in zip(seqs, self.pt.slots(seqs)):
+            t = self.pt.lengths[s]
+            first = self.pt.released[s]
+            freed = self.pt.release(seq, min(t + n - self.window - 7, PAGE_KEYS * (t // PAGE_KEYS)))
+            if self.pt.released[s] != first:
+                undo.append((seq, first, freed))
+        return undo
 
     def _launch_append(self, slots, lens, taken, k, v, n) -> None:
         for s, t in zip(slots, taken):
@@ -579,6 +654,9 @@ class PagedKVCache:
     @torch.no_grad()
     def to_dense(self, seq: int) -> QuantizedKVCache:
         slot, t = self.pt.slot(seq), self.pt.length(seq)
+        if self.pt.released[slot]:
+            raise ValueError(f"PagedKVCache.to_dense: sequence {seq} has released its first {self.pt.released[slot]} pages (window {self.window}) - "
+                             f"its keys below {PAGE_KEYS * self.pt.released[slot]} are gone")
         dense = QuantizedKVCache(1, self.kv_heads, self.head_dim, self.cfg0, self.cfg1, self.dtype, self.device, capacity=max(t, PAGE_KEYS))
         if t:
             with torch.cuda.device(self.device):
@@ -599,7 +677,7 @@ KERNEL_AUTO = "auto"
 
 @torch.no_grad()
 def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False, out_layout="bhsd", return_stats=False, ws=None,
-                             kernel=KERNEL_DECODE):
+                             kernel=KERNEL_DECODE, window=None):
     """attention_flexible(q[b:b+1], K_b, V_b, cache.cfg0, cache.cfg1, scaling, causal=causal, kernel=kernel) for every sequence
     seqs[b] of a PagedKVCache, bit for bit, in ONE call over sequences of different lengths.
     q [len(seqs), h, s, d]; `causal`: key j of sequence b visible to query i iff j <= i + (length_b - s).
@@ -610,10 +688,23 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     workspace follows the batch at hand.  kernel="auto": decode for s <= 8, prefill beyond.
     There is no mask tensor - the per-sequence lengths are what a padding mask stood for - and no other route: an empty sequence,
     causal with s > a length, s > 8 with kernel="decode", an unknown `kernel`, a wrong dtype, device or head count raise ValueError.
-    `out_layout` and `return_stats` as attention_flexible; ws: a uint8 workspace or None (the stream's)."""
+    `out_layout` and `return_stats` as attention_flexible; ws: a uint8 workspace or None (the stream's).
+    window=W >= 1 (default: the cache's window, None on a cache without one; needs causal=True, ValueError otherwise): sliding-window
+    attention - the query at position p sees keys p - W < j <= p, W keys including its own.  lqer_attention_q_decode_paged_window gives,
+    per sequence, the bits of attention_flexible(..., attention_mask=M, kernel="decode") on the FULL raw K and V with M = 0 inside the
+    window and torch.finfo(dtype).min outside, without reading a page wholly below the window - so it runs on sequences whose old pages
+    the cache has released.  On such sequences an explicit W must not exceed the cache's (the keys are gone).  The prefill kernel has
+    no window rule yet: kernel="prefill" (and "auto" beyond 8 rows) with a window is taken only while every addressed length is <= W,
+    where the rule changes nothing and nothing can have been released, and raises ValueError beyond."""
     if kernel not in (KERNEL_DECODE, KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"attention_flexible_paged: kernel={kernel!r} - 'decode', 'prefill' or 'auto'")
     _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
+    if window is None:
+        window = cache.window
+    elif not isinstance(window, int) or isinstance(window, bool) or window < 1:
+        raise ValueError(f"attention_flexible_paged: window {window!r} - None or a number of keys >= 1")
+    if window is not None and not causal:
+        raise ValueError(f"attention_flexible_paged: window={window} without causal=True - the window is a rule on top of the causal one")
     seqs = list(seqs)
     if q.dim() != 4:
         raise ValueError(f"attention_flexible_paged: q {tuple(q.shape)} is not [len(seqs), h, s, d]")
@@ -636,6 +727,15 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     if min(lens) < 1 or (causal and s > min(lens)) or (prefill and max(lens) > _ATTN_MAX_T):
         raise ValueError(f"attention_flexible_paged: lengths {lens} of sequences {seqs} - an empty sequence has nothing to attend to"
                          + (f", and causal needs {s} query rows <= every length" if causal else ""))
+    if window is not None:
+        if any(cache.pt.released[x] for x in slots) and (cache.window is None or window > cache.window):
+            raise ValueError(f"attention_flexible_paged: window={window} on sequences that have released the pages below the cache's window of "
+                             f"{cache.window} keys")
+        if prefill and max(lens) > window:
+            raise ValueError(f"attention_flexible_paged: kernel='prefill' with window={window} and lengths {lens} - the prefill kernel has no window "
+                             "rule; it is taken while every length is <= the window")
+        if prefill:
+            window = None  # (every length <= W: plain causal)
     if q.stride(3) != 1:
         q = q.contiguous()
     out, ob, stats = _attention_outputs(q, out_layout, return_stats)
@@ -646,9 +746,12 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     with torch.cuda.device(q.device):
         if ws is None:
             ws = ops.workspace(q.device, max(getattr(L, name + "_workspace_bytes")(b, h, cache.kv_heads, s, max_len, d), 16))
+        if window is not None:  # (the decode kernels with the window rule: the same arguments and workspace, plus W)
+            name += "_window"
         _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), ob.data_ptr(),
                                     stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, cache.kv_heads, s, d,
                                     _tri(q), _tri(ob), float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]),
-                                    C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device)),
+                                    C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device),
+                                    *(() if window is None else (min(window, 1 << 62),))),
                    name)
     return (out, stats) if return_stats else out
