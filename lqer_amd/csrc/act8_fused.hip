@@ -327,18 +327,22 @@ int act8_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t 
   // row chunks the kernel holds in registers (bf16 rows beyond 6144 elements: 112 raw registers + the wider conversion spill - three launches)
   const int maxch = nch_p <= 64 * 8 ? 8 : nch_p <= 64 * 12 ? 12 : (dtype == LQER_F16 && nch_p <= 64 * 28) ? 28 : 0;
   if (maxch == 0 || (dtype != LQER_F16 && dtype != LQER_BF16)) return LQER_E_UNSUPPORTED;
-  if (zeroed) *zeroed = zfit;  // (every return below this line has launched the kernel)
   auto run = [&](auto dt, auto mc) {
     return a8f::launch<decltype(dt)::value, decltype(mc)::value>(x, M, K, ldx, qx, xq8, cols_p8, xscale, a_frag, qa, L, (int)rp, xaq, zp, zn, st);
   };
   using std::integral_constant;
+  int rc;
   if (dtype == LQER_F16) {
-    if (maxch == 8) return run(integral_constant<int, LQER_F16>{}, integral_constant<int, 8>{});
-    if (maxch == 12) return run(integral_constant<int, LQER_F16>{}, integral_constant<int, 12>{});
-    return run(integral_constant<int, LQER_F16>{}, integral_constant<int, 28>{});
+    if (maxch == 8) rc = run(integral_constant<int, LQER_F16>{}, integral_constant<int, 8>{});
+    else if (maxch == 12) rc = run(integral_constant<int, LQER_F16>{}, integral_constant<int, 12>{});
+    else rc = run(integral_constant<int, LQER_F16>{}, integral_constant<int, 28>{});
+  } else if (maxch == 8) {
+    rc = run(integral_constant<int, LQER_BF16>{}, integral_constant<int, 8>{});
+  } else {
+    rc = run(integral_constant<int, LQER_BF16>{}, integral_constant<int, 12>{});
   }
-  if (maxch == 8) return run(integral_constant<int, LQER_BF16>{}, integral_constant<int, 8>{});
-  return run(integral_constant<int, LQER_BF16>{}, integral_constant<int, 12>{});
+  if (zeroed) *zeroed = zfit && rc == LQER_OK;  // (only a kernel that was launched has written the zeros)
+  return rc;
 }
 
 }  // namespace lqer

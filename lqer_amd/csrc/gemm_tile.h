@@ -1,5 +1,5 @@
 // What the tile kernels of the fused GEMM share (device code only): k_lqer_gemm (gemm_w4a8.hip, 128- and 64-row tiles) and
-// k_lqer_gemm_m256 (gemm_w4a8_m256.hip) take everything here; k_lqer_gemm_i8, qmm_image.h and lowrank_xa.hip the swizzle, the LDS
+// k_lqer_gemm_m256 (gemm_w4a8_m256.hip) take everything here; k_lqer_gemm_i8, qmm_image.h and xa_staged.hip the swizzle, the LDS
 // pointer type and the tile order.  Ring depth, slot sizes and tile height are each kernel's own.
 // Only pieces that leave every kernel's device code as it was live here (tools/codeobj_diff.py --by-symbol against the parent
 // commit; profiles/tile_shared_codeobj.txt also lists the pieces that were tried as functions and moved registers).

@@ -4,6 +4,13 @@
 // pointers handed in are never dereferenced by host code.  tests/test_launches_cpu.py builds it and holds its output to a record.
 //   launch_probe LIBRARY CUS < cases      CUS: what the device query answers; one case per line: K N rank tuning  5 x (kind width block
 //                                         exp_width exp_bias)  M dtype b_limbs
+//   launch_probe LIBRARY CUS act < cases  the ACTIVATION side (tests/test_act_launches_cpu.py): the descriptor as above, then
+//                                         M dtype a_limbs  pointers (0: x aligned, ldx = K; 1: x off by 2 bytes, ldx = K + 1; 2: xq == x)
+//                                         scratch (0: ample, 1: exactly lqer_lowrank_xa_scratch_bytes, 2: none).  Per case four calls, " |"
+//                                         between them: lqer_quantize_act_xa with xaq, without (the decode-partials form),
+//                                         lqer_quantize_act_xa_prep (and its *ready_bytes), lqer_lowrank_xa on the image.  Here the
+//                                         sizing arguments of the side kernels that a grid does not pin are printed as well, and the
+//                                         two stream calls of this side (hipMemcpy2DAsync, hipMemsetAsync) as pseudo-launches.
 #include <dlfcn.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -15,6 +22,10 @@ struct dim3 {
   uint32_t x, y, z;
 };
 static int g_cus = 256;
+static bool g_act = false;
+struct XaPlan {  // csrc/xa_common.h
+  int row_groups, nchunk, kc;
+};
 
 extern "C" {
 int hipGetDevice(int* dev) { return *dev = 0; }
@@ -32,8 +43,27 @@ int hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t ld
   const char* name = (dladdr(f, &info) && info.dli_sname) ? info.dli_sname : "?";
   printf(" %s %u,%u,%u %u %zu", name, grid.x, grid.y, grid.z, block.x, lds);
   if (strstr(name, "k_bout_amax")) printf(" [%d %d]", *(int*)args[1], *(int*)args[2]);
+  if (!g_act) return 0;
+  auto ints = [&](int first, int n) {  // n consecutive int arguments
+    for (int i = 0; i < n; ++i) printf("%s%d", i ? " " : " [", *(int*)args[first + i]);
+    printf("]");
+  };
+  auto plan = [&](int at, int rp_at) {
+    const XaPlan& p = *(const XaPlan*)args[at];
+    printf(" [plan %d %d %d rp %d]", p.row_groups, p.nchunk, p.kc, *(int*)args[rp_at]);
+  };
+  if (strstr(name, "k_xa_partial_lds")) ints(4, 4);  // row_groups, nch, spc, steps_total
+  else if (strstr(name, "k_quant_xa128")) ints(8, 4);
+  else if (strstr(name, "k_xa_partial")) plan(7, 6);
+  else if (strstr(name, "k_xa_reduce")) plan(1, 2);
+  else if (strstr(name, "k_quant_xa16")) printf(" [vec %d rp %d rg %d]", (int)*(bool*)args[4], *(int*)args[10], *(int*)args[11]);
+  else if (strstr(name, "k_act8_fused")) printf(" [zero_n %d]", *(int*)args[13]);
   return 0;
 }
+int hipMemcpy2DAsync(void*, size_t dpitch, const void*, size_t spitch, size_t width, size_t height, int, void*) {
+  return printf(" hipMemcpy2DAsync %zu %zu %zu %zu", dpitch, spitch, width, height), 0;
+}
+int hipMemsetAsync(void*, int value, size_t bytes, void*) { return printf(" hipMemsetAsync %d %zu", value, bytes), 0; }
 }
 
 int main(int argc, char** argv) {
@@ -45,6 +75,11 @@ int main(int argc, char** argv) {
   auto padded_r = (decltype(&lqer_padded_r))dlsym(lib, "lqer_padded_r");
   auto last_error = (decltype(&lqer_last_error))dlsym(lib, "lqer_last_error");
   void* const p = (void*)(uintptr_t)0x40000000;  // (aligned, never read)
+  g_act = argc > 3 && !strcmp(argv[3], "act");
+  auto act_xa = (decltype(&lqer_quantize_act_xa))dlsym(lib, "lqer_quantize_act_xa");
+  auto act_xa_prep = (decltype(&lqer_quantize_act_xa_prep))dlsym(lib, "lqer_quantize_act_xa_prep");
+  auto lowrank_xa = (decltype(&lqer_lowrank_xa))dlsym(lib, "lqer_lowrank_xa");
+  auto xa_scratch = (decltype(&lqer_lowrank_xa_scratch_bytes))dlsym(lib, "lqer_lowrank_xa_scratch_bytes");
   lqer_linear_desc_t d;
   long long M;
   int dtype, b_limbs;
@@ -55,6 +90,26 @@ int main(int argc, char** argv) {
     for (auto q : f)
       if (scanf("%d %d %d %d %d", &q->kind, &q->width, &q->block, &q->exp_width, &q->exp_bias) != 5) return 2;
     if (scanf("%lld %d %d", &M, &dtype, &b_limbs) != 3) return 2;
+    if (g_act) {
+      int ptrs, scr;
+      if (scanf("%d %d", &ptrs, &scr) != 2) return 2;
+      const int a_limbs = b_limbs;
+      const void* x = ptrs == 1 ? (char*)p + 2 : p;
+      const int64_t ldx = d.in_features + (ptrs == 1);
+      void* const xq = ptrs == 2 ? (void*)x : (char*)p + (1 << 28);
+      void* const a_t = d.rank > 0 ? p : nullptr;
+      const size_t bytes = scr == 0 ? (size_t)1 << 40 : scr == 1 ? xa_scratch(&d, M) : 0;
+      void* const scratch = bytes ? p : nullptr;
+      auto done = [&](int rc, const char* end) { printf(" -> %d%s%s%s", rc, rc ? " " : "", rc ? last_error() : "", end); };
+      done(act_xa(&d, x, dtype, M, ldx, a_t, a_limbs, xq, p, scratch, bytes, nullptr), " |");
+      done(act_xa(&d, x, dtype, M, ldx, a_t, a_limbs, xq, nullptr, scratch, bytes, nullptr), " |");
+      size_t ready = 0;
+      const int rc = act_xa_prep(&d, x, dtype, M, ldx, a_t, a_limbs, xq, p, scratch, bytes, p, &ready, nullptr);
+      printf(" ready=%zu", ready);
+      done(rc, " |");
+      done(lowrank_xa(&d, xq, M, a_t, a_limbs, p, scratch, bytes, nullptr), "\n");
+      continue;
+    }
     int xl = 1, al = 1;
     limbs(&d, &xl, &al);
     const int rc = gemm(&d, p, M, p, d.rank > 0 ? p : nullptr, padded_r(d.rank) * al, d.rank > 0 ? p : nullptr, b_limbs, nullptr, p, dtype,

@@ -107,7 +107,7 @@ def test_scratch_sizes_are_monotone(lib):
 
 
 def test_side_scratch_holds_the_fused_kernels_partial_tiles(lib):
-    """The one-launch quantizer + split-K kernel (csrc/lowrank_xa.hip, xa_fused_plan) leaves one fp32 partial tile of 32 token rows x
+    """The one-launch quantizer + split-K kernel (csrc/quant_xa16.hip, xa_fused_plan) leaves one fp32 partial tile of 32 token rows x
     padded rank per 256 k and row group in the side scratch, and checks the caller's bytes on the host: a size function that reports
     one row group less sends every forward of such a shape to the slower separate steps without an error - invisible to a guard zone
     (nothing overruns) and to the values (same bits).  From about K = 4096 and a few thousand tokens this plan, not the split-K bound,
