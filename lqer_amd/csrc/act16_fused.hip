@@ -121,15 +121,7 @@ __global__ __launch_bounds__(512) void k_act16_fused(const void* __restrict__ x,
     float v[8];
     const uint32_t wd[4] = {live ? raw[j][0] : 0u, live ? raw[j][1] : 0u, live ? raw[j][2] : 0u, live ? raw[j][3] : 0u};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr (DT == LQER_F16) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        const h2 h = __builtin_bit_cast(h2, wd[i]);
-        v[2 * i] = (float)h[0], v[2 * i + 1] = (float)h[1];
-      } else {
-        v[2 * i] = __uint_as_float(wd[i] << 16), v[2 * i + 1] = __uint_as_float(wd[i] & 0xffff0000u);
-      }
-    }
+    for (int i = 0; i < 4; ++i) pair_to_f32<DT>(wd[i], v[2 * i], v[2 * i + 1]);
     float amax = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
@@ -137,6 +129,7 @@ __global__ __launch_bounds__(512) void k_act16_fused(const void* __restrict__ x,
     uint32_t w[4] = {0, 0, 0, 0};
     if (amax > 0.f) {
       const int e = block_exponent_u(amax, qx);
+      // (mxint_bf16_image's text, common.h: called as the function, the three bf16 kernels come out in another instruction order)
       if (mxint16_fast_ok(e, qx)) {
         mxint16_bf16_fast<DT != LQER_F16, 8>(v, e, qx, w);
       } else {

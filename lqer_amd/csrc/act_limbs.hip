@@ -27,15 +27,7 @@ __global__ __launch_bounds__(256) void k_split_act(const void* __restrict__ x, i
         const uint4 t = *(const uint4*)((const bf16_t*)x + row * ldx + k0);
         const uint32_t w[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (DT == LQER_F16) {
-            typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-            const h2 h = __builtin_bit_cast(h2, w[j]);
-            v[2 * j] = (float)h[0], v[2 * j + 1] = (float)h[1];
-          } else {
-            v[2 * j] = __uint_as_float(w[j] << 16), v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-          }
-        }
+        for (int j = 0; j < 4; ++j) pair_to_f32<DT>(w[j], v[2 * j], v[2 * j + 1]);
       }
     } else {
 #pragma unroll

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       }
       uint32_t w[4][8];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) qmm::quant16_bf16<DT != LQER_F16>(x[j], a.qk, w[j]);
+      for (int j = 0; j < 4; ++j) quant16_bf16<DT != LQER_F16>(x[j], a.qk, w[j]);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {  // key 16 kb + i: the four d as one 8-byte store
         const int sh = 16 * (i & 1);
@@ -191,8 +191,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
           uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
           if (live) {
             float v[16];
-            qmm::load16<DT>(a.q, b * a.q_bs + h * a.q_hs + si * a.q_rs + ks * 16, 16, a.qvec, v);
-            qmm::quant16_bf16<DT != LQER_F16>(v, a.q0, w);
+            load16<DT>(a.q, b * a.q_bs + h * a.q_hs + si * a.q_rs + ks * 16, 16, a.qvec, v);
+            quant16_bf16<DT != LQER_F16>(v, a.q0, w);
           }
           const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
           const bf16x8 kf = *(const bf16x8*)(sK + (32 * wave + l31) * DEC_LS + (2 * ks + lh) * 16);
@@ -312,8 +312,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       if (t < T && !dead(t)) {
         float x[16];
-        qmm::load16<DT>(a.v, b * a.v_bs + g * a.v_hs + t * a.v_rs + 16 * db, 16, a.vvec, x);
-        qmm::quant16_bf16<DT != LQER_F16>(x, a.qv, w);
+        load16<DT>(a.v, b * a.v_bs + g * a.v_hs + t * a.v_rs + 16 * db, 16, a.vvec, x);
+        quant16_bf16<DT != LQER_F16>(x, a.qv, w);
       }
       uint4* dst = (uint4*)(sV + key * DEC_LS + db * 32);
       dst[0] = make_uint4(w[0], w[1], w[2], w[3]);

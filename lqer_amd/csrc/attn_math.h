@@ -1,5 +1,5 @@
 // The scalar arithmetic both fused attention kernels share (attn_q.hip: prefill, attn_decode.hip: up to 8 query rows): the ->DT
-// rounding, exp for the softmax, and the block-of-16 quantizer of P for a block split over a lane pair.  One spelling, so the two
+// rounding, exp for the softmax, and the block-of-16 quantizer of P for a block split over a lane pair (mxint_bf16_image, common.h).  One spelling, so the two
 // kernels cannot drift apart in a last bit.
 #pragma once
 #include "qmm_image.h"
@@ -25,7 +25,8 @@ __device__ __forceinline__ float exp_neg(float x) {
   return __builtin_fmaf(e, r * 0.693147182464599609375f, e);
 }
 
-// the 8 values a lane holds of a block of 16 (the other 8 sit in lane ^ 32) -> 8 exact bf16 values: quant16_bf16's arithmetic
+// the 8 values a lane holds of a block of 16 (the other 8 sit in lane ^ 32) -> 8 exact bf16 values: quant16_bf16 with
+// the maximum taken across the lane pair (block_exponent + mxint_bf16_image, common.h)
 template <bool FLUSH_TINY>
 __device__ __forceinline__ void quant8of16_bf16(const float (&v)[8], const QP& q, uint32_t (&w)[4]) {
   float am = 0.f;
@@ -37,16 +38,7 @@ __device__ __forceinline__ void quant8of16_bf16(const float (&v)[8], const QP& q
   for (int i = 0; i < 4; ++i) w[i] = 0;
   if (amax > 0.f) {
     const int e = block_exponent(amax, q);
-    if (mxint16_fast_ok(e, q)) {
-      mxint16_bf16_fast<FLUSH_TINY, 8>(v, e, q, w);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
-        const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
-        w[i] = lo | (hi << 16);
-      }
-    }
+    mxint_bf16_image<FLUSH_TINY, 8>(v, e, q, w);
   }
 }
 

@@ -99,8 +99,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (qi < a.S && ks * 16 < a.D) {
       float v[16];
-      qmm::load16<DT>(a.q, b * a.q_bs + h * a.q_hs + qi * a.q_rs + ks * 16, 16, a.qvec, v);
-      qmm::quant16_bf16<DT != LQER_F16>(v, a.q0, w);
+      load16<DT>(a.q, b * a.q_bs + h * a.q_hs + qi * a.q_rs + ks * 16, 16, a.qvec, v);
+      quant16_bf16<DT != LQER_F16>(v, a.q0, w);
     }
     const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
     qf[ks] = __builtin_bit_cast(bf16x8, f);
@@ -180,15 +180,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
             const uint2 m2 = *(const uint2*)((const bf16_t*)a.mask + moff + tc);
             const uint32_t wd[2] = {m2.x, m2.y};
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              if constexpr (DT == LQER_F16) {
-                typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-                const h2 hv = __builtin_bit_cast(h2, wd[j]);
-                mk[4 * g + 2 * j] = (float)hv[0], mk[4 * g + 2 * j + 1] = (float)hv[1];
-              } else {
-                mk[4 * g + 2 * j] = __uint_as_float(wd[j] << 16), mk[4 * g + 2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
-              }
-            }
+            for (int j = 0; j < 2; ++j) pair_to_f32<DT>(wd[j], mk[4 * g + 2 * j], mk[4 * g + 2 * j + 1]);
           }
         } else {
 #pragma unroll

@@ -43,16 +43,9 @@ __device__ __forceinline__ void unpack16(const u32x4 rawv, float (&v)[ColVec<DT>
   if constexpr (DT == LQER_F32) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(raw[j]);
-  } else if constexpr (DT == LQER_F16) {
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const h2 h = __builtin_bit_cast(h2, raw[j]);
-      v[2 * j] = (float)h[0], v[2 * j + 1] = (float)h[1];
-    }
   } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[2 * j] = __uint_as_float(raw[j] << 16), v[2 * j + 1] = __uint_as_float(raw[j] & 0xffff0000u);
+    for (int j = 0; j < 4; ++j) pair_to_f32<DT>(raw[j], v[2 * j], v[2 * j + 1]);
   }
 }
 

@@ -14,6 +14,8 @@ typedef unsigned short bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // one MFMA A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(16))) float f32x16;  // 32x32 accumulator
 typedef __attribute__((ext_vector_type(4))) float f32x4;    // 16x16 accumulator
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 // Resolved MXINT parameters handed to kernels by value.
 struct QP {
@@ -70,6 +72,86 @@ __device__ __forceinline__ float load_elem<LQER_F16>(const void* p, int64_t i) {
 template <>
 __device__ __forceinline__ float load_elem<LQER_BF16>(const void* p, int64_t i) {
   return __uint_as_float(((uint32_t)((const bf16_t*)p)[i]) << 16);
+}
+
+// ---- 16-bit pairs and 16-element pieces of the caller dtypes -> fp32: the one spelling every kernel uses ------------------------
+// the two 16-bit elements of one dword (fp16 or bf16)
+template <int DT>
+__device__ __forceinline__ void pair_to_f32(uint32_t word, float& lo, float& hi) {
+  static_assert(DT != LQER_F32, "16-bit types");
+  if constexpr (DT == LQER_F16) {
+    typedef __attribute__((ext_vector_type(2))) _Float16 h2;
+    const h2 h = __builtin_bit_cast(h2, word);
+    lo = (float)h[0], hi = (float)h[1];
+  } else {
+    lo = __uint_as_float(word << 16), hi = __uint_as_float(word & 0xffff0000u);
+  }
+}
+
+// 16 consecutive elements as the bytes they are stored in: 16-byte loads of an aligned piece (a request that costs 8 registers for
+// the 16-bit types, issued ahead and converted at its use)
+template <int DT>
+struct Raw16 {
+  static constexpr int N = DT == LQER_F32 ? 4 : 2;
+  u32x4 r[N];
+};
+template <int DT>
+__device__ __forceinline__ void load_raw16(const void* x, int64_t off, Raw16<DT>& b) {
+  const u32x4* p = (const u32x4*)((const char*)x + off * (DT == LQER_F32 ? 4 : 2));
+#pragma unroll
+  for (int i = 0; i < Raw16<DT>::N; ++i) b.r[i] = p[i];
+}
+template <int DT>
+__device__ __forceinline__ void raw16_to_f32(const Raw16<DT>& b, float (&v)[16]) {
+  if constexpr (DT == LQER_F32) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = __uint_as_float(b.r[i >> 2][i & 3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float lo, hi;
+      pair_to_f32<DT>(b.r[i >> 2][i & 3], lo, hi);
+      v[2 * i] = lo, v[2 * i + 1] = hi;
+    }
+  }
+}
+
+// 16 consecutive elements at x + off: the aligned, complete piece ...
+template <int DT>
+__device__ __forceinline__ void load16_vec(const void* x, int64_t off, float (&v)[16]) {
+  // (its own loads, not load_raw16 + raw16_to_f32: that form reorders or grows 67 kernels and spills in one - profiles/shared_pieces_codeobj.txt)
+  if constexpr (DT == LQER_F32) {
+    const float4* p = (const float4*)((const float*)x + off);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float4 t = p[i];
+      v[4 * i] = t.x, v[4 * i + 1] = t.y, v[4 * i + 2] = t.z, v[4 * i + 3] = t.w;
+    }
+  } else {
+    const uint4* p = (const uint4*)((const bf16_t*)x + off);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const uint4 t = p[i];
+      const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float lo, hi;
+        pair_to_f32<DT>(w[j], lo, hi);
+        v[8 * i + 2 * j] = lo, v[8 * i + 2 * j + 1] = hi;
+      }
+    }
+  }
+}
+// ... or whatever of it exists (`valid` elements up to the end of the row, zeros behind them), 128-bit loads when `vec` says the
+// piece is aligned
+template <int DT>
+__device__ __forceinline__ void load16(const void* x, int64_t off, int64_t valid, bool vec, float (&v)[16]) {
+  if (vec && valid >= 16) {
+    load16_vec<DT>(x, off, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = i < valid ? load_elem<DT>(x, off + i) : 0.0f;
+  }
 }
 
 // Internal fourth element type of the GEMM kernels: fp16 output AND fp16 activations multiplied natively
@@ -368,6 +450,40 @@ __device__ __forceinline__ void mxint16_i8_fast(const float (&v)[16], int e, con
 // bf16 bits of an exactly representable fp32 value (low 16 bits are zero by construction).
 __device__ __forceinline__ uint32_t exact_bf16_bits(float v) { return __float_as_uint(v) >> 16; }
 
+// N = 16 or 8 values of one block of 16 under its exponent e -> their exact bf16 image (w[i]: elements 2 i, 2 i + 1): the packed route
+// where the scale factors are normal floats, else element by element.  Callers that find the block maximum across lanes (or take
+// block_exponent_u) compute e themselves and call this.
+template <bool FLUSH_TINY, int N>
+__device__ __forceinline__ void mxint_bf16_image(const float (&v)[N], int e, const QP& q, uint32_t (&w)[N / 2]) {
+  if (mxint16_fast_ok(e, q)) {
+    mxint16_bf16_fast<FLUSH_TINY, N>(v, e, q, w);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) {
+      const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
+      const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
+      w[i] = lo | (hi << 16);
+    }
+  }
+}
+
+// THE block-of-16 quantizer: one block held by one lane -> 16 exact bf16 values (block_fp.py:7-82; zero block -> zeros; |x| <= 1e-8
+// flushed to 0 - FLUSH_TINY is false for fp16 inputs, which cannot hold a non-zero |x| <= 1e-8: four instructions less per pair).
+// Every bit-parity claim between kernels (one-launch decode = two-launch route, cached attention = raw attention, fused = split)
+// is this function called on both sides.
+template <bool FLUSH_TINY = true>
+__device__ __forceinline__ void quant16_bf16(const float (&v)[16], const QP& q, uint32_t (&w)[8]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = 0;
+  if (amax > 0.f) {
+    const int e = block_exponent(amax, q);
+    mxint_bf16_image<FLUSH_TINY, 16>(v, e, q, w);
+  }
+}
+
 // max over the 16 lanes of a DPP row (lanes 16g..16g+15); every lane of the row gets the result.
 __device__ __forceinline__ float row16_max(float v) {
   int t;
@@ -404,8 +520,6 @@ __device__ __forceinline__ uint32_t exp_byte_bits(uint32_t v) {
 // v_cvt_scalef32_pk_bf16_fp8 converts two elements per instruction and applies the scale.
 // 14 VALU ops per 8 weights; every step is exact (integers 0..7 and powers of two).
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 __device__ __forceinline__ bf16x8 expand_frag(uint32_t word, uint32_t scale_bits) {
   const float scale = __uint_as_float(scale_bits);
   constexpr uint32_t LUT_LO = 0x44403800u, LUT_HI = 0x4E4C4A48u;  // e4m3 bytes of 0,1,2,3 | 4,5,6,7
@@ -611,14 +725,9 @@ __device__ __forceinline__ u32x2 row8_chunk(const u32x4 raw, bool live, int e, c
     const uint32_t wd[4] = {raw[0], raw[1], raw[2], raw[3]};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      f2 xv;
-      if constexpr (DT == LQER_F16) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        const h2 hv = __builtin_bit_cast(h2, wd[j]);
-        xv = (f2){(float)hv[0], (float)hv[1]};
-      } else {
-        xv = (f2){__uint_as_float(wd[j] << 16), __uint_as_float(wd[j] & 0xffff0000u)};
-      }
+      float x0, x1;
+      pair_to_f32<DT>(wd[j], x0, x1);
+      const f2 xv = {x0, x1};
       f2 r;
       if constexpr (FAST) {
         const f2 cc = {copysignf(es, xv[0]), copysignf(es, xv[1])};

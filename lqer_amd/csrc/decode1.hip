@@ -8,11 +8,12 @@
 //     (v_mfma_f32_16x16x32_bf16: 4 waves x 2 k-slices, the waves' tiles summed in a fixed order) and publish the partial tile of x A as 8-byte
 //     {value, tag} granules - one write-through (sc1) store each, the tag is this LAUNCH's nonce (host counter + dispatch id): no flag, no counter, nothing
 //     to reset (MI355X_MICROARCH.md, hand-off price list: data-tagged granules);
-//   * consumers (one per 16 output columns, as in gemm_smallm.hip): request their first weight panels, quantize ALL of x
+//   * consumers (one per 16 output columns; panels, lane geometry and expand are smallm_tile.h's, shared with gemm_smallm.hip): request their first weight panels, quantize ALL of x
 //     into an LDS image themselves (M x K <= 8 x 4096 elements: cheaper than waiting for another kernel), stream their
 //     packed weight rows through the MFMA, and only at the very end read the producers' granules (sc1 loads, requested as
 //     the weight stream ends so that their round trip passes under the cross-wave combine, polled until the tags match),
-//     sum them in a fixed slab order, apply A_out and run the side path epilogue of gemm_smallm.hip.
+//     sum them in a fixed slab order, apply A_out and run gemm_smallm.hip's side path epilogue.
+// x is quantized by common.h's quant16_bf16 - the function behind k_quant_xa16 and the attention kernels: bit-identical images.
 // The kernel is a chain of latencies (measured with -DLQER_D1_STAMPS, tools/d1_stamps.py, M = 1, K = N = 4096: first data
 // 1.4 us after entry - every kernel starts behind cold caches -, producers acked at ~3 us, weight stream done at ~4-5,
 // granule round trip 1.2, tail 1.8), so the tail is written for instruction COUNT: branch-free exponent rule, power-of-two
@@ -33,7 +34,7 @@
 #include <cstdio>
 #include <ctime>
 
-#include "common.h"
+#include "smallm_tile.h"
 
 namespace lqer {
 namespace d1 {
@@ -119,94 +120,6 @@ struct Args {
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 
-struct SmPanel {
-  u32x4 cw;
-  uint32_t ex;
-};
-
-template <int DT>
-__device__ __forceinline__ void load_block16(const void* x, int64_t off, float (&v)[16]) {
-  if constexpr (DT == LQER_F32) {
-    const float4* p = (const float4*)((const float*)x + off);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 t = p[i];
-      v[4 * i] = t.x, v[4 * i + 1] = t.y, v[4 * i + 2] = t.z, v[4 * i + 3] = t.w;
-    }
-  } else {
-    const uint4* p = (const uint4*)((const bf16_t*)x + off);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint4 t = p[i];
-      const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (DT == LQER_F16) {
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-          const h2 h = __builtin_bit_cast(h2, w[j]);
-          v[8 * i + 2 * j] = (float)h[0], v[8 * i + 2 * j + 1] = (float)h[1];
-        } else {
-          v[8 * i + 2 * j] = __uint_as_float(w[j] << 16), v[8 * i + 2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-        }
-      }
-    }
-  }
-}
-
-// the same block as the bytes it is stored in (a request that costs 8 registers for the 16-bit types, converted at its use)
-template <int DT>
-struct RawBlk {
-  u32x4 r[DT == LQER_F32 ? 4 : 2];
-};
-template <int DT>
-__device__ __forceinline__ void load_raw16(const void* x, int64_t off, RawBlk<DT>& b) {
-  const u32x4* p = (const u32x4*)((const char*)x + off * (DT == LQER_F32 ? 4 : 2));
-#pragma unroll
-  for (int i = 0; i < (DT == LQER_F32 ? 4 : 2); ++i) b.r[i] = p[i];
-}
-template <int DT>
-__device__ __forceinline__ void raw16_to_f32(const RawBlk<DT>& b, float (&v)[16]) {
-  if constexpr (DT == LQER_F32) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = __uint_as_float(b.r[i >> 2][i & 3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint32_t w = b.r[i >> 2][i & 3];
-      if constexpr (DT == LQER_F16) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        const h2 h = __builtin_bit_cast(h2, w);
-        v[2 * i] = (float)h[0], v[2 * i + 1] = (float)h[1];
-      } else {
-        v[2 * i] = __uint_as_float(w << 16), v[2 * i + 1] = __uint_as_float(w & 0xffff0000u);
-      }
-    }
-  }
-}
-
-// one block of 16 -> its exact bf16 image (the arithmetic of k_quant_seg16 / k_quant_xa16: bit-identical images)
-template <int DT>
-__device__ __forceinline__ void quant_block16(const float (&v)[16], const QP& q, uint32_t (&w)[8]) {
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-#pragma unroll
-  for (int i = 0; i < 8; ++i) w[i] = 0;
-  if (amax > 0.f) {
-    const int e = block_exponent(amax, q);
-    if (mxint16_fast_ok(e, q)) {
-      mxint16_bf16_fast<DT != LQER_F16>(v, e, q, w);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
-        const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
-        w[i] = lo | (hi << 16);
-      }
-    }
-  }
-}
-
 // 16-byte chunk c of image row r (row pitch `pitch` bytes): chunks XOR-ed with 2 (r & 7), so that the rows one ds_read_b128
 // lane group touches (8 rows x two neighbouring chunks) spread over the 16 chunk slots of a 256-byte bank row
 __device__ __forceinline__ int img_off(int r, int c, int pitch) { return r * pitch + ((c ^ (2 * (r & 7))) << 4); }
@@ -277,8 +190,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
       uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       if (row < M && k0 < a.K) {
         float v[16];
-        load_block16<DT>(a.x, row * a.ldx + k0, v);
-        quant_block16<DT>(v, a.qx, w);
+        load16_vec<DT>(a.x, row * a.ldx + k0, v);
+        quant16_bf16<DT != LQER_F16>(v, a.qx, w);
       }
       if (tid == 0) D1_STAMP_AFTER(6, w[0]);
       *(uint4*)(pslab + img_off(row, 2 * seg, SLAB_K * 2)) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -360,12 +273,9 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
   // the member's x A is gathered once; the launch then fits the chip in ONE round whatever N and the group size are)
   const int cb_first = (cb_all - m_cb0) * a.cpw;
   const int nb_here = m_nblk - cb_first < a.cpw ? m_nblk - cb_first : a.cpw;
-  const int row = l15, q = lq;  // weight row / token within the tile; k group (gemm_smallm.hip's names)
+  const SmLane ln(lane);  // the lane's place in a packed panel (smallm_tile.h)
+  const int row = ln.row, q = ln.q;
   const int nk = Kp / 64;
-  const int codes_off = row * 32 + (q & 1) * 16;
-  const int exps_off = 512 + row * 4;
-  const bool hi = (q >> 1) != 0;
-  const int sh0 = 8 * (q >> 1), sh1 = 16 + 8 * (q >> 1);
   const bool lowrank = mb.bt != nullptr && rp > 0;
 
   // weight panels through a buffer descriptor: a request past the end is dropped by the range check,
@@ -382,8 +292,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
                         // of packed weights per token - 9.4 -> 9.0 us per forward over 48 rotating weights, bench d1; a single resident
                         // weight re-read from the Infinity Cache is slower with it, 4.8 -> 5.5 us: not what a model does)
 #endif
-    p.cw = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, codes_off, base, LQER_D1_WAUX));
-    p.ex = __builtin_amdgcn_raw_buffer_load_b32(w_rsrc, exps_off, base, LQER_D1_WAUX);
+    p.cw = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, ln.codes_off, base, LQER_D1_WAUX));
+    p.ex = __builtin_amdgcn_raw_buffer_load_b32(w_rsrc, ln.exps_off, base, LQER_D1_WAUX);
   };
   // wave w takes panels w, w + 8, ...; two register buffers of 4 panels
   constexpr int UNR = 4;
@@ -396,7 +306,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
   // wait for everything in flight at its first use; threads without such a block ignore the values.
   const int segs = Kp / 16;
   constexpr int XB = DT == LQER_F32 ? 2 : 4;  // (8 registers per 16-bit block, 16 per fp32 block)
-  RawBlk<DT> rb[XB];
+  Raw16<DT> rb[XB];
   auto request_x = [&](int b0) {
 #pragma unroll
     for (int u = 0; u < XB; ++u) {
@@ -426,7 +336,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
         if (seg * 16 < a.K) {
           float v[16];
           raw16_to_f32<DT>(rb[u], v);
-          quant_block16<DT>(v, a.qx, w);
+          quant16_bf16<DT != LQER_F16>(v, a.qx, w);
         }
         if (u == 0 && tid == 0) D1_STAMP_AFTER(6, w[0]);
         *(uint4*)(xs + img_off(r, 2 * seg, xpitch)) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -458,7 +368,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
       b.v1[u] = __builtin_amdgcn_raw_buffer_load_b128(gran_rsrc, (int)(off + 16u), 0, 16);
     }
   };
-  // ---- one column block's weight stream (gemm_smallm.hip's main loop with the activation fragments from LDS; token rows >= M
+  // ---- one column block's weight stream (gemm_smallm.hip's main loop - sm_expand per panel - with the activation fragments from LDS; token rows >= M
   // read row 0: their output columns are never stored), then (prefetch_c) the request for the NEXT block's first panels: they
   // travel under the combine and wave 0's epilogue (unconditional - past the workgroup's blocks the descriptor's range drops
   // them: no load under a branch)
@@ -476,9 +386,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
     asm volatile("" : "+v"(lrow));  // (re-derived per block: kept alive from the top of the kernel it costs a spill)
     const int xrow = lrow < M ? lrow : 0;
     auto compute_panel = [&](int kt, const SmPanel& p) {
-      const uint32_t w0 = hi ? p.cw[1] : p.cw[0], w1 = hi ? p.cw[3] : p.cw[2];
-      const bf16x8 wb0 = expand_frag(w0, ((p.ex >> sh0) & 0xffu) << 23);
-      const bf16x8 wb1 = expand_frag(w1, ((p.ex >> sh1) & 0xffu) << 23);
+      bf16x8 wb0, wb1;
+      sm_expand<false>(p, ln, wb0, wb1);
       const int kc = kt < nk ? kt : 0;  // (past the end: zero weights, any finite activation chunk)
       const bf16x8 x0 = *(const bf16x8*)(xs + img_off(xrow, kc * 8 + q, xpitch));
       const bf16x8 x1 = *(const bf16x8*)(xs + img_off(xrow, kc * 8 + 4 + q, xpitch));
@@ -551,14 +460,9 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
           s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb, xv, s, 0, 0, 0);
         }
       D1_STAMP_AFTER(9, s[0]);
-      if constexpr (BOUT == 1) {
+      if constexpr (BOUT == 1) {  // (the same text as gemm_smallm.hip's epilogue, written out in both: as a function it changes device code - profiles/shared_pieces_codeobj.txt, "not taken")
         float amax = fmaxf(fmaxf(fabsf(s[0]), fabsf(s[1])), fmaxf(fabsf(s[2]), fabsf(s[3])));
-        {  // max over lanes l, l ^ 16, l ^ 32 without the LDS crossbar: v_permlane16_swap / v_permlane32_swap
-          auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(amax), __float_as_uint(amax), false, false);
-          amax = fmaxf(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-          auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(amax), __float_as_uint(amax), false, false);
-          amax = fmaxf(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-        }
+        amax = quad16_max(amax);
         const int e = block_exponent(amax, g.bout);
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[j] = fabsf(s[j]) <= 1e-8f ? s[j] : mxint_value(s[j], e, g.bout);
@@ -661,7 +565,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
       if (!complete) __builtin_trap();  // its own write-through stores not visible after vmcnt(0): never sum untagged bytes
     }
     D1_STAMP(7);
-    // A_out in blocks of 16 = 4 consecutive threads
+    // A_out in blocks of 16 = 4 consecutive threads (gemm_smallm.hip's partials mode has the same text, written out in both: as a function it changes device code - profiles/shared_pieces_codeobj.txt, "not taken")
     float amax = fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fmaxf(fabsf(s.z), fabsf(s.w)));
     amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0xB1, 0xf, 0xf, true)));  // quad_perm [1,0,3,2]
     amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x4E, 0xf, 0xf, true)));  // quad_perm [2,3,0,1]

@@ -15,24 +15,14 @@
 // A B_out block (16 consecutive n of a token) is the 4 registers of the 4 lanes l, l^16, l^32, l^48.
 // The 8 waves' partial sums are added in a fixed order through LDS (bit-reproducible); wave 0 adds the side
 // path (MFMA straight from global memory, re-quantized in registers), the bias, and stores.
+// SmPanel, SmLane (the lane's place in a panel), sm_expand and quad16_max come from smallm_tile.h, shared with decode1.hip.
 #include "gemm_plan.h"
+#include "smallm_tile.h"
 
 namespace lqer {
 
 constexpr int SM_NW = 8;       // waves per workgroup: wave w takes panels w, w + 8, ...
 template <int MT> struct SmUnr { static constexpr int v = MT <= 2 ? 4 : 2; };  // panels per register buffer (two buffers)
-
-__device__ __forceinline__ float quad16_max(float v) {  // max over lanes l, l^16, l^32, l^48 (no LDS crossbar: the swaps)
-  auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-  auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-}
-
-struct SmPanel {
-  u32x4 cw;      // the lane's 16-byte half of its row's codes: chunks {h, h+2, h+4, h+6}, h = (lane >> 4) & 1
-  uint32_t ex;   // the row's 4 biased block exponents
-};
 
 template <int DT, bool LOWRANK, int BOUT, int MT>
 __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
@@ -41,16 +31,11 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) bf16_t xaq_l[LOWRANK ? MT * 16 * 64 : 8];  // [token][rp <= 64]: x A after A_out (partials mode)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int row = lane & 15, q = lane >> 4;  // weight row / token within the tile; k group
+  const SmLane ln(lane);
+  const int row = ln.row, q = ln.q;  // weight row / token within the tile; k group
   const int n0 = blockIdx.x * 16;
   const int nk = g.Kp / 64;
   const uint8_t* prow = g.wp + (int64_t)blockIdx.x * nk * LQER_PANEL_BYTES;
-  // the lane's words for the two 32-deep halves of a panel: chunks q and q + 4 = words q >> 1 and (q >> 1) + 2 of
-  // the half-row it loads; their block exponents are bytes q >> 1 and 2 + (q >> 1)
-  const int codes_off = row * 32 + (q & 1) * 16;
-  const int exps_off = 512 + row * 4;
-  const bool hi = (q >> 1) != 0;
-  const int sh0 = 8 * (q >> 1), sh1 = 16 + 8 * (q >> 1);
 
   f32x4 acc[MT];
 #pragma unroll
@@ -71,8 +56,8 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
   }
   auto load_panel = [&](int kt, SmPanel& p, bf16x8 (&x)[MT][2]) {
     const uint8_t* pp = prow + (int64_t)kt * LQER_PANEL_BYTES;
-    p.cw = *(const u32x4*)(pp + codes_off);
-    p.ex = *(const uint32_t*)(pp + exps_off);
+    p.cw = *(const u32x4*)(pp + ln.codes_off);
+    p.ex = *(const uint32_t*)(pp + ln.exps_off);
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       // token rows beyond M load nothing: the activation image (M x K x 2 B, read by every workgroup from L2) is
@@ -86,9 +71,8 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
     }
   };
   auto compute_panel = [&](const SmPanel& p, const bf16x8 (&x)[MT][2]) {
-    const uint32_t w0 = hi ? p.cw[1] : p.cw[0], w1 = hi ? p.cw[3] : p.cw[2];
-    const bf16x8 wb0 = expand_frag_t<XF16>(w0, ((p.ex >> sh0) & 0xffu) << 23);
-    const bf16x8 wb1 = expand_frag_t<XF16>(w1, ((p.ex >> sh1) & 0xffu) << 23);
+    bf16x8 wb0, wb1;
+    sm_expand<XF16>(p, ln, wb0, wb1);
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       acc[t] = mfma_16x16x32<XF16>(wb0, x[t][0], acc[t]);
@@ -110,7 +94,7 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
     if (from_partials) {
       // (after the first weight panels have been requested: the partial tiles' round trip passes under the weight stream's)
       // x A = sum over the split-K chunks, ascending (the order of k_xa_reduce4: same bits as the three-launch route),
-      // then A_out in blocks of 16 = 4 consecutive lanes; the bf16 image goes to LDS for wave 0's epilogue (it is read
+      // then A_out in blocks of 16 = 4 consecutive lanes (decode1.hip has the same text, written out in both: as a function it changes device code - profiles/shared_pieces_codeobj.txt, "not taken"); the bf16 image goes to LDS for wave 0's epilogue (it is read
       // after the combine barrier below).  One lane per 4 rank entries; M * rp / 4 <= 1024 items on 512 lanes.
       const int total = g.M * g.rp / 4;
       for (int base = 0; base < total; base += 64 * SM_NW) {
@@ -204,7 +188,7 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
           }
           s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb, xv, s, 0, 0, 0);
         }
-      if constexpr (BOUT == 1) {
+      if constexpr (BOUT == 1) {  // (the same text as decode1.hip's epilogue, written out in both: as a function it changes device code - profiles/shared_pieces_codeobj.txt, "not taken")
         float amax = fmaxf(fmaxf(fabsf(s[0]), fabsf(s[1])), fmaxf(fabsf(s[2]), fabsf(s[3])));
         amax = quad16_max(amax);
         const int e = block_exponent(amax, g.bout);  // amax = 0: every element takes the pass-through

@@ -52,7 +52,7 @@ __device__ __forceinline__ void store_kblock4(const float (&x)[4][16], const QP&
 template <int DT>
 __device__ __forceinline__ void store_vrow16(const void* vn, int64_t off, bool vec, const QP& qv, unsigned char* vc, unsigned char* ve) {
   float x[16];
-  qmm::load16<DT>(vn, off, 16, vec, x);
+  load16<DT>(vn, off, 16, vec, x);
   uint32_t cw[4];
   const uint32_t eb = quant16_codes<DT != LQER_F16>(x, qv, cw);
   *(uint4*)vc = make_uint4(cw[0], cw[1], cw[2], cw[3]);

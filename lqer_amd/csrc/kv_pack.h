@@ -226,13 +226,9 @@ __device__ __forceinline__ void load4(const void* base, int64_t off, bool vec, f
       const uint32_t wd[2] = {t.x, t.y};
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if constexpr (DT == LQER_F16) {
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-          const h2 hv = __builtin_bit_cast(h2, wd[j]);
-          v[2 * j] = (float)hv[0], v[2 * j + 1] = (float)hv[1];
-        } else {
-          v[2 * j] = __uint_as_float(wd[j] << 16), v[2 * j + 1] = __uint_as_float(wd[j] & 0xffff0000u);
-        }
+        float lo, hi;  // (into locals first: bound to the array elements directly, four k_kv_append kernels come out reordered)
+        pair_to_f32<DT>(wd[j], lo, hi);
+        v[2 * j] = lo, v[2 * j + 1] = hi;
       }
     }
   } else {

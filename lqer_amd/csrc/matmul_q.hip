@@ -104,8 +104,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void k_qmatmul(const void
         float v[16];
         Raw16<DT> raw;
 #pragma unroll
-        for (int n = 0; n < NR; ++n) raw.r[n] = st.x[u][n];
-        raw_to_f32<DT>(raw, v);
+        for (int n = 0; n < NR; ++n) raw.r[n] = __builtin_bit_cast(u32x4, st.x[u][n]);
+        raw16_to_f32<DT>(raw, v);
         quant16_bf16<DT != LQER_F16>(v, q, w[u]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) w[u][e] = live ? w[u][e] : 0u;

@@ -1,6 +1,6 @@
 // The operand-image side of the quantized attention products, shared by matmul_q.hip (the two separate products) and
-// attn_q.hip (the fused attention): 16-element loads, the block-of-16 quantizer to exact bf16 values, and the two kernels
-// that write w_quantizer(y) as a bf16 image [b][j][k], k contiguous.
+// attn_q.hip (the fused attention): the two kernels that write w_quantizer(y) as a bf16 image [b][j][k], k contiguous.  The
+// 16-element loads are common.h's load16 / Raw16, the block-of-16 quantizer is common.h's quant16_bf16.
 #pragma once
 #include <type_traits>
 
@@ -11,97 +11,6 @@ namespace lqer {
 namespace qmm {
 
 constexpr int BM = 128, BN = 128, BK = 64;
-
-// 16 consecutive elements (or fewer at the end of a row), 128-bit loads when the piece is aligned and complete
-template <int DT>
-__device__ __forceinline__ void load16(const void* base, int64_t off, int64_t valid, bool vec, float (&v)[16]) {
-  if (vec && valid >= 16) {
-    if constexpr (DT == LQER_F32) {
-      const float4* p = (const float4*)((const float*)base + off);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 t = p[i];
-        v[4 * i] = t.x, v[4 * i + 1] = t.y, v[4 * i + 2] = t.z, v[4 * i + 3] = t.w;
-      }
-    } else {
-      const uint4* p = (const uint4*)((const bf16_t*)base + off);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const uint4 t = p[i];
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (DT == LQER_F16) {
-            typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-            const h2 h = __builtin_bit_cast(h2, w[j]);
-            v[8 * i + 2 * j] = (float)h[0], v[8 * i + 2 * j + 1] = (float)h[1];
-          } else {
-            v[8 * i + 2 * j] = __uint_as_float(w[j] << 16), v[8 * i + 2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-          }
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = i < valid ? load_elem<DT>(base, off + i) : 0.0f;
-  }
-}
-
-// 16 consecutive elements as raw 16-byte loads (the aligned fast path: requested chunks ahead, converted at use)
-template <int DT>
-struct Raw16 {
-  static constexpr int N = DT == LQER_F32 ? 4 : 2;
-  uint4 r[N];
-};
-template <int DT>
-__device__ __forceinline__ void raw_to_f32(const Raw16<DT>& raw, float (&v)[16]) {
-  if constexpr (DT == LQER_F32) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[4 * i] = __uint_as_float(raw.r[i].x), v[4 * i + 1] = __uint_as_float(raw.r[i].y);
-      v[4 * i + 2] = __uint_as_float(raw.r[i].z), v[4 * i + 3] = __uint_as_float(raw.r[i].w);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint32_t w[4] = {raw.r[i].x, raw.r[i].y, raw.r[i].z, raw.r[i].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (DT == LQER_F16) {
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-          const h2 h = __builtin_bit_cast(h2, w[j]);
-          v[8 * i + 2 * j] = (float)h[0], v[8 * i + 2 * j + 1] = (float)h[1];
-        } else {
-          v[8 * i + 2 * j] = __uint_as_float(w[j] << 16), v[8 * i + 2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-        }
-      }
-    }
-  }
-}
-
-// one block of 16 -> 16 exact bf16 values (block_fp.py:7-82; zero block -> zeros; |x| <= 1e-8 flushed to 0 - FLUSH_TINY is
-// false for fp16 inputs, which cannot hold a non-zero |x| <= 1e-8: four instructions less per pair in the hot loop)
-template <bool FLUSH_TINY = true>
-__device__ __forceinline__ void quant16_bf16(const float (&v)[16], const QP& q, uint32_t (&w)[8]) {
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-#pragma unroll
-  for (int i = 0; i < 8; ++i) w[i] = 0;
-  if (amax > 0.f) {
-    const int e = block_exponent(amax, q);
-    if (mxint16_fast_ok(e, q)) {
-      mxint16_bf16_fast<FLUSH_TINY>(v, e, q, w);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
-        const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
-        w[i] = lo | (hi << 16);
-      }
-    }
-  }
-}
 
 // PRE: the values are ALREADY the quantizer's outputs (the standalone quantizer ran over the operand: block lengths other than
 // 16 - 16 n or whole rows - of formats whose values are bf16 numbers, width <= 9): the bf16 image is their high halves

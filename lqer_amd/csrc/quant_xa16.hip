@@ -6,40 +6,6 @@
 // ONE partial per workgroup.  The activation image is not read back from HBM for the side path.
 #include "xa_common.h"
 namespace lqer {
-template <int DT>
-__device__ __forceinline__ void qx_load16(const void* x, int64_t base, int64_t k0, int64_t cols, bool vec, float (&v)[16]) {
-  if (vec && k0 + 16 <= cols) {
-    if constexpr (DT == LQER_F32) {
-      const float4* p = (const float4*)((const float*)x + base + k0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 t = p[i];
-        v[4 * i] = t.x, v[4 * i + 1] = t.y, v[4 * i + 2] = t.z, v[4 * i + 3] = t.w;
-      }
-    } else {
-      const uint4* p = (const uint4*)((const bf16_t*)x + base + k0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const uint4 t = p[i];
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (DT == LQER_F16) {
-            typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-            const h2 h = __builtin_bit_cast(h2, w[j]);
-            v[8 * i + 2 * j] = (float)h[0], v[8 * i + 2 * j + 1] = (float)h[1];
-          } else {
-            v[8 * i + 2 * j] = __uint_as_float(w[j] << 16), v[8 * i + 2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-          }
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = (k0 + i < cols) ? load_elem<DT>(x, base + k0 + i) : 0.0f;
-  }
-}
-
 __device__ __forceinline__ int qx_swz(int row, int chunk) { return row * (QX_K * 2) + ((chunk ^ (row & 15)) << 4); }
 
 template <int DT, int NT>
@@ -75,22 +41,13 @@ __global__ __launch_bounds__(QX_K) void k_quant_xa16(const void* __restrict__ x,
     if (k0 < Kp) {
       if (m < M && k0 < K) {
         float v[16];
-        qx_load16<DT>(x, m * ldx, k0, K, vec, v);
+        load16<DT>(x, m * ldx + k0, K - k0, vec, v);
         float amax = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
         if (amax > 0.f) {
           const int e = block_exponent_u(amax, q);
-          if (mxint16_fast_ok(e, q)) {
-            mxint16_bf16_fast<DT != LQER_F16>(v, e, q, w);
-          } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-              const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, q), e - q.mbits));
-              const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, q), e - q.mbits));
-              w[i] = lo | (hi << 16);
-            }
-          }
+          mxint_bf16_image<DT != LQER_F16, 16>(v, e, q, w);
         }
       }
       uint4* dst = (uint4*)(xq + m * Kp + k0);   // rows up to the padded M are allocated

@@ -14,36 +14,14 @@
 
 namespace lqer {
 
+// The block at (row base, k0) of a row of `cols` elements: VEC - the aligned, complete piece (common.h's load16_vec); else element by
+// element, zeros past the row.  The tail keeps its own spelling, `k0 + i < cols` per element, instead of common.h's load16 (`i < valid`
+// with valid = cols - k0): with that one 21 kernels of this file change, and on the GPU k_quant_row<F32> is 2 us of 46 slower, k_quant_seg16<F32>,
+// k_quant_blk and k_quant_mf 0.2 - 0.4 us (profiles/shared_pieces_codeobj.txt, "not taken"; shared_pieces_ab.json).
 template <int DT, bool VEC>
-__device__ __forceinline__ void load16(const void* x, int64_t base, int64_t k0, int64_t cols, float (&v)[16]) {
+__device__ __forceinline__ void load_blk16(const void* x, int64_t base, int64_t k0, int64_t cols, float (&v)[16]) {
   if constexpr (VEC) {
-    if constexpr (DT == LQER_F32) {
-      const float4* p = (const float4*)((const float*)x + base + k0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float4 t = p[i];
-        v[4 * i] = t.x, v[4 * i + 1] = t.y, v[4 * i + 2] = t.z, v[4 * i + 3] = t.w;
-      }
-    } else {
-      const uint4* p = (const uint4*)((const bf16_t*)x + base + k0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        uint4 t = p[i];
-        uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (DT == LQER_F16) {
-            typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-            h2 h = __builtin_bit_cast(h2, w[j]);
-            v[8 * i + 2 * j] = (float)h[0];
-            v[8 * i + 2 * j + 1] = (float)h[1];
-          } else {
-            v[8 * i + 2 * j] = __uint_as_float(w[j] << 16);
-            v[8 * i + 2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-          }
-        }
-      }
-    }
+    load16_vec<DT>(x, base + k0, v);
   } else {
 #pragma unroll
     for (int i = 0; i < 16; ++i) v[i] = (k0 + i < cols) ? load_elem<DT>(x, base + k0 + i) : 0.0f;
@@ -111,9 +89,9 @@ __global__ __launch_bounds__(256) void k_quant_seg16(const void* __restrict__ x,
     const int64_t k0 = (idx - row * segs) * 16;
     float v[16];
     if (k0 + 16 <= cols) {
-      load16<DT, VEC>(x, row * ld, k0, cols, v);
+      load_blk16<DT, VEC>(x, row * ld, k0, cols, v);
     } else {
-      load16<DT, false>(x, row * ld, k0, cols, v);
+      load_blk16<DT, false>(x, row * ld, k0, cols, v);
     }
     float amax = 0.0f;
 #pragma unroll
@@ -147,9 +125,9 @@ __global__ __launch_bounds__(256) void k_quant_row(const void* __restrict__ x, i
       for (int i = 0; i < 16; ++i) v[j][i] = 0.f;
       if (sg < segs && sg * 16 < cols) {
         if (vec && sg * 16 + 16 <= cols)
-          load16<DT, true>(x, row * ld, sg * 16, cols, v[j]);
+          load_blk16<DT, true>(x, row * ld, sg * 16, cols, v[j]);
         else
-          load16<DT, false>(x, row * ld, sg * 16, cols, v[j]);
+          load_blk16<DT, false>(x, row * ld, sg * 16, cols, v[j]);
       }
 #pragma unroll
       for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[j][i]));
@@ -173,7 +151,7 @@ __global__ __launch_bounds__(256) void k_quant_row(const void* __restrict__ x, i
   } else {
     for (int64_t s = threadIdx.x; s < segs; s += 256) {
       float t[16];
-      load16<DT, false>(x, row * ld, s * 16, cols, t);
+      load_blk16<DT, false>(x, row * ld, s * 16, cols, t);
       emit16(t, any, e, q, o, row, s * 16, cols);
     }
   }
@@ -250,7 +228,7 @@ __global__ __launch_bounds__(256) void k_quant_blk(const void* __restrict__ x, i
     const int e = any ? block_exponent_u(amax, q) : 0;
     for (int64_t k0 = b0; k0 < b1; k0 += 16) {
       float v[16];
-      load16<DT, false>(x, row * ld, k0, cols, v);
+      load_blk16<DT, false>(x, row * ld, k0, cols, v);
       emit16(v, any, e, q, o, row, k0, cols);
     }
     if (o.exps && b0 < cols) o.exps[row * o.nblk + b0 / L] = (int8_t)(e > 127 ? 127 : e);
@@ -269,7 +247,7 @@ __global__ __launch_bounds__(256) void k_quant_int(const void* __restrict__ x, i
     const int64_t row = idx / segs;
     const int64_t k0 = (idx - row * segs) * 16;
     float v[16], m[16];
-    load16<DT, false>(x, row * ld, k0, cols, v);  // (elements past `cols` read as 0 -> code 0)
+    load_blk16<DT, false>(x, row * ld, k0, cols, v);  // (elements past `cols` read as 0 -> code 0)
 #pragma unroll
     for (int i = 0; i < 16; ++i) m[i] = mxint_mantissa(v[i], 0, q);
     if (o.xq) {
@@ -304,8 +282,8 @@ __global__ __launch_bounds__(256) void k_quant_mf(const void* __restrict__ x, in
     const int64_t k0 = (idx - row * segs) * 16;
     float v[16], m[16];
     int c[16];
-    if (VEC && k0 + 16 <= cols) load16<DT, true>(x, row * ld, k0, cols, v);
-    else load16<DT, false>(x, row * ld, k0, cols, v);  // (elements past `cols` read as 0 -> 0)
+    if (VEC && k0 + 16 <= cols) load_blk16<DT, true>(x, row * ld, k0, cols, v);
+    else load_blk16<DT, false>(x, row * ld, k0, cols, v);  // (elements past `cols` read as 0 -> 0)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const float a = fabsf(v[i]);

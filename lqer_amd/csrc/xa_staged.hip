@@ -282,13 +282,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_quant_xa128(const uint8_t* __res
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const uint32_t u = valid ? wd[j] : 0u;
-      if constexpr (DT == LQER_F16) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        const h2 hv = __builtin_bit_cast(h2, u);
-        v[2 * j] = (float)hv[0], v[2 * j + 1] = (float)hv[1];
-      } else {
-        v[2 * j] = __uint_as_float(u << 16), v[2 * j + 1] = __uint_as_float(u & 0xffff0000u);
-      }
+      pair_to_f32<DT>(u, v[2 * j], v[2 * j + 1]);
     }
     float amax = 0.f;
 #pragma unroll

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B timing of lqer_quantize_act_xa (fused activation quantize + side path) across library builds, C2 operands.
-usage: python tools/ab_quant.py [--M m --K k --r r] lib_a.so lib_b.so ..."""
+usage: python tools/ab_quant.py [--M m --K k --r r] [--tuning 0x800000] lib_a.so lib_b.so ...
+(--tuning: lqer_linear_desc_t.tuning, e.g. LQER_TUNE_ACT16_SPLIT = 0x800000 for k_quant_xa16 + reduce instead of the one-launch kernel)"""
 import ctypes as C, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,6 +10,7 @@ from tools.ab_gemm import load
 import argparse
 ap = argparse.ArgumentParser()
 ap.add_argument("--M", type=int, default=2048); ap.add_argument("--K", type=int, default=4096); ap.add_argument("--r", type=int, default=32)
+ap.add_argument("--tuning", type=lambda v: int(v, 0), default=0)
 ap.add_argument("--nocheck", action="store_true", help="ablation builds: skip the cross-build checksum")
 ap.add_argument("libs", nargs="+")
 args = ap.parse_args()
@@ -17,7 +19,7 @@ rp = -(-r // 16) * 16
 dev = torch.device("cuda:0")
 x = torch.randn(M, K, dtype=torch.float16, device=dev)
 f8 = _lib.QFmt(1, 8, 16, 8, 127); f4 = _lib.QFmt(1, 4, 16, 8, 127)
-desc = _lib.LinearDesc(K, N, r, 0, f8, f4, f8, f8, f8)
+desc = _lib.LinearDesc(K, N, r, 0, f8, f4, f8, f8, f8, args.tuning)
 at = (0.01 * torch.randn(3, rp, K)).to(torch.bfloat16).to(dev)
 xq = torch.empty(-(-M // 256) * 256, K, dtype=torch.bfloat16, device=dev)
 xaq = torch.empty(-(-M // 256) * 256, rp, dtype=torch.bfloat16, device=dev)
