@@ -669,7 +669,7 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * <= max_len.  A call that breaks this reads or writes outside the pool.  Nothing depends on the contents of a page beyond its
  * sequence's length or on staging rows beyond len % 16: pages and slots are reused dirty, a fresh pool needs no initialisation.
  * lqer_kv_pool_append: k_new / v_new [batch][kv_heads][n][D] of DT through k_strides[3] / v_strides[3], n >= 1 uniform over the call
- * (a decode step: n = 1 for every live sequence; a prompt: a call with batch = 1).  Per sequence lqer_kv_cache_append's semantics, word
+ * (a decode step: n = 1 for every live sequence; a prompt: a call with batch = 1; counts of their own: lqer_kv_pool_append_ragged).  Per sequence lqer_kv_cache_append's semantics, word
  * for word: V rows quantized and stored at once, every block of 16 keys the new keys touch re-quantized from the staging rows plus the
  * new keys, zero-padded on the right, and rewritten whole, the raw keys of the block left open to the slot's staging rows.  ONE launch
  * on `stream` whatever the lengths are (the thread that reads a staging column also writes it); like the dense append it is issued
@@ -711,6 +711,31 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * below lens[b] - converted codes below lens[b], zeros from there on - which is all the attention kernel reads of them; image
  * workgroups beyond that leave at once, so a ragged batch pays for its keys and not for max_len.  Three launches on `stream` (K image,
  * V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
+ * PER-SEQUENCE TOKEN COUNTS - a scheduler step in which most sequences decode one token while a few take a prompt chunk - go through
+ * the two _ragged calls.  The metadata contract is the one above, with:
+ *   new_starts / q_starts  int32 [batch + 1], on the DEVICE, written by the caller: non-decreasing, starts[0] >= 0, starts[batch] <=
+ *                total.  Sequence b of the call owns tokens starts[b] .. starts[b + 1] - 1 of a packed [total][heads][D] tensor,
+ *                addressed through TWO strides - elements over token, then over head; D dense.  A count of 0 is allowed.
+ *   max_n / max_s  host: an upper bound on every count, 1 <= bound.  It sizes grids only - no result depends on it, and no host
+ *                decision depends on a device value.
+ * lqer_kv_pool_append_ragged: lqer_kv_pool_append's pool and metadata, then new_starts and max_n, k_new / v_new [total][kv_heads][D] of
+ * DT through k_strides[2] / v_strides[2].  Sequence b is appended n_b = new_starts[b + 1] - new_starts[b] keys: afterwards the pool's
+ * bytes for it - codes, exponents, the staging rows below len % 16 - are those lqer_kv_pool_append leaves with batch = 1, n = n_b on the
+ * same keys; with n_b = 0 no byte of its pages or staging rows is written.  lens[b] + n_b <= max_len is the caller's to keep.  ONE
+ * launch on `stream` whatever the counts are, its grid sized by max_n; threads beyond a sequence's n_b leave at once, and per sequence
+ * the thread that reads a staging column is still the one that writes it.  Refused as lqer_kv_pool_append, and LQER_E_INVALID for a
+ * null new_starts, max_n < 1 or > max_len, total < 0, null strides.
+ * lqer_attention_q_paged_ragged: lqer_attention_q_paged with S replaced by (q_starts, max_s, total): q and out are [total][heads][D]
+ * through q_strides[2] / out_strides[2], row_stats a dense [total][heads][2] fp32 or NULL.  For every b, the rows of sequence b in out
+ * and row_stats are the SAME BITS as lqer_attention_q with batch = 1, S = S_b = q_starts[b + 1] - q_starts[b] on the raw K and V of that
+ * sequence - whatever else is in the batch, whatever max_s, max_len and total are and whatever the workspace held.  Causal uses the
+ * sequence's own offset T_b - S_b (S_b <= T_b is the caller's to keep).  With S_b = 0 nothing is written for the sequence; with
+ * lens[b] = 0 its rows get zeros and no statistics, as above.  The attention grid's x is ceil(max_s / 128): a workgroup whose tile lies
+ * beyond its sequence's S_b leaves at once, and the causal "long tiles first" order follows the sequence's own tile count.
+ * workspace: lqer_attention_q_paged_ragged_workspace_bytes(batch, heads, kv_heads, max_s, max_len, D) =
+ * lqer_attention_q_paged_workspace_bytes at the same arguments - the two images, nothing that follows the counts.  Three launches on
+ * `stream` (K image, V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
+ * Refused as lqer_attention_q_paged, and LQER_E_INVALID for a null q_starts, max_s < 1, total < 0.
  * lqer_kv_pool_gather: one sequence - row `slot` of block_table, T keys (host) - out of the pool into a dense lqer_kv_cache buffer of
  * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
  * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack) and an export path (more than 8 query rows
@@ -740,6 +765,11 @@ int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t sl
                         const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const void* k_new, const void* v_new,
                         const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t n,
                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
+int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                               const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const int32_t* new_starts, int64_t max_n,
+                               const void* k_new, const void* v_new, const int64_t* k_strides, const int64_t* v_strides, int dtype,
+                               int64_t batch, int64_t kv_heads, int64_t D, int64_t total, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt,
+                               void* stream);
 int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
                         const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
                         int64_t capacity, void* stream);
@@ -766,6 +796,13 @@ int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, i
                            int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
                            const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                            const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
+size_t lqer_attention_q_paged_ragged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t max_s, int64_t max_len, int64_t D);
+int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
+                                  float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, const int32_t* q_starts,
+                                  int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling,
+                                  int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                                  const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's

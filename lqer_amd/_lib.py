@@ -150,6 +150,14 @@ SIGNATURES = {
     "lqer_attention_q_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
                                     _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    # per-sequence token counts in one call (a mixed prefill / decode step): new_starts / q_starts [batch + 1] on the device, a host bound
+    # on the counts, packed [total][heads][D] tensors through stride PAIRS (token, head)
+    "lqer_kv_pool_append_ragged": (_i, [_vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64,
+                                        _qp, _qp, _vp]),
+    "lqer_attention_q_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    # lqer_attention_q_paged's list with S -> (q_starts, max_s, total)
+    "lqer_attention_q_paged_ragged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64, _i64,
+                                           _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

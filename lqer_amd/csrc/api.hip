@@ -1148,7 +1148,7 @@ static const AttnKernel ATTN_PREFILL = {0, "kernel takes", prefill_grid_limits, 
 static const AttnKernel ATTN_DECODE = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, decode_workspace_bytes,
                                        attention_q_decode_dispatch};
 
-// the check of the six attention calls, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
+// the check of every attention call, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
 static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) {
   if (c.batch < 0 || c.heads <= 0 || c.kv_heads <= 0 || c.S < 0 || c.T < 0 || c.D <= 0) {
     set_error("%s: bad shape batch=%lld heads=%lld kv_heads=%lld S=%lld T=%lld D=%lld", who, (long long)c.batch, (long long)c.heads,
@@ -1199,8 +1199,13 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
                 "formats run as the two products of lqer_matmul_q", who, f->kind, f->block);
       return LQER_E_UNSUPPORTED;
     }
+  const bool ragged = c.paged && c.pool.ragged;  // (S: the bound max_s on the per-sequence counts, which sizes the grid)
+  if (ragged && c.S < 1) {
+    set_error("%s: max_s = %lld query rows (max_s >= 1 bounds every sequence's count)", who, (long long)c.S);
+    return LQER_E_INVALID;
+  }
   if (const int rc = kn.grid_limits(who, c)) return rc;
-  if (c.batch == 0 || c.S == 0) return 1;
+  if (c.batch == 0 || c.S == 0 || (ragged && c.pool.total == 0)) return 1;
   if (c.T == 0) {
     set_error("%s: T = 0 (a softmax over no keys)", who);
     return LQER_E_INVALID;
@@ -1343,7 +1348,8 @@ size_t lqer_kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_he
 
 // what append, attention and gather ask of a pool and its page table (host arguments only: the table's and the lengths' CONTENTS are
 // the caller's contract).  A call that addresses sequences through seq_slots / lens (append, attention) needs the two arrays; gather
-// names its slot on the host.  The quantizers are the caller's to check (kv_codes_check, attn_check).  LQER_OK or the refusal
+// names its slot on the host; a call with per-sequence counts (p.ragged) also needs their starts.  The quantizers are the caller's to
+// check (kv_codes_check, attn_check).  LQER_OK or the refusal
 enum PoolUse { POOL_BATCH, POOL_ONE_SLOT };
 static int kv_pool_check(const char* who, const KvPool& p, PoolUse use) {
   if (p.pages < 1 || p.slots < 1 || p.kv_heads < 1 || p.table_stride < 1 || p.D <= 0) {
@@ -1374,6 +1380,11 @@ static int kv_pool_check(const char* who, const KvPool& p, PoolUse use) {
   }
   if (!p.block_table || (use == POOL_BATCH && (!p.seq_slots || !p.lens))) {
     set_error("%s: null block_table / seq_slots / lens of the KV pool", who);
+    return LQER_E_INVALID;
+  }
+  if (p.ragged && (!p.starts || p.total < 0)) {
+    set_error("%s: starts %p / total = %lld of a call with per-sequence counts on the KV pool (new_starts / q_starts: int32 [batch + 1] on the "
+              "device, total >= 0 tokens)", who, (const void*)p.starts, (long long)p.total);
     return LQER_E_INVALID;
   }
   if (!p.pool) {
@@ -1419,6 +1430,38 @@ int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t sl
     return LQER_E_UNSUPPORTED;
   }
   return kv_pool_append_dispatch(p, k_new, v_new, k_strides, v_strides, batch, n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
+}
+
+int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                               const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const int32_t* new_starts, int64_t max_n,
+                               const void* k_new, const void* v_new, const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch,
+                               int64_t kv_heads, int64_t D, int64_t total, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
+  if (batch < 0 || max_n < 1) {
+    set_error("kv_pool_append_ragged: batch %lld / max_n %lld new keys for the KV pool (batch >= 0, max_n >= 1 bounds every sequence's count)",
+              (long long)batch, (long long)max_n);
+    return LQER_E_INVALID;
+  }
+  KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  p.ragged = true, p.starts = new_starts, p.total = total;
+  int rc = kv_codes_check("kv_pool_append_ragged", D, k_fmt, v_fmt);
+  if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append_ragged", p, POOL_BATCH);
+  if (rc != LQER_OK) return rc;
+  if (max_n > max_len) {
+    set_error("kv_pool_append_ragged: max_n %lld new keys beyond max_len %lld of the KV pool (a bound on lens[b] + n_b)", (long long)max_n,
+              (long long)max_len);
+    return LQER_E_INVALID;
+  }
+  if (batch == 0 || total == 0) return LQER_OK;
+  if (!k_new || !v_new || !k_strides || !v_strides) {
+    set_error("kv_pool_append_ragged: null pointer (new keys / values for the KV pool or their strides)");
+    return LQER_E_INVALID;
+  }
+  if (batch * kv_heads * ((max_n + 14) / 16 + 1 + max_n) > ((int64_t)1 << 31)) {  // (work items over grid.x, as lqer_kv_pool_append's at n = max_n)
+    set_error("kv_pool_append_ragged: max_n %lld new keys for %lld KV pool streams beyond one launch grid: append in pieces", (long long)max_n,
+              (long long)(batch * kv_heads));
+    return LQER_E_UNSUPPORTED;
+  }
+  return kv_pool_append_ragged_dispatch(p, k_new, v_new, k_strides, v_strides, batch, max_n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
 }
 
 int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
@@ -1586,6 +1629,28 @@ int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, i
   c.packed = c.paged = true;
   c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
   return attn_run("attention_q_paged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
+}
+
+size_t lqer_attention_q_paged_ragged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t max_s, int64_t max_len, int64_t D) {
+  return lqer_attention_q_paged_workspace_bytes(batch, heads, kv_heads, max_s, max_len, D);  // (the images only: nothing follows the counts)
+}
+
+int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                                  int dtype, int64_t batch, int64_t heads, int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total,
+                                  int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                  const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  // the stride pairs (token, head) as the triples (batch, head, row) the record holds: no batch stride - a sequence's rows start at
+  // its token q_starts[b]; S: the bound max_s - the check's, the grid's
+  const int64_t qs[3] = {0, q_strides ? q_strides[1] : 0, q_strides ? q_strides[0] : 0};
+  const int64_t os[3] = {0, out_strides ? out_strides[1] : 0, out_strides ? out_strides[0] : 0};
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, max_s, max_len, D, q_strides ? qs : nullptr, nullptr,
+                         out_strides ? os : nullptr, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  c.packed = c.paged = true;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
+  return attn_run("attention_q_paged_ragged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

@@ -23,7 +23,9 @@
 //                                   Key tiles of 64 go through LDS (rows padded against bank conflicts), the next tile's loads are
 //                                   requested before the current tile's MFMAs (register staging; one buffer, two barriers per tile).
 //                                   A second instantiation (PSL) reads each sequence's number of keys from the device: one call over
-//                                   the sequences of a paged pool (lqer_attention_q_paged).
+//                                   the sequences of a paged pool (lqer_attention_q_paged).  A third (RAG) also reads each sequence's
+//                                   number of query rows, and where they start in a packed [total][heads][D] tensor, from the device:
+//                                   a scheduler step of decoders and prompt chunks in one call (lqer_attention_q_paged_ragged).
 #include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16: shared with attn_decode.hip
 
 namespace lqer {
@@ -47,6 +49,9 @@ struct Args {
   QP q0, q1;  // Q_x0 (queries), Q_x1 (probabilities)
   bool qvec, mvec;
   const int32_t* lens;  // PSL: [batch] keys of the b-th sequence (device); T above is then the bound max_len the images' strides come from
+  const int32_t* q_starts;  // RAG: [batch + 1] (device) - sequence b's query rows are tokens q_starts[b] .. q_starts[b + 1] - 1 of q / out
+                            // [total][heads][D] (q_bs = o_bs = 0, q_rs / o_rs the token strides) and of stats [total][heads][2]; S above
+                            // is then the bound max_s the grid's x comes from
 };
 
 template <int DT>
@@ -67,29 +72,39 @@ __global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v,
 
 // PSL (per-sequence lengths, the paged pool): a workgroup takes T = lens[b] - and with it the causal offset and every key bound below -
 // from the device; Tp and Tv stay those of the bound.  A sequence of no keys gets zeros and no statistics.
-template <int DT, int DK, bool PSL = false>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
+// RAG (per-sequence query counts, with PSL): a workgroup also takes S = q_starts[b + 1] - q_starts[b] - and with it the causal offset
+// T - S, its sequence's own number of query tiles and their order - from the device, and finds its rows of q, out and the statistics
+// at token q_starts[b] + (row in the sequence).  The grid's x covers the bound max_s: a workgroup whose tile lies beyond its
+// sequence's S - every one of a sequence with S = 0 - leaves before any barrier, load or store.
+template <int DT, int DK, bool PSL = false, bool RAG = false>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
 __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
+  static_assert(!RAG || PSL, "per-sequence query counts come with per-sequence lengths");
   constexpr int KS = 64 * DK + 16;  // bytes of a key row in LDS (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
   constexpr int VS = 128 + 8;       // bytes of a V^T row (64 keys) in LDS (+8: the 8-byte reads of 32 rows hit 32 bank pairs)
   __shared__ __attribute__((aligned(16))) unsigned char sK[BT * KS];
   __shared__ __attribute__((aligned(16))) unsigned char sV[32 * DK * VS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-  const int64_t nq = (a.S + BQ - 1) / BQ;
-  const int64_t qt = a.mode == 2 ? nq - 1 - (int64_t)blockIdx.x : (int64_t)blockIdx.x;  // causal: the long tiles first
   const int64_t h = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + h / (a.heads / a.kv_heads);
+  int64_t S = a.S, row0 = 0;  // this sequence's query rows, and the token of its first (RAG; else row 0 of batch b)
+  if constexpr (RAG) {
+    row0 = a.q_starts[b], S = a.q_starts[b + 1] - row0;
+    if ((int64_t)blockIdx.x * BQ >= S) return;  // (uniform over the workgroup, before any barrier)
+  }
+  const int64_t nq = (S + BQ - 1) / BQ;
+  const int64_t qt = a.mode == 2 ? nq - 1 - (int64_t)blockIdx.x : (int64_t)blockIdx.x;  // causal: the long tiles first
   const int64_t q0 = qt * BQ, qi = q0 + wave * 32 + l31;
   int64_t T = a.T;
   if constexpr (PSL) {
     T = a.lens[b];
     if (T == 0) {  // (uniform over the workgroup, before any barrier)
-      if (qi < a.S) {
+      if (qi < S) {
         const float o4[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int d = 4 * lh; d < (int)a.D; d += 8) store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + qi * a.o_rs + d, d, (int)a.D, o4);
+        for (int d = 4 * lh; d < (int)a.D; d += 8) store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + (row0 + qi) * a.o_rs + d, d, (int)a.D, o4);
       }
       return;
     }
   }
-  const int64_t off = T - a.S;  // causal: key j is visible to query i iff j <= i + off
+  const int64_t off = T - S;  // causal: key j is visible to query i iff j <= i + off
   const float NEG_INF = -__builtin_inff();
 
   // ---- this lane's query row, quantized: fragment ks holds d = 16 ks + 8 lh .. + 7
@@ -97,9 +112,9 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
 #pragma unroll
   for (int ks = 0; ks < 2 * DK; ++ks) {
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (qi < a.S && ks * 16 < a.D) {
+    if (qi < S && ks * 16 < a.D) {
       float v[16];
-      load16<DT>(a.q, b * a.q_bs + h * a.q_hs + qi * a.q_rs + ks * 16, 16, a.qvec, v);
+      load16<DT>(a.q, b * a.q_bs + h * a.q_hs + (row0 + qi) * a.q_rs + ks * 16, 16, a.qvec, v);
       quant16_bf16<DT != LQER_F16>(v, a.q0, w);
     }
     const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
@@ -107,7 +122,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
 
   // ---- key tiles this workgroup / wave / lane looks at
-  const int64_t q_last = (q0 + BQ < a.S ? q0 + BQ : a.S) - 1;
+  const int64_t q_last = (q0 + BQ < S ? q0 + BQ : S) - 1;
   int64_t t_end = T;  // keys [0, t_end) are visible to some query of the workgroup
   if (a.mode == 2) {
     const int64_t e = q_last + off + 1;
@@ -121,7 +136,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
   int64_t tmax = T - 1;  // the last key visible to this lane's query
   if (a.mode == 2) tmax = qi + off < tmax ? qi + off : tmax;
-  const int64_t qic = qi < a.S ? qi : a.S - 1;
+  const int64_t qic = qi < S ? qi : S - 1;
   const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + qic * a.m_rs : 0;
 
   // (the staged pieces travel BY VALUE: arrays captured by reference in these lambdas ended up in scratch memory)
@@ -239,8 +254,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     const float mref = M == NEG_INF ? 0.f : M;
     L = l0 * exp_neg(m0 - mref) + l1 * exp_neg(m1 - mref);
   }
-  if (a.stats && lh == 0 && qi < a.S) {
-    float* st = a.stats + ((b * a.heads + h) * a.S + qi) * 2;
+  if (a.stats && lh == 0 && qi < S) {
+    float* st = a.stats + (RAG ? (row0 + qi) * a.heads + h : (b * a.heads + h) * S + qi) * 2;  // RAG: [total][heads][2]
     st[0] = M, st[1] = L;
   }
 
@@ -286,8 +301,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
 
   // ---- O^T: this lane's query, d = 32 dt + 8 (r >> 2) + 4 lh + (r & 3)
-  if (qi < a.S) {
-    const int64_t at0 = b * a.o_bs + h * a.o_hs + qi * a.o_rs;
+  if (qi < S) {
+    const int64_t at0 = b * a.o_bs + h * a.o_hs + (row0 + qi) * a.o_rs;
 #pragma unroll
     for (int dt = 0; dt < DK; ++dt)
 #pragma unroll
@@ -317,18 +332,20 @@ static int launch(const AttnCall& c, Args a) {
   a.mvec = a.mode == 1 && a.T % 4 == 0 && (uintptr_t)a.mask % (4 * esz) == 0 && a.m_bs % 4 == 0 && a.m_hs % 4 == 0 && a.m_rs % 4 == 0;
   const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)c.batch);
   const int dk = (int)((a.D + 31) / 32);
-  const auto go = [&](auto psl) {
-    constexpr bool PSL = decltype(psl)::value;
+  const auto go = [&](auto psl, auto rag) {
+    constexpr bool PSL = decltype(psl)::value, RAG = decltype(rag)::value;
     switch (dk) {
-      case 1: k_attn_q<DT, 1, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      case 2: k_attn_q<DT, 2, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      case 3: k_attn_q<DT, 3, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      default: k_attn_q<DT, 4, PSL><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 1: k_attn_q<DT, 1, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 2: k_attn_q<DT, 2, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 3: k_attn_q<DT, 3, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      default: k_attn_q<DT, 4, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
     }
   };
-  if (c.paged) go(std::true_type{});
-  else go(std::false_type{});
-  return check_launch(c.paged ? "lqer_attention_q_paged" : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));
+  const bool ragged = c.paged && c.pool.ragged;  // (a.S: the bound max_s - the grid's x; the kernel takes S from q_starts)
+  if (ragged) go(std::true_type{}, std::true_type{});
+  else if (c.paged) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{});
+  return check_launch(ragged ? "lqer_attention_q_paged_ragged" : c.paged ? "lqer_attention_q_paged" : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));
 }
 
 }  // namespace attn
@@ -361,6 +378,7 @@ int attention_q_dispatch(const AttnCall& c) {
   a.q0 = make_qp(*c.q_fmt), a.q1 = make_qp(*c.p_fmt);
   a.qvec = a.mvec = false;  // (attn::launch sets them)
   a.lens = c.paged ? c.pool.lens : nullptr;  // (paged: c.T is the bound max_len - the images' strides; the kernels take T from lens[b])
+  a.q_starts = c.paged && c.pool.ragged ? c.pool.starts : nullptr;  // (ragged: c.S is the bound max_s, qs / os hold {0, head, token})
   if (c.packed) kv_cache_images_dispatch(c, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv);
   return with_dtype(c.dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(c, a); });
 }

@@ -894,14 +894,15 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
 
 size_t qmatmul_workspace_bytes(int64_t batch, int64_t K, int64_t S2);  // matmul_q.hip
 size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t S2, bool x_pre, bool y_pre);
-// One attention call as the C ABI receives it: what the six entry points fill - lqer_attention_q and lqer_attention_q_decode, each from
+// One attention call as the C ABI receives it: what the attention entry points fill - lqer_attention_q and lqer_attention_q_decode, each from
 // raw K and V, from the packed cache (_kv) and from the paged pool (_paged) - their one check reads and the two dispatch functions launch from.  Host only - never a kernel argument.  `packed`: K and V come from the packed KV cache of
 // `capacity` keys (kv_pack.h) and k, v, ks, vs are unused; a flag of its own because a null `cache` is the cache's check to refuse, in
 // its words.  The dispatch functions read `packed` alone; past the checks it implies cache != nullptr.  The stride triples are the
 // caller's pointers: the check must see a null one.  `paged` (with `packed`, which it implies: no k, v, ks, vs): the codes live in
 // the paged pool `pool` instead of `cache`, T is the pool's max_len - the bound that sizes the grid and the workspace - and the kernels
 // (the decode kernels, or the image kernels and k_attn_q's per-sequence-length instantiation) read every sequence's own length from
-// the device.
+// the device.  With `pool.ragged` (lqer_attention_q_paged_ragged) S is the bound max_s, which sizes the grid alone, q / out are
+// [total][heads][D] - qs / os hold {0, head stride, token stride} - and k_attn_q takes every sequence's own S from pool.starts.
 struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayout); the three metadata arrays are DEVICE pointers
   const void* pool;
   size_t pool_bytes;
@@ -909,6 +910,11 @@ struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayo
   int64_t pages, slots, kv_heads, D;
   const int32_t *block_table, *seq_slots, *lens;
   int64_t table_stride, max_len;
+  // per-sequence token counts (lqer_kv_pool_append_ragged, lqer_attention_q_paged_ragged): sequence b of the call owns tokens
+  // starts[b] .. starts[b + 1] - 1 of a packed [total][heads][D] tensor; starts: DEVICE, [batch + 1]
+  bool ragged;
+  const int32_t* starts;
+  int64_t total;
 };
 struct AttnCall {
   bool packed, paged;
@@ -949,6 +955,8 @@ int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_
 size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D);
 int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
                             const QP& qk, const QP& qv, hipStream_t st);
+int kv_pool_append_ragged_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks2, const int64_t* vs2, int64_t batch,
+                                   int64_t max_n, const QP& qk, const QP& qv, hipStream_t st);  // (p.starts; strides over token / kv head)
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st);
 int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, hipStream_t st);  // (p.seq_slots: the children's slots)
 constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128

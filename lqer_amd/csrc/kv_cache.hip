@@ -6,7 +6,8 @@
 //                new K rows: every block of 16 keys they touch is quantized along t from the staging rows (the raw keys of the open
 //                block that were there before) plus the new keys, zero-padded on the right, and stored whole - codes of all 16 rows,
 //                the exponents of the block (a thread: 4 d of the 16 keys, as k_attn_dec_scores reads raw keys).  The raw keys of the
-//                block left open go to the staging rows.  One launch, whatever the length was (see the kernel).
+//                block left open go to the staging rows.  One launch, whatever the length was (see the kernel).  A third instantiation
+//                (RAG) takes every sequence's own number of new keys from the device (lqer_kv_pool_append_ragged).
 //   k_kv_unpack  code x 2^(e - mbits) as fp32, one element per thread.
 //   k_kv_pool_gather   one sequence's bytes out of the pool into a dense cache.
 //   k_kv_pool_fork     children that share their parents' full pages: the open block's item and the staging rows, copied per child.
@@ -30,6 +31,9 @@ struct AArgs {
   int64_t k_bs, k_hs, k_rs, v_bs, v_hs, v_rs;
   QP qk, qv;
   bool kvec, vvec;
+  const int32_t* starts;  // RAG: [batch + 1] (device) - sequence b's new keys are tokens starts[b] .. starts[b + 1] - 1 of kn / vn
+                          // [total][kv heads][D] (k_bs = v_bs = 0, k_rs / v_rs the token strides); n and nkb above are then those of the
+                          // bound max_n, which sizes the grid
 };
 
 // 4 d of one block of 16 keys (x[j][r]: d0 + j of key r) -> the codes of the 16 rows (row pitch D bytes, the four d as one dword) and
@@ -78,8 +82,13 @@ __device__ __forceinline__ void copy_raw4(const void* kn, int64_t src, bool vec,
 // of the launch that reads the staging column (slot, kv head, d0 .. d0 + 3), every later block starts beyond len - also writes that
 // column's new rows, after its reads in program order; no other thread of the launch touches the column (a slot - with the dense cache
 // the batch index - is named once per call: the pool's caller's contract), so there is no race and nothing to order between launches.
-template <int DT, int SRC>
+// RAG (per-sequence counts, the paged pool): the grid is laid out for the bound a.n = max_n and sequence b takes n_b = starts[b + 1] -
+// starts[b] from the device; its threads at a block or a key beyond n_b - all of them with n_b = 0 - leave at once, before any load
+// or store.  The argument above holds per sequence as it stands: block j = 0 of (sequence, kv head, d0) exists for every n_b >= 1, its
+// one thread is the only reader of the staging column and the only writer of it, reads first; the later blocks start beyond len.
+template <int DT, int SRC, bool RAG = false>
 __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
+  static_assert(!RAG || SRC == attn::SRC_PAGED, "per-sequence counts come with per-sequence lengths");
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int D = (int)a.D, dq = D / 4, db_n = D / 16;
   const int64_t kvh = a.src.kvh, Z = a.batch * kvh, nK = Z * a.nkb * dq, nV = Z * a.n * db_n;
@@ -88,12 +97,17 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
     const int64_t z = i / (a.nkb * dq), rem = i % (a.nkb * dq);
     const int64_t j = rem / dq, b = z / kvh, g = z % kvh;
     const int d0 = 4 * (int)(rem % dq);
-    const int64_t len = seq<SRC>(a.src, b, a.len, row), end = len + a.n, kb = len / 16 + j;
+    int64_t n = a.n, tok0 = 0;  // this sequence's new keys and the first one's token
+    if constexpr (RAG) {
+      tok0 = a.starts[b], n = a.starts[b + 1] - tok0;
+      if (n < 1) return;
+    }
+    const int64_t len = seq<SRC>(a.src, b, a.len, row), end = len + n, kb = len / 16 + j;
     if (kb > (end - 1) / 16) return;  // this sequence's new keys touch fewer blocks
     int64_t slot = b;
     if constexpr (SRC == attn::SRC_PAGED) slot = a.src.slots[b];
     const int64_t zs = slot * kvh + g, blk = block<SRC>(a.src, row, z, g, kb);
-    const int64_t kn0 = b * a.k_bs + g * a.k_hs + d0;
+    const int64_t kn0 = b * a.k_bs + tok0 * a.k_rs + g * a.k_hs + d0;
     float x[4][16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -114,10 +128,16 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
   i -= nK;
   if (i < nV) {  // ---- 16 d of one new key
     const int64_t z = i / (a.n * db_n), rem = i % (a.n * db_n);
-    const int64_t j = rem / db_n, b = z / kvh, g = z % kvh, t = seq<SRC>(a.src, b, a.len, row) + j;
+    const int64_t j = rem / db_n, b = z / kvh, g = z % kvh;
+    int64_t tok0 = 0;
+    if constexpr (RAG) {
+      tok0 = a.starts[b];
+      if (j >= a.starts[b + 1] - tok0) return;  // a key beyond this sequence's count
+    }
+    const int64_t t = seq<SRC>(a.src, b, a.len, row) + j;
     const int db = (int)(rem % db_n);
     const int64_t blk = block<SRC>(a.src, row, z, g, t / 16);
-    store_vrow16<DT>(a.vn, b * a.v_bs + g * a.v_hs + j * a.v_rs + 16 * db, a.vvec, a.qv, a.src.vc + (blk * 16 + t % 16) * a.D + 16 * db,
+    store_vrow16<DT>(a.vn, b * a.v_bs + g * a.v_hs + (tok0 + j) * a.v_rs + 16 * db, a.vvec, a.qv, a.src.vc + (blk * 16 + t % 16) * a.D + 16 * db,
                      a.src.ve + (blk * db_n + db) * 16 + t % 16);
   }
 }
@@ -307,12 +327,13 @@ size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capaci
   return kvc::layout(dtype, batch, kv_heads, capacity, D).total;
 }
 
-// the one append: nkb blocks of 16 keys per (sequence, kv head) on the grid (kvc::AArgs)
-template <int SRC>
+// the one append: nkb blocks of 16 keys per (sequence, kv head) on the grid (kvc::AArgs); starts: the per-sequence counts' (RAG), else null
+template <int SRC, bool RAG = false>
 static int kv_append(const kvc::KvSrc<unsigned char>& src, int dtype, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs,
-                     int64_t batch, int64_t D, int64_t len, int64_t n, int64_t nkb, const QP& qk, const QP& qv, hipStream_t st, const char* who) {
+                     int64_t batch, int64_t D, int64_t len, int64_t n, int64_t nkb, const QP& qk, const QP& qv, hipStream_t st, const char* who,
+                     const int32_t* starts = nullptr) {
   kvc::AArgs a;
-  a.src = src, a.kn = k_new, a.vn = v_new;
+  a.src = src, a.kn = k_new, a.vn = v_new, a.starts = starts;
   a.batch = batch, a.D = D, a.n = n, a.len = len, a.nkb = nkb;
   a.k_bs = ks[0], a.k_hs = ks[1], a.k_rs = ks[2], a.v_bs = vs[0], a.v_hs = vs[1], a.v_rs = vs[2];
   a.qk = qk, a.qv = qv;
@@ -320,7 +341,7 @@ static int kv_append(const kvc::KvSrc<unsigned char>& src, int dtype, const void
   a.kvec = al16(k_new, ks, esz), a.vvec = al16(v_new, vs, esz);
   const int64_t items = batch * src.kvh * (nkb * (D / 4) + n * (D / 16));
   return with_dtype(dtype, [&](auto dt) {
-    kvc::k_kv_append<decltype(dt)::value, SRC><<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
+    kvc::k_kv_append<decltype(dt)::value, SRC, RAG><<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
     return check_launch(who);
   });
 }
@@ -340,6 +361,14 @@ int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_ne
                             const QP& qk, const QP& qv, hipStream_t st) {
   return kv_append<attn::SRC_PAGED>(kvc::src_of<unsigned char>(p), p.dtype, k_new, v_new, ks, vs, batch, p.D, 0, n, (n + 14) / 16 + 1, qk, qv, st,
                                     "lqer_kv_pool_append");
+}
+
+// p.starts: [batch + 1] token starts (device); ks2 / vs2: elements over token / kv head of [total][kv_heads][D]; the grid follows max_n
+int kv_pool_append_ragged_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks2, const int64_t* vs2, int64_t batch,
+                                   int64_t max_n, const QP& qk, const QP& qv, hipStream_t st) {
+  const int64_t ks[3] = {0, ks2[1], ks2[0]}, vs[3] = {0, vs2[1], vs2[0]};
+  return kv_append<attn::SRC_PAGED, true>(kvc::src_of<unsigned char>(p), p.dtype, k_new, v_new, ks, vs, batch, p.D, 0, max_n, (max_n + 14) / 16 + 1, qk,
+                                          qv, st, "lqer_kv_pool_append_ragged", p.starts);
 }
 
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st) {

@@ -224,6 +224,11 @@ def attention_flexible_cached(q, cache: QuantizedKVCache, scaling, attention_mas
 PAGE_KEYS = 16
 
 
+def _pair(t: torch.Tensor):
+    """The stride pair (elements over token / head) of a packed [total, heads, d] tensor for the C ABI's calls with per-sequence counts."""
+    return (C.c_int64 * 2)(t.stride(0), t.stride(1))
+
+
 def pool_bytes(dtype: torch.dtype, pages: int, slots: int, kv_heads: int, head_dim: int) -> int:
     return _lib.lib().lqer_kv_pool_bytes(ops._DT[dtype], pages, slots, kv_heads, head_dim)
 
@@ -343,20 +348,30 @@ class PageTable:
             raise ValueError(f"PagedKVCache: a sequence is named twice in {list(seqs)}")
         return out
 
-    def reserve(self, seqs, n: int):
-        """Pages for n more keys of every sequence of `seqs`, taken before anything is launched: (slots, lengths before, pages taken
-        per slot).  Raises with no page taken and nothing changed; the lengths advance with commit(), and rollback() hands the
-        pages back when the launch is refused after all."""
+    @staticmethod
+    def _counts(n, slots) -> list:
+        """One count per slot from `n`: an int (>= 1, the same for all) or one count (>= 0) per sequence."""
+        if isinstance(n, int):
+            if n < 1:
+                raise ValueError(f"PagedKVCache.append: {n} new keys")
+            return [n] * len(slots)
+        counts = [int(c) for c in n]
+        if len(counts) != len(slots) or any(c < 0 for c in counts):
+            raise ValueError(f"PagedKVCache.append: counts {counts} for {len(slots)} sequences - one count >= 0 per sequence")
+        return counts
+
+    def reserve(self, seqs, n):
+        """Pages for n more keys of every sequence of `seqs` - n an int, or one count per sequence (0: the sequence takes no page) -
+        taken before anything is launched: (slots, lengths before, pages taken per slot).  Raises with no page taken and nothing
+        changed; the lengths advance with commit(), and rollback() hands the pages back when the launch is refused after all."""
         slots = self.slots(seqs)
-        if n < 1:
-            raise ValueError(f"PagedKVCache.append: {n} new keys")
         need = []
-        for seq, s in zip(seqs, slots):
-            pages = (self.lengths[s] + n + PAGE_KEYS - 1) // PAGE_KEYS
-            if pages > self.max_pages_per_seq:
-                raise RuntimeError(f"PagedKVCache.append: sequence {seq} would hold {self.lengths[s] + n} keys = {pages} pages, beyond "
+        for seq, s, c in zip(seqs, slots, self._counts(n, slots)):
+            pages = (self.lengths[s] + c + PAGE_KEYS - 1) // PAGE_KEYS
+            if c and pages > self.max_pages_per_seq:
+                raise RuntimeError(f"PagedKVCache.append: sequence {seq} would hold {self.lengths[s] + c} keys = {pages} pages, beyond "
                                    f"max_pages_per_seq = {self.max_pages_per_seq}")
-            need.append(pages - self.pages_of[s])
+            need.append(pages - self.pages_of[s] if c else 0)
         if sum(need) > len(self._free_pages):
             raise RuntimeError(f"PagedKVCache.append: out of pages - {sum(need)} needed, {len(self._free_pages)} of {self.num_pages} free")
         for s, k in zip(slots, need):
@@ -374,9 +389,10 @@ class PageTable:
                 self._owners[self.table[s][self.pages_of[s]]] = 0
                 self._free_pages.append(self.table[s][self.pages_of[s]])
 
-    def commit(self, slots, n: int) -> None:
-        for s in slots:
-            self.lengths[s] += n
+    def commit(self, slots, n) -> None:
+        """The lengths after the launch: n as in reserve()."""
+        for s, c in zip(slots, self._counts(n, slots)):
+            self.lengths[s] += c
 
     def fork(self, parents):
         """One new sequence per entry of `parents` (repeats allowed), each of its parent's length: (children, parents' slots,
@@ -437,6 +453,8 @@ class PagedKVCache:
                        call are taken before anything is launched; out of pages, beyond max_pages_per_seq, an unknown, freed or
                        repeated seq raise with the pool untouched and no page taken - and so does a refusal of the library itself:
                        the reservation is rolled back
+    .append_ragged(seqs, k, v, counts)   k / v [sum(counts), kv_heads, head_dim]: counts[b] more keys for seqs[b] - the decoders' one
+                       key and the arrivals' prompt chunks of a scheduler step in ONE launch, with append's bytes, books and refusals
     .length(seq);  .pages_free;  .nbytes
     .to_dense(seq) -> QuantizedKVCache (batch 1) with the sequence's bytes - an export, and the test hook (more than 8 query rows
                        need no copy: attention_flexible_paged(kernel="prefill"));  .dequantized(seq) -> (K, V) [1, kv_heads, length,
@@ -486,6 +504,7 @@ class PagedKVCache:
         self.table = torch.zeros(max_seqs, self.pt.max_pages_per_seq, dtype=torch.int32, device=self.device)
         self._slots = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
         self._lens = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
+        self._starts = torch.zeros(max_seqs + 1, dtype=torch.int32, device=self.device)  # per-sequence counts of a call, as token starts
 
     num_pages = property(lambda self: self.pt.num_pages)
     max_seqs = property(lambda self: self.pt.max_seqs)
@@ -543,13 +562,17 @@ class PagedKVCache:
         self.pt.commit(slots, n)
 
     def _release_outside_window(self, seqs, n) -> list:
-        """Before an append of n keys to `seqs` (validated here, so a bad call releases nothing): every sequence gives up the pages no
-        later call can see and this append does not touch.  Returns what PageTable.unrelease needs, in the order of the calls."""
+        """Before an append of n keys to `seqs` - an int, or one count per sequence, each sequence then by its own; a count of 0 leaves
+        the sequence alone - (validated here, so a bad call releases nothing): every sequence gives up the pages no later call can
+        see and this append does not touch.  Returns what PageTable.unrelease needs, in the order of the calls."""
         undo = []
-        for seq, s in zip(seqs, self.pt.slots(seqs)):
+        slots = self.pt.slots(seqs)
+        for seq, s, c in zip(seqs, slots, self.pt._counts(n, slots)):
+            if not c:
+                continue
             t = self.pt.lengths[s]
             first = self.pt.released[s]
-            freed = self.pt.release(seq, min(t + n - self.window - 7, PAGE_KEYS * (t // PAGE_KEYS)))
+            freed = self.pt.release(seq, min(t + c - self.window - 7, PAGE_KEYS * (t // PAGE_KEYS)))
             if self.pt.released[s] != first:
                 undo.append((seq, first, freed))
         return undo
@@ -567,6 +590,66 @@ class PagedKVCache:
                                                       ops._DT[self.dtype], len(slots), self.kv_heads, self.head_dim, n, C.byref(self.fmts[1]),
                                                       C.byref(self.fmts[3]), ops._stream(self.device)),
                        "lqer_kv_pool_append")
+
+    @torch.no_grad()
+    def append_ragged(self, seqs, k: torch.Tensor, v: torch.Tensor, counts) -> None:
+        """append() with a count of its own per sequence - a scheduler step in which most sequences take one key and a few a prompt
+        chunk - in ONE launch (lqer_kv_pool_append_ragged): k / v [sum(counts), kv_heads, head_dim], sequence seqs[b] taking rows
+        sum(counts[:b]) .. + counts[b] - 1; a count of 0 leaves its sequence alone.  The pool's bytes afterwards are those of one
+        append() per sequence.  Reservation, refusals, rollback and - on a window=W cache - the release of unseen pages, each
+        sequence by its own count, are append()'s: a refused call leaves the books and the pool as they were."""
+        seqs = list(seqs)
+        try:
+            counts = [int(c) for c in counts]
+        except (TypeError, ValueError):
+            raise ValueError(f"PagedKVCache.append_ragged: counts {counts!r} - one count >= 0 per sequence") from None
+        if len(counts) != len(seqs) or any(c < 0 for c in counts):
+            raise ValueError(f"PagedKVCache.append_ragged: counts {counts} for {len(seqs)} sequences - one count >= 0 per sequence")
+        want = (sum(counts), self.kv_heads, self.head_dim)
+        if k.dim() != 3 or tuple(k.shape) != want or k.shape != v.shape or k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError(f"PagedKVCache.append_ragged: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} for counts {counts} of "
+                             f"[sum(counts), {self.kv_heads}, {self.head_dim}] {self.dtype}")
+        if k.device != self.buf.device or v.device != self.buf.device:
+            raise ValueError(f"PagedKVCache.append_ragged: k on {k.device} / v on {v.device} for a pool on {self.buf.device}")
+        if not any(counts):
+            self.pt.slots(seqs)
+            return
+        undo = self._release_outside_window(seqs, counts) if self.window is not None else []
+        try:
+            slots, lens, taken = self.pt.reserve(seqs, counts)  # (raises with nothing taken)
+            try:
+                self._launch_append_ragged(slots, lens, taken, k, v, counts)
+            except BaseException:
+                self.pt.rollback(slots, taken)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
+                raise
+        except BaseException:
+            for u in reversed(undo):
+                self.pt.unrelease(*u)
+            raise
+        self.pt.commit(slots, counts)
+
+    def _call_starts(self, counts):
+        """The token starts [len(counts) + 1] of a call with per-sequence counts on the device: one copy, as _call_meta's."""
+        starts = [0]
+        for c in counts:
+            starts.append(starts[-1] + c)
+        self._starts[:len(starts)].copy_(torch.tensor(starts, dtype=torch.int32))
+        return self._starts.data_ptr()
+
+    def _launch_append_ragged(self, slots, lens, taken, k, v, counts) -> None:
+        for s, t in zip(slots, taken):
+            if t:
+                self.table[s].copy_(torch.tensor(self.pt.table[s], dtype=torch.int32))
+        if k.stride(2) != 1:
+            k = k.contiguous()
+        if v.stride(2) != 1:
+            v = v.contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lqer_kv_pool_append_ragged(*self._pool_args(), *self._call_meta(slots, lens), self._call_starts(counts), max(counts),
+                                                             k.data_ptr(), v.data_ptr(), _pair(k), _pair(v), ops._DT[self.dtype], len(slots),
+                                                             self.kv_heads, self.head_dim, sum(counts), C.byref(self.fmts[1]),
+                                                             C.byref(self.fmts[3]), ops._stream(self.device)),
+                       "lqer_kv_pool_append_ragged")
 
     # ---- sequences over shared pages (lqer_kv_pool_fork) ----
     def fork(self, seq: int, n: int = 1) -> list:
@@ -754,4 +837,136 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
                                     C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device),
                                     *(() if window is None else (min(window, 1 << 62),))),
                    name)
+    return (out, stats) if return_stats else out
+
+
+def _ragged_call(q, cache: PagedKVCache, slots, lens, counts, scaling, causal, out, stats, ws) -> None:
+    """lqer_attention_q_paged_ragged: q / out [sum(counts), h, d] (any token and head strides), stats [sum(counts), h, 2] fp32 dense or
+    None, for the sequences in `slots` with `lens` keys and `counts` query rows each.  max_len as attention_flexible_paged's prefill
+    route: the longest addressed length rounded up to 128, capped at the table's room."""
+    total, h, d = q.shape
+    L, f = _lib.lib(), cache.fmts
+    max_len = min((max(lens) + 127) // 128 * 128, cache.pt.max_len)
+    with torch.cuda.device(q.device):
+        if ws is None:
+            ws = ops.workspace(q.device, max(L.lqer_attention_q_paged_ragged_workspace_bytes(len(slots), h, cache.kv_heads, max(counts), max_len, d), 16))
+        _lib.check(L.lqer_attention_q_paged_ragged(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), out.data_ptr(),
+                                                   stats.data_ptr() if stats is not None else None, ops.dtype_code(q), len(slots), h,
+                                                   cache.kv_heads, cache._call_starts(counts), max(counts), total, d, _pair(q), _pair(out),
+                                                   float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]),
+                                                   ws.data_ptr(), ws.numel(), ops._stream(q.device)),
+                   "lqer_attention_q_paged_ragged")
+
+
+@torch.no_grad()
+def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scaling, causal=False, return_stats=False, ws=None, kernel=KERNEL_AUTO,
+                                    window=None):
+    """attention_flexible_paged for sequences with a number of query rows of their own - one scheduler step of continuous batching,
+    most sequences decoding one token while a few take a prompt chunk.  q [sum(counts), h, d]: sequence seqs[b] owns rows
+    sum(counts[:b]) .. + counts[b] - 1; the output has q's shape, the statistics are [sum(counts), h, 2].  `causal`: key j of sequence b
+    visible to its query row i iff j <= i + (length_b - counts[b]).  A count of 0 leaves its sequence out (it may be empty).
+    kernel="prefill": the whole batch in ONE lqer_attention_q_paged_ragged call - the prefill kernel takes every sequence's length
+    and count from the device; each sequence gets the bits of attention_flexible(..., kernel="prefill") on its raw K and V alone.
+    kernel="auto" (the default): sequences of up to 8 rows go through attention_flexible_paged(kernel="decode"), one call per distinct
+    count, their rows gathered and scattered by index on the device; all others through one ragged call - every sequence gets the
+    bits attention_flexible_paged(kernel="auto") gives it alone.  A call whose sequences' rows are one range of q - the decoders named
+    first and the chunks last, say - takes them as a view instead, and the ragged call then writes its rows of the output in place.
+    `window` (default: the cache's) and every refusal are those of the route a sequence takes, in its words: the decode route has the
+    window rule, the prefill kernel is taken with a window only while every length it addresses is <= W.  ValueError before anything
+    is launched: len(counts) != len(seqs), a negative count, sum(counts) != q.shape[0], causal with counts[b] > length_b, an empty
+    sequence with a count, an unknown or repeated sequence, a wrong dtype, device or head count.  ws: a uint8 workspace or None."""
+    who = "attention_flexible_paged_ragged"
+    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
+        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
+        raise ValueError(f"{who}: window {window!r} - None or a number of keys >= 1")
+    eff_window = cache.window if window is None else window
+    if eff_window is not None and not causal:
+        raise ValueError(f"{who}: window={eff_window} without causal=True - the window is a rule on top of the causal one")
+    seqs = list(seqs)
+    try:
+        counts = [int(c) for c in counts]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: counts {counts!r} - one count >= 0 per sequence") from None
+    if len(counts) != len(seqs) or any(c < 0 for c in counts):
+        raise ValueError(f"{who}: counts {counts} for {len(seqs)} sequences - one count >= 0 per sequence")
+    if q.dim() != 3 or q.shape[0] != sum(counts):
+        raise ValueError(f"{who}: q {tuple(q.shape)} is not [sum(counts) = {sum(counts)}, h, d]")
+    total, h, d = q.shape
+    if (q.dtype != cache.dtype or q.device != cache.buf.device or d != cache.head_dim or h < 1 or h % cache.kv_heads or h > _MAX_GRID_Z):
+        raise ValueError(f"{who}: q {tuple(q.shape)} {q.dtype} on {q.device} for a cache [{cache.kv_heads}, {cache.head_dim}] {cache.dtype} on "
+                         f"{cache.buf.device}")
+    try:
+        slots = cache.pt.slots(seqs)
+    except KeyError as e:
+        raise ValueError(e.args[0]) from None
+    lens = [cache.pt.lengths[x] for x in slots]
+    for seq, t, c in zip(seqs, lens, counts):
+        if c and (t < 1 or (causal and c > t)):
+            raise ValueError(f"{who}: sequence {seq} of {t} keys with {c} query rows - an empty sequence has nothing to attend to"
+                             + (f", and causal needs {c} query rows <= the length" if causal else ""))
+    starts = [0]  # the first row of every sequence
+    for c in counts[:-1]:
+        starts.append(starts[-1] + c)
+    live =[b for b, c in enumerate(counts) if c]
+    small = [b for b in live if counts[b] <= _ATTN_DECODE_MAX_S] if kernel == KERNEL_AUTO else []
+    big = [b for b in live if counts[b] > _ATTN_DECODE_MAX_S] if kernel == KERNEL_AUTO else live
+    if eff_window is not None and live:
+        if any(cache.pt.released[slots[b]] for b in live) and (cache.window is None or eff_window > cache.window):
+            raise ValueError(f"{who}: window={eff_window} on sequences that have released the pages below the cache's window of {cache.window} keys")
+        if big and max(lens[b] for b in big) > eff_window:
+            raise ValueError(f"{who}: kernel='prefill' with window={eff_window} and lengths {[lens[b] for b in big]} - the prefill kernel has no "
+                             "window rule; it is taken while every length is <= the window")
+    if big and (max(lens[b] for b in big) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
+        raise ValueError(f"{who}: {len(big)} sequences of lengths {[lens[b] for b in big]} beyond the prefill kernel's launch grid")
+    if q.stride(2) != 1:
+        q = q.contiguous()
+    out = torch.empty(total, h, d, dtype=q.dtype, device=q.device)
+    stats = torch.empty(total, h, 2, dtype=torch.float32, device=q.device) if return_stats else None
+    # One call per distinct count of the decode route, one for all other sequences.  A call whose sequences' rows are ONE range of q (no
+    # other call's rows between them: the decoders in front and the chunks behind, say) runs on views of q and out; the rows of the
+    # others are gathered and scattered by index - all of them through one index tensor, copied to the device once.
+    calls = {}
+    for b in small:
+        calls.setdefault(counts[b], []).append(b)
+    calls = list(calls.values()) + ([big] if big else [])
+
+    def span(bs):
+        lo, hi = starts[bs[0]], starts[bs[-1]] + counts[bs[-1]]
+        return slice(lo, hi) if hi - lo == sum(counts[b] for b in bs) else None
+
+    rows, where = [], []
+    for bs in calls:
+        where.append(span(bs))
+        if where[-1] is None:
+            mine = [r for b in bs for r in range(starts[b], starts[b] + counts[b])]
+            where[-1] = (len(rows), len(rows) + len(mine))
+            rows += mine
+    idx = torch.tensor(rows, dtype=torch.int64).to(q.device) if rows else None
+    for bs, at in zip(calls, where):
+        ix = None if isinstance(at, slice) else idx[at[0]:at[1]]
+        qc = q[at] if ix is None else q.index_select(0, ix)
+        if bs is big:
+            args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], [counts[b] for b in bs], scaling, causal)
+            if ix is None:  # (in place: nothing to copy)
+                _ragged_call(qc, *args, out[at], stats[at] if return_stats else None, ws)
+                continue
+            oc = torch.empty_like(qc)
+            sc = torch.empty(qc.shape[0], h, 2, dtype=torch.float32, device=q.device) if return_stats else None
+            _ragged_call(qc, *args, oc, sc, ws)
+        else:
+            c = counts[bs[0]]
+            got = attention_flexible_paged(qc.view(len(bs), c, h, d).transpose(1, 2), cache, [seqs[b] for b in bs], scaling, causal=causal,
+                                           out_layout="bshd", return_stats=return_stats, ws=ws, kernel=KERNEL_DECODE, window=window)
+            oc, sc = got if return_stats else (got, None)
+            oc = oc.view(len(bs) * c, h, d)
+            sc = sc.transpose(1, 2).reshape(len(bs) * c, h, 2) if return_stats else None
+        if ix is None:
+            out[at].copy_(oc)
+            if return_stats:
+                stats[at].copy_(sc)
+        else:
+            out.index_copy_(0, ix, oc)
+            if return_stats:
+                stats.index_copy_(0, ix, sc)
     return (out, stats) if return_stats else out
