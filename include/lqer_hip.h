@@ -736,6 +736,25 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * lqer_attention_q_paged_workspace_bytes at the same arguments - the two images, nothing that follows the counts.  Three launches on
  * `stream` (K image, V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
  * Refused as lqer_attention_q_paged, and LQER_E_INVALID for a null q_starts, max_s < 1, total < 0.
+ * lqer_attention_q_decode_paged_ragged: lqer_attention_q_paged_ragged's argument list plus `window`, on the split-over-keys kernels of
+ * lqer_attention_q_decode_paged - for counts of up to 8 rows: the verify step of a speculative decoder (1 .. 8 draft tokens per
+ * sequence), a scheduler step of one-token decoders beside sequences that take a few.  1 <= max_s <= 8; counts above max_s are the
+ * caller's breach.  window = 0: no window rule; window = W >= 1: the rule of lqer_attention_q_decode_paged_window (causal = 1 is
+ * required), every sequence by its own count - row i of sequence b at position p = i + (lens[b] - S_b) sees keys p - W < j <= p.
+ * A workgroup takes S_b = q_starts[b + 1] - q_starts[b] from the device as it takes T_b = lens[b]: the causal offset T_b - S_b, the
+ * window's first key, its first live chunk and the token q_starts[b] at which the sequence's rows of q, out and row_stats begin.  For
+ * every b, the rows of sequence b in out and row_stats are the SAME BITS as lqer_attention_q_decode with batch = 1 and S = S_b on the
+ * raw K and V of that sequence - with a window: on its FULL raw K and V and the additive window mask, and no table entry and no page
+ * wholly below key lens[b] - S_b - window + 1 is read - whatever else is in the batch, whatever max_s, max_len and total are and
+ * whatever the workspace held.  With S_b = 0 nothing is written for the sequence; with lens[b] = 0 its rows get zeros and no
+ * statistics, as above.  The grid is (largest nch of any T <= max_len, kv_heads, batch); no result depends on max_s, which sizes
+ * the last launch alone.
+ * workspace: lqer_attention_q_decode_paged_ragged_workspace_bytes(total, heads, max_len, D) bytes, 16-byte aligned, contents
+ * irrelevant - the three parts of lqer_attention_q_decode_paged's with rows = total heads (its size at batch 1, S = total): the rows
+ * are indexed by packed token, sequence b owning rows q_starts[b] heads .. q_starts[b + 1] heads - 1, so the size follows the tokens
+ * of the step and not batch x max_s.  Three launches on `stream`, no allocation, no host synchronisation, no atomics: capturable in
+ * a hipGraph.  Refused as lqer_attention_q_decode_paged, and LQER_E_INVALID for a null q_starts, max_s < 1 or > 8, total < 0,
+ * window < 0, window > 0 with causal = 0, a short or misaligned workspace.  batch = 0 or total = 0: LQER_OK, nothing launched.
  * lqer_kv_pool_gather: one sequence - row `slot` of block_table, T keys (host) - out of the pool into a dense lqer_kv_cache buffer of
  * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
  * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack) and an export path (more than 8 query rows
@@ -803,6 +822,14 @@ int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_b
                                   int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling,
                                   int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
                                   const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
+size_t lqer_attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D);
+int lqer_attention_q_decode_paged_ragged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                         const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                         int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+                                         int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total, int64_t D,
+                                         const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                         const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                                         const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream, int64_t window);
 
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's

@@ -9,6 +9,7 @@ from .functional import attention_flexible, bmm_flexible, get_quantized_func, ma
 from .kvcache import QuantizedKVCache, attention_flexible_cached  # noqa: F401
 # (importable from the package; __all__ below is pinned by tests/test_kv_prefill_cpu.py and stays as it is)
 from .kvcache import PagedKVCache, attention_flexible_paged, attention_flexible_paged_ragged  # noqa: F401
+from .kvcache import attention_flexible_paged_decode_ragged  # noqa: F401
 from .linear import LinearFlexible, LinearFlexibleLqer, get_quantized_layer_cls  # noqa: F401
 
 __all__ = ["LinearFlexible", "LinearFlexibleLqer", "get_quantized_layer_cls", "matmul_flexible", "bmm_flexible",

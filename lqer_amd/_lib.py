@@ -158,6 +158,11 @@ SIGNATURES = {
     # lqer_attention_q_paged's list with S -> (q_starts, max_s, total)
     "lqer_attention_q_paged_ragged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64, _i64,
                                            _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    # ... for counts of up to 8 rows on the split-over-keys kernels (csrc/attn_decode.hip): the same list plus `window` (0: none); the
+    # workspace follows (total, heads, max_len, D)
+    "lqer_attention_q_decode_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "lqer_attention_q_decode_paged_ragged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64,
+                                                  _i64, _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1138,6 +1138,8 @@ static int decode_grid_limits(const char* who, const AttnCall& c) {
 static size_t prefill_workspace_bytes(const AttnCall& c) { return attention_q_workspace_bytes(c.batch, c.kv_heads, c.T, c.D); }
 // (on the paged pool c.T is the bound max_len, which sizes the workspace and the grid)
 static size_t decode_workspace_bytes(const AttnCall& c) {
+  // (per-sequence counts: rows by packed token; a negative total is the pool check's to refuse, right after this one)
+  if (c.paged && c.pool.ragged) return c.pool.total < 0 ? 0 : attention_q_decode_paged_ragged_workspace_bytes(c.pool.total, c.heads, c.T, c.D);
   return c.paged ? attention_q_decode_paged_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D)
                  : attention_q_decode_workspace_bytes(c.batch, c.heads, c.S, c.T, c.D);
 }
@@ -1180,6 +1182,12 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
     set_error("%s: null quantizer format", who);
     return LQER_E_INVALID;
   }
+  const bool ragged = c.paged && c.pool.ragged;  // (S: the bound max_s on the per-sequence counts, which sizes the grid)
+  if (ragged && kn.max_s && c.S > kn.max_s) {  // (a bound the caller chose, not a shape: invalid, as max_s < 1 below)
+    set_error("%s: max_s = %lld query rows - the split over the keys takes counts up to %d, and max_s bounds every sequence's count "
+              "(lqer_attention_q_paged_ragged takes any)", who, (long long)c.S, kn.max_s);
+    return LQER_E_INVALID;
+  }
   if (kn.max_s && c.S > kn.max_s) {
     set_error("%s: S = %lld query rows - the split over the keys takes up to %d (lqer_attention_q takes any)", who, (long long)c.S,
               kn.max_s);
@@ -1199,7 +1207,6 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
                 "formats run as the two products of lqer_matmul_q", who, f->kind, f->block);
       return LQER_E_UNSUPPORTED;
     }
-  const bool ragged = c.paged && c.pool.ragged;  // (S: the bound max_s on the per-sequence counts, which sizes the grid)
   if (ragged && c.S < 1) {
     set_error("%s: max_s = %lld query rows (max_s >= 1 bounds every sequence's count)", who, (long long)c.S);
     return LQER_E_INVALID;
@@ -1221,7 +1228,7 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
   const size_t need = kn.workspace_bytes(c);
   if (c.workspace_bytes < need) {
     set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need,
-              c.windowed ? "attention_q_decode_paged" : who);  // (the windowed call has the unwindowed one's workspace)
+              c.windowed && !ragged ? "attention_q_decode_paged" : who);  // (the windowed call has the unwindowed one's workspace)
     return LQER_E_INVALID;
   }
   return LQER_OK;
@@ -1651,6 +1658,30 @@ int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_b
   c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
   c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
   return attn_run("attention_q_paged_ragged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
+}
+
+size_t lqer_attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D) {
+  if (total <= 0 || heads <= 0 || max_len <= 0 || D <= 0) return 0;
+  return attention_q_decode_paged_ragged_workspace_bytes(total, heads, max_len, D);
+}
+
+int lqer_attention_q_decode_paged_ragged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                         const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                         int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+                                         int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total, int64_t D,
+                                         const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                         const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
+                                         void* workspace, size_t workspace_bytes, void* stream, int64_t window) {
+  // the call above on the decode kernels: the stride pairs as triples without a batch stride, S the bound max_s (here <= 8), and the
+  // window rule when window != 0 (a negative one is the check's to refuse)
+  const int64_t qs[3] = {0, q_strides ? q_strides[1] : 0, q_strides ? q_strides[0] : 0};
+  const int64_t os[3] = {0, out_strides ? out_strides[1] : 0, out_strides ? out_strides[0] : 0};
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, max_s, max_len, D, q_strides ? qs : nullptr, nullptr,
+                         out_strides ? os : nullptr, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  c.packed = c.paged = true, c.windowed = window != 0, c.window = window;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
+  return attn_run("attention_q_decode_paged_ragged", ATTN_DECODE, c);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

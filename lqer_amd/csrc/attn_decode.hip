@@ -34,6 +34,17 @@
 // left out of both folds (their workspace cells are never written and never read; chunk lo / C writes row_stats), and keys below the
 // page boundary 16 (lo / 16) are zero rows in LDS whose table entries and pages are never dereferenced - a released page may hold
 // anything.  A page is one block of Q_w0 along t and one group of Q_w1's exponents, so the live pages' codes do not depend on the rest.
+//
+// Per-sequence query counts (template parameter RAG, the paged source only: lqer_attention_q_decode_paged_ragged): a speculative
+// decoder's verify step, a scheduler step of one-token decoders beside sequences that take a few.  q and out are packed
+// [total][heads][D] tensors through a token and a head stride, and a workgroup (chunk, kv head, b) takes S_b = q_starts[b + 1] -
+// q_starts[b] from the device as it takes T_b: its row count R_b = rep S_b, the causal offset T_b - S_b, the window's first key
+// lo = max(0, T_b - S_b - W + 1) and with it the first live chunk, the page boundary and the chunk that writes row_stats, and the
+// token q_starts[b] at which its rows of q, out and row_stats begin.  S_b = 0: the workgroup leaves before the first barrier.  The
+// workspace rows are indexed by PACKED TOKEN: sequence b owns rows q_starts[b] heads .. q_starts[b + 1] heads - 1, row g R_b + r of
+// that range for row r of kv head g (a bijection), so the workspace follows total x heads and not batch x max_s.  The host bound
+// max_s sizes k_attn_dec_sum's grid alone.  Everything a row computes - chunks, folds, fragments, quantizers, rounding points - is
+// the uniform kernels' at S = S_b: the rows of a sequence are those of a call of batch 1 with S = S_b, whatever else is in the batch.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -75,6 +86,12 @@ struct DArgs {
   kvc::KvSrc<const unsigned char> src;  // the packed and the paged source (kv_pack.h)
   int64_t win;  // the window W of the kernels with WIN (mode 2 only); 0: none.  (Last: the members above keep their kernarg offsets)
 };
+// the argument record of the kernels with RAG: the token starts behind it, so the other kernels' record is what it was
+struct DArgsRag : DArgs {
+  const int32_t* q_starts;  // (device, [batch + 1]) sequence b owns tokens q_starts[b] .. q_starts[b + 1] - 1
+};
+template <bool RAG>
+using DArgsOf = std::conditional_t<RAG, DArgsRag, DArgs>;
 
 // the paged source: chunk length and chunk count of a sequence of T = lens[b] keys
 __device__ __forceinline__ void paged_chunks(const DArgs& a, int64_t T, int& C, int& nch) {
@@ -83,17 +100,39 @@ __device__ __forceinline__ void paged_chunks(const DArgs& a, int64_t T, int& C, 
 }
 
 // WIN: the first key that any of the S rows of a sequence of T keys sees
-__device__ __forceinline__ int64_t win_first(const DArgs& a, int64_t T) {
-  const int64_t lo = T - a.S - a.win + 1;
+__device__ __forceinline__ int64_t win_first(const DArgs& a, int64_t T, int64_t S) {
+  const int64_t lo = T - S - a.win + 1;
   return lo > 0 ? lo : 0;
 }
 
-template <int DT, int SRC, bool WIN>
-__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
+// The query rows of the call's b-th sequence: S rows per head and R = rep S per kv head, `tok` the token at which they begin in q,
+// out and row_stats (0 without RAG: those are addressed through a batch stride), `wrow` the workspace row of row 0 of kv head g.
+// RAG: S from q_starts, the same for every lane (made a scalar: the row loops and the divisions by S stay uniform).
+struct SeqRows {
+  int64_t S, R, tok, wrow;
+};
+template <bool RAG>
+__device__ __forceinline__ SeqRows seq_rows(const DArgsOf<RAG>& a, int64_t b, int64_t g) {
+  if constexpr (RAG) {
+    const int t0 = __builtin_amdgcn_readfirstlane(a.q_starts[b]), t1 = __builtin_amdgcn_readfirstlane(a.q_starts[b + 1]);
+    const int64_t S = t1 - t0, R = a.rep * S;
+    return {S, R, t0, (int64_t)t0 * a.heads + g * R};
+  } else {
+    return {a.S, a.R, 0, (b * a.kv_heads + g) * a.R};
+  }
+}
+
+template <int DT, int SRC, bool WIN, bool RAG>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a) {
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
+  const SeqRows sr = seq_rows<RAG>(a, b, g);
+  if constexpr (RAG) {
+    if (sr.S <= 0) return;  // (a sequence without query rows: uniform over the workgroup, before any barrier; nothing is written)
+  }
+  const int64_t S = sr.S, R = sr.R, wrow = sr.wrow;  // the workspace row of this kv head's row 0
   const int32_t* prow;  // the slot's row of the page table
   const int64_t T = kvc::seq<SRC>(a.src, b, a.T, prow);
   int C = a.C, nch = a.nch;
@@ -103,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   }
   int64_t plo = 0;  // WIN: keys below plo lie on pages wholly outside every row's window - zero rows, their table entries and pages unread
   if constexpr (WIN) {
-    const int64_t lo = win_first(a, T);
+    const int64_t lo = win_first(a, T, S);
     if (c < lo / C) return;  // (a dead chunk: nothing written, and nothing reads its workspace cells)
     plo = lo / 16 * 16;
   }
@@ -174,12 +213,12 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
   // ---- S^T = Kq Qq^T: wave w takes keys 32 w .. 32 w + 31 of the chunk, a lane ONE query row and 16 of those keys,
   // (r & 3) + 8 (r >> 2) + 4 lh (rows of sK at and beyond C hold whatever LDS held: their scores are never used)
   const int nsub = (C + 31) / 32;
-  const int64_t off = T - a.S;
-  for (int64_t rg = 0; rg < a.R; rg += 32) {
+  const int64_t off = T - S;
+  for (int64_t rg = 0; rg < R; rg += 32) {
     const int64_t row = rg + l31;
-    const bool live = row < a.R;
-    const int64_t rowc = live ? row : a.R - 1;
-    const int64_t h = g * a.rep + rowc / a.S, si = rowc % a.S;
+    const bool live = row < R;
+    const int64_t rowc = live ? row : R - 1;
+    const int64_t h = g * a.rep + rowc / S, si = rowc % S;
     float m = NEG_INF, l = 0.f;
     if (wave < nsub) {
       f32x16 acc;
@@ -191,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
           uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
           if (live) {
             float v[16];
-            load16<DT>(a.q, b * a.q_bs + h * a.q_hs + si * a.q_rs + ks * 16, 16, a.qvec, v);
+            load16<DT>(a.q, b * a.q_bs + h * a.q_hs + (sr.tok + si) * a.q_rs + ks * 16, 16, a.qvec, v);
             quant16_bf16<DT != LQER_F16>(v, a.q0, w);
           }
           const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
@@ -223,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) ls += vis[r] ? exp_neg(s2[r] - mref) : 0.f;
       if (live) {
-        float* dst = a.s2 + (z * a.R + row) * a.Tp + t0 + 32 * wave + 4 * lh;
+        float* dst = a.s2 + (wrow + row) * a.Tp + t0 + 32 * wave + 4 * lh;
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4)
           if (32 * wave + 8 * q4 + 4 * lh < C) *(float4*)(dst + 8 * q4) = make_float4(s2[4 * q4], s2[4 * q4 + 1], s2[4 * q4 + 2], s2[4 * q4 + 3]);
@@ -244,18 +283,23 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgs a) {
       const float mr = M == NEG_INF ? 0.f : M;
       float L = 0.f;
       for (int u = 0; u < nsub; ++u) L += sSt[u][l31][1] * exp_neg(sSt[u][l31][0] - mr);
-      float* cs = a.cst + ((z * a.R + row) * a.nchs + c) * 2;
+      float* cs = a.cst + ((wrow + row) * a.nchs + c) * 2;
       cs[0] = M, cs[1] = L;
     }
     __syncthreads();
   }
 }
 
-template <int DT, int SRC, bool WIN>
-__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
+template <int DT, int SRC, bool WIN, bool RAG>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG> a) {
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
+  const SeqRows sr = seq_rows<RAG>(a, b, g);
+  if constexpr (RAG) {
+    if (sr.S <= 0) return;
+  }
+  const int64_t S = sr.S, R = sr.R, wrow = sr.wrow;
   const int32_t* prow;
   const int64_t T = kvc::seq<SRC>(a.src, b, a.T, prow);
   int C = a.C, nch = a.nch;
@@ -266,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   int64_t plo = 0;
   int c_lo = 0;  // WIN: the first chunk that holds a visible key
   if constexpr (WIN) {
-    const int64_t lo = win_first(a, T);
+    const int64_t lo = win_first(a, T, S);
     c_lo = (int)(lo / C);
     if (c < c_lo) return;
     plo = lo / 16 * 16;
@@ -323,21 +367,22 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   __syncthreads();
   if (wave * 32 >= D) return;  // wave w owns d = 32 w .. 32 w + 31 (no barrier follows)
 
-  const int64_t off = T - a.S;
-  for (int64_t rg = 0; rg < a.R; rg += 32) {
+  const int64_t off = T - S;
+  for (int64_t rg = 0; rg < R; rg += 32) {
     const int64_t row = rg + l31;
-    const bool live = row < a.R;
-    const int64_t rowc = live ? row : a.R - 1;
-    const int64_t si = rowc % a.S;
+    const bool live = row < R;
+    const int64_t rowc = live ? row : R - 1;
+    const int64_t si = rowc % S;
     // ---- the row's maximum and sum from the chunk statistics, in chunk order
-    const float* cs = a.cst + (z * a.R + rowc) * a.nchs * 2;
+    const float* cs = a.cst + (wrow + rowc) * a.nchs * 2;
     float M = NEG_INF;
     for (int cc = c_lo; cc < nch; ++cc) M = fmaxf(M, cs[2 * cc]);
     const float mr = M == NEG_INF ? 0.f : M;
     float L = 0.f;
     for (int cc = c_lo; cc < nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
     if (a.stats && c == (WIN ? c_lo : 0) && wave == 0 && lh == 0 && live) {
-      float* st = a.stats + (z * a.R + row) * 2;
+      // (RAG: row_stats is [total][heads][2] - by token, then head; else [batch][heads][S][2], the workspace's row order)
+      float* st = a.stats + (RAG ? (sr.tok + si) * a.heads + g * a.rep + row / S : wrow + row) * 2;
       st[0] = M, st[1] = L;
     }
     int64_t tvis = T - 1;
@@ -350,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const float* srow = a.s2 + (z * a.R + rowc) * a.Tp;
+    const float* srow = a.s2 + (wrow + rowc) * a.Tp;
     for (int kst = 0; kst < C / 16; ++kst) {
       const int64_t tb = t0 + 16 * kst + 8 * lh;
       const float4 sa = *(const float4*)(srow + tb), sb = *(const float4*)(srow + tb + 4);
@@ -369,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vw), __builtin_bit_cast(bf16x8, pw), acc, 0, 0, 0);
     }
     if (live) {  // d = 32 wave + 8 q4 + 4 lh + (0..3)
-      float* dst = a.part + ((z * a.R + row) * a.nchs + c) * a.D + 32 * wave + 4 * lh;
+      float* dst = a.part + ((wrow + row) * a.nchs + c) * a.D + 32 * wave + 4 * lh;
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4)
         if (32 * wave + 8 * q4 + 4 * lh < D) *(float4*)(dst + 8 * q4) = make_float4(acc[4 * q4], acc[4 * q4 + 1], acc[4 * q4 + 2], acc[4 * q4 + 3]);
@@ -377,21 +422,32 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgs a) {
   }
 }
 
-// one thread = four consecutive d of one output row (PAGED: the chunks of the row's own sequence)
-template <int DT, bool PAGED, bool WIN>
-__global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
+// one thread = four consecutive d of one output row (PAGED: the chunks of the row's own sequence).  RAG: the grid's y is the
+// sequence and its x covers the max_s heads rows a sequence has at most - a thread beyond the S_b heads rows of ITS sequence leaves
+// (no barrier in this kernel); the row's sequence costs the two loads of its starts, not a search of q_starts.
+template <int DT, bool PAGED, bool WIN, bool RAG>
+__global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgsOf<RAG> a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int dq = (int)a.D / 4;
-  if (i >= a.rows * dq) return;
-  const int64_t grow = i / dq;
   const int d = 4 * (int)(i % dq);
+  int64_t grow = i / dq, b, h, si, S = a.S;  // the workspace row; the sequence, head and row - RAG: token - of out
+  if constexpr (RAG) {
+    b = blockIdx.y;
+    const int64_t tok = a.q_starts[b];
+    S = a.q_starts[b + 1] - tok;
+    if (grow >= S * a.heads) return;  // (also S_b = 0)
+    h = grow / S, si = tok + grow % S, grow += tok * a.heads;
+  } else {
+    if (i >= a.rows * dq) return;
+    b = grow / (a.heads * a.S), h = (grow / a.S) % a.heads, si = grow % a.S;
+  }
   int64_t T = a.T;
   int C = a.C, nch = a.nch, c_lo = 0;
   if constexpr (PAGED) {
-    T = a.src.lens[grow / (a.heads * a.S)];
+    T = a.src.lens[b];
     paged_chunks(a, T, C, nch);
   }
-  if constexpr (WIN) c_lo = (int)(win_first(a, T) / C);  // (the partials of the chunks below were never written)
+  if constexpr (WIN) c_lo = (int)(win_first(a, T, S) / C);  // (the partials of the chunks below were never written)
   const float* p = a.part + grow * a.nchs * a.D + d;
   float o[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
@@ -399,16 +455,18 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgs a) {
     const float4 t = *(const float4*)(p + (int64_t)cc * a.D);
     o[0] += t.x, o[1] += t.y, o[2] += t.z, o[3] += t.w;
   }
-  const int64_t b = grow / (a.heads * a.S), h = (grow / a.S) % a.heads, si = grow % a.S;
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
-template <int DT, int SRC, bool WIN = false>
-static int launch_decode(const DArgs& a, int64_t batch, hipStream_t st) {
+template <int DT, int SRC, bool WIN = false, bool RAG = false>
+static int launch_decode(const DArgsOf<RAG>& a, int64_t batch, hipStream_t st) {
   const dim3 grid((unsigned)a.nchs, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT, SRC, WIN><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT, SRC, WIN><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN><<<dim3((unsigned)((a.rows * (a.D / 4) + 255) / 256)), 256, 0, st>>>(a);
+  k_attn_dec_scores<DT, SRC, WIN, RAG><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT, SRC, WIN, RAG><<<grid, 256, 0, st>>>(a);
+  // (RAG: a.S is the bound max_s - x over the rows a sequence has at most, y the sequence)
+  const dim3 sgrid((unsigned)(((RAG ? a.S * a.heads : a.rows) * (a.D / 4) + 255) / 256), RAG ? (unsigned)batch : 1u);
+  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN, RAG><<<sgrid, 256, 0, st>>>(a);
+  if (RAG) return check_launch("lqer_attention_q_decode_paged_ragged");
   if (WIN) return check_launch("lqer_attention_q_decode_paged_window");
   return check_launch(SRC == SRC_PAGED ? "lqer_attention_q_decode_paged" : (SRC == SRC_PACKED ? "lqer_attention_q_decode_kv" : "lqer_attention_q_decode"));
 }
@@ -433,13 +491,21 @@ size_t attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, in
   return dec_align((size_t)(rows * Tp) * 4) + dec_align((size_t)(rows * nchs * 2) * 4) + dec_align((size_t)(rows * nchs * D) * 4);
 }
 
+// per-sequence counts: the same three parts over rows = total heads - a row per packed token and head, whatever the counts are
+size_t attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D) {
+  return attention_q_decode_paged_workspace_bytes(1, heads, total, max_len, D);
+}
+
 int attention_q_decode_dispatch(const AttnCall& c) {
-  attn::DArgs a;
+  attn::DArgsRag a;  // (the kernels without per-sequence counts take its base)
   a.q = c.q, a.k = c.k, a.v = c.v, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
   a.S = c.S, a.T = c.T, a.D = c.D;
   a.C = attn::dec_chunk(c.T, c.D), a.nch = a.nchs = (int)((c.T + a.C - 1) / a.C), a.Tp = (int64_t)a.nch * a.C;
   if (c.paged) a.nchs = attn::dec_max_chunks(c.T), a.Tp = (c.T + 127) / 128 * 128;  // (T = max_len; the kernels take T, C, nch from lens[b])
   a.rep = (int)(c.heads / c.kv_heads), a.R = a.rep * c.S, a.rows = c.batch * c.heads * c.S;
+  const bool ragged = c.paged && c.pool.ragged;  // (S: the bound max_s; the workspace rows follow the packed tokens)
+  a.q_starts = ragged ? c.pool.starts : nullptr;
+  if (ragged) a.rows = c.pool.total * c.heads;
   unsigned char* ws = (unsigned char*)c.workspace;
   a.s2 = (float*)ws;
   ws += dec_align((size_t)(a.rows * a.Tp) * 4);
@@ -462,7 +528,9 @@ int attention_q_decode_dispatch(const AttnCall& c) {
     a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
     a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
   }
-  // (the window has a public entry on the paged source only, so only that instantiation of the rule exists)
+  // (the window and the per-sequence counts have public entries on the paged source only, so only those instantiations exist)
+  if (ragged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true, true>(a, c.batch, c.st); });
+  if (ragged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, false, true>(a, c.batch, c.st); });
   if (c.paged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true>(a, c.batch, c.st); });
   if (c.paged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
   if (c.packed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });

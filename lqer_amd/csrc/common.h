@@ -903,6 +903,8 @@ size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t 
 // (the decode kernels, or the image kernels and k_attn_q's per-sequence-length instantiation) read every sequence's own length from
 // the device.  With `pool.ragged` (lqer_attention_q_paged_ragged) S is the bound max_s, which sizes the grid alone, q / out are
 // [total][heads][D] - qs / os hold {0, head stride, token stride} - and k_attn_q takes every sequence's own S from pool.starts.
+// The decode kernels have the same instantiation (lqer_attention_q_decode_paged_ragged, max_s <= 8, with or without `windowed`): there
+// the workspace rows follow pool.total too.
 struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayout); the three metadata arrays are DEVICE pointers
   const void* pool;
   size_t pool_bytes;
@@ -910,7 +912,7 @@ struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayo
   int64_t pages, slots, kv_heads, D;
   const int32_t *block_table, *seq_slots, *lens;
   int64_t table_stride, max_len;
-  // per-sequence token counts (lqer_kv_pool_append_ragged, lqer_attention_q_paged_ragged): sequence b of the call owns tokens
+  // per-sequence token counts (lqer_kv_pool_append_ragged, lqer_attention_q_paged_ragged, lqer_attention_q_decode_paged_ragged): sequence b of the call owns tokens
   // starts[b] .. starts[b + 1] - 1 of a packed [total][heads][D] tensor; starts: DEVICE, [batch + 1]
   bool ragged;
   const int32_t* starts;
@@ -946,6 +948,7 @@ int attention_q_dispatch(const AttnCall& c);  // (with a cache or a pool: kv_cac
 int attention_q_decode_max_s();
 size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D);
 size_t attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t max_len, int64_t D);
+size_t attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D);  // (pool.ragged: rows by packed token)
 int attention_q_decode_dispatch(const AttnCall& c);  // (with a cache or a pool: the kernels read its codes, kv_pack.h)
 size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D);  // kv_cache.hip
 int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int dtype, int64_t batch,

@@ -840,49 +840,44 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     return (out, stats) if return_stats else out
 
 
-def _ragged_call(q, cache: PagedKVCache, slots, lens, counts, scaling, causal, out, stats, ws) -> None:
-    """lqer_attention_q_paged_ragged: q / out [sum(counts), h, d] (any token and head strides), stats [sum(counts), h, 2] fp32 dense or
-    None, for the sequences in `slots` with `lens` keys and `counts` query rows each.  max_len as attention_flexible_paged's prefill
-    route: the longest addressed length rounded up to 128, capped at the table's room."""
+RAGGED_PREFILL, RAGGED_DECODE = "lqer_attention_q_paged_ragged", "lqer_attention_q_decode_paged_ragged"
+
+
+def _ragged_call(name, q, cache: PagedKVCache, slots, lens, counts, scaling, causal, out, stats, ws, window=None) -> None:
+    """One library call with per-sequence counts - RAGGED_PREFILL (the prefill kernel, any counts) or RAGGED_DECODE (the split-over-keys
+    kernels, counts up to 8, `window`: None or W) -: q / out [sum(counts), h, d] (any token and head strides), stats [sum(counts), h, 2]
+    fp32 dense or None, for the sequences in `slots` with `lens` keys and `counts` query rows each.  max_len as
+    attention_flexible_paged's prefill route: the longest addressed length rounded up to 128, capped at the table's room - tight,
+    since no result depends on it."""
     total, h, d = q.shape
     L, f = _lib.lib(), cache.fmts
-    max_len = min((max(lens) + 127) // 128 * 128, cache.pt.max_len)
+    max_len = min((max(max(lens), 1) + 127) // 128 * 128, cache.pt.max_len)
+    decode = name == RAGGED_DECODE
     with torch.cuda.device(q.device):
         if ws is None:
-            ws = ops.workspace(q.device, max(L.lqer_attention_q_paged_ragged_workspace_bytes(len(slots), h, cache.kv_heads, max(counts), max_len, d), 16))
-        _lib.check(L.lqer_attention_q_paged_ragged(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), out.data_ptr(),
-                                                   stats.data_ptr() if stats is not None else None, ops.dtype_code(q), len(slots), h,
-                                                   cache.kv_heads, cache._call_starts(counts), max(counts), total, d, _pair(q), _pair(out),
-                                                   float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]),
-                                                   ws.data_ptr(), ws.numel(), ops._stream(q.device)),
-                   "lqer_attention_q_paged_ragged")
+            need = (L.lqer_attention_q_decode_paged_ragged_workspace_bytes(total, h, max_len, d) if decode else
+                    L.lqer_attention_q_paged_ragged_workspace_bytes(len(slots), h, cache.kv_heads, max(counts), max_len, d))
+            ws = ops.workspace(q.device, max(need, 16))
+        _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), out.data_ptr(),
+                                    stats.data_ptr() if stats is not None else None, ops.dtype_code(q), len(slots), h,
+                                    cache.kv_heads, cache._call_starts(counts), max(counts), total, d, _pair(q), _pair(out),
+                                    float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]),
+                                    ws.data_ptr(), ws.numel(), ops._stream(q.device),
+                                    *((0 if window is None else min(window, 1 << 62),) if decode else ())),
+                   name)
 
 
-@torch.no_grad()
-def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scaling, causal=False, return_stats=False, ws=None, kernel=KERNEL_AUTO,
-                                    window=None):
-    """attention_flexible_paged for sequences with a number of query rows of their own - one scheduler step of continuous batching,
-    most sequences decoding one token while a few take a prompt chunk.  q [sum(counts), h, d]: sequence seqs[b] owns rows
-    sum(counts[:b]) .. + counts[b] - 1; the output has q's shape, the statistics are [sum(counts), h, 2].  `causal`: key j of sequence b
-    visible to its query row i iff j <= i + (length_b - counts[b]).  A count of 0 leaves its sequence out (it may be empty).
-    kernel="prefill": the whole batch in ONE lqer_attention_q_paged_ragged call - the prefill kernel takes every sequence's length
-    and count from the device; each sequence gets the bits of attention_flexible(..., kernel="prefill") on its raw K and V alone.
-    kernel="auto" (the default): sequences of up to 8 rows go through attention_flexible_paged(kernel="decode"), one call per distinct
-    count, their rows gathered and scattered by index on the device; all others through one ragged call - every sequence gets the
-    bits attention_flexible_paged(kernel="auto") gives it alone.  A call whose sequences' rows are one range of q - the decoders named
-    first and the chunks last, say - takes them as a view instead, and the ragged call then writes its rows of the output in place.
-    `window` (default: the cache's) and every refusal are those of the route a sequence takes, in its words: the decode route has the
-    window rule, the prefill kernel is taken with a window only while every length it addresses is <= W.  ValueError before anything
-    is launched: len(counts) != len(seqs), a negative count, sum(counts) != q.shape[0], causal with counts[b] > length_b, an empty
-    sequence with a count, an unknown or repeated sequence, a wrong dtype, device or head count.  ws: a uint8 workspace or None."""
-    who = "attention_flexible_paged_ragged"
-    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
-        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+def _ragged_window(who, cache, window, causal):
+    """The window a call with per-sequence counts runs under: `window`, or the cache's - validated, and refused without causal."""
     if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
         raise ValueError(f"{who}: window {window!r} - None or a number of keys >= 1")
     eff_window = cache.window if window is None else window
     if eff_window is not None and not causal:
         raise ValueError(f"{who}: window={eff_window} without causal=True - the window is a rule on top of the causal one")
+    return eff_window
+
+
+def _ragged_counts(who, seqs, counts):
     seqs = list(seqs)
     try:
         counts = [int(c) for c in counts]
@@ -890,6 +885,11 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
         raise ValueError(f"{who}: counts {counts!r} - one count >= 0 per sequence") from None
     if len(counts) != len(seqs) or any(c < 0 for c in counts):
         raise ValueError(f"{who}: counts {counts} for {len(seqs)} sequences - one count >= 0 per sequence")
+    return seqs, counts
+
+
+def _ragged_operands(who, q, cache, seqs, counts, causal):
+    """What every call with per-sequence counts asks of q, the sequences and their lengths: (slots, lens), or ValueError."""
     if q.dim() != 3 or q.shape[0] != sum(counts):
         raise ValueError(f"{who}: q {tuple(q.shape)} is not [sum(counts) = {sum(counts)}, h, d]")
     total, h, d = q.shape
@@ -905,68 +905,150 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
         if c and (t < 1 or (causal and c > t)):
             raise ValueError(f"{who}: sequence {seq} of {t} keys with {c} query rows - an empty sequence has nothing to attend to"
                              + (f", and causal needs {c} query rows <= the length" if causal else ""))
+    return slots, lens
+
+
+def _ragged_released(who, cache, slots, live, eff_window) -> None:
+    if eff_window is not None and any(cache.pt.released[slots[b]] for b in live) and (cache.window is None or eff_window > cache.window):
+        raise ValueError(f"{who}: window={eff_window} on sequences that have released the pages below the cache's window of {cache.window} keys")
+
+
+@torch.no_grad()
+def attention_flexible_paged_decode_ragged(q, cache: PagedKVCache, seqs, counts, scaling, causal=False, return_stats=False, ws=None, window=None):
+    """attention_flexible_paged(kernel="decode") for sequences with up to 8 query rows EACH, a count of its own per sequence, in ONE
+    library call (lqer_attention_q_decode_paged_ragged: three launches whatever the counts are) - the verify step of a speculative
+    decoder, 1 .. 8 draft tokens per sequence; a scheduler step of one-token decoders beside sequences that take a few.
+    q [sum(counts), h, d]: sequence seqs[b] owns rows sum(counts[:b]) .. + counts[b] - 1; the output has q's shape, the statistics are
+    [sum(counts), h, 2].  Every count is 0 .. 8; a count of 0 leaves its sequence out (it may be empty).  `causal`: key j of sequence
+    b visible to its query row i iff j <= i + (length_b - counts[b]).  Every sequence gets the bits of
+    attention_flexible_paged(kernel="decode") on it alone - those of attention_flexible(..., kernel="decode") on its raw K and V.
+    `window` (default: the cache's; needs causal=True): the window rule per sequence, as attention_flexible_paged's - the bits of the
+    decode kernel on the full raw K and V with the additive window mask, no released page read.  The workspace follows sum(counts),
+    and the library's bound max_len is the longest addressed length rounded up to 128 (capped at the table's room).  ValueError before
+    anything is launched: what attention_flexible_paged_ragged refuses, in its words, and a count above 8 (more rows:
+    attention_flexible_paged_ragged).  ws: a uint8 workspace or None (the stream's)."""
+    who = "attention_flexible_paged_decode_ragged"
+    eff_window = _ragged_window(who, cache, window, causal)
+    seqs, counts = _ragged_counts(who, seqs, counts)
+    if any(c > _ATTN_DECODE_MAX_S for c in counts):
+        raise ValueError(f"{who}: counts {counts} - the decode kernels over the paged cache take up to {_ATTN_DECODE_MAX_S} query rows per "
+                         "sequence (more: attention_flexible_paged_ragged)")
+    slots, lens = _ragged_operands(who, q, cache, seqs, counts, causal)
+    _ragged_released(who, cache, slots, [b for b, c in enumerate(counts) if c], eff_window)
+    if q.stride(2) != 1:
+        q = q.contiguous()
+    total, h, d = q.shape
+    out = torch.empty(total, h, d, dtype=q.dtype, device=q.device)
+    stats = torch.empty(total, h, 2, dtype=torch.float32, device=q.device) if return_stats else None
+    if total:
+        _ragged_call(RAGGED_DECODE, q, cache, slots, lens, counts, scaling, causal, out, stats, ws, eff_window)
+    return (out, stats) if return_stats else out
+
+
+def _ragged_plan(counts, kernel):
+    """The library calls of attention_flexible_paged_ragged for these counts, host arithmetic only: [(name, the indices of the call's
+    sequences, the slice of q's rows they own - None when their rows are not one range and are gathered)].  kernel="auto": all
+    sequences of up to 8 rows in one RAGGED_DECODE call, all others in one RAGGED_PREFILL call; "prefill": all in the latter.
+    Returns the plan and the first row of every sequence."""
     starts = [0]  # the first row of every sequence
     for c in counts[:-1]:
         starts.append(starts[-1] + c)
-    live =[b for b, c in enumerate(counts) if c]
+    live = [b for b, c in enumerate(counts) if c]
     small = [b for b in live if counts[b] <= _ATTN_DECODE_MAX_S] if kernel == KERNEL_AUTO else []
     big = [b for b in live if counts[b] > _ATTN_DECODE_MAX_S] if kernel == KERNEL_AUTO else live
-    if eff_window is not None and live:
-        if any(cache.pt.released[slots[b]] for b in live) and (cache.window is None or eff_window > cache.window):
-            raise ValueError(f"{who}: window={eff_window} on sequences that have released the pages below the cache's window of {cache.window} keys")
-        if big and max(lens[b] for b in big) > eff_window:
-            raise ValueError(f"{who}: kernel='prefill' with window={eff_window} and lengths {[lens[b] for b in big]} - the prefill kernel has no "
-                             "window rule; it is taken while every length is <= the window")
+    plan = []
+    for name, bs in ((RAGGED_DECODE, small), (RAGGED_PREFILL, big)):
+        if bs:
+            lo, hi = starts[bs[0]], starts[bs[-1]] + counts[bs[-1]]
+            plan.append((name, bs, slice(lo, hi) if hi - lo == sum(counts[b] for b in bs) else None))
+    return plan, starts
+
+
+@torch.no_grad()
+def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scaling, causal=False, return_stats=False, ws=None, kernel=KERNEL_AUTO,
+                                    window=None):
+    """attention_flexible_paged for sequences with a number of query rows of their own - one scheduler step of continuous batching,
+    most sequences decoding one token while a few take a prompt chunk.  q [sum(counts), h, d]: sequence seqs[b] owns rows
+    sum(counts[:b]) .. + counts[b] - 1; the output has q's shape, the statistics are [sum(counts), h, 2].  `causal`: key j of sequence b
+    visible to its query row i iff j <= i + (length_b - counts[b]).  A count of 0 leaves its sequence out (it may be empty).
+    kernel="prefill": the whole batch in ONE lqer_attention_q_paged_ragged call - the prefill kernel takes every sequence's length
+    and count from the device; each sequence gets the bits of attention_flexible(..., kernel="prefill") on its raw K and V alone.
+    kernel="auto" (the default): ALL sequences of up to 8 rows go through ONE lqer_attention_q_decode_paged_ragged call - the decode
+    kernels take every sequence's count from the device, whatever the distinct counts are (attention_flexible_paged_decode_ragged) -
+    and all others through one lqer_attention_q_paged_ragged call: at most two library calls, and every sequence gets the bits
+    attention_flexible_paged(kernel="auto") gives it alone.  A call whose sequences' rows are one range of q - the decoders named
+    first and the chunks last, say - takes them as a view and writes its rows of the output in place; the rows of a call that another
+    call's rows lie between are gathered and scattered by index on the device, once.  attention_flexible_paged_ragged.plan(cache,
+    seqs, counts, kernel, window) names the calls without touching a device.
+    `window` (default: the cache's) and every refusal are those of the route a sequence takes, in its words: the decode route has the
+    window rule, the prefill kernel is taken with a window only while every length it addresses is <= W.  ValueError before anything
+    is launched: len(counts) != len(seqs), a negative count, sum(counts) != q.shape[0], causal with counts[b] > length_b, an empty
+    sequence with a count, an unknown or repeated sequence, a wrong dtype, device or head count.  ws: a uint8 workspace or None."""
+    who = "attention_flexible_paged_ragged"
+    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
+        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    eff_window = _ragged_window(who, cache, window, causal)
+    seqs, counts = _ragged_counts(who, seqs, counts)
+    slots, lens = _ragged_operands(who, q, cache, seqs, counts, causal)
+    total, h, d = q.shape
+    plan, starts = _ragged_plan(counts, kernel)
+    live = [b for _, bs, _ in plan for b in bs]
+    big = [bs for name, bs, _ in plan if name == RAGGED_PREFILL]
+    big = big[0] if big else []
+    if live:
+        _ragged_released(who, cache, slots, live, eff_window)
+    if eff_window is not None and big and max(lens[b] for b in big) > eff_window:
+        raise ValueError(f"{who}: kernel='prefill' with window={eff_window} and lengths {[lens[b] for b in big]} - the prefill kernel has no "
+                         "window rule; it is taken while every length is <= the window")
     if big and (max(lens[b] for b in big) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
         raise ValueError(f"{who}: {len(big)} sequences of lengths {[lens[b] for b in big]} beyond the prefill kernel's launch grid")
     if q.stride(2) != 1:
         q = q.contiguous()
     out = torch.empty(total, h, d, dtype=q.dtype, device=q.device)
     stats = torch.empty(total, h, 2, dtype=torch.float32, device=q.device) if return_stats else None
-    # One call per distinct count of the decode route, one for all other sequences.  A call whose sequences' rows are ONE range of q (no
-    # other call's rows between them: the decoders in front and the chunks behind, say) runs on views of q and out; the rows of the
+    # At most two calls: one for the sequences of the decode route, one for all others.  A call whose sequences' rows are ONE range of q
+    # (no other call's rows between them: the decoders in front and the chunks behind, say) runs on views of q and out; the rows of the
     # others are gathered and scattered by index - all of them through one index tensor, copied to the device once.
-    calls = {}
-    for b in small:
-        calls.setdefault(counts[b], []).append(b)
-    calls = list(calls.values()) + ([big] if big else [])
-
-    def span(bs):
-        lo, hi = starts[bs[0]], starts[bs[-1]] + counts[bs[-1]]
-        return slice(lo, hi) if hi - lo == sum(counts[b] for b in bs) else None
-
     rows, where = [], []
-    for bs in calls:
-        where.append(span(bs))
-        if where[-1] is None:
+    for _, bs, at in plan:
+        where.append(at)
+        if at is None:
             mine = [r for b in bs for r in range(starts[b], starts[b] + counts[b])]
             where[-1] = (len(rows), len(rows) + len(mine))
             rows += mine
     idx = torch.tensor(rows, dtype=torch.int64).to(q.device) if rows else None
-    for bs, at in zip(calls, where):
-        ix = None if isinstance(at, slice) else idx[at[0]:at[1]]
-        qc = q[at] if ix is None else q.index_select(0, ix)
-        if bs is big:
-            args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], [counts[b] for b in bs], scaling, causal)
-            if ix is None:  # (in place: nothing to copy)
-                _ragged_call(qc, *args, out[at], stats[at] if return_stats else None, ws)
-                continue
-            oc = torch.empty_like(qc)
-            sc = torch.empty(qc.shape[0], h, 2, dtype=torch.float32, device=q.device) if return_stats else None
-            _ragged_call(qc, *args, oc, sc, ws)
-        else:
-            c = counts[bs[0]]
-            got = attention_flexible_paged(qc.view(len(bs), c, h, d).transpose(1, 2), cache, [seqs[b] for b in bs], scaling, causal=causal,
-                                           out_layout="bshd", return_stats=return_stats, ws=ws, kernel=KERNEL_DECODE, window=window)
-            oc, sc = got if return_stats else (got, None)
-            oc = oc.view(len(bs) * c, h, d)
-            sc = sc.transpose(1, 2).reshape(len(bs) * c, h, 2) if return_stats else None
-        if ix is None:
-            out[at].copy_(oc)
-            if return_stats:
-                stats[at].copy_(sc)
-        else:
-            out.index_copy_(0, ix, oc)
-            if return_stats:
-                stats.index_copy_(0, ix, sc)
+    for (name, bs, _), at in zip(plan, where):
+        args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], [counts[b] for b in bs], scaling, causal)
+        win = eff_window if name == RAGGED_DECODE else None  # (the prefill call: every length <= W, plain causal)
+        if isinstance(at, slice):  # (in place: nothing to copy)
+            _ragged_call(name, q[at], *args, out[at], stats[at] if return_stats else None, ws, win)
+            continue
+        ix = idx[at[0]:at[1]]
+        qc = q.index_select(0, ix)
+        oc = torch.empty_like(qc)
+        sc = torch.empty(qc.shape[0], h, 2, dtype=torch.float32, device=q.device) if return_stats else None
+        _ragged_call(name, qc, *args, oc, sc, ws, win)
+        out.index_copy_(0, ix, oc)
+        if return_stats:
+            stats.index_copy_(0, ix, sc)
     return (out, stats) if return_stats else out
+
+
+def _plan(cache: PagedKVCache, seqs, counts, kernel=KERNEL_AUTO, window=None) -> list:
+    """The library calls attention_flexible_paged_ragged(q, cache, seqs, counts, ..., kernel=kernel, window=window) makes, in order,
+    from host state alone (no device is touched, no length is read): one dict per call - "call": the C entry, "seqs": the indices into
+    `seqs` of the sequences it takes, "rows": "view" when their rows are one range of q and the call runs on views of q and out,
+    "gathered" when they are gathered and scattered by index, "window": the window rule it runs under (None: none; the prefill
+    call has no rule).  Each call is three launches.  Refuses an unknown `kernel`, a bad `window` and bad counts as the function does."""
+    who = "attention_flexible_paged_ragged"
+    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
+        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    eff_window = _ragged_window(who, cache, window, True)
+    seqs, counts = _ragged_counts(who, seqs, counts)
+    return [{"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered", "window": eff_window if name == RAGGED_DECODE else None}
+            for name, bs, at in _ragged_plan(counts, kernel)[0]]
+
+
+attention_flexible_paged_ragged.plan = _plan
+
+

@@ -1,6 +1,6 @@
 """Time one MIXED scheduler step over the paged KV pool - most sequences decode one token while one or two arrivals take a prompt chunk -
 done in one append_ragged plus one attention_flexible_paged_ragged(causal=True) (lqer_kv_pool_append_ragged; the decoders through
-lqer_attention_q_decode_paged, the chunks through lqer_attention_q_paged_ragged) against the same step done the way the pool offered
+lqer_attention_q_decode_paged_ragged, the chunks through lqer_attention_q_paged_ragged) against the same step done the way the pool offered
 before per-sequence counts, on the same commit: one append and one attention_flexible_paged(kernel="auto") per DISTINCT count.  Both
 in this process on the same box, with HIP events.
 
@@ -107,8 +107,9 @@ def one_shape(name, groups, cfg, a):
            "heads_kvheads_d": [H, HK, D], "dtype": "float16", "mask": "causal", "buffers": nbuf, "pool_bytes": pool_bytes, "same_bits": same,
            # library launches: an append is 1; an attention call is 3 (the decode kernels, or K image + V image + k_attn_q)
            "per_count_launches": {"append": len(by_count), "attention": 3 * len(by_count)},
-           # (the groups' rows are ranges of q here: nothing is gathered; a decode group's output is copied into its rows of out)
-           "ragged_launches": {"append": 1, "attention": 3 * len(small) + (3 if big else 0), "torch_copies_into_out": len(small)}}
+           # (all sequences of up to 8 rows are one call, the chunks another; the groups' rows are ranges of q here: nothing is gathered,
+           # and both calls write their rows of out in place)
+           "ragged_launches": {"append": 1, "attention": (3 if small else 0) + (3 if big else 0), "torch_copies_into_out": 0}}
     for leg in LEGS:
         out[f"us_{leg}"] = round(med[leg], 1)
         out[f"us_{leg}_rounds"] = [round(x, 1) for x in rounds[leg]]
