@@ -179,6 +179,11 @@ typedef struct lqer_linear_desc {
                                            block scale carrying 2^9.  Same bits - and REQUIRED for a weight image that holds an
                                            exponent byte above 245 (a block maximum of 2^121 or more; lqer_f16_prepare reports
                                            it as flags[0] & 2), where byte + 9 leaves the fp32 exponent field                  */
+#define LQER_TUNE_NO_KSPLIT 0x10000000 /* 128-row tile kernel, B_out in blocks of 16 under the main loop, side product of at most two
+                                          16-deep slices: every wave takes all four k slices of its own 32 columns (each reads the
+                                          whole activation slot from LDS) instead of the default - the two waves of a SIMD share 64
+                                          columns and take two slices each, and exchange partial sums behind the main loop
+                                          (csrc/gemm_w4a8.hip, KSPLIT)                                                          */
 #define LQER_TUNE_DECODE_NO_POLL 0x10000 /* one-launch decode route: no wait for the producers' tiles - every weight-streaming
                                          workgroup computes the partial tiles of x A itself (the bounded wait's fall-back)     */
 

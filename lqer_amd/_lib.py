@@ -23,6 +23,7 @@ TUNE_ACT16_SPLIT, TUNE_ACT16_FUSED = 0x800000, 0x1000000  # block-16 MXINT activ
 TUNE_ACT8_SPLIT, TUNE_ACT8_FUSED = 0x200000, 0x400000  # int8 route's activation side: three launches / the one-launch kernel at every M
 TUNE_AMAX_NO_MRX = 0x4000000  # int8 route over several rounds of 128-row tiles: the k_bout_amax pre-pass launch instead of the in-GEMM items
 TUNE_BOUT_IN_PROLOGUE = 0x2000000  # 128-row tile kernel: the B_out re-quantization in front of the main loop (rounds 1-5) instead of under it
+TUNE_NO_KSPLIT = 0x10000000  # 128-row tile kernel, deferred B_out, direct side path: every wave all four k slices of its own 32 columns
 TUNE_W_EXP_TABLE = 0x8000000  # bf16 tile kernel: the table expand of sign-magnitude nibbles (required for exponent bytes above 245)
 TUNE_AMAX_XCH_MISS = 0x100000  # int8 route's in-GEMM exchange of the B_out row maxima: every workgroup takes its fall-back
 

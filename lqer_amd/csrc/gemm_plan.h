@@ -34,6 +34,7 @@ struct GemmPlan {
   bool lowrank;
   bool f16x;                  // fp16 activations multiplied natively (LQER_F16X in place of LQER_F16)
   bool staged, defer;         // 128-row family: side-product operands through LDS; blocks of 16 re-quantized under the main loop
+  bool ksplit;                // ... the deferred, direct kernel with a SIMD's two waves splitting the k-step (gemm_w4a8.hip, KSPLIT)
   bool w_twos, w_mf;          // 128-row family: integer / minifloat nibbles
   bool i8_shift, i8_codes;    // int8 route: weight groups with shifts; 8-bit weight codes
   int mt;                     // small-M kernel: 16-row token tiles, 1..4

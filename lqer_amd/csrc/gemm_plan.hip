@@ -235,6 +235,9 @@ GemmPlan plan_gemm(const GemmArgs& g, bool lowrank, bool i8_image, int dtype, in
       // nibbles, K >= 1024, clamps within the magic-number rounding, and the 1e-8 pass-through that makes the clamped scale exponent exact
       p.defer = p.bout == 1 && !nibbles128 && p.tile_rows == 128 && !(g.tuning & LQER_TUNE_BOUT_IN_PROLOGUE) && g.Kp / BK >= 16 &&
                 g.bout.kind == LQER_Q_MXINT && g.bout.mmax <= 4194304.0f && g.bout.mneg <= 4194304.0f && g.bout.tiny >= 1e-8f;
+      // the wave pairs of a SIMD split the k-step (half the LDS activation reads): the deferred kernel with the direct side path on
+      // the bf16 main loop (gemm_w4a8.hip: that instantiation itself; the pin runs k_lqer_gemm_nks)
+      p.ksplit = p.defer && !p.staged && !p.f16x && !(g.tuning & LQER_TUNE_NO_KSPLIT);
       break;
   }
   return p;

@@ -48,6 +48,11 @@ constexpr int OFF_A = 0;
 // per tile height (MT 32-row tiles): activation slot 16 KiB (128 rows) or 8 KiB (64 rows), bf16; the panels behind the ring
 constexpr int a_slot_bytes(int mt) { return 32 * mt * BK * 2; }
 constexpr int gemm_lds_bytes(int mt) { return NSLOT * a_slot_bytes(mt) + NSLOT * R_SLOT; }  // 102400 B / 69632 B (two workgroups per CU)
+// KSPLIT: the stash of the side product's late operands is static LDS of the kernel, beside the ring's dynamic bytes (4 KiB of xAq
+// fragments, then 2 KiB of B^T fragments per wave); behind the main loop the drained ring is the exchange of the wave pairs' partial
+// sums, two m tiles = 8 KiB per wave at a time
+constexpr int KS_STASH_B = 4096, KS_STASH_BYTES = KS_STASH_B + 8 * 2048, KS_XCH = 8192;
+static_assert(8 * KS_XCH <= gemm_lds_bytes(4), "the exchange lies inside the ring");
 
 // ---- LDS access in inline asm -------------------------------------------------------------------
 // hipcc's waitcnt pass treats every global_load_lds in flight as a pending LDS write and puts
@@ -83,6 +88,10 @@ __device__ __forceinline__ int lds_read_i8_512(uint32_t addr) {
 }
 __device__ __forceinline__ void lds_write128(uint32_t addr, u32x4 v) {
   asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_write128_at(uint32_t addr, f32x4 v) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "i"(OFF) : "memory");
 }
 __device__ __forceinline__ void lds_wait(bf16x8& a, bf16x8& b, bf16x8& c, bf16x8& d) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
@@ -134,11 +143,22 @@ __device__ unsigned long long* g_stamp_buf = nullptr;  // diagnostic builds only
 // |x| <= 1e-8 passes through: gemm_w4a8_i8.hip's epilogue); blocks of 16, clamps up to 2^22 and K >= 1024 (launch_gemm).
 // WMF: the packed weight holds minifloat codes (w_quantizer = minifloat, 2..4 bits): the magnitude code indexes the format's e4m3 table
 // (g.w_lut, expand_frag_lut) instead of the integer one.  BOUT 3: a minifloat B_out, elementwise (minifloat_value) in the prologue.
-template <int DT, bool LOWRANK, int BOUT, bool STAGED = false, int MT = 4, bool WTWOS = false, bool DEFER = false, bool WMF = false>
-__global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
+// KSPLIT: the two waves of a SIMD (w and w + 4) share 128 rows x 64 columns and split the k-step between them: each reads the
+// activation fragments of two of its four 16-deep slices (8 x 16 B instead of 16: half the LDS activation reads of the workgroup),
+// expands the weight fragments of those slices for both 32-column halves (4 per step, as before) and issues the same 16 MFMAs, into
+// acc (the half it will store) and acc_o (its partner's half).  Behind the main loop the pairs exchange acc_o through LDS, over the
+// drained ring (two m tiles at a time), and each wave adds its partner's partial to its own.  Registers: acc + acc_o are 128, the fragments 32, so the
+// deferred side product is held 64 rows at a time: m tiles 0 and 1 from the prologue (pieces 0-7, added behind step 7), m tiles
+// 2 and 3 from operands the prologue stashes in static LDS and step 8 reads back (pieces 8-15, added behind step 15).
+// DEFER with the direct side path and the table-free expand only (the instantiation of 2048 x 4096 -> 4096 at rank 32).
+// (the body of both kernels below: the k split is k_lqer_gemm's deferred, direct instantiation; k_lqer_gemm_nks is that instantiation
+// with every wave on all four slices, the geometry of the other instantiations)
+template <int DT, bool LOWRANK, int BOUT, bool STAGED, int MT, bool WTWOS, bool DEFER, bool WMF, bool KSPLIT>
+__device__ __forceinline__ void gemm_tile_body(const GemmArgs& g) {
   static_assert(MT == 4 || MT == 2, "128- or 64-row tiles");
   static_assert(!DEFER || (LOWRANK && BOUT == 1 && MT == 4), "deferred B_out: blocks of 16 on 128-row tiles");
   static_assert(!WTWOS || DT != LQER_F16X, "integer weights: no fp16 main loop");
+  static_assert(!KSPLIT || (DEFER && !STAGED && !WTWOS && !WMF && DT != LQER_F16X), "k split: deferred B_out, direct side path, plain nibbles, bf16");
   constexpr int BMk = 32 * MT;   // tile rows
   constexpr int AP = MT / 2;     // 8-row LDS-DMA pieces of the activation tile per wave and k-step
   constexpr bool XF16 = DT == LQER_F16X;  // fp16 activation image, weights expanded to fp16, v_mfma_f32_32x32x16_f16
@@ -146,7 +166,10 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wn = wave;  // 8 waves side by side along n: each owns all 128 token rows x 32 output columns
+  // 8 waves side by side along n: each owns (KSPLIT: stores) all 128 token rows x 32 output columns.  KSPLIT: waves w and w + 4
+  // hold columns 64 (w % 4) .. + 64 - the lower wave stores the first half - and kh is the wave's pair of k slices (2 kh, 2 kh + 1)
+  const int kh = KSPLIT ? wave >> 2 : 0;
+  const int wn = KSPLIT ? 2 * (wave & 3) + kh : wave;
   const int l31 = lane & 31, lh = lane >> 5;
 #ifdef LQER_CLOCKPROBE
   unsigned long long cp_rin, cp_rq = 0;  // diagnostic build: the chip-wide 100 MHz counter at the wave's entry / in front of the B_out re-quantization
@@ -190,15 +213,25 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   // fragment read addresses (slot 0).  Activation: row = wave tile row + lane & 31, chunk 2 ks + (lane >> 5),
   // swizzled; the second m tile is +32 rows = +4096 B (row + 32 keeps (row >> 1) & 7).
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void*)smem;
+  uint32_t stash0 = 0;  // KSPLIT: the stash of the side product's late operands
+  if constexpr (KSPLIT) {
+    __shared__ __attribute__((aligned(16))) unsigned char ks_stash[KS_STASH_BYTES];
+    stash0 = (uint32_t)(uintptr_t)(lds_void*)ks_stash;
+  }
   uint32_t fa_addr[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) fa_addr[ks] = lds0 + OFF_A + swz(l31, 2 * ks + lh);  // m tile i: + i * 4096
+  for (int ks = 0; ks < 4; ++ks) fa_addr[ks] = lds0 + OFF_A + swz(l31, 2 * (KSPLIT ? (2 * kh + ks) & 3 : ks) + lh);  // m tile i: + i * 4096 (KSPLIT: [0], [1] are the wave's two slices)
   // Packed weights: weight row n = wave tile column + lane & 31 lives in panel n / 16 at row n % 16; its
   // 32 B of codes hold the words of chunks {0,2,4,6} then {1,3,5,7}, so the lane's 4 words (chunk
   // 2 ks + (lane >> 5), ks = 0..3) are one 16-byte read; its 4 biased block exponents are one 4-byte read.
   const int nw = wn * 32 + l31;
   const uint32_t fw_addr = lds0 + OFF_R + (nw >> 4) * LQER_PANEL_BYTES + (nw & 15) * 32 + lh * 16;
   const uint32_t fe_addr = lds0 + OFF_R + (nw >> 4) * LQER_PANEL_BYTES + (nw & 15) * 4;  // + 512
+  // KSPLIT: the wave's two slices are 8 of those 16 bytes of codes and 2 of the 4 exponent bytes, for its own column half and (+-
+  // two panels) for its partner's
+  const uint32_t ks_fw = fw_addr + 8 * kh, ks_fe = fe_addr + 2 * kh;
+  const uint32_t ks_fw_o = kh ? ks_fw - 2 * LQER_PANEL_BYTES : ks_fw + 2 * LQER_PANEL_BYTES;
+  const uint32_t ks_fe_o = kh ? ks_fe - 2 * LQER_PANEL_BYTES : ks_fe + 2 * LQER_PANEL_BYTES;
 
   // ---- side path, first half: fetch before the ring prefetch -----------------------------------------------------
   // acc = Q_Bout(xAq @ B) + bias opens the accumulators.  The tile's rows of xAq are staged through LDS - 64 rank
@@ -248,6 +281,10 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 #pragma unroll
     for (int sl = 0; sl < 2; ++sl) {
       const int l = two_limbs ? sl : 0, ks = two_limbs ? 0 : sl;
+      if constexpr (KSPLIT) {  // (a slice that does not exist is stashed as zeros: step 8 multiplies both without a branch)
+        db[sl] = bf16x8{};
+        dx[sl][2] = dx[sl][3] = bf16x8{};
+      }
       if (l < g.b_limbs && ks * 16 < g.rp) {
         db[sl] = *(const bf16x8*)(g.bt + ((int64_t)l * g.Np + n0 + wn * 32 + l31) * g.rp + ks * 16 + 8 * lh);
 #pragma unroll
@@ -265,12 +302,20 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[i][k] = 0.f;
-  f32x16 sp[DEFER ? MT : 1];  // DEFER: the side product, re-quantized in place during the first k-steps
+  constexpr int SPT = KSPLIT ? 2 : MT;  // m tiles of the side product held at a time
+  f32x16 sp[DEFER ? SPT : 1];  // DEFER: the side product, re-quantized in place during the first k-steps
   if constexpr (DEFER) {
+#pragma unroll
+    for (int i = 0; i < SPT; ++i)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sp[i][k] = 0.f;
+  }
+  f32x16 acc_o[KSPLIT ? MT : 1];  // KSPLIT: the partial sums of the partner's column half
+  if constexpr (KSPLIT) {
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int k = 0; k < 16; ++k) sp[i][k] = 0.f;
+      for (int k = 0; k < 16; ++k) acc_o[i][k] = 0.f;
   }
   auto side_acc = [&](int i) -> f32x16& {
     if constexpr (DEFER) return sp[i];
@@ -285,7 +330,20 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
         const int l = two_limbs ? sl : 0, ks = two_limbs ? 0 : sl;
         if (l < g.b_limbs && ks * 16 < g.rp) {
 #pragma unroll
-          for (int i = 0; i < MT; ++i) side_acc(i) = __builtin_amdgcn_mfma_f32_32x32x16_bf16(db[sl], dx[sl][i], side_acc(i), 0, 0, 0);
+          for (int i = 0; i < SPT; ++i) side_acc(i) = __builtin_amdgcn_mfma_f32_32x32x16_bf16(db[sl], dx[sl][i], side_acc(i), 0, 0, 0);
+        }
+      }
+      if constexpr (KSPLIT) {
+        // the operands of m tiles 2 and 3 wait in LDS for step 8: the activation side's fragments are the same in every wave
+        // (wave 0 writes them), the B^T fragments are the wave's own
+        const uint32_t st_b = stash0 + KS_STASH_B + wave * 2048 + lane * 16, st_x = stash0 + lane * 16;
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl) {
+          lds_write128(st_b + sl * 1024, __builtin_bit_cast(u32x4, db[sl]));
+          if (wave == 0) {
+            lds_write128(st_x + (2 * sl) * 1024, __builtin_bit_cast(u32x4, dx[sl][2]));
+            lds_write128(st_x + (2 * sl + 1) * 1024, __builtin_bit_cast(u32x4, dx[sl][3]));
+          }
         }
       }
     }
@@ -392,7 +450,8 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
   // which ends (lgkmcnt(0)) before barrier 2kt-1; the overwriting loads are issued after it.
   const bool late = wave >= 4;
   // loads(0) landed; two batches of AP + 1 (3, or 2 with 64-row tiles) may stay in flight
-  if constexpr (MT == 4) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
+  if constexpr (KSPLIT) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (and the stash is written)
+  else if constexpr (MT == 4) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
   if (late) asm volatile("s_barrier" ::: "memory");
 #ifdef LQER_CLOCKPROBE
@@ -426,7 +485,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     constexpr int P = decltype(piece_c)::value;
     if constexpr (DEFER && P >= 0) {
       typedef __attribute__((ext_vector_type(2))) float f2;
-      constexpr int J = P >> 1, I = J >> 1, B8 = 8 * (J & 1);
+      constexpr int J = P >> 1, I = (J >> 1) % SPT, B8 = 8 * (J & 1);  // (KSPLIT: sp holds m tiles 0, 1, from step 8 on m tiles 2, 3)
       if constexpr ((P & 1) == 0) {
         float amax = 0.f;
 #pragma unroll
@@ -460,7 +519,7 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     constexpr int P = decltype(piece_c)::value;
     (void)dq_s, (void)dq_inv, (void)sp;  // (captured here: operands of an asm statement inside a dependent branch do not make a capture)
     if constexpr (DEFER && P >= 0) {
-      constexpr int J = P >> 1, I = J >> 1, B8 = 8 * (J & 1);
+      constexpr int J = P >> 1, I = (J >> 1) % SPT, B8 = 8 * (J & 1);  // (KSPLIT: sp holds m tiles 0, 1, from step 8 on m tiles 2, 3)
       if constexpr ((P & 1) == 0) asm volatile("" : "+v"(dq_s), "+v"(dq_inv));
       else
         asm volatile("" : "+v"(sp[I][B8]), "+v"(sp[I][B8 + 1]), "+v"(sp[I][B8 + 2]), "+v"(sp[I][B8 + 3]), "+v"(sp[I][B8 + 4]), "+v"(sp[I][B8 + 5]),
@@ -479,7 +538,40 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     bf16x8 xa[4][MT];  // [ks][m tile]
     u32x4 wr;
     uint32_t we;
-    if constexpr (MT == 4) {
+    constexpr int P = decltype(piece_c)::value;
+    u32x2 wr2[2];      // KSPLIT: the code words of the wave's two slices, [own half, partner's half]
+    uint32_t we2[2];   // ... and their two exponent bytes
+    bf16x8 sdb[2], sdx[2][2];  // KSPLIT, step 8: the stashed side operands of m tiles 2 and 3
+    if constexpr (KSPLIT) {
+      if constexpr (P == 8) {
+        const uint32_t st_b = stash0 + KS_STASH_B + wave * 2048 + lane * 16, st_x = stash0 + lane * 16;
+        asm volatile(
+            "ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:1024\n\t"
+            "ds_read_b128 %2, %7\n\tds_read_b128 %3, %7 offset:1024\n\tds_read_b128 %4, %7 offset:2048\n\tds_read_b128 %5, %7 offset:3072\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(sdb[0]), "=&v"(sdb[1]), "=&v"(sdx[0][0]), "=&v"(sdx[0][1]), "=&v"(sdx[1][0]), "=&v"(sdx[1][1])
+            : "v"(st_b), "v"(st_x)
+            : "memory");
+      }
+      asm volatile(
+          "ds_read_b64 %[w0], %[fw] offset:%c[ro]\n\tds_read_b64 %[w1], %[fwo] offset:%c[ro]\n\t"
+          "ds_read_u16 %[e0], %[fe] offset:%c[ro]+512\n\tds_read_u16 %[e1], %[feo] offset:%c[ro]+512\n\t"
+          LQER_READ_X2("%[x00]", "%[x01]", "%[fa0]", "%c[ao]") LQER_READ_X2("%[x02]", "%[x03]", "%[fa0]", "%c[ao]+8192")
+          LQER_READ_X2("%[x10]", "%[x11]", "%[fa1]", "%c[ao]") LQER_READ_X2("%[x12]", "%[x13]", "%[fa1]", "%c[ao]+8192")
+          LQER_LDS_DMA("%[ma0]", "%[av0]", "%[ars]", "%[aso]") LQER_LDS_DMA("%[ma1]", "%[av1]", "%[ars]", "%[aso]")
+          LQER_LDS_DMA("%[mw]", "%[wv]", "%[wrs]", "%[wso]")
+          "s_cmp_lg_u32 %[wv0], 0\n\ts_cbranch_scc1 1f\n\t"
+          LQER_LDS_DMA("%[mw8]", "%[wv8]", "%[wrs]", "%[wso]")
+          "1:\n\ts_waitcnt vmcnt(6) lgkmcnt(0)"  // (as below)
+          : [w0] "=&v"(wr2[0]), [w1] "=&v"(wr2[1]), [e0] "=&v"(we2[0]), [e1] "=&v"(we2[1]), [x00] "=&v"(xa[0][0]), [x01] "=&v"(xa[0][1]),
+            [x02] "=&v"(xa[0][2]), [x03] "=&v"(xa[0][3]), [x10] "=&v"(xa[1][0]), [x11] "=&v"(xa[1][1]), [x12] "=&v"(xa[1][2]),
+            [x13] "=&v"(xa[1][3])
+          : [fw] "v"(ks_fw), [fwo] "v"(ks_fw_o), [fe] "v"(ks_fe), [feo] "v"(ks_fe_o), [fa0] "v"(fa_addr[0]), [fa1] "v"(fa_addr[1]),
+            [ao] "i"(SLOT * A_SLOT), [ro] "i"(SLOT * R_SLOT), [av0] "v"(a_voff[0]), [av1] "v"(a_voff[1]), [wv] "v"(w_voff),
+            [wv8] "v"(w_voff8), [ars] "s"(a_rs), [wrs] "s"(w_rs), [ma0] "s"(m0a0), [ma1] "s"(m0a1), [mw] "s"(m0w), [mw8] "s"(m0w8),
+            [aso] "s"(a_soff), [wso] "s"(w_soff), [wv0] "s"(wave)
+          : "memory", "scc");
+    } else if constexpr (MT == 4) {
       asm volatile(
           "ds_read_b128 %0, %18 offset:%c25\n\tds_read_b32 %1, %19 offset:%c25+512\n\t"
           LQER_READ_X2("%2", "%3", "%20", "%c24") LQER_READ_X2("%4", "%5", "%20", "%c24+8192")
@@ -521,27 +613,65 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
     // sign-magnitude nibbles on the bf16 main loop: the table-free expand (expand_frag_lin), its 2^9 added to the step's four
     // exponent bytes at once (no carry: the plan sends an image with a byte beyond LIN_EXP_BYTE_MAX to the WMF instantiation)
     constexpr bool WLIN = !WMF && !WTWOS && !XF16;
-    if constexpr (WLIN) we += 0x09090909u;
+    if constexpr (WLIN && !KSPLIT) we += 0x09090909u;
     auto expand = [&](uint32_t word, uint32_t scale_bits) {
       if constexpr (WMF) return expand_frag_lut(word, scale_bits, g.w_lut[0], g.w_lut[1]);
       else if constexpr (WTWOS) return expand_frag_twos(word, scale_bits);
       else if constexpr (WLIN) return expand_frag_lin(word, scale_bits);
       else return expand_frag_t<XF16>(word, scale_bits);
     };
+    if constexpr (KSPLIT) {
+      we2[0] += 0x0909u, we2[1] += 0x0909u;
+      wr[0] = wr2[0][0], we = we2[0];
+    }
     bf16x8 wb_first = expand(wr[0], exp_byte_bits<0>(we));
     asm volatile("s_barrier" : "+v"(wb_first)::"memory");
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     STAMP(4);  // expand of the first fragment + barrier
     // ---- COMPUTE(kt)
+    if constexpr (KSPLIT && P == 8) {  // m tiles 0 and 1 of the side product are done: add them, and multiply m tiles 2 and 3
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[i][k] += sp[i][k], sp[i][k] = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl) sp[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sdb[sl], sdx[sl][i], sp[i], 0, 0, 0);
+      }
+    }
     defer_piece(piece_c);
-    // biased exponent byte ks -> fp32 bits of the block scale 2^(e - mbits)
-    const uint32_t sc[4] = {0u, exp_byte_bits<1>(we), exp_byte_bits<2>(we), exp_byte_bits<3>(we)};  // ([0]: wb_first has it)
+    if constexpr (KSPLIT) {
+      // [column half][slice] -> fp32 bits of the block scale 2^(e - mbits + 9)
+      const uint32_t sc[2][2] = {{0u, exp_byte_bits<1>(we2[0])}, {exp_byte_bits<0>(we2[1]), exp_byte_bits<1>(we2[1])}};  // ([0][0]: wb_first has it)
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 wb = ks == 0 ? wb_first : expand(wr[ks], sc[ks]);
+      for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int i = 0; i < MT; ++i) acc[i] = mfma_32x32x16<XF16>(wb, xa[ks][i], acc[i]);
+        for (int h = 0; h < 2; ++h) {
+          const bf16x8 wb = j + h == 0 ? wb_first : expand(wr2[h][j], sc[h][j]);
+#pragma unroll
+          for (int i = 0; i < MT; ++i) {
+            if (h) acc_o[i] = mfma_32x32x16<XF16>(wb, xa[j][i], acc_o[i]);
+            else acc[i] = mfma_32x32x16<XF16>(wb, xa[j][i], acc[i]);
+          }
+        }
+      // one wave feeds the SIMD's MFMA pipe during COMPUTE: the next fragment's 11 vector instructions go three at a time into the
+      // shadows of the four MFMAs of this one (a clump of 11 between two MFMAs leaves the pipe idle)
+      if constexpr (P < 0) {
+#pragma unroll
+        for (int n = 0; n < 16; ++n) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+        }
+      }
+    } else {
+      // biased exponent byte ks -> fp32 bits of the block scale 2^(e - mbits)
+      const uint32_t sc[4] = {0u, exp_byte_bits<1>(we), exp_byte_bits<2>(we), exp_byte_bits<3>(we)};  // ([0]: wb_first has it)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8 wb = ks == 0 ? wb_first : expand(wr[ks], sc[ks]);
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[i] = mfma_32x32x16<XF16>(wb, xa[ks][i], acc[i]);
+      }
     }
     defer_pin(piece_c);
     __builtin_amdgcn_sched_barrier(0);
@@ -594,16 +724,50 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 
   if constexpr (DEFER) {
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
+    for (int i = 0; i < SPT; ++i)
 #pragma unroll
-      for (int k = 0; k < 16; ++k) acc[i][k] += sp[i][k];
+      for (int k = 0; k < 16; ++k) acc[MT - SPT + i][k] += sp[i][k];  // (KSPLIT: m tiles 2 and 3; step 8 added 0 and 1)
   }
+  if constexpr (KSPLIT) {
+    // every wave's LDS-DMA has landed (vmcnt(0) above); behind this barrier every ring read is done too: the ring is free
+    asm volatile("s_barrier" ::: "memory");
+  }
+  // KSPLIT, at the head of the stores of m tile i: the waves leave their partials of the partner's column half, two m tiles at a
+  // time, each in its own 8 KiB (16 B per lane and quad: conflict-free) - in front of tile 2 a barrier first, behind which everyone
+  // has read tiles 0 and 1 -, and each wave adds what its partner left for tile i (the stores of tile i - 1 are then in flight)
+  auto add_partner = [&](int i) {
+    if constexpr (KSPLIT) {
+      if (i == 0 || i == 2) {
+        const uint32_t x_out = lds0 + wave * KS_XCH + lane * 16;
+        if (i == 2) asm volatile("s_barrier" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          lds_write128_at<0>(x_out + j * 4096, __builtin_shufflevector(acc_o[i + j], acc_o[i + j], 0, 1, 2, 3));
+          lds_write128_at<1024>(x_out + j * 4096, __builtin_shufflevector(acc_o[i + j], acc_o[i + j], 4, 5, 6, 7));
+          lds_write128_at<2048>(x_out + j * 4096, __builtin_shufflevector(acc_o[i + j], acc_o[i + j], 8, 9, 10, 11));
+          lds_write128_at<3072>(x_out + j * 4096, __builtin_shufflevector(acc_o[i + j], acc_o[i + j], 12, 13, 14, 15));
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      }
+      const uint32_t x_in = lds0 + (wave ^ 4) * KS_XCH + lane * 16 + (i & 1) * 4096;
+      f32x4 q0, q1, q2, q3;
+      asm volatile(
+          "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\t"
+          "ds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+          : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
+          : "v"(x_in)
+          : "memory");
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[i][t] += q0[t], acc[i][4 + t] += q1[t], acc[i][8 + t] += q2[t], acc[i][12 + t] += q3[t];
+    }
+  };
   // ---- store ----------------------------------------------------------------------------------
   // per 32x32 tile and quad q: regs 4q..4q+3 = columns n = nb + 8q + 4 lh + (0..3) of token row m
   const bool aligned16 = (((uintptr_t)g.y) & 15) == 0;
   const int nb = n0 + wn * 32;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
+    add_partner(i);
     const int m = m0 + i * 32 + l31;
     if constexpr (DT == LQER_F32) {
 #pragma unroll
@@ -677,11 +841,23 @@ __global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
 #endif
 }
 
+template <int DT, bool LOWRANK, int BOUT, bool STAGED = false, int MT = 4, bool WTWOS = false, bool DEFER = false, bool WMF = false>
+__global__ __launch_bounds__(512) void k_lqer_gemm(GemmArgs g) {
+  // the deferred kernel with the direct side path and the table-free expand on the bf16 main loop: the k split
+  constexpr bool KSPLIT = DEFER && !STAGED && !WTWOS && !WMF && DT != LQER_F16X;
+  gemm_tile_body<DT, LOWRANK, BOUT, STAGED, MT, WTWOS, DEFER, WMF, KSPLIT>(g);
+}
+template <int DT>
+__global__ __launch_bounds__(512) void k_lqer_gemm_nks(GemmArgs g) {  // (LQER_TUNE_NO_KSPLIT)
+  gemm_tile_body<DT, true, 1, false, 4, false, true, false, false>(g);
+}
+
 // The instantiations of the tile kernel that exist - the variants the plan can ask for (gemm_plan.hip), per element type:
-template <int DT, bool LR, int BO, bool ST, int MT, bool WTWOS, bool DEFER, bool WMF>
+template <int DT, bool LR, int BO, bool ST, int MT, bool WTWOS, bool DEFER, bool WMF, bool NKS>
 constexpr bool tile_variant_exists() {
   constexpr bool nibbles = WTWOS || WMF;
   if (WTWOS && WMF) return false;
+  if (NKS && !(LR && BO == 1 && DEFER && !ST && MT == 4 && !nibbles && DT != LQER_F16X)) return false;  // the pin against the k split: where the k split exists
   // integer / minifloat nibbles, minifloat B_out: 128-row tiles, and no fp16 main loop beside them (the plan refuses)
   if ((nibbles || BO == 3) && (MT != 4 || DT == LQER_F16X)) return false;
   if (!LR) return BO == 0 && !ST && !DEFER;  // no side path: nothing of it to choose
@@ -694,10 +870,12 @@ constexpr bool tile_variant_exists() {
 template <int DT, int I>
 static bool run_tile(int key, const GemmPlan& p, const GemmArgs& g, hipStream_t st, int& rc) {
   constexpr bool LR = I & 1, ST = I & 2, WTWOS = I & 8, DEFER = I & 16, WMF = I & 32;
-  constexpr int MT = I & 4 ? 2 : 4, BO = I >> 6;
-  if constexpr (tile_variant_exists<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>()) {
+  constexpr bool NKS = I & 256;
+  constexpr int MT = I & 4 ? 2 : 4, BO = (I >> 6) & 3;
+  if constexpr (tile_variant_exists<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF, NKS>()) {
     if (key == I) {
-      rc = launch_k<k_lqer_gemm<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>>("lqer_gemm", p.grid, 512, gemm_lds_bytes(MT), st, g);
+      if constexpr (NKS) rc = launch_k<k_lqer_gemm_nks<DT>>("lqer_gemm", p.grid, 512, gemm_lds_bytes(MT), st, g);
+      else rc = launch_k<k_lqer_gemm<DT, LR, BO, ST, MT, WTWOS, DEFER, WMF>>("lqer_gemm", p.grid, 512, gemm_lds_bytes(MT), st, g);
       return true;
     }
   }
@@ -707,7 +885,8 @@ static bool run_tile(int key, const GemmPlan& p, const GemmArgs& g, hipStream_t 
 // the plan's variant -> the instantiation
 template <int DT, int... I>
 static int launch_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st, std::integer_sequence<int, I...>) {
-  const int key = p.lowrank | p.staged << 1 | (p.tile_rows == 64) << 2 | p.w_twos << 3 | p.defer << 4 | p.w_mf << 5 | p.bout << 6;
+  const int key = p.lowrank | p.staged << 1 | (p.tile_rows == 64) << 2 | p.w_twos << 3 | p.defer << 4 | p.w_mf << 5 | p.bout << 6 |
+                  (p.defer && !p.staged && !p.f16x && !p.ksplit) << 8;  // (bit 8: the k split exists for the variant and is pinned off)
   int rc;
   if ((run_tile<DT, I>(key, p, g, st, rc) || ...)) return rc;
   set_error("linear_gemm: the plan asks for a tile kernel variant that does not exist (%#x)", key);
@@ -715,7 +894,7 @@ static int launch_tile(const GemmPlan& p, const GemmArgs& g, hipStream_t st, std
 }
 
 int tile128_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {
-  constexpr std::make_integer_sequence<int, 4 << 6> variants{};
+  constexpr std::make_integer_sequence<int, 8 << 6> variants{};
   return with_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value;
     if constexpr (DT == LQER_F16)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """In-kernel clock of the GEMM main loop: a -DLQER_CLOCKPROBE build stamps s_memtime (shader cycles) and
 s_memrealtime (100 MHz) around the loop of every wave.  Runs >= 2 s of back-to-back launches first (DVFS settles),
-then reports cycles per k-step, the sustained clock and the launch's timeline.  usage: clock_probe.py lib_CLOCKPROBE.so [K [rank]]"""
+then reports cycles per k-step, the sustained clock and the launch's timeline.  usage: clock_probe.py lib_CLOCKPROBE.so [K [rank [tuning]]]"""
 import ctypes as C, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +17,7 @@ assert L.lqer_debug_set_stamp_buffer(buf.data_ptr()) == 0
 from tools._operands import real_operands  # (real bit patterns: random image bytes give random block exponents -> inf / NaN)
 op = real_operands(M, K, N, r)
 desc, xq, wp, xaq, bt, y = op["desc"], op["xq"], op["w"], op["xaq"], op["b_t"], op["y"]
+if len(sys.argv) > 4: desc.tuning = int(sys.argv[4], 0)  # LQER_TUNE_* pin of the kernel variant
 def launch():
     assert L.lqer_linear_gemm(C.byref(desc), xq.data_ptr(), M, wp.data_ptr(), xaq.data_ptr(), bt.data_ptr(), 1, None, y.data_ptr(), 1, N, None, 0, None) == 0
 t0 = time.time()
