@@ -670,7 +670,8 @@ def test_gpu_approximator_reconstruction_error(ops, with_scale, w_block):
 def test_large_m_tile_kernel_vs_oracle(ops, cfg, K, N):
     """M = 4096, N = 8192 (16 x 32 tiles of 256 x 256: the large-M kernel of gemm_w4a8_m256.hip) against the oracle:
     MXINT blocks of 16, the INT configuration (per-token B_out blocks: row-block maxima from the pre-pass) and a bias;
-    K = 320 / 384 / 64 give 5, 6 and 1 k-steps (ring wrap-around and the shortest pipeline)."""
+    K = 320 / 384 / 64 give 5, 6 and 1 k-steps (ring wrap-around and the shortest pipeline).  (The INT case takes the int8 MFMA kernel,
+    256-row tiles; the INT template on k_lqer_gemm_m256 is case 8 of tests/test_gpu_gemm256_exact.py.)"""
     import lqer_amd
     from bench import INT_Q, MXINT_Q, OPT_Q, make_case
 
@@ -687,15 +688,27 @@ def test_large_m_tile_kernel_vs_oracle(ops, cfg, K, N):
     mod.load_state_dict(sd)
     mod = mod.to(DEV).half()
     xin = x.half()
-    y = mod(xin.to(DEV)).float().cpu()
+    xd = xin.to(DEV)
+    yd = mod(xd).clone()
+    y = yd.float().cpu()
     ref = O.lqer_linear_forward(xin.float(), W.half().float(), b.half().float() if bias else None, A.half().float(),
                                 B.half().float(), qc)
     err = (y - ref).norm() / ref.norm()
     assert err <= 1e-3, float(err)
-    # rows are independent: the 128-row kernel (M = 300: one round of either tile size, the small tiles are chosen) must
-    # give the same bits for the same rows
-    y2 = mod(xin[:300].to(DEV)).float().cpu()
-    assert torch.equal(y2, y[:300])
+    # rows are independent: the same module on slices of 256 rows (one round of either tile size: never the 256-row kernel) must give
+    # the same bits for ALL 4096 rows
+    import ctypes as C
+
+    from lqer_amd import _lib
+
+    route = lambda m: (_lib.lib().lqer_gemm_route(C.byref(mod._desc()), m, _lib.F16), _lib.lib().lqer_gemm_tile_rows(C.byref(mod._desc()), m, _lib.F16))
+    full = route(M)
+    mod.tuning = _lib.TUNE_TILE_ROWS_128  # (the slices: the tile height the golden files pin, not the 64 rows the plan would pick)
+    if cfg != "int":  # (per-token activations beside weight blocks of 128 take the int8 MFMA kernel at both token counts: its tiles against its tiles)
+        assert full == (_lib.ROUTE_TILE256, 256) and route(256) == (_lib.ROUTE_TILE128, 128)
+    y2 = torch.cat([mod(xd[s:s + 256]) for s in range(0, M, 256)])
+    print(f"large-M {cfg} K{K} N{N}: route, rows {full} / slices {route(256)}, differing {int((y2 != yd).sum())}")
+    assert torch.equal(y2, yd)
 
 
 @pytest.mark.parametrize("dtype,tol,native", [(torch.float16, 1e-3, True), (torch.float16, 1e-3, False), (torch.bfloat16, 5e-3, True),
