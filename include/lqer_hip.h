@@ -410,6 +410,57 @@ int lqer_linear_forward_group(const lqer_group_member_t* members, int n_members,
                               int64_t ldx, const void* a_t_cat, int a_limbs, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ---- compact weight image: block_fp weights of 2 and 3 bits at their own width -----------------------------------------------
+ * The standard image spends 4.5 bits per weight whatever w_fmt.width is.  For w_fmt.kind = LQER_Q_MXINT with width 2 or 3 there is a
+ * second, opt-in image on the same panel grid (panel (n/16, k/64), padded to LQER_N_ALIGN / LQER_K_ALIGN, the panels of a 16-row band
+ * contiguous along k).  A compact panel takes 128 * width + 16 * E bytes:
+ *   [16 rows][4 q]  code dwords                                            offset 0
+ *   [16 rows][2]    sign dwords - width 3 only                             offset 256
+ *   [16 rows][E]    exponent bytes, biased as in the standard image        offset 128 * width
+ * E = 64 / block for blocks of 16 or 32 k; 1 for one block per row (block <= 0 or >= K) and for blocks that are a multiple of 64 k; 4
+ * (one byte per 16 k, the standard image's repetition) for any other block.  2-D tiles keep their per-row repetition.
+ * Code dword (row, q) holds what one lane of the decode-size kernels multiplies per panel: the row's 8 k of chunk q (k 8q .. 8q+7 of
+ * the panel) and of chunk q + 4.  Its byte j carries four 2-bit fields t = 0..3: k = j and k = 4 + j of chunk q, then of chunk q + 4.
+ *   width 2: field = sign << 1 | magnitude;
+ *   width 3: field = the 2-bit magnitude; the signs lie in sign dword (row, q >> 1): bit 4 (q & 1) + t of byte j.
+ * The sign bit is kept as the nibble has it, also beside a zero magnitude.  W2 in blocks of 16: 320 B per panel (0.56 of 576), W2 /
+ * 32: 288, W3 / 32: 416, W3 / 16: 448, W3 / 128: 400.
+ * lqer_weight_narrow converts the standard image of such a weight (as lqer_pack_weight_mxint[_2d] wrote it; the quantizer is not
+ * restated), lqer_weight_widen converts back: over the whole padded image widen(narrow(img)) == img byte for byte.  (A 16-k segment
+ * that starts at or past K carries the packer's padding byte 127 - (width - 1), whatever block it lies in; the compact image does not
+ * store it where its byte spans live k as well - widen writes it back from K.)  The _host functions do the same on host buffers with
+ * no HIP call; lqer_weight_narrow_host returns LQER_E_INVALID for bytes that are not such an image.  Images are 16-byte aligned.
+ * lqer_weight_narrow_bytes: bytes of the compact image; 0 for a format that is not served (widths 4..8, integer, minifloat).
+ *
+ * lqer_linear_forward_narrow is lqer_linear_forward with w_packed replaced by the compact image, lqer_linear_gemm_narrow is
+ * lqer_linear_gemm_ld likewise.  Where the weight-streaming kernels run - LQER_ROUTE_SMALLM, and the one-launch decode route of up to
+ * 8 tokens - they read the compact image directly: the same panels on the same waves in the same order, so the same bits as with the
+ * standard image.  Every other route (M > 64, B_out formats that send decode sizes to the tile kernel) first widens the image into
+ * caller memory - the workspace behind lqer_linear_sizes(...).workspace rounded up to 256 (lqer_linear_forward_narrow_workspace_bytes
+ * counts it where m_max can reach such a route), or widen_scratch (>= lqer_linear_sizes(...).w_packed bytes, 16-byte aligned; unused
+ * and may be NULL on the direct routes) - and runs the existing kernel on that copy.  LQER_E_UNSUPPORTED, with the reason in
+ * lqer_last_error(): LQER_Q_MXINT_I8 descriptors, pass-through bf16 / fp32 activations (one image copy per limb), weights that are
+ * not block_fp of width 2 or 3, descriptors with LQER_TUNE_W_EXP_TABLE.  lqer_linear_forward_group takes standard images only.
+ * lqer_weight_narrow_route says what a call does (host only, no HIP call): LQER_NARROW_DIRECT, LQER_NARROW_DIRECT_ONE_LAUNCH (the
+ * one-launch decode route, given a 16-byte aligned x and a shape its kernel serves) or LQER_NARROW_WIDEN; < 0: the refusal. */
+#define LQER_NARROW_DIRECT 1
+#define LQER_NARROW_DIRECT_ONE_LAUNCH 2
+#define LQER_NARROW_WIDEN 3
+size_t lqer_weight_narrow_bytes(int64_t N, int64_t K, const lqer_qfmt_t* w_fmt);
+int lqer_weight_narrow(const void* w_packed, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_narrow, void* stream);
+int lqer_weight_widen(const void* w_narrow, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_packed, void* stream);
+int lqer_weight_narrow_host(const void* w_packed, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_narrow);
+int lqer_weight_widen_host(const void* w_narrow, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_packed);
+int lqer_weight_narrow_route(const lqer_linear_desc_t* desc, int64_t M, int dtype, int64_t ldx, int a_limbs, int b_limbs);
+size_t lqer_linear_forward_narrow_workspace_bytes(const lqer_linear_desc_t* desc, int64_t m_max);
+int lqer_linear_forward_narrow(const lqer_linear_desc_t* desc, const void* x, int dtype, int64_t M, int64_t ldx,
+                               const void* w_narrow, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                               const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
+int lqer_linear_gemm_narrow(const lqer_linear_desc_t* desc, const void* xq_bf16, int64_t M, const void* w_narrow,
+                            const void* xaq_bf16, int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y,
+                            int dtype, int64_t ldy, void* scratch, size_t scratch_bytes, void* widen_scratch, size_t widen_bytes,
+                            void* stream);
+
 /* ---- pass-through activations ("A16": x_quantizer = passthrough, reference quantizers/passthrough.py:1, every
  * experiments/configs/template/ *-int.toml) ------------------------------------------------------------------
  * The kernels multiply exact bf16 operands.  A pass-through activation is therefore carried as the sum of

@@ -17,6 +17,7 @@ F32, F16, BF16 = 0, 1, 2
 Q_PASSTHROUGH, Q_MXINT, Q_PASSTHROUGH_F16, Q_MXINT_I8, Q_INT, Q_MINIFLOAT = 0, 1, 2, 3, 4, 5
 K_ALIGN, M_ALIGN, N_ALIGN, R_ALIGN = 64, 256, 256, 16
 ROUTE_SMALLM, ROUTE_TILE128, ROUTE_TILE256, ROUTE_I8 = 0, 1, 2, 3
+NARROW_DIRECT, NARROW_DIRECT_ONE_LAUNCH, NARROW_WIDEN = 1, 2, 3  # lqer_weight_narrow_route: what a call with the compact weight image does
 TUNE_TILE_ROWS_128, TUNE_TILE_ROWS_64, TUNE_DECODE_NO_POLL = 0x1, 0x2, 0x10000
 TUNE_I8_ROWS_128, TUNE_I8_ROWS_256, TUNE_AMAX_ATOMIC, TUNE_AMAX_PARTS = 0x4, 0x8, 0x40000, 0x80000
 TUNE_ACT16_SPLIT, TUNE_ACT16_FUSED = 0x800000, 0x1000000  # block-16 MXINT activation side: two launches / the one-launch kernel at every M
@@ -99,6 +100,17 @@ SIGNATURES = {
     "lqer_tile_partials": (_i, [_dp, _i64, _i]),
     "lqer_group_workspace_bytes": (_sz, [_i64, _i64]),
     "lqer_linear_forward_group": (_i, [C.POINTER(GroupMember), _i, _vp, _i, _i64, _i64, _vp, _i, _vp, _sz, _vp]),
+    # the compact image of 2- / 3-bit block_fp weights (csrc/w_narrow.h): conversions on the device and on host buffers, the forward and
+    # the GEMM that are handed it, and what such a call does (NARROW_*)
+    "lqer_weight_narrow_bytes": (_sz, [_i64, _i64, _qp]),
+    "lqer_weight_narrow": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),
+    "lqer_weight_widen": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),
+    "lqer_weight_narrow_host": (_i, [_vp, _i64, _i64, _qp, _vp]),
+    "lqer_weight_widen_host": (_i, [_vp, _i64, _i64, _qp, _vp]),
+    "lqer_weight_narrow_route": (_i, [_dp, _i64, _i, _i64, _i, _i]),
+    "lqer_linear_forward_narrow_workspace_bytes": (_sz, [_dp, _i64]),
+    "lqer_linear_forward_narrow": (_i, [_dp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "lqer_linear_gemm_narrow": (_i, [_dp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _vp, _vp, _i, _i64, _vp, _sz, _vp, _sz, _vp]),
     "lqer_gemm_route": (_i, [_dp, _i64, _i]),
     "lqer_gemm_tile_rows": (_i, [_dp, _i64, _i]),
     "lqer_f16_prepare": (_i, [_vp, _i64, _i64, _vp, _i, _i64, _vp, _vp, _vp]),

@@ -4,7 +4,8 @@ weight panels with their block exponents (0.5625 B per weight), the exact bf16 l
 bias - are written once and attached at load time, so a load touches 0.28x the bytes of the fp16 checkpoint and the
 dense weight / A / B tensors need not be materialised on the GPU at all.
 
-File = one safetensors file: tensors "<module path>.<w|a_t|b_t|bias_q|header>" (uint8 / int32) for every quantized
+File = one safetensors file: tensors "<module path>.<w|w_narrow|a_t|b_t|bias_q|header>" (uint8 / int32; a module with
+weight_image = "narrow" stores the compact image of its 2- / 3-bit weight as w_narrow in place of w) for every quantized
 Linear, every other parameter and buffer of the model under its state-dict key, and a metadata header
 {"format": "lqer_amd.packed", "version": "1"}.  Each module header carries (version, in, out, rank, limb counts, bias
 flag, the five quantizer settings); load_packed refuses a file whose header disagrees with the module it is loaded into.
@@ -20,7 +21,7 @@ from .linear import _LinearBase
 
 FORMAT = "lqer_amd.packed"
 VERSION = "1"
-_FIELDS = ("w", "a_t", "b_t", "bias_q", "header")
+_FIELDS = ("w", "w_narrow", "a_t", "b_t", "bias_q", "header")  # (w_narrow: a narrow module's compact image, in place of w)
 
 
 def _quantized_modules(model: nn.Module) -> Dict[str, _LinearBase]:

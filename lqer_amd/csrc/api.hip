@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "gemm_plan.h"
+#include "w_narrow.h"
 
 namespace lqer {
 
@@ -209,6 +210,41 @@ static int xa_limbs(const lqer_linear_desc_t* d) {
   if (d->a_out_fmt.kind != LQER_Q_PASSTHROUGH) return 1;
   return d->a_out_fmt.width <= 16 ? 2 : 3;
 }
+// The compact weight image (w_narrow.h) serves block_fp weights of width 2 and 3 whose image exists once: E > 0 = its exponent bytes
+// per row, 0 = not served (widths 4..8, integer and minifloat weights)
+static int narrow_exps(const lqer_qfmt_t* f, int64_t K) {
+  return (f && f->kind == LQER_Q_MXINT) ? wn_exps_per_row(f->width, f->block, K) : 0;
+}
+static size_t narrow_bytes(int64_t N, int64_t K, const lqer_qfmt_t* f) {
+  const int E = narrow_exps(f, K);
+  if (!E || N <= 0 || K <= 0) return 0;
+  return (size_t)(lqer_padded_n(N) / LQER_PANEL_ROWS) * (lqer_padded_k(K) / 64) * wn_panel_bytes(f->width, E);
+}
+// a descriptor whose forward can be handed the compact image; fills GemmArgs::w_narrow
+static int narrow_args(const lqer_linear_desc_t* d, GemmArgs& g) {
+  const int E = narrow_exps(&d->w_fmt, d->in_features);
+  if (!E) {
+    set_error("compact weight image: block_fp weights of width 2 or 3 only (w_quantizer kind %d width %d: the standard image)",
+              d->w_fmt.kind, d->w_fmt.width);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (x_is_i8(d)) {
+    set_error("compact weight image: not on the int8 route (LQER_Q_MXINT_I8 reads an int8 image of its own): use LQER_Q_MXINT");
+    return LQER_E_UNSUPPORTED;
+  }
+  if (act_limbs(d) != 1) {
+    set_error("compact weight image: pass-through bf16 / fp32 activations read one copy of the image per limb (%d): the standard image",
+              act_limbs(d));
+    return LQER_E_UNSUPPORTED;
+  }
+  if (d->tuning & LQER_TUNE_W_EXP_TABLE) {
+    set_error("compact weight image: a weight that needs LQER_TUNE_W_EXP_TABLE (an exponent byte above 245) keeps the standard image");
+    return LQER_E_UNSUPPORTED;
+  }
+  g.w_narrow = d->w_fmt.width << 8 | E;
+  return LQER_OK;
+}
+
 static bool passthrough_width_ok(const lqer_qfmt_t& f, const char* name) {
   if (f.kind == LQER_Q_PASSTHROUGH && (f.width < 1 || f.width > 24)) {
     set_error("%s: a passthrough format must say how many significand bits to carry in `width` (8 = bf16, 11 = fp16, "
@@ -534,7 +570,7 @@ struct Planned {
   GemmArgs g;
   GemmPlan p;
 };
-static Planned plan_for(const lqer_linear_desc_t* d, int64_t M, int dtype, int b_limbs, bool for_launch = true);
+static Planned plan_for(const lqer_linear_desc_t* d, int64_t M, int dtype, int b_limbs, bool for_launch = true, bool narrow = false);
 static int plan_route(const Planned& pl);
 // a call in front of the GEMM call can zero the pre-pass cells on its behalf (GemmPlan::prep_zero_bytes at the head of gemm_scratch): the
 // int8 route's one-launch activation kernel
@@ -721,11 +757,13 @@ static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, Ge
 }
 
 // for_launch = false (the route queries): no HIP call - the CU count, which only the travel of the row maxima depends on, is not asked
-static Planned plan_for(const lqer_linear_desc_t* d, int64_t M, int dtype, int b_limbs, bool for_launch) {
+// narrow: w_packed is the compact image of a 2- / 3-bit weight (the _narrow entry points)
+static Planned plan_for(const lqer_linear_desc_t* d, int64_t M, int dtype, int b_limbs, bool for_launch, bool narrow) {
   Planned pl;
   memset(&pl.g, 0, sizeof(pl.g));
   pl.rc = gemm_shape_args(d, M, dtype, pl.g);
   pl.g.b_limbs = b_limbs;
+  if (pl.rc == LQER_OK && narrow) pl.rc = narrow_args(d, pl.g);
   if (pl.rc == LQER_OK) {
     // (the device's CUs decide one thing: whether the int8 kernel exchanges the row maxima of a wide-block B_out itself)
     const bool asks_cus = for_launch && x_is_i8(d) && d->rank > 0 && d->b_out_fmt.kind == LQER_Q_MXINT && d->b_out_fmt.block != 16;
@@ -764,7 +802,7 @@ int lqer_gemm_tile_rows(const lqer_linear_desc_t* d, int64_t M, int dtype) {
 
 static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                             int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
-                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl);
+                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl, bool narrow = false);
 
 int lqer_linear_gemm_ld(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                         int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
@@ -788,7 +826,7 @@ int lqer_linear_gemm_prepared(const lqer_linear_desc_t* d, const void* xq, int64
 
 static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                             int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
-                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl) {
+                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl, bool narrow) {
   if (!d || !xq || !w_packed || !y || M < 0 || ldy < d->out_features) {
     set_error("linear_gemm: bad argument");
     return LQER_E_INVALID;
@@ -804,7 +842,7 @@ static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t
     return LQER_E_INVALID;
   }
   Planned own;
-  if (!pl) own = plan_for(d, M, dtype, b_limbs), pl = &own;
+  if (!pl) own = plan_for(d, M, dtype, b_limbs, true, narrow), pl = &own;
   if (pl->rc) {
     set_error("%s", pl->p.msg);
     return pl->rc;
@@ -841,10 +879,35 @@ static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t
   return gemm_launch(pl->p, g, dtype, scratch, scratch_bytes, amax_zeroed, (hipStream_t)stream);
 }
 
+// bytes of the standard image of d's weight (one copy: what a compact image widens into)
+static size_t std_image_bytes(const lqer_linear_desc_t* d) {
+  return (size_t)(lqer_padded_n(d->out_features) / LQER_PANEL_ROWS) * (lqer_padded_k(d->in_features) / 64) * LQER_PANEL_BYTES;
+}
+// one-launch decode route (decode1.hip): the conditions lqer_linear_forward checks besides lqer_decode_partials and x's own alignment
+static bool decode1_call_ok(const lqer_linear_desc_t* d, int dtype, int64_t M, int64_t ldx, int a_limbs, int b_limbs) {
+  const int esz = dtype == LQER_F32 ? 4 : 2;
+  return M <= 8 && a_limbs == 1 && !x_is_f16(d) && (ldx * esz) % 16 == 0 && b_limbs >= 1 && b_limbs <= 3;
+}
+
+static int linear_forward_impl(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
+                               const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                               const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                               void* stream, bool narrow);
+
 int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
                         const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
                         const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
                         void* stream) {
+  return linear_forward_impl(d, x, dtype, M, ldx, w_packed, a_t, b_t, a_limbs, b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream,
+                             false);
+}
+
+// narrow: w_packed is the compact image (lqer_linear_forward_narrow).  Routes whose kernel reads it directly go on as below with the
+// plan's w_img; every other route widens it into the workspace behind the standard carving and goes on as the standard image's call.
+static int linear_forward_impl(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
+                               const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                               const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                               void* stream, bool narrow) {
   if (!d) {
     set_error("linear_forward: null descriptor");
     return LQER_E_INVALID;
@@ -855,7 +918,24 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
   if (rc) return rc;
   HT_MARK(0);
   // the one plan of this forward (its refusals are reported where the GEMM call reports them)
-  Planned pl = plan_for(d, M, dtype, b_limbs);
+  Planned pl = plan_for(d, M, dtype, b_limbs, true, narrow);
+  if (narrow) {
+    if (plan_route(pl) < 0) return pl.rc ? pl.rc : pl.p.err;
+    if (pl.p.w_img < 0) {
+      const size_t at = align_up(sz.workspace, 256);
+      if (!workspace || workspace_bytes < at + std_image_bytes(d)) {
+        set_error("linear_forward_narrow: workspace %zu B < %zu B needed for M=%lld (the widened weight image included)", workspace_bytes,
+                  at + std_image_bytes(d), (long long)M);
+        return LQER_E_WORKSPACE;
+      }
+      if (M == 0) return LQER_OK;
+      void* wide = (unsigned char*)workspace + at;
+      rc = weight_widen_dispatch(w_packed, d->out_features, d->in_features, d->w_fmt.width, pl.g.w_narrow & 0xff, wide, (hipStream_t)stream);
+      if (rc) return rc;
+      w_packed = wide, narrow = false;
+      pl = plan_for(d, M, dtype, b_limbs);
+    }
+  }
   lqer_linear_desc_t plain;
   if (x_is_i8(d) && plan_route(pl) != LQER_ROUTE_I8) {
     // token counts the int8 tile kernel does not serve run the bf16 kernels on the sign-magnitude image (same buffers): a second
@@ -916,7 +996,7 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
     rc = lqer_quantize_act_xa(d, x, dtype, M, ldx, a_t, a_limbs, xq, nullptr, xa_scratch, nscr, stream);
     if (rc) return rc;
     return linear_gemm_impl(d, xq, M, w_packed, nullptr, lqer_padded_r(d->rank) * xa_limbs(d), b_t, b_limbs, bias_q, y, dtype, ldy, xa_scratch,
-                            nscr, stream, false, &pl);
+                            nscr, stream, false, &pl, narrow);
   }
   // (a pre-pass on atomicMax cells behind the one-launch int8 activation kernel: that kernel zeroes the cells - the two calls share the
   // scratch, whose size is the larger of their needs - instead of a memset launch between them)
@@ -926,7 +1006,111 @@ int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, i
   rc = quantize_act_xa_impl(d, x, dtype, M, ldx, a_t, a_limbs, xq, xaq, xa_scratch, side_bytes, stream, &zr);
   if (rc) return rc;
   return linear_gemm_impl(d, xq, M, w_packed, d->rank > 0 ? xaq : nullptr, lqer_padded_r(d->rank) * xa_limbs(d), b_t, b_limbs, bias_q, y, dtype,
-                          ldy, xa_scratch, gemm_bytes, stream, zr.done, &pl);
+                          ldy, xa_scratch, gemm_bytes, stream, zr.done, &pl, narrow);
+}
+
+// ---- the compact image of 2- / 3-bit block_fp weights (include/lqer_hip.h "compact weight image") -----------------------------------
+size_t lqer_weight_narrow_bytes(int64_t N, int64_t K, const lqer_qfmt_t* w_fmt) { return narrow_bytes(N, K, w_fmt); }
+
+static int narrow_conv_check(const char* who, const void* a, const void* b, int64_t N, int64_t K, const lqer_qfmt_t* f) {
+  if (!a || !b || !f || N <= 0 || K <= 0 || ((uintptr_t)a & 15) || ((uintptr_t)b & 15)) {
+    set_error("%s: bad argument (null pointer, non-positive size, or an image that is not 16-byte aligned)", who);
+    return LQER_E_INVALID;
+  }
+  if (!narrow_exps(f, K)) {
+    set_error("%s: the compact image holds block_fp weights of width 2 or 3 (kind %d width %d)", who, f->kind, f->width);
+    return LQER_E_UNSUPPORTED;
+  }
+  return LQER_OK;
+}
+
+int lqer_weight_narrow(const void* w_packed, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_narrow, void* stream) {
+  const int rc = narrow_conv_check("weight_narrow", w_packed, w_narrow, N, K, w_fmt);
+  return rc ? rc : weight_narrow_dispatch(w_packed, N, K, w_fmt->width, narrow_exps(w_fmt, K), w_narrow, (hipStream_t)stream);
+}
+
+int lqer_weight_widen(const void* w_narrow, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_packed, void* stream) {
+  const int rc = narrow_conv_check("weight_widen", w_narrow, w_packed, N, K, w_fmt);
+  return rc ? rc : weight_widen_dispatch(w_narrow, N, K, w_fmt->width, narrow_exps(w_fmt, K), w_packed, (hipStream_t)stream);
+}
+
+int lqer_weight_narrow_host(const void* w_packed, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_narrow) {
+  const int rc = narrow_conv_check("weight_narrow_host", w_packed, w_narrow, N, K, w_fmt);
+  if (rc) return rc;
+  if (!weight_narrow_host((const uint8_t*)w_packed, N, K, w_fmt->width, narrow_exps(w_fmt, K), (uint8_t*)w_narrow)) {
+    set_error("weight_narrow_host: not the standard image of a width-%d weight in blocks of %d (a magnitude bit above bit %d, or "
+              "exponent bytes of one block that differ): widening would not give it back", w_fmt->width, w_fmt->block, w_fmt->width - 2);
+    return LQER_E_INVALID;
+  }
+  return LQER_OK;
+}
+
+int lqer_weight_widen_host(const void* w_narrow, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_packed) {
+  const int rc = narrow_conv_check("weight_widen_host", w_narrow, w_packed, N, K, w_fmt);
+  if (rc) return rc;
+  weight_widen_host((const uint8_t*)w_narrow, N, K, w_fmt->width, narrow_exps(w_fmt, K), (uint8_t*)w_packed);
+  return LQER_OK;
+}
+
+int lqer_weight_narrow_route(const lqer_linear_desc_t* d, int64_t M, int dtype, int64_t ldx, int a_limbs, int b_limbs) {
+  if (!d || M < 0) {
+    set_error("weight_narrow_route: bad argument");
+    return LQER_E_INVALID;
+  }
+  const Planned pl = plan_for(d, M, dtype, b_limbs, false, true);
+  const int route = plan_route(pl);
+  if (route < 0) return route;
+  if (pl.p.w_img < 0) return LQER_NARROW_WIDEN;
+  const bool one = decode_partials_ok(d, M) && decode1_call_ok(d, dtype, M, ldx, a_limbs, b_limbs) && d->in_features % 16 == 0;
+  return one ? LQER_NARROW_DIRECT_ONE_LAUNCH : LQER_NARROW_DIRECT;
+}
+
+// does a token count up to m_max reach a route that widens?  Decode sizes share one answer (the small-M route does not depend on M
+// below 65), every larger count takes a tile kernel.
+static bool narrow_may_widen(const lqer_linear_desc_t* d, int64_t m_max) {
+  if (m_max > SM_MAX_M) return true;
+  const Planned pl = plan_for(d, m_max > 0 ? m_max : 1, LQER_F16, 0, false, true);
+  return pl.rc == LQER_OK && !pl.p.err && pl.p.w_img < 0;
+}
+
+size_t lqer_linear_forward_narrow_workspace_bytes(const lqer_linear_desc_t* d, int64_t m_max) {
+  lqer_linear_sizes_t sz;
+  if (!d || lqer_linear_sizes(d, m_max, &sz)) return 0;
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  if (narrow_args(d, g)) return 0;
+  return narrow_may_widen(d, m_max) ? align_up(sz.workspace, 256) + std_image_bytes(d) : sz.workspace;
+}
+
+int lqer_linear_forward_narrow(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx, const void* w_narrow,
+                               const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y, int64_t ldy,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  return linear_forward_impl(d, x, dtype, M, ldx, w_narrow, a_t, b_t, a_limbs, b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream,
+                             true);
+}
+
+int lqer_linear_gemm_narrow(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_narrow, const void* xaq, int64_t xaq_ld,
+                            const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy, void* scratch,
+                            size_t scratch_bytes, void* widen_scratch, size_t widen_bytes, void* stream) {
+  if (!d || !w_narrow || M < 0) {
+    set_error("linear_gemm_narrow: bad argument");
+    return LQER_E_INVALID;
+  }
+  const Planned pl = plan_for(d, M, dtype, b_limbs, true, true);
+  if (plan_route(pl) < 0) return pl.rc ? pl.rc : pl.p.err;
+  if (pl.p.w_img >= 0)
+    return linear_gemm_impl(d, xq, M, w_narrow, xaq, xaq_ld, b_t, b_limbs, bias_q, y, dtype, ldy, scratch, scratch_bytes, stream, false, &pl, true);
+  if (!widen_scratch || widen_bytes < std_image_bytes(d) || ((uintptr_t)widen_scratch & 15)) {
+    set_error("linear_gemm_narrow: M=%lld takes a kernel that reads standard panels: widen_scratch %zu B < %zu B (16-byte aligned)",
+              (long long)M, widen_bytes, std_image_bytes(d));
+    return LQER_E_WORKSPACE;
+  }
+  if (M == 0) return LQER_OK;
+  const int rc = weight_widen_dispatch(w_narrow, d->out_features, d->in_features, d->w_fmt.width, pl.g.w_narrow & 0xff, widen_scratch,
+                                       (hipStream_t)stream);
+  if (rc) return rc;
+  return linear_gemm_impl(d, xq, M, widen_scratch, xaq, xaq_ld, b_t, b_limbs, bias_q, y, dtype, ldy, scratch, scratch_bytes, stream, false,
+                          nullptr);
 }
 
 size_t lqer_group_workspace_bytes(int64_t K, int64_t rank_padded_sum) {

@@ -810,7 +810,8 @@ struct GemmArgs {
   int w_mbits;
   QP bout;
   int tiles_m, tiles_n;
-  int tiles_m_rows;     // (host-only, no kernel reads it; unused since GemmPlan::tile_rows carries the tile height - kept for the layout)
+  int w_narrow;         // wp is the compact image of a 2- / 3-bit weight (w_narrow.h): width << 8 | exponent bytes per row; 0: the standard
+                        // image.  Read by the plan and the small-M kernel's compact instantiations (the slot of the retired tiles_m_rows)
   float* bout_amax;     // [Mp][bout_nblk] row-block maxima of xAq @ B (B_out blocks other than 16), else null
   int bout_L, bout_nblk;
   int bout_nseg;        // > 0 (int8 route, one block per row): bout_amax holds [bout_nseg][Mp] column-segment partials (no atomics)
@@ -889,8 +890,17 @@ struct DecodeMember {  // one Linear of a one-launch decode forward (a group sha
   int64_t ldy;
   int N, Np, rp, b_limbs;
 };
+// (g.w_narrow != 0: a single Linear whose wp is the compact image - groups read standard images only)
 int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, const QP& qx, const bf16_t* a_t, int bout,
                      const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st);
+
+// pack.hip: standard image <-> compact image of a 2- / 3-bit block_fp weight (w_narrow.h), over the whole padded image; E = exponent
+// bytes per row of a compact panel.  The host twins run the same per-row functions in plain loops (no HIP call); narrow_host returns
+// false when the input is not the standard image of such a weight.
+int weight_narrow_dispatch(const void* w_packed, int64_t N, int64_t K, int width, int E, void* w_narrow, hipStream_t st);
+int weight_widen_dispatch(const void* w_narrow, int64_t N, int64_t K, int width, int E, void* w_packed, hipStream_t st);
+bool weight_narrow_host(const uint8_t* w_packed, int64_t N, int64_t K, int width, int E, uint8_t* w_narrow);
+void weight_widen_host(const uint8_t* w_narrow, int64_t N, int64_t K, int width, int E, uint8_t* w_packed);
 
 size_t qmatmul_workspace_bytes(int64_t batch, int64_t K, int64_t S2);  // matmul_q.hip
 size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t S2, bool x_pre, bool y_pre);

@@ -109,6 +109,7 @@ struct Args {
   int64_t ldx;
   int K;
   QP qx;
+  int w_exps;          // W != 0 (the compact image of a 2- / 3-bit weight, w_narrow.h): its exponent bytes per row (in the padding behind qx)
   const bf16_t* a_t;   // A^T bf16 image [rp_all][Kp] (one limb; the members' images concatenated along the rank)
   uint32_t* gran;      // granules [np][MAXM][rp_all] x {value, tag}
   uint32_t nonce;      // host part of the granule tag (a per-call counter); the kernel mixes in its dispatch id and queue
@@ -127,12 +128,11 @@ __device__ __forceinline__ int img_off(int r, int c, int pitch) { return r * pit
 // GROUP: more than one Linear in the launch (lqer_linear_forward_group) - a single Linear's instantiation reads its one table
 // entry from static argument offsets only (the scan of the table's other entries costs its first weight request ~0.8 us:
 // measured, rocprofv3 kernel durations 9.0 vs 8.1 us at M = 1).
-template <int DT, int BOUT, bool GROUP>
-// (two workgroups per CU: the grid is the N/16 consumers PLUS the producers - 272 for N = 4096 -, with one workgroup per CU the
-// last 16 would wait for a whole round; 4 waves per SIMD caps the kernel at 128 registers.  Wider launches - a group of
-// Linears, or M >= 6 where the x image leaves room for one workgroup per CU - give every consumer up to four column blocks, so
-// that the whole launch is resident at once)
-__global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1> a) {
+// W: 0 - standard panels; 2, 3 - the single Linear's weight is the compact image of that width (w_narrow.h): the weight stream's
+// loads, its descriptors' extents and the expand differ, nothing else.
+// (the body of both kernels below, inlined: the standard image's kernel keeps its name and its three template arguments)
+template <int DT, int BOUT, bool GROUP, int W>
+__device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const auto& g = a;  // (the shared formats and shapes: M, Kp, aout, bout)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
   // the member's x A is gathered once; the launch then fits the chip in ONE round whatever N and the group size are)
   const int cb_first = (cb_all - m_cb0) * a.cpw;
   const int nb_here = m_nblk - cb_first < a.cpw ? m_nblk - cb_first : a.cpw;
-  const SmLane ln(lane);  // the lane's place in a packed panel (smallm_tile.h)
+  const SmLaneT<W> ln(lane, a.w_exps);  // the lane's place in a packed panel (smallm_tile.h)
   const int row = ln.row, q = ln.q;
   const int nk = Kp / 64;
   const bool lowrank = mb.bt != nullptr && rp > 0;
@@ -281,23 +281,28 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
   // weight panels through a buffer descriptor: a request past the end is dropped by the range check,
   // so no load sits under a branch and the compiler's vmcnt counts stay exact
   auto block_rsrc = [&](int cb) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(m_wp + (int64_t)cb * nk * LQER_PANEL_BYTES), 0, nk * LQER_PANEL_BYTES, 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(m_wp + (int64_t)cb * nk * ln.panel_bytes), 0, nk * ln.panel_bytes, 0x00020000);
   };
-  auto load_panel = [&](const auto& w_rsrc, int kt, SmPanel& p) {  // kt >= nk: zeros
+  auto load_panel = [&](const auto& w_rsrc, int kt, SmPanelT<W>& p) {  // kt >= nk: zeros
     // (the panel's base as the SCALAR offset - part of the range check on gfx9 -, the lane's place inside a panel as the one
     // vector offset: no per-panel address registers to keep alive across column blocks)
-    const int base = __builtin_amdgcn_readfirstlane(kt < nk ? kt * LQER_PANEL_BYTES : 0x7ffffff0);
+    const int base = __builtin_amdgcn_readfirstlane(kt < nk ? kt * ln.panel_bytes : 0x7ffffff0);
 #ifndef LQER_D1_WAUX
 #define LQER_D1_WAUX 2  // cache policy of the weight stream's loads: 0 default, 2 non-temporal (once-read bytes: a model walks 3.6 GB
                         // of packed weights per token - 9.4 -> 9.0 us per forward over 48 rotating weights, bench d1; a single resident
                         // weight re-read from the Infinity Cache is slower with it, 4.8 -> 5.5 us: not what a model does)
 #endif
-    p.cw = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, ln.codes_off, base, LQER_D1_WAUX));
+    if constexpr (W == 0) {
+      p.cw = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, ln.codes_off, base, LQER_D1_WAUX));
+    } else {  // (aligned dwords inside the panel: a panel past the end is dropped whole by the range check, as above)
+      p.cw = __builtin_amdgcn_raw_buffer_load_b32(w_rsrc, ln.codes_off, base, LQER_D1_WAUX);
+      if constexpr (W == 3) p.sg = __builtin_amdgcn_raw_buffer_load_b32(w_rsrc, ln.signs_off, base, LQER_D1_WAUX);
+    }
     p.ex = __builtin_amdgcn_raw_buffer_load_b32(w_rsrc, ln.exps_off, base, LQER_D1_WAUX);
   };
   // wave w takes panels w, w + 8, ...; two register buffers of 4 panels
   constexpr int UNR = 4;
-  SmPanel pa[UNR], pb[UNR];
+  SmPanelT<W> pa[UNR], pb[UNR];
   const int per_wave = (nk - wave + NW - 1) / NW;
   auto kt_of = [&](int i) { return wave + NW * i; };
   // this thread's first XB blocks of x are requested BEFORE the weight panels (loads complete in order: the small L2-hot
@@ -373,8 +378,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
   // travel under the combine and wave 0's epilogue (unconditional - past the workgroup's blocks the descriptor's range drops
   // them: no load under a branch)
   auto request_first_panels = [&](int jb) {  // of column block jb (past the workgroup's blocks: an empty range, no traffic)
-    const auto w_blk = __builtin_amdgcn_make_buffer_rsrc((void*)(m_wp + (int64_t)(cb_first + jb) * nk * LQER_PANEL_BYTES), 0,
-                                                         jb < nb_here ? nk * LQER_PANEL_BYTES : 0, 0x00020000);
+    const auto w_blk = __builtin_amdgcn_make_buffer_rsrc((void*)(m_wp + (int64_t)(cb_first + jb) * nk * ln.panel_bytes), 0,
+                                                         jb < nb_here ? nk * ln.panel_bytes : 0, 0x00020000);
 #pragma unroll
     for (int u = 0; u < UNR; ++u) load_panel(w_blk, kt_of(u), pa[u]);
   };
@@ -385,9 +390,9 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
     int lrow = l15;
     asm volatile("" : "+v"(lrow));  // (re-derived per block: kept alive from the top of the kernel it costs a spill)
     const int xrow = lrow < M ? lrow : 0;
-    auto compute_panel = [&](int kt, const SmPanel& p) {
+    auto compute_panel = [&](int kt, const SmPanelT<W>& p) {
       bf16x8 wb0, wb1;
-      sm_expand<false>(p, ln, wb0, wb1);
+      sm_expand<false, W>(p, ln, wb0, wb1);
       const int kc = kt < nk ? kt : 0;  // (past the end: zero weights, any finite activation chunk)
       const bf16x8 x0 = *(const bf16x8*)(xs + img_off(xrow, kc * 8 + q, xpitch));
       const bf16x8 x1 = *(const bf16x8*)(xs + img_off(xrow, kc * 8 + 4 + q, xpitch));
@@ -592,6 +597,20 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1>
   D1_STAMP(5);
 }
 
+// (two workgroups per CU: the grid is the N/16 consumers PLUS the producers - 272 for N = 4096 -, with one workgroup per CU the
+// last 16 would wait for a whole round; 4 waves per SIMD caps the kernel at 128 registers.  Wider launches - a group of
+// Linears, or M >= 6 where the x image leaves room for one workgroup per CU - give every consumer up to four column blocks, so
+// that the whole launch is resident at once)
+template <int DT, int BOUT, bool GROUP>
+__global__ __launch_bounds__(64 * NW, 4) void k_decode1(Args<GROUP ? MAXMEM : 1> a) {
+  decode1_body<DT, BOUT, GROUP, 0>(a);
+}
+// ... a single Linear whose weight is the compact image of W = 2 or 3 bits
+template <int DT, int BOUT, int W>
+__global__ __launch_bounds__(64 * NW, 4) void k_decode1_narrow(Args<1> a) {
+  decode1_body<DT, BOUT, false, W>(a);
+}
+
 static std::atomic<uint32_t> g_nonce{1};  // the call's granule tag: any value the granule area does not hold yet
 
 }  // namespace d1
@@ -616,6 +635,8 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
   timespec ht0; clock_gettime(CLOCK_MONOTONIC, &ht0);
 #endif
   if (g.M < 1 || g.M > d1::MAXM || nmem < 1 || nmem > d1::MAXMEM || bout > 1 || K % 16 != 0) return LQER_E_UNSUPPORTED;
+  const int w_img = g.w_narrow >> 8;  // the compact image of a 2- / 3-bit weight: a single Linear's launch only
+  if (w_img && (nmem != 1 || (w_img != 2 && w_img != 3))) return LQER_E_UNSUPPORTED;
   d1::Args<d1::MAXMEM> a;
   int rp_all = 0, blocks = 0;
   for (int i = 0; i < nmem; ++i) {
@@ -665,6 +686,7 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
   d1::Args<1> a1;  // the single Linear's compact block
   a1.mem[0] = a.mem[0];
   a1.M = a.M, a1.Kp = a.Kp, a1.aout = a.aout, a1.bout = a.bout, a1.nmem = 1, a1.rp_all = a.rp_all, a1.x = a.x, a1.ldx = a.ldx, a1.K = a.K,
+  a.w_exps = a1.w_exps = g.w_narrow & 0xff,
   a1.qx = a.qx, a1.a_t = a.a_t, a1.gran = a.gran, a1.nonce = a.nonce, a1.np = a.np, a1.spin = a.spin, a1.cpw = a.cpw;
 #ifdef LQER_HOST_TIMING  // diagnostic build: host nanoseconds before / inside the launch call, printed at exit
   struct HostT {
@@ -680,6 +702,12 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
     if (nmem > 1)
       return bout == 1 ? launch_k<d1::k_decode1<DT, 1, true>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a)
                        : launch_k<d1::k_decode1<DT, 0, true>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a);
+    if (w_img == 2)
+      return bout == 1 ? launch_k<d1::k_decode1_narrow<DT, 1, 2>, LIMIT>("lqer_decode1 (compact image)", grid, block, (int)lds, st, a1)
+                       : launch_k<d1::k_decode1_narrow<DT, 0, 2>, LIMIT>("lqer_decode1 (compact image)", grid, block, (int)lds, st, a1);
+    if (w_img == 3)
+      return bout == 1 ? launch_k<d1::k_decode1_narrow<DT, 1, 3>, LIMIT>("lqer_decode1 (compact image)", grid, block, (int)lds, st, a1)
+                       : launch_k<d1::k_decode1_narrow<DT, 0, 3>, LIMIT>("lqer_decode1 (compact image)", grid, block, (int)lds, st, a1);
     return bout == 1 ? launch_k<d1::k_decode1<DT, 1, false>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a1)
                      : launch_k<d1::k_decode1<DT, 0, false>, LIMIT>("lqer_decode1", grid, block, (int)lds, st, a1);
   });

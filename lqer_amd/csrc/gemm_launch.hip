@@ -12,6 +12,10 @@ int gemm_launch(const GemmPlan& p, GemmArgs g, int dtype, void* scratch, size_t 
     set_error("%s", p.msg);
     return p.err;
   }
+  if (p.w_img < 0) {  // (api.hip widens into the caller's workspace and launches the standard image's plan: never reached from there)
+    set_error("linear_gemm: this route's kernel reads standard panels - the compact weight image must be widened first");
+    return LQER_E_INVALID;
+  }
   g.tiles_m = p.tiles_m, g.tiles_n = p.tiles_n;
   if (p.bout == 2) g.bout_L = p.bout_L, g.bout_nblk = p.bout_nblk, g.bout_amax = nullptr, g.bout_nseg = p.pre.nseg;
   if (p.amax != AMAX_NONE) {

@@ -38,6 +38,10 @@ struct GemmPlan {
   bool w_twos, w_mf;          // 128-row family: integer / minifloat nibbles
   bool i8_shift, i8_codes;    // int8 route: weight groups with shifts; 8-bit weight codes
   int mt;                     // small-M kernel: 16-row token tiles, 1..4
+  // the weight image the route's kernel reads when the caller holds the compact image of a 2- / 3-bit weight (GemmArgs::w_narrow):
+  // 2 or 3 - the small-M kernel's instantiation that reads it directly; -1 - the route's kernel reads standard panels only, the
+  // caller widens the image into its workspace first; 0 - the caller holds the standard image
+  int w_img;
 
   AmaxTravel amax;
   size_t need;        // bytes of the caller's scratch the maxima take

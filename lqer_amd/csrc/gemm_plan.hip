@@ -188,6 +188,17 @@ GemmPlan plan_gemm(const GemmArgs& g, bool lowrank, bool i8_image, int dtype, in
   } else {
     p.route = LQER_ROUTE_TILE128, p.tile_rows = tile128_rows(g);
   }
+  // ---- the compact image of a 2- / 3-bit weight: read directly by the weight-streaming kernel, widened first for every other
+  if (g.w_narrow) {
+    if (i8_image)
+      refuse(p, false, LQER_E_UNSUPPORTED, "compact weight image: not on the int8 route (LQER_Q_MXINT_I8 reads an int8 image of its own)");
+    else if (g.w_twos || g.w_mf)
+      refuse(p, false, LQER_E_UNSUPPORTED,
+             "compact weight image: block_fp weights on the table-free expand only (integer / minifloat nibbles, LQER_TUNE_W_EXP_TABLE)");
+    else
+      p.w_img = p.route == LQER_ROUTE_SMALLM ? (g.w_narrow >> 8) : -1;
+    if (p.err) return p;
+  }
   if (p.empty) return p;
 
   // ---- the row maxima of B_out blocks other than 16 ---------------------------------------------------------------------------------

@@ -24,18 +24,21 @@ namespace lqer {
 constexpr int SM_NW = 8;       // waves per workgroup: wave w takes panels w, w + 8, ...
 template <int MT> struct SmUnr { static constexpr int v = MT <= 2 ? 4 : 2; };  // panels per register buffer (two buffers)
 
-template <int DT, bool LOWRANK, int BOUT, int MT>
-__global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
+// W: 0 - the standard 4-bit image; 2, 3 - the compact image of a weight of that width (w_narrow.h), read directly: other loads and
+// another expand, the same panels on the same waves in the same order, so the same sums.
+// The kernel's body, inlined into both kernels below (the standard image's keeps its name and its four template arguments).
+template <int DT, bool LOWRANK, int BOUT, int MT, int W>
+__device__ __forceinline__ void smallm_body(const GemmArgs& g) {
   constexpr bool XF16 = DT == LQER_F16X;  // fp16 activation image and fp16 weight fragments in the main loop (gemm_w4a8.hip)
   __shared__ __attribute__((aligned(16))) float red[(SM_NW - 1) * MT * 4 * 64];
   __shared__ __attribute__((aligned(16))) bf16_t xaq_l[LOWRANK ? MT * 16 * 64 : 8];  // [token][rp <= 64]: x A after A_out (partials mode)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const SmLane ln(lane);
+  const SmLaneT<W> ln(lane, g.w_narrow & 0xff);
   const int row = ln.row, q = ln.q;  // weight row / token within the tile; k group
   const int n0 = blockIdx.x * 16;
   const int nk = g.Kp / 64;
-  const uint8_t* prow = g.wp + (int64_t)blockIdx.x * nk * LQER_PANEL_BYTES;
+  const uint8_t* prow = g.wp + (int64_t)blockIdx.x * nk * ln.panel_bytes;
 
   f32x4 acc[MT];
 #pragma unroll
@@ -54,9 +57,14 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
         if (t * 16 + row < g.M) sp_x[t] = *(const bf16x8*)(g.xaq + (int64_t)(t * 16 + row) * g.xaq_ld + 8 * q);
     }
   }
-  auto load_panel = [&](int kt, SmPanel& p, bf16x8 (&x)[MT][2]) {
-    const uint8_t* pp = prow + (int64_t)kt * LQER_PANEL_BYTES;
-    p.cw = *(const u32x4*)(pp + ln.codes_off);
+  auto load_panel = [&](int kt, SmPanelT<W>& p, bf16x8 (&x)[MT][2]) {
+    const uint8_t* pp = prow + (int64_t)kt * ln.panel_bytes;
+    if constexpr (W == 0) {
+      p.cw = *(const u32x4*)(pp + ln.codes_off);
+    } else {
+      p.cw = *(const uint32_t*)(pp + ln.codes_off);
+      if constexpr (W == 3) p.sg = *(const uint32_t*)(pp + ln.signs_off);
+    }
     p.ex = *(const uint32_t*)(pp + ln.exps_off);
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -70,9 +78,9 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
       }
     }
   };
-  auto compute_panel = [&](const SmPanel& p, const bf16x8 (&x)[MT][2]) {
+  auto compute_panel = [&](const SmPanelT<W>& p, const bf16x8 (&x)[MT][2]) {
     bf16x8 wb0, wb1;
-    sm_expand<XF16>(p, ln, wb0, wb1);
+    sm_expand<XF16, W>(p, ln, wb0, wb1);
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       acc[t] = mfma_16x16x32<XF16>(wb0, x[t][0], acc[t]);
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
 
   // wave w takes panels w, w + SM_NW, ...; two register buffers of SM_UNR panels keep 2 x SM_UNR panels of loads in flight
   constexpr int SM_UNR = SmUnr<MT>::v;
-  SmPanel pa[SM_UNR], pb[SM_UNR];
+  SmPanelT<W> pa[SM_UNR], pb[SM_UNR];
   bf16x8 xa[SM_UNR][MT][2], xb[SM_UNR][MT][2];
   const int per_wave = (nk - wave + SM_NW - 1) / SM_NW;  // panels of this wave
   auto kt_of = [&](int i) { return wave + SM_NW * i; };
@@ -205,20 +213,47 @@ __global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
   }
 }
 
-template <int DT, bool LR, int BO>
+template <int DT, bool LOWRANK, int BOUT, int MT>
+__global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm(GemmArgs g) {
+  smallm_body<DT, LOWRANK, BOUT, MT, 0>(g);
+}
+// ... reading the compact image of a weight of W = 2 or 3 bits
+template <int DT, bool LOWRANK, int BOUT, int MT, int W>
+__global__ __launch_bounds__(64 * SM_NW) void k_lqer_gemm_smallm_narrow(GemmArgs g) {
+  smallm_body<DT, LOWRANK, BOUT, MT, W>(g);
+}
+
+template <int DT, bool LR, int BO, int MT, int W>
+static int run_smallm_mt(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if constexpr (W == 0) return launch_k<k_lqer_gemm_smallm<DT, LR, BO, MT>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
+  else return launch_k<k_lqer_gemm_smallm_narrow<DT, LR, BO, MT, W>>("lqer_gemm_smallm (compact image)", p.grid, 64 * SM_NW, 0, st, g);
+}
+
+template <int DT, bool LR, int BO, int W>
 static int run_smallm(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
   switch (p.mt) {  // 16-row token tiles
-    case 1: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 1>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
-    case 2: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 2>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
-    case 3: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 3>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
-    default: return launch_k<k_lqer_gemm_smallm<DT, LR, BO, 4>>("lqer_gemm_smallm", p.grid, 64 * SM_NW, 0, st, g);
+    case 1: return run_smallm_mt<DT, LR, BO, 1, W>(p, g, st);
+    case 2: return run_smallm_mt<DT, LR, BO, 2, W>(p, g, st);
+    case 3: return run_smallm_mt<DT, LR, BO, 3, W>(p, g, st);
+    default: return run_smallm_mt<DT, LR, BO, 4, W>(p, g, st);
   }
+}
+
+template <int DT, int W>
+static int launch_smallm_w(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+  if (!p.lowrank) return run_smallm<DT, false, 0, W>(p, g, st);
+  return p.bout == 1 ? run_smallm<DT, true, 1, W>(p, g, st) : run_smallm<DT, true, 0, W>(p, g, st);
 }
 
 template <int DT>
 static int launch_smallm(const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
-  if (!p.lowrank) return run_smallm<DT, false, 0>(p, g, st);
-  return p.bout == 1 ? run_smallm<DT, true, 1>(p, g, st) : run_smallm<DT, true, 0>(p, g, st);
+  switch (p.w_img) {  // the image the kernel reads: the plan's (0: standard; 2, 3: compact, of that width)
+    case 0: return launch_smallm_w<DT, 0>(p, g, st);
+    case 2: return launch_smallm_w<DT, 2>(p, g, st);
+    case 3: return launch_smallm_w<DT, 3>(p, g, st);
+  }
+  set_error("lqer_gemm_smallm: no instantiation for a compact image of width %d", p.w_img);
+  return LQER_E_UNSUPPORTED;
 }
 
 int smallm_launch(const GemmPlan& p, const GemmArgs& g, int dtype, hipStream_t st) {

@@ -13,6 +13,7 @@
 // A coarser weight block (32, 128, whole row) repeats its exponent per segment, so the GEMM kernel
 // handles every block length with one code path.
 #include "common.h"
+#include "w_narrow.h"
 
 namespace lqer {
 
@@ -404,6 +405,75 @@ int f16_prepare_dispatch(const void* w_packed, int64_t N, int64_t K, const void*
                                                                                                    (_Float16*)a_f16, flags);
   }
   return check_launch("f16_prepare");
+}
+
+// ---- the compact image of 2- / 3-bit block_fp weights (w_narrow.h) ----------------------------------------------------------------
+// narrow: standard image -> compact image; widen: back.  One lane per (panel, row), the row functions of w_narrow.h.
+// widen(narrow(img)) == img byte for byte rests on what k_w_pack (above) writes for such a format, checked against its code:
+// (1) a nibble's magnitude is |mxint_mantissa| <= q.mmax = 2^(width-1) - 1 (make_qp: block_fp clamps both signs to mmax), so only the
+//     low width - 1 magnitude bits are ever set; padded and all-zero lanes write nibble 0;
+// (2) a live segment's exponent byte comes from scratch[row * nblk + k0 / L] alone: the segments of one block carry the same byte, and a
+//     block of 32, 64, 128, ... k starts at a multiple of its length, so it covers the span of a compact byte entirely (k_w_exps_rows
+//     only makes rows agree); an all-zero block writes e = 0 for all of its segments;
+// (3) NOT repeated: a segment that starts at or past K gets e = 0 whatever block it lies in - in the panel that K cuts, a block's byte
+//     stands next to the padding's.  That byte is a constant of the format (wn_pad_byte), so the compact image need not store it:
+//     narrow and widen are told the panel's live segments (wn_live_segs).  Rows past N are padding throughout: nothing to tell.
+template <int W>
+__global__ __launch_bounds__(256) void k_w_narrow(const uint8_t* __restrict__ in, int64_t panels, int64_t npk, int64_t K, int E,
+                                                  uint8_t* __restrict__ out) {
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < panels * 16; idx += (int64_t)gridDim.x * 256) {
+    const int64_t p = idx >> 4;
+    (void)wn_narrow_row<W>(in + p * LQER_PANEL_BYTES, out + p * wn_panel_bytes(W, E), (int)(idx & 15), E, wn_live_segs(K, p % npk));
+  }
+}
+template <int W>
+__global__ __launch_bounds__(256) void k_w_widen(const uint8_t* __restrict__ in, int64_t panels, int64_t npk, int64_t K, int E,
+                                                 uint8_t* __restrict__ out) {
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < panels * 16; idx += (int64_t)gridDim.x * 256) {
+    const int64_t p = idx >> 4;
+    wn_widen_row<W>(in + p * wn_panel_bytes(W, E), out + p * LQER_PANEL_BYTES, (int)(idx & 15), E, wn_live_segs(K, p % npk));
+  }
+}
+
+int weight_narrow_dispatch(const void* w_packed, int64_t N, int64_t K, int width, int E, void* w_narrow, hipStream_t st) {
+  const int64_t npk = lqer_padded_k(K) / 64, panels = (lqer_padded_n(N) / 16) * npk;
+  const unsigned grid = (unsigned)((panels * 16 + 255) / 256 < 65536 ? (panels * 16 + 255) / 256 : 65536);
+  if (width == 2) k_w_narrow<2><<<grid, 256, 0, st>>>((const uint8_t*)w_packed, panels, npk, K, E, (uint8_t*)w_narrow);
+  else k_w_narrow<3><<<grid, 256, 0, st>>>((const uint8_t*)w_packed, panels, npk, K, E, (uint8_t*)w_narrow);
+  return check_launch("weight_narrow");
+}
+
+int weight_widen_dispatch(const void* w_narrow, int64_t N, int64_t K, int width, int E, void* w_packed, hipStream_t st) {
+  const int64_t npk = lqer_padded_k(K) / 64, panels = (lqer_padded_n(N) / 16) * npk;
+  const unsigned grid = (unsigned)((panels * 16 + 255) / 256 < 65536 ? (panels * 16 + 255) / 256 : 65536);
+  if (width == 2) k_w_widen<2><<<grid, 256, 0, st>>>((const uint8_t*)w_narrow, panels, npk, K, E, (uint8_t*)w_packed);
+  else k_w_widen<3><<<grid, 256, 0, st>>>((const uint8_t*)w_narrow, panels, npk, K, E, (uint8_t*)w_packed);
+  return check_launch("weight_widen");
+}
+
+bool weight_narrow_host(const uint8_t* w_packed, int64_t N, int64_t K, int width, int E, uint8_t* w_narrow) {
+  const int64_t npk = lqer_padded_k(K) / 64, panels = (lqer_padded_n(N) / 16) * npk;
+  bool ok = true;
+  for (int64_t p = 0; p < panels; ++p)
+    for (int row = 0; row < 16; ++row) {
+      const uint8_t* sp = w_packed + p * LQER_PANEL_BYTES;
+      uint8_t* np = w_narrow + p * wn_panel_bytes(width, E);
+      const int live = wn_live_segs(K, p % npk);
+      ok = (width == 2 ? wn_narrow_row<2>(sp, np, row, E, live) : wn_narrow_row<3>(sp, np, row, E, live)) && ok;
+    }
+  return ok;
+}
+
+void weight_widen_host(const uint8_t* w_narrow, int64_t N, int64_t K, int width, int E, uint8_t* w_packed) {
+  const int64_t npk = lqer_padded_k(K) / 64, panels = (lqer_padded_n(N) / 16) * npk;
+  for (int64_t p = 0; p < panels; ++p)
+    for (int row = 0; row < 16; ++row) {
+      const uint8_t* np = w_narrow + p * wn_panel_bytes(width, E);
+      uint8_t* sp = w_packed + p * LQER_PANEL_BYTES;
+      const int live = wn_live_segs(K, p % npk);
+      if (width == 2) wn_widen_row<2>(np, sp, row, E, live);
+      else wn_widen_row<3>(np, sp, row, E, live);
+    }
 }
 
 int bias_passthrough_dispatch(const void* b, int dtype, int64_t N, float* out, hipStream_t st) {

@@ -67,6 +67,8 @@ class _LinearBase(nn.Linear):
         self._w_exp_table = False  # the weight image holds an exponent byte above 245: the bf16 GEMM's table expand (decided when the images are built)
         self.a16_fused = True      # block-16 MXINT activations: build the image the one-launch activation kernel reads (a_limbs = -2)
         self.tuning = 0            # lqer_linear_desc_t.tuning (_lib.TUNE_*): per-call kernel-variant knobs of tests, same bits
+        self._weight_image = "standard"  # `weight_image`: "narrow" keeps the compact image of a 2- / 3-bit block_fp weight instead
+        self._w_single_kind = "standard"  # ... and the kind of the image `_w_single` holds
         self._setup_quantizers(q_config)
         self._setup_lqer(l_config)
         # activation quantizers whose blocks can span token rows ([R, L] tiles, skip_first_dim = false): the tile route below
@@ -109,9 +111,52 @@ class _LinearBase(nn.Linear):
                           eff("x", _SIG_BITS[dt]), f["w"], f.get("b", none), eff("A_out", 24 if dt == torch.float32 else 16),
                           f.get("B_out", none), int(getattr(self, "tuning", 0)) | (_lib.TUNE_W_EXP_TABLE if self._w_exp_table else 0))
 
+    @property
+    def weight_image(self) -> str:
+        """"standard": the 4-bit panels every kernel reads (4.5 bits per weight at every width).  "narrow": block_fp weights of width 2 or
+        3 keep the compact image at their own width instead (include/lqer_hip.h "compact weight image"): the decode-size kernels read
+        it directly - same bits -, larger token counts widen it into the workspace first.  Settable at any time; a change drops the
+        derived images like any other invalidation.  A module the library does not serve raises NotImplementedError at pack()."""
+        return self._weight_image
+
+    @weight_image.setter
+    def weight_image(self, kind: str) -> None:
+        if kind not in ("standard", "narrow"):
+            raise ValueError(f"weight_image must be 'standard' or 'narrow', got {kind!r}")
+        if kind == self.__dict__.get("_weight_image", "standard"):
+            return
+        if self._packed_only and self._packed is not None:  # (the images are the only copy of the operands: through their own state)
+            state, dev = self.packed_state(), self._packed["w"].device
+            self._weight_image = kind
+            self.load_packed_state(state, dev)
+            return
+        self._weight_image = kind
+        self.invalidate_packed(weight_changed=False)
+
     def _limbs(self):
         """(activation limbs, x A limbs) of the packed images - 1, 1 unless x / A_out are pass-through."""
         return ops.desc_limbs(self._desc())
+
+    def _build_images(self, p: dict) -> dict:
+        """Single-copy images (p["w"]: the standard weight image) -> the images the kernels read.  With weight_image = "narrow" the
+        compact image takes the standard one's place - after every decision that reads the standard image's exponent bytes (fp16
+        route, table expand) - and the standard image is dropped; what the library does not serve raises, with its reason."""
+        q = self._replicate(p)
+        if self._weight_image != "narrow":
+            return q
+        L = _lib.lib()
+        N, K, fw = self.out_features, self.in_features, self._fmt["w"]
+        desc = self._desc()
+        rc = L.lqer_weight_narrow_route(C.byref(desc), 1, ops.dtype_code(self.weight), K, 1, 1)
+        if rc < 0:
+            self._packed = None
+            raise NotImplementedError("weight_image='narrow': " + L.lqer_last_error().decode())
+        q = dict(q)
+        std = q["w"]
+        q["w"] = ops.weight_narrow(std, N, K, fw)
+        if not torch.equal(ops.weight_widen(q["w"], N, K, fw), std.reshape(-1).view(torch.uint8)):
+            raise RuntimeError("weight_image='narrow': the compact image does not widen back to the packed weight image")
+        return q
 
     def _replicate(self, p: dict) -> dict:
         """Single-copy packed images -> the images the kernels read (no-op for block_fp x / A_out).  Pass-through fp16
@@ -246,6 +291,8 @@ class _LinearBase(nn.Linear):
         if keep and (self._fmt["x"].kind == _lib.Q_PASSTHROUGH or self._limbs() != (1, 1)):
             # pass-through formats: the images depend on the dtype (limb copies, fp16 route) - go back to one copy first
             singles = {k: self._single_copy(k) for k in ("w", "a_t", "b_t") if k in self._packed}
+            if self._weight_image == "narrow":  # (_build_images decides from the standard image and narrows it again)
+                singles["w"] = ops.weight_widen(singles["w"], self.out_features, self.in_features, self._fmt["w"])
             singles["a_limbs"] = int(self._packed.get("a_limbs_orig", self._packed.get("a_limbs", 0)))
         out = super()._apply(fn, recurse)
         if getattr(self, "_packed_only", False):
@@ -258,7 +305,7 @@ class _LinearBase(nn.Linear):
                 if singles is not None and self.weight.dtype != dt_before:
                     p.update(singles)
                     p.pop("a_t_limbs", None), p.pop("a_limbs_orig", None)
-                    p = self._replicate({k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in p.items()})
+                    p = self._build_images({k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in p.items()})
                 self._packed = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in p.items()}
         else:
             # .to() / .half(): the A / B images follow the new dtype and device; the weight stays quantized once
@@ -292,7 +339,9 @@ class _LinearBase(nn.Linear):
         self.pack()
         p = self._packed
         al, bl = int(p.get("a_limbs_orig", p.get("a_limbs", 0))), int(p.get("b_limbs", 0))
-        out = {"w": self._single_copy("w")}  # (a Linear with pass-through activations holds one copy per limb: store one)
+        # (a Linear with pass-through activations holds one copy per limb: store one; a narrow module stores its compact image, under a
+        # key of its own - the header does not change, load_packed_state takes either key into either kind of module)
+        out = {"w_narrow" if self._weight_image == "narrow" else "w": self._single_copy("w")}
         if self.rank > 0:
             Kp, Np = _lib.lib().lqer_padded_k(self.in_features), _lib.lib().lqer_padded_n(self.out_features)
             rp = _lib.lib().lqer_padded_r(self.rank)
@@ -333,14 +382,20 @@ class _LinearBase(nn.Linear):
             buf[: src.numel()] = src
             return buf
 
-        p = {"w": full("w", sz.w_packed)}
-        if p["w"].numel() != state["w"].numel():
-            raise RuntimeError("packed weight size mismatch")
+        if "w" in state:
+            p = {"w": full("w", sz.w_packed)}
+            if p["w"].numel() != state["w"].numel():
+                raise RuntimeError("packed weight size mismatch")
+        else:  # written by a narrow module: the compact image, widened here (a narrow module narrows it again after its decisions)
+            nb = ops.weight_narrow_bytes(self.out_features, self.in_features, self._fmt["w"])
+            if nb == 0 or state["w_narrow"].numel() != nb:
+                raise RuntimeError("packed weight size mismatch (compact image)")
+            p = {"w": ops.weight_widen(full("w_narrow", nb), self.out_features, self.in_features, self._fmt["w"])}
         if self.rank > 0:
             p["a_t"], p["b_t"], p["a_limbs"], p["b_limbs"] = full("a_t", sz.a_t), full("b_t", sz.b_t), al, bl
         if self.bias is not None:
             p["bias"] = full("bias_q", sz.bias_q).view(torch.float32)
-        self._packed = self._replicate(p)
+        self._packed = self._build_images(p)
         self._packed_only = True
         self.w_is_quantized = True
         self._w_ver = None
@@ -357,8 +412,11 @@ class _LinearBase(nn.Linear):
         with torch.cuda.device(W.device):
             if self.w_is_quantized and self._w_single is not None:
                 w_img = self._w_single = self._w_single.to(W.device)
+                if self._w_single_kind == "narrow":  # (the transient standard image: _build_images decides from its exponent bytes)
+                    w_img = ops.weight_widen(w_img, self.out_features, self.in_features, f["w"])
             else:
                 w_img = self._w_single = ops.pack_weight(W, f["w"])
+                self._w_single_kind = "standard"
                 # the parameter now carries w_quantizer(W) (|w| <= 1e-8 kept as is, block_fp.py:79-80)
                 if int(getattr(f["w"], "block_rows", 1)) == 1:
                     wq = ops.quantize_mxint(W, f["w"], want=("deq",))["deq"]
@@ -374,7 +432,11 @@ class _LinearBase(nn.Linear):
                 p["bias"] = self._bias_q = self._bias_q.to(W.device)
             if self.rank > 0:
                 p["a_t"], p["b_t"], p["a_limbs"], p["b_limbs"] = ops.pack_lowrank(self.A.data, self.B.data)
-            self._packed = self._replicate(p)
+            self._packed = self._build_images(p)
+            if self._weight_image == "narrow":  # only the compact image stays
+                self._w_single, self._w_single_kind = self._packed["w"], "narrow"
+            elif self._w_single_kind == "narrow":
+                self._w_single, self._w_single_kind = w_img, "standard"
             if self._x_i8:
                 # the int8 route's buffer starts with the sign-magnitude image: keep a VIEW of it as the single copy instead of a
                 # second full 4.5-bit image for the module's lifetime (several GB on a 7B W4A8-INT model)
@@ -509,7 +571,8 @@ class _LinearBase(nn.Linear):
             return y.reshape(*x.shape[:-1], N)
         # per token count and dtype, built once: descriptor, workspace size and the constant part of the argument list
         # (decode-size forwards are host-bound: the ctypes marshalling of 16 arguments is not free)
-        key = (M, x2.dtype, self.tuning)
+        narrow = self._weight_image == "narrow"
+        key = (M, x2.dtype, self.tuning, narrow)
         ent = self._fw_cache.get(key)
         if ent is None:
             desc = self._desc()
@@ -518,17 +581,18 @@ class _LinearBase(nn.Linear):
                 self._fw_cache = {}
             # (plain data only: the module must stay deep-copyable and picklable)
             a_t, a_limbs = self._side_image(M, desc, ops.dtype_code(x2))
-            ent = self._fw_cache[key] = (desc, ops.linear_sizes(desc, M).workspace, ops.dtype_code(x2),
+            ws_need = _lib.lib().lqer_linear_forward_narrow_workspace_bytes(C.byref(desc), M) if narrow else ops.linear_sizes(desc, M).workspace
+            ent = self._fw_cache[key] = (desc, ws_need, ops.dtype_code(x2),
                                          (p["w"].data_ptr(), a_t, ops._ptr(p.get("b_t")),
                                           a_limbs, p.get("b_limbs", 0), ops._ptr(p.get("bias"))))
         desc, ws_bytes, dt, consts = ent
         dref = C.byref(desc)
         st = ops._stream(x.device)
         ws = ops.workspace_on(x.device, st, ws_bytes)
-        rc = _lib.lib().lqer_linear_forward(dref, x2.data_ptr(), dt, M, x2.stride(0) if M > 1 else K, *consts,
-                                            y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        fwd = _lib.lib().lqer_linear_forward_narrow if narrow else _lib.lib().lqer_linear_forward  # (narrow: consts[0] is the compact image)
+        rc = fwd(dref, x2.data_ptr(), dt, M, x2.stride(0) if M > 1 else K, *consts, y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
         if rc:
-            check(rc, "lqer_linear_forward")
+            check(rc, "lqer_linear_forward_narrow" if narrow else "lqer_linear_forward")
         return y.reshape(*x.shape[:-1], N)
 
     def _side_image(self, M: int, desc, dt_code: int):
@@ -545,8 +609,9 @@ class _LinearBase(nn.Linear):
         return a_t, a_limbs
 
     def __repr__(self):
-        return "{}(in_features={}, out_features={}, bias={}, is_ptq={}, rank={}, backend=hip/gfx950)".format(
-            self.__class__.__name__, self.in_features, self.out_features, self.bias is not None, self.is_ptq, self.rank)
+        return "{}(in_features={}, out_features={}, bias={}, is_ptq={}, rank={}, backend=hip/gfx950{})".format(
+            self.__class__.__name__, self.in_features, self.out_features, self.bias is not None, self.is_ptq, self.rank,
+            ", weight_image=narrow" if self.__dict__.get("_weight_image") == "narrow" else "")
 
 
 class SharedActivation:
@@ -697,7 +762,8 @@ class SharedActivation:
         L = _lib.lib()
         dev = x2.device
         if plan is False:
-            if any(m._packed_only for m in self.members):  # (a packed checkpoint carries no dense A to concatenate)
+            # (a packed checkpoint carries no dense A to concatenate; lqer_group_member_t holds standard images only)
+            if any(m._packed_only or m._weight_image == "narrow" for m in self.members):
                 self._dplans[(M, dtc)] = None
                 return None
             for m in self.members:
@@ -785,8 +851,12 @@ class SharedActivation:
             for m in self.members:  # (plain data and ctypes structs only)
                 d = m._desc(plain=not i8)
                 pk = m._packed
+                # (a member with the compact image: lqer_linear_gemm_narrow, with room to widen where its route reads standard panels)
+                wide = 0
+                if m._weight_image == "narrow":
+                    wide = max(16, ops.linear_sizes(d, 1).w_packed if L.lqer_weight_narrow_route(C.byref(d), M, dtc, K, 1, 1) == _lib.NARROW_WIDEN else 16)
                 mem.append((d, L.lqer_linear_gemm_scratch_bytes(C.byref(d), M), pk["w"].data_ptr(), pk["b_t"].data_ptr(),
-                            pk["b_limbs"], ops._ptr(pk.get("bias")), m.out_features))
+                            pk["b_limbs"], ops._ptr(pk.get("bias")), m.out_features, wide))
             if len(self._plans) > 64:
                 self._plans = {}
             plan = self._plans[(M, dtc)] = {
@@ -814,12 +884,17 @@ class SharedActivation:
         self._served.add(idx)
         if len(self._served) == len(self.members):
             self._x = None  # every member has been served: do not pin the activation tensor until the next call
-        desc, gs, w_ptr, bt_ptr, b_limbs, bias_ptr, N = plan["members"][idx]
-        scr = ops.workspace(dev, max(gs, 16))
-        rc = L.lqer_linear_gemm_ld(C.byref(desc), cur["xq"], M, w_ptr, cur["xaq"] + 2 * self._cat["offs"][idx],
-                                   self._cat["rp_total"], bt_ptr, b_limbs, bias_ptr, y.data_ptr(), dtc, N, scr.data_ptr(), gs, st)
+        desc, gs, w_ptr, bt_ptr, b_limbs, bias_ptr, N, wide = plan["members"][idx]
+        gs_al = (max(gs, 16) + 255) // 256 * 256
+        scr = ops.workspace(dev, gs_al + wide)
+        if wide:  # the compact image: the widened copy, where this token count needs one, lies behind the GEMM's scratch
+            rc = L.lqer_linear_gemm_narrow(C.byref(desc), cur["xq"], M, w_ptr, cur["xaq"] + 2 * self._cat["offs"][idx], self._cat["rp_total"],
+                                           bt_ptr, b_limbs, bias_ptr, y.data_ptr(), dtc, N, scr.data_ptr(), gs, scr.data_ptr() + gs_al, wide, st)
+        else:
+            rc = L.lqer_linear_gemm_ld(C.byref(desc), cur["xq"], M, w_ptr, cur["xaq"] + 2 * self._cat["offs"][idx],
+                                       self._cat["rp_total"], bt_ptr, b_limbs, bias_ptr, y.data_ptr(), dtc, N, scr.data_ptr(), gs, st)
         if rc:
-            check(rc, "lqer_linear_gemm_ld (shared input)")
+            check(rc, "lqer_linear_gemm_narrow (shared input)" if wide else "lqer_linear_gemm_ld (shared input)")
         return True
 
 

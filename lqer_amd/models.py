@@ -55,10 +55,13 @@ def _layer_cfg(cfg: Optional[dict], layer_id: int, group: str, name: str) -> Opt
 _SHARED_INPUTS = {"self_attn": (("q_proj", "k_proj", "v_proj"),), "mlp": (("gate_proj", "up_proj"),)}
 
 
-def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], share_inputs: bool = True) -> nn.Module:
+def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], share_inputs: bool = True,
+                   weight_image: str = "standard") -> nn.Module:
     """Replace the projections of every decoder layer in place; weights are carried over.  share_inputs: projections
     fed by the same tensor quantize it once and share one side GEMM (linear.SharedActivation); per-projection results
-    are unchanged up to the fp32 summation order of the side product."""
+    are unchanged up to the fp32 summation order of the side product.  weight_image: "narrow" makes every projection keep the
+    compact image of its 2- / 3-bit block_fp weight (linear._LinearBase.weight_image; a projection it does not serve raises when
+    it packs)."""
     layers, table = _decoder_layers(model)
     for layer_id, layer in enumerate(layers):
         for group, names in table.items():
@@ -73,6 +76,7 @@ def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], s
                 new = cls(old.in_features, old.out_features, bias=old.bias is not None, q_config=qc, l_config=lc)
                 new.to(device=old.weight.device, dtype=old.weight.dtype)
                 new.load_state_dict(old.state_dict(), strict=False)  # A, B stay zero until loaded
+                new.weight_image = weight_image
                 setattr(parent, name, new)
             if share_inputs:
                 for names2 in _SHARED_INPUTS.get(group, ()):

@@ -284,6 +284,34 @@ def pack_weight(W: torch.Tensor, fmt: QFmt) -> torch.Tensor:
     return packed
 
 
+def weight_narrow_bytes(N: int, K: int, fmt: QFmt) -> int:
+    """Bytes of the compact image of a 2- / 3-bit block_fp weight (include/lqer_hip.h "compact weight image"); 0: format not served."""
+    return int(_lib.lib().lqer_weight_narrow_bytes(N, K, C.byref(fmt)))
+
+
+@_on_tensor_device
+def weight_narrow(w_packed: torch.Tensor, N: int, K: int, fmt: QFmt) -> torch.Tensor:
+    """Standard packed image (single copy) -> compact image."""
+    _need_gpu(w_packed)
+    nbytes = weight_narrow_bytes(N, K, fmt)
+    if nbytes == 0:
+        raise NotImplementedError("the compact weight image holds block_fp weights of width 2 or 3 "
+                                  f"(w_quantizer kind {fmt.kind}, width {fmt.width}): keep weight_image='standard'")
+    out = torch.empty(nbytes, dtype=torch.uint8, device=w_packed.device)
+    check(_lib.lib().lqer_weight_narrow(w_packed.data_ptr(), N, K, C.byref(fmt), out.data_ptr(), _stream(w_packed.device)), "lqer_weight_narrow")
+    return out
+
+
+@_on_tensor_device
+def weight_widen(w_narrow: torch.Tensor, N: int, K: int, fmt: QFmt) -> torch.Tensor:
+    """Compact image -> standard packed image (single copy)."""
+    _need_gpu(w_narrow)
+    L = _lib.lib()
+    out = torch.empty((L.lqer_padded_n(N) // 16) * (L.lqer_padded_k(K) // 64) * 576, dtype=torch.uint8, device=w_narrow.device)
+    check(L.lqer_weight_widen(w_narrow.data_ptr(), N, K, C.byref(fmt), out.data_ptr(), _stream(w_narrow.device)), "lqer_weight_widen")
+    return out
+
+
 @_on_tensor_device
 def replicate_rows(src: torch.Tensor, rows: int, row_bytes: int, copies: int) -> torch.Tensor:
     """[rows][row_bytes] -> [rows][copies * row_bytes] (every row repeated): the packed images of a Linear with
