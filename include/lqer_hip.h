@@ -767,6 +767,20 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * below lens[b] - converted codes below lens[b], zeros from there on - which is all the attention kernel reads of them; image
  * workgroups beyond that leave at once, so a ragged batch pays for its keys and not for max_len.  Three launches on `stream` (K image,
  * V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
+ * lqer_attention_q_paged_window: lqer_attention_q_paged's argument list plus `window` = W >= 1, the SLIDING WINDOW of
+ * lqer_attention_q_decode_paged_window for any S >= 1 (causal = 1 is required): query row i of sequence b sits at position
+ * p = i + (lens[b] - S) and sees the keys p - W < j <= p.  The rule is a compile-time instantiation of the prefill kernel: a workgroup
+ * starts both sweeps at the first 64-key tile one of its 128 queries sees, a wave skips the 32-key subtiles wholly below its own first
+ * key, a lane selects by its own - work per call follows W + S, not lens[b].  For every b, out[b] and row_stats[b] are the SAME BITS as
+ * lqer_attention_q with batch = 1 on the FULL raw K and V of that sequence and the additive window mask - 0 inside the window, the
+ * dtype's most negative finite value outside - WHATEVER THE PAGES BELOW THE WINDOW NOW HOLD AND WHATEVER THE WORKSPACE HELD: with
+ * lo_b = max(0, lens[b] - S - W + 1), the first key the call's first row sees, the caller guarantees that the keys from
+ * 16 (lo_b / 16) on are in the pool; no table entry and no page below that key is read (K or V, codes or exponents).  Of sequence b's
+ * images the call writes from key 64 (lo_b / 64) on: zeros up to 16 (lo_b / 16) (a zero probability times a stale image row must be 0,
+ * not NaN), the converted codes from there; image workgroups below that tile leave at once and the attention kernel loads no tile
+ * below it.  The images stay indexed by absolute key: workspace, grid and strides are lqer_attention_q_paged's
+ * (lqer_attention_q_paged_workspace_bytes, sized by max_len), three launches, capturable alike.  Refused as lqer_attention_q_paged,
+ * and LQER_E_INVALID for window < 1 or causal = 0.
  * PER-SEQUENCE TOKEN COUNTS - a scheduler step in which most sequences decode one token while a few take a prompt chunk - go through
  * the two _ragged calls.  The metadata contract is the one above, with:
  *   new_starts / q_starts  int32 [batch + 1], on the DEVICE, written by the caller: non-decreasing, starts[0] >= 0, starts[batch] <=
@@ -792,6 +806,12 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * lqer_attention_q_paged_workspace_bytes at the same arguments - the two images, nothing that follows the counts.  Three launches on
  * `stream` (K image, V image, the attention kernel), no allocation, no host synchronisation, no atomics: capturable in a hipGraph.
  * Refused as lqer_attention_q_paged, and LQER_E_INVALID for a null q_starts, max_s < 1, total < 0.
+ * lqer_attention_q_paged_ragged_window: lqer_attention_q_paged_ragged's argument list plus `window` = W >= 1 - the rule and the
+ * guarantees of lqer_attention_q_paged_window, every sequence by its own count: lo_b = max(0, lens[b] - S_b - W + 1), the keys from
+ * 16 (lo_b / 16) on are in the pool (the caller's to keep), nothing below is read, and the rows of sequence b are the SAME BITS as
+ * lqer_attention_q with batch = 1, S = S_b on its FULL raw K and V and the additive window mask.  Workspace
+ * (lqer_attention_q_paged_ragged_workspace_bytes), grid and launches are lqer_attention_q_paged_ragged's.  Refused as that call, and
+ * LQER_E_INVALID for window < 1 or causal = 0.
  * lqer_attention_q_decode_paged_ragged: lqer_attention_q_paged_ragged's argument list plus `window`, on the split-over-keys kernels of
  * lqer_attention_q_decode_paged - for counts of up to 8 rows: the verify step of a speculative decoder (1 .. 8 draft tokens per
  * sequence), a scheduler step of one-token decoders beside sequences that take a few.  1 <= max_s <= 8; counts above max_s are the
@@ -871,6 +891,12 @@ int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, i
                            int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
                            const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                            const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
+int lqer_attention_q_paged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                           int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                           int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
+                           const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                           const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream,
+                           int64_t window);
 size_t lqer_attention_q_paged_ragged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t max_s, int64_t max_len, int64_t D);
 int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                                   int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
@@ -878,6 +904,13 @@ int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_b
                                   int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling,
                                   int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
                                   const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream);
+int lqer_attention_q_paged_ragged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                  const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                  int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads,
+                                  const int32_t* q_starts, int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides,
+                                  const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                                  const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream,
+                                  int64_t window);
 size_t lqer_attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D);
 int lqer_attention_q_decode_paged_ragged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
                                          const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,

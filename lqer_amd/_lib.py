@@ -163,6 +163,9 @@ SIGNATURES = {
     "lqer_attention_q_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
                                     _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    # ... with the sliding-window rule in k_attn_q and the image kernels: the same list plus `window`
+    "lqer_attention_q_paged_window": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
+                                           _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
     # per-sequence token counts in one call (a mixed prefill / decode step): new_starts / q_starts [batch + 1] on the device, a host bound
     # on the counts, packed [total][heads][D] tensors through stride PAIRS (token, head)
     "lqer_kv_pool_append_ragged": (_i, [_vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64,
@@ -171,6 +174,8 @@ SIGNATURES = {
     # lqer_attention_q_paged's list with S -> (q_starts, max_s, total)
     "lqer_attention_q_paged_ragged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64, _i64,
                                            _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    "lqer_attention_q_paged_ragged_window": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64,
+                                                  _i64, _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
     # ... for counts of up to 8 rows on the split-over-keys kernels (csrc/attn_decode.hip): the same list plus `window` (0: none); the
     # workspace follows (total, heads, max_len, D)
     "lqer_attention_q_decode_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),

@@ -1411,8 +1411,11 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
   }
   const size_t need = kn.workspace_bytes(c);
   if (c.workspace_bytes < need) {
-    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need,
-              c.windowed && !ragged ? "attention_q_decode_paged" : who);  // (the windowed call has the unwindowed one's workspace)
+    // (a windowed call has the unwindowed one's workspace; the ragged decode call takes its window as an argument of its own)
+    const char* sized_by = !c.windowed ? who
+                           : kn.max_s  ? (ragged ? who : "attention_q_decode_paged")
+                                       : (ragged ? "attention_q_paged_ragged" : "attention_q_paged");
+    set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need, sized_by);
     return LQER_E_INVALID;
   }
   return LQER_OK;
@@ -1822,6 +1825,20 @@ int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, i
   return attn_run("attention_q_paged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
 }
 
+int lqer_attention_q_paged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                                  int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
+                                  const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                                  const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream,
+                                  int64_t window) {
+  // (the call above with the window rule; grid and workspace still follow max_len)
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
+                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  c.packed = c.paged = c.windowed = true, c.window = window;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  return attn_run("attention_q_paged_window", ATTN_PREFILL, c);
+}
+
 size_t lqer_attention_q_paged_ragged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t max_s, int64_t max_len, int64_t D) {
   return lqer_attention_q_paged_workspace_bytes(batch, heads, kv_heads, max_s, max_len, D);  // (the images only: nothing follows the counts)
 }
@@ -1842,6 +1859,24 @@ int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_b
   c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
   c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
   return attn_run("attention_q_paged_ragged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
+}
+
+int lqer_attention_q_paged_ragged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                         const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                         int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+                                         int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total, int64_t D,
+                                         const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                         const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
+                                         void* workspace, size_t workspace_bytes, void* stream, int64_t window) {
+  // (the call above with the window rule, every sequence by its own count)
+  const int64_t qs[3] = {0, q_strides ? q_strides[1] : 0, q_strides ? q_strides[0] : 0};
+  const int64_t os[3] = {0, out_strides ? out_strides[1] : 0, out_strides ? out_strides[0] : 0};
+  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, max_s, max_len, D, q_strides ? qs : nullptr, nullptr,
+                         out_strides ? os : nullptr, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  c.packed = c.paged = c.windowed = true, c.window = window;
+  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
+  return attn_run("attention_q_paged_ragged_window", ATTN_PREFILL, c);
 }
 
 size_t lqer_attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D) {

@@ -26,6 +26,9 @@
 //                                   the sequences of a paged pool (lqer_attention_q_paged).  A third (RAG) also reads each sequence's
 //                                   number of query rows, and where they start in a packed [total][heads][D] tensor, from the device:
 //                                   a scheduler step of decoders and prompt chunks in one call (lqer_attention_q_paged_ragged).
+//                                   WIN, on either paged form, adds the sliding-window rule at compile time: query p sees keys
+//                                   p - W < j <= p, and the sweeps start at the first key tile the workgroup can see
+//                                   (lqer_attention_q_paged_window, lqer_attention_q_paged_ragged_window).
 #include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16: shared with attn_decode.hip
 
 namespace lqer {
@@ -52,6 +55,7 @@ struct Args {
   const int32_t* q_starts;  // RAG: [batch + 1] (device) - sequence b's query rows are tokens q_starts[b] .. q_starts[b + 1] - 1 of q / out
                             // [total][heads][D] (q_bs = o_bs = 0, q_rs / o_rs the token strides) and of stats [total][heads][2]; S above
                             // is then the bound max_s the grid's x comes from
+  int64_t window;  // WIN: W >= 1 - query i sees key j iff i + off - W < j <= i + off (read by no other instantiation)
 };
 
 template <int DT>
@@ -76,9 +80,15 @@ __global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v,
 // T - S, its sequence's own number of query tiles and their order - from the device, and finds its rows of q, out and the statistics
 // at token q_starts[b] + (row in the sequence).  The grid's x covers the bound max_s: a workgroup whose tile lies beyond its
 // sequence's S - every one of a sequence with S = 0 - leaves before any barrier, load or store.
-template <int DT, int DK, bool PSL = false, bool RAG = false>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
+// WIN (the sliding window, with PSL; the call is causal): the causal rule's three levels once more at the LOW end.  The workgroup's
+// sweeps start at key tile it0 = max(0, q0 + off - W + 1) / BT - no image tile below it is loaded, and the image kernels
+// (kv_cache.hip) have written none -, a wave skips a 32-key subtile that ends at or below w_begin = max(0, q0 + 32 wave + off - W + 1),
+// and a lane's register is visible iff its key is at or above tmin = max(0, qi + off - W + 1) as well: a SELECT wherever the causal
+// limit is tested - never a product with a mask, the image rows of dead keys may hold anything.
+template <int DT, int DK, bool PSL = false, bool RAG = false, bool WIN = false>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
 __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   static_assert(!RAG || PSL, "per-sequence query counts come with per-sequence lengths");
+  static_assert(!WIN || PSL, "the window rule runs on the paged forms");
   constexpr int KS = 64 * DK + 16;  // bytes of a key row in LDS (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
   constexpr int VS = 128 + 8;       // bytes of a V^T row (64 keys) in LDS (+8: the 8-byte reads of 32 rows hit 32 bank pairs)
   __shared__ __attribute__((aligned(16))) unsigned char sK[BT * KS];
@@ -136,6 +146,20 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
   int64_t tmax = T - 1;  // the last key visible to this lane's query
   if (a.mode == 2) tmax = qi + off < tmax ? qi + off : tmax;
+  int it0 = 0;                   // WIN: the first key tile some query of the workgroup sees
+  int64_t w_begin = 0, tmin = 0;  // ... the first key visible to the wave, to this lane's query
+  if constexpr (WIN) {
+    const int64_t g = q0 + off - a.window + 1, wb = g + wave * 32, lb = qi + off - a.window + 1;
+    it0 = g > 0 ? (int)(g / BT) : 0;
+    w_begin = wb > 0 ? wb : 0;
+    tmin = lb > 0 ? lb : 0;
+  }
+  // register r of the subtile at tb holds key tb + 4 lh + (r & 3) + 8 (r >> 2): visible iff that offset is <= lim (and, WIN, >= lim_lo)
+  auto vis = [](int r, int64_t lim_lo, int64_t lim) {
+    const int kr = (r & 3) + 8 * (r >> 2);
+    if constexpr (WIN) return lim_lo <= kr && kr <= lim;
+    else return kr <= lim;
+  };
   const int64_t qic = qi < S ? qi : S - 1;
   const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + qic * a.m_rs : 0;
 
@@ -221,8 +245,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
 
   // ---- sweep 1: row maximum and row sum of exp(S2 - maximum), per lane over its own keys, then across the lane pair
   float m = NEG_INF, l = 0.f;
-  Stage kr = fetch_k(0), vr;  // (nt = 0: rows 0-63 of the image exist)
-  for (int it = 0; it < nt; ++it) {
+  Stage kr = fetch_k(it0), vr;  // (nt = 0: rows 0-63 of the image exist)
+  for (int it = it0; it < nt; ++it) {
     __syncthreads();  // the previous tile's fragment reads are done
     put_k(kr);
     __syncthreads();
@@ -231,16 +255,18 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     for (int u = 0; u < 2; ++u) {
       const int64_t tb = (int64_t)it * BT + 32 * u;
       if (tb >= w_end) continue;  // wave-uniform: no key of the subtile is visible to the wave
+      if constexpr (WIN)
+        if (tb + 32 <= w_begin) continue;  // (the same at the window's low end)
       float s2[16];
       scores(tb, u, s2);
-      const int64_t lim = tmax - tb - 4 * lh;  // register r is visible iff (r & 3) + 8 (r >> 2) <= lim
+      const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh;  // register r is visible iff (WIN: lim_lo <=) (r & 3) + 8 (r >> 2) <= lim
       float tm = NEG_INF;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tm = (r & 3) + 8 * (r >> 2) <= lim ? fmaxf(tm, s2[r]) : tm;
+      for (int r = 0; r < 16; ++r) tm = vis(r, lim_lo, lim) ? fmaxf(tm, s2[r]) : tm;
       const float mn = fmaxf(m, tm), mref = mn == NEG_INF ? 0.f : mn;
       float ls = 0.f;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ls += (r & 3) + 8 * (r >> 2) <= lim ? exp_neg(s2[r] - mref) : 0.f;
+      for (int r = 0; r < 16; ++r) ls += vis(r, lim_lo, lim) ? exp_neg(s2[r] - mref) : 0.f;
       l = l * exp_neg(m - mref) + ls;
       m = mn;
     }
@@ -265,8 +291,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   for (int dt = 0; dt < DK; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-  kr = fetch_k(0), vr = fetch_v(0);
-  for (int it = 0; it < nt; ++it) {
+  kr = fetch_k(it0), vr = fetch_v(it0);
+  for (int it = it0; it < nt; ++it) {
     __syncthreads();
     put_k(kr);
     put_v(vr);
@@ -277,11 +303,13 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     for (int u = 0; u < 2; ++u) {
       const int64_t tb = (int64_t)it * BT + 32 * u;
       if (tb >= w_end) continue;
+      if constexpr (WIN)
+        if (tb + 32 <= w_begin) continue;
       float s2[16];
       scores(tb, u, s2);
-      const int64_t lim = tmax - tb - 4 * lh;
+      const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) s2[r] = (r & 3) + 8 * (r >> 2) <= lim ? rnd<DT>(exp_neg(s2[r] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
+      for (int r = 0; r < 16; ++r) s2[r] = vis(r, lim_lo, lim) ? rnd<DT>(exp_neg(s2[r] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {  // registers 8 s .. 8 s + 7: keys tb + 16 s + {0-3, 8-11} + 4 lh - half a block of 16, one k-step of P V
         const float v8[8] = {s2[8 * s], s2[8 * s + 1], s2[8 * s + 2], s2[8 * s + 3], s2[8 * s + 4], s2[8 * s + 5], s2[8 * s + 6], s2[8 * s + 7]};
@@ -332,20 +360,25 @@ static int launch(const AttnCall& c, Args a) {
   a.mvec = a.mode == 1 && a.T % 4 == 0 && (uintptr_t)a.mask % (4 * esz) == 0 && a.m_bs % 4 == 0 && a.m_hs % 4 == 0 && a.m_rs % 4 == 0;
   const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)c.batch);
   const int dk = (int)((a.D + 31) / 32);
-  const auto go = [&](auto psl, auto rag) {
-    constexpr bool PSL = decltype(psl)::value, RAG = decltype(rag)::value;
+  const auto go = [&](auto psl, auto rag, auto win) {
+    constexpr bool PSL = decltype(psl)::value, RAG = decltype(rag)::value, WIN = decltype(win)::value;
     switch (dk) {
-      case 1: k_attn_q<DT, 1, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      case 2: k_attn_q<DT, 2, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      case 3: k_attn_q<DT, 3, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      default: k_attn_q<DT, 4, PSL, RAG><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 1: k_attn_q<DT, 1, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 2: k_attn_q<DT, 2, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      case 3: k_attn_q<DT, 3, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      default: k_attn_q<DT, 4, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
     }
   };
   const bool ragged = c.paged && c.pool.ragged;  // (a.S: the bound max_s - the grid's x; the kernel takes S from q_starts)
-  if (ragged) go(std::true_type{}, std::true_type{});
-  else if (c.paged) go(std::true_type{}, std::false_type{});
-  else go(std::false_type{}, std::false_type{});
-  return check_launch(ragged ? "lqer_attention_q_paged_ragged" : c.paged ? "lqer_attention_q_paged" : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));
+  const bool win = c.paged && c.windowed;        // (the two _window entries: causal, W >= 1 - the check's)
+  if (ragged && win) go(std::true_type{}, std::true_type{}, std::true_type{});
+  else if (win) go(std::true_type{}, std::false_type{}, std::true_type{});
+  else if (ragged) go(std::true_type{}, std::true_type{}, std::false_type{});
+  else if (c.paged) go(std::true_type{}, std::false_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{}, std::false_type{});
+  return check_launch(ragged ? (win ? "lqer_attention_q_paged_ragged_window" : "lqer_attention_q_paged_ragged")
+                      : c.paged ? (win ? "lqer_attention_q_paged_window" : "lqer_attention_q_paged")
+                                : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));
 }
 
 }  // namespace attn
@@ -379,6 +412,7 @@ int attention_q_dispatch(const AttnCall& c) {
   a.qvec = a.mvec = false;  // (attn::launch sets them)
   a.lens = c.paged ? c.pool.lens : nullptr;  // (paged: c.T is the bound max_len - the images' strides; the kernels take T from lens[b])
   a.q_starts = c.paged && c.pool.ragged ? c.pool.starts : nullptr;  // (ragged: c.S is the bound max_s, qs / os hold {0, head, token})
+  a.window = c.paged && c.windowed ? c.window : 0;
   if (c.packed) kv_cache_images_dispatch(c, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv);
   return with_dtype(c.dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(c, a); });
 }

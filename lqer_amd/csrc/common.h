@@ -941,7 +941,7 @@ struct AttnCall {
   const int64_t *qs, *ks, *vs, *ms, *os;  // elements over batch / head / row (ms: only with a mask)
   float scaling;
   int causal;
-  bool windowed;   // a sliding window over the causal rule (lqer_attention_q_decode_paged_window): query p sees keys p - window < j <= p
+  bool windowed;   // a sliding window over the causal rule (the _window entries, decode and prefill): query p sees keys p - window < j <= p
   int64_t window;
   const lqer_qfmt_t *q_fmt, *k_fmt, *p_fmt, *v_fmt;  // Q_x0, Q_w0, Q_x1, Q_w1
   void* workspace;

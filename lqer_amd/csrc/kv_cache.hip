@@ -14,7 +14,9 @@
 //   k_kv_kimage / k_kv_vimage   the cache -> the two bf16 images k_attn_q reads (attn_q.hip; what k_attn_kimage / k_attn_vimage write from
 //                the raw K and V): codes16_to_bf16 on 16 codes per 16-byte load, zeros wherever the raw image kernels write their
 //                padding - every key at or beyond T, every d at or beyond D.  Nothing of the cache at or beyond key T reaches an image.
-//                From the pool: T = lens[b] per sequence of the call (lqer_attention_q_paged).
+//                From the pool: T = lens[b] per sequence of the call (lqer_attention_q_paged).  With the window rule (WIN:
+//                lqer_attention_q_paged_window, lqer_attention_q_paged_ragged_window) nothing of the pool below the page of the first
+//                key the call's first query row sees is read either: tiles wholly below it are not written, the rest of its tile is zeros.
 #include "kv_pack.h"
 
 namespace lqer {
@@ -229,15 +231,29 @@ struct IArgs {
   bf16_t *kimg, *vimg;  // [Z][Tp][Dp], [Z][ATTN_V_ROWS][Tv]
   int64_t D, T, Tp, Dp, Tv;
   QP qk, qv;
+  // WIN (the paged pool under the sliding window): W, and the query rows of a sequence - S, or (per-sequence counts) q_starts on the device
+  int64_t window, S;
+  const int32_t* q_starts;
 };
+
+// WIN: the first key sequence b's first query row sees, lo = max(0, T - S_b - W + 1) - no query of the call sees a key below it.  The
+// images are written from the 64-key tile that holds lo on (k_attn_q's first tile of the sequence): zeros below 16 (lo / 16) - WITH NO
+// TABLE ENTRY AND NO PAGE READ, those pages may have been released and serve another sequence; zeros and not nothing, because 0 x stale
+// in the P V product must be 0 and not NaN -, the converted codes from there on.
+__device__ __forceinline__ int64_t window_lo(const IArgs& a, int64_t b, int64_t T) {
+  const int64_t S = a.q_starts ? (int64_t)(a.q_starts[b + 1] - a.q_starts[b]) : a.S, lo = T - S - a.window + 1;
+  return lo > 0 ? lo : 0;
+}
 
 // K image: the codes' own layout, no transpose.  A thread: 16 d of one key - 16 code bytes, the 16 exponent bytes of (block of keys, d),
 // 32 bytes of the image row; consecutive threads, consecutive pieces of the row.  grid.x covers Tp (Dp / 16) exactly (a multiple of 512).
 // SRC_PAGED: the block of 16 keys is found through the sequence's row of the page table - one entry per thread, the two loads one round
 // trip behind it - and keys at and beyond lens[b] are zeros up to the end of the 64-key tile k_attn_q reads last; a workgroup (32 or 64
 // keys) that starts beyond that tile writes nothing and leaves at once: a short sequence of a ragged batch costs its own keys.
-template <int SRC>
+// WIN: a workgroup whose keys all lie below the tile of lo (window_lo) leaves too, and keys below lo's page are zeros, unread.
+template <int SRC, bool WIN = false>
 __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
+  static_assert(!WIN || SRC == attn::SRC_PAGED, "the window rule runs on the paged pool");
   const int64_t z = blockIdx.y, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int dq = (int)(a.Dp / 16);
   const int64_t t = i / dq;
@@ -247,8 +263,14 @@ __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
   const int64_t T = seq<SRC>(a.src, z / a.src.kvh, a.T, prow);
   if constexpr (SRC == attn::SRC_PAGED)
     if ((int64_t)blockIdx.x * (256 / dq) >= (T + 63) / 64 * 64) return;  // (uniform over the workgroup; the kernel has no barrier)
+  int64_t live = 0;  // WIN: the first key read - the start of lo's page
+  if constexpr (WIN) {
+    const int64_t lo = window_lo(a, z / a.src.kvh, T);
+    if ((int64_t)(blockIdx.x + 1) * (256 / dq) <= lo / 64 * 64) return;  // (uniform over the workgroup)
+    live = lo / 16 * 16;
+  }
   uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (t < T && d0 < a.D) {
+  if (t < T && d0 < a.D && (!WIN || t >= live)) {
     const int64_t blk = block<SRC>(a.src, prow, z, g, t / 16);
     const uint4 c = *(const uint4*)(a.src.kc + (blk * 16 + t % 16) * a.D + d0), e = *(const uint4*)(a.src.ke + blk * a.D + d0);
     const uint32_t eb[4] = {e.x, e.y, e.z, e.w};
@@ -272,8 +294,11 @@ __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
 // conflict-free.
 // SRC_PAGED: T = lens[b]; the four keys of a thread lie in one page - one table entry, the five loads one round trip behind it; a
 // workgroup whose 64 keys start at or beyond T (a tile k_attn_q does not read for this sequence) leaves before the barrier.
-template <int SRC>
+// WIN: so does a workgroup whose 64 keys lie below the tile of lo (window_lo); the four keys of a thread lie in one page, below lo's -
+// zeros, nothing read - or not.
+template <int SRC, bool WIN = false>
 __global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
+  static_assert(!WIN || SRC == attn::SRC_PAGED, "the window rule runs on the paged pool");
   __shared__ __attribute__((aligned(16))) unsigned char tile[ATTN_V_ROWS * 128];
   static_assert(ATTN_V_ROWS == 128, "the thread maps below cover 8 blocks of 16 d");
   const int tid = threadIdx.x;
@@ -283,6 +308,12 @@ __global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
   const int64_t T = seq<SRC>(a.src, z / a.src.kvh, a.T, prow);
   if constexpr (SRC == attn::SRC_PAGED)
     if (t0 >= T) return;  // (uniform over the workgroup)
+  int64_t live = 0;  // WIN: the first key read - the start of lo's page
+  if constexpr (WIN) {
+    const int64_t lo = window_lo(a, z / a.src.kvh, T);
+    if (t0 + 64 <= lo / 64 * 64) return;  // (uniform over the workgroup, before the barrier)
+    live = lo / 16 * 16;
+  }
   {
     const int db = tid & 7, tg = tid >> 3;
     const int64_t t = t0 + 4 * tg;
@@ -291,7 +322,7 @@ __global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int j = 0; j < 8; ++j) w[r][j] = 0;
-    if (16 * db < a.D && t < T) {  // (t < T <= cap, t a multiple of 4: the dword of exponents lies inside the section)
+    if (16 * db < a.D && t < T && (!WIN || t >= live)) {  // (t < T <= cap, t a multiple of 4: the dword of exponents lies inside the section)
       uint4 c[4];
       const uint32_t e4 = load_v4(a.src, block<SRC>(a.src, prow, z, g, t / 16), t, T, (int)a.D, db, c);
 #pragma unroll
@@ -405,8 +436,12 @@ void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64
   a.src = kvc::src_of(c);
   a.kimg = kimg, a.vimg = vimg, a.D = c.D, a.T = c.T, a.Tp = Tp, a.Dp = Dp, a.Tv = Tv;
   a.qk = make_qp(*c.k_fmt), a.qv = make_qp(*c.v_fmt);
+  a.window = c.window, a.S = c.S, a.q_starts = c.paged && c.pool.ragged ? c.pool.starts : nullptr;  // (read by the WIN kernels alone)
   const dim3 kgrid((unsigned)(Tp * (Dp / 16) / 256), (unsigned)(c.batch * c.kv_heads)), vgrid((unsigned)(Tv / 64), (unsigned)(c.batch * c.kv_heads));
-  if (c.paged) {
+  if (c.paged && c.windowed) {
+    kvc::k_kv_kimage<attn::SRC_PAGED, true><<<kgrid, 256, 0, c.st>>>(a);
+    kvc::k_kv_vimage<attn::SRC_PAGED, true><<<vgrid, 128, 0, c.st>>>(a);
+  } else if (c.paged) {
     kvc::k_kv_kimage<attn::SRC_PAGED><<<kgrid, 256, 0, c.st>>>(a);
     kvc::k_kv_vimage<attn::SRC_PAGED><<<vgrid, 128, 0, c.st>>>(a);
   } else {

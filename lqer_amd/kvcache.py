@@ -480,19 +480,33 @@ class PagedKVCache:
     n <= W + 7 keys a sequence holds at most (W + 37) // 16 pages (.pages_held(seq)).  Forks share pages as ever: a released page
     goes back to the pool with its last owner.  The table's rows stay indexed by absolute key / 16 (no ring), so max_pages_per_seq
     still bounds a sequence's total length.  The early keys of a sequence that has released pages are gone: to_dense() and
-    dequantized() raise ValueError for it."""
+    dequantized() raise ValueError for it.
+
+    max_query_rows=R (None: 8, and everything above as it stands; else an int >= 8): the most query rows per sequence a later
+    attention call may bring.  It switches on the prefill kernel's window rule - attention_flexible_paged(kernel="prefill" / "auto")
+    and the prefill call of attention_flexible_paged_ragged beyond the window (lqer_attention_q_paged_window,
+    lqer_attention_q_paged_ragged_window): a long prompt in chunks, a second turn, a prompt chunk beside windowed decoders - and it
+    widens what `append` keeps: a sequence gives up the pages wholly below min(T_after - W - (R - 1), 16 (T_before // 16)); R = 8 is
+    the rule above, term for term.  Two facts, for appends of at most W + R - 1 keys each:
+      - after such an append a sequence holds at most (W + R + 29) // 16 pages, and the bound is reached (R = 8: (W + 37) // 16);
+      - for every later call of s <= R rows on a sequence of T keys, 16 released <= max(0, T - s - W + 1): the page of the first key
+        the call's first row sees is still there.  A call that breaks it (more rows than R) raises ValueError: the keys are gone.
+    With window=None nothing is ever released, and R only allows an explicit window= on the prefill route."""
 
     covers = staticmethod(QuantizedKVCache.covers)
 
     def __init__(self, num_pages: int, max_seqs: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device,
-                 max_pages_per_seq=None, window=None):
+                 max_pages_per_seq=None, window=None, max_query_rows=None):
         if not self.covers(cfg0, cfg1, head_dim, dtype):
             raise NotImplementedError(f"PagedKVCache: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
                                       "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
                                       "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
         if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
             raise ValueError(f"PagedKVCache: window {window!r} - None or a number of keys >= 1")
-        self.window = window
+        if max_query_rows is not None and (not isinstance(max_query_rows, int) or isinstance(max_query_rows, bool)
+                                           or max_query_rows < _ATTN_DECODE_MAX_S):
+            raise ValueError(f"PagedKVCache: max_query_rows {max_query_rows!r} - None or a number of query rows >= {_ATTN_DECODE_MAX_S}")
+        self.window, self.max_query_rows = window, max_query_rows
         self.pt = PageTable(num_pages, max_seqs, max_pages_per_seq)
         if kv_heads < 1 or kv_heads > _MAX_GRID_Z or max_seqs > _MAX_GRID_Z or self.pt.max_len > 1 << 30:
             raise ValueError(f"PagedKVCache: kv_heads {kv_heads}, max_seqs {max_seqs}, max_pages_per_seq {self.pt.max_pages_per_seq}")
@@ -572,7 +586,8 @@ class PagedKVCache:
                 continue
             t = self.pt.lengths[s]
             first = self.pt.released[s]
-            freed = self.pt.release(seq, min(t + c - self.window - 7, PAGE_KEYS * (t // PAGE_KEYS)))
+            rows = _ATTN_DECODE_MAX_S if self.max_query_rows is None else self.max_query_rows  # a later call's most query rows
+            freed = self.pt.release(seq, min(t + c - self.window - (rows - 1), PAGE_KEYS * (t // PAGE_KEYS)))
             if self.pt.released[s] != first:
                 undo.append((seq, first, freed))
         return undo
@@ -776,9 +791,12 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     attention - the query at position p sees keys p - W < j <= p, W keys including its own.  lqer_attention_q_decode_paged_window gives,
     per sequence, the bits of attention_flexible(..., attention_mask=M, kernel="decode") on the FULL raw K and V with M = 0 inside the
     window and torch.finfo(dtype).min outside, without reading a page wholly below the window - so it runs on sequences whose old pages
-    the cache has released.  On such sequences an explicit W must not exceed the cache's (the keys are gone).  The prefill kernel has
-    no window rule yet: kernel="prefill" (and "auto" beyond 8 rows) with a window is taken only while every addressed length is <= W,
-    where the rule changes nothing and nothing can have been released, and raises ValueError beyond."""
+    the cache has released.  On such sequences an explicit W must not exceed the cache's (the keys are gone).  kernel="prefill" (and
+    "auto" beyond 8 rows) with a window: while every addressed length is <= W the rule changes nothing, nothing can have been released
+    and the unwindowed call runs.  Beyond, a cache made with max_query_rows runs lqer_attention_q_paged_window - the prefill kernel's
+    window rule, the bits of attention_flexible(..., attention_mask=M, kernel="prefill") on the full raw K and V, no page below the
+    window read; a sequence that has released the page of the first key this call's first row sees (16 released > max(0, T - s - W +
+    1): more rows than the cache was made for) raises ValueError.  A cache without max_query_rows raises ValueError beyond W."""
     if kernel not in (KERNEL_DECODE, KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"attention_flexible_paged: kernel={kernel!r} - 'decode', 'prefill' or 'auto'")
     _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
@@ -814,10 +832,12 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
         if any(cache.pt.released[x] for x in slots) and (cache.window is None or window > cache.window):
             raise ValueError(f"attention_flexible_paged: window={window} on sequences that have released the pages below the cache's window of "
                              f"{cache.window} keys")
-        if prefill and max(lens) > window:
+        if prefill and max(lens) > window and cache.max_query_rows is None:
             raise ValueError(f"attention_flexible_paged: kernel='prefill' with window={window} and lengths {lens} - the prefill kernel has no window "
-                             "rule; it is taken while every length is <= the window")
-        if prefill:
+                             "rule on a cache made without max_query_rows; it is taken while every length is <= the window")
+        if prefill and max(lens) > window:
+            _keys_still_there("attention_flexible_paged", cache, seqs, slots, lens, [s] * b, window)
+        elif prefill:
             window = None  # (every length <= W: plain causal)
     if q.stride(3) != 1:
         q = q.contiguous()
@@ -829,7 +849,7 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     with torch.cuda.device(q.device):
         if ws is None:
             ws = ops.workspace(q.device, max(getattr(L, name + "_workspace_bytes")(b, h, cache.kv_heads, s, max_len, d), 16))
-        if window is not None:  # (the decode kernels with the window rule: the same arguments and workspace, plus W)
+        if window is not None:  # (the kernels with the window rule: the same arguments and workspace, plus W)
             name += "_window"
         _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), ob.data_ptr(),
                                     stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, cache.kv_heads, s, d,
@@ -843,9 +863,19 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
 RAGGED_PREFILL, RAGGED_DECODE = "lqer_attention_q_paged_ragged", "lqer_attention_q_decode_paged_ragged"
 
 
+def _keys_still_there(who, cache, seqs, slots, lens, counts, window) -> None:
+    """What the prefill kernel's window rule asks of the pool: the page of the first key a sequence's first query row sees is still
+    the sequence's."""
+    for seq, x, t, c in zip(seqs, slots, lens, counts):
+        if PAGE_KEYS * cache.pt.released[x] > max(0, t - c - window + 1):
+            raise ValueError(f"{who}: sequence {seq} of {t} keys has released its first {cache.pt.released[x]} pages, and {c} query rows under "
+                             f"window={window} start at key {max(0, t - c - window + 1)} - the keys are gone (the cache keeps them for up to "
+                             f"max_query_rows = {cache.max_query_rows} rows)")
+
+
 def _ragged_call(name, q, cache: PagedKVCache, slots, lens, counts, scaling, causal, out, stats, ws, window=None) -> None:
-    """One library call with per-sequence counts - RAGGED_PREFILL (the prefill kernel, any counts) or RAGGED_DECODE (the split-over-keys
-    kernels, counts up to 8, `window`: None or W) -: q / out [sum(counts), h, d] (any token and head strides), stats [sum(counts), h, 2]
+    """One library call with per-sequence counts - RAGGED_PREFILL (the prefill kernel, any counts; `window`: None, or W for
+    lqer_attention_q_paged_ragged_window) or RAGGED_DECODE (the split-over-keys kernels, counts up to 8, `window`: None or W) -: q / out [sum(counts), h, d] (any token and head strides), stats [sum(counts), h, 2]
     fp32 dense or None, for the sequences in `slots` with `lens` keys and `counts` query rows each.  max_len as
     attention_flexible_paged's prefill route: the longest addressed length rounded up to 128, capped at the table's room - tight,
     since no result depends on it."""
@@ -858,12 +888,15 @@ def _ragged_call(name, q, cache: PagedKVCache, slots, lens, counts, scaling, cau
             need = (L.lqer_attention_q_decode_paged_ragged_workspace_bytes(total, h, max_len, d) if decode else
                     L.lqer_attention_q_paged_ragged_workspace_bytes(len(slots), h, cache.kv_heads, max(counts), max_len, d))
             ws = ops.workspace(q.device, max(need, 16))
+        if not decode and window is not None:  # (the same arguments and workspace, plus W)
+            name += "_window"
         _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), out.data_ptr(),
                                     stats.data_ptr() if stats is not None else None, ops.dtype_code(q), len(slots), h,
                                     cache.kv_heads, cache._call_starts(counts), max(counts), total, d, _pair(q), _pair(out),
                                     float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]),
                                     ws.data_ptr(), ws.numel(), ops._stream(q.device),
-                                    *((0 if window is None else min(window, 1 << 62),) if decode else ())),
+                                    *((0 if window is None else min(window, 1 << 62),) if decode else
+                                      () if window is None else (min(window, 1 << 62),))),
                    name)
 
 
@@ -981,7 +1014,9 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     call's rows lie between are gathered and scattered by index on the device, once.  attention_flexible_paged_ragged.plan(cache,
     seqs, counts, kernel, window) names the calls without touching a device.
     `window` (default: the cache's) and every refusal are those of the route a sequence takes, in its words: the decode route has the
-    window rule, the prefill kernel is taken with a window only while every length it addresses is <= W.  ValueError before anything
+    window rule; the prefill call runs unwindowed while every length it addresses is <= W and, beyond, as
+    lqer_attention_q_paged_ragged_window on a cache made with max_query_rows (ValueError on any other, and for a sequence whose count
+    reaches below the pages it still holds - attention_flexible_paged's rule).  ValueError before anything
     is launched: len(counts) != len(seqs), a negative count, sum(counts) != q.shape[0], causal with counts[b] > length_b, an empty
     sequence with a count, an unknown or repeated sequence, a wrong dtype, device or head count.  ws: a uint8 workspace or None."""
     who = "attention_flexible_paged_ragged"
@@ -997,9 +1032,12 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     big = big[0] if big else []
     if live:
         _ragged_released(who, cache, slots, live, eff_window)
-    if eff_window is not None and big and max(lens[b] for b in big) > eff_window:
+    big_window = eff_window if eff_window is not None and big and max(lens[b] for b in big) > eff_window else None
+    if big_window is not None and cache.max_query_rows is None:
         raise ValueError(f"{who}: kernel='prefill' with window={eff_window} and lengths {[lens[b] for b in big]} - the prefill kernel has no "
-                         "window rule; it is taken while every length is <= the window")
+                         "window rule on a cache made without max_query_rows; it is taken while every length is <= the window")
+    if big_window is not None:
+        _keys_still_there(who, cache, [seqs[b] for b in big], [slots[b] for b in big], [lens[b] for b in big], [counts[b] for b in big], big_window)
     if big and (max(lens[b] for b in big) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
         raise ValueError(f"{who}: {len(big)} sequences of lengths {[lens[b] for b in big]} beyond the prefill kernel's launch grid")
     if q.stride(2) != 1:
@@ -1019,7 +1057,7 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     idx = torch.tensor(rows, dtype=torch.int64).to(q.device) if rows else None
     for (name, bs, _), at in zip(plan, where):
         args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], [counts[b] for b in bs], scaling, causal)
-        win = eff_window if name == RAGGED_DECODE else None  # (the prefill call: every length <= W, plain causal)
+        win = eff_window if name == RAGGED_DECODE else big_window  # (the prefill call while every length <= W: plain causal)
         if isinstance(at, slice):  # (in place: nothing to copy)
             _ragged_call(name, q[at], *args, out[at], stats[at] if return_stats else None, ws, win)
             continue
@@ -1036,17 +1074,29 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
 
 def _plan(cache: PagedKVCache, seqs, counts, kernel=KERNEL_AUTO, window=None) -> list:
     """The library calls attention_flexible_paged_ragged(q, cache, seqs, counts, ..., kernel=kernel, window=window) makes, in order,
-    from host state alone (no device is touched, no length is read): one dict per call - "call": the C entry, "seqs": the indices into
-    `seqs` of the sequences it takes, "rows": "view" when their rows are one range of q and the call runs on views of q and out,
-    "gathered" when they are gathered and scattered by index, "window": the window rule it runs under (None: none; the prefill
-    call has no rule).  Each call is three launches.  Refuses an unknown `kernel`, a bad `window` and bad counts as the function does."""
+    from host state alone (no device is touched): one dict per call - "call": the C entry, "seqs": the indices into `seqs` of the
+    sequences it takes, "rows": "view" when their rows are one range of q and the call runs on views of q and out, "gathered" when
+    they are gathered and scattered by index, "window": the window rule it runs under (None: none).  The prefill call has a rule
+    only on a cache made with max_query_rows, and only when a length it addresses - read from the host's books, which then must know
+    `seqs` - lies beyond the window: it is then lqer_attention_q_paged_ragged_window.  On any other cache no length is read.  Each
+    call is three launches.  Refuses an unknown `kernel`, a bad `window` and bad counts as the function does."""
     who = "attention_flexible_paged_ragged"
     if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
     eff_window = _ragged_window(who, cache, window, True)
     seqs, counts = _ragged_counts(who, seqs, counts)
-    return [{"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered", "window": eff_window if name == RAGGED_DECODE else None}
-            for name, bs, at in _ragged_plan(counts, kernel)[0]]
+    out = []
+    for name, bs, at in _ragged_plan(counts, kernel)[0]:
+        win = eff_window if name == RAGGED_DECODE else None
+        if name == RAGGED_PREFILL and eff_window is not None and cache.max_query_rows is not None:
+            try:
+                lens = [cache.pt.lengths[x] for x in cache.pt.slots([seqs[b] for b in bs])]
+            except KeyError as e:
+                raise ValueError(e.args[0]) from None
+            if max(lens) > eff_window:
+                name, win = name + "_window", eff_window
+        out.append({"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered", "window": win})
+    return out
 
 
 attention_flexible_paged_ragged.plan = _plan
