@@ -62,6 +62,18 @@ _vp, _i, _i64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 _qp, _dp = C.POINTER(QFmt), C.POINTER(LinearDesc)
 _sp = C.POINTER(C.c_int64)  # a stride triple
 
+# the pieces of the paged pool's argument lists (include/lqer_hip.h "paged KV pool"):
+# pool, bytes, pages, slots, block_table, table_stride, then the call's seq_slots, lens, max_len
+_POOL = [_vp, _sz, _i64, _i64, _vp, _i64] + [_vp, _vp, _i64]
+# k_new, v_new, two stride triples (ragged: pairs), dtype, batch, kv_heads, D, n (ragged: total), the K and V formats, stream
+_APPEND = [_vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64, _qp, _qp, _vp]
+# q, the pool, out, row_stats, dtype, batch, heads, kv_heads | S or (q_starts, max_s, total) | D, the strides of q and out (triples,
+# ragged: pairs), scaling, causal, four formats, workspace, bytes, stream
+_PAGED_HEAD = [_vp] + _POOL + [_vp, _vp, _i, _i64, _i64, _i64]
+_PAGED_TAIL = [_i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]
+_PAGED = _PAGED_HEAD + [_i64] + _PAGED_TAIL
+_PAGED_RAGGED = _PAGED_HEAD + [_vp, _i64, _i64] + _PAGED_TAIL
+
 # name -> (restype, argtypes); must list every symbol declared in include/lqer_hip.h
 SIGNATURES = {
     "lqer_version": (_i, []),
@@ -149,38 +161,30 @@ SIGNATURES = {
                                  _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
     # the paged KV pool (csrc/kv_cache.hip, csrc/attn_decode.hip): pages of 16 keys, a block table, per-sequence lengths on the device
     "lqer_kv_pool_bytes": (_sz, [_i, _i64, _i64, _i64, _i64]),
-    "lqer_kv_pool_append": (_i, [_vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64, _qp, _qp, _vp]),
+    "lqer_kv_pool_append": (_i, _POOL + _APPEND),
     "lqer_kv_pool_gather": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _i64, _vp]),
     # pool, bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, src_slots, dst_slots, lens, pairs, stream
     "lqer_kv_pool_fork": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "lqer_attention_q_decode_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
-    "lqer_attention_q_decode_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
-                                           _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    "lqer_attention_q_decode_paged": (_i, _PAGED),
     # ... with a sliding window over the causal rule: the same argument list plus `window`
-    "lqer_attention_q_decode_paged_window": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64,
-                                                  _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
+    "lqer_attention_q_decode_paged_window": (_i, _PAGED + [_i64]),
     # ... for any number of query rows: the prefill kernel on images written from the pool through the block table, T = lens[b]
     "lqer_attention_q_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
-    "lqer_attention_q_paged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
-                                    _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
+    "lqer_attention_q_paged": (_i, _PAGED),
     # ... with the sliding-window rule in k_attn_q and the image kernels: the same list plus `window`
-    "lqer_attention_q_paged_window": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _sp,
-                                           _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
+    "lqer_attention_q_paged_window": (_i, _PAGED + [_i64]),
     # per-sequence token counts in one call (a mixed prefill / decode step): new_starts / q_starts [batch + 1] on the device, a host bound
     # on the counts, packed [total][heads][D] tensors through stride PAIRS (token, head)
-    "lqer_kv_pool_append_ragged": (_i, [_vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sp, _sp, _i, _i64, _i64, _i64, _i64,
-                                        _qp, _qp, _vp]),
+    "lqer_kv_pool_append_ragged": (_i, _POOL + [_vp, _i64] + _APPEND),
     "lqer_attention_q_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     # lqer_attention_q_paged's list with S -> (q_starts, max_s, total)
-    "lqer_attention_q_paged_ragged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64, _i64,
-                                           _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp]),
-    "lqer_attention_q_paged_ragged_window": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64,
-                                                  _i64, _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
+    "lqer_attention_q_paged_ragged": (_i, _PAGED_RAGGED),
+    "lqer_attention_q_paged_ragged_window": (_i, _PAGED_RAGGED + [_i64]),
     # ... for counts of up to 8 rows on the split-over-keys kernels (csrc/attn_decode.hip): the same list plus `window` (0: none); the
     # workspace follows (total, heads, max_len, D)
     "lqer_attention_q_decode_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
-    "lqer_attention_q_decode_paged_ragged": (_i, [_vp, _vp, _sz, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64,
-                                                  _i64, _i64, _sp, _sp, C.c_float, _i, _qp, _qp, _qp, _qp, _vp, _sz, _vp, _i64]),
+    "lqer_attention_q_decode_paged_ragged": (_i, _PAGED_RAGGED + [_i64]),
 }
 
 _lib: Optional[C.CDLL] = None

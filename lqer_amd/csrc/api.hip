@@ -1597,6 +1597,12 @@ static int kv_pool_check(const char* who, const KvPool& p, PoolUse use) {
   return LQER_OK;
 }
 
+// the pool record from the arguments every pool call has, in the order the ABI lists them (no per-sequence counts: the caller's to add)
+static KvPool kv_pool(const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                      const int32_t* seq_slots, const int32_t* lens, int64_t max_len, int dtype, int64_t kv_heads, int64_t D) {
+  return {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+}
+
 int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
                         const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const void* k_new, const void* v_new,
                         const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t n,
@@ -1605,7 +1611,7 @@ int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t sl
     set_error("kv_pool_append: batch %lld / %lld new keys for the KV pool (batch >= 0, at least one new key)", (long long)batch, (long long)n);
     return LQER_E_INVALID;
   }
-  const KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  const KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
   int rc = kv_codes_check("kv_pool_append", D, k_fmt, v_fmt);
   if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append", p, POOL_BATCH);
   if (rc != LQER_OK) return rc;
@@ -1635,7 +1641,7 @@ int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int
               (long long)batch, (long long)max_n);
     return LQER_E_INVALID;
   }
-  KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
+  KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
   p.ragged = true, p.starts = new_starts, p.total = total;
   int rc = kv_codes_check("kv_pool_append_ragged", D, k_fmt, v_fmt);
   if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append_ragged", p, POOL_BATCH);
@@ -1666,7 +1672,7 @@ int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t 
               (long long)T, (long long)capacity);
     return LQER_E_INVALID;
   }
-  const KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, nullptr, nullptr, table_stride, T > 0 ? T : 1};
+  const KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, nullptr, nullptr, T > 0 ? T : 1, dtype, kv_heads, D);
   const int rc = kv_pool_check("kv_pool_gather", p, POOL_ONE_SLOT);
   if (rc != LQER_OK) return rc;
   if (!cache || (uintptr_t)cache % 16 != 0 || cache_bytes < kv_cache_bytes(dtype, 1, kv_heads, capacity, D)) {
@@ -1694,7 +1700,7 @@ int lqer_kv_pool_fork(void* pool, size_t pool_bytes, int dtype, int64_t pages, i
   }
   // the bound on the lengths is the room of a table row, or the library's 2^30 where the row has more
   const int64_t room = table_stride < ((int64_t)1 << 26) ? 16 * table_stride : (int64_t)1 << 30;
-  const KvPool p = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, dst_slots, lens, table_stride, room};
+  const KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, dst_slots, lens, room, dtype, kv_heads, D);
   const int rc = kv_pool_check("kv_pool_fork", p, POOL_BATCH);
   if (rc != LQER_OK) return rc;
   if (n > (((int64_t)1 << 31) - 1) / kv_heads) {  // (a workgroup pair per (pair, kv head) over grid.x)
@@ -1781,17 +1787,39 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
   return attn_run("attention_q_kv", ATTN_PREFILL, c);
 }
 
+// The record of an attention call over the pool from the arguments all seven entries have, in the ABI's order (no mask; T: the bound max_len -
+// the check's, the workspace's).  Built in place, never copied: with per-sequence counts it points into the stride triples it holds.
+struct PagedAttn {
+  AttnCall c;
+  int64_t qs[3], os[3];
+  PagedAttn(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+            const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+            int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+            const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+            size_t workspace_bytes, void* stream)
+      : c(attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
+                    k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream)) {
+    c.packed = c.paged = true;
+    c.pool = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
+  }
+  PagedAttn(const PagedAttn&) = delete;
+  // per-sequence counts: a stride pair (token, head) becomes the triple (batch, head, row) the record holds, with no batch stride - a
+  // sequence's rows start at its token starts[b]; null strides stay null, for the check to refuse
+  void ragged(const int32_t* starts, int64_t total) {
+    c.pool.ragged = true, c.pool.starts = starts, c.pool.total = total;
+    c.qs = triple(qs, c.qs), c.os = triple(os, c.os);
+  }
+  static const int64_t* triple(int64_t (&t)[3], const int64_t* pair) { return pair ? (t[0] = 0, t[1] = pair[1], t[2] = pair[0], t) : nullptr; }
+};
+
 int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                                   int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
                                   int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
                                   const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                                   const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
-  // (no mask; T: the bound max_len - the check's, the workspace's)
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
-                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = true;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  return attn_run("attention_q_decode_paged", ATTN_DECODE, c);
+  const PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads,
+                    kv_heads, S, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  return attn_run("attention_q_decode_paged", ATTN_DECODE, a.c);
 }
 
 int lqer_attention_q_decode_paged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
@@ -1800,12 +1828,10 @@ int lqer_attention_q_decode_paged_window(const void* q, const void* pool, size_t
                                          const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
                                          const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
                                          size_t workspace_bytes, void* stream, int64_t window) {
-  // (the call above with the window rule; grid and workspace still follow max_len)
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
-                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = c.windowed = true, c.window = window;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  return attn_run("attention_q_decode_paged_window", ATTN_DECODE, c);
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads, S,
+              D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.c.windowed = true, a.c.window = window;  // (the call above with the window rule; grid and workspace still follow max_len)
+  return attn_run("attention_q_decode_paged_window", ATTN_DECODE, a.c);
 }
 
 size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
@@ -1817,12 +1843,9 @@ int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, i
                            int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides,
                            const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                            const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream) {
-  // (no mask; T: the bound max_len - the check's, the workspace's)
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
-                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = true;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  return attn_run("attention_q_paged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
+  const PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads,
+                    kv_heads, S, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  return attn_run("attention_q_paged", ATTN_PREFILL, a.c);  // (the prefill kernel's limits and workspace at T = max_len)
 }
 
 int lqer_attention_q_paged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
@@ -1831,12 +1854,10 @@ int lqer_attention_q_paged_window(const void* q, const void* pool, size_t pool_b
                                   const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                                   const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream,
                                   int64_t window) {
-  // (the call above with the window rule; grid and workspace still follow max_len)
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, S, max_len, D, q_strides, nullptr, out_strides, scaling, causal, q_fmt,
-                         k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = c.windowed = true, c.window = window;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  return attn_run("attention_q_paged_window", ATTN_PREFILL, c);
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads, S,
+              D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.c.windowed = true, a.c.window = window;  // (the call above with the window rule; grid and workspace still follow max_len)
+  return attn_run("attention_q_paged_window", ATTN_PREFILL, a.c);
 }
 
 size_t lqer_attention_q_paged_ragged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t max_s, int64_t max_len, int64_t D) {
@@ -1849,16 +1870,11 @@ int lqer_attention_q_paged_ragged(const void* q, const void* pool, size_t pool_b
                                   int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
                                   const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-  // the stride pairs (token, head) as the triples (batch, head, row) the record holds: no batch stride - a sequence's rows start at
-  // its token q_starts[b]; S: the bound max_s - the check's, the grid's
-  const int64_t qs[3] = {0, q_strides ? q_strides[1] : 0, q_strides ? q_strides[0] : 0};
-  const int64_t os[3] = {0, out_strides ? out_strides[1] : 0, out_strides ? out_strides[0] : 0};
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, max_s, max_len, D, q_strides ? qs : nullptr, nullptr,
-                         out_strides ? os : nullptr, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = true;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
-  return attn_run("attention_q_paged_ragged", ATTN_PREFILL, c);  // (the prefill kernel's limits and workspace at T = max_len)
+  // (S: the bound max_s - the check's, the grid's)
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads,
+              max_s, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.ragged(q_starts, total);
+  return attn_run("attention_q_paged_ragged", ATTN_PREFILL, a.c);  // (the prefill kernel's limits and workspace at T = max_len)
 }
 
 int lqer_attention_q_paged_ragged_window(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
@@ -1868,15 +1884,11 @@ int lqer_attention_q_paged_ragged_window(const void* q, const void* pool, size_t
                                          const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
                                          const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
                                          void* workspace, size_t workspace_bytes, void* stream, int64_t window) {
-  // (the call above with the window rule, every sequence by its own count)
-  const int64_t qs[3] = {0, q_strides ? q_strides[1] : 0, q_strides ? q_strides[0] : 0};
-  const int64_t os[3] = {0, out_strides ? out_strides[1] : 0, out_strides ? out_strides[0] : 0};
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, max_s, max_len, D, q_strides ? qs : nullptr, nullptr,
-                         out_strides ? os : nullptr, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = c.windowed = true, c.window = window;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
-  return attn_run("attention_q_paged_ragged_window", ATTN_PREFILL, c);
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads,
+              max_s, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.ragged(q_starts, total);
+  a.c.windowed = true, a.c.window = window;  // (the call above with the window rule, every sequence by its own count)
+  return attn_run("attention_q_paged_ragged_window", ATTN_PREFILL, a.c);
 }
 
 size_t lqer_attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D) {
@@ -1891,16 +1903,13 @@ int lqer_attention_q_decode_paged_ragged(const void* q, const void* pool, size_t
                                          const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
                                          const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
                                          void* workspace, size_t workspace_bytes, void* stream, int64_t window) {
-  // the call above on the decode kernels: the stride pairs as triples without a batch stride, S the bound max_s (here <= 8), and the
-  // window rule when window != 0 (a negative one is the check's to refuse)
-  const int64_t qs[3] = {0, q_strides ? q_strides[1] : 0, q_strides ? q_strides[0] : 0};
-  const int64_t os[3] = {0, out_strides ? out_strides[1] : 0, out_strides ? out_strides[0] : 0};
-  AttnCall c = attn_call(q, nullptr, out, row_stats, dtype, batch, heads, kv_heads, max_s, max_len, D, q_strides ? qs : nullptr, nullptr,
-                         out_strides ? os : nullptr, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
-  c.packed = c.paged = true, c.windowed = window != 0, c.window = window;
-  c.pool = {pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, seq_slots, lens, table_stride, max_len};
-  c.pool.ragged = true, c.pool.starts = q_starts, c.pool.total = total;
-  return attn_run("attention_q_decode_paged_ragged", ATTN_DECODE, c);
+  // the call above on the decode kernels: S the bound max_s (here <= 8), and the window rule when window != 0 (a negative one is the
+  // check's to refuse)
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads,
+              max_s, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.ragged(q_starts, total);
+  a.c.windowed = window != 0, a.c.window = window;
+  return attn_run("attention_q_decode_paged_ragged", ATTN_DECODE, a.c);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

@@ -84,6 +84,13 @@ def prefill_packed(q, buf, kv_heads, capacity, length, fmts, scaling, attention_
                     fmts=fmts, scaling=scaling, ws=ws)
 
 
+def _check_covers(who: str, cfg0: dict, cfg1: dict, head_dim: int, dtype: torch.dtype) -> None:
+    if not QuantizedKVCache.covers(cfg0, cfg1, head_dim, dtype):
+        raise NotImplementedError(f"{who}: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
+                                  "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
+                                  "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
+
+
 class QuantizedKVCache:
     """K and V of one attention layer as the codes and block exponents of the layer's two matmul configs (cfg0: Q K^T, cfg1: P V).
 
@@ -100,10 +107,7 @@ class QuantizedKVCache:
                 and dtype in ops._DT)
 
     def __init__(self, batch: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device, capacity: int = 256):
-        if not self.covers(cfg0, cfg1, head_dim, dtype):
-            raise NotImplementedError(f"QuantizedKVCache: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
-                                      "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
-                                      "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
+        _check_covers("QuantizedKVCache", cfg0, cfg1, head_dim, dtype)
         if batch < 1 or kv_heads < 1 or capacity < 1 or batch > _MAX_GRID_Z or kv_heads > _MAX_GRID_Z:
             raise ValueError(f"QuantizedKVCache: batch {batch}, kv_heads {kv_heads}, capacity {capacity}")
         self.batch, self.kv_heads, self.head_dim, self.dtype, self.device = batch, kv_heads, head_dim, dtype, torch.device(device)
@@ -113,8 +117,8 @@ class QuantizedKVCache:
         self.capacity = (capacity + 15) // 16 * 16
         self.buf = self._alloc(self.capacity)
 
-    def _alloc(self, capacity: int) -> torch.Tensor:
-        return torch.empty(cache_bytes(self.dtype, self.batch, self.kv_heads, capacity, self.head_dim), dtype=torch.uint8, device=self.device)
+    def _alloc(self, capacity: int, batch=None) -> torch.Tensor:
+        return torch.empty(cache_bytes(self.dtype, batch or self.batch, self.kv_heads, capacity, self.head_dim), dtype=torch.uint8, device=self.device)
 
     @property
     def nbytes(self) -> int:
@@ -127,19 +131,24 @@ class QuantizedKVCache:
         cap = self.capacity
         while cap < need:
             cap *= 2
-        new = self._alloc(cap)
-        old_s, _ = _sections(self.dtype, self.batch, self.kv_heads, self.capacity, self.head_dim)
-        new_s, _ = _sections(self.dtype, self.batch, self.kv_heads, cap, self.head_dim)
-        z, blocks = self.batch * self.kv_heads, (self.length + 15) // 16
+        self.buf, self.capacity = self._moved(self.batch, cap), cap
+
+    def _moved(self, new_batch: int, new_capacity: int, idx=None) -> torch.Tensor:
+        """A new buffer for new_batch rows of new_capacity keys with what lives in this one: both as [batch, kv_heads, row] per section,
+        the live blocks of the four code and exponent sections and the staging rows (one size at every capacity) - one copy each, of
+        the batch rows `idx` (an int64 tensor on the device) where given."""
+        new = self._alloc(new_capacity, new_batch)
+        hk = self.kv_heads
+        old_s, _ = _sections(self.dtype, self.batch, hk, self.capacity, self.head_dim)
+        new_s, _ = _sections(self.dtype, new_batch, hk, new_capacity, self.head_dim)
+        stage, blocks = 16 * self.head_dim * torch.empty((), dtype=self.dtype).element_size(), (self.length + 15) // 16
         for (_, o_at, per_block), (_, n_at, _) in zip(old_s, new_s):
-            if per_block is None:  # the staging rows: one size at every capacity
-                n = z * 16 * self.head_dim * torch.empty((), dtype=self.dtype).element_size()
-                new[n_at:n_at + n].copy_(self.buf[o_at:o_at + n])
-            elif blocks:
-                o_row, n_row = (self.capacity // 16) * per_block, (cap // 16) * per_block
-                src = self.buf[o_at:o_at + z * o_row].view(z, o_row)[:, :blocks * per_block]
-                new[n_at:n_at + z * n_row].view(z, n_row)[:, :blocks * per_block].copy_(src)
-        self.buf, self.capacity = new, cap
+            o_row, n_row = (stage, stage) if per_block is None else ((self.capacity // 16) * per_block, (new_capacity // 16) * per_block)
+            live = stage if per_block is None else blocks * per_block
+            if live:
+                src = self.buf[o_at:o_at + self.batch * hk * o_row].view(self.batch, hk, o_row)[:, :, :live]
+                new[n_at:n_at + new_batch * hk * n_row].view(new_batch, hk, n_row)[:, :, :live].copy_(src if idx is None else src.index_select(0, idx))
+        return new
 
     @torch.no_grad()
     def append(self, k: torch.Tensor, v: torch.Tensor) -> None:
@@ -168,23 +177,7 @@ class QuantizedKVCache:
         if idx.numel() < 1 or idx.numel() > _MAX_GRID_Z or int(idx.min()) < 0 or int(idx.max()) >= self.batch:
             raise ValueError(f"QuantizedKVCache.select: indices {idx.tolist()} for a batch of {self.batch}")
         idx = idx.to(self.device)
-        old_batch, old_buf, hk = self.batch, self.buf, self.kv_heads
-        self.batch = idx.numel()
-        try:
-            new = self._alloc(self.capacity)
-        except BaseException:
-            self.batch = old_batch
-            raise
-        old_s, _ = _sections(self.dtype, old_batch, hk, self.capacity, self.head_dim)
-        new_s, _ = _sections(self.dtype, self.batch, hk, self.capacity, self.head_dim)
-        blocks = (self.length + 15) // 16
-        for (_, o_at, per_block), (_, n_at, _) in zip(old_s, new_s):
-            row = 16 * self.head_dim * torch.empty((), dtype=self.dtype).element_size() if per_block is None else (self.capacity // 16) * per_block
-            live = row if per_block is None else blocks * per_block
-            if live:
-                src = old_buf[o_at:o_at + old_batch * hk * row].view(old_batch, hk, row)[:, :, :live]
-                new[n_at:n_at + self.batch * hk * row].view(self.batch, hk, row)[:, :, :live].copy_(src.index_select(0, idx))
-        self.buf = new
+        self.buf, self.batch = self._moved(idx.numel(), self.capacity, idx), idx.numel()
 
 
 @torch.no_grad()
@@ -497,12 +490,8 @@ class PagedKVCache:
 
     def __init__(self, num_pages: int, max_seqs: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device,
                  max_pages_per_seq=None, window=None, max_query_rows=None):
-        if not self.covers(cfg0, cfg1, head_dim, dtype):
-            raise NotImplementedError(f"PagedKVCache: head_dim {head_dim}, dtype {dtype} or the quantizers of these configs are outside the "
-                                      "packed cache (block_fp of width <= 8 with blocks of 16, head dims that are multiples of 16 up to 128, "
-                                      "fp32 / fp16 / bf16) - and a cache without the raw values has no other route")
-        if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
-            raise ValueError(f"PagedKVCache: window {window!r} - None or a number of keys >= 1")
+        _check_covers("PagedKVCache", cfg0, cfg1, head_dim, dtype)
+        _window_arg("PagedKVCache", window, None, causal=True)  # (no call, so no causal to ask for)
         if max_query_rows is not None and (not isinstance(max_query_rows, int) or isinstance(max_query_rows, bool)
                                            or max_query_rows < _ATTN_DECODE_MAX_S):
             raise ValueError(f"PagedKVCache: max_query_rows {max_query_rows!r} - None or a number of query rows >= {_ATTN_DECODE_MAX_S}")
@@ -561,11 +550,17 @@ class PagedKVCache:
         if n == 0 or not seqs:
             self.pt.slots(seqs)
             return
+        self._append(seqs, n, self._launch_append, k, v)
+
+    def _append(self, seqs, n, launch, k, v) -> None:
+        """The body of both appends, n an int or one count per sequence: release what the window lets go, reserve the pages of the
+        whole call, launch(slots, lengths before, pages taken per slot, k, v, n) - the caller's _launch_* as the instance has it now -,
+        commit the lengths - and, when the reservation or the launch is refused, the books as they were."""
         undo = self._release_outside_window(seqs, n) if self.window is not None else []
         try:
             slots, lens, taken = self.pt.reserve(seqs, n)  # (raises with nothing taken)
             try:
-                self._launch_append(slots, lens, taken, k, v, n)
+                launch(slots, lens, taken, k, v, n)
             except BaseException:
                 self.pt.rollback(slots, taken)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
                 raise
@@ -592,10 +587,14 @@ class PagedKVCache:
                 undo.append((seq, first, freed))
         return undo
 
-    def _launch_append(self, slots, lens, taken, k, v, n) -> None:
+    def _upload_rows(self, slots, taken) -> None:
+        """The table rows that took pages, to the device."""
         for s, t in zip(slots, taken):
             if t:
                 self.table[s].copy_(torch.tensor(self.pt.table[s], dtype=torch.int32))
+
+    def _launch_append(self, slots, lens, taken, k, v, n) -> None:
+        self._upload_rows(slots, taken)
         if k.stride(3) != 1:
             k = k.contiguous()
         if v.stride(3) != 1:
@@ -613,13 +612,7 @@ class PagedKVCache:
         sum(counts[:b]) .. + counts[b] - 1; a count of 0 leaves its sequence alone.  The pool's bytes afterwards are those of one
         append() per sequence.  Reservation, refusals, rollback and - on a window=W cache - the release of unseen pages, each
         sequence by its own count, are append()'s: a refused call leaves the books and the pool as they were."""
-        seqs = list(seqs)
-        try:
-            counts = [int(c) for c in counts]
-        except (TypeError, ValueError):
-            raise ValueError(f"PagedKVCache.append_ragged: counts {counts!r} - one count >= 0 per sequence") from None
-        if len(counts) != len(seqs) or any(c < 0 for c in counts):
-            raise ValueError(f"PagedKVCache.append_ragged: counts {counts} for {len(seqs)} sequences - one count >= 0 per sequence")
+        seqs, counts = _ragged_counts("PagedKVCache.append_ragged", seqs, counts)
         want = (sum(counts), self.kv_heads, self.head_dim)
         if k.dim() != 3 or tuple(k.shape) != want or k.shape != v.shape or k.dtype != self.dtype or v.dtype != self.dtype:
             raise ValueError(f"PagedKVCache.append_ragged: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} for counts {counts} of "
@@ -629,19 +622,7 @@ class PagedKVCache:
         if not any(counts):
             self.pt.slots(seqs)
             return
-        undo = self._release_outside_window(seqs, counts) if self.window is not None else []
-        try:
-            slots, lens, taken = self.pt.reserve(seqs, counts)  # (raises with nothing taken)
-            try:
-                self._launch_append_ragged(slots, lens, taken, k, v, counts)
-            except BaseException:
-                self.pt.rollback(slots, taken)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
-                raise
-        except BaseException:
-            for u in reversed(undo):
-                self.pt.unrelease(*u)
-            raise
-        self.pt.commit(slots, counts)
+        self._append(seqs, counts, self._launch_append_ragged, k, v)
 
     def _call_starts(self, counts):
         """The token starts [len(counts) + 1] of a call with per-sequence counts on the device: one copy, as _call_meta's."""
@@ -652,9 +633,7 @@ class PagedKVCache:
         return self._starts.data_ptr()
 
     def _launch_append_ragged(self, slots, lens, taken, k, v, counts) -> None:
-        for s, t in zip(slots, taken):
-            if t:
-                self.table[s].copy_(torch.tensor(self.pt.table[s], dtype=torch.int32))
+        self._upload_rows(slots, taken)
         if k.stride(2) != 1:
             k = k.contiguous()
         if v.stride(2) != 1:
@@ -800,12 +779,7 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     if kernel not in (KERNEL_DECODE, KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"attention_flexible_paged: kernel={kernel!r} - 'decode', 'prefill' or 'auto'")
     _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
-    if window is None:
-        window = cache.window
-    elif not isinstance(window, int) or isinstance(window, bool) or window < 1:
-        raise ValueError(f"attention_flexible_paged: window {window!r} - None or a number of keys >= 1")
-    if window is not None and not causal:
-        raise ValueError(f"attention_flexible_paged: window={window} without causal=True - the window is a rule on top of the causal one")
+    window = _window_arg("attention_flexible_paged", window, cache.window, causal)
     seqs = list(seqs)
     if q.dim() != 4:
         raise ValueError(f"attention_flexible_paged: q {tuple(q.shape)} is not [len(seqs), h, s, d]")
@@ -829,85 +803,95 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
         raise ValueError(f"attention_flexible_paged: lengths {lens} of sequences {seqs} - an empty sequence has nothing to attend to"
                          + (f", and causal needs {s} query rows <= every length" if causal else ""))
     if window is not None:
-        if any(cache.pt.released[x] for x in slots) and (cache.window is None or window > cache.window):
-            raise ValueError(f"attention_flexible_paged: window={window} on sequences that have released the pages below the cache's window of "
-                             f"{cache.window} keys")
-        if prefill and max(lens) > window and cache.max_query_rows is None:
-            raise ValueError(f"attention_flexible_paged: kernel='prefill' with window={window} and lengths {lens} - the prefill kernel has no window "
-                             "rule on a cache made without max_query_rows; it is taken while every length is <= the window")
-        if prefill and max(lens) > window:
-            _keys_still_there("attention_flexible_paged", cache, seqs, slots, lens, [s] * b, window)
-        elif prefill:
-            window = None  # (every length <= W: plain causal)
+        _released_below("attention_flexible_paged", cache, slots, window)
+        if prefill:
+            window = _prefill_window("attention_flexible_paged", cache, seqs, slots, lens, [s] * b, window)
     if q.stride(3) != 1:
         q = q.contiguous()
     out, ob, stats = _attention_outputs(q, out_layout, return_stats)
-    L, f = _lib.lib(), cache.fmts
-    # the bound that sizes grids and workspace: the table's room for the decode kernels (as ever), the batch at hand for the images
-    max_len = min((max(lens) + 127) // 128 * 128, cache.pt.max_len) if prefill else cache.pt.max_len
-    name = "lqer_attention_q_paged" if prefill else "lqer_attention_q_decode_paged"
-    with torch.cuda.device(q.device):
-        if ws is None:
-            ws = ops.workspace(q.device, max(getattr(L, name + "_workspace_bytes")(b, h, cache.kv_heads, s, max_len, d), 16))
-        if window is not None:  # (the kernels with the window rule: the same arguments and workspace, plus W)
-            name += "_window"
-        _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), ob.data_ptr(),
-                                    stats.data_ptr() if stats is not None else None, ops.dtype_code(q), b, h, cache.kv_heads, s, d,
-                                    _tri(q), _tri(ob), float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]),
-                                    C.byref(f[2]), C.byref(f[3]), ws.data_ptr(), ws.numel(), ops._stream(q.device),
-                                    *(() if window is None else (min(window, 1 << 62),))),
-                   name)
+    _paged_call(PAGED_PREFILL if prefill else PAGED_DECODE, q, ob, stats, cache, slots, lens, scaling, causal, ws, window, S=s)
     return (out, stats) if return_stats else out
 
 
+PAGED_PREFILL, PAGED_DECODE = "lqer_attention_q_paged", "lqer_attention_q_decode_paged"
 RAGGED_PREFILL, RAGGED_DECODE = "lqer_attention_q_paged_ragged", "lqer_attention_q_decode_paged_ragged"
 
 
-def _keys_still_there(who, cache, seqs, slots, lens, counts, window) -> None:
-    """What the prefill kernel's window rule asks of the pool: the page of the first key a sequence's first query row sees is still
-    the sequence's."""
+def _window_arg(who, window, default, causal):
+    """The window a call runs under: `window` - None or a number of keys >= 1, ValueError otherwise - or, for None, `default` (the
+    cache's).  A window without `causal` is refused."""
+    if window is None:
+        window = default
+    elif not isinstance(window, int) or isinstance(window, bool) or window < 1:
+        raise ValueError(f"{who}: window {window!r} - None or a number of keys >= 1")
+    if window is not None and not causal:
+        raise ValueError(f"{who}: window={window} without causal=True - the window is a rule on top of the causal one")
+    return window
+
+
+def _released_below(who, cache, slots, window) -> None:
+    """An explicit window wider than the cache's cannot run on sequences that have let pages go."""
+    if window is not None and any(cache.pt.released[x] for x in slots) and (cache.window is None or window > cache.window):
+        raise ValueError(f"{who}: window={window} on sequences that have released the pages below the cache's window of {cache.window} keys")
+
+
+def _prefill_window(who, cache, seqs, slots, lens, counts, window):
+    """The window rule of ONE prefill call on sequences `seqs` (in `slots`, of `lens` keys, with `counts` query rows) under the
+    effective window: None - the unwindowed entry - without a window or while every length is <= W (the rule changes nothing, and
+    nothing can have been released); else W - the *_window entry -, which needs a cache made with max_query_rows and, of every
+    sequence, still the page of the first key its first query row sees.  ValueError otherwise."""
+    if window is None or max(lens) <= window:
+        return None
+    if cache.max_query_rows is None:
+        raise ValueError(f"{who}: kernel='prefill' with window={window} and lengths {lens} - the prefill kernel has no window "
+                         "rule on a cache made without max_query_rows; it is taken while every length is <= the window")
     for seq, x, t, c in zip(seqs, slots, lens, counts):
         if PAGE_KEYS * cache.pt.released[x] > max(0, t - c - window + 1):
             raise ValueError(f"{who}: sequence {seq} of {t} keys has released its first {cache.pt.released[x]} pages, and {c} query rows under "
                              f"window={window} start at key {max(0, t - c - window + 1)} - the keys are gone (the cache keeps them for up to "
                              f"max_query_rows = {cache.max_query_rows} rows)")
+    return window
 
 
-def _ragged_call(name, q, cache: PagedKVCache, slots, lens, counts, scaling, causal, out, stats, ws, window=None) -> None:
-    """One library call with per-sequence counts - RAGGED_PREFILL (the prefill kernel, any counts; `window`: None, or W for
-    lqer_attention_q_paged_ragged_window) or RAGGED_DECODE (the split-over-keys kernels, counts up to 8, `window`: None or W) -: q / out [sum(counts), h, d] (any token and head strides), stats [sum(counts), h, 2]
-    fp32 dense or None, for the sequences in `slots` with `lens` keys and `counts` query rows each.  max_len as
-    attention_flexible_paged's prefill route: the longest addressed length rounded up to 128, capped at the table's room - tight,
-    since no result depends on it."""
-    total, h, d = q.shape
-    L, f = _lib.lib(), cache.fmts
-    max_len = min((max(max(lens), 1) + 127) // 128 * 128, cache.pt.max_len)
-    decode = name == RAGGED_DECODE
+def _paged_max_len(base, cache, lens) -> int:
+    """The bound handed to the library, which sizes grids and workspace: the table's room for PAGED_DECODE (as ever), for all others
+    the longest addressed length rounded up to 128, capped at the room - tight, since no result depends on it."""
+    return cache.pt.max_len if base == PAGED_DECODE else min((max(max(lens), 1) + 127) // 128 * 128, cache.pt.max_len)
+
+
+def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, window, ws_ptr, ws_bytes, stream, S=None, counts=None):
+    """(entry, its argument tuple) for one of the seven attention entries over the pool: `base` - PAGED_* on q / out [b, h, S, d]
+    (out: any strides over b, h, S), RAGGED_* on q / out [sum(counts), h, d] (any token and head strides) with `counts` query rows per
+    sequence -, stats fp32 dense or None, for the sequences in `slots` with `lens` keys.  `window`: None or W - the entry is then
+    `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  The workspace and the stream come as values, so nothing
+    here needs a GPU: the call's metadata is copied to the cache's device tensors, wherever they are."""
+    ragged, f = counts is not None, cache.fmts
+    h, d = q.shape[1], q.shape[-1]
+    max_len = _paged_max_len(base, cache, lens)
+    args = (q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), out.data_ptr(),
+            stats.data_ptr() if stats is not None else None, ops.dtype_code(q), len(slots), h, cache.kv_heads,
+            *((cache._call_starts(counts), max(counts), q.shape[0]) if ragged else (S,)), d,
+            *((_pair(q), _pair(out)) if ragged else (_tri(q), _tri(out))), float(scaling), int(bool(causal)),
+            C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]), ws_ptr, ws_bytes, stream)
+    if base == RAGGED_DECODE:
+        return base, args + (0 if window is None else min(window, 1 << 62),)
+    return (base, args) if window is None else (base + "_window", args + (min(window, 1 << 62),))
+
+
+def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, ws, window, S=None, counts=None) -> None:
+    """The library call _paged_args describes; ws: a uint8 workspace, or None for the stream's at the size `base`_workspace_bytes asks
+    (a *_window entry has its sibling's)."""
+    L = _lib.lib()
     with torch.cuda.device(q.device):
         if ws is None:
-            need = (L.lqer_attention_q_decode_paged_ragged_workspace_bytes(total, h, max_len, d) if decode else
-                    L.lqer_attention_q_paged_ragged_workspace_bytes(len(slots), h, cache.kv_heads, max(counts), max_len, d))
+            h, d = q.shape[1], q.shape[-1]
+            max_len = _paged_max_len(base, cache, lens)
+            need = (L.lqer_attention_q_decode_paged_ragged_workspace_bytes(q.shape[0], h, max_len, d) if base == RAGGED_DECODE else
+                    getattr(L, base + "_workspace_bytes")(len(slots), h, cache.kv_heads, S if counts is None else max(counts), max_len, d))
             ws = ops.workspace(q.device, max(need, 16))
-        if not decode and window is not None:  # (the same arguments and workspace, plus W)
-            name += "_window"
-        _lib.check(getattr(L, name)(q.data_ptr(), *cache._pool_args(), *cache._call_meta(slots, lens, max_len), out.data_ptr(),
-                                    stats.data_ptr() if stats is not None else None, ops.dtype_code(q), len(slots), h,
-                                    cache.kv_heads, cache._call_starts(counts), max(counts), total, d, _pair(q), _pair(out),
-                                    float(scaling), int(bool(causal)), C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]),
-                                    ws.data_ptr(), ws.numel(), ops._stream(q.device),
-                                    *((0 if window is None else min(window, 1 << 62),) if decode else
-                                      () if window is None else (min(window, 1 << 62),))),
-                   name)
-
-
-def _ragged_window(who, cache, window, causal):
-    """The window a call with per-sequence counts runs under: `window`, or the cache's - validated, and refused without causal."""
-    if window is not None and (not isinstance(window, int) or isinstance(window, bool) or window < 1):
-        raise ValueError(f"{who}: window {window!r} - None or a number of keys >= 1")
-    eff_window = cache.window if window is None else window
-    if eff_window is not None and not causal:
-        raise ValueError(f"{who}: window={eff_window} without causal=True - the window is a rule on top of the causal one")
-    return eff_window
+        name, args = _paged_args(base, q, out, stats, cache, slots, lens, scaling, causal, window, ws.data_ptr(), ws.numel(), ops._stream(q.device),
+                                 S, counts)
+        _lib.check(getattr(L, name)(*args), name)
 
 
 def _ragged_counts(who, seqs, counts):
@@ -941,11 +925,6 @@ def _ragged_operands(who, q, cache, seqs, counts, causal):
     return slots, lens
 
 
-def _ragged_released(who, cache, slots, live, eff_window) -> None:
-    if eff_window is not None and any(cache.pt.released[slots[b]] for b in live) and (cache.window is None or eff_window > cache.window):
-        raise ValueError(f"{who}: window={eff_window} on sequences that have released the pages below the cache's window of {cache.window} keys")
-
-
 @torch.no_grad()
 def attention_flexible_paged_decode_ragged(q, cache: PagedKVCache, seqs, counts, scaling, causal=False, return_stats=False, ws=None, window=None):
     """attention_flexible_paged(kernel="decode") for sequences with up to 8 query rows EACH, a count of its own per sequence, in ONE
@@ -961,20 +940,20 @@ def attention_flexible_paged_decode_ragged(q, cache: PagedKVCache, seqs, counts,
     anything is launched: what attention_flexible_paged_ragged refuses, in its words, and a count above 8 (more rows:
     attention_flexible_paged_ragged).  ws: a uint8 workspace or None (the stream's)."""
     who = "attention_flexible_paged_decode_ragged"
-    eff_window = _ragged_window(who, cache, window, causal)
+    eff_window = _window_arg(who, window, cache.window, causal)
     seqs, counts = _ragged_counts(who, seqs, counts)
     if any(c > _ATTN_DECODE_MAX_S for c in counts):
         raise ValueError(f"{who}: counts {counts} - the decode kernels over the paged cache take up to {_ATTN_DECODE_MAX_S} query rows per "
                          "sequence (more: attention_flexible_paged_ragged)")
     slots, lens = _ragged_operands(who, q, cache, seqs, counts, causal)
-    _ragged_released(who, cache, slots, [b for b, c in enumerate(counts) if c], eff_window)
+    _released_below(who, cache, (x for x, c in zip(slots, counts) if c), eff_window)
     if q.stride(2) != 1:
         q = q.contiguous()
     total, h, d = q.shape
     out = torch.empty(total, h, d, dtype=q.dtype, device=q.device)
     stats = torch.empty(total, h, 2, dtype=torch.float32, device=q.device) if return_stats else None
     if total:
-        _ragged_call(RAGGED_DECODE, q, cache, slots, lens, counts, scaling, causal, out, stats, ws, eff_window)
+        _paged_call(RAGGED_DECODE, q, out, stats, cache, slots, lens, scaling, causal, ws, eff_window, counts=counts)
     return (out, stats) if return_stats else out
 
 
@@ -1022,7 +1001,7 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     who = "attention_flexible_paged_ragged"
     if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
-    eff_window = _ragged_window(who, cache, window, causal)
+    eff_window = _window_arg(who, window, cache.window, causal)
     seqs, counts = _ragged_counts(who, seqs, counts)
     slots, lens = _ragged_operands(who, q, cache, seqs, counts, causal)
     total, h, d = q.shape
@@ -1030,16 +1009,12 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     live = [b for _, bs, _ in plan for b in bs]
     big = [bs for name, bs, _ in plan if name == RAGGED_PREFILL]
     big = big[0] if big else []
-    if live:
-        _ragged_released(who, cache, slots, live, eff_window)
-    big_window = eff_window if eff_window is not None and big and max(lens[b] for b in big) > eff_window else None
-    if big_window is not None and cache.max_query_rows is None:
-        raise ValueError(f"{who}: kernel='prefill' with window={eff_window} and lengths {[lens[b] for b in big]} - the prefill kernel has no "
-                         "window rule on a cache made without max_query_rows; it is taken while every length is <= the window")
-    if big_window is not None:
-        _keys_still_there(who, cache, [seqs[b] for b in big], [slots[b] for b in big], [lens[b] for b in big], [counts[b] for b in big], big_window)
-    if big and (max(lens[b] for b in big) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
-        raise ValueError(f"{who}: {len(big)} sequences of lengths {[lens[b] for b in big]} beyond the prefill kernel's launch grid")
+    _released_below(who, cache, (slots[b] for b in live), eff_window)
+    big_lens, big_window = [lens[b] for b in big], None
+    if big:
+        big_window = _prefill_window(who, cache, [seqs[b] for b in big], [slots[b] for b in big], big_lens, [counts[b] for b in big], eff_window)
+    if big and (max(big_lens) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
+        raise ValueError(f"{who}: {len(big)} sequences of lengths {big_lens} beyond the prefill kernel's launch grid")
     if q.stride(2) != 1:
         q = q.contiguous()
     out = torch.empty(total, h, d, dtype=q.dtype, device=q.device)
@@ -1056,16 +1031,17 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
             rows += mine
     idx = torch.tensor(rows, dtype=torch.int64).to(q.device) if rows else None
     for (name, bs, _), at in zip(plan, where):
-        args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], [counts[b] for b in bs], scaling, causal)
-        win = eff_window if name == RAGGED_DECODE else big_window  # (the prefill call while every length <= W: plain causal)
+        args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], scaling, causal, ws,
+                eff_window if name == RAGGED_DECODE else big_window)  # (the prefill call while every length <= W: plain causal)
+        mine = [counts[b] for b in bs]
         if isinstance(at, slice):  # (in place: nothing to copy)
-            _ragged_call(name, q[at], *args, out[at], stats[at] if return_stats else None, ws, win)
+            _paged_call(name, q[at], out[at], stats[at] if return_stats else None, *args, counts=mine)
             continue
         ix = idx[at[0]:at[1]]
         qc = q.index_select(0, ix)
         oc = torch.empty_like(qc)
         sc = torch.empty(qc.shape[0], h, 2, dtype=torch.float32, device=q.device) if return_stats else None
-        _ragged_call(name, qc, *args, oc, sc, ws, win)
+        _paged_call(name, qc, oc, sc, *args, counts=mine)
         out.index_copy_(0, ix, oc)
         if return_stats:
             stats.index_copy_(0, ix, sc)
@@ -1078,23 +1054,25 @@ def _plan(cache: PagedKVCache, seqs, counts, kernel=KERNEL_AUTO, window=None) ->
     sequences it takes, "rows": "view" when their rows are one range of q and the call runs on views of q and out, "gathered" when
     they are gathered and scattered by index, "window": the window rule it runs under (None: none).  The prefill call has a rule
     only on a cache made with max_query_rows, and only when a length it addresses - read from the host's books, which then must know
-    `seqs` - lies beyond the window: it is then lqer_attention_q_paged_ragged_window.  On any other cache no length is read.  Each
+    `seqs` - lies beyond the window: it is then lqer_attention_q_paged_ragged_window, by the function's own rule (_prefill_window),
+    its refusal of a count that reaches below the pages a sequence still holds included.  On any other cache no length is read.  Each
     call is three launches.  Refuses an unknown `kernel`, a bad `window` and bad counts as the function does."""
     who = "attention_flexible_paged_ragged"
     if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
-    eff_window = _ragged_window(who, cache, window, True)
+    eff_window = _window_arg(who, window, cache.window, True)
     seqs, counts = _ragged_counts(who, seqs, counts)
     out = []
     for name, bs, at in _ragged_plan(counts, kernel)[0]:
         win = eff_window if name == RAGGED_DECODE else None
         if name == RAGGED_PREFILL and eff_window is not None and cache.max_query_rows is not None:
+            mine = [seqs[b] for b in bs]
             try:
-                lens = [cache.pt.lengths[x] for x in cache.pt.slots([seqs[b] for b in bs])]
+                slots = cache.pt.slots(mine)
             except KeyError as e:
                 raise ValueError(e.args[0]) from None
-            if max(lens) > eff_window:
-                name, win = name + "_window", eff_window
+            win = _prefill_window(who, cache, mine, slots, [cache.pt.lengths[x] for x in slots], [counts[b] for b in bs], eff_window)
+            name += "_window" if win is not None else ""
         out.append({"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered", "window": win})
     return out
 
