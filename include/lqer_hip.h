@@ -753,6 +753,31 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * position: the table stays indexed by absolute key / 16.  Chunks wholly below that key cost nothing but an early exit.  Workspace,
  * grid and strides are lqer_attention_q_decode_paged's (lqer_attention_q_decode_paged_workspace_bytes, sized by max_len), three
  * launches, capturable alike.  Refused as the call above, and LQER_E_INVALID for window < 1 or causal = 0.
+ * lqer_attention_q_decode_paged_shared: lqer_attention_q_decode_paged's argument list plus (grp_of, grp_starts, grp_members, grp_keys,
+ * n_groups): sequences that hold their first keys on the SAME PAGES (lqer_kv_pool_fork: beams, samples of one prompt, requests behind
+ * one system prompt) are named as a group, and a chunk of keys that every member of a group holds on shared pages is loaded ONCE, by
+ * the workgroup of the group's first member (its leader), which computes that chunk for the query rows of all members; the other
+ * members' workgroups of that chunk leave at once.  Four int32 arrays on the DEVICE, written by the caller:
+ *   grp_of       [batch]         the group of the call's b-th sequence, in [0, n_groups)
+ *   grp_starts   [n_groups + 1]  group i owns entries grp_starts[i] .. grp_starts[i + 1] - 1 of grp_members (CSR: grp_starts[0] = 0,
+ *                                non-decreasing, grp_starts[n_groups] = batch); no group is empty
+ *   grp_members  [batch]         call indices, group by group; the first member of a group is its leader
+ *   grp_keys     [n_groups]      P: the leading keys the group's members hold on the same pages; a multiple of 16, 0 for a group of one
+ * They fall under the caller's contract, as the table and the lengths do: the arrays are a partition of 0 .. batch - 1 (every call
+ * index in exactly one group, grp_of[grp_members[e]] = i for the entries e of group i); for every group with P > 0 all members have
+ * the same chunk length lqer_attention_q_decode_chunk(lens[b], D); the first P / 16 entries of all members' table rows are the same
+ * pages; P <= 16 (lens[b] / 16) for every member b.  A call that breaks this reads or writes outside its buffers or gives a sequence
+ * another's keys.  Chunk c (keys c C .. c C + C - 1, C the chunk length) of a group of two or more is shared when (c + 1) C <= P;
+ * every other chunk, and every chunk of a group of one, is computed as lqer_attention_q_decode_paged computes it.  P is a licence, not
+ * a fact the kernels rely on beyond it: a smaller P than the members really share (0 included) is valid and gives the same bits.
+ * For every b, out[b] and row_stats[b] are the SAME BITS as lqer_attention_q_decode_paged gives - those of lqer_attention_q_decode with
+ * batch = 1 on the raw K and V of that sequence - whatever the groups are: a row's arithmetic is that row's alone.  Workspace
+ * (lqer_attention_q_decode_paged_workspace_bytes - there is no size function of its own), grid and strides are
+ * lqer_attention_q_decode_paged's; every workspace cell is written by exactly one workgroup; three launches on `stream`, no allocation,
+ * no host synchronisation, no atomics: capturable in a hipGraph.  The pool is only read.  Refused as lqer_attention_q_decode_paged,
+ * and LQER_E_INVALID for a null group array, n_groups < 1 or n_groups > batch (so also batch = 0).
+ * lqer_attention_q_decode_chunk(T, D): the chunk length C of a sequence of T keys in the split-over-keys kernels - 16 ceil(T / 256)
+ * clamped to [16, 128]; D is accepted for the rule's sake and does not enter it today.
  * lqer_attention_q_paged: lqer_attention_q_decode_paged's argument list, word for word, and its metadata contract, for ANY S >= 1
  * (uniform over the call) - a prompt, a second turn, a chunk of a long prompt or a speculated block of more than 8 tokens on paged
  * sequences, the whole ragged batch in one call.  It is to lqer_attention_q_kv what the call above is to lqer_attention_q_decode_kv:
@@ -885,6 +910,15 @@ int lqer_attention_q_decode_paged_window(const void* q, const void* pool, size_t
                                          float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
                                          const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
                                          void* stream, int64_t window);
+int lqer_attention_q_decode_paged_shared(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                         const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                         int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+                                         int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides, const int64_t* out_strides,
+                                         float scaling, int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt,
+                                         const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes,
+                                         void* stream, const int32_t* grp_of, const int32_t* grp_starts, const int32_t* grp_members,
+                                         const int32_t* grp_keys, int64_t n_groups);
+int lqer_attention_q_decode_chunk(int64_t T, int64_t D);
 size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
 int lqer_attention_q_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                            int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,

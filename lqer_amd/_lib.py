@@ -169,6 +169,10 @@ SIGNATURES = {
     "lqer_attention_q_decode_paged": (_i, _PAGED),
     # ... with a sliding window over the causal rule: the same argument list plus `window`
     "lqer_attention_q_decode_paged_window": (_i, _PAGED + [_i64]),
+    # ... with a prefix on shared pages read once per group: the same list plus grp_of, grp_starts, grp_members, grp_keys (int32, on the
+    # device) and n_groups; the chunk length of a sequence of T keys, so that the grouping rule is spelled once
+    "lqer_attention_q_decode_paged_shared": (_i, _PAGED + [_vp, _vp, _vp, _vp, _i64]),
+    "lqer_attention_q_decode_chunk": (_i, [_i64, _i64]),
     # ... for any number of query rows: the prefill kernel on images written from the pool through the block table, T = lens[b]
     "lqer_attention_q_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_paged": (_i, _PAGED),

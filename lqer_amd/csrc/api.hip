@@ -1395,6 +1395,12 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
     set_error("%s: max_s = %lld query rows (max_s >= 1 bounds every sequence's count)", who, (long long)c.S);
     return LQER_E_INVALID;
   }
+  if (c.grouped && (!c.grp_of || !c.grp_starts || !c.grp_members || !c.grp_keys || c.n_groups < 1 || c.n_groups > c.batch)) {
+    set_error("%s: group arrays %p / %p / %p / %p, n_groups = %lld for batch %lld (grp_of, grp_starts, grp_members, grp_keys: int32 on the "
+              "device, 1 <= n_groups <= batch)", who, (const void*)c.grp_of, (const void*)c.grp_starts, (const void*)c.grp_members,
+              (const void*)c.grp_keys, (long long)c.n_groups, (long long)c.batch);
+    return LQER_E_INVALID;
+  }
   if (const int rc = kn.grid_limits(who, c)) return rc;
   if (c.batch == 0 || c.S == 0 || (ragged && c.pool.total == 0)) return 1;
   if (c.T == 0) {
@@ -1412,8 +1418,9 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
   const size_t need = kn.workspace_bytes(c);
   if (c.workspace_bytes < need) {
     // (a windowed call has the unwindowed one's workspace; the ragged decode call takes its window as an argument of its own)
-    const char* sized_by = !c.windowed ? who
-                           : kn.max_s  ? (ragged ? who : "attention_q_decode_paged")
+    const char* sized_by = c.grouped   ? "attention_q_decode_paged"  // (the grouped call has the plain call's workspace too)
+                           : !c.windowed ? who
+                           : kn.max_s  ?(ragged ? who : "attention_q_decode_paged")
                                        : (ragged ? "attention_q_paged_ragged" : "attention_q_paged");
     set_error("%s: workspace %zu B < %zu B (lqer_%s_workspace_bytes)", who, c.workspace_bytes, need, sized_by);
     return LQER_E_INVALID;
@@ -1787,7 +1794,7 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
   return attn_run("attention_q_kv", ATTN_PREFILL, c);
 }
 
-// The record of an attention call over the pool from the arguments all seven entries have, in the ABI's order (no mask; T: the bound max_len -
+// The record of an attention call over the pool from the arguments all eight entries have, in the ABI's order (no mask; T: the bound max_len -
 // the check's, the workspace's).  Built in place, never copied: with per-sequence counts it points into the stride triples it holds.
 struct PagedAttn {
   AttnCall c;
@@ -1832,6 +1839,23 @@ int lqer_attention_q_decode_paged_window(const void* q, const void* pool, size_t
               D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
   a.c.windowed = true, a.c.window = window;  // (the call above with the window rule; grid and workspace still follow max_len)
   return attn_run("attention_q_decode_paged_window", ATTN_DECODE, a.c);
+}
+
+int lqer_attention_q_decode_chunk(int64_t T, int64_t D) { return attention_q_decode_chunk(T, D); }
+
+int lqer_attention_q_decode_paged_shared(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                         int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
+                                         float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t D,
+                                         const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                                         const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                                         size_t workspace_bytes, void* stream, const int32_t* grp_of, const int32_t* grp_starts,
+                                         const int32_t* grp_members, const int32_t* grp_keys, int64_t n_groups) {
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads, S,
+              D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  // (lqer_attention_q_decode_paged with a shared chunk read once per group; grid and workspace are that call's)
+  a.c.grouped = true, a.c.grp_of = grp_of, a.c.grp_starts = grp_starts, a.c.grp_members = grp_members, a.c.grp_keys = grp_keys;
+  a.c.n_groups = n_groups;
+  return attn_run("attention_q_decode_paged_shared", ATTN_DECODE, a.c);
 }
 
 size_t lqer_attention_q_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {

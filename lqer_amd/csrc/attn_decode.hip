@@ -45,6 +45,21 @@
 // that range for row r of kv head g (a bijection), so the workspace follows total x heads and not batch x max_s.  The host bound
 // max_s sizes k_attn_dec_sum's grid alone.  Everything a row computes - chunks, folds, fragments, quantizers, rounding points - is
 // the uniform kernels' at S = S_b: the rows of a sequence are those of a call of batch 1 with S = S_b, whatever else is in the batch.
+//
+// A prefix on shared pages read ONCE PER GROUP (template parameter GRP, the paged source without WIN and RAG:
+// lqer_attention_q_decode_paged_shared): beams, samples of one prompt, requests behind one system prompt hold their first P keys on
+// the same pages (lqer_kv_pool_fork).  The caller names the groups (DArgsGrp: grp_of, and grp_starts / grp_members in CSR form, the
+// first member of a group its leader) and P per group, a multiple of 16.  Grid, workspace and k_attn_dec_sum are the plain paged
+// call's.  Workgroup (c, g, b) takes T_b, C and nch from lens[b] as ever; chunk c is SHARED when b's group has more than one member
+// and (c + 1) C <= P.  Of a shared chunk the leader's workgroup loads the keys (the V rows) once, through its own table row - every
+// key lies below P <= every member's length - and runs the row loop over n_members R rows: row r is row r % R of member r / R, and
+// that member's call index, length, causal offset, q / row_stats offset and workspace rows are per-LANE values; the 32-row groups run
+// straight through the member boundaries.  The other members' workgroups of that chunk leave before the first barrier.  A lane still
+// owns one query row, an MFMA output column depends on that lane's operand alone, and in k_attn_dec_pv a lane folds the chunk
+// statistics of its own member's chunks 0 .. nch_j - 1 in chunk order: every row has the bits of the plain call.  Every workspace cell
+// is still written by exactly one workgroup (a member's cells of a shared chunk by the leader's, all others by its own) - no atomics,
+// no counters, three launches.  All members of a group with P > 0 have one chunk length (the caller's contract): the leader's C is
+// the C of every row it computes.  P is a licence - a smaller P than the members really share gives the same bits.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -90,13 +105,37 @@ struct DArgs {
 struct DArgsRag : DArgs {
   const int32_t* q_starts;  // (device, [batch + 1]) sequence b owns tokens q_starts[b] .. q_starts[b + 1] - 1
 };
-template <bool RAG>
-using DArgsOf = std::conditional_t<RAG, DArgsRag, DArgs>;
+// the argument record of the kernels with GRP: the groups of sequences that hold a prefix on the same pages, behind the same record
+struct DArgsGrp : DArgs {
+  const int32_t* grp_of;       // (device, [batch]) the group of the call's b-th sequence
+  const int32_t* grp_starts;   // (device, [groups + 1]) group i owns entries grp_starts[i] .. grp_starts[i + 1] - 1 of grp_members
+  const int32_t* grp_members;  // (device, [batch]) call indices, group by group; a group's first member is its leader
+  const int32_t* grp_keys;     // (device, [groups]) P: the leading keys a group's members hold on the same pages, a multiple of 16
+};
+template <bool RAG, bool GRP = false>
+using DArgsOf = std::conditional_t<GRP, DArgsGrp, std::conditional_t<RAG, DArgsRag, DArgs>>;
 
 // the paged source: chunk length and chunk count of a sequence of T = lens[b] keys
 __device__ __forceinline__ void paged_chunks(const DArgs& a, int64_t T, int& C, int& nch) {
   C = dec_chunk(T, a.D);
   nch = (int)((T + C - 1) / C);
+}
+
+// GRP: what workgroup (chunk c, sequence b) does with a chunk of C keys.  The chunk is SHARED when b's group has more than one member
+// and the chunk lies wholly below the group's P keys: the group's leader then loads it once and runs the rows of all n members
+// (`mem`: their call indices), every other member leaves (n = 0).  Any other chunk is the workgroup's own: n = 1, mem = nullptr.
+// Uniform over the workgroup (scalars), decided before the first barrier.
+struct GrpChunk {
+  int n;
+  const int32_t* mem;
+};
+__device__ __forceinline__ GrpChunk grp_chunk(const DArgsGrp& a, int64_t b, int64_t c, int C) {
+  const int gi = __builtin_amdgcn_readfirstlane(a.grp_of[b]);
+  const int m0 = __builtin_amdgcn_readfirstlane(a.grp_starts[gi]), m1 = __builtin_amdgcn_readfirstlane(a.grp_starts[gi + 1]);
+  const int P = __builtin_amdgcn_readfirstlane(a.grp_keys[gi]);
+  if (m1 - m0 < 2 || (c + 1) * C > P) return {1, nullptr};
+  if (__builtin_amdgcn_readfirstlane(a.grp_members[m0]) != b) return {0, nullptr};
+  return {m1 - m0, a.grp_members + m0};
 }
 
 // WIN: the first key that any of the S rows of a sequence of T keys sees
@@ -122,8 +161,8 @@ __device__ __forceinline__ SeqRows seq_rows(const DArgsOf<RAG>& a, int64_t b, in
   }
 }
 
-template <int DT, int SRC, bool WIN, bool RAG>
-__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a) {
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, GRP> a) {
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
@@ -132,13 +171,20 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a
   if constexpr (RAG) {
     if (sr.S <= 0) return;  // (a sequence without query rows: uniform over the workgroup, before any barrier; nothing is written)
   }
-  const int64_t S = sr.S, R = sr.R, wrow = sr.wrow;  // the workspace row of this kv head's row 0
+  const int64_t S = sr.S, R = sr.R;
   const int32_t* prow;  // the slot's row of the page table
   const int64_t T = kvc::seq<SRC>(a.src, b, a.T, prow);
   int C = a.C, nch = a.nch;
   if constexpr (SRC == SRC_PAGED) {
     paged_chunks(a, T, C, nch);
     if (c >= nch) return;  // (none of this sequence's chunks; uniform over the workgroup, before any barrier)
+  }
+  int64_t Rt = R;  // GRP: the rows of the row loop - a shared chunk's leader runs those of every member
+  const int32_t* mem = nullptr;
+  if constexpr (GRP) {
+    const GrpChunk gc = grp_chunk(a, b, c, C);
+    if (gc.n == 0) return;  // (the leader's workgroup computes this chunk for this sequence's rows)
+    Rt = gc.n * R, mem = gc.mem;
   }
   int64_t plo = 0;  // WIN: keys below plo lie on pages wholly outside every row's window - zero rows, their table entries and pages unread
   if constexpr (WIN) {
@@ -213,11 +259,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a
   // ---- S^T = Kq Qq^T: wave w takes keys 32 w .. 32 w + 31 of the chunk, a lane ONE query row and 16 of those keys,
   // (r & 3) + 8 (r >> 2) + 4 lh (rows of sK at and beyond C hold whatever LDS held: their scores are never used)
   const int nsub = (C + 31) / 32;
-  const int64_t off = T - S;
-  for (int64_t rg = 0; rg < R; rg += 32) {
-    const int64_t row = rg + l31;
-    const bool live = row < R;
-    const int64_t rowc = live ? row : R - 1;
+  for (int64_t rg = 0; rg < Rt; rg += 32) {
+    int64_t row = rg + l31;
+    const bool live = row < Rt;
+    int64_t rowc = live ? row : Rt - 1;
+    int64_t bq = b, Tq = T, wrow = sr.wrow;  // the sequence of this lane's row: its call index, its length, its workspace row 0
+    if constexpr (GRP) {
+      if (mem) {  // a shared chunk: row r is row r % R of member r / R - the 32-row groups run straight through the members
+        const int64_t j = rowc / R;
+        bq = mem[j], Tq = a.src.lens[bq], wrow = (bq * a.kv_heads + g) * R;
+        row = rowc = rowc - j * R;  // (a lane that is not live stores nothing)
+      }
+    }
+    const int64_t off = Tq - S;
     const int64_t h = g * a.rep + rowc / S, si = rowc % S;
     float m = NEG_INF, l = 0.f;
     if (wave < nsub) {
@@ -230,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a
           uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
           if (live) {
             float v[16];
-            load16<DT>(a.q, b * a.q_bs + h * a.q_hs + (sr.tok + si) * a.q_rs + ks * 16, 16, a.qvec, v);
+            load16<DT>(a.q, bq * a.q_bs + h * a.q_hs + (sr.tok + si) * a.q_rs + ks * 16, 16, a.qvec, v);
             quant16_bf16<DT != LQER_F16>(v, a.q0, w);
           }
           const u32x4 f = {lh ? w[4] : w[0], lh ? w[5] : w[1], lh ? w[6] : w[2], lh ? w[7] : w[3]};
@@ -238,11 +292,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8, f), acc, 0, 0, 0);
         }
       }
-      int64_t tvis = T - 1;  // the last key visible to this lane's query
+      int64_t tvis = Tq - 1;  // the last key visible to this lane's query
       if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
       int64_t tlo = 0;  // WIN: the first key this lane's query sees (negative: all of them)
       if constexpr (WIN) tlo = si + off - a.win + 1;
-      const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + si * a.m_rs : 0;
+      const int64_t moff = a.mode == 1 ? bq * a.m_bs + h * a.m_hs + si * a.m_rs : 0;
       float s2[16];
       bool vis[16];
 #pragma unroll
@@ -250,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a
         const int kk = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int64_t t = t0 + kk;
         float s = rnd<DT>(rnd<DT>(acc[r]) * a.scaling);
-        if (a.mode == 1) s = rnd<DT>(s + (t < T ? load_elem<DT>(a.mask, moff + t) : 0.f));
+        if (a.mode == 1) s = rnd<DT>(s + (t < Tq ? load_elem<DT>(a.mask, moff + t) : 0.f));
         s2[r] = s;
         vis[r] = kk < C && t <= tvis && (!WIN || t >= tlo);
       }
@@ -290,8 +344,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG> a
   }
 }
 
-template <int DT, int SRC, bool WIN, bool RAG>
-__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG> a) {
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> a) {
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
@@ -299,13 +353,20 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG> a) {
   if constexpr (RAG) {
     if (sr.S <= 0) return;
   }
-  const int64_t S = sr.S, R = sr.R, wrow = sr.wrow;
+  const int64_t S = sr.S, R = sr.R;
   const int32_t* prow;
   const int64_t T = kvc::seq<SRC>(a.src, b, a.T, prow);
   int C = a.C, nch = a.nch;
   if constexpr (SRC == SRC_PAGED) {
     paged_chunks(a, T, C, nch);
     if (c >= nch) return;
+  }
+  int64_t Rt = R;
+  const int32_t* mem = nullptr;
+  if constexpr (GRP) {
+    const GrpChunk gc = grp_chunk(a, b, c, C);
+    if (gc.n == 0) return;
+    Rt = gc.n * R, mem = gc.mem;
   }
   int64_t plo = 0;
   int c_lo = 0;  // WIN: the first chunk that holds a visible key
@@ -367,25 +428,34 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG> a) {
   __syncthreads();
   if (wave * 32 >= D) return;  // wave w owns d = 32 w .. 32 w + 31 (no barrier follows)
 
-  const int64_t off = T - S;
-  for (int64_t rg = 0; rg < R; rg += 32) {
-    const int64_t row = rg + l31;
-    const bool live = row < R;
-    const int64_t rowc = live ? row : R - 1;
+  for (int64_t rg = 0; rg < Rt; rg += 32) {
+    int64_t row = rg + l31;
+    const bool live = row < Rt;
+    int64_t rowc = live ? row : Rt - 1;
+    int64_t Tq = T, wrow = sr.wrow;  // the sequence of this lane's row: its length, its workspace row 0 - and its chunk count
+    int nchq = nch;
+    if constexpr (GRP) {
+      if (mem) {  // a shared chunk: row r is row r % R of member r / R, which folds the statistics of ITS chunks 0 .. nch_j - 1
+        const int64_t j = rowc / R, bq = mem[j];
+        Tq = a.src.lens[bq], wrow = (bq * a.kv_heads + g) * R, nchq = (int)((Tq + C - 1) / C);
+        row = rowc = rowc - j * R;  // (a lane that is not live stores nothing)
+      }
+    }
+    const int64_t off = Tq - S;
     const int64_t si = rowc % S;
     // ---- the row's maximum and sum from the chunk statistics, in chunk order
     const float* cs = a.cst + (wrow + rowc) * a.nchs * 2;
     float M = NEG_INF;
-    for (int cc = c_lo; cc < nch; ++cc) M = fmaxf(M, cs[2 * cc]);
+    for (int cc = c_lo; cc < nchq; ++cc) M = fmaxf(M, cs[2 * cc]);
     const float mr = M == NEG_INF ? 0.f : M;
     float L = 0.f;
-    for (int cc = c_lo; cc < nch; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
+    for (int cc = c_lo; cc < nchq; ++cc) L += cs[2 * cc + 1] * exp_neg(cs[2 * cc] - mr);
     if (a.stats && c == (WIN ? c_lo : 0) && wave == 0 && lh == 0 && live) {
       // (RAG: row_stats is [total][heads][2] - by token, then head; else [batch][heads][S][2], the workspace's row order)
       float* st = a.stats + (RAG ? (sr.tok + si) * a.heads + g * a.rep + row / S : wrow + row) * 2;
       st[0] = M, st[1] = L;
     }
-    int64_t tvis = T - 1;
+    int64_t tvis = Tq - 1;
     if (a.mode == 2) tvis = si + off < tvis ? si + off : tvis;
     if (!live) tvis = -1;
     int64_t tlo = 0;
@@ -458,14 +528,15 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgsOf<RAG> a) {
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
-template <int DT, int SRC, bool WIN = false, bool RAG = false>
-static int launch_decode(const DArgsOf<RAG>& a, int64_t batch, hipStream_t st) {
+template <int DT, int SRC, bool WIN = false, bool RAG = false, bool GRP = false>
+static int launch_decode(const DArgsOf<RAG, GRP>& a, int64_t batch, hipStream_t st) {
   const dim3 grid((unsigned)a.nchs, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT, SRC, WIN, RAG><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT, SRC, WIN, RAG><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_scores<DT, SRC, WIN, RAG, GRP><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT, SRC, WIN, RAG, GRP><<<grid, 256, 0, st>>>(a);
   // (RAG: a.S is the bound max_s - x over the rows a sequence has at most, y the sequence)
   const dim3 sgrid((unsigned)(((RAG ? a.S * a.heads : a.rows) * (a.D / 4) + 255) / 256), RAG ? (unsigned)batch : 1u);
-  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN, RAG><<<sgrid, 256, 0, st>>>(a);
+  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN, RAG><<<sgrid, 256, 0, st>>>(a);  // (GRP: the plain call's kernel, on the record's base)
+  if (GRP) return check_launch("lqer_attention_q_decode_paged_shared");
   if (RAG) return check_launch("lqer_attention_q_decode_paged_ragged");
   if (WIN) return check_launch("lqer_attention_q_decode_paged_window");
   return check_launch(SRC == SRC_PAGED ? "lqer_attention_q_decode_paged" : (SRC == SRC_PACKED ? "lqer_attention_q_decode_kv" : "lqer_attention_q_decode"));
@@ -476,6 +547,7 @@ static int launch_decode(const DArgsOf<RAG>& a, int64_t batch, hipStream_t st) {
 static size_t dec_align(size_t v) { return (v + 255) / 256 * 256; }
 
 int attention_q_decode_max_s() { return attn::DEC_MAX_S; }
+int attention_q_decode_chunk(int64_t T, int64_t D) { return attn::dec_chunk(T, D); }
 
 // rows = batch heads S, C = dec_chunk(T, D), nch = ceil(T / C):
 // [S2: rows x nch C fp32][chunk statistics: rows x nch x 2 fp32][partial outputs: rows x nch x D fp32], each rounded up to 256 bytes
@@ -531,6 +603,12 @@ int attention_q_decode_dispatch(const AttnCall& c) {
   // (the window and the per-sequence counts have public entries on the paged source only, so only those instantiations exist)
   if (ragged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true, true>(a, c.batch, c.st); });
   if (ragged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, false, true>(a, c.batch, c.st); });
+  if (c.paged && c.grouped) {  // (the plain paged call's record and, behind it, the groups)
+    attn::DArgsGrp ag;
+    (attn::DArgs&)ag = a;
+    ag.grp_of = c.grp_of, ag.grp_starts = c.grp_starts, ag.grp_members = c.grp_members, ag.grp_keys = c.grp_keys;
+    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, false, false, true>(ag, c.batch, c.st); });
+  }
   if (c.paged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true>(a, c.batch, c.st); });
   if (c.paged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
   if (c.packed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });

@@ -941,6 +941,11 @@ struct AttnCall {
   const int64_t *qs, *ks, *vs, *ms, *os;  // elements over batch / head / row (ms: only with a mask)
   float scaling;
   int causal;
+  // sequences that hold a prefix on the same pages (lqer_attention_q_decode_paged_shared; `paged`, no window, no per-sequence counts):
+  // four DEVICE arrays - the group of every sequence, the groups' members in CSR form (first member: the leader), the shared keys P
+  bool grouped;
+  const int32_t *grp_of, *grp_starts, *grp_members, *grp_keys;
+  int64_t n_groups;
   bool windowed;   // a sliding window over the causal rule (the _window entries, decode and prefill): query p sees keys p - window < j <= p
   int64_t window;
   const lqer_qfmt_t *q_fmt, *k_fmt, *p_fmt, *v_fmt;  // Q_x0, Q_w0, Q_x1, Q_w1
@@ -956,6 +961,7 @@ size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, i
 int attention_q_dispatch(const AttnCall& c);  // (with a cache or a pool: kv_cache.hip writes the two images from the codes, k_attn_q runs on them)
 // attn_decode.hip: the same attention for 1 <= S <= attention_q_decode_max_s() query rows, split over the keys
 int attention_q_decode_max_s();
+int attention_q_decode_chunk(int64_t T, int64_t D);  // keys per chunk of a sequence of T keys
 size_t attention_q_decode_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t T, int64_t D);
 size_t attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t S, int64_t max_len, int64_t D);
 size_t attention_q_decode_paged_ragged_workspace_bytes(int64_t total, int64_t heads, int64_t max_len, int64_t D);  // (pool.ragged: rows by packed token)

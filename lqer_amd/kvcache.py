@@ -423,6 +423,33 @@ class PageTable:
             self.free(child)
         self._next_seq -= len(children)
 
+    def prefix_groups(self, slots, lens, chunk_of) -> list:
+        """The sequences of one call - in `slots`, of `lens` keys - grouped by the prefix they hold on the SAME pages: a list of
+        (members, shared_keys), members the call indices in ascending order (the first is the group's leader), the groups ordered by
+        their first member, every call index in exactly one group.  chunk_of(length): the decode kernels' chunk length.
+        A sequence is eligible with no released page and at least one full page (16 keys).  Eligible sequences cluster by
+        (chunk_of(len), first page); of a cluster of two or more, n = the leading row entries equal in ALL members' rows, capped at
+        min(len) // 16 - an open block is never shared -, and P = 16 n keys.  P below the chunk length shares no chunk: the cluster
+        then dissolves into groups of one, as everything not eligible is (P = 0).  ONE level: a subset that shares more than its
+        whole cluster does (a beam tree) still gets the cluster's P."""
+        clusters = {}
+        for i, (s, t) in enumerate(zip(slots, lens)):
+            if self.released[s] == 0 and t >= PAGE_KEYS:
+                clusters.setdefault((chunk_of(t), self.table[s][0]), []).append(i)
+        shared = {}  # leader -> (members, P)
+        for (chunk, _), mem in clusters.items():
+            if len(mem) < 2:
+                continue
+            first, n = self.table[slots[mem[0]]], min(lens[i] for i in mem) // PAGE_KEYS
+            for i in mem[1:]:  # (whole-slice compares: beams that share everything below their open blocks cost one each)
+                row = self.table[slots[i]]
+                if row[:n] != first[:n]:
+                    n = next(e for e, (x, y) in enumerate(zip(row, first)) if x != y)
+            if PAGE_KEYS * n >= chunk:
+                shared[mem[0]] = (mem, PAGE_KEYS * n)
+        grouped = {i for mem, _ in shared.values() for i in mem[1:]}
+        return [shared.get(i, ([i], 0)) for i in range(len(slots)) if i not in grouped]
+
     def snapshot(self, seqs=()):
         """The books, and the table rows of `seqs` - what restore() needs to put back sequences that were freed since."""
         return (self._free_pages[:], self._free_slots[:], dict(self._slot), self._next_seq, self.pages_of[:], self.lengths[:], self._owners.copy(),
@@ -508,6 +535,7 @@ class PagedKVCache:
         self._slots = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
         self._lens = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
         self._starts = torch.zeros(max_seqs + 1, dtype=torch.int32, device=self.device)  # per-sequence counts of a call, as token starts
+        self._groups = torch.zeros(4 * max_seqs + 1, dtype=torch.int32, device=self.device)  # the prefix groups of a call (_call_groups)
 
     num_pages = property(lambda self: self.pt.num_pages)
     max_seqs = property(lambda self: self.pt.max_seqs)
@@ -632,6 +660,21 @@ class PagedKVCache:
         self._starts[:len(starts)].copy_(torch.tensor(starts, dtype=torch.int32))
         return self._starts.data_ptr()
 
+    def _call_groups(self, groups):
+        """The prefix groups of a call (PageTable.prefix_groups) on the device, in ONE copy as _call_meta's: grp_of [n], grp_starts
+        [groups + 1], grp_members [n] and grp_keys [groups] one behind the other - their four pointers and the group count."""
+        n = sum(len(mem) for mem, _ in groups)
+        of, starts, members = [0] * n, [0], []
+        for i, (mem, _) in enumerate(groups):
+            for b in mem:
+                of[b] = i
+            members += mem
+            starts.append(len(members))
+        flat = of + starts + members + [p for _, p in groups]
+        self._groups[:len(flat)].copy_(torch.tensor(flat, dtype=torch.int32))
+        at = (0, n, n + len(starts), 2 * n + len(starts))
+        return tuple(self._groups.data_ptr() + 4 * x for x in at) + (len(groups),)
+
     def _launch_append_ragged(self, slots, lens, taken, k, v, counts) -> None:
         self._upload_rows(slots, taken)
         if k.stride(2) != 1:
@@ -754,7 +797,7 @@ KERNEL_AUTO = "auto"
 
 @torch.no_grad()
 def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False, out_layout="bhsd", return_stats=False, ws=None,
-                             kernel=KERNEL_DECODE, window=None):
+                             kernel=KERNEL_DECODE, window=None, shared_prefix=False):
     """attention_flexible(q[b:b+1], K_b, V_b, cache.cfg0, cache.cfg1, scaling, causal=causal, kernel=kernel) for every sequence
     seqs[b] of a PagedKVCache, bit for bit, in ONE call over sequences of different lengths.
     q [len(seqs), h, s, d]; `causal`: key j of sequence b visible to query i iff j <= i + (length_b - s).
@@ -775,7 +818,12 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     and the unwindowed call runs.  Beyond, a cache made with max_query_rows runs lqer_attention_q_paged_window - the prefill kernel's
     window rule, the bits of attention_flexible(..., attention_mask=M, kernel="prefill") on the full raw K and V, no page below the
     window read; a sequence that has released the page of the first key this call's first row sees (16 released > max(0, T - s - W +
-    1): more rows than the cache was made for) raises ValueError.  A cache without max_query_rows raises ValueError beyond W."""
+    1): more rows than the cache was made for) raises ValueError.  A cache without max_query_rows raises ValueError beyond W.
+    shared_prefix=True (the decode kernel only; the default changes nothing): sequences that hold a prefix on the same pages - beams,
+    samples of one prompt, forks behind one system prompt - are grouped from the host's books (PageTable.prefix_groups) and
+    lqer_attention_q_decode_paged_shared reads every chunk of keys that lies wholly inside a group's shared pages ONCE per group
+    instead of once per sequence; the same bits, row for row.  When no two sequences of the call share a chunk the plain entry runs.
+    With a window in effect (the call's or the cache's) or with the prefill kernel: ValueError."""
     if kernel not in (KERNEL_DECODE, KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"attention_flexible_paged: kernel={kernel!r} - 'decode', 'prefill' or 'auto'")
     _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
@@ -787,6 +835,9 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     if kernel == KERNEL_AUTO:
         kernel = KERNEL_DECODE if s <= _ATTN_DECODE_MAX_S else KERNEL_PREFILL
     prefill = kernel == KERNEL_PREFILL
+    if shared_prefix and (prefill or window is not None):
+        raise ValueError("attention_flexible_paged: shared_prefix=True " + ("with the prefill kernel" if prefill else f"with window={window}")
+                         + " - only the decode kernel without a window reads a shared prefix once per group")
     if not prefill and s > _ATTN_DECODE_MAX_S:
         raise ValueError(f"attention_flexible_paged: {s} query rows per head - the decode kernel over the paged cache takes up to "
                          f"{_ATTN_DECODE_MAX_S} (more: kernel='prefill')")
@@ -809,11 +860,16 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     if q.stride(3) != 1:
         q = q.contiguous()
     out, ob, stats = _attention_outputs(q, out_layout, return_stats)
-    _paged_call(PAGED_PREFILL if prefill else PAGED_DECODE, q, ob, stats, cache, slots, lens, scaling, causal, ws, window, S=s)
+    groups = None
+    if shared_prefix:
+        L = _lib.lib()
+        groups = cache.pt.prefix_groups(slots, lens, lambda t: L.lqer_attention_q_decode_chunk(t, d))
+    _paged_call(PAGED_PREFILL if prefill else PAGED_DECODE, q, ob, stats, cache, slots, lens, scaling, causal, ws, window, S=s, groups=groups)
     return (out, stats) if return_stats else out
 
 
 PAGED_PREFILL, PAGED_DECODE = "lqer_attention_q_paged", "lqer_attention_q_decode_paged"
+SHARED_DECODE = "lqer_attention_q_decode_paged_shared"
 RAGGED_PREFILL, RAGGED_DECODE = "lqer_attention_q_paged_ragged", "lqer_attention_q_decode_paged_ragged"
 
 
@@ -859,11 +915,14 @@ def _paged_max_len(base, cache, lens) -> int:
     return cache.pt.max_len if base == PAGED_DECODE else min((max(max(lens), 1) + 127) // 128 * 128, cache.pt.max_len)
 
 
-def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, window, ws_ptr, ws_bytes, stream, S=None, counts=None):
-    """(entry, its argument tuple) for one of the seven attention entries over the pool: `base` - PAGED_* on q / out [b, h, S, d]
+def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, window, ws_ptr, ws_bytes, stream, S=None, counts=None,
+                groups=None):
+    """(entry, its argument tuple) for one of the eight attention entries over the pool: `base` - PAGED_* on q / out [b, h, S, d]
     (out: any strides over b, h, S), RAGGED_* on q / out [sum(counts), h, d] (any token and head strides) with `counts` query rows per
     sequence -, stats fp32 dense or None, for the sequences in `slots` with `lens` keys.  `window`: None or W - the entry is then
-    `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  The workspace and the stream come as values, so nothing
+    `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  `groups` (PAGED_DECODE without a window only): the call's
+    prefix groups (PageTable.prefix_groups) - with a group of two or more the entry is SHARED_DECODE, `base`'s list plus the group
+    arrays; with none, or without any such group, `base`.  The workspace and the stream come as values, so nothing
     here needs a GPU: the call's metadata is copied to the cache's device tensors, wherever they are."""
     ragged, f = counts is not None, cache.fmts
     h, d = q.shape[1], q.shape[-1]
@@ -875,10 +934,14 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
             C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]), ws_ptr, ws_bytes, stream)
     if base == RAGGED_DECODE:
         return base, args + (0 if window is None else min(window, 1 << 62),)
+    if groups is not None and any(len(mem) > 1 for mem, _ in groups):
+        if base != PAGED_DECODE or window is not None:
+            raise ValueError(f"prefix groups on {base} with window={window} - {SHARED_DECODE} is {PAGED_DECODE} alone")
+        return SHARED_DECODE, args + cache._call_groups(groups)
     return (base, args) if window is None else (base + "_window", args + (min(window, 1 << 62),))
 
 
-def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, ws, window, S=None, counts=None) -> None:
+def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, ws, window, S=None, counts=None, groups=None) -> None:
     """The library call _paged_args describes; ws: a uint8 workspace, or None for the stream's at the size `base`_workspace_bytes asks
     (a *_window entry has its sibling's)."""
     L = _lib.lib()
@@ -890,7 +953,7 @@ def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
                     getattr(L, base + "_workspace_bytes")(len(slots), h, cache.kv_heads, S if counts is None else max(counts), max_len, d))
             ws = ops.workspace(q.device, max(need, 16))
         name, args = _paged_args(base, q, out, stats, cache, slots, lens, scaling, causal, window, ws.data_ptr(), ws.numel(), ops._stream(q.device),
-                                 S, counts)
+                                 S, counts, groups)
         _lib.check(getattr(L, name)(*args), name)
 
 
