@@ -94,6 +94,12 @@ extern "C" {
                         Minifloat weights of 5..8 bits, minifloat on the int8 route (LQER_Q_MXINT_I8) and 2-D weight tiles:
                         LQER_E_UNSUPPORTED */
 
+#define LQER_Q_MXINT_C4 6 /* k_fmt / v_fmt of the paged KV pool's entries only: block_fp quantized exactly as LQER_Q_MXINT of the same
+                            width, exp_width and exp_bias (width 2..4, block 16), the operand's codes STORED AS NIBBLES - two per byte,
+                            see "paged KV pool", nibble codes.  Names a storage, as the two kinds above name a route, not another
+                            quantizer.  Anywhere else - q / p formats, the dense lqer_kv_cache_* entries, a Linear's formats,
+                            lqer_attention_q_decode_paged_shared - LQER_E_UNSUPPORTED */
+
 /* Geometry of the packed operands (fixed by the kernels; exported so callers can size buffers). */
 #define LQER_K_ALIGN 64     /* K is zero-padded to a multiple of this                        */
 #define LQER_M_ALIGN 256    /* activation workspaces are row-padded to a multiple of this    */
@@ -711,6 +717,24 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  *   V exponents  [pages][kv_heads][D / 16][16]   uint8   the dense cache's regrouping: four consecutive keys' exponents in one dword
  *   K staging    [slots][kv_heads][16][D]        DT      raw keys of a sequence's open block - one set per sequence SLOT, not per page
  * Within an item the bytes are exactly the dense cache's bytes for that block of 16 keys.
+ * NIBBLE CODES (opt-in, per operand: k_fmt / v_fmt of kind LQER_Q_MXINT_C4, width 2..4, so |mantissa| <= 7).  The operand's code section
+ * is then, in place of the byte section above,
+ *   K / V codes  [pages][kv_heads][16][D / 2]    uint8   elements d = 2 j and 2 j + 1 of a key's row are the low and the high nibble of
+ *                                                        byte j; a nibble is sign << 3 | |mantissa| - sign-magnitude, so the quantizer's
+ *                                                        -0 is kept as the byte code keeps it; the byte code is (n & 7) | ((n & 8) << 4)
+ * and everything else - the exponent sections, the staging rows, the item index p kv_heads + g, the 256-byte rounding of each section -
+ * is unchanged: 2 D (1/2 + 1/16) bytes per token and kv head with both operands in nibbles, 144 B instead of 272 B at D = 128.  A key's
+ * row is D / 2 bytes, a multiple of 8, and the 16 codes of one block of 16 d are one aligned 8-byte piece.  K and V choose
+ * independently (K of width 8 beside V in nibbles is a valid pool).  The pool is sized by lqer_kv_pool_bytes_fmt(dtype, pages, slots,
+ * kv_heads, D, k_fmt, v_fmt) - lqer_kv_pool_bytes when both kinds are LQER_Q_MXINT, 0 for anything the pool does not take - and EVERY
+ * call on it passes the same two kinds: the appends and the attention entries in their k_fmt / v_fmt, gather and fork through
+ * lqer_kv_pool_gather_fmt / lqer_kv_pool_fork_fmt (the entries without formats address a pool of byte codes).  The values, and with
+ * them every result, are those of a byte pool of LQER_Q_MXINT formats with the same fields: the storage changes no rounding.  An
+ * append writes every byte of a nibble section whole, from one thread - the open block is still rewritten over all 16 rows -, so
+ * pages are reused dirty as ever.  lqer_kv_pool_gather_fmt writes the dense BYTE cache lqer_kv_pool_gather writes from a byte pool
+ * (nibbles widened, exponents and staging rows copied); lqer_kv_pool_fork_fmt copies an item at the size the formats give it.
+ * Refused, LQER_E_UNSUPPORTED: the kind with width > 4 or block != 16; the kind on lqer_attention_q_decode_paged_shared (the grouped
+ * kernels are not instantiated for it - lqer_attention_q_decode_paged gives the same bits).
  * Metadata, all on the DEVICE and written by the caller:
  *   block_table  int32 [slots][table_stride]: entry [s][i] is the page of keys 16 i .. 16 i + 15 of the sequence in slot s;
  *   seq_slots    int32 [batch]: the slot of the b-th sequence of THIS call - any subset of the slots, in any order;
@@ -877,10 +901,13 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  *                       max_len > 2^30 (every call); lqer_attention_q_paged: what lqer_attention_q_kv refuses so instead (formats, D, S
  *                       or max_len beyond the launch grid, batch, heads or batch x kv_heads > 65535) - S > 8 is not among them;
  *   LQER_E_INVALID      null block_table / seq_slots / lens or any other null pointer; pages, slots or table_stride < 1; max_len < 1
- *                       or > 16 table_stride; n < 1 or n > max_len; a pool shorter than lqer_kv_pool_bytes or not 16-byte aligned;
+ *                       or > 16 table_stride; n < 1 or n > max_len; a pool shorter than lqer_kv_pool_bytes (with nibble codes:
+ *                       lqer_kv_pool_bytes_fmt) or not 16-byte aligned;
  *                       a short or misaligned workspace; gather: slot outside [0, slots), T > capacity, a short or misaligned cache. */
 #define LQER_KV_PAGE_KEYS 16
 size_t lqer_kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D);
+size_t lqer_kv_pool_bytes_fmt(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D, const lqer_qfmt_t* k_fmt,
+                              const lqer_qfmt_t* v_fmt);
 int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
                         const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const void* k_new, const void* v_new,
                         const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t n,
@@ -896,6 +923,12 @@ int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t 
 int lqer_kv_pool_fork(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
                       const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
                       int64_t n, void* stream);
+int lqer_kv_pool_gather_fmt(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                            const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
+                            int64_t capacity, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
+int lqer_kv_pool_fork_fmt(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                          const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots,
+                          const int32_t* lens, int64_t n, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
 size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
 int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                                   int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,

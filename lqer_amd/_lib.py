@@ -15,6 +15,7 @@ BUILD_SCRIPT = os.path.join(_HERE, "csrc", "build.sh")
 ABI_VERSION = 14
 F32, F16, BF16 = 0, 1, 2
 Q_PASSTHROUGH, Q_MXINT, Q_PASSTHROUGH_F16, Q_MXINT_I8, Q_INT, Q_MINIFLOAT = 0, 1, 2, 3, 4, 5
+Q_MXINT_C4 = 6  # k_fmt / v_fmt of the paged KV pool: block_fp of width <= 4 whose codes are stored as nibbles
 K_ALIGN, M_ALIGN, N_ALIGN, R_ALIGN = 64, 256, 256, 16
 ROUTE_SMALLM, ROUTE_TILE128, ROUTE_TILE256, ROUTE_I8 = 0, 1, 2, 3
 NARROW_DIRECT, NARROW_DIRECT_ONE_LAUNCH, NARROW_WIDEN = 1, 2, 3  # lqer_weight_narrow_route: what a call with the compact weight image does
@@ -165,6 +166,10 @@ SIGNATURES = {
     "lqer_kv_pool_gather": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _i64, _vp]),
     # pool, bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, src_slots, dst_slots, lens, pairs, stream
     "lqer_kv_pool_fork": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    # ... for a pool whose K and / or V codes are nibbles (Q_MXINT_C4): the size, gather and fork with the two formats behind their lists
+    "lqer_kv_pool_bytes_fmt": (_sz, [_i, _i64, _i64, _i64, _i64, _qp, _qp]),
+    "lqer_kv_pool_gather_fmt": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _i64, _qp, _qp, _vp]),
+    "lqer_kv_pool_fork_fmt": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _qp, _qp, _vp]),
     "lqer_attention_q_decode_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_decode_paged": (_i, _PAGED),
     # ... with a sliding window over the causal rule: the same argument list plus `window`

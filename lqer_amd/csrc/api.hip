@@ -72,6 +72,11 @@ static bool fmt_ok(const lqer_qfmt_t* f, const char* name, int max_width) {
     set_error("%s: LQER_Q_MXINT_I8 is an x_quantizer kind", name);
     return false;
   }
+  if (f->kind == LQER_Q_MXINT_C4) {  // (the pool entries replace it by LQER_Q_MXINT before they come here: pool_code_fmt)
+    set_error("%s: LQER_Q_MXINT_C4 names the nibble code storage of the paged KV pool - a k_fmt / v_fmt kind of the lqer_kv_pool_* and "
+              "lqer_attention_q_*paged* entries only", name);
+    return false;
+  }
   if (f->kind == LQER_Q_INT) {  // fixed point: exp_bias = frac_width, exp_width = is_signed
     const bool role_ok = !strcmp(name, "x_quantizer") || !strcmp(name, "b_quantizer") || !strcmp(name, "A_out_quantizer") ||
                          !strcmp(name, "B_out_quantizer") || !strcmp(name, "quantize_mxint") || !strcmp(name, "w_quantizer");
@@ -1547,6 +1552,46 @@ size_t lqer_kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_he
   return kv_pool_bytes(dtype, pages, slots, kv_heads, D);
 }
 
+// LQER_Q_MXINT_C4 as the k_fmt / v_fmt of a pool entry: the operand's codes are stored as nibbles (kv_pack.h) and quantized exactly as
+// LQER_Q_MXINT of the same fields.  The format the checks and the kernels go by - `own`, the caller's with the kind replaced, or the
+// caller's itself (null included: the checks' to refuse) - and whether the storage is nibbles.
+static const lqer_qfmt_t* pool_code_fmt(const lqer_qfmt_t* f, lqer_qfmt_t& own, bool& n4) {
+  n4 = f && f->kind == LQER_Q_MXINT_C4;
+  if (!n4) return f;
+  own = *f, own.kind = LQER_Q_MXINT;
+  return &own;
+}
+// what nibble storage asks of the operand's format (a magnitude of at most 7, the 8-byte piece of one block of 16 d): LQER_OK or the refusal
+static int pool_nibble_check(const char* who, const KvPool& p, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt) {
+  const struct { bool n4; const lqer_qfmt_t* f; const char* name; } ops[2] = {{p.k4, k_fmt, "k_fmt"}, {p.v4, v_fmt, "v_fmt"}};
+  for (const auto& o : ops)
+    if (o.n4 && (o.f->width < 2 || o.f->width > 4 || o.f->block != 16)) {
+      set_error("%s: %s of kind LQER_Q_MXINT_C4 with width %d, block %d - nibble codes of the KV pool hold block_fp of width 2..4 with blocks of 16",
+                who, o.name, o.f->width, o.f->block);
+      return LQER_E_UNSUPPORTED;
+    }
+  return LQER_OK;
+}
+// the two formats of a pool entry resolved in place: k_fmt / v_fmt then point at what the checks and the kernels go by, p knows the storage
+struct PoolFmts {
+  lqer_qfmt_t k, v;
+  void resolve(KvPool& p, const lqer_qfmt_t*& k_fmt, const lqer_qfmt_t*& v_fmt) {
+    k_fmt = pool_code_fmt(k_fmt, k, p.k4), v_fmt = pool_code_fmt(v_fmt, v, p.v4);
+  }
+};
+
+size_t lqer_kv_pool_bytes_fmt(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D, const lqer_qfmt_t* k_fmt,
+                              const lqer_qfmt_t* v_fmt) {
+  if (!lqer_kv_pool_bytes(dtype, pages, slots, kv_heads, D) || !k_fmt || !v_fmt) return 0;
+  KvPool p = {};
+  PoolFmts own;
+  own.resolve(p, k_fmt, v_fmt);
+  if (pool_nibble_check("kv_pool_bytes_fmt", p, k_fmt, v_fmt) != LQER_OK) return 0;
+  for (const lqer_qfmt_t* f : {k_fmt, v_fmt})
+    if (f->kind != LQER_Q_MXINT || f->block != 16 || !fmt_ok(f, "attention K / V quantizer", 8)) return 0;
+  return kv_pool_bytes(dtype, pages, slots, kv_heads, D, p.k4, p.v4);
+}
+
 // what append, attention and gather ask of a pool and its page table (host arguments only: the table's and the lengths' CONTENTS are
 // the caller's contract).  A call that addresses sequences through seq_slots / lens (append, attention) needs the two arrays; gather
 // names its slot on the host; a call with per-sequence counts (p.ragged) also needs their starts.  The quantizers are the caller's to
@@ -1596,9 +1641,9 @@ static int kv_pool_check(const char* who, const KvPool& p, PoolUse use) {
     set_error("%s: KV pool %p is not 16-byte aligned", who, p.pool);
     return LQER_E_INVALID;
   }
-  const size_t need = kv_pool_bytes(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  const size_t need = kv_pool_bytes(p.dtype, p.pages, p.slots, p.kv_heads, p.D, p.k4, p.v4);
   if (p.pool_bytes < need) {
-    set_error("%s: KV pool of %zu B < %zu B (lqer_kv_pool_bytes)", who, p.pool_bytes, need);
+    set_error("%s: KV pool of %zu B < %zu B (lqer_kv_pool_bytes%s)", who, p.pool_bytes, need, p.k4 || p.v4 ? "_fmt" : "");
     return LQER_E_INVALID;
   }
   return LQER_OK;
@@ -1618,8 +1663,11 @@ int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t sl
     set_error("kv_pool_append: batch %lld / %lld new keys for the KV pool (batch >= 0, at least one new key)", (long long)batch, (long long)n);
     return LQER_E_INVALID;
   }
-  const KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
-  int rc = kv_codes_check("kv_pool_append", D, k_fmt, v_fmt);
+  KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
+  PoolFmts own;
+  own.resolve(p, k_fmt, v_fmt);
+  int rc = pool_nibble_check("kv_pool_append", p, k_fmt, v_fmt);
+  if (rc == LQER_OK) rc = kv_codes_check("kv_pool_append", D, k_fmt, v_fmt);
   if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append", p, POOL_BATCH);
   if (rc != LQER_OK) return rc;
   if (n > max_len) {
@@ -1650,7 +1698,10 @@ int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int
   }
   KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
   p.ragged = true, p.starts = new_starts, p.total = total;
-  int rc = kv_codes_check("kv_pool_append_ragged", D, k_fmt, v_fmt);
+  PoolFmts own;
+  own.resolve(p, k_fmt, v_fmt);
+  int rc = pool_nibble_check("kv_pool_append_ragged", p, k_fmt, v_fmt);
+  if (rc == LQER_OK) rc = kv_codes_check("kv_pool_append_ragged", D, k_fmt, v_fmt);
   if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append_ragged", p, POOL_BATCH);
   if (rc != LQER_OK) return rc;
   if (max_n > max_len) {
@@ -1671,50 +1722,94 @@ int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int
   return kv_pool_append_ragged_dispatch(p, k_new, v_new, k_strides, v_strides, batch, max_n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
 }
 
-int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
-                        const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
-                        int64_t capacity, void* stream) {
+// gather with and without formats: k_fmt / v_fmt null (both) - lqer_kv_pool_gather, a pool of byte codes
+static int kv_pool_gather(const char* who, const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                          const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
+                          int64_t capacity, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, bool with_fmts, void* stream) {
   if (slot < 0 || slot >= slots || T < 0 || capacity < 1 || T > capacity) {
-    set_error("kv_pool_gather: slot %lld of %lld / %lld keys of the KV pool into a cache of capacity %lld", (long long)slot, (long long)slots,
+    set_error("%s: slot %lld of %lld / %lld keys of the KV pool into a cache of capacity %lld", who, (long long)slot, (long long)slots,
               (long long)T, (long long)capacity);
     return LQER_E_INVALID;
   }
-  const KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, nullptr, nullptr, T > 0 ? T : 1, dtype, kv_heads, D);
-  const int rc = kv_pool_check("kv_pool_gather", p, POOL_ONE_SLOT);
+  KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, nullptr, nullptr, T > 0 ? T : 1, dtype, kv_heads, D);
+  PoolFmts own;
+  int rc = LQER_OK;
+  if (with_fmts) {
+    own.resolve(p, k_fmt, v_fmt);
+    rc = pool_nibble_check(who, p, k_fmt, v_fmt);
+  }
+  if (rc == LQER_OK) rc = kv_pool_check(who, p, POOL_ONE_SLOT);
+  if (rc == LQER_OK && with_fmts) rc = kv_codes_check(who, D, k_fmt, v_fmt);
   if (rc != LQER_OK) return rc;
   if (!cache || (uintptr_t)cache % 16 != 0 || cache_bytes < kv_cache_bytes(dtype, 1, kv_heads, capacity, D)) {
-    set_error("kv_pool_gather: KV cache %p of %zu B - null, not 16-byte aligned or shorter than lqer_kv_cache_bytes(batch 1) = %zu B", cache,
+    set_error("%s: KV cache %p of %zu B - null, not 16-byte aligned or shorter than lqer_kv_cache_bytes(batch 1) = %zu B", who, cache,
               cache_bytes, kv_cache_bytes(dtype, 1, kv_heads, capacity, D));
     return LQER_E_INVALID;
   }
   return kv_pool_gather_dispatch(p, slot, T, cache, capacity, (hipStream_t)stream);
 }
 
-int lqer_kv_pool_fork(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
-                      const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
-                      int64_t n, void* stream) {
+int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                        const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
+                        int64_t capacity, void* stream) {
+  return kv_pool_gather("kv_pool_gather", pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, slot, T, cache, cache_bytes,
+                        capacity, nullptr, nullptr, false, stream);
+}
+
+int lqer_kv_pool_gather_fmt(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                            const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
+                            int64_t capacity, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
+  return kv_pool_gather("kv_pool_gather_fmt", pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, slot, T, cache,
+                        cache_bytes, capacity, k_fmt, v_fmt, true, stream);
+}
+
+// fork with and without formats: without (lqer_kv_pool_fork) a pool of byte codes
+static int kv_pool_fork(const char* who, void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                        const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
+                        int64_t n, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, bool with_fmts, void* stream) {
   if (n < 1) {
-    set_error("kv_pool_fork: %lld pairs for the KV pool (at least one)", (long long)n);
+    set_error("%s: %lld pairs for the KV pool (at least one)", who, (long long)n);
     return LQER_E_INVALID;
   }
   if (!src_slots) {
-    set_error("kv_pool_fork: null src_slots for the KV pool");
+    set_error("%s: null src_slots for the KV pool", who);
     return LQER_E_INVALID;
   }
   if (!kv_dtype_ok(dtype)) {  // (what lqer_kv_pool_bytes rejects, one code for dtype and head dim)
-    set_error("kv_pool_fork: dtype %d - the KV pool takes fp32, fp16 and bf16", dtype);
+    set_error("%s: dtype %d - the KV pool takes fp32, fp16 and bf16", who, dtype);
     return LQER_E_UNSUPPORTED;
   }
   // the bound on the lengths is the room of a table row, or the library's 2^30 where the row has more
   const int64_t room = table_stride < ((int64_t)1 << 26) ? 16 * table_stride : (int64_t)1 << 30;
-  const KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, dst_slots, lens, room, dtype, kv_heads, D);
-  const int rc = kv_pool_check("kv_pool_fork", p, POOL_BATCH);
+  KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, dst_slots, lens, room, dtype, kv_heads, D);
+  PoolFmts own;
+  int rc = LQER_OK;
+  if (with_fmts) {
+    own.resolve(p, k_fmt, v_fmt);
+    rc = pool_nibble_check(who, p, k_fmt, v_fmt);
+  }
+  if (rc == LQER_OK) rc = kv_pool_check(who, p, POOL_BATCH);
+  if (rc == LQER_OK && with_fmts) rc = kv_codes_check(who, D, k_fmt, v_fmt);
   if (rc != LQER_OK) return rc;
   if (n > (((int64_t)1 << 31) - 1) / kv_heads) {  // (a workgroup pair per (pair, kv head) over grid.x)
-    set_error("kv_pool_fork: %lld pairs x %lld kv heads of the KV pool beyond one launch grid: fork in pieces", (long long)n, (long long)kv_heads);
+    set_error("%s: %lld pairs x %lld kv heads of the KV pool beyond one launch grid: fork in pieces", who, (long long)n, (long long)kv_heads);
     return LQER_E_UNSUPPORTED;
   }
   return kv_pool_fork_dispatch(p, src_slots, n, (hipStream_t)stream);
+}
+
+int lqer_kv_pool_fork(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                      const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
+                      int64_t n, void* stream) {
+  return kv_pool_fork("kv_pool_fork", pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, src_slots, dst_slots, lens, n,
+                      nullptr, nullptr, false, stream);
+}
+
+int lqer_kv_pool_fork_fmt(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
+                          const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots, const int32_t* lens,
+                          int64_t n, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
+  return kv_pool_fork("kv_pool_fork_fmt", pool, pool_bytes, dtype, pages, slots, kv_heads, D, block_table, table_stride, src_slots, dst_slots, lens,
+                      n, k_fmt, v_fmt, true, stream);
 }
 
 size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
@@ -1724,6 +1819,14 @@ size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t head
 
 // the check for the kernel that will run, the cache's or the pool's check where K and V come from one, the launches
 static int attn_run(const char* who, const AttnKernel& kn, const AttnCall& c) {
+  if (c.paged && (c.pool.k4 || c.pool.v4)) {  // a pool with nibble codes (PagedAttn resolved k_fmt / v_fmt: non-null where the flag is set)
+    if (const int rc4 = pool_nibble_check(who, c.pool, c.k_fmt, c.v_fmt)) return rc4;
+    if (c.grouped) {
+      set_error("%s: k_fmt / v_fmt of kind LQER_Q_MXINT_C4 - the grouped kernels are not instantiated for nibble codes; "
+                "lqer_attention_q_decode_paged gives the same bits", who);
+      return LQER_E_UNSUPPORTED;
+    }
+  }
   int rc = attn_check(who, kn, c);
   if (rc != LQER_OK) return rc > 0 ? LQER_OK : rc;
   if (c.paged) {
@@ -1799,6 +1902,7 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
 struct PagedAttn {
   AttnCall c;
   int64_t qs[3], os[3];
+  PoolFmts own;  // k_fmt / v_fmt of kind LQER_Q_MXINT_C4 as the formats the kernels go by (pool_code_fmt); c.pool knows the storage
   PagedAttn(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
             const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
             int64_t kv_heads, int64_t S, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
@@ -1808,6 +1912,7 @@ struct PagedAttn {
                     k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream)) {
     c.packed = c.paged = true;
     c.pool = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
+    own.resolve(c.pool, c.k_fmt, c.v_fmt);
   }
   PagedAttn(const PagedAttn&) = delete;
   // per-sequence counts: a stride pair (token, head) becomes the triple (batch, head, row) the record holds, with no batch stride - a

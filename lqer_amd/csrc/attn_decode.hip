@@ -60,6 +60,10 @@
 // is still written by exactly one workgroup (a member's cells of a shared chunk by the leader's, all others by its own) - no atomics,
 // no counters, three launches.  All members of a group with P > 0 have one chunk length (the caller's contract): the leader's C is
 // the C of every row it computes.  P is a licence - a smaller P than the members really share gives the same bits.
+//
+// Nibble codes in the paged pool (template parameter N4 of the two kernels, the paged source without GRP: k_fmt / v_fmt of kind
+// LQER_Q_MXINT_C4, kv_pack.h): the packed stage loads 8 bytes per 16 codes and widens them to the byte codes (kvc::load_codes16) in
+// front of the same codes16_to_bf16 - the scores kernel's flag is K's storage, the PV kernel's V's.  Nothing else differs.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -161,8 +165,9 @@ __device__ __forceinline__ SeqRows seq_rows(const DArgsOf<RAG>& a, int64_t b, in
   }
 }
 
-template <int DT, int SRC, bool WIN, bool RAG, bool GRP>
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4 = false>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, GRP> a) {
+  static_assert(!N4 || (SRC == SRC_PAGED && !GRP), "nibble K codes: the paged pool, no grouped instantiation");
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
         e4 = *(const uint4*)(a.src.ke + blk * D + 16 * dg);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (tq + j < T) c[j] = *(const uint4*)(a.src.kc + (blk * 16 + tq % 16 + j) * D + 16 * dg);
+          if (tq + j < T) c[j] = kvc::load_codes16<N4>(a.src.kc, blk, tq % 16 + j, D, dg);
       }
       const uint32_t eb[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
@@ -344,8 +349,9 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
   }
 }
 
-template <int DT, int SRC, bool WIN, bool RAG, bool GRP>
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4 = false>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> a) {
+  static_assert(!N4 || (SRC == SRC_PAGED && !GRP), "nibble V codes: the paged pool, no grouped instantiation");
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
@@ -396,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> 
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = make_uint4(0, 0, 0, 0);
       const bool gone = dead(tq);
-      if (tq < T && !gone) e4 = kvc::load_v4(a.src, kvc::block<SRC>(a.src, prow, z, g, tq / 16), tq, T, D, db, c);
+      if (tq < T && !gone) e4 = kvc::load_v4<N4>(a.src, kvc::block<SRC>(a.src, prow, z, g, tq / 16), tq, T, D, db, c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -528,11 +534,12 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgsOf<RAG> a) {
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
-template <int DT, int SRC, bool WIN = false, bool RAG = false, bool GRP = false>
+// K4 / V4 (the paged pool): the scores kernel reads K alone and the PV kernel V alone - one flag each
+template <int DT, int SRC, bool WIN = false, bool RAG = false, bool GRP = false, bool K4 = false, bool V4 = false>
 static int launch_decode(const DArgsOf<RAG, GRP>& a, int64_t batch, hipStream_t st) {
   const dim3 grid((unsigned)a.nchs, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT, SRC, WIN, RAG, GRP><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT, SRC, WIN, RAG, GRP><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_scores<DT, SRC, WIN, RAG, GRP, K4><<<grid, 256, 0, st>>>(a);
+  k_attn_dec_pv<DT, SRC, WIN, RAG, GRP, V4><<<grid, 256, 0, st>>>(a);
   // (RAG: a.S is the bound max_s - x over the rows a sequence has at most, y the sequence)
   const dim3 sgrid((unsigned)(((RAG ? a.S * a.heads : a.rows) * (a.D / 4) + 255) / 256), RAG ? (unsigned)batch : 1u);
   k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN, RAG><<<sgrid, 256, 0, st>>>(a);  // (GRP: the plain call's kernel, on the record's base)
@@ -599,6 +606,20 @@ int attention_q_decode_dispatch(const AttnCall& c) {
   } else {
     a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
     a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
+  }
+  if (c.paged && (c.pool.k4 || c.pool.v4)) {  // nibble codes: plain, WIN, RAG and RAG + WIN (no grouped instantiation: the check refused)
+    return with_dtype(c.dtype, [&](auto dt) {
+      return with_flag(c.windowed, [&](auto win) {
+        return with_flag(ragged, [&](auto rag) {
+          return with_flag(c.pool.k4, [&](auto k4) {
+            return with_flag(c.pool.v4, [&](auto v4) {
+              return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, decltype(win)::value, decltype(rag)::value, false, decltype(k4)::value,
+                                         decltype(v4)::value>(a, c.batch, c.st);
+            });
+          });
+        });
+      });
+    });
   }
   // (the window and the per-sequence counts have public entries on the paged source only, so only those instantiations exist)
   if (ragged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true, true>(a, c.batch, c.st); });

@@ -927,6 +927,7 @@ struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayo
   bool ragged;
   const int32_t* starts;
   int64_t total;
+  bool k4, v4;  // the K / V code section holds nibbles (k_fmt / v_fmt of kind LQER_Q_MXINT_C4; kv_pack.h)
 };
 struct AttnCall {
   bool packed, paged;
@@ -971,7 +972,7 @@ int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, 
                              int64_t kv_heads, int64_t capacity, int64_t D, int64_t len, int64_t n, const QP& qk, const QP& qv, hipStream_t st);
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,
                              const QP& qv, float* k_f32, float* v_f32, hipStream_t st);
-size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D);
+size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D, bool k4 = false, bool v4 = false);
 int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
                             const QP& qk, const QP& qv, hipStream_t st);
 int kv_pool_append_ragged_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks2, const int64_t* vs2, int64_t batch,
@@ -1025,6 +1026,12 @@ int with_dtype(int dtype, F&& f) {
   }
   set_error("unknown dtype %d", dtype);
   return LQER_E_INVALID;
+}
+
+// f(std::bool_constant<b>): a run-time flag as a template argument
+template <class F>
+auto with_flag(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 }  // namespace lqer

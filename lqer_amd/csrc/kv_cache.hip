@@ -17,6 +17,9 @@
 //                From the pool: T = lens[b] per sequence of the call (lqer_attention_q_paged).  With the window rule (WIN:
 //                lqer_attention_q_paged_window, lqer_attention_q_paged_ragged_window) nothing of the pool below the page of the first
 //                key the call's first query row sees is read either: tiles wholly below it are not written, the rest of its tile is zeros.
+// NIBBLE codes (the paged pool, per operand - kv_pack.h; template parameters K4 / V4 / N4): the append's store stage packs two codes
+// per byte, every byte written whole by one thread; the readers load 8 bytes where they loaded 16 and widen them in front of the same
+// conversion; gather widens into the dense cache's byte codes; fork copies the smaller item.  Byte pools run the instantiations they ran.
 #include "kv_pack.h"
 
 namespace lqer {
@@ -38,9 +41,11 @@ struct AArgs {
                           // bound max_n, which sizes the grid
 };
 
-// 4 d of one block of 16 keys (x[j][r]: d0 + j of key r) -> the codes of the 16 rows (row pitch D bytes, the four d as one dword) and
-// the four exponent bytes of the block: the K side of an append, dense or paged
-template <int DT>
+// 4 d of one block of 16 keys (x[j][r]: d0 + j of key r) -> the codes of the 16 rows (kc: the block's first row at d0; row pitch D bytes,
+// the four d as one dword) and the four exponent bytes of the block: the K side of an append, dense or paged.  N4 (nibble codes, kc at
+// d0 / 2, row pitch D / 2): the four d are the two WHOLE bytes d0 / 2, d0 / 2 + 1 of every row - one 2-byte store, no byte shared with
+// another thread and none read back, so a dirty page leaves no stale neighbour nibble
+template <int DT, bool N4>
 __device__ __forceinline__ void store_kblock4(const float (&x)[4][16], const QP& qk, unsigned char* kc, int64_t D, unsigned char* ke) {
   uint32_t cw[4][4], eb = 0;
 #pragma unroll
@@ -48,20 +53,24 @@ __device__ __forceinline__ void store_kblock4(const float (&x)[4][16], const QP&
 #pragma unroll
   for (int r = 0; r < 16; ++r) {  // key r of the block: the four d as one dword
     const int sh = 8 * (r & 3);
-    *(uint32_t*)(kc + r * D) = ((cw[0][r >> 2] >> sh) & 0xffu) | (((cw[1][r >> 2] >> sh) & 0xffu) << 8) |
-                               (((cw[2][r >> 2] >> sh) & 0xffu) << 16) | (((cw[3][r >> 2] >> sh) & 0xffu) << 24);
+    const uint32_t c4 = ((cw[0][r >> 2] >> sh) & 0xffu) | (((cw[1][r >> 2] >> sh) & 0xffu) << 8) |
+                        (((cw[2][r >> 2] >> sh) & 0xffu) << 16) | (((cw[3][r >> 2] >> sh) & 0xffu) << 24);
+    if constexpr (N4) *(unsigned short*)(kc + r * code_pitch<true>(D)) = (unsigned short)narrow8(c4, 0);
+    else *(uint32_t*)(kc + r * D) = c4;
   }
   *(uint32_t*)ke = eb;
 }
 
-// 16 d of one new V row -> its 16 codes and its exponent byte: the V side of an append, dense or paged
-template <int DT>
+// 16 d of one new V row -> its 16 codes (16 bytes, or with N4 the 8 bytes of their nibbles) and its exponent byte: the V side of an
+// append, dense or paged
+template <int DT, bool N4>
 __device__ __forceinline__ void store_vrow16(const void* vn, int64_t off, bool vec, const QP& qv, unsigned char* vc, unsigned char* ve) {
   float x[16];
   load16<DT>(vn, off, 16, vec, x);
   uint32_t cw[4];
   const uint32_t eb = quant16_codes<DT != LQER_F16>(x, qv, cw);
-  *(uint4*)vc = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  if constexpr (N4) *(uint2*)vc = make_uint2(narrow8(cw[0], cw[1]), narrow8(cw[2], cw[3]));
+  else *(uint4*)vc = make_uint4(cw[0], cw[1], cw[2], cw[3]);
   *ve = (unsigned char)eb;
 }
 
@@ -88,9 +97,11 @@ __device__ __forceinline__ void copy_raw4(const void* kn, int64_t src, bool vec,
 // starts[b] from the device; its threads at a block or a key beyond n_b - all of them with n_b = 0 - leave at once, before any load
 // or store.  The argument above holds per sequence as it stands: block j = 0 of (sequence, kv head, d0) exists for every n_b >= 1, its
 // one thread is the only reader of the staging column and the only writer of it, reads first; the later blocks start beyond len.
-template <int DT, int SRC, bool RAG = false>
+// K4 / V4 (the paged pool): the K / V code section holds nibbles - the store stage alone differs (store_kblock4, store_vrow16).
+template <int DT, int SRC, bool RAG = false, bool K4 = false, bool V4 = false>
 __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
   static_assert(!RAG || SRC == attn::SRC_PAGED, "per-sequence counts come with per-sequence lengths");
+  static_assert(!(K4 || V4) || SRC == attn::SRC_PAGED, "nibble codes are a storage of the paged pool");
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int D = (int)a.D, dq = D / 4, db_n = D / 16;
   const int64_t kvh = a.src.kvh, Z = a.batch * kvh, nK = Z * a.nkb * dq, nV = Z * a.n * db_n;
@@ -120,7 +131,7 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) x[jj][r] = v4[jj];
     }
-    store_kblock4<DT>(x, a.qk, a.src.kc + blk * 16 * a.D + d0, a.D, a.src.ke + blk * a.D + d0);
+    store_kblock4<DT, K4>(x, a.qk, a.src.kc + blk * 16 * code_pitch<K4>(a.D) + (K4 ? d0 / 2 : d0), a.D, a.src.ke + blk * a.D + d0);
     if (j == 0) {  // the raw keys of the block left open -> staging rows t % 16 of this thread's column
       const int64_t open0 = end / 16 * 16, s0 = open0 > len ? open0 : len;
       for (int64_t t = s0; t < end; ++t) copy_raw4<DT>(a.kn, kn0 + (t - len) * a.k_rs, a.kvec, a.src.stage, (zs * 16 + t % 16) * a.D + d0);
@@ -139,8 +150,8 @@ __global__ __launch_bounds__(256) void k_kv_append(const AArgs a) {
     const int64_t t = seq<SRC>(a.src, b, a.len, row) + j;
     const int db = (int)(rem % db_n);
     const int64_t blk = block<SRC>(a.src, row, z, g, t / 16);
-    store_vrow16<DT>(a.vn, b * a.v_bs + g * a.v_hs + (tok0 + j) * a.v_rs + 16 * db, a.vvec, a.qv, a.src.vc + (blk * 16 + t % 16) * a.D + 16 * db,
-                     a.src.ve + (blk * db_n + db) * 16 + t % 16);
+    store_vrow16<DT, V4>(a.vn, b * a.v_bs + g * a.v_hs + (tok0 + j) * a.v_rs + 16 * db, a.vvec, a.qv,
+                         a.src.vc + (blk * 16 + t % 16) * code_pitch<V4>(a.D) + (V4 ? 8 : 16) * db, a.src.ve + (blk * db_n + db) * 16 + t % 16);
   }
 }
 
@@ -153,6 +164,9 @@ struct GArgs {
 
 // One sequence out of the pool into a dense cache of batch 1: bytes as they are, in 16-byte pieces.  A thread: one piece of one
 // (kv head, block) - D pieces of K codes, D / 16 of K exponents, D of V codes, D / 16 of V exponents - or one piece of the staging rows.
+// K4 / V4: the pool's K / V codes are nibbles and the dense cache's are bytes, as ever - a 16-byte piece of the cache is then the 8-byte
+// piece of the pool at the same index, widened (16 codes of one block of 16 d: the pieces of an item number alike on both sides).
+template <bool K4 = false, bool V4 = false>
 __global__ __launch_bounds__(256) void k_kv_pool_gather(const GArgs a) {
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t e16 = a.D / 16, per = 2 * (a.D + e16), nB = a.kvh * a.nblk * per;
@@ -165,7 +179,8 @@ __global__ __launch_bounds__(256) void k_kv_pool_gather(const GArgs a) {
     if (sec == 1 && u >= e16) u -= e16, sec = 2;
     if (sec == 2 && u >= a.D) u -= a.D, sec = 3;
     const int64_t item = (sec & 1) ? e16 : a.D;  // 16-byte pieces of a block in this section
-    ((uint4*)a.dst[sec])[dblk * item + u] = ((const uint4*)a.src[sec])[sblk * item + u];
+    if ((K4 && sec == 0) || (V4 && sec == 2)) ((uint4*)a.dst[sec])[dblk * item + u] = widen16(((const uint2*)a.src[sec])[sblk * item + u]);
+    else ((uint4*)a.dst[sec])[dblk * item + u] = ((const uint4*)a.src[sec])[sblk * item + u];
     return;
   }
   i -= nB;
@@ -176,6 +191,7 @@ struct FArgs {
   KvSrc<unsigned char> src;  // the pool; src.slots / src.lens: the CHILD's slot and the length forked at, per pair (device)
   const int32_t* from;       // the parent's slot, per pair (device)
   int64_t D, stage16;        // 16-byte pieces of a kv head's staging rows
+  int64_t kc16, vc16;        // 16-byte pieces of an item's K / V codes: D with byte codes, D / 2 with nibbles
 };
 
 // Fork: pair i makes the sequence in slot src.slots[i] a copy of the first L = src.lens[i] keys of the one in slot from[i], whose full
@@ -194,15 +210,15 @@ __global__ __launch_bounds__(256) void k_kv_pool_fork(const FArgs a) {
     return;
   }
   if (L % 16 == 0) return;  // (uniform over the workgroup)
-  const int64_t e16 = a.D / 16, per = 2 * (a.D + e16);
+  const int64_t e16 = a.D / 16, per = a.kc16 + a.vc16 + 2 * e16;
   const int64_t sblk = page_block(slot_row(a.src, from), kvh, g, L / 16), dblk = page_block(drow, kvh, g, L / 16);
   for (int64_t p = threadIdx.x; p < per; p += 256) {
     int64_t u = p;
     int sec = 0;
-    if (u >= a.D) u -= a.D, sec = 1;
+    if (u >= a.kc16) u -= a.kc16, sec = 1;
     if (sec == 1 && u >= e16) u -= e16, sec = 2;
-    if (sec == 2 && u >= a.D) u -= a.D, sec = 3;
-    const int64_t item = (sec & 1) ? e16 : a.D;  // 16-byte pieces of a block in this section
+    if (sec == 2 && u >= a.vc16) u -= a.vc16, sec = 3;
+    const int64_t item = sec == 0 ? a.kc16 : sec == 2 ? a.vc16 : e16;  // 16-byte pieces of a block in this section
     uint4* base = (uint4*)(sec == 0 ? a.src.kc : sec == 1 ? a.src.ke : sec == 2 ? a.src.vc : a.src.ve);
     base[dblk * item + u] = base[sblk * item + u];
   }
@@ -251,7 +267,8 @@ __device__ __forceinline__ int64_t window_lo(const IArgs& a, int64_t b, int64_t 
 // trip behind it - and keys at and beyond lens[b] are zeros up to the end of the 64-key tile k_attn_q reads last; a workgroup (32 or 64
 // keys) that starts beyond that tile writes nothing and leaves at once: a short sequence of a ragged batch costs its own keys.
 // WIN: a workgroup whose keys all lie below the tile of lo (window_lo) leaves too, and keys below lo's page are zeros, unread.
-template <int SRC, bool WIN = false>
+// N4: the pool's K codes are nibbles - an 8-byte load, widened in front of the same conversion.
+template <int SRC, bool WIN = false, bool N4 = false>
 __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
   static_assert(!WIN || SRC == attn::SRC_PAGED, "the window rule runs on the paged pool");
   const int64_t z = blockIdx.y, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -272,7 +289,7 @@ __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
   uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (t < T && d0 < a.D && (!WIN || t >= live)) {
     const int64_t blk = block<SRC>(a.src, prow, z, g, t / 16);
-    const uint4 c = *(const uint4*)(a.src.kc + (blk * 16 + t % 16) * a.D + d0), e = *(const uint4*)(a.src.ke + blk * a.D + d0);
+    const uint4 c = load_codes16<N4>(a.src.kc, blk, t % 16, a.D, d0 / 16), e = *(const uint4*)(a.src.ke + blk * a.D + d0);
     const uint32_t eb[4] = {e.x, e.y, e.z, e.w};
     codes16_to_bf16(c, eb, a.qk, w);
   }
@@ -296,7 +313,8 @@ __global__ __launch_bounds__(256) void k_kv_kimage(const IArgs a) {
 // workgroup whose 64 keys start at or beyond T (a tile k_attn_q does not read for this sequence) leaves before the barrier.
 // WIN: so does a workgroup whose 64 keys lie below the tile of lo (window_lo); the four keys of a thread lie in one page, below lo's -
 // zeros, nothing read - or not.
-template <int SRC, bool WIN = false>
+// N4: the pool's V codes are nibbles (load_v4).
+template <int SRC, bool WIN = false, bool N4 = false>
 __global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
   static_assert(!WIN || SRC == attn::SRC_PAGED, "the window rule runs on the paged pool");
   __shared__ __attribute__((aligned(16))) unsigned char tile[ATTN_V_ROWS * 128];
@@ -324,7 +342,7 @@ __global__ __launch_bounds__(128) void k_kv_vimage(const IArgs a) {
       for (int j = 0; j < 8; ++j) w[r][j] = 0;
     if (16 * db < a.D && t < T && (!WIN || t >= live)) {  // (t < T <= cap, t a multiple of 4: the dword of exponents lies inside the section)
       uint4 c[4];
-      const uint32_t e4 = load_v4(a.src, block<SRC>(a.src, prow, z, g, t / 16), t, T, (int)a.D, db, c);
+      const uint32_t e4 = load_v4<N4>(a.src, block<SRC>(a.src, prow, z, g, t / 16), t, T, (int)a.D, db, c);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (t + r < T) {
@@ -358,8 +376,9 @@ size_t kv_cache_bytes(int dtype, int64_t batch, int64_t kv_heads, int64_t capaci
   return kvc::layout(dtype, batch, kv_heads, capacity, D).total;
 }
 
-// the one append: nkb blocks of 16 keys per (sequence, kv head) on the grid (kvc::AArgs); starts: the per-sequence counts' (RAG), else null
-template <int SRC, bool RAG = false>
+// the one append: nkb blocks of 16 keys per (sequence, kv head) on the grid (kvc::AArgs); starts: the per-sequence counts' (RAG), else null;
+// K4 / V4: the pool's code sections that hold nibbles
+template <int SRC, bool RAG = false, bool K4 = false, bool V4 = false>
 static int kv_append(const kvc::KvSrc<unsigned char>& src, int dtype, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs,
                      int64_t batch, int64_t D, int64_t len, int64_t n, int64_t nkb, const QP& qk, const QP& qv, hipStream_t st, const char* who,
                      const int32_t* starts = nullptr) {
@@ -372,7 +391,7 @@ static int kv_append(const kvc::KvSrc<unsigned char>& src, int dtype, const void
   a.kvec = al16(k_new, ks, esz), a.vvec = al16(v_new, vs, esz);
   const int64_t items = batch * src.kvh * (nkb * (D / 4) + n * (D / 16));
   return with_dtype(dtype, [&](auto dt) {
-    kvc::k_kv_append<decltype(dt)::value, SRC, RAG><<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
+    kvc::k_kv_append<decltype(dt)::value, SRC, RAG, K4, V4><<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
     return check_launch(who);
   });
 }
@@ -384,22 +403,33 @@ int kv_cache_append_dispatch(void* cache, const void* k_new, const void* v_new, 
                                      "lqer_kv_cache_append");
 }
 
-size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D) {
-  return kvc::pool_layout(dtype, pages, slots, kv_heads, D).total;
+size_t kv_pool_bytes(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D, bool k4, bool v4) {
+  return kvc::pool_layout(dtype, pages, slots, kv_heads, D, k4, v4).total;
+}
+
+// the pool's append, uniform or with per-sequence counts, on the instantiation of the pool's code storage (p.k4, p.v4)
+template <bool RAG>
+static int kv_pool_append(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
+                          const QP& qk, const QP& qv, hipStream_t st, const char* who) {
+  return with_flag(p.k4, [&](auto k4) {
+    return with_flag(p.v4, [&](auto v4) {
+      return kv_append<attn::SRC_PAGED, RAG, decltype(k4)::value, decltype(v4)::value>(kvc::src_of<unsigned char>(p), p.dtype, k_new, v_new, ks, vs, batch,
+                                                                                       p.D, 0, n, (n + 14) / 16 + 1, qk, qv, st, who,
+                                                                                       RAG ? p.starts : nullptr);
+    });
+  });
 }
 
 int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks, const int64_t* vs, int64_t batch, int64_t n,
                             const QP& qk, const QP& qv, hipStream_t st) {
-  return kv_append<attn::SRC_PAGED>(kvc::src_of<unsigned char>(p), p.dtype, k_new, v_new, ks, vs, batch, p.D, 0, n, (n + 14) / 16 + 1, qk, qv, st,
-                                    "lqer_kv_pool_append");
+  return kv_pool_append<false>(p, k_new, v_new, ks, vs, batch, n, qk, qv, st, "lqer_kv_pool_append");
 }
 
 // p.starts: [batch + 1] token starts (device); ks2 / vs2: elements over token / kv head of [total][kv_heads][D]; the grid follows max_n
 int kv_pool_append_ragged_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks2, const int64_t* vs2, int64_t batch,
                                    int64_t max_n, const QP& qk, const QP& qv, hipStream_t st) {
   const int64_t ks[3] = {0, ks2[1], ks2[0]}, vs[3] = {0, vs2[1], vs2[0]};
-  return kv_append<attn::SRC_PAGED, true>(kvc::src_of<unsigned char>(p), p.dtype, k_new, v_new, ks, vs, batch, p.D, 0, max_n, (max_n + 14) / 16 + 1, qk,
-                                          qv, st, "lqer_kv_pool_append_ragged", p.starts);
+  return kv_pool_append<true>(p, k_new, v_new, ks, vs, batch, max_n, qk, qv, st, "lqer_kv_pool_append_ragged");
 }
 
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st) {
@@ -409,13 +439,18 @@ int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cach
   a.row = p.block_table + slot * p.table_stride, a.slot = slot, a.kvh = p.kv_heads, a.D = p.D;
   a.nblk = (T + 15) / 16, a.capb = d.cap16, a.stage16 = p.D * (p.dtype == LQER_F32 ? 4 : 2);  // 16 rows x D x esz / 16
   const int64_t items = p.kv_heads * (a.nblk * 2 * (p.D + p.D / 16) + a.stage16);
-  kvc::k_kv_pool_gather<<<dim3((unsigned)((items + 255) / 256)), 256, 0, st>>>(a);
-  return check_launch("lqer_kv_pool_gather");
+  const dim3 grid((unsigned)((items + 255) / 256));  // (the pieces of an item number alike with byte and with nibble codes)
+  if (p.k4 && p.v4) kvc::k_kv_pool_gather<true, true><<<grid, 256, 0, st>>>(a);
+  else if (p.k4) kvc::k_kv_pool_gather<true, false><<<grid, 256, 0, st>>>(a);
+  else if (p.v4) kvc::k_kv_pool_gather<false, true><<<grid, 256, 0, st>>>(a);
+  else kvc::k_kv_pool_gather<><<<grid, 256, 0, st>>>(a);
+  return check_launch(p.k4 || p.v4 ? "lqer_kv_pool_gather_fmt" : "lqer_kv_pool_gather");
 }
 
 // p.seq_slots: the children's slots; the grid comes from n and kv_heads alone
 int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, hipStream_t st) {
-  kvc::FArgs a = {kvc::src_of<unsigned char>(p), src_slots, p.D, p.D * (p.dtype == LQER_F32 ? 4 : 2)};  // 16 rows x D x esz / 16
+  kvc::FArgs a = {kvc::src_of<unsigned char>(p), src_slots, p.D, p.D * (p.dtype == LQER_F32 ? 4 : 2),  // 16 rows x D x esz / 16
+                  kvc::code_pitch(p.D, p.k4), kvc::code_pitch(p.D, p.v4)};                             // 16 rows x pitch / 16
   kvc::k_kv_pool_fork<<<dim3((unsigned)(n * p.kv_heads), 2), 256, 0, st>>>(a);
   return check_launch("lqer_kv_pool_fork");
 }
@@ -438,12 +473,16 @@ void kv_cache_images_dispatch(const AttnCall& c, bf16_t* kimg, int64_t Tp, int64
   a.qk = make_qp(*c.k_fmt), a.qv = make_qp(*c.v_fmt);
   a.window = c.window, a.S = c.S, a.q_starts = c.paged && c.pool.ragged ? c.pool.starts : nullptr;  // (read by the WIN kernels alone)
   const dim3 kgrid((unsigned)(Tp * (Dp / 16) / 256), (unsigned)(c.batch * c.kv_heads)), vgrid((unsigned)(Tv / 64), (unsigned)(c.batch * c.kv_heads));
-  if (c.paged && c.windowed) {
-    kvc::k_kv_kimage<attn::SRC_PAGED, true><<<kgrid, 256, 0, c.st>>>(a);
-    kvc::k_kv_vimage<attn::SRC_PAGED, true><<<vgrid, 128, 0, c.st>>>(a);
+  if (c.paged && c.windowed) {  // (each image kernel reads one operand: its own flag of the pool's code storage)
+    if (c.pool.k4) kvc::k_kv_kimage<attn::SRC_PAGED, true, true><<<kgrid, 256, 0, c.st>>>(a);
+    else kvc::k_kv_kimage<attn::SRC_PAGED, true><<<kgrid, 256, 0, c.st>>>(a);
+    if (c.pool.v4) kvc::k_kv_vimage<attn::SRC_PAGED, true, true><<<vgrid, 128, 0, c.st>>>(a);
+    else kvc::k_kv_vimage<attn::SRC_PAGED, true><<<vgrid, 128, 0, c.st>>>(a);
   } else if (c.paged) {
-    kvc::k_kv_kimage<attn::SRC_PAGED><<<kgrid, 256, 0, c.st>>>(a);
-    kvc::k_kv_vimage<attn::SRC_PAGED><<<vgrid, 128, 0, c.st>>>(a);
+    if (c.pool.k4) kvc::k_kv_kimage<attn::SRC_PAGED, false, true><<<kgrid, 256, 0, c.st>>>(a);
+    else kvc::k_kv_kimage<attn::SRC_PAGED><<<kgrid, 256, 0, c.st>>>(a);
+    if (c.pool.v4) kvc::k_kv_vimage<attn::SRC_PAGED, false, true><<<vgrid, 128, 0, c.st>>>(a);
+    else kvc::k_kv_vimage<attn::SRC_PAGED><<<vgrid, 128, 0, c.st>>>(a);
   } else {
     kvc::k_kv_kimage<attn::SRC_PACKED><<<kgrid, 256, 0, c.st>>>(a);
     kvc::k_kv_vimage<attn::SRC_PACKED><<<vgrid, 128, 0, c.st>>>(a);

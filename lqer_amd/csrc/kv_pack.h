@@ -7,6 +7,12 @@
 // knows a -0 (a negative value that rounds to zero keeps its sign in the slow path; an fp16 -0 in the fast one): sign-magnitude
 // carries it, and the way back is a v_cvt_f32_ubyte, a multiply and an OR of the sign - no sign extension, no special code.
 // An exponent byte is e - emin = e + exp_bias (0 .. 2^exp_width - 1); a zero block stores the exponent closest to 0.
+//
+// NIBBLE codes (the paged pool only, per operand: LQER_Q_MXINT_C4 as k_fmt / v_fmt, width <= 4, so the magnitude is at most 7): two
+// codes per byte, a nibble = sign << 3 | magnitude, elements d = 2 j and 2 j + 1 of a key's row the low and the high nibble of byte j.
+// A key's row is then D / 2 bytes and the 16 codes of one block of 16 d one aligned 8-byte piece.  The row pitch (code_pitch), the way
+// to nibbles (narrow8) and the way back to the byte codes (widen16, in front of codes16_to_bf16) are spelled here once; the kernels
+// take the storage as a template parameter N4 and everything else about an item - exponents, staging rows, the item index - is as it was.
 #pragma once
 #include "qmm_image.h"
 
@@ -49,15 +55,20 @@ struct PoolLayout {
   size_t k_codes, k_exps, v_codes, v_exps, k_stage, total;
 };
 
-// D a multiple of 16, dtype one of the three: the caller checked
-__host__ inline PoolLayout pool_layout(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D) {
+// bytes of one key's row of codes: a byte per element, or (N4) a nibble
+template <bool N4>
+__host__ __device__ constexpr int64_t code_pitch(int64_t D) { return N4 ? D / 2 : D; }
+__host__ inline int64_t code_pitch(int64_t D, bool n4) { return n4 ? code_pitch<true>(D) : code_pitch<false>(D); }
+
+// D a multiple of 16, dtype one of the three: the caller checked.  k4 / v4: the operand's code section holds nibbles
+__host__ inline PoolLayout pool_layout(int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D, bool k4 = false, bool v4 = false) {
   PoolLayout l;
   const size_t items = (size_t)(pages * kv_heads), esz = dtype == LQER_F32 ? 4 : 2;
-  const size_t codes = up256(items * 16 * D), exps = up256(items * D);
+  const size_t exps = up256(items * D);
   l.k_codes = 0;
-  l.k_exps = l.k_codes + codes;
+  l.k_exps = l.k_codes + up256(items * 16 * code_pitch(D, k4));
   l.v_codes = l.k_exps + exps;
-  l.v_exps = l.v_codes + codes;
+  l.v_exps = l.v_codes + up256(items * 16 * code_pitch(D, v4));
   l.k_stage = l.v_exps + exps;
   l.total = l.k_stage + up256((size_t)(slots * kv_heads) * 16 * D * esz);
   return l;
@@ -82,7 +93,7 @@ __host__ inline KvSrc<B> src_of(B* cache, const Layout& l) {
 }
 template <class B = const unsigned char>  // (the one place that turns a pool into section pointers)
 __host__ inline KvSrc<B> src_of(const KvPool& p) {
-  const PoolLayout l = pool_layout(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  const PoolLayout l = pool_layout(p.dtype, p.pages, p.slots, p.kv_heads, p.D, p.k4, p.v4);
   B* base = (B*)p.pool;
   return {base + l.k_codes, base + l.k_exps, base + l.v_codes, base + l.v_exps, 0, (int)p.kv_heads, p.block_table, p.seq_slots, p.lens, p.table_stride, base + l.k_stage};
 }
@@ -112,14 +123,41 @@ __device__ __forceinline__ int64_t block(const KvSrc<B>& s, const int32_t* row, 
   else return z * s.cap16 + kb;
 }
 
+// eight nibbles -> their byte codes: (n & 7) | ((n & 8) << 4), nibble i of x in byte i of the pair
+__device__ __forceinline__ uint2 widen8(uint32_t x) {
+  uint32_t lo = x & 0xffffu, hi = x >> 16;
+  lo = (lo | (lo << 8)) & 0x00ff00ffu, hi = (hi | (hi << 8)) & 0x00ff00ffu;
+  lo = (lo | (lo << 4)) & 0x0f0f0f0fu, hi = (hi | (hi << 4)) & 0x0f0f0f0fu;
+  return make_uint2((lo & 0x07070707u) | ((lo & 0x08080808u) << 4), (hi & 0x07070707u) | ((hi & 0x08080808u) << 4));
+}
+// the 8-byte piece of 16 nibbles -> the uint4 of 16 byte codes codes16_to_bf16 takes
+__device__ __forceinline__ uint4 widen16(const uint2& n) {
+  const uint2 a = widen8(n.x), b = widen8(n.y);
+  return make_uint4(a.x, a.y, b.x, b.y);
+}
+// eight byte codes of magnitude <= 7 (lo: elements 0 - 3, hi: 4 - 7) -> eight nibbles, element i in nibble i: widen8's inverse
+__device__ __forceinline__ uint32_t narrow8(uint32_t lo, uint32_t hi) {
+  lo = (lo & 0x07070707u) | ((lo >> 4) & 0x08080808u), hi = (hi & 0x07070707u) | ((hi >> 4) & 0x08080808u);
+  lo = (lo | (lo >> 4)) & 0x00ff00ffu, hi = (hi | (hi >> 4)) & 0x00ff00ffu;
+  lo = (lo | (lo >> 8)) & 0xffffu, hi = (hi | (hi >> 8)) & 0xffffu;
+  return lo | (hi << 16);
+}
+
+// the 16 codes of (row r of block blk, block dg of 16 d) of a code section as byte codes: one 16-byte load, or (N4) one 8-byte load, widened
+template <bool N4, class B>
+__device__ __forceinline__ uint4 load_codes16(const B* codes, int64_t blk, int64_t r, int64_t D, int dg) {
+  if constexpr (N4) return widen16(*(const uint2*)(codes + (blk * 16 + r) * code_pitch<true>(D) + 8 * dg));
+  else return *(const uint4*)(codes + (blk * 16 + r) * D + 16 * dg);
+}
+
 // 16 d (block db of D / 16) of the V rows of keys t .. t + 3 of block blk, t a multiple of 4: the dword of their four exponents
 // (returned) and the four 16-byte code rows; a key at or beyond T is not read and leaves c[r] as it was
-template <class B>
+template <bool N4 = false, class B>
 __device__ __forceinline__ uint32_t load_v4(const KvSrc<B>& s, int64_t blk, int64_t t, int64_t T, int D, int db, uint4 (&c)[4]) {
   const uint32_t e4 = *(const uint32_t*)(s.ve + (blk * (D / 16) + db) * 16 + t % 16);
 #pragma unroll
   for (int r = 0; r < 4; ++r)
-    if (t + r < T) c[r] = *(const uint4*)(s.vc + (blk * 16 + t % 16 + r) * D + 16 * db);
+    if (t + r < T) c[r] = load_codes16<N4>(s.vc, blk, t % 16 + r, D, db);
   return e4;
 }
 

@@ -222,8 +222,26 @@ def _pair(t: torch.Tensor):
     return (C.c_int64 * 2)(t.stride(0), t.stride(1))
 
 
-def pool_bytes(dtype: torch.dtype, pages: int, slots: int, kv_heads: int, head_dim: int) -> int:
-    return _lib.lib().lqer_kv_pool_bytes(ops._DT[dtype], pages, slots, kv_heads, head_dim)
+def pool_bytes(dtype: torch.dtype, pages: int, slots: int, kv_heads: int, head_dim: int, k_fmt=None, v_fmt=None) -> int:
+    """lqer_kv_pool_bytes, or - with the pool's K and V formats, either of which may name nibble codes (ops.nibble_qfmt) -
+    lqer_kv_pool_bytes_fmt."""
+    if k_fmt is None and v_fmt is None:
+        return _lib.lib().lqer_kv_pool_bytes(ops._DT[dtype], pages, slots, kv_heads, head_dim)
+    return _lib.lib().lqer_kv_pool_bytes_fmt(ops._DT[dtype], pages, slots, kv_heads, head_dim, C.byref(k_fmt), C.byref(v_fmt))
+
+
+def _code_bits(code_bits, fmts):
+    """PagedKVCache's code_bits -> (K bits, V bits), each 8 (a byte per code) or 4 (a nibble): None or 8 - bytes for both; 4 - nibbles
+    for both; a pair - K and V on their own.  ValueError for anything else, and for 4 on an operand whose config is wider than 4 bits."""
+    pair = (code_bits, code_bits) if code_bits is None or isinstance(code_bits, int) else tuple(code_bits)
+    if len(pair) != 2 or any(isinstance(b, bool) or b not in (None, 4, 8) for b in pair):
+        raise ValueError(f"PagedKVCache: code_bits {code_bits!r} - None, 8, 4 or a pair (k_bits, v_bits) of those")
+    pair = tuple(8 if b is None else b for b in pair)
+    for name, bits, f in zip(("K", "V"), pair, (fmts[1], fmts[3])):
+        if bits == 4 and f.width > 4:
+            raise ValueError(f"PagedKVCache: code_bits 4 for {name}, whose config is block_fp of width {f.width} - a nibble holds a sign and a "
+                             "magnitude of at most 7: widths 2..4")
+    return pair
 
 
 class PageTable:
@@ -511,13 +529,23 @@ class PagedKVCache:
       - after such an append a sequence holds at most (W + R + 29) // 16 pages, and the bound is reached (R = 8: (W + 37) // 16);
       - for every later call of s <= R rows on a sequence of T keys, 16 released <= max(0, T - s - W + 1): the page of the first key
         the call's first row sees is still there.  A call that breaks it (more rows than R) raises ValueError: the keys are gone.
-    With window=None nothing is ever released, and R only allows an explicit window= on the prefill route."""
+    With window=None nothing is ever released, and R only allows an explicit window= on the prefill route.
+
+    code_bits (None or 8: a byte per code, the pool as ever; 4; or a pair (k_bits, v_bits)): 4 stores the operand's codes as NIBBLES -
+    for configs of width <= 4 (ValueError otherwise, before anything is allocated), where sign and magnitude are exactly four bits:
+    2 d (1/2 + 1/16) bytes per token and kv head instead of 2 d (1 + 1/16), 144 B against 272 B at d = 128, so the same memory holds
+    1.89x the tokens.  The values are those of the byte pool of the same configs - the storage changes no rounding - and every method
+    and every attention_flexible_paged* function works unchanged: `.nbytes` is the smaller pool (lqer_kv_pool_bytes_fmt), to_dense()
+    gives a byte QuantizedKVCache (lqer_kv_pool_gather_fmt widens the nibbles), fork copies the smaller item.  K and V choose on
+    their own: (8, 4) keeps a wide K beside a 4-bit V.  shared_prefix=True runs the ungrouped call on such a pool (the grouped
+    kernels are not instantiated for nibble codes; the bits are the same by that feature's contract)."""
 
     covers = staticmethod(QuantizedKVCache.covers)
 
     def __init__(self, num_pages: int, max_seqs: int, kv_heads: int, head_dim: int, cfg0: dict, cfg1: dict, dtype: torch.dtype, device,
-                 max_pages_per_seq=None, window=None, max_query_rows=None):
+                 max_pages_per_seq=None, window=None, max_query_rows=None, code_bits=None):
         _check_covers("PagedKVCache", cfg0, cfg1, head_dim, dtype)
+        self.code_bits = _code_bits(code_bits, _attn_fmts(cfg0, cfg1))  # (raises before anything is allocated)
         _window_arg("PagedKVCache", window, None, causal=True)  # (no call, so no causal to ask for)
         if max_query_rows is not None and (not isinstance(max_query_rows, int) or isinstance(max_query_rows, bool)
                                            or max_query_rows < _ATTN_DECODE_MAX_S):
@@ -529,7 +557,13 @@ class PagedKVCache:
         self.kv_heads, self.head_dim, self.dtype, self.device = kv_heads, head_dim, dtype, torch.device(device)
         self.cfg0, self.cfg1 = cfg0, cfg1
         self.fmts = _attn_fmts(cfg0, cfg1)  # Q, K^T, P, V
-        self.buf = torch.empty(pool_bytes(dtype, num_pages, max_seqs, kv_heads, head_dim), dtype=torch.uint8, device=self.device)
+        self.nibble = 4 in self.code_bits  # some code section holds nibbles: K and V then carry the kind that says which, in every call
+        if self.nibble:
+            for i, bits in zip((1, 3), self.code_bits):
+                if bits == 4:
+                    self.fmts[i] = ops.nibble_qfmt(self.fmts[i])
+        self.buf = torch.empty(pool_bytes(dtype, num_pages, max_seqs, kv_heads, head_dim, *((self.fmts[1], self.fmts[3]) if self.nibble else ())),
+                               dtype=torch.uint8, device=self.device)
         # the device copies of the metadata: the table (rows updated when they change), the slots and the lengths of the current call
         self.table = torch.zeros(max_seqs, self.pt.max_pages_per_seq, dtype=torch.int32, device=self.device)
         self._slots = torch.zeros(max_seqs, dtype=torch.int32, device=self.device)
@@ -714,6 +748,11 @@ class PagedKVCache:
             raise
         return children
 
+    def _with_code_fmts(self, entry):
+        """A pool entry that takes no formats (gather, fork) as this pool calls it: `entry` and no formats on a pool of byte codes, its
+        _fmt sibling and the K and V formats, which name the storage, on one with nibble codes."""
+        return (entry + "_fmt", (C.byref(self.fmts[1]), C.byref(self.fmts[3]))) if self.nibble else (entry, ())
+
     def _launch_fork(self, src, dst, lens) -> None:
         """The children's table rows, then the one launch.  Everything the device needs goes up in ONE small copy - the three arrays of
         the call, and (child's slot, entry, page) of every open block - and the rows are made on the device: the parent's row, which
@@ -732,10 +771,11 @@ class PagedKVCache:
             k = len(own)
             self.table.index_put_((idx[3, :k], idx[4, :k]), meta[5, :k])
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().lqer_kv_pool_fork(self.buf.data_ptr(), self.buf.numel(), ops._DT[self.dtype], self.pt.num_pages, self.pt.max_seqs,
-                                                    self.kv_heads, self.head_dim, self.table.data_ptr(), self.pt.max_pages_per_seq,
-                                                    meta[0].data_ptr(), meta[1].data_ptr(), meta[2].data_ptr(), n, ops._stream(self.device)),
-                       "lqer_kv_pool_fork")
+            name, fmts = self._with_code_fmts("lqer_kv_pool_fork")
+            _lib.check(getattr(_lib.lib(), name)(self.buf.data_ptr(), self.buf.numel(), ops._DT[self.dtype], self.pt.num_pages, self.pt.max_seqs,
+                                                 self.kv_heads, self.head_dim, self.table.data_ptr(), self.pt.max_pages_per_seq,
+                                                 meta[0].data_ptr(), meta[1].data_ptr(), meta[2].data_ptr(), n, *fmts, ops._stream(self.device)),
+                       name)
 
     @torch.no_grad()
     def reorder(self, seqs, parent_idx) -> list:
@@ -780,11 +820,12 @@ class PagedKVCache:
         dense = QuantizedKVCache(1, self.kv_heads, self.head_dim, self.cfg0, self.cfg1, self.dtype, self.device, capacity=max(t, PAGE_KEYS))
         if t:
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().lqer_kv_pool_gather(self.buf.data_ptr(), self.buf.numel(), ops._DT[self.dtype], self.pt.num_pages,
-                                                          self.pt.max_seqs, self.kv_heads, self.head_dim, self.table.data_ptr(),
-                                                          self.pt.max_pages_per_seq, slot, t, dense.buf.data_ptr(), dense.buf.numel(),
-                                                          dense.capacity, ops._stream(self.device)),
-                           "lqer_kv_pool_gather")
+                name, fmts = self._with_code_fmts("lqer_kv_pool_gather")
+                _lib.check(getattr(_lib.lib(), name)(self.buf.data_ptr(), self.buf.numel(), ops._DT[self.dtype], self.pt.num_pages,
+                                                     self.pt.max_seqs, self.kv_heads, self.head_dim, self.table.data_ptr(),
+                                                     self.pt.max_pages_per_seq, slot, t, dense.buf.data_ptr(), dense.buf.numel(),
+                                                     dense.capacity, *fmts, ops._stream(self.device)),
+                           name)
         dense.length = t
         return dense
 
@@ -823,7 +864,8 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
     samples of one prompt, forks behind one system prompt - are grouped from the host's books (PageTable.prefix_groups) and
     lqer_attention_q_decode_paged_shared reads every chunk of keys that lies wholly inside a group's shared pages ONCE per group
     instead of once per sequence; the same bits, row for row.  When no two sequences of the call share a chunk the plain entry runs.
-    With a window in effect (the call's or the cache's) or with the prefill kernel: ValueError."""
+    With a window in effect (the call's or the cache's) or with the prefill kernel: ValueError.  On a cache with nibble codes
+    (code_bits=4) the plain entry runs whatever the groups are - the same bits."""
     if kernel not in (KERNEL_DECODE, KERNEL_PREFILL, KERNEL_AUTO):
         raise ValueError(f"attention_flexible_paged: kernel={kernel!r} - 'decode', 'prefill' or 'auto'")
     _check_layout_and_mask("attention_flexible_paged", out_layout, None, causal)
@@ -922,7 +964,8 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
     sequence -, stats fp32 dense or None, for the sequences in `slots` with `lens` keys.  `window`: None or W - the entry is then
     `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  `groups` (PAGED_DECODE without a window only): the call's
     prefix groups (PageTable.prefix_groups) - with a group of two or more the entry is SHARED_DECODE, `base`'s list plus the group
-    arrays; with none, or without any such group, `base`.  The workspace and the stream come as values, so nothing
+    arrays; with none, without any such group, or on a cache with nibble codes (the grouped kernels are not instantiated for them; the
+    bits are the same), `base`.  The workspace and the stream come as values, so nothing
     here needs a GPU: the call's metadata is copied to the cache's device tensors, wherever they are."""
     ragged, f = counts is not None, cache.fmts
     h, d = q.shape[1], q.shape[-1]
@@ -937,7 +980,8 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
     if groups is not None and any(len(mem) > 1 for mem, _ in groups):
         if base != PAGED_DECODE or window is not None:
             raise ValueError(f"prefix groups on {base} with window={window} - {SHARED_DECODE} is {PAGED_DECODE} alone")
-        return SHARED_DECODE, args + cache._call_groups(groups)
+        if not cache.nibble:
+            return SHARED_DECODE, args + cache._call_groups(groups)
     return (base, args) if window is None else (base + "_window", args + (min(window, 1 << 62),))
 
 

@@ -126,6 +126,14 @@ def make_qfmt(cfg: Optional[dict], role: str = "x") -> QFmt:
     return fmt
 
 
+def nibble_qfmt(fmt: QFmt) -> QFmt:
+    """A block_fp format of width 2..4 with blocks of 16 as the K or V format of a paged KV pool that stores the operand's codes as
+    nibbles (LQER_Q_MXINT_C4): the same quantizer, two codes per byte.  ValueError for any other format - a wider one does not fit."""
+    if fmt.kind != _lib.Q_MXINT or not 2 <= fmt.width <= 4 or fmt.block != 16:
+        raise ValueError(f"nibble codes hold block_fp of width 2..4 with blocks of 16 (got kind {fmt.kind}, width {fmt.width}, block {fmt.block})")
+    return QFmt(_lib.Q_MXINT_C4, fmt.width, fmt.block, fmt.exp_width, fmt.exp_bias)
+
+
 def _minifloat_qfmt(cfg: dict, role: str) -> QFmt:
     """The reference's `minifloat` (quantizers/minifloat.py:120-182, minifloat_ieee) -> LQER_Q_MINIFLOAT: width, exp_width, the resolved
     exp_bias.  Elementwise in every role (block_size / skip_first_dim do not apply).  Refused: a config without `exponent_width` (it names
