@@ -896,6 +896,25 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * named once and is not a src of the same call; the table rows of dst are valid up to ceil(L / 16) entries before the launch; L is
  * at most src's length.  Refused: LQER_E_INVALID - any null pointer, n < 1, pages, slots, kv_heads, table_stride or D < 1, a short or
  * misaligned pool; LQER_E_UNSUPPORTED - a dtype or D lqer_kv_pool_bytes rejects, n x kv_heads beyond the launch grid (2^31 - 1).
+ * lqer_kv_pool_copy: pages and slots' staging rows from one pool to another, bytes as they are - swap sequences out to a small pool
+ * (which may then go to the host or a file) and back in, hand cached keys from a prefill pool to a decode pool, move pages within one
+ * pool.  The two pools have the same dtype, kv_heads, D and code storage and their OWN page and slot counts: (src_pool, src_bytes,
+ * src_pages, src_slots) and (dst_pool, dst_bytes, dst_pages, dst_slots), each sized by lqer_kv_pool_bytes - or, with k_fmt / v_fmt,
+ * lqer_kv_pool_bytes_fmt - for its own counts.  k_fmt and v_fmt are both NULL for pools of byte codes, otherwise the two formats whose
+ * kinds name the storage (as lqer_kv_pool_fork_fmt's; nothing is quantized).  Four int32 arrays on the DEVICE, written by the caller:
+ * pair i < n_pages copies page src_page_ids[i] to page dst_page_ids[i] - for every kv head g the item of the K codes, the K exponents,
+ * the V codes and the V exponents -, pair j < n_slots the staging rows [kv_heads][16][D] of DT of slot src_slot_ids[j] to slot
+ * dst_slot_ids[j].  No table and no length enters: which pages make a sequence is the caller's books' to say, on both sides.  ONE
+ * launch on `stream`, a workgroup of 256 per (page pair, kv head) and per (slot pair, kv head), in 16-byte pieces; no allocation, no
+ * host synchronisation, no atomics: capturable in a hipGraph.  Either count may be 0; with both 0 the call validates, launches nothing
+ * and returns LQER_OK.  The source is only read.  Caller's contract: every id lies in range (pages: [0, src_pages) / [0, dst_pages),
+ * slots: [0, src_slots) / [0, dst_slots)); dst_page_ids are distinct, and so are dst_slot_ids; the two pools are either disjoint
+ * buffers or the same buffer with the same geometry; if they are the same buffer, no destination page or slot is also a source of
+ * this call.  A call that breaks this reads or writes outside the pools or leaves a destination undefined.  Refused with a message,
+ * nothing launched: LQER_E_INVALID - a null pool, a pool not 16-byte aligned or shorter than lqer_kv_pool_bytes(_fmt) for its own
+ * counts, pages, slots, kv_heads or D < 1, a negative count, a null id array with a positive count, exactly one of k_fmt / v_fmt
+ * NULL, two buffers that overlap without being the same pool (same pointer, same counts); LQER_E_UNSUPPORTED - whatever
+ * lqer_kv_pool_bytes(_fmt) answers 0 for (dtype, D, kind, width, block), (n_pages + n_slots) x kv_heads beyond the launch grid (2^31 - 1).
  * Refused with a message, nothing launched or touched (decided from host arguments only):
  *   LQER_E_UNSUPPORTED  what lqer_attention_q_decode_kv / lqer_kv_cache_append refuse so (S > 8, formats, D, batch or kv_heads > 65535);
  *                       max_len > 2^30 (every call); lqer_attention_q_paged: what lqer_attention_q_kv refuses so instead (formats, D, S
@@ -929,6 +948,10 @@ int lqer_kv_pool_gather_fmt(const void* pool, size_t pool_bytes, int dtype, int6
 int lqer_kv_pool_fork_fmt(void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
                           const int32_t* block_table, int64_t table_stride, const int32_t* src_slots, const int32_t* dst_slots,
                           const int32_t* lens, int64_t n, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
+int lqer_kv_pool_copy(const void* src_pool, size_t src_bytes, int64_t src_pages, int64_t src_slots, void* dst_pool, size_t dst_bytes,
+                      int64_t dst_pages, int64_t dst_slots, int dtype, int64_t kv_heads, int64_t D, const int32_t* src_page_ids,
+                      const int32_t* dst_page_ids, int64_t n_pages, const int32_t* src_slot_ids, const int32_t* dst_slot_ids, int64_t n_slots,
+                      const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
 size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D);
 int lqer_attention_q_decode_paged(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
                                   int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,

@@ -170,6 +170,9 @@ SIGNATURES = {
     "lqer_kv_pool_bytes_fmt": (_sz, [_i, _i64, _i64, _i64, _i64, _qp, _qp]),
     "lqer_kv_pool_gather_fmt": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _i64, _qp, _qp, _vp]),
     "lqer_kv_pool_fork_fmt": (_i, [_vp, _sz, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _qp, _qp, _vp]),
+    # pages and slots' staging rows between two pools of one dtype, kv_heads, D and storage: (pool, bytes, pages, slots) of the source and
+    # of the destination, dtype, kv_heads, D, src / dst page ids and their count, src / dst slot ids and theirs, K / V formats or none
+    "lqer_kv_pool_copy": (_i, [_vp, _sz, _i64, _i64, _vp, _sz, _i64, _i64, _i, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _qp, _qp, _vp]),
     "lqer_attention_q_decode_paged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "lqer_attention_q_decode_paged": (_i, _PAGED),
     # ... with a sliding window over the causal rule: the same argument list plus `window`

@@ -1812,6 +1812,80 @@ int lqer_kv_pool_fork_fmt(void* pool, size_t pool_bytes, int dtype, int64_t page
                       n, k_fmt, v_fmt, true, stream);
 }
 
+// one side of lqer_kv_pool_copy - a pool by its own page and slot counts, no table and no lengths: p.k4 / p.v4 and `need`, the bytes
+// lqer_kv_pool_bytes(_fmt) gives its geometry, or the refusal
+static int kv_pool_copy_side(const char* side, KvPool& p, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, size_t& need) {
+  if (!p.pool) {
+    set_error("kv_pool_copy: null %s KV pool", side);
+    return LQER_E_INVALID;
+  }
+  if (p.pages < 1 || p.slots < 1 || p.kv_heads < 1 || p.D < 1) {
+    set_error("kv_pool_copy: bad shape of the %s KV pool pages=%lld slots=%lld kv_heads=%lld D=%lld", side, (long long)p.pages, (long long)p.slots,
+              (long long)p.kv_heads, (long long)p.D);
+    return LQER_E_INVALID;
+  }
+  need = k_fmt ? lqer_kv_pool_bytes_fmt(p.dtype, p.pages, p.slots, p.kv_heads, p.D, k_fmt, v_fmt)
+               : lqer_kv_pool_bytes(p.dtype, p.pages, p.slots, p.kv_heads, p.D);
+  if (!need) {
+    set_error("kv_pool_copy: lqer_kv_pool_bytes%s sizes no %s KV pool of dtype %d, head dim %lld%s (fp32 / fp16 / bf16, multiples of 16 up to "
+              "128, block_fp of width <= 8 - nibble codes: 2..4 - with blocks of 16)", k_fmt ? "_fmt" : "", side, p.dtype, (long long)p.D,
+              k_fmt ? " and these K / V formats" : "");
+    return LQER_E_UNSUPPORTED;
+  }
+  PoolFmts own;
+  own.resolve(p, k_fmt, v_fmt);  // (the storage alone: nothing here quantizes)
+  if ((uintptr_t)p.pool % 16 != 0) {
+    set_error("kv_pool_copy: %s KV pool %p is not 16-byte aligned", side, p.pool);
+    return LQER_E_INVALID;
+  }
+  if (p.pool_bytes < need) {
+    set_error("kv_pool_copy: %s KV pool of %zu B < %zu B (lqer_kv_pool_bytes%s)", side, p.pool_bytes, need, k_fmt ? "_fmt" : "");
+    return LQER_E_INVALID;
+  }
+  return LQER_OK;
+}
+
+int lqer_kv_pool_copy(const void* src_pool, size_t src_bytes, int64_t src_pages, int64_t src_slots, void* dst_pool, size_t dst_bytes,
+                      int64_t dst_pages, int64_t dst_slots, int dtype, int64_t kv_heads, int64_t D, const int32_t* src_page_ids,
+                      const int32_t* dst_page_ids, int64_t n_pages, const int32_t* src_slot_ids, const int32_t* dst_slot_ids, int64_t n_slots,
+                      const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
+  if (!k_fmt != !v_fmt) {
+    set_error("kv_pool_copy: k_fmt %p / v_fmt %p of the KV pools - both null (byte codes) or the two formats whose kinds name the storage",
+              (const void*)k_fmt, (const void*)v_fmt);
+    return LQER_E_INVALID;
+  }
+  if (n_pages < 0 || n_slots < 0) {
+    set_error("kv_pool_copy: %lld page pairs / %lld slot pairs of the KV pools (each >= 0)", (long long)n_pages, (long long)n_slots);
+    return LQER_E_INVALID;
+  }
+  KvPool s = kv_pool(src_pool, src_bytes, src_pages, src_slots, nullptr, 0, nullptr, nullptr, 0, dtype, kv_heads, D);
+  KvPool d = kv_pool(dst_pool, dst_bytes, dst_pages, dst_slots, nullptr, 0, nullptr, nullptr, 0, dtype, kv_heads, D);
+  size_t s_need = 0, d_need = 0;
+  if (const int rc = kv_pool_copy_side("source", s, k_fmt, v_fmt, s_need)) return rc;
+  if (const int rc = kv_pool_copy_side("destination", d, k_fmt, v_fmt, d_need)) return rc;
+  if ((n_pages > 0 && (!src_page_ids || !dst_page_ids)) || (n_slots > 0 && (!src_slot_ids || !dst_slot_ids))) {
+    set_error("kv_pool_copy: null id array of the KV pools (src / dst page ids for %lld pairs, src / dst slot ids for %lld: int32 on the device)",
+              (long long)n_pages, (long long)n_slots);
+    return LQER_E_INVALID;
+  }
+  // the kernel reaches s_need / d_need bytes of each: two ranges that meet must be ONE pool (the caller then keeps sources and destinations apart)
+  const uintptr_t s0 = (uintptr_t)src_pool, d0 = (uintptr_t)dst_pool;
+  if (s0 < d0 + d_need && d0 < s0 + s_need && !(s0 == d0 && src_pages == dst_pages && src_slots == dst_slots)) {
+    set_error("kv_pool_copy: source KV pool %p (%zu B, %lld pages, %lld slots) and destination %p (%zu B, %lld pages, %lld slots) overlap "
+              "without being the same pool", src_pool, s_need, (long long)src_pages, (long long)src_slots, (const void*)dst_pool, d_need,
+              (long long)dst_pages, (long long)dst_slots);
+    return LQER_E_INVALID;
+  }
+  const int64_t room = (((int64_t)1 << 31) - 1) / kv_heads;  // (a workgroup per (pair, kv head) over grid.x)
+  if (n_pages > room || n_slots > room || n_pages + n_slots > room) {
+    set_error("kv_pool_copy: (%lld page pairs + %lld slot pairs) x %lld kv heads of the KV pools beyond one launch grid: copy in pieces",
+              (long long)n_pages, (long long)n_slots, (long long)kv_heads);
+    return LQER_E_UNSUPPORTED;
+  }
+  if (n_pages + n_slots == 0) return LQER_OK;
+  return kv_pool_copy_dispatch(s, d, src_page_ids, dst_page_ids, n_pages, src_slot_ids, dst_slot_ids, n_slots, (hipStream_t)stream);
+}
+
 size_t lqer_attention_q_decode_paged_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t S, int64_t max_len, int64_t D) {
   if (batch <= 0 || heads <= 0 || kv_heads <= 0 || S <= 0 || max_len <= 0 || D <= 0) return 0;
   return attention_q_decode_paged_workspace_bytes(batch, heads, S, max_len, D);

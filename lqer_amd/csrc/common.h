@@ -979,6 +979,8 @@ int kv_pool_append_ragged_dispatch(const KvPool& p, const void* k_new, const voi
                                    int64_t max_n, const QP& qk, const QP& qv, hipStream_t st);  // (p.starts; strides over token / kv head)
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st);
 int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, hipStream_t st);  // (p.seq_slots: the children's slots)
+int kv_pool_copy_dispatch(const KvPool& src, const KvPool& dst, const int32_t* src_pages, const int32_t* dst_pages, int64_t n_pages,
+                          const int32_t* src_slots, const int32_t* dst_slots, int64_t n_slots, hipStream_t st);  // (pools without table or lengths)
 constexpr int ATTN_V_ROWS = 128;  // rows of the V image per (batch, kv head): D padded to 128
 // the two images of lqer_attention_q's workspace from the first T keys of c's cache, or from the first lens[b] keys of every sequence
 // of c's pool (strides of T = max_len); the caller (attn_q.hip) checks the launches

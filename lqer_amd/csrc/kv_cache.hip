@@ -11,6 +11,7 @@
 //   k_kv_unpack  code x 2^(e - mbits) as fp32, one element per thread.
 //   k_kv_pool_gather   one sequence's bytes out of the pool into a dense cache.
 //   k_kv_pool_fork     children that share their parents' full pages: the open block's item and the staging rows, copied per child.
+//   k_kv_pool_copy     pages and slots' staging rows from one pool to another (or within one), by id lists: fork's section walk.
 //   k_kv_kimage / k_kv_vimage   the cache -> the two bf16 images k_attn_q reads (attn_q.hip; what k_attn_kimage / k_attn_vimage write from
 //                the raw K and V): codes16_to_bf16 on 16 codes per 16-byte load, zeros wherever the raw image kernels write their
 //                padding - every key at or beyond T, every d at or beyond D.  Nothing of the cache at or beyond key T reaches an image.
@@ -187,6 +188,34 @@ __global__ __launch_bounds__(256) void k_kv_pool_gather(const GArgs a) {
   if (i < a.kvh * a.stage16) ((uint4*)a.dst[4])[i] = ((const uint4*)a.src[4])[a.slot * a.kvh * a.stage16 + i];
 }
 
+// The section walk of fork and copy: item sblk of `s` to item dblk of `d` in the four code and exponent sections - kc16 / e16 / vc16 /
+// e16 16-byte pieces -, bytes as they are, over the 256 threads of a workgroup (at D = 128 with byte codes 272 pieces: more than one
+// round).  s and d may be one pool; the caller keeps the two items apart.
+template <class S, class T>
+__device__ __forceinline__ void copy_item(const KvSrc<S>& s, const KvSrc<T>& d, int64_t sblk, int64_t dblk, int64_t kc16, int64_t vc16,
+                                          int64_t e16) {
+  const int64_t per = kc16 + vc16 + 2 * e16;
+  for (int64_t p = threadIdx.x; p < per; p += 256) {
+    int64_t u = p;
+    int sec = 0;
+    if (u >= kc16) u -= kc16, sec = 1;
+    if (sec == 1 && u >= e16) u -= e16, sec = 2;
+    if (sec == 2 && u >= vc16) u -= vc16, sec = 3;
+    const int64_t item = sec == 0 ? kc16 : sec == 2 ? vc16 : e16;  // 16-byte pieces of a block in this section
+    const uint4* from = (const uint4*)(sec == 0 ? s.kc : sec == 1 ? s.ke : sec == 2 ? s.vc : s.ve);
+    uint4* to = (uint4*)(sec == 0 ? d.kc : sec == 1 ? d.ke : sec == 2 ? d.vc : d.ve);
+    to[dblk * item + u] = from[sblk * item + u];
+  }
+}
+
+// the staging rows of (slot sslot, kv head g) of `s` to (slot dslot, kv head g) of `d`: stage16 16-byte pieces
+template <class S, class T>
+__device__ __forceinline__ void copy_stage(const KvSrc<S>& s, const KvSrc<T>& d, int64_t sslot, int64_t dslot, int64_t g, int64_t stage16) {
+  const uint4* from = (const uint4*)s.stage + (sslot * s.kvh + g) * stage16;
+  uint4* to = (uint4*)d.stage + (dslot * d.kvh + g) * stage16;
+  for (int64_t u = threadIdx.x; u < stage16; u += 256) to[u] = from[u];
+}
+
 struct FArgs {
   KvSrc<unsigned char> src;  // the pool; src.slots / src.lens: the CHILD's slot and the length forked at, per pair (device)
   const int32_t* from;       // the parent's slot, per pair (device)
@@ -204,24 +233,28 @@ __global__ __launch_bounds__(256) void k_kv_pool_fork(const FArgs a) {
   const int32_t* drow;
   const int64_t L = seq<attn::SRC_PAGED>(a.src, i, 0, drow), from = a.from[i];
   if (blockIdx.y == 0) {
-    const uint4* s = (const uint4*)a.src.stage + (from * kvh + g) * a.stage16;
-    uint4* d = (uint4*)a.src.stage + ((int64_t)a.src.slots[i] * kvh + g) * a.stage16;
-    for (int64_t u = threadIdx.x; u < a.stage16; u += 256) d[u] = s[u];
+    copy_stage(a.src, a.src, from, (int64_t)a.src.slots[i], g, a.stage16);
     return;
   }
   if (L % 16 == 0) return;  // (uniform over the workgroup)
-  const int64_t e16 = a.D / 16, per = a.kc16 + a.vc16 + 2 * e16;
-  const int64_t sblk = page_block(slot_row(a.src, from), kvh, g, L / 16), dblk = page_block(drow, kvh, g, L / 16);
-  for (int64_t p = threadIdx.x; p < per; p += 256) {
-    int64_t u = p;
-    int sec = 0;
-    if (u >= a.kc16) u -= a.kc16, sec = 1;
-    if (sec == 1 && u >= e16) u -= e16, sec = 2;
-    if (sec == 2 && u >= a.vc16) u -= a.vc16, sec = 3;
-    const int64_t item = sec == 0 ? a.kc16 : sec == 2 ? a.vc16 : e16;  // 16-byte pieces of a block in this section
-    uint4* base = (uint4*)(sec == 0 ? a.src.kc : sec == 1 ? a.src.ke : sec == 2 ? a.src.vc : a.src.ve);
-    base[dblk * item + u] = base[sblk * item + u];
-  }
+  copy_item(a.src, a.src, page_block(slot_row(a.src, from), kvh, g, L / 16), page_block(drow, kvh, g, L / 16), a.kc16, a.vc16, a.D / 16);
+}
+
+struct CArgs {
+  KvSrc<const unsigned char> src;  // two pools of one dtype, kv_heads, D and code storage - or one pool twice
+  KvSrc<unsigned char> dst;
+  const int32_t *src_pages, *dst_pages, *src_slots, *dst_slots;  // the pairs (device)
+  int64_t n_pages, D, stage16, kc16, vc16;                      // FArgs' piece counts
+};
+
+// Copy: a workgroup per (pair, kv head), the page pairs first - pair i < n_pages copies the item (src_pages[i], g) to (dst_pages[i], g)
+// in all four code and exponent sections, pair n_pages + j the staging rows of slot src_slots[j] to slot dst_slots[j].  Bytes as they
+// are; no table, no length: what a page means is the caller's books'.  Nothing here is read by another workgroup of the launch (a
+// destination is named once and is no source).
+__global__ __launch_bounds__(256) void k_kv_pool_copy(const CArgs a) {
+  const int64_t kvh = a.src.kvh, i = blockIdx.x / kvh, g = blockIdx.x % kvh;
+  if (i < a.n_pages) copy_item(a.src, a.dst, (int64_t)a.src_pages[i] * kvh + g, (int64_t)a.dst_pages[i] * kvh + g, a.kc16, a.vc16, a.D / 16);
+  else copy_stage(a.src, a.dst, (int64_t)a.src_slots[i - a.n_pages], (int64_t)a.dst_slots[i - a.n_pages], g, a.stage16);
 }
 
 struct UArgs {
@@ -453,6 +486,15 @@ int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, 
                   kvc::code_pitch(p.D, p.k4), kvc::code_pitch(p.D, p.v4)};                             // 16 rows x pitch / 16
   kvc::k_kv_pool_fork<<<dim3((unsigned)(n * p.kv_heads), 2), 256, 0, st>>>(a);
   return check_launch("lqer_kv_pool_fork");
+}
+
+// src / dst: pool, dtype, pages, slots, kv_heads, D, k4, v4 (no table, no lengths); the four id arrays are device pointers
+int kv_pool_copy_dispatch(const KvPool& src, const KvPool& dst, const int32_t* src_pages, const int32_t* dst_pages, int64_t n_pages,
+                          const int32_t* src_slots, const int32_t* dst_slots, int64_t n_slots, hipStream_t st) {
+  kvc::CArgs a = {kvc::src_of(src), kvc::src_of<unsigned char>(dst), src_pages, dst_pages, src_slots, dst_slots, n_pages, src.D,
+                  src.D * (src.dtype == LQER_F32 ? 4 : 2), kvc::code_pitch(src.D, src.k4), kvc::code_pitch(src.D, src.v4)};
+  kvc::k_kv_pool_copy<<<dim3((unsigned)((n_pages + n_slots) * src.kv_heads)), 256, 0, st>>>(a);
+  return check_launch("lqer_kv_pool_copy");
 }
 
 int kv_cache_unpack_dispatch(const void* cache, int dtype, int64_t batch, int64_t kv_heads, int64_t capacity, int64_t D, int64_t T, const QP& qk,

@@ -244,6 +244,69 @@ def _code_bits(code_bits, fmts):
     return pair
 
 
+@torch.no_grad()
+def pool_copy(src: torch.Tensor, src_pages: int, src_slots: int, dst: torch.Tensor, dst_pages: int, dst_slots: int, dtype: torch.dtype,
+              kv_heads: int, head_dim: int, ids: torch.Tensor, n_pages: int, n_slots: int, k_fmt=None, v_fmt=None) -> None:
+    """lqer_kv_pool_copy on two pool buffers of the device: `ids`, an int32 tensor there, holds the source page ids, the destination page
+    ids (n_pages each), the source slot ids and the destination slot ids (n_slots each) one behind the other.  k_fmt / v_fmt: the pools'
+    K and V formats where a code section holds nibbles, else none."""
+    ops._need_gpu(src, dst, ids)
+    if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.numel() != 2 * (n_pages + n_slots) or ids.device != dst.device or src.device != dst.device:
+        raise ValueError(f"pool_copy: ids {tuple(ids.shape)} {ids.dtype} on {ids.device} for {n_pages} page pairs and {n_slots} slot pairs of pools "
+                         f"on {src.device} / {dst.device}")
+    at = [ids.data_ptr() + 4 * x for x in (0, n_pages, 2 * n_pages, 2 * n_pages + n_slots)]
+    fmts = (None, None) if k_fmt is None and v_fmt is None else (C.byref(k_fmt), C.byref(v_fmt))
+    with torch.cuda.device(dst.device):
+        _lib.check(_lib.lib().lqer_kv_pool_copy(src.data_ptr(), src.numel(), src_pages, src_slots, dst.data_ptr(), dst.numel(), dst_pages, dst_slots,
+                                                ops._DT[dtype], kv_heads, head_dim, at[0], at[1], n_pages, at[2], at[3], n_slots, *fmts,
+                                                ops._stream(dst.device)),
+                   "lqer_kv_pool_copy")
+
+
+class KVPoolImage:
+    """Sequences taken out of a PagedKVCache (export, swap_out): a small pool in the library's own layout - `pages` pages, the distinct
+    pages of the sequences, and `slots` slots, one per sequence - with the books that say which pages make which sequence.  The bytes
+    are the pool's as they are, so nibble codes, released pages under a window and pages shared between forks need no special case.
+
+    .buf        uint8, pool layout (lqer_kv_pool_bytes(_fmt) of pages x slots; a pool has at least one page, so an image of empty
+                sequences holds one that nothing names), on the device or in pinned host memory
+    .books      PageTable.export's data, the pages renumbered 0 .. pages - 1: the image's own
+    .signature  ints: dtype, kv_heads, head_dim, the K and V format fields, code_bits, window, max_query_rows - what adopt() compares
+    .ready      a torch event recorded after the last copy that wrote buf (None once loaded from a state dict);  .synchronize() waits
+    .nbytes;  .lengths  the sequences' lengths
+    .state_dict() / KVPoolImage.from_state_dict(d): tensors and ints only - torch.save / torch.load work."""
+
+    def __init__(self, buf: torch.Tensor, pages: int, books: dict, signature, ready=None):
+        self.buf, self.pages, self.books, self.signature, self.ready = buf, pages, books, tuple(int(x) for x in signature), ready
+
+    slots = property(lambda self: len(self.books["seqs"]))
+    nbytes = property(lambda self: self.buf.numel())
+    lengths = property(lambda self: [s[0] for s in self.books["seqs"]])
+
+    def synchronize(self) -> None:
+        if self.ready is not None:
+            self.ready.synchronize()
+
+    def state_dict(self) -> dict:
+        self.synchronize()
+        seqs = self.books["seqs"]
+        return {"buf": self.buf.cpu(), "pages": self.pages, "signature": torch.tensor(self.signature, dtype=torch.int64),
+                "lengths": torch.tensor([s[0] for s in seqs], dtype=torch.int64), "released": torch.tensor([s[1] for s in seqs], dtype=torch.int64),
+                "rows": torch.tensor([p for s in seqs for p in s[2]], dtype=torch.int32)}
+
+    @classmethod
+    def from_state_dict(cls, d: dict) -> "KVPoolImage":
+        rows, seqs, at = d["rows"].tolist(), [], 0
+        for length, gone in zip(d["lengths"].tolist(), d["released"].tolist()):
+            n = (length + PAGE_KEYS - 1) // PAGE_KEYS
+            seqs.append((length, gone, rows[at:at + n]))
+            at += n
+        named = {p for _, gone, row in seqs for p in row[gone:]}
+        if at != len(rows) or named != set(range(len(named))) or d["buf"].dtype != torch.uint8:
+            raise ValueError("KVPoolImage.from_state_dict: the rows do not fit the lengths, or the buffer is not uint8")
+        return cls(d["buf"], int(d["pages"]), {"pages": list(range(len(named))), "seqs": seqs}, d["signature"].tolist())
+
+
 class PageTable:
     """The page allocator and the host mirror of the block table and the lengths: plain host state, no torch device in it.
 
@@ -441,6 +504,66 @@ class PageTable:
             self.free(child)
         self._next_seq -= len(children)
 
+    def export(self, seqs) -> dict:
+        """The books of `seqs` as plain host data, for another table to adopt: {"pages": the distinct pages the sequences hold (their
+        row entries released .. pages_of - 1), in order of first appearance - a page two of them hold appears once; "seqs": per
+        sequence (length, released, local row)}, a local row being the sequence's row with every held entry replaced by the page's
+        position in "pages" and the released entries by 0.  Nothing in the books changes."""
+        local, out = {}, []
+        for s in self.slots(seqs):
+            gone = self.released[s]
+            row = [0] * gone + [local.setdefault(p, len(local)) for p in self.table[s][gone:self.pages_of[s]]]
+            out.append((self.lengths[s], gone, row))
+        return {"pages": list(local), "seqs": out}
+
+    def adopt(self, books):
+        """New sequences with the books export() gave (of this table or another): (seqs, slots, page map - the page of this table that
+        stands for each entry of books["pages"]).  All or nothing, as fork: the slots of all sequences, the free pages of all
+        distinct pages and max_pages_per_seq for every row are counted first; short of any raises RuntimeError with nothing taken.
+        Rows stay indexed by absolute key / 16: released entries become 0 - a valid index that nothing reads -, `released` and
+        `lengths` are the exported ones, and a page has as many owners as adopted sequences name it.  rollback_adopt() undoes it."""
+        n, seqs = len(books["pages"]), list(books["seqs"])
+        named = set()
+        for length, gone, row in seqs:
+            if length < 0 or len(row) != (length + PAGE_KEYS - 1) // PAGE_KEYS or not 0 <= gone <= length // PAGE_KEYS:
+                raise ValueError(f"PagedKVCache.adopt: a sequence of {length} keys with a row of {len(row)} entries, {gone} released")
+            named.update(row[gone:])
+        if named != set(range(n)):
+            raise ValueError(f"PagedKVCache.adopt: the rows name pages {sorted(named)} of {n}")
+        if len(seqs) > len(self._free_slots):
+            raise RuntimeError(f"PagedKVCache.adopt: {len(seqs)} new sequences, {len(self._free_slots)} of {self.max_seqs} sequence slots free")
+        if n > len(self._free_pages):
+            raise RuntimeError(f"PagedKVCache.adopt: out of pages - {n} needed, {len(self._free_pages)} of {self.num_pages} free")
+        for length, _, row in seqs:
+            if len(row) > self.max_pages_per_seq:
+                raise RuntimeError(f"PagedKVCache.adopt: a sequence of {length} keys = {len(row)} pages, beyond max_pages_per_seq = "
+                                   f"{self.max_pages_per_seq}")
+        pages = [self._free_pages.pop() for _ in range(n)]
+        out, slots = [], []
+        for length, gone, row in seqs:
+            seq = self.alloc()
+            s = self._slot[seq]
+            mine = [pages[i] for i in row[gone:]]
+            self.table[s][:len(row)] = [0] * gone + mine
+            if mine:
+                self._owners[np.array(mine)] += 1
+            self.pages_of[s], self.lengths[s], self.released[s] = len(row), length, gone
+            out.append(seq), slots.append(s)
+        return out, slots, pages
+
+    def rollback_adopt(self, seqs) -> None:
+        """Undo an adopt() whose launch did not happen: the ids, slots and pages go back so that the next call takes the same."""
+        held = lambda s: self.table[s][self.released[s]:self.pages_of[s]]
+        pages = list(dict.fromkeys(p for seq in seqs for p in held(self.slot(seq))))  # in the order adopt() took them
+        if pages:
+            self._owners[np.array(pages)] = 0
+        self._free_pages.extend(reversed(pages))
+        for seq in reversed(seqs):
+            s = self._slot.pop(seq)
+            self.pages_of[s] = self.lengths[s] = self.released[s] = 0
+            self._free_slots.append(s)
+        self._next_seq -= len(seqs)
+
     def prefix_groups(self, slots, lens, chunk_of) -> list:
         """The sequences of one call - in `slots`, of `lens` keys - grouped by the prefix they hold on the SAME pages: a list of
         (members, shared_keys), members the call indices in ascending order (the first is the group's leader), the groups ordered by
@@ -538,7 +661,19 @@ class PagedKVCache:
     and every attention_flexible_paged* function works unchanged: `.nbytes` is the smaller pool (lqer_kv_pool_bytes_fmt), to_dense()
     gives a byte QuantizedKVCache (lqer_kv_pool_gather_fmt widens the nibbles), fork copies the smaller item.  K and V choose on
     their own: (8, 4) keeps a wide K beside a 4-bit V.  shared_prefix=True runs the ungrouped call on such a pool (the grouped
-    kernels are not instantiated for nibble codes; the bits are the same by that feature's contract)."""
+    kernels are not instantiated for nibble codes; the bits are the same by that feature's contract).
+
+    Sequences out of the pool and into one (lqer_kv_pool_copy: a list of pages and a list of slots' staging rows from one pool to
+    another in one launch, bytes as they are): .export(seqs, device=None) -> KVPoolImage, a small pool in the library's own layout
+    with its books, on the device or ("cpu") in pinned host memory, the sequences still live; .adopt(image) -> new sequences;
+    .swap_out(seqs) = export to the host + free (preemption: when append raises "out of pages" a victim's bytes leave and come back
+    instead of being recomputed), .swap_in(image) = adopt; .adopt_from(other, seqs): pool to pool with no image (a prefill pool to a
+    decode pool; `other` may be this cache).  An image survives state_dict() / torch.save / torch.load / from_state_dict().  THE
+    GUARANTEE: an adopted sequence is from then on a sequence like any other - every attention_flexible_paged* function gives the
+    SAME BITS on it as on the sequence it was exported from, and so does every later append / append_ragged (the staging rows
+    travelled), fork and to_dense - whatever pages it lands on, whichever pool it lands in, whether or not the image went through
+    the host or a file.  Nibble pools, sequences with released pages (adopted only under the same window and max_query_rows:
+    ValueError otherwise) and forks - a shared page travels once and is shared again - need no special case."""
 
     covers = staticmethod(QuantizedKVCache.covers)
 
@@ -562,7 +697,7 @@ class PagedKVCache:
             for i, bits in zip((1, 3), self.code_bits):
                 if bits == 4:
                     self.fmts[i] = ops.nibble_qfmt(self.fmts[i])
-        self.buf = torch.empty(pool_bytes(dtype, num_pages, max_seqs, kv_heads, head_dim, *((self.fmts[1], self.fmts[3]) if self.nibble else ())),
+        self.buf = torch.empty(pool_bytes(dtype, num_pages, max_seqs, kv_heads, head_dim, *self._code_fmts()),
                                dtype=torch.uint8, device=self.device)
         # the device copies of the metadata: the table (rows updated when they change), the slots and the lengths of the current call
         self.table = torch.zeros(max_seqs, self.pt.max_pages_per_seq, dtype=torch.int32, device=self.device)
@@ -808,6 +943,119 @@ class PagedKVCache:
                 self.table[s].copy_(torch.tensor(row, dtype=torch.int32))
             raise
         return [next(children) if s is None else s for s in out]
+
+    # ---- sequences out of the pool and into one (lqer_kv_pool_copy) ----
+    def _code_fmts(self) -> tuple:
+        """The K and V formats where they name the storage (a pool with nibble codes), nothing on a pool of byte codes."""
+        return (self.fmts[1], self.fmts[3]) if self.nibble else ()
+
+    def _signature(self) -> tuple:
+        """What two pools must agree on for bytes to move between them - dtype, kv_heads, head_dim, the K and V format fields (their
+        kinds name the storage), code_bits - and, last, what decides which pages a sequence may have released: window (0: none) and
+        the query rows a later call may bring."""
+        fields = lambda f: (f.kind, f.width, f.block, f.exp_width, f.exp_bias)
+        rows = _ATTN_DECODE_MAX_S if self.max_query_rows is None else self.max_query_rows
+        return (ops._DT[self.dtype], self.kv_heads, self.head_dim, *fields(self.fmts[1]), *fields(self.fmts[3]), *self.code_bits,
+                self.window or 0, rows)
+
+    def _check_signature(self, who: str, signature, books) -> None:
+        mine, theirs = self._signature(), tuple(signature)
+        if len(theirs) != len(mine) or theirs[:-2] != mine[:-2]:
+            raise ValueError(f"{who}: sequences of a pool with (dtype, kv_heads, head_dim, K format, V format, code_bits) = {theirs[:-2]} for one "
+                             f"with {mine[:-2]} - bytes move as they are, between pools of one geometry, formats and storage")
+        if theirs[-2:] != mine[-2:] and any(gone for _, gone, _ in books["seqs"]):
+            raise ValueError(f"{who}: a sequence has released pages under (window, max_query_rows) = {theirs[-2:]}, this cache has {mine[-2:]} - "
+                             "the keys below are gone, and only that window rule never reads them")
+
+    @torch.no_grad()
+    def export(self, seqs, device=None) -> KVPoolImage:
+        """The sequences' bytes as a KVPoolImage, on this cache's device or (device="cpu") in pinned host memory; the sequences stay
+        live.  The id lists go up in one small copy, ONE lqer_kv_pool_copy writes a device image - the distinct pages, a page shared
+        by forks once, and a slot per sequence - and for the host one non-blocking copy follows on the current stream; image.ready is
+        recorded behind it.  Unknown, freed or repeated sequences raise, as elsewhere; so does an empty list."""
+        seqs = list(seqs)
+        host = device is not None and torch.device(device).type == "cpu"
+        if not seqs or (device is not None and not host and torch.empty(0, device=device).device != self.buf.device):
+            raise ValueError(f"PagedKVCache.export: {len(seqs)} sequences to {device!r} - at least one, to 'cpu' or the pool's device {self.buf.device}")
+        books, slots = self.pt.export(seqs), self.pt.slots(seqs)
+        n, m = len(books["pages"]), len(seqs)
+        pages = max(n, 1)  # (the library sizes no pool of 0 pages)
+        img = torch.empty(pool_bytes(self.dtype, pages, m, self.kv_heads, self.head_dim, *self._code_fmts()), dtype=torch.uint8, device=self.buf.device)
+        ids = torch.tensor(books["pages"] + list(range(n)) + slots + list(range(m)), dtype=torch.int32).to(self.buf.device)
+        pool_copy(self.buf, self.pt.num_pages, self.pt.max_seqs, img, pages, m, self.dtype, self.kv_heads, self.head_dim, ids, n, m, *self._code_fmts())
+        if host:
+            dev_img, img = img, torch.empty(img.numel(), dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.device(self.buf.device):
+                img.copy_(dev_img, non_blocking=True)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.buf.device))
+        return KVPoolImage(img, pages, {"pages": list(range(n)), "seqs": books["seqs"]}, self._signature(), ready)
+
+    def _adopt(self, who: str, signature, books, source) -> list:
+        """The body of adopt and adopt_from: the checks, the reservation (PageTable.adopt: all or nothing), source() -> (buffer on this
+        device, its pages, its slots, page ids, slot ids), the new rows and the id lists up in one copy each, ONE lqer_kv_pool_copy -
+        and, when anything after the reservation is refused, the books as they were."""
+        self._check_signature(who, signature, books)
+        seqs, slots, pages = self.pt.adopt(books)  # (raises with nothing taken)
+        try:
+            buf, src_pages, src_slots, page_ids, slot_ids = source()
+            n, m = len(pages), len(slots)
+            ids = torch.tensor(list(page_ids) + pages + list(slot_ids) + slots, dtype=torch.int32).to(self.buf.device)
+            rows = torch.tensor([self.pt.table[s] for s in slots], dtype=torch.int32).to(self.buf.device)
+            self.table.index_copy_(0, ids[2 * n + m:].long(), rows)
+            pool_copy(buf, src_pages, src_slots, self.buf, self.pt.num_pages, self.pt.max_seqs, self.dtype, self.kv_heads, self.head_dim, ids, n, m,
+                      *self._code_fmts())
+        except BaseException:
+            self.pt.rollback_adopt(seqs)  # (the device rows of the table may keep the entries: nothing reads beyond a length)
+            raise
+        return seqs
+
+    @torch.no_grad()
+    def adopt(self, image: KVPoolImage) -> list:
+        """New sequences with the bytes of an image's - from this cache or another of the same signature, straight from export(), from
+        the host or from a file: from then on sequences like any other.  The current stream waits on image.ready, a host image comes up
+        in one copy, ONE lqer_kv_pool_copy puts the pages and staging rows where the books (PageTable.adopt) found room.  ValueError for
+        an image of another dtype, head count, head dim, format or code_bits, and for a sequence with released pages into a cache of
+        another window or max_query_rows; RuntimeError out of slots, pages or beyond max_pages_per_seq; a refusal leaves the books
+        and the pool as they were."""
+        def source():  # (behind the signature check: the image's geometry is this pool's)
+            want = pool_bytes(self.dtype, image.pages, image.slots, self.kv_heads, self.head_dim, *self._code_fmts())
+            if image.buf.dtype != torch.uint8 or image.buf.numel() != want or len(image.books["pages"]) > image.pages:
+                raise ValueError(f"PagedKVCache.adopt: an image of {image.buf.numel()} B {image.buf.dtype} for {image.pages} pages and {image.slots} "
+                                 f"slots ({want} B)")
+            if image.ready is not None:
+                torch.cuda.current_stream(self.buf.device).wait_event(image.ready)
+            with torch.cuda.device(self.buf.device):
+                buf = image.buf.to(self.buf.device, non_blocking=True)
+            return buf, image.pages, image.slots, range(len(image.books["pages"])), range(image.slots)
+
+        return self._adopt("PagedKVCache.adopt", image.signature, image.books, source)
+
+    @torch.no_grad()
+    def adopt_from(self, other: "PagedKVCache", seqs) -> list:
+        """adopt(other.export(seqs)) without the image: ONE lqer_kv_pool_copy straight from other's pool into this one - a prefill
+        pool handing its sequences to a decode pool, or (other is this cache) copies on pages of their own.  The sequences stay live
+        in `other`; adopt's checks and rollback."""
+        seqs = list(seqs)
+        if not isinstance(other, PagedKVCache) or other.buf.device != self.buf.device or not seqs:
+            raise ValueError(f"PagedKVCache.adopt_from: {len(seqs)} sequences of {type(other).__name__} - at least one, of a PagedKVCache on {self.buf.device}")
+        books, slots = other.pt.export(seqs), other.pt.slots(seqs)
+        return self._adopt("PagedKVCache.adopt_from", other._signature(), books,
+                           lambda: (other.buf, other.pt.num_pages, other.pt.max_seqs, books["pages"], slots))
+
+    @torch.no_grad()
+    def swap_out(self, seqs) -> KVPoolImage:
+        """export(seqs, device="cpu"), then free() of every sequence: preemption.  The frees come after the launch on the same stream,
+        so whoever takes the pages next overwrites them only behind the copy."""
+        seqs = list(seqs)
+        image = self.export(seqs, device="cpu")
+        for s in seqs:
+            self.pt.free(s)
+        return image
+
+    def swap_in(self, image: KVPoolImage) -> list:
+        """adopt(image)."""
+        return self.adopt(image)
 
     pages_shared = property(lambda self: self.pt.pages_shared)
 
