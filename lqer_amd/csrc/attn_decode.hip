@@ -64,6 +64,10 @@
 // Nibble codes in the paged pool (template parameter N4 of the two kernels, the paged source without GRP: k_fmt / v_fmt of kind
 // LQER_Q_MXINT_C4, kv_pack.h): the packed stage loads 8 bytes per 16 codes and widens them to the byte codes (kvc::load_codes16) in
 // front of the same codes16_to_bf16 - the scores kernel's flag is K's storage, the PV kernel's V's.  Nothing else differs.
+//
+// Written once: a key's 16 quantized values to its LDS row (put_key16: the packed stage of both kernels, the raw V stage); the fold of
+// the lane pair's (max, sum) (fold_lane_pair, attn_math.h); which instantiations exist (decode_variant_exists) -
+// attention_q_decode_dispatch is one fold over (element type, source, WIN, RAG, GRP, K4, V4) behind it.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -165,6 +169,13 @@ __device__ __forceinline__ SeqRows seq_rows(const DArgsOf<RAG>& a, int64_t b, in
   }
 }
 
+// 16 quantized values of one key (the 8 words of quant16_bf16 / codes16_to_bf16) -> their 32 bytes of the key's row of the LDS image
+__device__ __forceinline__ void put_key16(unsigned char* at, const uint32_t (&w)[8]) {
+  uint4* dst = (uint4*)at;
+  dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
 template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4 = false>
 __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, GRP> a) {
   static_assert(!N4 || (SRC == SRC_PAGED && !GRP), "nibble K codes: the paged pool, no grouped instantiation");
@@ -228,9 +239,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
       for (int j = 0; j < 4; ++j) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (tq + j < T && !gone) kvc::codes16_to_bf16(c[j], eb, a.qk, w);
-        uint4* dst = (uint4*)(sK + (4 * kq + j) * DEC_LS + dg * 32);
-        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+        put_key16(sK + (4 * kq + j) * DEC_LS + dg * 32, w);
       }
     }
   } else {
@@ -326,13 +335,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
         for (int q4 = 0; q4 < 4; ++q4)
           if (32 * wave + 8 * q4 + 4 * lh < C) *(float4*)(dst + 8 * q4) = make_float4(s2[4 * q4], s2[4 * q4 + 1], s2[4 * q4 + 2], s2[4 * q4 + 3]);
       }
-      // the lane pair (l, l ^ 32): lower lane's keys first in both lanes
-      const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(tm), __float_as_uint(tm), false, false);
-      const auto sl = __builtin_amdgcn_permlane32_swap(__float_as_uint(ls), __float_as_uint(ls), false, false);
-      const float m0 = __uint_as_float(sm[0]), m1 = __uint_as_float(sm[1]), l0 = __uint_as_float(sl[0]), l1 = __uint_as_float(sl[1]);
-      m = fmaxf(m0, m1);
-      const float mr = m == NEG_INF ? 0.f : m;
-      l = l0 * exp_neg(m0 - mr) + l1 * exp_neg(m1 - mr);
+      fold_lane_pair(tm, ls, m, l);  // the lane pair (l, l ^ 32): lower lane's keys first in both lanes
       if (lh == 0) sSt[wave][l31][0] = m, sSt[wave][l31][1] = l;
     }
     __syncthreads();
@@ -409,9 +412,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> 
         const uint32_t e1 = ((e4 >> (8 * j)) & 0xffu) * 0x01010101u;
         const uint32_t eb[4] = {e1, e1, e1, e1};
         if (tq + j < T && !gone) kvc::codes16_to_bf16(c[j], eb, a.qv, w);
-        uint4* dst = (uint4*)(sV + (4 * kq + j) * DEC_LS + db * 32);
-        dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+        put_key16(sV + (4 * kq + j) * DEC_LS + db * 32, w);
       }
     }
   } else {
@@ -426,9 +427,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> 
         load16<DT>(a.v, b * a.v_bs + g * a.v_hs + t * a.v_rs + 16 * db, 16, a.vvec, x);
         quant16_bf16<DT != LQER_F16>(x, a.qv, w);
       }
-      uint4* dst = (uint4*)(sV + key * DEC_LS + db * 32);
-      dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-      dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+      put_key16(sV + key * DEC_LS + db * 32, w);
     }
   }
   __syncthreads();
@@ -534,6 +533,14 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgsOf<RAG> a) {
   store_row4<DT>(a.out, b * a.o_bs + h * a.o_hs + si * a.o_rs + d, d, (int)a.D, o);
 }
 
+// The instantiations of the decode kernels that exist, stated once: the window, the per-sequence counts, the groups and the nibble codes
+// have public entries on the paged source only, and the grouped kernels take none of the other three.
+template <int SRC, bool WIN, bool RAG, bool GRP, bool K4, bool V4>
+constexpr bool decode_variant_exists() {
+  if (SRC != SRC_PAGED) return !(WIN || RAG || GRP || K4 || V4);
+  return !GRP || !(WIN || RAG || K4 || V4);
+}
+
 // K4 / V4 (the paged pool): the scores kernel reads K alone and the PV kernel V alone - one flag each
 template <int DT, int SRC, bool WIN = false, bool RAG = false, bool GRP = false, bool K4 = false, bool V4 = false>
 static int launch_decode(const DArgsOf<RAG, GRP>& a, int64_t batch, hipStream_t st) {
@@ -607,33 +614,25 @@ int attention_q_decode_dispatch(const AttnCall& c) {
     a.k_bs = c.ks[0], a.k_hs = c.ks[1], a.k_rs = c.ks[2], a.v_bs = c.vs[0], a.v_hs = c.vs[1], a.v_rs = c.vs[2];
     a.kvec = al16(c.k, c.ks, esz), a.vvec = al16(c.v, c.vs, esz);
   }
-  if (c.paged && (c.pool.k4 || c.pool.v4)) {  // nibble codes: plain, WIN, RAG and RAG + WIN (no grouped instantiation: the check refused)
-    return with_dtype(c.dtype, [&](auto dt) {
-      return with_flag(c.windowed, [&](auto win) {
-        return with_flag(ragged, [&](auto rag) {
-          return with_flag(c.pool.k4, [&](auto k4) {
-            return with_flag(c.pool.v4, [&](auto v4) {
-              return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, decltype(win)::value, decltype(rag)::value, false, decltype(k4)::value,
-                                         decltype(v4)::value>(a, c.batch, c.st);
-            });
-          });
-        });
-      });
-    });
-  }
-  // (the window and the per-sequence counts have public entries on the paged source only, so only those instantiations exist)
-  if (ragged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true, true>(a, c.batch, c.st); });
-  if (ragged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, false, true>(a, c.batch, c.st); });
-  if (c.paged && c.grouped) {  // (the plain paged call's record and, behind it, the groups)
-    attn::DArgsGrp ag;
+  attn::DArgsGrp ag;  // (the plain paged call's record and, behind it, the groups)
+  if (c.paged && c.grouped) {
     (attn::DArgs&)ag = a;
     ag.grp_of = c.grp_of, ag.grp_starts = c.grp_starts, ag.grp_members = c.grp_members, ag.grp_keys = c.grp_keys;
-    return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, false, false, true>(ag, c.batch, c.st); });
   }
-  if (c.paged && c.windowed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED, true>(a, c.batch, c.st); });
-  if (c.paged) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PAGED>(a, c.batch, c.st); });
-  if (c.packed) return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_PACKED>(a, c.batch, c.st); });
-  return with_dtype(c.dtype, [&](auto dt) { return attn::launch_decode<decltype(dt)::value, attn::SRC_RAW>(a, c.batch, c.st); });
+  return with_dtype(c.dtype, [&](auto dt) {
+    return with_flags(
+        [&](auto packed, auto paged, auto win, auto rag, auto grp, auto k4, auto v4) {
+          constexpr int SRC = paged ? attn::SRC_PAGED : (packed ? attn::SRC_PACKED : attn::SRC_RAW);
+          if constexpr ((packed || !paged) && attn::decode_variant_exists<SRC, win, rag, grp, k4, v4>()) {
+            if constexpr (grp) return attn::launch_decode<dt, SRC, win, rag, grp, k4, v4>(ag, c.batch, c.st);
+            else return attn::launch_decode<dt, SRC, win, rag, grp, k4, v4>(a, c.batch, c.st);
+          } else {  // (the checks of api.hip let no such call through)
+            set_error("attention_q_decode: no kernel for this combination of source, window, per-sequence counts, groups and nibble codes");
+            return (int)LQER_E_UNSUPPORTED;
+          }
+        },
+        c.packed, c.paged, c.paged && c.windowed, ragged, c.paged && c.grouped, c.paged && c.pool.k4, c.paged && c.pool.v4);
+  });
 }
 
 }  // namespace lqer

@@ -1,6 +1,6 @@
 // The scalar arithmetic both fused attention kernels share (attn_q.hip: prefill, attn_decode.hip: up to 8 query rows): the ->DT
-// rounding, exp for the softmax, and the block-of-16 quantizer of P for a block split over a lane pair (mxint_bf16_image, common.h).  One spelling, so the two
-// kernels cannot drift apart in a last bit.
+// rounding, exp for the softmax, the block-of-16 quantizer of P for a block split over a lane pair (mxint_bf16_image, common.h) and the
+// fold of a lane pair's (max, sum).  One spelling, so the two kernels cannot drift apart in a last bit.
 #pragma once
 #include "qmm_image.h"
 
@@ -40,6 +40,19 @@ __device__ __forceinline__ void quant8of16_bf16(const float (&v)[8], const QP& q
     const int e = block_exponent(amax, q);
     mxint_bf16_image<FLUSH_TINY, 8>(v, e, q, w);
   }
+}
+
+// The fold of two (max, sum) pairs {m_i, l_i = sum exp(s - m_i)}: M = max m_i, L = sum l_i exp_neg(m_i - M) (nothing visible in
+// either: M = -inf and the reference 0) - here the pairs of lanes l and l ^ 32, the lower lane's first in both lanes: the end of
+// k_attn_q's sweep 1 and of a subtile in k_attn_dec_scores.  (The folds over a chunk's subtiles and over a row's chunks, the same
+// rule over an array, keep their loops in attn_decode.hip: as a function they move registers - profiles/attn_pieces_codeobj.txt.)
+__device__ __forceinline__ void fold_lane_pair(float m, float l, float& M, float& L) {
+  const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+  const auto sl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l), __float_as_uint(l), false, false);
+  const float m0 = __uint_as_float(sm[0]), m1 = __uint_as_float(sm[1]), l0 = __uint_as_float(sl[0]), l1 = __uint_as_float(sl[1]);
+  M = fmaxf(m0, m1);
+  const float mr = M == -__builtin_inff() ? 0.f : M;
+  L = l0 * exp_neg(m0 - mr) + l1 * exp_neg(m1 - mr);
 }
 
 }  // namespace attn

@@ -29,7 +29,10 @@
 //                                   WIN, on either paged form, adds the sliding-window rule at compile time: query p sees keys
 //                                   p - W < j <= p, and the sweeps start at the first key tile the workgroup can see
 //                                   (lqer_attention_q_paged_window, lqer_attention_q_paged_ragged_window).
-#include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16: shared with attn_decode.hip
+// Written once: the fold of the lane pair's (max, sum) behind sweep 1 (fold_lane_pair, attn_math.h); the skip of a subtile no key of
+// which the wave sees, for both sweeps (`unseen`); which instantiations exist (attn_variant_exists) - attn::launch folds over
+// (PSL, RAG, WIN) behind it.
+#include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16, fold_lane_pair: shared with attn_decode.hip
 
 namespace lqer {
 
@@ -243,6 +246,15 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     }
   };
 
+  // the 32-key subtile at tb, in either sweep: no key of it is visible to the wave (wave-uniform) - beyond the causal limit or, WIN, below
+  // the window's low end
+  auto unseen = [&](int64_t tb) {
+    if (tb >= w_end) return true;
+    if constexpr (WIN)
+      if (tb + 32 <= w_begin) return true;
+    return false;
+  };
+
   // ---- sweep 1: row maximum and row sum of exp(S2 - maximum), per lane over its own keys, then across the lane pair
   float m = NEG_INF, l = 0.f;
   Stage kr = fetch_k(it0), vr;  // (nt = 0: rows 0-63 of the image exist)
@@ -254,9 +266,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int64_t tb = (int64_t)it * BT + 32 * u;
-      if (tb >= w_end) continue;  // wave-uniform: no key of the subtile is visible to the wave
-      if constexpr (WIN)
-        if (tb + 32 <= w_begin) continue;  // (the same at the window's low end)
+      if (unseen(tb)) continue;
       float s2[16];
       scores(tb, u, s2);
       const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh;  // register r is visible iff (WIN: lim_lo <=) (r & 3) + 8 (r >> 2) <= lim
@@ -272,14 +282,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     }
   }
   float M, L;
-  {
-    const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-    const auto sl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l), __float_as_uint(l), false, false);
-    const float m0 = __uint_as_float(sm[0]), m1 = __uint_as_float(sm[1]), l0 = __uint_as_float(sl[0]), l1 = __uint_as_float(sl[1]);
-    M = fmaxf(m0, m1);
-    const float mref = M == NEG_INF ? 0.f : M;
-    L = l0 * exp_neg(m0 - mref) + l1 * exp_neg(m1 - mref);
-  }
+  fold_lane_pair(m, l, M, L);
   if (a.stats && lh == 0 && qi < S) {
     float* st = a.stats + (RAG ? (row0 + qi) * a.heads + h : (b * a.heads + h) * S + qi) * 2;  // RAG: [total][heads][2]
     st[0] = M, st[1] = L;
@@ -302,9 +305,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int64_t tb = (int64_t)it * BT + 32 * u;
-      if (tb >= w_end) continue;
-      if constexpr (WIN)
-        if (tb + 32 <= w_begin) continue;
+      if (unseen(tb)) continue;
       float s2[16];
       scores(tb, u, s2);
       const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh;
@@ -344,6 +345,12 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
 }
 
+// The instantiations of k_attn_q that exist, stated once: the per-sequence query counts and the window run on the paged forms (PSL)
+template <bool PSL, bool RAG, bool WIN>
+constexpr bool attn_variant_exists() {
+  return PSL || !(RAG || WIN);
+}
+
 // with a cache the two images are already on their way on c.st (kv_cache_images_dispatch: written from the packed KV cache)
 template <int DT>
 static int launch(const AttnCall& c, Args a) {
@@ -360,22 +367,19 @@ static int launch(const AttnCall& c, Args a) {
   a.mvec = a.mode == 1 && a.T % 4 == 0 && (uintptr_t)a.mask % (4 * esz) == 0 && a.m_bs % 4 == 0 && a.m_hs % 4 == 0 && a.m_rs % 4 == 0;
   const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)c.batch);
   const int dk = (int)((a.D + 31) / 32);
-  const auto go = [&](auto psl, auto rag, auto win) {
-    constexpr bool PSL = decltype(psl)::value, RAG = decltype(rag)::value, WIN = decltype(win)::value;
-    switch (dk) {
-      case 1: k_attn_q<DT, 1, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      case 2: k_attn_q<DT, 2, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      case 3: k_attn_q<DT, 3, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
-      default: k_attn_q<DT, 4, PSL, RAG, WIN><<<grid, 64 * NW, 0, c.st>>>(a); break;
-    }
-  };
   const bool ragged = c.paged && c.pool.ragged;  // (a.S: the bound max_s - the grid's x; the kernel takes S from q_starts)
   const bool win = c.paged && c.windowed;        // (the two _window entries: causal, W >= 1 - the check's)
-  if (ragged && win) go(std::true_type{}, std::true_type{}, std::true_type{});
-  else if (win) go(std::true_type{}, std::false_type{}, std::true_type{});
-  else if (ragged) go(std::true_type{}, std::true_type{}, std::false_type{});
-  else if (c.paged) go(std::true_type{}, std::false_type{}, std::false_type{});
-  else go(std::false_type{}, std::false_type{}, std::false_type{});
+  with_flags(
+      [&](auto psl, auto rag, auto w) {
+        if constexpr (attn_variant_exists<psl, rag, w>()) switch (dk) {
+            case 1: k_attn_q<DT, 1, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
+            case 2: k_attn_q<DT, 2, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
+            case 3: k_attn_q<DT, 3, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
+            default: k_attn_q<DT, 4, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
+          }
+        return 0;
+      },
+      c.paged, ragged, win);
   return check_launch(ragged ? (win ? "lqer_attention_q_paged_ragged_window" : "lqer_attention_q_paged_ragged")
                       : c.paged ? (win ? "lqer_attention_q_paged_window" : "lqer_attention_q_paged")
                                 : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));

@@ -1035,5 +1035,14 @@ template <class F>
 auto with_flag(bool b, F&& f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
 }
+// the fold over several: with_flags(f, b0, b1, ...) = f(std::bool_constant<b0>, std::bool_constant<b1>, ...)
+template <bool... B, class F>
+auto with_flags(F&& f) {
+  return f(std::bool_constant<B>{}...);
+}
+template <bool... B, class F, class... R>
+auto with_flags(F&& f, bool b, R... rest) {
+  return b ? with_flags<B..., true>(f, rest...) : with_flags<B..., false>(f, rest...);
+}
 
 }  // namespace lqer

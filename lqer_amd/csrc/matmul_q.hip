@@ -12,6 +12,9 @@
 //                    loads one block of 16 (32 B, four threads cover 128 B of a row), quantizes it in registers and writes
 //                    the bf16 image to an LDS slab - x (the attention probabilities in P V: the big operand) is read from HBM
 //                    exactly once and no quantized copy of it ever exists in HBM.  fp32 accumulation of exact products.
+//   k_qmatmul_xr     the same product for K <= 128 with the x tile resident in LDS over four column tiles.
+// Written once for both products: the store of a finished tile (qmm_store.h, included as text by the two kernels).  launch_qmm: the
+// image launch in its three forms, the grids, and the choice of product kernel (XPRE, xr, PF, plain) as one decision.
 #include "qmm_image.h"
 
 namespace lqer {
@@ -192,94 +195,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void k_qmatmul(const void
     mma_chunk();
   }
   }
-  // ---- store: lane = output row, register r of tile (a, c): column (r & 3) + 8 (r >> 2) + 4 lh
+  // ---- store (qmm_store.h): after the loop the 32 KiB at smem hold the 16-bit output tile
   const int esz = DT == LQER_F32 ? 4 : 2;
   const bool aligned = (((uintptr_t)out) & 15) == 0 && (S2 * esz) % 16 == 0;
-  const bool staged = DT != LQER_F32 && aligned && j0 + BN <= S2;  // workgroup-uniform
-  if (staged) __syncthreads();  // the last chunk's fragment reads are done: the tiles' LDS is free
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int64_t i = i0 + wm * 64 + c * 32 + l31;
-#pragma unroll
-    for (int a = 0; a < JT; ++a) {
-      const int64_t jb = j0 + wn * (32 * JT) + a * 32;
-      if constexpr (DT == LQER_F32) {
-        if (i >= S1) continue;
-        float* dst = (float*)out + (b * S1 + i) * S2;
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          const int64_t j = jb + 8 * qd + 4 * lh;
-          if (aligned && j + 3 < S2) {
-            *(float4*)(dst + j) = make_float4(acc[a][c][4 * qd], acc[a][c][4 * qd + 1], acc[a][c][4 * qd + 2], acc[a][c][4 * qd + 3]);
-          } else {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-              if (j + t < S2) dst[j + t] = acc[a][c][4 * qd + t];
-          }
-        }
-      } else {
-        // 16-bit outputs: pack 4 columns into 8 B, then merge quads (2p, 2p+1) of lanes l / l^32 into one 16-byte store
-        // (gemm_w4a8.hip's store): lanes 0-31 write columns 16p .. 16p+7, lanes 32-63 columns 16p+8 .. 16p+15 - the output
-        // is the large stream of Q K^T (S1 x S2 per head)
-        uint32_t pk[4][2];
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const float v0 = acc[a][c][4 * qd + 2 * h], v1 = acc[a][c][4 * qd + 2 * h + 1];
-            if constexpr (DT == LQER_F16) {
-              typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-              const h2 hv = {(_Float16)v0, (_Float16)v1};
-              pk[qd][h] = __builtin_bit_cast(uint32_t, hv);
-            } else {
-              pk[qd][h] = (uint32_t)f32_to_bf16_rne(v0) | ((uint32_t)f32_to_bf16_rne(v1) << 16);
-            }
-          }
-        bf16_t* dst = (bf16_t*)out + (b * S1 + i) * S2;
-        const bool wide = aligned && jb + 32 <= S2;  // wave-uniform
-        if (staged) {
-          // whole tile inside the output: the 16-byte pieces go to LDS (row-major 256 B per row, chunks XOR-ed with the row
-          // so that the 32 rows of a wave's store spread over the banks) and leave as full 256-byte row segments below
-          const int row_l = wm * 64 + c * 32 + l31;
-#pragma unroll
-          for (int p2 = 0; p2 < 2; ++p2) {
-            auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][0], pk[2 * p2 + 1][0], false, false);
-            auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][1], pk[2 * p2 + 1][1], false, false);
-            const int chunk = (wn * (32 * JT) + a * 32 + 16 * p2 + 8 * lh) >> 3;
-            *(uint4*)(smem + row_l * 256 + ((chunk ^ (row_l & 15)) << 4)) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-          }
-        } else if (wide) {
-#pragma unroll
-          for (int p2 = 0; p2 < 2; ++p2) {
-            auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][0], pk[2 * p2 + 1][0], false, false);
-            auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][1], pk[2 * p2 + 1][1], false, false);
-            if (i < S1) *(uint4*)(dst + jb + 16 * p2 + 8 * lh) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-          }
-        } else if (i < S1) {
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd) {
-            const int64_t j = jb + 8 * qd + 4 * lh;
-            if (j < S2) dst[j] = (bf16_t)(pk[qd][0] & 0xffff);
-            if (j + 1 < S2) dst[j + 1] = (bf16_t)(pk[qd][0] >> 16);
-            if (j + 2 < S2) dst[j + 2] = (bf16_t)(pk[qd][1] & 0xffff);
-            if (j + 3 < S2) dst[j + 3] = (bf16_t)(pk[qd][1] >> 16);
-          }
-        }
-      }
-    }
-  }
-  if (staged) {
-    __syncthreads();
-    bf16_t* const ob = (bf16_t*)out + (b * S1) * S2 + j0;
-#pragma unroll
-    for (int u = 0; u < 2048 / T; ++u) {  // 16 consecutive lanes = one row of the tile: 256 contiguous bytes
-      const int idx = tid + T * u, row_l = idx >> 4, chunk = idx & 15;
-      const uint4 v = *(const uint4*)(smem + row_l * 256 + ((chunk ^ (row_l & 15)) << 4));
-      if (i0 + row_l < S1) *(uint4*)(ob + (i0 + row_l) * S2 + chunk * 8) = v;
-    }
-  }
+#define QMM_STORE_LDS smem
+#include "qmm_store.h"
+#undef QMM_STORE_LDS
 }
-
 
 // ---- the product for a short contraction dim (K <= 128: Q K^T, K = head_dim) ---------------------------------------------
 // There the OUTPUT is the stream (S1 x S2 per head) and the first operand is small: one workgroup quantizes its 128-row tile
@@ -370,85 +292,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void k_qmatmul_xr(const v
           for (int c = 0; c < 2; ++c) acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fj[a], fi[c], acc[a][c], 0, 0, 0);
       }
     }
-    // ---- store (k_qmatmul's): fp32 directly; 16-bit through LDS as full 256-byte row segments when the tile is inside
-    const bool staged = DT != LQER_F32 && aligned && j0 + BN <= S2;  // workgroup-uniform
-    if (staged) __syncthreads();  // every wave has read its image fragments: sb is free
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int64_t i = i0 + wm * 64 + c * 32 + l31;
-#pragma unroll
-      for (int a = 0; a < JT; ++a) {
-        const int64_t jb = j0 + wn * (32 * JT) + a * 32;
-        if constexpr (DT == LQER_F32) {
-          if (i >= S1) continue;
-          float* dst = (float*)out + (b * S1 + i) * S2;
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd) {
-            const int64_t j = jb + 8 * qd + 4 * lh;
-            if (aligned && j + 3 < S2) {
-              *(float4*)(dst + j) = make_float4(acc[a][c][4 * qd], acc[a][c][4 * qd + 1], acc[a][c][4 * qd + 2], acc[a][c][4 * qd + 3]);
-            } else {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (j + e < S2) dst[j + e] = acc[a][c][4 * qd + e];
-            }
-          }
-        } else {
-          uint32_t pk[4][2];
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const float v0 = acc[a][c][4 * qd + 2 * h], v1 = acc[a][c][4 * qd + 2 * h + 1];
-              if constexpr (DT == LQER_F16) {
-                typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-                const h2 hv = {(_Float16)v0, (_Float16)v1};
-                pk[qd][h] = __builtin_bit_cast(uint32_t, hv);
-              } else {
-                pk[qd][h] = (uint32_t)f32_to_bf16_rne(v0) | ((uint32_t)f32_to_bf16_rne(v1) << 16);
-              }
-            }
-          bf16_t* dst = (bf16_t*)out + (b * S1 + i) * S2;
-          const bool wide = aligned && jb + 32 <= S2;  // wave-uniform
-          if (staged) {
-            const int row_l = wm * 64 + c * 32 + l31;
-#pragma unroll
-            for (int p2 = 0; p2 < 2; ++p2) {
-              auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][0], pk[2 * p2 + 1][0], false, false);
-              auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][1], pk[2 * p2 + 1][1], false, false);
-              const int chunk = (wn * (32 * JT) + a * 32 + 16 * p2 + 8 * lh) >> 3;
-              *(uint4*)(sb + row_l * 256 + ((chunk ^ (row_l & 15)) << 4)) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-            }
-          } else if (wide) {
-#pragma unroll
-            for (int p2 = 0; p2 < 2; ++p2) {
-              auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][0], pk[2 * p2 + 1][0], false, false);
-              auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * p2][1], pk[2 * p2 + 1][1], false, false);
-              if (i < S1) *(uint4*)(dst + jb + 16 * p2 + 8 * lh) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-            }
-          } else if (i < S1) {
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-              const int64_t j = jb + 8 * qd + 4 * lh;
-              if (j < S2) dst[j] = (bf16_t)(pk[qd][0] & 0xffff);
-              if (j + 1 < S2) dst[j + 1] = (bf16_t)(pk[qd][0] >> 16);
-              if (j + 2 < S2) dst[j + 2] = (bf16_t)(pk[qd][1] & 0xffff);
-              if (j + 3 < S2) dst[j + 3] = (bf16_t)(pk[qd][1] >> 16);
-            }
-          }
-        }
-      }
-    }
-    if (staged) {
-      __syncthreads();
-      bf16_t* const ob = (bf16_t*)out + (b * S1) * S2 + j0;
-#pragma unroll
-      for (int u = 0; u < 2048 / T; ++u) {  // 16 consecutive lanes = one row of the tile: 256 contiguous bytes
-        const int idx = tid + T * u, row_l = idx >> 4, chunk = idx & 15;
-        const uint4 v = *(const uint4*)(sb + row_l * 256 + ((chunk ^ (row_l & 15)) << 4));
-        if (i0 + row_l < S1) *(uint4*)(ob + (i0 + row_l) * S2 + chunk * 8) = v;
-      }
-    }
+    // ---- store (qmm_store.h): the image tile's LDS is reused for the 16-bit output tile
+#define QMM_STORE_LDS sb
+#include "qmm_store.h"
+#undef QMM_STORE_LDS
   }
 }
 
@@ -468,6 +315,10 @@ size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t 
   return n;
 }
 
+#ifndef LQER_QMM_NW
+#define LQER_QMM_NW 8  // waves of the prefetching product (4: its 256-thread geometry)
+#endif
+
 template <int DT>
 static int launch_qmm(const void* x, const void* y, void* out, int64_t batch, int64_t S1, int64_t K, int64_t S2, int64_t x_bs, int64_t x_rs,
                       int64_t y_bs, int64_t y_ks, int64_t y_js, const QP& qx, const QP& qy, bf16_t* img, hipStream_t st) {
@@ -477,60 +328,46 @@ static int launch_qmm(const void* x, const void* y, void* out, int64_t batch, in
   // ---- operands whose blocks are not 16 elements: the standalone quantizer writes their bf16 images first (any 16 n, whole
   // rows), the image / product kernels then take those as they are (PRE / XPRE) - the same bits as the fused form would give
   const bool x_pre = qx.block != 16, y_pre = qy.block != 16;
-  if (x_pre || y_pre) {
-    unsigned char* wsp = (unsigned char*)img + qmm_align(qmatmul_workspace_bytes(batch, K, S2));
-    const int64_t S2q = (S2 + 63) / 64 * 64;
-    const bf16_t* xi = nullptr;
-    const bf16_t* yi = nullptr;
-    if (x_pre) {  // rows (b, i) must be evenly spaced: x_bs == S1 x_rs (the caller guarantees it)
-      QuantOut o{nullptr, nullptr, nullptr, (bf16_t*)wsp, Kp, 0};
-      const int rc = quantize_dispatch(x, DT, batch * S1, K, x_rs, qx, o, st);
-      if (rc) return rc;
-      xi = (const bf16_t*)wsp;
-      wsp += qmm_align((size_t)lqer_padded_m(batch * S1) * Kp * sizeof(bf16_t));
-    }
-    if (y_pre) {  // y [b][k][j] dense along j, rows (b, k) evenly spaced: y_bs == K y_ks
-      QuantOut o{nullptr, nullptr, nullptr, (bf16_t*)wsp, S2q, 0};
-      const int rc = quantize_dispatch(y, DT, batch * K, S2, y_ks, qy, o, st);
-      if (rc) return rc;
-      yi = (const bf16_t*)wsp;
-    }
-    const dim3 gi((unsigned)(S2p / 64), (unsigned)(Kp / 64), (unsigned)batch);
-    if (y_pre)
-      qmm::k_qmm_bimage_j<LQER_BF16, true><<<gi, 256, 0, st>>>(yi, K, S2, K * S2q, S2q, qy, img, S2p, Kp, true);
-    else if (y_js == 1)
-      qmm::k_qmm_bimage_j<DT><<<gi, 256, 0, st>>>(y, K, S2, y_bs, y_ks, qy, img, S2p, Kp, al16(y, y_bs, y_ks));
-    else
-      qmm::k_qmm_bimage_k<DT><<<dim3((unsigned)(Kp / 64), (unsigned)(S2p / 64), (unsigned)batch), 256, 0, st>>>(y, K, S2, y_bs, y_js, qy, img, S2p, Kp,
-                                                                                                          al16(y, y_bs, y_js));
-    const dim3 grid((unsigned)(S2p / qmm::BN), (unsigned)((S1 + qmm::BM - 1) / qmm::BM), (unsigned)batch);
-    if (x_pre)
-      qmm::k_qmatmul<DT, false, 4, true><<<grid, 256, 0, st>>>(xi, img, out, S1, K, S2, S1 * Kp, Kp, S2p, Kp, qx, true);
-    else
-      qmm::k_qmatmul<DT, false><<<grid, 256, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, al16(x, x_bs, x_rs));
-    return check_launch("lqer_matmul_q");
+  const int64_t S2q = (S2 + 63) / 64 * 64;
+  const bf16_t* xi = nullptr;
+  const bf16_t* yi = nullptr;
+  unsigned char* wsp = (unsigned char*)img + qmm_align(qmatmul_workspace_bytes(batch, K, S2));
+  if (x_pre) {  // rows (b, i) must be evenly spaced: x_bs == S1 x_rs (the caller guarantees it)
+    QuantOut o{nullptr, nullptr, nullptr, (bf16_t*)wsp, Kp, 0};
+    const int rc = quantize_dispatch(x, DT, batch * S1, K, x_rs, qx, o, st);
+    if (rc) return rc;
+    xi = (const bf16_t*)wsp;
+    wsp += qmm_align((size_t)lqer_padded_m(batch * S1) * Kp * sizeof(bf16_t));
   }
-  if (y_js == 1) {
-    const dim3 grid((unsigned)(S2p / 64), (unsigned)(Kp / 64), (unsigned)batch);
-    qmm::k_qmm_bimage_j<DT><<<grid, 256, 0, st>>>(y, K, S2, y_bs, y_ks, qy, img, S2p, Kp, al16(y, y_bs, y_ks));
-  } else {
-    const dim3 grid((unsigned)(Kp / 64), (unsigned)(S2p / 64), (unsigned)batch);
-    qmm::k_qmm_bimage_k<DT><<<grid, 256, 0, st>>>(y, K, S2, y_bs, y_js, qy, img, S2p, Kp, al16(y, y_bs, y_js));
+  if (y_pre) {  // y [b][k][j] dense along j, rows (b, k) evenly spaced: y_bs == K y_ks
+    QuantOut o{nullptr, nullptr, nullptr, (bf16_t*)wsp, S2q, 0};
+    const int rc = quantize_dispatch(y, DT, batch * K, S2, y_ks, qy, o, st);
+    if (rc) return rc;
+    yi = (const bf16_t*)wsp;
   }
-  if (Kp <= qmm::XR_MAXK && S2p / qmm::BN >= 2 * qmm::XR_JT) {  // short contraction, many column tiles: x tile resident in LDS
-    const dim3 grid((unsigned)((S2p / qmm::BN + qmm::XR_JT - 1) / qmm::XR_JT), (unsigned)((S1 + qmm::BM - 1) / qmm::BM), (unsigned)batch);
-    qmm::k_qmatmul_xr<DT><<<grid, 512, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, al16(x, x_bs, x_rs));
-    return check_launch("lqer_matmul_q");
-  }
-  const dim3 grid((unsigned)(S2p / qmm::BN), (unsigned)((S1 + qmm::BM - 1) / qmm::BM), (unsigned)batch);
+  // ---- the image of y, in one of three forms: the standalone quantizer's image taken as it is (PRE), y contiguous along j, along k
+  const dim3 grid_j((unsigned)(S2p / 64), (unsigned)(Kp / 64), (unsigned)batch), grid_k((unsigned)(Kp / 64), (unsigned)(S2p / 64), (unsigned)batch);
+  if (y_pre) qmm::k_qmm_bimage_j<LQER_BF16, true><<<grid_j, 256, 0, st>>>(yi, K, S2, K * S2q, S2q, qy, img, S2p, Kp, true);
+  else if (y_js == 1) qmm::k_qmm_bimage_j<DT><<<grid_j, 256, 0, st>>>(y, K, S2, y_bs, y_ks, qy, img, S2p, Kp, al16(y, y_bs, y_ks));
+  else qmm::k_qmm_bimage_k<DT><<<grid_k, 256, 0, st>>>(y, K, S2, y_bs, y_js, qy, img, S2p, Kp, al16(y, y_bs, y_js));
+  // ---- the product: a 128 x 128 tile per workgroup; k_qmatmul_xr walks XR_JT column tiles with one x tile
+  const unsigned tj = (unsigned)(S2p / qmm::BN), ti = (unsigned)((S1 + qmm::BM - 1) / qmm::BM);
+  const dim3 grid(tj, ti, (unsigned)batch);
   const bool vec = al16(x, x_bs, x_rs);
-#ifndef LQER_QMM_NW
-#define LQER_QMM_NW 8
-#endif
-  if (vec && K % 16 == 0 && K >= 16)
-    qmm::k_qmatmul<DT, true, LQER_QMM_NW><<<grid, 64 * LQER_QMM_NW, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, vec);
-  else
-    qmm::k_qmatmul<DT, false><<<grid, 256, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, vec);
+  enum { XPRE, XR, PF, PLAIN };
+  const int product = x_pre                                                 ? XPRE   // x is the standalone quantizer's image
+                      : y_pre                                               ? PLAIN  // (beside a PRE image: the plain loop)
+                      : Kp <= qmm::XR_MAXK && S2p / qmm::BN >= 2 * qmm::XR_JT ? XR     // short contraction, many column tiles: x tile resident in LDS
+                      : vec && K % 16 == 0 && K >= 16                       ? PF     // aligned rows of whole blocks: the register ring
+                                                                            : PLAIN;
+  switch (product) {
+    case XPRE: qmm::k_qmatmul<DT, false, 4, true><<<grid, 256, 0, st>>>(xi, img, out, S1, K, S2, S1 * Kp, Kp, S2p, Kp, qx, true); break;
+    case XR:
+      qmm::k_qmatmul_xr<DT><<<dim3((tj + qmm::XR_JT - 1) / qmm::XR_JT, ti, (unsigned)batch), 512, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, vec);
+      break;
+    case PF: qmm::k_qmatmul<DT, true, LQER_QMM_NW><<<grid, 64 * LQER_QMM_NW, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, vec); break;
+    default: qmm::k_qmatmul<DT, false><<<grid, 256, 0, st>>>(x, img, out, S1, K, S2, x_bs, x_rs, S2p, Kp, qx, vec);
+  }
   return check_launch("lqer_matmul_q");
 }
 

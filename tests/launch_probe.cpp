@@ -11,6 +11,18 @@
 //                                         lqer_quantize_act_xa_prep (and its *ready_bytes), lqer_lowrank_xa on the image.  Here the
 //                                         sizing arguments of the side kernels that a grid does not pin are printed as well, and the
 //                                         two stream calls of this side (hipMemcpy2DAsync, hipMemsetAsync) as pseudo-launches.
+//   launch_probe LIBRARY CUS attn < cases the ATTENTION side (tests/test_attn_launches_cpu.py), one call per line, the entry point's name
+//                                         (without lqer_) first:
+//                                           matmul_q dtype batch S1 K S2 x_block y_block y_layout (0: j contiguous, 1: k contiguous)
+//                                                    x_off y_off (pointer off by so many elements) ws (0: what the size function says,
+//                                                    1: one byte less)
+//                                           attention_q... dtype batch heads kv_heads S T D mask (0: none, 1: tensor with rows of a
+//                                                    multiple of four elements, 2: rows of one more, 3: the causal rule) q_off ws nulls
+//                                                    (1: no q_strides) block k_kind v_kind window total n_groups
+//                                         with S the bound max_s of the entries with per-sequence counts and T the bound max_len of the
+//                                         paged ones (window, total, n_groups: read by the entries that have them).  Caches, pools and
+//                                         workspaces are sized by the library's own functions; printed behind the launches: ws= the value
+//                                         of the entry's *_workspace_bytes function, the return code, the refusal's text.
 #include <dlfcn.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -66,10 +78,118 @@ int hipMemcpy2DAsync(void*, size_t dpitch, const void*, size_t spitch, size_t wi
 int hipMemsetAsync(void*, int value, size_t bytes, void*) { return printf(" hipMemsetAsync %d %zu", value, bytes), 0; }
 }
 
+// mode attn: the two products and the twelve attention entries
+static int attn_cases(void* lib) {
+#define SYM(n) const auto n = (decltype(&lqer_##n))dlsym(lib, "lqer_" #n)
+  SYM(last_error);
+  SYM(matmul_q);
+  SYM(matmul_q_workspace_bytes_fmt);
+  SYM(kv_cache_bytes);
+  SYM(kv_pool_bytes_fmt);
+  SYM(attention_q);
+  SYM(attention_q_workspace_bytes);
+  SYM(attention_q_decode);
+  SYM(attention_q_decode_workspace_bytes);
+  SYM(attention_q_decode_kv);
+  SYM(attention_q_decode_kv_workspace_bytes);
+  SYM(attention_q_kv);
+  SYM(attention_q_kv_workspace_bytes);
+  SYM(attention_q_decode_paged);
+  SYM(attention_q_decode_paged_window);
+  SYM(attention_q_decode_paged_shared);
+  SYM(attention_q_decode_paged_workspace_bytes);
+  SYM(attention_q_decode_paged_ragged);
+  SYM(attention_q_decode_paged_ragged_workspace_bytes);
+  SYM(attention_q_paged);
+  SYM(attention_q_paged_window);
+  SYM(attention_q_paged_workspace_bytes);
+  SYM(attention_q_paged_ragged);
+  SYM(attention_q_paged_ragged_window);
+  SYM(attention_q_paged_ragged_workspace_bytes);
+#undef SYM
+  char* const p = (char*)(uintptr_t)0x40000000;  // (aligned, never read; the operands 256 MiB apart)
+  const auto at = [&](int i) { return p + ((size_t)i << 28); };
+  const auto done = [&](size_t need, int rc) { printf(" ws=%zu -> %d%s%s\n", need, rc, rc ? " " : "", rc ? last_error() : ""); };
+  char name[64];
+  while (scanf("%63s", name) == 1) {
+    const auto is = [&](const char* s) { return !strcmp(name, s); };
+    int dtype;
+    long long batch;
+    if (is("matmul_q")) {
+      long long S1, K, S2;
+      int xb, yb, lay, xo, yo, wsv;
+      if (scanf("%d %lld %lld %lld %lld %d %d %d %d %d %d", &dtype, &batch, &S1, &K, &S2, &xb, &yb, &lay, &xo, &yo, &wsv) != 11) return 2;
+      const int esz = dtype == LQER_F32 ? 4 : 2;
+      const lqer_qfmt_t fx = {LQER_Q_MXINT, 8, xb, 8, 127}, fy = {LQER_Q_MXINT, 8, yb, 8, 127};
+      const size_t need = matmul_q_workspace_bytes_fmt(batch, S1, K, S2, &fx, &fy);
+      done(need, matmul_q(at(1) + xo * esz, at(2) + yo * esz, at(3), dtype, batch, S1, K, S2, S1 * K, K, K * S2, lay ? 1 : S2, lay ? K : 1, &fx, &fy,
+                          at(4), need - (wsv && need), nullptr));
+      continue;
+    }
+    long long heads, kvh, S, T, D, W, total, groups;
+    int mask, qo, wsv, nulls, blk, kk, vk;
+    if (scanf("%d %lld %lld %lld %lld %lld %lld %d %d %d %d %d %d %d %lld %lld %lld", &dtype, &batch, &heads, &kvh, &S, &T, &D, &mask, &qo, &wsv, &nulls,
+              &blk, &kk, &vk, &W, &total, &groups) != 17)
+      return 2;
+    const int esz = dtype == LQER_F32 ? 4 : 2, causal = mask == 3;
+    const lqer_qfmt_t f = {LQER_Q_MXINT, 8, blk, 8, 127}, fk = {kk, kk == LQER_Q_MXINT_C4 ? 4 : 8, blk, 8, 127},
+                      fv = {vk, vk == LQER_Q_MXINT_C4 ? 4 : 8, blk, 8, 127};
+    const int64_t mr = (T + 3) / 4 * 4 + (mask == 2);
+    const int64_t qs3[3] = {heads * S * D, S * D, D}, kv3[3] = {kvh * T * D, T * D, D}, ms3[3] = {heads * S * mr, S * mr, mr};
+    const int64_t qs2[2] = {heads * D, D};  // per-sequence counts: (token, head)
+    const int64_t *qs = nulls ? nullptr : qs3, *qsr = nulls ? nullptr : qs2;
+    const void *q = at(1) + qo * esz, *k = at(2), *v = at(3), *m = mask == 1 || mask == 2 ? at(4) : nullptr;
+    void *out = at(5), *ws = at(6), *kvbuf = at(7);
+    float* stats = (float*)at(8);
+    const int32_t* dev = (const int32_t*)at(9);  // (every int32 array on the device)
+    const auto cut = [&](size_t need) { return need - (wsv && need); };
+    // a cache of exactly T keys; a pool of one table row per sequence, max_len keys each
+    const int64_t cap = T > 0 ? T : 1, stride = (cap + 15) / 16, slots = batch > 0 ? batch : 1, pages = slots * stride;
+    size_t need = 0;
+    int rc = 0;
+#define DENSE(fn) (need = fn##_workspace_bytes(batch, heads, kvh, S, T, D), \
+                   fn(q, k, v, m, out, stats, dtype, batch, heads, kvh, S, T, D, qs, kv3, kv3, ms3, qs3, 0.125f, causal, &f, &fk, &f, &fv, ws, cut(need), nullptr))
+#define CACHE(fn) (need = fn##_workspace_bytes(batch, heads, kvh, S, T, D),                                                                \
+                   fn(q, kvbuf, kv_cache_bytes(dtype, batch, kvh, cap, D), cap, m, out, stats, dtype, batch, heads, kvh, S, T, D, qs, ms3, qs3, 0.125f, \
+                      causal, &f, &fk, &f, &fv, ws, cut(need), nullptr))
+#define POOL kvbuf, kv_pool_bytes_fmt(dtype, pages, slots, kvh, D, &fk, &fv), pages, slots, dev, stride, dev, dev, T, out, stats, dtype, batch, heads, kvh
+#define TAIL 0.125f, causal, &f, &fk, &f, &fv, ws, cut(need), nullptr
+    if (is("attention_q")) rc = DENSE(attention_q);
+    else if (is("attention_q_decode")) rc = DENSE(attention_q_decode);
+    else if (is("attention_q_decode_kv")) rc = CACHE(attention_q_decode_kv);
+    else if (is("attention_q_kv")) rc = CACHE(attention_q_kv);
+    else if (!strncmp(name, "attention_q_decode_paged", 24)) {
+      need = is("attention_q_decode_paged_ragged") ? attention_q_decode_paged_ragged_workspace_bytes(total, heads, T, D)
+                                                   : attention_q_decode_paged_workspace_bytes(batch, heads, kvh, S, T, D);
+      if (is("attention_q_decode_paged")) rc = attention_q_decode_paged(q, POOL, S, D, qs, qs3, TAIL);
+      else if (is("attention_q_decode_paged_window")) rc = attention_q_decode_paged_window(q, POOL, S, D, qs, qs3, TAIL, W);
+      else if (is("attention_q_decode_paged_shared")) rc = attention_q_decode_paged_shared(q, POOL, S, D, qs, qs3, TAIL, dev, dev, dev, dev, groups);
+      else if (is("attention_q_decode_paged_ragged")) rc = attention_q_decode_paged_ragged(q, POOL, dev, S, total, D, qsr, qs2, TAIL, W);
+      else return 2;
+    } else if (is("attention_q_paged") || is("attention_q_paged_window")) {
+      need = attention_q_paged_workspace_bytes(batch, heads, kvh, S, T, D);
+      rc = is("attention_q_paged") ? attention_q_paged(q, POOL, S, D, qs, qs3, TAIL) : attention_q_paged_window(q, POOL, S, D, qs, qs3, TAIL, W);
+    } else if (is("attention_q_paged_ragged") || is("attention_q_paged_ragged_window")) {
+      need = attention_q_paged_ragged_workspace_bytes(batch, heads, kvh, S, T, D);
+      rc = is("attention_q_paged_ragged") ? attention_q_paged_ragged(q, POOL, dev, S, total, D, qsr, qs2, TAIL)
+                                          : attention_q_paged_ragged_window(q, POOL, dev, S, total, D, qsr, qs2, TAIL, W);
+    } else {
+      return 2;
+    }
+#undef DENSE
+#undef CACHE
+#undef POOL
+#undef TAIL
+    done(need, rc);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   void* lib = argc > 1 ? dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL) : nullptr;
   if (argc > 2) sscanf(argv[2], "%d", &g_cus);
   if (!lib) return fprintf(stderr, "launch_probe: %s\n", dlerror()), 2;
+  if (argc > 3 && !strcmp(argv[3], "attn")) return attn_cases(lib);
   auto gemm = (decltype(&lqer_linear_gemm_ld))dlsym(lib, "lqer_linear_gemm_ld");
   auto limbs = (decltype(&lqer_desc_limbs))dlsym(lib, "lqer_desc_limbs");
   auto padded_r = (decltype(&lqer_padded_r))dlsym(lib, "lqer_padded_r");
