@@ -28,105 +28,108 @@ int check_launch(const char* what) {
 }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// a refusal as one statement: its text, and the code to return - or a check's "no"
+template <class... A>
+static int fail(int rc, const char* fmt, A... a) {
+  set_error(fmt, a...);
+  return rc;
+}
+template <class... A>
+static bool refuse(const char* fmt, A... a) {
+  set_error(fmt, a...);
+  return false;
+}
 
-// a minifloat format the HIP path serves: width 2..max_width, exp_width 1..width-1, every non-zero value a normal bf16 number (the bf16
-// images are exact, the MFMAs see no subnormal operand); weights also need the e4m3 table of their 4-bit codes (mf_e4m3_table)
-static bool minifloat_fmt_ok(const lqer_qfmt_t& f, const char* name, int max_width) {
-  if (f.width < 2 || f.width > max_width) {
-    set_error("%s: minifloat width %d outside [2,%d]%s", name, f.width, max_width,
-              max_width == 4 ? " (minifloat weights of 5..8 bits need an 8-bit code image: not implemented)" : "");
-    return false;
-  }
-  if (f.exp_width < 1 || f.exp_width > f.width - 1) {
-    set_error("%s: minifloat exponent_width %d outside [1,%d] (width %d: mantissa bits = width - exponent_width - 1 >= 0)", name,
-              f.exp_width, f.width - 1, f.width);
-    return false;
-  }
+// What a format may be, by the role it plays in a call: one row per role.  `name` opens every refusal's text.
+enum Role {
+  ROLE_X, ROLE_W, ROLE_W_GROUP, ROLE_B, ROLE_A_OUT, ROLE_B_OUT, ROLE_QUANTIZE, ROLE_QUANTIZE_TILES, ROLE_MATMUL_X, ROLE_MATMUL_W,
+  ROLE_ATTN_Q, ROLE_ATTN_K, ROLE_ATTN_P, ROLE_ATTN_V, ROLE_ATTN_KV
+};
+struct RoleRow {
+  const char* name;
+  int max_width;            // the widest block_fp or signed integer format
+  bool integer, minifloat;  // LQER_Q_INT / LQER_Q_MINIFLOAT are served
+  bool weight;              // a packed weight: signed integers only (two's-complement nibbles), minifloats of 2..4 bits with an e4m3 table
+  bool f16, i8;             // LQER_Q_PASSTHROUGH_F16 / LQER_Q_MXINT_I8 are accepted (the x_quantizer kinds)
+};
+static const RoleRow ROLES[] = {
+    {"x_quantizer", 9, true, true, false, true, true},
+    {"w_quantizer", 8, true, true, true, false, false},
+    {"w_quantizer", 4, true, true, true, false, false},  // a group member's: the one-launch decode kernel reads one image of 4-bit panels
+    {"b_quantizer", 24, true, true, false, false, false},
+    {"A_out_quantizer", 9, true, true, false, false, false},
+    {"B_out_quantizer", 24, true, true, false, false, false},
+    {"quantize_mxint", 24, true, true, false, false, false},
+    {"quantize_mxint_tiles", 24, false, false, false, false, false},
+    {"matmul x_quantizer", 8, false, true, false, false, false},
+    {"matmul w_quantizer", 8, false, true, false, false, false},
+    {"attention Q quantizer", 8, false, false, false, false, false},
+    {"attention K quantizer", 8, false, false, false, false, false},
+    {"attention P quantizer", 8, false, false, false, false, false},
+    {"attention V quantizer", 8, false, false, false, false, false},
+    {"attention K / V quantizer", 8, false, false, false, false, false},
+};
+
+// a minifloat format the HIP path serves: width 2..8 (weights: 2..4), exp_width 1..width-1, every non-zero value a normal bf16 number (the
+// bf16 images are exact, the MFMAs see no subnormal operand); weights also need the e4m3 table of their 4-bit codes (mf_e4m3_table)
+static bool minifloat_fmt_ok(const lqer_qfmt_t& f, const char* name, bool weight) {
+  const int max_width = weight ? 4 : 8;
+  if (f.width < 2 || f.width > max_width)
+    return refuse("%s: minifloat width %d outside [2,%d]%s", name, f.width, max_width,
+                  weight ? " (minifloat weights of 5..8 bits need an 8-bit code image: not implemented)" : "");
+  if (f.exp_width < 1 || f.exp_width > f.width - 1)
+    return refuse("%s: minifloat exponent_width %d outside [1,%d] (width %d: mantissa bits = width - exponent_width - 1 >= 0)", name,
+                  f.exp_width, f.width - 1, f.width);
   const int mbits = f.width - f.exp_width - 1;
   const int emax = (1 << f.exp_width) - 1 - f.exp_bias, lowest = 1 - f.exp_bias - mbits;  // exponents of the largest / smallest value
-  if (f.exp_bias < -1000 || f.exp_bias > 1000 || emax > 127 || lowest < -126) {
-    set_error("%s: minifloat exponent_bias %d: the values span 2^%d .. 2^%d, outside the normal bf16 range 2^-126 .. 2^127", name,
-              f.exp_bias, lowest, emax);
-    return false;
-  }
-  if (max_width == 4) {
+  if (f.exp_bias < -1000 || f.exp_bias > 1000 || emax > 127 || lowest < -126)
+    return refuse("%s: minifloat exponent_bias %d: the values span 2^%d .. 2^%d, outside the normal bf16 range 2^-126 .. 2^127", name,
+                  f.exp_bias, lowest, emax);
+  if (weight) {
     uint32_t lut[2];
     int s;
-    if (!mf_e4m3_table(f, lut, &s)) {
-      set_error("%s: minifloat(%d, %d, %d): its values are not e4m3 numbers times one power of two", name, f.width, f.exp_width,
-                f.exp_bias);
-      return false;
-    }
+    if (!mf_e4m3_table(f, lut, &s))
+      return refuse("%s: minifloat(%d, %d, %d): its values are not e4m3 numbers times one power of two", name, f.width, f.exp_width,
+                    f.exp_bias);
   }
   return true;
 }
 
-static bool fmt_ok(const lqer_qfmt_t* f, const char* name, int max_width) {
-  if (!f) {
-    set_error("%s: null format", name);
-    return false;
-  }
+static bool fmt_ok(const lqer_qfmt_t* f, Role role) {
+  const RoleRow& r = ROLES[role];
+  const char* const name = r.name;
+  const int max_width = r.max_width;
+  if (!f) return refuse("%s: null format", name);
   if (f->kind == LQER_Q_PASSTHROUGH) return true;
-  if (f->kind == LQER_Q_PASSTHROUGH_F16 && strcmp(name, "x_quantizer") == 0) return true;
-  if (f->kind == LQER_Q_MXINT_I8 && strcmp(name, "x_quantizer") != 0) {
-    set_error("%s: LQER_Q_MXINT_I8 is an x_quantizer kind", name);
-    return false;
-  }
-  if (f->kind == LQER_Q_MXINT_C4) {  // (the pool entries replace it by LQER_Q_MXINT before they come here: pool_code_fmt)
-    set_error("%s: LQER_Q_MXINT_C4 names the nibble code storage of the paged KV pool - a k_fmt / v_fmt kind of the lqer_kv_pool_* and "
-              "lqer_attention_q_*paged* entries only", name);
-    return false;
-  }
+  if (f->kind == LQER_Q_PASSTHROUGH_F16 && r.f16) return true;
+  if (f->kind == LQER_Q_MXINT_I8 && !r.i8) return refuse("%s: LQER_Q_MXINT_I8 is an x_quantizer kind", name);
+  if (f->kind == LQER_Q_MXINT_C4)  // (the pool entries replace it by LQER_Q_MXINT before they come here: pool_code_fmt)
+    return refuse("%s: LQER_Q_MXINT_C4 names the nibble code storage of the paged KV pool - a k_fmt / v_fmt kind of the lqer_kv_pool_* and "
+                  "lqer_attention_q_*paged* entries only", name);
   if (f->kind == LQER_Q_INT) {  // fixed point: exp_bias = frac_width, exp_width = is_signed
-    const bool role_ok = !strcmp(name, "x_quantizer") || !strcmp(name, "b_quantizer") || !strcmp(name, "A_out_quantizer") ||
-                         !strcmp(name, "B_out_quantizer") || !strcmp(name, "quantize_mxint") || !strcmp(name, "w_quantizer");
-    if (!role_ok) {
-      set_error("%s: the integer quantizer is not implemented in this role", name);
-      return false;
-    }
-    if (!strcmp(name, "w_quantizer") && !f->exp_width) {  // codes travel as two's-complement nibbles: signed, 2..4 bits
-      set_error("w_quantizer: an unsigned integer weight is not implemented (4-bit codes 0..15 do not fit the two's-complement nibble)");
-      return false;
-    }
+    if (!r.integer) return refuse("%s: the integer quantizer is not implemented in this role", name);
+    if (r.weight && !f->exp_width)  // codes travel as two's-complement nibbles: signed, 2..4 bits
+      return refuse("%s: an unsigned integer weight is not implemented (4-bit codes 0..15 do not fit the two's-complement nibble)", name);
     const int maxw = f->exp_width ? max_width : max_width - 1;  // unsigned: one magnitude bit more per width
-    if (f->width < 1 || f->width > maxw || f->exp_bias < -100 || f->exp_bias > 100) {
-      set_error("%s: integer width %d outside [1,%d] or frac_width %d outside [-100,100]", name, f->width, maxw, f->exp_bias);
-      return false;
-    }
+    if (f->width < 1 || f->width > maxw || f->exp_bias < -100 || f->exp_bias > 100)
+      return refuse("%s: integer width %d outside [1,%d] or frac_width %d outside [-100,100]", name, f->width, maxw, f->exp_bias);
     return true;
   }
   if (f->kind == LQER_Q_MINIFLOAT) {  // width, exp_width, exp_bias = the resolved bias (include/lqer_hip.h)
-    const bool role_ok = !strcmp(name, "x_quantizer") || !strcmp(name, "b_quantizer") || !strcmp(name, "A_out_quantizer") ||
-                         !strcmp(name, "B_out_quantizer") || !strcmp(name, "quantize_mxint") || !strcmp(name, "w_quantizer") ||
-                         !strncmp(name, "matmul ", 7);
-    if (!role_ok) {
-      set_error("%s: the minifloat quantizer is not implemented in this role", name);
-      return false;
-    }
-    return minifloat_fmt_ok(*f, name, !strcmp(name, "w_quantizer") ? 4 : 8);
+    if (!r.minifloat) return refuse("%s: the minifloat quantizer is not implemented in this role", name);
+    return minifloat_fmt_ok(*f, name, r.weight);
   }
-  if (f->kind != LQER_Q_MXINT && f->kind != LQER_Q_MXINT_I8) {
-    set_error("%s: quantizer kind %d is not implemented on the HIP path", name, f->kind);
-    return false;
-  }
-  if (f->width < 2 || f->width > max_width) {
-    set_error("%s: width %d outside [2,%d]", name, f->width, max_width);
-    return false;
-  }
-  if (f->exp_width < 1 || f->exp_width > 8) {
-    set_error("%s: exponent_width %d outside [1,8]", name, f->exp_width);
-    return false;
-  }
+  if (f->kind != LQER_Q_MXINT && f->kind != LQER_Q_MXINT_I8) return refuse("%s: quantizer kind %d is not implemented on the HIP path", name, f->kind);
+  if (f->width < 2 || f->width > max_width) return refuse("%s: width %d outside [2,%d]", name, f->width, max_width);
+  if (f->exp_width < 1 || f->exp_width > 8) return refuse("%s: exponent_width %d outside [1,8]", name, f->exp_width);
   // every block scale 2^(e - mbits), e in [emin, emax], must be reachable as a normal float from some block: the kernels build it from
   // exponent bits (and flush what is below 1e-8) on the argument that e - mbits < -126 happens only under an upper clamp nobody
   // configures - and an emin beyond 127 would put every block's 2^e past fp32 (include/lqer_hip.h, lqer_qfmt_t)
   const int mbits = f->width - 1, emin = -f->exp_bias, emax = (1 << f->exp_width) - 1 - f->exp_bias;
-  if (f->exp_bias > 1000 || f->exp_bias < -1000 || emax - mbits < -126 || emin > 127) {
-    set_error("%s: block_fp exponent_bias %d (exponent_width %d, width %d): exponents [%d,%d] - needs emax - (width-1) >= -126 and "
-              "emin <= 127, i.e. a bias in [-127,%d]", name, f->exp_bias, f->exp_width, f->width, emin, emax,
-              (1 << f->exp_width) - 1 - mbits + 126);
-    return false;
-  }
+  if (f->exp_bias > 1000 || f->exp_bias < -1000 || emax - mbits < -126 || emin > 127)
+    return refuse("%s: block_fp exponent_bias %d (exponent_width %d, width %d): exponents [%d,%d] - needs emax - (width-1) >= -126 and "
+                  "emin <= 127, i.e. a bias in [-127,%d]", name, f->exp_bias, f->exp_width, f->width, emin, emax,
+                  (1 << f->exp_width) - 1 - mbits + 126);
   return true;
 }
 
@@ -142,21 +145,6 @@ static int w_panel_limbs(const lqer_linear_desc_t* d) { return (d->w_fmt.kind ==
 // ... and the copies of the activation image that go with them: none on the int8 route (its kernel multiplies the int8 CODES of such
 // a weight, one image of its own behind the limb panels)
 static int w_limbs(const lqer_linear_desc_t* d) { return d->x_fmt.kind == LQER_Q_MXINT_I8 ? 1 : w_panel_limbs(d); }
-// bytes of the activation image buffer `xq` of the split calls: [Mp][act limbs x weight limbs x Kp] bf16 and, when the weight has
-// limbs, the single-copy image behind it (256-byte aligned) - the quantizer and the side GEMM work on that one, the GEMM on the wide one
-static size_t act_image_bytes(const lqer_linear_desc_t* d, int64_t m_max) {
-  const size_t one = align_up((size_t)lqer_padded_m(m_max) * lqer_padded_k(d->in_features) * 2 * act_limbs(d), 256);
-  // (an LQER_Q_MXINT_I8 descriptor sizes for the bf16 kernels too: token counts the int8 kernel does not serve run them on the
-  // same buffers - lqer_linear_forward switches the kind)
-  const int wl = d->x_fmt.kind == LQER_Q_MXINT_I8 ? w_panel_limbs(d) : w_limbs(d);
-  return wl > 1 ? align_up(one * wl, 256) + one : one;
-}
-static void* act_single_copy(const lqer_linear_desc_t* d, void* xq, int64_t M) {
-  const int wl = w_limbs(d);
-  if (wl == 1) return xq;
-  const size_t one = align_up((size_t)lqer_padded_m(M) * lqer_padded_k(d->in_features) * 2 * act_limbs(d), 256);
-  return (unsigned char*)xq + align_up(one * wl, 256);
-}
 static bool x_is_f16(const lqer_linear_desc_t* d) { return d->x_fmt.kind == LQER_Q_PASSTHROUGH_F16; }
 static bool x_is_i8(const lqer_linear_desc_t* d) { return d->x_fmt.kind == LQER_Q_MXINT_I8; }
 // byte offset of the int8 weight image inside w_packed (behind the sign-magnitude panels)
@@ -168,18 +156,11 @@ static size_t i8_image_offset(const lqer_linear_desc_t* d) {
 static bool i8_formats_ok(const lqer_linear_desc_t* d) {
   const lqer_qfmt_t &x = d->x_fmt, &w = d->w_fmt;
   const int64_t K = d->in_features;
-  if (x.width < 2 || x.width > 8 || !(x.block <= 0 || x.block >= K)) {
-    set_error("LQER_Q_MXINT_I8: x_quantizer must be block_fp with width <= 8 and one block per row (got width %d block %d)", x.width, x.block);
-    return false;
-  }
-  if (w.kind != LQER_Q_MXINT || w.width > 8 || !(w.block <= 0 || w.block >= K || w.block % I8_BK == 0)) {
-    set_error("LQER_Q_MXINT_I8: w_quantizer blocks must span a multiple of 128 k or the whole row (got block %d)", w.block);
-    return false;
-  }
-  if (K < I8_BK) {
-    set_error("LQER_Q_MXINT_I8: in_features %lld < 128", (long long)K);
-    return false;
-  }
+  if (x.width < 2 || x.width > 8 || !(x.block <= 0 || x.block >= K))
+    return refuse("LQER_Q_MXINT_I8: x_quantizer must be block_fp with width <= 8 and one block per row (got width %d block %d)", x.width, x.block);
+  if (w.kind != LQER_Q_MXINT || w.width > 8 || !(w.block <= 0 || w.block >= K || w.block % I8_BK == 0))
+    return refuse("LQER_Q_MXINT_I8: w_quantizer blocks must span a multiple of 128 k or the whole row (got block %d)", w.block);
+  if (K < I8_BK) return refuse("LQER_Q_MXINT_I8: in_features %lld < 128", (long long)K);
   return true;
 }
 // LQER_Q_PASSTHROUGH_F16: a dense fp16 tensor whose extents are already the padded ones IS the activation image
@@ -204,16 +185,54 @@ static bool decode_partials_ok(const lqer_linear_desc_t* d, int64_t M) {
   return bo.kind == LQER_Q_PASSTHROUGH || (bo.kind == LQER_Q_MXINT && bo.block == 16);
 }
 static bool need_f16(const lqer_linear_desc_t* d, int dtype, const char* what) {
-  if (x_is_f16(d) && dtype != LQER_F16) {
-    set_error("%s: x_quantizer LQER_Q_PASSTHROUGH_F16 takes fp16 tensors (dtype %d given)", what, dtype);
-    return false;
-  }
+  if (x_is_f16(d) && dtype != LQER_F16) return refuse("%s: x_quantizer LQER_Q_PASSTHROUGH_F16 takes fp16 tensors (dtype %d given)", what, dtype);
   return true;
 }
 // the side product x A is an fp32 sum: two limbs at least
 static int xa_limbs(const lqer_linear_desc_t* d) {
   if (d->a_out_fmt.kind != LQER_Q_PASSTHROUGH) return 1;
   return d->a_out_fmt.width <= 16 ? 2 : 3;
+}
+// row stride of xaq in elements: the padded rank, once per limb of a pass-through A_out
+static int64_t xaq_row_elems(const lqer_linear_desc_t* d) { return lqer_padded_r(d->rank) * xa_limbs(d); }
+// bytes of the standard image of d's weight (one copy: what a compact image widens into)
+static size_t std_image_bytes(const lqer_linear_desc_t* d) {
+  return (size_t)(lqer_padded_n(d->out_features) / LQER_PANEL_ROWS) * (lqer_padded_k(d->in_features) / 64) * LQER_PANEL_BYTES;
+}
+
+// Where the pieces of a forward's workspace lie for (d, m_max), as byte offsets from its start, each 256-byte aligned:
+//   [activation image | its single copy] [xaq] [shared scratch] ... [widened weight image]
+// The ONE carving: lqer_linear_sizes().workspace, lqer_act_image_bytes, the single-copy image of the split calls, lqer_linear_forward
+// and lqer_linear_forward_narrow_workspace_bytes read it.
+struct Carving {
+  // the activation image `xq` of the split calls: [Mp][act limbs x weight limbs x Kp] bf16 from offset 0 and, when the weight has limbs,
+  // the single-copy image behind it - the quantizer and the side GEMM work on that one, the GEMM on the wide one (0: one and the same)
+  size_t single;
+  size_t xaq;         // [Mp][xaq_row_elems] bf16; its offset = the bytes of the activation image buffer
+  size_t scratch;     // the side path's scratch, then the GEMM's: the two uses never overlap in time
+  size_t side_bytes;  // ... what the side path needs of it (lqer_lowrank_xa_scratch_bytes)
+  size_t gemm_bytes;  // ... what the GEMM needs (lqer_linear_gemm_scratch_bytes)
+  size_t total;       // lqer_linear_sizes().workspace
+  size_t widened;     // lqer_linear_forward_narrow: the standard image (std_image_bytes) a compact one is widened into
+};
+static Carving carve(const lqer_linear_desc_t* d, int64_t m_max) {
+  Carving c;
+  const size_t Mp = lqer_padded_m(m_max), one = align_up(Mp * lqer_padded_k(d->in_features) * 2 * act_limbs(d), 256);
+  // (an LQER_Q_MXINT_I8 descriptor sizes for the bf16 kernels too: token counts the int8 kernel does not serve run them on the same
+  // buffers - lqer_linear_forward switches the kind - while its own quantizer writes one image at the head: only `single` differs)
+  const size_t wl = w_panel_limbs(d), wide = wl > 1 ? align_up(one * wl, 256) : 0;
+  c.single = w_limbs(d) > 1 ? wide : 0;
+  c.xaq = wide + one;
+  const bool side = d->rank > 0;
+  c.scratch = c.xaq + (side ? align_up(Mp * xaq_row_elems(d) * 2, 256) : 0);
+  c.side_bytes = side ? xa_scratch_bytes(m_max, d->in_features, lqer_padded_r(d->rank)) : 0;
+  c.gemm_bytes = side && d->b_out_fmt.kind == LQER_Q_MXINT ? gemm_scratch_bytes(m_max, d->out_features, make_qp(d->b_out_fmt)) : 0;
+  c.total = c.scratch + align_up(c.side_bytes > c.gemm_bytes ? c.side_bytes : c.gemm_bytes, 256);
+  c.widened = align_up(c.total, 256);
+  return c;
+}
+static void* act_single_copy(const lqer_linear_desc_t* d, void* xq, int64_t M) {
+  return w_limbs(d) == 1 ? xq : (unsigned char*)xq + carve(d, M).single;
 }
 // The compact weight image (w_narrow.h) serves block_fp weights of width 2 and 3 whose image exists once: E > 0 = its exponent bytes
 // per row, 0 = not served (widths 4..8, integer and minifloat weights)
@@ -228,34 +247,24 @@ static size_t narrow_bytes(int64_t N, int64_t K, const lqer_qfmt_t* f) {
 // a descriptor whose forward can be handed the compact image; fills GemmArgs::w_narrow
 static int narrow_args(const lqer_linear_desc_t* d, GemmArgs& g) {
   const int E = narrow_exps(&d->w_fmt, d->in_features);
-  if (!E) {
-    set_error("compact weight image: block_fp weights of width 2 or 3 only (w_quantizer kind %d width %d: the standard image)",
-              d->w_fmt.kind, d->w_fmt.width);
-    return LQER_E_UNSUPPORTED;
-  }
-  if (x_is_i8(d)) {
-    set_error("compact weight image: not on the int8 route (LQER_Q_MXINT_I8 reads an int8 image of its own): use LQER_Q_MXINT");
-    return LQER_E_UNSUPPORTED;
-  }
-  if (act_limbs(d) != 1) {
-    set_error("compact weight image: pass-through bf16 / fp32 activations read one copy of the image per limb (%d): the standard image",
-              act_limbs(d));
-    return LQER_E_UNSUPPORTED;
-  }
-  if (d->tuning & LQER_TUNE_W_EXP_TABLE) {
-    set_error("compact weight image: a weight that needs LQER_TUNE_W_EXP_TABLE (an exponent byte above 245) keeps the standard image");
-    return LQER_E_UNSUPPORTED;
-  }
+  if (!E)
+    return fail(LQER_E_UNSUPPORTED, "compact weight image: block_fp weights of width 2 or 3 only (w_quantizer kind %d width %d: the standard image)",
+                d->w_fmt.kind, d->w_fmt.width);
+  if (x_is_i8(d))
+    return fail(LQER_E_UNSUPPORTED, "compact weight image: not on the int8 route (LQER_Q_MXINT_I8 reads an int8 image of its own): use LQER_Q_MXINT");
+  if (act_limbs(d) != 1)
+    return fail(LQER_E_UNSUPPORTED, "compact weight image: pass-through bf16 / fp32 activations read one copy of the image per limb (%d): the standard image",
+                act_limbs(d));
+  if (d->tuning & LQER_TUNE_W_EXP_TABLE)
+    return fail(LQER_E_UNSUPPORTED, "compact weight image: a weight that needs LQER_TUNE_W_EXP_TABLE (an exponent byte above 245) keeps the standard image");
   g.w_narrow = d->w_fmt.width << 8 | E;
   return LQER_OK;
 }
 
 static bool passthrough_width_ok(const lqer_qfmt_t& f, const char* name) {
-  if (f.kind == LQER_Q_PASSTHROUGH && (f.width < 1 || f.width > 24)) {
-    set_error("%s: a passthrough format must say how many significand bits to carry in `width` (8 = bf16, 11 = fp16, "
-              "16, 24 = fp32), got %d", name, f.width);
-    return false;
-  }
+  if (f.kind == LQER_Q_PASSTHROUGH && (f.width < 1 || f.width > 24))
+    return refuse("%s: a passthrough format must say how many significand bits to carry in `width` (8 = bf16, 11 = fp16, "
+                  "16, 24 = fp32), got %d", name, f.width);
   return true;
 }
 
@@ -305,7 +314,7 @@ int lqer_quantize_mxint(const void* x, int dtype, int64_t rows, int64_t cols, in
     set_error("quantize_mxint: bad shape rows=%lld cols=%lld ld=%lld", (long long)rows, (long long)cols, (long long)ld);
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(fmt, "quantize_mxint", 24)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(fmt, ROLE_QUANTIZE)) return LQER_E_UNSUPPORTED;
   if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT && fmt->kind != LQER_Q_MINIFLOAT) {
     set_error("quantize_mxint: format is neither block_fp, integer nor minifloat");
     return LQER_E_INVALID;
@@ -336,7 +345,7 @@ int lqer_quantize_mxint_tiles(const void* x, int dtype, int64_t batches, int64_t
     set_error("quantize_mxint_tiles: null pointer");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(fmt, "quantize_mxint_tiles", 24)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(fmt, ROLE_QUANTIZE_TILES)) return LQER_E_UNSUPPORTED;
   if (fmt->kind != LQER_Q_MXINT) {
     set_error("quantize_mxint_tiles: the format is not block_fp");
     return LQER_E_INVALID;
@@ -355,7 +364,7 @@ int lqer_quantize_act_mxint(const void* x, int dtype, int64_t M, int64_t K, int6
     set_error("quantize_act: bad shape M=%lld K=%lld ldx=%lld", (long long)M, (long long)K, (long long)ldx);
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(fmt, "x_quantizer", 9)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(fmt, ROLE_X)) return LQER_E_UNSUPPORTED;
   if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT && fmt->kind != LQER_Q_MINIFLOAT) {
     set_error("x_quantizer: only block_fp, integer and minifloat activations have a bf16 image on the HIP path");
     return LQER_E_UNSUPPORTED;
@@ -428,18 +437,17 @@ int lqer_unpack_weight_i8_fmt(const void* w_packed, int64_t N, int64_t K, const 
   return i8_unpack_dispatch((const unsigned char*)w_packed + i8_image_offset(&d), N, K, w_f32, (hipStream_t)stream, w_panel_limbs(&d) > 1);
 }
 
-int lqer_linear_sizes(const lqer_linear_desc_t* d, int64_t m_max, lqer_linear_sizes_t* out) {
-  if (!d || !out || d->in_features <= 0 || d->out_features <= 0 || d->rank < 0 || m_max < 0) {
-    set_error("linear_sizes: bad descriptor");
-    return LQER_E_INVALID;
-  }
+// lqer_linear_sizes, and the carving its workspace is the total of (the forward goes on with it)
+static int linear_sizes_carved(const lqer_linear_desc_t* d, int64_t m_max, lqer_linear_sizes_t* out, Carving* cv) {
+  if (!d || !out || d->in_features <= 0 || d->out_features <= 0 || d->rank < 0 || m_max < 0)
+    return fail(LQER_E_INVALID, "linear_sizes: bad descriptor");
   const size_t Kp = lqer_padded_k(d->in_features), Np = lqer_padded_n(d->out_features);
   const size_t rp = lqer_padded_r(d->rank), Mp = lqer_padded_m(m_max);
   if (!passthrough_width_ok(d->x_fmt, "x_quantizer") || (d->rank > 0 && !passthrough_width_ok(d->a_out_fmt, "A_out_quantizer")))
     return LQER_E_INVALID;
   const size_t xl = act_limbs(d), al = xa_limbs(d);  // pass-through activations: images repeated per limb
   const size_t wl = w_panel_limbs(d);
-  if (!fmt_ok(&d->w_fmt, "w_quantizer", 8)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(&d->w_fmt, ROLE_W)) return LQER_E_UNSUPPORTED;
   out->w_packed = (Np / LQER_PANEL_ROWS) * (Kp / 64) * LQER_PANEL_BYTES * xl * wl;
   if (x_is_i8(d)) {
     if (!i8_formats_ok(d)) return LQER_E_UNSUPPORTED;
@@ -449,20 +457,17 @@ int lqer_linear_sizes(const lqer_linear_desc_t* d, int64_t m_max, lqer_linear_si
   out->a_t = 3 * rp * Kp * 2 * xl;
   out->b_t = 3 * Np * rp * 2 * al;
   out->bias_q = Np * 4;
-  size_t side = 0;
-  if (rp) {
-    const size_t a = xa_scratch_bytes(m_max, d->in_features, rp);
-    const size_t b = d->b_out_fmt.kind == LQER_Q_MXINT ? gemm_scratch_bytes(m_max, d->out_features, make_qp(d->b_out_fmt)) : 0;
-    side = align_up(a > b ? a : b, 256);  // the two scratch uses never overlap in time
-  }
+  *cv = carve(d, m_max);
   // (the int8 activation image + row scales of LQER_Q_MXINT_I8 fit the bf16 image's slot: K >= 128)
-  const size_t act = act_image_bytes(d, m_max);
-  if (x_is_i8(d) && i8_act_image_bytes(m_max, d->in_features) + Mp * sizeof(float) > act) {
-    set_error("linear_sizes: int8 activation image larger than the bf16 one (K %d)", d->in_features);
-    return LQER_E_UNSUPPORTED;
-  }
-  out->workspace = act + align_up(Mp * rp * 2 * al, 256) + side;
+  if (x_is_i8(d) && i8_act_image_bytes(m_max, d->in_features) + Mp * sizeof(float) > cv->xaq)
+    return fail(LQER_E_UNSUPPORTED, "linear_sizes: int8 activation image larger than the bf16 one (K %d)", d->in_features);
+  out->workspace = cv->total;
   return LQER_OK;
+}
+
+int lqer_linear_sizes(const lqer_linear_desc_t* d, int64_t m_max, lqer_linear_sizes_t* out) {
+  Carving cv;
+  return linear_sizes_carved(d, m_max, out, &cv);
 }
 
 int lqer_pack_weight_mxint(const void* W, int dtype, int64_t N, int64_t K, int64_t ldw, const lqer_qfmt_t* fmt,
@@ -471,7 +476,7 @@ int lqer_pack_weight_mxint(const void* W, int dtype, int64_t N, int64_t K, int64
     set_error("pack_weight: bad argument");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(fmt, "w_quantizer", 8)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(fmt, ROLE_W)) return LQER_E_UNSUPPORTED;
   if (fmt->kind != LQER_Q_MXINT && fmt->kind != LQER_Q_INT && fmt->kind != LQER_Q_MINIFLOAT) {
     set_error("w_quantizer: only block_fp, integer and minifloat weights can be packed");
     return LQER_E_UNSUPPORTED;
@@ -494,7 +499,7 @@ int lqer_pack_weight_mxint_2d(const void* W, int dtype, int64_t N, int64_t K, in
     set_error("pack_weight: bad argument");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(fmt, "w_quantizer", 8)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(fmt, ROLE_W)) return LQER_E_UNSUPPORTED;
   if (fmt->kind != LQER_Q_MXINT) {
     set_error("w_quantizer: only block_fp weights can be packed");
     return LQER_E_UNSUPPORTED;
@@ -511,7 +516,7 @@ int lqer_unpack_weight_mxint(const void* w_packed, int64_t N, int64_t K, const l
   if (fmt->kind == LQER_Q_MINIFLOAT) {  // (the image's own e4m3 table and scale bytes, as the GEMM reads them)
     uint32_t lut[2];
     int s;
-    if (!fmt_ok(fmt, "w_quantizer", 8) || !mf_e4m3_table(*fmt, lut, &s)) return LQER_E_UNSUPPORTED;
+    if (!fmt_ok(fmt, ROLE_W) || !mf_e4m3_table(*fmt, lut, &s)) return LQER_E_UNSUPPORTED;
     return unpack_weight_mf_dispatch(w_packed, N, K, lut, w_f32, (hipStream_t)stream);
   }
   return unpack_weight_dispatch(w_packed, N, K, fmt->width - 1, fmt->kind == LQER_Q_INT, w_f32, (hipStream_t)stream);
@@ -531,7 +536,7 @@ int lqer_pack_bias(const void* bias, int dtype, int64_t N, const lqer_qfmt_t* fm
     set_error("pack_bias: bad argument");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(fmt, "b_quantizer", 24)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(fmt, ROLE_B)) return LQER_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (fmt->kind == LQER_Q_PASSTHROUGH) return bias_passthrough_dispatch(bias, dtype, N, bias_q, st);
   (void)hipMemsetAsync(bias_q, 0, lqer_padded_n(N) * sizeof(float), st);
@@ -550,7 +555,7 @@ int lqer_lowrank_xa(const lqer_linear_desc_t* d, const void* xq, int64_t M, cons
     set_error("lowrank_xa: bad argument");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(&d->a_out_fmt, "A_out_quantizer", 9)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(&d->a_out_fmt, ROLE_A_OUT)) return LQER_E_UNSUPPORTED;
   if (!passthrough_width_ok(d->x_fmt, "x_quantizer") || !passthrough_width_ok(d->a_out_fmt, "A_out_quantizer")) return LQER_E_INVALID;
   if ((a_limbs < 0 || a_limbs > 3) && !(a_limbs == -1 && x_is_i8(d))) {
     set_error("lowrank_xa: a_limbs %d outside [0,3] (-1 = one fp16 image of A^T: the int8 route only)", a_limbs);
@@ -612,7 +617,7 @@ static int quantize_act_xa_impl(const lqer_linear_desc_t* d, const void* x, int 
     set_error("quantize_act_xa: bad argument");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(&d->w_fmt, "w_quantizer", 8)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(&d->w_fmt, ROLE_W)) return LQER_E_UNSUPPORTED;
   const int wl = w_limbs(d);
   if (wl == 1) return quantize_act_xa_single(d, x, dtype, M, ldx, a_t, a_limbs, xq, xaq, scratch, scratch_bytes, stream, zr);
   // a weight of three 4-bit limbs: the quantizer and the side GEMM work on the single-copy image behind the wide one, which is
@@ -629,8 +634,8 @@ static int quantize_act_xa_single(const lqer_linear_desc_t* d, const void* x, in
   if (a_limbs == -2) {
     // the bf16 image of A^T with its fragment-major copy (lqer_a_b16_prepare): block-16 MXINT activations run quantizer + x A + A_out as
     // ONE launch where act16_fused.hip applies; everything else reads the image's first part as the one-limb image it is
-    if (d->rank > 0 && a_t && xaq && xq && d->x_fmt.kind == LQER_Q_MXINT && fmt_ok(&d->x_fmt, "x_quantizer", 9) &&
-        fmt_ok(&d->a_out_fmt, "A_out_quantizer", 9)) {
+    if (d->rank > 0 && a_t && xaq && xq && d->x_fmt.kind == LQER_Q_MXINT && fmt_ok(&d->x_fmt, ROLE_X) &&
+        fmt_ok(&d->a_out_fmt, ROLE_A_OUT)) {
       const int rc = act16_fused_dispatch(x, dtype, M, d->in_features, ldx, make_qp(d->x_fmt), (bf16_t*)xq, a_t, d->rank, make_qp(d->a_out_fmt),
                                           (bf16_t*)xaq, d->tuning, (hipStream_t)stream);
       if (rc != LQER_E_UNSUPPORTED) return rc;
@@ -650,7 +655,7 @@ static int quantize_act_xa_single(const lqer_linear_desc_t* d, const void* x, in
     return rc == LQER_E_UNSUPPORTED ? LQER_E_WORKSPACE : rc;
   }
   if (d->rank > 0 && a_t && xaq) {
-    if (!fmt_ok(&d->x_fmt, "x_quantizer", 9) || !fmt_ok(&d->a_out_fmt, "A_out_quantizer", 9)) return LQER_E_UNSUPPORTED;
+    if (!fmt_ok(&d->x_fmt, ROLE_X) || !fmt_ok(&d->a_out_fmt, ROLE_A_OUT)) return LQER_E_UNSUPPORTED;
     const int rc = quant_xa_fused_dispatch(x, dtype, M, d->in_features, ldx, make_qp(d->x_fmt), (bf16_t*)xq,
                                            (const bf16_t*)a_t, a_limbs, d->rank, make_qp(d->a_out_fmt), (bf16_t*)xaq,
                                            (float*)scratch, scratch_bytes, (hipStream_t)stream);
@@ -694,7 +699,7 @@ static int quantize_act_xa_single(const lqer_linear_desc_t* d, const void* x, in
 }
 
 size_t lqer_act_image_bytes(const lqer_linear_desc_t* d, int64_t m_max) {
-  return (d && m_max >= 0 && d->in_features > 0) ? act_image_bytes(d, m_max) : 0;
+  return (d && m_max >= 0 && d->in_features > 0) ? carve(d, m_max).xaq : 0;
 }
 
 size_t lqer_linear_gemm_scratch_bytes(const lqer_linear_desc_t* d, int64_t m_max) {
@@ -705,15 +710,15 @@ size_t lqer_linear_gemm_scratch_bytes(const lqer_linear_desc_t* d, int64_t m_max
 int lqer_linear_gemm(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                      const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy, void* scratch,
                      size_t scratch_bytes, void* stream) {
-  return lqer_linear_gemm_ld(d, xq, M, w_packed, xaq, d ? lqer_padded_r(d->rank) * xa_limbs(d) : 0, b_t, b_limbs, bias_q, y,
+  return lqer_linear_gemm_ld(d, xq, M, w_packed, xaq, d ? xaq_row_elems(d) : 0, b_t, b_limbs, bias_q, y,
                              dtype, ldy, scratch, scratch_bytes, stream);
 }
 
 // fills the kernel arguments that depend on the descriptor and the token count alone (shapes, formats, limb counts)
 static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, GemmArgs& g) {
   const bool lowrank = d->rank > 0;
-  if (!fmt_ok(&d->w_fmt, "w_quantizer", 8)) return LQER_E_UNSUPPORTED;
-  if (lowrank && !fmt_ok(&d->b_out_fmt, "B_out_quantizer", 24)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(&d->w_fmt, ROLE_W)) return LQER_E_UNSUPPORTED;
+  if (lowrank && !fmt_ok(&d->b_out_fmt, ROLE_B_OUT)) return LQER_E_UNSUPPORTED;
   if (!passthrough_width_ok(d->x_fmt, "x_quantizer") || (lowrank && !passthrough_width_ok(d->a_out_fmt, "A_out_quantizer")))
     return LQER_E_INVALID;
   if (!need_f16(d, dtype, "linear_gemm")) return LQER_E_INVALID;
@@ -731,11 +736,9 @@ static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, Ge
   g.w_twos = d->w_fmt.kind == LQER_Q_INT ? 1 : 0;
   if (d->w_fmt.kind == LQER_Q_MINIFLOAT) {  // minifloat weights: the nibble's magnitude code through the format's e4m3 table
     int s;
-    if (x_is_f16(d) || x_is_i8(d)) {
-      set_error("linear_gemm: minifloat weights run the bf16 128-row tile kernel only (x_quantizer %s)",
-                x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");
-      return LQER_E_UNSUPPORTED;
-    }
+    if (x_is_f16(d) || x_is_i8(d))
+      return fail(LQER_E_UNSUPPORTED, "linear_gemm: minifloat weights run the bf16 128-row tile kernel only (x_quantizer %s)",
+                  x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");
     if (!mf_e4m3_table(d->w_fmt, g.w_lut, &s)) return LQER_E_UNSUPPORTED;
     g.w_mf = 1;
   }
@@ -745,11 +748,9 @@ static int gemm_shape_args(const lqer_linear_desc_t* d, int64_t M, int dtype, Ge
     g.w_lut[0] = 0x44403800u, g.w_lut[1] = 0x4E4C4A48u;
     g.w_mf = 1;
   }
-  if (lowrank && d->b_out_fmt.kind == LQER_Q_MINIFLOAT && (x_is_i8(d) || x_is_f16(d))) {
-    set_error("linear_gemm: a minifloat B_out runs on the bf16 128-row tile kernel only (x_quantizer %s)",
-              x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH with width 11" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");
-    return LQER_E_UNSUPPORTED;
-  }
+  if (lowrank && d->b_out_fmt.kind == LQER_Q_MINIFLOAT && (x_is_i8(d) || x_is_f16(d)))
+    return fail(LQER_E_UNSUPPORTED, "linear_gemm: a minifloat B_out runs on the bf16 128-row tile kernel only (x_quantizer %s)",
+                x_is_f16(d) ? "LQER_Q_PASSTHROUGH_F16: use LQER_Q_PASSTHROUGH with width 11" : "LQER_Q_MXINT_I8: use LQER_Q_MXINT");
   if (lowrank) g.bout = make_qp(d->b_out_fmt);
   if (x_is_i8(d)) {
     if (!i8_formats_ok(d)) return LQER_E_UNSUPPORTED;
@@ -788,26 +789,61 @@ static int plan_route(const Planned& pl) {
 }
 
 int lqer_gemm_route(const lqer_linear_desc_t* d, int64_t M, int dtype) {
-  if (!d || M < 0) {
-    set_error("gemm_route: bad argument");
-    return LQER_E_INVALID;
-  }
+  if (!d || M < 0) return fail(LQER_E_INVALID, "gemm_route: bad argument");
   return plan_route(plan_for(d, M, dtype, 0, false));
 }
 
 int lqer_gemm_tile_rows(const lqer_linear_desc_t* d, int64_t M, int dtype) {
-  if (!d || M < 0) {
-    set_error("gemm_tile_rows: bad argument");
-    return LQER_E_INVALID;
-  }
+  if (!d || M < 0) return fail(LQER_E_INVALID, "gemm_tile_rows: bad argument");
   const Planned pl = plan_for(d, M, dtype, 0, false);
   const int route = plan_route(pl);
   return route < 0 ? route : pl.p.tile_rows;
 }
 
+// The operands of ONE Linear in a launch, written once: as the one-launch decode kernel's table entry, and from it as the per-call part
+// of GemmArgs (linear_gemm_impl; the one-launch branch of the forward and the group hand the entries to decode1_dispatch)
+static DecodeMember member_of(const lqer_linear_desc_t* d, const void* w_packed, const void* b_t, int b_limbs, const float* bias_q, void* y,
+                              int64_t ldy) {
+  return DecodeMember{(const uint8_t*)w_packed, (const bf16_t*)b_t, d->has_bias ? bias_q : nullptr, y, ldy, d->out_features,
+                      (int)lqer_padded_n(d->out_features), (int)xaq_row_elems(d), b_limbs};
+}
+static void fill_call(GemmArgs& g, const DecodeMember& m) {
+  g.wp = m.wp, g.bt = m.bt, g.bias = m.bias, g.y = m.y, g.ldy = m.ldy, g.b_limbs = m.b_limbs;
+}
+
 static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                             int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
-                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl, bool narrow = false);
+                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl, bool narrow = false) {
+  if (!d || !xq || !w_packed || !y || M < 0 || ldy < d->out_features) return fail(LQER_E_INVALID, "linear_gemm: bad argument");
+  const bool lowrank = d->rank > 0;
+  const bool from_partials = lowrank && !xaq && b_t && scratch && decode_partials_ok(d, M);
+  if (lowrank && ((!xaq && !from_partials) || !b_t))
+    return fail(LQER_E_INVALID, "linear_gemm: rank %d but no side-path operands (xaq == NULL: only the decode route, see lqer_decode_partials)", d->rank);
+  if (b_limbs < 0 || b_limbs > 3) return fail(LQER_E_INVALID, "linear_gemm: b_limbs %d outside [0,3]", b_limbs);
+  Planned own;
+  if (!pl) own = plan_for(d, M, dtype, b_limbs, true, narrow), pl = &own;
+  if (pl->rc) return fail(pl->rc, "%s", pl->p.msg);
+  if (lowrank && !from_partials && (xaq_ld < xaq_row_elems(d) || xaq_ld % 8 != 0 || ((uintptr_t)xaq & 15) != 0))
+    return fail(LQER_E_INVALID, "linear_gemm: xaq row stride %lld (elements) must be a multiple of 8 and at least the padded rank %lld, "
+                "xaq 16-byte aligned", (long long)xaq_ld, (long long)lqer_padded_r(d->rank));
+  GemmArgs g = pl->g;
+  fill_call(g, member_of(d, w_packed, b_t, b_limbs, bias_q, y, ldy));
+  g.xq = (const bf16_t*)xq;
+  g.xaq = (const bf16_t*)xaq;
+  g.xaq_ld = (int)xaq_ld;
+  if (x_is_i8(d)) {
+    g.w8 = (const uint8_t*)w_packed + i8_image_offset(d);
+    g.xscale = i8_row_scales(xq, M, d->in_features);
+  }
+  if (from_partials) {
+    xa_fused_plan(M, d->in_features, d->rank, &g.xa_nchunk, &g.xa_cstride);
+    if (scratch_bytes < (size_t)g.xa_nchunk * g.xa_cstride * sizeof(float))
+      return fail(LQER_E_WORKSPACE, "linear_gemm: scratch %zu B does not hold the partial tiles of x A", scratch_bytes);
+    g.xa_part = (const float*)scratch;
+    g.aout = make_qp(d->a_out_fmt);
+  }
+  return gemm_launch(pl->p, g, dtype, scratch, scratch_bytes, amax_zeroed, (hipStream_t)stream);
+}
 
 int lqer_linear_gemm_ld(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
                         int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
@@ -825,207 +861,148 @@ int lqer_linear_gemm_prepared(const lqer_linear_desc_t* d, const void* xq, int64
     pl = plan_for(d, M, dtype, b_limbs);
     zeroed = pl.rc == LQER_OK && pl.p.prep_zero_bytes > 0 && ready_bytes >= pl.p.prep_zero_bytes;
   }
-  return linear_gemm_impl(d, xq, M, w_packed, xaq, d ? lqer_padded_r(d->rank) * xa_limbs(d) : 0, b_t, b_limbs, bias_q, y, dtype, ldy,
+  return linear_gemm_impl(d, xq, M, w_packed, xaq, d ? xaq_row_elems(d) : 0, b_t, b_limbs, bias_q, y, dtype, ldy,
                           scratch, scratch_bytes, stream, zeroed, planned ? &pl : nullptr);
 }
 
-static int linear_gemm_impl(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_packed, const void* xaq,
-                            int64_t xaq_ld, const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy,
-                            void* scratch, size_t scratch_bytes, void* stream, bool amax_zeroed, const Planned* pl, bool narrow) {
-  if (!d || !xq || !w_packed || !y || M < 0 || ldy < d->out_features) {
-    set_error("linear_gemm: bad argument");
-    return LQER_E_INVALID;
-  }
-  const bool lowrank = d->rank > 0;
-  const bool from_partials = lowrank && !xaq && b_t && scratch && decode_partials_ok(d, M);
-  if (lowrank && ((!xaq && !from_partials) || !b_t)) {
-    set_error("linear_gemm: rank %d but no side-path operands (xaq == NULL: only the decode route, see lqer_decode_partials)", d->rank);
-    return LQER_E_INVALID;
-  }
-  if (b_limbs < 0 || b_limbs > 3) {
-    set_error("linear_gemm: b_limbs %d outside [0,3]", b_limbs);
-    return LQER_E_INVALID;
-  }
-  Planned own;
-  if (!pl) own = plan_for(d, M, dtype, b_limbs, true, narrow), pl = &own;
-  if (pl->rc) {
-    set_error("%s", pl->p.msg);
-    return pl->rc;
-  }
-  GemmArgs g = pl->g;
-  g.xq = (const bf16_t*)xq;
-  g.wp = (const uint8_t*)w_packed;
-  g.xaq = (const bf16_t*)xaq;
-  if (x_is_i8(d)) {
-    g.w8 = (const uint8_t*)w_packed + i8_image_offset(d);
-    g.xscale = i8_row_scales(xq, M, d->in_features);
-  }
-  const int al = lowrank ? xa_limbs(d) : 1;
-  if (lowrank && !from_partials && (xaq_ld < lqer_padded_r(d->rank) * al || xaq_ld % 8 != 0 || ((uintptr_t)xaq & 15) != 0)) {
-    set_error("linear_gemm: xaq row stride %lld (elements) must be a multiple of 8 and at least the padded rank %lld, "
-              "xaq 16-byte aligned", (long long)xaq_ld, (long long)lqer_padded_r(d->rank));
-    return LQER_E_INVALID;
-  }
-  g.xaq_ld = (int)xaq_ld;
-  g.bt = (const bf16_t*)b_t;
-  g.bias = d->has_bias ? bias_q : nullptr;
-  g.y = y;
-  g.ldy = ldy;
-  g.b_limbs = b_limbs;
-  if (from_partials) {
-    xa_fused_plan(M, d->in_features, d->rank, &g.xa_nchunk, &g.xa_cstride);
-    if (scratch_bytes < (size_t)g.xa_nchunk * g.xa_cstride * sizeof(float)) {
-      set_error("linear_gemm: scratch %zu B does not hold the partial tiles of x A", scratch_bytes);
-      return LQER_E_WORKSPACE;
-    }
-    g.xa_part = (const float*)scratch;
-    g.aout = make_qp(d->a_out_fmt);
-  }
-  return gemm_launch(pl->p, g, dtype, scratch, scratch_bytes, amax_zeroed, (hipStream_t)stream);
-}
-
-// bytes of the standard image of d's weight (one copy: what a compact image widens into)
-static size_t std_image_bytes(const lqer_linear_desc_t* d) {
-  return (size_t)(lqer_padded_n(d->out_features) / LQER_PANEL_ROWS) * (lqer_padded_k(d->in_features) / 64) * LQER_PANEL_BYTES;
-}
-// one-launch decode route (decode1.hip): the conditions lqer_linear_forward checks besides lqer_decode_partials and x's own alignment
-static bool decode1_call_ok(const lqer_linear_desc_t* d, int dtype, int64_t M, int64_t ldx, int a_limbs, int b_limbs) {
+// "The one-launch decode kernel (decode1.hip) takes this call" - asked by lqer_linear_forward, by lqer_weight_narrow_route and, per
+// member, by lqer_linear_forward_group.  The limits are the kernel's own (d1:: in common.h).  What only its dispatch can say - K a
+// multiple of d1::K_STEP, a token image that fits the LDS, the scratch - it answers with LQER_E_UNSUPPORTED, and every caller goes its
+// own way from there.  First the form for a query, which has no pointer; then the call's.
+static bool decode1_takes(const lqer_linear_desc_t* d, int64_t M, int dtype, int64_t ldx, int a_limbs, int b_limbs) {
   const int esz = dtype == LQER_F32 ? 4 : 2;
-  return M <= 8 && a_limbs == 1 && !x_is_f16(d) && (ldx * esz) % 16 == 0 && b_limbs >= 1 && b_limbs <= 3;
+  return M <= d1::MAXM && a_limbs == 1 && !x_is_f16(d) && (ldx * esz) % 16 == 0 && b_limbs >= 1 && b_limbs <= 3 && decode_partials_ok(d, M);
+}
+static bool decode1_takes(const lqer_linear_desc_t* d, int64_t M, int dtype, const void* x, int64_t ldx, int a_limbs, int b_limbs) {
+  return ((uintptr_t)x & 15) == 0 && decode1_takes(d, M, dtype, ldx, a_limbs, b_limbs);
+}
+// ... and its launch for the Linears `mem`, which are handed the same tokens: `shared` = the arguments of (d, M) that do not depend on
+// the Linear (gemm_shape_args), A_out and the B_out form are d's
+static int decode1_call(const GemmArgs& shared, const lqer_linear_desc_t* d, int dtype, const void* x, int64_t ldx, const void* a_t,
+                        const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, void* stream) {
+  GemmArgs g = shared;
+  g.aout = make_qp(d->a_out_fmt);
+  const int bout = d->b_out_fmt.kind == LQER_Q_PASSTHROUGH ? 0 : 1;  // (decode_partials_ok: pass-through or blocks of 16)
+  return decode1_dispatch(g, dtype, x, ldx, d->in_features, make_qp(d->x_fmt), (const bf16_t*)a_t, bout, mem, nmem, scratch, scratch_bytes,
+                          (hipStream_t)stream);
 }
 
-static int linear_forward_impl(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
-                               const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
-                               const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
-                               void* stream, bool narrow);
+// what lqer_linear_forward / lqer_linear_forward_narrow are handed besides the descriptor and the weight image
+struct FwdArgs {
+  const void* x; int dtype; int64_t M, ldx;
+  const void *a_t, *b_t; int a_limbs, b_limbs;
+  const float* bias_q; void* y; int64_t ldy;
+  void* workspace; size_t workspace_bytes; void* stream;
+};
 
-int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
-                        const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
-                        const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
-                        void* stream) {
-  return linear_forward_impl(d, x, dtype, M, ldx, w_packed, a_t, b_t, a_limbs, b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream,
-                             false);
-}
-
-// narrow: w_packed is the compact image (lqer_linear_forward_narrow).  Routes whose kernel reads it directly go on as below with the
-// plan's w_img; every other route widens it into the workspace behind the standard carving and goes on as the standard image's call.
-static int linear_forward_impl(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
-                               const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
-                               const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
-                               void* stream, bool narrow) {
-  if (!d) {
-    set_error("linear_forward: null descriptor");
-    return LQER_E_INVALID;
-  }
-  HT_START();
-  lqer_linear_sizes_t sz;
-  int rc = lqer_linear_sizes(d, M, &sz);
-  if (rc) return rc;
-  HT_MARK(0);
-  // the one plan of this forward (its refusals are reported where the GEMM call reports them)
-  Planned pl = plan_for(d, M, dtype, b_limbs, true, narrow);
-  if (narrow) {
-    if (plan_route(pl) < 0) return pl.rc ? pl.rc : pl.p.err;
-    if (pl.p.w_img < 0) {
-      const size_t at = align_up(sz.workspace, 256);
-      if (!workspace || workspace_bytes < at + std_image_bytes(d)) {
-        set_error("linear_forward_narrow: workspace %zu B < %zu B needed for M=%lld (the widened weight image included)", workspace_bytes,
-                  at + std_image_bytes(d), (long long)M);
-        return LQER_E_WORKSPACE;
-      }
-      if (M == 0) return LQER_OK;
-      void* wide = (unsigned char*)workspace + at;
-      rc = weight_widen_dispatch(w_packed, d->out_features, d->in_features, d->w_fmt.width, pl.g.w_narrow & 0xff, wide, (hipStream_t)stream);
-      if (rc) return rc;
-      w_packed = wide, narrow = false;
-      pl = plan_for(d, M, dtype, b_limbs);
-    }
-  }
-  lqer_linear_desc_t plain;
-  if (x_is_i8(d) && plan_route(pl) != LQER_ROUTE_I8) {
-    // token counts the int8 tile kernel does not serve run the bf16 kernels on the sign-magnitude image (same buffers): a second
-    // descriptor, a second plan
-    plain = *d;
-    plain.x_fmt.kind = LQER_Q_MXINT;
-    d = &plain;
-    pl = plan_for(d, M, dtype, b_limbs);
-  }
-  if (workspace_bytes < sz.workspace || (!workspace && sz.workspace)) {
-    set_error("linear_forward: workspace %zu B < %zu B needed for M=%lld", workspace_bytes, sz.workspace, (long long)M);
-    return LQER_E_WORKSPACE;
-  }
-  if (M == 0) return LQER_OK;
-  const size_t Mp = lqer_padded_m(M);
-  unsigned char* ws = (unsigned char*)workspace;
-  void* xq = ws;
-  const size_t rp = lqer_padded_r(d->rank);
-  const size_t al = xa_limbs(d);
+// The forward of descriptor d on the weight image w_packed (narrow: the compact one, read by the plan's kernel directly) under its
+// plan pl, on the carving cv
+static int forward_body(const lqer_linear_desc_t* d, const void* w_packed, bool narrow, const Planned& pl, const Carving& cv, const FwdArgs& a) {
+  if (a.workspace_bytes < cv.total || (!a.workspace && cv.total))
+    return fail(LQER_E_WORKSPACE, "linear_forward: workspace %zu B < %zu B needed for M=%lld", a.workspace_bytes, cv.total, (long long)a.M);
+  if (a.M == 0) return LQER_OK;
+  unsigned char* const ws = (unsigned char*)a.workspace;
   HT_MARK(1);
-  if (dtype == LQER_F16 && f16_image_is_input(d, x, M, ldx, plan_route(pl))) xq = const_cast<void*>(x);  // no copy (never written)
+  const bool x_is_image = a.dtype == LQER_F16 && f16_image_is_input(d, a.x, a.M, a.ldx, plan_route(pl));  // no copy (never written)
+  void* const xq = x_is_image ? const_cast<void*>(a.x) : ws;
   HT_MARK(2);
-  const size_t act = act_image_bytes(d, M);
-  void* xaq = ws + act;
-  void* xa_scratch = ws + act + align_up(Mp * rp * 2 * al, 256);
-  if (decode_partials_ok(d, M) && a_t && b_t) {
+  void *const xaq = ws + cv.xaq, *const scratch = ws + cv.scratch;
+  const bool sides = a.a_t && a.b_t;
+  const bool one_launch = sides && decode1_takes(d, a.M, a.dtype, a.x, a.ldx, a.a_limbs, a.b_limbs);
+  if (one_launch || (sides && decode_partials_ok(d, a.M))) {
     HT_MARK(3);
-    const size_t nscr = lqer_lowrank_xa_scratch_bytes(d, M);
+    const size_t nscr = cv.side_bytes;
     HT_MARK(4);
     // up to 8 tokens: ONE launch (decode1.hip) - producer workgroups publish the partial tiles of x A, the weight-streaming
     // workgroups quantize x themselves and pick the tiles up at their very end
-    const int esz = dtype == LQER_F32 ? 4 : 2;
     // (capturable: the kernel mixes its dispatch id into the granule tag, so a replayed graph node never accepts the
     // previous replay's tiles although its arguments - the host's per-call counter among them - are frozen)
-    if (M <= 8 && a_limbs == 1 && !x_is_f16(d) && ((uintptr_t)x & 15) == 0 &&
-        (ldx * esz) % 16 == 0 && b_limbs >= 1 && b_limbs <= 3) {
-      if (pl.rc) {
-        set_error("%s", pl.p.msg);
-        return pl.rc;
-      }
-      GemmArgs g = pl.g;
+    if (one_launch) {
+      if (pl.rc) return fail(pl.rc, "%s", pl.p.msg);
       HT_MARK(5);
-      g.wp = (const uint8_t*)w_packed;
-      g.bt = (const bf16_t*)b_t;
-      g.bias = d->has_bias ? bias_q : nullptr;
-      g.y = y;
-      g.ldy = ldy;
-      g.aout = make_qp(d->a_out_fmt);
-      const int bout = d->b_out_fmt.kind == LQER_Q_PASSTHROUGH ? 0 : 1;  // (decode_partials_ok: pass-through or blocks of 16)
-      const DecodeMember one{g.wp, g.bt, g.bias, g.y, g.ldy, g.N, g.Np, g.rp, g.b_limbs};
-      rc = decode1_dispatch(g, dtype, x, ldx, d->in_features, make_qp(d->x_fmt), (const bf16_t*)a_t, bout, &one, 1, xa_scratch, nscr,
-                            (hipStream_t)stream);
+      const DecodeMember one = member_of(d, w_packed, a.b_t, a.b_limbs, a.bias_q, a.y, a.ldy);
+      const int rc = decode1_call(pl.g, d, a.dtype, a.x, a.ldx, a.a_t, &one, 1, scratch, nscr, a.stream);
       HT_MARK(6);
       HT_DONE();
       if (rc != LQER_E_UNSUPPORTED) return rc;
     }
     // two launches: the GEMM sums the partial tiles of x A itself
-    rc = lqer_quantize_act_xa(d, x, dtype, M, ldx, a_t, a_limbs, xq, nullptr, xa_scratch, nscr, stream);
+    const int rc = lqer_quantize_act_xa(d, a.x, a.dtype, a.M, a.ldx, a.a_t, a.a_limbs, xq, nullptr, scratch, nscr, a.stream);
     if (rc) return rc;
-    return linear_gemm_impl(d, xq, M, w_packed, nullptr, lqer_padded_r(d->rank) * xa_limbs(d), b_t, b_limbs, bias_q, y, dtype, ldy, xa_scratch,
-                            nscr, stream, false, &pl, narrow);
+    return linear_gemm_impl(d, xq, a.M, w_packed, nullptr, xaq_row_elems(d), a.b_t, a.b_limbs, a.bias_q, a.y, a.dtype, a.ldy, scratch, nscr,
+                            a.stream, false, &pl, narrow);
   }
   // (a pre-pass on atomicMax cells behind the one-launch int8 activation kernel: that kernel zeroes the cells - the two calls share the
   // scratch, whose size is the larger of their needs - instead of a memset launch between them)
-  AmaxZeroReq zr{b_t ? xa_scratch : nullptr, 0, false};
-  if (can_prep_amax(d, M, a_limbs, zr.p) && pl.rc == LQER_OK) zr.bytes = pl.p.prep_zero_bytes;
-  const size_t side_bytes = lqer_lowrank_xa_scratch_bytes(d, M), gemm_bytes = lqer_linear_gemm_scratch_bytes(d, M);
-  rc = quantize_act_xa_impl(d, x, dtype, M, ldx, a_t, a_limbs, xq, xaq, xa_scratch, side_bytes, stream, &zr);
+  AmaxZeroReq zr{a.b_t ? scratch : nullptr, 0, false};
+  if (can_prep_amax(d, a.M, a.a_limbs, zr.p) && pl.rc == LQER_OK) zr.bytes = pl.p.prep_zero_bytes;
+  const int rc = quantize_act_xa_impl(d, a.x, a.dtype, a.M, a.ldx, a.a_t, a.a_limbs, xq, xaq, scratch, cv.side_bytes, a.stream, &zr);
   if (rc) return rc;
-  return linear_gemm_impl(d, xq, M, w_packed, d->rank > 0 ? xaq : nullptr, lqer_padded_r(d->rank) * xa_limbs(d), b_t, b_limbs, bias_q, y, dtype,
-                          ldy, xa_scratch, gemm_bytes, stream, zr.done, &pl, narrow);
+  return linear_gemm_impl(d, xq, a.M, w_packed, d->rank > 0 ? xaq : nullptr, xaq_row_elems(d), a.b_t, a.b_limbs, a.bias_q, a.y, a.dtype, a.ldy,
+                          scratch, cv.gemm_bytes, a.stream, zr.done, &pl, narrow);
+}
+
+// Step in front of the body: token counts the int8 tile kernel does not serve run the bf16 kernels on the sign-magnitude image (same
+// buffers, same carving but for the single-copy image, which only the split calls place) - a second descriptor, a second plan
+static int forward_planned(const lqer_linear_desc_t* d, const void* w_packed, bool narrow, const Planned& pl, const Carving& cv, const FwdArgs& a) {
+  if (!x_is_i8(d) || plan_route(pl) == LQER_ROUTE_I8) return forward_body(d, w_packed, narrow, pl, cv, a);
+  lqer_linear_desc_t plain = *d;
+  plain.x_fmt.kind = LQER_Q_MXINT;
+  return forward_body(&plain, w_packed, narrow, plan_for(&plain, a.M, a.dtype, a.b_limbs), cv, a);
+}
+
+// the standard image of the compact image w_narrow, whose plan is pl, written to `wide` (std_image_bytes)
+static int widen_for(const lqer_linear_desc_t* d, const Planned& pl, const void* w_narrow, void* wide, void* stream) {
+  return weight_widen_dispatch(w_narrow, d->out_features, d->in_features, d->w_fmt.width, pl.g.w_narrow & 0xff, wide, (hipStream_t)stream);
+}
+
+// Step in front of the body: a compact image on a route whose kernel reads standard panels is widened into the workspace behind the
+// standard carving, and the call goes on as the standard image's
+static int forward_widened(const lqer_linear_desc_t* d, const void* w_narrow, const Planned& pl, const Carving& cv, const FwdArgs& a) {
+  if (!a.workspace || a.workspace_bytes < cv.widened + std_image_bytes(d))
+    return fail(LQER_E_WORKSPACE, "linear_forward_narrow: workspace %zu B < %zu B needed for M=%lld (the widened weight image included)", a.workspace_bytes,
+                cv.widened + std_image_bytes(d), (long long)a.M);
+  if (a.M == 0) return LQER_OK;
+  void* const wide = (unsigned char*)a.workspace + cv.widened;
+  const int rc = widen_for(d, pl, w_narrow, wide, a.stream);
+  if (rc) return rc;
+  return forward_planned(d, wide, false, plan_for(d, a.M, a.dtype, a.b_limbs), cv, a);
+}
+
+// narrow: w_packed is the compact image (lqer_linear_forward_narrow).  Routes whose kernel reads it directly go on with the plan's
+// w_img; every other route widens it first.
+static int linear_forward_impl(const lqer_linear_desc_t* d, const void* w_packed, bool narrow, const FwdArgs& a) {
+  if (!d) return fail(LQER_E_INVALID, "linear_forward: null descriptor");
+  HT_START();
+  lqer_linear_sizes_t sz;
+  Carving cv;
+  const int rc = linear_sizes_carved(d, a.M, &sz, &cv);
+  if (rc) return rc;
+  HT_MARK(0);
+  // the one plan of this forward (its refusals are reported where the GEMM call reports them)
+  const Planned pl = plan_for(d, a.M, a.dtype, a.b_limbs, true, narrow);
+  if (narrow) {
+    if (plan_route(pl) < 0) return pl.rc ? pl.rc : pl.p.err;
+    if (pl.p.w_img < 0) return forward_widened(d, w_packed, pl, cv, a);
+  }
+  return forward_planned(d, w_packed, narrow, pl, cv, a);
+}
+
+int lqer_linear_forward(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx,
+                        const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                        const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  return linear_forward_impl(d, w_packed, false, FwdArgs{x, dtype, M, ldx, a_t, b_t, a_limbs, b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream});
 }
 
 // ---- the compact image of 2- / 3-bit block_fp weights (include/lqer_hip.h "compact weight image") -----------------------------------
 size_t lqer_weight_narrow_bytes(int64_t N, int64_t K, const lqer_qfmt_t* w_fmt) { return narrow_bytes(N, K, w_fmt); }
 
 static int narrow_conv_check(const char* who, const void* a, const void* b, int64_t N, int64_t K, const lqer_qfmt_t* f) {
-  if (!a || !b || !f || N <= 0 || K <= 0 || ((uintptr_t)a & 15) || ((uintptr_t)b & 15)) {
-    set_error("%s: bad argument (null pointer, non-positive size, or an image that is not 16-byte aligned)", who);
-    return LQER_E_INVALID;
-  }
-  if (!narrow_exps(f, K)) {
-    set_error("%s: the compact image holds block_fp weights of width 2 or 3 (kind %d width %d)", who, f->kind, f->width);
-    return LQER_E_UNSUPPORTED;
-  }
+  if (!a || !b || !f || N <= 0 || K <= 0 || ((uintptr_t)a & 15) || ((uintptr_t)b & 15))
+    return fail(LQER_E_INVALID, "%s: bad argument (null pointer, non-positive size, or an image that is not 16-byte aligned)", who);
+  if (!narrow_exps(f, K))
+    return fail(LQER_E_UNSUPPORTED, "%s: the compact image holds block_fp weights of width 2 or 3 (kind %d width %d)", who, f->kind, f->width);
   return LQER_OK;
 }
 
@@ -1042,11 +1019,9 @@ int lqer_weight_widen(const void* w_narrow, int64_t N, int64_t K, const lqer_qfm
 int lqer_weight_narrow_host(const void* w_packed, int64_t N, int64_t K, const lqer_qfmt_t* w_fmt, void* w_narrow) {
   const int rc = narrow_conv_check("weight_narrow_host", w_packed, w_narrow, N, K, w_fmt);
   if (rc) return rc;
-  if (!weight_narrow_host((const uint8_t*)w_packed, N, K, w_fmt->width, narrow_exps(w_fmt, K), (uint8_t*)w_narrow)) {
-    set_error("weight_narrow_host: not the standard image of a width-%d weight in blocks of %d (a magnitude bit above bit %d, or "
-              "exponent bytes of one block that differ): widening would not give it back", w_fmt->width, w_fmt->block, w_fmt->width - 2);
-    return LQER_E_INVALID;
-  }
+  if (!weight_narrow_host((const uint8_t*)w_packed, N, K, w_fmt->width, narrow_exps(w_fmt, K), (uint8_t*)w_narrow))
+    return fail(LQER_E_INVALID, "weight_narrow_host: not the standard image of a width-%d weight in blocks of %d (a magnitude bit above bit %d, or "
+                "exponent bytes of one block that differ): widening would not give it back", w_fmt->width, w_fmt->block, w_fmt->width - 2);
   return LQER_OK;
 }
 
@@ -1058,15 +1033,13 @@ int lqer_weight_widen_host(const void* w_narrow, int64_t N, int64_t K, const lqe
 }
 
 int lqer_weight_narrow_route(const lqer_linear_desc_t* d, int64_t M, int dtype, int64_t ldx, int a_limbs, int b_limbs) {
-  if (!d || M < 0) {
-    set_error("weight_narrow_route: bad argument");
-    return LQER_E_INVALID;
-  }
+  if (!d || M < 0) return fail(LQER_E_INVALID, "weight_narrow_route: bad argument");
   const Planned pl = plan_for(d, M, dtype, b_limbs, false, true);
   const int route = plan_route(pl);
   if (route < 0) return route;
   if (pl.p.w_img < 0) return LQER_NARROW_WIDEN;
-  const bool one = decode_partials_ok(d, M) && decode1_call_ok(d, dtype, M, ldx, a_limbs, b_limbs) && d->in_features % 16 == 0;
+  // (a query answers for the kernel's dispatch as well, which the forward simply asks: K in whole steps)
+  const bool one = decode1_takes(d, M, dtype, ldx, a_limbs, b_limbs) && d->in_features % d1::K_STEP == 0;
   return one ? LQER_NARROW_DIRECT_ONE_LAUNCH : LQER_NARROW_DIRECT;
 }
 
@@ -1080,39 +1053,33 @@ static bool narrow_may_widen(const lqer_linear_desc_t* d, int64_t m_max) {
 
 size_t lqer_linear_forward_narrow_workspace_bytes(const lqer_linear_desc_t* d, int64_t m_max) {
   lqer_linear_sizes_t sz;
-  if (!d || lqer_linear_sizes(d, m_max, &sz)) return 0;
+  Carving cv;
+  if (!d || linear_sizes_carved(d, m_max, &sz, &cv)) return 0;
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   if (narrow_args(d, g)) return 0;
-  return narrow_may_widen(d, m_max) ? align_up(sz.workspace, 256) + std_image_bytes(d) : sz.workspace;
+  return narrow_may_widen(d, m_max) ? cv.widened + std_image_bytes(d) : cv.total;
 }
 
 int lqer_linear_forward_narrow(const lqer_linear_desc_t* d, const void* x, int dtype, int64_t M, int64_t ldx, const void* w_narrow,
                                const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y, int64_t ldy,
                                void* workspace, size_t workspace_bytes, void* stream) {
-  return linear_forward_impl(d, x, dtype, M, ldx, w_narrow, a_t, b_t, a_limbs, b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream,
-                             true);
+  return linear_forward_impl(d, w_narrow, true, FwdArgs{x, dtype, M, ldx, a_t, b_t, a_limbs, b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream});
 }
 
 int lqer_linear_gemm_narrow(const lqer_linear_desc_t* d, const void* xq, int64_t M, const void* w_narrow, const void* xaq, int64_t xaq_ld,
                             const void* b_t, int b_limbs, const float* bias_q, void* y, int dtype, int64_t ldy, void* scratch,
                             size_t scratch_bytes, void* widen_scratch, size_t widen_bytes, void* stream) {
-  if (!d || !w_narrow || M < 0) {
-    set_error("linear_gemm_narrow: bad argument");
-    return LQER_E_INVALID;
-  }
+  if (!d || !w_narrow || M < 0) return fail(LQER_E_INVALID, "linear_gemm_narrow: bad argument");
   const Planned pl = plan_for(d, M, dtype, b_limbs, true, true);
   if (plan_route(pl) < 0) return pl.rc ? pl.rc : pl.p.err;
   if (pl.p.w_img >= 0)
     return linear_gemm_impl(d, xq, M, w_narrow, xaq, xaq_ld, b_t, b_limbs, bias_q, y, dtype, ldy, scratch, scratch_bytes, stream, false, &pl, true);
-  if (!widen_scratch || widen_bytes < std_image_bytes(d) || ((uintptr_t)widen_scratch & 15)) {
-    set_error("linear_gemm_narrow: M=%lld takes a kernel that reads standard panels: widen_scratch %zu B < %zu B (16-byte aligned)",
-              (long long)M, widen_bytes, std_image_bytes(d));
-    return LQER_E_WORKSPACE;
-  }
+  if (!widen_scratch || widen_bytes < std_image_bytes(d) || ((uintptr_t)widen_scratch & 15))
+    return fail(LQER_E_WORKSPACE, "linear_gemm_narrow: M=%lld takes a kernel that reads standard panels: widen_scratch %zu B < %zu B (16-byte aligned)",
+                (long long)M, widen_bytes, std_image_bytes(d));
   if (M == 0) return LQER_OK;
-  const int rc = weight_widen_dispatch(w_narrow, d->out_features, d->in_features, d->w_fmt.width, pl.g.w_narrow & 0xff, widen_scratch,
-                                       (hipStream_t)stream);
+  const int rc = widen_for(d, pl, w_narrow, widen_scratch, stream);
   if (rc) return rc;
   return linear_gemm_impl(d, xq, M, widen_scratch, xaq, xaq_ld, b_t, b_limbs, bias_q, y, dtype, ldy, scratch, scratch_bytes, stream, false,
                           nullptr);
@@ -1124,64 +1091,47 @@ size_t lqer_group_workspace_bytes(int64_t K, int64_t rank_padded_sum) {
 
 int lqer_linear_forward_group(const lqer_group_member_t* members, int n_members, const void* x, int dtype, int64_t M, int64_t ldx,
                               const void* a_t_cat, int a_limbs, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!members || n_members < 1 || !x || !a_t_cat || !workspace || M < 0) {
-    set_error("linear_forward_group: bad argument");
-    return LQER_E_INVALID;
-  }
+  if (!members || n_members < 1 || !x || !a_t_cat || !workspace || M < 0) return fail(LQER_E_INVALID, "linear_forward_group: bad argument");
   if (M == 0) return LQER_OK;
   const lqer_linear_desc_t* d0 = members[0].desc;
-  const int esz = dtype == LQER_F32 ? 4 : 2;
   auto same = [](const lqer_qfmt_t& a, const lqer_qfmt_t& b) {
     return a.kind == b.kind && a.width == b.width && a.block == b.block && a.exp_width == b.exp_width && a.exp_bias == b.exp_bias;
   };
-  // the one-launch route's conditions (lqer_linear_forward), for every member; anything else: the caller's member-by-member loop
-  bool ok = n_members >= 2 && n_members <= 4 && M <= 8 && a_limbs == 1 && d0 && !x_is_f16(d0) && ((uintptr_t)x & 15) == 0 &&
-            (ldx * esz) % 16 == 0 && ((uintptr_t)workspace & 15) == 0;
-  DecodeMember mem[4];
+  // the one-launch route's conditions (lqer_linear_forward's: decode1_takes), for every member; anything else: the caller's
+  // member-by-member loop
+  bool ok = n_members >= 2 && n_members <= d1::MAXMEM && ((uintptr_t)workspace & 15) == 0;
+  DecodeMember mem[d1::MAXMEM];
   int64_t rp_all = 0;
   // malformed members are errors, not "outside the route" (what lqer_linear_forward gets from lqer_linear_sizes / gemm_shape_args)
-  for (int i = 0; i < n_members && i < 4; ++i) {
+  for (int i = 0; i < n_members && i < d1::MAXMEM; ++i) {
     const lqer_linear_desc_t* d = members[i].desc;
-    if (!d || d->in_features <= 0 || d->out_features <= 0 || d->rank < 0) {
-      set_error("linear_forward_group: member %d: bad descriptor", i);
-      return LQER_E_INVALID;
-    }
-    if (!fmt_ok(&d->w_fmt, "w_quantizer", 4) || !fmt_ok(&d->x_fmt, "x_quantizer", 9) || !fmt_ok(&d->a_out_fmt, "A_out_quantizer", 9) ||
-        !fmt_ok(&d->b_out_fmt, "B_out_quantizer", 24))
+    if (!d || d->in_features <= 0 || d->out_features <= 0 || d->rank < 0)
+      return fail(LQER_E_INVALID, "linear_forward_group: member %d: bad descriptor", i);
+    if (!fmt_ok(&d->w_fmt, ROLE_W_GROUP) || !fmt_ok(&d->x_fmt, ROLE_X) || !fmt_ok(&d->a_out_fmt, ROLE_A_OUT) ||
+        !fmt_ok(&d->b_out_fmt, ROLE_B_OUT))
       return LQER_E_UNSUPPORTED;
-    if (d->has_bias && !members[i].bias_q) {
-      set_error("linear_forward_group: member %d: has_bias = 1 but bias_q == NULL", i);
-      return LQER_E_INVALID;
-    }
+    if (d->has_bias && !members[i].bias_q) return fail(LQER_E_INVALID, "linear_forward_group: member %d: has_bias = 1 but bias_q == NULL", i);
   }
   for (int i = 0; ok && i < n_members; ++i) {
     const lqer_group_member_t& m = members[i];
     const lqer_linear_desc_t* d = m.desc;
-    ok = d && m.w_packed && m.b_t && m.y && decode_partials_ok(d, M) && d->in_features == d0->in_features && same(d->x_fmt, d0->x_fmt) &&
-         same(d->a_out_fmt, d0->a_out_fmt) && same(d->b_out_fmt, d0->b_out_fmt) && m.b_limbs >= 1 && m.b_limbs <= 3 &&
-         m.ldy >= d->out_features && ldx >= d->in_features;
+    ok = m.w_packed && m.b_t && m.y && decode1_takes(d, M, dtype, x, ldx, a_limbs, m.b_limbs) && d->in_features == d0->in_features &&
+         same(d->x_fmt, d0->x_fmt) && same(d->a_out_fmt, d0->a_out_fmt) && same(d->b_out_fmt, d0->b_out_fmt) && m.ldy >= d->out_features &&
+         ldx >= d->in_features;
     if (!ok) break;
-    mem[i] = DecodeMember{(const uint8_t*)m.w_packed, (const bf16_t*)m.b_t, d->has_bias ? m.bias_q : nullptr, m.y, m.ldy, d->out_features,
-                          (int)lqer_padded_n(d->out_features), (int)lqer_padded_r(d->rank), m.b_limbs};
-    rp_all += lqer_padded_r(d->rank);
+    mem[i] = member_of(d, m.w_packed, m.b_t, m.b_limbs, m.bias_q, m.y, m.ldy);
+    rp_all += mem[i].rp;
   }
-  if (!ok || rp_all > 128) {
-    set_error("linear_forward_group: outside the one-launch decode route (2..4 members with equal K and x / A_out / B_out formats, "
-              "lqer_decode_partials, M <= 8, one limb of A, aligned x): run the members one by one");
-    return LQER_E_UNSUPPORTED;
-  }
-  if (workspace_bytes < lqer_group_workspace_bytes(d0->in_features, rp_all)) {
-    set_error("linear_forward_group: workspace %zu B < %zu B", workspace_bytes, lqer_group_workspace_bytes(d0->in_features, rp_all));
-    return LQER_E_WORKSPACE;
-  }
+  if (!ok || rp_all > d1::MAX_RP_ALL)
+    return fail(LQER_E_UNSUPPORTED, "linear_forward_group: outside the one-launch decode route (2..4 members with equal K and x / A_out / B_out formats, "
+                "lqer_decode_partials, M <= 8, one limb of A, aligned x): run the members one by one");
+  if (workspace_bytes < lqer_group_workspace_bytes(d0->in_features, rp_all))
+    return fail(LQER_E_WORKSPACE, "linear_forward_group: workspace %zu B < %zu B", workspace_bytes, lqer_group_workspace_bytes(d0->in_features, rp_all));
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   int rc = gemm_shape_args(d0, M, dtype, g);  // the shared part: M, Kp, formats
   if (rc) return rc;
-  g.aout = make_qp(d0->a_out_fmt);
-  const int bout = d0->b_out_fmt.kind == LQER_Q_PASSTHROUGH ? 0 : 1;  // (decode_partials_ok: pass-through or blocks of 16)
-  rc = decode1_dispatch(g, dtype, x, ldx, d0->in_features, make_qp(d0->x_fmt), (const bf16_t*)a_t_cat, bout, mem, n_members, workspace,
-                        workspace_bytes, (hipStream_t)stream);
+  rc = decode1_call(g, d0, dtype, x, ldx, a_t_cat, mem, n_members, workspace, workspace_bytes, stream);
   if (rc == LQER_E_UNSUPPORTED) set_error("linear_forward_group: shape outside the one-launch decode kernel (K too long for its LDS image)");
   return rc;
 }
@@ -1246,7 +1196,7 @@ int lqer_matmul_q(const void* x, const void* y, void* out, int dtype, int64_t ba
     set_error("matmul_q: null pointer");
     return LQER_E_INVALID;
   }
-  if (!fmt_ok(x_fmt, "matmul x_quantizer", 8) || !fmt_ok(y_fmt, "matmul w_quantizer", 8)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(x_fmt, ROLE_MATMUL_X) || !fmt_ok(y_fmt, ROLE_MATMUL_W)) return LQER_E_UNSUPPORTED;
   auto blk_ok = [](const lqer_qfmt_t* f, int64_t cols) { return f->block <= 0 || f->block >= cols || f->block % 16 == 0; };
   // (minifloat operands: elementwise - block -1, the standalone quantizer's bf16 image)
   auto kind_ok = [](const lqer_qfmt_t* f) { return f->kind == LQER_Q_MXINT || f->kind == LQER_Q_MINIFLOAT; };
@@ -1387,8 +1337,8 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
               kn.takes);
     return LQER_E_UNSUPPORTED;
   }
-  if (!fmt_ok(c.q_fmt, "attention Q quantizer", 8) || !fmt_ok(c.k_fmt, "attention K quantizer", 8) ||
-      !fmt_ok(c.p_fmt, "attention P quantizer", 8) || !fmt_ok(c.v_fmt, "attention V quantizer", 8))
+  if (!fmt_ok(c.q_fmt, ROLE_ATTN_Q) || !fmt_ok(c.k_fmt, ROLE_ATTN_K) ||
+      !fmt_ok(c.p_fmt, ROLE_ATTN_P) || !fmt_ok(c.v_fmt, ROLE_ATTN_V))
     return LQER_E_UNSUPPORTED;
   for (const lqer_qfmt_t* f : {c.q_fmt, c.k_fmt, c.p_fmt, c.v_fmt})
     if (f->kind != LQER_Q_MXINT || f->block != 16) {
@@ -1451,7 +1401,7 @@ static int kv_codes_check(const char* who, int64_t D, const lqer_qfmt_t* k_fmt, 
     set_error("%s: head dim %lld - the packed KV cache takes multiples of 16 up to 128", who, (long long)D);
     return LQER_E_UNSUPPORTED;
   }
-  if (!fmt_ok(k_fmt, "attention K quantizer", 8) || !fmt_ok(v_fmt, "attention V quantizer", 8)) return LQER_E_UNSUPPORTED;
+  if (!fmt_ok(k_fmt, ROLE_ATTN_K) || !fmt_ok(v_fmt, ROLE_ATTN_V)) return LQER_E_UNSUPPORTED;
   for (const lqer_qfmt_t* f : {k_fmt, v_fmt})
     if (f->kind != LQER_Q_MXINT || f->block != 16) {
       set_error("%s: the packed KV cache holds block_fp codes of width <= 8 with blocks of 16 (got kind %d, block %d)", who, f->kind, f->block);
@@ -1588,7 +1538,7 @@ size_t lqer_kv_pool_bytes_fmt(int dtype, int64_t pages, int64_t slots, int64_t k
   own.resolve(p, k_fmt, v_fmt);
   if (pool_nibble_check("kv_pool_bytes_fmt", p, k_fmt, v_fmt) != LQER_OK) return 0;
   for (const lqer_qfmt_t* f : {k_fmt, v_fmt})
-    if (f->kind != LQER_Q_MXINT || f->block != 16 || !fmt_ok(f, "attention K / V quantizer", 8)) return 0;
+    if (f->kind != LQER_Q_MXINT || f->block != 16 || !fmt_ok(f, ROLE_ATTN_KV)) return 0;
   return kv_pool_bytes(dtype, pages, slots, kv_heads, D, p.k4, p.v4);
 }
 

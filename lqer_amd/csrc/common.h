@@ -1,6 +1,7 @@
 // Shared device helpers for the LQER HIP kernels (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <mutex>
@@ -31,6 +32,7 @@ struct QP {
   float tiny;  // |x| <= tiny is not quantized (block_fp.py:79-80: 1e-8; integer: -1 = never)
   int width;   // bits per element incl. sign
 };
+static_assert(sizeof(QP) == 40, "tests/launch_probe.cpp mirrors QP");
 
 __host__ inline QP make_qp(const lqer_qfmt_t& f) {
   QP q;
@@ -788,6 +790,7 @@ struct QuantOut {
   int64_t cols_p8 = 0;
   float* xscale = nullptr;
 };
+static_assert(offsetof(QuantOut, xq) == 24 && offsetof(QuantOut, xq8) == 48 && offsetof(QuantOut, xscale) == 64, "tests/launch_probe.cpp mirrors QuantOut");
 
 struct GemmArgs {
   const bf16_t* xq;    // [Mp][Kp]
@@ -833,6 +836,10 @@ struct GemmArgs {
   int w_mf;
   uint32_t w_lut[2];
 };
+// (tests/launch_probe.cpp mirrors the struct up to xscale and prints where its pointers lie)
+static_assert(offsetof(GemmArgs, xaq_ld) == 24 && offsetof(GemmArgs, bt) == 32 && offsetof(GemmArgs, ldy) == 56 && offsetof(GemmArgs, M) == 64 &&
+                  offsetof(GemmArgs, xa_part) == 96 && offsetof(GemmArgs, bout_amax) == 216 && offsetof(GemmArgs, w8) == 240 &&
+                  offsetof(GemmArgs, xscale) == 248, "tests/launch_probe.cpp mirrors GemmArgs");
 
 int quantize_dispatch(const void* x, int dtype, int64_t rows, int64_t cols, int64_t ld, const QP& q,
                       const QuantOut& o, hipStream_t st);
@@ -881,6 +888,13 @@ int i8_prepare_dispatch(const void* w_packed, int64_t N, int64_t K, int mbits, v
 int i8_unpack_dispatch(const void* w_i8, int64_t N, int64_t K, float* out, hipStream_t st, bool codes8 = false);
 
 // decode1.hip: the whole forward of M <= 8 tokens in one launch (LQER_E_UNSUPPORTED without launching when outside its shapes)
+namespace d1 {  // the kernel's limits, which the host's "the kernel takes this call" rule reads as well (api.hip, decode1_takes)
+constexpr int MAXM = 8;          // token rows
+constexpr int MAXMEM = 4;        // Linears of one launch (q/k/v, gate/up)
+constexpr int MAXNT = 4;         // rank tiles of 16 per Linear (padded rank <= 64)
+constexpr int MAX_RP_ALL = 128;  // padded ranks summed over the Linears of a launch
+constexpr int K_STEP = 16;       // in_features in whole quantizer blocks
+}  // namespace d1
 size_t decode1_scratch_bytes(int64_t Kp, int rp);
 struct DecodeMember {  // one Linear of a one-launch decode forward (a group shares the tokens and the launch)
   const uint8_t* wp;

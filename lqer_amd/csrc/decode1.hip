@@ -40,9 +40,8 @@ namespace lqer {
 namespace d1 {
 
 constexpr int NW = 8;          // waves per workgroup
-constexpr int MAXM = 8;        // token rows
+// (MAXM = 8 token rows, MAXNT = 4 rank tiles of 16, MAXMEM = 4 Linears of one launch, MAX_RP_ALL, K_STEP: common.h - the host's rule reads them)
 constexpr int SLAB_K = 256;    // k per producer
-constexpr int MAXNT = 4;       // rank tiles of 16 (padded rank <= 64)
 #ifndef LQER_QD1_SPIN
 #define LQER_QD1_SPIN 4096
 #endif
@@ -83,7 +82,6 @@ __device__ unsigned long long* g_d1_stamps = nullptr;  // diagnostic build: s_me
 // the intrinsic, and the kernel descriptor then requests the two system SGPRs)
 extern "C" __device__ unsigned long long lqer_dispatch_id() __asm("llvm.amdgcn.dispatch.id");
 
-constexpr int MAXMEM = 4;  // Linears of one launch (q/k/v, gate/up)
 struct Member {        // one Linear of the launch: its own packed operands and output
   const uint8_t* wp;   // packed panels
   const bf16_t* bt;    // [limbs][Np][rp]
@@ -117,6 +115,9 @@ struct Args {
   int spin;            // poll sweeps before a consumer computes the tiles itself
   int cpw;             // column blocks per consumer workgroup: the grid never exceeds what is resident at once (one round)
 };
+// (tests/launch_probe.cpp mirrors Member and Args and prints where their pointers lie)
+static_assert(sizeof(Member) == 72 && offsetof(Args<1>, M) == 72 && offsetof(Args<1>, x) == 168 && offsetof(Args<1>, w_exps) == 228 &&
+                  offsetof(Args<1>, gran) == 240 && offsetof(Args<1>, cpw) == 260 && offsetof(Args<MAXMEM>, x) == 384, "tests/launch_probe.cpp mirrors d1::Args");
 
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
@@ -634,7 +635,7 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
 #ifdef LQER_HOST_TIMING
   timespec ht0; clock_gettime(CLOCK_MONOTONIC, &ht0);
 #endif
-  if (g.M < 1 || g.M > d1::MAXM || nmem < 1 || nmem > d1::MAXMEM || bout > 1 || K % 16 != 0) return LQER_E_UNSUPPORTED;
+  if (g.M < 1 || g.M > d1::MAXM || nmem < 1 || nmem > d1::MAXMEM || bout > 1 || K % d1::K_STEP != 0) return LQER_E_UNSUPPORTED;
   const int w_img = g.w_narrow >> 8;  // the compact image of a 2- / 3-bit weight: a single Linear's launch only
   if (w_img && (nmem != 1 || (w_img != 2 && w_img != 3))) return LQER_E_UNSUPPORTED;
   d1::Args<d1::MAXMEM> a;
@@ -646,7 +647,7 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
     rp_all += mem[i].rp;
     blocks += mem[i].Np / 16;
   }
-  if (rp_all > 128) return LQER_E_UNSUPPORTED;
+  if (rp_all > d1::MAX_RP_ALL) return LQER_E_UNSUPPORTED;
   if (scratch_bytes < decode1_scratch_bytes(g.Kp, rp_all) || ((uintptr_t)scratch & 15)) return LQER_E_UNSUPPORTED;
   a.np = (int)((g.Kp + d1::SLAB_K - 1) / d1::SLAB_K);
   // ONE round: at most what the chip holds at once (two workgroups per CU by registers, one when a workgroup's LDS - the x image
