@@ -756,8 +756,8 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * once per step, in order.
  * lqer_attention_q_decode_paged: lqer_attention_q_decode_kv with (cache, cache_bytes, capacity, T) replaced by (pool, pool_bytes, pages,
  * slots, block_table, table_stride, seq_slots, lens, max_len) and without a mask tensor: the mask forms are none and causal = 1, with
- * sequence b's own offset T_b - S (S <= T_b is the caller's to keep); per-sequence lengths replace the padding mask.  S <= 8, uniform
- * over the call.  A workgroup takes T = lens[b] and from it the chunk length C, the chunk count nch and the causal offset of ITS
+ * sequence b's own offset T_b - S (S <= T_b is the caller's to keep); per-sequence lengths replace the padding mask.  (A draft tree's
+ * mask is one word per query row: the two _tree entries below.)  S <= 8, uniform over the call.  A workgroup takes T = lens[b] and from it the chunk length C, the chunk count nch and the causal offset of ITS
  * sequence; the grid's x is the largest nch that any T <= max_len has (nch is not monotonic in T), and workgroups beyond their
  * sequence's nch leave at once.  For every b, out[b] and row_stats[b] are the SAME BITS as lqer_attention_q_decode with batch = 1 on
  * the raw K and V of that sequence - whatever else is in the batch, whatever pages it lives on, whatever max_len is.  A sequence
@@ -880,6 +880,31 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * of the step and not batch x max_s.  Three launches on `stream`, no allocation, no host synchronisation, no atomics: capturable in
  * a hipGraph.  Refused as lqer_attention_q_decode_paged, and LQER_E_INVALID for a null q_starts, max_s < 1 or > 8, total < 0,
  * window < 0, window > 0 with causal = 0, a short or misaligned workspace.  batch = 0 or total = 0: LQER_OK, nothing launched.
+ * A DRAFT TREE - the verify step of a speculative decoder that drafts a tree (Medusa, EAGLE, SpecInfer) - goes through the two _tree
+ * calls, one rule for both.  The draft nodes of sequence b are its last S_b = q_starts[b + 1] - q_starts[b] keys, in the order they were
+ * appended (lqer_kv_pool_append_ragged), parents before children; query row i is node i.  Per packed query token there is one word
+ *   tree     uint64 [total], on the DEVICE, written by the caller: bit j (0 <= j < S_b) of tree[q_starts[b] + i] is set iff draft node
+ *            j of sequence b is node i itself or one of its ancestors.
+ * With T_b = lens[b] and base = T_b - S_b, row i of sequence b sees key t iff t < base (the committed context, all of it) or
+ * t = base + j with j <= i and bit j of its word set; bits j > i are ignored.  It is the causal rule with holes in the draft region - a
+ * chain, word i = (2 << i) - 1, IS the causal rule - applied as a select in the kernels' TREE instantiation wherever the causal limit is
+ * tested; a key a row does not see contributes exactly 0 and is left out of the row's maximum and sum.  Caller's contract, on device
+ * data like the table and the lengths: bit i of row i is set (a token sees itself), and S_b <= T_b.
+ * lqer_attention_q_decode_paged_tree: lqer_attention_q_decode_paged_ragged's argument list with the trailing `window` replaced by `tree`;
+ * 1 <= max_s <= 8, only bits 0 .. 7 are read.  lqer_attention_q_paged_tree: lqer_attention_q_paged_ragged's argument list plus `tree`;
+ * 1 <= max_s <= 64.  causal = 1 is required by both.  THE GUARANTEE: for every b, the rows of sequence b in out and row_stats are the
+ * SAME BITS as a call of batch 1 with S = S_b - lqer_attention_q_decode for the first entry, lqer_attention_q for the second - on the
+ * raw K and V of that sequence (the context plus ALL its draft nodes) with the tree as an additive mask tensor, 0 where visible and
+ * the dtype's most negative finite value elsewhere - whatever else is in the batch, whatever pages it lives on, whatever max_s,
+ * max_len and total are and whatever the workspace held: a masked score's exponential is exactly 0 in every dtype, as under the
+ * window rule.  Mind what that comparison says: sibling draft nodes share blocks of the K quantizer (blocks of 16 keys along t), so a
+ * node's bits are those of the masked call on the WHOLE draft, not those of a chain verify of its root-to-node path alone.
+ * With S_b = 0 nothing is written for the sequence; with lens[b] = 0 its rows get zeros and no statistics.  The pool is only read.
+ * Workspace, grid and launch count are the sibling's - lqer_attention_q_decode_paged_ragged_workspace_bytes(total, heads, max_len, D)
+ * and lqer_attention_q_paged_ragged_workspace_bytes(batch, heads, kv_heads, max_s, max_len, D); there is no size function of their
+ * own -, three launches on `stream` (the second entry's two image kernels run unchanged, nibble pools included), no allocation, no
+ * host synchronisation, no atomics: capturable in a hipGraph.  Refused as the sibling, in its words, and LQER_E_INVALID for a null
+ * tree, causal = 0, max_s > 8 (the first entry) or > 64 (the second).  batch = 0 or total = 0: LQER_OK, nothing launched.
  * lqer_kv_pool_gather: one sequence - row `slot` of block_table, T keys (host) - out of the pool into a dense lqer_kv_cache buffer of
  * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
  * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack) and an export path (more than 8 query rows
@@ -1009,6 +1034,19 @@ int lqer_attention_q_decode_paged_ragged(const void* q, const void* pool, size_t
                                          const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
                                          const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
                                          const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream, int64_t window);
+int lqer_attention_q_decode_paged_tree(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                       const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                       int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads,
+                                       int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total, int64_t D,
+                                       const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                       const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                                       const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream, const uint64_t* tree);
+int lqer_attention_q_paged_tree(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
+                                float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, const int32_t* q_starts,
+                                int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling,
+                                int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                                const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream, const uint64_t* tree);
 
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's

@@ -197,6 +197,10 @@ SIGNATURES = {
     # workspace follows (total, heads, max_len, D)
     "lqer_attention_q_decode_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "lqer_attention_q_decode_paged_ragged": (_i, _PAGED_RAGGED + [_i64]),
+    # a draft tree per sequence: the two lists above with `tree` - one uint64 per packed query token, on the device - in the last place
+    # (the decode entry: instead of `window`, up to 8 nodes; the prefill entry: up to 64); workspaces are the siblings'
+    "lqer_attention_q_decode_paged_tree": (_i, _PAGED_RAGGED + [_vp]),
+    "lqer_attention_q_paged_tree": (_i, _PAGED_RAGGED + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1317,6 +1317,22 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
               c.causal);
     return LQER_E_INVALID;
   }
+  if (c.treed) {  // (what the host can see of a tree; the words themselves fall under the caller's contract, as the table and the lengths do)
+    const int most = kn.max_s ? kn.max_s : 64;  // (a row's word has 64 bits; the split over the keys takes 8 rows)
+    if (!c.tree) {
+      set_error("%s: null tree (one uint64 per packed query token, on the device)", who);
+      return LQER_E_INVALID;
+    }
+    if (!c.causal) {
+      set_error("%s: causal = 0 - a tree is a rule on top of the causal one (causal = 1)", who);
+      return LQER_E_INVALID;
+    }
+    if (c.S > most) {
+      set_error("%s: max_s = %lld nodes - a tree of this call has up to %d, and max_s bounds every sequence's count%s", who, (long long)c.S,
+                most, kn.max_s ? " (lqer_attention_q_paged_tree takes up to 64)" : "");
+      return LQER_E_INVALID;
+    }
+  }
   if (!c.q_fmt || !c.k_fmt || !c.p_fmt || !c.v_fmt) {
     set_error("%s: null quantizer format", who);
     return LQER_E_INVALID;
@@ -1374,6 +1390,7 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
   if (c.workspace_bytes < need) {
     // (a windowed call has the unwindowed one's workspace; the ragged decode call takes its window as an argument of its own)
     const char* sized_by = c.grouped   ? "attention_q_decode_paged"  // (the grouped call has the plain call's workspace too)
+                           : c.treed   ? (kn.max_s ? "attention_q_decode_paged_ragged" : "attention_q_paged_ragged")  // (a tree call its sibling's)
                            : !c.windowed ? who
                            : kn.max_s  ?(ragged ? who : "attention_q_decode_paged")
                                        : (ragged ? "attention_q_paged_ragged" : "attention_q_paged");
@@ -1921,7 +1938,7 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
   return attn_run("attention_q_kv", ATTN_PREFILL, c);
 }
 
-// The record of an attention call over the pool from the arguments all eight entries have, in the ABI's order (no mask; T: the bound max_len -
+// The record of an attention call over the pool from the arguments all ten entries have, in the ABI's order (no mask; T: the bound max_len -
 // the check's, the workspace's).  Built in place, never copied: with per-sequence counts it points into the stride triples it holds.
 struct PagedAttn {
   AttnCall c;
@@ -2063,6 +2080,35 @@ int lqer_attention_q_decode_paged_ragged(const void* q, const void* pool, size_t
   a.ragged(q_starts, total);
   a.c.windowed = window != 0, a.c.window = window;
   return attn_run("attention_q_decode_paged_ragged", ATTN_DECODE, a.c);
+}
+
+int lqer_attention_q_decode_paged_tree(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots,
+                                       const int32_t* block_table, int64_t table_stride, const int32_t* seq_slots, const int32_t* lens,
+                                       int64_t max_len, void* out, float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads,
+                                       const int32_t* q_starts, int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides,
+                                       const int64_t* out_strides, float scaling, int causal, const lqer_qfmt_t* q_fmt,
+                                       const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt, void* workspace,
+                                       size_t workspace_bytes, void* stream, const uint64_t* tree) {
+  // lqer_attention_q_decode_paged_ragged without a window, every row with the word of its node of the sequence's draft tree
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads,
+              max_s, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.ragged(q_starts, total);
+  a.c.treed = true, a.c.tree = tree;
+  return attn_run("attention_q_decode_paged_tree", ATTN_DECODE, a.c);
+}
+
+int lqer_attention_q_paged_tree(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                                int dtype, int64_t batch, int64_t heads, int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total,
+                                int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
+                                void* workspace, size_t workspace_bytes, void* stream, const uint64_t* tree) {
+  // lqer_attention_q_paged_ragged for trees of up to 64 nodes: the image kernels as they are, the attention kernel's TREE instantiation
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads,
+              max_s, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.ragged(q_starts, total);
+  a.c.treed = true, a.c.tree = tree;
+  return attn_run("attention_q_paged_tree", ATTN_PREFILL, a.c);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

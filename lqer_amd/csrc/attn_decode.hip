@@ -61,13 +61,24 @@
 // no counters, three launches.  All members of a group with P > 0 have one chunk length (the caller's contract): the leader's C is
 // the C of every row it computes.  P is a licence - a smaller P than the members really share gives the same bits.
 //
+// A draft tree (template parameter TREE of the two bodies, the paged source with RAG, without WIN and GRP:
+// lqer_attention_q_decode_paged_tree): the verify step of a speculative decoder that drafts a TREE of up to 8 nodes per sequence.  The
+// last S_b keys of a sequence are its draft nodes in append order (parents before children), and every packed query token has one
+// uint64 word on the device (DArgsTree::tree, read once per row at sr.tok + si): bit j set iff node j is the row's node or one of
+// its ancestors.  Row i sees the committed context - the keys below off = T_b - S_b - and key off + j iff j <= i and bit j is set
+// (tree_sees, attn_math.h): the causal rule with holes, as a SELECT wherever the causal limit is tested.  A hidden key is left out
+// of the row's maximum and sum and gives P = +0 - what the additive mask tensor gives it (its exponential underflows to 0, and a
+// chunk none of whose keys a row sees folds with factor 0) - so the rows have the bits of the uniform kernels under that mask.
+// Chunks, grid, workspace and k_attn_dec_sum are the RAG ones.  The kernels' names are k_attn_dec_scores_tree / k_attn_dec_pv_tree:
+// the two bodies are written once (dec_scores, dec_pv), and the kernels that existed keep their symbols and argument records.
+//
 // Nibble codes in the paged pool (template parameter N4 of the two kernels, the paged source without GRP: k_fmt / v_fmt of kind
 // LQER_Q_MXINT_C4, kv_pack.h): the packed stage loads 8 bytes per 16 codes and widens them to the byte codes (kvc::load_codes16) in
 // front of the same codes16_to_bf16 - the scores kernel's flag is K's storage, the PV kernel's V's.  Nothing else differs.
 //
 // Written once: a key's 16 quantized values to its LDS row (put_key16: the packed stage of both kernels, the raw V stage); the fold of
 // the lane pair's (max, sum) (fold_lane_pair, attn_math.h); which instantiations exist (decode_variant_exists) -
-// attention_q_decode_dispatch is one fold over (element type, source, WIN, RAG, GRP, K4, V4) behind it.
+// attention_q_decode_dispatch is one fold over (element type, source, WIN, RAG, GRP, K4, V4, TREE) behind it.
 #include "attn_math.h"
 #include "kv_pack.h"
 
@@ -119,6 +130,10 @@ struct DArgsGrp : DArgs {
   const int32_t* grp_starts;   // (device, [groups + 1]) group i owns entries grp_starts[i] .. grp_starts[i + 1] - 1 of grp_members
   const int32_t* grp_members;  // (device, [batch]) call indices, group by group; a group's first member is its leader
   const int32_t* grp_keys;     // (device, [groups]) P: the leading keys a group's members hold on the same pages, a multiple of 16
+};
+// the argument record of the kernels with TREE: the rows' masks behind the RAG record
+struct DArgsTree : DArgsRag {
+  const uint64_t* tree;  // (device, [total]) one word per packed query token - bit j: draft node j is the token's node or an ancestor of it
 };
 template <bool RAG, bool GRP = false>
 using DArgsOf = std::conditional_t<GRP, DArgsGrp, std::conditional_t<RAG, DArgsRag, DArgs>>;
@@ -176,9 +191,11 @@ __device__ __forceinline__ void put_key16(unsigned char* at, const uint32_t (&w)
   dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4 = false>
-__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, GRP> a) {
+// the body of k_attn_dec_scores and k_attn_dec_scores_tree, on the record A of the kernel
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4, bool TREE, class A>
+__device__ __forceinline__ void dec_scores(const A a) {
   static_assert(!N4 || (SRC == SRC_PAGED && !GRP), "nibble K codes: the paged pool, no grouped instantiation");
+  static_assert(!TREE || (SRC == SRC_PAGED && RAG && !WIN && !GRP), "the tree rule: the paged pool with per-sequence counts, no window, no groups");
   __shared__ __attribute__((aligned(16))) unsigned char sK[DEC_CMAX * DEC_LS];
   __shared__ float sSt[4][32][2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
@@ -311,6 +328,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
       int64_t tlo = 0;  // WIN: the first key this lane's query sees (negative: all of them)
       if constexpr (WIN) tlo = si + off - a.win + 1;
       const int64_t moff = a.mode == 1 ? bq * a.m_bs + h * a.m_hs + si * a.m_rs : 0;
+      uint64_t tmask = 0;  // TREE: this lane's row of the tree
+      if constexpr (TREE) tmask = a.tree[sr.tok + si];
       float s2[16];
       bool vis[16];
 #pragma unroll
@@ -320,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
         float s = rnd<DT>(rnd<DT>(acc[r]) * a.scaling);
         if (a.mode == 1) s = rnd<DT>(s + (t < Tq ? load_elem<DT>(a.mask, moff + t) : 0.f));
         s2[r] = s;
-        vis[r] = kk < C && t <= tvis && (!WIN || t >= tlo);
+        vis[r] = kk < C && t <= tvis && (!WIN || t >= tlo) && (!TREE || tree_sees(tmask, t - off));
       }
       float tm = NEG_INF;
 #pragma unroll
@@ -353,8 +372,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, G
 }
 
 template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4 = false>
-__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> a) {
+__global__ __launch_bounds__(256, 2) void k_attn_dec_scores(const DArgsOf<RAG, GRP> a) {
+  dec_scores<DT, SRC, WIN, RAG, GRP, N4, false>(a);
+}
+template <int DT, bool N4>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_scores_tree(const DArgsTree a) {
+  dec_scores<DT, SRC_PAGED, false, true, false, N4, true>(a);
+}
+
+// the body of k_attn_dec_pv and k_attn_dec_pv_tree, on the record A of the kernel
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4, bool TREE, class A>
+__device__ __forceinline__ void dec_pv(const A a) {
   static_assert(!N4 || (SRC == SRC_PAGED && !GRP), "nibble V codes: the paged pool, no grouped instantiation");
+  static_assert(!TREE || (SRC == SRC_PAGED && RAG && !WIN && !GRP), "the tree rule: the paged pool with per-sequence counts, no window, no groups");
   __shared__ __attribute__((aligned(16))) unsigned char sV[DEC_CMAX * DEC_LS];  // [key][d] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int64_t c = blockIdx.x, g = blockIdx.y, b = blockIdx.z, z = b * a.kv_heads + g;
@@ -465,6 +495,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> 
     if (!live) tvis = -1;
     int64_t tlo = 0;
     if constexpr (WIN) tlo = si + off - a.win + 1;
+    uint64_t tmask = 0;  // TREE: this lane's row of the tree
+    if constexpr (TREE) tmask = a.tree[sr.tok + si];
 
     // ---- O^T += Vq^T Pq^T: a k-step is one block of 16 keys of Q_x1, this lane's half of it keys 8 lh .. 8 lh + 7
     f32x16 acc;
@@ -477,7 +509,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> 
       const float s8[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
       float p[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) p[i] = tb + i <= tvis && (!WIN || tb + i >= tlo) ? rnd<DT>(exp_neg(s8[i] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
+      for (int i = 0; i < 8; ++i) p[i] = tb + i <= tvis && (!WIN || tb + i >= tlo) && (!TREE || tree_sees(tmask, tb + i - off)) ? rnd<DT>(exp_neg(s8[i] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
       uint32_t w[4];
       quant8of16_bf16<DT != LQER_F16>(p, a.q1, w);
       const u32x4 pw = {w[0], w[1], w[2], w[3]};
@@ -495,6 +527,15 @@ __global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> 
         if (32 * wave + 8 * q4 + 4 * lh < D) *(float4*)(dst + 8 * q4) = make_float4(acc[4 * q4], acc[4 * q4 + 1], acc[4 * q4 + 2], acc[4 * q4 + 3]);
     }
   }
+}
+
+template <int DT, int SRC, bool WIN, bool RAG, bool GRP, bool N4 = false>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_pv(const DArgsOf<RAG, GRP> a) {
+  dec_pv<DT, SRC, WIN, RAG, GRP, N4, false>(a);
+}
+template <int DT, bool N4>
+__global__ __launch_bounds__(256, 2) void k_attn_dec_pv_tree(const DArgsTree a) {
+  dec_pv<DT, SRC_PAGED, false, true, false, N4, true>(a);
 }
 
 // one thread = four consecutive d of one output row (PAGED: the chunks of the row's own sequence).  RAG: the grid's y is the
@@ -534,22 +575,30 @@ __global__ __launch_bounds__(256) void k_attn_dec_sum(const DArgsOf<RAG> a) {
 }
 
 // The instantiations of the decode kernels that exist, stated once: the window, the per-sequence counts, the groups and the nibble codes
-// have public entries on the paged source only, and the grouped kernels take none of the other three.
-template <int SRC, bool WIN, bool RAG, bool GRP, bool K4, bool V4>
+// have public entries on the paged source only, and the grouped kernels take none of the other three; the tree rule comes with the
+// per-sequence counts, without a window and without groups.
+template <int SRC, bool WIN, bool RAG, bool GRP, bool K4, bool V4, bool TREE = false>
 constexpr bool decode_variant_exists() {
+  if (TREE) return SRC == SRC_PAGED && RAG && !WIN && !GRP;
   if (SRC != SRC_PAGED) return !(WIN || RAG || GRP || K4 || V4);
   return !GRP || !(WIN || RAG || K4 || V4);
 }
 
 // K4 / V4 (the paged pool): the scores kernel reads K alone and the PV kernel V alone - one flag each
-template <int DT, int SRC, bool WIN = false, bool RAG = false, bool GRP = false, bool K4 = false, bool V4 = false>
-static int launch_decode(const DArgsOf<RAG, GRP>& a, int64_t batch, hipStream_t st) {
+template <int DT, int SRC, bool WIN = false, bool RAG = false, bool GRP = false, bool K4 = false, bool V4 = false, bool TREE = false>
+static int launch_decode(const std::conditional_t<TREE, DArgsTree, DArgsOf<RAG, GRP>>& a, int64_t batch, hipStream_t st) {
   const dim3 grid((unsigned)a.nchs, (unsigned)a.kv_heads, (unsigned)batch);
-  k_attn_dec_scores<DT, SRC, WIN, RAG, GRP, K4><<<grid, 256, 0, st>>>(a);
-  k_attn_dec_pv<DT, SRC, WIN, RAG, GRP, V4><<<grid, 256, 0, st>>>(a);
+  if constexpr (TREE) {
+    k_attn_dec_scores_tree<DT, K4><<<grid, 256, 0, st>>>(a);
+    k_attn_dec_pv_tree<DT, V4><<<grid, 256, 0, st>>>(a);
+  } else {
+    k_attn_dec_scores<DT, SRC, WIN, RAG, GRP, K4><<<grid, 256, 0, st>>>(a);
+    k_attn_dec_pv<DT, SRC, WIN, RAG, GRP, V4><<<grid, 256, 0, st>>>(a);
+  }
   // (RAG: a.S is the bound max_s - x over the rows a sequence has at most, y the sequence)
   const dim3 sgrid((unsigned)(((RAG ? a.S * a.heads : a.rows) * (a.D / 4) + 255) / 256), RAG ? (unsigned)batch : 1u);
-  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN, RAG><<<sgrid, 256, 0, st>>>(a);  // (GRP: the plain call's kernel, on the record's base)
+  k_attn_dec_sum<DT, SRC == SRC_PAGED, WIN, RAG><<<sgrid, 256, 0, st>>>(a);  // (GRP, TREE: the plain / RAG call's kernel, on the record's base)
+  if (TREE) return check_launch("lqer_attention_q_decode_paged_tree");
   if (GRP) return check_launch("lqer_attention_q_decode_paged_shared");
   if (RAG) return check_launch("lqer_attention_q_decode_paged_ragged");
   if (WIN) return check_launch("lqer_attention_q_decode_paged_window");
@@ -619,19 +668,26 @@ int attention_q_decode_dispatch(const AttnCall& c) {
     (attn::DArgs&)ag = a;
     ag.grp_of = c.grp_of, ag.grp_starts = c.grp_starts, ag.grp_members = c.grp_members, ag.grp_keys = c.grp_keys;
   }
+  attn::DArgsTree at;  // (the record with per-sequence counts and, behind it, the rows' tree masks)
+  const bool tree = ragged && c.treed;
+  if (tree) {
+    (attn::DArgsRag&)at = a;
+    at.tree = c.tree;
+  }
   return with_dtype(c.dtype, [&](auto dt) {
     return with_flags(
-        [&](auto packed, auto paged, auto win, auto rag, auto grp, auto k4, auto v4) {
+        [&](auto packed, auto paged, auto win, auto rag, auto grp, auto k4, auto v4, auto tr) {
           constexpr int SRC = paged ? attn::SRC_PAGED : (packed ? attn::SRC_PACKED : attn::SRC_RAW);
-          if constexpr ((packed || !paged) && attn::decode_variant_exists<SRC, win, rag, grp, k4, v4>()) {
-            if constexpr (grp) return attn::launch_decode<dt, SRC, win, rag, grp, k4, v4>(ag, c.batch, c.st);
+          if constexpr ((packed || !paged) && attn::decode_variant_exists<SRC, win, rag, grp, k4, v4, tr>()) {
+            if constexpr (tr) return attn::launch_decode<dt, SRC, win, rag, grp, k4, v4, tr>(at, c.batch, c.st);
+            else if constexpr (grp) return attn::launch_decode<dt, SRC, win, rag, grp, k4, v4>(ag, c.batch, c.st);
             else return attn::launch_decode<dt, SRC, win, rag, grp, k4, v4>(a, c.batch, c.st);
           } else {  // (the checks of api.hip let no such call through)
-            set_error("attention_q_decode: no kernel for this combination of source, window, per-sequence counts, groups and nibble codes");
+            set_error("attention_q_decode: no kernel for this combination of source, window, per-sequence counts, groups, nibble codes and tree");
             return (int)LQER_E_UNSUPPORTED;
           }
         },
-        c.packed, c.paged, c.paged && c.windowed, ragged, c.paged && c.grouped, c.paged && c.pool.k4, c.paged && c.pool.v4);
+        c.packed, c.paged, c.paged && c.windowed, ragged, c.paged && c.grouped, c.paged && c.pool.k4, c.paged && c.pool.v4, tree);
   });
 }
 

@@ -55,6 +55,12 @@ __device__ __forceinline__ void fold_lane_pair(float m, float l, float& M, float
   L = l0 * exp_neg(m0 - mr) + l1 * exp_neg(m1 - mr);
 }
 
+// The tree rule of a draft-tree verify (the TREE kernels of attn_decode.hip and attn_q.hip), on top of the causal one: the last S_b
+// keys of a sequence are its draft nodes in append order, `mask` is the query row's own word - bit j set iff node j is the row's node
+// or one of its ancestors - and j = t - (T_b - S_b) the node that key t holds.  j < 0: the committed context, all of it visible.
+// (j beyond the row's own node is the causal limit's to refuse: the bit read there is never used.)
+__device__ __forceinline__ bool tree_sees(uint64_t mask, int64_t j) { return j < 0 || ((mask >> (j & 63)) & 1); }
+
 }  // namespace attn
 
 }  // namespace lqer

@@ -29,9 +29,14 @@
 //                                   WIN, on either paged form, adds the sliding-window rule at compile time: query p sees keys
 //                                   p - W < j <= p, and the sweeps start at the first key tile the workgroup can see
 //                                   (lqer_attention_q_paged_window, lqer_attention_q_paged_ragged_window).
+//                                   TREE, on the RAG form without WIN, adds the rule of a draft-tree verify (k_attn_q_tree,
+//                                   lqer_attention_q_paged_tree): a sequence's S_b <= 64 query rows are the nodes of a draft tree,
+//                                   its last S_b keys theirs, and a lane selects by its own row's uint64 word as well (tree_sees,
+//                                   attn_math.h) - the causal rule with holes, every tile, subtile and lane bound the causal one.
+//                                   The body is written once (attn_q_body); the kernels that existed keep their symbols and record.
 // Written once: the fold of the lane pair's (max, sum) behind sweep 1 (fold_lane_pair, attn_math.h); the skip of a subtile no key of
 // which the wave sees, for both sweeps (`unseen`); which instantiations exist (attn_variant_exists) - attn::launch folds over
-// (PSL, RAG, WIN) behind it.
+// (PSL, RAG, WIN, TREE) behind it.
 #include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16, fold_lane_pair: shared with attn_decode.hip
 
 namespace lqer {
@@ -61,6 +66,11 @@ struct Args {
   int64_t window;  // WIN: W >= 1 - query i sees key j iff i + off - W < j <= i + off (read by no other instantiation)
 };
 
+// the argument record of the kernel with TREE: the rows' masks behind the record of the others, which stays what it was
+struct ArgsTree : Args {
+  const uint64_t* tree;  // (device, [total]) one word per packed query token - bit j: draft node j is the token's node or an ancestor of it
+};
+
 template <int DT>
 __global__ __launch_bounds__(256) void k_attn_kimage(const void* __restrict__ k, int64_t D, int64_t T, int64_t k_bs, int64_t k_hs, int64_t k_rs,
                                                       int kv_heads, QP q, bf16_t* __restrict__ img, int64_t Tp, int64_t Dp, bool vec) {
@@ -88,10 +98,15 @@ __global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v,
 // (kv_cache.hip) have written none -, a wave skips a 32-key subtile that ends at or below w_begin = max(0, q0 + 32 wave + off - W + 1),
 // and a lane's register is visible iff its key is at or above tmin = max(0, qi + off - W + 1) as well: a SELECT wherever the causal
 // limit is tested - never a product with a mask, the image rows of dead keys may hold anything.
-template <int DT, int DK, bool PSL = false, bool RAG = false, bool WIN = false>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
-__global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
+// TREE (a draft tree, with RAG and without WIN; the call is causal): sequence b's rows are the S_b nodes of its tree and its last S_b
+// keys - at and above off = T - S - theirs, in the same order.  The lane reads its row's word once and sees key off + j iff j <= its
+// own row and bit j is set: one more SELECT in `vis`.  t_end, w_end, tmax and `unseen` are the causal ones - the rule only takes keys away.
+// The body of k_attn_q and k_attn_q_tree, on the record A of the kernel.
+template <int DT, int DK, bool PSL, bool RAG, bool WIN, bool TREE, class A>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
+__device__ __forceinline__ void attn_q_body(const A a) {
   static_assert(!RAG || PSL, "per-sequence query counts come with per-sequence lengths");
   static_assert(!WIN || PSL, "the window rule runs on the paged forms");
+  static_assert(!TREE || (RAG && !WIN), "the tree rule comes with the per-sequence counts, without a window");
   constexpr int KS = 64 * DK + 16;  // bytes of a key row in LDS (+16: the 16-byte fragment reads of 16 consecutive rows hit 16 bank groups)
   constexpr int VS = 128 + 8;       // bytes of a V^T row (64 keys) in LDS (+8: the 8-byte reads of 32 rows hit 32 bank pairs)
   __shared__ __attribute__((aligned(16))) unsigned char sK[BT * KS];
@@ -157,13 +172,17 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
     w_begin = wb > 0 ? wb : 0;
     tmin = lb > 0 ? lb : 0;
   }
-  // register r of the subtile at tb holds key tb + 4 lh + (r & 3) + 8 (r >> 2): visible iff that offset is <= lim (and, WIN, >= lim_lo)
-  auto vis = [](int r, int64_t lim_lo, int64_t lim) {
+  const int64_t qic = qi < S ? qi : S - 1;
+  uint64_t tmask = 0;  // TREE: this lane's row of the tree
+  if constexpr (TREE) tmask = a.tree[row0 + qic];
+  // register r of the subtile at tb holds key tb + 4 lh + (r & 3) + 8 (r >> 2): visible iff that offset is <= lim (and, WIN, >= lim_lo;
+  // TREE: the key is draft node jb + offset, jb = tb + 4 lh - off, or - below node 0 - one of the committed context)
+  auto vis = [](int r, int64_t lim_lo, int64_t lim, uint64_t tm, int64_t jb) {
     const int kr = (r & 3) + 8 * (r >> 2);
-    if constexpr (WIN) return lim_lo <= kr && kr <= lim;
+    if constexpr (TREE) return kr <= lim && tree_sees(tm, jb + kr);
+    else if constexpr (WIN) return lim_lo <= kr && kr <= lim;
     else return kr <= lim;
   };
-  const int64_t qic = qi < S ? qi : S - 1;
   const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + qic * a.m_rs : 0;
 
   // (the staged pieces travel BY VALUE: arrays captured by reference in these lambdas ended up in scratch memory)
@@ -270,13 +289,14 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
       float s2[16];
       scores(tb, u, s2);
       const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh;  // register r is visible iff (WIN: lim_lo <=) (r & 3) + 8 (r >> 2) <= lim
+      const int64_t jb = tb + 4 * lh - off;
       float tm = NEG_INF;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tm = vis(r, lim_lo, lim) ? fmaxf(tm, s2[r]) : tm;
+      for (int r = 0; r < 16; ++r) tm = vis(r, lim_lo, lim, tmask, jb) ? fmaxf(tm, s2[r]) : tm;
       const float mn = fmaxf(m, tm), mref = mn == NEG_INF ? 0.f : mn;
       float ls = 0.f;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ls += vis(r, lim_lo, lim) ? exp_neg(s2[r] - mref) : 0.f;
+      for (int r = 0; r < 16; ++r) ls += vis(r, lim_lo, lim, tmask, jb) ? exp_neg(s2[r] - mref) : 0.f;
       l = l * exp_neg(m - mref) + ls;
       m = mn;
     }
@@ -308,9 +328,9 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
       if (unseen(tb)) continue;
       float s2[16];
       scores(tb, u, s2);
-      const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh;
+      const int64_t lim = tmax - tb - 4 * lh, lim_lo = tmin - tb - 4 * lh, jb = tb + 4 * lh - off;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) s2[r] = vis(r, lim_lo, lim) ? rnd<DT>(exp_neg(s2[r] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
+      for (int r = 0; r < 16; ++r) s2[r] = vis(r, lim_lo, lim, tmask, jb) ? rnd<DT>(exp_neg(s2[r] - M) / L) : 0.f;  // (S2 = max = -inf: NaN, as the unfused route)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {  // registers 8 s .. 8 s + 7: keys tb + 16 s + {0-3, 8-11} + 4 lh - half a block of 16, one k-step of P V
         const float v8[8] = {s2[8 * s], s2[8 * s + 1], s2[8 * s + 2], s2[8 * s + 3], s2[8 * s + 4], s2[8 * s + 5], s2[8 * s + 6], s2[8 * s + 7]};
@@ -345,9 +365,20 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
   }
 }
 
-// The instantiations of k_attn_q that exist, stated once: the per-sequence query counts and the window run on the paged forms (PSL)
-template <bool PSL, bool RAG, bool WIN>
+template <int DT, int DK, bool PSL = false, bool RAG = false, bool WIN = false>
+__global__ __launch_bounds__(64 * NW, 2) void k_attn_q(const Args a) {
+  attn_q_body<DT, DK, PSL, RAG, WIN, false>(a);
+}
+template <int DT, int DK>
+__global__ __launch_bounds__(64 * NW, 2) void k_attn_q_tree(const ArgsTree a) {
+  attn_q_body<DT, DK, true, true, false, true>(a);
+}
+
+// The instantiations of the attention kernel that exist, stated once: the per-sequence query counts and the window run on the paged
+// forms (PSL), the tree rule on the form with per-sequence counts and no window
+template <bool PSL, bool RAG, bool WIN, bool TREE = false>
 constexpr bool attn_variant_exists() {
+  if (TREE) return PSL && RAG && !WIN;
   return PSL || !(RAG || WIN);
 }
 
@@ -369,17 +400,25 @@ static int launch(const AttnCall& c, Args a) {
   const int dk = (int)((a.D + 31) / 32);
   const bool ragged = c.paged && c.pool.ragged;  // (a.S: the bound max_s - the grid's x; the kernel takes S from q_starts)
   const bool win = c.paged && c.windowed;        // (the two _window entries: causal, W >= 1 - the check's)
+  const bool tree = ragged && c.treed;           // (lqer_attention_q_paged_tree: causal, max_s <= 64 - the check's)
   with_flags(
-      [&](auto psl, auto rag, auto w) {
-        if constexpr (attn_variant_exists<psl, rag, w>()) switch (dk) {
-            case 1: k_attn_q<DT, 1, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
-            case 2: k_attn_q<DT, 2, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
-            case 3: k_attn_q<DT, 3, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
-            default: k_attn_q<DT, 4, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a); break;
+      [&](auto psl, auto rag, auto w, auto tr) {
+        if constexpr (attn_variant_exists<psl, rag, w, tr>()) {
+          const auto run = [&](auto k) {
+            if constexpr (tr) k_attn_q_tree<DT, k><<<grid, 64 * NW, 0, c.st>>>(ArgsTree{a, c.tree});
+            else k_attn_q<DT, k, psl, rag, w><<<grid, 64 * NW, 0, c.st>>>(a);
+          };
+          switch (dk) {
+            case 1: run(std::integral_constant<int, 1>{}); break;
+            case 2: run(std::integral_constant<int, 2>{}); break;
+            case 3: run(std::integral_constant<int, 3>{}); break;
+            default: run(std::integral_constant<int, 4>{}); break;
           }
+        }
         return 0;
       },
-      c.paged, ragged, win);
+      c.paged, ragged, win, tree);
+  if (tree) return check_launch("lqer_attention_q_paged_tree");
   return check_launch(ragged ? (win ? "lqer_attention_q_paged_ragged_window" : "lqer_attention_q_paged_ragged")
                       : c.paged ? (win ? "lqer_attention_q_paged_window" : "lqer_attention_q_paged")
                                 : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));

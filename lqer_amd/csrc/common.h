@@ -928,7 +928,8 @@ size_t qmatmul_workspace_bytes_ex(int64_t batch, int64_t S1, int64_t K, int64_t 
 // the device.  With `pool.ragged` (lqer_attention_q_paged_ragged) S is the bound max_s, which sizes the grid alone, q / out are
 // [total][heads][D] - qs / os hold {0, head stride, token stride} - and k_attn_q takes every sequence's own S from pool.starts.
 // The decode kernels have the same instantiation (lqer_attention_q_decode_paged_ragged, max_s <= 8, with or without `windowed`): there
-// the workspace rows follow pool.total too.
+// the workspace rows follow pool.total too.  `treed` (lqer_attention_q_decode_paged_tree, lqer_attention_q_paged_tree): the call with
+// per-sequence counts and the rows' tree masks - both kernels' TREE instantiation.
 struct KvPool {  // the paged pool as the C ABI receives it (kv_pack.h: PoolLayout); the three metadata arrays are DEVICE pointers
   const void* pool;
   size_t pool_bytes;
@@ -963,6 +964,10 @@ struct AttnCall {
   int64_t n_groups;
   bool windowed;   // a sliding window over the causal rule (the _window entries, decode and prefill): query p sees keys p - window < j <= p
   int64_t window;
+  // a draft tree over the causal rule (the two _tree entries; `paged` with `pool.ragged`, no window): one word per packed query token,
+  // DEVICE, [pool.total] - bit j set iff draft node j of the token's sequence is the token's node or one of its ancestors
+  bool treed;
+  const uint64_t* tree;
   const lqer_qfmt_t *q_fmt, *k_fmt, *p_fmt, *v_fmt;  // Q_x0, Q_w0, Q_x1, Q_w1
   void* workspace;
   size_t workspace_bytes;

@@ -631,6 +631,9 @@ class PagedKVCache:
     its keys are accepted, `cache.free(seq)` and append those m keys' k / v - the step still has them - to `snap`, which goes on as
     the sequence: the bits of one that only ever saw the m.  There is no in-place crop: the raw keys of a closed block are gone,
     so a shortened block cannot be given the codes and exponents it would have had.
+    The recipe is a draft TREE's too (attention_flexible_paged_tree): fork a snapshot, append_ragged the WHOLE tree - its nodes in an
+    order that puts parents before children -, attend with the nodes' parents, free the sequence and append the rows of k / v of the
+    accepted root-to-leaf path to the snapshot.
 
     window=W (None: keep everything): a SLIDING-WINDOW cache - attention_flexible_paged then defaults to the window rule (a query at
     position p sees keys p - W < j <= p), and `append` hands back the pages nothing can see any more: for each addressed sequence
@@ -1161,6 +1164,9 @@ def attention_flexible_paged(q, cache: PagedKVCache, seqs, scaling, causal=False
 PAGED_PREFILL, PAGED_DECODE = "lqer_attention_q_paged", "lqer_attention_q_decode_paged"
 SHARED_DECODE = "lqer_attention_q_decode_paged_shared"
 RAGGED_PREFILL, RAGGED_DECODE = "lqer_attention_q_paged_ragged", "lqer_attention_q_decode_paged_ragged"
+TREE_PREFILL, TREE_DECODE = "lqer_attention_q_paged_tree", "lqer_attention_q_decode_paged_tree"
+_SIBLING = {TREE_PREFILL: RAGGED_PREFILL, TREE_DECODE: RAGGED_DECODE}  # whose workspace a tree entry has
+TREE_MAX_NODES = 64  # a row's mask is one 64-bit word
 
 
 def _window_arg(who, window, default, causal):
@@ -1206,11 +1212,12 @@ def _paged_max_len(base, cache, lens) -> int:
 
 
 def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, window, ws_ptr, ws_bytes, stream, S=None, counts=None,
-                groups=None):
-    """(entry, its argument tuple) for one of the eight attention entries over the pool: `base` - PAGED_* on q / out [b, h, S, d]
-    (out: any strides over b, h, S), RAGGED_* on q / out [sum(counts), h, d] (any token and head strides) with `counts` query rows per
-    sequence -, stats fp32 dense or None, for the sequences in `slots` with `lens` keys.  `window`: None or W - the entry is then
-    `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  `groups` (PAGED_DECODE without a window only): the call's
+                groups=None, tree=None):
+    """(entry, its argument tuple) for one of the ten attention entries over the pool: `base` - PAGED_* on q / out [b, h, S, d]
+    (out: any strides over b, h, S), RAGGED_* / TREE_* on q / out [sum(counts), h, d] (any token and head strides) with `counts` query
+    rows per sequence -, stats fp32 dense or None, for the sequences in `slots` with `lens` keys.  `window`: None or W - the entry is
+    then `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  `tree` (TREE_* alone, which take no window): the
+    rows' masks, int64 [sum(counts)] on the device, in the last place.  `groups` (PAGED_DECODE without a window only): the call's
     prefix groups (PageTable.prefix_groups) - with a group of two or more the entry is SHARED_DECODE, `base`'s list plus the group
     arrays; with none, without any such group, or on a cache with nibble codes (the grouped kernels are not instantiated for them; the
     bits are the same), `base`.  The workspace and the stream come as values, so nothing
@@ -1223,6 +1230,10 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
             *((cache._call_starts(counts), max(counts), q.shape[0]) if ragged else (S,)), d,
             *((_pair(q), _pair(out)) if ragged else (_tri(q), _tri(out))), float(scaling), int(bool(causal)),
             C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]), ws_ptr, ws_bytes, stream)
+    if base in _SIBLING:
+        if tree is None or window is not None:
+            raise ValueError(f"{base} with tree={tree!r}, window={window} - a tree entry takes the rows' masks and no window")
+        return base, args + (tree.data_ptr(),)
     if base == RAGGED_DECODE:
         return base, args + (0 if window is None else min(window, 1 << 62),)
     if groups is not None and any(len(mem) > 1 for mem, _ in groups):
@@ -1233,19 +1244,21 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
     return (base, args) if window is None else (base + "_window", args + (min(window, 1 << 62),))
 
 
-def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, ws, window, S=None, counts=None, groups=None) -> None:
+def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, ws, window, S=None, counts=None, groups=None,
+                tree=None) -> None:
     """The library call _paged_args describes; ws: a uint8 workspace, or None for the stream's at the size `base`_workspace_bytes asks
-    (a *_window entry has its sibling's)."""
+    (a *_window entry and a TREE_* entry have their sibling's)."""
     L = _lib.lib()
     with torch.cuda.device(q.device):
         if ws is None:
             h, d = q.shape[1], q.shape[-1]
             max_len = _paged_max_len(base, cache, lens)
-            need = (L.lqer_attention_q_decode_paged_ragged_workspace_bytes(q.shape[0], h, max_len, d) if base == RAGGED_DECODE else
-                    getattr(L, base + "_workspace_bytes")(len(slots), h, cache.kv_heads, S if counts is None else max(counts), max_len, d))
+            sized_by = _SIBLING.get(base, base)
+            need = (L.lqer_attention_q_decode_paged_ragged_workspace_bytes(q.shape[0], h, max_len, d) if sized_by == RAGGED_DECODE else
+                    getattr(L, sized_by + "_workspace_bytes")(len(slots), h, cache.kv_heads, S if counts is None else max(counts), max_len, d))
             ws = ops.workspace(q.device, max(need, 16))
         name, args = _paged_args(base, q, out, stats, cache, slots, lens, scaling, causal, window, ws.data_ptr(), ws.numel(), ops._stream(q.device),
-                                 S, counts, groups)
+                                 S, counts, groups, tree)
         _lib.check(getattr(L, name)(*args), name)
 
 
@@ -1312,11 +1325,11 @@ def attention_flexible_paged_decode_ragged(q, cache: PagedKVCache, seqs, counts,
     return (out, stats) if return_stats else out
 
 
-def _ragged_plan(counts, kernel):
-    """The library calls of attention_flexible_paged_ragged for these counts, host arithmetic only: [(name, the indices of the call's
-    sequences, the slice of q's rows they own - None when their rows are not one range and are gathered)].  kernel="auto": all
-    sequences of up to 8 rows in one RAGGED_DECODE call, all others in one RAGGED_PREFILL call; "prefill": all in the latter.
-    Returns the plan and the first row of every sequence."""
+def _ragged_plan(counts, kernel, names=(RAGGED_DECODE, RAGGED_PREFILL)):
+    """The library calls of attention_flexible_paged_ragged (`names`: of attention_flexible_paged_tree) for these counts, host
+    arithmetic only: [(name, the indices of the call's sequences, the slice of q's rows they own - None when their rows are not one
+    range and are gathered)].  kernel="auto": all sequences of up to 8 rows in one call of the decode entry names[0], all others in
+    one call of the prefill entry names[1]; "prefill": all in the latter.  Returns the plan and the first row of every sequence."""
     starts = [0]  # the first row of every sequence
     for c in counts[:-1]:
         starts.append(starts[-1] + c)
@@ -1324,7 +1337,7 @@ def _ragged_plan(counts, kernel):
     small = [b for b in live if counts[b] <= _ATTN_DECODE_MAX_S] if kernel == KERNEL_AUTO else []
     big = [b for b in live if counts[b] > _ATTN_DECODE_MAX_S] if kernel == KERNEL_AUTO else live
     plan = []
-    for name, bs in ((RAGGED_DECODE, small), (RAGGED_PREFILL, big)):
+    for name, bs in zip(names, (small, big)):
         if bs:
             lo, hi = starts[bs[0]], starts[bs[-1]] + counts[bs[-1]]
             plan.append((name, bs, slice(lo, hi) if hi - lo == sum(counts[b] for b in bs) else None))
@@ -1359,7 +1372,6 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     eff_window = _window_arg(who, window, cache.window, causal)
     seqs, counts = _ragged_counts(who, seqs, counts)
     slots, lens = _ragged_operands(who, q, cache, seqs, counts, causal)
-    total, h, d = q.shape
     plan, starts = _ragged_plan(counts, kernel)
     live = [b for _, bs, _ in plan for b in bs]
     big = [bs for name, bs, _ in plan if name == RAGGED_PREFILL]
@@ -1370,6 +1382,16 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
         big_window = _prefill_window(who, cache, [seqs[b] for b in big], [slots[b] for b in big], big_lens, [counts[b] for b in big], eff_window)
     if big and (max(big_lens) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
         raise ValueError(f"{who}: {len(big)} sequences of lengths {big_lens} beyond the prefill kernel's launch grid")
+    windows = {RAGGED_DECODE: eff_window, RAGGED_PREFILL: big_window}  # (the prefill call while every length <= W: plain causal)
+    return _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, causal, return_stats, ws, windows)
+
+
+def _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, causal, return_stats, ws, windows, tree=None):
+    """The calls of a plan (_ragged_plan) over q [sum(counts), h, d], the body of attention_flexible_paged_ragged and
+    attention_flexible_paged_tree: the output and the statistics allocated, every call on its rows of q, its results at those rows.
+    `windows`: the window each entry of the plan runs under; `tree`: the rows' masks, int64 [sum(counts)] on the device (they travel
+    with q's rows), or None."""
+    total, h, d = q.shape
     if q.stride(2) != 1:
         q = q.contiguous()
     out = torch.empty(total, h, d, dtype=q.dtype, device=q.device)
@@ -1386,17 +1408,16 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
             rows += mine
     idx = torch.tensor(rows, dtype=torch.int64).to(q.device) if rows else None
     for (name, bs, _), at in zip(plan, where):
-        args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], scaling, causal, ws,
-                eff_window if name == RAGGED_DECODE else big_window)  # (the prefill call while every length <= W: plain causal)
+        args = (cache, [slots[b] for b in bs], [lens[b] for b in bs], scaling, causal, ws, windows[name])
         mine = [counts[b] for b in bs]
         if isinstance(at, slice):  # (in place: nothing to copy)
-            _paged_call(name, q[at], out[at], stats[at] if return_stats else None, *args, counts=mine)
+            _paged_call(name, q[at], out[at], stats[at] if return_stats else None, *args, counts=mine, tree=None if tree is None else tree[at])
             continue
         ix = idx[at[0]:at[1]]
         qc = q.index_select(0, ix)
         oc = torch.empty_like(qc)
         sc = torch.empty(qc.shape[0], h, 2, dtype=torch.float32, device=q.device) if return_stats else None
-        _paged_call(name, qc, oc, sc, *args, counts=mine)
+        _paged_call(name, qc, oc, sc, *args, counts=mine, tree=None if tree is None else tree.index_select(0, ix))
         out.index_copy_(0, ix, oc)
         if return_stats:
             stats.index_copy_(0, ix, sc)
@@ -1435,3 +1456,84 @@ def _plan(cache: PagedKVCache, seqs, counts, kernel=KERNEL_AUTO, window=None) ->
 attention_flexible_paged_ragged.plan = _plan
 
 
+def tree_masks(parents) -> list:
+    """One sequence's rows of a draft tree from its nodes' parents: parents[i] is -1 for a child of the committed context, else the
+    index - below i: parents come before children - of node i's parent.  Row i of the result has bit j set iff node j is node i or
+    one of its ancestors: what lqer_attention_q_decode_paged_tree / lqer_attention_q_paged_tree read per query row.  A chain gives
+    (2 << i) - 1, the causal rule; a star 1 << i.  ValueError for more than 64 nodes, a parent at or above its node's index or below -1."""
+    try:
+        parents = [int(p) for p in parents]
+    except (TypeError, ValueError):
+        raise ValueError(f"tree_masks: parents {parents!r} - one index per node, -1 for a child of the committed context") from None
+    if len(parents) > TREE_MAX_NODES:
+        raise ValueError(f"tree_masks: {len(parents)} nodes - a row's mask is one 64-bit word: up to {TREE_MAX_NODES} nodes per sequence")
+    masks = []
+    for i, p in enumerate(parents):
+        if p < -1 or p >= i:
+            raise ValueError(f"tree_masks: node {i} with parent {p} - -1 (the committed context) or a node before it: parents come before children")
+        masks.append((1 << i) | (masks[p] if p >= 0 else 0))
+    return masks
+
+
+def _tree_operands(who, cache, seqs, parents, kernel):
+    """What attention_flexible_paged_tree and its .plan ask of the host arguments alone: (seqs, counts, every row's mask), or ValueError."""
+    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
+        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    if cache.window is not None:
+        raise ValueError(f"{who}: a cache made with window={cache.window} - a tree row's position is its depth, not its index, so the "
+                         "window rule is undefined on a draft tree")
+    seqs = list(seqs)
+    try:
+        parents = [list(p) for p in parents]
+    except TypeError:
+        raise ValueError(f"{who}: parents {parents!r} - one list of parent indices per sequence") from None
+    if len(parents) != len(seqs):
+        raise ValueError(f"{who}: {len(parents)} parent lists for {len(seqs)} sequences - one list of parent indices per sequence")
+    try:
+        masks = [m for p in parents for m in tree_masks(p)]
+    except ValueError as e:
+        raise ValueError(f"{who}: {e.args[0]}") from None
+    return seqs, [len(p) for p in parents], masks
+
+
+@torch.no_grad()
+def attention_flexible_paged_tree(q, cache: PagedKVCache, seqs, parents, scaling, return_stats=False, ws=None, kernel=KERNEL_AUTO):
+    """The verify step of a speculative decoder that drafts a TREE (Medusa, EAGLE, SpecInfer) on paged sequences, in at most two
+    library calls and without a copy of any sequence.  parents[b] lists the parents of sequence seqs[b]'s draft nodes (tree_masks:
+    -1 for a child of the committed context, else an earlier node); its nodes are the LAST len(parents[b]) keys of the sequence, in
+    the order they were appended (append_ragged the whole tree first), and q [sum(counts), h, d] holds their queries in that order,
+    counts[b] = len(parents[b]).  Node i sees the committed context - every key before the draft - and, of the draft, itself and its
+    ancestors.  The output has q's shape, the statistics are [sum(counts), h, 2].  A count of 0 leaves its sequence out.
+    kernel="auto" (the default): ALL sequences of up to 8 nodes go through ONE lqer_attention_q_decode_paged_tree call, those of 9 ..
+    64 nodes through ONE lqer_attention_q_paged_tree call; "prefill": all through the latter.  Rows are taken as views or gathered as
+    attention_flexible_paged_ragged takes them (one body).  The masks go to the device in one copy per call.  Every sequence gets the
+    bits of attention_flexible(q_b, K_b, V_b, ..., attention_mask=M, kernel="decode" / "prefill") on its raw K and V - the context
+    plus ALL its draft nodes - with M = 0 where visible and torch.finfo(dtype).min elsewhere.  Sibling nodes share K quantizer blocks
+    (16 keys along t), so these are not the bits of a chain verify of one path alone; the accepted path's keys get those when they
+    are appended to the snapshot (PagedKVCache: "Taking speculated tokens back").
+    attention_flexible_paged_tree.plan(cache, seqs, parents, kernel) names the calls without touching a device.
+    ValueError before anything is launched: what attention_flexible_paged_ragged refuses, in its words (a node count above the
+    sequence's length among them), more than 64 nodes, a bad parents list, a cache made with window=.  ws: a uint8 workspace or None."""
+    who = "attention_flexible_paged_tree"
+    seqs, counts, masks = _tree_operands(who, cache, seqs, parents, kernel)
+    slots, lens = _ragged_operands(who, q, cache, seqs, counts, True)
+    plan, starts = _ragged_plan(counts, kernel, (TREE_DECODE, TREE_PREFILL))
+    for name, bs, _ in plan:
+        if name == TREE_PREFILL and (max(lens[b] for b in bs) > _ATTN_MAX_T or len(bs) * cache.kv_heads > _MAX_GRID_Z):
+            raise ValueError(f"{who}: {len(bs)} sequences of lengths {[lens[b] for b in bs]} beyond the prefill kernel's launch grid")
+    # (int64 holds the 64 bits: bit 63 - row 63's own - is the sign)
+    tree = torch.tensor([m - (1 << 64) if m >> 63 else m for m in masks], dtype=torch.int64).to(q.device)
+    return _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, True, return_stats, ws, {TREE_DECODE: None, TREE_PREFILL: None}, tree)
+
+
+def _tree_plan(cache: PagedKVCache, seqs, parents, kernel=KERNEL_AUTO) -> list:
+    """The library calls attention_flexible_paged_tree(q, cache, seqs, parents, ..., kernel=kernel) makes, in order, from host state
+    alone (no device is touched, no length is read): one dict per call - "call": the C entry, "seqs": the indices into `seqs` of the
+    sequences it takes, "rows": "view" or "gathered" (attention_flexible_paged_ragged.plan's words).  Each call is three launches.
+    Refuses an unknown `kernel`, bad parents and a cache with a window as the function does."""
+    seqs, counts, _ = _tree_operands("attention_flexible_paged_tree", cache, seqs, parents, kernel)
+    return [{"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered"}
+            for name, bs, at in _ragged_plan(counts, kernel, (TREE_DECODE, TREE_PREFILL))[0]]
+
+
+attention_flexible_paged_tree.plan = _tree_plan
