@@ -1063,6 +1063,31 @@ size_t lqer_col_abs_stats_workspace_bytes(int64_t M, int64_t K);
 int lqer_col_abs_stats(const void* x, int dtype, int64_t M, int64_t K, int64_t ldx, float* run_absmean_max, float* col_absmax,
                        float threshold, int32_t* n_cols_ge, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- quantization-error products (the approximator's O(N K) step; reference approximate/lqer_svd.py:37-47, lqer_act.py:84-97) --
+ * The error operator of a weight W [N, K] (row stride ldw elements; fp32 / fp16 / bf16, upcast to fp32 as W.float() does) is
+ *   E_s = diag(scale) (W - Q_w(W))^T   [K, N],   scale [K] fp32 or NULL (all ones: LQER-SVD; L2QER passes the activation scale).
+ * lqer_qerr_matmul multiplies it with a skinny fp32 matrix of 1 <= L <= 256 columns WITHOUT forming it:
+ *   trans = 0:  Y [N, L] = E_s^T X [K, L] = (W - Q_w(W)) (scale . X)       (scale . X rounded to fp32, then multiplied)
+ *   trans = 1:  Y [K, L] = E_s   X [N, L] = scale . ((W - Q_w(W))^T X)
+ * X and Y are row-major fp32 with row strides ldx, ldy >= L.  Two sources of W - Q_w(W):
+ *   fused (w_fmt != NULL): W is the weight; each block is quantized in registers exactly as lqer_quantize_mxint's deq_f32 (block
+ *     exponent, the |w| <= 1e-8 keep-as-is rule, the clamp) and subtracted in fp32.  Served: LQER_Q_MXINT of width 2..8 with blocks of
+ *     16, 32, 64 or 128 along K (a partial last block is zero-padded); anything else: LQER_E_UNSUPPORTED, the text names the dense source;
+ *   dense (w_fmt == NULL): W is E = W - Q_w(W) itself, fp32 [N, K] (dtype must be LQER_F32) - every other weight quantizer
+ *     (whole-row blocks, 2-D tiles, integer, minifloat): the caller computes E once with the quantizer entry that serves the format.
+ * Both sources run one kernel body and give the same bits on the same E.  Operands enter the matrix pipe as fp32
+ * (v_mfma_f32_32x32x2_f32), fp32 accumulation.  The contraction is split over workgroups; the partial sums lie in the workspace and are
+ * added in an order fixed by (N, K, trans) - no floating-point atomics, two calls give the same bits over any workspace contents.
+ * Any N, K >= 1, any ldw >= K and alignment of W (16-byte aligned rows take 16-byte loads, others element loads: same bits); Y is
+ * written at row * ldy + column < L only.  workspace: lqer_qerr_matmul_workspace_bytes(N, K, L, trans) bytes (0 for arguments the
+ * call refuses), 4-byte aligned.  Every check runs before the first of the two launches on `stream`. */
+size_t lqer_qerr_matmul_workspace_bytes(int64_t N, int64_t K, int64_t L, int trans);
+int lqer_qerr_matmul(const void* W, int dtype, int64_t N, int64_t K, int64_t ldw,
+                     const lqer_qfmt_t* w_fmt,      /* NULL: W is E itself (dense source; dtype must be LQER_F32) */
+                     const float* scale,            /* [K] or NULL */
+                     int trans, const float* X, int64_t ldx, int64_t L,
+                     float* Y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement aid ---------------------------------------------------------------------------------------------------
  * The shader clock the chip holds while other work runs: `nblocks` (1..64) one-wave workgroups on `stream` (a stream of its
  * own, beside the kernels under study) each write {shader cycles, 100 MHz ticks} elapsed over the last three quarters of about `duration_us` of real time to

@@ -9,7 +9,8 @@ WeightApproximatorLqerAct.approximate (lqer_act.py:84-97):
 
 Q_w, Q_A, Q_B run on the library's HIP quantizer kernels (the A / B quantizers' blocks run along dim 0 - block_size
 [16, 1], llama-7b.toml:60-73 - which is the last dim of the transposed operand); the SVD is torch.linalg.svd on the GPU
-(rocSOLVER), in fp32.  A and B themselves are not comparable across SVD implementations (sign / rotation of close
+(rocSOLVER), in fp32 - or, with method="subspace", a randomized subspace iteration whose O(N K) steps are the library's fused
+quantization-error GEMM (csrc/qerr_mm.hip: W read once per product, E never formed).  A and B themselves are not comparable across SVD implementations (sign / rotation of close
 singular vectors); the tests pin the reconstruction error |E^T - A B|.
 """
 from __future__ import annotations
@@ -38,12 +39,52 @@ def _quantize_along_dim0(t: torch.Tensor, cfg: Optional[dict]) -> torch.Tensor:
     return ops.quantize_mxint(t.contiguous(), ops.make_qfmt(cfg, "w"), want=("deq",))["deq"]
 
 
+def _subspace_factors(W: torch.Tensor, w_cfg: dict, rank: int, s: Optional[torch.Tensor], oversample: int, power_iters: int,
+                      seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """U_r [K, r] and diag(sigma_r) V_r^T [r, N] of E_s = diag(s) (W - Q_w(W))^T by randomized subspace iteration (Halko, Martinsson,
+    Tropp 2011, alg. 4.4 + 5.1): every O(N K) step is ops.qerr_matmul (one read of W, E never formed when the kernel's fused source
+    covers w_cfg; else E is formed once with the quantizer kernel and multiplied as the dense source); the O((N + K) l^2) algebra -
+    QR of the skinny iterates, the SVD of the l x N projection - stays in torch."""
+    N, K = W.shape
+    l = min(rank + oversample, K, N)
+    if l > 256:
+        raise ValueError(f"method='subspace': rank + oversample = {l} exceeds the 256 columns of qerr_matmul (use method='svd')")
+    if ops.qerr_fused_covers(ops.make_qfmt(w_cfg, "w")):
+        src, cfg = W, w_cfg
+    else:
+        Wf = W.float()
+        src, cfg = Wf - ops.quantize_mxint(Wf.contiguous(), ops.make_qfmt(w_cfg, "w"), want=("deq",))["deq"], None
+    gen = torch.Generator(device=W.device)
+    gen.manual_seed(seed)
+    omega = torch.randn(N, l, generator=gen, device=W.device, dtype=torch.float32)
+    Y = ops.qerr_matmul(src, cfg, omega, 1, s)  # E_s Omega  [K, l]
+    for _ in range(power_iters):
+        Q = torch.linalg.qr(Y).Q
+        Qz = torch.linalg.qr(ops.qerr_matmul(src, cfg, Q, 0, s)).Q  # E_s^T Q  [N, l]
+        Y = ops.qerr_matmul(src, cfg, Qz, 1, s)
+    Q = torch.linalg.qr(Y).Q
+    Bh = ops.qerr_matmul(src, cfg, Q, 0, s).t()  # Q^T E_s  [l, N]
+    Uh, S, Vh = torch.linalg.svd(Bh, full_matrices=False)
+    return Q @ Uh[:, :rank], S[:rank, None] * Vh[:rank]
+
+
 @torch.no_grad()
 def lqer_factors(W: torch.Tensor, w_cfg: dict, rank: int, a_cfg: Optional[dict] = None, b_cfg: Optional[dict] = None,
-                 scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 scale: Optional[torch.Tensor] = None, method: str = "svd", oversample: int = 16, power_iters: int = 2,
+                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """A [in, rank], B [rank, out] (fp32, on W's device) for one weight W [out, in].  `scale` [in] is the activation
-    scale of L2QER (lqer_act.py); None gives LQER-SVD."""
+    scale of L2QER (lqer_act.py); None gives LQER-SVD.  method="svd": the full decomposition of the materialised error (the reference's
+    route); method="subspace": the leading `rank` triplets by randomized subspace iteration on the fused quantization-error GEMM
+    (_subspace_factors; `oversample` extra columns, `power_iters` refinements, `seed` of the device generator - same seed, same factors)."""
+    if method not in ("svd", "subspace"):
+        raise ValueError(f"lqer_factors: unknown method {method!r} ('svd' or 'subspace')")
     ops._need_gpu(W)
+    if method == "subspace":
+        s = None if scale is None else scale.to(W.device, torch.float32)
+        A, B = _subspace_factors(W, w_cfg, rank, s, oversample, power_iters, seed)
+        if s is not None:
+            A = A / s[:, None]
+        return _quantize_along_dim0(A.contiguous(), a_cfg), _quantize_along_dim0(B.contiguous(), b_cfg)
     Wf = W.float()
     Wq = ops.quantize_mxint(Wf.contiguous(), ops.make_qfmt(w_cfg, "w"), want=("deq",))["deq"]
     err_t = (Wf - Wq).t()
@@ -73,7 +114,8 @@ def module_owners(names, world: int) -> Dict[str, int]:
 
 @torch.no_grad()
 def approximate_model(model: nn.Module, a_cfg: Optional[dict] = None, b_cfg: Optional[dict] = None,
-                      scale_dict: Optional[Dict[str, torch.Tensor]] = None, factors_fn=None) -> Dict[str, torch.Tensor]:
+                      scale_dict: Optional[Dict[str, torch.Tensor]] = None, factors_fn=None, method: str = "svd",
+                      **factor_kwargs) -> Dict[str, torch.Tensor]:
     """Fill A and B of every LinearFlexibleLqer of a model prepared by models.quantize_model (weights still dense, on
     the GPU).  Returns the dictionary the reference stores as low_rank_dict.pt ({"<module>.A", "<module>.B"}).
     scale_dict maps "<module name>.scale" (what calibrate.profile_model / the reference's profiler write) or the plain module name to
@@ -82,7 +124,8 @@ def approximate_model(model: nn.Module, a_cfg: Optional[dict] = None, b_cfg: Opt
     With an initialised torch.distributed group (one process per GPU, every rank holding the same model) the SVDs are
     split over the ranks by decoder layer (module_owners) and each module's A, B are broadcast from their owner, so all
     ranks end with the full set - the one exchange step of this offline path (RCCL broadcast of K*r + r*N elements).
-    factors_fn (tests): replaces lqer_factors."""
+    factors_fn (tests): replaces lqer_factors.  method / factor_kwargs (oversample, power_iters, seed): handed to lqer_factors when they
+    differ from its defaults - a call without them is the call it was."""
     import torch.distributed as dist
 
     factors_fn = factors_fn or lqer_factors
@@ -97,7 +140,8 @@ def approximate_model(model: nn.Module, a_cfg: Optional[dict] = None, b_cfg: Opt
             w_cfg = m.q_config.get("w_quantizer", m.q_config["default"])
             # (the reference's key first - "<module>.scale", statistic_profiler/scale.py:65, lqer_act.py:156 -, then the plain name)
             sc = (scale_dict[name + ".scale"] if name + ".scale" in scale_dict else scale_dict.get(name)) if scale_dict else None
-            A, B = factors_fn(m.weight.data, w_cfg, m.rank, a_cfg, b_cfg, sc)
+            extra = dict(factor_kwargs, method=method) if (method != "svd" or factor_kwargs) else {}
+            A, B = factors_fn(m.weight.data, w_cfg, m.rank, a_cfg, b_cfg, sc, **extra)
             m.A.data.copy_(A.to(m.A.dtype))
             m.B.data.copy_(B.to(m.B.dtype))
         if world > 1:

@@ -2128,4 +2128,38 @@ int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_by
   return LQER_OK;
 }
 
+// ---- quantization-error products (qerr_mm.hip) ----
+size_t lqer_qerr_matmul_workspace_bytes(int64_t N, int64_t K, int64_t L, int trans) {
+  if (N <= 0 || K <= 0 || L <= 0 || L > 256 || N > ((int64_t)1 << 30) || K > ((int64_t)1 << 30)) return 0;
+  return lqer::qerr_workspace(N, K, L, trans ? 1 : 0);
+}
+
+int lqer_qerr_matmul(const void* W, int dtype, int64_t N, int64_t K, int64_t ldw, const lqer_qfmt_t* w_fmt, const float* scale, int trans,
+                     const float* X, int64_t ldx, int64_t L, float* Y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  if (L < 1 || L > 256) return fail(LQER_E_INVALID, "qerr_matmul: L = %lld outside [1,256]", (long long)L);
+  if (!W || !X || !Y || N < 1 || K < 1 || N > ((int64_t)1 << 30) || K > ((int64_t)1 << 30) || ldw < K || ldx < L || ldy < L ||
+      (trans != 0 && trans != 1))
+    return fail(LQER_E_INVALID, "qerr_matmul: bad argument (W %p, X %p, Y %p, N %lld, K %lld, ldw %lld, ldx %lld, ldy %lld, L %lld, trans %d)", W,
+                (const void*)X, (const void*)Y, (long long)N, (long long)K, (long long)ldw, (long long)ldx, (long long)ldy, (long long)L, trans);
+  if (dtype != LQER_F32 && dtype != LQER_F16 && dtype != LQER_BF16) return fail(LQER_E_INVALID, "qerr_matmul: unknown dtype %d", dtype);
+  QP q{};
+  if (!w_fmt) {
+    if (dtype != LQER_F32) return fail(LQER_E_INVALID, "qerr_matmul: w_fmt = NULL names the dense source - W is E itself and must be LQER_F32 (dtype %d)", dtype);
+  } else {
+    static const char* const DENSE = "compute E = W - Q_w(W) with lqer_quantize_mxint and pass it as the dense source (w_fmt = NULL)";
+    if (w_fmt->kind != LQER_Q_MXINT)
+      return fail(LQER_E_UNSUPPORTED, "qerr_matmul: the fused source quantizes block_fp weights only (w_fmt kind %d): %s", w_fmt->kind, DENSE);
+    if (!fmt_ok(w_fmt, ROLE_W)) return LQER_E_UNSUPPORTED;
+    if (w_fmt->block != 16 && w_fmt->block != 32 && w_fmt->block != 64 && w_fmt->block != 128)
+      return fail(LQER_E_UNSUPPORTED, "qerr_matmul: the fused source takes blocks of 16, 32, 64 or 128 along K (w_fmt block %d): %s", w_fmt->block,
+                  DENSE);
+    q = make_qp(*w_fmt);
+  }
+  const size_t need = lqer::qerr_workspace(N, K, L, trans);
+  if (workspace_bytes < need)
+    return fail(LQER_E_WORKSPACE, "qerr_matmul: workspace %zu B < %zu B (lqer_qerr_matmul_workspace_bytes)", workspace_bytes, need);
+  if (!workspace || ((uintptr_t)workspace & 3)) return fail(LQER_E_INVALID, "qerr_matmul: workspace null or not 4-byte aligned");
+  return lqer::qerr_mm_dispatch(W, dtype, N, K, ldw, w_fmt != nullptr, q, scale, trans, X, ldx, L, Y, ldy, workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

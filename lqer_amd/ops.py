@@ -520,6 +520,55 @@ def col_abs_stats(x: torch.Tensor, run: Optional[torch.Tensor] = None, want_absm
     return ColStats(run, absmax, count)
 
 
+def qerr_fused_covers(fmt: Optional[QFmt]) -> bool:
+    """True when lqer_qerr_matmul's fused source quantizes this weight format itself (block_fp, 1-D blocks of 16 / 32 / 64 / 128 along K)."""
+    return (fmt is not None and fmt.kind == _lib.Q_MXINT and int(getattr(fmt, "block_rows", 1)) == 1 and fmt.block in (16, 32, 64, 128))
+
+
+@_on_tensor_device
+def qerr_matmul(W: torch.Tensor, w_cfg: Optional[dict], X: torch.Tensor, trans: int, scale: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Product of the quantization-error operator E_s = diag(scale) (W - Q_w(W))^T [K, N] of a weight W [N, K] with a skinny fp32
+    matrix (lqer_qerr_matmul; at most 256 columns): trans = 0 gives E_s^T X for X [K, L], trans = 1 gives E_s X for X [N, L].  With a
+    w_quantizer config the weight is quantized inside the kernel (fused source: block_fp with 1-D blocks of 16 / 32 / 64 / 128; other
+    formats raise NotImplementedError); with w_cfg = None, W is E = W - Q_w(W) itself in fp32 (dense source).  `out`: a float32
+    [rows, L] tensor with unit column stride to write into (any row stride)."""
+    fmt = None
+    if w_cfg is not None:
+        fmt = make_qfmt(w_cfg, "w")
+        if int(getattr(fmt, "block_rows", 1)) != 1:
+            raise NotImplementedError(f"qerr_matmul: the fused source takes 1-D blocks along K, not 2-D tiles (block_size {w_cfg.get('block_size')}): "
+                                      "pass E = W - quantize_mxint(W) as the dense source (w_cfg = None)")
+    _need_gpu(W, X, scale, out)
+    if W.dim() != 2 or X.dim() != 2:
+        raise ValueError(f"qerr_matmul: W {tuple(W.shape)} and X {tuple(X.shape)} must be matrices")
+    N, K = W.shape
+    rows_in, rows_out = (N, K) if trans else (K, N)
+    L = X.shape[1]
+    if X.shape[0] != rows_in or X.dtype != torch.float32:
+        raise ValueError(f"qerr_matmul: X must be float32 [{rows_in}, L] for trans = {int(trans)} (got {X.dtype} {tuple(X.shape)})")
+    if W.stride(1) != 1:
+        W = W.contiguous()
+    if X.stride(1) != 1:
+        X = X.contiguous()
+    dev = W.device
+    if scale is not None:
+        scale = scale.to(dev, torch.float32).contiguous()
+        if scale.shape != (K,):
+            raise ValueError(f"qerr_matmul: scale must be [{K}]")
+    if out is None:
+        out = torch.empty(rows_out, L, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.shape != (rows_out, L) or out.stride(1) != 1 or out.device != dev:
+        raise ValueError(f"qerr_matmul: out must be float32 [{rows_out}, {L}] on {dev} with unit column stride")
+    lib = _lib.lib()
+    nbytes = lib.lqer_qerr_matmul_workspace_bytes(N, K, L, int(trans))
+    ws = workspace(dev, max(nbytes, 4))
+    check(lib.lqer_qerr_matmul(W.data_ptr(), dtype_code(W), N, K, W.stride(0) if N > 1 else K, C.byref(fmt) if fmt is not None else None,
+                               _ptr(scale), int(trans), X.data_ptr(), X.stride(0) if rows_in > 1 else L, L, out.data_ptr(),
+                               out.stride(0) if rows_out > 1 else L, ws.data_ptr(), nbytes, _stream(dev)), "lqer_qerr_matmul")
+    return out
+
+
 # grow-only per-(device, stream) scratch shared by every Linear (stream-ordered reuse is safe)
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
 
