@@ -905,6 +905,16 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * own -, three launches on `stream` (the second entry's two image kernels run unchanged, nibble pools included), no allocation, no
  * host synchronisation, no atomics: capturable in a hipGraph.  Refused as the sibling, in its words, and LQER_E_INVALID for a null
  * tree, causal = 0, max_s > 8 (the first entry) or > 64 (the second).  batch = 0 or total = 0: LQER_OK, nothing launched.
+ * lqer_attention_q_paged_direct: lqer_attention_q_paged_ragged's argument list plus `window` (0: none; W >= 1: the rule of
+ * lqer_attention_q_paged_ragged_window) and `tree` (NULL: none; else the rows' words of lqer_attention_q_paged_tree, 1 <= max_s <= 64),
+ * on a kernel that reads the pool's codes and exponent bytes inside its key loop, through the block table: no bf16 image is written,
+ * ONE launch on `stream`, and lqer_attention_q_paged_direct_workspace_bytes(the ragged query's arguments) is 0 - `workspace` may be
+ * NULL with workspace_bytes 0.  THE GUARANTEE is the sibling's: for every b the rows of sequence b in out and row_stats are the same
+ * bits as the sibling entry's, i.e. as the batch-1 lqer_attention_q on the sequence's raw K and V with the rule as a mask tensor.  No
+ * table entry at or beyond ceil(lens[b] / 16) is read and, under a window, none below the page of the first key the sequence's first
+ * query row sees, nor any page behind such an entry.  Counts of any size, 1 .. 8 included.  Refused as the siblings, in their words
+ * (causal = 0 with a window or a tree, a negative window, a null pointer, max_s > 64 with a tree, ...), and: LQER_E_UNSUPPORTED for a
+ * pool with nibble codes (k_fmt / v_fmt of kind LQER_Q_MXINT_C4), LQER_E_INVALID for `window` together with `tree`.
  * lqer_kv_pool_gather: one sequence - row `slot` of block_table, T keys (host) - out of the pool into a dense lqer_kv_cache buffer of
  * batch 1 and the given capacity (>= T): codes, exponents and the slot's staging rows, a pure byte copy in one launch.  The result is
  * the cache lqer_kv_cache_append would have built: the test hook (lqer_kv_cache_unpack) and an export path (more than 8 query rows
@@ -1047,6 +1057,14 @@ int lqer_attention_q_paged_tree(const void* q, const void* pool, size_t pool_byt
                                 int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling,
                                 int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
                                 const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream, const uint64_t* tree);
+size_t lqer_attention_q_paged_direct_workspace_bytes(int64_t batch, int64_t heads, int64_t kv_heads, int64_t max_s, int64_t max_len, int64_t D);
+int lqer_attention_q_paged_direct(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out,
+                                  float* row_stats, int dtype, int64_t batch, int64_t heads, int64_t kv_heads, const int32_t* q_starts,
+                                  int64_t max_s, int64_t total, int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling,
+                                  int causal, const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt,
+                                  const lqer_qfmt_t* v_fmt, void* workspace, size_t workspace_bytes, void* stream, int64_t window,
+                                  const uint64_t* tree);
 
 /* ---- calibration statistics (the producer of L2QER's scale_dict; reference src/lqer/statistic_profiler/) ----------------------
  * One pass over an activation x [M, K] (row stride ldx elements; fp32 / fp16 / bf16, values upcast to fp32 as the hook's

@@ -204,6 +204,10 @@ SIGNATURES = {
     # (the decode entry: instead of `window`, up to 8 nodes; the prefill entry: up to 64); workspaces are the siblings'
     "lqer_attention_q_decode_paged_tree": (_i, _PAGED_RAGGED + [_vp]),
     "lqer_attention_q_paged_tree": (_i, _PAGED_RAGGED + [_vp]),
+    # the prefill kernel that reads the pool's codes in its key loop (k_attn_q_direct): the ragged list plus `window` (0: none) and
+    # `tree` (NULL: none); one launch, a workspace of 0 bytes
+    "lqer_attention_q_paged_direct_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "lqer_attention_q_paged_direct": (_i, _PAGED_RAGGED + [_i64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1288,6 +1288,9 @@ static const AttnKernel ATTN_PREFILL = {0, "kernel takes", prefill_grid_limits, 
                                         attention_q_dispatch};
 static const AttnKernel ATTN_DECODE = {attention_q_decode_max_s(), "kernels take", decode_grid_limits, true, decode_workspace_bytes,
                                        attention_q_decode_dispatch};
+// (the prefill kernel on the pool's codes: its limits, no workspace - a null one is then no null pointer)
+static const AttnKernel ATTN_DIRECT = {0, "kernel takes", prefill_grid_limits, false, [](const AttnCall&) { return (size_t)0; },
+                                       attention_q_direct_dispatch};
 
 // the check of every attention call, for the kernel `kn` that will run: LQER_OK = go on, 1 = nothing to do, else the refusal
 static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) {
@@ -1378,7 +1381,7 @@ static int attn_check(const char* who, const AttnKernel& kn, const AttnCall& c) 
     set_error("%s: T = 0 (a softmax over no keys)", who);
     return LQER_E_INVALID;
   }
-  if (!c.q || (!c.packed && (!c.k || !c.v)) || !c.out || !c.workspace) {
+  if (!c.q || (!c.packed && (!c.k || !c.v)) || !c.out || (!c.workspace && kn.workspace_bytes(c) > 0)) {
     set_error("%s: null pointer", who);
     return LQER_E_INVALID;
   }
@@ -2109,6 +2112,34 @@ int lqer_attention_q_paged_tree(const void* q, const void* pool, size_t pool_byt
   a.ragged(q_starts, total);
   a.c.treed = true, a.c.tree = tree;
   return attn_run("attention_q_paged_tree", ATTN_PREFILL, a.c);
+}
+
+size_t lqer_attention_q_paged_direct_workspace_bytes(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t) { return 0; }
+
+int lqer_attention_q_paged_direct(const void* q, const void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table,
+                                  int64_t table_stride, const int32_t* seq_slots, const int32_t* lens, int64_t max_len, void* out, float* row_stats,
+                                  int dtype, int64_t batch, int64_t heads, int64_t kv_heads, const int32_t* q_starts, int64_t max_s, int64_t total,
+                                  int64_t D, const int64_t* q_strides, const int64_t* out_strides, float scaling, int causal,
+                                  const lqer_qfmt_t* q_fmt, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* p_fmt, const lqer_qfmt_t* v_fmt,
+                                  void* workspace, size_t workspace_bytes, void* stream, int64_t window, const uint64_t* tree) {
+  // lqer_attention_q_paged_ragged, _ragged_window (window != 0) and _tree (tree != NULL) on the kernel that reads the pool's codes in its
+  // key loop: the same record, the same check, one launch and no workspace
+  PagedAttn a(q, pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, out, row_stats, dtype, batch, heads, kv_heads,
+              max_s, D, q_strides, out_strides, scaling, causal, q_fmt, k_fmt, p_fmt, v_fmt, workspace, workspace_bytes, stream);
+  a.ragged(q_starts, total);
+  a.c.windowed = window != 0, a.c.window = window;  // (a negative one, and either rule without causal = 1, are the check's to refuse)
+  a.c.treed = tree != nullptr, a.c.tree = tree;
+  if (a.c.windowed && a.c.treed) {
+    set_error("attention_q_paged_direct: window = %lld with a tree - a tree row's position is its depth, the window rule is undefined on it "
+              "(window = 0 or tree = NULL)", (long long)window);
+    return LQER_E_INVALID;
+  }
+  if (a.c.pool.k4 || a.c.pool.v4) {
+    set_error("attention_q_paged_direct: k_fmt / v_fmt of kind LQER_Q_MXINT_C4 - the kernel is not instantiated for nibble codes; "
+              "lqer_attention_q_paged_ragged gives the same bits");
+    return LQER_E_UNSUPPORTED;
+  }
+  return attn_run("attention_q_paged_direct", ATTN_DIRECT, a.c);
 }
 
 int lqer_replicate_rows(const void* src, void* dst, int64_t rows, int64_t row_bytes, int copies, void* stream) {

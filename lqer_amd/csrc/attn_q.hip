@@ -38,6 +38,7 @@
 // which the wave sees, for both sweeps (`unseen`); which instantiations exist (attn_variant_exists) - attn::launch folds over
 // (PSL, RAG, WIN, TREE) behind it.
 #include "attn_math.h"  // rnd<DT>, exp_neg, quant8of16_bf16, fold_lane_pair: shared with attn_decode.hip
+#include "kv_pack.h"    // CODES: the pool's source record, load_codes16, load_v4, codes16_to_bf16, page_block
 
 namespace lqer {
 
@@ -71,6 +72,35 @@ struct ArgsTree : Args {
   const uint64_t* tree;  // (device, [total]) one word per packed query token - bit j: draft node j is the token's node or an ancestor of it
 };
 
+// the argument record of the kernels with CODES (k_attn_q_direct): no image - kimg, vimg, Tp, Dp and Tv of the base are unread -, the
+// pool's sections, table, slots and lengths instead, the two formats the codes are converted by, and the rows' masks (TREE; else unread)
+struct ArgsDirect : Args {
+  const uint64_t* tree;
+  kvc::KvSrc<const unsigned char> src;
+  QP qk, qv;
+};
+
+// What a thread stages of the next key tile under the current tile's MFMAs, by the tiles' source.  Images: DK 16-byte pieces of K and
+// DK of V.  CODES: of K two 16-byte code rows (c[0], c[1]) and the 16 exponent bytes they share (e); of V four code rows and the dword
+// of their exponents (e.x) - 3 + 4.25 pieces where the images stage 2 DK = 8 at D = 128.
+template <int DK>
+struct ImgStage {
+  uint4 r[DK];
+};
+struct CodeStage {
+  uint4 c[4], e;
+};
+// CODES: what a thread knows of its sequence's pages - the slot's row of the table, the blocks of 16 keys that may be read [blk0, nblk)
+// - and the table entries it has requested ahead: ek / ev for the K unit / V item of tile ek_it / ev_it (-1: a block not to be read).
+struct NoWalk {};
+struct PageWalk {
+  const int32_t* row;
+  int64_t T;
+  int g, nblk, blk0;
+  int32_t ek, ev;
+  int ek_it, ev_it;
+};
+
 template <int DT>
 __global__ __launch_bounds__(256) void k_attn_kimage(const void* __restrict__ k, int64_t D, int64_t T, int64_t k_bs, int64_t k_hs, int64_t k_rs,
                                                       int kv_heads, QP q, bf16_t* __restrict__ img, int64_t Tp, int64_t Dp, bool vec) {
@@ -102,8 +132,9 @@ __global__ __launch_bounds__(256) void k_attn_vimage(const void* __restrict__ v,
 // keys - at and above off = T - S - theirs, in the same order.  The lane reads its row's word once and sees key off + j iff j <= its
 // own row and bit j is set: one more SELECT in `vis`.  t_end, w_end, tmax and `unseen` are the causal ones - the rule only takes keys away.
 // The body of k_attn_q and k_attn_q_tree, on the record A of the kernel.
-template <int DT, int DK, bool PSL, bool RAG, bool WIN, bool TREE, class A>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
+template <int DT, int DK, bool PSL, bool RAG, bool WIN, bool TREE, bool CODES = false, class A>  // DK: 32-wide tiles of the head dim (D <= 32 DK)
 __device__ __forceinline__ void attn_q_body(const A a) {
+  static_assert(!CODES || RAG, "the tiles come from the pool's codes on the form with per-sequence counts");
   static_assert(!RAG || PSL, "per-sequence query counts come with per-sequence lengths");
   static_assert(!WIN || PSL, "the window rule runs on the paged forms");
   static_assert(!TREE || (RAG && !WIN), "the tree rule comes with the per-sequence counts, without a window");
@@ -186,42 +217,110 @@ __device__ __forceinline__ void attn_q_body(const A a) {
   const int64_t moff = a.mode == 1 ? b * a.m_bs + h * a.m_hs + qic * a.m_rs : 0;
 
   // (the staged pieces travel BY VALUE: arrays captured by reference in these lambdas ended up in scratch memory)
-  struct Stage {
-    uint4 r[DK];
-  };
+  using Stage = std::conditional_t<CODES, CodeStage, ImgStage<DK>>;
+  [[maybe_unused]] std::conditional_t<CODES, PageWalk, NoWalk> pw;
+  if constexpr (CODES) {  // (see k_attn_q_direct)
+    int64_t lo = 0;       // WIN: the first key the sequence's first query row sees (kv_cache.hip: window_lo) - nothing below its page is read
+    if constexpr (WIN) lo = off - a.window + 1 > 0 ? off - a.window + 1 : 0;
+    pw = {kvc::slot_row(a.src, (int64_t)a.src.slots[b]), T, (int)(h / (a.heads / a.kv_heads)), (int)((T + 15) / 16), (int)(lo / 16), -1, -1, -1, -1};
+  }
   auto fetch_k = [&](int it) {
     Stage st;
-    const bf16_t* base = a.kimg + (z * a.Tp + (int64_t)it * BT) * a.Dp;
+    if constexpr (CODES) {
+      // unit tid < 64 DK: keys r0 and r0 + 8 of page pg of the tile, 16 d at dg - consecutive lanes, consecutive bytes of a key's row
+      const int dg = tid % (2 * DK), r0 = (tid / (2 * DK)) & 7, kb = 4 * it + tid / (16 * DK);
+      const bool mine = tid < 64 * DK && 16 * dg < a.D;
+      const auto entry = [&](int k) { return mine && k >= pw.blk0 && k < pw.nblk ? pw.row[k] : -1; };
+      const int32_t e = pw.ek_it == it ? pw.ek : entry(kb);  // (wave-uniform: a sweep's first tile and its last one's re-read alone ask now)
+      pw.ek = entry(kb + 4), pw.ek_it = it + 1;              // the next tile's entry: a round trip ahead of its codes
+      st.c[0] = st.c[1] = st.e = make_uint4(0, 0, 0, 0);
+      if (e >= 0) {
+        const int64_t blk = (int64_t)e * a.src.kvh + pw.g, t = 16 * (int64_t)kb + r0;
+        st.e = *(const uint4*)(a.src.ke + blk * a.D + 16 * dg);
+        if (t < pw.T) st.c[0] = kvc::load_codes16<false>(a.src.kc, blk, r0, a.D, dg);
+        if (t + 8 < pw.T) st.c[1] = kvc::load_codes16<false>(a.src.kc, blk, r0 + 8, a.D, dg);
+      }
+    } else {
+      const bf16_t* base = a.kimg + (z * a.Tp + (int64_t)it * BT) * a.Dp;
 #pragma unroll
-    for (int u = 0; u < DK; ++u) {
-      const int p = tid + 256 * u, row = p / (4 * DK), ch = p % (4 * DK);
-      st.r[u] = *(const uint4*)(base + (int64_t)row * a.Dp + ch * 8);
+      for (int u = 0; u < DK; ++u) {
+        const int p = tid + 256 * u, row = p / (4 * DK), ch = p % (4 * DK);
+        st.r[u] = *(const uint4*)(base + (int64_t)row * a.Dp + ch * 8);
+      }
     }
     return st;
   };
   auto put_k = [&](const Stage st) {
+    if constexpr (CODES) {
+      if (tid < 64 * DK) {
+        const int dg = tid % (2 * DK), row = 16 * (tid / (16 * DK)) + ((tid / (2 * DK)) & 7);
+        const uint32_t eb[4] = {st.e.x, st.e.y, st.e.z, st.e.w};
+        const bool sw = dg & 4;  // the upper four d blocks store their halves in the other order (bank argument: k_attn_q_direct)
 #pragma unroll
-    for (int u = 0; u < DK; ++u) {
-      const int p = tid + 256 * u, row = p / (4 * DK), ch = p % (4 * DK);
-      *(uint4*)(sK + row * KS + ch * 16) = st.r[u];
+        for (int j = 0; j < 2; ++j) {
+          uint32_t w[8];
+          kvc::codes16_to_bf16(st.c[j], eb, a.qk, w);
+          unsigned char* p = sK + (row + 8 * j) * KS + dg * 32;
+          // (selected dword by dword: a select between two uint4 objects went through scratch memory)
+          *(uint4*)(p + (sw ? 16 : 0)) = make_uint4(sw ? w[4] : w[0], sw ? w[5] : w[1], sw ? w[6] : w[2], sw ? w[7] : w[3]);
+          *(uint4*)(p + (sw ? 0 : 16)) = make_uint4(sw ? w[0] : w[4], sw ? w[1] : w[5], sw ? w[2] : w[6], sw ? w[3] : w[7]);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < DK; ++u) {
+        const int p = tid + 256 * u, row = p / (4 * DK), ch = p % (4 * DK);
+        *(uint4*)(sK + row * KS + ch * 16) = st.r[u];
+      }
     }
   };
   auto fetch_v = [&](int it) {
     Stage st;
-    const bf16_t* base = a.vimg + z * VD * a.Tv + (int64_t)it * BT;
+    if constexpr (CODES) {
+      // item tid < 32 DK: 16 d at db of the keys 4 tg .. 4 tg + 3 of the tile (one page) - 16 consecutive lanes, one db and 16 tg
+      const int tg = tid & 15, db = tid >> 4, kb = 4 * it + (tg >> 2);
+      const bool mine = tid < 32 * DK && 16 * db < a.D;
+      const auto entry = [&](int k) { return mine && k >= pw.blk0 && k < pw.nblk ? pw.row[k] : -1; };
+      const int32_t e = pw.ev_it == it ? pw.ev : entry(kb);
+      pw.ev = entry(kb + 4), pw.ev_it = it + 1;
+      st.c[0] = st.c[1] = st.c[2] = st.c[3] = st.e = make_uint4(0, 0, 0, 0);
+      const int64_t t = 64 * (int64_t)it + 4 * tg;
+      if (e >= 0 && t < pw.T) st.e.x = kvc::load_v4<false>(a.src, (int64_t)e * a.src.kvh + pw.g, t, pw.T, (int)a.D, db, st.c);
+    } else {
+      const bf16_t* base = a.vimg + z * VD * a.Tv + (int64_t)it * BT;
 #pragma unroll
-    for (int u = 0; u < DK; ++u) {
-      const int p = tid + 256 * u, row = p >> 3, ch = p & 7;
-      st.r[u] = *(const uint4*)(base + (int64_t)row * a.Tv + ch * 8);
+      for (int u = 0; u < DK; ++u) {
+        const int p = tid + 256 * u, row = p >> 3, ch = p & 7;
+        st.r[u] = *(const uint4*)(base + (int64_t)row * a.Tv + ch * 8);
+      }
     }
     return st;
   };
   auto put_v = [&](const Stage st) {
+    if constexpr (CODES) {
+      if (tid < 32 * DK) {
+        uint32_t w[4][8];
 #pragma unroll
-    for (int u = 0; u < DK; ++u) {
-      const int p = tid + 256 * u, row = p >> 3, ch = p & 7;
-      *(uint2*)(sV + row * VS + ch * 16) = make_uint2(st.r[u].x, st.r[u].y);
-      *(uint2*)(sV + row * VS + ch * 16 + 8) = make_uint2(st.r[u].z, st.r[u].w);
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t e = ((st.e.x >> (8 * r)) & 0xffu) * 0x01010101u;  // one exponent for the 16 d
+          const uint32_t eb[4] = {e, e, e, e};
+          kvc::codes16_to_bf16(st.c[r], eb, a.qv, w[r]);
+        }
+        unsigned char* row = sV + 16 * (tid >> 4) * VS + 8 * (tid & 15);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {  // d = 16 db + i: the four keys' bf16 as 8 bytes of its row
+          const int sh = 16 * (i & 1);
+          *(uint2*)(row + i * VS) = make_uint2(((w[0][i >> 1] >> sh) & 0xffffu) | (((w[1][i >> 1] >> sh) & 0xffffu) << 16),
+                                               ((w[2][i >> 1] >> sh) & 0xffffu) | (((w[3][i >> 1] >> sh) & 0xffffu) << 16));
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < DK; ++u) {
+        const int p = tid + 256 * u, row = p >> 3, ch = p & 7;
+        *(uint2*)(sV + row * VS + ch * 16) = make_uint2(st.r[u].x, st.r[u].y);
+        *(uint2*)(sV + row * VS + ch * 16 + 8) = make_uint2(st.r[u].z, st.r[u].w);
+      }
     }
   };
 
@@ -374,10 +473,45 @@ __global__ __launch_bounds__(64 * NW, 2) void k_attn_q_tree(const ArgsTree a) {
   attn_q_body<DT, DK, true, true, false, true>(a);
 }
 
+// CODES - the prefill kernel that reads the paged pool's codes in its key loop (lqer_attention_q_paged_direct): no image, no image
+// kernel, no workspace.  Everything from `scores` downward is the body's; the four tile lambdas have a second spelling that puts the
+// SAME bytes at the same places of sK and sV, from the pool's pages:
+//   K tile = 64 keys = 4 pages of the kv head.  A unit (tid < 64 DK; at D = 128 every thread has one) is 16 d (dg) of the keys r0 and
+//     r0 + 8 of one page: two 16-byte code loads and ONE load of the 16 exponent bytes of (page, dg) both keys share, dg fastest over
+//     the lanes - at D = 128 a wave reads 8 whole key rows, 1 KB contiguous.  put_k converts each key's 16 codes (codes16_to_bf16) to
+//     the 32 bytes the image row holds at d = 16 dg and stores them as two 16-byte halves at sK + key * KS + 32 dg.  Eight consecutive
+//     lanes (one key row at D = 128) would put the same half of dg and dg + 4 on the same four banks (32 dg bytes = 8 dg dwords: 0 and
+//     32); so lanes with dg >= 4 store the upper half first: the eight lanes' 16-byte stores then cover 32 different banks in either
+//     instruction (dg 0-3: dwords 8 dg + 0-3; dg 4-7: 8 dg + 4-7 = 4-7 mod 8 in the other octets).  At DK < 4 a row pitch of 36 or 52
+//     dwords moves the second key row of the eight lanes onto the banks the first leaves free.
+//   V tile: codes are [t][d], sV is [d][t].  An item (tid < 32 DK) is 16 d (db) of four consecutive keys 4 tg .. 4 tg + 3 - always one
+//     page: four code loads and one dword of exponents (load_v4, as k_kv_vimage) -, converted per key and stored, per d, as the four
+//     keys' bf16 in ONE 8-byte store at sV + (16 db + i) * VS + 8 tg.  VS = 136 bytes = 34 dwords, so 16 rows are 544 = 17 x 32 dwords:
+//     db does not move the bank at all, and k_kv_vimage's map (db = tid & 7) would put eight lanes on one bank pair (8-way).  The map
+//     here is tg = tid & 15, db = tid >> 4: the 16 lanes an 8-byte store is served for hold ONE db and the 16 tg - dwords 34 i + 2 tg +
+//     {0, 1}, the 32 banks once each; two such groups (db, db + 1) are 544 = 32 mod 64 apart, so 32 lanes on 64 banks do not meet
+//     either.  No rotation: the fragment reads of sweep 2 find every byte where the image route puts it.  The price is on the global
+//     side - a wave's load instruction touches 16 key rows x 64 bytes instead of 8 x 128 - and it is paid in L2: the other half of every line
+//     is the next four db's, lanes of the same or the next wave.
+//   Table entries: a unit / item lies in one page, so a thread reads ONE entry per tile and operand, and it reads it a tile early:
+//     fetch(it) takes the entry it requested in fetch(it - 1), issues the code loads, and requests the entry of tile it + 1 - the
+//     staged loads travel under a tile's work as the image loads do, not behind a table round trip.  Only a sweep's first tile (and the
+//     re-read past its end) waits for its entry.
+//   Bounds, by selection: no entry at or beyond ceil(T / 16) and (WIN) none below the page of window_lo is read, and no page behind
+//     one; such blocks, keys at and beyond T and d at and beyond D stay the zero codes the stage starts from - zero bf16 in LDS.
+// Resource usage (D = 128, the compiler's): DESIGN.md section 4.  The kernel is compiled without the packed fp32 forms (the target
+// attribute: qerr_mm.hip's flag for one kernel) - its fp32 arithmetic is the same operations, one lane at a time, the same bits.
+template <int DT, int DK, bool WIN, bool TREE>
+__global__ __launch_bounds__(64 * NW, 2) __attribute__((target("no-packed-fp32-ops"))) void k_attn_q_direct(const ArgsDirect a) {
+  attn_q_body<DT, DK, true, true, WIN, TREE, true>(a);
+}
+
 // The instantiations of the attention kernel that exist, stated once: the per-sequence query counts and the window run on the paged
-// forms (PSL), the tree rule on the form with per-sequence counts and no window
-template <bool PSL, bool RAG, bool WIN, bool TREE = false>
+// forms (PSL), the tree rule on the form with per-sequence counts and no window; the tiles come from the pool's codes (CODES) on the
+// three forms with per-sequence counts
+template <bool PSL, bool RAG, bool WIN, bool TREE = false, bool CODES = false>
 constexpr bool attn_variant_exists() {
+  if (CODES && !RAG) return false;
   if (TREE) return PSL && RAG && !WIN;
   return PSL || !(RAG || WIN);
 }
@@ -424,6 +558,29 @@ static int launch(const AttnCall& c, Args a) {
                                 : (c.packed ? "lqer_attention_q_kv" : "lqer_attention_q"));
 }
 
+// lqer_attention_q_paged_direct: one launch of k_attn_q_direct on the pool's codes - the grid of the ragged call, no image kernel
+template <int DT>
+static int launch_direct(const AttnCall& c, ArgsDirect a) {
+  a.qvec = al16(c.q, c.qs, DT == LQER_F32 ? 4 : 2);
+  const dim3 grid((unsigned)((a.S + BQ - 1) / BQ), (unsigned)a.heads, (unsigned)c.batch);
+  const int dk = (int)((a.D + 31) / 32);
+  with_flags(
+      [&](auto w, auto tr) {
+        if constexpr (attn_variant_exists<true, true, w, tr, true>()) {
+          const auto run = [&](auto k) { k_attn_q_direct<DT, k, w, tr><<<grid, 64 * NW, 0, c.st>>>(a); };
+          switch (dk) {
+            case 1: run(std::integral_constant<int, 1>{}); break;
+            case 2: run(std::integral_constant<int, 2>{}); break;
+            case 3: run(std::integral_constant<int, 3>{}); break;
+            default: run(std::integral_constant<int, 4>{}); break;
+          }
+        }
+        return 0;
+      },
+      c.windowed, c.treed);
+  return check_launch("lqer_attention_q_paged_direct");
+}
+
 }  // namespace attn
 
 static size_t attn_align(size_t v) { return (v + 255) / 256 * 256; }
@@ -437,27 +594,43 @@ size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, i
   return attn_align((size_t)(batch * kv_heads * Tp * Dp) * sizeof(bf16_t)) + attn_align((size_t)(batch * kv_heads * attn::VD * Tv) * sizeof(bf16_t));
 }
 
-// the two images at their places in the workspace - from the raw K and V (attn::launch) or from the codes of the packed KV cache or
-// of the paged pool (kv_cache.hip) - then k_attn_q on them
-int attention_q_dispatch(const AttnCall& c) {
-  attn::Args a;
+// what every record of the prefill kernel holds of a call, whatever its tiles come from
+static void attn_args(const AttnCall& c, attn::Args& a) {
   a.q = c.q, a.mask = c.mask, a.out = c.out, a.stats = c.row_stats;
   a.S = c.S, a.T = c.T, a.D = c.D;
-  attn_dims(c.T, c.D, &a.Tp, &a.Dp, &a.Tv);
-  a.kimg = (const bf16_t*)c.workspace;
-  a.vimg = (const bf16_t*)((const unsigned char*)c.workspace + attn_align((size_t)(c.batch * c.kv_heads * a.Tp * a.Dp) * sizeof(bf16_t)));
   a.q_bs = c.qs[0], a.q_hs = c.qs[1], a.q_rs = c.qs[2];
   a.m_bs = c.mask ? c.ms[0] : 0, a.m_hs = c.mask ? c.ms[1] : 0, a.m_rs = c.mask ? c.ms[2] : 0;
   a.o_bs = c.os[0], a.o_hs = c.os[1], a.o_rs = c.os[2];
   a.heads = (int)c.heads, a.kv_heads = (int)c.kv_heads, a.mode = c.causal ? 2 : (c.mask ? 1 : 0);
   a.scaling = c.scaling;
   a.q0 = make_qp(*c.q_fmt), a.q1 = make_qp(*c.p_fmt);
-  a.qvec = a.mvec = false;  // (attn::launch sets them)
+  a.qvec = a.mvec = false;  // (the launch sets them)
   a.lens = c.paged ? c.pool.lens : nullptr;  // (paged: c.T is the bound max_len - the images' strides; the kernels take T from lens[b])
   a.q_starts = c.paged && c.pool.ragged ? c.pool.starts : nullptr;  // (ragged: c.S is the bound max_s, qs / os hold {0, head, token})
   a.window = c.paged && c.windowed ? c.window : 0;
+}
+
+// the two images at their places in the workspace - from the raw K and V (attn::launch) or from the codes of the packed KV cache or
+// of the paged pool (kv_cache.hip) - then k_attn_q on them
+int attention_q_dispatch(const AttnCall& c) {
+  attn::Args a;
+  attn_args(c, a);
+  attn_dims(c.T, c.D, &a.Tp, &a.Dp, &a.Tv);
+  a.kimg = (const bf16_t*)c.workspace;
+  a.vimg = (const bf16_t*)((const unsigned char*)c.workspace + attn_align((size_t)(c.batch * c.kv_heads * a.Tp * a.Dp) * sizeof(bf16_t)));
   if (c.packed) kv_cache_images_dispatch(c, (bf16_t*)a.kimg, a.Tp, a.Dp, (bf16_t*)a.vimg, a.Tv);
   return with_dtype(c.dtype, [&](auto dt) { return attn::launch<decltype(dt)::value>(c, a); });
+}
+
+// the pool's codes as they are (c.paged with pool.ragged, byte codes: the entry's check), k_attn_q_direct on them: no workspace
+int attention_q_direct_dispatch(const AttnCall& c) {
+  attn::ArgsDirect a;
+  attn_args(c, a);
+  a.kimg = a.vimg = nullptr, a.Tp = a.Dp = a.Tv = 0;
+  a.tree = c.treed ? c.tree : nullptr;
+  a.src = kvc::src_of(c.pool);
+  a.qk = make_qp(*c.k_fmt), a.qv = make_qp(*c.v_fmt);
+  return with_dtype(c.dtype, [&](auto dt) { return attn::launch_direct<decltype(dt)::value>(c, a); });
 }
 
 }  // namespace lqer

@@ -983,6 +983,7 @@ __host__ inline bool al16(const void* p, const int64_t* s, int esz) {
 }
 size_t attention_q_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t T, int64_t D);  // attn_q.hip
 int attention_q_dispatch(const AttnCall& c);  // (with a cache or a pool: kv_cache.hip writes the two images from the codes, k_attn_q runs on them)
+int attention_q_direct_dispatch(const AttnCall& c);  // (a pool with per-sequence counts and byte codes: k_attn_q_direct reads its pages, no workspace)
 // attn_decode.hip: the same attention for 1 <= S <= attention_q_decode_max_s() query rows, split over the keys
 int attention_q_decode_max_s();
 int attention_q_decode_chunk(int64_t T, int64_t D);  // keys per chunk of a sequence of T keys

@@ -1167,6 +1167,8 @@ RAGGED_PREFILL, RAGGED_DECODE = "lqer_attention_q_paged_ragged", "lqer_attention
 TREE_PREFILL, TREE_DECODE = "lqer_attention_q_paged_tree", "lqer_attention_q_decode_paged_tree"
 _SIBLING = {TREE_PREFILL: RAGGED_PREFILL, TREE_DECODE: RAGGED_DECODE}  # whose workspace a tree entry has
 TREE_MAX_NODES = 64  # a row's mask is one 64-bit word
+# the prefill kernel that reads the pool's codes in its key loop: one entry for the causal rule, the window and the tree, no workspace
+KERNEL_DIRECT, DIRECT = "direct", "lqer_attention_q_paged_direct"
 
 
 def _window_arg(who, window, default, causal):
@@ -1217,7 +1219,7 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
     (out: any strides over b, h, S), RAGGED_* / TREE_* on q / out [sum(counts), h, d] (any token and head strides) with `counts` query
     rows per sequence -, stats fp32 dense or None, for the sequences in `slots` with `lens` keys.  `window`: None or W - the entry is
     then `base`_window, but for RAGGED_DECODE, which always takes one (0: none).  `tree` (TREE_* alone, which take no window): the
-    rows' masks, int64 [sum(counts)] on the device, in the last place.  `groups` (PAGED_DECODE without a window only): the call's
+    rows' masks, int64 [sum(counts)] on the device, in the last place.  DIRECT takes both, each in its place (0 / NULL: none).  `groups` (PAGED_DECODE without a window only): the call's
     prefix groups (PageTable.prefix_groups) - with a group of two or more the entry is SHARED_DECODE, `base`'s list plus the group
     arrays; with none, without any such group, or on a cache with nibble codes (the grouped kernels are not instantiated for them; the
     bits are the same), `base`.  The workspace and the stream come as values, so nothing
@@ -1230,6 +1232,8 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
             *((cache._call_starts(counts), max(counts), q.shape[0]) if ragged else (S,)), d,
             *((_pair(q), _pair(out)) if ragged else (_tri(q), _tri(out))), float(scaling), int(bool(causal)),
             C.byref(f[0]), C.byref(f[1]), C.byref(f[2]), C.byref(f[3]), ws_ptr, ws_bytes, stream)
+    if base == DIRECT:
+        return base, args + (0 if window is None else min(window, 1 << 62), None if tree is None else tree.data_ptr())
     if base in _SIBLING:
         if tree is None or window is not None:
             raise ValueError(f"{base} with tree={tree!r}, window={window} - a tree entry takes the rows' masks and no window")
@@ -1247,9 +1251,14 @@ def _paged_args(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, 
 def _paged_call(base, q, out, stats, cache: PagedKVCache, slots, lens, scaling, causal, ws, window, S=None, counts=None, groups=None,
                 tree=None) -> None:
     """The library call _paged_args describes; ws: a uint8 workspace, or None for the stream's at the size `base`_workspace_bytes asks
-    (a *_window entry and a TREE_* entry have their sibling's)."""
+    (a *_window entry and a TREE_* entry have their sibling's; DIRECT has none: NULL and 0 bytes)."""
     L = _lib.lib()
     with torch.cuda.device(q.device):
+        if ws is None and base == DIRECT:
+            name, args = _paged_args(base, q, out, stats, cache, slots, lens, scaling, causal, window, None, 0, ops._stream(q.device), S, counts, groups,
+                                     tree)
+            _lib.check(getattr(L, name)(*args), name)
+            return
         if ws is None:
             h, d = q.shape[1], q.shape[-1]
             max_len = _paged_max_len(base, cache, lens)
@@ -1329,7 +1338,7 @@ def _ragged_plan(counts, kernel, names=(RAGGED_DECODE, RAGGED_PREFILL)):
     """The library calls of attention_flexible_paged_ragged (`names`: of attention_flexible_paged_tree) for these counts, host
     arithmetic only: [(name, the indices of the call's sequences, the slice of q's rows they own - None when their rows are not one
     range and are gathered)].  kernel="auto": all sequences of up to 8 rows in one call of the decode entry names[0], all others in
-    one call of the prefill entry names[1]; "prefill": all in the latter.  Returns the plan and the first row of every sequence."""
+    one call of the prefill entry names[1]; "prefill" and "direct": all in the latter.  Returns the plan and the first row of every sequence."""
     starts = [0]  # the first row of every sequence
     for c in counts[:-1]:
         starts.append(starts[-1] + c)
@@ -1360,6 +1369,9 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     first and the chunks last, say - takes them as a view and writes its rows of the output in place; the rows of a call that another
     call's rows lie between are gathered and scattered by index on the device, once.  attention_flexible_paged_ragged.plan(cache,
     seqs, counts, kernel, window) names the calls without touching a device.
+    kernel="direct": the whole batch, counts of 1 .. 8 included, in ONE lqer_attention_q_paged_direct call - the prefill kernel reading
+    the pool's codes inside its key loop: no bf16 image, one launch, no workspace, and the bits of kernel="prefill".  Byte pools only
+    (ValueError on a code_bits=4 pool); the window rule and its refusals are the prefill call's.
     `window` (default: the cache's) and every refusal are those of the route a sequence takes, in its words: the decode route has the
     window rule; the prefill call runs unwindowed while every length it addresses is <= W and, beyond, as
     lqer_attention_q_paged_ragged_window on a cache made with max_query_rows (ValueError on any other, and for a sequence whose count
@@ -1367,14 +1379,13 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
     is launched: len(counts) != len(seqs), a negative count, sum(counts) != q.shape[0], causal with counts[b] > length_b, an empty
     sequence with a count, an unknown or repeated sequence, a wrong dtype, device or head count.  ws: a uint8 workspace or None."""
     who = "attention_flexible_paged_ragged"
-    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
-        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    prefill = _direct_or_prefill(who, cache, kernel, RAGGED_PREFILL)
     eff_window = _window_arg(who, window, cache.window, causal)
     seqs, counts = _ragged_counts(who, seqs, counts)
     slots, lens = _ragged_operands(who, q, cache, seqs, counts, causal)
-    plan, starts = _ragged_plan(counts, kernel)
+    plan, starts = _ragged_plan(counts, kernel, (RAGGED_DECODE, prefill))
     live = [b for _, bs, _ in plan for b in bs]
-    big = [bs for name, bs, _ in plan if name == RAGGED_PREFILL]
+    big = [bs for name, bs, _ in plan if name == prefill]
     big = big[0] if big else []
     _released_below(who, cache, (slots[b] for b in live), eff_window)
     big_lens, big_window = [lens[b] for b in big], None
@@ -1382,8 +1393,19 @@ def attention_flexible_paged_ragged(q, cache: PagedKVCache, seqs, counts, scalin
         big_window = _prefill_window(who, cache, [seqs[b] for b in big], [slots[b] for b in big], big_lens, [counts[b] for b in big], eff_window)
     if big and (max(big_lens) > _ATTN_MAX_T or len(big) * cache.kv_heads > _MAX_GRID_Z):
         raise ValueError(f"{who}: {len(big)} sequences of lengths {big_lens} beyond the prefill kernel's launch grid")
-    windows = {RAGGED_DECODE: eff_window, RAGGED_PREFILL: big_window}  # (the prefill call while every length <= W: plain causal)
+    windows = {RAGGED_DECODE: eff_window, prefill: big_window}  # (the prefill call while every length <= W: plain causal)
     return _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, causal, return_stats, ws, windows)
+
+
+def _direct_or_prefill(who, cache, kernel, prefill):
+    """The entry the sequences of more than 8 rows take under `kernel` - "prefill" and "auto": `prefill`; "direct": DIRECT, on a pool
+    with byte codes -, or ValueError."""
+    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO, KERNEL_DIRECT):
+        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill', 'auto' or 'direct'")
+    if kernel == KERNEL_DIRECT and cache.nibble:
+        raise ValueError(f"{who}: kernel='direct' on a pool with code_bits=4 - the kernel that reads the pool's codes in its key loop is "
+                         "not instantiated for nibble codes; kernel='prefill' gives the same bits")
+    return DIRECT if kernel == KERNEL_DIRECT else prefill
 
 
 def _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, causal, return_stats, ws, windows, tree=None):
@@ -1432,23 +1454,23 @@ def _plan(cache: PagedKVCache, seqs, counts, kernel=KERNEL_AUTO, window=None) ->
     only on a cache made with max_query_rows, and only when a length it addresses - read from the host's books, which then must know
     `seqs` - lies beyond the window: it is then lqer_attention_q_paged_ragged_window, by the function's own rule (_prefill_window),
     its refusal of a count that reaches below the pages a sequence still holds included.  On any other cache no length is read.  Each
-    call is three launches.  Refuses an unknown `kernel`, a bad `window` and bad counts as the function does."""
+    call is three launches - but lqer_attention_q_paged_direct (kernel="direct": one call for all sequences), which is one and takes
+    its rule as an argument, not in its name.  Refuses an unknown `kernel`, a bad `window` and bad counts as the function does."""
     who = "attention_flexible_paged_ragged"
-    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
-        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    prefill = _direct_or_prefill(who, cache, kernel, RAGGED_PREFILL)
     eff_window = _window_arg(who, window, cache.window, True)
     seqs, counts = _ragged_counts(who, seqs, counts)
     out = []
-    for name, bs, at in _ragged_plan(counts, kernel)[0]:
+    for name, bs, at in _ragged_plan(counts, kernel, (RAGGED_DECODE, prefill))[0]:
         win = eff_window if name == RAGGED_DECODE else None
-        if name == RAGGED_PREFILL and eff_window is not None and cache.max_query_rows is not None:
+        if name == prefill and eff_window is not None and cache.max_query_rows is not None:
             mine = [seqs[b] for b in bs]
             try:
                 slots = cache.pt.slots(mine)
             except KeyError as e:
                 raise ValueError(e.args[0]) from None
             win = _prefill_window(who, cache, mine, slots, [cache.pt.lengths[x] for x in slots], [counts[b] for b in bs], eff_window)
-            name += "_window" if win is not None else ""
+            name += "_window" if win is not None and name != DIRECT else ""
         out.append({"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered", "window": win})
     return out
 
@@ -1476,9 +1498,9 @@ def tree_masks(parents) -> list:
 
 
 def _tree_operands(who, cache, seqs, parents, kernel):
-    """What attention_flexible_paged_tree and its .plan ask of the host arguments alone: (seqs, counts, every row's mask), or ValueError."""
-    if kernel not in (KERNEL_PREFILL, KERNEL_AUTO):
-        raise ValueError(f"{who}: kernel={kernel!r} - 'prefill' or 'auto'")
+    """What attention_flexible_paged_tree and its .plan ask of the host arguments alone: (seqs, counts, every row's mask, the entry of
+    the trees of more than 8 nodes), or ValueError."""
+    prefill = _direct_or_prefill(who, cache, kernel, TREE_PREFILL)
     if cache.window is not None:
         raise ValueError(f"{who}: a cache made with window={cache.window} - a tree row's position is its depth, not its index, so the "
                          "window rule is undefined on a draft tree")
@@ -1493,7 +1515,7 @@ def _tree_operands(who, cache, seqs, parents, kernel):
         masks = [m for p in parents for m in tree_masks(p)]
     except ValueError as e:
         raise ValueError(f"{who}: {e.args[0]}") from None
-    return seqs, [len(p) for p in parents], masks
+    return seqs, [len(p) for p in parents], masks, prefill
 
 
 @torch.no_grad()
@@ -1505,7 +1527,8 @@ def attention_flexible_paged_tree(q, cache: PagedKVCache, seqs, parents, scaling
     counts[b] = len(parents[b]).  Node i sees the committed context - every key before the draft - and, of the draft, itself and its
     ancestors.  The output has q's shape, the statistics are [sum(counts), h, 2].  A count of 0 leaves its sequence out.
     kernel="auto" (the default): ALL sequences of up to 8 nodes go through ONE lqer_attention_q_decode_paged_tree call, those of 9 ..
-    64 nodes through ONE lqer_attention_q_paged_tree call; "prefill": all through the latter.  Rows are taken as views or gathered as
+    64 nodes through ONE lqer_attention_q_paged_tree call; "prefill": all through the latter; "direct": all through ONE
+    lqer_attention_q_paged_direct call - the prefill kernel on the pool's codes, no image and no workspace, the same bits.  Rows are taken as views or gathered as
     attention_flexible_paged_ragged takes them (one body).  The masks go to the device in one copy per call.  Every sequence gets the
     bits of attention_flexible(q_b, K_b, V_b, ..., attention_mask=M, kernel="decode" / "prefill") on its raw K and V - the context
     plus ALL its draft nodes - with M = 0 where visible and torch.finfo(dtype).min elsewhere.  Sibling nodes share K quantizer blocks
@@ -1515,15 +1538,15 @@ def attention_flexible_paged_tree(q, cache: PagedKVCache, seqs, parents, scaling
     ValueError before anything is launched: what attention_flexible_paged_ragged refuses, in its words (a node count above the
     sequence's length among them), more than 64 nodes, a bad parents list, a cache made with window=.  ws: a uint8 workspace or None."""
     who = "attention_flexible_paged_tree"
-    seqs, counts, masks = _tree_operands(who, cache, seqs, parents, kernel)
+    seqs, counts, masks, prefill = _tree_operands(who, cache, seqs, parents, kernel)
     slots, lens = _ragged_operands(who, q, cache, seqs, counts, True)
-    plan, starts = _ragged_plan(counts, kernel, (TREE_DECODE, TREE_PREFILL))
+    plan, starts = _ragged_plan(counts, kernel, (TREE_DECODE, prefill))
     for name, bs, _ in plan:
-        if name == TREE_PREFILL and (max(lens[b] for b in bs) > _ATTN_MAX_T or len(bs) * cache.kv_heads > _MAX_GRID_Z):
+        if name == prefill and (max(lens[b] for b in bs) > _ATTN_MAX_T or len(bs) * cache.kv_heads > _MAX_GRID_Z):
             raise ValueError(f"{who}: {len(bs)} sequences of lengths {[lens[b] for b in bs]} beyond the prefill kernel's launch grid")
     # (int64 holds the 64 bits: bit 63 - row 63's own - is the sign)
     tree = torch.tensor([m - (1 << 64) if m >> 63 else m for m in masks], dtype=torch.int64).to(q.device)
-    return _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, True, return_stats, ws, {TREE_DECODE: None, TREE_PREFILL: None}, tree)
+    return _ragged_calls(q, cache, slots, lens, counts, plan, starts, scaling, True, return_stats, ws, {TREE_DECODE: None, prefill: None}, tree)
 
 
 def _tree_plan(cache: PagedKVCache, seqs, parents, kernel=KERNEL_AUTO) -> list:
@@ -1531,9 +1554,9 @@ def _tree_plan(cache: PagedKVCache, seqs, parents, kernel=KERNEL_AUTO) -> list:
     alone (no device is touched, no length is read): one dict per call - "call": the C entry, "seqs": the indices into `seqs` of the
     sequences it takes, "rows": "view" or "gathered" (attention_flexible_paged_ragged.plan's words).  Each call is three launches.
     Refuses an unknown `kernel`, bad parents and a cache with a window as the function does."""
-    seqs, counts, _ = _tree_operands("attention_flexible_paged_tree", cache, seqs, parents, kernel)
+    seqs, counts, _, prefill = _tree_operands("attention_flexible_paged_tree", cache, seqs, parents, kernel)
     return [{"call": name, "seqs": bs, "rows": "view" if at is not None else "gathered"}
-            for name, bs, at in _ragged_plan(counts, kernel, (TREE_DECODE, TREE_PREFILL))[0]]
+            for name, bs, at in _ragged_plan(counts, kernel, (TREE_DECODE, prefill))[0]]
 
 
 attention_flexible_paged_tree.plan = _tree_plan
