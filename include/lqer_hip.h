@@ -508,6 +508,36 @@ size_t lqer_a_f16_image_bytes(int64_t K, int64_t r);
 size_t lqer_a_b16_image_bytes(int64_t K, int64_t r);
 int lqer_a_b16_prepare(const void* a_t_limbs, int64_t K, int64_t r, void* out, void* stream);
 
+/* ---- gated MLP: the activation in front of a down projection inside its activation side (additive to ABI 14) -------------------
+ * down_proj(act_fn(gate_proj(x)) * up_proj(x)) (reference models/llama_decoder.py:176) and fc2(relu(fc1(x))) (opt_decoder.py): instead
+ * of an x tensor the call takes `gate` and `up` [M, K] (fp16 or bf16, row strides ld_gate / ld_up elements - the two halves of one
+ * [M, 2K] tensor work) and forms, element by element in registers,
+ *     s = round_dt(g / (1 + exp(-g)))   in fp32, full-precision expf, a true division   (LQER_ACT_RELU: s = max(g, 0), exact)
+ *     h = round_dt(float(s) * float(u))                                                  (up == NULL: h = s)
+ * - the two roundings eager F.silu(g) * u performs in dt; against torch's own GPU silu only the last bit of s can differ, on elements
+ * that sit on a rounding boundary of dt.  h then goes where x would go: x_quantizer -> the bf16 activation image xq
+ * [lqer_padded_m(M)][lqer_padded_k(K)] (rows < M written), h_q A on the MFMA and A_out_quantizer -> xaq [lqer_padded_m(M)][padded rank]
+ * (linear.py:154-156) - ONE launch (csrc/act_gated.hip) for every M >= 1, no scratch, bit-stable from run to run.  h never reaches
+ * memory.  a_t is the image of lqer_a_b16_prepare and a_limbs must be -2; rank 0 writes the image alone (a_t, xaq unused).
+ * LQER_E_INVALID: a null desc / gate / xq (or a_t / xaq with rank > 0), M < 0, ld_gate or ld_up < K, an unknown act, a_limbs != -2.
+ * LQER_E_UNSUPPORTED, nothing launched, the reason in lqer_last_error(): fp32 tensors; an x_quantizer that is not block_fp in blocks
+ * of 16; K % 16 != 0; pointers or row strides not 16-byte aligned; a padded rank other than 16 / 32 / 64; an A_out_quantizer that is
+ * not block_fp with blocks of 4..64 columns dividing the padded rank (or one block per row); weights of 5..8 bits (their activation
+ * image is three copies side by side). */
+#define LQER_ACT_SILU 0
+#define LQER_ACT_RELU 1
+int lqer_quantize_act_xa_gated(const lqer_linear_desc_t* desc, const void* gate, const void* up, int act, int dtype, int64_t M,
+                               int64_t ld_gate, int64_t ld_up, const void* a_t, int a_limbs, void* xq_bf16, void* xaq_bf16,
+                               void* stream);
+/* The forward of the down projection on (gate, up): the call above, then lqer_linear_gemm on the image and xaq - two launches (three
+ * with the pre-pass of B_out blocks other than 16 columns), the workspace carved as lqer_linear_forward carves it
+ * (lqer_linear_sizes(...).workspace for m_max >= M).  y [M, N] has the dtype of gate / up.  Refused as the call above and as
+ * lqer_linear_gemm. */
+int lqer_linear_forward_gated(const lqer_linear_desc_t* desc, const void* gate, const void* up, int act, int dtype, int64_t M,
+                              int64_t ld_gate, int64_t ld_up, const void* w_packed, const void* a_t, const void* b_t, int a_limbs,
+                              int b_limbs, const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* ---- weights of 5..8 bits (the reference's no-LQER baseline: W8A8 block_fp with one block per row and per token,
  * experiments/pipeline/sweep_baseline_no_lqer.sh:73-76, through LinearFlexible, quantized_layers/linear.py:50-64) ---------------
  * The packed image holds 4-bit codes, so a mantissa m of up to 8 bits (|m| <= 127) travels as three signed base-8 digits,

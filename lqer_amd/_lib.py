@@ -22,6 +22,7 @@ NARROW_DIRECT, NARROW_DIRECT_ONE_LAUNCH, NARROW_WIDEN = 1, 2, 3  # lqer_weight_n
 TUNE_TILE_ROWS_128, TUNE_TILE_ROWS_64, TUNE_DECODE_NO_POLL = 0x1, 0x2, 0x10000
 TUNE_I8_ROWS_128, TUNE_I8_ROWS_256, TUNE_AMAX_ATOMIC, TUNE_AMAX_PARTS = 0x4, 0x8, 0x40000, 0x80000
 TUNE_ACT16_SPLIT, TUNE_ACT16_FUSED = 0x800000, 0x1000000  # block-16 MXINT activation side: two launches / the one-launch kernel at every M
+ACT_SILU, ACT_RELU = 0, 1  # `act` of the gated-MLP entries (lqer_quantize_act_xa_gated, lqer_linear_forward_gated)
 TUNE_ACT8_SPLIT, TUNE_ACT8_FUSED = 0x200000, 0x400000  # int8 route's activation side: three launches / the one-launch kernel at every M
 TUNE_AMAX_NO_MRX = 0x4000000  # int8 route over several rounds of 128-row tiles: the k_bout_amax pre-pass launch instead of the in-GEMM items
 TUNE_BOUT_IN_PROLOGUE = 0x2000000  # 128-row tile kernel: the B_out re-quantization in front of the main loop (rounds 1-5) instead of under it
@@ -130,6 +131,10 @@ SIGNATURES = {
     "lqer_a_f16_image_bytes": (C.c_size_t, [_i64, _i64]),
     "lqer_a_b16_image_bytes": (C.c_size_t, [_i64, _i64]),
     "lqer_a_b16_prepare": (_i, [_vp, _i64, _i64, _vp, _vp]),
+    # gated MLP (csrc/act_gated.hip): desc, gate, up or none, act, dtype, M, ld_gate, ld_up, then lqer_quantize_act_xa's operands without
+    # the scratch / lqer_linear_forward's operands
+    "lqer_quantize_act_xa_gated": (_i, [_dp, _vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
+    "lqer_linear_forward_gated": (_i, [_dp, _vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
     "lqer_i8_prepare": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),
     "lqer_unpack_weight_i8": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "lqer_unpack_weight_i8_fmt": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),

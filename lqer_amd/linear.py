@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 from copy import deepcopy
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -30,6 +31,7 @@ from ._lib import LinearDesc, QFmt, check
 
 _SIG_BITS = {torch.float32: 24, torch.float16: 11, torch.bfloat16: 8}  # significand bits incl. the hidden one
 _NDEV = []
+_GATED_ACTS = {"silu": _lib.ACT_SILU, "relu": _lib.ACT_RELU}  # forward_gated's `act` -> LQER_ACT_*
 
 
 def _device_count() -> int:
@@ -607,6 +609,76 @@ class _LinearBase(nn.Linear):
         if "a_t_b16" in p and M > 64 and not self._x_i8:
             return p["a_t_b16"].data_ptr(), -2
         return a_t, a_limbs
+
+    # -- gated MLP ----------------------------------------------------------------------------
+    # Token counts from which forward_gated takes the fused entry.  tools/gated_mlp_bench.py at the Llama-7B down projection
+    # (profiles/gated_mlp.json, DESIGN.md "Gated MLP"): 0.93x the time of torch silu + mul + forward at M = 2048, but 1.18x / 1.95x / 1.41x at
+    # M = 1 / 8 / 64, where one workgroup per 8 token rows leaves the kernel compute-bound on a few CUs - below 2048 tokens h is formed by
+    # torch and forward() runs as before
+    gated_min_m = 2048
+
+    def forward_gated(self, gate: torch.Tensor, up: Optional[torch.Tensor] = None, act: str = "silu") -> torch.Tensor:
+        """This Linear on h = act(gate) * up (up = None: h = act(gate)) - Llama / Mistral's down_proj(silu(gate_proj(x)) * up_proj(x)),
+        OPT's fc2(relu(fc1(x))) - with h formed inside the activation-side kernel (csrc/act_gated.hip through lqer_linear_forward_gated:
+        two launches, h never written) where that kernel applies: fp16 / bf16 tensors, block-16 MXINT x_quantizer, an A of one bf16 limb
+        with padded rank 16 / 32 / 64, the standard weight image.  Elsewhere h is computed with torch and handed to forward().  `gate`
+        and `up` may be the two halves of one [..., 2 K] tensor.  The result is forward(F.silu(gate) * up) up to the last bit of silu on
+        elements that sit on a rounding boundary of the dtype, and the side product's fp32 summation order."""
+        code = _GATED_ACTS.get(act)
+        if code is None:
+            raise ValueError(f"forward_gated: act must be one of {sorted(_GATED_ACTS)}, got {act!r}")
+        if up is not None and (up.shape != gate.shape or up.dtype != gate.dtype or up.device != gate.device):
+            raise RuntimeError(f"forward_gated: gate {tuple(gate.shape)} {gate.dtype} and up {tuple(up.shape)} {up.dtype} differ")
+        if gate.shape[-1] != self.in_features:
+            raise RuntimeError(f"expected last dim {self.in_features}, got {tuple(gate.shape)}")
+        if self.is_ptq and gate.is_cuda and gate.dtype in (torch.float16, torch.bfloat16) and not (self._tiles and self._needs_tiles(gate)):
+            if _device_count() > 1 and gate.device.index != torch.cuda.current_device():
+                with torch.cuda.device(gate.device):
+                    y = self._forward_gated_hip(gate, up, code)
+            else:
+                y = self._forward_gated_hip(gate, up, code)
+            if y is not None:
+                return y
+        h = torch.nn.functional.silu(gate) if act == "silu" else torch.relu(gate)
+        return _LinearBase.forward(self, h if up is None else h * up)
+
+    def _forward_gated_hip(self, gate: torch.Tensor, up: Optional[torch.Tensor], code: int) -> Optional[torch.Tensor]:
+        """The fused entry, or None where the kernel does not serve this module / these tensors (the caller computes h with torch)."""
+        self._written_in_place()
+        if self._packed is None or self.w_is_quantized is False:
+            self._pack()
+        p, K, N = self._packed, self.in_features, self.out_features
+        M = gate.numel() // K
+        if ("a_t_b16" not in p or self._weight_image == "narrow" or ops.w_limbs(self._fmt["w"]) != 1 or K % 16 or M < self.gated_min_m):
+            return None
+
+        def rows(t):  # [M, K] with unit column stride, 16-byte aligned rows
+            t = t.reshape(-1, K)
+            if t.stride(-1) != 1 or t.data_ptr() % 16 or (M > 1 and (t.stride(0) < K or t.stride(0) % 8)):
+                t = t.contiguous()
+            return t
+
+        g2 = rows(gate)
+        u2 = None if up is None else rows(up)
+        y = torch.empty(M, N, dtype=gate.dtype, device=gate.device)
+        key = ("gated", M, gate.dtype, self.tuning)
+        ent = self._fw_cache.get(key)
+        if ent is None:
+            desc = self._desc()
+            if len(self._fw_cache) > 64:
+                self._fw_cache = {}
+            ent = self._fw_cache[key] = (desc, ops.linear_sizes(desc, M).workspace, ops.dtype_code(g2),
+                                         (p["w"].data_ptr(), p["a_t_b16"].data_ptr(), ops._ptr(p.get("b_t")), -2, p.get("b_limbs", 0),
+                                          ops._ptr(p.get("bias"))))
+        desc, ws_bytes, dt, consts = ent
+        st = ops._stream(gate.device)
+        ws = ops.workspace_on(gate.device, st, ws_bytes)
+        rc = _lib.lib().lqer_linear_forward_gated(C.byref(desc), g2.data_ptr(), None if u2 is None else u2.data_ptr(), code, dt, M,
+                                                  g2.stride(0) if M > 1 else K, K if (u2 is None or M == 1) else u2.stride(0), *consts,
+                                                  y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        if rc:
+            check(rc, "lqer_linear_forward_gated")
+        return y.reshape(*gate.shape[:-1], N)
 
     def __repr__(self):
         return "{}(in_features={}, out_features={}, bias={}, is_ptq={}, rank={}, backend=hip/gfx950{})".format(

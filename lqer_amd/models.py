@@ -55,13 +55,50 @@ def _layer_cfg(cfg: Optional[dict], layer_id: int, group: str, name: str) -> Opt
 _SHARED_INPUTS = {"self_attn": (("q_proj", "k_proj", "v_proj"),), "mlp": (("gate_proj", "up_proj"),)}
 
 
+class _ActInFront(LinearFlexibleLqer):
+    """OPT's fc2 under fuse_mlp: the layer's activation_fn is an identity and this Linear applies relu inside its activation side."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.forward_gated(x, None, "relu")
+
+
+def _gated_mlp_forward(self, x):
+    return self.down_proj.forward_gated(self.gate_proj(x), self.up_proj(x), self._lqer_act)
+
+
+_FUSED_MLP_CLS: Dict[type, type] = {}
+
+
+def _fuse_mlp(model: nn.Module, layer: nn.Module, table: dict) -> None:
+    """One decoder layer's MLP -> gate / up through their projections, then down_proj.forward_gated(g, u) (Llama-like: the mlp's class
+    becomes a subclass whose forward is that statement - no module is added, state-dict keys stay, deep copies keep working);
+    OPT: activation_fn becomes an identity and fc2 applies the relu itself."""
+    llama = table is _LLAMA_LIKE
+    act = getattr(model.config, "hidden_act" if llama else "activation_function", None)
+    if act not in (("silu", "relu") if llama else ("relu",)):
+        raise NotImplementedError(f"fuse_mlp: activation {act!r} is not served by forward_gated ({'silu, relu' if llama else 'relu'})")
+    if llama:
+        mlp = layer.mlp
+        if not isinstance(mlp.down_proj, LinearFlexibleLqer):  # (a per-layer override to a plain LinearFlexible: left as it is)
+            return
+        cls = type(mlp)
+        if cls not in _FUSED_MLP_CLS:
+            _FUSED_MLP_CLS[cls] = type("Gated" + cls.__name__, (cls,), {"forward": _gated_mlp_forward})
+        mlp._lqer_act = act
+        mlp.__class__ = _FUSED_MLP_CLS[cls]
+    elif type(layer.fc2) is LinearFlexibleLqer:
+        layer.fc2.__class__ = _ActInFront
+        layer.activation_fn = nn.Identity()
+
+
 def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], share_inputs: bool = True,
-                   weight_image: str = "standard") -> nn.Module:
+                   weight_image: str = "standard", fuse_mlp: bool = False) -> nn.Module:
     """Replace the projections of every decoder layer in place; weights are carried over.  share_inputs: projections
     fed by the same tensor quantize it once and share one side GEMM (linear.SharedActivation); per-projection results
     are unchanged up to the fp32 summation order of the side product.  weight_image: "narrow" makes every projection keep the
     compact image of its 2- / 3-bit block_fp weight (linear._LinearBase.weight_image; a projection it does not serve raises when
-    it packs)."""
+    it packs).  fuse_mlp: the activation between the MLP's projections runs inside the down projection's activation-side kernel
+    (linear._LinearBase.forward_gated: silu(gate) * up for Llama-like layers, relu for OPT's fc2) instead of as torch launches."""
     layers, table = _decoder_layers(model)
     for layer_id, layer in enumerate(layers):
         for group, names in table.items():
@@ -83,6 +120,8 @@ def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], s
                     mods = [getattr(parent, n, None) for n in names2]
                     if all(isinstance(m, LinearFlexibleLqer) for m in mods):
                         SharedActivation(mods)
+        if fuse_mlp:
+            _fuse_mlp(model, layer, table)
     return model
 
 
