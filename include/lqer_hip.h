@@ -538,6 +538,36 @@ int lqer_linear_forward_gated(const lqer_linear_desc_t* desc, const void* gate, 
                               int b_limbs, const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ---- fused RMSNorm: the norm in front of q/k/v and gate/up inside their activation side (additive to ABI 14) ---------------------
+ * Llama / Mistral run input_layernorm in front of q/k/v and post_attention_layernorm in front of gate/up.  Instead of the normalised x
+ * the call takes the RAW hidden state h [M, K] (fp16 or bf16, row stride ld_h elements), the norm weight w [K] of the same dtype and
+ * eps, and forms per token row, in registers, HF LlamaRMSNorm with its two roundings in the tensor dtype dt:
+ *     S    = sum_k float(h_k)^2                    in fp32
+ *     rstd = 1.0f / sqrtf(S / (float)K + eps)      correctly rounded IEEE division and square root
+ *     n_k  = round_dt(float(h_k) * rstd)
+ *     x_k  = round_dt(float(w_k) * float(n_k))     (the product of two dt values is exact in fp32)
+ * Summation order of S: a lane adds the squares of its 8 consecutive elements in ascending k, 512-k slab s of the row belongs to wave
+ * s % 8 (a wave adds its slabs in ascending k), the 64 lanes of a wave meet in an xor tree over lane distances 32, 16, 8, 4, 2, 1, the
+ * eight wave sums are added in wave order: one order whatever M and the grid are, no atomics, bit-stable from run to run.
+ * x then goes where the x of lqer_quantize_act_xa goes: x_quantizer -> the bf16 activation image xq
+ * [lqer_padded_m(M)][lqer_padded_k(K)] (rows < M written), x_q A on the MFMA and A_out_quantizer -> xaq [lqer_padded_m(M)][padded
+ * rank] - ONE launch (csrc/act_normed.hip) for every M >= 1, no scratch.  x never reaches memory.  a_t is the image of
+ * lqer_a_b16_prepare and a_limbs must be -2; rank 0 writes the image alone (a_t, xaq unused).
+ * LQER_E_INVALID: a null desc / h / norm_weight / xq (or a_t / xaq with rank > 0), M < 0, ld_h < K, a_limbs != -2, eps < 0 or not
+ * finite.
+ * LQER_E_UNSUPPORTED, nothing launched, the reason in lqer_last_error(): fp32 tensors; an x_quantizer that is not block_fp in blocks
+ * of 16; K % 16 != 0 or K > 8192; pointers or the row stride not 16-byte aligned; a padded rank other than 16 / 32 / 48 / 64 / 96 /
+ * 128; an A_out_quantizer that is not block_fp with blocks of 4..64 columns dividing the padded rank (or one block per row); weights
+ * of 5..8 bits (their activation image is three copies side by side). */
+int lqer_quantize_act_xa_normed(const lqer_linear_desc_t* desc, const void* h, const void* norm_weight, float eps, int dtype, int64_t M,
+                                int64_t ld_h, const void* a_t, int a_limbs, void* xq_bf16, void* xaq_bf16, void* stream);
+/* The forward of ONE Linear on RMSNorm(h): the call above, then lqer_linear_gemm on the image and xaq - two launches (three with the
+ * pre-pass of B_out blocks other than 16 columns), the workspace carved as lqer_linear_forward carves it
+ * (lqer_linear_sizes(...).workspace for m_max >= M).  y [M, N] has the dtype of h.  Refused as the call above and as lqer_linear_gemm. */
+int lqer_linear_forward_normed(const lqer_linear_desc_t* desc, const void* h, const void* norm_weight, float eps, int dtype, int64_t M,
+                               int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                               const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- weights of 5..8 bits (the reference's no-LQER baseline: W8A8 block_fp with one block per row and per token,
  * experiments/pipeline/sweep_baseline_no_lqer.sh:73-76, through LinearFlexible, quantized_layers/linear.py:50-64) ---------------
  * The packed image holds 4-bit codes, so a mantissa m of up to 8 bits (|m| <= 127) travels as three signed base-8 digits,

@@ -135,6 +135,9 @@ SIGNATURES = {
     # the scratch / lqer_linear_forward's operands
     "lqer_quantize_act_xa_gated": (_i, [_dp, _vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
     "lqer_linear_forward_gated": (_i, [_dp, _vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    # fused RMSNorm (csrc/act_normed.hip): desc, h, norm weight, eps, dtype, M, ld_h, then as the gated pair
+    "lqer_quantize_act_xa_normed": (_i, [_dp, _vp, _vp, C.c_float, _i, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
+    "lqer_linear_forward_normed": (_i, [_dp, _vp, _vp, C.c_float, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
     "lqer_i8_prepare": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),
     "lqer_unpack_weight_i8": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "lqer_unpack_weight_i8_fmt": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),

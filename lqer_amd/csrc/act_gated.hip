@@ -24,22 +24,12 @@
 // summation-order envelope (tests/_envelope.py).
 //
 // LDS: 8 x 8 x 1040 B slabs + 8 x 8 x rp x 4 B partial tiles = 65 KiB + 4..16 KiB.  rank 0: the image alone, no LDS.
-#include "common.h"
+#include "act_rows.h"
 
 namespace lqer {
 namespace ag {
 
-constexpr int ROWS = 8, WAVES = 8, SLAB = 512, PITCH = 1040, STEPS = SLAB / 32;
-
-__host__ inline size_t lds_bytes(int rp) { return rp ? (size_t)WAVES * ROWS * PITCH + (size_t)WAVES * ROWS * rp * sizeof(float) : 0; }
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
-
-template <int DT>
-__device__ __forceinline__ float round_dt(float v) {
-  if constexpr (DT == LQER_F16) return (float)(_Float16)v;  // v_cvt_f16_f32 + back: round to nearest even, subnormals kept
-  else return __uint_as_float((uint32_t)f32_to_bf16_rne(v) << 16);
-}
+using namespace arow;  // the work split and the pieces shared with act_normed.hip
 
 // one element of h (act: wave-uniform)
 template <int DT, bool UP>
@@ -54,7 +44,7 @@ __global__ __launch_bounds__(512) void k_act_gated(const void* __restrict__ gate
                                                     int64_t ldu, int64_t K, int64_t Kp, const bf16_t* __restrict__ a_frag, bf16_t* __restrict__ xq,
                                                     bf16_t* __restrict__ xaq, QP qx, QP qa, int L_aout) {
   constexpr int RP = 16 * RT, NT = RT ? RT : 1;
-  constexpr int HB = RT == 4 ? 2 : (RT == 2 ? 4 : 8);  // steps per fragment part: a register set holds HB x RT fragments = 32 registers
+  constexpr int HB = part_steps(RT);                   // steps per fragment part: a register set holds HB x RT fragments = 32 registers
   constexpr int NP = STEPS / HB;                       // parts per slab; part p (steps HB p .. HB p + HB - 1) lives in set p & 1
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
@@ -90,7 +80,6 @@ __global__ __launch_bounds__(512) void k_act_gated(const void* __restrict__ gate
   };
   load_rows(wave);
   unsigned char* const wb = smem + (size_t)wave * ROWS * PITCH;          // this wave's slab: [ROWS][PITCH]
-  float* const red = (float*)(smem + (size_t)WAVES * ROWS * PITCH);      // [WAVES][ROWS][RP] partial tiles
   const int g4 = lane >> 4;
   const unsigned char* const tok = wb + (lane & 7) * PITCH + 16 * g4;    // + 64 step: row lane & 7, chunk 4 step + g4
   f32x4 acc[NT];
@@ -112,50 +101,12 @@ __global__ __launch_bounds__(512) void k_act_gated(const void* __restrict__ gate
         if constexpr (UP) pair_to_f32<DT>(live ? ru[j][i] : 0u, u0, u1);
         v[2 * i] = gated<DT, UP>(g0, u0, act), v[2 * i + 1] = gated<DT, UP>(g1, u1, act);
       }
-      float amax = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
-      amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(amax), 0xB1, 0xf, 0xf, true)));  // quad_perm [1,0,3,2]
-      if (amax > 0.f) {
-        const int e = block_exponent_u(amax, qx);
-        // (h is a dt value: an fp16 h cannot be a non-zero |h| <= 1e-8)
-        if (mxint16_fast_ok(e, qx)) {
-          mxint16_bf16_fast<DT != LQER_F16, 8>(v, e, qx, w);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const uint32_t lo = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i], e, qx), e - qx.mbits));
-            const uint32_t hi = exact_bf16_bits(ldexpf(mxint_mantissa(v[2 * i + 1], e, qx), e - qx.mbits));
-            w[i] = lo | (hi << 16);
-          }
-        }
-      }
+      quant_half_block<DT>(v, qx, w);
       if (k < Kp) *(u32x4*)(xq + (m0 + j) * Kp + k) = (u32x4){w[0], w[1], w[2], w[3]};  // (k past K up to the padded K: zeros)
     }
     if constexpr (RT > 0) *(u32x4*)(wb + j * PITCH + 16 * lane) = (u32x4){w[0], w[1], w[2], w[3]};
     __builtin_amdgcn_sched_barrier(0);  // (rows are not interleaved: each would keep its temporaries alive beside the fragment sets)
   };
-  // ---- multiply part p: HB steps of 32 k
-  auto mult = [&](const u32x4 (&f)[HB][NT], int p) {
-    u32x4 tk[HB];
-#pragma unroll
-    for (int i = 0; i < HB; ++i) tk[i] = *(const u32x4*)(tok + 64 * (HB * p + i));
-#pragma unroll
-    for (int i = 0; i < HB; ++i)
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16v8, tk[i]), __builtin_bit_cast(bf16v8, f[i][t]), acc[t], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  // (the wave reads back what it wrote itself: LDS executes a wave's accesses in order - no workgroup barrier; the fences keep the
-  // compiler from moving the reads above the writes, or the next slab's writes above the reads)
-  auto wave_fence = [&] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
   for (int s = wave; s < nslab; s += WAVES) {
     if constexpr (RT > 0) load_part(fa, s, 0), load_part(fb, s, 1);
 #pragma unroll
@@ -165,53 +116,16 @@ __global__ __launch_bounds__(512) void k_act_gated(const void* __restrict__ gate
       wave_fence();
 #pragma unroll
       for (int p = 0; p < NP; p += 2) {
-        mult(fa, p);
+        mult_part<HB, NT>(tok, fa, p, acc);
         if (p + 2 < NP) load_part(fa, s, p + 2);
-        mult(fb, p + 1);
+        mult_part<HB, NT>(tok, fb, p + 1, acc);
         if (p + 3 < NP) load_part(fb, s, p + 3);
       }
       wave_fence();
     }
   }
-  if constexpr (RT > 0) {
-    // D layout: column n = lane & 15, rows 4 g4 + i: token rows 0-7 live in g4 = 0, 1
-    if (g4 < 2) {
-#pragma unroll
-      for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[(wave * ROWS + 4 * g4 + i) * RP + 16 * t + (lane & 15)] = acc[t][i];
-    }
-    __syncthreads();
-    // ---- fixed-order sum of the 8 partial tiles, A_out (k_act16_fused's rules: a thread holds 4 columns of a row, a block of L columns
-    // is L / 4 neighbouring lanes), bf16 store
-    const int tid = threadIdx.x;
-    const bool live = tid < ROWS * RP / 4;
-    const int r = tid / (RP / 4), c4 = tid - r * (RP / 4);
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) {
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) {
-        const float4 v = *(const float4*)(red + (w * ROWS + r) * RP + 4 * c4);
-        sum.x += v.x, sum.y += v.y, sum.z += v.z, sum.w += v.w;
-      }
-    }
-    if (tid >= 64 * ((ROWS * RP / 4 + 63) / 64)) return;  // (whole waves only: the shuffles below need their partners)
-    float bmax = fmaxf(fmaxf(fabsf(sum.x), fabsf(sum.y)), fmaxf(fabsf(sum.z), fabsf(sum.w)));
-    const int G = L_aout / 4;
-    for (int d = 1; d < G; d <<= 1) bmax = fmaxf(bmax, __shfl_xor(bmax, d, 64));
-    if (!live || m0 + r >= M) return;
-    const bool anyb = bmax > 0.f;
-    const int eb = anyb ? block_exponent(bmax, qa) : 0;
-    const float v[4] = {sum.x, sum.y, sum.z, sum.w};
-    uint32_t w2[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float a = anyb ? mxint_mantissa(v[2 * i], eb, qa) : 0.f;
-      const float b = anyb ? mxint_mantissa(v[2 * i + 1], eb, qa) : 0.f;
-      w2[i] = exact_bf16_bits(ldexpf(a, eb - qa.mbits)) | (exact_bf16_bits(ldexpf(b, eb - qa.mbits)) << 16);
-    }
-    *(uint2*)(xaq + ((m0 + r) * RP + 4 * c4)) = make_uint2(w2[0], w2[1]);
-  }
+  // the eight partial tiles summed in wave order, A_out, the bf16 store
+  if constexpr (RT > 0) tiles_sum_aout<RT, false>(smem, acc, wave, lane, m0, M, xaq, qa, L_aout);
 }
 
 }  // namespace ag

@@ -20,6 +20,7 @@ branch (linear.py:158-166) raises.  There is no CPU path: a CPU tensor raises.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from copy import deepcopy
 from typing import Optional
 
@@ -680,6 +681,95 @@ class _LinearBase(nn.Linear):
             check(rc, "lqer_linear_forward_gated")
         return y.reshape(*gate.shape[:-1], N)
 
+    # -- fused RMSNorm ------------------------------------------------------------------------
+    # Token counts from which forward_normed and a SharedActivation round armed by a fused norm (models.quantize_model(fuse_norm=True))
+    # take the normed entry.  tools/rmsnorm_bench.py at the Llama-7B q/k/v and gate/up groups (profiles/rmsnorm_fused.json, DESIGN.md "Fused
+    # RMSNorm"): against torch's HF-form norm + the group's forward the fused round takes 0.67x / 0.78x / 0.78x / 0.81x (q/k/v) and 0.88x /
+    # 0.80x / 0.84x / 0.86x (gate/up) of the time at M = 64 / 512 / 2048 / 8192 - no slower at any measured size, so the threshold is the
+    # smallest one measured (nothing below 64 tokens was timed; up to 8 tokens the groups take the one-launch decode route anyway)
+    normed_min_m = 64
+    _NORMED_RANKS = (16, 32, 48, 64, 96, 128)  # padded ranks csrc/act_normed.hip serves (and rank 0)
+
+    @staticmethod
+    def rms_norm_torch(h: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> torch.Tensor:
+        """HF LlamaRMSNorm, statement by statement (the route forward_normed replaces)."""
+        h32 = h.to(torch.float32)
+        h32 = h32 * torch.rsqrt(h32.pow(2).mean(-1, keepdim=True) + eps)
+        return norm_weight * h32.to(h.dtype)
+
+    def forward_normed(self, h: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> torch.Tensor:
+        """This Linear on x = RMSNorm(h) = norm_weight * (h * rsqrt(mean h^2 + eps)) (HF LlamaRMSNorm, both roundings in h's dtype) with
+        the norm formed inside the activation-side kernel (csrc/act_normed.hip through lqer_linear_forward_normed: two launches, x never
+        written) where that kernel applies: fp16 / bf16 tensors from normed_min_m tokens on, in_features % 16 == 0 and <= 8192, block-16
+        MXINT x_quantizer, an A of one bf16 limb with padded rank 16 / 32 / 48 / 64 / 96 / 128 (or no A), the standard weight image.
+        Elsewhere the norm is computed with torch and handed to forward().  Against that route the result differs by 1 / sqrt against
+        torch's rsqrt (the last bit of some x) and the side product's fp32 summation order."""
+        if h.shape[-1] != self.in_features or norm_weight.shape != (self.in_features,):
+            raise RuntimeError(f"expected last dim {self.in_features}, got h {tuple(h.shape)}, norm weight {tuple(norm_weight.shape)}")
+        if (self.is_ptq and h.is_cuda and h.dtype in (torch.float16, torch.bfloat16) and norm_weight.dtype == h.dtype
+                and norm_weight.device == h.device and not (self._tiles and self._needs_tiles(h))):
+            if _device_count() > 1 and h.device.index != torch.cuda.current_device():
+                with torch.cuda.device(h.device):
+                    y = self._forward_normed_hip(h, norm_weight, float(eps))
+            else:
+                y = self._forward_normed_hip(h, norm_weight, float(eps))
+            if y is not None:
+                return y
+        return _LinearBase.forward(self, self.rms_norm_torch(h, norm_weight, eps))
+
+    def _normed_a_image(self):
+        """The A^T image the normed kernel reads (lqer_a_b16_prepare), None where there is none: the block-16 route's own where the module
+        keeps one, else built at the first call (padded ranks 48 / 96 / 128, which act16_fused.hip does not serve)."""
+        p = self._packed
+        img = p.get("a_t_b16", p.get("a_t_b16_normed"))
+        if img is None and self.rank > 0 and int(p.get("a_limbs", 0)) == 1 and not self._x_i8 and not self._x_f16:
+            img = p["a_t_b16_normed"] = ops.a_b16_image(p["a_t"], self.in_features, self.rank)
+        return img
+
+    def _forward_normed_hip(self, h: torch.Tensor, nw: torch.Tensor, eps: float) -> Optional[torch.Tensor]:
+        """The fused entry, or None where the kernel does not serve this module / these tensors (the caller computes the norm with torch)."""
+        self._written_in_place()
+        if self._packed is None or self.w_is_quantized is False:
+            self._pack()
+        K, N = self.in_features, self.out_features
+        M = h.numel() // K
+        fx, fa = self._fmt["x"], self._fmt.get("A_out")
+        if (M < self.normed_min_m or K % 16 or K > 8192 or self._weight_image == "narrow" or ops.w_limbs(self._fmt["w"]) != 1 or self._x_i8
+                or fx.kind != _lib.Q_MXINT or fx.block != 16 or fx.width > 9):
+            return None
+        a_img = None
+        if self.rank > 0:
+            if _lib.lib().lqer_padded_r(self.rank) not in self._NORMED_RANKS or fa is None or fa.kind != _lib.Q_MXINT or fa.width > 9:
+                return None
+            a_img = self._normed_a_image()
+            if a_img is None:
+                return None
+        p = self._packed
+        h2 = h.reshape(-1, K)
+        if h2.stride(-1) != 1 or h2.data_ptr() % 16 or (M > 1 and (h2.stride(0) < K or h2.stride(0) % 8)):
+            h2 = h2.contiguous()
+        nw = nw if nw.is_contiguous() and nw.data_ptr() % 16 == 0 else nw.clone()
+        y = torch.empty(M, N, dtype=h.dtype, device=h.device)
+        key = ("normed", M, h.dtype, self.tuning)
+        ent = self._fw_cache.get(key)
+        if ent is None:
+            desc = self._desc()
+            if len(self._fw_cache) > 64:
+                self._fw_cache = {}
+            ent = self._fw_cache[key] = (desc, ops.linear_sizes(desc, M).workspace, ops.dtype_code(h2),
+                                         (p["w"].data_ptr(), ops._ptr(a_img), ops._ptr(p.get("b_t")), -2, p.get("b_limbs", 0),
+                                          ops._ptr(p.get("bias"))))
+        desc, ws_bytes, dt, consts = ent
+        st = ops._stream(h.device)
+        ws = ops.workspace_on(h.device, st, ws_bytes)
+        rc = _lib.lib().lqer_linear_forward_normed(C.byref(desc), h2.data_ptr(), nw.data_ptr(), eps, dt, M, h2.stride(0) if M > 1 else K, *consts,
+                                                   y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        if rc == -2:  # LQER_E_UNSUPPORTED (nothing was launched): the torch norm + forward()
+            return None
+        if rc:
+            check(rc, "lqer_linear_forward_normed")
+        return y.reshape(*h.shape[:-1], N)
+
     def __repr__(self):
         return "{}(in_features={}, out_features={}, bias={}, is_ptq={}, rank={}, backend=hip/gfx950{})".format(
             self.__class__.__name__, self.in_features, self.out_features, self.bias is not None, self.is_ptq, self.rank,
@@ -731,6 +821,7 @@ class SharedActivation:
         self._x = None        # the tensor the images below were made from (strong reference: its address stays taken)
         self._ver = -1
         self._round = 0       # rounds started by this group (pool ownership)
+        self.normed_rounds = 0  # ... of which started from a raw hidden state (lqer_quantize_act_xa_normed)
         self._cur = None
         self._served = set()  # members served from the current images
         self._plans = {}      # (M, dtype) -> launch constants of the group quantizer and of every member's GEMM
@@ -740,6 +831,7 @@ class SharedActivation:
         self._dstream = None  # ... and the stream they were launched on
         self._dys = None      # outputs of the current round, one per member
         self._dserved = set()
+        self._armed = None    # (h or a weak reference to it, its version, norm weight, eps): a fused norm's raw hidden state (arm_normed)
         if self.enabled:
             for i, m in enumerate(self.members):
                 m._group = self
@@ -747,6 +839,7 @@ class SharedActivation:
 
     def invalidate(self):
         self._cat, self._x, self._cur, self._served = None, None, None, set()
+        self._armed = None
         self._plans = {}
         self._dplans, self._dx, self._dys, self._dserved = {}, None, None, set()
 
@@ -755,7 +848,7 @@ class SharedActivation:
         # pointers of THIS group's members and of the shared pool - the copy rebuilds them at its first call
         st = self.__dict__.copy()
         st.update(_cat=None, _x=None, _cur=None, _served=set(), _plans={}, _ver=-1, _dplans={}, _dx=None, _dys=None, _dserved=set(),
-                  _dver=-1, _dstream=None)
+                  _dver=-1, _dstream=None, _armed=None)
         return st
 
     @classmethod
@@ -788,6 +881,44 @@ class SharedActivation:
             ok16, a16 = ops.a_f16_image(m0._packed["w"], m0.out_features, K, a_t, 2, off)
             if ok16:
                 self._cat["a_t_f16"] = a16
+        # one bf16 limb: the image with its fragment-major copy that the fused-norm kernel reads (csrc/act_normed.hip, a_limbs = -2)
+        if a_limbs == 1 and off in _LinearBase._NORMED_RANKS and not any(m._x_i8 or m._x_f16 for m in self.members):
+            self._cat["a_t_b16"] = ops.a_b16_image(a_t, K, off)
+
+    # -- fused RMSNorm: a round started from the raw hidden state ------------------------------------------------------------------
+    def normed_serves(self, h: torch.Tensor) -> bool:
+        """Will a round of this group on h run the fused-norm kernel (lqer_quantize_act_xa_normed)?  Asked by the norm in front of the
+        group BEFORE it decides to hand the raw hidden state on: everything the kernel or this route refuses is answered here."""
+        m0 = self.members[0]
+        K = m0.in_features
+        M = h.numel() // K if K else 0
+        if (not self.enabled or not h.is_cuda or h.dtype not in (torch.float16, torch.bfloat16) or h.shape[-1] != K or K % 16 or K > 8192
+                or M <= 8 or M < m0.normed_min_m or not h.is_contiguous() or h.data_ptr() % 16
+                or any(m._packed_only or not m.is_ptq or m.weight.device != h.device for m in self.members)):
+            return False
+        fx, fa = m0._fmt["x"], m0._fmt["A_out"]
+        if fx.block != 16 or fx.width > 9 or fa.width > 9:
+            return False
+        if _device_count() > 1 and h.device.index != torch.cuda.current_device():
+            return False
+        for m in self.members:
+            m._written_in_place()
+            if m._packed is None or m.w_is_quantized is False:
+                m._pack()
+        if self._cat is None:
+            self._pack_cat(h.device)
+        return "a_t_b16" in self._cat
+
+    def arm_normed(self, h: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> None:
+        """The next round on this very tensor, unmodified, starts from RMSNorm(h) formed inside the group's quantizer launch."""
+        self._armed = (h, None if h.is_inference() else h._version, norm_weight, float(eps))
+
+    def _armed_for(self, x: torch.Tensor):
+        a = self._armed
+        if a is None:
+            return None
+        h = a[0]() if isinstance(a[0], weakref.ref) else a[0]
+        return a if (h is x and a[1] == (None if x.is_inference() else x._version)) else None
 
     def take(self, mod, x):
         """A member comes with the tensor of the open decode round: its output, once, if the tensor is unmodified."""
@@ -884,7 +1015,10 @@ class SharedActivation:
     @torch.no_grad()
     def forward_member(self, mod, x, x2, y) -> bool:
         """Run `mod`'s forward on the shared images; False = not applicable, the caller takes the ordinary route."""
+        armed = self._armed_for(x)  # a fused norm handed the group its RAW hidden state: this round starts from RMSNorm(x)
         if not self.enabled or any(m._packed_only for m in self.members):  # (a packed checkpoint carries no dense A)
+            if armed is not None:
+                raise RuntimeError("SharedActivation: a round armed by a fused norm cannot be served (normed_serves() had said it would)")
             return False
         for m in self.members:  # every member packed (the group image needs the final A values)
             if m._packed is None or m.w_is_quantized is False:
@@ -947,15 +1081,25 @@ class SharedActivation:
             self._round += 1
             pool["owner"] = (id(self), self._round)
             b = {"xq": pool["xq"].data_ptr(), "xaq": pool["xaq"].data_ptr(), "keep": (pool["xq"], pool["xaq"])}
-            rc = L.lqer_quantize_act_xa(C.byref(plan["gdesc"]), x2.data_ptr(), dtc, M, x2.stride(0) if M > 1 else K,
-                                        *plan["a_img"], b["xq"], b["xaq"], pool["scr"].data_ptr(), plan["nscr"], st)
-            if rc:
-                check(rc, "lqer_quantize_act_xa (shared input)")
+            if armed is not None:  # norm + quantizer + x A + A_out in one launch; the members' GEMM calls below are untouched
+                nw = armed[2].data
+                rc = L.lqer_quantize_act_xa_normed(C.byref(plan["gdesc"]), x2.data_ptr(), nw.data_ptr(), armed[3], dtc, M, x2.stride(0),
+                                                   self._cat["a_t_b16"].data_ptr(), -2, b["xq"], b["xaq"], st)
+                if rc:
+                    check(rc, "lqer_quantize_act_xa_normed (shared input)")
+                self.normed_rounds += 1
+            else:
+                rc = L.lqer_quantize_act_xa(C.byref(plan["gdesc"]), x2.data_ptr(), dtc, M, x2.stride(0) if M > 1 else K,
+                                            *plan["a_img"], b["xq"], b["xaq"], pool["scr"].data_ptr(), plan["nscr"], st)
+                if rc:
+                    check(rc, "lqer_quantize_act_xa (shared input)")
             self._x, self._ver, self._cur, self._served = x, ver, dict(b, M=M), set()
         cur = self._cur
         self._served.add(idx)
         if len(self._served) == len(self.members):
             self._x = None  # every member has been served: do not pin the activation tensor until the next call
+            if armed is not None and not isinstance(armed[0], weakref.ref):  # (a member that comes back with it still finds it armed)
+                self._armed = (weakref.ref(armed[0]),) + armed[1:]
         desc, gs, w_ptr, bt_ptr, b_limbs, bias_ptr, N, wide = plan["members"][idx]
         gs_al = (max(gs, 16) + 255) // 256 * 256
         scr = ops.workspace(dev, gs_al + wide)

@@ -91,14 +91,55 @@ def _fuse_mlp(model: nn.Module, layer: nn.Module, table: dict) -> None:
         layer.activation_fn = nn.Identity()
 
 
+def _fused_norm_forward(self, hidden_states):
+    """The RMSNorm in front of a SharedActivation group under fuse_norm: where the group's next round will run the fused-norm kernel the
+    RAW hidden state is handed on (the group is armed with it, its version, the weight and eps, and forms the norm inside its quantizer
+    launch); everywhere else the original norm runs."""
+    g, w = self._lqer_group, self.weight
+    if (g is not None and w.dtype == hidden_states.dtype and w.device == hidden_states.device and w.is_contiguous()
+            and w.data_ptr() % 16 == 0 and g.normed_serves(hidden_states)):
+        g.arm_normed(hidden_states, w, self.variance_epsilon)
+        return hidden_states
+    return type(self).__mro__[1].forward(self, hidden_states)
+
+
+_FUSED_NORM_CLS: Dict[type, type] = {}
+_NORM_IN_FRONT = {"input_layernorm": ("self_attn", "q_proj"), "post_attention_layernorm": ("mlp", "gate_proj")}
+
+
+def _fuse_norm(layer: nn.Module, table: dict) -> None:
+    """One decoder layer's two norms -> a subclass whose forward arms the group behind it (no module is added, state-dict keys stay,
+    deep copies keep working).  Only weight * (x * rsqrt(mean x^2 + eps)) is served: HF's LlamaRMSNorm / MistralRMSNorm."""
+    if table is not _LLAMA_LIKE:
+        raise NotImplementedError("fuse_norm: OPT's LayerNorm is not of the form weight * (x * rsqrt(mean x^2 + eps)); not served")
+    for name, (parent, first) in _NORM_IN_FRONT.items():
+        norm = getattr(layer, name, None)
+        form = (norm is not None and not isinstance(norm, nn.LayerNorm) and type(norm).__name__.endswith("RMSNorm")
+                and not type(norm).__name__.startswith("Gemma") and isinstance(getattr(norm, "weight", None), nn.Parameter)
+                and hasattr(norm, "variance_epsilon") and getattr(norm, "bias", None) is None)
+        if not form:
+            raise NotImplementedError(f"fuse_norm: {name} ({type(norm).__name__}) is not of the form weight * (x * rsqrt(mean x^2 + eps)) "
+                                      "(LlamaRMSNorm / MistralRMSNorm); LayerNorm and 1 + weight norms are not served")
+        group = getattr(getattr(getattr(layer, parent), first), "_group", None)
+        if group is None:  # (no enabled group behind this norm: left as it is)
+            continue
+        cls = type(norm)
+        if cls not in _FUSED_NORM_CLS:
+            _FUSED_NORM_CLS[cls] = type("Fused" + cls.__name__, (cls,), {"forward": _fused_norm_forward})
+        norm.__dict__["_lqer_group"] = group
+        norm.__class__ = _FUSED_NORM_CLS[cls]
+
+
 def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], share_inputs: bool = True,
-                   weight_image: str = "standard", fuse_mlp: bool = False) -> nn.Module:
+                   weight_image: str = "standard", fuse_mlp: bool = False, fuse_norm: bool = False) -> nn.Module:
     """Replace the projections of every decoder layer in place; weights are carried over.  share_inputs: projections
     fed by the same tensor quantize it once and share one side GEMM (linear.SharedActivation); per-projection results
     are unchanged up to the fp32 summation order of the side product.  weight_image: "narrow" makes every projection keep the
     compact image of its 2- / 3-bit block_fp weight (linear._LinearBase.weight_image; a projection it does not serve raises when
     it packs).  fuse_mlp: the activation between the MLP's projections runs inside the down projection's activation-side kernel
-    (linear._LinearBase.forward_gated: silu(gate) * up for Llama-like layers, relu for OPT's fc2) instead of as torch launches."""
+    (linear._LinearBase.forward_gated: silu(gate) * up for Llama-like layers, relu for OPT's fc2) instead of as torch launches.  fuse_norm: the RMSNorm in front of
+    q/k/v and of gate/up (Llama-like layers with share_inputs) runs inside the group's quantizer launch (csrc/act_normed.hip) from
+    linear._LinearBase.normed_min_m tokens on - the normalised tensor is never written; other norms raise NotImplementedError."""
     layers, table = _decoder_layers(model)
     for layer_id, layer in enumerate(layers):
         for group, names in table.items():
@@ -122,6 +163,8 @@ def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], s
                         SharedActivation(mods)
         if fuse_mlp:
             _fuse_mlp(model, layer, table)
+        if fuse_norm:
+            _fuse_norm(layer, table)
     return model
 
 
