@@ -904,6 +904,24 @@ int lqer_attention_q_kv(const void* q, const void* cache, size_t cache_bytes, in
  * launch on `stream` whatever the counts are, its grid sized by max_n; threads beyond a sequence's n_b leave at once, and per sequence
  * the thread that reads a staging column is still the one that writes it.  Refused as lqer_kv_pool_append, and LQER_E_INVALID for a
  * null new_starts, max_n < 1 or > max_len, total < 0, null strides.
+ * lqer_kv_pool_append_rope: lqer_kv_pool_append_ragged with the rotary position embedding of a Llama-family layer in the same launch -
+ * the raw q, k, v of the projections go in, q and k are rotated, k and v are appended (lqer_amd/csrc/kv_rope.hip, whose header comment
+ * spells THE RULE: HF's rotate_half form, rounded to DT after each of its three operations - eager torch's bits on DT tensors; fp32 without
+ * contraction).  After lqer_kv_pool_append_ragged's pool / metadata / new_starts / max_n arguments: q and q_out [total][heads][D] of DT
+ * through q_strides[2] / q_out_strides[2] (elements over token, then head; D dense) - q_out == q rotates in place, any other overlap is
+ * the caller's fault; q = NULL with heads = 0 rotates K alone; a token that lies in no sequence's range of new_starts is not written -,
+ * then k_new / v_new and their stride pairs as the sibling's, then rope_cos / rope_sin [rope_rows][D / 2] of DT, dense, 16-byte aligned,
+ * on the device: the FIRST HALF of what the model's rotary module returns (HF duplicates the halves), whatever scaling rule the model
+ * uses already in them - no trigonometry is computed here -, then positions: NULL - new token j of sequence b sits at position
+ * lens[b] + j, the length before the call, read from the device where the append reads it -, or int32 [total] on the device - the
+ * position of packed token new_starts[b] + j (a draft tree: base + depth, not append order); their range [0, rope_rows) is then the
+ * caller's contract, like the table's entries.  THE GUARANTEE: afterwards the pool and the staging rows hold, byte for byte, what
+ * lqer_kv_pool_append_ragged leaves when handed the keys rotated by the rule, and q_out holds the rule's bits - whatever else is in the
+ * batch and whatever pages it lives on.  ONE launch on `stream`, no workspace, no allocation, no host synchronisation, no atomics:
+ * capturable in a hipGraph.  Refused, from host arguments only and with nothing launched: as lqer_kv_pool_append_ragged, in its words;
+ * LQER_E_INVALID - null rope_cos / rope_sin, rope_rows < 1, tables not 16-byte aligned, positions == NULL with max_len + max_n >
+ * rope_rows, q NULL with heads > 0 or the reverse, q set with q_out or a stride pair NULL; LQER_E_UNSUPPORTED - total x heads beyond the
+ * launch grid (2^31).
  * lqer_attention_q_paged_ragged: lqer_attention_q_paged with S replaced by (q_starts, max_s, total): q and out are [total][heads][D]
  * through q_strides[2] / out_strides[2], row_stats a dense [total][heads][2] fp32 or NULL.  For every b, the rows of sequence b in out
  * and row_stats are the SAME BITS as lqer_attention_q with batch = 1, S = S_b = q_starts[b + 1] - q_starts[b] on the raw K and V of that
@@ -1031,6 +1049,12 @@ int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int
                                const void* k_new, const void* v_new, const int64_t* k_strides, const int64_t* v_strides, int dtype,
                                int64_t batch, int64_t kv_heads, int64_t D, int64_t total, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt,
                                void* stream);
+int lqer_kv_pool_append_rope(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                             const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const int32_t* new_starts, int64_t max_n,
+                             const void* q, void* q_out, const int64_t* q_strides, const int64_t* q_out_strides, int64_t heads, const void* k_new,
+                             const void* v_new, const int64_t* k_strides, const int64_t* v_strides, const void* rope_cos, const void* rope_sin,
+                             int64_t rope_rows, const int32_t* positions, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t total,
+                             const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream);
 int lqer_kv_pool_gather(const void* pool, size_t pool_bytes, int dtype, int64_t pages, int64_t slots, int64_t kv_heads, int64_t D,
                         const int32_t* block_table, int64_t table_stride, int64_t slot, int64_t T, void* cache, size_t cache_bytes,
                         int64_t capacity, void* stream);

@@ -200,6 +200,9 @@ SIGNATURES = {
     # per-sequence token counts in one call (a mixed prefill / decode step): new_starts / q_starts [batch + 1] on the device, a host bound
     # on the counts, packed [total][heads][D] tensors through stride PAIRS (token, head)
     "lqer_kv_pool_append_ragged": (_i, _POOL + [_vp, _i64] + _APPEND),
+    # ... with the rotary embedding of q and k in the launch (csrc/kv_rope.hip): q, q_out, their stride pairs and heads in front of k_new;
+    # the cos / sin tables, their rows and the positions (or none) behind the strides of k and v
+    "lqer_kv_pool_append_rope": (_i, _POOL + [_vp, _i64] + [_vp, _vp, _sp, _sp, _i64] + _APPEND[:4] + [_vp, _vp, _i64, _vp] + _APPEND[4:]),
     "lqer_attention_q_paged_ragged_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     # lqer_attention_q_paged's list with S -> (q_starts, max_s, total)
     "lqer_attention_q_paged_ragged": (_i, _PAGED_RAGGED),

@@ -1774,39 +1774,91 @@ int lqer_kv_pool_append(void* pool, size_t pool_bytes, int64_t pages, int64_t sl
   return kv_pool_append_dispatch(p, k_new, v_new, k_strides, v_strides, batch, n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
 }
 
+// what lqer_kv_pool_append_ragged asks of its host arguments, in the words of `who` (that entry, or lqer_kv_pool_append_rope): p with the
+// counts and the storage, k_fmt / v_fmt resolved through `own`.  LQER_OK or the refusal; `empty`: nothing to launch
+static int kv_pool_append_ragged_check(const char* who, KvPool& p, PoolFmts& own, const int32_t* new_starts, int64_t max_n, const void* k_new,
+                                       const void* v_new, const int64_t* k_strides, const int64_t* v_strides, int64_t batch, int64_t total,
+                                       const lqer_qfmt_t*& k_fmt, const lqer_qfmt_t*& v_fmt, bool& empty) {
+  empty = false;
+  if (batch < 0 || max_n < 1) {
+    set_error("%s: batch %lld / max_n %lld new keys for the KV pool (batch >= 0, max_n >= 1 bounds every sequence's count)", who, (long long)batch,
+              (long long)max_n);
+    return LQER_E_INVALID;
+  }
+  p.ragged = true, p.starts = new_starts, p.total = total;
+  own.resolve(p, k_fmt, v_fmt);
+  int rc = pool_nibble_check(who, p, k_fmt, v_fmt);
+  if (rc == LQER_OK) rc = kv_codes_check(who, p.D, k_fmt, v_fmt);
+  if (rc == LQER_OK) rc = kv_pool_check(who, p, POOL_BATCH);
+  if (rc != LQER_OK) return rc;
+  if (max_n > p.max_len) {
+    set_error("%s: max_n %lld new keys beyond max_len %lld of the KV pool (a bound on lens[b] + n_b)", who, (long long)max_n, (long long)p.max_len);
+    return LQER_E_INVALID;
+  }
+  if (batch == 0 || total == 0) {
+    empty = true;
+    return LQER_OK;
+  }
+  if (!k_new || !v_new || !k_strides || !v_strides) {
+    set_error("%s: null pointer (new keys / values for the KV pool or their strides)", who);
+    return LQER_E_INVALID;
+  }
+  if (batch * p.kv_heads * ((max_n + 14) / 16 + 1 + max_n) > ((int64_t)1 << 31)) {  // (work items over grid.x, as lqer_kv_pool_append's at n = max_n)
+    set_error("%s: max_n %lld new keys for %lld KV pool streams beyond one launch grid: append in pieces", who, (long long)max_n,
+              (long long)(batch * p.kv_heads));
+    return LQER_E_UNSUPPORTED;
+  }
+  return LQER_OK;
+}
+
 int lqer_kv_pool_append_ragged(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
                                const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const int32_t* new_starts, int64_t max_n,
                                const void* k_new, const void* v_new, const int64_t* k_strides, const int64_t* v_strides, int dtype, int64_t batch,
                                int64_t kv_heads, int64_t D, int64_t total, const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
-  if (batch < 0 || max_n < 1) {
-    set_error("kv_pool_append_ragged: batch %lld / max_n %lld new keys for the KV pool (batch >= 0, max_n >= 1 bounds every sequence's count)",
-              (long long)batch, (long long)max_n);
-    return LQER_E_INVALID;
-  }
   KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
-  p.ragged = true, p.starts = new_starts, p.total = total;
   PoolFmts own;
-  own.resolve(p, k_fmt, v_fmt);
-  int rc = pool_nibble_check("kv_pool_append_ragged", p, k_fmt, v_fmt);
-  if (rc == LQER_OK) rc = kv_codes_check("kv_pool_append_ragged", D, k_fmt, v_fmt);
-  if (rc == LQER_OK) rc = kv_pool_check("kv_pool_append_ragged", p, POOL_BATCH);
+  bool empty;
+  const int rc = kv_pool_append_ragged_check("kv_pool_append_ragged", p, own, new_starts, max_n, k_new, v_new, k_strides, v_strides, batch, total,
+                                             k_fmt, v_fmt, empty);
+  if (rc != LQER_OK || empty) return rc;
+  return kv_pool_append_ragged_dispatch(p, k_new, v_new, k_strides, v_strides, batch, max_n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
+}
+
+int lqer_kv_pool_append_rope(void* pool, size_t pool_bytes, int64_t pages, int64_t slots, const int32_t* block_table, int64_t table_stride,
+                             const int32_t* seq_slots, const int32_t* lens, int64_t max_len, const int32_t* new_starts, int64_t max_n,
+                             const void* q, void* q_out, const int64_t* q_strides, const int64_t* q_out_strides, int64_t heads, const void* k_new,
+                             const void* v_new, const int64_t* k_strides, const int64_t* v_strides, const void* rope_cos, const void* rope_sin,
+                             int64_t rope_rows, const int32_t* positions, int dtype, int64_t batch, int64_t kv_heads, int64_t D, int64_t total,
+                             const lqer_qfmt_t* k_fmt, const lqer_qfmt_t* v_fmt, void* stream) {
+  const char* who = "kv_pool_append_rope";
+  KvPool p = kv_pool(pool, pool_bytes, pages, slots, block_table, table_stride, seq_slots, lens, max_len, dtype, kv_heads, D);
+  PoolFmts own;
+  bool empty;
+  const int rc = kv_pool_append_ragged_check(who, p, own, new_starts, max_n, k_new, v_new, k_strides, v_strides, batch, total, k_fmt, v_fmt, empty);
   if (rc != LQER_OK) return rc;
-  if (max_n > max_len) {
-    set_error("kv_pool_append_ragged: max_n %lld new keys beyond max_len %lld of the KV pool (a bound on lens[b] + n_b)", (long long)max_n,
-              (long long)max_len);
+  if (!rope_cos || !rope_sin || rope_rows < 1 || (uintptr_t)rope_cos % 16 != 0 || (uintptr_t)rope_sin % 16 != 0) {
+    set_error("%s: rotary tables cos %p / sin %p of %lld rows for the KV pool's append ([rope_rows][D / 2] of the dtype, 16-byte aligned, at least "
+              "one row)", who, rope_cos, rope_sin, (long long)rope_rows);
     return LQER_E_INVALID;
   }
-  if (batch == 0 || total == 0) return LQER_OK;
-  if (!k_new || !v_new || !k_strides || !v_strides) {
-    set_error("kv_pool_append_ragged: null pointer (new keys / values for the KV pool or their strides)");
+  if (!positions && max_len + max_n > rope_rows) {
+    set_error("%s: rotary tables of %lld rows for max_len %lld + max_n %lld of the KV pool (without `positions` the rows follow the lengths)", who,
+              (long long)rope_rows, (long long)max_len, (long long)max_n);
     return LQER_E_INVALID;
   }
-  if (batch * kv_heads * ((max_n + 14) / 16 + 1 + max_n) > ((int64_t)1 << 31)) {  // (work items over grid.x, as lqer_kv_pool_append's at n = max_n)
-    set_error("kv_pool_append_ragged: max_n %lld new keys for %lld KV pool streams beyond one launch grid: append in pieces", (long long)max_n,
-              (long long)(batch * kv_heads));
+  if (heads < 0 || (heads > 0) != (q != nullptr) || (q && (!q_out || !q_strides || !q_out_strides))) {
+    set_error("%s: q %p / q_out %p / their strides with %lld query heads beside the KV pool's new keys (q and heads > 0 come together, and with "
+              "them q_out and both stride pairs)", who, q, (const void*)q_out, (long long)heads);
+    return LQER_E_INVALID;
+  }
+  if (total * heads > ((int64_t)1 << 31)) {  // (the query rows' work items over grid.x, 256 a workgroup: D / 8 <= 16 per row)
+    set_error("%s: %lld tokens x %lld query heads beside the KV pool's new keys beyond one launch grid: append in pieces", who, (long long)total,
+              (long long)heads);
     return LQER_E_UNSUPPORTED;
   }
-  return kv_pool_append_ragged_dispatch(p, k_new, v_new, k_strides, v_strides, batch, max_n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
+  if (empty) return LQER_OK;
+  const KvRope r = {q, q_out, q_strides, q_out_strides, heads, rope_cos, rope_sin, positions};
+  return kv_pool_append_rope_dispatch(p, r, k_new, v_new, k_strides, v_strides, batch, max_n, make_qp(*k_fmt), make_qp(*v_fmt), (hipStream_t)stream);
 }
 
 // gather with and without formats: k_fmt / v_fmt null (both) - lqer_kv_pool_gather, a pool of byte codes

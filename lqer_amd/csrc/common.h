@@ -1007,6 +1007,18 @@ int kv_pool_append_dispatch(const KvPool& p, const void* k_new, const void* v_ne
                             const QP& qk, const QP& qv, hipStream_t st);
 int kv_pool_append_ragged_dispatch(const KvPool& p, const void* k_new, const void* v_new, const int64_t* ks2, const int64_t* vs2, int64_t batch,
                                    int64_t max_n, const QP& qk, const QP& qv, hipStream_t st);  // (p.starts; strides over token / kv head)
+// kv_rope.hip: what lqer_kv_pool_append_rope adds to the ragged append - the queries (heads = 0: none), their output, the stride pairs
+// (elements over token / head; the caller's pointers) and the rotation's tables [rope_rows][D / 2] with the optional positions (device)
+struct KvRope {
+  const void* q;
+  void* q_out;
+  const int64_t *qs, *os;
+  int64_t heads;
+  const void *cos, *sin;
+  const int32_t* positions;
+};
+int kv_pool_append_rope_dispatch(const KvPool& p, const KvRope& r, const void* k_new, const void* v_new, const int64_t* ks2, const int64_t* vs2,
+                                 int64_t batch, int64_t max_n, const QP& qk, const QP& qv, hipStream_t st);  // (p.starts, p.total)
 int kv_pool_gather_dispatch(const KvPool& p, int64_t slot, int64_t T, void* cache, int64_t capacity, hipStream_t st);
 int kv_pool_fork_dispatch(const KvPool& p, const int32_t* src_slots, int64_t n, hipStream_t st);  // (p.seq_slots: the children's slots)
 int kv_pool_copy_dispatch(const KvPool& src, const KvPool& dst, const int32_t* src_pages, const int32_t* dst_pages, int64_t n_pages,

@@ -42,39 +42,6 @@ struct AArgs {
                           // bound max_n, which sizes the grid
 };
 
-// 4 d of one block of 16 keys (x[j][r]: d0 + j of key r) -> the codes of the 16 rows (kc: the block's first row at d0; row pitch D bytes,
-// the four d as one dword) and the four exponent bytes of the block: the K side of an append, dense or paged.  N4 (nibble codes, kc at
-// d0 / 2, row pitch D / 2): the four d are the two WHOLE bytes d0 / 2, d0 / 2 + 1 of every row - one 2-byte store, no byte shared with
-// another thread and none read back, so a dirty page leaves no stale neighbour nibble
-template <int DT, bool N4>
-__device__ __forceinline__ void store_kblock4(const float (&x)[4][16], const QP& qk, unsigned char* kc, int64_t D, unsigned char* ke) {
-  uint32_t cw[4][4], eb = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) eb |= quant16_codes<DT != LQER_F16>(x[j], qk, cw[j]) << (8 * j);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {  // key r of the block: the four d as one dword
-    const int sh = 8 * (r & 3);
-    const uint32_t c4 = ((cw[0][r >> 2] >> sh) & 0xffu) | (((cw[1][r >> 2] >> sh) & 0xffu) << 8) |
-                        (((cw[2][r >> 2] >> sh) & 0xffu) << 16) | (((cw[3][r >> 2] >> sh) & 0xffu) << 24);
-    if constexpr (N4) *(unsigned short*)(kc + r * code_pitch<true>(D)) = (unsigned short)narrow8(c4, 0);
-    else *(uint32_t*)(kc + r * D) = c4;
-  }
-  *(uint32_t*)ke = eb;
-}
-
-// 16 d of one new V row -> its 16 codes (16 bytes, or with N4 the 8 bytes of their nibbles) and its exponent byte: the V side of an
-// append, dense or paged
-template <int DT, bool N4>
-__device__ __forceinline__ void store_vrow16(const void* vn, int64_t off, bool vec, const QP& qv, unsigned char* vc, unsigned char* ve) {
-  float x[16];
-  load16<DT>(vn, off, 16, vec, x);
-  uint32_t cw[4];
-  const uint32_t eb = quant16_codes<DT != LQER_F16>(x, qv, cw);
-  if constexpr (N4) *(uint2*)vc = make_uint2(narrow8(cw[0], cw[1]), narrow8(cw[2], cw[3]));
-  else *(uint4*)vc = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-  *ve = (unsigned char)eb;
-}
-
 // 4 d of one raw key -> a staging row, bits as they are (dst 16- / 8-byte aligned: d0 a multiple of 4 of a row of D elements)
 template <int DT>
 __device__ __forceinline__ void copy_raw4(const void* kn, int64_t src, bool vec, void* stage, int64_t dst) {

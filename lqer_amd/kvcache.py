@@ -222,6 +222,18 @@ def _pair(t: torch.Tensor):
     return (C.c_int64 * 2)(t.stride(0), t.stride(1))
 
 
+@torch.no_grad()
+def rope_tables(rotary_emb, rows: int, dtype: torch.dtype, device):
+    """The (cos, sin) tables PagedKVCache.append_ragged_rope rotates by, [rows, head_dim / 2] of `dtype` on `device`: the model's rotary
+    module (HF's *RotaryEmbedding: forward(x, position_ids) -> cos, sin [1, rows, head_dim] of x's dtype) run ONCE on arange(rows), and
+    the first half of what it returns - HF duplicates the halves.  Whatever scaling rule the module applies (linear, llama3,
+    attention_scaling) is in the tables: the bits are the model's."""
+    device = torch.device(device)
+    cos, sin = rotary_emb(torch.empty(0, dtype=dtype, device=device), torch.arange(rows, device=device)[None])
+    half = cos.shape[-1] // 2
+    return cos[0, :, :half].contiguous(), sin[0, :, :half].contiguous()
+
+
 def pool_bytes(dtype: torch.dtype, pages: int, slots: int, kv_heads: int, head_dim: int, k_fmt=None, v_fmt=None) -> int:
     """lqer_kv_pool_bytes, or - with the pool's K and V formats, either of which may name nibble codes (ops.nibble_qfmt) -
     lqer_kv_pool_bytes_fmt."""
@@ -616,6 +628,8 @@ class PagedKVCache:
                        the reservation is rolled back
     .append_ragged(seqs, k, v, counts)   k / v [sum(counts), kv_heads, head_dim]: counts[b] more keys for seqs[b] - the decoders' one
                        key and the arrivals' prompt chunks of a scheduler step in ONE launch, with append's bytes, books and refusals
+    .append_ragged_rope(seqs, q, k, v, counts, rope, positions=None, out=None) -> q_rot   append_ragged on the RAW q, k, v of the
+                       projections: the rotary embedding of q and k happens inside the append's launch (rope = rope_tables(...))
     .length(seq);  .pages_free;  .nbytes
     .to_dense(seq) -> QuantizedKVCache (batch 1) with the sequence's bytes - an export, and the test hook (more than 8 query rows
                        need no copy: attention_flexible_paged(kernel="prefill"));  .dequantized(seq) -> (K, V) [1, kv_heads, length,
@@ -824,6 +838,52 @@ class PagedKVCache:
             return
         self._append(seqs, counts, self._launch_append_ragged, k, v)
 
+    @torch.no_grad()
+    def append_ragged_rope(self, seqs, q, k: torch.Tensor, v: torch.Tensor, counts, rope, positions=None, out=None):
+        """append_ragged() on the RAW outputs of a Llama-family layer's q / k / v projections, with the rotary position embedding in
+        the same launch (lqer_kv_pool_append_rope): q [sum(counts), heads, head_dim] and k are rotated by HF's rotate_half rule,
+        rounded to the dtype after each operation - the bits of eager apply_rotary_pos_emb -, the rotated k and v are appended, and the
+        rotated q comes back (out=None: a new tensor; out=q: in place; q=None: K alone, and None comes back).  rope = (cos, sin) of
+        rope_tables(): [rows, head_dim / 2] of the pool's dtype on its device.  New token j of seqs[b] sits at position length(seqs[b])
+        + j - no position is computed on the host -, or at positions[sum(counts[:b]) + j] when `positions`, an int32 tensor
+        [sum(counts)] on the device, is given: a draft tree's base + depth.  The tables need max(length + count) + max(counts) rows
+        without `positions` (the library's bound); with them the range is the caller's to keep.  The uniform case is counts =
+        [n] * len(seqs).  Checks, reservation, window release and rollback are append_ragged's; the attention calls run unchanged."""
+        seqs, counts = _ragged_counts("PagedKVCache.append_ragged_rope", seqs, counts)
+        total, half = sum(counts), self.head_dim // 2
+        want = (total, self.kv_heads, self.head_dim)
+        if k.dim() != 3 or tuple(k.shape) != want or k.shape != v.shape or k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError(f"PagedKVCache.append_ragged_rope: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} for counts {counts} of "
+                             f"[sum(counts), {self.kv_heads}, {self.head_dim}] {self.dtype}")
+        if q is None and out is not None:
+            raise ValueError("PagedKVCache.append_ragged_rope: out without q")
+        if q is not None:
+            if q.dim() != 3 or q.shape[0] != total or q.shape[1] < 1 or q.shape[2] != self.head_dim or q.dtype != self.dtype:
+                raise ValueError(f"PagedKVCache.append_ragged_rope: q {tuple(q.shape)} {q.dtype} for [{total}, heads, {self.head_dim}] {self.dtype}")
+            if out is None:
+                out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+            elif out.shape != q.shape or out.dtype != q.dtype or out.stride(2) != 1:
+                raise ValueError(f"PagedKVCache.append_ragged_rope: out {tuple(out.shape)} {out.dtype} strides {out.stride()} for q {tuple(q.shape)} "
+                                 f"{q.dtype} (rows of head_dim dense)")
+        try:
+            cos, sin = rope
+        except (TypeError, ValueError):
+            raise ValueError("PagedKVCache.append_ragged_rope: rope is the pair (cos, sin) of rope_tables()") from None
+        for t in (cos, sin):
+            if t.dim() != 2 or t.shape[1] != half or t.shape != cos.shape or t.dtype != self.dtype or not t.is_contiguous():
+                raise ValueError(f"PagedKVCache.append_ragged_rope: rope table {tuple(t.shape)} {t.dtype} for [rows, {half}] {self.dtype}, contiguous")
+        if positions is not None and (positions.dim() != 1 or positions.shape[0] != total or positions.dtype != torch.int32 or
+                                      not positions.is_contiguous()):
+            raise ValueError(f"PagedKVCache.append_ragged_rope: positions {tuple(positions.shape)} {positions.dtype} for int32 [{total}]")
+        for name, t in (("q", q), ("out", out), ("k", k), ("v", v), ("cos", cos), ("sin", sin), ("positions", positions)):
+            if t is not None and t.device != self.buf.device:
+                raise ValueError(f"PagedKVCache.append_ragged_rope: {name} on {t.device} for a pool on {self.buf.device}")
+        if not any(counts):
+            self.pt.slots(seqs)
+            return out
+        self._append(seqs, counts, lambda *a: self._launch_append_rope(*a, q, out, cos, sin, positions), k, v)
+        return out
+
     def _call_starts(self, counts):
         """The token starts [len(counts) + 1] of a call with per-sequence counts on the device: one copy, as _call_meta's."""
         starts = [0]
@@ -859,6 +919,25 @@ class PagedKVCache:
                                                              self.kv_heads, self.head_dim, sum(counts), C.byref(self.fmts[1]),
                                                              C.byref(self.fmts[3]), ops._stream(self.device)),
                        "lqer_kv_pool_append_ragged")
+
+    def _launch_append_rope(self, slots, lens, taken, k, v, counts, q, out, cos, sin, positions) -> None:
+        self._upload_rows(slots, taken)
+        if k.stride(2) != 1:
+            k = k.contiguous()
+        if v.stride(2) != 1:
+            v = v.contiguous()
+        if q is not None and q.stride(2) != 1:
+            q = q.contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        qargs = (None, None, None, None, 0) if q is None else (q.data_ptr(), out.data_ptr(), _pair(q), _pair(out), q.shape[1])
+        bound = max(t + c for t, c in zip(lens, counts))  # (max_len: a bound on the lengths after the call, which the tables' rows go by)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().lqer_kv_pool_append_rope(*self._pool_args(), *self._call_meta(slots, lens, bound), self._call_starts(counts),
+                                                           max(counts), *qargs, k.data_ptr(), v.data_ptr(), _pair(k), _pair(v), cos.data_ptr(),
+                                                           sin.data_ptr(), cos.shape[0], ptr(positions), ops._DT[self.dtype], len(slots),
+                                                           self.kv_heads, self.head_dim, sum(counts), C.byref(self.fmts[1]),
+                                                           C.byref(self.fmts[3]), ops._stream(self.device)),
+                       "lqer_kv_pool_append_rope")
 
     # ---- sequences over shared pages (lqer_kv_pool_fork) ----
     def fork(self, seq: int, n: int = 1) -> list:
