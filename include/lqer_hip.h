@@ -568,6 +568,32 @@ int lqer_linear_forward_normed(const lqer_linear_desc_t* desc, const void* h, co
                                int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
                                const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fused LayerNorm: the norm in front of OPT's q/k/v and fc1 inside their activation side (additive to ABI 14) ------------------
+ * OPT (do_layer_norm_before) runs self_attn_layer_norm in front of q/k/v and final_layer_norm in front of fc1 (reference
+ * opt_decoder.py).  The call is that of the fused RMSNorm above with a norm bias b [K] beside the weight w [K] (all of one dtype dt,
+ * fp16 or bf16).  Per token row, in registers, every step an fp32 operation rounded on its own - no fused multiply-add stands for a
+ * multiply followed by an add:
+ *     S1   = sum_k float(h_k)                      in fp32
+ *     mean = S1 / (float)K                         correctly rounded division
+ *     d_k  = float(h_k) - mean
+ *     S2   = sum_k d_k * d_k                       in fp32, a lane's chain as fmaf(d, d, acc)
+ *     rstd = 1.0f / sqrtf(S2 / (float)K + eps)     correctly rounded division and square root
+ *     x_k  = round_dt((d_k * rstd) * float(w_k) + float(b_k))     three fp32 roundings, then one to dt
+ * - nn.LayerNorm's biased variance with one rounding to the tensor dtype, in the centred form (not E[x^2] - mean^2, which loses the
+ * variance of a row whose mean is large against its spread).  Both sums run in the order stated for S above; a k past K adds nothing
+ * to S2 and its x is zero.  x then goes where the x of lqer_quantize_act_xa goes, as above: ONE launch (csrc/act_normed.hip) for
+ * every M >= 1, no scratch, bit-stable; x never reaches memory; a_limbs must be -2; rank 0 writes the image alone.
+ * Refused as the fused RMSNorm entries, and: LQER_E_INVALID for a null norm_bias; LQER_E_UNSUPPORTED for a norm_bias that is not
+ * 16-byte aligned. */
+int lqer_quantize_act_xa_layernormed(const lqer_linear_desc_t* desc, const void* h, const void* norm_weight, const void* norm_bias,
+                                     float eps, int dtype, int64_t M, int64_t ld_h, const void* a_t, int a_limbs, void* xq_bf16,
+                                     void* xaq_bf16, void* stream);
+/* The forward of ONE Linear on LayerNorm(h): the call above, then lqer_linear_gemm, exactly as lqer_linear_forward_normed. */
+int lqer_linear_forward_layernormed(const lqer_linear_desc_t* desc, const void* h, const void* norm_weight, const void* norm_bias,
+                                    float eps, int dtype, int64_t M, int64_t ld_h, const void* w_packed, const void* a_t,
+                                    const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y, int64_t ldy,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- weights of 5..8 bits (the reference's no-LQER baseline: W8A8 block_fp with one block per row and per token,
  * experiments/pipeline/sweep_baseline_no_lqer.sh:73-76, through LinearFlexible, quantized_layers/linear.py:50-64) ---------------
  * The packed image holds 4-bit codes, so a mantissa m of up to 8 bits (|m| <= 127) travels as three signed base-8 digits,

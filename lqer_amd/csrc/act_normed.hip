@@ -23,6 +23,20 @@
 // rank 32 = 96); a fragment register set is at most 32 registers (one step per part from 6 tiles on).
 //
 // LDS: 8 x 8 x 1040 B slabs + 8 x 8 x rp x 4 B partial tiles (65 KiB + 4..32 KiB) + 256 B of row partials.  rank 0: the 256 B alone.
+//
+// NORM = NORM_LAYER: the same kernel behind a LayerNorm with weight and bias (OPT: self_attn_layer_norm -> q/k/v, final_layer_norm -> fc1),
+// the rule of include/lqer_hip.h "fused LayerNorm" - every step an fp32 operation rounded on its own, no fused multiply-add for a
+// multiply followed by an add:
+//   S1   = sum_k float(h_k)                     mean = S1 / (float)K
+//   d_k  = float(h_k) - mean                    S2 = sum_k d_k * d_k (the lane's chain: fmaf(d, d, acc))
+//   rstd = 1.0f / sqrtf(S2 / (float)K + eps)
+//   x_k  = round_dt((d_k * rstd) * float(w_k) + float(b_k))
+// The centred form needs the mean before the first square, so pass 1 runs TWO row reductions over the same registers, each in the order
+// stated above, each through a 256-B LDS area of its own (the second reduction's partials may be written while a slow wave still reads
+// the first's) and one barrier; the fragment requests land under both.  d is recomputed from the row registers wherever it is used -
+// no second copy of the row.  A lane whose chunk lies past K (and so a wave with no slab) holds h = 0 but would hold d = -mean: it adds
+// ZERO to S2 and writes zeros, not b, into the padded k.  The lane's 16 bytes of b per slab travel beside those of w.  LDS: 256 B more.
+// The RMS instantiations keep the statement sequence (and the compiled instruction stream) they had before NORM existed.
 #include "act_rows.h"
 
 namespace lqer {
@@ -32,25 +46,37 @@ using namespace arow;
 
 constexpr int MAX_K = 8192;  // two slabs per wave
 
-__host__ inline size_t lds_bytes_n(int rp) { return lds_bytes(rp) + (size_t)WAVES * ROWS * sizeof(float); }
+// one 256-B area of row partials per reduction: RMSNorm one, LayerNorm two
+__host__ inline size_t lds_bytes_n(int rp, int norm) { return lds_bytes(rp) + (size_t)(norm == NORM_LAYER ? 2 : 1) * WAVES * ROWS * sizeof(float); }
 
-template <int DT, int RT, int NS>
+// LayerNorm's elementwise rule: three fp32 roundings, then one to dt (contraction off: a multiply and the add behind it stay two operations)
+template <int DT>
+__device__ __forceinline__ float layer_norm_x(float h, float mean, float rstd, float w, float b) {
+#pragma clang fp contract(off)
+  const float d = h - mean;
+  const float t = d * rstd;
+  const float u = t * w;
+  return round_dt<DT>(u + b);
+}
+
+template <int DT, int RT, int NS, int NORM>
 __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h, const bf16_t* __restrict__ nw, float eps, int64_t M, int64_t ldh,
                                                      int64_t K, int64_t Kp, const bf16_t* __restrict__ a_frag, bf16_t* __restrict__ xq,
-                                                     bf16_t* __restrict__ xaq, QP qx, QP qa, int L_aout) {
+                                                     bf16_t* __restrict__ xaq, QP qx, QP qa, int L_aout, const bf16_t* __restrict__ nb) {
+  constexpr bool LN = NORM == NORM_LAYER;
   constexpr int NT = RT ? RT : 1, HB = part_steps(RT), NP = STEPS / HB;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t m0 = (int64_t)blockIdx.x * ROWS;
   const int nslab = (int)((Kp + SLAB - 1) / SLAB), nst = (int)(Kp / 32);
-  float* const part = (float*)(smem + lds_bytes(16 * RT));  // [WAVES][ROWS] partial sums of squares
+  float* const part = (float*)(smem + lds_bytes(16 * RT));  // [WAVES][ROWS] partial sums of squares (LN: [2][WAVES][ROWS], S1 then S2)
   unsigned char* const wb = smem + (size_t)wave * ROWS * PITCH;          // this wave's slab: [ROWS][PITCH]
   const unsigned char* const tok = wb + (lane & 7) * PITCH + 16 * (lane >> 4);
 
   // ---- pass 1, requests.  Every load is unconditional and inside its tensor: a row past M reads row M - 1, a chunk past K the row's last
   // chunk, a slab past the last one the last one, a step past the padded K fragment block 0; what is out of range is zeroed where it is used.
-  u32x4 rh[NS][ROWS], rw[NS];
+  u32x4 rh[NS][ROWS], rw[NS], rb[LN ? NS : 1];
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int si = 0; si < NS; ++si) {
@@ -62,6 +88,7 @@ __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h
       rh[si][j] = *(const u32x4*)(h + r * ldh + kc);
     }
     rw[si] = *(const u32x4*)(nw + kc);
+    if constexpr (LN) rb[si] = *(const u32x4*)(nb + kc);
   }
   asm volatile("" ::: "memory");
   const u32x4* const fr = (const u32x4*)a_frag + lane;  // block (step, rank tile): fr[(step * RT + tile) * 64]
@@ -79,39 +106,83 @@ __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h
   };
   if constexpr (RT > 0) load_part(fa, wave, 0), load_part(fb, wave, 1);
 
-  // ---- pass 1, the sums of squares: lane, wave, workgroup - each in one fixed order
-  float mine = 0.f;  // lane j: row j's sum over this wave's slabs
+  float rs[ROWS], mn[LN ? ROWS : 1];  // rstd (and LN: the mean) of the 8 rows, wave-uniform
+  if constexpr (LN) {
+    // ---- pass 1 behind a LayerNorm: two row sums, each in the fixed order of the sum of squares below (lane, tree, LDS [wave][row] in an
+    // area of its own, one barrier, the eight partials in wave order).  term(acc, v, live, j) adds one element of row j to the lane's chain
+    auto row_sum = [&](float* area, auto term) {
+      float mine = 0.f;
 #pragma unroll
-  for (int j = 0; j < ROWS; ++j) {
-    float ss = 0.f;
-    if (m0 + j < M) {  // (wave-uniform)
+      for (int j = 0; j < ROWS; ++j) {
+        float ss = 0.f;
+        if (m0 + j < M) {  // (wave-uniform)
 #pragma unroll
-      for (int si = 0; si < NS; ++si) {
-        const int64_t k = (int64_t)(wave + WAVES * si) * SLAB + 8 * lane;
-        const bool live = k < K;  // (K % 8 == 0: a chunk is inside the tensor or outside it as a whole)
+          for (int si = 0; si < NS; ++si) {
+            const bool live = (int64_t)(wave + WAVES * si) * SLAB + 8 * lane < K;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float a, b;
-          pair_to_f32<DT>(live ? rh[si][j][i] : 0u, a, b);
-          ss = __builtin_fmaf(a, a, ss);
-          ss = __builtin_fmaf(b, b, ss);
+            for (int i = 0; i < 4; ++i) {
+              float a, b;
+              pair_to_f32<DT>(live ? rh[si][j][i] : 0u, a, b);
+              ss = term(term(ss, a, live, j), b, live, j);
+            }
+          }
+#pragma unroll
+          for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
         }
+        mine = lane == j ? ss : mine;
       }
+      if (lane < ROWS) area[wave * ROWS + lane] = mine;
+      __syncthreads();
+      float S = 0.f;
 #pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
-    }
-    mine = lane == j ? ss : mine;
-  }
-  if (lane < ROWS) part[wave * ROWS + lane] = mine;
-  __syncthreads();
-  float rs[ROWS];  // rstd of the 8 rows, wave-uniform
-  {
-    float S = 0.f;
+      for (int w = 0; w < WAVES; ++w) S += area[w * ROWS + (lane & 7)];
+      return S;  // lane l: row l & 7
+    };
+    const float mine_mean = row_sum(part, [](float acc, float v, bool, int) { return acc + v; }) / (float)K;
 #pragma unroll
-    for (int w = 0; w < WAVES; ++w) S += part[w * ROWS + (lane & 7)];
-    const float mine_rstd = 1.0f / sqrtf(S / (float)K + eps);
+    for (int j = 0; j < ROWS; ++j) mn[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_mean), j));
+    // (a chunk past K holds h = 0, its d would be -mean: it adds nothing)
+    const float S2 = row_sum(part + WAVES * ROWS, [&](float acc, float v, bool live, int j) {
+      const float d = live ? v - mn[j] : 0.f;
+      return __builtin_fmaf(d, d, acc);
+    });
+    const float mine_rstd = 1.0f / sqrtf(S2 / (float)K + eps);
 #pragma unroll
     for (int j = 0; j < ROWS; ++j) rs[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_rstd), j));
+  } else {
+    // ---- pass 1, the sums of squares: lane, wave, workgroup - each in one fixed order
+    float mine = 0.f;  // lane j: row j's sum over this wave's slabs
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j) {
+      float ss = 0.f;
+      if (m0 + j < M) {  // (wave-uniform)
+#pragma unroll
+        for (int si = 0; si < NS; ++si) {
+          const int64_t k = (int64_t)(wave + WAVES * si) * SLAB + 8 * lane;
+          const bool live = k < K;  // (K % 8 == 0: a chunk is inside the tensor or outside it as a whole)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            float a, b;
+            pair_to_f32<DT>(live ? rh[si][j][i] : 0u, a, b);
+            ss = __builtin_fmaf(a, a, ss);
+            ss = __builtin_fmaf(b, b, ss);
+          }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
+      }
+      mine = lane == j ? ss : mine;
+    }
+    if (lane < ROWS) part[wave * ROWS + lane] = mine;
+    __syncthreads();
+    {
+      float S = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) S += part[w * ROWS + (lane & 7)];
+      const float mine_rstd = 1.0f / sqrtf(S / (float)K + eps);
+#pragma unroll
+      for (int j = 0; j < ROWS; ++j) rs[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_rstd), j));
+    }
   }
 
   f32x4 acc[NT];
@@ -132,8 +203,15 @@ __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h
         float h0, h1, w0, w1;
         pair_to_f32<DT>(live ? rh[si][j][i] : 0u, h0, h1);
         pair_to_f32<DT>(live ? rw[si][i] : 0u, w0, w1);
-        v[2 * i] = round_dt<DT>(w0 * round_dt<DT>(h0 * rs[j]));
-        v[2 * i + 1] = round_dt<DT>(w1 * round_dt<DT>(h1 * rs[j]));
+        if constexpr (LN) {  // (a chunk past K: zeros, not b)
+          float b0, b1;
+          pair_to_f32<DT>(rb[si][i], b0, b1);
+          v[2 * i] = live ? layer_norm_x<DT>(h0, mn[j], rs[j], w0, b0) : 0.f;
+          v[2 * i + 1] = live ? layer_norm_x<DT>(h1, mn[j], rs[j], w1, b1) : 0.f;
+        } else {
+          v[2 * i] = round_dt<DT>(w0 * round_dt<DT>(h0 * rs[j]));
+          v[2 * i + 1] = round_dt<DT>(w1 * round_dt<DT>(h1 * rs[j]));
+        }
       }
       quant_half_block<DT>(v, qx, w);
       if (k < Kp) *(u32x4*)(xq + (m0 + j) * Kp + k) = (u32x4){w[0], w[1], w[2], w[3]};  // (k past K up to the padded K: zeros)
@@ -168,13 +246,15 @@ __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h
 
 }  // namespace an
 
-// The launch of lqer_quantize_act_xa_normed (api.hip has checked pointers for NULL, the stride against K and eps): everything this kernel
-// does not serve is refused here, in words, with nothing launched.  r == 0: the image alone (a_b16 and xaq unused).
-// check_only: the refusals alone (api.hip asks before it plans the GEMM call).
-int act_normed_dispatch(const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t K, int64_t ldh, const QP& qx, bf16_t* xq,
-                        const void* a_b16, int64_t r, const QP& qa, bf16_t* xaq, hipStream_t st, bool check_only) {
-  auto no = [](const char* why) {
-    set_error("quantize_act_xa_normed: %s", why);
+// The launch of lqer_quantize_act_xa_normed and (norm = NORM_LAYER, nb the norm bias) of lqer_quantize_act_xa_layernormed (api.hip has
+// checked pointers for NULL, the stride against K and eps): everything this kernel does not serve is refused here, in words, with
+// nothing launched.  r == 0: the image alone (a_b16 and xaq unused).  check_only: the refusals alone (api.hip asks before it plans the
+// GEMM call).
+int act_normed_dispatch(int norm, const void* h, const void* nw, const void* nb, float eps, int dtype, int64_t M, int64_t K, int64_t ldh,
+                        const QP& qx, bf16_t* xq, const void* a_b16, int64_t r, const QP& qa, bf16_t* xaq, hipStream_t st, bool check_only) {
+  const char* const what = norm == NORM_LAYER ? "quantize_act_xa_layernormed" : "quantize_act_xa_normed";
+  auto no = [&](const char* why) {
+    set_error("%s: %s", what, why);
     return LQER_E_UNSUPPORTED;
   };
   if (dtype != LQER_F16 && dtype != LQER_BF16) return no("h must be fp16 or bf16 (the two roundings of x are those of a 16-bit eager model)");
@@ -183,6 +263,7 @@ int act_normed_dispatch(const void* h, const void* nw, float eps, int dtype, int
   if (K > an::MAX_K) return no("in_features above 8192 (a wave keeps the rows of at most two 512-k slabs in registers)");
   if (((uintptr_t)h % 16) != 0 || ((ldh * 2) % 16) != 0 || ((uintptr_t)nw % 16) != 0 || ((uintptr_t)xq % 16) != 0)
     return no("h, its row stride, the norm weight and the image must be 16-byte aligned");
+  if (norm == NORM_LAYER && ((uintptr_t)nb % 16) != 0) return no("the norm bias must be 16-byte aligned");
   const int64_t rp = r > 0 ? lqer_padded_r(r) : 0, Kp = lqer_padded_k(K);
   int L = 0;
   if (rp) {
@@ -196,24 +277,28 @@ int act_normed_dispatch(const void* h, const void* nw, float eps, int dtype, int
   if (M == 0 || check_only) return LQER_OK;
   const bf16_t* const a_frag = rp ? (const bf16_t*)a_b16 + rp * Kp : nullptr;
   const unsigned grid = (unsigned)((M + an::ROWS - 1) / an::ROWS);
-  const int lds = (int)an::lds_bytes_n((int)rp);
-  auto run = [&](auto dt, auto ns) {
-    constexpr int DT = decltype(dt)::value, NS = decltype(ns)::value, LIMIT = 160 * 1024;
-    const char* const what = "quantize_act_xa_normed";
-    const bf16_t* const hp = (const bf16_t*)h;
-    const bf16_t* const wp = (const bf16_t*)nw;
-    switch (rp / 16) {  // 16-column tiles of the padded rank
-      case 0: return launch_k<an::k_act_normed<DT, 0, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
-      case 1: return launch_k<an::k_act_normed<DT, 1, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
-      case 2: return launch_k<an::k_act_normed<DT, 2, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
-      case 3: return launch_k<an::k_act_normed<DT, 3, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
-      case 4: return launch_k<an::k_act_normed<DT, 4, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
-      case 6: return launch_k<an::k_act_normed<DT, 6, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
-      default: return launch_k<an::k_act_normed<DT, 8, NS>, LIMIT>(what, grid, 512, lds, st, hp, wp, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L);
+  const int lds = (int)an::lds_bytes_n((int)rp, norm);
+  auto run = [&](auto dt, auto ns, auto nm, auto rt) {
+    constexpr int LIMIT = 160 * 1024;
+    return launch_k<an::k_act_normed<decltype(dt)::value, decltype(rt)::value, decltype(ns)::value, decltype(nm)::value>, LIMIT>(
+        what, grid, 512, lds, st, (const bf16_t*)h, (const bf16_t*)nw, eps, M, ldh, K, Kp, a_frag, xq, xaq, qx, qa, L, (const bf16_t*)nb);
+  };
+  auto by_rt = [&](auto dt, auto ns, auto nm) {  // 16-column tiles of the padded rank
+    switch (rp / 16) {
+      case 0: return run(dt, ns, nm, std::integral_constant<int, 0>{});
+      case 1: return run(dt, ns, nm, std::integral_constant<int, 1>{});
+      case 2: return run(dt, ns, nm, std::integral_constant<int, 2>{});
+      case 3: return run(dt, ns, nm, std::integral_constant<int, 3>{});
+      case 4: return run(dt, ns, nm, std::integral_constant<int, 4>{});
+      case 6: return run(dt, ns, nm, std::integral_constant<int, 6>{});
+      default: return run(dt, ns, nm, std::integral_constant<int, 8>{});
     }
   };
+  auto by_norm = [&](auto dt, auto ns) {
+    return norm == NORM_LAYER ? by_rt(dt, ns, std::integral_constant<int, NORM_LAYER>{}) : by_rt(dt, ns, std::integral_constant<int, NORM_RMS>{});
+  };
   auto by_ns = [&](auto dt) {  // slabs a wave keeps in registers
-    return Kp > 8 * an::SLAB ? run(dt, std::integral_constant<int, 2>{}) : run(dt, std::integral_constant<int, 1>{});
+    return Kp > 8 * an::SLAB ? by_norm(dt, std::integral_constant<int, 2>{}) : by_norm(dt, std::integral_constant<int, 1>{});
   };
   return dtype == LQER_F16 ? by_ns(std::integral_constant<int, LQER_F16>{}) : by_ns(std::integral_constant<int, LQER_BF16>{});
 }

@@ -1,4 +1,4 @@
-// What the row-request activation kernels share (act_gated.hip: h = act(gate) * up; act_normed.hip: x = RMSNorm(h)): a workgroup of 8 waves
+// What the row-request activation kernels share (act_gated.hip: h = act(gate) * up; act_normed.hip: x = RMSNorm(h) or LayerNorm(h)): a workgroup of 8 waves
 // owns 8 token rows over all of K, wave w the 512-k slabs s = w (mod 8), a lane 8 elements of a row.  Each kernel forms its own activation
 // values in registers; from there on the two run the same three pieces:
 //   quant_half_block  the block-of-16 quantizer on the lane's 8 values (the block's other half sits in lane ^ 1) -> 4 words of bf16 image

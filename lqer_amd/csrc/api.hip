@@ -1054,13 +1054,15 @@ int lqer_linear_forward_gated(const lqer_linear_desc_t* d, const void* gate, con
   return linear_gemm_impl(d, ws, M, w_packed, xaq, xaq_row_elems(d), b_t, b_limbs, bias_q, y, dtype, ldy, ws + cv.scratch, cv.gemm_bytes, stream, false, &pl);
 }
 
-// ---- fused RMSNorm (include/lqer_hip.h "fused RMSNorm"): the activation side of the Linears behind a norm, on the raw hidden state ---
-// the checks the two entries share; what the kernel itself does not serve, act_normed_dispatch refuses
-static int normed_check(const char* who, const lqer_linear_desc_t* d, const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t ld_h,
-                        const void* a_t, int a_limbs, void* xq, void* xaq) {
+// ---- fused RMSNorm / LayerNorm (include/lqer_hip.h "fused RMSNorm", "fused LayerNorm"): the activation side of the Linears behind a norm,
+// on the raw hidden state.  The four entries are two bodies: norm = NORM_RMS (nb unused) or NORM_LAYER (nb the norm bias).
+// the checks the entries share; what the kernel itself does not serve, act_normed_dispatch refuses
+static int normed_check(const char* who, int norm, const lqer_linear_desc_t* d, const void* h, const void* nw, const void* nb, float eps, int dtype,
+                        int64_t M, int64_t ld_h, const void* a_t, int a_limbs, void* xq, void* xaq) {
   if (!d) return fail(LQER_E_INVALID, "%s: null descriptor", who);
   if (M < 0 || (!h && M > 0)) return fail(LQER_E_INVALID, "%s: %s", who, M < 0 ? "negative token count" : "null hidden state");
   if (!nw) return fail(LQER_E_INVALID, "%s: null norm weight", who);
+  if (norm == NORM_LAYER && !nb) return fail(LQER_E_INVALID, "%s: null norm bias", who);
   if (ld_h < d->in_features) return fail(LQER_E_INVALID, "%s: row stride %lld of h < in_features %d", who, (long long)ld_h, d->in_features);
   if (!(eps >= 0.0f) || !std::isfinite(eps)) return fail(LQER_E_INVALID, "%s: eps %g must be finite and >= 0", who, (double)eps);
   if (a_limbs != -2) return fail(LQER_E_INVALID, "%s: a_limbs %d: the kernel reads the image of lqer_a_b16_prepare (a_limbs = -2) only", who, a_limbs);
@@ -1074,25 +1076,25 @@ static int normed_check(const char* who, const lqer_linear_desc_t* d, const void
   if (!fmt_ok(&d->x_fmt, ROLE_X) || !fmt_ok(&d->w_fmt, ROLE_W) || (d->rank > 0 && !fmt_ok(&d->a_out_fmt, ROLE_A_OUT))) return LQER_E_UNSUPPORTED;
   if (w_limbs(d) != 1)
     return fail(LQER_E_UNSUPPORTED, "%s: weights of 5..8 bits read three copies of the activation image: compute the norm and call the x entry", who);
-  return act_normed_dispatch(h, nw, eps, dtype, M, d->in_features, ld_h, make_qp(d->x_fmt), (bf16_t*)xq, a_t, d->rank > 0 ? d->rank : 0,
+  return act_normed_dispatch(norm, h, nw, nb, eps, dtype, M, d->in_features, ld_h, make_qp(d->x_fmt), (bf16_t*)xq, a_t, d->rank > 0 ? d->rank : 0,
                              make_qp(d->a_out_fmt), (bf16_t*)xaq, nullptr, true);
 }
 
-int lqer_quantize_act_xa_normed(const lqer_linear_desc_t* d, const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t ld_h,
-                                const void* a_t, int a_limbs, void* xq, void* xaq, void* stream) {
-  const char* const who = "quantize_act_xa_normed";
-  const int rc = normed_check(who, d, h, nw, eps, dtype, M, ld_h, a_t, a_limbs, xq, xaq);
+static int quantize_act_xa_normed_impl(const char* who, int norm, const lqer_linear_desc_t* d, const void* h, const void* nw, const void* nb,
+                                       float eps, int dtype, int64_t M, int64_t ld_h, const void* a_t, int a_limbs, void* xq, void* xaq,
+                                       void* stream) {
+  const int rc = normed_check(who, norm, d, h, nw, nb, eps, dtype, M, ld_h, a_t, a_limbs, xq, xaq);
   if (rc) return rc;
   if (!xq || (d->rank > 0 && !xaq)) return fail(LQER_E_INVALID, "%s: null %s", who, xq ? "xaq" : "activation image");
-  return act_normed_dispatch(h, nw, eps, dtype, M, d->in_features, ld_h, make_qp(d->x_fmt), (bf16_t*)xq, a_t, d->rank > 0 ? d->rank : 0,
+  return act_normed_dispatch(norm, h, nw, nb, eps, dtype, M, d->in_features, ld_h, make_qp(d->x_fmt), (bf16_t*)xq, a_t, d->rank > 0 ? d->rank : 0,
                              make_qp(d->a_out_fmt), (bf16_t*)xaq, (hipStream_t)stream);
 }
 
-int lqer_linear_forward_normed(const lqer_linear_desc_t* d, const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t ld_h,
-                               const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y,
-                               int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* const who = "linear_forward_normed";
-  int rc = normed_check(who, d, h, nw, eps, dtype, M, ld_h, a_t, a_limbs, workspace, nullptr);
+static int linear_forward_normed_impl(const char* who, int norm, const lqer_linear_desc_t* d, const void* h, const void* nw, const void* nb,
+                                      float eps, int dtype, int64_t M, int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t,
+                                      int a_limbs, int b_limbs, const float* bias_q, void* y, int64_t ldy, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  int rc = normed_check(who, norm, d, h, nw, nb, eps, dtype, M, ld_h, a_t, a_limbs, workspace, nullptr);
   if (rc) return rc;
   if (!w_packed || !y || ldy < d->out_features || (d->rank > 0 && !b_t))
     return fail(LQER_E_INVALID, "%s: null weight image, y or B^T image, or ldy %lld < out_features %d", who, (long long)ldy, d->out_features);
@@ -1106,10 +1108,34 @@ int lqer_linear_forward_normed(const lqer_linear_desc_t* d, const void* h, const
   if (pl.rc) return fail(pl.rc, "%s", pl.p.msg);
   unsigned char* const ws = (unsigned char*)workspace;
   void* const xaq = d->rank > 0 ? ws + cv.xaq : nullptr;
-  rc = act_normed_dispatch(h, nw, eps, dtype, M, d->in_features, ld_h, make_qp(d->x_fmt), (bf16_t*)ws, a_t, d->rank > 0 ? d->rank : 0,
+  rc = act_normed_dispatch(norm, h, nw, nb, eps, dtype, M, d->in_features, ld_h, make_qp(d->x_fmt), (bf16_t*)ws, a_t, d->rank > 0 ? d->rank : 0,
                            make_qp(d->a_out_fmt), (bf16_t*)xaq, (hipStream_t)stream);
   if (rc) return rc;
   return linear_gemm_impl(d, ws, M, w_packed, xaq, xaq_row_elems(d), b_t, b_limbs, bias_q, y, dtype, ldy, ws + cv.scratch, cv.gemm_bytes, stream, false, &pl);
+}
+
+int lqer_quantize_act_xa_normed(const lqer_linear_desc_t* d, const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t ld_h,
+                                const void* a_t, int a_limbs, void* xq, void* xaq, void* stream) {
+  return quantize_act_xa_normed_impl("quantize_act_xa_normed", NORM_RMS, d, h, nw, nullptr, eps, dtype, M, ld_h, a_t, a_limbs, xq, xaq, stream);
+}
+
+int lqer_linear_forward_normed(const lqer_linear_desc_t* d, const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t ld_h,
+                               const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y,
+                               int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  return linear_forward_normed_impl("linear_forward_normed", NORM_RMS, d, h, nw, nullptr, eps, dtype, M, ld_h, w_packed, a_t, b_t, a_limbs, b_limbs,
+                                    bias_q, y, ldy, workspace, workspace_bytes, stream);
+}
+
+int lqer_quantize_act_xa_layernormed(const lqer_linear_desc_t* d, const void* h, const void* nw, const void* nb, float eps, int dtype, int64_t M,
+                                     int64_t ld_h, const void* a_t, int a_limbs, void* xq, void* xaq, void* stream) {
+  return quantize_act_xa_normed_impl("quantize_act_xa_layernormed", NORM_LAYER, d, h, nw, nb, eps, dtype, M, ld_h, a_t, a_limbs, xq, xaq, stream);
+}
+
+int lqer_linear_forward_layernormed(const lqer_linear_desc_t* d, const void* h, const void* nw, const void* nb, float eps, int dtype, int64_t M,
+                                    int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                                    const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  return linear_forward_normed_impl("linear_forward_layernormed", NORM_LAYER, d, h, nw, nb, eps, dtype, M, ld_h, w_packed, a_t, b_t, a_limbs,
+                                    b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream);
 }
 
 // ---- the compact image of 2- / 3-bit block_fp weights (include/lqer_hip.h "compact weight image") -----------------------------------

@@ -875,8 +875,11 @@ int act16_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t
 int act_gated_dispatch(const void* gate, const void* up, int act, int dtype, int64_t M, int64_t K, int64_t ldg, int64_t ldu, const QP& qx, bf16_t* xq,
                        const void* a_b16, int64_t r, const QP& qa, bf16_t* xaq, hipStream_t st, bool check_only = false);
 // ... and for the Linears behind an RMSNorm (act_normed.hip): x = w * (h * rstd) formed in registers from the raw hidden state; every M >= 1
-int act_normed_dispatch(const void* h, const void* norm_weight, float eps, int dtype, int64_t M, int64_t K, int64_t ldh, const QP& qx, bf16_t* xq,
-                        const void* a_b16, int64_t r, const QP& qa, bf16_t* xaq, hipStream_t st, bool check_only = false);
+// norm = NORM_LAYER: behind a LayerNorm (OPT), x = ((h - mean) * rstd) * w + b with norm_bias b; NORM_RMS takes no bias (nullptr)
+enum { NORM_RMS = 0, NORM_LAYER = 1 };
+int act_normed_dispatch(int norm, const void* h, const void* norm_weight, const void* norm_bias, float eps, int dtype, int64_t M, int64_t K,
+                        int64_t ldh, const QP& qx, bf16_t* xq, const void* a_b16, int64_t r, const QP& qa, bf16_t* xaq, hipStream_t st,
+                        bool check_only = false);
 size_t a_b16_image_bytes(int64_t K, int64_t r);
 int a_b16_prepare_dispatch(const void* a_t_limbs, int64_t K, int64_t r, void* out, hipStream_t st);
 int act8_fused_dispatch(const void* x, int dtype, int64_t M, int64_t K, int64_t ldx, const QP& qx, void* xq_i8, const void* a_f16, int64_t r,

@@ -42,6 +42,20 @@ def _device_count() -> int:
     return _NDEV[0]
 
 
+def _arm(h: torch.Tensor, *operands):
+    """A fused norm hands a consumer (a SharedActivation group, a lone Linear) its RAW hidden state: the consumer's next call on this
+    very tensor object, unmodified (object identity + version counter; inference tensors have no counter), starts from norm(h)."""
+    return (h, None if h.is_inference() else h._version) + operands
+
+
+def _armed_for(a, x: torch.Tensor):
+    """The armed record if x is the tensor it was armed with, unmodified; else None."""
+    if a is None:
+        return None
+    h = a[0]() if isinstance(a[0], weakref.ref) else a[0]
+    return a if (h is x and a[1] == (None if x.is_inference() else x._version)) else None
+
+
 class _LinearBase(nn.Linear):
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None,
                  q_config: dict = None, l_config: dict = None) -> None:
@@ -61,6 +75,8 @@ class _LinearBase(nn.Linear):
         self._w_ver = None         # (weight._version, bias._version) when the images were built: an in-place write to the
                                    # parameters (`with torch.no_grad(): mod.weight.copy_(W2)`) is seen by the next forward
         self._group = None         # SharedActivation of Linears fed by the same tensor (models.quantize_model)
+        self._armed = None         # _arm(h, ...): a fused LayerNorm's raw hidden state for the next forward (arm_layer_normed)
+        self.layer_normed_rounds = 0  # forwards that ran lqer_linear_forward_layernormed
         self._fw_cache = {}        # token count -> (descriptor, workspace bytes)
         self._x_f16 = False        # pass-through fp16 activations on the fp16 MFMA route (decided when the images are built)
         self.a16_native = True     # False: keep pass-through fp16 activations on the bf16-limb route
@@ -246,6 +262,7 @@ class _LinearBase(nn.Linear):
         # copy.deepcopy / pickle: the per-token-count launch cache holds raw device pointers of THIS module's images
         st = self.__dict__.copy()
         st["_fw_cache"] = {}
+        st["_armed"] = None
         # the copy's parameters are new tensors with version counters of their own: its first forward adopts them instead of
         # mistaking the copy for an in-place write (which would quantize the already quantized weight a second time)
         st["_w_ver"] = None
@@ -456,6 +473,11 @@ class _LinearBase(nn.Linear):
             y = g.take(self, x)
             if y is not None:
                 return y
+        a = self._armed
+        if a is not None:  # a fused LayerNorm handed this Linear its raw hidden state (one shot)
+            self._armed = None
+            if _armed_for(a, x) is not None:
+                return self.forward_layer_normed(x, a[2], a[4], a[3])
         if not self.is_ptq:
             raise NotImplementedError("lqer_amd implements the PTQ inference branch only (q_config['is_ptq'] = True)")
         if not x.is_cuda:
@@ -726,15 +748,16 @@ class _LinearBase(nn.Linear):
             img = p["a_t_b16_normed"] = ops.a_b16_image(p["a_t"], self.in_features, self.rank)
         return img
 
-    def _forward_normed_hip(self, h: torch.Tensor, nw: torch.Tensor, eps: float) -> Optional[torch.Tensor]:
-        """The fused entry, or None where the kernel does not serve this module / these tensors (the caller computes the norm with torch)."""
+    def _forward_normed_hip(self, h: torch.Tensor, nw: torch.Tensor, eps: float, nb: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """The fused entry (nb: the LayerNorm one), or None where the kernel does not serve this module / these tensors (the caller
+        computes the norm with torch)."""
         self._written_in_place()
         if self._packed is None or self.w_is_quantized is False:
             self._pack()
         K, N = self.in_features, self.out_features
         M = h.numel() // K
         fx, fa = self._fmt["x"], self._fmt.get("A_out")
-        if (M < self.normed_min_m or K % 16 or K > 8192 or self._weight_image == "narrow" or ops.w_limbs(self._fmt["w"]) != 1 or self._x_i8
+        if (M < (self.normed_min_m if nb is None else self.layer_normed_min_m) or K % 16 or K > 8192 or self._weight_image == "narrow" or ops.w_limbs(self._fmt["w"]) != 1 or self._x_i8
                 or fx.kind != _lib.Q_MXINT or fx.block != 16 or fx.width > 9):
             return None
         a_img = None
@@ -748,7 +771,7 @@ class _LinearBase(nn.Linear):
         h2 = h.reshape(-1, K)
         if h2.stride(-1) != 1 or h2.data_ptr() % 16 or (M > 1 and (h2.stride(0) < K or h2.stride(0) % 8)):
             h2 = h2.contiguous()
-        nw = nw if nw.is_contiguous() and nw.data_ptr() % 16 == 0 else nw.clone()
+        nw, nb = (None if t is None else t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone() for t in (nw, nb))
         y = torch.empty(M, N, dtype=h.dtype, device=h.device)
         key = ("normed", M, h.dtype, self.tuning)
         ent = self._fw_cache.get(key)
@@ -762,13 +785,50 @@ class _LinearBase(nn.Linear):
         desc, ws_bytes, dt, consts = ent
         st = ops._stream(h.device)
         ws = ops.workspace_on(h.device, st, ws_bytes)
-        rc = _lib.lib().lqer_linear_forward_normed(C.byref(desc), h2.data_ptr(), nw.data_ptr(), eps, dt, M, h2.stride(0) if M > 1 else K, *consts,
-                                                   y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        tail = (eps, dt, M, h2.stride(0) if M > 1 else K, *consts, y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        if nb is None:
+            rc = _lib.lib().lqer_linear_forward_normed(C.byref(desc), h2.data_ptr(), nw.data_ptr(), *tail)
+        else:
+            rc = _lib.lib().lqer_linear_forward_layernormed(C.byref(desc), h2.data_ptr(), nw.data_ptr(), nb.data_ptr(), *tail)
         if rc == -2:  # LQER_E_UNSUPPORTED (nothing was launched): the torch norm + forward()
             return None
         if rc:
-            check(rc, "lqer_linear_forward_normed")
+            check(rc, "lqer_linear_forward_normed" if nb is None else "lqer_linear_forward_layernormed")
+        if nb is not None:
+            self.layer_normed_rounds += 1
         return y.reshape(*h.shape[:-1], N)
+
+    # -- fused LayerNorm ----------------------------------------------------------------------
+    # Token count from which forward_layer_normed (and so a lone Linear armed by a fused LayerNorm: OPT's fc1 under
+    # models.quantize_model(fuse_layernorm=True)) takes the fused entry.  tools/rmsnorm_bench.py --norm layer at OPT-6.7B's fc1
+    # (profiles/layernorm_fused.json, DESIGN.md "Fused LayerNorm"): 1.01x / 1.04x / 1.00x / 0.98x the time of F.layer_norm + forward at
+    # M = 64 / 512 / 2048 / 8192; the fused leg's fastest round lies above the torch leg's median at 512 and at no larger size
+    layer_normed_min_m = 2048
+
+    def forward_layer_normed(self, h: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float) -> torch.Tensor:
+        """This Linear on x = LayerNorm(h) = ((h - mean) * rstd) * weight + bias (nn.LayerNorm's biased variance, one rounding to h's
+        dtype) with the norm formed inside the activation-side kernel (csrc/act_normed.hip through lqer_linear_forward_layernormed: two
+        launches, x never written) where that kernel applies - the conditions of forward_normed, from layer_normed_min_m tokens on.
+        Elsewhere torch.nn.functional.layer_norm and forward().  Against that route some x differ by one step of the dtype (the
+        kernel's fp32 rule is include/lqer_hip.h's; torch's own kernel sums in another order)."""
+        K = self.in_features
+        if h.shape[-1] != K or weight.shape != (K,) or bias.shape != (K,):
+            raise RuntimeError(f"expected last dim {K}, got h {tuple(h.shape)}, weight {tuple(weight.shape)}, bias {tuple(bias.shape)}")
+        if (self.is_ptq and h.is_cuda and h.dtype in (torch.float16, torch.bfloat16) and weight.dtype == h.dtype == bias.dtype
+                and weight.device == h.device == bias.device and not (self._tiles and self._needs_tiles(h))):
+            if _device_count() > 1 and h.device.index != torch.cuda.current_device():
+                with torch.cuda.device(h.device):
+                    y = self._forward_normed_hip(h, weight.data, float(eps), bias.data)
+            else:
+                y = self._forward_normed_hip(h, weight.data, float(eps), bias.data)
+            if y is not None:
+                return y
+        return _LinearBase.forward(self, torch.nn.functional.layer_norm(h, (K,), weight, bias, eps))
+
+    def arm_layer_normed(self, h: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float) -> None:
+        """The next forward on this very tensor, unmodified, is forward_layer_normed(h, weight, bias, eps): h is NOT a valid x, so where
+        the fused entry does not serve the call this Linear computes the norm with torch itself."""
+        self._armed = _arm(h, weight, float(eps), bias)
 
     def __repr__(self):
         return "{}(in_features={}, out_features={}, bias={}, is_ptq={}, rank={}, backend=hip/gfx950{})".format(
@@ -831,7 +891,7 @@ class SharedActivation:
         self._dstream = None  # ... and the stream they were launched on
         self._dys = None      # outputs of the current round, one per member
         self._dserved = set()
-        self._armed = None    # (h or a weak reference to it, its version, norm weight, eps): a fused norm's raw hidden state (arm_normed)
+        self._armed = None    # _arm(h, norm weight, eps, norm bias or None): a fused norm's raw hidden state (arm_normed, arm_layer_normed)
         if self.enabled:
             for i, m in enumerate(self.members):
                 m._group = self
@@ -886,14 +946,24 @@ class SharedActivation:
             self._cat["a_t_b16"] = ops.a_b16_image(a_t, K, off)
 
     # -- fused RMSNorm: a round started from the raw hidden state ------------------------------------------------------------------
-    def normed_serves(self, h: torch.Tensor) -> bool:
-        """Will a round of this group on h run the fused-norm kernel (lqer_quantize_act_xa_normed)?  Asked by the norm in front of the
-        group BEFORE it decides to hand the raw hidden state on: everything the kernel or this route refuses is answered here."""
+    # Token count from which a round armed by a fused LayerNorm takes lqer_quantize_act_xa_layernormed (the q/k/v group of an OPT layer).
+    # tools/rmsnorm_bench.py --norm layer at OPT-6.7B's q/k/v (profiles/layernorm_fused.json, DESIGN.md "Fused LayerNorm"): 0.98x / 1.04x /
+    # 1.01x / 1.02x the time of F.layer_norm + the group's forward at M = 64 / 512 / 2048 / 8192, the fused leg's fastest round above the
+    # torch leg's median at 512 and at 8192 - no measured size from which it is no slower at every larger one, so by default a group
+    # never takes the entry (set a token count to switch it on)
+    layer_normed_min_m = float("inf")
+
+    def normed_serves(self, h: torch.Tensor, layer_norm: bool = False) -> bool:
+        """Will a round of this group on h run the fused-norm kernel (lqer_quantize_act_xa_normed; layer_norm: ..._layernormed)?  Asked by
+        the norm in front of the group BEFORE it decides to hand the raw hidden state on: everything the kernel or this route refuses is
+        answered here."""
         m0 = self.members[0]
         K = m0.in_features
         M = h.numel() // K if K else 0
+        if layer_norm and M < self.layer_normed_min_m:
+            return False
         if (not self.enabled or not h.is_cuda or h.dtype not in (torch.float16, torch.bfloat16) or h.shape[-1] != K or K % 16 or K > 8192
-                or M <= 8 or M < m0.normed_min_m or not h.is_contiguous() or h.data_ptr() % 16
+                or M <= 8 or (M < m0.normed_min_m and not layer_norm) or not h.is_contiguous() or h.data_ptr() % 16
                 or any(m._packed_only or not m.is_ptq or m.weight.device != h.device for m in self.members)):
             return False
         fx, fa = m0._fmt["x"], m0._fmt["A_out"]
@@ -911,14 +981,11 @@ class SharedActivation:
 
     def arm_normed(self, h: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> None:
         """The next round on this very tensor, unmodified, starts from RMSNorm(h) formed inside the group's quantizer launch."""
-        self._armed = (h, None if h.is_inference() else h._version, norm_weight, float(eps))
+        self._armed = _arm(h, norm_weight, float(eps), None)
 
-    def _armed_for(self, x: torch.Tensor):
-        a = self._armed
-        if a is None:
-            return None
-        h = a[0]() if isinstance(a[0], weakref.ref) else a[0]
-        return a if (h is x and a[1] == (None if x.is_inference() else x._version)) else None
+    def arm_layer_normed(self, h: torch.Tensor, norm_weight: torch.Tensor, norm_bias: torch.Tensor, eps: float) -> None:
+        """The same for a LayerNorm with weight and bias (lqer_quantize_act_xa_layernormed)."""
+        self._armed = _arm(h, norm_weight, float(eps), norm_bias)
 
     def take(self, mod, x):
         """A member comes with the tensor of the open decode round: its output, once, if the tensor is unmodified."""
@@ -1015,7 +1082,7 @@ class SharedActivation:
     @torch.no_grad()
     def forward_member(self, mod, x, x2, y) -> bool:
         """Run `mod`'s forward on the shared images; False = not applicable, the caller takes the ordinary route."""
-        armed = self._armed_for(x)  # a fused norm handed the group its RAW hidden state: this round starts from RMSNorm(x)
+        armed = _armed_for(self._armed, x)  # a fused norm handed the group its RAW hidden state: this round starts from RMSNorm(x)
         if not self.enabled or any(m._packed_only for m in self.members):  # (a packed checkpoint carries no dense A)
             if armed is not None:
                 raise RuntimeError("SharedActivation: a round armed by a fused norm cannot be served (normed_serves() had said it would)")
@@ -1082,11 +1149,14 @@ class SharedActivation:
             pool["owner"] = (id(self), self._round)
             b = {"xq": pool["xq"].data_ptr(), "xaq": pool["xaq"].data_ptr(), "keep": (pool["xq"], pool["xaq"])}
             if armed is not None:  # norm + quantizer + x A + A_out in one launch; the members' GEMM calls below are untouched
-                nw = armed[2].data
-                rc = L.lqer_quantize_act_xa_normed(C.byref(plan["gdesc"]), x2.data_ptr(), nw.data_ptr(), armed[3], dtc, M, x2.stride(0),
-                                                   self._cat["a_t_b16"].data_ptr(), -2, b["xq"], b["xaq"], st)
+                nw, nb = armed[2].data, armed[4]
+                tail = (armed[3], dtc, M, x2.stride(0), self._cat["a_t_b16"].data_ptr(), -2, b["xq"], b["xaq"], st)
+                if nb is None:
+                    rc = L.lqer_quantize_act_xa_normed(C.byref(plan["gdesc"]), x2.data_ptr(), nw.data_ptr(), *tail)
+                else:
+                    rc = L.lqer_quantize_act_xa_layernormed(C.byref(plan["gdesc"]), x2.data_ptr(), nw.data_ptr(), nb.data.data_ptr(), *tail)
                 if rc:
-                    check(rc, "lqer_quantize_act_xa_normed (shared input)")
+                    check(rc, "lqer_quantize_act_xa_normed (shared input)" if nb is None else "lqer_quantize_act_xa_layernormed (shared input)")
                 self.normed_rounds += 1
             else:
                 rc = L.lqer_quantize_act_xa(C.byref(plan["gdesc"]), x2.data_ptr(), dtc, M, x2.stride(0) if M > 1 else K,

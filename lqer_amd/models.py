@@ -111,7 +111,8 @@ def _fuse_norm(layer: nn.Module, table: dict) -> None:
     """One decoder layer's two norms -> a subclass whose forward arms the group behind it (no module is added, state-dict keys stay,
     deep copies keep working).  Only weight * (x * rsqrt(mean x^2 + eps)) is served: HF's LlamaRMSNorm / MistralRMSNorm."""
     if table is not _LLAMA_LIKE:
-        raise NotImplementedError("fuse_norm: OPT's LayerNorm is not of the form weight * (x * rsqrt(mean x^2 + eps)); not served")
+        raise NotImplementedError("fuse_norm: OPT's LayerNorm is not of the form weight * (x * rsqrt(mean x^2 + eps)); not served "
+                                  "(fuse_layernorm=True serves it)")
     for name, (parent, first) in _NORM_IN_FRONT.items():
         norm = getattr(layer, name, None)
         form = (norm is not None and not isinstance(norm, nn.LayerNorm) and type(norm).__name__.endswith("RMSNorm")
@@ -130,8 +131,50 @@ def _fuse_norm(layer: nn.Module, table: dict) -> None:
         norm.__class__ = _FUSED_NORM_CLS[cls]
 
 
+def _fused_layernorm_forward(self, hidden_states):
+    """The LayerNorm in front of OPT's q/k/v group or of fc1 under fuse_layernorm: the RAW hidden state is handed on and the consumer is
+    armed with it, the weight, the bias and eps.  A group must answer first that its round will run the fused kernel (its members take
+    whatever tensor they are handed for x); a lone Linear computes the norm with torch itself where the kernel does not serve the call."""
+    c, w, b, h = self._lqer_consumer, self.weight, self.bias, hidden_states
+    if (len(self.normalized_shape) == 1 and h.is_cuda and w.dtype == h.dtype == b.dtype and w.device == h.device == b.device
+            and (isinstance(c, LinearFlexibleLqer) or (all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (w, b))
+                                                       and c.normed_serves(h, layer_norm=True)))):
+        c.arm_layer_normed(h, w, b, self.eps)
+        return h
+    return nn.LayerNorm.forward(self, h)
+
+
+class _FusedLayerNorm(nn.LayerNorm):
+    forward = _fused_layernorm_forward
+
+
+_LAYERNORM_IN_FRONT = {"self_attn_layer_norm": ("self_attn", "q_proj"), "final_layer_norm": ("", "fc1")}
+
+
+def _fuse_layernorm(model: nn.Module, layer: nn.Module, table: dict) -> None:
+    """One OPT decoder layer's two LayerNorms -> _FusedLayerNorm (a class swap: no module is added, state-dict keys stay, deep copies
+    keep working): self_attn_layer_norm arms the q/k/v group, final_layer_norm arms fc1."""
+    if table is not _OPT:
+        raise NotImplementedError("fuse_layernorm: serves OPT's LayerNorm in front of q/k/v and fc1; a Llama-like model's RMSNorm is "
+                                  "fuse_norm=True's")
+    if not getattr(layer, "do_layer_norm_before", getattr(model.config, "do_layer_norm_before", True)):
+        raise NotImplementedError("fuse_layernorm: do_layer_norm_before=False (OPT-350m) applies the norms behind the residual additions, "
+                                  "not in front of a Linear")
+    for name, (parent, first) in _LAYERNORM_IN_FRONT.items():
+        norm = getattr(layer, name, None)
+        if type(norm) not in (nn.LayerNorm, _FusedLayerNorm) or norm.weight is None or norm.bias is None:
+            raise NotImplementedError(f"fuse_layernorm: {name} ({type(norm).__name__}) is not an nn.LayerNorm with weight and bias")
+        lin = getattr(getattr(layer, parent) if parent else layer, first)
+        consumer = lin if not parent else getattr(lin, "_group", None)
+        if not isinstance(consumer, (LinearFlexibleLqer, SharedActivation)):  # (no enabled group / a plain LinearFlexible: left as it is)
+            continue
+        norm.__dict__["_lqer_consumer"] = consumer
+        norm.__class__ = _FusedLayerNorm
+
+
 def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], share_inputs: bool = True,
-                   weight_image: str = "standard", fuse_mlp: bool = False, fuse_norm: bool = False) -> nn.Module:
+                   weight_image: str = "standard", fuse_mlp: bool = False, fuse_norm: bool = False,
+                   fuse_layernorm: bool = False) -> nn.Module:
     """Replace the projections of every decoder layer in place; weights are carried over.  share_inputs: projections
     fed by the same tensor quantize it once and share one side GEMM (linear.SharedActivation); per-projection results
     are unchanged up to the fp32 summation order of the side product.  weight_image: "narrow" makes every projection keep the
@@ -139,7 +182,9 @@ def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], s
     it packs).  fuse_mlp: the activation between the MLP's projections runs inside the down projection's activation-side kernel
     (linear._LinearBase.forward_gated: silu(gate) * up for Llama-like layers, relu for OPT's fc2) instead of as torch launches.  fuse_norm: the RMSNorm in front of
     q/k/v and of gate/up (Llama-like layers with share_inputs) runs inside the group's quantizer launch (csrc/act_normed.hip) from
-    linear._LinearBase.normed_min_m tokens on - the normalised tensor is never written; other norms raise NotImplementedError."""
+    linear._LinearBase.normed_min_m tokens on - the normalised tensor is never written; other norms raise NotImplementedError.
+    fuse_layernorm: the same for an OPT layer's LayerNorms (do_layer_norm_before): self_attn_layer_norm inside the q/k/v group's
+    quantizer launch, final_layer_norm inside fc1's, from the layer_normed_min_m tokens of linear.SharedActivation / _LinearBase on."""
     layers, table = _decoder_layers(model)
     for layer_id, layer in enumerate(layers):
         for group, names in table.items():
@@ -165,6 +210,8 @@ def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], s
             _fuse_mlp(model, layer, table)
         if fuse_norm:
             _fuse_norm(layer, table)
+        if fuse_layernorm:
+            _fuse_layernorm(model, layer, table)
     return model
 
 

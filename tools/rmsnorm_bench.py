@@ -5,7 +5,7 @@
     leg B   the group armed with (h, weight, eps), every member's forward on h             (lqer_quantize_act_xa_normed once -
             csrc/act_normed.hip - + the same GEMM calls; x is never written)
 
-    python tools/rmsnorm_bench.py [--rounds 12] [--rotate 6] [--out profiles/rmsnorm_fused.json]
+    python tools/rmsnorm_bench.py [--norm rms|layer] [--rounds 12] [--rotate 6] [--out profiles/rmsnorm_fused.json]
 
 Shapes: the q/k/v group (4096 -> 3 x 4096, rank 32) and the gate/up group (4096 -> 2 x 11008, rank 32), W4A8 MXINT in blocks of 16
 (bench.MXINT_Q), fp16, at M = 64, 512, 2048, 8192.
@@ -16,7 +16,15 @@ spread (min, max).  What is timed is a CALL as a user makes it, Python and ctype
 launches (by construction: leg A = the 8 torch kernels of the HF formula + the two of the group's quantizer and side product + one
 GEMM per member; leg B = 1 + one GEMM per member) and the algorithmic bytes computed from the shapes.  `no_slower` marks a size where
 leg B's median is at or below leg A's; LinearFlexibleLqer.normed_min_m is the smallest M from which it holds for both groups at every
-larger measured M.  Not part of bench.py.  Needs a GPU: there is no fall-back."""
+larger measured M.  Not part of bench.py.  Needs a GPU: there is no fall-back.
+
+--norm layer: the same for the LayerNorms of an OPT-6.7B layer (profiles/layernorm_fused.json): leg A = F.layer_norm (ONE launch) + the
+forward, leg B = the consumer armed with (h, weight, bias, eps) (lqer_quantize_act_xa_layernormed / lqer_linear_forward_layernormed).  The
+customers are the q/k/v group (4096 -> 3 x 4096) and fc1 alone (4096 -> 16384; its forward's activation side is one launch from 1024 to
+4096 tokens, two elsewhere).  Leg A moves 4 bytes per element beyond leg B: x written by the norm and read by the quantizer.  Each
+customer's layer_normed_min_m is the smallest M from which, at that size and every larger one, leg B is not `fused_slower`: its FASTEST
+round above leg A's median (slow outliers widen a leg's max with the number of rounds, so the spread is taken on the side that cannot
+be noise from other work); None: no such M, the default must never take the fused entry."""
 import argparse
 import copy
 import json
@@ -33,7 +41,7 @@ from benchlib.hipevents import HipEvent  # noqa: E402
 from benchlib.workloads import MXINT_Q, make_weights  # noqa: E402
 
 K, RANK, EPS = 4096, 32, 1e-5
-GROUPS = {"qkv": (4096, 4096, 4096), "gate_up": (11008, 11008)}
+GROUPS = {"rms": {"qkv": (4096, 4096, 4096), "gate_up": (11008, 11008)}, "layer": {"qkv": (4096, 4096, 4096), "fc1": (16384,)}}
 TOKENS = [64, 512, 2048, 8192]
 EV_FLAGS = 0x20000000  # hipEventDisableSystemFence (benchlib.hipevents)
 DEV = "cuda:0"
@@ -52,7 +60,7 @@ def _round(calls, stream, e0, e1):
     return e0.elapsed_time(e1) * 1e3 / len(calls)
 
 
-def _bytes(M, mods):
+def _bytes(M, mods, norm_extra):
     """Algorithmic bytes of the two legs from the shapes: what both move (h read once, the image written once and read by every member's
     GEMM, xaq, weights, A^T, B^T, y) + the norm's own traffic on leg A (the HF formula: h read and an fp32 copy written, that copy read by
     pow and by the multiply, an fp32 product written and read by the cast, x written by the cast, read and written by the weight multiply,
@@ -64,26 +72,33 @@ def _bytes(M, mods):
     common = M * K * 2 + M * Kp * 2 + 2 * M * rp * 2 + 2 * rp * Kp * 2
     for m in mods:
         common += M * Kp * 2 + m._packed["w"].numel() + L.lqer_padded_r(m.rank) * L.lqer_padded_n(m.out_features) * 2 + M * m.out_features * 2
-    return {"torch_norm": common + 30 * M * K, "fused_norm": common}
+    return {"torch_norm": common + norm_extra * M * K, "fused_norm": common}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--rotate", type=int, default=6)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rmsnorm_fused.json"))
+    ap.add_argument("--norm", choices=("rms", "layer"), default="rms")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    layer = a.norm == "layer"
+    a.out = a.out or os.path.join(ROOT, "profiles", "layernorm_fused.json" if layer else "rmsnorm_fused.json")
     assert torch.cuda.is_available(), "needs a GPU"
     import lqer_amd
     from lqer_amd import ops
     from lqer_amd.linear import SharedActivation
 
-    lqer_amd.LinearFlexibleLqer.normed_min_m = 1  # (leg B is the fused entry at every size, whatever the default keeps)
-    norm = lqer_amd.LinearFlexibleLqer.rms_norm_torch
+    # (leg B is the fused entry at every size, whatever the defaults keep)
+    lqer_amd.LinearFlexibleLqer.normed_min_m = lqer_amd.LinearFlexibleLqer.layer_normed_min_m = SharedActivation.layer_normed_min_m = 1
+    if layer:
+        norm = lambda h, wb, eps: torch.nn.functional.layer_norm(h, (K,), wb[0], wb[1], eps)
+    else:
+        norm = lambda h, wb, eps: lqer_amd.LinearFlexibleLqer.rms_norm_torch(h, wb[0], eps)
     st = ops._stream(torch.device(DEV))
     e0, e1 = HipEvent(EV_FLAGS), HipEvent(EV_FLAGS)
     rows = []
-    for gname, outs in GROUPS.items():
+    for gname, outs in GROUPS[a.norm].items():
         protos = []
         for i, N in enumerate(outs):
             W, A, B = make_weights(torch.Generator().manual_seed(11 + i), K, N, RANK)
@@ -93,27 +108,33 @@ def main():
             m.pack()
             protos.append(m)
         copies = [[copy.deepcopy(m) for m in protos] for _ in range(a.rotate)]
-        groups = [SharedActivation(ms) for ms in copies]
-        assert all(g.enabled for g in groups)
+        groups = [SharedActivation(ms) if len(ms) > 1 else ms[0] for ms in copies]  # (a lone Linear is its own consumer)
+        assert all(g.enabled for g in groups if len(outs) > 1)
+        fused_rounds = (lambda g: g.normed_rounds) if len(outs) > 1 else (lambda g: g.layer_normed_rounds)
         for M in TOKENS:
             gen = torch.Generator().manual_seed(M)
             hs = [torch.randn(M, K, generator=gen).half().to(DEV) for _ in range(a.rotate)]
-            ws = [(1 + 0.1 * torch.randn(K, generator=gen)).half().to(DEV) for _ in range(a.rotate)]
+            ws = [((1 + 0.1 * torch.randn(K, generator=gen)).half().to(DEV), (0.1 * torch.randn(K, generator=gen)).half().to(DEV))
+                  for _ in range(a.rotate)]  # (weight, bias: the RMSNorm takes the weight alone)
 
             def leg_a(ms, h, w):
                 x = norm(h, w, EPS)
                 return [m(x) for m in ms]
 
             def leg_b(g, ms, h, w):
-                assert g.normed_serves(h)  # (the question the fused norm module asks before it hands h on)
-                g.arm_normed(h, w, EPS)
+                if len(ms) > 1:
+                    assert g.normed_serves(h, layer)  # (the question the fused norm module asks before it hands h on)
+                if layer:
+                    g.arm_layer_normed(h, w[0], w[1], EPS)
+                else:
+                    g.arm_normed(h, w[0], EPS)
                 return [m(h) for m in ms]
 
             legs = {"torch_norm": [(lambda ms=ms, h=h, w=w: leg_a(ms, h, w)) for ms, h, w in zip(copies, hs, ws)],
                     "fused_norm": [(lambda g=g, ms=ms, h=h, w=w: leg_b(g, ms, h, w)) for g, ms, h, w in zip(groups, copies, hs, ws)]}
-            n0 = groups[0].normed_rounds
+            n0 = fused_rounds(groups[0])
             ya, yb = legs["torch_norm"][0](), legs["fused_norm"][0]()
-            assert groups[0].normed_rounds == n0 + 1  # leg B really is the normed entry
+            assert fused_rounds(groups[0]) == n0 + 1  # leg B really is the normed entry
             err = max(float((p.float() - q.float()).norm() / p.float().norm()) for p, q in zip(ya, yb))
             del ya, yb
             times = {k: [] for k in legs}
@@ -123,29 +144,36 @@ def main():
                     if r >= 2:
                         times[k].append(t)
             sa, sb = _stats(times["torch_norm"]), _stats(times["fused_norm"])
-            nb = _bytes(M, protos)
+            nb = _bytes(M, protos, 4 if layer else 30)
+            act_side = 2 if len(outs) > 1 or not 1024 <= M <= 4096 else 1  # (launches of the torch leg's quantizer + side product)
             row = {"group": gname, "M": M, "K": K, "N": list(outs), "rank": RANK,
-                   "torch_norm": dict(sa, launches=8 + 2 + len(outs), algorithmic_bytes=nb["torch_norm"]),
+                   "torch_norm": dict(sa, launches=(1 if layer else 8) + act_side + len(outs), algorithmic_bytes=nb["torch_norm"]),
                    "fused_norm": dict(sb, launches=1 + len(outs), algorithmic_bytes=nb["fused_norm"]),
                    "time_ratio": round(sb["ms"] / sa["ms"], 4), "no_slower": bool(sb["ms"] <= sa["ms"]),
-                   "slower_beyond_spread": bool(sb["ms"] > sa["max_ms"]), "max_rel_l2_between_legs": err}
+                   "slower_beyond_spread": bool(sb["ms"] > sa["max_ms"]), "fused_slower": bool(sb["min_ms"] > sa["ms"]),
+                   "max_rel_l2_between_legs": err}
             rows.append(row)
             print(json.dumps(row), flush=True)
             del hs, ws, legs
         del copies, groups, protos
         SharedActivation.release_pool()
         torch.cuda.empty_cache()
-    ok = [M for M in TOKENS if all(r["no_slower"] for r in rows if r["M"] >= M)]
-    doc = {"tool": "tools/rmsnorm_bench.py", "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "rotate": a.rotate,
+    if layer:  # per customer
+        ok = {g: [M for M in TOKENS if not any(r["fused_slower"] for r in rows if r["group"] == g and r["M"] >= M)] for g in GROUPS["layer"]}
+        min_m = {g: (min(v) if v else None) for g, v in ok.items()}
+    else:
+        ok = [M for M in TOKENS if all(r["no_slower"] for r in rows if r["M"] >= M)]
+        min_m = min(ok) if ok else None
+    doc = {"tool": "tools/rmsnorm_bench.py --norm " + a.norm, "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "rotate": a.rotate,
            "note": "per-call times: one HIP event pair around `rotate` calls of one leg, each on another copy of h, the norm weight and the "
                    "group's modules; median / min / max over the rounds, the legs alternating; Python and ctypes included on both legs; "
                    "launches by construction, bytes from the shapes",
-           "normed_min_m": min(ok) if ok else None, "rows": rows}
+           ("layer_normed_min_m" if layer else "normed_min_m"): min_m, "rows": rows}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
-    print(f"wrote {a.out}: the fused leg is no slower than torch norm + forward for both groups from M = {doc['normed_min_m']} on")
+    print(f"wrote {a.out}: the fused leg is no slower than torch norm + forward from M = {min_m} on")
 
 
 if __name__ == "__main__":
