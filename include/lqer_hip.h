@@ -594,6 +594,36 @@ int lqer_linear_forward_layernormed(const lqer_linear_desc_t* desc, const void* 
                                     const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y, int64_t ldy,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- one-launch decode behind a norm: RMSNorm / LayerNorm formed inside the decode kernel (additive to ABI 14) -----------------------
+ * Up to 8 tokens a forward is ONE launch (csrc/decode1.hip: lqer_linear_forward's decode route, lqer_linear_forward_group).  These four
+ * entries take the RAW hidden state h [M, K] (fp16 or bf16, row stride ld_h elements) in place of x, with the norm weight w [K] (and,
+ * LayerNorm, the bias b [K]) of the same dtype and eps: the kernel forms x by the rules spelled above - "fused RMSNorm", "fused
+ * LayerNorm": every fp32 step rounded on its own, correctly rounded division and square root, the stated summation order, a k past K
+ * adds nothing and is zero - and quantizes it where the loaded x went.  Every workgroup computes the statistics of all M rows itself
+ * (no hand-off between workgroups); x has the bits lqer_quantize_act_xa_normed / _layernormed form for the same input, so an 8-token
+ * and a 9-token step agree on the norm, and y has the bits of the x entry handed that x.  Still one launch, capturable, bit-stable.
+ *   lqer_linear_forward_group_normed / _layernormed: lqer_linear_forward_group with (h, norm_weight[, norm_bias], eps) for x;
+ *   lqer_linear_decode_normed / _layernormed:        ONE Linear - operands as for lqer_linear_forward's decode route: a_t the plain
+ *       [padded rank][padded K] image of lqer_pack_lowrank with a_limbs = 1, workspace >= lqer_linear_sizes(desc, M).workspace - served
+ *       where lqer_decode_partials(desc, M) == 1.  (lqer_linear_forward_normed / _layernormed keep their two-launch route at every M.)
+ * LQER_E_INVALID: a null h / norm_weight (LayerNorm: norm_bias), eps < 0 or not finite, ld_h < K, and what the x entries call invalid.
+ * LQER_E_UNSUPPORTED, nothing launched, the reason in lqer_last_error(): fp32 tensors; M > 8; K % 16 != 0 or K > 8192; h, its row
+ * stride, norm_weight or norm_bias not 16-byte aligned; everything lqer_linear_forward_group / the decode route refuse (formats,
+ * limbs, ranks, "K too long for the LDS image": the image and 64 bytes of row statistics share the workgroup's LDS). */
+int lqer_linear_forward_group_normed(const lqer_group_member_t* members, int n_members, const void* h, const void* norm_weight, float eps,
+                                     int dtype, int64_t M, int64_t ld_h, const void* a_t_cat, int a_limbs, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int lqer_linear_forward_group_layernormed(const lqer_group_member_t* members, int n_members, const void* h, const void* norm_weight,
+                                          const void* norm_bias, float eps, int dtype, int64_t M, int64_t ld_h, const void* a_t_cat,
+                                          int a_limbs, void* workspace, size_t workspace_bytes, void* stream);
+int lqer_linear_decode_normed(const lqer_linear_desc_t* desc, const void* h, const void* norm_weight, float eps, int dtype, int64_t M,
+                              int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                              const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
+int lqer_linear_decode_layernormed(const lqer_linear_desc_t* desc, const void* h, const void* norm_weight, const void* norm_bias, float eps,
+                                   int dtype, int64_t M, int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t, int a_limbs,
+                                   int b_limbs, const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
 /* ---- weights of 5..8 bits (the reference's no-LQER baseline: W8A8 block_fp with one block per row and per token,
  * experiments/pipeline/sweep_baseline_no_lqer.sh:73-76, through LinearFlexible, quantized_layers/linear.py:50-64) ---------------
  * The packed image holds 4-bit codes, so a mantissa m of up to 8 bits (|m| <= 127) travels as three signed base-8 digits,

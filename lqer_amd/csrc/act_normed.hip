@@ -49,16 +49,6 @@ constexpr int MAX_K = 8192;  // two slabs per wave
 // one 256-B area of row partials per reduction: RMSNorm one, LayerNorm two
 __host__ inline size_t lds_bytes_n(int rp, int norm) { return lds_bytes(rp) + (size_t)(norm == NORM_LAYER ? 2 : 1) * WAVES * ROWS * sizeof(float); }
 
-// LayerNorm's elementwise rule: three fp32 roundings, then one to dt (contraction off: a multiply and the add behind it stay two operations)
-template <int DT>
-__device__ __forceinline__ float layer_norm_x(float h, float mean, float rstd, float w, float b) {
-#pragma clang fp contract(off)
-  const float d = h - mean;
-  const float t = d * rstd;
-  const float u = t * w;
-  return round_dt<DT>(u + b);
-}
-
 template <int DT, int RT, int NS, int NORM>
 __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h, const bf16_t* __restrict__ nw, float eps, int64_t M, int64_t ldh,
                                                      int64_t K, int64_t Kp, const bf16_t* __restrict__ a_frag, bf16_t* __restrict__ xq,
@@ -106,82 +96,16 @@ __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h
   };
   if constexpr (RT > 0) load_part(fa, wave, 0), load_part(fb, wave, 1);
 
-  float rs[ROWS], mn[LN ? ROWS : 1];  // rstd (and LN: the mean) of the 8 rows, wave-uniform
-  if constexpr (LN) {
-    // ---- pass 1 behind a LayerNorm: two row sums, each in the fixed order of the sum of squares below (lane, tree, LDS [wave][row] in an
-    // area of its own, one barrier, the eight partials in wave order).  term(acc, v, live, j) adds one element of row j to the lane's chain
-    auto row_sum = [&](float* area, auto term) {
-      float mine = 0.f;
-#pragma unroll
-      for (int j = 0; j < ROWS; ++j) {
-        float ss = 0.f;
-        if (m0 + j < M) {  // (wave-uniform)
-#pragma unroll
-          for (int si = 0; si < NS; ++si) {
-            const bool live = (int64_t)(wave + WAVES * si) * SLAB + 8 * lane < K;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              float a, b;
-              pair_to_f32<DT>(live ? rh[si][j][i] : 0u, a, b);
-              ss = term(term(ss, a, live, j), b, live, j);
-            }
-          }
-#pragma unroll
-          for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
-        }
-        mine = lane == j ? ss : mine;
-      }
-      if (lane < ROWS) area[wave * ROWS + lane] = mine;
-      __syncthreads();
-      float S = 0.f;
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) S += area[w * ROWS + (lane & 7)];
-      return S;  // lane l: row l & 7
-    };
-    const float mine_mean = row_sum(part, [](float acc, float v, bool, int) { return acc + v; }) / (float)K;
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) mn[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_mean), j));
-    // (a chunk past K holds h = 0, its d would be -mean: it adds nothing)
-    const float S2 = row_sum(part + WAVES * ROWS, [&](float acc, float v, bool live, int j) {
-      const float d = live ? v - mn[j] : 0.f;
-      return __builtin_fmaf(d, d, acc);
-    });
-    const float mine_rstd = 1.0f / sqrtf(S2 / (float)K + eps);
-#pragma unroll
-    for (int j = 0; j < ROWS; ++j) rs[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_rstd), j));
-  } else {
-    // ---- pass 1, the sums of squares: lane, wave, workgroup - each in one fixed order
-    float mine = 0.f;  // lane j: row j's sum over this wave's slabs
+  // ---- pass 1, the row statistics (act_rows.h row_stats: the sum of squares, or behind a LayerNorm the two row sums, in the one fixed
+  // order - lane, wave, workgroup); wave-uniform from here on
+  float rs[ROWS], mn[LN ? ROWS : 1];  // rstd (and LN: the mean) of the 8 rows
+  {
+    float mine_rstd, mine_mean;
+    row_stats<DT, NS, LN>(part, wave, lane, M - m0, K, eps, [&](int si, int j) { return rh[si][j]; }, mine_rstd, mine_mean);
 #pragma unroll
     for (int j = 0; j < ROWS; ++j) {
-      float ss = 0.f;
-      if (m0 + j < M) {  // (wave-uniform)
-#pragma unroll
-        for (int si = 0; si < NS; ++si) {
-          const int64_t k = (int64_t)(wave + WAVES * si) * SLAB + 8 * lane;
-          const bool live = k < K;  // (K % 8 == 0: a chunk is inside the tensor or outside it as a whole)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float a, b;
-            pair_to_f32<DT>(live ? rh[si][j][i] : 0u, a, b);
-            ss = __builtin_fmaf(a, a, ss);
-            ss = __builtin_fmaf(b, b, ss);
-          }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
-      }
-      mine = lane == j ? ss : mine;
-    }
-    if (lane < ROWS) part[wave * ROWS + lane] = mine;
-    __syncthreads();
-    {
-      float S = 0.f;
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) S += part[w * ROWS + (lane & 7)];
-      const float mine_rstd = 1.0f / sqrtf(S / (float)K + eps);
-#pragma unroll
-      for (int j = 0; j < ROWS; ++j) rs[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_rstd), j));
+      rs[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_rstd), j));
+      if constexpr (LN) mn[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_mean), j));
     }
   }
 
@@ -209,8 +133,8 @@ __global__ __launch_bounds__(512) void k_act_normed(const bf16_t* __restrict__ h
           v[2 * i] = live ? layer_norm_x<DT>(h0, mn[j], rs[j], w0, b0) : 0.f;
           v[2 * i + 1] = live ? layer_norm_x<DT>(h1, mn[j], rs[j], w1, b1) : 0.f;
         } else {
-          v[2 * i] = round_dt<DT>(w0 * round_dt<DT>(h0 * rs[j]));
-          v[2 * i + 1] = round_dt<DT>(w1 * round_dt<DT>(h1 * rs[j]));
+          v[2 * i] = rms_norm_x<DT>(h0, rs[j], w0);
+          v[2 * i + 1] = rms_norm_x<DT>(h1, rs[j], w1);
         }
       }
       quant_half_block<DT>(v, qx, w);

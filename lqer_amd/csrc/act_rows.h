@@ -4,6 +4,8 @@
 //   quant_half_block  the block-of-16 quantizer on the lane's 8 values (the block's other half sits in lane ^ 1) -> 4 words of bf16 image
 //   mult_part         HB MFMA steps of the wave's LDS slab against one fragment register set, one accumulator chain per rank tile
 //   tiles_sum_aout    the 8 waves' partial tiles summed in wave order, A_out_quantizer, the bf16 store of xaq
+// and the norms' own pieces, shared by act_normed.hip and the NORM instantiations of decode1.hip (whose workgroup is 8 waves over <= 8 rows too):
+//   rms_norm_x, layer_norm_x   the elementwise rules;  row_sum, row_stats   a row's sums in the one fixed order, rstd and mean
 #pragma once
 #include "common.h"
 
@@ -23,6 +25,83 @@ template <int DT>
 __device__ __forceinline__ float round_dt(float v) {
   if constexpr (DT == LQER_F16) return (float)(_Float16)v;  // v_cvt_f16_f32 + back: round to nearest even, subnormals kept
   else return __uint_as_float((uint32_t)f32_to_bf16_rne(v) << 16);
+}
+
+// ---- the norms in front of the quantizer (act_normed.hip; the NORM instantiations of decode1.hip): the rules of include/lqer_hip.h,
+// "fused RMSNorm" and "fused LayerNorm", each written once
+// RMSNorm's elementwise rule: HF LlamaRMSNorm's two roundings in dt (the product of two dt values is exact in fp32)
+template <int DT>
+__device__ __forceinline__ float rms_norm_x(float h, float rstd, float w) {
+  return round_dt<DT>(w * round_dt<DT>(h * rstd));
+}
+// LayerNorm's elementwise rule: three fp32 roundings, then one to dt (contraction off: a multiply and the add behind it stay two operations)
+template <int DT>
+__device__ __forceinline__ float layer_norm_x(float h, float mean, float rstd, float w, float b) {
+#pragma clang fp contract(off)
+  const float d = h - mean;
+  const float t = d * rstd;
+  const float u = t * w;
+  return round_dt<DT>(u + b);
+}
+
+// One sum over each of the workgroup's `rows` (<= 8) token rows, in THE order of the header: a lane's chain over its 8 consecutive elements
+// in ascending k, slab after slab (512-k slab s belongs to wave s % 8: wave w holds slabs w + 8 si, si < NS); an xor tree over lane
+// distances 32..1; lane j writes row j's wave sum to LDS area [WAVES][ROWS]; ONE workgroup barrier; the eight wave sums in wave order.
+// chunk(si, j): the lane's 16 bytes (8 elements at k = (wave + 8 si) * 512 + 8 lane) of row j, anything where that k is not below K (it is
+// masked to zero here); term(acc, v, live, j): the chain's step for element v of row j.  Returns, in lane l, the sum of row l & 7: one
+// order whatever M and the grid are, no atomics.  Called by all 512 threads.
+template <int DT, int NS, class Chunk, class Term>
+__device__ __forceinline__ float row_sum(float* area, int wave, int lane, int64_t rows, int64_t K, Chunk chunk, Term term) {
+  float mine = 0.f;
+#pragma unroll
+  for (int j = 0; j < ROWS; ++j) {
+    float ss = 0.f;
+    if (j < rows) {  // (wave-uniform)
+#pragma unroll
+      for (int si = 0; si < NS; ++si) {
+        const bool live = (int64_t)(wave + WAVES * si) * SLAB + 8 * lane < K;  // (K % 8 == 0: a chunk is inside the tensor or outside it as a whole)
+        const u32x4 c = chunk(si, j);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float a, b;
+          pair_to_f32<DT>(live ? c[i] : 0u, a, b);
+          ss = term(term(ss, a, live, j), b, live, j);
+        }
+      }
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d, 64);
+    }
+    mine = lane == j ? ss : mine;
+  }
+  if (lane < ROWS) area[wave * ROWS + lane] = mine;
+  __syncthreads();
+  float S = 0.f;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) S += area[w * ROWS + (lane & 7)];
+  return S;  // lane l: row l & 7
+}
+
+// The statistics of the rows: rstd (and LN: the mean) of row l & 7 in lane l.  RMSNorm: one row sum (the squares); LayerNorm: two, the
+// centred squares behind the mean - each through a 256-B area of its own (part: [LN ? 2 : 1][WAVES][ROWS]; the second sum's partials may
+// be written while a slow wave still reads the first's).  A chunk past K holds h = 0, its d would be -mean: it adds nothing to S2.
+template <int DT, int NS, bool LN, class Chunk>
+__device__ __forceinline__ void row_stats(float* part, int wave, int lane, int64_t rows, int64_t K, float eps, Chunk chunk, float& rstd,
+                                          float& mean) {
+  if constexpr (LN) {
+    mean = row_sum<DT, NS>(part, wave, lane, rows, K, chunk, [](float acc, float v, bool, int) { return acc + v; }) / (float)K;
+    float mn[ROWS];
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j) mn[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mean), j));
+    const float S2 = row_sum<DT, NS>(part + WAVES * ROWS, wave, lane, rows, K, chunk, [&](float acc, float v, bool live, int j) {
+      const float d = live ? v - mn[j] : 0.f;
+      return __builtin_fmaf(d, d, acc);
+    });
+    rstd = 1.0f / sqrtf(S2 / (float)K + eps);
+  } else {
+    const float S = row_sum<DT, NS>(part, wave, lane, rows, K, chunk, [](float acc, float v, bool, int) { return __builtin_fmaf(v, v, acc); });
+    mean = 0.f;
+    rstd = 1.0f / sqrtf(S / (float)K + eps);
+  }
 }
 
 // the lane's 8 values of a block of 16 (dt values: an fp16 one cannot be a non-zero |v| <= 1e-8) -> w, which arrives zeroed

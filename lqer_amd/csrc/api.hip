@@ -879,12 +879,12 @@ static bool decode1_takes(const lqer_linear_desc_t* d, int64_t M, int dtype, con
 // ... and its launch for the Linears `mem`, which are handed the same tokens: `shared` = the arguments of (d, M) that do not depend on
 // the Linear (gemm_shape_args), A_out and the B_out form are d's
 static int decode1_call(const GemmArgs& shared, const lqer_linear_desc_t* d, int dtype, const void* x, int64_t ldx, const void* a_t,
-                        const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, void* stream) {
+                        const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, void* stream, const DecodeNorm* nz = nullptr) {
   GemmArgs g = shared;
   g.aout = make_qp(d->a_out_fmt);
   const int bout = d->b_out_fmt.kind == LQER_Q_PASSTHROUGH ? 0 : 1;  // (decode_partials_ok: pass-through or blocks of 16)
   return decode1_dispatch(g, dtype, x, ldx, d->in_features, make_qp(d->x_fmt), (const bf16_t*)a_t, bout, mem, nmem, scratch, scratch_bytes,
-                          (hipStream_t)stream);
+                          (hipStream_t)stream, nz);
 }
 
 // what lqer_linear_forward / lqer_linear_forward_narrow are handed besides the descriptor and the weight image
@@ -1232,9 +1232,47 @@ size_t lqer_group_workspace_bytes(int64_t K, int64_t rank_padded_sum) {
   return (K > 0 && rank_padded_sum > 0) ? (decode1_scratch_bytes(lqer_padded_k(K), (int)rank_padded_sum) + 255) / 256 * 256 : 0;
 }
 
+// ---- the decode step behind a norm (include/lqer_hip.h "one-launch decode behind a norm"): the norm's own operands, checked once for
+// the group entries and the single-Linear entries.  What the kernel's route refuses besides, the callers' own checks say.
+static int decode_norm_check(const char* who, const DecodeNorm& nz, const void* h, int dtype, int64_t M, int64_t ld_h, int64_t K) {
+  if (!h || !nz.nw) return fail(LQER_E_INVALID, "%s: null %s", who, h ? "norm weight" : "hidden state");
+  if (nz.norm == NORM_LAYER && !nz.nb) return fail(LQER_E_INVALID, "%s: null norm bias", who);
+  if (!(nz.eps >= 0.0f) || !std::isfinite(nz.eps)) return fail(LQER_E_INVALID, "%s: eps %g must be finite and >= 0", who, (double)nz.eps);
+  if (ld_h < K) return fail(LQER_E_INVALID, "%s: row stride %lld of h < in_features %lld", who, (long long)ld_h, (long long)K);
+  if (dtype == LQER_F32) return fail(LQER_E_UNSUPPORTED, "%s: fp32 h (the roundings of x are those of a 16-bit eager model: fp16 or bf16)", who);
+  if (dtype != LQER_F16 && dtype != LQER_BF16) return fail(LQER_E_INVALID, "%s: unknown dtype %d", who, dtype);
+  if (M > d1::MAXM) return fail(LQER_E_UNSUPPORTED, "%s: M = %lld: the one-launch decode kernel takes up to %d tokens", who, (long long)M, d1::MAXM);
+  if (K % 16 != 0 || K > 8192)
+    return fail(LQER_E_UNSUPPORTED, "%s: in_features %lld must be a multiple of 16 and at most 8192 (a wave sums at most two 512-k slabs)", who, (long long)K);
+  if (((uintptr_t)h & 15) || (ld_h * 2) % 16 || ((uintptr_t)nz.nw & 15) || (nz.norm == NORM_LAYER && ((uintptr_t)nz.nb & 15)))
+    return fail(LQER_E_UNSUPPORTED, "%s: h, its row stride, the norm weight and the norm bias must be 16-byte aligned", who);
+  return LQER_OK;
+}
+
+// lqer_linear_forward_group, and (nz: x is the raw hidden state h) lqer_linear_forward_group_normed / _layernormed
+static int forward_group_impl(const char* who, const lqer_group_member_t* members, int n_members, const void* x, int dtype, int64_t M, int64_t ldx,
+                              const void* a_t_cat, int a_limbs, void* workspace, size_t workspace_bytes, void* stream, const DecodeNorm* nz);
+
 int lqer_linear_forward_group(const lqer_group_member_t* members, int n_members, const void* x, int dtype, int64_t M, int64_t ldx,
                               const void* a_t_cat, int a_limbs, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!members || n_members < 1 || !x || !a_t_cat || !workspace || M < 0) return fail(LQER_E_INVALID, "linear_forward_group: bad argument");
+  return forward_group_impl("linear_forward_group", members, n_members, x, dtype, M, ldx, a_t_cat, a_limbs, workspace, workspace_bytes, stream, nullptr);
+}
+int lqer_linear_forward_group_normed(const lqer_group_member_t* members, int n_members, const void* h, const void* nw, float eps, int dtype, int64_t M,
+                                     int64_t ld_h, const void* a_t_cat, int a_limbs, void* workspace, size_t workspace_bytes, void* stream) {
+  const DecodeNorm nz{NORM_RMS, nw, nullptr, eps};
+  return forward_group_impl("linear_forward_group_normed", members, n_members, h, dtype, M, ld_h, a_t_cat, a_limbs, workspace, workspace_bytes, stream, &nz);
+}
+int lqer_linear_forward_group_layernormed(const lqer_group_member_t* members, int n_members, const void* h, const void* nw, const void* nb, float eps,
+                                          int dtype, int64_t M, int64_t ld_h, const void* a_t_cat, int a_limbs, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  const DecodeNorm nz{NORM_LAYER, nw, nb, eps};
+  return forward_group_impl("linear_forward_group_layernormed", members, n_members, h, dtype, M, ld_h, a_t_cat, a_limbs, workspace, workspace_bytes, stream,
+                            &nz);
+}
+
+static int forward_group_impl(const char* who, const lqer_group_member_t* members, int n_members, const void* x, int dtype, int64_t M, int64_t ldx,
+                              const void* a_t_cat, int a_limbs, void* workspace, size_t workspace_bytes, void* stream, const DecodeNorm* nz) {
+  if (!members || n_members < 1 || !x || !a_t_cat || !workspace || M < 0) return fail(LQER_E_INVALID, "%s: bad argument", who);
   if (M == 0) return LQER_OK;
   const lqer_linear_desc_t* d0 = members[0].desc;
   auto same = [](const lqer_qfmt_t& a, const lqer_qfmt_t& b) {
@@ -1249,11 +1287,15 @@ int lqer_linear_forward_group(const lqer_group_member_t* members, int n_members,
   for (int i = 0; i < n_members && i < d1::MAXMEM; ++i) {
     const lqer_linear_desc_t* d = members[i].desc;
     if (!d || d->in_features <= 0 || d->out_features <= 0 || d->rank < 0)
-      return fail(LQER_E_INVALID, "linear_forward_group: member %d: bad descriptor", i);
+      return fail(LQER_E_INVALID, "%s: member %d: bad descriptor", who, i);
     if (!fmt_ok(&d->w_fmt, ROLE_W_GROUP) || !fmt_ok(&d->x_fmt, ROLE_X) || !fmt_ok(&d->a_out_fmt, ROLE_A_OUT) ||
         !fmt_ok(&d->b_out_fmt, ROLE_B_OUT))
       return LQER_E_UNSUPPORTED;
-    if (d->has_bias && !members[i].bias_q) return fail(LQER_E_INVALID, "linear_forward_group: member %d: has_bias = 1 but bias_q == NULL", i);
+    if (d->has_bias && !members[i].bias_q) return fail(LQER_E_INVALID, "%s: member %d: has_bias = 1 but bias_q == NULL", who, i);
+  }
+  if (nz) {
+    const int rc = decode_norm_check(who, *nz, x, dtype, M, ldx, d0->in_features);
+    if (rc) return rc;
   }
   for (int i = 0; ok && i < n_members; ++i) {
     const lqer_group_member_t& m = members[i];
@@ -1266,17 +1308,57 @@ int lqer_linear_forward_group(const lqer_group_member_t* members, int n_members,
     rp_all += mem[i].rp;
   }
   if (!ok || rp_all > d1::MAX_RP_ALL)
-    return fail(LQER_E_UNSUPPORTED, "linear_forward_group: outside the one-launch decode route (2..4 members with equal K and x / A_out / B_out formats, "
-                "lqer_decode_partials, M <= 8, one limb of A, aligned x): run the members one by one");
+    return fail(LQER_E_UNSUPPORTED, "%s: outside the one-launch decode route (2..4 members with equal K and x / A_out / B_out formats, "
+                "lqer_decode_partials, M <= 8, one limb of A, aligned x): run the members one by one", who);
   if (workspace_bytes < lqer_group_workspace_bytes(d0->in_features, rp_all))
-    return fail(LQER_E_WORKSPACE, "linear_forward_group: workspace %zu B < %zu B", workspace_bytes, lqer_group_workspace_bytes(d0->in_features, rp_all));
+    return fail(LQER_E_WORKSPACE, "%s: workspace %zu B < %zu B", who, workspace_bytes, lqer_group_workspace_bytes(d0->in_features, rp_all));
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   int rc = gemm_shape_args(d0, M, dtype, g);  // the shared part: M, Kp, formats
   if (rc) return rc;
-  rc = decode1_call(g, d0, dtype, x, ldx, a_t_cat, mem, n_members, workspace, workspace_bytes, stream);
-  if (rc == LQER_E_UNSUPPORTED) set_error("linear_forward_group: shape outside the one-launch decode kernel (K too long for its LDS image)");
+  rc = decode1_call(g, d0, dtype, x, ldx, a_t_cat, mem, n_members, workspace, workspace_bytes, stream, nz);
+  if (rc == LQER_E_UNSUPPORTED) set_error("%s: outside the one-launch decode kernel: %s", who, decode1_last_refusal());
   return rc;
+}
+
+// One Linear on norm(h) in ONE launch: lqer_linear_forward's decode route with the norm formed inside the kernel
+static int linear_decode_normed_impl(const char* who, const DecodeNorm& nz, const lqer_linear_desc_t* d, const void* h, int dtype, int64_t M, int64_t ld_h,
+                                     const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y,
+                                     int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!d || M < 0) return fail(LQER_E_INVALID, "%s: %s", who, d ? "negative token count" : "null descriptor");
+  int rc = decode_norm_check(who, nz, h, dtype, M, ld_h, d->in_features);
+  if (rc) return rc;
+  if (!w_packed || !a_t || !b_t || !y || ldy < d->out_features || (d->has_bias && !bias_q))
+    return fail(LQER_E_INVALID, "%s: null weight image, A^T / B^T image, bias or y, or ldy %lld < out_features %d", who, (long long)ldy, d->out_features);
+  lqer_linear_sizes_t sz;
+  Carving cv;  // (lqer_linear_forward's own)
+  if ((rc = linear_sizes_carved(d, M, &sz, &cv)) != 0) return rc;
+  if (workspace_bytes < cv.total || (!workspace && cv.total))
+    return fail(LQER_E_WORKSPACE, "%s: workspace %zu B < %zu B needed for M=%lld", who, workspace_bytes, cv.total, (long long)M);
+  if (M == 0) return LQER_OK;
+  if (!decode1_takes(d, M, dtype, h, ld_h, a_limbs, b_limbs))
+    return fail(LQER_E_UNSUPPORTED, "%s: outside the one-launch decode route (lqer_decode_partials(desc, M) == 1, the plain A^T image with a_limbs = 1, "
+                "1..3 limbs of B): compute the norm and call lqer_linear_forward", who);
+  const Planned pl = plan_for(d, M, dtype, b_limbs);
+  if (pl.rc) return fail(pl.rc, "%s", pl.p.msg);
+  const DecodeMember one = member_of(d, w_packed, b_t, b_limbs, bias_q, y, ldy);
+  rc = decode1_call(pl.g, d, dtype, h, ld_h, a_t, &one, 1, (unsigned char*)workspace + cv.scratch, cv.side_bytes, stream, &nz);
+  if (rc == LQER_E_UNSUPPORTED) set_error("%s: outside the one-launch decode kernel: %s", who, decode1_last_refusal());
+  return rc;
+}
+
+int lqer_linear_decode_normed(const lqer_linear_desc_t* d, const void* h, const void* nw, float eps, int dtype, int64_t M, int64_t ld_h,
+                              const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q, void* y,
+                              int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  return linear_decode_normed_impl("linear_decode_normed", DecodeNorm{NORM_RMS, nw, nullptr, eps}, d, h, dtype, M, ld_h, w_packed, a_t, b_t, a_limbs,
+                                   b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream);
+}
+
+int lqer_linear_decode_layernormed(const lqer_linear_desc_t* d, const void* h, const void* nw, const void* nb, float eps, int dtype, int64_t M,
+                                   int64_t ld_h, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                                   const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  return linear_decode_normed_impl("linear_decode_layernormed", DecodeNorm{NORM_LAYER, nw, nb, eps}, d, h, dtype, M, ld_h, w_packed, a_t, b_t, a_limbs,
+                                   b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream);
 }
 
 int lqer_desc_limbs(const lqer_linear_desc_t* d, int* act, int* xa) {

@@ -917,9 +917,15 @@ struct DecodeMember {  // one Linear of a one-launch decode forward (a group sha
   int64_t ldy;
   int N, Np, rp, b_limbs;
 };
+const char* decode1_last_refusal();  // why decode1_dispatch last answered LQER_E_UNSUPPORTED on this thread
+struct DecodeNorm {  // the norm the kernel forms itself from the raw hidden state (handed in x's place): NORM_RMS (nb unused) or NORM_LAYER
+  int norm;
+  const void *nw, *nb;
+  float eps;
+};
 // (g.w_narrow != 0: a single Linear whose wp is the compact image - groups read standard images only)
 int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, const QP& qx, const bf16_t* a_t, int bout,
-                     const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st);
+                     const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st, const DecodeNorm* nz = nullptr);
 
 // pack.hip: standard image <-> compact image of a 2- / 3-bit block_fp weight (w_narrow.h), over the whole padded image; E = exponent
 // bytes per row of a compact panel.  The host twins run the same per-row functions in plain loops (no HIP call); narrow_host returns

@@ -17,7 +17,8 @@ import torch
 
 
 class GraphedCallable:
-    def __init__(self, fn, *static_inputs: torch.Tensor, warmup: int = 2):
+    def __init__(self, fn, *static_inputs: torch.Tensor, warmup: int = 2, keep_graph: bool = False):
+        """keep_graph: keep the captured hipGraph beside its executable, so that kernel_nodes() can walk it."""
         self.fn = fn
         self.static_inputs = static_inputs
         dev = static_inputs[0].device if static_inputs else torch.device("cuda", torch.cuda.current_device())
@@ -28,9 +29,27 @@ class GraphedCallable:
                 for _ in range(max(warmup, 1)):
                     fn(*static_inputs)
             torch.cuda.current_stream().wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
+            self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.static_output = fn(*static_inputs)
+
+    def kernel_nodes(self) -> int:
+        """How many kernel nodes the captured graph holds (hipGraphGetNodes / hipGraphNodeGetType; needs keep_graph=True)."""
+        import ctypes as C
+
+        hip = C.CDLL("libamdhip64.so")
+        graph, n, kind = C.c_void_p(self.graph.raw_cuda_graph()), C.c_size_t(0), C.c_int(-1)
+        if hip.hipGraphGetNodes(graph, None, C.byref(n)):
+            raise RuntimeError("hipGraphGetNodes failed")
+        nodes = (C.c_void_p * n.value)()
+        if n.value and hip.hipGraphGetNodes(graph, nodes, C.byref(n)):
+            raise RuntimeError("hipGraphGetNodes failed")
+        count = 0
+        for node in nodes:
+            if hip.hipGraphNodeGetType(C.c_void_p(node), C.byref(kind)):
+                raise RuntimeError("hipGraphNodeGetType failed")
+            count += kind.value == 0  # hipGraphNodeTypeKernel
+        return count
 
     def copy_inputs(self, *new_inputs: torch.Tensor) -> None:
         if len(new_inputs) != len(self.static_inputs):

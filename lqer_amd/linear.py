@@ -76,7 +76,8 @@ class _LinearBase(nn.Linear):
                                    # parameters (`with torch.no_grad(): mod.weight.copy_(W2)`) is seen by the next forward
         self._group = None         # SharedActivation of Linears fed by the same tensor (models.quantize_model)
         self._armed = None         # _arm(h, ...): a fused LayerNorm's raw hidden state for the next forward (arm_layer_normed)
-        self.layer_normed_rounds = 0  # forwards that ran lqer_linear_forward_layernormed
+        self.layer_normed_rounds = 0  # forwards that ran lqer_linear_forward_layernormed / lqer_linear_decode_layernormed
+        self.decode_normed_rounds = 0  # forwards that ran lqer_linear_decode_normed
         self._fw_cache = {}        # token count -> (descriptor, workspace bytes)
         self._x_f16 = False        # pass-through fp16 activations on the fp16 MFMA route (decided when the images are built)
         self.a16_native = True     # False: keep pass-through fp16 activations on the bf16-limb route
@@ -724,6 +725,8 @@ class _LinearBase(nn.Linear):
         the norm formed inside the activation-side kernel (csrc/act_normed.hip through lqer_linear_forward_normed: two launches, x never
         written) where that kernel applies: fp16 / bf16 tensors from normed_min_m tokens on, in_features % 16 == 0 and <= 8192, block-16
         MXINT x_quantizer, an A of one bf16 limb with padded rank 16 / 32 / 48 / 64 / 96 / 128 (or no A), the standard weight image.
+        Up to 8 tokens, where decode_normed is set (the default) and the one-launch decode route serves the call, the whole forward is ONE
+        launch that forms the norm itself (csrc/decode1_kernel.h through lqer_linear_decode_normed).
         Elsewhere the norm is computed with torch and handed to forward().  Against that route the result differs by 1 / sqrt against
         torch's rsqrt (the last bit of some x) and the side product's fp32 summation order."""
         if h.shape[-1] != self.in_features or norm_weight.shape != (self.in_features,):
@@ -757,6 +760,10 @@ class _LinearBase(nn.Linear):
         K, N = self.in_features, self.out_features
         M = h.numel() // K
         fx, fa = self._fmt["x"], self._fmt.get("A_out")
+        if 0 < M <= 8 and (self.decode_normed if nb is None else self.decode_layer_normed):
+            y = self._forward_decode_normed(h, nw, eps, nb)  # ONE launch; refused or switched off: the thresholds below, as before
+            if y is not None:
+                return y
         if (M < (self.normed_min_m if nb is None else self.layer_normed_min_m) or K % 16 or K > 8192 or self._weight_image == "narrow" or ops.w_limbs(self._fmt["w"]) != 1 or self._x_i8
                 or fx.kind != _lib.Q_MXINT or fx.block != 16 or fx.width > 9):
             return None
@@ -798,6 +805,60 @@ class _LinearBase(nn.Linear):
             self.layer_normed_rounds += 1
         return y.reshape(*h.shape[:-1], N)
 
+    # -- the decode step behind a norm (M <= 8) ---------------------------------------------------
+    # Does a lone Linear's forward_normed / forward_layer_normed take the one-launch entry (lqer_linear_decode_normed / _layernormed:
+    # csrc/decode1.hip forms the norm itself) by default?  Set from tools/rmsnorm_bench.py --decode (profiles/rmsnorm_decode.json,
+    # profiles/layernorm_decode.json; DESIGN.md "One-launch decode behind a norm") by the standing rule: off where the fused leg's
+    # fastest round lies above the torch leg's median at a measured size.  Off: exactly the route of before (torch's norm, forward()).
+    # RMSNorm (a lone q_proj, 4096 -> 4096): 0.26x / 0.27x / 0.33x the time of the HF norm's eight launches + forward at M = 1 / 4 / 8: on.
+    # LayerNorm (OPT-6.7B's fc1): 0.94x at M = 1, 1.07x at M = 4 with the fused leg's fastest round above F.layer_norm + forward's median
+    # (26.2 us against 24.6: the norm inside the kernel costs more than the one torch launch it saves), M = 8 outside the one-launch route: off.
+    decode_normed = True
+    decode_layer_normed = False
+
+    def _forward_decode_normed(self, h: torch.Tensor, nw: torch.Tensor, eps: float, nb: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """Up to 8 tokens: this Linear on norm(h) in ONE launch, or None where the entry does not serve the call (nothing launched)."""
+        p = self._packed
+        K, N = self.in_features, self.out_features
+        M = h.numel() // K
+        if (self.rank <= 0 or K % 16 or K > 8192 or self._weight_image == "narrow" or self._x_i8 or self._x_f16 or int(p.get("a_limbs", 0)) != 1
+                or p.get("b_t") is None):
+            return None
+        h2 = h.reshape(-1, K)
+        if h2.stride(-1) != 1 or h2.data_ptr() % 16 or (M > 1 and (h2.stride(0) < K or h2.stride(0) % 8)):
+            h2 = h2.contiguous()
+        nw, nb = (None if t is None else t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone() for t in (nw, nb))
+        key = ("decode_normed", M, h.dtype, self.tuning)
+        ent = self._fw_cache.get(key)
+        if ent is None:
+            desc = self._desc(plain=True)  # (decode sizes never take the int8 tile kernel)
+            if len(self._fw_cache) > 64:
+                self._fw_cache = {}
+            served = _lib.lib().lqer_decode_partials(C.byref(desc), M) == 1
+            ent = self._fw_cache[key] = (desc, ops.linear_sizes(desc, M).workspace, ops.dtype_code(h2), served,
+                                         (p["w"].data_ptr(), p["a_t"].data_ptr(), p["b_t"].data_ptr(), 1, p.get("b_limbs", 0), ops._ptr(p.get("bias"))))
+        desc, ws_bytes, dt, served, consts = ent
+        if not served:
+            return None
+        y = torch.empty(M, N, dtype=h.dtype, device=h.device)
+        st = ops._stream(h.device)
+        ws = ops.workspace_on(h.device, st, ws_bytes)
+        tail = (eps, dt, M, h2.stride(0) if M > 1 else K, *consts, y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        if nb is None:
+            rc = _lib.lib().lqer_linear_decode_normed(C.byref(desc), h2.data_ptr(), nw.data_ptr(), *tail)
+        else:
+            rc = _lib.lib().lqer_linear_decode_layernormed(C.byref(desc), h2.data_ptr(), nw.data_ptr(), nb.data_ptr(), *tail)
+        if rc == -2:  # LQER_E_UNSUPPORTED (nothing was launched)
+            self._fw_cache[key] = (desc, ws_bytes, dt, False, consts)
+            return None
+        if rc:
+            check(rc, "lqer_linear_decode_normed" if nb is None else "lqer_linear_decode_layernormed")
+        if nb is None:
+            self.decode_normed_rounds += 1
+        else:
+            self.layer_normed_rounds += 1
+        return y.reshape(*h.shape[:-1], N)
+
     # -- fused LayerNorm ----------------------------------------------------------------------
     # Token count from which forward_layer_normed (and so a lone Linear armed by a fused LayerNorm: OPT's fc1 under
     # models.quantize_model(fuse_layernorm=True)) takes the fused entry.  tools/rmsnorm_bench.py --norm layer at OPT-6.7B's fc1
@@ -809,6 +870,8 @@ class _LinearBase(nn.Linear):
         """This Linear on x = LayerNorm(h) = ((h - mean) * rstd) * weight + bias (nn.LayerNorm's biased variance, one rounding to h's
         dtype) with the norm formed inside the activation-side kernel (csrc/act_normed.hip through lqer_linear_forward_layernormed: two
         launches, x never written) where that kernel applies - the conditions of forward_normed, from layer_normed_min_m tokens on.
+        Up to 8 tokens, where decode_layer_normed is set (by default it is not) and the one-launch decode route serves the call: ONE launch
+        that forms the norm itself (lqer_linear_decode_layernormed).
         Elsewhere torch.nn.functional.layer_norm and forward().  Against that route some x differ by one step of the dtype (the
         kernel's fp32 rule is include/lqer_hip.h's; torch's own kernel sums in another order)."""
         K = self.in_features
@@ -952,18 +1015,28 @@ class SharedActivation:
     # torch leg's median at 512 and at 8192 - no measured size from which it is no slower at every larger one, so by default a group
     # never takes the entry (set a token count to switch it on)
     layer_normed_min_m = float("inf")
+    # Up to 8 tokens: does a round armed by a fused RMSNorm / LayerNorm take the one-launch entry (lqer_linear_forward_group_normed /
+    # _layernormed) by default?  Measured and set as _LinearBase.decode_normed; off: exactly the route of before.  Llama-7B q/k/v: 0.42x /
+    # 0.43x / 0.46x at M = 1 / 4 / 8, gate/up: 0.37x / 0.39x (M = 8 is outside the one-launch route on both legs); OPT-6.7B q/k/v behind
+    # its LayerNorm: 0.94x / 0.94x / 0.94x, the fused leg's fastest round below the torch leg's median at every size: both on.
+    decode_normed = True
+    decode_layer_normed = True
 
     def normed_serves(self, h: torch.Tensor, layer_norm: bool = False) -> bool:
         """Will a round of this group on h run the fused-norm kernel (lqer_quantize_act_xa_normed; layer_norm: ..._layernormed)?  Asked by
         the norm in front of the group BEFORE it decides to hand the raw hidden state on: everything the kernel or this route refuses is
-        answered here."""
+        answered here.  Up to 8 tokens the answer is for the group's one-launch decode round with the norm formed inside it
+        (lqer_linear_forward_group_normed / _layernormed), where decode_normed / decode_layer_normed is set (both are by default)."""
         m0 = self.members[0]
         K = m0.in_features
         M = h.numel() // K if K else 0
-        if layer_norm and M < self.layer_normed_min_m:
+        decode = 0 < M <= 8  # the one-launch decode round forms the norm itself (csrc/decode1.hip)
+        if decode and not (self.decode_layer_normed if layer_norm else self.decode_normed):
+            return False
+        if layer_norm and M < self.layer_normed_min_m and not decode:
             return False
         if (not self.enabled or not h.is_cuda or h.dtype not in (torch.float16, torch.bfloat16) or h.shape[-1] != K or K % 16 or K > 8192
-                or M <= 8 or (M < m0.normed_min_m and not layer_norm) or not h.is_contiguous() or h.data_ptr() % 16
+                or M < 1 or (not decode and (M <= 8 or (M < m0.normed_min_m and not layer_norm))) or not h.is_contiguous() or h.data_ptr() % 16
                 or any(m._packed_only or not m.is_ptq or m.weight.device != h.device for m in self.members)):
             return False
         fx, fa = m0._fmt["x"], m0._fmt["A_out"]
@@ -977,7 +1050,8 @@ class SharedActivation:
                 m._pack()
         if self._cat is None:
             self._pack_cat(h.device)
-        return "a_t_b16" in self._cat
+        # (a decode round the C ABI refuses is served by forward_member, which needs the image the large-M kernel reads)
+        return "a_t_b16" in self._cat and (not decode or self._decode_plan(M, ops.dtype_code(h), h.device) is not None)
 
     def arm_normed(self, h: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> None:
         """The next round on this very tensor, unmodified, starts from RMSNorm(h) formed inside the group's quantizer launch."""
@@ -1006,6 +1080,41 @@ class SharedActivation:
             self._dx, self._dys = None, None  # every member served: do not pin the tensors until the next round
         return y
 
+    def _decode_plan(self, M: int, dtc: int, dev):
+        """The member table of the one-launch decode round for (M, dtype), built once; None where the group does not take that route."""
+        plan = self._dplans.get((M, dtc), False)
+        if plan is not False:
+            return plan
+        L = _lib.lib()
+        K = self.members[0].in_features
+        # (a packed checkpoint carries no dense A to concatenate; lqer_group_member_t holds standard images only)
+        if any(m._packed_only or m._weight_image == "narrow" for m in self.members):
+            self._dplans[(M, dtc)] = None
+            return None
+        for m in self.members:
+            if m._packed is None or m.w_is_quantized is False:
+                m._pack()
+        if self._cat is None:
+            self._pack_cat(dev)
+        n = len(self.members)
+        descs = [m._desc(plain=True) for m in self.members]  # (decode sizes never take the int8 tile kernel)
+        tab = (_lib.GroupMember * n)()
+        for i, (m, d) in enumerate(zip(self.members, descs)):
+            pk = m._packed
+            tab[i].desc, tab[i].w_packed, tab[i].b_t = C.pointer(d), pk["w"].data_ptr(), pk["b_t"].data_ptr()
+            tab[i].b_limbs, tab[i].bias_q, tab[i].ldy = pk["b_limbs"], ops._ptr(pk.get("bias")), m.out_features
+        ok = (2 <= n <= 4 and self._cat["a_limbs"] == 1 and all(L.lqer_decode_partials(C.byref(d), M) == 1 for d in descs)
+              and not any(m._x_f16 for m in self.members) and self._cat["rp_total"] <= 128)
+        if not ok:
+            self._dplans[(M, dtc)] = None
+            return None
+        if len(self._dplans) > 64:
+            self._dplans = {}
+        plan = self._dplans[(M, dtc)] = {
+            "tab": tab, "descs": descs, "n": n, "Ns": [m.out_features for m in self.members],
+            "ws": L.lqer_group_workspace_bytes(K, self._cat["rp_total"]), "a_t": self._cat["a_t"].data_ptr()}
+        return plan
+
     def decode_member(self, mod, x, x2):
         """Up to 8 tokens: every member's forward in ONE launch (lqer_linear_forward_group: the producers multiply x with the
         concatenated A, each member's weight-streaming workgroups read their rank columns - per member the bits of its own
@@ -1026,38 +1135,14 @@ class SharedActivation:
                 if not m.is_ptq:
                     return None
                 m._written_in_place()
-        plan = self._dplans.get((M, dtc), False)
-        if plan is None:
-            return None
         L = _lib.lib()
         dev = x2.device
-        if plan is False:
-            # (a packed checkpoint carries no dense A to concatenate; lqer_group_member_t holds standard images only)
-            if any(m._packed_only or m._weight_image == "narrow" for m in self.members):
-                self._dplans[(M, dtc)] = None
-                return None
-            for m in self.members:
-                if m._packed is None or m.w_is_quantized is False:
-                    m._pack()
-            if self._cat is None:
-                self._pack_cat(dev)
-            n = len(self.members)
-            descs = [m._desc(plain=True) for m in self.members]  # (decode sizes never take the int8 tile kernel)
-            tab = (_lib.GroupMember * n)()
-            for i, (m, d) in enumerate(zip(self.members, descs)):
-                pk = m._packed
-                tab[i].desc, tab[i].w_packed, tab[i].b_t = C.pointer(d), pk["w"].data_ptr(), pk["b_t"].data_ptr()
-                tab[i].b_limbs, tab[i].bias_q, tab[i].ldy = pk["b_limbs"], ops._ptr(pk.get("bias")), m.out_features
-            ok = (2 <= n <= 4 and self._cat["a_limbs"] == 1 and all(L.lqer_decode_partials(C.byref(d), M) == 1 for d in descs)
-                  and not any(m._x_f16 for m in self.members) and self._cat["rp_total"] <= 128)
-            if not ok:
-                self._dplans[(M, dtc)] = None
-                return None
-            if len(self._dplans) > 64:
-                self._dplans = {}
-            plan = self._dplans[(M, dtc)] = {
-                "tab": tab, "descs": descs, "n": n, "Ns": [m.out_features for m in self.members],
-                "ws": L.lqer_group_workspace_bytes(K, self._cat["rp_total"]), "a_t": self._cat["a_t"].data_ptr()}
+        plan = self._decode_plan(M, dtc, dev)
+        if plan is None:
+            return None
+        armed = _armed_for(self._armed, x)  # a fused norm handed the group its RAW hidden state: the kernel forms norm(x) itself
+        if armed is not None and not (self.decode_normed if armed[4] is None else self.decode_layer_normed):
+            return None  # (forward_member serves the armed round)
         if x2.stride(0) < K or (x2.data_ptr() & 15) or (x2.stride(0) * x2.element_size()) % 16:
             return None
         Ns = plan["Ns"]
@@ -1069,13 +1154,22 @@ class SharedActivation:
             tab[i].y = yi.data_ptr()
         st = ops._stream(dev)
         ws = ops.workspace_on(dev, st, plan["ws"])
-        rc = L.lqer_linear_forward_group(tab, plan["n"], x2.data_ptr(), dtc, M, x2.stride(0) if M > 1 else K, plan["a_t"], 1,
-                                         ws.data_ptr(), ws.numel(), st)
+        tail = (dtc, M, x2.stride(0) if M > 1 else K, plan["a_t"], 1, ws.data_ptr(), ws.numel(), st)
+        if armed is None:
+            rc = L.lqer_linear_forward_group(tab, plan["n"], x2.data_ptr(), *tail)
+        elif armed[4] is None:
+            rc = L.lqer_linear_forward_group_normed(tab, plan["n"], x2.data_ptr(), armed[2].data_ptr(), armed[3], *tail)
+        else:
+            rc = L.lqer_linear_forward_group_layernormed(tab, plan["n"], x2.data_ptr(), armed[2].data_ptr(), armed[4].data_ptr(), armed[3], *tail)
         if rc == -2:  # LQER_E_UNSUPPORTED (nothing was launched): this token count / shape stays on the per-member route
             self._dplans[(M, dtc)] = None
             return None
         if rc:
-            check(rc, "lqer_linear_forward_group")
+            check(rc, "lqer_linear_forward_group" if armed is None else "lqer_linear_forward_group_normed / _layernormed")
+        if armed is not None:
+            self.normed_rounds += 1
+            if not isinstance(armed[0], weakref.ref):  # (do not pin the hidden state; a member that comes back with it still finds it armed)
+                self._armed = (weakref.ref(armed[0]),) + armed[1:]
         self._dx, self._dver, self._dys, self._dserved, self._dstream = x, ver, ys, {idx}, st
         return ys[idx]
 

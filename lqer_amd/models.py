@@ -182,7 +182,9 @@ def quantize_model(model: nn.Module, q_config: dict, l_config: Optional[dict], s
     it packs).  fuse_mlp: the activation between the MLP's projections runs inside the down projection's activation-side kernel
     (linear._LinearBase.forward_gated: silu(gate) * up for Llama-like layers, relu for OPT's fc2) instead of as torch launches.  fuse_norm: the RMSNorm in front of
     q/k/v and of gate/up (Llama-like layers with share_inputs) runs inside the group's quantizer launch (csrc/act_normed.hip) from
-    linear._LinearBase.normed_min_m tokens on - the normalised tensor is never written; other norms raise NotImplementedError.
+    linear._LinearBase.normed_min_m tokens on - the normalised tensor is never written - and, up to 8 tokens, inside the group's one-launch
+    decode kernel (linear.SharedActivation.decode_normed / decode_layer_normed, _LinearBase.decode_layer_normed for fc1); other norms raise
+    NotImplementedError.
     fuse_layernorm: the same for an OPT layer's LayerNorms (do_layer_norm_before): self_attn_layer_norm inside the q/k/v group's
     quantizer launch, final_layer_norm inside fc1's, from the layer_normed_min_m tokens of linear.SharedActivation / _LinearBase on."""
     layers, table = _decoder_layers(model)
