@@ -624,6 +624,24 @@ int lqer_linear_decode_layernormed(const lqer_linear_desc_t* desc, const void* h
                                    int b_limbs, const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes,
                                    void* stream);
 
+/* ---- one-launch decode behind a gated MLP: h = act(gate) * up formed inside the decode kernel (additive to ABI 14) -------------------
+ * ONE Linear (a down projection, OPT's fc2) on h = act(gate) * up (up == NULL: h = act(gate)) in ONE launch, up to 8 tokens: gate / up
+ * [M, K] (fp16 or bf16, row strides ld_gate / ld_up elements) stand in x's place, act is LQER_ACT_SILU or LQER_ACT_RELU, and the kernel
+ * forms h by the rule spelled under "gated MLP" - s = round_dt(g / (1 + expf(-g))) in fp32 with the full-precision expf and a true
+ * division (relu: max(g, 0)), h = round_dt(float(s) * float(u)) - in the one function lqer_quantize_act_xa_gated's kernel calls, and
+ * quantizes it where the loaded x went.  h has the bits that entry forms for any input, so an 8-token and a 9-token step agree on h;
+ * y has the bits of lqer_linear_forward's decode route handed that h.  One launch, capturable, bit-stable.  The other operands are
+ * lqer_linear_decode_normed's: a_t the plain [padded rank][padded K] image with a_limbs = 1, workspace >=
+ * lqer_linear_sizes(desc, M).workspace, served where lqer_decode_partials(desc, M) == 1.  h is elementwise, so K has no limit but the
+ * LDS image of all M token rows (150 KiB with the sum buffers): K = 11008 (row pitch 22016 B) is served up to M = 6, K = 16384 up to
+ * M = 4; beyond, the refusal reads "K too long for the LDS image".
+ * LQER_E_INVALID: a null gate, an unknown act, ld_gate or ld_up < K, and what the x entry calls invalid.
+ * LQER_E_UNSUPPORTED, nothing launched, the reason in lqer_last_error() behind "linear_decode_gated:": fp32 tensors; M > 8; K % 16 != 0;
+ * gate, up or their row strides not 16-byte aligned; a compact weight image; everything the decode route refuses. */
+int lqer_linear_decode_gated(const lqer_linear_desc_t* desc, const void* gate, const void* up, int act, int dtype, int64_t M, int64_t ld_gate,
+                             int64_t ld_up, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs,
+                             const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- weights of 5..8 bits (the reference's no-LQER baseline: W8A8 block_fp with one block per row and per token,
  * experiments/pipeline/sweep_baseline_no_lqer.sh:73-76, through LinearFlexible, quantized_layers/linear.py:50-64) ---------------
  * The packed image holds 4-bit codes, so a mantissa m of up to 8 bits (|m| <= 127) travels as three signed base-8 digits,

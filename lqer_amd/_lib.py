@@ -146,6 +146,7 @@ SIGNATURES = {
     "lqer_linear_forward_group_layernormed": (_i, [C.POINTER(GroupMember), _i, _vp, _vp, _vp, C.c_float, _i, _i64, _i64, _vp, _i, _vp, _sz, _vp]),
     "lqer_linear_decode_normed": (_i, [_dp, _vp, _vp, C.c_float, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
     "lqer_linear_decode_layernormed": (_i, [_dp, _vp, _vp, _vp, C.c_float, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "lqer_linear_decode_gated": (_i, [_dp, _vp, _vp, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
     "lqer_i8_prepare": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),
     "lqer_unpack_weight_i8": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "lqer_unpack_weight_i8_fmt": (_i, [_vp, _i64, _i64, _qp, _vp, _vp]),

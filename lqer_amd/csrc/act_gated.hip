@@ -29,15 +29,7 @@
 namespace lqer {
 namespace ag {
 
-using namespace arow;  // the work split and the pieces shared with act_normed.hip
-
-// one element of h (act: wave-uniform)
-template <int DT, bool UP>
-__device__ __forceinline__ float gated(float g, float u, int act) {
-  const float s = act == LQER_ACT_RELU ? (g > 0.f ? g : 0.f) : round_dt<DT>(g / (1.0f + expf(-g)));
-  if constexpr (UP) return round_dt<DT>(s * u);
-  else return s;
-}
+using namespace arow;  // the work split and the pieces shared with act_normed.hip; gated(): one element of h (act: wave-uniform)
 
 template <int DT, int RT, bool UP>
 __global__ __launch_bounds__(512) void k_act_gated(const void* __restrict__ gate, const void* __restrict__ up, int act, int64_t M, int64_t ldg,

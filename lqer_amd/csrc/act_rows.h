@@ -27,6 +27,16 @@ __device__ __forceinline__ float round_dt(float v) {
   else return __uint_as_float((uint32_t)f32_to_bf16_rne(v) << 16);
 }
 
+// ---- the gated MLP's rule for one element of h (include/lqer_hip.h "gated MLP"), written once for act_gated.hip and the GATE
+// instantiations of decode1_kernel.h: s = round_dt(g / (1 + exp(-g))) with the full-precision expf and a true division (relu: max(g, 0),
+// exact), h = round_dt(float(s) * float(u)) - the product of two dt values is exact in fp32 - or, without up, h = s
+template <int DT, bool UP>
+__device__ __forceinline__ float gated(float g, float u, int act) {
+  const float s = act == LQER_ACT_RELU ? (g > 0.f ? g : 0.f) : round_dt<DT>(g / (1.0f + expf(-g)));
+  if constexpr (UP) return round_dt<DT>(s * u);
+  else return s;
+}
+
 // ---- the norms in front of the quantizer (act_normed.hip; the NORM instantiations of decode1.hip): the rules of include/lqer_hip.h,
 // "fused RMSNorm" and "fused LayerNorm", each written once
 // RMSNorm's elementwise rule: HF LlamaRMSNorm's two roundings in dt (the product of two dt values is exact in fp32)

@@ -879,12 +879,13 @@ static bool decode1_takes(const lqer_linear_desc_t* d, int64_t M, int dtype, con
 // ... and its launch for the Linears `mem`, which are handed the same tokens: `shared` = the arguments of (d, M) that do not depend on
 // the Linear (gemm_shape_args), A_out and the B_out form are d's
 static int decode1_call(const GemmArgs& shared, const lqer_linear_desc_t* d, int dtype, const void* x, int64_t ldx, const void* a_t,
-                        const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, void* stream, const DecodeNorm* nz = nullptr) {
+                        const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, void* stream, const DecodeNorm* nz = nullptr,
+                        const DecodeGate* gz = nullptr) {
   GemmArgs g = shared;
   g.aout = make_qp(d->a_out_fmt);
   const int bout = d->b_out_fmt.kind == LQER_Q_PASSTHROUGH ? 0 : 1;  // (decode_partials_ok: pass-through or blocks of 16)
   return decode1_dispatch(g, dtype, x, ldx, d->in_features, make_qp(d->x_fmt), (const bf16_t*)a_t, bout, mem, nmem, scratch, scratch_bytes,
-                          (hipStream_t)stream, nz);
+                          (hipStream_t)stream, nz, gz);
 }
 
 // what lqer_linear_forward / lqer_linear_forward_narrow are handed besides the descriptor and the weight image
@@ -1359,6 +1360,47 @@ int lqer_linear_decode_layernormed(const lqer_linear_desc_t* d, const void* h, c
                                    const float* bias_q, void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
   return linear_decode_normed_impl("linear_decode_layernormed", DecodeNorm{NORM_LAYER, nw, nb, eps}, d, h, dtype, M, ld_h, w_packed, a_t, b_t, a_limbs,
                                    b_limbs, bias_q, y, ldy, workspace, workspace_bytes, stream);
+}
+
+// One Linear on h = act(gate) * up in ONE launch (include/lqer_hip.h "one-launch decode behind a gated MLP"): lqer_linear_forward's decode
+// route with h formed inside the kernel.  No limit on K but the LDS image's, which decode1_dispatch knows.
+int lqer_linear_decode_gated(const lqer_linear_desc_t* d, const void* gate, const void* up, int act, int dtype, int64_t M, int64_t ld_gate,
+                             int64_t ld_up, const void* w_packed, const void* a_t, const void* b_t, int a_limbs, int b_limbs, const float* bias_q,
+                             void* y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* const who = "linear_decode_gated";
+  if (!d || M < 0) return fail(LQER_E_INVALID, "%s: %s", who, d ? "negative token count" : "null descriptor");
+  const int64_t K = d->in_features;
+  if (!gate) return fail(LQER_E_INVALID, "%s: null gate tensor", who);
+  if (act != LQER_ACT_SILU && act != LQER_ACT_RELU) return fail(LQER_E_INVALID, "%s: unknown activation %d (LQER_ACT_SILU, LQER_ACT_RELU)", who, act);
+  if (ld_gate < K || (up && ld_up < K))
+    return fail(LQER_E_INVALID, "%s: row stride %lld of %s < in_features %lld", who, (long long)(ld_gate < K ? ld_gate : ld_up), ld_gate < K ? "gate" : "up",
+                (long long)K);
+  if (dtype == LQER_F32)
+    return fail(LQER_E_UNSUPPORTED, "%s: fp32 gate / up (the two roundings of h are those of a 16-bit eager model: fp16 or bf16)", who);
+  if (dtype != LQER_F16 && dtype != LQER_BF16) return fail(LQER_E_INVALID, "%s: unknown dtype %d", who, dtype);
+  if (M > d1::MAXM) return fail(LQER_E_UNSUPPORTED, "%s: M = %lld: the one-launch decode kernel takes up to %d tokens", who, (long long)M, d1::MAXM);
+  if (K % 16 != 0) return fail(LQER_E_UNSUPPORTED, "%s: in_features %lld must be a multiple of 16", who, (long long)K);
+  if (((uintptr_t)gate & 15) || (ld_gate * 2) % 16 || ((uintptr_t)up & 15) || (up && (ld_up * 2) % 16))
+    return fail(LQER_E_UNSUPPORTED, "%s: gate, up and their row strides must be 16-byte aligned", who);
+  if (!w_packed || !a_t || !b_t || !y || ldy < d->out_features || (d->has_bias && !bias_q))
+    return fail(LQER_E_INVALID, "%s: null weight image, A^T / B^T image, bias or y, or ldy %lld < out_features %d", who, (long long)ldy, d->out_features);
+  lqer_linear_sizes_t sz;
+  Carving cv;  // (lqer_linear_forward's own)
+  int rc = linear_sizes_carved(d, M, &sz, &cv);
+  if (rc) return rc;
+  if (workspace_bytes < cv.total || (!workspace && cv.total))
+    return fail(LQER_E_WORKSPACE, "%s: workspace %zu B < %zu B needed for M=%lld", who, workspace_bytes, cv.total, (long long)M);
+  if (M == 0) return LQER_OK;
+  if (!decode1_takes(d, M, dtype, gate, ld_gate, a_limbs, b_limbs))
+    return fail(LQER_E_UNSUPPORTED, "%s: outside the one-launch decode route (lqer_decode_partials(desc, M) == 1, the plain A^T image with a_limbs = 1, "
+                "1..3 limbs of B): compute h and call lqer_linear_forward", who);
+  const Planned pl = plan_for(d, M, dtype, b_limbs);
+  if (pl.rc) return fail(pl.rc, "%s", pl.p.msg);
+  const DecodeMember one = member_of(d, w_packed, b_t, b_limbs, bias_q, y, ldy);
+  const DecodeGate gz{up, up ? ld_up : 0, act};
+  rc = decode1_call(pl.g, d, dtype, gate, ld_gate, a_t, &one, 1, (unsigned char*)workspace + cv.scratch, cv.side_bytes, stream, nullptr, &gz);
+  if (rc == LQER_E_UNSUPPORTED) set_error("%s: outside the one-launch decode kernel: %s", who, decode1_last_refusal());
+  return rc;
 }
 
 int lqer_desc_limbs(const lqer_linear_desc_t* d, int* act, int* xa) {

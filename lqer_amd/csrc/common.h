@@ -923,9 +923,15 @@ struct DecodeNorm {  // the norm the kernel forms itself from the raw hidden sta
   const void *nw, *nb;
   float eps;
 };
+struct DecodeGate {  // the gated MLP's h = act(gate) * up, formed by the kernel itself: `gate` is handed in x's place (up == nullptr: h = act(gate))
+  const void* up;
+  int64_t ld_up;
+  int act;  // LQER_ACT_SILU, LQER_ACT_RELU
+};
 // (g.w_narrow != 0: a single Linear whose wp is the compact image - groups read standard images only)
 int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, const QP& qx, const bf16_t* a_t, int bout,
-                     const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st, const DecodeNorm* nz = nullptr);
+                     const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st, const DecodeNorm* nz = nullptr,
+                     const DecodeGate* gz = nullptr);
 
 // pack.hip: standard image <-> compact image of a 2- / 3-bit block_fp weight (w_narrow.h), over the whole padded image; E = exponent
 // bytes per row of a compact panel.  The host twins run the same per-row functions in plain loops (no HIP call); narrow_host returns

@@ -35,8 +35,11 @@ size_t decode1_scratch_bytes(int64_t Kp, int rp) { return (size_t)((Kp + d1::SLA
 // concatenation of their A^T images along the rank.  Returns LQER_E_UNSUPPORTED when the shape is outside.
 // nz != nullptr: x is the raw hidden state h, and the kernel forms the norm of nz->norm (NORM_RMS, NORM_LAYER) itself - api.hip has
 // checked the norm's operands (dtype, K, alignment); the NORM instantiations take standard images only.
+// gz != nullptr: x is the gate projection's output, and the kernel forms h = act(x) * gz->up itself (one Linear, standard image; api.hip
+// has checked act, the strides and the alignment).  No limit on K but the LDS image's.
 int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, const QP& qx, const bf16_t* a_t, int bout,
-                     const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st, const DecodeNorm* nz) {
+                     const DecodeMember* mem, int nmem, void* scratch, size_t scratch_bytes, hipStream_t st, const DecodeNorm* nz,
+                     const DecodeGate* gz) {
 #ifdef LQER_HOST_TIMING
   timespec ht0; clock_gettime(CLOCK_MONOTONIC, &ht0);
 #endif
@@ -50,6 +53,8 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
   if (w_img && (nmem != 1 || (w_img != 2 && w_img != 3))) return no("a compact weight image in a group, or of a width other than 2 or 3");
   if (nz && (w_img || (dtype != LQER_F16 && dtype != LQER_BF16) || K > arow::ROWS * arow::SLAB * 2))
     return no("the norm is formed for fp16 / bf16 tensors, standard weight images and in_features <= 8192");
+  if (gz && (nz || nmem != 1 || w_img || (dtype != LQER_F16 && dtype != LQER_BF16)))
+    return no("the gated MLP's h is formed for one Linear, fp16 / bf16 tensors and the standard weight image (a compact weight image: compute h)");
   d1::Args<d1::MAXMEM> a;
   int rp_all = 0, blocks = 0;
   for (int i = 0; i < nmem; ++i) {
@@ -115,6 +120,12 @@ int decode1_dispatch(GemmArgs g, int dtype, const void* x, int64_t ldx, int K, c
     (d1::Args<d1::MAXMEM>&)an = a, (d1::Args<1>&)an1 = a1;
     an.nz = an1.nz = d1::NormTail{nz->nw, nz->nb, nz->eps};
     return decode1_normed_launch(dtype, bout, nz->norm, grid, (int)lds, st, an, an1, nmem > 1);
+  }
+  if (gz) {  // the GATE instantiations (decode1_gated.hip): the single Linear's block with up behind it
+    d1::ArgsG ag;
+    (d1::Args<1>&)ag = a1;
+    ag.gz = d1::GateTail{gz->up, gz->ld_up};
+    return decode1_gated_launch(dtype, bout, gz->act, grid, (int)lds, st, ag);
   }
   const int rc = with_dtype(dtype, [&](auto dt) {
     constexpr int DT = decltype(dt)::value, LIMIT = 150 * 1024;

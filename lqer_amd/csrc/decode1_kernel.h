@@ -28,7 +28,7 @@
 // after QD1_SPIN sweeps (it has, in practice, long before a consumer asks - producers are the first blocks of the grid and
 // finish in ~2 us) the consumer workgroup computes every partial tile itself with the producers' own routine (same bits)
 // and goes on: every wave reaches the end of the kernel whatever the dispatch order.
-// (the kernels of decode1.hip and decode1_normed.hip: the NORM instantiations are compiled in a translation unit of their own - beside them
+// (the kernels of decode1.hip, decode1_normed.hip and decode1_gated.hip: the NORM and the GATE instantiations are compiled in translation units of their own - beside them
 // in ONE module the optimizer emits the standard kernels with another register numbering and scalar order)
 #pragma once
 #include <type_traits>
@@ -131,6 +131,15 @@ template <int NM>
 struct ArgsN : Args<NM> {
   NormTail nz;
 };
+// GATE instantiations (lqer_linear_decode_gated): the tokens `x` are the gate projection's output g (ldx its row stride), and the kernel
+// forms h = act(g) * up itself, by act_rows.h's gated().  up and its stride ride behind the block above, as the norm's operands do.
+struct GateTail {
+  const void* up;  // [M, K], the dtype of gate
+  int64_t ld_up;
+};
+struct ArgsG : Args<1> {
+  GateTail gz;
+};
 constexpr int STAT_BYTES = MAXM * 2 * 4;  // the rows' rstd and mean: behind the flag, where the fall-back's produce() leaves them alone
 static_assert(NW == arow::WAVES && MAXM == arow::ROWS, "act_rows.h's row reduction: 8 waves over 8 token rows");
 
@@ -165,6 +174,21 @@ template <int NORM>
 struct NormKind {
   static constexpr bool on = NORM != 0, layer = NORM == 2;
 };
+// GATE: 0 none; 1 silu(g) * up, 2 silu(g), 3 relu(g) * up, 4 relu(g) - the activation is a compile-time constant (relu carries no expf)
+template <int GATE>
+struct GateKind {
+  static constexpr bool on = GATE != 0, up = (GATE & 1) != 0;
+  static constexpr int act = GATE > 2 ? LQER_ACT_RELU : LQER_ACT_SILU;
+};
+// v: 16 elements of gate -> h (ru: the 32 bytes of up at the same place)
+template <int DT, int GATE>
+__device__ __forceinline__ void gate16(float (&v)[16], const Raw16<DT>& ru) {
+  using GK = GateKind<GATE>;
+  float uv[16] = {};
+  if constexpr (GK::up) raw16_to_f32<DT>(ru, uv);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) v[i] = arow::gated<DT, GK::up>(v[i], uv[i], GK::act);
+}
 // the rows' statistics [rstd x MAXM][mean x MAXM]: the LDS words behind the workgroup's flag
 __device__ __forceinline__ float* stat_of(volatile uint32_t* miss_flag) { return (float*)((unsigned char*)miss_flag + FLAG_BYTES); }
 // chunk(si, j): the lane's 16 bytes of row j in its wave's slab number si (act_rows.h row_sum).  Leaves rstd / mean of row l & 7 in lane l
@@ -197,11 +221,22 @@ __device__ __forceinline__ void norm_stats(float* part, float* stat, int wave, i
 //   * the norm weight (and bias) of a thread's first blocks are requested before the reduction, so that their round trip (behind the
 //     first weight panels: loads return in order) passes under its barriers;
 //   * the consumers' fall-back produce(p) reads rstd / mean from LDS again: all three quantize identical x bits.
+// GATE (GateKind): a.x holds the gate projection's output g, gz.up the up projection's, and x = h = act(g) * up is formed HERE by
+// act_rows.h's gated(), the function act_gated.hip calls: the same h bits for any input, so a step of 8 tokens and one of 9 agree.  h is
+// elementwise - no statistics, no hand-off, no K limit but the LDS image's:
+//   * a consumer requests its lanes' blocks of g AND of up where it requested x (before the first weight panels), forms h in registers
+//     and hands it to the quantizer where the loaded x went.  Two 32-byte inputs stand behind a 32-byte image block, so nothing can be
+//     parked in the image's slots: with up, a pass holds XB = 2 blocks per thread (2 x 2 x 8 registers in flight, what x's four cost);
+//   * produce(p) loads its slab of g and up and forms h before it quantizes - in a producer and in the consumers' fall-back alike, which
+//     re-reads both from L2: identical bits.
+// Every consumer workgroup evaluates expf and a division on all M x K elements (the price of waiting for nobody).
 // (the body of all kernels below, inlined: the standard image's kernel keeps its name and its three template arguments)
-template <int DT, int BOUT, bool GROUP, int W, int NORM = 0>
-__device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a, const NormTail& nz = NormTail{}) {
+template <int DT, int BOUT, bool GROUP, int W, int NORM = 0, int GATE = 0>
+__device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a, const NormTail& nz = NormTail{}, const GateTail& gz = GateTail{}) {
   using NK = NormKind<NORM>;  // (compile-time only: the NORM = 0 instantiations hold no statement that the parent's did not)
+  using GK = GateKind<GATE>;  // (likewise)
   static_assert(!NK::on || (DT != LQER_F32 && W == 0), "the norms: 16-bit tensors, standard weight image");
+  static_assert(!GK::on || (DT != LQER_F32 && W == 0 && !GROUP && !NK::on), "the gate: 16-bit tensors, one Linear, standard weight image");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const auto& g = a;  // (the shared formats and shapes: M, Kp, aout, bout)
   int tid = threadIdx.x;  // (tid, l15, lq: not const - the NORM instantiations re-derive them inside produce())
@@ -239,7 +274,7 @@ __device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a, 
     constexpr int PW = 4, PS = SLAB_K / 32 / PW;  // multiplying waves, k-slices of 32 per wave
     // (NORM: the thread's indices pass through an empty asm, so that what hangs on them is derived again in every call - hoisted out of
     // the fall-back's loop it costs the fp16 instantiations a spill; the values do not change)
-    if constexpr (NK::on) asm volatile("" : "+v"(l15), "+v"(lq), "+v"(tid));
+    if constexpr (NK::on || GK::on) asm volatile("" : "+v"(l15), "+v"(lq), "+v"(tid));
     bf16x8 af[PS][MAXNT];
     const int64_t kw = (int64_t)p * SLAB_K + 32 * PS * wave;
     auto load_af = [&](int t0) {
@@ -269,6 +304,11 @@ __device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a, 
           load_kvec<DT>(nz.nw, (int)k0, rw);
           if constexpr (NK::layer) load_kvec<DT>(nz.nb, (int)k0, rb);
           norm16<DT, NK::layer>(v, st[row], st[MAXM + row], rw, rb);
+        }
+        if constexpr (GK::on) {
+          Raw16<DT> ru = {};
+          if constexpr (GK::up) load_raw16<DT>(gz.up, row * gz.ld_up + k0, ru);
+          gate16<DT, GATE>(v, ru);
         }
         quant16_bf16<DT != LQER_F16>(v, a.qx, w);
       }
@@ -405,14 +445,15 @@ __device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a, 
   // instead of one per block.  Always loaded, from a clamped in-range offset: a load under a branch would make the compiler
   // wait for everything in flight at its first use; threads without such a block ignore the values.
   const int segs = Kp / 16;
-  constexpr int XB = DT == LQER_F32 ? 2 : 4;  // (8 registers per 16-bit block, 16 per fp32 block)
-  Raw16<DT> rb[XB];
+  constexpr int XB = DT == LQER_F32 || GK::up ? 2 : 4;  // (8 registers per 16-bit block, 16 per fp32 block or per block of gate AND up)
+  Raw16<DT> rb[XB], ru[GK::up ? XB : 1];
   auto request_x = [&](int b0) {
 #pragma unroll
     for (int u = 0; u < XB; ++u) {
       const int b = b0 + 64 * NW * u;
       const int r = b / segs, seg = b - r * segs;
       load_raw16<DT>(a.x, b < M * segs && seg * 16 < a.K ? r * a.ldx + seg * 16 : 0, rb[u]);
+      if constexpr (GK::up) load_raw16<DT>(gz.up, b < M * segs && seg * 16 < a.K ? r * gz.ld_up + seg * 16 : 0, ru[u]);
     }
   };
   request_x(tid);
@@ -499,8 +540,10 @@ __device__ __forceinline__ void decode1_body(const Args<GROUP ? MAXMEM : 1>& a, 
           if (seg * 16 < a.K) {
             float v[16];
             raw16_to_f32<DT>(rb[u], v);
+            if constexpr (GK::on) gate16<DT, GATE>(v, ru[GK::up ? u : 0]);
             quant16_bf16<DT != LQER_F16>(v, a.qx, w);
           }
+          if constexpr (GK::on) __builtin_amdgcn_sched_barrier(0);  // (blocks are not interleaved: each would keep its temporaries alive beside the weight panels)
           if (u == 0 && tid == 0) D1_STAMP_AFTER(6, w[0]);
           *(uint4*)(xs + img_off(r, 2 * seg, xpitch)) = make_uint4(w[0], w[1], w[2], w[3]);
           *(uint4*)(xs + img_off(r, 2 * seg + 1, xpitch)) = make_uint4(w[4], w[5], w[6], w[7]);
@@ -769,6 +812,11 @@ template <int DT, int BOUT, bool GROUP, int NORM>
 __global__ __launch_bounds__(64 * NW, 4) void k_decode1_normed(ArgsN<GROUP ? MAXMEM : 1> a) {
   decode1_body<DT, BOUT, GROUP, 0, NORM>(a, a.nz);
 }
+// ... one Linear on h = act(gate) * up (GateKind; fp16 / bf16, standard image): a.x holds gate
+template <int DT, int BOUT, int GATE>
+__global__ __launch_bounds__(64 * NW, 4) void k_decode1_gated(ArgsG a) {
+  decode1_body<DT, BOUT, false, 0, 0, GATE>(a, NormTail{}, a.gz);
+}
 // ... a single Linear whose weight is the compact image of W = 2 or 3 bits
 template <int DT, int BOUT, int W>
 __global__ __launch_bounds__(64 * NW, 4) void k_decode1_narrow(Args<1> a) {
@@ -780,5 +828,7 @@ __global__ __launch_bounds__(64 * NW, 4) void k_decode1_narrow(Args<1> a) {
 // decode1_normed.hip: the launch of k_decode1_normed for the blocks decode1_dispatch has filled (norm: NORM_RMS / NORM_LAYER)
 int decode1_normed_launch(int dtype, int bout, int norm, unsigned grid, int lds, hipStream_t st, const d1::ArgsN<d1::MAXMEM>& group,
                           const d1::ArgsN<1>& one, bool is_group);
+// decode1_gated.hip: the launch of k_decode1_gated (act: LQER_ACT_SILU / LQER_ACT_RELU; one.gz.up may be null)
+int decode1_gated_launch(int dtype, int bout, int act, unsigned grid, int lds, hipStream_t st, const d1::ArgsG& one);
 
 }  // namespace lqer

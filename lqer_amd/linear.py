@@ -78,6 +78,7 @@ class _LinearBase(nn.Linear):
         self._armed = None         # _arm(h, ...): a fused LayerNorm's raw hidden state for the next forward (arm_layer_normed)
         self.layer_normed_rounds = 0  # forwards that ran lqer_linear_forward_layernormed / lqer_linear_decode_layernormed
         self.decode_normed_rounds = 0  # forwards that ran lqer_linear_decode_normed
+        self.decode_gated_rounds = 0  # forwards that ran lqer_linear_decode_gated
         self._fw_cache = {}        # token count -> (descriptor, workspace bytes)
         self._x_f16 = False        # pass-through fp16 activations on the fp16 MFMA route (decided when the images are built)
         self.a16_native = True     # False: keep pass-through fp16 activations on the bf16-limb route
@@ -645,7 +646,9 @@ class _LinearBase(nn.Linear):
         """This Linear on h = act(gate) * up (up = None: h = act(gate)) - Llama / Mistral's down_proj(silu(gate_proj(x)) * up_proj(x)),
         OPT's fc2(relu(fc1(x))) - with h formed inside the activation-side kernel (csrc/act_gated.hip through lqer_linear_forward_gated:
         two launches, h never written) where that kernel applies: fp16 / bf16 tensors, block-16 MXINT x_quantizer, an A of one bf16 limb
-        with padded rank 16 / 32 / 64, the standard weight image.  Elsewhere h is computed with torch and handed to forward().  `gate`
+        with padded rank 16 / 32 / 64, the standard weight image.  Up to decode_gated_max_m tokens, where decode_gated is set and the
+        one-launch decode route serves the call, the whole forward is ONE launch that forms h itself (csrc/decode1_kernel.h through
+        lqer_linear_decode_gated: the same h bits).  Elsewhere h is computed with torch and handed to forward().  `gate`
         and `up` may be the two halves of one [..., 2 K] tensor.  The result is forward(F.silu(gate) * up) up to the last bit of silu on
         elements that sit on a rounding boundary of the dtype, and the side product's fp32 summation order."""
         code = _GATED_ACTS.get(act)
@@ -673,17 +676,14 @@ class _LinearBase(nn.Linear):
             self._pack()
         p, K, N = self._packed, self.in_features, self.out_features
         M = gate.numel() // K
+        if 0 < M <= self.decode_gated_max_m and self.decode_gated:
+            y = self._forward_decode_gated(gate, up, code)  # ONE launch; refused or switched off: the route of before
+            if y is not None:
+                return y
         if ("a_t_b16" not in p or self._weight_image == "narrow" or ops.w_limbs(self._fmt["w"]) != 1 or K % 16 or M < self.gated_min_m):
             return None
-
-        def rows(t):  # [M, K] with unit column stride, 16-byte aligned rows
-            t = t.reshape(-1, K)
-            if t.stride(-1) != 1 or t.data_ptr() % 16 or (M > 1 and (t.stride(0) < K or t.stride(0) % 8)):
-                t = t.contiguous()
-            return t
-
-        g2 = rows(gate)
-        u2 = None if up is None else rows(up)
+        g2 = self._rows16(gate, K)
+        u2 = None if up is None else self._rows16(up, K)
         y = torch.empty(M, N, dtype=gate.dtype, device=gate.device)
         key = ("gated", M, gate.dtype, self.tuning)
         ent = self._fw_cache.get(key)
@@ -702,6 +702,61 @@ class _LinearBase(nn.Linear):
                                                   y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
         if rc:
             check(rc, "lqer_linear_forward_gated")
+        return y.reshape(*gate.shape[:-1], N)
+
+    @staticmethod
+    def _rows16(t: torch.Tensor, K: int) -> torch.Tensor:
+        """[M, K] with unit column stride and 16-byte aligned rows (a copy only where t is not that already)"""
+        t = t.reshape(-1, K)
+        if t.stride(-1) != 1 or t.data_ptr() % 16 or (t.shape[0] > 1 and (t.stride(0) < K or t.stride(0) % 8)):
+            t = t.contiguous()
+        return t
+
+    # -- the decode step behind a gated MLP (M <= 8) --------------------------------------------
+    # Does forward_gated take the one-launch entry (lqer_linear_decode_gated: csrc/decode1_kernel.h forms h itself) up to
+    # decode_gated_max_m tokens?  Set from tools/gated_mlp_bench.py --decode (profiles/gated_decode.json; DESIGN.md "One-launch decode
+    # behind a gated MLP"): on only at sizes where the one launch is faster than torch's activation + forward() beyond the spread of both.
+    # Llama-7B down projection (11008 -> 4096, silu * up, 3 launches -> 1): 0.74x / 0.89x the time at M = 1 / 2, but 1.15x / 1.35x at
+    # M = 4 / 6 - every consumer workgroup evaluates expf and a division on all M x K elements, which stops passing under the weight stream.
+    # OPT-6.7B's fc2 (16384 -> 4096, relu, bias, 2 launches -> 1): 0.86x / 0.91x at M = 1 / 4 (no expf), under the same threshold.
+    # Off, or above the threshold: exactly the route of before.
+    decode_gated = True
+    decode_gated_max_m = 2
+
+    def _forward_decode_gated(self, gate: torch.Tensor, up: Optional[torch.Tensor], code: int) -> Optional[torch.Tensor]:
+        """Up to 8 tokens: this Linear on act(gate) * up in ONE launch, or None where the entry does not serve the call (nothing launched)."""
+        p = self._packed
+        K, N = self.in_features, self.out_features
+        M = gate.numel() // K
+        if (self.rank <= 0 or K % 16 or self._weight_image == "narrow" or self._x_i8 or self._x_f16 or int(p.get("a_limbs", 0)) != 1
+                or p.get("b_t") is None):
+            return None
+        g2 = self._rows16(gate, K)
+        u2 = None if up is None else self._rows16(up, K)
+        key = ("decode_gated", M, gate.dtype, self.tuning)
+        ent = self._fw_cache.get(key)
+        if ent is None:
+            desc = self._desc(plain=True)  # (decode sizes never take the int8 tile kernel)
+            if len(self._fw_cache) > 64:
+                self._fw_cache = {}
+            served = _lib.lib().lqer_decode_partials(C.byref(desc), M) == 1
+            ent = self._fw_cache[key] = (desc, ops.linear_sizes(desc, M).workspace, ops.dtype_code(g2), served,
+                                         (p["w"].data_ptr(), p["a_t"].data_ptr(), p["b_t"].data_ptr(), 1, p.get("b_limbs", 0), ops._ptr(p.get("bias"))))
+        desc, ws_bytes, dt, served, consts = ent
+        if not served:
+            return None
+        y = torch.empty(M, N, dtype=gate.dtype, device=gate.device)
+        st = ops._stream(gate.device)
+        ws = ops.workspace_on(gate.device, st, ws_bytes)
+        rc = _lib.lib().lqer_linear_decode_gated(C.byref(desc), g2.data_ptr(), None if u2 is None else u2.data_ptr(), code, dt, M,
+                                                 g2.stride(0) if M > 1 else K, K if (u2 is None or M == 1) else u2.stride(0), *consts,
+                                                 y.data_ptr(), N, ws.data_ptr(), ws.numel(), st)
+        if rc == -2:  # LQER_E_UNSUPPORTED (nothing was launched)
+            self._fw_cache[key] = (desc, ws_bytes, dt, False, consts)
+            return None
+        if rc:
+            check(rc, "lqer_linear_decode_gated")
+        self.decode_gated_rounds += 1
         return y.reshape(*gate.shape[:-1], N)
 
     # -- fused RMSNorm ------------------------------------------------------------------------

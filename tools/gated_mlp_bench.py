@@ -14,7 +14,16 @@ two torch kernels + the forward's - one at M <= 8, two above; the fused leg: two
 `slower_beyond_spread` marks a size where leg B's median lies above leg A's slowest round.  `act_kernel` is lqer_quantize_act_xa_gated
 alone through the C ABI on the same rotation: its time, the bytes it must move (g and u read, the image written; the A^T fragments are
 re-read by every workgroup from cache and not counted) and that rate as a fraction of the HBM peak (benchlib.workloads.HBM_PEAK_GBS).
-Not part of bench.py.  Needs a GPU: there is no fall-back."""
+Not part of bench.py.  Needs a GPU: there is no fall-back.
+
+--decode: the decode step (profiles/gated_decode.json).  Leg A = torch's activation (silu + mul: two launches; relu: one) + forward(), whose
+decode route is ONE launch: today's default at these sizes; leg B = forward_gated with decode_gated switched on (lqer_linear_decode_gated:
+ONE launch, h formed inside csrc/decode1_kernel.h).  Cases: the Llama-7B down projection (11008 -> 4096, rank 32, silu * up) at M = 1, 2, 4,
+6 and OPT-6.7B's fc2 (16384 -> 4096, rank 32, relu, with bias) at M = 1, 4 - the largest M are the last whose LDS image fits.  A launch
+streams ~25 MB of weights in ~10 us, so the default --rotate is 16 copies (past the Infinity Cache) and a round times 64 x rotate calls.
+`fused_slower` marks a row where leg B's FASTEST round lies above leg A's median, `faster_beyond_spread` one where leg B's slowest round
+lies below leg A's fastest: `decode_default` holds, per case, the largest M up to which every row is faster beyond the spread (0: none) -
+LinearFlexibleLqer.decode_gated / decode_gated_max_m follow it."""
 import argparse
 import copy
 import ctypes as C
@@ -61,13 +70,83 @@ def _bytes(M, mod):
     return {"torch_silu_mul": 6 * M * K * 2 + common, "forward_gated": 2 * M * K * 2 + common}
 
 
+DECODE_CASES = {"llama7b_down": dict(K=11008, N=4096, act="silu", up=True, bias=False, q="MXINT_Q", tokens=(1, 2, 4, 6)),
+                "opt6.7b_fc2": dict(K=16384, N=4096, act="relu", up=False, bias=True, q="OPT_Q", tokens=(1, 4))}
+
+
+def _decode(a):
+    import benchlib.workloads as WL
+    import lqer_amd
+    from lqer_amd import ops
+
+    st = ops._stream(torch.device(DEV))
+    e0, e1 = HipEvent(EV_FLAGS), HipEvent(EV_FLAGS)
+    rows, default = [], {}
+    for name, c in DECODE_CASES.items():
+        Kc, Nc = c["K"], c["N"]
+        W, A, B = make_weights(torch.Generator().manual_seed(11), Kc, Nc, RANK)
+        mod = lqer_amd.LinearFlexibleLqer(Kc, Nc, bias=c["bias"], q_config=getattr(WL, c["q"]), l_config={"rank": RANK})
+        sd = {"weight": W, "A": A, "B": B}
+        if c["bias"]:
+            sd["bias"] = 0.1 * torch.randn(Nc, generator=torch.Generator().manual_seed(12))
+        mod.load_state_dict(sd)
+        mod = mod.to(DEV).half()
+        mod.pack()
+        mods = [mod] + [copy.deepcopy(mod) for _ in range(a.rotate - 1)]
+        for m in mods:
+            m.decode_gated, m.decode_gated_max_m = True, 8  # (leg B is the new entry at every size, whatever the defaults keep)
+        act_t = torch.nn.functional.silu if c["act"] == "silu" else torch.relu
+        for M in c["tokens"]:
+            gen = torch.Generator().manual_seed(M)
+            gs = [(4 * torch.randn(M, Kc, generator=gen)).half().to(DEV) for _ in range(a.rotate)]
+            us = [torch.randn(M, Kc, generator=gen).half().to(DEV) if c["up"] else None for _ in range(a.rotate)]
+            legs = {"torch_act": [(lambda m=m, g=g, u=u: m(act_t(g) if u is None else act_t(g) * u)) for m, g, u in zip(mods, gs, us)],
+                    "decode_gated": [(lambda m=m, g=g, u=u: m.forward_gated(g, u, c["act"])) for m, g, u in zip(mods, gs, us)]}
+            n0 = mods[0].decode_gated_rounds
+            ya, yb = legs["torch_act"][0](), legs["decode_gated"][0]()
+            assert mods[0].decode_gated_rounds == n0 + 1, "leg B did not take lqer_linear_decode_gated"
+            err = float((ya.float() - yb.float()).norm() / ya.float().norm())
+            times = {k: [] for k in legs}
+            for r in range(2 + a.rounds):
+                for k, calls in legs.items():  # (the legs alternate round by round)
+                    t = _round(calls * 64, st, e0, e1)
+                    if r >= 2:
+                        times[k].append(t)
+            sa, sb = _stats(times["torch_act"]), _stats(times["decode_gated"])
+            row = {"case": name, "M": M, "K": Kc, "N": Nc, "rank": RANK, "act": c["act"], "up": c["up"], "bias": c["bias"],
+                   "torch_act": dict(sa, launches=(2 if c["up"] else 1) + 1), "decode_gated": dict(sb, launches=1),
+                   "time_ratio": round(sb["ms"] / sa["ms"], 4), "fused_slower": bool(sb["min_ms"] > sa["ms"]),
+                   "faster_beyond_spread": bool(sb["max_ms"] < sa["min_ms"]), "rel_l2_between_legs": err}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del gs, us, legs
+        ok = [M for M in c["tokens"] if all(r["faster_beyond_spread"] for r in rows if r["case"] == name and r["M"] <= M)]
+        default[name] = max(ok) if ok else 0
+        del mods, mod
+        torch.cuda.empty_cache()
+    doc = {"tool": "tools/gated_mlp_bench.py --decode", "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "rotate": a.rotate,
+           "note": "per-call times: one HIP event pair around 64 x `rotate` calls of one leg, each on another copy of (g, u) and of the module; "
+                   "median / min / max over the rounds, the legs alternating; Python and ctypes included on both legs; launches by construction",
+           "decode_default": default, "rows": rows}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(f"wrote {a.out}: the one-launch entry is faster beyond the spread up to M = {default}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--rotate", type=int, default=12)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gated_mlp.json"))
+    ap.add_argument("--rotate", type=int, default=None)
+    ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.rotate = a.rotate or (16 if a.decode else 12)
+    a.out = a.out or os.path.join(ROOT, "profiles", "gated_decode.json" if a.decode else "gated_mlp.json")
     assert torch.cuda.is_available(), "needs a GPU"
+    if a.decode:
+        return _decode(a)
     import lqer_amd
     from lqer_amd import _lib, ops
 
